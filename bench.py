@@ -12,7 +12,11 @@ The schedule is the LIBRARY's: a step is ONE call, rmcv_pipeline_submit (include
 kernels alternating over two HIP streams, the per-frame kernels on four higher-priority streams, chained by events inside
 librmcv_hip.so.  tools/pipeline_bench.c drives the same calls from C; this file adds what the driver's contract asks for around it.
 
-Prints ONE JSON line on rank 0: the contract fields plus
+A plain run sets up, warms up, times exactly --steps steps in one region, writes the last timed step's armour lists if
+--dump-outputs DIR is given, and prints ONE JSON line on rank 0: the contract fields (value, ms_per_step, ...), timed_region, config.
+With --full the line also carries the side measurements, each of which takes runs of its own:
+  timed_region  --repeats regions of --steps steps (default 7 with --full), value = the median region
+  lone_batch_ms, stage_ms, and steady_state, steps_with_collect (skipped by --no-extras)
   roofline      k_binary (the kernel that moves the algorithmic 4 B/px), timed with HIP events on its own launch stream inside this
                 process, COLD (every launch on another context's frames and buffers); `in_schedule_frac` = the same kernel in the
                 steps' own schedule (two launches overlapping, nothing else on the machine)
@@ -63,8 +67,15 @@ def parse_args(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=100)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--repeats", type=int, default=7,
-                    help="the timed region (exactly --steps steps between two barriers) is repeated this many times; value = median")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the metric, every side measurement (roofline, stages, lone batch, steady state, C2, C5, density sweep, "
+                         "per-frame chain, CPU baseline); a plain run does only the timed steps")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the armour lists of the last timed step (what rmcv_pipeline_collect returns; on "
+                         "rank 0 of a launched run, the gathered lists) as DIR/<name>.npy in float32 / float64")
+    ap.add_argument("--repeats", type=int, default=None,
+                    help="the timed region (exactly --steps steps between two barriers) is repeated this many times; value = median "
+                         "(default: 1; 7 with --full)")
     ap.add_argument("--warmup-seconds", type=float, default=0.4,
                     help="besides --warmup steps: untimed steps for at least this long, so the clocks have ramped before the timed region")
     ap.add_argument("--frames", type=int, default=FRAMES, help="frames per GPU per step")
@@ -73,7 +84,7 @@ def parse_args(argv=None):
                          "bright windows per frame, 5 %% foreground -- frames beyond findContours' LDS tables; a workload beside the metric)")
     ap.add_argument("--one-dense", action="store_true", help="one dense4 frame in every batch of the stream (a camera frame with a lit window; a workload beside the metric)")
     ap.add_argument("--cpu-frames", type=int, default=256, help="frames per pass of the CPU-baseline sample (0 = skip)")
-    ap.add_argument("--no-extras", action="store_true", help="skip the side measurements (C2, C5, density sweep, per-frame chain)")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the side measurements (C2, C5, density sweep, per-frame chain)")
     ap.add_argument("--density-sweep", action="store_true", help="the density sweep with all five levels instead of the default three")
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="c3",
                     help="c3: 1280x1024 full path (the metric's config); c5: 1920x1200 full path + SVM digit classify on the icons; "
@@ -102,7 +113,12 @@ def parse_args(argv=None):
                          "in turn) between HIP events -- the command tools/profile_round4.sh runs under rocprofv3, so that the trace's average "
                          "duration of k_binary is ONE kind of launch (the full command mixes cold, warm, overlapping and 2-per-CU launches)")
     ap.add_argument("--dev", action="store_true", help="accept the environment knobs that change the timed region (%s)" % ", ".join(DEV_KNOBS))
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.repeats is None:
+        a.repeats = 7 if a.full else 1
+    if a.dump_outputs and a.roofline_only:
+        ap.error("--dump-outputs needs the steps; --roofline-only runs none")
+    return a
 
 
 def free_port():
@@ -190,12 +206,31 @@ def c_host_chain(W, H, image_export=None):
         return {"error": repr(e)[:200]}
 
 
+def write_outputs(out_dir, arm, offs, ctx, stages):
+    """--dump-outputs: one step's results as DIR/<name>.npy, float32 where the library returns float32, float64 otherwise.
+    arm / offs: the armour lists and frame offsets; ctx (None for a gathered list): the context the step ran in, for the identities
+    and poses of a classify / pose stage"""
+    from rmcv_amd import STAGE_IDENTITY, STAGE_POSE
+    res = {"armour_vertices": arm["vertices"], "armour_icon": arm["icon"], "armour_bbox": arm["bbox"],
+           "armour_blob_i": arm["blob_i"].astype(np.float64), "armour_blob_j": arm["blob_j"].astype(np.float64),
+           "armour_frame_offsets": np.asarray(offs, np.float64)}
+    if ctx is not None and stages & STAGE_IDENTITY:
+        res["armour_identity"] = ctx.identities().astype(np.float64)
+    if ctx is not None and stages & STAGE_POSE:
+        res["armour_rvec"], res["armour_tvec"], res["armour_position"] = ctx.poses()
+    if sum(a.nbytes for a in res.values()) > 64 << 20:
+        raise SystemExit("bench.py: the outputs exceed 64 MB")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in res.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, np.float32 if a.dtype == np.float32 else np.float64))
+
+
 def main():
     args = parse_args()
     world, rank, local_rank, launched = resolve_world(args, os.environ)
     knobs = dev_knobs(os.environ, args.dev)
     c_host_first = None
-    if world == 1 and rank == 0 and not args.no_extras and not args.roofline_only and args.workload == "c3":
+    if args.full and world == 1 and rank == 0 and not args.no_extras and not args.roofline_only and args.workload == "c3":
         c_host_first = c_host_chain(*WORKLOADS[args.workload])   # before this process touches the GPU (see single_frame_ms)
     if args.gpus > 1 and not launched:
         import torch                                             # (may call hipGetDeviceCount; harmless: the ranks are fresh children)
@@ -214,7 +249,7 @@ def main():
     import torch
     import torch.distributed as dist
 
-    from rmcv_amd import (CAMP_BLUE, CAMP_RED, MORPH_CLOSE, MORPH_DILATE, OPT_PIXEL_GROUPS, OPT_PIXEL_SHAPE, OPT_SPARSE_WAVES, STAGE_ALL, STAGE_BINARY,
+    from rmcv_amd import (ARMOUR, CAMP_BLUE, CAMP_RED, MORPH_CLOSE, MORPH_DILATE, OPT_PIXEL_GROUPS, OPT_PIXEL_SHAPE, OPT_SPARSE_WAVES, STAGE_ALL, STAGE_BINARY,
                           STAGE_IDENTITY, STAGE_NO_IMAGE, STAGE_POSE, Context, LegacyParams, Pipeline, default_params, synth)
     from rmcv_amd import dist as rdist
 
@@ -405,13 +440,20 @@ def main():
     for _ in range(args.warmup):
         step()
     barrier()
-    # warm-up by time as well: a GPU that idled while the frames were generated has to ramp its clocks; 5 steps are 1.5 ms
-    tw, warm_steps = time.perf_counter(), 0
+    # warm-up by time as well: a GPU that idled while the frames were generated has to ramp its clocks; 5 steps are 1.5 ms.
+    # In chunks of at most 64 steps, so that a long --steps does not stretch the warm-up far past --warmup-seconds.
+    tw, warm_steps, chunk = time.perf_counter(), 0, max(1, min(args.steps, 64))
     while agree_max(time.perf_counter() - tw) < args.warmup_seconds:
-        for _ in range(max(1, args.steps)):
+        for _ in range(chunk):
             step()
-        warm_steps += max(1, args.steps)
+        warm_steps += chunk
         barrier()
+    # the timed region starts on frame set 0 whatever the warm-up by time ran, so that its last step (the one --dump-outputs
+    # writes) runs on the same frames from run to run
+    while step_no[0] % n_sets:
+        step()
+        warm_steps += 1
+    barrier()
     # the timed region: EXACTLY --steps steps between two (barrier + synchronize), MAX over ranks; repeated --repeats times,
     # value = the median repeat (median and min over the passes)
     del hot_each[:]
@@ -425,11 +467,48 @@ def main():
     dt = median(rep_dt)
     ms_per_step = dt / args.steps * 1e3
     value = world * n * args.steps / dt
+
+    # ---- what was computed (outside the timed region): the last `depth` batches through rmcv_pipeline_collect + the gathered list
+    barrier()
+    arm_by_set = {}
+    submitted = pl.get_info().submitted                          # tickets count the submits on this pipeline = the steps so far
+    for t_ in range(max(0, submitted - ns), submitted):
+        a_, o_ = pl.collect(t_)
+        arm_by_set[t_ % n_sets] = int(len(a_))                    # (step t ran on frame set t % n_sets)
+        assert o_[-1] == len(a_)
+    last_arm, last_offs = a_, o_                                  # the last timed step's lists, as rmcv_pipeline_collect returns them
+    last_ticket = submitted - 1
+    ctx_last = pl.context_of(last_ticket)
+    cnt = ctx_last.counts()
+    bad = int(np.count_nonzero(cnt["status"] & 15))
+    slow = int(np.count_nonzero(cnt["status"] & 16))              # frames findContours handed to the sequential scanner
+    mid = int(np.count_nonzero(cnt["status"] & 64))               # frames beyond the LDS tables: mid tier (tables in global memory)
+    n_arm_local = arm_by_set.get(0, int(cnt["n_armours"].sum()))   # the armours of frame set 0 (= the frames the CPU baseline runs on)
+    gathered = None
+    if rank == 0:
+        if use_dist and hook is not None:
+            recs = hook.records(last_ticket)
+        elif use_dist:
+            d_, b_ = pl.gathered(last_ticket)
+            whole = rdist.tensor_at(d_, b_, dev)
+            recs = [whole[r_ * info.record_bytes:(r_ + 1) * info.record_bytes] for r_ in range(world)]
+        else:
+            d_, _s = pl.record(last_ticket)
+            recs = [rdist.tensor_at(d_, info.record_bytes, dev)]
+        arm, offs = rdist.unpack_records(recs, n, cap)
+        gathered = int(arm.shape[0])
+        assert offs[-1] == gathered and len(offs) == world * n + 1
+        if use_dist:
+            last_arm, last_offs = arm.view(ARMOUR).reshape(-1), offs
+
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, last_arm, last_offs, pl.context_of(last_ticket) if not use_dist else None, stages)
+
     # beside the metric: ONE long region (25 x --steps steps): a timed region starts with an empty pipeline and ends by draining it,
     # which a 20-step region pays in full and a camera feed never does.  Reported, never `value`.
     steady = None
     collect_variant = None
-    if not args.no_extras:
+    if args.full and not args.no_extras:
         # beside the metric: the same regions with every list READ by the host inside the loop -- rmcv_pipeline_collect of ticket
         # t - depth + 1 right behind submit t, as the header's example loop does (the metric's region only submits; its lists go to
         # pinned host memory every step but nobody reads them until the region is over)
@@ -454,36 +533,6 @@ def main():
         (dts,), _ = regions(long_steps, 1)
         steady = {"steps": long_steps, "ms_per_step": round(dts / long_steps * 1e3, 4), "frames_per_s": round(world * n * long_steps / dts, 1),
                   "note": "one region of 25 x --steps steps between barrier+synchronize pairs: the pipeline's fill and drain amortised; not the metric"}
-
-    # ---- what was computed (outside the timed region): the last `depth` batches through rmcv_pipeline_collect + the gathered list
-    barrier()
-    arm_by_set = {}
-    submitted = pl.get_info().submitted                          # tickets count the submits on this pipeline = the steps so far
-    for t_ in range(max(0, submitted - ns), submitted):
-        a_, o_ = pl.collect(t_)
-        arm_by_set[t_ % n_sets] = int(len(a_))                    # (step t ran on frame set t % n_sets)
-        assert o_[-1] == len(a_)
-    last_ticket = submitted - 1
-    ctx_last = pl.context_of(last_ticket)
-    cnt = ctx_last.counts()
-    bad = int(np.count_nonzero(cnt["status"] & 15))
-    slow = int(np.count_nonzero(cnt["status"] & 16))              # frames findContours handed to the sequential scanner
-    mid = int(np.count_nonzero(cnt["status"] & 64))               # frames beyond the LDS tables: mid tier (tables in global memory)
-    n_arm_local = arm_by_set.get(0, int(cnt["n_armours"].sum()))   # the armours of frame set 0 (= the frames the CPU baseline runs on)
-    gathered = None
-    if rank == 0:
-        if use_dist and hook is not None:
-            recs = hook.records(last_ticket)
-        elif use_dist:
-            d_, b_ = pl.gathered(last_ticket)
-            whole = rdist.tensor_at(d_, b_, dev)
-            recs = [whole[r_ * info.record_bytes:(r_ + 1) * info.record_bytes] for r_ in range(world)]
-        else:
-            d_, _s = pl.record(last_ticket)
-            recs = [rdist.tensor_at(d_, info.record_bytes, dev)]
-        arm, offs = rdist.unpack_records(recs, n, cap)
-        gathered = int(arm.shape[0])
-        assert offs[-1] == gathered and len(offs) == world * n + 1
 
     # ---- dev tool: RMCV_BENCH_AB -- regions of 5 x --steps steps alternating between two settings IN ONE PROCESS
     ab = None
@@ -553,6 +602,59 @@ def main():
               "a": {"median_ms": round(float(np.median(res_[0])), 4), "mean_ms": round(float(np.mean(res_[0])), 4), "each": [round(x, 4) for x in res_[0]]},
               "b": {"median_ms": round(float(np.median(res_[1])), 4), "mean_ms": round(float(np.mean(res_[1])), 4), "each": [round(x, 4) for x in res_[1]]}}
         ab["b_over_a"] = round(ab["b"]["mean_ms"] / ab["a"]["mean_ms"], 4)
+
+    def headline():
+        """the contract fields, the timed region and the configuration: all a plain run reports"""
+        srt = sorted(rep_dt)
+        return {
+            "metric": "frames/sec (%dx%d BGR) armour detect" % (W, H), "value": round(value, 1), "unit": "frames/s",
+            "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
+            "timed_region": {"repeats": len(rep_dt), "ms_per_step_each": [round(d / args.steps * 1e3, 4) for d in rep_dt],
+                             "batches_in_hot_contexts_each": hot_timed,
+                             "ms_per_step_median": round(ms_per_step, 4), "ms_per_step_min": round(srt[0] / args.steps * 1e3, 4),
+                             "value_at_min": round(world * n * args.steps / srt[0], 1), "warmup_steps_requested": args.warmup, "warmup_steps_by_time": warm_steps,
+                             "host_enqueue_ms_per_step": round(median(enq_dt) / args.steps * 1e3, 4),
+                             "max_submit_host_ms_each": [round(x * 1e3, 4) for x in submit_max_timed],
+                             "host_blocking_calls": int(pl.get_info().host_blocking_calls),
+                             "note": "each repeat = exactly `steps` calls of rmcv_pipeline_submit between barrier+synchronize pairs; value/ms_per_step = the median repeat. "
+                                     "A region starts on an empty machine and ends with a drain: its second pixel launch is held back (k_delay, <= 60 us) so that the first takes "
+                                     "every CU, and its last batch's sparse stage runs with the latency kernel (the drain knows nothing follows) -- both are the library's "
+                                     "behaviour for any burst, not the bench's; steady_state and steps_with_collect show the same loop without / beside them"},
+            "steady_state": steady, "steps_with_collect": collect_variant,
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
+            "config": {"workload": "%s: batch=%d/GPU %dx%d BGR, blue lb=80, close3x3 + findContours + lightblob fit + armour "
+                                   "pairing%s%s" % (args.workload.upper(), n, W, H,
+                                                    (" + icon rectification + 7-class linear SVM (synthetic weights)" if svm else "") +
+                                                    (" [legacy blob stage: FindLightBlobs, minAreaRect boxes, camp vote]" if legacy else "") +
+                                                    (" + solve_PnP (IPPE square) and world position per armour" if args.pose else ""),
+                                                    " + RCCL gather of armour lists (C4)" if world > 1 else ""),
+                       "frames_per_gpu": n, "stream_variant": args.variant, "one_dense_frame_per_batch": args.one_dense, "parallelism": "frame-shard x%d" % world,
+                       "host_api": "rmcv_pipeline_submit (librmcv_hip.so): one call per step",
+                       "batches_in_flight": info.depth, "pixel_streams": info.pixel_streams, "sparse_streams": info.sparse_streams, "dense_streams": info.dense_streams,
+                       "hot_contexts": info.hot_contexts, "batches_in_hot_contexts": int(pl.get_info().hot_batches), "batches_finished_with_the_latency_kernel": int(pl.get_info().latency_batches), "pixel_kernel_of_calm_batches": roof_kernel,
+                       "frame_sets": n_sets, "gpu_max_hw_queues": info.hw_queues_env, "pixel_groups_per_cu": info.pixel_groups,
+                       "sparse_waves_per_frame": info.sparse_waves, "results_to_host_every_step": info.host_results == 1,
+                       "stages": stages, "dev_knobs": knobs or None,
+                       "armours_rank0_shard": n_arm_local, "armours_by_frame_set": [arm_by_set.get(k) for k in range(n_sets)], "armours_gathered": gathered,
+                       "frames_over_capacity": bad, "frames_slow_path": slow, "frames_mid_tier": mid, "batches_with_dense_frames_split_off": int(pl.get_info().dense_split),
+                       "rccl_ranks": (dist.get_world_size() if use_dist else None), "gather": gather_note},
+            **({"ab": ab} if ab else {}),
+            "path_hbm_frac": round(value / world * BYTES_PER_FRAME / 1e9 / HBM_PEAK_GBS, 4),
+        }
+
+    def finish(out):
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        barrier()                                       # rank 0 has the extras and the CPU baseline to itself: leave together
+        pl.close()
+        if abi_gather is not None:
+            abi_gather.close()
+        if use_dist:
+            dist.destroy_process_group()
+
+    if not args.full:
+        finish(headline())
+        return
 
     # ---- "alone" measurements on the ring's own contexts (the pipeline is drained), each on its own frames: HBM, not the Infinity Cache
     barrier()
@@ -677,43 +779,10 @@ def main():
 
     def frac(ms):
         return round(n * BYTES_PER_FRAME / (ms * 1e-3) / 1e9 / HBM_PEAK_GBS, 4)
-    srt = sorted(rep_dt)
-    out = {
-        "metric": "frames/sec (%dx%d BGR) armour detect" % (W, H), "value": round(value, 1), "unit": "frames/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
-        "timed_region": {"repeats": len(rep_dt), "ms_per_step_each": [round(d / args.steps * 1e3, 4) for d in rep_dt],
-                         "batches_in_hot_contexts_each": hot_timed,
-                         "ms_per_step_median": round(ms_per_step, 4), "ms_per_step_min": round(srt[0] / args.steps * 1e3, 4),
-                         "value_at_min": round(world * n * args.steps / srt[0], 1), "warmup_steps_requested": args.warmup, "warmup_steps_by_time": warm_steps,
-                         "host_enqueue_ms_per_step": round(median(enq_dt) / args.steps * 1e3, 4),
-                         "max_submit_host_ms_each": [round(x * 1e3, 4) for x in submit_max_timed],
-                         "host_blocking_calls": int(pl.get_info().host_blocking_calls),
-                         "note": "each repeat = exactly `steps` calls of rmcv_pipeline_submit between barrier+synchronize pairs; value/ms_per_step = the median repeat. "
-                                 "A region starts on an empty machine and ends with a drain: its second pixel launch is held back (k_delay, <= 60 us) so that the first takes "
-                                 "every CU, and its last batch's sparse stage runs with the latency kernel (the drain knows nothing follows) -- both are the library's "
-                                 "behaviour for any burst, not the bench's; steady_state and steps_with_collect show the same loop without / beside them"},
-        "steady_state": steady, "steps_with_collect": collect_variant,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "u8", "data": "synthetic",
-        "config": {"workload": "%s: batch=%d/GPU %dx%d BGR, blue lb=80, close3x3 + findContours + lightblob fit + armour "
-                               "pairing%s%s" % (args.workload.upper(), n, W, H,
-                                                (" + icon rectification + 7-class linear SVM (synthetic weights)" if svm else "") +
-                                                (" [legacy blob stage: FindLightBlobs, minAreaRect boxes, camp vote]" if legacy else "") +
-                                                (" + solve_PnP (IPPE square) and world position per armour" if args.pose else ""),
-                                                " + RCCL gather of armour lists (C4)" if world > 1 else ""),
-                   "frames_per_gpu": n, "stream_variant": args.variant, "one_dense_frame_per_batch": args.one_dense, "parallelism": "frame-shard x%d" % world,
-                   "host_api": "rmcv_pipeline_submit (librmcv_hip.so): one call per step",
-                   "batches_in_flight": info.depth, "pixel_streams": info.pixel_streams, "sparse_streams": info.sparse_streams, "dense_streams": info.dense_streams,
-                   "hot_contexts": info.hot_contexts, "batches_in_hot_contexts": int(pl.get_info().hot_batches), "batches_finished_with_the_latency_kernel": int(pl.get_info().latency_batches), "pixel_kernel_of_calm_batches": roof_kernel,
-                   "frame_sets": n_sets, "gpu_max_hw_queues": info.hw_queues_env, "pixel_groups_per_cu": groups_in_steps,
-                   "sparse_waves_per_frame": waves_in_steps, "results_to_host_every_step": info.host_results == 1,
-                   "stages": stages, "dev_knobs": knobs or None,
-                   "armours_rank0_shard": n_arm_local, "armours_by_frame_set": [arm_by_set.get(k) for k in range(n_sets)], "armours_gathered": gathered,
-                   "frames_over_capacity": bad, "frames_slow_path": slow, "frames_mid_tier": mid, "batches_with_dense_frames_split_off": int(pl.get_info().dense_split),
-                   "rccl_ranks": (dist.get_world_size() if use_dist else None), "gather": gather_note},
+    out = headline()
+    out.update({
         "lone_batch_ms": {"median": round(lone[len(lone) // 2], 4), "min": round(lone[0], 4), "passes": len(lone),
                           "note": "one batch at a time on one stream, events around detect + compaction (latency, not the metric)"},
-        **({"ab": ab} if ab else {}),
-        "path_hbm_frac": round(value / world * BYTES_PER_FRAME / 1e9 / HBM_PEAK_GBS, 4),
         "stage_ms": {"binary": round(float(stage[0]), 4), "contours": round(float(stage[1]), 4),
                      "blobs": round(float(stage[2]), 4), "armours": round(float(stage[3]), 4),
                      "sum": round(float(stage[4]), 4),
@@ -735,7 +804,7 @@ def main():
                      "pixel_kernels_only_in_the_steps_schedule": None if k1_pipe_ms is None else {
                          "ms_per_launch": round(k1_pipe_ms, 4), "frac": frac(k1_pipe_ms),
                          "note": "%d steps of the pipeline with the stage mask cut down to RMCV_STAGE_BINARY, wall clock between two drains" % (4 * R)}},
-    }
+    })
 
     extras = not args.no_extras and rank == 0 and world == 1
     if not args.no_extras and rank == 0:
@@ -973,14 +1042,7 @@ def main():
                                                    "sample": "%d passes over all %d frames of the batch (%.1f s), one frame per task, %d threads = "
                                                              "every hardware thread the host shows" % (passes_ev, n, dev_, every),
                                                    "armours": tot_ev}
-    if rank == 0:
-        print(json.dumps(out), flush=True)
-    barrier()                                       # rank 0 has the extras and the CPU baseline to itself: leave together
-    pl.close()
-    if abi_gather is not None:
-        abi_gather.close()
-    if use_dist:
-        dist.destroy_process_group()
+    finish(out)
 
 
 if __name__ == "__main__":

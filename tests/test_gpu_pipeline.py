@@ -222,14 +222,13 @@ def test_pipeline_identity_and_legacy_stages(oracle):
     pl.close()
 
 
-def test_c_host_drives_the_same_pipeline(oracle):
+def test_c_host_drives_the_same_pipeline(oracle, tmp_path):
     """tools/pipeline_bench.c: the three calls from a C program (no Python, no torch in that process) -- a small run, its armour
     counts against the oracle's for the same synthetic frames"""
     cc = shutil.which("gcc") or shutil.which("cc")
     if not cc:
         pytest.skip("no C compiler on this box")
-    exe = os.path.join(ROOT, "gpurun_out", "pipeline_bench_test")
-    os.makedirs(os.path.dirname(exe), exist_ok=True)
+    exe = str(tmp_path / "pipeline_bench_test")
     libdir = os.path.join(ROOT, "rmcv_amd", "lib")
     subprocess.run([cc, "-O2", "-I", os.path.join(ROOT, "include"), os.path.join(ROOT, "tools", "pipeline_bench.c"), "-o", exe, "-L", libdir,
                     "-lrmcv_hip", "-Wl,-rpath," + libdir, "-lpthread"], check=True, timeout=120)

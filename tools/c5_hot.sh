@@ -3,7 +3,7 @@
 # box: the product build (out), the dev build with RMCV_HOT_IDENTITY=1 and 3..6 contexts in rotation.
 cd $GRAFT_REPO_ROOT
 tag=${1:-c5hot}; out=gpurun_out/$tag; mkdir -p $out
-B="python bench.py --workload c5 --no-extras --cpu-frames 0 --steps 20 --warmup 5"
+B="python bench.py --full --workload c5 --no-extras --cpu-frames 0 --steps 20 --warmup 5"
 pick='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(sys.argv[1], d["ms_per_step"], d["timed_region"]["ms_per_step_each"], "hot", d["config"]["hot_contexts"], d["config"]["batches_in_hot_contexts"], "steady", d["steady_state"])'
 for rep in 1 2; do
   $B 2>$out/err.txt | python -c "$pick" "product(identity out)" || exit 1

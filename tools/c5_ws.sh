@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 tag=${1:-c5ws}; out=gpurun_out/$tag; mkdir -p $out
 pick='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); r=d["roofline"]; print(sys.argv[1], "step", d["ms_per_step"], d["timed_region"]["ms_per_step_each"][:4], "steady", (d["steady_state"] or {}).get("ms_per_step"), "ws launches hot", d["config"]["batches_in_hot_contexts"])'
-B="python bench.py --workload c5 --cpu-frames 0 --steps 20 --warmup 5 --dev"
+B="python bench.py --full --workload c5 --cpu-frames 0 --steps 20 --warmup 5 --dev"
 export RMCV_LIB_PATH=$PWD/rmcv_amd/lib/dev/librmcv_hip.so
 for rep in 1 2; do
   $B 2>$out/err.txt | python -c "$pick" "k_binary (default)" || exit 1

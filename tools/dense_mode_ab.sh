@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 tag=${1:-densemode}; out=gpurun_out/$tag; mkdir -p $out
 pick='import json,sys; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(sys.argv[1], d["ms_per_step"], d["timed_region"]["ms_per_step_each"][:4], "mid", d["config"]["frames_mid_tier"])'
-B="python bench.py --no-extras --cpu-frames 0 --steps 20 --warmup 5 --dev"
+B="python bench.py --full --no-extras --cpu-frames 0 --steps 20 --warmup 5 --dev"
 export RMCV_LIB_PATH=$PWD/rmcv_amd/lib/dev/librmcv_hip.so
 for v in dense2 dense4 dense3; do
   RMCV_HEAVY_OFF=1 $B --variant $v 2>$out/err.txt | python -c "$pick" "$v dense-mode-off" || exit 1

@@ -11,10 +11,10 @@ if [ "$wl" = c5 ]; then W=1920; H=1200; else W=1280; H=1024; fi
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out/prof_$tag; mkdir -p $out
 RO="--workload $wl --roofline-only"
-Q="--workload $wl --cpu-frames 0 --no-extras --repeats 1 --warmup-seconds 0 --steps 12 --warmup 10"   # (the default ring: after the first cycle the calm batches run k_binary_ws in the hot contexts)
+Q="--full --workload $wl --cpu-frames 0 --no-extras --repeats 1 --warmup-seconds 0 --steps 12 --warmup 10"   # (the default ring: after the first cycle the calm batches run k_binary_ws in the hot contexts)
 python3 bench.py $RO > $out/roofline_plain.json 2> $out/roofline_plain.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $out/roofline -- python3 bench.py $RO > $out/roofline_traced.json 2> $out/roofline.err
-rocprofv3 --kernel-trace --stats --output-format csv -d $out/default -- python3 bench.py --workload $wl --steps 20 --warmup 5 --cpu-frames 0 --no-extras > $out/bench_default.json 2> $out/default.err
+rocprofv3 --kernel-trace --stats --output-format csv -d $out/default -- python3 bench.py --full --workload $wl --steps 20 --warmup 5 --cpu-frames 0 --no-extras > $out/bench_default.json 2> $out/default.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_fetch -- python3 bench.py $RO > /dev/null 2> $out/pmc_fetch.err
 rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format csv -d $out/pmc_cal -- python3 tools/k1_bench.py 3 0 $W $H > $out/cal.txt 2> $out/pmc_cal.err
 rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format csv -d $out/pmc_write -- python3 bench.py $RO > /dev/null 2> $out/pmc_write.err
