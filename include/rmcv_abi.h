@@ -217,6 +217,25 @@ const char* rmcv_last_error(const rmcv_ctx* ctx);
  * microseconds (one sleeping wavefront): a stand-in for a kernel that does not finish in time.  One shot.  A test hook
  * (tests/test_gpu_deadline.py). */
 #define RMCV_OPT_TEST_DELAY_US 16
+/* RMCV_OPT_INPUT_FORMAT: what the frame pointers of this context hold -- RMCV_INPUT_BGR (0, default): CV_8UC3 BGR, 3 bytes per
+ * pixel; or one of the four RMCV_BAYER_* patterns: a raw 8-bit mosaic straight from the sensor, 1 byte per pixel (rows `stride >= w`
+ * bytes apart, frames `frame_pitch >= stride * (h - 1) + w` apart, w >= 3, h >= 3; no 10/12-bit data, no mirror, no flip).  Every
+ * result for a mosaic m is, bit for bit, what the BGR path gives for the frame D(m), the library's demosaic (rmcv_demosaic): bilinear
+ * in integers as OpenCV's 8-bit COLOR_Bayer*2BGR is recalled to do it (not pinned against OpenCV), the outermost rows and columns
+ * repeating their interior neighbour.  The pixel kernel reads the mosaic itself (k_binary_bayer: 1 B/px instead of 3); no colour frame
+ * is ever made.  Batch calls record the format when frames are bound (rmcv_batch_upload, rmcv_batch_set_device_frames,
+ * rmcv_pipeline_submit); rmcv_extract_color and rmcv_classify_armours read their frame as a mosaic while it is set.  The legacy matcher
+ * (rmcv_find_lightblobs, rmcv_batch_run_legacy, rmcv_pipeline_submit_legacy) votes camps from BGR means and answers RMCV_ERR_BAD_ARG
+ * under a Bayer format.
+ * The pattern values are those of the Daheng SDK's DX_PIXEL_COLOR_FILTER, so a camera host passes its value straight through; each
+ * name gives the top-left 2x2 block of the mosaic.  OpenCV names the same layouts by the second row's pair (as recalled, not pinned
+ * here): RMCV_BAYER_RG is its COLOR_BayerBG2BGR, GB its GR, GR its GB, BG its RG. */
+#define RMCV_OPT_INPUT_FORMAT 19
+#define RMCV_INPUT_BGR 0
+#define RMCV_BAYER_RG 1 /* R G / G B */
+#define RMCV_BAYER_GB 2 /* G B / R G */
+#define RMCV_BAYER_GR 3 /* G R / B G */
+#define RMCV_BAYER_BG 4 /* B G / G R */
 int  rmcv_ctx_set_option(rmcv_ctx* ctx, int option, int value);
 /* launches of k_binary_ws (RMCV_OPT_PIXEL_SHAPE 1) by this process so far: a diagnostic -- an option that is set but whose
  * conditions a batch does not meet falls back to k_binary silently (tests/test_gpu_pixel_shape.py) */
@@ -257,6 +276,11 @@ int rmcv_filter_armours(rmcv_ctx* ctx, const rmcv_lightblob* blobs, int n_blobs,
 
 /* cv::fitEllipseDirect on one contour (the step of src/objdetect.cpp:68), for stage-wise parity */
 int rmcv_fit_ellipse(rmcv_ctx* ctx, const rmcv_point* pts, int n, rmcv_rrect* out);
+
+/* D(m) of one host mosaic (RMCV_OPT_INPUT_FORMAT) as a host BGR frame, for stage-wise parity and for callers that still want a
+ * colour frame (a recorder).  raw: h rows of `stride >= w` bytes; bgr_out: h rows of `out_stride >= 3 w` bytes; w, h >= 3;
+ * pattern RMCV_BAYER_RG .. RMCV_BAYER_BG.  Independent of the context's RMCV_OPT_INPUT_FORMAT. */
+int rmcv_demosaic(rmcv_ctx* ctx, const uint8_t* raw, int w, int h, int stride, int pattern, uint8_t* bgr_out, int out_stride);
 
 /* ---- batch of independent frames, resident on the device ------------------------------ */
 

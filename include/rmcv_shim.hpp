@@ -15,6 +15,7 @@
 // Default arguments stay on the reference's declarations (include/objdetect.h:22-37, include/mobility.h:106-108).
 // Also the legacy matcher rm::MatchLightBlob / rm::FindLightBlobs / rm::LightBlobOverlap (include/objdetect.h:22-37, 62)
 // and rm::solve_PnP (include/mobility.h:106-108).
+// One addition the reference does not have: rm::extract_color_bayer, rm::extract_color on a raw 8-bit Bayer mosaic (CV_8UC1).
 // The legacy names of the north star are aliased at the bottom (docs/core_8h_source.html:101,114).
 //
 // Every signature mentions cv:: types, so this header only compiles where OpenCV headers exist.
@@ -89,10 +90,10 @@ inline rmcv_lightblob from_lightblob(const lightblob& b)
 
 } // namespace hip_detail
 
-RMCV_SHIM_LINKAGE std::tuple<std::vector<contour>, cv::Mat> extract_color(cv::InputArray image, camp target, int lower_bound)
+namespace hip_detail {
+// rm::extract_color's body for whatever the thread's context reads its frame as (RMCV_OPT_INPUT_FORMAT)
+inline std::tuple<std::vector<contour>, cv::Mat> extract(const cv::Mat& img, camp target, int lower_bound)
 {
-    cv::Mat img = image.getMat();
-    CV_Assert(img.type() == CV_8UC3);
     cv::Mat binary(img.rows, img.cols, CV_8UC1);
     static thread_local std::vector<rmcv_point> pts;
     static thread_local std::vector<int32_t> offs;
@@ -110,6 +111,29 @@ RMCV_SHIM_LINKAGE std::tuple<std::vector<contour>, cv::Mat> extract_color(cv::In
         for (int k = offs[i]; k < offs[i + 1]; k++) contours[i].emplace_back(pts[k].x, pts[k].y);
     }
     return {contours, binary};
+}
+} // namespace hip_detail
+
+RMCV_SHIM_LINKAGE std::tuple<std::vector<contour>, cv::Mat> extract_color(cv::InputArray image, camp target, int lower_bound)
+{
+    cv::Mat img = image.getMat();
+    CV_Assert(img.type() == CV_8UC3);
+    return hip_detail::extract(img, target, lower_bound);
+}
+
+// Not a reference function: rm::extract_color on the camera's raw 8-bit Bayer mosaic (CV_8UC1), so that a camera host hands over
+// the sensor's buffer instead of converting it on the CPU first.  `pattern` is RMCV_BAYER_RG .. RMCV_BAYER_BG (the
+// Daheng SDK's DX_PIXEL_COLOR_FILTER values).  The results are rm::extract_color's on D(raw), the library's demosaic
+// (include/rmcv_abi.h: RMCV_OPT_INPUT_FORMAT).  The thread's context reads mosaics for this call only: rm::extract_color is unchanged.
+RMCV_SHIM_LINKAGE std::tuple<std::vector<contour>, cv::Mat> extract_color_bayer(cv::InputArray raw, int pattern, camp target, int lower_bound)
+{
+    cv::Mat img = raw.getMat();
+    CV_Assert(img.type() == CV_8UC1);
+    hip_detail::check(rmcv_ctx_set_option(hip_detail::ctx(), RMCV_OPT_INPUT_FORMAT, pattern));
+    struct Restore { // back to BGR however the call ends
+        ~Restore() { rmcv_ctx_set_option(hip_detail::ctx(), RMCV_OPT_INPUT_FORMAT, RMCV_INPUT_BGR); }
+    } restore;
+    return hip_detail::extract(img, target, lower_bound);
 }
 
 RMCV_SHIM_LINKAGE auto filter_lightblobs(const std::vector<contour>& contours, const float tilt_max, const range<float> ratio_range,

@@ -43,13 +43,17 @@ OPT_WAIT_TIMEOUT_MS = 15
 OPT_TEST_DELAY_US = 16
 OPT_IMAGE_EXPORT = 17
 OPT_TEST_SLOW_US = 18
+OPT_INPUT_FORMAT = 19
+# RMCV_OPT_INPUT_FORMAT values: BGR frames, or a raw 8-bit mosaic named by its top-left 2x2 block (the Daheng SDK's DX_PIXEL_COLOR_FILTER values)
+INPUT_BGR, BAYER_RG, BAYER_GB, BAYER_GR, BAYER_BG = 0, 1, 2, 3, 4
+BAYER_PATTERNS = (BAYER_RG, BAYER_GB, BAYER_GR, BAYER_BG)
 STAGE_BINARY, STAGE_CONTOURS, STAGE_BLOBS, STAGE_ARMOURS, STAGE_ALL, STAGE_IDENTITY, STAGE_POSE, STAGE_NO_IMAGE = 1, 2, 4, 8, 15, 16, 32, 64
 SVM_FEATURES = 1200
 FRAME_OVF_CONTOURS, FRAME_OVF_POINTS, FRAME_OVF_BLOBS, FRAME_OVF_ARMOURS, FRAME_SLOW_PATH, FRAME_MID_PATH = 1, 2, 4, 8, 16, 64
 
 EXPORTS = [
     "rmcv_abi_version", "rmcv_default_params", "rmcv_default_limits", "rmcv_ctx_create", "rmcv_ctx_destroy",
-    "rmcv_last_error", "rmcv_ctx_set_option", "rmcv_ctx_forget_frame_buffer", "rmcv_ctx_check_guards", "rmcv_ctx_frame_timing", "rmcv_extract_color", "rmcv_filter_lightblobs", "rmcv_filter_armours", "rmcv_fit_ellipse",
+    "rmcv_last_error", "rmcv_ctx_set_option", "rmcv_ctx_forget_frame_buffer", "rmcv_ctx_check_guards", "rmcv_ctx_frame_timing", "rmcv_extract_color", "rmcv_filter_lightblobs", "rmcv_filter_armours", "rmcv_fit_ellipse", "rmcv_demosaic",
     "rmcv_batch_upload", "rmcv_batch_set_device_frames", "rmcv_batch_run", "rmcv_batch_sync", "rmcv_batch_run_timed",
     "rmcv_batch_counts", "rmcv_batch_get_binary", "rmcv_batch_get_contours", "rmcv_batch_get_blobs",
     "rmcv_batch_get_armours", "rmcv_batch_device_views", "rmcv_batch_compact_armours", "rmcv_synth_frame", "rmcv_synth_checksum",
@@ -151,6 +155,9 @@ def load(path):
     L.rmcv_pipeline_record.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     L.rmcv_pipeline_gathered.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p]
     L.rmcv_pipeline_set_gather.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    if hasattr(L, "rmcv_demosaic"):  # (builds from before raw Bayer input stay loadable for A/B runs)
+        L.rmcv_demosaic.restype = C.c_int
+        L.rmcv_demosaic.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L

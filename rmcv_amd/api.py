@@ -34,12 +34,14 @@ class Context:
         self._made_by = lib()                                     # (a process can hold two builds: bench.py's RMCV_BENCH_AB=lib:...)
         self.device = device
         self._frames_ref = None
+        self.input_format = abi.INPUT_BGR
 
     @classmethod
     def borrowed(cls, handle, limits, device=0):
         """a view of a context somebody else owns (a slot of a Pipeline): the same methods, no destroy"""
         self = cls.__new__(cls)
         self.limits, self._h, self._made_by, self.device, self._frames_ref, self._borrowed = limits, C.c_void_p(handle), lib(), device, None, True
+        self.input_format = abi.INPUT_BGR
         return self
 
     def close(self):
@@ -66,16 +68,38 @@ class Context:
         xy = np.stack([pts["x"], pts["y"]], axis=1) if len(pts) else np.zeros((0, 2), np.int32)
         return [xy[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)], binary
 
-    def extract_color_csr(self, image, target=CAMP_BLUE, lower_bound=80, morph=MORPH_CLOSE):
+    def _frame(self, image):
+        """(image, h, w, row bytes) of one host frame: (h, w, 3) BGR, or (h, w) under a Bayer input format"""
         image = np.ascontiguousarray(image, np.uint8)
+        if self.input_format:
+            assert image.ndim == 2, "a Bayer input format takes (h, w) uint8 mosaics"
+            h, w = image.shape
+            return image, h, w, w
         h, w, ch = image.shape
         assert ch == 3
+        return image, h, w, 3 * w
+
+    def set_input_format(self, fmt):
+        """RMCV_OPT_INPUT_FORMAT: abi.INPUT_BGR (0) or one of abi.BAYER_PATTERNS -- what the frames handed in from now on hold"""
+        self.set_option(abi.OPT_INPUT_FORMAT, fmt)
+        self.input_format = int(fmt)
+
+    def demosaic(self, raw, pattern):
+        """D(m) of one (h, w) uint8 mosaic as an (h, w, 3) BGR frame (rmcv_demosaic: the library's demosaic, on the GPU)"""
+        raw = np.ascontiguousarray(raw, np.uint8)
+        h, w = raw.shape
+        out = np.empty((h, w, 3), np.uint8)
+        self._chk(lib().rmcv_demosaic(self._h, ptr(raw), w, h, w, int(pattern), ptr(out), 3 * w))
+        return out
+
+    def extract_color_csr(self, image, target=CAMP_BLUE, lower_bound=80, morph=MORPH_CLOSE):
+        image, h, w, rowb = self._frame(image)
         binary = np.empty((h, w), np.uint8)
         cap_p, cap_c = self.limits.max_points, self.limits.max_contours
         pts = np.empty(cap_p, POINT)
         offs = np.empty(cap_c + 1, np.int32)
         nc, npnt = C.c_int32(0), C.c_int32(0)
-        self._chk(lib().rmcv_extract_color(self._h, ptr(image), w, h, 3 * w, int(target), int(lower_bound), int(morph),
+        self._chk(lib().rmcv_extract_color(self._h, ptr(image), w, h, rowb, int(target), int(lower_bound), int(morph),
                                            ptr(binary), ptr(pts), cap_p, ptr(offs), cap_c, C.byref(nc), C.byref(npnt)))
         self.shape = (1, h, w)
         return pts[:npnt.value].copy(), offs[:nc.value + 1].copy(), binary
@@ -273,16 +297,22 @@ class Context:
 
     # ---------------------------------------------------------------- batch
     def upload(self, frames):
-        """frames: uint8 [n, h, w, 3] on the host -> the context's HBM buffer"""
+        """frames: uint8 [n, h, w, 3] on the host (or [n, h, w] mosaics under a Bayer input format) -> the context's HBM buffer"""
         frames = np.ascontiguousarray(frames, np.uint8)
-        n, h, w, ch = frames.shape
-        assert ch == 3
-        self._chk(lib().rmcv_batch_upload(self._h, ptr(frames), n, w, h, 3 * w, C.c_int64(3 * w * h)))
+        if self.input_format:
+            assert frames.ndim == 3, "a Bayer input format takes (n, h, w) uint8 mosaics"
+            n, h, w = frames.shape
+            rowb = w
+        else:
+            n, h, w, ch = frames.shape
+            assert ch == 3
+            rowb = 3 * w
+        self._chk(lib().rmcv_batch_upload(self._h, ptr(frames), n, w, h, rowb, C.c_int64(rowb * h)))
         self.shape = (n, h, w)
 
     def bind_device_frames(self, data_ptr, n, h, w, stride=None, frame_pitch=None, keepalive=None):
-        """borrow frames already in HBM (e.g. torch_tensor.data_ptr())"""
-        stride = stride or 3 * w
+        """borrow frames already in HBM (e.g. torch_tensor.data_ptr()); the default stride is 3 w, w under a Bayer input format"""
+        stride = stride or (w if self.input_format else 3 * w)
         frame_pitch = frame_pitch or stride * h
         self._frames_ref = keepalive
         self._chk(lib().rmcv_batch_set_device_frames(self._h, C.c_void_p(data_ptr), n, w, h, stride, C.c_int64(frame_pitch)))
@@ -365,13 +395,12 @@ class Context:
 
     def classify_armours(self, image, armours):
         """main.cpp:178-181 for one frame -> (identity int32[n], armours with clamped icon, icons uint8[n,20,20,3])"""
-        image = np.ascontiguousarray(image, np.uint8)
-        h, w, _ = image.shape
+        image, h, w, rowb = self._frame(image)
         arm = np.ascontiguousarray(armours, ARMOUR).copy()
         n = len(arm)
         ident = np.empty(max(n, 1), np.int32)
         icons = np.empty((max(n, 1), 20, 20, 3), np.uint8)
-        self._chk(lib().rmcv_classify_armours(self._h, ptr(image), w, h, 3 * w, ptr(arm), n, ptr(ident), ptr(icons)))
+        self._chk(lib().rmcv_classify_armours(self._h, ptr(image), w, h, rowb, ptr(arm), n, ptr(ident), ptr(icons)))
         return ident[:n].copy(), arm, icons[:n].copy()
 
     def identities(self):

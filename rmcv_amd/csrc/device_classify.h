@@ -6,6 +6,7 @@
 #pragma once
 #include <float.h>
 
+#include "device_bayer.h"
 #include "device_fit.h"
 #include "rmcv_internal.h"
 
@@ -21,9 +22,14 @@ struct WarpCtx {
     const uint8_t* roi; // frame + by*stride + 3*bx
     int stride, bw, bh;
     double M[6]; // inverted map
+    // a Bayer frame (RMCV_OPT_INPUT_FORMAT): the mosaic, its size, the ROI's corner in it and the pattern's R site (device_bayer.h)
+    const uint8_t* frame;
+    int fw, fh, bx, by, rx, ry;
 };
 
-// one channel triple of the warped ROI at (x, y): cv::warpAffine INTER_LINEAR, BORDER_CONSTANT 0, CV_8UC3
+// one channel triple of the warped ROI at (x, y): cv::warpAffine INTER_LINEAR, BORDER_CONSTANT 0, CV_8UC3.  BAYER: the ROI's pixels
+// are D(m) of the frame's mosaic, each computed from the FRAME's neighbourhood (not the ROI's); outside the box still 0.
+template <int BAYER = 0>
 __device__ inline void warp_px(const WarpCtx& W, int x, int y, int out[3])
 {
     const int AB_SCALE = 1 << 10, round_delta = 16;
@@ -39,13 +45,27 @@ __device__ inline void warp_px(const WarpCtx& W, int x, int y, int out[3])
     if (w00 > 32767) { w00 = 32767; w11 += 1; }
     const bool y0ok = sy >= 0 && sy < W.bh, y1ok = sy + 1 >= 0 && sy + 1 < W.bh;
     const bool x0ok = sx >= 0 && sx < W.bw, x1ok = sx + 1 >= 0 && sx + 1 < W.bw;
-    const uint8_t* p = W.roi + (int64_t)sy * W.stride + 3 * sx;
+    if constexpr (BAYER) {
+        int q00[3] = {0, 0, 0}, q01[3] = {0, 0, 0}, q10[3] = {0, 0, 0}, q11[3] = {0, 0, 0};
+        const int X0 = W.bx + sx, Y0 = W.by + sy;
+        if (y0ok && x0ok) bayer_bgr(W.frame, W.stride, W.fw, W.fh, W.rx, W.ry, X0, Y0, q00);
+        if (y0ok && x1ok) bayer_bgr(W.frame, W.stride, W.fw, W.fh, W.rx, W.ry, X0 + 1, Y0, q01);
+        if (y1ok && x0ok) bayer_bgr(W.frame, W.stride, W.fw, W.fh, W.rx, W.ry, X0, Y0 + 1, q10);
+        if (y1ok && x1ok) bayer_bgr(W.frame, W.stride, W.fw, W.fh, W.rx, W.ry, X0 + 1, Y0 + 1, q11);
 #pragma unroll
-    for (int c = 0; c < 3; c++) {
-        const int v00 = (y0ok && x0ok) ? p[c] : 0, v01 = (y0ok && x1ok) ? p[3 + c] : 0;
-        const int v10 = (y1ok && x0ok) ? p[W.stride + c] : 0, v11 = (y1ok && x1ok) ? p[W.stride + 3 + c] : 0;
-        const int v = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
-        out[c] = v < 0 ? 0 : (v > 255 ? 255 : v);
+        for (int c = 0; c < 3; c++) {
+            const int v = (q00[c] * w00 + q01[c] * w01 + q10[c] * w10 + q11[c] * w11 + (1 << 14)) >> 15;
+            out[c] = v < 0 ? 0 : (v > 255 ? 255 : v);
+        }
+    } else {
+        const uint8_t* p = W.roi + (int64_t)sy * W.stride + 3 * sx;
+#pragma unroll
+        for (int c = 0; c < 3; c++) {
+            const int v00 = (y0ok && x0ok) ? p[c] : 0, v01 = (y0ok && x1ok) ? p[3 + c] : 0;
+            const int v10 = (y1ok && x0ok) ? p[W.stride + c] : 0, v11 = (y1ok && x1ok) ? p[W.stride + 3 + c] : 0;
+            const int v = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
+            out[c] = v < 0 ? 0 : (v > 255 ? 255 : v);
+        }
     }
 }
 
@@ -63,8 +83,10 @@ struct ClassifyArgs { // what the classification of a frame's armours needs (Buf
 ClassifyArgs classify_args(const Geom& g, const Bufs& b); // k_classify.hip
 
 // armours wave, wave + nwaves, ... of frame f by this wavefront.  feat: NFEAT floats, sums: 32 doubles of wave-private LDS.
+// BAYER: the frames are mosaics of pattern `pattern` (the stand-alone k_classify only: the sparse kernel classifies BGR frames)
+template <int BAYER = 0>
 __device__ inline void classify_frame(int f, int lane, int wave, int nwaves, int n, const ClassifyArgs& C, rmcv_armour* __restrict__ armours,
-                                      int max_armours, float* feat, double* sums)
+                                      int max_armours, float* feat, double* sums, int pattern = 0)
 {
     const uint8_t* frame = C.frames + (int64_t)f * C.frame_pitch;
     const int w = C.w, h = C.h, stride = C.stride, n_class = C.n_class;
@@ -98,6 +120,15 @@ __device__ inline void classify_frame(int f, int lane, int wave, int nwaves, int
         W.stride = stride;
         W.bw = bw;
         W.bh = bh;
+        if constexpr (BAYER) {
+            W.frame = frame;
+            W.fw = w;
+            W.fh = h;
+            W.bx = bx;
+            W.by = by;
+            W.rx = bayer_rx(pattern);
+            W.ry = bayer_ry(pattern);
+        }
         {
             const float src[3][2] = {{ic[1][0] - (float)bx, ic[1][1] - (float)by},
                                      {ic[2][0] - (float)bx, ic[2][1] - (float)by},
@@ -164,10 +195,10 @@ __device__ inline void classify_frame(int f, int lane, int wave, int nwaves, int
             if (!degenerate) {
                 if (area) {
                     int p00[3], p01[3], p10[3], p11[3];
-                    warp_px(W, 2 * dx, 2 * dy, p00);
-                    warp_px(W, 2 * dx + 1, 2 * dy, p01);
-                    warp_px(W, 2 * dx, 2 * dy + 1, p10);
-                    warp_px(W, 2 * dx + 1, 2 * dy + 1, p11);
+                    warp_px<BAYER>(W, 2 * dx, 2 * dy, p00);
+                    warp_px<BAYER>(W, 2 * dx + 1, 2 * dy, p01);
+                    warp_px<BAYER>(W, 2 * dx, 2 * dy + 1, p10);
+                    warp_px<BAYER>(W, 2 * dx + 1, 2 * dy + 1, p11);
 #pragma unroll
                     for (int c = 0; c < 3; c++) res[c] = (p00[c] + p01[c] + p10[c] + p11[c] + 2) >> 2;
                 } else {
@@ -189,12 +220,12 @@ __device__ inline void classify_frame(int f, int lane, int wave, int nwaves, int
                     sy0 = sy0 < 0 ? 0 : (sy0 > bh - 1 ? bh - 1 : sy0);
                     sy1 = sy1 < 0 ? 0 : (sy1 > bh - 1 ? bh - 1 : sy1);
                     int p00[3], p01[3] = {0, 0, 0}, p10[3], p11[3] = {0, 0, 0};
-                    warp_px(W, sx, sy0, p00);
-                    warp_px(W, sx, sy1, p10);
+                    warp_px<BAYER>(W, sx, sy0, p00);
+                    warp_px<BAYER>(W, sx, sy1, p10);
                     // xmax is the first dx whose right tap falls outside: every later dx is an edge column too
                     if (!edge) {
-                        warp_px(W, sx + 1, sy0, p01);
-                        warp_px(W, sx + 1, sy1, p11);
+                        warp_px<BAYER>(W, sx + 1, sy0, p01);
+                        warp_px<BAYER>(W, sx + 1, sy1, p11);
                     }
 #pragma unroll
                     for (int c = 0; c < 3; c++) {

@@ -73,6 +73,7 @@ struct rmcv_ctx {
     bool mid_failed = false;      // ... could not be allocated: the mid tier is absent for this context
     int sparse_waves = 8;         // RMCV_OPT_SPARSE_WAVES
     int pixel_groups = 3;         // RMCV_OPT_PIXEL_GROUPS
+    int input_format = 0;         // RMCV_OPT_INPUT_FORMAT: 0 BGR, 1..4 a Bayer pattern (a binding records it in Geom::input_format)
     // Waits with a deadline (round 5): no entry point parks its caller in the runtime without a bound.  `last_what` names the kernel or
     // copy enqueued last (every HIPCHK of an enqueue leaves its label here): a wait that runs out returns RMCV_ERR_TIMEOUT with it.
     int wait_timeout_ms = 5000;   // RMCV_OPT_WAIT_TIMEOUT_MS (0: no deadline)
@@ -401,6 +402,7 @@ int ctx_wait_timeout_ms(const rmcv_ctx* c) { return c->wait_timeout_ms; }
 bool pixel_ws_full(const rmcv_ctx* c, int lower_bound) { return binary_ws_full(c->geom, c->bufs, lower_bound); }
 void ctx_defer_phase(rmcv_ctx* c, int phase) { c->geom.dense_defer = phase; }
 void ctx_sparse_lean(rmcv_ctx* c, int on) { c->geom.sparse_lean = on ? 1 : 0; }
+int ctx_input_format(const rmcv_ctx* c) { return c->input_format; }
 int ctx_compact(rmcv_ctx* c, void* d_armours_out, int cap, void* d_frame_offs, void* d_status_or, hipStream_t s, void* hd_record, int host_head)
 {
     HIPCHK(c, launch_compact_armours(c->geom, c->bufs, c->lim, (rmcv_armour*)d_armours_out, cap, (int32_t*)d_frame_offs, s, (int32_t*)d_status_or, (uint8_t*)hd_record, host_head), "k_compact_armours");
@@ -612,9 +614,12 @@ static int set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t
 {
     if (n_frames < 1 || n_frames > c->lim.max_frames) return fail(c, RMCV_ERR_BAD_ARG, "n_frames out of range");
     if (w < 1 || h < 1 || w > c->lim.max_width || h > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, "frame size out of range");
-    if (stride < 3 * w || frame_pitch < (int64_t)stride * (h - 1) + 3 * w) return fail(c, RMCV_ERR_BAD_ARG, "bad stride/pitch");
+    const int bpp = c->input_format ? 1 : 3; // bytes per pixel of what is bound (RMCV_OPT_INPUT_FORMAT)
+    if (c->input_format && (w < 3 || h < 3)) return fail(c, RMCV_ERR_BAD_ARG, "a Bayer frame needs w >= 3 and h >= 3");
+    if (stride < bpp * w || frame_pitch < (int64_t)stride * (h - 1) + bpp * w) return fail(c, RMCV_ERR_BAD_ARG, "bad stride/pitch");
     { const int rcm = ensure_mid(c, n_frames); if (rcm) return rcm; }
     Geom& g = c->geom;
+    g.input_format = c->input_format;
     g.n_frames = n_frames;
     g.w = w;
     g.h = h;
@@ -678,6 +683,7 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
     // every argument check comes BEFORE the first enqueue: an error return leaves the streams as they were
     if ((stages & RMCV_STAGE_IDENTITY) && !b.svm_w) return fail(c, RMCV_ERR_BAD_ARG, "RMCV_STAGE_IDENTITY needs rmcv_svm_load first");
     if ((stages & RMCV_STAGE_POSE) && !b.pnp_cfg) return fail(c, RMCV_ERR_BAD_ARG, "RMCV_STAGE_POSE needs rmcv_pnp_load first");
+    if (lp && g.input_format) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
     if ((rc = order_begin(c, s))) return rc;
     if (c->test_delay_us) { // RMCV_OPT_TEST_DELAY_US: a stand-in for a kernel that does not finish in time (one shot)
         HIPCHK(c, launch_delay((unsigned long long)c->test_delay_us * 1000ull, s), "k_delay (RMCV_OPT_TEST_DELAY_US)");
@@ -696,11 +702,13 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
     static const bool fuse_ok = !(getenv("RMCV_FUSE_SPARSE") && atoi(getenv("RMCV_FUSE_SPARSE")) == 0);
     const bool one_sparse = fuse_ok && !timed && !lp && (stages & RMCV_STAGE_CONTOURS) && (stages & RMCV_STAGE_BLOBS);
     if (stages & RMCV_STAGE_BINARY) {
-        HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, !(stages & RMCV_STAGE_NO_IMAGE), c->pixel_groups, s), "k_binary");
+        HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, !(stages & RMCV_STAGE_NO_IMAGE), c->pixel_groups, s),
+               g.input_format ? "k_binary_bayer" : "k_binary");
     }
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
     // the icon classifier rides in the per-frame kernel when the armours come from it (BASELINE config 5: no launch of its own)
-    const bool identity_fused = one_sparse && (stages & RMCV_STAGE_ARMOURS) && (stages & RMCV_STAGE_IDENTITY);
+    // (not for mosaics: the sparse kernel's classifier reads BGR; k_classify has the Bayer accessor)
+    const bool identity_fused = one_sparse && (stages & RMCV_STAGE_ARMOURS) && (stages & RMCV_STAGE_IDENTITY) && g.input_format == RMCV_INPUT_BGR;
     if (one_sparse) HIPCHK(c, launch_sparse(g, b, c->lim, *p, (stages & RMCV_STAGE_ARMOURS) != 0, identity_fused, c->sparse_waves, s), "k_contours (fused)");
     else if (stages & RMCV_STAGE_CONTOURS) HIPCHK(c, launch_contours(g, b, c->lim, s), "k_contours");
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
@@ -752,8 +760,10 @@ int rmcv_batch_upload(rmcv_ctx* c, const uint8_t* frames, int n_frames, int w, i
     int rc = rmcv_batch_sync(c); // the buffer about to be overwritten may still be read by a batch in flight
     if (rc) return rc;
     resident_none(c);
-    // device layout: tightly packed rows (stride 3*w rounded up to 16 bytes), frames back to back
-    const int dstride = (3 * w + 15) & ~15;
+    // device layout: tightly packed rows (stride 3*w -- w for a mosaic -- rounded up to 16 bytes), frames back to back
+    const int rowb = c->input_format ? w : 3 * w;
+    if (c->input_format && (stride < w || frame_pitch < (int64_t)stride * (h - 1) + w)) return fail(c, RMCV_ERR_BAD_ARG, "bad stride/pitch");
+    const int dstride = (rowb + 15) & ~15;
     const int64_t dpitch = (int64_t)dstride * h;
     rc = set_geom(c, n_frames, w, h, dstride, dpitch);
     if (rc) return rc;
@@ -765,7 +775,7 @@ int rmcv_batch_upload(rmcv_ctx* c, const uint8_t* frames, int n_frames, int w, i
     } else {
         for (int f = 0; f < n_frames; f++)
             HIPCHK(c, hipMemcpy2DAsync(c->own_frames + (size_t)f * dpitch, dstride, frames + (size_t)f * frame_pitch, stride,
-                                       (size_t)3 * w, h, hipMemcpyHostToDevice, c->stream),
+                                       (size_t)rowb, h, hipMemcpyHostToDevice, c->stream),
                    "H2D frames 2D");
     }
     WAITCHK(c, wait_stream(c, c->stream, "H2D frames"));
@@ -816,6 +826,7 @@ int rmcv_batch_run_legacy(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_p
     int rc = check_params(c, p, stages);
     if (rc) return rc;
     if (!lp) return fail(c, RMCV_ERR_BAD_ARG, "null legacy params");
+    if (c->input_format || c->geom.input_format) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
     hipSetDevice(c->device);
     return run_stages(c, p, stages, hip_stream ? (hipStream_t)hip_stream : c->stream, false, lp);
 }
@@ -876,6 +887,10 @@ int rmcv_ctx_set_option(rmcv_ctx* c, int option, int value)
     }
     if (option == RMCV_OPT_TEST_DELAY_US && value >= 0 && value <= 10000000) {
         c->test_delay_us = value;
+        return RMCV_OK;
+    }
+    if (option == RMCV_OPT_INPUT_FORMAT && value >= RMCV_INPUT_BGR && value <= RMCV_BAYER_BG) {
+        c->input_format = value; // (frames bound before keep the format they were bound with)
         return RMCV_OK;
     }
     if (option == RMCV_OPT_PIXEL_GROUPS && value >= 1 && value <= 8) {
@@ -1178,15 +1193,16 @@ int rmcv_classify_armours(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int str
  * resident buffers instead of uploading them again. */
 static constexpr int SF_OFFS_WIN = 1024, SF_PTS_WIN = 8192, SF_BLOB_WIN = 64, SF_NEG_WIN = 1024, SF_ARM_WIN = 32;
 
-// bring one BGR frame into own_frames (frame slot 0) on the context's stream; RMCV_OPT_FRAME_UPLOAD selects how
-static int upload_one(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, int dstride)
+// bring one frame (BGR, or a mosaic: rowb = 3 w or w bytes per row) into own_frames (frame slot 0) on the context's stream;
+// RMCV_OPT_FRAME_UPLOAD selects how
+static int upload_one(rmcv_ctx* c, const uint8_t* bgr, int rowb, int h, int stride, int dstride)
 {
     const size_t dpitch = (size_t)dstride * h;
     hipStream_t s = c->stream;
     const int mode = c->frame_upload == 3 ? (c->hold_upload > 0 ? 1 : 0) : c->frame_upload;
     c->upload_now = mode;
     if (mode == 2) { // pin the caller's buffer once (camera SDKs hand out a small ring of frame buffers) and DMA from it
-        const size_t span = (size_t)stride * (h - 1) + (size_t)3 * w;
+        const size_t span = (size_t)stride * (h - 1) + (size_t)rowb;
         bool known = false;
         for (auto& r : c->registered) known |= (r.p == bgr && r.bytes >= span);
         if (!known) {
@@ -1201,11 +1217,11 @@ static int upload_one(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride,
                 (void)hipGetLastError(); // e.g. already registered by the application: plain copy below
             }
         }
-        HIPCHK(c, hipMemcpy2DAsync(c->own_frames, dstride, bgr, stride, (size_t)3 * w, h, hipMemcpyHostToDevice, s), "H2D frame");
+        HIPCHK(c, hipMemcpy2DAsync(c->own_frames, dstride, bgr, stride, (size_t)rowb, h, hipMemcpyHostToDevice, s), "H2D frame");
         return RMCV_OK;
     }
     if (mode == 0) { // the runtime's own pageable path
-        HIPCHK(c, hipMemcpy2DAsync(c->own_frames, dstride, bgr, stride, (size_t)3 * w, h, hipMemcpyHostToDevice, s), "H2D frame");
+        HIPCHK(c, hipMemcpy2DAsync(c->own_frames, dstride, bgr, stride, (size_t)rowb, h, hipMemcpyHostToDevice, s), "H2D frame");
         return RMCV_OK;
     }
     if (dpitch > c->h_frame_bytes) {
@@ -1225,7 +1241,7 @@ static int upload_one(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride,
         if (y1 <= y0) continue;
         if (stride == dstride) memcpy(c->h_frame + (size_t)y0 * dstride, bgr + (size_t)y0 * stride, (size_t)(y1 - y0) * dstride);
         else
-            for (int y = y0; y < y1; y++) memcpy(c->h_frame + (size_t)y * dstride, bgr + (size_t)y * stride, (size_t)3 * w);
+            for (int y = y0; y < y1; y++) memcpy(c->h_frame + (size_t)y * dstride, bgr + (size_t)y * stride, (size_t)rowb);
         HIPCHK(c, hipMemcpyAsync(c->own_frames + (size_t)y0 * dstride, c->h_frame + (size_t)y0 * dstride, (size_t)(y1 - y0) * dstride,
                                  hipMemcpyHostToDevice, s), "H2D frame");
     }
@@ -1391,11 +1407,12 @@ static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int
     if (rc) return rc;
     resident_none(c);
     if ((rc = ensure_staging(c))) return rc;
-    const int dstride = (3 * w + 15) & ~15;
+    const int rowb = c->input_format ? w : 3 * w; // a mosaic (RMCV_OPT_INPUT_FORMAT): one byte per pixel
+    const int dstride = (rowb + 15) & ~15;
     if ((rc = set_geom(c, 1, w, h, dstride, (int64_t)dstride * h))) return rc;
-    if (stride < 3 * w) return fail(c, RMCV_ERR_BAD_ARG, "bad stride");
+    if (stride < rowb) return fail(c, RMCV_ERR_BAD_ARG, "bad stride");
     if ((rc = ensure_own_frames(c, (size_t)dstride * h))) return rc;
-    if ((rc = upload_one(c, bgr, w, h, stride, dstride))) return rc;
+    if ((rc = upload_one(c, bgr, rowb, h, stride, dstride))) return rc;
     c->marks[1] = now_us(); // the upload is enqueued (pageable: the runtime may have copied it by now)
     c->bufs.frames = c->own_frames;
     const Geom& g = c->geom;
@@ -1405,7 +1422,7 @@ static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int
         HIPCHK(c, launch_delay((unsigned long long)c->test_delay_us * 1000ull, s), "k_delay (RMCV_OPT_TEST_DELAY_US)");
         c->test_delay_us = 0;
     }
-    HIPCHK(c, launch_binary(g, b, camp, lower_bound, morph, binary_out != nullptr, c->pixel_groups, s), "k_binary");
+    HIPCHK(c, launch_binary(g, b, camp, lower_bound, morph, binary_out != nullptr, c->pixel_groups, s), g.input_format ? "k_binary_bayer" : "k_binary");
     if (binary_out) HIPCHK(c, hipEventRecord(c->ev_fork, s), "image download: mark");
     // running ahead with both parameter sets known: the frame's whole sparse part is ONE kernel (the fused per-frame kernel of
     // the batch path: findContours, fits and pairing back to back), not three
@@ -1532,7 +1549,8 @@ static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int
     c->marks[7] = now_us();
     if (binary_out) { // what the runtime's copies cost this frame (see rmcv_ctx::image_export)
         const double up_us = c->marks[3] - c->marks[1] + c->test_slow_us, img_us = c->marks[4] - c->marks[3] + c->test_slow_us;
-        const double frame_bytes = 3.0 * w * h, image_bytes = (double)w * h;
+        // (the upload moves what the frame holds: 3 B/px of BGR, 1 B/px of a mosaic -- RMCV_OPT_INPUT_FORMAT)
+        const double frame_bytes = (c->geom.input_format ? 1.0 : 3.0) * w * h, image_bytes = (double)w * h;
         if (c->upload_now == 0) {
             c->slow_upload = up_us > frame_bytes / 45e3 + 100.0 ? c->slow_upload + 1 : 0; // (45 GB/s + the pixel kernel + the waits' slack)
             if (c->frame_upload == 3 && c->slow_upload >= 3) { c->hold_upload = 512; c->slow_upload = 0; }
@@ -1884,11 +1902,42 @@ int rmcv_match_lightblob(rmcv_ctx* c, const rmcv_point* pts, int n, const rmcv_l
     return match_one(c, pts, n, *lp, 0, box_out, matched);
 }
 
+int rmcv_demosaic(rmcv_ctx* c, const uint8_t* raw, int w, int h, int stride, int pattern, uint8_t* bgr_out, int out_stride)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!raw || !bgr_out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: null buffer");
+    if (w < 3 || h < 3) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: a mosaic needs w >= 3 and h >= 3");
+    if (stride < w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: stride < w");
+    if (out_stride < 3 * w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: out_stride < 3 w");
+    if (pattern < RMCV_BAYER_RG || pattern > RMCV_BAYER_BG) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: unknown Bayer pattern");
+    hipSetDevice(c->device);
+    int rc = rmcv_batch_sync(c);
+    if (rc) return rc;
+    // (a stage-wise helper: buffers of its own, so that nothing bound to the context moves)
+    uint8_t *d_raw = nullptr, *d_out = nullptr;
+    const size_t in_bytes = (size_t)w * h, out_bytes = (size_t)3 * w * h;
+    hipError_t e = hipMalloc((void**)&d_raw, in_bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&d_out, out_bytes);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(d_raw, w, raw, stride, w, h, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_demosaic(d_raw, w, w, h, pattern, d_out, 3 * w, c->stream);
+    c->last_what = "k_demosaic";
+    int rcw = 0;
+    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_demosaic");
+    if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(bgr_out, out_stride, d_out, 3 * w, 3 * w, h, hipMemcpyDeviceToHost);
+    if (rcw == 0 || e != hipSuccess) { // (after a wait that ran out the kernel may still be using them)
+        if (d_raw) hipFree(d_raw);
+        if (d_out) hipFree(d_out);
+    }
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_demosaic", e);
+    return rcw;
+}
+
 int rmcv_find_lightblobs(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, const rmcv_point* pts, const int32_t* offs,
                          int n_contours, const rmcv_legacy_params* lp, rmcv_lightblob* blobs_out, int blobs_cap, int32_t* n_blobs,
                          int32_t* blob_src, rmcv_rrect* boxes_out)
 {
     if (!c || !bgr || !lp || (n_contours > 0 && (!pts || !offs))) return RMCV_ERR_BAD_ARG;
+    if (c->input_format) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
     hipSetDevice(c->device);
     int rc = rmcv_batch_upload(c, bgr, 1, w, h, stride, (int64_t)stride * h); // source.channels() == 3 is the ABI's only format
     if (rc) return rc;

@@ -25,10 +25,11 @@ struct Geom {
     int overloads;       // RMCV_OPT_OVERLOADS: SURVEY A.6, which functions the reference's unqualified abs / atan2 / sin / cos on floats are
     int sparse_lean;     // a pipeline's dense mode: the batch's sparse stage runs the lean build (k_contours_lean.hip), every frame on the mid tier
     int contour_tier;    // RMCV_OPT_CONTOUR_TIER: 0 = per frame (LDS tables, else mid tier, else literal scanner), 1 = literal, 2 = mid tier
+    int input_format;    // RMCV_OPT_INPUT_FORMAT of the frames bound: 0 BGR, 1..4 a Bayer pattern (recorded when the frames are bound)
     int n_frames;
     int w, h;
-    int stride;          // bytes between rows of the BGR input
-    int64_t frame_pitch; // bytes between frames of the BGR input
+    int stride;          // bytes between rows of the input (BGR or mosaic)
+    int64_t frame_pitch; // bytes between frames of the input
     int ww;              // words per row = ceil(w / 64)
     int prow;            // padded words per row = ww + 2
     int64_t plane_pitch; // words per frame = (h + 2) * prow
@@ -140,6 +141,10 @@ hipError_t launch_sparse(const Geom& g, const Bufs& b, const Limits& lim, const 
 hipError_t launch_pnp(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s);
 hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, int groups, hipStream_t s);
 bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound); // the batch will run as one launch of k_binary_ws with a workgroup on every CU
+// the pixel stage of a Bayer batch (Geom::input_format != 0; k_binary_bayer.hip); launch_binary hands such batches to it
+hipError_t launch_binary_bayer(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, hipStream_t s);
+// D(m) of one device mosaic into a device BGR frame (rmcv_demosaic)
+hipError_t launch_demosaic(const uint8_t* d_raw, int stride, int w, int h, int pattern, uint8_t* d_out, int out_stride, hipStream_t s);
 bool sparse_lean_applies(const Geom& g, const Bufs& b); // Geom::sparse_lean can be honoured for what is bound (k_contours.hip)
 hipError_t launch_contours(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s);
 hipError_t launch_blobs(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, hipStream_t s);
@@ -204,5 +209,7 @@ int ctx_check_stages(rmcv_ctx* c, const rmcv_params* p, int stages);
 void ctx_defer_phase(rmcv_ctx* c, int phase);
 // Geom::sparse_lean for the runs that follow
 void ctx_sparse_lean(rmcv_ctx* c, int on);
+// RMCV_OPT_INPUT_FORMAT as set on the context (what the next binding records)
+int ctx_input_format(const rmcv_ctx* c);
 
 } // namespace rmcv

@@ -619,6 +619,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     const bool fast = pl->hot && pl->calm && !lp && !(stages & RMCV_STAGE_POSE) && (pl->hot_identity || !(stages & RMCV_STAGE_IDENTITY));
     const size_t j = fast ? (size_t)(pl->hot_seq % (uint64_t)pl->hot) : k;
     rmcv_ctx* c = pl->ring[j];
+    if (lp && ctx_input_format(c)) return pfail(pl, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
     hipStream_t A = pl->pix[(size_t)(t % (uint64_t)pl->cfg.pixel_streams)], B = pl->sp[k % (size_t)pl->cfg.sparse_streams];
     int rc;
     // ---- waits first: stream A is behind everything that still uses the slot and the context when the binding below enqueues on it.
@@ -677,7 +678,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     rc = rmcv_batch_run(c, p, pixel, A);
     if (heavy && pl->heavy_pixel_groups > 0) rmcv_ctx_set_option(c, RMCV_OPT_PIXEL_GROUPS, pl->cfg.pixel_groups);
     if (rc) return cfail(pl, c, rc);
-    pl->last_what = "the pixel kernel (k_binary / k_binary_ws)";
+    pl->last_what = ctx_input_format(c) ? "the pixel kernel (k_binary_bayer)" : "the pixel kernel (k_binary / k_binary_ws)";
     // ---- accepted: the pipeline's state moves
     pl->was_cold = cold;
     if (fast) { pl->hot_seq++; pl->hot_batches++; }

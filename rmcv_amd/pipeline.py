@@ -16,7 +16,7 @@ from .api import Context
 
 class Pipeline:
     def __init__(self, device=0, depth=0, pixel_streams=0, sparse_streams=0, armour_cap=0, sparse_waves=0, pixel_groups=0,
-                 host_results=0, dense_streams=0, hot_contexts=0, **limits):
+                 host_results=0, dense_streams=0, hot_contexts=0, input_format=0, **limits):
         lim = Limits()
         lib().rmcv_default_limits(C.byref(lim))
         for k, v in limits.items():
@@ -36,6 +36,10 @@ class Pipeline:
         self._ticket = C.c_uint64(0)
         self._params = default_params()
         self.contexts = [Context.borrowed(self._lib.rmcv_pipeline_context(self._h, k), lim, device) for k in range(self.depth)]
+        self.input_format = int(input_format)
+        if self.input_format:  # RMCV_OPT_INPUT_FORMAT on every slot: each batch reads its own context's option
+            for c in self.contexts:
+                c.set_input_format(self.input_format)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -64,7 +68,7 @@ class Pipeline:
         """enqueue one batch of frames resident in HBM (data_ptr: e.g. torch_tensor.data_ptr()); returns the ticket"""
         if params is not None:
             self._params = params
-        stride = stride or 3 * w
+        stride = stride or (w if self.input_format else 3 * w)
         frame_pitch = frame_pitch or stride * h
         if legacy is not None:
             rc = self._lib.rmcv_pipeline_submit_legacy(self._h, data_ptr, n, w, h, stride, frame_pitch, C.addressof(self._params), C.addressof(legacy),

@@ -25,6 +25,23 @@ def batch(first, n, w=1280, h=1024, camp=CAMP_BLUE, variant=0, threads=8):
     return out
 
 
+def mosaic(bgr, pattern):
+    """the colour filter array of `pattern` (abi.BAYER_RG .. BAYER_BG: the top-left 2x2 block) sampled from synthetic BGR frames
+    [..., h, w, 3] -> raw 8-bit mosaics [..., h, w]: each pixel keeps the one channel its filter passes"""
+    from .abi import BAYER_BG, BAYER_GB, BAYER_GR, BAYER_RG
+    if pattern not in (BAYER_RG, BAYER_GB, BAYER_GR, BAYER_BG):
+        raise ValueError("unknown Bayer pattern %r" % (pattern,))
+    bgr = np.asarray(bgr, np.uint8)
+    rx = 1 if pattern in (BAYER_GR, BAYER_BG) else 0  # the R site of the 2x2 block
+    ry = 1 if pattern in (BAYER_GB, BAYER_BG) else 0
+    h, w = bgr.shape[-3], bgr.shape[-2]
+    x = np.arange(w)[None, :]
+    y = np.arange(h)[:, None]
+    px, py = (x ^ rx) & 1, (y ^ ry) & 1
+    ch = np.where((px == 0) & (py == 0), 2, np.where((px == 1) & (py == 1), 0, 1))  # R site, B site, else G (BGR channel index)
+    return np.take_along_axis(bgr, np.broadcast_to(ch[..., None], bgr.shape[:-1] + (1,)), axis=-1)[..., 0].copy()
+
+
 def checksum(img):
     h, w, _ = img.shape
     img = np.ascontiguousarray(img)
