@@ -544,7 +544,7 @@ static std::atomic<int64_t> g_ws_launches{0};
 int64_t pixel_ws_launches() { return g_ws_launches.load(std::memory_order_relaxed); }
 
 template <int CA, int CB>
-static hipError_t launch_binary_t(const Geom& g, const Bufs& b, int lower_bound, int morph, bool image, int groups,
+static hipError_t launch_binary_t(const Geom& g, const Bufs& b, int lower_bound, int morph, bool image, const RunPlan& plan,
                                   hipStream_t s)
 {
     const int strips = (g.h + SR - 1) / SR;
@@ -560,13 +560,11 @@ static hipError_t launch_binary_t(const Geom& g, const Bufs& b, int lower_bound,
     const int64_t per_frame = std::max<int64_t>(std::max<int64_t>(g.frame_pitch, g.plane_pitch * 8), (int64_t)g.w * g.h);
     const int chunk = aligned ? (int)std::min<int64_t>(g.n_frames, std::max<int64_t>(1, (lim - 1) / per_frame)) : g.n_frames;
     const bool fast = aligned && (int64_t)chunk * per_frame < lim;
-    // rows contiguous in memory: the linear loader (Geom::pixel_rowquad, from RMCV_K1_LINEAR=0 when the context is made: the row-quad
-    // loader everywhere -- a dev knob for A/B runs)
+    // rows contiguous in memory: the linear loader (Geom::pixel_rowquad, hidden option 1001: the row-quad loader everywhere -- for A/B runs)
     const bool linear = fast && !g.pixel_rowquad && g.stride == 3 * g.w;
-    // persistent grid: `groups` workgroups per CU (RMCV_OPT_PIXEL_GROUPS; RMCV_K1_BPC overrides for A/B runs): alone the kernel is
-    // equally fast with 2 and 3 and slower with 4 and more; 2 leaves room on every CU for the kernels of the other batches in flight
-    static const int bpc_env = getenv("RMCV_K1_BPC") ? atoi(getenv("RMCV_K1_BPC")) : 0;
-    const int bpc = bpc_env > 0 ? bpc_env : groups;
+    // persistent grid: RMCV_OPT_PIXEL_GROUPS workgroups per CU: alone the kernel is equally fast with 2 and 3 and slower with 4 and
+    // more; 2 leaves room on every CU for the kernels of the other batches in flight
+    const int bpc = plan.pixel_groups;
     for (int f0 = 0; f0 < g.n_frames; f0 += chunk) {
         const int nf = std::min(chunk, g.n_frames - f0);
         const int n_blocks = nf * strips;
@@ -600,7 +598,7 @@ static hipError_t launch_binary_t(const Geom& g, const Bufs& b, int lower_bound,
         // the wave-specialised kernel, ONE 1024-thread workgroup per CU -- 8 loader wavefronts with 2 items (8 loads) in flight each, 8 storers
         constexpr int WS_NL = 8, WS_NS = 8, WS_RING = 2, WS_AUX = 2 /* nt */;
         const size_t planes_ws = ((size_t)2 * (SR + 4) + SR) * g.ww * sizeof(uint64_t);
-        if (g.pixel_ws && linear && !all_pass && taper_head == 0 && planes_ws <= 60 * 1024) {
+        if (plan.pixel_ws && linear && !all_pass && taper_head == 0 && planes_ws <= 60 * 1024) {
             K1Args ka;
             ka.frames = frames; ka.frame_pitch = g.frame_pitch; ka.stride = g.stride; ka.n_frames = nf; ka.w = g.w; ka.h = g.h; ka.ww = g.ww;
             ka.lb = lb; ka.morph = morph; ka.binary = binary; ka.bits = bits; ka.prow = g.prow; ka.plane_pitch = g.plane_pitch;
@@ -629,7 +627,7 @@ static hipError_t launch_binary_t(const Geom& g, const Bufs& b, int lower_bound,
 
 // launch_binary_t's own rule, for the pipeline's hold-back of a burst's second launch: will the batch bound to (g, b) run as ONE launch of
 // k_binary_ws with a workgroup on every CU?
-bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound)
+bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound, int pixel_ws)
 {
     const int strips = (g.h + SR - 1) / SR;
     const bool aligned = (g.w % 64 == 0) && (g.stride % 16 == 0) && (g.frame_pitch % 16 == 0) && ((uintptr_t)b.frames % 16 == 0);
@@ -639,17 +637,17 @@ bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound)
     const bool linear = one_launch && !g.pixel_rowquad && g.stride == 3 * g.w;
     const int n_cu = g.n_cu > 0 ? g.n_cu : 256, n_blocks = g.n_frames * strips;
     const size_t planes_ws = ((size_t)2 * (SR + 4) + SR) * g.ww * sizeof(uint64_t);
-    return g.input_format == RMCV_INPUT_BGR && g.pixel_ws && linear && lower_bound > 0 && n_blocks * 2 > n_cu && planes_ws <= 60 * 1024 && n_blocks >= n_cu;
+    return g.input_format == RMCV_INPUT_BGR && pixel_ws && linear && lower_bound > 0 && n_blocks * 2 > n_cu && planes_ws <= 60 * 1024 && n_blocks >= n_cu;
 }
 
-hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, int groups, hipStream_t s)
+hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s)
 {
     // a Bayer mosaic (RMCV_OPT_INPUT_FORMAT): its own kernel, never k_binary_ws (k_binary_bayer.hip)
     if (g.input_format != RMCV_INPUT_BGR) return launch_binary_bayer(g, b, camp, lower_bound, morph, image, s);
     // imgproc.cpp:56-65: GUIDELIGHT G-R; BLUE B-R; everything else (RED, NEUTRAL) R-B.  BGR byte order.
-    if (camp == RMCV_CAMP_GUIDELIGHT) return launch_binary_t<1, 2>(g, b, lower_bound, morph, image, groups, s);
-    if (camp == RMCV_CAMP_BLUE) return launch_binary_t<0, 2>(g, b, lower_bound, morph, image, groups, s);
-    return launch_binary_t<2, 0>(g, b, lower_bound, morph, image, groups, s);
+    if (camp == RMCV_CAMP_GUIDELIGHT) return launch_binary_t<1, 2>(g, b, lower_bound, morph, image, plan, s);
+    if (camp == RMCV_CAMP_BLUE) return launch_binary_t<0, 2>(g, b, lower_bound, morph, image, plan, s);
+    return launch_binary_t<2, 0>(g, b, lower_bound, morph, image, plan, s);
 }
 
 // binary (0 / non-zero bytes) -> padded bit plane; used when a caller hands in its own binary image

@@ -38,19 +38,9 @@ namespace rmcv {
 
 static_assert(sizeof(ContoursLds) >= (CT_THREADS_MAX / 64) * sizeof(WaveLds), "the fit rows reuse the contour tables");
 
-// Geom::sparse_lean (a pipeline's dense mode) can be honoured: the mid tier applies to every frame (its scratch is there, the row tables
-// cover the frame).
-bool sparse_lean_applies(const Geom& g, const Bufs& b)
+static hipError_t launch_contours_w8(const Geom& g, const Bufs& b, const Limits& lim, const SparseTail& X, int flags, const SparseSched& Q, int grid,
+                                     SparseLds lds, hipStream_t s)
 {
-    return g.sparse_lean && !g.dense_defer && g.contour_tier == 0 && b.mid && g.h <= CT_MAXH && g.ww <= 32;
-}
-
-static hipError_t launch_contours_x(const Geom& g, const Bufs& b, const Limits& lim, const SparseTail& X, int waves, hipStream_t s)
-{
-    SparseSched Q;
-    Q.order = b.frame_order;
-    const int grid = g.n_frames;
-    static const int force_literal = getenv("RMCV_CONTOURS_LITERAL") ? atoi(getenv("RMCV_CONTOURS_LITERAL")) : 0; // dev/test knob
     static bool attr_set[MAX_DEVICES] = {}; // hipFuncSetAttribute applies to the current device only (a process may drive several)
     if (!attr_set[g.device]) {
         hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(k_contours_w8), hipFuncAttributeMaxDynamicSharedMemorySize,
@@ -58,43 +48,41 @@ static hipError_t launch_contours_x(const Geom& g, const Bufs& b, const Limits& 
         if (e != hipSuccess) return e;
         attr_set[g.device] = true;
     }
-    const int force = force_literal ? force_literal : g.contour_tier;
-    // a pipeline's dense mode: the whole batch through the lean build (every frame on the mid tier, 61 KB of LDS: two workgroups per CU);
-    // not with a classifier stage (the lean build has no room for its feature rows)
-    if (waves == 4 && X.fused && !X.C.enabled && sparse_lean_applies(g, b) && force == 0) return launch_contours_lean(g, b, lim, X, 2, Q, grid, s);
-    if (waves == 4) {
-        // RMCV_OPT_DENSE_DEFER (off by default): the 4-wavefront launch leaves the frames beyond its LDS tables alone and the
-        // 8-wavefront kernel takes them in a launch of its own right behind (1.4-1.5x faster per frame; a workgroup of any other
-        // frame reads one word and ends).  Pays where every frame is dense, costs where a few are: DESIGN.md 5c.
-        // g.dense_defer: 1 = both launches here, on this stream; 2 / 3 = the first / the second launch only (rmcv_pipeline.hip puts the
-        // second on a stream of its own, so that a batch's few dense frames do not hold up the sparse stream)
-        const bool defer = g.dense_defer && (force & 3) == 0 && b.mid;
-        if (g.dense_defer == 3 && !defer) return hipSuccess; // (nothing was deferred: the first launch finished every frame)
-        hipError_t e = g.dense_defer == 3 ? hipSuccess : launch_contours_w4(g, b, lim, X, force | (defer ? 4 : 0), Q, grid, s);
-        if (e != hipSuccess || !defer || g.dense_defer == 2) return e;
-        const SparseSched& Q2 = Q;
-        static const bool second_w4 = getenv("RMCV_DEFER_W4") && atoi(getenv("RMCV_DEFER_W4")); // dev knob: the second launch with 4 wavefronts per frame too
-        if (second_w4) return launch_contours_w4(g, b, lim, X, 2 | 8, Q2, grid, s);
-        return launch(k_contours_w8, dim3(grid), dim3(512), lds_bytes(g.h), s, b.bits, b.rowmask, g.h, b.lab, b.neg, g.w,
+    return launch(k_contours_w8, dim3(grid), dim3(512), sparse_lds(lds, lds_bytes(g.h)), s, b.bits, b.rowmask, g.h, b.lab, b.neg, g.w,
                        g.h, g.ww, g.prow, g.plane_pitch, b.points, b.cont_start, b.cont_len, b.n_contours, b.n_points, b.status,
-                       lim.max_contours, lim.max_points, 2 | 8, b.elig, b.n_elig, b.slot_kind, X, b.visit_xy, b.mid, b.mid_stride,
-                       b.mid_slot_cap, Q2, lds_rows_cap(g.h));
-    }
-    return launch(k_contours_w8, dim3(grid), dim3(512), lds_bytes(g.h), s, b.bits, b.rowmask, g.h, b.lab, b.neg, g.w,
-                       g.h, g.ww, g.prow, g.plane_pitch, b.points, b.cont_start, b.cont_len, b.n_contours, b.n_points, b.status,
-                       lim.max_contours, lim.max_points, force, b.elig, b.n_elig, b.slot_kind, X, b.visit_xy, b.mid, b.mid_stride,
+                       lim.max_contours, lim.max_points, flags, b.elig, b.n_elig, b.slot_kind, X, b.visit_xy, b.mid, b.mid_stride,
                        b.mid_slot_cap, Q, lds_rows_cap(g.h));
+}
+
+// the launches resolve_sparse (sparse_plan.h) decides for this run: the 8- or 4-wavefront build, the lean build of a pipeline's dense mode,
+// or a split batch's two launches
+static hipError_t launch_contours_x(const Geom& g, const Bufs& b, const Limits& lim, const SparseTail& X, const RunPlan& plan, hipStream_t s,
+                                    bool* lean)
+{
+    SparseSched Q;
+    Q.order = b.frame_order;
+    const SparseLaunches L = resolve_sparse({plan.form, plan.sparse_waves, X.fused != 0, X.C.enabled != 0, g.contour_tier, b.mid != nullptr,
+                                             g.h <= CT_MAXH && g.ww <= 32, plan.pixel_ws != 0});
+    if (lean) *lean = L.n == 1 && L.l[0].kernel == SPARSE_W_LEAN;
+    for (int i = 0; i < L.n; i++) {
+        const SparseLaunch& l = L.l[i];
+        const hipError_t e = (l.kernel == SPARSE_W8 ? launch_contours_w8 : l.kernel == SPARSE_W4 ? launch_contours_w4 : launch_contours_lean)(
+            g, b, lim, X, l.flags, Q, g.n_frames, l.lds, s);
+        if (e != hipSuccess) return e;
+    }
+    return hipSuccess;
 }
 
 hipError_t launch_contours(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s)
 {
     SparseTail X;
     memset(&X, 0, sizeof(X));
-    return launch_contours_x(g, b, lim, X, 8, s);
+    return launch_contours_x(g, b, lim, X, RunPlan{0, 0, 8, SPARSE_STANDARD}, s, nullptr);
 }
 
 // findContours + filter_lightblobs (+ filter_armours) of every frame in ONE launch
-hipError_t launch_sparse(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, bool pairs, bool identity, int waves, hipStream_t s)
+hipError_t launch_sparse(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, bool pairs, bool identity, const RunPlan& plan,
+                         hipStream_t s, bool* lean)
 {
     SparseTail X;
     memset(&X, 0, sizeof(X));
@@ -120,7 +108,7 @@ hipError_t launch_sparse(const Geom& g, const Bufs& b, const Limits& lim, const 
     T.length_ratio_max = p.length_ratio_max;
     T.ov = g.overloads;
     if (identity && pairs) X.C = classify_args(g, b);
-    return launch_contours_x(g, b, lim, X, waves, s);
+    return launch_contours_x(g, b, lim, X, plan, s, lean);
 }
 
 // see ExportArgs (rmcv_internal.h): the lists and header words, by `nthreads` threads of which this is number `gtid`

@@ -10,7 +10,7 @@
 // (which the fused tail's wave-private rows overlay afterwards) and a work list.  The pipeline switches a stream to this kernel
 // while the records that come back say the batches are heavy
 // (rmcv_pipeline.hip: dense mode).  Same results: the mid tier is the same formulation as the LDS tier, bit for bit (tests/test_gpu_dense.py).
-// Measured (round 5, tools/dense_mode_ab.sh, ms per step off / on): dense2 0.320 / 0.291, dense3 0.396 / 0.372, dense4 0.571 / 0.512 (with
+// Measured (round 5, profiles/r05_dense_mode_ab.txt, ms per step off / on): dense2 0.320 / 0.291, dense3 0.396 / 0.372, dense4 0.571 / 0.512 (with
 // the pixel kernel's two workgroups per CU and launch; with one -- room for two of these per CU -- 0.314 / 0.368 / 0.504).  Tried and not kept: the same
 // build WITHOUT the fused tail (114 VGPRs, 6 spilled SGPRs instead of 155 / 292 -- the fits are what the registers go to) with k_fit
 // and k_pairs as launches of their own behind it: dense4 0.545 (rocprofv3: k_contours_lean 1.05 ms, k_fit 0.73 ms, k_pairs 0.08 ms per
@@ -44,7 +44,8 @@ namespace rmcv {
 static_assert(sizeof(ContoursLds) <= 54 * 1024, "two of these workgroups and two pixel workgroups share a CU's 160 KB");
 
 // every frame on the mid tier (`flags`: 2, + 8 = only the frames the first launch marked as deferred)
-hipError_t launch_contours_lean(const Geom& g, const Bufs& b, const Limits& lim, const SparseTail& X, int flags, const SparseSched& Q, int grid, hipStream_t s)
+hipError_t launch_contours_lean(const Geom& g, const Bufs& b, const Limits& lim, const SparseTail& X, int flags, const SparseSched& Q, int grid, SparseLds lds,
+                                hipStream_t s)
 {
     static bool attr_set[MAX_DEVICES] = {}; // hipFuncSetAttribute applies to the current device only (a process may drive several)
     if (!attr_set[g.device]) {
@@ -52,7 +53,7 @@ hipError_t launch_contours_lean(const Geom& g, const Bufs& b, const Limits& lim,
         if (e != hipSuccess) return e;
         attr_set[g.device] = true;
     }
-    return launch(k_contours_lean, dim3(grid), dim3(256), lds_bytes(g.h), s, b.bits, b.rowmask, g.h, b.lab, b.neg, g.w,
+    return launch(k_contours_lean, dim3(grid), dim3(256), sparse_lds(lds, lds_bytes(g.h)), s, b.bits, b.rowmask, g.h, b.lab, b.neg, g.w,
                   g.h, g.ww, g.prow, g.plane_pitch, b.points, b.cont_start, b.cont_len, b.n_contours, b.n_points, b.status,
                   lim.max_contours, lim.max_points, flags, b.elig, b.n_elig, b.slot_kind, X, b.visit_xy, b.mid, b.mid_stride,
                   b.mid_slot_cap, Q, lds_rows_cap(g.h));

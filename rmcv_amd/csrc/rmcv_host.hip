@@ -73,6 +73,8 @@ struct rmcv_ctx {
     bool mid_failed = false;      // ... could not be allocated: the mid tier is absent for this context
     int sparse_waves = 8;         // RMCV_OPT_SPARSE_WAVES
     int pixel_groups = 3;         // RMCV_OPT_PIXEL_GROUPS
+    int pixel_shape = 1;          // RMCV_OPT_PIXEL_SHAPE
+    int dense_defer = 0;          // RMCV_OPT_DENSE_DEFER
     int input_format = 0;         // RMCV_OPT_INPUT_FORMAT: 0 BGR, 1..4 a Bayer pattern (a binding records it in Geom::input_format)
     // Waits with a deadline (round 5): no entry point parks its caller in the runtime without a bound.  `last_what` names the kernel or
     // copy enqueued last (every HIPCHK of an enqueue leaves its label here): a wait that runs out returns RMCV_ERR_TIMEOUT with it.
@@ -165,13 +167,6 @@ static int wait_failed(rmcv_ctx* c, int rcw, const char* what, hipError_t e)
 static int wait_stream(rmcv_ctx* c, hipStream_t s, const char* what)
 {
     hipError_t e = hipSuccess;
-#ifdef RMCV_DEV_KNOBS // A/B against the runtime's own wait (round 4's): make EXTRA=-DRMCV_DEV_KNOBS, RMCV_WAIT_RUNTIME=1
-    static const bool runtime_wait = getenv("RMCV_WAIT_RUNTIME") && atoi(getenv("RMCV_WAIT_RUNTIME"));
-    if (runtime_wait) {
-        e = hipStreamSynchronize(s);
-        return e == hipSuccess ? RMCV_OK : fail(c, RMCV_ERR_HIP, what, e);
-    }
-#endif
     const int rcw = wait_stream_deadline(s, c->wait_timeout_ms, &e);
     if (rcw) return wait_failed(c, rcw, what, e);
     return RMCV_OK;
@@ -207,8 +202,6 @@ static hipError_t dalloc_named(rmcv_ctx* c, T** p, size_t count, const char* nam
         c->allocs.push_back(q);
         c->guarded.push_back({(uint8_t*)q, bytes, name});
         *p = (T*)((uint8_t*)q + GUARD);
-        static const bool trace_alloc = getenv("RMCV_TRACE_ALLOC") && atoi(getenv("RMCV_TRACE_ALLOC")); // dev knob (tools/placement_probe.py)
-        if (trace_alloc && bytes >= (1u << 20)) fprintf(stderr, "[alloc] ctx %p %-14s %p %zu\n", (void*)c, name, (void*)*p, bytes);
         e = hipMemset(q, GUARD_BYTE, GUARD);
         // the rounding slack behind the payload belongs to the rear zone
         if (e == hipSuccess) e = hipMemset((uint8_t*)q + GUARD + count * sizeof(T), GUARD_BYTE, bytes - count * sizeof(T) + GUARD);
@@ -322,12 +315,8 @@ int rmcv_ctx_create(int device, const rmcv_limits* limits, rmcv_ctx** out)
     if (e == hipSuccess) {
         hipDeviceProp_t prop;
         c->geom.device = device;
-        c->geom.pixel_halo_nt = getenv("RMCV_K1_HALO_NT") ? atoi(getenv("RMCV_K1_HALO_NT")) : 0;
-        c->geom.pixel_rowquad = getenv("RMCV_K1_LINEAR") && atoi(getenv("RMCV_K1_LINEAR")) == 0;
         if (getenv("RMCV_IMAGE_EXPORT")) c->image_export = atoi(getenv("RMCV_IMAGE_EXPORT")); // (the options' defaults for hosts that cannot call them: tools/frame_chain.c)
         if (getenv("RMCV_FRAME_UPLOAD")) c->frame_upload = atoi(getenv("RMCV_FRAME_UPLOAD"));
-        c->geom.pixel_ws = 1; // RMCV_OPT_PIXEL_SHAPE: whole batches with contiguous rows -> k_binary_ws
-        c->geom.dense_defer = getenv("RMCV_DENSE_DEFER") ? atoi(getenv("RMCV_DENSE_DEFER")) : 0; // RMCV_OPT_DENSE_DEFER (env: dev A/B knob)
         c->geom.n_cu = (device < MAX_DEVICES && hipGetDeviceProperties(&prop, device) == hipSuccess) ? prop.multiProcessorCount : 0;
         if (device >= MAX_DEVICES) e = hipErrorInvalidDevice;
     }
@@ -396,12 +385,10 @@ void ctx_external_order(rmcv_ctx* c, hipEvent_t done)
     c->ext_done = done;
 }
 const Limits& ctx_limits(const rmcv_ctx* c) { return c->lim; }
-void ctx_pixel_shape(rmcv_ctx* c, int shape) { c->geom.pixel_ws = shape ? 1 : 0; }
 uint64_t ctx_blocking_calls(const rmcv_ctx* c) { return c->blocking_calls; }
 int ctx_wait_timeout_ms(const rmcv_ctx* c) { return c->wait_timeout_ms; }
-bool pixel_ws_full(const rmcv_ctx* c, int lower_bound) { return binary_ws_full(c->geom, c->bufs, lower_bound); }
-void ctx_defer_phase(rmcv_ctx* c, int phase) { c->geom.dense_defer = phase; }
-void ctx_sparse_lean(rmcv_ctx* c, int on) { c->geom.sparse_lean = on ? 1 : 0; }
+bool pixel_ws_full(const rmcv_ctx* c, int lower_bound, int pixel_ws) { return binary_ws_full(c->geom, c->bufs, lower_bound, pixel_ws); }
+RunPlan ctx_plan(const rmcv_ctx* c) { return {c->pixel_shape, c->pixel_groups, c->sparse_waves, c->dense_defer ? SPARSE_SPLIT_BOTH : SPARSE_STANDARD}; }
 int ctx_input_format(const rmcv_ctx* c) { return c->input_format; }
 int ctx_compact(rmcv_ctx* c, void* d_armours_out, int cap, void* d_frame_offs, void* d_status_or, hipStream_t s, void* hd_record, int host_head)
 {
@@ -672,17 +659,15 @@ static int order_end(rmcv_ctx* c, hipStream_t s)
     return RMCV_OK;
 }
 
-static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t s, bool timed,
-                      const rmcv_legacy_params* lp = nullptr)
+static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t s, bool timed, const RunPlan& plan,
+                      const rmcv_legacy_params* lp = nullptr, bool* lean = nullptr)
 {
     const Geom& g = c->geom;
     const Bufs& b = c->bufs;
     int k = 0;
     resident_none(c);
     int rc;
-    // every argument check comes BEFORE the first enqueue: an error return leaves the streams as they were
-    if ((stages & RMCV_STAGE_IDENTITY) && !b.svm_w) return fail(c, RMCV_ERR_BAD_ARG, "RMCV_STAGE_IDENTITY needs rmcv_svm_load first");
-    if ((stages & RMCV_STAGE_POSE) && !b.pnp_cfg) return fail(c, RMCV_ERR_BAD_ARG, "RMCV_STAGE_POSE needs rmcv_pnp_load first");
+    // every argument check comes BEFORE the first enqueue (the callers': check_bound): an error return leaves the streams as they were
     if (lp && g.input_format) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
     if ((rc = order_begin(c, s))) return rc;
     if (c->test_delay_us) { // RMCV_OPT_TEST_DELAY_US: a stand-in for a kernel that does not finish in time (one shot)
@@ -698,18 +683,18 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
         if (own) HIPCHK(c, launch_status_clear(g, b, own, s), "k_status_clear");
     }
     // findContours + filter_lightblobs (+ filter_armours) as ONE per-frame kernel when the stages are asked for together;
-    // the per-stage events of rmcv_batch_run_timed need per-stage launches (RMCV_FUSE_SPARSE=0: dev knob for A/B runs)
-    static const bool fuse_ok = !(getenv("RMCV_FUSE_SPARSE") && atoi(getenv("RMCV_FUSE_SPARSE")) == 0);
-    const bool one_sparse = fuse_ok && !timed && !lp && (stages & RMCV_STAGE_CONTOURS) && (stages & RMCV_STAGE_BLOBS);
+    // the per-stage events of rmcv_batch_run_timed need per-stage launches
+    if (lean) *lean = false;
+    const bool one_sparse = !timed && !lp && (stages & RMCV_STAGE_CONTOURS) && (stages & RMCV_STAGE_BLOBS);
     if (stages & RMCV_STAGE_BINARY) {
-        HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, !(stages & RMCV_STAGE_NO_IMAGE), c->pixel_groups, s),
+        HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, !(stages & RMCV_STAGE_NO_IMAGE), plan, s),
                g.input_format ? "k_binary_bayer" : "k_binary");
     }
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
     // the icon classifier rides in the per-frame kernel when the armours come from it (BASELINE config 5: no launch of its own)
     // (not for mosaics: the sparse kernel's classifier reads BGR; k_classify has the Bayer accessor)
     const bool identity_fused = one_sparse && (stages & RMCV_STAGE_ARMOURS) && (stages & RMCV_STAGE_IDENTITY) && g.input_format == RMCV_INPUT_BGR;
-    if (one_sparse) HIPCHK(c, launch_sparse(g, b, c->lim, *p, (stages & RMCV_STAGE_ARMOURS) != 0, identity_fused, c->sparse_waves, s), "k_contours (fused)");
+    if (one_sparse) HIPCHK(c, launch_sparse(g, b, c->lim, *p, (stages & RMCV_STAGE_ARMOURS) != 0, identity_fused, plan, s, lean), "k_contours (fused)");
     else if (stages & RMCV_STAGE_CONTOURS) HIPCHK(c, launch_contours(g, b, c->lim, s), "k_contours");
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
     const bool fused = (stages & RMCV_STAGE_BLOBS) && (stages & RMCV_STAGE_ARMOURS); // one launch for both
@@ -731,24 +716,24 @@ static int check_params(rmcv_ctx* c, const rmcv_params* p, int stages)
     if (!p) return fail(c, RMCV_ERR_BAD_ARG, "null params");
     if (p->morph < RMCV_MORPH_NONE || p->morph > RMCV_MORPH_CLOSE) return fail(c, RMCV_ERR_BAD_ARG, "bad morph");
     if (stages <= 0 || stages > (RMCV_STAGE_ALL | RMCV_STAGE_IDENTITY | RMCV_STAGE_POSE | RMCV_STAGE_NO_IMAGE)) return fail(c, RMCV_ERR_BAD_ARG, "bad stage mask");
-    if (c->geom.n_frames <= 0 || !c->bufs.frames) {
-        if (stages & RMCV_STAGE_BINARY) return fail(c, RMCV_ERR_BAD_ARG, "no frames bound");
-    }
-    return RMCV_OK;
-}
-
-namespace rmcv {
-// everything rmcv_batch_run would refuse for this stage mask, WITHOUT enqueuing anything: the pipeline splits a batch into several
-// runs on different streams and must not find out at the second one that the batch cannot run (a pixel kernel already enqueued,
-// nothing ordered behind it)
-int ctx_check_stages(rmcv_ctx* c, const rmcv_params* p, int stages)
-{
-    const int rc = check_params(c, p, stages);
-    if (rc) return rc;
     if ((stages & RMCV_STAGE_IDENTITY) && !c->bufs.svm_w) return fail(c, RMCV_ERR_BAD_ARG, "RMCV_STAGE_IDENTITY needs rmcv_svm_load first");
     if ((stages & RMCV_STAGE_POSE) && !c->bufs.pnp_cfg) return fail(c, RMCV_ERR_BAD_ARG, "RMCV_STAGE_POSE needs rmcv_pnp_load first");
     return RMCV_OK;
 }
+// check_params of the public entry points, which run on what the caller has bound
+static int check_bound(rmcv_ctx* c, const rmcv_params* p, int stages)
+{
+    const int rc = check_params(c, p, stages);
+    if (rc) return rc;
+    if ((c->geom.n_frames <= 0 || !c->bufs.frames) && (stages & RMCV_STAGE_BINARY)) return fail(c, RMCV_ERR_BAD_ARG, "no frames bound");
+    return RMCV_OK;
+}
+
+namespace rmcv {
+// everything rmcv_batch_run would refuse for this stage mask, WITHOUT enqueuing anything and before any frames are bound: the pipeline
+// splits a batch into several runs on different streams and must not find out at the second one that the batch cannot run (a pixel
+// kernel already enqueued, nothing ordered behind it), nor after its binding has enqueued a change of geometry
+int ctx_check_stages(rmcv_ctx* c, const rmcv_params* p, int stages) { return check_params(c, p, stages); }
 } // namespace rmcv
 
 extern "C" {
@@ -810,25 +795,31 @@ int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int 
 }
 // what binding a batch would allocate, now (a pipeline does this for every context of its ring when it is created)
 int ctx_prepare_ring(rmcv_ctx* c) { return ensure_mid(c, c->lim.max_frames); }
+int ctx_run(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_params* lp, int stages, hipStream_t s, const RunPlan& plan, bool* lean)
+{
+    const int rc = check_bound(c, p, stages);
+    if (rc) return rc;
+    return run_stages(c, p, stages, s, false, plan, lp, lean);
+}
 } // namespace rmcv
 extern "C" {
 
 int rmcv_batch_run(rmcv_ctx* c, const rmcv_params* p, int stages, void* hip_stream)
 {
-    int rc = check_params(c, p, stages);
+    int rc = check_bound(c, p, stages);
     if (rc) return rc;
     hipSetDevice(c->device);
-    return run_stages(c, p, stages, hip_stream ? (hipStream_t)hip_stream : c->stream, false);
+    return run_stages(c, p, stages, hip_stream ? (hipStream_t)hip_stream : c->stream, false, ctx_plan(c));
 }
 
 int rmcv_batch_run_legacy(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_params* lp, int stages, void* hip_stream)
 {
-    int rc = check_params(c, p, stages);
+    int rc = check_bound(c, p, stages);
     if (rc) return rc;
     if (!lp) return fail(c, RMCV_ERR_BAD_ARG, "null legacy params");
     if (c->input_format || c->geom.input_format) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
     hipSetDevice(c->device);
-    return run_stages(c, p, stages, hip_stream ? (hipStream_t)hip_stream : c->stream, false, lp);
+    return run_stages(c, p, stages, hip_stream ? (hipStream_t)hip_stream : c->stream, false, ctx_plan(c), lp);
 }
 
 int rmcv_ctx_set_option(rmcv_ctx* c, int option, int value)
@@ -860,7 +851,7 @@ int rmcv_ctx_set_option(rmcv_ctx* c, int option, int value)
         return RMCV_OK;
     }
     if (option == RMCV_OPT_PIXEL_SHAPE && (value == 0 || value == 1)) {
-        c->geom.pixel_ws = value;
+        c->pixel_shape = value;
         return RMCV_OK;
     }
     if (option == RMCV_OPT_OVERLOADS && value >= 0 && value <= 3) {
@@ -869,7 +860,7 @@ int rmcv_ctx_set_option(rmcv_ctx* c, int option, int value)
         return RMCV_OK;
     }
     if (option == RMCV_OPT_DENSE_DEFER && (value == 0 || value == 1)) {
-        c->geom.dense_defer = value;
+        c->dense_defer = value;
         return RMCV_OK;
     }
     if (option == RMCV_OPT_CONTOUR_TIER && value >= 0 && value <= 2) {
@@ -964,12 +955,12 @@ int rmcv_batch_sync(rmcv_ctx* c)
 
 int rmcv_batch_run_timed(rmcv_ctx* c, const rmcv_params* p, int stages, void* hip_stream, float stage_ms[5])
 {
-    int rc = check_params(c, p, stages);
+    int rc = check_bound(c, p, stages);
     if (rc) return rc;
     if (!stage_ms) return fail(c, RMCV_ERR_BAD_ARG, "null stage_ms");
     hipSetDevice(c->device);
     hipStream_t s = hip_stream ? (hipStream_t)hip_stream : c->stream;
-    rc = run_stages(c, p, stages, s, true);
+    rc = run_stages(c, p, stages, s, true, ctx_plan(c));
     if (rc) return rc;
     WAITCHK(c, wait_stream(c, s, "waiting for the stream"));
     for (int i = 0; i < 4; i++) HIPCHK(c, hipEventElapsedTime(&stage_ms[i], c->ev[i], c->ev[i + 1]), "elapsed");
@@ -1418,11 +1409,13 @@ static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int
     const Geom& g = c->geom;
     const Bufs& b = c->bufs;
     hipStream_t s = c->stream;
+    RunPlan plan = ctx_plan(c);
+    plan.sparse_waves = 8; // one frame: the latency setting
     if (c->test_delay_us) { // RMCV_OPT_TEST_DELAY_US: a stand-in for a kernel that does not finish in time (one shot)
         HIPCHK(c, launch_delay((unsigned long long)c->test_delay_us * 1000ull, s), "k_delay (RMCV_OPT_TEST_DELAY_US)");
         c->test_delay_us = 0;
     }
-    HIPCHK(c, launch_binary(g, b, camp, lower_bound, morph, binary_out != nullptr, c->pixel_groups, s), g.input_format ? "k_binary_bayer" : "k_binary");
+    HIPCHK(c, launch_binary(g, b, camp, lower_bound, morph, binary_out != nullptr, plan, s), g.input_format ? "k_binary_bayer" : "k_binary");
     if (binary_out) HIPCHK(c, hipEventRecord(c->ev_fork, s), "image download: mark");
     // running ahead with both parameter sets known: the frame's whole sparse part is ONE kernel (the fused per-frame kernel of
     // the batch path: findContours, fits and pairing back to back), not three
@@ -1439,7 +1432,7 @@ static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int
         p.angle_diff_max = c->last_ar.angle_diff_max;
         p.shear_max = c->last_ar.shear_max;
         p.length_ratio_max = c->last_ar.length_ratio_max;
-        HIPCHK(c, launch_sparse(g, b, c->lim, p, true, false, 8, s), "k_contours (fused)");
+        HIPCHK(c, launch_sparse(g, b, c->lim, p, true, false, plan, s), "k_contours (fused)");
     } else {
         HIPCHK(c, launch_contours(g, b, c->lim, s), "k_contours");
     }
@@ -1497,9 +1490,8 @@ static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int
         const long long bytes = (long long)w * h;
         if (++c->img_seq == 0) c->img_seq = 1;
         HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0), "image download: fork");
-        static const int env_chunks = getenv("RMCV_IMG_CHUNKS") ? atoi(getenv("RMCV_IMG_CHUNKS")) : 0, env_groups = getenv("RMCV_IMG_GROUPS") ? atoi(getenv("RMCV_IMG_GROUPS")) : 0; // dev knobs
-        const int n_chunks = env_chunks >= 1 && env_chunks <= IMG_CHUNKS ? env_chunks : IMG_CHUNKS_DEFAULT, n_groups = env_groups >= 1 && env_groups <= 256 ? env_groups : IMG_GROUPS;
-        HIPCHK(c, launch(k_image_export, dim3(n_groups), dim3(256), 0, c->side, b.binary, c->hd_image, bytes, c->hd_iflags, c->img_seq, c->d_iarrived, n_chunks), "k_image_export");
+        const int n_chunks = IMG_CHUNKS_DEFAULT;
+        HIPCHK(c, launch(k_image_export, dim3(IMG_GROUPS), dim3(256), 0, c->side, b.binary, c->hd_image, bytes, c->hd_iflags, c->img_seq, c->d_iarrived, n_chunks), "k_image_export");
         c->last_what = "k_binary, k_image_export";
         const volatile uint32_t* fl = c->h_iflags;
         const double t0w = now_us();

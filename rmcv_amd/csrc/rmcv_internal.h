@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "../../include/rmcv_abi.h"
+#include "sparse_plan.h"
 
 namespace rmcv {
 
@@ -19,11 +20,8 @@ struct Geom {
     int device;          // HIP device of the owning context: per-device launch state (function attributes) is indexed by it
     int n_cu;            // compute units of that device (sizes the persistent grid of k_binary)
     int pixel_halo_nt;   // RMCV_OPT_PIXEL_HALO_NT: the row quads a strip shares with its neighbours are loaded non-temporal too
-    int pixel_rowquad;   // dev knob (RMCV_K1_LINEAR=0 in the environment when the context is made): k_binary's row-quad loader even where rows are contiguous
-    int pixel_ws;        // RMCV_OPT_PIXEL_SHAPE: whole batches with contiguous rows go to k_binary_ws (one 1024-thread workgroup per CU)
-    int dense_defer;     // RMCV_OPT_DENSE_DEFER: frames beyond the LDS tables are left to a second launch with 8 wavefronts per frame
+    int pixel_rowquad;   // hidden option 1001 (bench.py's RMCV_BENCH_AB): k_binary's row-quad loader even where rows are contiguous
     int overloads;       // RMCV_OPT_OVERLOADS: SURVEY A.6, which functions the reference's unqualified abs / atan2 / sin / cos on floats are
-    int sparse_lean;     // a pipeline's dense mode: the batch's sparse stage runs the lean build (k_contours_lean.hip), every frame on the mid tier
     int contour_tier;    // RMCV_OPT_CONTOUR_TIER: 0 = per frame (LDS tables, else mid tier, else literal scanner), 1 = literal, 2 = mid tier
     int input_format;    // RMCV_OPT_INPUT_FORMAT of the frames bound: 0 BGR, 1..4 a Bayer pattern (recorded when the frames are bound)
     int n_frames;
@@ -33,6 +31,15 @@ struct Geom {
     int ww;              // words per row = ceil(w / 64)
     int prow;            // padded words per row = ww + 2
     int64_t plane_pitch; // words per frame = (h + 2) * prow
+};
+
+// What a run's launches depend on beyond geometry, buffers and params.  The public entry points take it from the context's options
+// (ctx_plan); a pipeline overrides parts of it per batch (rmcv_pipeline.hip) instead of writing options before a run and undoing them after.
+struct RunPlan {
+    int pixel_ws;     // RMCV_OPT_PIXEL_SHAPE: whole batches with contiguous rows go to k_binary_ws (one 1024-thread workgroup per CU)
+    int pixel_groups; // RMCV_OPT_PIXEL_GROUPS: k_binary's workgroups per CU
+    int sparse_waves; // RMCV_OPT_SPARSE_WAVES: wavefronts per frame of the fused sparse kernel
+    SparseForm form;  // see sparse_plan.h (RMCV_OPT_DENSE_DEFER: SPARSE_SPLIT_BOTH)
 };
 
 static constexpr int CTR_STRIDE = 32;   // ints between the heads of k_binary's strip queues (Bufs::strip_ctr): a 128-byte line each, 9 of them
@@ -137,15 +144,16 @@ int64_t pixel_ws_launches(); // launches of k_binary_ws by this process (rmcv_pi
 hipError_t launch_match(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, const rmcv_legacy_params& lp,
                         int mode, bool with_frames, bool pairs, hipStream_t s);
 // identity: the frame's armours are classified by the same kernel (RMCV_STAGE_IDENTITY; needs pairs)
-hipError_t launch_sparse(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, bool pairs, bool identity, int waves, hipStream_t s);
+// lean (nullable): set to whether the lean build ran
+hipError_t launch_sparse(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, bool pairs, bool identity, const RunPlan& plan,
+                         hipStream_t s, bool* lean = nullptr);
 hipError_t launch_pnp(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s);
-hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, int groups, hipStream_t s);
-bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound); // the batch will run as one launch of k_binary_ws with a workgroup on every CU
+hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s);
+bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound, int pixel_ws); // the batch will run as one launch of k_binary_ws with a workgroup on every CU
 // the pixel stage of a Bayer batch (Geom::input_format != 0; k_binary_bayer.hip); launch_binary hands such batches to it
 hipError_t launch_binary_bayer(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, hipStream_t s);
 // D(m) of one device mosaic into a device BGR frame (rmcv_demosaic)
 hipError_t launch_demosaic(const uint8_t* d_raw, int stride, int w, int h, int pattern, uint8_t* d_out, int out_stride, hipStream_t s);
-bool sparse_lean_applies(const Geom& g, const Bufs& b); // Geom::sparse_lean can be honoured for what is bound (k_contours.hip)
 hipError_t launch_contours(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s);
 hipError_t launch_blobs(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, hipStream_t s);
 hipError_t launch_armours(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, hipStream_t s);
@@ -188,8 +196,11 @@ void ctx_external_order(rmcv_ctx* c, hipEvent_t done);
 // rmcv_batch_compact_armours + the batch's OR-ed status word
 int ctx_compact(rmcv_ctx* c, void* d_armours_out, int cap, void* d_frame_offs, void* d_status_or, hipStream_t s, void* hd_record = nullptr, int host_head = 0);
 const Limits& ctx_limits(const rmcv_ctx* c);
-// 1: whole batches with contiguous rows go to the wave-specialised pixel kernel (k_binary_ws.inc), 0: k_binary
-void ctx_pixel_shape(rmcv_ctx* c, int shape);
+// the plan of a run from the context's own options
+RunPlan ctx_plan(const rmcv_ctx* c);
+// rmcv_batch_run / rmcv_batch_run_legacy (lp non-null) with a plan of the caller's, on frames the caller has bound (ctx_bind_frames);
+// lean (nullable): set to whether the sparse stage ran the lean build
+int ctx_run(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_params* lp, int stages, hipStream_t s, const RunPlan& plan, bool* lean = nullptr);
 // rmcv_batch_set_device_frames without a blocking call: a change of geometry (planes zeroed, frame order recomputed) is ENQUEUED on `s`,
 // which the caller has made wait for the context's last batch
 int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t s);
@@ -198,17 +209,13 @@ int ctx_prepare_ring(rmcv_ctx* c);
 // allocations, host-side synchronisations and blocking copies this context has made while binding geometries
 uint64_t ctx_blocking_calls(const rmcv_ctx* c);
 int ctx_wait_timeout_ms(const rmcv_ctx* c);
-bool pixel_ws_full(const rmcv_ctx* c, int lower_bound); // binary_ws_full of what is bound to the context
+bool pixel_ws_full(const rmcv_ctx* c, int lower_bound, int pixel_ws); // binary_ws_full of what is bound to the context
 // waits that poll with a deadline instead of parking the thread in the runtime: 0 done, 1 deadline passed, -1 HIP error (*err)
 int wait_stream_deadline(hipStream_t s, int timeout_ms, hipError_t* err);
 int wait_event_deadline(hipEvent_t ev, int timeout_ms, hipError_t* err);
 hipError_t launch_delay(unsigned long long ns, hipStream_t s); // holds `s` back for `ns` nanoseconds
-// what rmcv_batch_run would refuse for (p, stages), checked without enqueuing anything
+// what rmcv_batch_run would refuse for (p, stages) apart from frames not bound, checked without enqueuing anything
 int ctx_check_stages(rmcv_ctx* c, const rmcv_params* p, int stages);
-// Geom::dense_defer for the runs that follow: 0 off, 1 both launches on the run's stream (RMCV_OPT_DENSE_DEFER), 2 / 3 the first / second only
-void ctx_defer_phase(rmcv_ctx* c, int phase);
-// Geom::sparse_lean for the runs that follow
-void ctx_sparse_lean(rmcv_ctx* c, int on);
 // RMCV_OPT_INPUT_FORMAT as set on the context (what the next binding records)
 int ctx_input_format(const rmcv_ctx* c);
 

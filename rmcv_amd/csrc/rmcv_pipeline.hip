@@ -68,27 +68,24 @@ struct rmcv_pipeline {
         rmcv_ctx* c = nullptr;
         rmcv_params p{};
         rmcv_legacy_params lp{};
-        bool has_lp = false, used = false, heavy = false;
+        bool has_lp = false, used = false;
+        RunPlan plan{}; // the batch's plan: the context's options, the pixel shape submit chose, SPARSE_LEAN in dense mode
         int sparse = 0, n_frames = 0;
         hipStream_t B = nullptr;
     } pend;
     uint64_t latency_batches = 0;
-    bool lazy_back = true;              // (dev knob RMCV_LAZY_BACK=0)
-    bool chain_cold = true, was_cold = false; // (dev knob RMCV_CHAIN_COLD=0)
-    int chain_cold_us = 60;             // (dev knob RMCV_CHAIN_COLD=n > 1: the delay in microseconds; 1: wait for the first launch's end instead)
-    bool early_free = true;             // (dev knob RMCV_EARLY_FREE=0: a context's next batch waits for the whole list, as ev_done)
+    bool was_cold = false;             // the batch before the newest one found the pixel stream idle (a burst's first launch)
     // DENSE MODE (round 5).  While the records that come back say the batches are heavy -- more than an eighth of the frames beyond
     // findContours' LDS tables, or 1 500 border points per frame and more (a plain frame has 650) -- the stream is bound by its sparse
     // stage, not by the pixel kernel: one workgroup of the standard sparse kernel per CU, 0.2-0.6 ms per frame.  Such batches run the LEAN
     // build of the sparse kernel (k_contours_lean.hip: every frame on the mid tier, 61 KB of LDS instead of 80).  The way back: fewer than
     // 1 200 points per frame (in this mode every frame reports the mid tier, so only the points say what the stream is like).
-    // Measured (tools/dense_mode_ab.sh, process against process on one box, ms per step off / on): dense2 0.320 / 0.291, dense3 0.396 /
+    // Measured (profiles/r05_dense_mode_ab.txt, process against process on one box, ms per step off / on): dense2 0.320 / 0.291, dense3 0.396 /
     // 0.372, dense4 0.571 / 0.512; with ONE pixel workgroup per CU and launch as well (room for two lean workgroups per CU, but the pixel
     // kernel needs four resident workgroups to hide its latency): 0.314 / 0.368 / 0.504 -- not kept as the default.
     bool heavy = false;
-    int heavy_pixel_groups = 0;        // pixel workgroups per CU and launch in dense mode; 0: as configured (dev knob RMCV_HEAVY_PG; -1: dense mode off)
     uint64_t heavy_batches = 0;
-    std::vector<char> slot_lean;       // per slot: its batch ran in dense mode (every frame of its record reports the mid tier)
+    std::vector<char> slot_lean;       // per slot: its batch's sparse stage ran the lean build (every frame of its record reports the mid tier)
     bool split_now = false;            // the batches of the moment have a FEW dense frames: give those a launch and a stream of their own
     uint64_t split_batches = 0;        // batches submitted that way
     rmcv_pipeline_hook hook = nullptr;
@@ -109,9 +106,6 @@ struct rmcv_pipeline {
     const char* last_what = "nothing"; // the enqueue made last (PCHK's label): named when a wait runs out
     int hot_cfg = 0;                   // rmcv_pipeline_config::hot_contexts as given (0: derived from the bound geometry)
     int64_t hot_plane_bytes = 0;       // ... the bit planes' bytes of a batch of the geometry `hot` was derived for
-    bool ws_always = false;            // dev knob RMCV_WS_ALWAYS: the wave-specialised pixel kernel for every batch, hot rotation or not
-    bool hot_identity = false;         // batches with a classifier stage take turns at the hot contexts too: measured in round 5 (three contexts at
-                                       // 256 x 1920x1200: 0.514 against 0.426 ms per step), off; RMCV_HOT_IDENTITY=1 in a dev build
     double max_submit_us = 0;          // the longest single submit call (host time) since rmcv_pipeline_reset_stats
     char err[256] = {0};
 };
@@ -339,16 +333,6 @@ int rmcv_pipeline_create(int device, const rmcv_limits* limits, const rmcv_pipel
     pl->slot_ctx.assign((size_t)d.depth, 0);
     pl->hot = hot_for(pl, pl->lim.max_frames, pl->lim.max_width, pl->lim.max_height); // (derived again for the geometry of every submit)
     pl->wait_timeout_ms = ctx_wait_timeout_ms(pl->ring[0]);
-#ifdef RMCV_DEV_KNOBS // A/B switches of the schedule's parts (make EXTRA=-DRMCV_DEV_KNOBS): not in a product build
-    pl->lazy_back = !(getenv("RMCV_LAZY_BACK") && atoi(getenv("RMCV_LAZY_BACK")) == 0);
-    pl->chain_cold = !(getenv("RMCV_CHAIN_COLD") && atoi(getenv("RMCV_CHAIN_COLD")) == 0);
-    if (getenv("RMCV_CHAIN_COLD")) pl->chain_cold_us = atoi(getenv("RMCV_CHAIN_COLD")) > 1 ? atoi(getenv("RMCV_CHAIN_COLD")) : 0;
-    pl->early_free = !(getenv("RMCV_EARLY_FREE") && atoi(getenv("RMCV_EARLY_FREE")) == 0);
-    if (getenv("RMCV_HOT_IDENTITY")) pl->hot_identity = atoi(getenv("RMCV_HOT_IDENTITY")) != 0;
-    if (getenv("RMCV_WS_ALWAYS")) pl->ws_always = atoi(getenv("RMCV_WS_ALWAYS")) != 0;
-    if (getenv("RMCV_HEAVY_PG")) pl->heavy_pixel_groups = atoi(getenv("RMCV_HEAVY_PG")) > 0 ? atoi(getenv("RMCV_HEAVY_PG")) : 0;
-    if (getenv("RMCV_HEAVY_OFF") && atoi(getenv("RMCV_HEAVY_OFF"))) pl->heavy_pixel_groups = -1; // (dense mode off)
-#endif
     pl->blocking_base = ring_blocking(pl);
     if (e != hipSuccess) {
         fprintf(stderr, "rmcv_pipeline_create: %s\n", hipGetErrorString(e));
@@ -506,13 +490,14 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
     const int sparse = pl->pend.sparse, n_frames = pl->pend.n_frames;
     hipStream_t B = pl->pend.B;
     int rc = RMCV_OK;
-    const bool heavy = pl->pend.heavy;
+    // the back half of the batch's plan: 8 wavefronts per frame for a batch nothing is launched beside, or a split batch's two launches
+    RunPlan plan = pl->pend.plan;
+    const bool heavy = plan.form == SPARSE_LEAN;
     const bool w8 = latency && pl->cfg.sparse_waves == 4 && !lp && !heavy;
     if (w8) {
-        rmcv_ctx_set_option(c, RMCV_OPT_SPARSE_WAVES, 8);
+        plan.sparse_waves = 8;
         pl->latency_batches++;
     }
-    struct Restore { rmcv_ctx* c; bool on; ~Restore() { if (on) rmcv_ctx_set_option(c, RMCV_OPT_SPARSE_WAVES, 4); } } restore{c, w8};
     // Dense frames (beyond findContours' LDS tables: hundreds of borders, 0.5-1 ms on one workgroup) are left by the per-frame launch
     // to a second launch with 8 wavefronts per frame on a stream of its own, the compaction behind it: the sparse stream B is free
     // for the next batch when the batch's ordinary frames are through (one lit window per batch used to cost the whole loop 20-35 %).
@@ -535,21 +520,19 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
         PCHK(pl, hipEventRecord(pl->ev_chg[k], pl->slot_stream[k]), "pipeline: change of the slot's stream (mark)");
         PCHK(pl, hipStreamWaitEvent(T, pl->ev_chg[k], 0), "pipeline: change of the slot's stream (wait)");
     }
+    bool lean = false; // (the launcher takes the lean build where it applies: fused stages, no classifier, the mid tier's scratch there)
     if (sparse) {
         if (split) {
-            ctx_defer_phase(c, 2); // the first launch only: frames beyond the LDS tables are marked and left alone
-            rc = rmcv_batch_run(c, p, sparse & ~RMCV_STAGE_POSE, B);
+            plan.form = SPARSE_SPLIT_FIRST; // the first launch only: frames beyond the LDS tables are marked and left alone
+            rc = ctx_run(c, p, nullptr, sparse & ~RMCV_STAGE_POSE, B, plan);
             if (rc == RMCV_OK) {
                 PCHK(pl, hipEventRecord(pl->ev_sp[k], B), "pipeline: mark the first sparse launch");
                 PCHK(pl, hipStreamWaitEvent(T, pl->ev_sp[k], 0), "pipeline: chain the dense frames");
-                ctx_defer_phase(c, 3); // the second launch only (+ the pose stage, which needs every frame's armours)
-                rc = rmcv_batch_run(c, p, sparse, T);
+                plan.form = SPARSE_SPLIT_SECOND; // the second launch only (+ the pose stage, which needs every frame's armours)
+                rc = ctx_run(c, p, nullptr, sparse, T, plan);
             }
-            ctx_defer_phase(c, 0);
         } else {
-            if (heavy) ctx_sparse_lean(c, 1); // (the launcher takes the lean build where it applies: fused stages, no classifier, the mid tier's scratch there)
-            rc = lp ? rmcv_batch_run_legacy(c, p, lp, sparse, B) : rmcv_batch_run(c, p, sparse, B);
-            if (heavy) ctx_sparse_lean(c, 0);
+            rc = ctx_run(c, p, lp, sparse, B, plan, &lean);
         }
         if (rc) return cfail(pl, c, rc);
     }
@@ -568,7 +551,7 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
     PCHK(pl, hipEventRecord(pl->ev_done[k], T), "pipeline: mark the slot");
     pl->slot_ticket[k] = t + 1;
     pl->slot_frames[k] = n_frames;
-    pl->slot_lean[k] = heavy ? 1 : 0;
+    pl->slot_lean[k] = lean ? 1 : 0;
     pl->slot_stream[k] = T;
     if (pl->comm) {
         // one communicator: its operations must execute in one order on every rank; they are issued in ticket order on alternating
@@ -614,14 +597,23 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
         (void)hipGetLastError(); // (hipErrorNotReady is not an error)
     }
     // (dense mode needs the records on the host, the 4-wavefront kernel and two pixel streams to make up for the halved launches)
-    const bool heavy = pl->heavy && pl->heavy_pixel_groups >= 0 && pl->cfg.host_results == 1 && pl->cfg.sparse_waves == 4 && pl->cfg.dense_streams >= 0 && !lp &&
+    const bool heavy = pl->heavy && pl->cfg.host_results == 1 && pl->cfg.sparse_waves == 4 && !lp &&
                        !(stages & (RMCV_STAGE_IDENTITY | RMCV_STAGE_POSE)) && (stages & RMCV_STAGE_CONTOURS) && (stages & RMCV_STAGE_BLOBS);
-    const bool fast = pl->hot && pl->calm && !lp && !(stages & RMCV_STAGE_POSE) && (pl->hot_identity || !(stages & RMCV_STAGE_IDENTITY));
+    // (batches with a classifier stage stay out of the hot rotation: measured in round 5, three contexts at 256 x 1920x1200, 0.514 against
+    // 0.426 ms per step with them in it)
+    const bool fast = pl->hot && pl->calm && !lp && !(stages & RMCV_STAGE_POSE) && !(stages & RMCV_STAGE_IDENTITY);
     const size_t j = fast ? (size_t)(pl->hot_seq % (uint64_t)pl->hot) : k;
     rmcv_ctx* c = pl->ring[j];
-    if (lp && ctx_input_format(c)) return pfail(pl, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
-    hipStream_t A = pl->pix[(size_t)(t % (uint64_t)pl->cfg.pixel_streams)], B = pl->sp[k % (size_t)pl->cfg.sparse_streams];
     int rc;
+    if (lp && ctx_input_format(c)) return pfail(pl, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
+    // a batch is several runs on several streams: everything that could refuse it is checked before the first enqueue (the binding below
+    // enqueues a new geometry's work on A)
+    if ((rc = ctx_check_stages(c, p, stages))) return cfail(pl, c, rc);
+    // the front half of the batch's plan: the context's options, the wave-specialised pixel kernel for the hot rotation's batches
+    RunPlan plan = ctx_plan(c);
+    plan.pixel_ws = fast ? 1 : 0;
+    if (heavy) plan.form = SPARSE_LEAN;
+    hipStream_t A = pl->pix[(size_t)(t % (uint64_t)pl->cfg.pixel_streams)], B = pl->sp[k % (size_t)pl->cfg.sparse_streams];
     // ---- waits first: stream A is behind everything that still uses the slot and the context when the binding below enqueues on it.
     // (Nothing of the pipeline's own state moves before the batch has been accepted: an error return leaves tickets, rotation and
     // context ownership as they were; the waits already enqueued on A are harmless.)
@@ -634,17 +626,14 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     // with four contexts in rotation the whole slack is ~80 us).
     if (pl->ctx_last[j] >= 0 && pl->ctx_last[j] != (int)k) {
         const size_t last = (size_t)pl->ctx_last[j];
-        const bool early = pl->early_free && pl->slot_stream[last] == B;
+        const bool early = pl->slot_stream[last] == B;
         PCHK(pl, hipStreamWaitEvent(A, early ? pl->ev_free[last] : pl->ev_done[last], 0), "pipeline: wait for the context");
     }
     // ---- bind: a new geometry's work (planes zeroed, frame order) is ENQUEUED on A, nothing blocks
     rc = ctx_bind_frames(c, d_frames, n_frames, w, h, stride, frame_pitch, A);
     if (rc) return cfail(pl, c, rc);
-    // a batch is several runs on several streams: everything that could refuse it is checked before the first launch
-    if ((rc = ctx_check_stages(c, p, stages))) return cfail(pl, c, rc);
     const int pixel = stages & (RMCV_STAGE_BINARY | RMCV_STAGE_NO_IMAGE), sparse = stages & ~(RMCV_STAGE_BINARY | RMCV_STAGE_NO_IMAGE);
     ctx_external_order(c, pl->ev_done[k]);
-    ctx_pixel_shape(c, (fast || pl->ws_always) ? 1 : 0);
     // A burst's SECOND pixel launch is held back (k_delay on its stream).  k_binary_ws is one workgroup per CU: when two launches
     // reach an empty machine 15 us apart, whether the first has taken every CU by then is a coin toss -- if not, the two split the
     // CUs, run side by side and END together, and so do the next pairs (each pair's ramp and tail in the open, both sparse kernels
@@ -655,28 +644,23 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     // WILL be k_binary_ws on every CU (launch_binary's own rule: pixel_ws_full) -- and for a quarter of the launch's expected time
     // (its bytes at 5.5 TB/s), 60 us at most, nothing below 100 us of launch: two 16-frame batches are not held back at all.
     bool cold = false;
-    if (fast && pl->chain_cold) {
+    if (fast) {
         cold = t == 0;
         const size_t s_ = t ? (size_t)((t - 1) % (uint64_t)pl->cfg.depth) : 0;
         if (t > 0) {
             cold = pl->slot_ticket[s_] == t && hipEventQuery(pl->ev_done[s_]) == hipSuccess;
             (void)hipGetLastError();
         }
-        if (!cold && pl->was_cold && pl->slot_ticket[s_] == t && pixel_ws_full(c, p->lower_bound)) {
+        if (!cold && pl->was_cold && pl->slot_ticket[s_] == t && pixel_ws_full(c, p->lower_bound, plan.pixel_ws)) {
             const double launch_us = (double)n_frames * 4.0 * w * h / 5.5e6;
-            const int hold_us = launch_us < 100.0 ? 0 : (int)(launch_us / 4.0 < pl->chain_cold_us ? launch_us / 4.0 : pl->chain_cold_us);
-            if (pl->chain_cold_us > 0) { // hold the second launch back until the first one's workgroups have taken every CU
-                if (hold_us > 0) {
-                    PCHK(pl, launch_delay((unsigned long long)hold_us * 1000ull, A), "pipeline: k_delay");
-                    pl->held_back++;
-                }
-            } else
-                PCHK(pl, hipStreamWaitEvent(A, pl->ev_bin[s_], 0), "pipeline: chain a burst's second launch");
+            const int hold_us = launch_us < 100.0 ? 0 : (int)(launch_us / 4.0 < 60.0 ? launch_us / 4.0 : 60.0);
+            if (hold_us > 0) { // hold the second launch back until the first one's workgroups have taken every CU
+                PCHK(pl, launch_delay((unsigned long long)hold_us * 1000ull, A), "pipeline: k_delay");
+                pl->held_back++;
+            }
         }
     }
-    if (heavy && pl->heavy_pixel_groups > 0) rmcv_ctx_set_option(c, RMCV_OPT_PIXEL_GROUPS, pl->heavy_pixel_groups);
-    rc = rmcv_batch_run(c, p, pixel, A);
-    if (heavy && pl->heavy_pixel_groups > 0) rmcv_ctx_set_option(c, RMCV_OPT_PIXEL_GROUPS, pl->cfg.pixel_groups);
+    rc = ctx_run(c, p, nullptr, pixel, A, plan);
     if (rc) return cfail(pl, c, rc);
     pl->last_what = ctx_input_format(c) ? "the pixel kernel (k_binary_bayer)" : "the pixel kernel (k_binary / k_binary_ws)";
     // ---- accepted: the pipeline's state moves
@@ -697,12 +681,12 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     pl->pend.has_lp = lp != nullptr;
     if (lp) pl->pend.lp = *lp;
     pl->pend.used = used;
-    pl->pend.heavy = heavy;
+    pl->pend.plan = plan;
     pl->pend.sparse = sparse;
     pl->pend.n_frames = n_frames;
     pl->pend.B = B;
     // (a hook or the gather hands the record to a consumer the pipeline does not see waiting: its batches are finished here and now)
-    if (!pl->lazy_back || pl->hook || pl->comm) return finish_back(pl, false);
+    if (pl->hook || pl->comm) return finish_back(pl, false);
     return RMCV_OK;
 }
 

@@ -606,9 +606,11 @@ struct SparseTail {
     ClassifyArgs C; // C.enabled: the frame's armours are classified by the same workgroup (RMCV_STAGE_IDENTITY)
 };
 
-hipError_t launch_contours_w4(const Geom& g, const Bufs& b, const Limits& lim, const SparseTail& X, int force_literal, const SparseSched& Q, int grid,
-                              hipStream_t s);
+// the sparse kernel's builds beside k_contours_w8 (flags, lds: SparseLaunch, sparse_plan.h)
+hipError_t launch_contours_w4(const Geom& g, const Bufs& b, const Limits& lim, const SparseTail& X, int flags, const SparseSched& Q, int grid,
+                              SparseLds lds, hipStream_t s);
 // the lean build for dense streams (k_contours_lean.hip): every frame on the mid tier, two workgroups per CU; flags: 2 (+ 8: deferred frames only)
-hipError_t launch_contours_lean(const Geom& g, const Bufs& b, const Limits& lim, const SparseTail& X, int flags, const SparseSched& Q, int grid, hipStream_t s);
+hipError_t launch_contours_lean(const Geom& g, const Bufs& b, const Limits& lim, const SparseTail& X, int flags, const SparseSched& Q, int grid, SparseLds lds,
+                                hipStream_t s);
 
 } // namespace rmcv

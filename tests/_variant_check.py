@@ -1,5 +1,6 @@
-"""helper of test_gpu_variants.py: run in a fresh process (the library reads its dev knobs once per process);
-compares extract_color against the oracle on a few images and exits non-zero on a mismatch"""
+"""helper of test_gpu_variants.py, run in a fresh process with the case as its argument: default, literal (RMCV_OPT_CONTOUR_TIER 1),
+mid (RMCV_OPT_CONTOUR_TIER 2) or groups2 (RMCV_OPT_PIXEL_GROUPS 2); compares extract_color and a batch against the oracle and exits
+non-zero on a mismatch"""
 import os
 import sys
 
@@ -9,10 +10,13 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, HERE)
 sys.path.insert(0, os.path.dirname(HERE))
 import oracle_lib as O  # noqa: E402
-from rmcv_amd import CAMP_BLUE, MORPH_CLOSE, STAGE_ALL, Context, default_params, synth  # noqa: E402
+from rmcv_amd import CAMP_BLUE, MORPH_CLOSE, OPT_CONTOUR_TIER, OPT_PIXEL_GROUPS, Context, default_params, synth  # noqa: E402
 
 O.set_math_mode(0)
 ctx = Context(device=0, max_frames=4)
+option = {"default": None, "literal": (OPT_CONTOUR_TIER, 1), "mid": (OPT_CONTOUR_TIER, 2), "groups2": (OPT_PIXEL_GROUPS, 2)}[sys.argv[1]]
+if option:
+    ctx.set_option(*option)
 rng = np.random.default_rng(3)
 imgs = []
 for (h, w) in [(64, 64), (120, 200), (256, 256)]:

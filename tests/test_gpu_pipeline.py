@@ -382,6 +382,30 @@ def test_geometry_changes_with_batches_in_flight(oracle):
     pl.close()
 
 
+def test_refused_submit_at_a_new_geometry_binds_nothing(oracle):
+    """a submit that the stage check refuses is refused before its context binds the new geometry: the batches after it, at the old
+    geometry and at the new one, come back equal to the oracle"""
+    import torch
+    dev = torch.device("cuda", 0)
+    pl = Pipeline(device=0, depth=2, max_frames=24, max_width=1280, max_height=1024)
+    p = default_params()
+    old = synth.batch(770000, 24, 640, 512, CAMP_BLUE, 0, threads=16)
+    new = synth.batch(770100, 9, 1280, 720, CAMP_BLUE, 1, threads=16)
+    d_old, d_new = torch.from_numpy(old).to(dev), torch.from_numpy(new).to(dev)
+    t = pl.submit(d_old.data_ptr(), 24, 512, 640, p, STAGE_ALL)
+    check_batch(oracle, old, *pl.collect(t))
+    submitted = pl.get_info().submitted
+    with pytest.raises(RmcvError) as e:
+        pl.submit(d_new.data_ptr(), 9, 720, 1280, p, STAGE_ALL | STAGE_IDENTITY)  # no SVM loaded
+    assert e.value.code == abi.ERR_BAD_ARG
+    assert pl.get_info().submitted == submitted
+    for fr, d in [(old, d_old), (new, d_new), (old, d_old)]:
+        n, h, w, _ = fr.shape
+        t = pl.submit(d.data_ptr(), n, h, w, p, STAGE_ALL)
+        check_batch(oracle, fr, *pl.collect(t))
+    pl.close()
+
+
 def test_hot_contexts_config_and_switch():
     """rmcv_pipeline_config::hot_contexts: the default, off, out of range, what it needs; rmcv_pipeline_set_hot_contexts at run time"""
     import torch
