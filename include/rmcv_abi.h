@@ -219,7 +219,8 @@ const char* rmcv_last_error(const rmcv_ctx* ctx);
 #define RMCV_OPT_TEST_DELAY_US 16
 /* RMCV_OPT_INPUT_FORMAT: what the frame pointers of this context hold -- RMCV_INPUT_BGR (0, default): CV_8UC3 BGR, 3 bytes per
  * pixel; or one of the four RMCV_BAYER_* patterns: a raw 8-bit mosaic straight from the sensor, 1 byte per pixel (rows `stride >= w`
- * bytes apart, frames `frame_pitch >= stride * (h - 1) + w` apart, w >= 3, h >= 3; no 10/12-bit data, no mirror, no flip).  Every
+ * bytes apart, frames `frame_pitch >= stride * (h - 1) + w` apart, w >= 3, h >= 3; 10/12-bit data, mirror and flip: the three
+ * RMCV_OPT_INPUT_* options below).  Every
  * result for a mosaic m is, bit for bit, what the BGR path gives for the frame D(m), the library's demosaic (rmcv_demosaic): bilinear
  * in integers as OpenCV's 8-bit COLOR_Bayer*2BGR is recalled to do it (not pinned against OpenCV), the outermost rows and columns
  * repeating their interior neighbour.  The pixel kernel reads the mosaic itself (k_binary_bayer: 1 B/px instead of 3); no colour frame
@@ -236,6 +237,30 @@ const char* rmcv_last_error(const rmcv_ctx* ctx);
 #define RMCV_BAYER_GB 2 /* G B / R G */
 #define RMCV_BAYER_GR 3 /* G R / B G */
 #define RMCV_BAYER_BG 4 /* B G / G R */
+/* The raw frame AS THE SENSOR DELIVERS IT (Bayer formats only).  A delivered buffer r of w x h samples is read as the 8-bit mosaic
+ *     T(r)(x, y) = n(r(mirror ? w-1-x : x, flip ? h-1-y : y)),     n(s) = s for 1-byte samples, (s >> valid_bit) & 0xFF for 2-byte ones
+ * and every result for r is, bit for bit, what the 8-bit Bayer path gives for the mosaic T(r): all coordinates (byte image, contour
+ * points, blobs, armours, icons, poses) are those of the ORIENTED frame.  The pattern of RMCV_OPT_INPUT_FORMAT stays that of the buffer
+ * as delivered (what the SDK reports as the colour filter); the library derives the pattern of T(r): the R site's column parity becomes
+ * (w-1-rx) & 1 under mirror, its row parity (h-1-ry) & 1 under flip.  The pixel kernel does all of it while it loads; no oriented or
+ * narrowed copy is ever made.
+ *   RMCV_OPT_INPUT_SAMPLE_BITS  8 (default) or 16: bytes per sample 1 or 2, little-endian.  With 16, `stride` and `frame_pitch` stay
+ *                               in BYTES: stride >= 2 w and even, frame_pitch >= stride (h-1) + 2 w and even, frame pointers 2-byte
+ *                               aligned; anything else is RMCV_ERR_BAD_ARG.
+ *   RMCV_OPT_INPUT_VALID_BIT    0 (default) .. 4, the Daheng SDK's DX_VALID_BIT values (DX_BIT_0_7 .. DX_BIT_4_11): bits v .. v+7 of a
+ *                               16-bit sample are the pixel.  Bits above the window are DROPPED (the literal reading of the vendor
+ *                               header's "bit 2~9"); what the SDK's closed DxRaw16toRaw8 does with them is not known and not pinned --
+ *                               for data inside its nominal depth (12-bit data with DX_BIT_4_11, 10-bit with DX_BIT_2_9) dropping and
+ *                               saturating agree.  Read only with 16-bit samples.
+ *   RMCV_OPT_INPUT_ORIENT       bit 0 RMCV_ORIENT_MIRROR (left-right), bit 1 RMCV_ORIENT_FLIP (top-bottom); 0 (default): as delivered.
+ * Like the format they are recorded when frames are bound and read per call by rmcv_extract_color / rmcv_classify_armours.  Unknown
+ * values are refused and leave the option as it was.  BGR frames have neither: binding or reading a BGR frame while the sample bits
+ * are not 8 or the orientation is not 0 is RMCV_ERR_BAD_ARG (the reference's BGR frames are already oriented). */
+#define RMCV_OPT_INPUT_SAMPLE_BITS 20
+#define RMCV_OPT_INPUT_VALID_BIT 21
+#define RMCV_OPT_INPUT_ORIENT 22
+#define RMCV_ORIENT_MIRROR 1
+#define RMCV_ORIENT_FLIP 2
 int  rmcv_ctx_set_option(rmcv_ctx* ctx, int option, int value);
 /* launches of k_binary_ws (RMCV_OPT_PIXEL_SHAPE 1) by this process so far: a diagnostic -- an option that is set but whose
  * conditions a batch does not meet falls back to k_binary silently (tests/test_gpu_pixel_shape.py) */
@@ -281,6 +306,11 @@ int rmcv_fit_ellipse(rmcv_ctx* ctx, const rmcv_point* pts, int n, rmcv_rrect* ou
  * colour frame (a recorder).  raw: h rows of `stride >= w` bytes; bgr_out: h rows of `out_stride >= 3 w` bytes; w, h >= 3;
  * pattern RMCV_BAYER_RG .. RMCV_BAYER_BG.  Independent of the context's RMCV_OPT_INPUT_FORMAT. */
 int rmcv_demosaic(rmcv_ctx* ctx, const uint8_t* raw, int w, int h, int stride, int pattern, uint8_t* bgr_out, int out_stride);
+/* D(T(r)) of one delivered host buffer r (RMCV_OPT_INPUT_SAMPLE_BITS / _VALID_BIT / _ORIENT above, here as arguments): the BGR frame
+ * of the ORIENTED mosaic.  pattern: that of r as delivered.  sample_bits 8 or 16 (then `stride >= 2 w` bytes and even, raw 2-byte
+ * aligned), valid_bit 0 .. 4 (read only with 16), orient a combination of RMCV_ORIENT_*.  Independent of the context's options. */
+int rmcv_demosaic_raw(rmcv_ctx* ctx, const void* raw, int w, int h, int stride, int pattern, int sample_bits, int valid_bit, int orient,
+                      uint8_t* bgr_out, int out_stride);
 
 /* ---- batch of independent frames, resident on the device ------------------------------ */
 

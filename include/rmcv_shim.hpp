@@ -15,7 +15,8 @@
 // Default arguments stay on the reference's declarations (include/objdetect.h:22-37, include/mobility.h:106-108).
 // Also the legacy matcher rm::MatchLightBlob / rm::FindLightBlobs / rm::LightBlobOverlap (include/objdetect.h:22-37, 62)
 // and rm::solve_PnP (include/mobility.h:106-108).
-// One addition the reference does not have: rm::extract_color_bayer, rm::extract_color on a raw 8-bit Bayer mosaic (CV_8UC1).
+// One addition the reference does not have: rm::extract_color_bayer, rm::extract_color on a raw 8-bit Bayer mosaic (CV_8UC1), and
+// rm::extract_color_raw, the same on the sensor's buffer as delivered (8- or 16-bit samples, to be mirrored and / or flipped).
 // The legacy names of the north star are aliased at the bottom (docs/core_8h_source.html:101,114).
 //
 // Every signature mentions cv:: types, so this header only compiles where OpenCV headers exist.
@@ -135,6 +136,36 @@ RMCV_SHIM_LINKAGE std::tuple<std::vector<contour>, cv::Mat> extract_color_bayer(
     } restore;
     return hip_detail::extract(img, target, lower_bound);
 }
+
+// The same on the buffer exactly as the sensor delivers it (frameData.pImgBuf of the reference's hardware/src/daheng.cpp): CV_8UC1, or
+// CV_16UC1 for the 10/12-bit formats with the SDK's DX_VALID_BIT value (0 .. 4; ignored for CV_8UC1), plus the `mirror` / `flip`
+// arguments of camera.capture().  `pattern` is the colour filter of the buffer as delivered; the results -- the binary image and the
+// contour coordinates -- are those of the ORIENTED frame, as the reference's detection sees it (include/rmcv_abi.h:
+// RMCV_OPT_INPUT_SAMPLE_BITS / _VALID_BIT / _ORIENT).  All four options are the thread's for this call only.
+// (Guarded: only where the cv:: headers in use know 16-bit matrices.)
+#ifdef CV_16UC1
+RMCV_SHIM_LINKAGE std::tuple<std::vector<contour>, cv::Mat> extract_color_raw(cv::InputArray raw, int pattern, int valid_bit, bool mirror, bool flip,
+                                                                              camp target, int lower_bound)
+{
+    cv::Mat img = raw.getMat();
+    CV_Assert(img.type() == CV_8UC1 || img.type() == CV_16UC1);
+    struct Restore { // back to 8-bit BGR as delivered however the call ends (a refused value below included)
+        ~Restore()
+        {
+            rmcv_ctx_set_option(hip_detail::ctx(), RMCV_OPT_INPUT_FORMAT, RMCV_INPUT_BGR);
+            rmcv_ctx_set_option(hip_detail::ctx(), RMCV_OPT_INPUT_SAMPLE_BITS, 8);
+            rmcv_ctx_set_option(hip_detail::ctx(), RMCV_OPT_INPUT_VALID_BIT, 0);
+            rmcv_ctx_set_option(hip_detail::ctx(), RMCV_OPT_INPUT_ORIENT, 0);
+        }
+    } restore;
+    const bool wide = img.type() == CV_16UC1;
+    hip_detail::check(rmcv_ctx_set_option(hip_detail::ctx(), RMCV_OPT_INPUT_FORMAT, pattern));
+    hip_detail::check(rmcv_ctx_set_option(hip_detail::ctx(), RMCV_OPT_INPUT_SAMPLE_BITS, wide ? 16 : 8));
+    hip_detail::check(rmcv_ctx_set_option(hip_detail::ctx(), RMCV_OPT_INPUT_VALID_BIT, wide ? valid_bit : 0));
+    hip_detail::check(rmcv_ctx_set_option(hip_detail::ctx(), RMCV_OPT_INPUT_ORIENT, (mirror ? RMCV_ORIENT_MIRROR : 0) | (flip ? RMCV_ORIENT_FLIP : 0)));
+    return hip_detail::extract(img, target, lower_bound);
+}
+#endif
 
 RMCV_SHIM_LINKAGE auto filter_lightblobs(const std::vector<contour>& contours, const float tilt_max, const range<float> ratio_range,
                               const range<double> area_range, camp enemy)

@@ -47,13 +47,18 @@ OPT_INPUT_FORMAT = 19
 # RMCV_OPT_INPUT_FORMAT values: BGR frames, or a raw 8-bit mosaic named by its top-left 2x2 block (the Daheng SDK's DX_PIXEL_COLOR_FILTER values)
 INPUT_BGR, BAYER_RG, BAYER_GB, BAYER_GR, BAYER_BG = 0, 1, 2, 3, 4
 BAYER_PATTERNS = (BAYER_RG, BAYER_GB, BAYER_GR, BAYER_BG)
+# the Bayer frame as the sensor delivers it: 8- or 16-bit samples, the pixel's first bit in a 16-bit sample (the Daheng SDK's DX_VALID_BIT, 0..4), mirror / flip
+OPT_INPUT_SAMPLE_BITS = 20
+OPT_INPUT_VALID_BIT = 21
+OPT_INPUT_ORIENT = 22
+ORIENT_MIRROR, ORIENT_FLIP = 1, 2
 STAGE_BINARY, STAGE_CONTOURS, STAGE_BLOBS, STAGE_ARMOURS, STAGE_ALL, STAGE_IDENTITY, STAGE_POSE, STAGE_NO_IMAGE = 1, 2, 4, 8, 15, 16, 32, 64
 SVM_FEATURES = 1200
 FRAME_OVF_CONTOURS, FRAME_OVF_POINTS, FRAME_OVF_BLOBS, FRAME_OVF_ARMOURS, FRAME_SLOW_PATH, FRAME_MID_PATH = 1, 2, 4, 8, 16, 64
 
 EXPORTS = [
     "rmcv_abi_version", "rmcv_default_params", "rmcv_default_limits", "rmcv_ctx_create", "rmcv_ctx_destroy",
-    "rmcv_last_error", "rmcv_ctx_set_option", "rmcv_ctx_forget_frame_buffer", "rmcv_ctx_check_guards", "rmcv_ctx_frame_timing", "rmcv_extract_color", "rmcv_filter_lightblobs", "rmcv_filter_armours", "rmcv_fit_ellipse", "rmcv_demosaic",
+    "rmcv_last_error", "rmcv_ctx_set_option", "rmcv_ctx_forget_frame_buffer", "rmcv_ctx_check_guards", "rmcv_ctx_frame_timing", "rmcv_extract_color", "rmcv_filter_lightblobs", "rmcv_filter_armours", "rmcv_fit_ellipse", "rmcv_demosaic", "rmcv_demosaic_raw",
     "rmcv_batch_upload", "rmcv_batch_set_device_frames", "rmcv_batch_run", "rmcv_batch_sync", "rmcv_batch_run_timed",
     "rmcv_batch_counts", "rmcv_batch_get_binary", "rmcv_batch_get_contours", "rmcv_batch_get_blobs",
     "rmcv_batch_get_armours", "rmcv_batch_device_views", "rmcv_batch_compact_armours", "rmcv_synth_frame", "rmcv_synth_checksum",
@@ -158,6 +163,9 @@ def load(path):
     if hasattr(L, "rmcv_demosaic"):  # (builds from before raw Bayer input stay loadable for A/B runs)
         L.rmcv_demosaic.restype = C.c_int
         L.rmcv_demosaic.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    if hasattr(L, "rmcv_demosaic_raw"):
+        L.rmcv_demosaic_raw.restype = C.c_int
+        L.rmcv_demosaic_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L

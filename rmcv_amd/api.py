@@ -35,6 +35,7 @@ class Context:
         self.device = device
         self._frames_ref = None
         self.input_format = abi.INPUT_BGR
+        self.sample_bits = 8
 
     @classmethod
     def borrowed(cls, handle, limits, device=0):
@@ -42,6 +43,7 @@ class Context:
         self = cls.__new__(cls)
         self.limits, self._h, self._made_by, self.device, self._frames_ref, self._borrowed = limits, C.c_void_p(handle), lib(), device, None, True
         self.input_format = abi.INPUT_BGR
+        self.sample_bits = 8
         return self
 
     def close(self):
@@ -69,12 +71,13 @@ class Context:
         return [xy[offs[i]:offs[i + 1]] for i in range(len(offs) - 1)], binary
 
     def _frame(self, image):
-        """(image, h, w, row bytes) of one host frame: (h, w, 3) BGR, or (h, w) under a Bayer input format"""
-        image = np.ascontiguousarray(image, np.uint8)
+        """(image, h, w, row bytes) of one host frame: (h, w, 3) BGR, or (h, w) under a Bayer input format (uint16 with 16-bit samples)"""
         if self.input_format:
-            assert image.ndim == 2, "a Bayer input format takes (h, w) uint8 mosaics"
+            image = np.ascontiguousarray(image, self._sample_dtype())
+            assert image.ndim == 2, "a Bayer input format takes (h, w) mosaics"
             h, w = image.shape
-            return image, h, w, w
+            return image, h, w, w * image.itemsize
+        image = np.ascontiguousarray(image, np.uint8)
         h, w, ch = image.shape
         assert ch == 3
         return image, h, w, 3 * w
@@ -83,6 +86,29 @@ class Context:
         """RMCV_OPT_INPUT_FORMAT: abi.INPUT_BGR (0) or one of abi.BAYER_PATTERNS -- what the frames handed in from now on hold"""
         self.set_option(abi.OPT_INPUT_FORMAT, fmt)
         self.input_format = int(fmt)
+
+    def _sample_dtype(self):
+        return np.dtype("<u2") if self.sample_bits == 16 else np.dtype(np.uint8)
+
+    def set_input_layout(self, sample_bits=8, valid_bit=0, mirror=False, flip=False):
+        """the Bayer frame as the sensor delivers it (RMCV_OPT_INPUT_SAMPLE_BITS / _VALID_BIT / _ORIENT): 8- or 16-bit samples, the
+        first of the 8 bits of a 16-bit sample that are the pixel (0 .. 4), mirrored left-right and / or flipped top-bottom.  Every
+        result is that of the oriented 8-bit mosaic; the pattern of set_input_format stays that of the buffer as delivered."""
+        self.set_option(abi.OPT_INPUT_SAMPLE_BITS, sample_bits)
+        self.sample_bits = int(sample_bits)
+        self.set_option(abi.OPT_INPUT_VALID_BIT, valid_bit)
+        self.set_option(abi.OPT_INPUT_ORIENT, (abi.ORIENT_MIRROR if mirror else 0) | (abi.ORIENT_FLIP if flip else 0))
+
+    def demosaic_raw(self, raw, pattern, valid_bit=0, mirror=False, flip=False):
+        """D(T(r)) of one delivered (h, w) uint8 or uint16 buffer as the (h, w, 3) BGR frame of the oriented mosaic (rmcv_demosaic_raw)"""
+        raw = np.asarray(raw)
+        bits = 16 if raw.dtype.itemsize == 2 else 8
+        raw = np.ascontiguousarray(raw, np.dtype("<u2") if bits == 16 else np.uint8)
+        h, w = raw.shape
+        out = np.empty((h, w, 3), np.uint8)
+        orient = (abi.ORIENT_MIRROR if mirror else 0) | (abi.ORIENT_FLIP if flip else 0)
+        self._chk(lib().rmcv_demosaic_raw(self._h, ptr(raw), w, h, w * raw.itemsize, int(pattern), bits, int(valid_bit), orient, ptr(out), 3 * w))
+        return out
 
     def demosaic(self, raw, pattern):
         """D(m) of one (h, w) uint8 mosaic as an (h, w, 3) BGR frame (rmcv_demosaic: the library's demosaic, on the GPU)"""
@@ -297,13 +323,15 @@ class Context:
 
     # ---------------------------------------------------------------- batch
     def upload(self, frames):
-        """frames: uint8 [n, h, w, 3] on the host (or [n, h, w] mosaics under a Bayer input format) -> the context's HBM buffer"""
-        frames = np.ascontiguousarray(frames, np.uint8)
+        """frames: uint8 [n, h, w, 3] on the host (or [n, h, w] mosaics under a Bayer input format, uint16 with 16-bit samples) -> the
+        context's HBM buffer"""
         if self.input_format:
-            assert frames.ndim == 3, "a Bayer input format takes (n, h, w) uint8 mosaics"
+            frames = np.ascontiguousarray(frames, self._sample_dtype())
+            assert frames.ndim == 3, "a Bayer input format takes (n, h, w) mosaics"
             n, h, w = frames.shape
-            rowb = w
+            rowb = w * frames.itemsize
         else:
+            frames = np.ascontiguousarray(frames, np.uint8)
             n, h, w, ch = frames.shape
             assert ch == 3
             rowb = 3 * w
@@ -311,8 +339,9 @@ class Context:
         self.shape = (n, h, w)
 
     def bind_device_frames(self, data_ptr, n, h, w, stride=None, frame_pitch=None, keepalive=None):
-        """borrow frames already in HBM (e.g. torch_tensor.data_ptr()); the default stride is 3 w, w under a Bayer input format"""
-        stride = stride or (w if self.input_format else 3 * w)
+        """borrow frames already in HBM (e.g. torch_tensor.data_ptr()); strides are bytes, the default is 3 w, under a Bayer input
+        format w (2 w with 16-bit samples)"""
+        stride = stride or (w * self.sample_bits // 8 if self.input_format else 3 * w)
         frame_pitch = frame_pitch or stride * h
         self._frames_ref = keepalive
         self._chk(lib().rmcv_batch_set_device_frames(self._h, C.c_void_p(data_ptr), n, w, h, stride, C.c_int64(frame_pitch)))

@@ -22,9 +22,10 @@ struct WarpCtx {
     const uint8_t* roi; // frame + by*stride + 3*bx
     int stride, bw, bh;
     double M[6]; // inverted map
-    // a Bayer frame (RMCV_OPT_INPUT_FORMAT): the mosaic, its size, the ROI's corner in it and the pattern's R site (device_bayer.h)
+    // a Bayer frame (RMCV_OPT_INPUT_FORMAT): the mosaic, its size, the ROI's corner in it, the R site of the oriented mosaic and the
+    // layout word of the buffer (device_bayer.h)
     const uint8_t* frame;
-    int fw, fh, bx, by, rx, ry;
+    int fw, fh, bx, by, rx, ry, lay;
 };
 
 // one channel triple of the warped ROI at (x, y): cv::warpAffine INTER_LINEAR, BORDER_CONSTANT 0, CV_8UC3.  BAYER: the ROI's pixels
@@ -48,10 +49,10 @@ __device__ inline void warp_px(const WarpCtx& W, int x, int y, int out[3])
     if constexpr (BAYER) {
         int q00[3] = {0, 0, 0}, q01[3] = {0, 0, 0}, q10[3] = {0, 0, 0}, q11[3] = {0, 0, 0};
         const int X0 = W.bx + sx, Y0 = W.by + sy;
-        if (y0ok && x0ok) bayer_bgr(W.frame, W.stride, W.fw, W.fh, W.rx, W.ry, X0, Y0, q00);
-        if (y0ok && x1ok) bayer_bgr(W.frame, W.stride, W.fw, W.fh, W.rx, W.ry, X0 + 1, Y0, q01);
-        if (y1ok && x0ok) bayer_bgr(W.frame, W.stride, W.fw, W.fh, W.rx, W.ry, X0, Y0 + 1, q10);
-        if (y1ok && x1ok) bayer_bgr(W.frame, W.stride, W.fw, W.fh, W.rx, W.ry, X0 + 1, Y0 + 1, q11);
+        if (y0ok && x0ok) bayer_bgr_raw(W.frame, W.stride, W.fw, W.fh, W.rx, W.ry, W.lay, X0, Y0, q00);
+        if (y0ok && x1ok) bayer_bgr_raw(W.frame, W.stride, W.fw, W.fh, W.rx, W.ry, W.lay, X0 + 1, Y0, q01);
+        if (y1ok && x0ok) bayer_bgr_raw(W.frame, W.stride, W.fw, W.fh, W.rx, W.ry, W.lay, X0, Y0 + 1, q10);
+        if (y1ok && x1ok) bayer_bgr_raw(W.frame, W.stride, W.fw, W.fh, W.rx, W.ry, W.lay, X0 + 1, Y0 + 1, q11);
 #pragma unroll
         for (int c = 0; c < 3; c++) {
             const int v = (q00[c] * w00 + q01[c] * w01 + q10[c] * w10 + q11[c] * w11 + (1 << 14)) >> 15;
@@ -83,10 +84,10 @@ struct ClassifyArgs { // what the classification of a frame's armours needs (Buf
 ClassifyArgs classify_args(const Geom& g, const Bufs& b); // k_classify.hip
 
 // armours wave, wave + nwaves, ... of frame f by this wavefront.  feat: NFEAT floats, sums: 32 doubles of wave-private LDS.
-// BAYER: the frames are mosaics of pattern `pattern` (the stand-alone k_classify only: the sparse kernel classifies BGR frames)
+// BAYER: the frames are mosaics of pattern `pattern` in the layout `lay` (the stand-alone k_classify only: the sparse kernel classifies BGR frames)
 template <int BAYER = 0>
 __device__ inline void classify_frame(int f, int lane, int wave, int nwaves, int n, const ClassifyArgs& C, rmcv_armour* __restrict__ armours,
-                                      int max_armours, float* feat, double* sums, int pattern = 0)
+                                      int max_armours, float* feat, double* sums, int pattern = 0, int lay = 0)
 {
     const uint8_t* frame = C.frames + (int64_t)f * C.frame_pitch;
     const int w = C.w, h = C.h, stride = C.stride, n_class = C.n_class;
@@ -126,8 +127,9 @@ __device__ inline void classify_frame(int f, int lane, int wave, int nwaves, int
             W.fh = h;
             W.bx = bx;
             W.by = by;
-            W.rx = bayer_rx(pattern);
-            W.ry = bayer_ry(pattern);
+            W.rx = raw_rx(pattern, lay, w);
+            W.ry = raw_ry(pattern, lay, h);
+            W.lay = lay;
         }
         {
             const float src[3][2] = {{ic[1][0] - (float)bx, ic[1][1] - (float)by},

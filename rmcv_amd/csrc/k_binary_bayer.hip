@@ -1,4 +1,5 @@
-// k_binary_bayer.hip -- K1 for raw 8-bit Bayer frames (RMCV_OPT_INPUT_FORMAT 1..4): demosaic + split + saturating channel subtract
+// k_binary_bayer.hip -- K1 for raw Bayer frames (RMCV_OPT_INPUT_FORMAT 1..4; 8-bit mosaics, or the sensor's own layout -- 16-bit samples,
+// mirror, flip: RMCV_OPT_INPUT_SAMPLE_BITS / _VALID_BIT / _ORIENT, read as the oriented 8-bit mosaic T(r) by the loader): demosaic + split + saturating channel subtract
 // + inRange + 3x3 MORPH_CLOSE in ONE pass over the mosaic.  The contract (include/rmcv_abi.h): every output for a mosaic m equals
 // what k_binary gives for the BGR frame D(m) (device_bayer.h), so this kernel writes exactly what k_binary writes -- the byte image
 // (unless RMCV_STAGE_NO_IMAGE), the padded plane F and the row masks -- and everything downstream is the BGR path's.
@@ -70,12 +71,24 @@ __device__ __forceinline__ uint32_t bayer_mask16(const Row& a, const Row& b, con
 // below 4 GiB: unconditional raw-buffer loads (dwordx4 per lane); otherwise bounds-checked byte loads (any w and stride, e.g. 5-pixel
 // rows).
 // Register budget as k_binary's (k_binary.hip: at most 80 VGPRs, so that the sparse kernel of the previous batch fits beside it).
-template <int CA, int CB, int VEC>
+//
+// LD, the phase-1 loader.  0 and 1 read a plain 8-bit mosaic as delivered (1 = VEC above, 0 = byte-wise).  2 and 4..7 read the sensor's
+// own layout (device_bayer.h: 2-byte samples narrowed to their valid window, mirror, flip) and hand phases 1-4 the same Row of the
+// ORIENTED mosaic T(r); the launcher passes the R site of T(r) and the layout word in the bits of `ry` above bit 0:
+//   flip    the source row is h-1-y: run-time in all of them
+//   2       byte-wise, any width, stride and layout (all run-time; with mirror the ragged end of a row sits in the first lane)
+//   4 | MIR | S16 << 1   dwordx4 loads under the same alignment rules as 1.  MIR: a lane's 16 oriented pixels are 16 consecutive source
+//           samples read backwards -- loaded at the mirrored offset, the dwords swapped and byte-reversed (v_perm_b32).  S16: two
+//           dwordx4 per lane and row, each dword shifted by the (wave-uniform) valid bit and the two window bytes of each pair of
+//           dwords packed by one v_perm_b32.  The neighbour exchange and the wave-edge loads work in oriented coordinates.
+template <int CA, int CB, int LD>
 __global__ __launch_bounds__(256, 6) void k_binary_bayer(const uint8_t* __restrict__ frames, int64_t frame_pitch, int stride, int n_frames,
                                                          int w, int h, int ww, int rx, int ry, int lb, int all_pass, int morph,
                                                          uint8_t* __restrict__ binary, uint64_t* __restrict__ bits, int prow,
                                                          int64_t plane_pitch, int strips, int sr, uint32_t* __restrict__ rowmask)
 {
+    constexpr bool VEC = LD == 1 || LD >= 4, RAW = LD >= 2, MIR = LD >= 4 && (LD & 1), S16 = LD >= 4 && (LD & 2);
+    const int lay = RAW ? ry >> 1 : 0; // (RAW only: the layout word; bit 0 of ry is the row parity of the R site everywhere below)
     extern __shared__ uint64_t smem[];
     const int halo = morph; // NONE 0, DILATE 1, CLOSE 2
     uint64_t* T = smem;
@@ -98,7 +111,7 @@ __global__ __launch_bounds__(256, 6) void k_binary_bayer(const uint8_t* __restri
         const int items = nb * wq;
         uint16_t* T16 = reinterpret_cast<uint16_t*>(T);
         const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(
-            const_cast<uint8_t*>(frames), 0, VEC ? (int)((int64_t)(n_frames - 1) * frame_pitch + (int64_t)(h - 1) * stride + w) : 0, B_RSRC3);
+            const_cast<uint8_t*>(frames), 0, VEC ? (int)((int64_t)(n_frames - 1) * frame_pitch + (int64_t)(h - 1) * stride + (S16 ? 2 * w : w)) : 0, B_RSRC3);
         const uint32_t fbase = VEC ? (uint32_t)((int64_t)f * frame_pitch) : 0u;
         for (int it0 = tid - lane; it0 < items; it0 += 256) { // wave-uniform loop: every lane takes part in the exchanges
             const int it = it0 + lane;
@@ -109,7 +122,63 @@ __global__ __launch_bounds__(256, 6) void k_binary_bayer(const uint8_t* __restri
             // one mosaic row of this lane's 16 pixels + its two neighbours; yrow < 0: nothing (zeros, no traffic)
             auto load_row = [&](int yrow) -> Row {
                 Row R;
-                if (VEC) {
+                if constexpr (RAW && VEC) {
+                    const bool ok = yrow >= 0 && live && x0 < w;
+                    const uint32_t rowoff = fbase + (uint32_t)((lay & LAY_FLIP) ? h - 1 - yrow : yrow) * (uint32_t)stride;
+                    const uint32_t off = ok ? rowoff + (uint32_t)(MIR ? w - 16 - x0 : x0) * (S16 ? 2u : 1u) : B_OOB;
+                    if constexpr (S16) {
+                        const u32x4b v0 = __builtin_amdgcn_raw_buffer_load_b128(r_in, off, 0, 0);
+                        const u32x4b v1 = __builtin_amdgcn_raw_buffer_load_b128(r_in, ok ? off + 16u : B_OOB, 0, 0);
+                        const int vb = lay_vbit(lay);
+                        const uint32_t t[8] = {v0.x >> vb, v0.y >> vb, v0.z >> vb, v0.w >> vb, v1.x >> vb, v1.y >> vb, v1.z >> vb, v1.w >> vb};
+#pragma unroll
+                        for (int k = 0; k < 4; k++) // bytes 0 and 2 of a shifted dword are the windows of its two samples
+                            R.d[k] = MIR ? __builtin_amdgcn_perm(t[7 - 2 * k], t[6 - 2 * k], 0x00020406u) : __builtin_amdgcn_perm(t[2 * k + 1], t[2 * k], 0x06040200u);
+                    } else {
+                        const u32x4b v = __builtin_amdgcn_raw_buffer_load_b128(r_in, off, 0, 0);
+                        if (MIR) {
+                            R.d[0] = __builtin_amdgcn_perm(0u, v.w, 0x00010203u); R.d[1] = __builtin_amdgcn_perm(0u, v.z, 0x00010203u);
+                            R.d[2] = __builtin_amdgcn_perm(0u, v.y, 0x00010203u); R.d[3] = __builtin_amdgcn_perm(0u, v.x, 0x00010203u);
+                        } else { R.d[0] = v.x; R.d[1] = v.y; R.d[2] = v.z; R.d[3] = v.w; }
+                    }
+                    // the neighbours, in oriented coordinates as below: from the lanes beside, the wave's edge lanes load one sample
+                    const int from_l = __shfl((int)(R.d[3] >> 24), lane - 1 < 0 ? 0 : lane - 1);
+                    const int from_r = __shfl((int)(R.d[0] & 0xFFu), lane + 1 > 63 ? 63 : lane + 1);
+                    int xc = -1; // the oriented column an edge lane loads (columns -1 and >= w: nothing)
+                    if (ok && lane == 0 && x0 > 0) xc = x0 - 1;
+                    if (ok && lane == 63 && x0 + 16 < w) xc = x0 + 16;
+                    const uint32_t eo = xc >= 0 ? rowoff + (uint32_t)(MIR ? w - 1 - xc : xc) * (S16 ? 2u : 1u) : B_OOB;
+                    int edge;
+                    if constexpr (S16) edge = ((int)__builtin_amdgcn_raw_buffer_load_b16(r_in, eo, 0, 0) >> lay_vbit(lay)) & 0xFF;
+                    else edge = (int)__builtin_amdgcn_raw_buffer_load_b8(r_in, eo, 0, 0);
+                    R.l = lane == 0 ? edge : from_l;
+                    R.r = lane == 63 ? edge : from_r;
+                } else if constexpr (RAW) {
+                    const bool ok = yrow >= 0 && live;
+                    const uint8_t* p = frame + (int64_t)(yrow < 0 ? 0 : (lay & LAY_FLIP) ? h - 1 - yrow : yrow) * stride;
+                    // the sample of oriented column x: source column x, or w-1-x mirrored; sgn / xm and the shifts are wave-uniform
+                    const int vb = lay_vbit(lay), sh = (lay & LAY_S16) ? 1 : 0, sgn = (lay & LAY_MIRROR) ? -1 : 1, xm = (lay & LAY_MIRROR) ? w - 1 : 0;
+                    auto px = [&](int x) -> uint32_t {
+                        const uint8_t* q = p + ((xm + sgn * x) << sh);
+                        return sh ? (uint32_t)(*reinterpret_cast<const uint16_t*>(q) >> vb) & 0xFFu : (uint32_t)*q;
+                    };
+                    // (rolled, the dwords rotating through: this loader is the fallback for odd geometry and has to stay inside the
+                    // register budget with three rows live)
+                    uint32_t d0 = 0, d1 = 0, d2 = 0, d3 = 0;
+#pragma unroll 1
+                    for (int k = 0; k < 4; k++) {
+                        uint32_t dw = 0;
+#pragma unroll 1
+                        for (int j = 0; j < 4; j++) {
+                            const int x = x0 + 4 * k + j;
+                            if (ok && x < w) dw |= px(x) << (8 * j);
+                        }
+                        d0 = d1; d1 = d2; d2 = d3; d3 = dw;
+                    }
+                    R.d[0] = d0; R.d[1] = d1; R.d[2] = d2; R.d[3] = d3;
+                    R.l = (ok && x0 > 0 && x0 - 1 < w) ? (int)px(x0 - 1) : 0;
+                    R.r = (ok && x0 + 16 < w) ? (int)px(x0 + 16) : 0;
+                } else if (VEC) {
                     const uint32_t off = (yrow >= 0 && live) ? fbase + (uint32_t)yrow * (uint32_t)stride + (uint32_t)x0 : B_OOB;
                     const u32x4b v = __builtin_amdgcn_raw_buffer_load_b128(r_in, off, 0, 0);
                     R.d[0] = v.x; R.d[1] = v.y; R.d[2] = v.z; R.d[3] = v.w;
@@ -173,7 +242,8 @@ __global__ __launch_bounds__(256, 6) void k_binary_bayer(const uint8_t* __restri
                         uint32_t nb15 = left15;
                         if (lane == 0) {
                             int px3[3];
-                            bayer_bgr(frame, stride, w, h, rx, ry, w - 2, y, px3);
+                            if constexpr (RAW) bayer_bgr_raw(frame, stride, w, h, rx, ry & 1, lay, w - 2, y, px3);
+                            else bayer_bgr(frame, stride, w, h, rx, ry, w - 2, y, px3);
                             nb15 = (uint32_t)(px3[CA] - px3[CB] >= lb);
                         }
                         m = (m & ~1u) | nb15;
@@ -289,8 +359,25 @@ __global__ __launch_bounds__(256) void k_demosaic(const uint8_t* __restrict__ ra
     o[2] = (uint8_t)v[2];
 }
 
-hipError_t launch_demosaic(const uint8_t* d_raw, int stride, int w, int h, int pattern, uint8_t* d_out, int out_stride, hipStream_t s)
+// the same of a delivered buffer: D(T(r)) (rmcv_demosaic_raw)
+__global__ __launch_bounds__(256) void k_demosaic_raw(const uint8_t* __restrict__ raw, int stride, int w, int h, int rx, int ry, int lay,
+                                                      uint8_t* __restrict__ out, int out_stride)
 {
+    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
+    if (x >= w) return;
+    int v[3];
+    bayer_bgr_raw(raw, stride, w, h, rx, ry, lay, x, y, v);
+    uint8_t* o = out + (int64_t)y * out_stride + 3 * x;
+    o[0] = (uint8_t)v[0];
+    o[1] = (uint8_t)v[1];
+    o[2] = (uint8_t)v[2];
+}
+
+hipError_t launch_demosaic(const uint8_t* d_raw, int stride, int w, int h, int pattern, int lay, uint8_t* d_out, int out_stride, hipStream_t s)
+{
+    if (lay)
+        return launch(k_demosaic_raw, dim3((w + 255) / 256, h), dim3(256), 0, s, d_raw, stride, w, h, raw_rx(pattern, lay, w), raw_ry(pattern, lay, h), lay,
+                      d_out, out_stride);
     return launch(k_demosaic, dim3((w + 255) / 256, h), dim3(256), 0, s, d_raw, stride, w, h, bayer_rx(pattern), bayer_ry(pattern), d_out, out_stride);
 }
 
@@ -311,14 +398,22 @@ static hipError_t launch_bayer_t(const Geom& g, const Bufs& b, int lower_bound, 
     const int64_t per_frame = std::max<int64_t>(g.frame_pitch, 1);
     const int chunk = aligned ? (int)std::min<int64_t>(g.n_frames, std::max<int64_t>(1, (lim - 1) / per_frame)) : g.n_frames;
     const bool vec = aligned && (int64_t)chunk * per_frame < lim;
-    static size_t lds_set[MAX_DEVICES][2] = {};
-    if (planes > 60 * 1024 && planes > lds_set[g.device][vec]) {
-        const void* fn = vec ? reinterpret_cast<const void*>(k_binary_bayer<CA, CB, 1>) : reinterpret_cast<const void*>(k_binary_bayer<CA, CB, 0>);
-        const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)planes);
+    // the loader (k_binary_bayer's LD): a plain 8-bit mosaic keeps 0 / 1; the sensor's own layout takes 2 or 4 | mirror | 16-bit << 1
+    const int lay = raw_layout(8 * g.sample_bytes, g.valid_bit, g.orient);
+    const int ld = !lay ? (vec ? 1 : 0) : !vec ? 2 : 4 | ((lay & LAY_MIRROR) ? 1 : 0) | ((lay & LAY_S16) ? 2 : 0);
+    static size_t lds_set[MAX_DEVICES][8] = {};
+    if (planes > 60 * 1024 && planes > lds_set[g.device][ld]) {
+        const void* const fns[8] = {reinterpret_cast<const void*>(k_binary_bayer<CA, CB, 0>), reinterpret_cast<const void*>(k_binary_bayer<CA, CB, 1>),
+                                    reinterpret_cast<const void*>(k_binary_bayer<CA, CB, 2>), nullptr,
+                                    reinterpret_cast<const void*>(k_binary_bayer<CA, CB, 4>), reinterpret_cast<const void*>(k_binary_bayer<CA, CB, 5>),
+                                    reinterpret_cast<const void*>(k_binary_bayer<CA, CB, 6>), reinterpret_cast<const void*>(k_binary_bayer<CA, CB, 7>)};
+        const hipError_t ea = hipFuncSetAttribute(fns[ld], hipFuncAttributeMaxDynamicSharedMemorySize, (int)planes);
         if (ea != hipSuccess) return ea;
-        lds_set[g.device][vec] = planes;
+        lds_set[g.device][ld] = planes;
     }
-    const int rx = bayer_rx(g.input_format), ry = bayer_ry(g.input_format);
+    // the R site of what phases 1-4 see: the mosaic itself, or T(r) with the layout word riding above the row parity
+    const int rx = lay ? raw_rx(g.input_format, lay, g.w) : bayer_rx(g.input_format);
+    const int ry = lay ? raw_ry(g.input_format, lay, g.h) | (lay << 1) : bayer_ry(g.input_format);
     for (int f0 = 0; f0 < g.n_frames; f0 += chunk) {
         const int nf = std::min(chunk, g.n_frames - f0);
         const uint8_t* frames = b.frames + (int64_t)f0 * g.frame_pitch;
@@ -328,7 +423,16 @@ static hipError_t launch_bayer_t(const Geom& g, const Bufs& b, int lower_bound, 
 #define RMCV_KB_LAUNCH(V)                                                                                                                  \
     launch(k_binary_bayer<CA, CB, V>, dim3(nf * strips), dim3(256), planes, s, frames, g.frame_pitch, g.stride, nf, g.w, g.h, g.ww, rx, ry, \
            lb, all_pass, morph, binary, bits, g.prow, g.plane_pitch, strips, sr, rowmask)
-        const hipError_t e = vec ? RMCV_KB_LAUNCH(1) : RMCV_KB_LAUNCH(0);
+        hipError_t e;
+        switch (ld) {
+        case 0: e = RMCV_KB_LAUNCH(0); break;
+        case 1: e = RMCV_KB_LAUNCH(1); break;
+        case 2: e = RMCV_KB_LAUNCH(2); break;
+        case 4: e = RMCV_KB_LAUNCH(4); break;
+        case 5: e = RMCV_KB_LAUNCH(5); break;
+        case 6: e = RMCV_KB_LAUNCH(6); break;
+        default: e = RMCV_KB_LAUNCH(7); break;
+        }
 #undef RMCV_KB_LAUNCH
         if (e != hipSuccess) return e;
     }

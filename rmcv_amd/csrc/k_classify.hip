@@ -23,14 +23,15 @@ __global__ __launch_bounds__(256) void k_classify(ClassifyArgs C, rmcv_armour* _
     classify_frame(f, lane, wave, 4, n_armours[f], C, armours, max_armours, s_feat[wave], s_sum[wave]);
 }
 
-// the same for mosaics (RMCV_OPT_INPUT_FORMAT): the icon's pixels are D(m) of the frame (device_bayer.h)
+// the same for mosaics (RMCV_OPT_INPUT_FORMAT): the icon's pixels are D(m) of the frame (device_bayer.h) -- D(T(r)) of a frame in the
+// sensor's own layout `lay`, in oriented coordinates like the armours
 __global__ __launch_bounds__(256) void k_classify_bayer(ClassifyArgs C, rmcv_armour* __restrict__ armours, const int32_t* __restrict__ n_armours,
-                                                       int max_armours, int pattern)
+                                                       int max_armours, int pattern, int lay)
 {
     __shared__ float s_feat[4][NFEAT];
     __shared__ double s_sum[4][32];
     const int f = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    classify_frame<1>(f, lane, wave, 4, n_armours[f], C, armours, max_armours, s_feat[wave], s_sum[wave], pattern);
+    classify_frame<1>(f, lane, wave, 4, n_armours[f], C, armours, max_armours, s_feat[wave], s_sum[wave], pattern, lay);
 }
 
 ClassifyArgs classify_args(const Geom& g, const Bufs& b)
@@ -54,7 +55,8 @@ ClassifyArgs classify_args(const Geom& g, const Bufs& b)
 hipError_t launch_classify(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s)
 {
     if (g.input_format != RMCV_INPUT_BGR)
-        return launch(k_classify_bayer, dim3(g.n_frames), dim3(256), 0, s, classify_args(g, b), b.armours, b.n_armours, lim.max_armours, g.input_format);
+        return launch(k_classify_bayer, dim3(g.n_frames), dim3(256), 0, s, classify_args(g, b), b.armours, b.n_armours, lim.max_armours, g.input_format,
+                      raw_layout(8 * g.sample_bytes, g.valid_bit, g.orient));
     return launch(k_classify, dim3(g.n_frames), dim3(256), 0, s, classify_args(g, b), b.armours, b.n_armours, lim.max_armours);
 }
 

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "rmcv_internal.h"
+#include "device_bayer.h"
 
 using namespace rmcv;
 
@@ -76,6 +77,9 @@ struct rmcv_ctx {
     int pixel_shape = 1;          // RMCV_OPT_PIXEL_SHAPE
     int dense_defer = 0;          // RMCV_OPT_DENSE_DEFER
     int input_format = 0;         // RMCV_OPT_INPUT_FORMAT: 0 BGR, 1..4 a Bayer pattern (a binding records it in Geom::input_format)
+    int input_sample_bits = 8;    // RMCV_OPT_INPUT_SAMPLE_BITS: 8 or 16   } the Bayer frame as the sensor delivers it; recorded by a
+    int input_valid_bit = 0;      // RMCV_OPT_INPUT_VALID_BIT: 0 .. 4      } binding next to the format (Geom::sample_bytes, valid_bit,
+    int input_orient = 0;         // RMCV_OPT_INPUT_ORIENT: RMCV_ORIENT_*  } orient)
     // Waits with a deadline (round 5): no entry point parks its caller in the runtime without a bound.  `last_what` names the kernel or
     // copy enqueued last (every HIPCHK of an enqueue leaves its label here): a wait that runs out returns RMCV_ERR_TIMEOUT with it.
     int wait_timeout_ms = 5000;   // RMCV_OPT_WAIT_TIMEOUT_MS (0: no deadline)
@@ -390,6 +394,8 @@ int ctx_wait_timeout_ms(const rmcv_ctx* c) { return c->wait_timeout_ms; }
 bool pixel_ws_full(const rmcv_ctx* c, int lower_bound, int pixel_ws) { return binary_ws_full(c->geom, c->bufs, lower_bound, pixel_ws); }
 RunPlan ctx_plan(const rmcv_ctx* c) { return {c->pixel_shape, c->pixel_groups, c->sparse_waves, c->dense_defer ? SPARSE_SPLIT_BOTH : SPARSE_STANDARD}; }
 int ctx_input_format(const rmcv_ctx* c) { return c->input_format; }
+// bytes of one sample of what the context's options describe: 3 per BGR pixel, 1 or 2 per Bayer sample
+static int ctx_pixel_bytes(const rmcv_ctx* c) { return c->input_format ? c->input_sample_bits / 8 : 3; }
 int ctx_compact(rmcv_ctx* c, void* d_armours_out, int cap, void* d_frame_offs, void* d_status_or, hipStream_t s, void* hd_record, int host_head)
 {
     HIPCHK(c, launch_compact_armours(c->geom, c->bufs, c->lim, (rmcv_armour*)d_armours_out, cap, (int32_t*)d_frame_offs, s, (int32_t*)d_status_or, (uint8_t*)hd_record, host_head), "k_compact_armours");
@@ -597,16 +603,37 @@ static inline void image_chunk(long long bytes, int n_chunks, int g, long long* 
 // ENQUEUED: on `as` when the caller (a pipeline) orders this context's work on its own streams and has already made `as` wait for the
 // context's last batch; otherwise on the context's stream, behind a wait for everything the context has in flight and with a wait for
 // them behind (the launches that follow may go to any stream of the caller's).
+// BGR frames have no sample size and no orientation of their own: a context left at 16 bits or mirrored / flipped would read them wrongly
+static int check_layout(rmcv_ctx* c)
+{
+    if (c->input_format != RMCV_INPUT_BGR) return RMCV_OK;
+    if (c->input_sample_bits != 8) return fail(c, RMCV_ERR_BAD_ARG, "a BGR frame with RMCV_OPT_INPUT_SAMPLE_BITS = 16: the option is for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
+    if (c->input_orient != 0) return fail(c, RMCV_ERR_BAD_ARG, "a BGR frame with RMCV_OPT_INPUT_ORIENT set: the option is for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
+    return RMCV_OK;
+}
+// a frame pointer of 2-byte samples
+static int check_sample_ptr(rmcv_ctx* c, const void* p)
+{
+    if (c->input_format && c->input_sample_bits == 16 && ((uintptr_t)p & 1))
+        return fail(c, RMCV_ERR_BAD_ARG, "16-bit samples (RMCV_OPT_INPUT_SAMPLE_BITS): the frame pointer must be 2-byte aligned");
+    return RMCV_OK;
+}
+
 static int set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t as = nullptr)
 {
     if (n_frames < 1 || n_frames > c->lim.max_frames) return fail(c, RMCV_ERR_BAD_ARG, "n_frames out of range");
     if (w < 1 || h < 1 || w > c->lim.max_width || h > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, "frame size out of range");
-    const int bpp = c->input_format ? 1 : 3; // bytes per pixel of what is bound (RMCV_OPT_INPUT_FORMAT)
+    { const int rcl = check_layout(c); if (rcl) return rcl; }
+    const int bpp = ctx_pixel_bytes(c); // bytes per pixel of what is bound (RMCV_OPT_INPUT_FORMAT, RMCV_OPT_INPUT_SAMPLE_BITS)
     if (c->input_format && (w < 3 || h < 3)) return fail(c, RMCV_ERR_BAD_ARG, "a Bayer frame needs w >= 3 and h >= 3");
     if (stride < bpp * w || frame_pitch < (int64_t)stride * (h - 1) + bpp * w) return fail(c, RMCV_ERR_BAD_ARG, "bad stride/pitch");
+    if (bpp == 2 && ((stride & 1) || (frame_pitch & 1))) return fail(c, RMCV_ERR_BAD_ARG, "16-bit samples (RMCV_OPT_INPUT_SAMPLE_BITS): stride and frame_pitch are bytes and must be even");
     { const int rcm = ensure_mid(c, n_frames); if (rcm) return rcm; }
     Geom& g = c->geom;
     g.input_format = c->input_format;
+    g.sample_bytes = c->input_format ? c->input_sample_bits / 8 : 1;
+    g.valid_bit = g.sample_bytes == 2 ? c->input_valid_bit : 0;
+    g.orient = c->input_format ? c->input_orient : 0;
     g.n_frames = n_frames;
     g.w = w;
     g.h = h;
@@ -745,9 +772,12 @@ int rmcv_batch_upload(rmcv_ctx* c, const uint8_t* frames, int n_frames, int w, i
     int rc = rmcv_batch_sync(c); // the buffer about to be overwritten may still be read by a batch in flight
     if (rc) return rc;
     resident_none(c);
-    // device layout: tightly packed rows (stride 3*w -- w for a mosaic -- rounded up to 16 bytes), frames back to back
-    const int rowb = c->input_format ? w : 3 * w;
-    if (c->input_format && (stride < w || frame_pitch < (int64_t)stride * (h - 1) + w)) return fail(c, RMCV_ERR_BAD_ARG, "bad stride/pitch");
+    // device layout: tightly packed rows (stride 3*w -- w or 2*w for a mosaic -- rounded up to 16 bytes), frames back to back
+    if ((rc = check_layout(c)) || (rc = check_sample_ptr(c, frames))) return rc;
+    const int bpp = ctx_pixel_bytes(c);
+    const int rowb = bpp * w;
+    if (c->input_format && (stride < rowb || frame_pitch < (int64_t)stride * (h - 1) + rowb)) return fail(c, RMCV_ERR_BAD_ARG, "bad stride/pitch");
+    if (bpp == 2 && ((stride & 1) || (frame_pitch & 1))) return fail(c, RMCV_ERR_BAD_ARG, "16-bit samples (RMCV_OPT_INPUT_SAMPLE_BITS): stride and frame_pitch are bytes and must be even");
     const int dstride = (rowb + 15) & ~15;
     const int64_t dpitch = (int64_t)dstride * h;
     rc = set_geom(c, n_frames, w, h, dstride, dpitch);
@@ -774,7 +804,9 @@ int rmcv_batch_set_device_frames(rmcv_ctx* c, const void* d_frames, int n_frames
     if (!c || !d_frames) return RMCV_ERR_BAD_ARG;
     hipSetDevice(c->device);
     resident_none(c);
-    int rc = set_geom(c, n_frames, w, h, stride, frame_pitch);
+    int rc = check_sample_ptr(c, d_frames);
+    if (rc) return rc;
+    rc = set_geom(c, n_frames, w, h, stride, frame_pitch);
     if (rc) return rc;
     c->bufs.frames = (const uint8_t*)d_frames;
     return RMCV_OK;
@@ -788,7 +820,9 @@ int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int 
 {
     if (!c || !d_frames || !s) return RMCV_ERR_BAD_ARG;
     resident_none(c);
-    const int rc = set_geom(c, n_frames, w, h, stride, frame_pitch, s);
+    int rc = check_sample_ptr(c, d_frames);
+    if (rc) return rc;
+    rc = set_geom(c, n_frames, w, h, stride, frame_pitch, s);
     if (rc) return rc;
     c->bufs.frames = (const uint8_t*)d_frames;
     return RMCV_OK;
@@ -882,6 +916,18 @@ int rmcv_ctx_set_option(rmcv_ctx* c, int option, int value)
     }
     if (option == RMCV_OPT_INPUT_FORMAT && value >= RMCV_INPUT_BGR && value <= RMCV_BAYER_BG) {
         c->input_format = value; // (frames bound before keep the format they were bound with)
+        return RMCV_OK;
+    }
+    if (option == RMCV_OPT_INPUT_SAMPLE_BITS && (value == 8 || value == 16)) {
+        c->input_sample_bits = value; // (like the format: frames bound before keep what they were bound with)
+        return RMCV_OK;
+    }
+    if (option == RMCV_OPT_INPUT_VALID_BIT && value >= 0 && value <= 4) {
+        c->input_valid_bit = value;
+        return RMCV_OK;
+    }
+    if (option == RMCV_OPT_INPUT_ORIENT && value >= 0 && value <= (RMCV_ORIENT_MIRROR | RMCV_ORIENT_FLIP)) {
+        c->input_orient = value;
         return RMCV_OK;
     }
     if (option == RMCV_OPT_PIXEL_GROUPS && value >= 1 && value <= 8) {
@@ -1398,10 +1444,12 @@ static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int
     if (rc) return rc;
     resident_none(c);
     if ((rc = ensure_staging(c))) return rc;
-    const int rowb = c->input_format ? w : 3 * w; // a mosaic (RMCV_OPT_INPUT_FORMAT): one byte per pixel
+    if ((rc = check_layout(c)) || (rc = check_sample_ptr(c, bgr))) return rc;
+    const int rowb = ctx_pixel_bytes(c) * w; // a mosaic (RMCV_OPT_INPUT_FORMAT): one sample per pixel, 1 or 2 bytes
     const int dstride = (rowb + 15) & ~15;
     if ((rc = set_geom(c, 1, w, h, dstride, (int64_t)dstride * h))) return rc;
     if (stride < rowb) return fail(c, RMCV_ERR_BAD_ARG, "bad stride");
+    if (c->geom.sample_bytes == 2 && (stride & 1)) return fail(c, RMCV_ERR_BAD_ARG, "16-bit samples (RMCV_OPT_INPUT_SAMPLE_BITS): stride is bytes and must be even");
     if ((rc = ensure_own_frames(c, (size_t)dstride * h))) return rc;
     if ((rc = upload_one(c, bgr, rowb, h, stride, dstride))) return rc;
     c->marks[1] = now_us(); // the upload is enqueued (pageable: the runtime may have copied it by now)
@@ -1541,8 +1589,8 @@ static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int
     c->marks[7] = now_us();
     if (binary_out) { // what the runtime's copies cost this frame (see rmcv_ctx::image_export)
         const double up_us = c->marks[3] - c->marks[1] + c->test_slow_us, img_us = c->marks[4] - c->marks[3] + c->test_slow_us;
-        // (the upload moves what the frame holds: 3 B/px of BGR, 1 B/px of a mosaic -- RMCV_OPT_INPUT_FORMAT)
-        const double frame_bytes = (c->geom.input_format ? 1.0 : 3.0) * w * h, image_bytes = (double)w * h;
+        // (the upload moves what the frame holds: 3 B/px of BGR, 1 or 2 B/px of a mosaic -- RMCV_OPT_INPUT_FORMAT, _SAMPLE_BITS)
+        const double frame_bytes = (double)geom_pixel_bytes(c->geom) * w * h, image_bytes = (double)w * h;
         if (c->upload_now == 0) {
             c->slow_upload = up_us > frame_bytes / 45e3 + 100.0 ? c->slow_upload + 1 : 0; // (45 GB/s + the pixel kernel + the waits' slack)
             if (c->frame_upload == 3 && c->slow_upload >= 3) { c->hold_upload = 512; c->slow_upload = 0; }
@@ -1894,24 +1942,22 @@ int rmcv_match_lightblob(rmcv_ctx* c, const rmcv_point* pts, int n, const rmcv_l
     return match_one(c, pts, n, *lp, 0, box_out, matched);
 }
 
-int rmcv_demosaic(rmcv_ctx* c, const uint8_t* raw, int w, int h, int stride, int pattern, uint8_t* bgr_out, int out_stride)
+} // extern "C"
+
+// rmcv_demosaic / rmcv_demosaic_raw: the arguments are checked, then D(T(r)) of the buffer in layout `lay` (0: a plain 8-bit mosaic)
+static int demosaic_body(rmcv_ctx* c, const uint8_t* raw, int w, int h, int stride, int pattern, int lay, uint8_t* bgr_out, int out_stride)
 {
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!raw || !bgr_out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: null buffer");
-    if (w < 3 || h < 3) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: a mosaic needs w >= 3 and h >= 3");
-    if (stride < w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: stride < w");
-    if (out_stride < 3 * w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: out_stride < 3 w");
-    if (pattern < RMCV_BAYER_RG || pattern > RMCV_BAYER_BG) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: unknown Bayer pattern");
+    const int sb = rmcv::lay_bytes(lay);
     hipSetDevice(c->device);
     int rc = rmcv_batch_sync(c);
     if (rc) return rc;
     // (a stage-wise helper: buffers of its own, so that nothing bound to the context moves)
     uint8_t *d_raw = nullptr, *d_out = nullptr;
-    const size_t in_bytes = (size_t)w * h, out_bytes = (size_t)3 * w * h;
+    const size_t in_bytes = (size_t)sb * w * h, out_bytes = (size_t)3 * w * h;
     hipError_t e = hipMalloc((void**)&d_raw, in_bytes);
     if (e == hipSuccess) e = hipMalloc((void**)&d_out, out_bytes);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(d_raw, w, raw, stride, w, h, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_demosaic(d_raw, w, w, h, pattern, d_out, 3 * w, c->stream);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(d_raw, (size_t)sb * w, raw, stride, (size_t)sb * w, h, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_demosaic(d_raw, sb * w, w, h, pattern, lay, d_out, 3 * w, c->stream);
     c->last_what = "k_demosaic";
     int rcw = 0;
     if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_demosaic");
@@ -1922,6 +1968,36 @@ int rmcv_demosaic(rmcv_ctx* c, const uint8_t* raw, int w, int h, int stride, int
     }
     if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_demosaic", e);
     return rcw;
+}
+
+extern "C" {
+
+int rmcv_demosaic(rmcv_ctx* c, const uint8_t* raw, int w, int h, int stride, int pattern, uint8_t* bgr_out, int out_stride)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!raw || !bgr_out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: null buffer");
+    if (w < 3 || h < 3) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: a mosaic needs w >= 3 and h >= 3");
+    if (stride < w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: stride < w");
+    if (out_stride < 3 * w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: out_stride < 3 w");
+    if (pattern < RMCV_BAYER_RG || pattern > RMCV_BAYER_BG) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: unknown Bayer pattern");
+    return demosaic_body(c, raw, w, h, stride, pattern, 0, bgr_out, out_stride);
+}
+
+int rmcv_demosaic_raw(rmcv_ctx* c, const void* raw, int w, int h, int stride, int pattern, int sample_bits, int valid_bit, int orient,
+                      uint8_t* bgr_out, int out_stride)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!raw || !bgr_out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: null buffer");
+    if (w < 3 || h < 3) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: a mosaic needs w >= 3 and h >= 3");
+    if (sample_bits != 8 && sample_bits != 16) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: sample_bits is 8 or 16");
+    if (valid_bit < 0 || valid_bit > 4) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: valid_bit is 0 .. 4");
+    if (orient < 0 || orient > (RMCV_ORIENT_MIRROR | RMCV_ORIENT_FLIP)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: unknown orientation bits");
+    if (stride < sample_bits / 8 * w) return fail(c, RMCV_ERR_BAD_ARG, sample_bits == 16 ? "rmcv_demosaic_raw: stride < 2 w" : "rmcv_demosaic_raw: stride < w");
+    if (sample_bits == 16 && (stride & 1)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: odd stride with 16-bit samples");
+    if (sample_bits == 16 && ((uintptr_t)raw & 1)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: 16-bit samples need a 2-byte aligned buffer");
+    if (out_stride < 3 * w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: out_stride < 3 w");
+    if (pattern < RMCV_BAYER_RG || pattern > RMCV_BAYER_BG) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: unknown Bayer pattern");
+    return demosaic_body(c, (const uint8_t*)raw, w, h, stride, pattern, rmcv::raw_layout(sample_bits, valid_bit, orient), bgr_out, out_stride);
 }
 
 int rmcv_find_lightblobs(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, const rmcv_point* pts, const int32_t* offs,

@@ -24,6 +24,9 @@ struct Geom {
     int overloads;       // RMCV_OPT_OVERLOADS: SURVEY A.6, which functions the reference's unqualified abs / atan2 / sin / cos on floats are
     int contour_tier;    // RMCV_OPT_CONTOUR_TIER: 0 = per frame (LDS tables, else mid tier, else literal scanner), 1 = literal, 2 = mid tier
     int input_format;    // RMCV_OPT_INPUT_FORMAT of the frames bound: 0 BGR, 1..4 a Bayer pattern (recorded when the frames are bound)
+    int sample_bytes;    // RMCV_OPT_INPUT_SAMPLE_BITS of the frames bound, as bytes: 1, or 2 (16-bit Bayer samples; BGR: always 1)
+    int valid_bit;       // RMCV_OPT_INPUT_VALID_BIT: the pixel is bits valid_bit .. valid_bit + 7 of a 2-byte sample
+    int orient;          // RMCV_OPT_INPUT_ORIENT: RMCV_ORIENT_MIRROR | RMCV_ORIENT_FLIP of the frames bound
     int n_frames;
     int w, h;
     int stride;          // bytes between rows of the input (BGR or mosaic)
@@ -153,7 +156,10 @@ bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound, int pixel_ws)
 // the pixel stage of a Bayer batch (Geom::input_format != 0; k_binary_bayer.hip); launch_binary hands such batches to it
 hipError_t launch_binary_bayer(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, hipStream_t s);
 // D(m) of one device mosaic into a device BGR frame (rmcv_demosaic)
-hipError_t launch_demosaic(const uint8_t* d_raw, int stride, int w, int h, int pattern, uint8_t* d_out, int out_stride, hipStream_t s);
+// lay: the buffer's layout word (device_bayer.h: raw_layout; 0 = a plain 8-bit mosaic) -> D(T(r)) (rmcv_demosaic_raw)
+hipError_t launch_demosaic(const uint8_t* d_raw, int stride, int w, int h, int pattern, int lay, uint8_t* d_out, int out_stride, hipStream_t s);
+// bytes of one pixel of the frames a geometry / a context's options describe: 3 (BGR), or the Bayer sample's 1 or 2
+inline int geom_pixel_bytes(const Geom& g) { return g.input_format ? g.sample_bytes : 3; }
 hipError_t launch_contours(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s);
 hipError_t launch_blobs(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, hipStream_t s);
 hipError_t launch_armours(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, hipStream_t s);

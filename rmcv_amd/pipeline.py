@@ -16,7 +16,7 @@ from .api import Context
 
 class Pipeline:
     def __init__(self, device=0, depth=0, pixel_streams=0, sparse_streams=0, armour_cap=0, sparse_waves=0, pixel_groups=0,
-                 host_results=0, dense_streams=0, hot_contexts=0, input_format=0, **limits):
+                 host_results=0, dense_streams=0, hot_contexts=0, input_format=0, sample_bits=8, valid_bit=0, mirror=False, flip=False, **limits):
         lim = Limits()
         lib().rmcv_default_limits(C.byref(lim))
         for k, v in limits.items():
@@ -40,6 +40,10 @@ class Pipeline:
         if self.input_format:  # RMCV_OPT_INPUT_FORMAT on every slot: each batch reads its own context's option
             for c in self.contexts:
                 c.set_input_format(self.input_format)
+        self.sample_bits = int(sample_bits)
+        if self.sample_bits != 8 or valid_bit or mirror or flip:  # the frame as the sensor delivers it, on every slot likewise
+            for c in self.contexts:
+                c.set_input_layout(sample_bits, valid_bit, mirror, flip)
 
     def close(self):
         if getattr(self, "_h", None):
@@ -68,7 +72,7 @@ class Pipeline:
         """enqueue one batch of frames resident in HBM (data_ptr: e.g. torch_tensor.data_ptr()); returns the ticket"""
         if params is not None:
             self._params = params
-        stride = stride or (w if self.input_format else 3 * w)
+        stride = stride or (w * self.sample_bits // 8 if self.input_format else 3 * w)
         frame_pitch = frame_pitch or stride * h
         if legacy is not None:
             rc = self._lib.rmcv_pipeline_submit_legacy(self._h, data_ptr, n, w, h, stride, frame_pitch, C.addressof(self._params), C.addressof(legacy),

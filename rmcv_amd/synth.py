@@ -42,6 +42,25 @@ def mosaic(bgr, pattern):
     return np.take_along_axis(bgr, np.broadcast_to(ch[..., None], bgr.shape[:-1] + (1,)), axis=-1)[..., 0].copy()
 
 
+def raw_frame(mosaic, sample_bits=8, valid_bit=0, mirror=False, flip=False, rng=None):
+    """a buffer as a sensor delivers it whose oriented 8-bit reading is `mosaic` [..., h, w] (include/rmcv_abi.h: T(r) = mosaic): the
+    pixels mirrored / flipped back into the sensor's order and, with 16-bit samples, placed at bits valid_bit .. valid_bit + 7 of
+    little-endian uint16 samples whose bits below AND above that window hold random data (a reader has to drop both)"""
+    m = np.asarray(mosaic, np.uint8)
+    if mirror:
+        m = m[..., ::-1]
+    if flip:
+        m = m[..., ::-1, :]
+    if sample_bits == 8:
+        return np.ascontiguousarray(m)
+    if sample_bits != 16 or not 0 <= valid_bit <= 4:
+        raise ValueError("sample_bits is 8 or 16, valid_bit 0 .. 4")
+    rng = rng or np.random.default_rng(20241008)
+    window = np.uint16(0xFF << valid_bit)
+    noise = rng.integers(0, 1 << 16, m.shape, dtype=np.uint16) & ~window
+    return np.ascontiguousarray((m.astype(np.uint16) << np.uint16(valid_bit)) | noise).astype("<u2")
+
+
 def checksum(img):
     h, w, _ = img.shape
     img = np.ascontiguousarray(img)

@@ -1,10 +1,14 @@
-"""Raw Bayer input (RMCV_OPT_INPUT_FORMAT) against BGR, in one process with the two alternating, printed as ONE JSON line:
+"""Raw Bayer input (RMCV_OPT_INPUT_FORMAT) against BGR, and the sensor's own layouts (RMCV_OPT_INPUT_SAMPLE_BITS / _VALID_BIT / _ORIENT:
+8-bit flipped, 8-bit mirrored, 16-bit samples, 16-bit mirrored and flipped) against the plain 8-bit mosaic, in one process with all of
+them alternating, printed as ONE JSON line:
   pipeline   ms per step and frames/s of 256 x 1280x1024 batches, 7 regions x 20 steps per format (median and spread)
   pixel      the pixel stage alone (rmcv_batch_run_timed's events): k_binary on BGR, k_binary_bayer on the mosaics, with and
              without the byte image
   chain      the per-frame drop-in chain (rmcv_extract_color -> rmcv_filter_lightblobs -> rmcv_filter_armours, one host frame):
              median and p90 in ms
-The mosaics are the synthetic frames' colour filter arrays (synth.mosaic, pattern RG).   python tools/bayer_bench.py [regions steps]"""
+The mosaics are the synthetic frames' colour filter arrays (synth.mosaic, pattern RG); the 16-bit buffers hold them at bits 4..11 with
+random bits around (synth.raw_frame).  An orientation reads the same buffers mirrored / flipped: another scene, the same work.
+python tools/bayer_bench.py [regions steps]"""
 import ctypes as C
 import json
 import os
@@ -35,55 +39,69 @@ def stats(xs):
 
 # ---------------------------------------------------------------- inputs: 4 batches per format, resident in HBM
 bgr_sets = [synth.batch(k * 1000003, N, W, H, CAMP_BLUE, 0, threads=16) for k in range(4)]
-fmt_sets = {0: [torch.from_numpy(b).to(dev) for b in bgr_sets],
-            BAYER_RG: [torch.from_numpy(synth.mosaic(b, BAYER_RG)).to(dev) for b in bgr_sets]}
+mosaics = [synth.mosaic(b, BAYER_RG) for b in bgr_sets]
+sets = {"bgr": [torch.from_numpy(b).to(dev) for b in bgr_sets], "m8": [torch.from_numpy(m).to(dev) for m in mosaics],
+        "m16": [torch.from_numpy(synth.raw_frame(m, 16, 4).view(np.uint8)).to(dev) for m in mosaics]}
+# name -> (input format, layout keywords of Context.set_input_layout / Pipeline, the buffers it reads, bytes per pixel read)
+CASES = {"bgr": (0, {}, "bgr", 3), "bayer": (BAYER_RG, {}, "m8", 1),
+         "bayer_flip": (BAYER_RG, dict(flip=True), "m8", 1), "bayer_mirror": (BAYER_RG, dict(mirror=True), "m8", 1),
+         "raw16": (BAYER_RG, dict(sample_bits=16, valid_bit=4), "m16", 2),
+         "raw16_mirror_flip": (BAYER_RG, dict(sample_bits=16, valid_bit=4, mirror=True, flip=True), "m16", 2)}
+NAMES = list(CASES)
+
+
+def rotation(r):
+    """the cases in an order that starts one further on in every round, so that none always runs behind the same neighbour"""
+    k = r % len(NAMES)
+    return NAMES[k:] + NAMES[:k]
+
 
 # ---------------------------------------------------------------- pipeline, regions alternating
-pls = {0: Pipeline(device=0, max_frames=N, max_width=W, max_height=H),
-       BAYER_RG: Pipeline(device=0, max_frames=N, max_width=W, max_height=H, input_format=BAYER_RG)}
-counter = {0: 0, BAYER_RG: 0}
+pls = {name: Pipeline(device=0, max_frames=N, max_width=W, max_height=H, input_format=fmt, **lay) for name, (fmt, lay, _, _) in CASES.items()}
+counter = {name: 0 for name in NAMES}
 
 
-def region(fmt, k):
-    pl, sets = pls[fmt], fmt_sets[fmt]
+def region(name, k):
+    pl, bufs = pls[name], sets[CASES[name][2]]
     pl.drain()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     for _ in range(k):
-        pl.submit(sets[counter[fmt] % 4].data_ptr(), N, H, W, p, STAGE_ALL)
-        counter[fmt] += 1
+        pl.submit(bufs[counter[name] % 4].data_ptr(), N, H, W, p, STAGE_ALL)
+        counter[name] += 1
     pl.drain()
     torch.cuda.synchronize()
     return (time.perf_counter() - t0) / k * 1e3
 
 
-for fmt in (0, BAYER_RG):  # warm-up: every context of the ring has bound the geometry
-    region(fmt, 100)
-ms = {0: [], BAYER_RG: []}
+for name in NAMES:  # warm-up: every context of the ring has bound the geometry
+    region(name, 100)
+ms = {name: [] for name in NAMES}
 for r in range(REGIONS):
-    for fmt in ((0, BAYER_RG) if r % 2 == 0 else (BAYER_RG, 0)):
-        ms[fmt].append(region(fmt, STEPS))
+    for name in rotation(r):
+        ms[name].append(region(name, STEPS))
 for pl in pls.values():
     pl.close()
 
 # ---------------------------------------------------------------- the pixel stage alone (events around the launch)
 ctx = Context(device=0, max_frames=N, max_width=W, max_height=H)
-pix = {}
-for fmt in (0, BAYER_RG):
-    pix[fmt] = {"image": [], "no_image": []}
+pix = {name: {"image": [], "no_image": []} for name in NAMES}
 for r in range(2 * REGIONS):
-    for fmt in ((0, BAYER_RG) if r % 2 == 0 else (BAYER_RG, 0)):
-        t = fmt_sets[fmt][r % 4]
+    for name in rotation(r):
+        fmt, lay, which, _ = CASES[name]
+        t = sets[which][r % 4]
         ctx.set_input_format(fmt)
+        ctx.set_input_layout(**lay)
         ctx.bind_device_frames(t.data_ptr(), N, H, W, keepalive=t)
-        pix[fmt]["image"].append(ctx.run_timed(p, STAGE_BINARY)[0])
-        pix[fmt]["no_image"].append(ctx.run_timed(p, STAGE_BINARY | STAGE_NO_IMAGE)[0])
+        pix[name]["image"].append(ctx.run_timed(p, STAGE_BINARY)[0])
+        pix[name]["no_image"].append(ctx.run_timed(p, STAGE_BINARY | STAGE_NO_IMAGE)[0])
 ctx.close()
 
 # ---------------------------------------------------------------- the per-frame chain
 L = lib()
 c1 = Context(device=0, max_frames=1, max_width=W, max_height=H)
-frames = {0: [np.ascontiguousarray(bgr_sets[0][i]) for i in range(4)], BAYER_RG: [synth.mosaic(bgr_sets[0][i], BAYER_RG) for i in range(4)]}
+frames = {"bgr": [np.ascontiguousarray(bgr_sets[0][i]) for i in range(4)], "m8": [np.ascontiguousarray(mosaics[0][i]) for i in range(4)],
+          "m16": [synth.raw_frame(mosaics[0][i], 16, 4) for i in range(4)]}
 binary = np.empty((H, W), np.uint8)
 pts, offs = np.empty(c1.limits.max_points, POINT), np.empty(c1.limits.max_contours + 1, np.int32)
 blobs, neg = np.empty(c1.limits.max_blobs, LIGHTBLOB), np.empty(c1.limits.max_contours, np.int32)
@@ -103,32 +121,35 @@ def one_chain(img, rowb):
     return (time.perf_counter() - t0) * 1e3
 
 
-chain = {0: [], BAYER_RG: []}
+chain = {name: [] for name in NAMES}
 for r in range(2 * REGIONS):
-    for fmt in ((0, BAYER_RG) if r % 2 == 0 else (BAYER_RG, 0)):
+    for name in rotation(r):
+        fmt, lay, which, bpp = CASES[name]
         c1.set_input_format(fmt)
-        rowb = W if fmt else 3 * W
+        c1.set_input_layout(**lay)
         for i in range(4):
-            one_chain(frames[fmt][i], rowb)
-        chain[fmt] += [one_chain(frames[fmt][i % 4], rowb) for i in range(50)]
+            one_chain(frames[which][i], bpp * W)
+        chain[name] += [one_chain(frames[which][i % 4], bpp * W) for i in range(50)]
 c1.close()
 
-name = {0: "bgr", BAYER_RG: "bayer"}
 out = {"tool": "bayer_bench", "frames": N, "w": W, "h": H, "regions": REGIONS, "steps": STEPS, "pattern": "RG"}
-for fmt in (0, BAYER_RG):
-    s = stats(ms[fmt])
-    out[name[fmt]] = {
+px = N * W * H
+for name in NAMES:
+    s = stats(ms[name])
+    out[name] = {
         "pipeline_ms_per_step": s,
         "pipeline_frames_per_s": round(N / s["median"] * 1e3, 1),
-        "pixel_ms": stats(pix[fmt]["image"]),
-        "pixel_ms_no_image": stats(pix[fmt]["no_image"]),
-        "chain_ms_median": round(float(np.median(chain[fmt])), 4),
-        "chain_ms_p90": round(float(np.percentile(chain[fmt], 90)), 4),
+        "pixel_ms": stats(pix[name]["image"]),
+        "pixel_ms_no_image": stats(pix[name]["no_image"]),
+        "chain_ms_median": round(float(np.median(chain[name])), 4),
+        "chain_ms_p90": round(float(np.percentile(chain[name], 90)), 4),
     }
-# the Bayer pixel stage against its byte bound: 2.125 B/px (1.125 without the byte image) at 8 TB/s
-px = N * W * H
-out["bayer"]["pixel_bound_ms"] = round(px * 2.125 / 8e12 * 1e3, 4)
-out["bayer"]["pixel_fraction_of_bound"] = round(out["bayer"]["pixel_bound_ms"] / out["bayer"]["pixel_ms"]["median"], 3)
-out["bayer"]["pixel_bound_ms_no_image"] = round(px * 1.125 / 8e12 * 1e3, 4)
-out["bayer"]["pixel_fraction_of_bound_no_image"] = round(out["bayer"]["pixel_bound_ms_no_image"] / out["bayer"]["pixel_ms_no_image"]["median"], 3)
+    if name == "bgr":
+        continue
+    # the Bayer pixel stage against its byte bound at 8 TB/s: the samples read + 1 B/px of byte image + 1/8 for the plane
+    read = CASES[name][3]
+    out[name]["pixel_bound_ms"] = round(px * (read + 1.125) / 8e12 * 1e3, 4)
+    out[name]["pixel_fraction_of_bound"] = round(out[name]["pixel_bound_ms"] / out[name]["pixel_ms"]["median"], 3)
+    out[name]["pixel_bound_ms_no_image"] = round(px * (read + 0.125) / 8e12 * 1e3, 4)
+    out[name]["pixel_fraction_of_bound_no_image"] = round(out[name]["pixel_bound_ms_no_image"] / out[name]["pixel_ms_no_image"]["median"], 3)
 print(json.dumps(out), flush=True)
