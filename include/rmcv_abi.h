@@ -261,7 +261,35 @@ const char* rmcv_last_error(const rmcv_ctx* ctx);
 #define RMCV_OPT_INPUT_ORIENT 22
 #define RMCV_ORIENT_MIRROR 1
 #define RMCV_ORIENT_FLIP 2
+/* RMCV_OPT_ENHANCE: 1: every frame is read through rm::AutoEnhance (src/imgproc.cpp:77-98), the reference's answer to changing light --
+ * 0 (default): as it is.  For a BGR frame f of w x h pixels and the gains (max_gain, min_gain) of rmcv_ctx_set_enhance_gains:
+ *     S_c      = exact integer sum of channel c over the frame                                  (c = B, G, R)
+ *     m_c      = (double)S_c * (1.0 / (double)(w h))                                            cv::mean, as recalled (not pinned against OpenCV)
+ *     meanC3   = (float)(m_B + m_G + m_R) / 3.0f
+ *     k        = 2.0f / (max_gain - min_gain);  b = 3.0f - max_gain * k;  g = k * meanC3 + b    float, no contraction
+ *     g        = 1.0f + (g - 1.0f) / 4.0f  if -3 <= g <= 1;   0.0f  if g < -3;   unchanged otherwise
+ *     LUT_g[i] = saturate_cast<uchar>(pow(i / 255.0, (double)g) * 255.0)                        round half to even; pow(0, 0) = 1
+ *     E(f)     = LUT_g applied to every byte of f
+ * and every result for f -- byte image, contours, blobs, armours, icons, identities, poses -- is, bit for bit, what the same call gives for
+ * the frame E(f) with the option off.  No enhanced frame is ever written: a pass over the frames sums the channels (k_frame_sums), one
+ * workgroup per frame builds the table (k_enhance_table; pow is the library's own, pinned against the host libm by the CPU tests), and the
+ * pixel kernel (k_binary_enh) and the classifier read the frame through it.  Like the input format the option (with the gains) is recorded
+ * when frames are bound and read per call by rmcv_extract_color / rmcv_classify_armours; sums and tables are computed by every run that
+ * includes RMCV_STAGE_BINARY, at run time (a run without that stage reads the tables the last one with it left).  Batches with the
+ * option take the k_binary shape (never k_binary_ws) and the stand-alone classifier; a pipeline keeps them out of its hot rotation and
+ * refuses a submit (RMCV_ERR_BAD_ARG) while its contexts disagree about the option.  The frame is read TWICE (the mean precedes the
+ * table): with RMCV_OPT_FRAME_UPLOAD 2 on a device that reads the registered buffer in place, both reads cross the host link.
+ * RMCV_ERR_BAD_ARG: binding or reading a frame with the option on while a Bayer input format is set (the mean of a demosaiced frame is no
+ * function of the mosaic's sums), and the legacy matcher (rmcv_find_lightblobs, rmcv_batch_run_legacy, rmcv_pipeline_submit_legacy: it
+ * votes camps from BGR means) with the option on. */
+#define RMCV_OPT_ENHANCE 23
 int  rmcv_ctx_set_option(rmcv_ctx* ctx, int option, int value);
+/* the gains of RMCV_OPT_ENHANCE: defaults 100, 50 (include/imgproc.h:35).  RMCV_ERR_BAD_ARG (and nothing changes) unless both are finite and
+ * differ.  For a pipeline: every slot's context (rmcv_pipeline_context), like the option. */
+int  rmcv_ctx_set_enhance_gains(rmcv_ctx* ctx, float max_gain, float min_gain);
+/* what the context is set to: RMCV_OPT_ENHANCE and the gains (any pointer may be NULL) -- for code that sets them for one call and puts
+ * back what it found (rm::extract_color_enhanced in rmcv_shim.hpp does) */
+int  rmcv_ctx_get_enhance(const rmcv_ctx* ctx, int32_t* on, float* max_gain, float* min_gain);
 /* launches of k_binary_ws (RMCV_OPT_PIXEL_SHAPE 1) by this process so far: a diagnostic -- an option that is set but whose
  * conditions a batch does not meet falls back to k_binary silently (tests/test_gpu_pixel_shape.py) */
 int64_t rmcv_pixel_ws_launches(void);
@@ -312,6 +340,20 @@ int rmcv_demosaic(rmcv_ctx* ctx, const uint8_t* raw, int w, int h, int stride, i
 int rmcv_demosaic_raw(rmcv_ctx* ctx, const void* raw, int w, int h, int stride, int pattern, int sample_bits, int valid_bit, int orient,
                       uint8_t* bgr_out, int out_stride);
 
+/* ---- rm::CalcGamma / rm::AutoEnhance (include/imgproc.h:33-35, src/imgproc.cpp:37-48, 77-98): see RMCV_OPT_ENHANCE for the arithmetic ---- */
+/* LUT_gamma, host-side (no context, no device): the table builder is a function of gamma alone.  RMCV_ERR_BAD_ARG: gamma negative or not
+ * finite (rm::AutoEnhance never yields one). */
+int rmcv_gamma_lut(float gamma, uint8_t lut[256]);
+/* the gamma rm::AutoEnhance derives from a frame's channel sums, host-side.  RMCV_ERR_BAD_ARG: n_pixels < 1, gains not finite or equal. */
+int rmcv_enhance_gamma(const uint64_t sums_bgr[3], int64_t n_pixels, float max_gain, float min_gain, float* gamma);
+/* rm::CalcGamma on a host image of any channel count (the table acts on bytes): `rows` rows of `row_bytes` bytes, `src_stride` /
+ * `dst_stride` >= row_bytes apart; dst == src allowed, as the reference calls it.  RMCV_ERR_BAD_ARG: gamma negative or not finite. */
+int rmcv_calc_gamma(rmcv_ctx* ctx, const uint8_t* src, int row_bytes, int rows, int src_stride, float gamma, uint8_t* dst, int dst_stride);
+/* E(f) of one host BGR frame (w, h <= 65536), sums and table on the device; out == bgr allowed; gamma_out nullable.  Independent of the
+ * context's RMCV_OPT_ENHANCE and gains.  RMCV_ERR_BAD_ARG: gains not finite or equal. */
+int rmcv_auto_enhance(rmcv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, float max_gain, float min_gain, uint8_t* out, int out_stride,
+                      float* gamma_out);
+
 /* ---- batch of independent frames, resident on the device ------------------------------ */
 
 /* copy n_frames host frames (each h rows of `stride` bytes, frames `frame_pitch` bytes apart)
@@ -337,6 +379,10 @@ int rmcv_batch_get_contours(rmcv_ctx* ctx, int frame, rmcv_point* pts_out, int p
                             int contours_cap, int32_t* n_contours, int32_t* n_points);
 int rmcv_batch_get_blobs(rmcv_ctx* ctx, int frame, rmcv_lightblob* blobs_out, int cap, int32_t* n_blobs,
                          int32_t* blob_src);
+/* the gamma each frame bound was read with by the last run (RMCV_OPT_ENHANCE; the one of the last rmcv_extract_color as frame 0): the
+ * first min(cap, n_frames) entries; 1 for every frame while the option is off, and before the first such run of a context.
+ * Synchronises the context. */
+int rmcv_batch_get_gammas(rmcv_ctx* ctx, float* gamma_out, int cap);
 /* all armours of the batch, frame-major: frame_offs has n_frames+1 entries */
 int rmcv_batch_get_armours(rmcv_ctx* ctx, rmcv_armour* armours_out, int cap, int32_t* frame_offs,
                            int32_t* n_total);

@@ -17,6 +17,8 @@
 // and rm::solve_PnP (include/mobility.h:106-108).
 // One addition the reference does not have: rm::extract_color_bayer, rm::extract_color on a raw 8-bit Bayer mosaic (CV_8UC1), and
 // rm::extract_color_raw, the same on the sensor's buffer as delivered (8- or 16-bit samples, to be mirrored and / or flipped).
+// rm::CalcGamma and rm::AutoEnhance (include/imgproc.h:23, 35) are here too, and one more addition: rm::extract_color_enhanced, the two
+// of rm::AutoEnhance + rm::extract_color fused (the enhanced frame is never written).
 // The legacy names of the north star are aliased at the bottom (docs/core_8h_source.html:101,114).
 //
 // Every signature mentions cv:: types, so this header only compiles where OpenCV headers exist.
@@ -166,6 +168,47 @@ RMCV_SHIM_LINKAGE std::tuple<std::vector<contour>, cv::Mat> extract_color_raw(cv
     return hip_detail::extract(img, target, lower_bound);
 }
 #endif
+
+// ---- rm::CalcGamma / rm::AutoEnhance (include/imgproc.h:23, 35; bodies src/imgproc.cpp:37-48, 77-98).  The default arguments
+// (gamma = 0.5f; maxGainFactor = 100, minGainFactor = 50) live on the reference's declarations.  8-bit matrices of one or three
+// channels (the table acts on bytes); `calibration` may be `source` itself, as rm::AutoEnhance calls it.
+RMCV_SHIM_LINKAGE void CalcGamma(cv::Mat& source, cv::Mat& calibration, float gamma)
+{
+    CV_Assert(source.type() == CV_8UC1 || source.type() == CV_8UC3);
+    if (calibration.data != source.data) calibration = cv::Mat(source.rows, source.cols, source.type());
+    hip_detail::check(rmcv_calc_gamma(hip_detail::ctx(), source.data, source.cols * source.channels(), source.rows, (int)source.step, gamma,
+                                      calibration.data, (int)calibration.step));
+}
+
+RMCV_SHIM_LINKAGE void AutoEnhance(cv::Mat& frame, float maxGainFactor, float minGainFactor)
+{
+    CV_Assert(frame.type() == CV_8UC3);
+    hip_detail::check(rmcv_auto_enhance(hip_detail::ctx(), frame.data, frame.cols, frame.rows, (int)frame.step, maxGainFactor, minGainFactor,
+                                        frame.data, (int)frame.step, nullptr));
+}
+
+// Not a reference function: rm::AutoEnhance + rm::extract_color as ONE call -- the results are rm::extract_color's on the enhanced
+// frame, which is never written (include/rmcv_abi.h: RMCV_OPT_ENHANCE): the host drops two full-frame CPU passes and `image` stays as
+// the camera delivered it.  Option and gains are the thread's for this call only: rm::extract_color is unchanged.
+RMCV_SHIM_LINKAGE std::tuple<std::vector<contour>, cv::Mat> extract_color_enhanced(cv::InputArray image, camp target, int lower_bound,
+                                                                                   float maxGainFactor, float minGainFactor)
+{
+    cv::Mat img = image.getMat();
+    CV_Assert(img.type() == CV_8UC3);
+    struct Restore { // back to what the thread's context was set to, however the call ends
+        int32_t on = 0;
+        float max_gain = 100.0f, min_gain = 50.0f;
+        Restore() { rmcv_ctx_get_enhance(hip_detail::ctx(), &on, &max_gain, &min_gain); }
+        ~Restore()
+        {
+            rmcv_ctx_set_option(hip_detail::ctx(), RMCV_OPT_ENHANCE, on);
+            rmcv_ctx_set_enhance_gains(hip_detail::ctx(), max_gain, min_gain);
+        }
+    } restore;
+    hip_detail::check(rmcv_ctx_set_enhance_gains(hip_detail::ctx(), maxGainFactor, minGainFactor));
+    hip_detail::check(rmcv_ctx_set_option(hip_detail::ctx(), RMCV_OPT_ENHANCE, 1));
+    return hip_detail::extract(img, target, lower_bound);
+}
 
 RMCV_SHIM_LINKAGE auto filter_lightblobs(const std::vector<contour>& contours, const float tilt_max, const range<float> ratio_range,
                               const range<double> area_range, camp enemy)

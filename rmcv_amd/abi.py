@@ -52,6 +52,9 @@ OPT_INPUT_SAMPLE_BITS = 20
 OPT_INPUT_VALID_BIT = 21
 OPT_INPUT_ORIENT = 22
 ORIENT_MIRROR, ORIENT_FLIP = 1, 2
+# exposure-adaptive detection: frames are read through their rm::AutoEnhance table (gains: rmcv_ctx_set_enhance_gains, defaults 100, 50)
+OPT_ENHANCE = 23
+ENHANCE_MAX_GAIN, ENHANCE_MIN_GAIN = 100.0, 50.0
 STAGE_BINARY, STAGE_CONTOURS, STAGE_BLOBS, STAGE_ARMOURS, STAGE_ALL, STAGE_IDENTITY, STAGE_POSE, STAGE_NO_IMAGE = 1, 2, 4, 8, 15, 16, 32, 64
 SVM_FEATURES = 1200
 FRAME_OVF_CONTOURS, FRAME_OVF_POINTS, FRAME_OVF_BLOBS, FRAME_OVF_ARMOURS, FRAME_SLOW_PATH, FRAME_MID_PATH = 1, 2, 4, 8, 16, 64
@@ -69,6 +72,7 @@ EXPORTS = [
     "rmcv_pipeline_submit", "rmcv_pipeline_submit_legacy", "rmcv_pipeline_wait", "rmcv_pipeline_collect", "rmcv_pipeline_drain", "rmcv_pipeline_record",
     "rmcv_pipeline_set_hook", "rmcv_pipeline_set_gather", "rmcv_pipeline_gathered", "rmcv_device_alloc", "rmcv_device_free", "rmcv_device_upload", "rmcv_device_download",
     "rmcv_track_init", "rmcv_track_reset", "rmcv_track_update", "rmcv_track_predict", "rmcv_track_step", "rmcv_min_area_rect", "rmcv_match_lightblob", "rmcv_find_lightblobs", "rmcv_lightblob_overlap", "rmcv_batch_run_legacy",
+    "rmcv_ctx_set_enhance_gains", "rmcv_ctx_get_enhance", "rmcv_gamma_lut", "rmcv_enhance_gamma", "rmcv_calc_gamma", "rmcv_auto_enhance", "rmcv_batch_get_gammas",
 ]
 
 
@@ -166,6 +170,14 @@ def load(path):
     if hasattr(L, "rmcv_demosaic_raw"):
         L.rmcv_demosaic_raw.restype = C.c_int
         L.rmcv_demosaic_raw.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+    if hasattr(L, "rmcv_auto_enhance"):  # (builds from before RMCV_OPT_ENHANCE stay loadable for A/B runs)
+        L.rmcv_ctx_set_enhance_gains.argtypes = [C.c_void_p, C.c_float, C.c_float]
+        L.rmcv_ctx_get_enhance.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_gamma_lut.argtypes = [C.c_float, C.c_void_p]
+        L.rmcv_enhance_gamma.argtypes = [C.c_void_p, C.c_int64, C.c_float, C.c_float, C.c_void_p]
+        L.rmcv_calc_gamma.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int]
+        L.rmcv_auto_enhance.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p]
+        L.rmcv_batch_get_gammas.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L
@@ -189,6 +201,26 @@ def use(L):
 
 def ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def gamma_lut(gamma):
+    """rm::CalcGamma's 256-entry table of `gamma` (rmcv_gamma_lut: host-side, the table builder the device runs too)"""
+    out = np.empty(256, np.uint8)
+    rc = lib().rmcv_gamma_lut(C.c_float(gamma), ptr(out))
+    if rc:
+        raise RmcvError(rc, "rmcv_gamma_lut: gamma must be finite and not negative")
+    return out
+
+
+def enhance_gamma(sums_bgr, n_pixels, max_gain=ENHANCE_MAX_GAIN, min_gain=ENHANCE_MIN_GAIN):
+    """the gamma rm::AutoEnhance derives from a frame's exact channel sums (rmcv_enhance_gamma: host-side)"""
+    s = np.ascontiguousarray(sums_bgr, np.uint64)
+    assert s.shape == (3,)
+    g = C.c_float(0)
+    rc = lib().rmcv_enhance_gamma(ptr(s), C.c_int64(int(n_pixels)), C.c_float(max_gain), C.c_float(min_gain), C.byref(g))
+    if rc:
+        raise RmcvError(rc, "rmcv_enhance_gamma: the gains must be finite and differ, n_pixels >= 1")
+    return np.float32(g.value)
 
 
 def default_pnp_config():

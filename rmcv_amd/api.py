@@ -118,6 +118,48 @@ class Context:
         self._chk(lib().rmcv_demosaic(self._h, ptr(raw), w, h, w, int(pattern), ptr(out), 3 * w))
         return out
 
+    # ---------------------------------------------------------------- exposure-adaptive detection (rm::CalcGamma / rm::AutoEnhance)
+    def set_enhance(self, on=True, max_gain=None, min_gain=None):
+        """RMCV_OPT_ENHANCE: frames handed in from now on are read through their rm::AutoEnhance table (gains: the reference's 100, 50
+        unless given); every result is that of the enhanced frame, which is never written"""
+        if max_gain is not None or min_gain is not None:
+            self._chk(lib().rmcv_ctx_set_enhance_gains(self._h, C.c_float(abi.ENHANCE_MAX_GAIN if max_gain is None else max_gain),
+                                                       C.c_float(abi.ENHANCE_MIN_GAIN if min_gain is None else min_gain)))
+        self.set_option(abi.OPT_ENHANCE, 1 if on else 0)
+
+    def get_enhance(self):
+        """(RMCV_OPT_ENHANCE, max_gain, min_gain) as the context is set"""
+        on, hi, lo = C.c_int32(0), C.c_float(0), C.c_float(0)
+        self._chk(lib().rmcv_ctx_get_enhance(self._h, C.byref(on), C.byref(hi), C.byref(lo)))
+        return bool(on.value), hi.value, lo.value
+
+    def calc_gamma(self, image, gamma, inplace=False):
+        """rm::CalcGamma of a uint8 image of any shape whose last axes are contiguous rows ((h, w), (h, w, c)): the table of `gamma`
+        applied to every byte, on the GPU"""
+        img = image if inplace else np.ascontiguousarray(image, np.uint8)
+        assert img.dtype == np.uint8 and img.flags.c_contiguous and img.ndim >= 2
+        rows, rowb = img.shape[0], img.strides[0]
+        out = img if inplace else np.empty_like(img)
+        self._chk(lib().rmcv_calc_gamma(self._h, ptr(img), rowb, rows, rowb, C.c_float(gamma), ptr(out), rowb))
+        return out
+
+    def auto_enhance(self, image, max_gain=abi.ENHANCE_MAX_GAIN, min_gain=abi.ENHANCE_MIN_GAIN, inplace=False):
+        """rm::AutoEnhance of one (h, w, 3) BGR frame -> (enhanced frame, gamma); sums, table and mapping on the GPU"""
+        img = image if inplace else np.ascontiguousarray(image, np.uint8)
+        assert img.dtype == np.uint8 and img.flags.c_contiguous and img.ndim == 3 and img.shape[2] == 3
+        h, w, _ = img.shape
+        out = img if inplace else np.empty_like(img)
+        g = C.c_float(0)
+        self._chk(lib().rmcv_auto_enhance(self._h, ptr(img), w, h, 3 * w, C.c_float(max_gain), C.c_float(min_gain), ptr(out), 3 * w, C.byref(g)))
+        return out, np.float32(g.value)
+
+    def gammas(self):
+        """the gamma each frame of the last batch run (or the last extract_color, as frame 0) was read with"""
+        n = self.shape[0]
+        out = np.empty(n, np.float32)
+        self._chk(lib().rmcv_batch_get_gammas(self._h, ptr(out), n))
+        return out
+
     def extract_color_csr(self, image, target=CAMP_BLUE, lower_bound=80, morph=MORPH_CLOSE):
         image, h, w, rowb = self._frame(image)
         binary = np.empty((h, w), np.uint8)

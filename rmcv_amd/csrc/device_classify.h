@@ -26,10 +26,13 @@ struct WarpCtx {
     // layout word of the buffer (device_bayer.h)
     const uint8_t* frame;
     int fw, fh, bx, by, rx, ry, lay;
+    // a frame read through its gamma table (RMCV_OPT_ENHANCE, BAYER == 2): the frame's 256 entries
+    const uint8_t* lut;
 };
 
 // one channel triple of the warped ROI at (x, y): cv::warpAffine INTER_LINEAR, BORDER_CONSTANT 0, CV_8UC3.  BAYER: the ROI's pixels
 // are D(m) of the frame's mosaic, each computed from the FRAME's neighbourhood (not the ROI's); outside the box still 0.
+// BAYER == 2: a BGR frame whose every byte goes through W.lut -- the icon of E(f); outside the box still 0 (the border constant is no frame byte).
 template <int BAYER = 0>
 __device__ inline void warp_px(const WarpCtx& W, int x, int y, int out[3])
 {
@@ -46,7 +49,7 @@ __device__ inline void warp_px(const WarpCtx& W, int x, int y, int out[3])
     if (w00 > 32767) { w00 = 32767; w11 += 1; }
     const bool y0ok = sy >= 0 && sy < W.bh, y1ok = sy + 1 >= 0 && sy + 1 < W.bh;
     const bool x0ok = sx >= 0 && sx < W.bw, x1ok = sx + 1 >= 0 && sx + 1 < W.bw;
-    if constexpr (BAYER) {
+    if constexpr (BAYER == 1) {
         int q00[3] = {0, 0, 0}, q01[3] = {0, 0, 0}, q10[3] = {0, 0, 0}, q11[3] = {0, 0, 0};
         const int X0 = W.bx + sx, Y0 = W.by + sy;
         if (y0ok && x0ok) bayer_bgr_raw(W.frame, W.stride, W.fw, W.fh, W.rx, W.ry, W.lay, X0, Y0, q00);
@@ -62,8 +65,14 @@ __device__ inline void warp_px(const WarpCtx& W, int x, int y, int out[3])
         const uint8_t* p = W.roi + (int64_t)sy * W.stride + 3 * sx;
 #pragma unroll
         for (int c = 0; c < 3; c++) {
-            const int v00 = (y0ok && x0ok) ? p[c] : 0, v01 = (y0ok && x1ok) ? p[3 + c] : 0;
-            const int v10 = (y1ok && x0ok) ? p[W.stride + c] : 0, v11 = (y1ok && x1ok) ? p[W.stride + 3 + c] : 0;
+            int v00 = (y0ok && x0ok) ? p[c] : 0, v01 = (y0ok && x1ok) ? p[3 + c] : 0;
+            int v10 = (y1ok && x0ok) ? p[W.stride + c] : 0, v11 = (y1ok && x1ok) ? p[W.stride + 3 + c] : 0;
+            if constexpr (BAYER == 2) {
+                if (y0ok && x0ok) v00 = W.lut[v00];
+                if (y0ok && x1ok) v01 = W.lut[v01];
+                if (y1ok && x0ok) v10 = W.lut[v10];
+                if (y1ok && x1ok) v11 = W.lut[v11];
+            }
             const int v = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
             out[c] = v < 0 ? 0 : (v > 255 ? 255 : v);
         }
@@ -87,7 +96,7 @@ ClassifyArgs classify_args(const Geom& g, const Bufs& b); // k_classify.hip
 // BAYER: the frames are mosaics of pattern `pattern` in the layout `lay` (the stand-alone k_classify only: the sparse kernel classifies BGR frames)
 template <int BAYER = 0>
 __device__ inline void classify_frame(int f, int lane, int wave, int nwaves, int n, const ClassifyArgs& C, rmcv_armour* __restrict__ armours,
-                                      int max_armours, float* feat, double* sums, int pattern = 0, int lay = 0)
+                                      int max_armours, float* feat, double* sums, int pattern = 0, int lay = 0, const uint8_t* __restrict__ luts = nullptr)
 {
     const uint8_t* frame = C.frames + (int64_t)f * C.frame_pitch;
     const int w = C.w, h = C.h, stride = C.stride, n_class = C.n_class;
@@ -121,7 +130,8 @@ __device__ inline void classify_frame(int f, int lane, int wave, int nwaves, int
         W.stride = stride;
         W.bw = bw;
         W.bh = bh;
-        if constexpr (BAYER) {
+        if constexpr (BAYER == 2) W.lut = luts + (int64_t)f * 256;
+        if constexpr (BAYER == 1) {
             W.frame = frame;
             W.fw = w;
             W.fh = h;

@@ -34,6 +34,16 @@ __global__ __launch_bounds__(256) void k_classify_bayer(ClassifyArgs C, rmcv_arm
     classify_frame<1>(f, lane, wave, 4, n_armours[f], C, armours, max_armours, s_feat[wave], s_sum[wave], pattern, lay);
 }
 
+// the same for frames read through their gamma tables (RMCV_OPT_ENHANCE): the icon is cut from E(f); luts: [frame][256] (Bufs::enh_lut)
+__global__ __launch_bounds__(256) void k_classify_enh(ClassifyArgs C, rmcv_armour* __restrict__ armours, const int32_t* __restrict__ n_armours,
+                                                     int max_armours, const uint8_t* __restrict__ luts)
+{
+    __shared__ float s_feat[4][NFEAT];
+    __shared__ double s_sum[4][32];
+    const int f = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    classify_frame<2>(f, lane, wave, 4, n_armours[f], C, armours, max_armours, s_feat[wave], s_sum[wave], 0, 0, luts);
+}
+
 ClassifyArgs classify_args(const Geom& g, const Bufs& b)
 {
     ClassifyArgs C;
@@ -57,6 +67,7 @@ hipError_t launch_classify(const Geom& g, const Bufs& b, const Limits& lim, hipS
     if (g.input_format != RMCV_INPUT_BGR)
         return launch(k_classify_bayer, dim3(g.n_frames), dim3(256), 0, s, classify_args(g, b), b.armours, b.n_armours, lim.max_armours, g.input_format,
                       raw_layout(8 * g.sample_bytes, g.valid_bit, g.orient));
+    if (g.enhance) return launch(k_classify_enh, dim3(g.n_frames), dim3(256), 0, s, classify_args(g, b), b.armours, b.n_armours, lim.max_armours, b.enh_lut);
     return launch(k_classify, dim3(g.n_frames), dim3(256), 0, s, classify_args(g, b), b.armours, b.n_armours, lim.max_armours);
 }
 

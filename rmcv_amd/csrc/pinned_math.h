@@ -244,4 +244,73 @@ PM_FN double pm_fmod180(double x)
     return x;
 }
 
+/* ---- pow, for the gamma table of rm::CalcGamma (src/imgproc.cpp:43: pow(i / 255.0, gamma) * 255.0) -------------------------
+ * pow(x, g) = exp(g * log(x)) for finite x > 0 (normal) and EVERY finite g, with pow(x, 0) = 1 and pow(0, g > 0) = 0; a result below
+ * the normal range is 0 (pm_exp), so the table of a huge gamma is 0 .. 0 255, as the host libm's is.
+ * log: x = 2^k m, m in [sqrt(1/2), sqrt(2)), log m = 2 atanh(s), s = (m - 1) / (m + 1), |s| <= 0.1716 (the odd series to s^23);
+ * exp: y = n ln2 + r, |r| <= 0.347 (Cody-Waite in two pieces, Taylor to r^13).  Both kernels are good to ~1 ulp; the product
+ * g * log(x) (up to 51 for the table's arguments) carries its rounding into the exponent, so the result's relative error is up to
+ * ~1e-14 -- the table needs 1e-9 (no pow(..) * 255 of the contract's gammas comes closer than 3e-7 to a rounding tie;
+ * tests/test_enhance_cpu.py compares all 256 entries with the host libm's for every such gamma). */
+PM_FN double pm_log(double x)
+{
+    const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
+    uint64_t u;
+    int k;
+    double m, s, z, p;
+    __builtin_memcpy(&u, &x, 8);
+    k = (int)(u >> 52) - 1023;
+    u = (u & 0x000FFFFFFFFFFFFFull) | 0x3FF0000000000000ull;
+    __builtin_memcpy(&m, &u, 8);
+    if (m > 1.4142135623730951) { m = m * 0.5; k = k + 1; }
+    s = (m - 1.0) / (m + 1.0);
+    z = s * s;
+    p = z * (1.0 / 3.0 + z * (1.0 / 5.0 + z * (1.0 / 7.0 + z * (1.0 / 9.0 + z * (1.0 / 11.0 + z * (1.0 / 13.0 + z * (1.0 / 15.0 +
+        z * (1.0 / 17.0 + z * (1.0 / 19.0 + z * (1.0 / 21.0 + z * (1.0 / 23.0)))))))))));
+    return (double)k * ln2_hi + ((2.0 * s + 2.0 * s * p) + (double)k * ln2_lo);
+}
+
+/* exp for every y that is not NaN: 0 below -708 (there the result leaves the normal range; its one caller rounds anything below
+ * 0.5 / 255 to 0, so the subnormal range is flushed rather than computed), +infinity above 709; in between the result is a normal
+ * number and so is the scale 2^n built below (-1022 <= n <= 1023). */
+PM_FN double pm_exp(double y)
+{
+    const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10, inv_ln2 = 1.44269504088896338700e+00;
+    double fn, dn, r, p, scale;
+    int n;
+    uint64_t u;
+    if (y != y) return y;
+    if (y < -708.0) return 0.0;
+    if (y > 709.0) return __builtin_huge_val();
+    fn = y * inv_ln2;
+    n = (int)(fn < 0 ? fn - 0.5 : fn + 0.5);
+    dn = (double)n;
+    r = (y - dn * ln2_hi) - dn * ln2_lo;
+    p = 1.0 / 6227020800.0;
+    p = 1.0 / 479001600.0 + r * p;
+    p = 1.0 / 39916800.0 + r * p;
+    p = 1.0 / 3628800.0 + r * p;
+    p = 1.0 / 362880.0 + r * p;
+    p = 1.0 / 40320.0 + r * p;
+    p = 1.0 / 5040.0 + r * p;
+    p = 1.0 / 720.0 + r * p;
+    p = 1.0 / 120.0 + r * p;
+    p = 1.0 / 24.0 + r * p;
+    p = 1.0 / 6.0 + r * p;
+    p = 0.5 + r * p;
+    p = 1.0 + r * p;
+    p = 1.0 + r * p;
+    u = (uint64_t)(n + 1023) << 52;
+    __builtin_memcpy(&scale, &u, 8);
+    return p * scale;
+}
+
+PM_FN double pm_pow(double x, double g)
+{
+    if (g == 0.0) return 1.0;
+    if (x == 0.0) return 0.0;
+    if (x == 1.0) return 1.0;
+    return pm_exp(g * pm_log(x));
+}
+
 #endif /* RMCV_PINNED_MATH_H */

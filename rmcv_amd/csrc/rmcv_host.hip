@@ -5,6 +5,7 @@
 // rm::extract_color / rm::filter_lightblobs / rm::filter_armours (executable/main.cpp:172-176).
 // No CPU path exists here: every entry point enqueues hand-written HIP kernels.
 #include <math.h>
+#include <cmath>
 #include <sched.h>
 #include <time.h>
 #include <stdio.h>
@@ -16,6 +17,7 @@
 
 #include "rmcv_internal.h"
 #include "device_bayer.h"
+#include "enhance_math.h"
 
 using namespace rmcv;
 
@@ -80,6 +82,8 @@ struct rmcv_ctx {
     int input_sample_bits = 8;    // RMCV_OPT_INPUT_SAMPLE_BITS: 8 or 16   } the Bayer frame as the sensor delivers it; recorded by a
     int input_valid_bit = 0;      // RMCV_OPT_INPUT_VALID_BIT: 0 .. 4      } binding next to the format (Geom::sample_bytes, valid_bit,
     int input_orient = 0;         // RMCV_OPT_INPUT_ORIENT: RMCV_ORIENT_*  } orient)
+    int enhance = 0;              // RMCV_OPT_ENHANCE: frames are read through their rm::AutoEnhance table (a binding records it in Geom::enhance)
+    float enh_max_gain = 100.0f, enh_min_gain = 50.0f; // rmcv_ctx_set_enhance_gains (include/imgproc.h:35)
     // Waits with a deadline (round 5): no entry point parks its caller in the runtime without a bound.  `last_what` names the kernel or
     // copy enqueued last (every HIPCHK of an enqueue leaves its label here): a wait that runs out returns RMCV_ERR_TIMEOUT with it.
     int wait_timeout_ms = 5000;   // RMCV_OPT_WAIT_TIMEOUT_MS (0: no deadline)
@@ -362,6 +366,10 @@ int rmcv_ctx_create(int device, const rmcv_limits* limits, rmcv_ctx** out)
     if (e == hipSuccess) e = dalloc(c, &b.status, F);
     if (e == hipSuccess) e = dalloc(c, &b.frame_order, F);
     if (e == hipSuccess) e = dalloc(c, &c->order_scratch, 2 * F);
+    if (e == hipSuccess) e = dalloc(c, &b.enh_sums, 3 * F);
+    if (e == hipSuccess) e = dalloc(c, &b.enh_gamma, F);
+    if (e == hipSuccess) e = dalloc(c, &b.enh_lut, 256 * F);
+    if (e == hipSuccess) e = dalloc(c, &b.enh_m, 256 * F);
     if (e == hipSuccess) {
         hipMemset(b.strip_ctr, 0, 9 * CTR_STRIDE * sizeof(int));
         hipMemset(b.n_contours, 0, F * 4);
@@ -370,6 +378,10 @@ int rmcv_ctx_create(int device, const rmcv_limits* limits, rmcv_ctx** out)
         hipMemset(b.n_neg, 0, F * 4);
         hipMemset(b.n_armours, 0, F * 4);
         e = hipMemset(b.status, 0, F * 4);
+    }
+    if (e == hipSuccess) { // rmcv_batch_get_gammas before the first run with the option: every frame reads 1 (the identity table)
+        const std::vector<float> ones(F, 1.0f);
+        e = hipMemcpy(b.enh_gamma, ones.data(), F * sizeof(float), hipMemcpyHostToDevice);
     }
     if (e != hipSuccess) {
         fprintf(stderr, "rmcv_ctx_create: %s\n", hipGetErrorString(e));
@@ -394,6 +406,8 @@ int ctx_wait_timeout_ms(const rmcv_ctx* c) { return c->wait_timeout_ms; }
 bool pixel_ws_full(const rmcv_ctx* c, int lower_bound, int pixel_ws) { return binary_ws_full(c->geom, c->bufs, lower_bound, pixel_ws); }
 RunPlan ctx_plan(const rmcv_ctx* c) { return {c->pixel_shape, c->pixel_groups, c->sparse_waves, c->dense_defer ? SPARSE_SPLIT_BOTH : SPARSE_STANDARD}; }
 int ctx_input_format(const rmcv_ctx* c) { return c->input_format; }
+int ctx_enhance(const rmcv_ctx* c) { return c->enhance; }
+int ctx_bound_enhance(const rmcv_ctx* c) { return c->geom.enhance; }
 // bytes of one sample of what the context's options describe: 3 per BGR pixel, 1 or 2 per Bayer sample
 static int ctx_pixel_bytes(const rmcv_ctx* c) { return c->input_format ? c->input_sample_bits / 8 : 3; }
 int ctx_compact(rmcv_ctx* c, void* d_armours_out, int cap, void* d_frame_offs, void* d_status_or, hipStream_t s, void* hd_record, int host_head)
@@ -628,8 +642,12 @@ static int set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t
     if (c->input_format && (w < 3 || h < 3)) return fail(c, RMCV_ERR_BAD_ARG, "a Bayer frame needs w >= 3 and h >= 3");
     if (stride < bpp * w || frame_pitch < (int64_t)stride * (h - 1) + bpp * w) return fail(c, RMCV_ERR_BAD_ARG, "bad stride/pitch");
     if (bpp == 2 && ((stride & 1) || (frame_pitch & 1))) return fail(c, RMCV_ERR_BAD_ARG, "16-bit samples (RMCV_OPT_INPUT_SAMPLE_BITS): stride and frame_pitch are bytes and must be even");
+    if (c->enhance && c->input_format) return fail(c, RMCV_ERR_BAD_ARG, "RMCV_OPT_ENHANCE with a Bayer input format: the mean of a demosaiced frame is not a function of the mosaic's sums");
     { const int rcm = ensure_mid(c, n_frames); if (rcm) return rcm; }
     Geom& g = c->geom;
+    g.enhance = c->enhance;
+    g.enh_max_gain = c->enh_max_gain;
+    g.enh_min_gain = c->enh_min_gain;
     g.input_format = c->input_format;
     g.sample_bytes = c->input_format ? c->input_sample_bits / 8 : 1;
     g.valid_bit = g.sample_bytes == 2 ? c->input_valid_bit : 0;
@@ -696,6 +714,7 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
     int rc;
     // every argument check comes BEFORE the first enqueue (the callers': check_bound): an error return leaves the streams as they were
     if (lp && g.input_format) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
+    if (lp && g.enhance) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not with RMCV_OPT_ENHANCE");
     if ((rc = order_begin(c, s))) return rc;
     if (c->test_delay_us) { // RMCV_OPT_TEST_DELAY_US: a stand-in for a kernel that does not finish in time (one shot)
         HIPCHK(c, launch_delay((unsigned long long)c->test_delay_us * 1000ull, s), "k_delay (RMCV_OPT_TEST_DELAY_US)");
@@ -714,13 +733,15 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
     if (lean) *lean = false;
     const bool one_sparse = !timed && !lp && (stages & RMCV_STAGE_CONTOURS) && (stages & RMCV_STAGE_BLOBS);
     if (stages & RMCV_STAGE_BINARY) {
+        // RMCV_OPT_ENHANCE: every frame's sums, gamma and tables first, at RUN time (borrowed frames may have changed since they were bound)
+        if (g.enhance) HIPCHK(c, launch_enhance_tables(g, b, p->lower_bound, s), "k_frame_sums + k_enhance_table");
         HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, !(stages & RMCV_STAGE_NO_IMAGE), plan, s),
-               g.input_format ? "k_binary_bayer" : "k_binary");
+               g.input_format ? "k_binary_bayer" : (g.enhance ? "k_binary_enh" : "k_binary"));
     }
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
     // the icon classifier rides in the per-frame kernel when the armours come from it (BASELINE config 5: no launch of its own)
-    // (not for mosaics: the sparse kernel's classifier reads BGR; k_classify has the Bayer accessor)
-    const bool identity_fused = one_sparse && (stages & RMCV_STAGE_ARMOURS) && (stages & RMCV_STAGE_IDENTITY) && g.input_format == RMCV_INPUT_BGR;
+    // (not for mosaics: the sparse kernel's classifier reads BGR; k_classify has the Bayer accessor -- and the one through a frame's gamma table)
+    const bool identity_fused = one_sparse && (stages & RMCV_STAGE_ARMOURS) && (stages & RMCV_STAGE_IDENTITY) && g.input_format == RMCV_INPUT_BGR && !g.enhance;
     if (one_sparse) HIPCHK(c, launch_sparse(g, b, c->lim, *p, (stages & RMCV_STAGE_ARMOURS) != 0, identity_fused, plan, s, lean), "k_contours (fused)");
     else if (stages & RMCV_STAGE_CONTOURS) HIPCHK(c, launch_contours(g, b, c->lim, s), "k_contours");
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
@@ -852,6 +873,7 @@ int rmcv_batch_run_legacy(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_p
     if (rc) return rc;
     if (!lp) return fail(c, RMCV_ERR_BAD_ARG, "null legacy params");
     if (c->input_format || c->geom.input_format) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
+    if (c->enhance || c->geom.enhance) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not with RMCV_OPT_ENHANCE");
     hipSetDevice(c->device);
     return run_stages(c, p, stages, hip_stream ? (hipStream_t)hip_stream : c->stream, false, ctx_plan(c), lp);
 }
@@ -928,6 +950,10 @@ int rmcv_ctx_set_option(rmcv_ctx* c, int option, int value)
     }
     if (option == RMCV_OPT_INPUT_ORIENT && value >= 0 && value <= (RMCV_ORIENT_MIRROR | RMCV_ORIENT_FLIP)) {
         c->input_orient = value;
+        return RMCV_OK;
+    }
+    if (option == RMCV_OPT_ENHANCE && (value == 0 || value == 1)) {
+        c->enhance = value; // (like the format: frames bound before keep what they were bound with)
         return RMCV_OK;
     }
     if (option == RMCV_OPT_PIXEL_GROUPS && value >= 1 && value <= 8) {
@@ -1214,6 +1240,7 @@ int rmcv_classify_armours(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int str
     if (n == 0) return RMCV_OK;
     HIPCHK(c, hipMemcpy(c->bufs.armours, armours, (size_t)n * sizeof(rmcv_armour), hipMemcpyHostToDevice), "H2D armours");
     HIPCHK(c, hipMemcpy(c->bufs.n_armours, &n, 4, hipMemcpyHostToDevice), "H2D");
+    if (c->geom.enhance) HIPCHK(c, launch_enhance_tables(c->geom, c->bufs, 1, c->stream), "k_frame_sums + k_enhance_table"); // the icon is cut from E(f)
     HIPCHK(c, launch_classify(c->geom, c->bufs, c->lim, c->stream), "k_classify");
     WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
     HIPCHK(c, hipMemcpy(armours, c->bufs.armours, (size_t)n * sizeof(rmcv_armour), hipMemcpyDeviceToHost), "D2H armours");
@@ -1463,7 +1490,8 @@ static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int
         HIPCHK(c, launch_delay((unsigned long long)c->test_delay_us * 1000ull, s), "k_delay (RMCV_OPT_TEST_DELAY_US)");
         c->test_delay_us = 0;
     }
-    HIPCHK(c, launch_binary(g, b, camp, lower_bound, morph, binary_out != nullptr, plan, s), g.input_format ? "k_binary_bayer" : "k_binary");
+    if (g.enhance) HIPCHK(c, launch_enhance_tables(g, b, lower_bound, s), "k_frame_sums + k_enhance_table"); // RMCV_OPT_ENHANCE: the frame is read through its table
+    HIPCHK(c, launch_binary(g, b, camp, lower_bound, morph, binary_out != nullptr, plan, s), g.input_format ? "k_binary_bayer" : (g.enhance ? "k_binary_enh" : "k_binary"));
     if (binary_out) HIPCHK(c, hipEventRecord(c->ev_fork, s), "image download: mark");
     // running ahead with both parameter sets known: the frame's whole sparse part is ONE kernel (the fused per-frame kernel of
     // the batch path: findContours, fits and pairing back to back), not three
@@ -2000,12 +2028,131 @@ int rmcv_demosaic_raw(rmcv_ctx* c, const void* raw, int w, int h, int stride, in
     return demosaic_body(c, (const uint8_t*)raw, w, h, stride, pattern, rmcv::raw_layout(sample_bits, valid_bit, orient), bgr_out, out_stride);
 }
 
+/* ---- exposure-adaptive detection: rm::CalcGamma / rm::AutoEnhance (src/imgproc.cpp:37-48, 77-98) ---- */
+
+int rmcv_gamma_lut(float gamma, uint8_t lut[256])
+{
+    if (!lut || !(gamma >= 0.0f) || !std::isfinite(gamma)) return RMCV_ERR_BAD_ARG;
+    for (int i = 0; i < 256; i++) lut[i] = enh_lut_entry(i, gamma);
+    return RMCV_OK;
+}
+
+static bool gains_ok(float max_gain, float min_gain) { return std::isfinite(max_gain) && std::isfinite(min_gain) && max_gain != min_gain; }
+
+int rmcv_enhance_gamma(const uint64_t sums_bgr[3], int64_t n_pixels, float max_gain, float min_gain, float* gamma)
+{
+    if (!sums_bgr || !gamma || n_pixels <= 0 || !gains_ok(max_gain, min_gain)) return RMCV_ERR_BAD_ARG;
+    *gamma = enh_gamma(sums_bgr, n_pixels, max_gain, min_gain);
+    return RMCV_OK;
+}
+
+int rmcv_ctx_set_enhance_gains(rmcv_ctx* c, float max_gain, float min_gain)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!gains_ok(max_gain, min_gain)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_ctx_set_enhance_gains: the gains must be finite and differ");
+    c->enh_max_gain = max_gain; // (like the option: frames bound before keep what they were bound with)
+    c->enh_min_gain = min_gain;
+    return RMCV_OK;
+}
+
+int rmcv_ctx_get_enhance(const rmcv_ctx* c, int32_t* on, float* max_gain, float* min_gain)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (on) *on = c->enhance;
+    if (max_gain) *max_gain = c->enh_max_gain;
+    if (min_gain) *min_gain = c->enh_min_gain;
+    return RMCV_OK;
+}
+
+int rmcv_batch_get_gammas(rmcv_ctx* c, float* gamma_out, int cap)
+{
+    if (!c || !gamma_out || cap < 0) return RMCV_ERR_BAD_ARG;
+    hipSetDevice(c->device);
+    int rc = rmcv_batch_sync(c);
+    if (rc) return rc;
+    const int n = std::min(cap, c->geom.n_frames);
+    if (n <= 0) return RMCV_OK;
+    if (!c->geom.enhance) { // read as they are: gamma 1 is the identity table
+        for (int i = 0; i < n; i++) gamma_out[i] = 1.0f;
+        return RMCV_OK;
+    }
+    HIPCHK(c, hipMemcpy(gamma_out, c->bufs.enh_gamma, (size_t)n * sizeof(float), hipMemcpyDeviceToHost), "D2H gammas");
+    return RMCV_OK;
+}
+
+} // extern "C"
+
+// rmcv_calc_gamma / rmcv_auto_enhance: a host image of `rows` rows of `row_bytes` bytes through a table, on the device.  A stage-wise
+// helper like rmcv_demosaic: buffers of its own, so that nothing bound to the context moves.  auto_w > 0: the image is a BGR frame of
+// auto_w pixels per row and the table is that of ITS gamma (sums and table on the device); otherwise the table of `gamma`.
+static int bytemap_body(rmcv_ctx* c, const uint8_t* src, int row_bytes, int rows, int src_stride, float gamma, int auto_w, float max_gain, float min_gain,
+                        uint8_t* dst, int dst_stride, float* gamma_out, const char* who)
+{
+    hipSetDevice(c->device);
+    int rc = rmcv_batch_sync(c);
+    if (rc) return rc;
+    const int dstride = (row_bytes + 15) & ~15;
+    const size_t img = (size_t)dstride * rows;
+    // [image | sums 3 x 8 | gamma 4 + pad 4 | table 256 | threshold table 512]
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, img + 32 + 256 + 512);
+    hipStream_t s = c->stream;
+    if (e == hipSuccess && dstride != row_bytes) e = hipMemsetAsync(d, 0, img, s); // (the pad bytes go through the table too: keep them defined)
+    if (e == hipSuccess) e = hipMemcpy2DAsync(d, dstride, src, src_stride, (size_t)row_bytes, rows, hipMemcpyHostToDevice, s);
+    uint8_t* d_lut = d + img + 32;
+    if (e == hipSuccess) {
+        if (auto_w > 0) {
+            Geom g1 = c->geom;
+            g1.n_frames = 1; g1.w = auto_w; g1.h = rows; g1.stride = dstride; g1.frame_pitch = (int64_t)img;
+            g1.enh_max_gain = max_gain; g1.enh_min_gain = min_gain;
+            Bufs b1{};
+            b1.frames = d;
+            b1.enh_sums = reinterpret_cast<uint64_t*>(d + img);
+            b1.enh_gamma = reinterpret_cast<float*>(d + img + 24);
+            b1.enh_lut = d_lut;
+            b1.enh_m = reinterpret_cast<uint16_t*>(d + img + 32 + 256);
+            e = launch_enhance_tables(g1, b1, 1, s);
+        } else e = launch_gamma_lut(gamma, d_lut, s);
+    }
+    if (e == hipSuccess) e = launch_bytemap(d, d, (int64_t)(img / 16), d_lut, c->geom.n_cu, s);
+    c->last_what = auto_w > 0 ? "k_frame_sums, k_enhance_table, k_bytemap" : "k_gamma_lut, k_bytemap";
+    int rcw = 0;
+    if (e == hipSuccess) rcw = wait_stream(c, s, who);
+    if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(dst, dst_stride, d, dstride, (size_t)row_bytes, rows, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rcw == 0 && gamma_out && auto_w > 0) e = hipMemcpy(gamma_out, d + img + 24, sizeof(float), hipMemcpyDeviceToHost);
+    if (d && (rcw == 0 || e != hipSuccess)) hipFree(d); // (after a wait that ran out the kernels may still be using it)
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, who, e);
+    return rcw;
+}
+
+extern "C" {
+
+int rmcv_calc_gamma(rmcv_ctx* c, const uint8_t* src, int row_bytes, int rows, int src_stride, float gamma, uint8_t* dst, int dst_stride)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!src || !dst) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_calc_gamma: null buffer");
+    if (row_bytes < 1 || rows < 1 || src_stride < row_bytes || dst_stride < row_bytes) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_calc_gamma: bad size or stride");
+    if (!(gamma >= 0.0f) || !std::isfinite(gamma)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_calc_gamma: gamma must be finite and not negative");
+    return bytemap_body(c, src, row_bytes, rows, src_stride, gamma, 0, 0.0f, 0.0f, dst, dst_stride, nullptr, "rmcv_calc_gamma");
+}
+
+int rmcv_auto_enhance(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, float max_gain, float min_gain, uint8_t* out, int out_stride,
+                      float* gamma_out)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!bgr || !out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_auto_enhance: null buffer");
+    if (w < 1 || h < 1 || w > 65536 || h > 65536 || stride < 3 * w || out_stride < 3 * w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_auto_enhance: bad size or stride");
+    if (!gains_ok(max_gain, min_gain)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_auto_enhance: the gains must be finite and differ");
+    return bytemap_body(c, bgr, 3 * w, h, stride, 0.0f, w, max_gain, min_gain, out, out_stride, gamma_out, "rmcv_auto_enhance");
+}
+
 int rmcv_find_lightblobs(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, const rmcv_point* pts, const int32_t* offs,
                          int n_contours, const rmcv_legacy_params* lp, rmcv_lightblob* blobs_out, int blobs_cap, int32_t* n_blobs,
                          int32_t* blob_src, rmcv_rrect* boxes_out)
 {
     if (!c || !bgr || !lp || (n_contours > 0 && (!pts || !offs))) return RMCV_ERR_BAD_ARG;
     if (c->input_format) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
+    if (c->enhance) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not with RMCV_OPT_ENHANCE");
     hipSetDevice(c->device);
     int rc = rmcv_batch_upload(c, bgr, 1, w, h, stride, (int64_t)stride * h); // source.channels() == 3 is the ABI's only format
     if (rc) return rc;

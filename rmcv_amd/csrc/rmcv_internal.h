@@ -34,6 +34,8 @@ struct Geom {
     int ww;              // words per row = ceil(w / 64)
     int prow;            // padded words per row = ww + 2
     int64_t plane_pitch; // words per frame = (h + 2) * prow
+    int enhance;         // RMCV_OPT_ENHANCE of the frames bound: the pixel pass and the classifier read every byte through the frame's gamma table
+    float enh_max_gain, enh_min_gain; // rmcv_ctx_set_enhance_gains, recorded with it
 };
 
 // What a run's launches depend on beyond geometry, buffers and params.  The public entry points take it from the context's options
@@ -109,6 +111,11 @@ struct Bufs {
     rmcv_pnp_config* pnp_cfg;
     double* base2gripper;  // [frame][16]
     double* poses;         // [frame][max_armours][9]  rvec | tvec | world position
+    // exposure-adaptive detection (RMCV_OPT_ENHANCE; k_enhance.hip): rewritten by every run with the option on, in front of the pixel pass
+    uint64_t* enh_sums;    // [frame][3]   exact sums of the B, G, R bytes
+    float* enh_gamma;      // [frame]      rm::AutoEnhance's gamma of the frame
+    uint8_t* enh_lut;      // [frame][256] rm::CalcGamma's table of that gamma
+    uint16_t* enh_m;       // [frame][256] the pixel kernel's threshold table (enhance_math.h: enh_m_entry) for the run's lower bound
 };
 
 // internal value of a frame's status word BETWEEN the two launches of the sparse stage (never seen by a caller: the second launch
@@ -155,6 +162,15 @@ hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound
 bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound, int pixel_ws); // the batch will run as one launch of k_binary_ws with a workgroup on every CU
 // the pixel stage of a Bayer batch (Geom::input_format != 0; k_binary_bayer.hip); launch_binary hands such batches to it
 hipError_t launch_binary_bayer(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, hipStream_t s);
+// exposure-adaptive detection (k_enhance.hip, k_binary_enh.hip).  launch_enhance_tables: the channel sums of the frames bound, then every
+// frame's gamma, table and threshold table for `lower_bound` (Bufs::enh_*), in front of the pixel pass on the same stream.
+hipError_t launch_enhance_tables(const Geom& g, const Bufs& b, int lower_bound, hipStream_t s);
+// the pixel stage reading through Bufs::enh_m (Geom::enhance; launch_binary hands such batches to it): k_binary's shape, never k_binary_ws
+hipError_t launch_binary_enh(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s);
+// dst[i] = lut[src[i]] over n16 16-byte vectors of a staged image (rm::CalcGamma); dst == src allowed
+hipError_t launch_bytemap(const uint8_t* d_src, uint8_t* d_dst, int64_t n16, const uint8_t* d_lut, int n_cu, hipStream_t s);
+// lut[0..255] of `gamma` on the device (the table builder of enhance_math.h)
+hipError_t launch_gamma_lut(float gamma, uint8_t* d_lut, hipStream_t s);
 // D(m) of one device mosaic into a device BGR frame (rmcv_demosaic)
 // lay: the buffer's layout word (device_bayer.h: raw_layout; 0 = a plain 8-bit mosaic) -> D(T(r)) (rmcv_demosaic_raw)
 hipError_t launch_demosaic(const uint8_t* d_raw, int stride, int w, int h, int pattern, int lay, uint8_t* d_out, int out_stride, hipStream_t s);
@@ -224,5 +240,9 @@ hipError_t launch_delay(unsigned long long ns, hipStream_t s); // holds `s` back
 int ctx_check_stages(rmcv_ctx* c, const rmcv_params* p, int stages);
 // RMCV_OPT_INPUT_FORMAT as set on the context (what the next binding records)
 int ctx_input_format(const rmcv_ctx* c);
+// RMCV_OPT_ENHANCE as set on the context
+int ctx_enhance(const rmcv_ctx* c);
+// ... and as the frames bound last recorded it (what the runs on them do)
+int ctx_bound_enhance(const rmcv_ctx* c);
 
 } // namespace rmcv

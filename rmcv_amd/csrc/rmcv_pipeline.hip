@@ -601,11 +601,19 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
                        !(stages & (RMCV_STAGE_IDENTITY | RMCV_STAGE_POSE)) && (stages & RMCV_STAGE_CONTOURS) && (stages & RMCV_STAGE_BLOBS);
     // (batches with a classifier stage stay out of the hot rotation: measured in round 5, three contexts at 256 x 1920x1200, 0.514 against
     // 0.426 ms per step with them in it)
-    const bool fast = pl->hot && pl->calm && !lp && !(stages & RMCV_STAGE_POSE) && !(stages & RMCV_STAGE_IDENTITY);
+    // (so do batches read through their gamma tables, RMCV_OPT_ENHANCE on the slot's context: they take the k_binary shape, and the sums pass in
+    // front of it has no use for another batch's planes in the cache)
+    const bool fast = pl->hot && pl->calm && !lp && !(stages & RMCV_STAGE_POSE) && !(stages & RMCV_STAGE_IDENTITY) && !ctx_enhance(pl->ring[k]);
     const size_t j = fast ? (size_t)(pl->hot_seq % (uint64_t)pl->hot) : k;
     rmcv_ctx* c = pl->ring[j];
     int rc;
     if (lp && ctx_input_format(c)) return pfail(pl, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
+    // the rotation is decided from the slot's own context and the batch may run in another (ring[j]): a ring whose contexts disagree
+    // about the option would mix the two paths batch by batch -- refused, loudly, whichever slot this batch would take
+    for (size_t i = 1; i < pl->ring.size(); i++)
+        if (ctx_enhance(pl->ring[i]) != ctx_enhance(pl->ring[0]))
+            return pfail(pl, RMCV_ERR_BAD_ARG, "RMCV_OPT_ENHANCE differs between the pipeline's contexts: set it on EVERY slot (rmcv_pipeline_context)");
+    if (lp && ctx_enhance(c)) return pfail(pl, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not with RMCV_OPT_ENHANCE");
     // a batch is several runs on several streams: everything that could refuse it is checked before the first enqueue (the binding below
     // enqueues a new geometry's work on A)
     if ((rc = ctx_check_stages(c, p, stages))) return cfail(pl, c, rc);
@@ -662,7 +670,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     }
     rc = ctx_run(c, p, nullptr, pixel, A, plan);
     if (rc) return cfail(pl, c, rc);
-    pl->last_what = ctx_input_format(c) ? "the pixel kernel (k_binary_bayer)" : "the pixel kernel (k_binary / k_binary_ws)";
+    pl->last_what = ctx_input_format(c) ? "the pixel kernel (k_binary_bayer)" : ctx_bound_enhance(c) ? "k_frame_sums, k_enhance_table, the pixel kernel (k_binary_enh)" : "the pixel kernel (k_binary / k_binary_ws)";
     // ---- accepted: the pipeline's state moves
     pl->was_cold = cold;
     if (fast) { pl->hot_seq++; pl->hot_batches++; }

@@ -16,7 +16,8 @@ from .api import Context
 
 class Pipeline:
     def __init__(self, device=0, depth=0, pixel_streams=0, sparse_streams=0, armour_cap=0, sparse_waves=0, pixel_groups=0,
-                 host_results=0, dense_streams=0, hot_contexts=0, input_format=0, sample_bits=8, valid_bit=0, mirror=False, flip=False, **limits):
+                 host_results=0, dense_streams=0, hot_contexts=0, input_format=0, sample_bits=8, valid_bit=0, mirror=False, flip=False, enhance=None,
+                 **limits):
         lim = Limits()
         lib().rmcv_default_limits(C.byref(lim))
         for k, v in limits.items():
@@ -44,6 +45,14 @@ class Pipeline:
         if self.sample_bits != 8 or valid_bit or mirror or flip:  # the frame as the sensor delivers it, on every slot likewise
             for c in self.contexts:
                 c.set_input_layout(sample_bits, valid_bit, mirror, flip)
+        if enhance:  # RMCV_OPT_ENHANCE on every slot: True, or the gains (max, min)
+            self.set_enhance(True, *(enhance if isinstance(enhance, (tuple, list)) else ()))
+
+    def set_enhance(self, on=True, max_gain=None, min_gain=None):
+        """RMCV_OPT_ENHANCE (and the gains) on every slot's context, from the next submit on: batches are read through their frames'
+        rm::AutoEnhance tables and stay out of the hot rotation"""
+        for c in self.contexts:
+            c.set_enhance(on, max_gain, min_gain)
 
     def close(self):
         if getattr(self, "_h", None):
