@@ -391,6 +391,53 @@ int rmcv_batch_get_armours(rmcv_ctx* ctx, rmcv_armour* armours_out, int cap, int
 int rmcv_batch_device_views(rmcv_ctx* ctx, void** d_armours, void** d_counts, int32_t* per_frame_cap,
                             int32_t* n_frames);
 
+/* ---- windowed detection: look only where the target was (rm::utils::GetROI, src/core.cpp:218-263; extract_color on image(roi);
+ * the ROI argument of rm::solve_PnP, src/mobility.cpp:168-185) ------------------------------------------------------------------
+ * A windowed batch: the n frames bound (frame_w x frame_h, stride, frame_pitch as ever), ONE window size win_w x win_h for the batch and
+ * one requested origin (x, y) per frame, int32 of any value.  The EFFECTIVE origin of a frame is computed on the device, in one place
+ * (k_window_origins), written to a per-frame table and read from there by every consumer:
+ *     x_eff = clamp(x, 0, frame_w - win_w) & ~15          y_eff = clamp(y, 0, frame_h - win_h)
+ * The clamp is there because origins may come from a tracker on the device that the host never reads; the snap to 16 pixels (48 bytes)
+ * keeps window rows 16-byte aligned for the pixel kernel's loader -- it is part of the semantics and always applied, whichever loader runs.
+ * Every result for frame f is, bit for bit, what the same run gives for the cropped image frame[y_eff : y_eff + win_h, x_eff : x_eff +
+ * win_w] bound as a whole frame -- what the reference computes on image(roi): the byte image is win_h x win_w; contours, light blobs and
+ * armours are in WINDOW coordinates; RMCV_STAGE_IDENTITY clamps icons to win_w - 1, win_h - 1; the legacy matcher votes camps from the
+ * crop's means.  RMCV_STAGE_POSE follows mobility.cpp:172, 182-185: every image point is vertex + (float)x_eff, vertex + (float)y_eff
+ * in float before undistortion.  NOT promised: equality with whole-frame detection translated into the window -- window edges cut
+ * contours, and the ellipse fit is not bit-translation-invariant (on the synthetic stream, 512x384 windows centred on the first
+ * whole-frame armour: an armour in 64 of 64 windows, the whole-frame armour's exact vertices in 9).  rmcv_armours_to_frame is a
+ * convenience, not a second detection.
+ * The pixel pass reads 3 win_w win_h bytes per frame instead of 3 w h (k_binary_win: the pixel kernel at the effective origins; k_binary's
+ * shape, never k_binary_ws); everything behind it runs on window-sized planes.
+ * RMCV_ERR_BAD_ARG, with a message: windows with a Bayer RMCV_OPT_INPUT_FORMAT or with RMCV_OPT_ENHANCE (crop-then-demosaic and
+ * crop-then-AutoEnhance have other border and mean semantics); win_w / win_h < 1, larger than the frames, or larger than the context's
+ * limits; no frames bound.  One window size per batch. */
+/* after the frames are bound (rmcv_batch_upload / rmcv_batch_set_device_frames; a new binding returns to whole frames): origins =
+ * n_frames host points, copied.  win_w == 0: back to whole frames (origins ignored).  Synchronises the context. */
+int rmcv_batch_set_windows(rmcv_ctx* ctx, const rmcv_point* origins, int win_w, int win_h);
+/* the same with the origins in device memory (n_frames rmcv_point), BORROWED: every run that includes RMCV_STAGE_BINARY reads them again,
+ * on its stream, in front of its pixel pass -- a tracker kernel enqueued before the run may have rewritten them */
+int rmcv_batch_set_device_windows(rmcv_ctx* ctx, const void* d_origins, int win_w, int win_h);
+/* the effective origins of the frames bound (the first min(cap, n_frames); (0, 0) without windows) and the window size (0, 0 without);
+ * any pointer may be NULL with cap 0.  Synchronises the context. */
+int rmcv_batch_get_windows(rmcv_ctx* ctx, rmcv_point* eff_out, int cap, int32_t* win_w, int32_t* win_h);
+/* device view of the effective-origin table (n_frames rmcv_point; NULL without windows), valid behind the run on its stream: for a
+ * consumer on the device that moves results to frame coordinates */
+int rmcv_batch_device_windows(rmcv_ctx* ctx, void** d_eff, int32_t* win_w, int32_t* win_h);
+/* Host-side helpers of the locked-target loop (no context, no device), detect -> track -> GetROI -> window -> detect:
+ * rm::utils::GetROI, verbatim: points = n (x, y) float pairs; boundingRect on float points (floor of min, floor of max - floor of min + 1;
+ * n == 0: the empty rect), + previous.x / .y (previous[4] = x, y, w, h; NULL: zeros); unless both scales are 1: margins
+ * (int)((double)w * scale_w / 2.0), (int)((double)h * scale_h / 2.0), x -= mw, y -= mh, w += 2 mw, h += 2 MW -- the reference adds the
+ * WIDTH's margin to the height (core.cpp:238), mirrored; x, y < 0 -> 0 (sizes unchanged); x + w >= frame_w -> w = frame_w - x - 1, same
+ * for h; a negative size -> {0, 0, 0, 0}.  out[4] = x, y, w, h. */
+int rmcv_get_roi(const float* points, int n, float scale_w, float scale_h, int frame_w, int frame_h, const int32_t previous[4], int32_t out[4]);
+/* the requested origin of a win_w x win_h window centred on rect[4]: (x + w / 2 - win_w / 2, y + h / 2 - win_h / 2), integer arithmetic
+ * (the library clamps and snaps it: see above) */
+int rmcv_window_origin(const int32_t rect[4], int win_w, int win_h, int32_t out_xy[2]);
+/* window -> frame coordinates: icon, vertices and bbox.x / .y of every armour + ((float)x, (float)y), one f32 add each (a convenience:
+ * see NOT promised above) */
+int rmcv_armours_to_frame(rmcv_armour* armours, int n, int x, int y);
+
 /* ---- icon classifier: the "next" row of the path (executable/main.cpp:178-181) ------------------------ */
 #define RMCV_SVM_FEATURES 1200 /* 20 x 20 x BGR, executable/main.cpp:180 ({20, 20}), core.cpp:202-216 */
 /* linear one-vs-one C_SVC as cv::ml::SVM keeps it after training (executable/svm/optimizer.cpp:16-19): one weight
@@ -638,6 +685,14 @@ int  rmcv_pipeline_submit(rmcv_pipeline* pl, const void* d_frames, int n_frames,
 /* the same with rm::FindLightBlobs as the blob stage (rmcv_batch_run_legacy) */
 int  rmcv_pipeline_submit_legacy(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch,
                                  const rmcv_params* p, const rmcv_legacy_params* lp, int stages, uint64_t* ticket);
+/* a WINDOWED batch (see rmcv_batch_set_windows): d_origins = n_frames rmcv_point in DEVICE memory, borrowed like the frames and read on
+ * the batch's stream in front of its pixel pass -- the host need never see them; nothing blocks (host_blocking_calls stays 0).  The
+ * batch takes the k_binary shape and stays out of the hot-context rotation, as batches with RMCV_OPT_ENHANCE do; windowed and whole-frame
+ * submits may alternate on one pipeline (each change of a context's geometry is enqueued work: planes zeroed, frame order recomputed).
+ * The record is the usual one, armours in window coordinates; rmcv_pipeline_context_of(ticket) + rmcv_batch_get_windows give the
+ * effective origins. */
+int  rmcv_pipeline_submit_windows(rmcv_pipeline* pl, const void* d_frames, int n_frames, int frame_w, int frame_h, int stride, int64_t frame_pitch,
+                                  const void* d_origins, int win_w, int win_h, const rmcv_params* p, int stages, uint64_t* ticket);
 /* block until the batch is through (its record complete in HBM and, with host_results, on the host) */
 int  rmcv_pipeline_wait(rmcv_pipeline* pl, uint64_t ticket);
 /* wait + hand the batch's armours over, frame-major, in submission order of the frames: frame_offs (nullable) has n_frames + 1

@@ -19,6 +19,7 @@
 // rm::extract_color_raw, the same on the sensor's buffer as delivered (8- or 16-bit samples, to be mirrored and / or flipped).
 // rm::CalcGamma and rm::AutoEnhance (include/imgproc.h:23, 35) are here too, and one more addition: rm::extract_color_enhanced, the two
 // of rm::AutoEnhance + rm::extract_color fused (the enhanced frame is never written).
+// rm::utils::GetROI (include/core.h:142-147), the reference's tracked-ROI helper, is here as well (where the cv:: headers know cv::Size).
 // The legacy names of the north star are aliased at the bottom (docs/core_8h_source.html:101,114).
 //
 // Every signature mentions cv:: types, so this header only compiles where OpenCV headers exist.
@@ -338,6 +339,31 @@ RMCV_SHIM_LINKAGE std::tuple<cv::Mat, cv::Mat> solve_PnP(const cv::Point2f point
                                           translation_vector.ptr<double>(), nullptr));
     return {rotation_vector, translation_vector};
 }
+
+// ---- rm::utils::GetROI, both overloads of include/core.h:142-147 (body src/core.cpp:218-263) over rmcv_get_roi, which mirrors the body
+// statement by statement -- the height grown by the WIDTH's margin included (src/core.cpp:238).  The default arguments live on the
+// reference's declarations.  The locked-target loop needs nothing else of the shim: rm::extract_color takes the sub-view image(roi) as
+// it takes any cv::Mat (the view's step is the frame's), and rm::solve_PnP above puts the ROI's corner back.
+// (Guarded: only where the cv:: headers in use know cv::Size -- real OpenCV, or a stand-in that says so.)
+#if defined(CV_VERSION) || defined(RMCV_CV_HAS_SIZE)
+namespace utils {
+RMCV_SHIM_LINKAGE cv::Rect GetROI(cv::Point2f* imagePoints, int pointsCount, const cv::Size2f& scaleFactor, const cv::Size& frameSize,
+                                  const cv::Rect& previous)
+{
+    static_assert(sizeof(cv::Point2f) == 2 * sizeof(float), "cv::Point2f is two floats");
+    const int32_t prev[4] = {previous.x, previous.y, previous.width, previous.height};
+    int32_t out[4] = {0, 0, 0, 0};
+    if (rmcv_get_roi(reinterpret_cast<const float*>(imagePoints), pointsCount, scaleFactor.width, scaleFactor.height, frameSize.width,
+                     frameSize.height, prev, out) != RMCV_OK)
+        throw std::invalid_argument("rm::utils::GetROI: null points or a negative count");
+    return cv::Rect(out[0], out[1], out[2], out[3]);
+}
+RMCV_SHIM_LINKAGE cv::Rect GetROI(cv::Point2f* imagePoints, int pointsCount, float scaleFactor, const cv::Size& frameSize, const cv::Rect& previous)
+{
+    return GetROI(imagePoints, pointsCount, cv::Size2f(scaleFactor, scaleFactor), frameSize, previous); // src/core.cpp:221
+}
+} // namespace utils
+#endif
 
 using LightBlob = lightblob; // pre-2024 API names used by the north star
 using Armour = armour;

@@ -73,6 +73,8 @@ EXPORTS = [
     "rmcv_pipeline_set_hook", "rmcv_pipeline_set_gather", "rmcv_pipeline_gathered", "rmcv_device_alloc", "rmcv_device_free", "rmcv_device_upload", "rmcv_device_download",
     "rmcv_track_init", "rmcv_track_reset", "rmcv_track_update", "rmcv_track_predict", "rmcv_track_step", "rmcv_min_area_rect", "rmcv_match_lightblob", "rmcv_find_lightblobs", "rmcv_lightblob_overlap", "rmcv_batch_run_legacy",
     "rmcv_ctx_set_enhance_gains", "rmcv_ctx_get_enhance", "rmcv_gamma_lut", "rmcv_enhance_gamma", "rmcv_calc_gamma", "rmcv_auto_enhance", "rmcv_batch_get_gammas",
+    "rmcv_batch_set_windows", "rmcv_batch_set_device_windows", "rmcv_batch_get_windows", "rmcv_batch_device_windows", "rmcv_pipeline_submit_windows",
+    "rmcv_get_roi", "rmcv_window_origin", "rmcv_armours_to_frame",
 ]
 
 
@@ -178,6 +180,16 @@ def load(path):
         L.rmcv_calc_gamma.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_void_p, C.c_int]
         L.rmcv_auto_enhance.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_void_p, C.c_int, C.c_void_p]
         L.rmcv_batch_get_gammas.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+    if hasattr(L, "rmcv_get_roi"):  # (builds from before windowed detection stay loadable for A/B runs)
+        L.rmcv_batch_set_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.rmcv_batch_set_device_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.rmcv_batch_get_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
+        L.rmcv_batch_device_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_pipeline_submit_windows.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int,
+                                                   C.c_void_p, C.c_int, C.c_void_p]
+        L.rmcv_get_roi.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.rmcv_window_origin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
+        L.rmcv_armours_to_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L
@@ -221,6 +233,42 @@ def enhance_gamma(sums_bgr, n_pixels, max_gain=ENHANCE_MAX_GAIN, min_gain=ENHANC
     if rc:
         raise RmcvError(rc, "rmcv_enhance_gamma: the gains must be finite and differ, n_pixels >= 1")
     return np.float32(g.value)
+
+
+def get_roi(points, scale=1.0, frame_size=(-1, -1), previous=(0, 0, 0, 0)):
+    """rm::utils::GetROI (rmcv_get_roi: host-side, verbatim -- the height grows by the WIDTH's margin, as the reference writes it):
+    points (n, 2) float32, scale a float or (scale_w, scale_h), frame_size (w, h), previous (x, y, w, h) -> (x, y, w, h)"""
+    pts = np.ascontiguousarray(points, np.float32).reshape(-1, 2)
+    sw, sh = (scale, scale) if np.isscalar(scale) else scale
+    prev = np.ascontiguousarray(previous, np.int32)
+    assert prev.shape == (4,)
+    out = np.zeros(4, np.int32)
+    rc = lib().rmcv_get_roi(ptr(pts) if len(pts) else None, len(pts), C.c_float(sw), C.c_float(sh), int(frame_size[0]), int(frame_size[1]), ptr(prev), ptr(out))
+    if rc:
+        raise RmcvError(rc, "rmcv_get_roi")
+    return tuple(int(v) for v in out)
+
+
+def window_origin(rect, win_w, win_h):
+    """the requested origin (x, y) of a win_w x win_h window centred on rect = (x, y, w, h) (rmcv_window_origin: integers; the library
+    clamps it into the frame and snaps x down to a multiple of 16 when the window is used)"""
+    r = np.ascontiguousarray(rect, np.int32)
+    assert r.shape == (4,)
+    out = np.zeros(2, np.int32)
+    rc = lib().rmcv_window_origin(ptr(r), int(win_w), int(win_h), ptr(out))
+    if rc:
+        raise RmcvError(rc, "rmcv_window_origin: win_w, win_h >= 1")
+    return int(out[0]), int(out[1])
+
+
+def armours_to_frame(armours, x, y):
+    """a copy of window-coordinate armours moved to frame coordinates: icon, vertices, bbox.x / .y + (float32(x), float32(y)), one f32 add each
+    (rmcv_armours_to_frame; a convenience -- not what whole-frame detection would have found)"""
+    a = np.ascontiguousarray(armours, ARMOUR).copy()
+    rc = lib().rmcv_armours_to_frame(ptr(a) if len(a) else None, len(a), int(x), int(y))
+    if rc:
+        raise RmcvError(rc, "rmcv_armours_to_frame")
+    return a
 
 
 def default_pnp_config():

@@ -378,7 +378,7 @@ class Context:
             assert ch == 3
             rowb = 3 * w
         self._chk(lib().rmcv_batch_upload(self._h, ptr(frames), n, w, h, rowb, C.c_int64(rowb * h)))
-        self.shape = (n, h, w)
+        self.shape, self._windowed = (n, h, w), False
 
     def bind_device_frames(self, data_ptr, n, h, w, stride=None, frame_pitch=None, keepalive=None):
         """borrow frames already in HBM (e.g. torch_tensor.data_ptr()); strides are bytes, the default is 3 w, under a Bayer input
@@ -387,7 +387,47 @@ class Context:
         frame_pitch = frame_pitch or stride * h
         self._frames_ref = keepalive
         self._chk(lib().rmcv_batch_set_device_frames(self._h, C.c_void_p(data_ptr), n, w, h, stride, C.c_int64(frame_pitch)))
-        self.shape = (n, h, w)
+        self.shape, self._windowed = (n, h, w), False
+
+    # ---------------------------------------------------------------- windowed detection (rm::utils::GetROI -> extract_color(image(roi)))
+    def set_windows(self, origins, win_w, win_h, keepalive=None):
+        """read every frame bound through a win_w x win_h window: origins = (n, 2) integers (x, y) on the host (a numpy array or
+        anything that converts to one), or an int = a device pointer to n rmcv_point (borrowed; read again by every run).  Any values:
+        the library clamps them into the frame and snaps x down to a multiple of 16 (windows()).  binary / contours / blobs / armours
+        are then those of the crops, in window coordinates.  win_w = 0: whole frames again."""
+        n = self.shape[0]
+        if not getattr(self, "_windowed", False):
+            self._frame_shape = self.shape           # (n, h, w) of the frames as bound
+        if win_w == 0:
+            self._chk(lib().rmcv_batch_set_windows(self._h, None, 0, 0))
+            self.shape, self._windowed = self._frame_shape, False
+            return
+        if isinstance(origins, (int, np.integer)):
+            self._win_ref = keepalive
+            self._chk(lib().rmcv_batch_set_device_windows(self._h, C.c_void_p(int(origins)), int(win_w), int(win_h)))
+        else:
+            o = np.ascontiguousarray(origins, np.int32).reshape(-1, 2)
+            assert len(o) == n, "one origin per frame bound"
+            self._chk(lib().rmcv_batch_set_windows(self._h, ptr(o), int(win_w), int(win_h)))
+        self.shape, self._windowed = (n, int(win_h), int(win_w)), True
+
+    def windows(self):
+        """(effective origins int32 (n, 2) as (x, y), win_w, win_h) of the frames bound; zeros and (0, 0) without windows"""
+        n = self.shape[0]
+        eff = np.zeros((n, 2), np.int32)
+        ww, wh = C.c_int32(0), C.c_int32(0)
+        self._chk(lib().rmcv_batch_get_windows(self._h, ptr(eff), n, C.byref(ww), C.byref(wh)))
+        return eff, ww.value, wh.value
+
+    def device_windows(self):
+        """(device pointer of the effective-origin table or None, win_w, win_h)"""
+        d, ww, wh = C.c_void_p(), C.c_int32(0), C.c_int32(0)
+        self._chk(lib().rmcv_batch_device_windows(self._h, C.byref(d), C.byref(ww), C.byref(wh)))
+        return d.value, ww.value, wh.value
+
+    get_roi = staticmethod(abi.get_roi)
+    window_origin = staticmethod(abi.window_origin)
+    armours_to_frame = staticmethod(abi.armours_to_frame)
 
     def run(self, params=None, stages=STAGE_ALL, stream=None):
         self._params = params or default_params()

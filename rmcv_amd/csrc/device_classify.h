@@ -96,9 +96,10 @@ ClassifyArgs classify_args(const Geom& g, const Bufs& b); // k_classify.hip
 // BAYER: the frames are mosaics of pattern `pattern` in the layout `lay` (the stand-alone k_classify only: the sparse kernel classifies BGR frames)
 template <int BAYER = 0>
 __device__ inline void classify_frame(int f, int lane, int wave, int nwaves, int n, const ClassifyArgs& C, rmcv_armour* __restrict__ armours,
-                                      int max_armours, float* feat, double* sums, int pattern = 0, int lay = 0, const uint8_t* __restrict__ luts = nullptr)
+                                      int max_armours, float* feat, double* sums, int pattern = 0, int lay = 0, const uint8_t* __restrict__ luts = nullptr,
+                                      int64_t origin = 0 /* frame_origin_offset of the frame's window (C.w, C.h are then the window's); 0: the whole frame */)
 {
-    const uint8_t* frame = C.frames + (int64_t)f * C.frame_pitch;
+    const uint8_t* frame = C.frames + (int64_t)f * C.frame_pitch + origin;
     const int w = C.w, h = C.h, stride = C.stride, n_class = C.n_class;
     const float* __restrict__ weights = C.weights;
     const double* __restrict__ rho = C.rho;

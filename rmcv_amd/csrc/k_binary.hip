@@ -55,7 +55,7 @@ bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound, int pixel_ws)
     const bool linear = one_launch && !g.pixel_rowquad && g.stride == 3 * g.w;
     const int n_cu = g.n_cu > 0 ? g.n_cu : 256, n_blocks = g.n_frames * strips;
     const size_t planes_ws = ((size_t)2 * (SR + 4) + SR) * g.ww * sizeof(uint64_t);
-    return g.input_format == RMCV_INPUT_BGR && !g.enhance && pixel_ws && linear && lower_bound > 0 && n_blocks * 2 > n_cu && planes_ws <= 60 * 1024 && n_blocks >= n_cu;
+    return g.input_format == RMCV_INPUT_BGR && !g.enhance && !g.win && pixel_ws && linear && lower_bound > 0 && n_blocks * 2 > n_cu && planes_ws <= 60 * 1024 && n_blocks >= n_cu;
 }
 
 hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s)
@@ -64,6 +64,8 @@ hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound
     if (g.input_format != RMCV_INPUT_BGR) return launch_binary_bayer(g, b, camp, lower_bound, morph, image, s);
     // through the frames' gamma tables (RMCV_OPT_ENHANCE): the same kernel with a lookup in its compare (k_binary_enh.hip)
     if (g.enhance) return launch_binary_enh(g, b, camp, lower_bound, morph, image, plan, s);
+    // a window of every frame (rmcv_batch_set_windows): the same kernel reading from the frames' effective origins (k_binary_win.hip)
+    if (g.win) return launch_binary_win(g, b, camp, lower_bound, morph, image, plan, s);
     // imgproc.cpp:56-65: GUIDELIGHT G-R; BLUE B-R; everything else (RED, NEUTRAL) R-B.  BGR byte order.
     if (camp == RMCV_CAMP_GUIDELIGHT) return launch_binary_t<1, 2>(g, b, lower_bound, morph, image, plan, s);
     if (camp == RMCV_CAMP_BLUE) return launch_binary_t<0, 2>(g, b, lower_bound, morph, image, plan, s);

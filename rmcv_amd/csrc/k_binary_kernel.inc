@@ -1,6 +1,10 @@
 // k_binary_kernel.inc -- the pixel kernel's body, compiled once per translation unit that includes it (k_binary.hip: K1_ENH 0, the kernel
 // k_binary; k_binary_enh.hip: K1_ENH 1, k_binary_enh, the compare through the frame's threshold table).  The includer defines K1_KERNEL,
-// K1_ENH, K1_THRESH(d) and K1_PASS(a, b) and has included k_binary_device.h.
+// K1_ENH, K1_THRESH(d) and K1_PASS(a, b) and has included k_binary_device.h.  k_binary_win.hip: K1_WIN 1, k_binary_win, every frame read at
+// its window's effective origin (with K1_WIN 0 -- the default -- this file preprocesses to what it was before the switch existed).
+#ifndef K1_WIN
+#define K1_WIN 0
+#endif
 
 // Register budget: 6 waves per SIMD = at most 80 VGPRs.  Two launches of consecutive batches overlap (2 workgroups per CU each = 4
 // waves per SIMD) next to one wave of the 4-wavefront sparse kernel (168 VGPRs): 4 x 80 + 168 <= 512.  At 88 the sparse kernel
@@ -17,6 +21,10 @@ __global__ __launch_bounds__(256, RMCV_K1_MINBLOCKS) void K1_KERNEL(const uint8_
                                                  int halo_nt /* RMCV_OPT_PIXEL_HALO_NT */
 #if K1_ENH
                                                  , const uint16_t* __restrict__ mtab /* [frame][256] Bufs::enh_m */
+#endif
+#if K1_WIN
+                                                 , const rmcv_point* __restrict__ win_eff /* [frame] Bufs::win_eff; w, h are the window's */
+                                                 , int in_extent /* bytes from `frames` to the end of the launch's last WHOLE frame */
 #endif
                                                  )
 {
@@ -90,7 +98,13 @@ __global__ __launch_bounds__(256, RMCV_K1_MINBLOCKS) void K1_KERNEL(const uint8_
     const int y0 = strip * SR + piece * (SR / 4);
     if (y0 >= h) continue; // a piece of the frame's last strip that lies below the image (h % SR <= 24): nothing to load or store
     const int srh = sr + 2 * halo;
+#if K1_WIN
+    // the window's first byte inside its frame (wave-uniform; x_eff is a multiple of 16 pixels, so 16-byte alignment survives)
+    const uint32_t win_off = (uint32_t)__builtin_amdgcn_readfirstlane((int)frame_origin_offset(win_eff, f, stride));
+    const uint8_t* frame = frames + (int64_t)f * frame_pitch + win_off;
+#else
     const uint8_t* frame = frames + (int64_t)f * frame_pitch;
+#endif
 #if K1_ENH
     // (every wave has left the previous strip's phase 1 -- two barriers ago -- so the table may change under nobody)
     if (f != f_m) { s_m[tid] = mtab[(int64_t)f * 256 + tid]; f_m = f; }
@@ -103,9 +117,15 @@ __global__ __launch_bounds__(256, RMCV_K1_MINBLOCKS) void K1_KERNEL(const uint8_
         // parallelism per wave); every 16-bit mask goes straight to its place in the LDS plane (ds_write_b16)
         constexpr int U = RMCV_K1_UNROLL;
         const int items = srh * wq;
+#if K1_WIN
+        // the extent covers whole frames: a ragged block's lanes beyond the window's row read the frame's pixels to its right (masked below)
+        const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(const_cast<uint8_t*>(frames), 0, in_extent, RSRC3);
+        const uint32_t fbase = (uint32_t)((int64_t)f * frame_pitch) + win_off;
+#else
         const __amdgpu_buffer_rsrc_t r_in = __builtin_amdgcn_make_buffer_rsrc(
             const_cast<uint8_t*>(frames), 0, (int)((int64_t)(n_frames - 1) * frame_pitch + (int64_t)(h - 1) * stride + 3 * w), RSRC3);
         const uint32_t fbase = (uint32_t)((int64_t)f * frame_pitch);
+#endif
         // Wave-coalesced loads: an item is a 256-pixel block of FOUR rows; lane i loads pixels 4i..4i+3 of each row with one
         // dwordx3, so the wave reads 768 contiguous bytes = six whole cache lines per instruction and every line is touched by
         // exactly one instruction -- which is what lets the loads carry the non-temporal hint (round 2 measured it: per-lane

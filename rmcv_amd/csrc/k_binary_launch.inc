@@ -1,6 +1,10 @@
 // k_binary_launch.inc -- the launcher of the kernel k_binary_kernel.inc has just defined: geometry -> loader form, chunks of frames below
 // 4 GiB, the persistent grid.  The includer defines K1_LAUNCH_T and K1_EXTRA (trailing kernel arguments); with K1_ENH 0 it has also
-// included k_binary_ws.inc and defined g_ws_launches.
+// included k_binary_ws.inc and defined g_ws_launches.  K1_WIN (k_binary_win.hip): window rows are not contiguous -- never the linear
+// loader, never k_binary_ws; FAST 2 is not even instantiated.
+#ifndef K1_WIN
+#define K1_WIN 0
+#endif
 template <int CA, int CB>
 static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int morph, bool image, const RunPlan& plan,
                                   hipStream_t s)
@@ -19,7 +23,11 @@ static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int
     const int chunk = aligned ? (int)std::min<int64_t>(g.n_frames, std::max<int64_t>(1, (lim - 1) / per_frame)) : g.n_frames;
     const bool fast = aligned && (int64_t)chunk * per_frame < lim;
     // rows contiguous in memory: the linear loader (Geom::pixel_rowquad, hidden option 1001: the row-quad loader everywhere -- for A/B runs)
+#if K1_WIN
+    const bool linear = false;
+#else
     const bool linear = fast && !g.pixel_rowquad && g.stride == 3 * g.w;
+#endif
     // persistent grid: RMCV_OPT_PIXEL_GROUPS workgroups per CU: alone the kernel is equally fast with 2 and 3 and slower with 4 and
     // more; 2 leaves room on every CU for the kernels of the other batches in flight
     const int bpc = plan.pixel_groups;
@@ -47,12 +55,16 @@ static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int
         const int mode = fast ? (linear ? 2 : 1) : 0;
         const int inst = mode;
         if (planes > 60 * 1024 && planes > lds_set[g.device][inst]) {
+#if K1_WIN
+            const void* fn = mode == 1 ? reinterpret_cast<const void*>(K1_KERNEL<CA, CB, 1>) : reinterpret_cast<const void*>(K1_KERNEL<CA, CB, 0>);
+#else
             const void* fn = mode == 2 ? reinterpret_cast<const void*>(K1_KERNEL<CA, CB, 2>) : mode == 1 ? reinterpret_cast<const void*>(K1_KERNEL<CA, CB, 1>) : reinterpret_cast<const void*>(K1_KERNEL<CA, CB, 0>);
+#endif
             const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)planes);
             if (ea != hipSuccess) return ea;
             lds_set[g.device][inst] = planes;
         }
-#if !K1_ENH // (a batch with enhancement takes the k_binary shape whatever the plan says)
+#if !K1_ENH && !K1_WIN // (a batch with enhancement or windows takes the k_binary shape whatever the plan says)
         // whole batches with contiguous rows, when the caller asks for it (RMCV_OPT_PIXEL_SHAPE; a pipeline does for its calm batches):
         // the wave-specialised kernel, ONE 1024-thread workgroup per CU -- 8 loader wavefronts with 2 items (8 loads) in flight each, 8 storers
         constexpr int WS_NL = 8, WS_NS = 8, WS_RING = 2, WS_AUX = 2 /* nt */;
@@ -78,7 +90,11 @@ static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int
     launch(K1_KERNEL<CA, CB, F>, dim3(grid), dim3(256), planes, s, frames, g.frame_pitch, g.stride, nf, g.w, g.h, g.ww, lb, all_pass, \
            morph, binary, bits, g.prow, g.plane_pitch, strips, n_blocks, rowmask, b.strip_ctr, taper_head, taper_tail,               \
            g.pixel_halo_nt K1_EXTRA)
+#if K1_WIN
+        const hipError_t e = mode == 1 ? RMCV_K1_LAUNCH(1) : RMCV_K1_LAUNCH(0);
+#else
         const hipError_t e = mode == 2 ? RMCV_K1_LAUNCH(2) : mode == 1 ? RMCV_K1_LAUNCH(1) : RMCV_K1_LAUNCH(0);
+#endif
 #undef RMCV_K1_LAUNCH
         if (e != hipSuccess) return e;
     }

@@ -14,13 +14,14 @@
 
 namespace rmcv {
 
+// win_eff (nullable): the frames' window origins (Geom::win) -- the icon is cut from the window, clamped to ITS size, as affine_correction on image(roi)
 __global__ __launch_bounds__(256) void k_classify(ClassifyArgs C, rmcv_armour* __restrict__ armours, const int32_t* __restrict__ n_armours,
-                                                 int max_armours)
+                                                 int max_armours, const rmcv_point* __restrict__ win_eff)
 {
     __shared__ float s_feat[4][NFEAT];
     __shared__ double s_sum[4][32];
     const int f = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    classify_frame(f, lane, wave, 4, n_armours[f], C, armours, max_armours, s_feat[wave], s_sum[wave]);
+    classify_frame(f, lane, wave, 4, n_armours[f], C, armours, max_armours, s_feat[wave], s_sum[wave], 0, 0, nullptr, frame_origin_offset(win_eff, f, C.stride));
 }
 
 // the same for mosaics (RMCV_OPT_INPUT_FORMAT): the icon's pixels are D(m) of the frame (device_bayer.h) -- D(T(r)) of a frame in the
@@ -68,7 +69,7 @@ hipError_t launch_classify(const Geom& g, const Bufs& b, const Limits& lim, hipS
         return launch(k_classify_bayer, dim3(g.n_frames), dim3(256), 0, s, classify_args(g, b), b.armours, b.n_armours, lim.max_armours, g.input_format,
                       raw_layout(8 * g.sample_bytes, g.valid_bit, g.orient));
     if (g.enhance) return launch(k_classify_enh, dim3(g.n_frames), dim3(256), 0, s, classify_args(g, b), b.armours, b.n_armours, lim.max_armours, b.enh_lut);
-    return launch(k_classify, dim3(g.n_frames), dim3(256), 0, s, classify_args(g, b), b.armours, b.n_armours, lim.max_armours);
+    return launch(k_classify, dim3(g.n_frames), dim3(256), 0, s, classify_args(g, b), b.armours, b.n_armours, lim.max_armours, g.win ? b.win_eff : nullptr);
 }
 
 } // namespace rmcv

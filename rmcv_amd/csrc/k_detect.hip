@@ -50,6 +50,7 @@ struct MatchArgs {
     const uint8_t* frames; // may be null: no camp vote (the blob gets CAMP_NEUTRAL)
     int64_t frame_pitch;
     int stride;
+    const rmcv_point* win_eff; // nullable: the frames' window origins (Geom::win) -- the vote reads the window, as FindLightBlobs on image(roi) does
 };
 
 static constexpr int MATCH_CHUNKS = 16;
@@ -133,7 +134,7 @@ __global__ __launch_bounds__(64) void k_match(const rmcv_point* __restrict__ poi
                     if (ok) {
                         int camp = RMCV_CAMP_NEUTRAL;
                         if (A.frames) // :43-51
-                            camp = camp_from_mean_wave(A.frames + (int64_t)f * A.frame_pitch, A.stride, minx, miny, W, Hh, lane);
+                            camp = camp_from_mean_wave(A.frames + (int64_t)f * A.frame_pitch + frame_origin_offset(A.win_eff, f, A.stride), A.stride, minx, miny, W, Hh, lane);
                         word = 1 | ((camp + 2) << 4);
                     }
                 }
@@ -326,6 +327,7 @@ hipError_t launch_match(const Geom& g, const Bufs& b, const Limits& lim, const r
     A.frames = with_frames ? b.frames : nullptr;
     A.frame_pitch = g.frame_pitch;
     A.stride = g.stride;
+    A.win_eff = g.win ? b.win_eff : nullptr;
     const int full_w = lim.max_width < HULL_MAX_DIM ? lim.max_width : HULL_MAX_DIM;
     const bool hull = mode == 1 || !lp.fit_ellipse;
     // pass 0 (every contour): small hull tables, ~10 KB of LDS per wavefront; pass 1 repeats the contours pass 0 marked

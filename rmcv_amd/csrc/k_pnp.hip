@@ -177,17 +177,17 @@ __device__ inline float reproj_error(const double obj[4][2], const double img[4]
     return __builtin_sqrtf(err / (2.0f * 4));
 }
 
-// mobility.cpp:166-190 with the default ROI; returns 1 for degenerate points (rvec = tvec = 0)
-__device__ inline int solve_pnp(const float vertices[4][2], const rmcv_pnp_config& cfg, double rvec[3], double tvec[3])
+// mobility.cpp:166-190; (ox, oy) = (float)ROI.x, (float)ROI.y of :172 (the default ROI: 0, 0); returns 1 for degenerate points (rvec = tvec = 0)
+__device__ inline int solve_pnp(const float vertices[4][2], const rmcv_pnp_config& cfg, double rvec[3], double tvec[3], float ox = 0.0f, float oy = 0.0f)
 {
     const float hw = cfg.square_w / 2.0f, hhgt = cfg.square_h / 2.0f;
     const double obj[4][2] = {{-hw, hhgt}, {hw, hhgt}, {hw, -hhgt}, {-hw, -hhgt}}; // :175-180
     double img[4][2];
 #pragma unroll
-    for (int i = 0; i < 4; i++) { // :182-185: image points 1, 2, 3, 0 (+ the zero ROI offset)
+    for (int i = 0; i < 4; i++) { // :182-185: image points 1, 2, 3, 0 + the ROI offset, added in float
         const int o = (i + 1) & 3;
         float nx, ny;
-        undistort_point(vertices[o][0] + 0.0f, vertices[o][1] + 0.0f, cfg.camera_matrix, cfg.dist, &nx, &ny);
+        undistort_point(vertices[o][0] + ox, vertices[o][1] + oy, cfg.camera_matrix, cfg.dist, &nx, &ny);
         img[i][0] = nx;
         img[i][1] = ny;
     }
@@ -225,20 +225,22 @@ __device__ inline int solve_pnp(const float vertices[4][2], const rmcv_pnp_confi
 // one wavefront per frame, one lane per armour; poses[frame][armour] = rvec[3] | tvec[3] | position[3]
 __global__ __launch_bounds__(64) void k_pnp(const rmcv_armour* __restrict__ armours, const int32_t* __restrict__ n_armours,
                                            int max_armours, const rmcv_pnp_config* __restrict__ cfg_p,
-                                           const double* __restrict__ base2gripper, double* __restrict__ poses)
+                                           const double* __restrict__ base2gripper, double* __restrict__ poses,
+                                           const rmcv_point* __restrict__ win_eff /* nullable: the frames' window origins = the ROI of solve_PnP */)
 {
     const int f = blockIdx.x;
     const rmcv_pnp_config cfg = *cfg_p;
     int n = n_armours[f];
     n = n > max_armours ? max_armours : n;
     const double* B = base2gripper + (int64_t)f * 16;
+    const float ox = win_eff ? (float)win_eff[f].x : 0.0f, oy = win_eff ? (float)win_eff[f].y : 0.0f; // mobility.cpp:172
     for (int i = threadIdx.x; i < n; i += 64) {
         const rmcv_armour* a = armours + (int64_t)f * max_armours + i;
         float v[4][2];
 #pragma unroll
         for (int k = 0; k < 4; k++) { v[k][0] = a->vertices[k][0]; v[k][1] = a->vertices[k][1]; }
         double r[3], t[3];
-        solve_pnp(v, cfg, r, t);
+        solve_pnp(v, cfg, r, t, ox, oy);
         // main.cpp:186-192: world = h_base2gripper * (h_gripper2camera * [tvec; 1])
         const double cam[4] = {t[0], t[1], t[2], 1.0};
         double mid[4], out[3];
@@ -257,7 +259,7 @@ __global__ __launch_bounds__(64) void k_pnp(const rmcv_armour* __restrict__ armo
 hipError_t launch_pnp(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s)
 {
     return launch(k_pnp, dim3(g.n_frames), dim3(64), 0, s, b.armours, b.n_armours, lim.max_armours, b.pnp_cfg, b.base2gripper,
-                       b.poses);
+                       b.poses, g.win ? b.win_eff : nullptr);
 }
 
 } // namespace rmcv

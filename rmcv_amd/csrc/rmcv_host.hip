@@ -108,6 +108,7 @@ struct rmcv_ctx {
     double marks[9] = {};         // rmcv_ctx_frame_timing: host clock at the steps of the last rmcv_extract_color (microseconds)
     uint64_t blocking_calls = 0;  // allocations, host-side synchronisations and blocking copies made while binding a geometry (ctx_blocking_calls)
     int32_t* order_scratch = nullptr; // [2 * max_frames] k_frame_order's work lists for batches beyond its LDS tables
+    rmcv_point* win_own = nullptr;    // [max_frames] the context's copy of host origins (rmcv_batch_set_windows); Bufs::win_req points here or at the caller's
     char err[256] = {0};
     std::vector<void*> allocs;
     struct Guarded { uint8_t* base; size_t bytes; const char* name; size_t rear = 0; };
@@ -370,6 +371,8 @@ int rmcv_ctx_create(int device, const rmcv_limits* limits, rmcv_ctx** out)
     if (e == hipSuccess) e = dalloc(c, &b.enh_gamma, F);
     if (e == hipSuccess) e = dalloc(c, &b.enh_lut, 256 * F);
     if (e == hipSuccess) e = dalloc(c, &b.enh_m, 256 * F);
+    if (e == hipSuccess) e = dalloc(c, &b.win_eff, F);
+    if (e == hipSuccess) e = dalloc(c, &c->win_own, F);
     if (e == hipSuccess) {
         hipMemset(b.strip_ctr, 0, 9 * CTR_STRIDE * sizeof(int));
         hipMemset(b.n_contours, 0, F * 4);
@@ -378,6 +381,8 @@ int rmcv_ctx_create(int device, const rmcv_limits* limits, rmcv_ctx** out)
         hipMemset(b.n_neg, 0, F * 4);
         hipMemset(b.n_armours, 0, F * 4);
         e = hipMemset(b.status, 0, F * 4);
+        if (e == hipSuccess) e = hipMemset(b.win_eff, 0, F * sizeof(rmcv_point));
+        if (e == hipSuccess) e = hipMemset(c->win_own, 0, F * sizeof(rmcv_point));
     }
     if (e == hipSuccess) { // rmcv_batch_get_gammas before the first run with the option: every frame reads 1 (the identity table)
         const std::vector<float> ones(F, 1.0f);
@@ -408,6 +413,7 @@ RunPlan ctx_plan(const rmcv_ctx* c) { return {c->pixel_shape, c->pixel_groups, c
 int ctx_input_format(const rmcv_ctx* c) { return c->input_format; }
 int ctx_enhance(const rmcv_ctx* c) { return c->enhance; }
 int ctx_bound_enhance(const rmcv_ctx* c) { return c->geom.enhance; }
+int ctx_bound_windows(const rmcv_ctx* c) { return c->geom.win; }
 // bytes of one sample of what the context's options describe: 3 per BGR pixel, 1 or 2 per Bayer sample
 static int ctx_pixel_bytes(const rmcv_ctx* c) { return c->input_format ? c->input_sample_bits / 8 : 3; }
 int ctx_compact(rmcv_ctx* c, void* d_armours_out, int cap, void* d_frame_offs, void* d_status_or, hipStream_t s, void* hd_record, int host_head)
@@ -633,7 +639,23 @@ static int check_sample_ptr(rmcv_ctx* c, const void* p)
     return RMCV_OK;
 }
 
-static int set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t as = nullptr)
+// what rmcv_batch_set_windows refuses, checked before anything of the context moves (fw x fh: the frames; fmt / enh: what they are read as)
+static int check_windows(rmcv_ctx* c, int fw, int fh, int fmt, int enh, int win_w, int win_h)
+{
+    if (fmt != RMCV_INPUT_BGR) return fail(c, RMCV_ERR_BAD_ARG, "windows with a Bayer input format (RMCV_OPT_INPUT_FORMAT): crop-then-demosaic has other border semantics; not supported");
+    if (enh) return fail(c, RMCV_ERR_BAD_ARG, "windows with RMCV_OPT_ENHANCE: the mean of a crop is not the frame's; not supported");
+    if (win_w < 1 || win_h < 1) return fail(c, RMCV_ERR_BAD_ARG, "window size out of range: win_w and win_h must be at least 1");
+    if (win_w > fw || win_h > fh) return fail(c, RMCV_ERR_BAD_ARG, "window size out of range: larger than the frames");
+    if (win_w > c->lim.max_width || win_h > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, "window size out of range: larger than the context's limits");
+    return RMCV_OK;
+}
+
+// Make w x h the extent everything behind the frame loads sees (the frames' own, or their windows').  When it changes the padded planes
+// are zeroed and the frame order is recomputed, as set_geom's comment says.
+static int set_extent(rmcv_ctx* c, int w, int h, hipStream_t as);
+
+// win_w > 0: the frames are read through win_w x win_h windows (checked by the caller: check_windows)
+static int set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t as = nullptr, int win_w = 0, int win_h = 0)
 {
     if (n_frames < 1 || n_frames > c->lim.max_frames) return fail(c, RMCV_ERR_BAD_ARG, "n_frames out of range");
     if (w < 1 || h < 1 || w > c->lim.max_width || h > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, "frame size out of range");
@@ -643,6 +665,7 @@ static int set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t
     if (stride < bpp * w || frame_pitch < (int64_t)stride * (h - 1) + bpp * w) return fail(c, RMCV_ERR_BAD_ARG, "bad stride/pitch");
     if (bpp == 2 && ((stride & 1) || (frame_pitch & 1))) return fail(c, RMCV_ERR_BAD_ARG, "16-bit samples (RMCV_OPT_INPUT_SAMPLE_BITS): stride and frame_pitch are bytes and must be even");
     if (c->enhance && c->input_format) return fail(c, RMCV_ERR_BAD_ARG, "RMCV_OPT_ENHANCE with a Bayer input format: the mean of a demosaiced frame is not a function of the mosaic's sums");
+    if (win_w > 0) { const int rcw = check_windows(c, w, h, c->input_format, c->enhance, win_w, win_h); if (rcw) return rcw; }
     { const int rcm = ensure_mid(c, n_frames); if (rcm) return rcm; }
     Geom& g = c->geom;
     g.enhance = c->enhance;
@@ -653,10 +676,20 @@ static int set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t
     g.valid_bit = g.sample_bytes == 2 ? c->input_valid_bit : 0;
     g.orient = c->input_format ? c->input_orient : 0;
     g.n_frames = n_frames;
-    g.w = w;
-    g.h = h;
     g.stride = stride;
     g.frame_pitch = frame_pitch;
+    g.frame_w = w;
+    g.frame_h = h;
+    g.win = win_w > 0;
+    return set_extent(c, g.win ? win_w : w, g.win ? win_h : h, as);
+}
+
+static int set_extent(rmcv_ctx* c, int w, int h, hipStream_t as)
+{
+    Geom& g = c->geom;
+    const int n_frames = g.n_frames;
+    g.w = w;
+    g.h = h;
     g.ww = (w + 63) / 64;
     g.prow = g.ww + 2;
     g.plane_pitch = (int64_t)(h + 2) * g.prow;
@@ -735,13 +768,15 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
     if (stages & RMCV_STAGE_BINARY) {
         // RMCV_OPT_ENHANCE: every frame's sums, gamma and tables first, at RUN time (borrowed frames may have changed since they were bound)
         if (g.enhance) HIPCHK(c, launch_enhance_tables(g, b, p->lower_bound, s), "k_frame_sums + k_enhance_table");
+        // windows: the effective origins first, at RUN time too (the requests may be a tracker's, rewritten on the device since they were set)
+        if (g.win) HIPCHK(c, launch_window_origins(g, b, s), "k_window_origins");
         HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, !(stages & RMCV_STAGE_NO_IMAGE), plan, s),
-               g.input_format ? "k_binary_bayer" : (g.enhance ? "k_binary_enh" : "k_binary"));
+               g.input_format ? "k_binary_bayer" : (g.enhance ? "k_binary_enh" : (g.win ? "k_binary_win" : "k_binary")));
     }
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
     // the icon classifier rides in the per-frame kernel when the armours come from it (BASELINE config 5: no launch of its own)
     // (not for mosaics: the sparse kernel's classifier reads BGR; k_classify has the Bayer accessor -- and the one through a frame's gamma table)
-    const bool identity_fused = one_sparse && (stages & RMCV_STAGE_ARMOURS) && (stages & RMCV_STAGE_IDENTITY) && g.input_format == RMCV_INPUT_BGR && !g.enhance;
+    const bool identity_fused = one_sparse && (stages & RMCV_STAGE_ARMOURS) && (stages & RMCV_STAGE_IDENTITY) && g.input_format == RMCV_INPUT_BGR && !g.enhance && !g.win; // (windows: k_classify takes the origins)
     if (one_sparse) HIPCHK(c, launch_sparse(g, b, c->lim, *p, (stages & RMCV_STAGE_ARMOURS) != 0, identity_fused, plan, s, lean), "k_contours (fused)");
     else if (stages & RMCV_STAGE_CONTOURS) HIPCHK(c, launch_contours(g, b, c->lim, s), "k_contours");
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
@@ -837,15 +872,18 @@ int rmcv_batch_set_device_frames(rmcv_ctx* c, const void* d_frames, int n_frames
 namespace rmcv {
 // rmcv_batch_set_device_frames for a pipeline: nothing blocks -- a change of geometry is enqueued on `s`, which the caller has made
 // wait for the context's last batch
-int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t s)
+int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t s,
+                    const void* d_origins, int win_w, int win_h)
 {
     if (!c || !d_frames || !s) return RMCV_ERR_BAD_ARG;
     resident_none(c);
     int rc = check_sample_ptr(c, d_frames);
     if (rc) return rc;
-    rc = set_geom(c, n_frames, w, h, stride, frame_pitch, s);
+    if (d_origins && win_w <= 0) return fail(c, RMCV_ERR_BAD_ARG, "window size out of range: win_w and win_h must be at least 1");
+    rc = set_geom(c, n_frames, w, h, stride, frame_pitch, s, d_origins ? win_w : 0, win_h);
     if (rc) return rc;
     c->bufs.frames = (const uint8_t*)d_frames;
+    c->bufs.win_req = (const rmcv_point*)d_origins; // (the run computes the effective origins in front of its pixel pass)
     return RMCV_OK;
 }
 // what binding a batch would allocate, now (a pipeline does this for every context of its ring when it is created)
@@ -1856,6 +1894,7 @@ int rmcv_locate_armours(rmcv_ctx* c, const rmcv_armour* armours, int n, const do
     HIPCHK(c, hipMemcpy(c->bufs.base2gripper, base2gripper ? base2gripper : eye, sizeof(eye), hipMemcpyHostToDevice), "H2D base2gripper");
     Geom g1 = c->geom;
     g1.n_frames = 1;
+    g1.win = 0; // (the caller's armours, the default ROI: whatever windows the batch bound to the context has)
     HIPCHK(c, launch_pnp(g1, c->bufs, c->lim, c->stream), "k_pnp");
     WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
     std::vector<double> all((size_t)n * 9);
@@ -2077,6 +2116,136 @@ int rmcv_batch_get_gammas(rmcv_ctx* c, float* gamma_out, int cap)
         return RMCV_OK;
     }
     HIPCHK(c, hipMemcpy(gamma_out, c->bufs.enh_gamma, (size_t)n * sizeof(float), hipMemcpyDeviceToHost), "D2H gammas");
+    return RMCV_OK;
+}
+
+/* ---- windowed detection: the frames bound are read through one window each (rm::utils::GetROI -> extract_color(image(roi))) ---- */
+
+// origins: the host's (copied into the context's own table) or the caller's device memory (borrowed); win_w == 0: back to whole frames
+static int set_windows(rmcv_ctx* c, const rmcv_point* h_origins, const void* d_origins, int win_w, int win_h)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    Geom& g = c->geom;
+    if (g.n_frames <= 0 || !c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, "no frames bound: windows are set after the frames");
+    hipSetDevice(c->device);
+    resident_none(c);
+    if (win_w == 0) { // whole frames again
+        if (!g.win) return RMCV_OK;
+        g.win = 0;
+        c->bufs.win_req = nullptr;
+        return set_extent(c, g.frame_w, g.frame_h, nullptr);
+    }
+    if (!h_origins && !d_origins) return fail(c, RMCV_ERR_BAD_ARG, "null origins");
+    int rc = check_windows(c, g.frame_w, g.frame_h, g.input_format, g.enhance, win_w, win_h);
+    if (rc) return rc;
+    if ((rc = rmcv_batch_sync(c))) return rc; // the tables about to be rewritten may still be read by a batch in flight
+    if (h_origins) HIPCHK(c, hipMemcpy(c->win_own, h_origins, (size_t)g.n_frames * sizeof(rmcv_point), hipMemcpyHostToDevice), "H2D window origins");
+    c->bufs.win_req = h_origins ? c->win_own : (const rmcv_point*)d_origins;
+    g.win = 1;
+    if ((rc = set_extent(c, win_w, win_h, nullptr))) return rc;
+    // the effective origins now (rmcv_batch_get_windows before the first run reads them); every run with the pixel pass computes them again
+    if ((rc = order_begin(c, c->stream))) return rc;
+    HIPCHK(c, launch_window_origins(g, c->bufs, c->stream), "k_window_origins");
+    return order_end(c, c->stream);
+}
+
+int rmcv_batch_set_windows(rmcv_ctx* c, const rmcv_point* origins, int win_w, int win_h)
+{
+    if (c && win_w != 0 && !origins) return fail(c, RMCV_ERR_BAD_ARG, "null origins");
+    return set_windows(c, origins, nullptr, win_w, win_h);
+}
+
+int rmcv_batch_set_device_windows(rmcv_ctx* c, const void* d_origins, int win_w, int win_h)
+{
+    if (c && win_w != 0 && !d_origins) return fail(c, RMCV_ERR_BAD_ARG, "null origins");
+    return set_windows(c, nullptr, d_origins, win_w, win_h);
+}
+
+int rmcv_batch_get_windows(rmcv_ctx* c, rmcv_point* eff_out, int cap, int32_t* win_w, int32_t* win_h)
+{
+    if (!c || cap < 0 || (cap > 0 && !eff_out)) return RMCV_ERR_BAD_ARG;
+    hipSetDevice(c->device);
+    int rc = rmcv_batch_sync(c);
+    if (rc) return rc;
+    const Geom& g = c->geom;
+    if (win_w) *win_w = g.win ? g.w : 0;
+    if (win_h) *win_h = g.win ? g.h : 0;
+    const int n = std::min(cap, g.n_frames);
+    if (n <= 0) return RMCV_OK;
+    if (!g.win) { // whole frames: every origin is (0, 0)
+        memset(eff_out, 0, (size_t)n * sizeof(rmcv_point));
+        return RMCV_OK;
+    }
+    HIPCHK(c, hipMemcpy(eff_out, c->bufs.win_eff, (size_t)n * sizeof(rmcv_point), hipMemcpyDeviceToHost), "D2H window origins");
+    return RMCV_OK;
+}
+
+int rmcv_batch_device_windows(rmcv_ctx* c, void** d_eff, int32_t* win_w, int32_t* win_h)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (d_eff) *d_eff = c->geom.win ? c->bufs.win_eff : nullptr;
+    if (win_w) *win_w = c->geom.win ? c->geom.w : 0;
+    if (win_h) *win_h = c->geom.win ? c->geom.h : 0;
+    return RMCV_OK;
+}
+
+/* rm::utils::GetROI (src/core.cpp:224-263), verbatim: host-side, no context, no device */
+int rmcv_get_roi(const float* points, int n, float scale_w, float scale_h, int frame_w, int frame_h, const int32_t previous[4], int32_t out[4])
+{
+    if (!out || n < 0 || (n > 0 && !points)) return RMCV_ERR_BAD_ARG;
+    int x = 0, y = 0, w = 0, h = 0; // cv::boundingRect of no points: the empty rect
+    if (n > 0) { // :227, SURVEY A.8: min / max in float, then floor
+        float minx = points[0], maxx = points[0], miny = points[1], maxy = points[1];
+        for (int i = 1; i < n; i++) {
+            const float px = points[2 * i], py = points[2 * i + 1];
+            minx = px < minx ? px : minx;
+            maxx = px > maxx ? px : maxx;
+            miny = py < miny ? py : miny;
+            maxy = py > maxy ? py : maxy;
+        }
+        const int ix = (int)floorf(minx), iy = (int)floorf(miny), ax = (int)floorf(maxx), ay = (int)floorf(maxy);
+        x = ix; y = iy; w = ax - ix + 1; h = ay - iy + 1;
+    }
+    if (previous) { x += previous[0]; y += previous[1]; } // :228-229
+    if (scale_w != 1.0f || scale_h != 1.0f) {             // :230
+        const int sw = (int)((double)w * scale_w / 2.0), sh = (int)((double)h * scale_h / 2.0); // :232-233
+        x -= sw;
+        y -= sh;
+        w += sw * 2;
+        h += sw * 2; // :238, as written: the WIDTH's margin
+    }
+    if (x < 0) x = 0;                           // :240-247 (the size is not reduced by what the corner moved)
+    if (y < 0) y = 0;
+    if (x + w >= frame_w) w = frame_w - x - 1;  // :248-255
+    if (y + h >= frame_h) h = frame_h - y - 1;
+    if (w < 0 || h < 0) x = y = w = h = 0;      // :257-260
+    out[0] = x; out[1] = y; out[2] = w; out[3] = h;
+    return RMCV_OK;
+}
+
+int rmcv_window_origin(const int32_t rect[4], int win_w, int win_h, int32_t out_xy[2])
+{
+    if (!rect || !out_xy || win_w < 1 || win_h < 1) return RMCV_ERR_BAD_ARG;
+    // the window centred on the rect: rect centre (x + w / 2, y + h / 2) minus half the window, integer division truncating
+    out_xy[0] = rect[0] + rect[2] / 2 - win_w / 2;
+    out_xy[1] = rect[1] + rect[3] / 2 - win_h / 2;
+    return RMCV_OK;
+}
+
+int rmcv_armours_to_frame(rmcv_armour* armours, int n, int x, int y)
+{
+    if (n < 0 || (n > 0 && !armours)) return RMCV_ERR_BAD_ARG;
+    const float fx = (float)x, fy = (float)y;
+    for (int i = 0; i < n; i++) {
+        for (int k = 0; k < 4; k++) {
+            armours[i].icon[k][0] += fx;
+            armours[i].icon[k][1] += fy;
+            armours[i].vertices[k][0] += fx;
+            armours[i].vertices[k][1] += fy;
+        }
+        armours[i].bbox[0] += fx;
+        armours[i].bbox[1] += fy;
+    }
     return RMCV_OK;
 }
 

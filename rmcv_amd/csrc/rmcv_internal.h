@@ -36,6 +36,10 @@ struct Geom {
     int64_t plane_pitch; // words per frame = (h + 2) * prow
     int enhance;         // RMCV_OPT_ENHANCE of the frames bound: the pixel pass and the classifier read every byte through the frame's gamma table
     float enh_max_gain, enh_min_gain; // rmcv_ctx_set_enhance_gains, recorded with it
+    // windowed detection (rmcv_batch_set_windows): w, h, ww, prow, plane_pitch above are the WINDOW's -- everything behind the pixel pass
+    // sees a batch of win_w x win_h images -- while stride and frame_pitch stay the frames'; the frames' own extent is kept here
+    int win;             // 1: every frame is read at its effective origin (Bufs::win_eff)
+    int frame_w, frame_h; // the frames as bound (== w, h without windows)
 };
 
 // What a run's launches depend on beyond geometry, buffers and params.  The public entry points take it from the context's options
@@ -116,7 +120,27 @@ struct Bufs {
     float* enh_gamma;      // [frame]      rm::AutoEnhance's gamma of the frame
     uint8_t* enh_lut;      // [frame][256] rm::CalcGamma's table of that gamma
     uint16_t* enh_m;       // [frame][256] the pixel kernel's threshold table (enhance_math.h: enh_m_entry) for the run's lower bound
+    // windowed detection (Geom::win): rewritten by every run that includes the pixel pass, in front of it
+    const rmcv_point* win_req; // [frame] the requested origins, any value (the context's own copy of host origins, or the caller's device memory)
+    rmcv_point* win_eff;   // [frame]      the effective origins (window_origin_eff): what every consumer of the frames reads
 };
+
+// The effective origin of a window, the one place it is computed: clamped into the frame, x snapped down to a multiple
+// of 16 pixels (48 bytes: window rows keep the 16-byte alignment the raw-buffer loader wants).  Part of the semantics, always applied.
+__host__ __device__ inline rmcv_point window_origin_eff(rmcv_point req, int frame_w, int frame_h, int win_w, int win_h)
+{
+    const int xm = frame_w - win_w, ym = frame_h - win_h;
+    rmcv_point e;
+    e.x = (req.x < 0 ? 0 : (req.x > xm ? xm : req.x)) & ~15;
+    e.y = req.y < 0 ? 0 : (req.y > ym ? ym : req.y);
+    return e;
+}
+// Byte offset of what frame f's consumers read inside the frame: its window's effective origin; a null table is whole frames (0).
+// Shared by the pixel kernel (k_binary_win), the classifier and the legacy matcher's camp vote; k_pnp adds the same origin as floats.
+__host__ __device__ inline int64_t frame_origin_offset(const rmcv_point* __restrict__ win_eff, int f, int stride)
+{
+    return win_eff ? (int64_t)win_eff[f].y * stride + 3 * (int64_t)win_eff[f].x : 0;
+}
 
 // internal value of a frame's status word BETWEEN the two launches of the sparse stage (never seen by a caller: the second launch
 // rewrites the word of every frame that carries it)
@@ -167,6 +191,10 @@ hipError_t launch_binary_bayer(const Geom& g, const Bufs& b, int camp, int lower
 hipError_t launch_enhance_tables(const Geom& g, const Bufs& b, int lower_bound, hipStream_t s);
 // the pixel stage reading through Bufs::enh_m (Geom::enhance; launch_binary hands such batches to it): k_binary's shape, never k_binary_ws
 hipError_t launch_binary_enh(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s);
+// windowed detection (k_binary_win.hip).  launch_window_origins: Bufs::win_req -> Bufs::win_eff for the frames bound, in front of the pixel pass
+hipError_t launch_window_origins(const Geom& g, const Bufs& b, hipStream_t s);
+// the pixel stage of a windowed batch (Geom::win; launch_binary hands such batches to it): k_binary's shape, row-quad or byte-wise loader
+hipError_t launch_binary_win(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s);
 // dst[i] = lut[src[i]] over n16 16-byte vectors of a staged image (rm::CalcGamma); dst == src allowed
 hipError_t launch_bytemap(const uint8_t* d_src, uint8_t* d_dst, int64_t n16, const uint8_t* d_lut, int n_cu, hipStream_t s);
 // lut[0..255] of `gamma` on the device (the table builder of enhance_math.h)
@@ -225,7 +253,9 @@ RunPlan ctx_plan(const rmcv_ctx* c);
 int ctx_run(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_params* lp, int stages, hipStream_t s, const RunPlan& plan, bool* lean = nullptr);
 // rmcv_batch_set_device_frames without a blocking call: a change of geometry (planes zeroed, frame order recomputed) is ENQUEUED on `s`,
 // which the caller has made wait for the context's last batch
-int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t s);
+// d_origins non-null: a windowed batch (rmcv_batch_set_device_windows in the same step: ONE change of geometry, the window's)
+int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t s,
+                    const void* d_origins = nullptr, int win_w = 0, int win_h = 0);
 // everything binding a full batch would allocate (the mid tier's scratch), now
 int ctx_prepare_ring(rmcv_ctx* c);
 // allocations, host-side synchronisations and blocking copies this context has made while binding geometries
@@ -244,5 +274,7 @@ int ctx_input_format(const rmcv_ctx* c);
 int ctx_enhance(const rmcv_ctx* c);
 // ... and as the frames bound last recorded it (what the runs on them do)
 int ctx_bound_enhance(const rmcv_ctx* c);
+// whether the frames bound last are read through windows
+int ctx_bound_windows(const rmcv_ctx* c);
 
 } // namespace rmcv

@@ -571,8 +571,9 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
     return RMCV_OK;
 }
 
+// d_origins non-null: a windowed batch (rmcv_pipeline_submit_windows) -- every frame read through a win_w x win_h window
 static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, const rmcv_params* p,
-                  const rmcv_legacy_params* lp, int stages, uint64_t* ticket)
+                  const rmcv_legacy_params* lp, int stages, uint64_t* ticket, const void* d_origins = nullptr, int win_w = 0, int win_h = 0)
 {
     if (!pl || !d_frames || !p) return RMCV_ERR_BAD_ARG;
     if (!(stages & RMCV_STAGE_BINARY)) return pfail(pl, RMCV_ERR_BAD_ARG, "a pipelined batch starts at RMCV_STAGE_BINARY");
@@ -581,7 +582,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     const uint64_t t = pl->next_ticket;
     const size_t k = (size_t)(t % (uint64_t)pl->cfg.depth);
     const bool used = pl->slot_ticket[k] != 0;
-    pl->hot = hot_for(pl, n_frames, w, h);
+    pl->hot = hot_for(pl, n_frames, d_origins ? win_w : w, d_origins ? win_h : h);
     if (pl->cfg.host_results == 1) { // the newest record that has come back: did any of its frames go beyond the LDS tables?  how heavy was it?
         for (uint64_t d = 1; d <= (uint64_t)pl->cfg.depth && d <= t; d++) {
             const size_t s_ = (size_t)((t - d) % (uint64_t)pl->cfg.depth);
@@ -603,7 +604,8 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     // 0.426 ms per step with them in it)
     // (so do batches read through their gamma tables, RMCV_OPT_ENHANCE on the slot's context: they take the k_binary shape, and the sums pass in
     // front of it has no use for another batch's planes in the cache)
-    const bool fast = pl->hot && pl->calm && !lp && !(stages & RMCV_STAGE_POSE) && !(stages & RMCV_STAGE_IDENTITY) && !ctx_enhance(pl->ring[k]);
+    // (and windowed batches: the k_binary shape too, and a geometry of their own -- in the rotation they would re-zero the hot contexts' planes)
+    const bool fast = pl->hot && pl->calm && !lp && !(stages & RMCV_STAGE_POSE) && !(stages & RMCV_STAGE_IDENTITY) && !ctx_enhance(pl->ring[k]) && !d_origins;
     const size_t j = fast ? (size_t)(pl->hot_seq % (uint64_t)pl->hot) : k;
     rmcv_ctx* c = pl->ring[j];
     int rc;
@@ -638,7 +640,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
         PCHK(pl, hipStreamWaitEvent(A, early ? pl->ev_free[last] : pl->ev_done[last], 0), "pipeline: wait for the context");
     }
     // ---- bind: a new geometry's work (planes zeroed, frame order) is ENQUEUED on A, nothing blocks
-    rc = ctx_bind_frames(c, d_frames, n_frames, w, h, stride, frame_pitch, A);
+    rc = ctx_bind_frames(c, d_frames, n_frames, w, h, stride, frame_pitch, A, d_origins, win_w, win_h);
     if (rc) return cfail(pl, c, rc);
     const int pixel = stages & (RMCV_STAGE_BINARY | RMCV_STAGE_NO_IMAGE), sparse = stages & ~(RMCV_STAGE_BINARY | RMCV_STAGE_NO_IMAGE);
     ctx_external_order(c, pl->ev_done[k]);
@@ -670,7 +672,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     }
     rc = ctx_run(c, p, nullptr, pixel, A, plan);
     if (rc) return cfail(pl, c, rc);
-    pl->last_what = ctx_input_format(c) ? "the pixel kernel (k_binary_bayer)" : ctx_bound_enhance(c) ? "k_frame_sums, k_enhance_table, the pixel kernel (k_binary_enh)" : "the pixel kernel (k_binary / k_binary_ws)";
+    pl->last_what = ctx_input_format(c) ? "the pixel kernel (k_binary_bayer)" : ctx_bound_enhance(c) ? "k_frame_sums, k_enhance_table, the pixel kernel (k_binary_enh)" : ctx_bound_windows(c) ? "k_window_origins, the pixel kernel (k_binary_win)" : "the pixel kernel (k_binary / k_binary_ws)";
     // ---- accepted: the pipeline's state moves
     pl->was_cold = cold;
     if (fast) { pl->hot_seq++; pl->hot_batches++; }
@@ -700,13 +702,13 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
 
 // submit + its own bookkeeping: the host time of the call, and the blocking calls the ring's contexts counted during it
 static int submit_counted(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, const rmcv_params* p,
-                          const rmcv_legacy_params* lp, int stages, uint64_t* ticket)
+                          const rmcv_legacy_params* lp, int stages, uint64_t* ticket, const void* d_origins = nullptr, int win_w = 0, int win_h = 0)
 {
     if (!pl) return RMCV_ERR_BAD_ARG;
     timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     const uint64_t b0 = ring_blocking(pl);
-    const int rc = submit(pl, d_frames, n_frames, w, h, stride, frame_pitch, p, lp, stages, ticket);
+    const int rc = submit(pl, d_frames, n_frames, w, h, stride, frame_pitch, p, lp, stages, ticket, d_origins, win_w, win_h);
     pl->own_blocking += ring_blocking(pl) - b0;
     clock_gettime(CLOCK_MONOTONIC, &t1);
     const double us = (t1.tv_sec - t0.tv_sec) * 1e6 + (t1.tv_nsec - t0.tv_nsec) * 1e-3;
@@ -732,6 +734,15 @@ int rmcv_pipeline_submit_legacy(rmcv_pipeline* pl, const void* d_frames, int n_f
 {
     if (!lp) return RMCV_ERR_BAD_ARG;
     return submit_counted(pl, d_frames, n_frames, w, h, stride, frame_pitch, p, lp, stages, ticket);
+}
+
+int rmcv_pipeline_submit_windows(rmcv_pipeline* pl, const void* d_frames, int n_frames, int frame_w, int frame_h, int stride, int64_t frame_pitch,
+                                 const void* d_origins, int win_w, int win_h, const rmcv_params* p, int stages, uint64_t* ticket)
+{
+    if (!pl) return RMCV_ERR_BAD_ARG;
+    if (!d_origins) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_windows: null origins (device memory: one rmcv_point per frame)");
+    if (win_w < 1 || win_h < 1) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_windows: window size out of range");
+    return submit_counted(pl, d_frames, n_frames, frame_w, frame_h, stride, frame_pitch, p, nullptr, stages, ticket, d_origins, win_w, win_h);
 }
 
 // slot of a live ticket, or -1

@@ -34,6 +34,7 @@ class Pipeline:
         self._hook = None              # keeps the ctypes callback alive
         self._keep = {}                # slot -> the frames object of the batch in flight there
         self._n = {}                   # slot -> frames of the batch that lives there
+        self._shape = {}               # slot -> (n, h, w) of what that batch's getters return (the window's for a windowed batch)
         self._ticket = C.c_uint64(0)
         self._params = default_params()
         self.contexts = [Context.borrowed(self._lib.rmcv_pipeline_context(self._h, k), lim, device) for k in range(self.depth)]
@@ -77,13 +78,20 @@ class Pipeline:
         return o
 
     # ------------------------------------------------------------------ the three calls
-    def submit(self, data_ptr, n, h, w, params=None, stages=STAGE_ALL, stride=None, frame_pitch=None, keepalive=None, legacy=None):
-        """enqueue one batch of frames resident in HBM (data_ptr: e.g. torch_tensor.data_ptr()); returns the ticket"""
+    def submit(self, data_ptr, n, h, w, params=None, stages=STAGE_ALL, stride=None, frame_pitch=None, keepalive=None, legacy=None, windows=None):
+        """enqueue one batch of frames resident in HBM (data_ptr: e.g. torch_tensor.data_ptr()); returns the ticket.
+        windows = (d_origins_ptr, win_w, win_h): a windowed batch -- d_origins_ptr a device pointer to n (x, y) int32 pairs (e.g. an
+        int32 (n, 2) torch tensor's data_ptr(); keep it alive like the frames), results in window coordinates (Context.set_windows)"""
         if params is not None:
             self._params = params
         stride = stride or (w * self.sample_bits // 8 if self.input_format else 3 * w)
         frame_pitch = frame_pitch or stride * h
-        if legacy is not None:
+        if windows is not None:
+            assert legacy is None, "the legacy matcher has no windowed submit"
+            d_origins, win_w, win_h = windows
+            rc = self._lib.rmcv_pipeline_submit_windows(self._h, data_ptr, n, w, h, stride, frame_pitch, int(d_origins), int(win_w), int(win_h),
+                                                        C.addressof(self._params), int(stages), C.addressof(self._ticket))
+        elif legacy is not None:
             rc = self._lib.rmcv_pipeline_submit_legacy(self._h, data_ptr, n, w, h, stride, frame_pitch, C.addressof(self._params), C.addressof(legacy),
                                                        int(stages), C.addressof(self._ticket))
         else:
@@ -94,7 +102,8 @@ class Pipeline:
         t = self._ticket.value
         self._keep[t % self.depth] = keepalive
         self._n[t % self.depth] = n
-        self.shape = (n, h, w)
+        self.shape = (n, h, w) if windows is None else (n, int(windows[2]), int(windows[1]))
+        self._shape[t % self.depth] = self.shape     # (windowed and whole-frame batches may alternate: context_of hands out the ticket's)
         for c in self.contexts:
             c.shape = self.shape
         return t
@@ -130,6 +139,7 @@ class Pipeline:
             raise RmcvError(abi.ERR_BAD_ARG, "ticket %d: %s" % (ticket, self._lib.rmcv_pipeline_last_error(self._h).decode()))
         for c in self.contexts:
             if c._h.value == h:
+                c.shape = self._shape.get(int(ticket) % self.depth, c.shape)
                 return c
         raise RmcvError(abi.ERR_BAD_ARG, "unknown context")
 
