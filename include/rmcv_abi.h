@@ -526,7 +526,13 @@ int  rmcv_batch_set_base2gripper(rmcv_ctx* ctx, const double* mats, int n_frames
 int  rmcv_batch_get_poses(rmcv_ctx* ctx, double* rvecs, double* tvecs, double* positions, int cap, int32_t* n_total);
 
 /* ---- tracker: the "next" row SURVEY 8f-4 (src/core.cpp:51-162, executable/main.cpp:57-88) --------------------------------
- * Host-side functions over caller memory: the tracker is sequential per target by nature and works on a handful of armours. */
+ * Two forms exist.  These are host-side functions over caller memory, one target or one list at a time, for a host that tracks a
+ * single camera itself; the device-resident tracker further down (rmcv_tracker_*) keeps the state of a whole batch of streams in
+ * HBM and steps it behind a batch without the host.  The two share every operation but ONE: the Jacobi rotation inside
+ * cv::solve(DECOMP_SVD) calls hypot, which these functions (like the CPU oracle they are tested against) take from the host's libm
+ * -- not correctly rounded, and not the same from one libm to the next -- and the device tracker takes from the library's own
+ * correctly rounded pm_hypot.  The filter fields (state, covariances, gain) of the two forms may therefore differ in the last bits;
+ * everything discrete (matching, counts, lost counts, histograms, timestamps) is the same. */
 /* rm::armour::max_IoU (src/core.cpp:144-162): *index = the armour of `list` with the largest IoU of bounding boxes with `self`
  * (first on ties, -1 when none overlaps), *iou = that IoU */
 int rmcv_max_iou(const rmcv_armour* self, const rmcv_armour* list, int n, int32_t* index, float* iou);
@@ -568,6 +574,69 @@ int  rmcv_track_predict(rmcv_track* t, int64_t new_timestamp, double tick_freque
  * matching observations need cap >= N, as the reference's vectors do -- or when a target would see its 33rd distinct identity
  * (lists handed back consistent). */
 int  rmcv_track_step(rmcv_track* tracking, int32_t* n_tracking, int cap, rmcv_track* observations, int32_t* n_obs, double tick_frequency);
+
+/* ---- device-resident tracker: detect, track and re-window without the host -----------------------------------------
+ * A tracker holds, in HBM, the tracking state of n_streams independent camera streams: frame f of every batch stepped against it is
+ * the next frame of stream f.  Per stream: up to track_cap rmcv_track records, their number, a status word and ONE requested window
+ * origin; per track a side record, the frame-coordinate vertices of the observation that created the track or matched it last
+ * (rmcv_track::armour is never refreshed by update(), mirrored: the side record alone knows where the target is now).
+ * One STEP, behind a run that included RMCV_STAGE_ARMOURS, does for every stream f:
+ *  1. observations: the frame's armours in rmcv_batch_get_armours order, moved to frame coordinates as rmcv_armours_to_frame(a, n,
+ *     x_eff, y_eff) does ((0, 0) without windows), each rmcv_track_init(armour, identity, timestamp, position) + rmcv_track_reset(
+ *     process_noise, measurement_noise, error); identity from the run's RMCV_STAGE_IDENTITY, else -1; position from its
+ *     RMCV_STAGE_POSE, else (0, 0, 0); timestamp: one int64 per step (all frames of a batch are one instant on different cameras);
+ *  2. one pass of the tracking thread, exactly rmcv_track_step's (no observation: nothing happens, not even ageing) -- with the
+ *     library's correctly rounded hypot in the filter (see the note above rmcv_max_iou);
+ *  3. capacity: what the pass would leave behind is counted first, on indices.  If surviving targets + unmatched observations exceed
+ *     track_cap, or a matched target would see its 33rd distinct identity, the stream's step is NOT APPLIED AT ALL -- lists, side
+ *     records and origin stay as they were -- and RMCV_TRACKER_OVF is set in the stream's status, sticky until rmcv_tracker_reset;
+ *  4. next window (win_w > 0): the target is the stream's track with the greatest timestamp, lowest index on ties; its side record's
+ *     four vertices go through rmcv_get_roi(v, 4, roi_scale_w, roi_scale_h, frame_w, frame_h, NULL) and rmcv_window_origin(rect,
+ *     win_w, win_h); the int32 pair becomes the stream's requested origin (k_window_origins clamps and snaps it in front of the next
+ *     pixel pass, as for any origin).  No tracks: the origin stays.  (A step without observations changes no list but still does 4.)
+ * Every byte of every rmcv_track, count, status, side record and origin equals the CPU restatement
+ * (tests/track_ref.py: the oracle's tracker with only hypot replaced by an independent correctly rounded one). */
+#define RMCV_TRACKER_OVF 1
+#define RMCV_TRACKER_MAX_CAP 64
+typedef struct rmcv_tracker rmcv_tracker;
+typedef struct {
+    int32_t n_streams;         /* camera streams = frames of every batch stepped against the tracker   (256)  */
+    int32_t track_cap;         /* tracks per stream, 1 .. RMCV_TRACKER_MAX_CAP                         (64)   */
+    double  process_noise, measurement_noise, error; /* rmcv_track_reset's                (5e-5, 0.5, 0.05)   */
+    double  tick_frequency;    /* timestamp ticks per second, cv::getTickFrequency()                   (1e9)  */
+    float   roi_scale_w, roi_scale_h; /* rmcv_get_roi's                                              (1, 1)   */
+    int32_t frame_w, frame_h;  /* the streams' frames                                          (1280, 1024)   */
+    int32_t win_w, win_h;      /* the window the origins are for; win_w == 0: track only, no origins (0, 0)   */
+} rmcv_tracker_config;
+void rmcv_default_tracker_config(rmcv_tracker_config* c);
+/* RMCV_ERR_BAD_ARG: n_streams < 1, track_cap out of range, noises / tick_frequency not finite or tick_frequency <= 0, frame or window
+ * sizes out of range (a window larger than the frame).  cfg NULL: the defaults. */
+int  rmcv_tracker_create(int device, const rmcv_tracker_config* cfg, rmcv_tracker** out);
+void rmcv_tracker_destroy(rmcv_tracker* trk);   /* waits for the step in flight first */
+const char* rmcv_tracker_last_error(const rmcv_tracker* trk);
+/* all lists empty, status cleared (origins stay).  Waits for the step in flight. */
+int  rmcv_tracker_reset(rmcv_tracker* trk);
+/* the initial requests: n_streams host points, copied.  Waits for the step in flight. */
+int  rmcv_tracker_set_origins(rmcv_tracker* trk, const rmcv_point* origins);
+/* device view of the requested origins (n_streams rmcv_point): what a caller hands to rmcv_batch_set_device_windows /
+ * rmcv_pipeline_submit_windows.  Owned by the tracker. */
+int  rmcv_tracker_device_origins(rmcv_tracker* trk, void** d_origins);
+/* enqueue one step on `hip_stream` (NULL: the context's stream) behind the context's last run, on the batch bound to it.  Never
+ * synchronises.  RMCV_ERR_BAD_ARG with a message: the batch's n_frames != n_streams; its frame size differs from the config's; the last
+ * run had no RMCV_STAGE_ARMOURS; windows are set and their size differs from the config's; context and tracker on different devices. */
+int  rmcv_batch_track(rmcv_ctx* ctx, rmcv_tracker* trk, int64_t timestamp, void* hip_stream);
+/* synchronous downloads (they wait for the step in flight, with a 5 s deadline: RMCV_ERR_TIMEOUT).  counts: the first min(cap,
+ * n_streams) entries, either pointer may be NULL.  get: one stream's list (RMCV_ERR_CAPACITY when *n > cap; tracks_out /
+ * last_vertices_out ([cap][4][2] floats) / origin_out nullable). */
+int  rmcv_tracker_counts(rmcv_tracker* trk, int32_t* n_tracking, int32_t* status, int cap);
+int  rmcv_tracker_get(rmcv_tracker* trk, int stream, rmcv_track* tracks_out, int cap, int32_t* n, float* last_vertices_out, rmcv_point* origin_out);
+/* the same step for ONE stream on the CPU over host arrays (no device; the same source the kernel is compiled from): tracks
+ * [track_cap], last_vertices [track_cap][4][2], *n_tracking, *status, *origin are read and updated; the observations are n_obs armours
+ * in WINDOW coordinates with the effective origin (x_eff, y_eff) they are moved by, identities (NULL: -1) and positions (n_obs x 3
+ * doubles; NULL: zeros).  cfg->n_streams is not read.  A C host gets the device tracker's exact semantics for a single camera. */
+int  rmcv_tracker_step_host(const rmcv_tracker_config* cfg, rmcv_track* tracks, float* last_vertices, int32_t* n_tracking, int32_t* status,
+                            rmcv_point* origin, const rmcv_armour* armours, int n_obs, const int32_t* identities, const double* positions,
+                            int x_eff, int y_eff, int64_t timestamp);
 
 /* ---- pipelined batches: the process loop behind the ABI ------------------------------------------------------------------------
  * The reference's process_function is a `while (1)` that takes the newest camera frame, runs the three detection calls and hands
@@ -693,6 +762,18 @@ int  rmcv_pipeline_submit_legacy(rmcv_pipeline* pl, const void* d_frames, int n_
  * effective origins. */
 int  rmcv_pipeline_submit_windows(rmcv_pipeline* pl, const void* d_frames, int n_frames, int frame_w, int frame_h, int stride, int64_t frame_pitch,
                                   const void* d_origins, int win_w, int win_h, const rmcv_params* p, int stages, uint64_t* ticket);
+/* a TRACKED batch: frame f is the next frame of stream f of `trk` (device-resident tracker, above).  With the tracker's win_w > 0 this is
+ * rmcv_pipeline_submit_windows whose origins are the tracker's requested origins; with win_w == 0 a whole-frame submit.  In both cases one
+ * step of the tracker (`timestamp`: see rmcv_batch_track) is enqueued behind the batch's compaction on its finishing stream, and the NEXT
+ * tracked submit on the same tracker waits on the GPU, by event, for that step in front of its k_window_origins: a strict closed loop --
+ * batch k + 1 sees the origins of step k -- in which the host only submits.  (The pipeline enqueues a batch's back half on the next call:
+ * that call enqueues back half, step and event before the next front half.)  rmcv_pipeline_wait / _collect / _drain of a tracked ticket
+ * complete the step too.  Submits on different trackers, and untracked submits, are not ordered against it: two trackers interleave on one
+ * pipeline and overlap as batches do.  Tracked batches stay out of the hot-context rotation.  Nothing blocks: host_blocking_calls stays 0.
+ * RMCV_ERR_BAD_ARG, with a message and before anything is enqueued: n_frames != the tracker's n_streams, a frame size other than its
+ * config's, stages without RMCV_STAGE_ARMOURS, a tracker on another device. */
+int  rmcv_pipeline_submit_tracked(rmcv_pipeline* pl, rmcv_tracker* trk, const void* d_frames, int n_frames, int frame_w, int frame_h, int stride,
+                                  int64_t frame_pitch, const rmcv_params* p, int stages, int64_t timestamp, uint64_t* ticket);
 /* block until the batch is through (its record complete in HBM and, with host_results, on the host) */
 int  rmcv_pipeline_wait(rmcv_pipeline* pl, uint64_t ticket);
 /* wait + hand the batch's armours over, frame-major, in submission order of the frames: frame_offs (nullable) has n_frames + 1

@@ -11,5 +11,6 @@ from .abi import (ARMOUR, BAYER_BG, BAYER_GB, BAYER_GR, BAYER_PATTERNS, BAYER_RG
                   Params, PnpConfig, RmcvError, armours_to_frame, default_params, default_pnp_config, get_roi, window_origin)
 from .api import Context
 from .pipeline import Pipeline
+from .tracker import TRACKER_OVF, Tracker, TrackerConfig, default_tracker_config
 
 __all__ = [n for n in dir() if not n.startswith("_")]

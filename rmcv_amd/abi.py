@@ -75,6 +75,8 @@ EXPORTS = [
     "rmcv_ctx_set_enhance_gains", "rmcv_ctx_get_enhance", "rmcv_gamma_lut", "rmcv_enhance_gamma", "rmcv_calc_gamma", "rmcv_auto_enhance", "rmcv_batch_get_gammas",
     "rmcv_batch_set_windows", "rmcv_batch_set_device_windows", "rmcv_batch_get_windows", "rmcv_batch_device_windows", "rmcv_pipeline_submit_windows",
     "rmcv_get_roi", "rmcv_window_origin", "rmcv_armours_to_frame",
+    "rmcv_default_tracker_config", "rmcv_tracker_create", "rmcv_tracker_destroy", "rmcv_tracker_last_error", "rmcv_tracker_reset", "rmcv_tracker_set_origins",
+    "rmcv_tracker_device_origins", "rmcv_batch_track", "rmcv_tracker_counts", "rmcv_tracker_get", "rmcv_tracker_step_host", "rmcv_pipeline_submit_tracked",
 ]
 
 
@@ -190,6 +192,23 @@ def load(path):
         L.rmcv_get_roi.argtypes = [C.c_void_p, C.c_int, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
         L.rmcv_window_origin.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p]
         L.rmcv_armours_to_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+    if hasattr(L, "rmcv_tracker_create"):  # (builds from before the device tracker stay loadable for A/B runs)
+        L.rmcv_default_tracker_config.restype = None
+        L.rmcv_default_tracker_config.argtypes = [C.c_void_p]
+        L.rmcv_tracker_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_destroy.restype = None
+        L.rmcv_tracker_destroy.argtypes = [C.c_void_p]
+        L.rmcv_tracker_last_error.restype = C.c_char_p
+        L.rmcv_tracker_last_error.argtypes = [C.c_void_p]
+        L.rmcv_tracker_reset.argtypes = [C.c_void_p]
+        L.rmcv_tracker_set_origins.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_device_origins.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_batch_track.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+        L.rmcv_tracker_counts.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_tracker_get.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_step_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
+                                             C.c_int, C.c_int, C.c_int64]
+        L.rmcv_pipeline_submit_tracked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L

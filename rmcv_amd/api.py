@@ -433,6 +433,11 @@ class Context:
         self._params = params or default_params()
         self._chk(lib().rmcv_batch_run(self._h, C.byref(self._params), int(stages), C.c_void_p(stream or 0)))
 
+    def track(self, tracker, timestamp, stream=None):
+        """rmcv_batch_track: one step of a device-resident Tracker behind this context's last run (which included STAGE_ARMOURS), on
+        that batch -- frame f is the next frame of the tracker's stream f.  Asynchronous; never synchronises."""
+        self._chk(lib().rmcv_batch_track(self._h, tracker._h, C.c_int64(int(timestamp)), C.c_void_p(stream or 0)))
+
     def run_timed(self, params=None, stages=STAGE_ALL, stream=None):
         """returns ms of [binary, contours, blobs, armours, total] measured with HIP events on the launch stream"""
         self._params = params or default_params()

@@ -22,6 +22,10 @@
  * x^2.  Coefficients were re-verified against mpmath (rel. error < 5e-18).
  * Float variants evaluate in double and round once (correctly rounded float
  * results except with probability ~2^-29).
+ *
+ * pm_hypot (the device tracker's Jacobi rotation) is the one function here that
+ * is CORRECTLY ROUNDED, and the one that uses sqrt and the explicit fma besides:
+ * see its own comment.
  */
 #ifndef RMCV_PINNED_MATH_H
 #define RMCV_PINNED_MATH_H
@@ -311,6 +315,98 @@ PM_FN double pm_pow(double x, double g)
     if (x == 0.0) return 0.0;
     if (x == 1.0) return 1.0;
     return pm_exp(g * pm_log(x));
+}
+
+/* ---- hypot, for the Jacobi rotation of the device tracker's cv::solve(DECOMP_SVD) (device_track.h) -------------------------------
+ * CORRECTLY ROUNDED over the whole finite range (round to nearest even, subnormal results included), C99 for 0, infinity and NaN.
+ * The host libm's hypot is not correctly rounded and differs between machines, and a GPU has none: this one has a single right
+ * answer, which tests/test_pinned_hypot.py checks against exact integer arithmetic.  Unlike the rest of this file it uses fma --
+ * the explicit, exactly rounded one (__builtin_fma), never a contraction.
+ * Method: both arguments scaled by a power of two into [2^-376, 2^500); x^2 and y^2 as exact double-double products; a candidate
+ * from sqrt of their sum with one Newton correction (within an ulp); then the candidate is MOVED until x^2 + y^2 lies between the
+ * squares of its two rounding boundaries, the sign of  x^2 + y^2 - (r +- half ulp)^2  being that of an eight-term sum computed
+ * without error (Shewchuk's grow-expansion: the largest non-zero component of a non-overlapping expansion carries the sign).
+ * A tie (a Pythagorean triple whose hypotenuse needs 54 bits) goes to the even neighbour.  When the larger argument is subnormal the
+ * result's grid is 2^-1074 whatever its size: the arguments become integers and the candidate is rounded to an integer instead. */
+#define PM_TS_(q, e)                          \
+    {                                         \
+        const double x_ = (q) + (e);          \
+        const double bv_ = x_ - (q);          \
+        const double av_ = x_ - bv_;          \
+        (e) = ((q) - av_) + ((e) - bv_);      \
+        (q) = x_;                             \
+    }
+/* the sign (-1, 0, 1) of t0 + ... + t7, exactly: no overflow, no underflow (the caller's scaling) */
+PM_FN int pm_sign_sum8(double t0, double t1, double t2, double t3, double t4, double t5, double t6, double t7)
+{
+    double e0 = t0, e1, e2, e3, e4, e5, e6, e7, q;
+    q = t1; PM_TS_(q, e0) e1 = q;
+    q = t2; PM_TS_(q, e0) PM_TS_(q, e1) e2 = q;
+    q = t3; PM_TS_(q, e0) PM_TS_(q, e1) PM_TS_(q, e2) e3 = q;
+    q = t4; PM_TS_(q, e0) PM_TS_(q, e1) PM_TS_(q, e2) PM_TS_(q, e3) e4 = q;
+    q = t5; PM_TS_(q, e0) PM_TS_(q, e1) PM_TS_(q, e2) PM_TS_(q, e3) PM_TS_(q, e4) e5 = q;
+    q = t6; PM_TS_(q, e0) PM_TS_(q, e1) PM_TS_(q, e2) PM_TS_(q, e3) PM_TS_(q, e4) PM_TS_(q, e5) e6 = q;
+    q = t7; PM_TS_(q, e0) PM_TS_(q, e1) PM_TS_(q, e2) PM_TS_(q, e3) PM_TS_(q, e4) PM_TS_(q, e5) PM_TS_(q, e6) e7 = q;
+    q = e7 != 0 ? e7 : (e6 != 0 ? e6 : (e5 != 0 ? e5 : (e4 != 0 ? e4 : (e3 != 0 ? e3 : (e2 != 0 ? e2 : (e1 != 0 ? e1 : e0))))));
+    return q > 0 ? 1 : (q < 0 ? -1 : 0);
+}
+#undef PM_TS_
+
+PM_FN double pm_hypot(double x, double y)
+{
+    const double inf = __builtin_huge_val();
+    const double p537 = 0x1p537, m537 = 0x1p-537; /* 2^537, 2^-537 */
+    const double p600 = 0x1p600, m600 = 0x1p-600; /* 2^600, 2^-600 */
+    const double p700 = 0x1p700, m700 = 0x1p-700; /* 2^700, 2^-700 */
+    double ax = __builtin_fabs(x), ay = __builtin_fabs(y), un1 = 1.0, un2 = 1.0, r;
+    double hx, lx, hy, ly, s, e;
+    int fixed = 0, it;
+    if (ax == inf || ay == inf) return inf;
+    if (x != x || y != y) return x + y;
+    if (ax < ay) { const double t = ax; ax = ay; ay = t; }
+    if (ay == 0.0) return ax;
+    if (ay <= ax * 0x1p-54) return ax; /* 2^-54 of the larger: y^2 / (2 x) is below 2^-55 of an ulp of x */
+    if (ax >= 0x1p500) { /* 2^500 */
+        ax *= m600; ay *= m600; un1 = p600;
+    } else if (ax < 0x1p-1022) { /* subnormal: integers below 2^52 */
+        ax = ax * p537 * p537; ay = ay * p537 * p537; un1 = m537; un2 = m537; fixed = 1;
+    } else if (ax < 0x1p-250) { /* 2^-250 */
+        ax *= p700; ay *= p700; un1 = m700;
+    }
+    hx = ax * ax; lx = __builtin_fma(ax, ax, -hx);
+    hy = ay * ay; ly = __builtin_fma(ay, ay, -hy);
+    s = hx + hy;
+    e = ((hx - s) + hy) + (lx + ly);
+    r = __builtin_sqrt(s);
+    {
+        const double rr = r * r, rl = __builtin_fma(r, r, -rr);
+        r = r + (((s - rr) - rl) + e) / (2.0 * r);
+    }
+    if (fixed && r < 4503599627370496.0) r = (r + 4503599627370496.0) - 4503599627370496.0;
+    for (it = 0; it < 4; it++) { /* the candidate is within an ulp: one move at most; the bound is a bound */
+        uint64_t u;
+        double up, dn, hu, hd, rr, rl;
+        int odd, sg;
+        __builtin_memcpy(&u, &r, 8);
+        if (fixed) { up = r + 1.0; dn = r - 1.0; odd = (int)((uint64_t)r & 1u); }
+        else {
+            uint64_t v = u + 1;
+            __builtin_memcpy(&up, &v, 8);
+            v = u - 1;
+            __builtin_memcpy(&dn, &v, 8);
+            odd = (int)(u & 1u);
+        }
+        hu = (up - r) * 0.5;
+        hd = (r - dn) * 0.5;
+        rr = r * r;
+        rl = __builtin_fma(r, r, -rr);
+        sg = pm_sign_sum8(hx, lx, hy, ly, -rr, -rl, -(2.0 * r * hu), -(hu * hu));
+        if (sg > 0 || (sg == 0 && odd)) { r = up; continue; }
+        sg = pm_sign_sum8(hx, lx, hy, ly, -rr, -rl, 2.0 * r * hd, -(hd * hd));
+        if (sg < 0 || (sg == 0 && odd)) { r = dn; continue; }
+        break;
+    }
+    return r * un1 * un2;
 }
 
 #endif /* RMCV_PINNED_MATH_H */

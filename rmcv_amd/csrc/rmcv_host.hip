@@ -18,6 +18,7 @@
 #include "rmcv_internal.h"
 #include "device_bayer.h"
 #include "enhance_math.h"
+#include "device_track.h"
 
 using namespace rmcv;
 
@@ -108,6 +109,7 @@ struct rmcv_ctx {
     double marks[9] = {};         // rmcv_ctx_frame_timing: host clock at the steps of the last rmcv_extract_color (microseconds)
     uint64_t blocking_calls = 0;  // allocations, host-side synchronisations and blocking copies made while binding a geometry (ctx_blocking_calls)
     int32_t* order_scratch = nullptr; // [2 * max_frames] k_frame_order's work lists for batches beyond its LDS tables
+    int last_stages = 0;              // the stages the batch bound has been through since its last pixel pass (rmcv_batch_track asks for RMCV_STAGE_ARMOURS)
     rmcv_point* win_own = nullptr;    // [max_frames] the context's copy of host origins (rmcv_batch_set_windows); Bufs::win_req points here or at the caller's
     char err[256] = {0};
     std::vector<void*> allocs;
@@ -790,6 +792,7 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
     if ((stages & RMCV_STAGE_IDENTITY) && !identity_fused) HIPCHK(c, launch_classify(g, b, c->lim, s), "k_classify");
     if (stages & RMCV_STAGE_POSE) HIPCHK(c, launch_pnp(g, b, c->lim, s), "k_pnp");
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
+    c->last_stages = (stages & RMCV_STAGE_BINARY) ? stages : (c->last_stages | stages);
     return order_end(c, s);
 }
 
@@ -851,6 +854,7 @@ int rmcv_batch_upload(rmcv_ctx* c, const uint8_t* frames, int n_frames, int w, i
     }
     WAITCHK(c, wait_stream(c, c->stream, "H2D frames"));
     c->bufs.frames = c->own_frames;
+    c->last_stages = 0; // a new batch: nothing of it has run
     return RMCV_OK;
 }
 
@@ -865,6 +869,7 @@ int rmcv_batch_set_device_frames(rmcv_ctx* c, const void* d_frames, int n_frames
     rc = set_geom(c, n_frames, w, h, stride, frame_pitch);
     if (rc) return rc;
     c->bufs.frames = (const uint8_t*)d_frames;
+    c->last_stages = 0;
     return RMCV_OK;
 }
 
@@ -884,6 +889,7 @@ int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int 
     if (rc) return rc;
     c->bufs.frames = (const uint8_t*)d_frames;
     c->bufs.win_req = (const rmcv_point*)d_origins; // (the run computes the effective origins in front of its pixel pass)
+    c->last_stages = 0;
     return RMCV_OK;
 }
 // what binding a batch would allocate, now (a pipeline does this for every context of its ring when it is created)
@@ -2193,42 +2199,14 @@ int rmcv_batch_device_windows(rmcv_ctx* c, void** d_eff, int32_t* win_w, int32_t
 int rmcv_get_roi(const float* points, int n, float scale_w, float scale_h, int frame_w, int frame_h, const int32_t previous[4], int32_t out[4])
 {
     if (!out || n < 0 || (n > 0 && !points)) return RMCV_ERR_BAD_ARG;
-    int x = 0, y = 0, w = 0, h = 0; // cv::boundingRect of no points: the empty rect
-    if (n > 0) { // :227, SURVEY A.8: min / max in float, then floor
-        float minx = points[0], maxx = points[0], miny = points[1], maxy = points[1];
-        for (int i = 1; i < n; i++) {
-            const float px = points[2 * i], py = points[2 * i + 1];
-            minx = px < minx ? px : minx;
-            maxx = px > maxx ? px : maxx;
-            miny = py < miny ? py : miny;
-            maxy = py > maxy ? py : maxy;
-        }
-        const int ix = (int)floorf(minx), iy = (int)floorf(miny), ax = (int)floorf(maxx), ay = (int)floorf(maxy);
-        x = ix; y = iy; w = ax - ix + 1; h = ay - iy + 1;
-    }
-    if (previous) { x += previous[0]; y += previous[1]; } // :228-229
-    if (scale_w != 1.0f || scale_h != 1.0f) {             // :230
-        const int sw = (int)((double)w * scale_w / 2.0), sh = (int)((double)h * scale_h / 2.0); // :232-233
-        x -= sw;
-        y -= sh;
-        w += sw * 2;
-        h += sw * 2; // :238, as written: the WIDTH's margin
-    }
-    if (x < 0) x = 0;                           // :240-247 (the size is not reduced by what the corner moved)
-    if (y < 0) y = 0;
-    if (x + w >= frame_w) w = frame_w - x - 1;  // :248-255
-    if (y + h >= frame_h) h = frame_h - y - 1;
-    if (w < 0 || h < 0) x = y = w = h = 0;      // :257-260
-    out[0] = x; out[1] = y; out[2] = w; out[3] = h;
+    trk_get_roi(points, n, scale_w, scale_h, frame_w, frame_h, previous, out); // (device_track.h: the device tracker compiles the same body)
     return RMCV_OK;
 }
 
 int rmcv_window_origin(const int32_t rect[4], int win_w, int win_h, int32_t out_xy[2])
 {
     if (!rect || !out_xy || win_w < 1 || win_h < 1) return RMCV_ERR_BAD_ARG;
-    // the window centred on the rect: rect centre (x + w / 2, y + h / 2) minus half the window, integer division truncating
-    out_xy[0] = rect[0] + rect[2] / 2 - win_w / 2;
-    out_xy[1] = rect[1] + rect[3] / 2 - win_h / 2;
+    trk_window_origin(rect, win_w, win_h, out_xy); // (device_track.h)
     return RMCV_OK;
 }
 
@@ -2249,7 +2227,48 @@ int rmcv_armours_to_frame(rmcv_armour* armours, int n, int x, int y)
     return RMCV_OK;
 }
 
+int rmcv_batch_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, void* hip_stream)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    hipSetDevice(c->device);
+    return ctx_track(c, trk, timestamp, c->last_stages, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
 } // extern "C"
+
+namespace rmcv {
+// one step of the device tracker behind the context's last run (every check before the first enqueue); never synchronises
+int ctx_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, int stages, hipStream_t s)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!trk) return fail(c, RMCV_ERR_BAD_ARG, "null tracker");
+    const Geom& g = c->geom;
+    const rmcv_tracker_config& tc = tracker_config(trk);
+    char msg[200];
+    if (tracker_device(trk) != c->device) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_track: the tracker lives on another device than the context");
+    if (g.n_frames <= 0 || !c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_track: no frames bound");
+    if (g.n_frames != tc.n_streams) {
+        snprintf(msg, sizeof(msg), "rmcv_batch_track: the batch has %d frames, the tracker %d streams (frame f is the next frame of stream f)", g.n_frames, tc.n_streams);
+        return fail(c, RMCV_ERR_BAD_ARG, msg);
+    }
+    if (g.frame_w != tc.frame_w || g.frame_h != tc.frame_h) {
+        snprintf(msg, sizeof(msg), "rmcv_batch_track: the frames are %d x %d, the tracker's config says %d x %d", g.frame_w, g.frame_h, tc.frame_w, tc.frame_h);
+        return fail(c, RMCV_ERR_BAD_ARG, msg);
+    }
+    if (!(stages & RMCV_STAGE_ARMOURS)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_track: the last run had no RMCV_STAGE_ARMOURS: nothing to track");
+    if (g.win && (g.w != tc.win_w || g.h != tc.win_h)) {
+        snprintf(msg, sizeof(msg), "rmcv_batch_track: the batch's windows are %d x %d, the tracker's config says %d x %d", g.w, g.h, tc.win_w, tc.win_h);
+        return fail(c, RMCV_ERR_BAD_ARG, msg);
+    }
+    int rc;
+    if ((rc = order_begin(c, s))) return rc;
+    HIPCHK(c, tracker_order_begin(trk, s), "tracker: wait for its previous step");
+    HIPCHK(c, launch_track(tc, tracker_bufs(trk), c->bufs, c->lim, (stages & RMCV_STAGE_IDENTITY) != 0, (stages & RMCV_STAGE_POSE) != 0,
+                           g.win ? c->bufs.win_eff : nullptr, timestamp, s), "k_track");
+    HIPCHK(c, tracker_order_end(trk, s), "tracker: record the step");
+    return order_end(c, s);
+}
+} // namespace rmcv
 
 // rmcv_calc_gamma / rmcv_auto_enhance: a host image of `rows` rows of `row_bytes` bytes through a table, on the device.  A stage-wise
 // helper like rmcv_demosaic: buffers of its own, so that nothing bound to the context moves.  auto_w > 0: the image is a BGR frame of

@@ -277,4 +277,31 @@ int ctx_bound_enhance(const rmcv_ctx* c);
 // whether the frames bound last are read through windows
 int ctx_bound_windows(const rmcv_ctx* c);
 
+
+// ---- device-resident tracker (k_track.hip) ----
+// Device state of a tracker: two copies of every stream's list (a step reads the current one and writes the other; `sel` says which is
+// current, per stream -- a stream whose step is refused or sees no observation simply does not flip)
+struct TrackerBufs {
+    rmcv_track* tracks;  // [2][n_streams][track_cap]
+    float* side;         // [2][n_streams][track_cap][8]   frame-coordinate vertices of the observation that created / last matched the track
+    int32_t* sel;        // [n_streams] 0 / 1
+    int32_t* n_tracking; // [n_streams]
+    int32_t* status;     // [n_streams] RMCV_TRACKER_OVF
+    rmcv_point* origins; // [n_streams] the requested window origins (what Bufs::win_req borrows)
+};
+// one step for the n_streams frames of the batch in `b`; identity / pose: the run included those stages; win_eff: null without windows
+hipError_t launch_track(const rmcv_tracker_config& cfg, const TrackerBufs& tb, const Bufs& b, const Limits& lim, bool identity, bool pose,
+                        const rmcv_point* win_eff, int64_t timestamp, hipStream_t s);
+// rmcv_batch_track with the stages given (a pipeline runs a batch's halves separately: the context's record of its last run is not the batch's)
+int ctx_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, int stages, hipStream_t s);
+// what the step reads of the tracker; the event is recorded behind every step enqueued
+const rmcv_tracker_config& tracker_config(const rmcv_tracker* t);
+const TrackerBufs& tracker_bufs(const rmcv_tracker* t);
+int tracker_device(const rmcv_tracker* t);
+// order a step on `s`: wait (on the GPU) for the tracker's last step if that ran on another stream; afterwards record it
+hipError_t tracker_order_begin(rmcv_tracker* t, hipStream_t s);
+hipError_t tracker_order_end(rmcv_tracker* t, hipStream_t s);
+// make `s` wait for the tracker's last step (a consumer of its origins on another stream)
+hipError_t tracker_wait_on(rmcv_tracker* t, hipStream_t s);
+
 } // namespace rmcv

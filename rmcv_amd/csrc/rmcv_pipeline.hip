@@ -72,6 +72,9 @@ struct rmcv_pipeline {
         RunPlan plan{}; // the batch's plan: the context's options, the pixel shape submit chose, SPARSE_LEAN in dense mode
         int sparse = 0, n_frames = 0;
         hipStream_t B = nullptr;
+        rmcv_tracker* trk = nullptr; // rmcv_pipeline_submit_tracked: the tracker's step goes behind the batch's compaction, in front of ev_done
+        int64_t timestamp = 0;
+        int stages = 0;
     } pend;
     uint64_t latency_batches = 0;
     bool was_cold = false;             // the batch before the newest one found the pixel stream idle (a burst's first launch)
@@ -547,6 +550,15 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
     // writes over PCIe, only the armours there are); the slot's event -- a default event: system-scope release -- makes them visible
     rc = ctx_compact(c, pl->d_rec[k] + pl->head_bytes, pl->cfg.armour_cap, offs, offs + pl->lim.max_frames + 1, T, pl->hd_rec[k], (int)pl->head_bytes);
     if (rc) return cfail(pl, c, rc);
+    // a tracked batch: the tracker's step right behind the compaction, on the stream the list was finished on -- it reads the context's
+    // armours, identities, poses and effective origins, so it comes BEFORE ev_done frees them; ctx_track records the tracker's event
+    // behind it (the next tracked submit's k_window_origins waits for that), and wait / collect / drain of the ticket cover the step
+    if (pl->pend.trk) {
+        rc = ctx_track(c, pl->pend.trk, pl->pend.timestamp, pl->pend.stages, T);
+        pl->pend.trk = nullptr;
+        if (rc) return cfail(pl, c, rc);
+        pl->last_what = "k_track";
+    }
     // the context's buffers are free from here on: the next pixel kernel of this slot does not wait for the hook
     PCHK(pl, hipEventRecord(pl->ev_done[k], T), "pipeline: mark the slot");
     pl->slot_ticket[k] = t + 1;
@@ -573,10 +585,18 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
 
 // d_origins non-null: a windowed batch (rmcv_pipeline_submit_windows) -- every frame read through a win_w x win_h window
 static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, const rmcv_params* p,
-                  const rmcv_legacy_params* lp, int stages, uint64_t* ticket, const void* d_origins = nullptr, int win_w = 0, int win_h = 0)
+                  const rmcv_legacy_params* lp, int stages, uint64_t* ticket, const void* d_origins = nullptr, int win_w = 0, int win_h = 0,
+                  rmcv_tracker* trk = nullptr, int64_t timestamp = 0)
 {
     if (!pl || !d_frames || !p) return RMCV_ERR_BAD_ARG;
     if (!(stages & RMCV_STAGE_BINARY)) return pfail(pl, RMCV_ERR_BAD_ARG, "a pipelined batch starts at RMCV_STAGE_BINARY");
+    if (trk) { // everything rmcv_batch_track would refuse, before anything is enqueued
+        const rmcv_tracker_config& tc = tracker_config(trk);
+        if (tracker_device(trk) != pl->device) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_tracked: the tracker lives on another device than the pipeline");
+        if (n_frames != tc.n_streams) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_tracked: n_frames differs from the tracker's n_streams (frame f is the next frame of stream f)");
+        if (w != tc.frame_w || h != tc.frame_h) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_tracked: the frame size differs from the tracker's config");
+        if (!(stages & RMCV_STAGE_ARMOURS)) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_tracked: the stages have no RMCV_STAGE_ARMOURS: nothing to track");
+    }
     hipSetDevice(pl->device);
     { const int rcb = finish_back(pl, false); if (rcb) return rcb; } // the batch before this one: a pixel launch follows it
     const uint64_t t = pl->next_ticket;
@@ -605,7 +625,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     // (so do batches read through their gamma tables, RMCV_OPT_ENHANCE on the slot's context: they take the k_binary shape, and the sums pass in
     // front of it has no use for another batch's planes in the cache)
     // (and windowed batches: the k_binary shape too, and a geometry of their own -- in the rotation they would re-zero the hot contexts' planes)
-    const bool fast = pl->hot && pl->calm && !lp && !(stages & RMCV_STAGE_POSE) && !(stages & RMCV_STAGE_IDENTITY) && !ctx_enhance(pl->ring[k]) && !d_origins;
+    const bool fast = pl->hot && pl->calm && !lp && !(stages & RMCV_STAGE_POSE) && !(stages & RMCV_STAGE_IDENTITY) && !ctx_enhance(pl->ring[k]) && !d_origins && !trk; // (nor tracked ones: the step reads the context's lists behind the compaction)
     const size_t j = fast ? (size_t)(pl->hot_seq % (uint64_t)pl->hot) : k;
     rmcv_ctx* c = pl->ring[j];
     int rc;
@@ -670,6 +690,9 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
             }
         }
     }
+    // strict closed loop: the origins k_window_origins is about to read are those the tracker's last step wrote -- an event wait on the GPU
+    // (that step was enqueued by the finish_back above, or earlier)
+    if (trk && d_origins) PCHK(pl, tracker_wait_on(trk, A), "pipeline: wait for the tracker's last step");
     rc = ctx_run(c, p, nullptr, pixel, A, plan);
     if (rc) return cfail(pl, c, rc);
     pl->last_what = ctx_input_format(c) ? "the pixel kernel (k_binary_bayer)" : ctx_bound_enhance(c) ? "k_frame_sums, k_enhance_table, the pixel kernel (k_binary_enh)" : ctx_bound_windows(c) ? "k_window_origins, the pixel kernel (k_binary_win)" : "the pixel kernel (k_binary / k_binary_ws)";
@@ -695,6 +718,9 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     pl->pend.sparse = sparse;
     pl->pend.n_frames = n_frames;
     pl->pend.B = B;
+    pl->pend.trk = trk;
+    pl->pend.timestamp = timestamp;
+    pl->pend.stages = stages;
     // (a hook or the gather hands the record to a consumer the pipeline does not see waiting: its batches are finished here and now)
     if (pl->hook || pl->comm) return finish_back(pl, false);
     return RMCV_OK;
@@ -702,13 +728,14 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
 
 // submit + its own bookkeeping: the host time of the call, and the blocking calls the ring's contexts counted during it
 static int submit_counted(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, const rmcv_params* p,
-                          const rmcv_legacy_params* lp, int stages, uint64_t* ticket, const void* d_origins = nullptr, int win_w = 0, int win_h = 0)
+                          const rmcv_legacy_params* lp, int stages, uint64_t* ticket, const void* d_origins = nullptr, int win_w = 0, int win_h = 0,
+                          rmcv_tracker* trk = nullptr, int64_t timestamp = 0)
 {
     if (!pl) return RMCV_ERR_BAD_ARG;
     timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     const uint64_t b0 = ring_blocking(pl);
-    const int rc = submit(pl, d_frames, n_frames, w, h, stride, frame_pitch, p, lp, stages, ticket, d_origins, win_w, win_h);
+    const int rc = submit(pl, d_frames, n_frames, w, h, stride, frame_pitch, p, lp, stages, ticket, d_origins, win_w, win_h, trk, timestamp);
     pl->own_blocking += ring_blocking(pl) - b0;
     clock_gettime(CLOCK_MONOTONIC, &t1);
     const double us = (t1.tv_sec - t0.tv_sec) * 1e6 + (t1.tv_nsec - t0.tv_nsec) * 1e-3;
@@ -743,6 +770,17 @@ int rmcv_pipeline_submit_windows(rmcv_pipeline* pl, const void* d_frames, int n_
     if (!d_origins) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_windows: null origins (device memory: one rmcv_point per frame)");
     if (win_w < 1 || win_h < 1) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_windows: window size out of range");
     return submit_counted(pl, d_frames, n_frames, frame_w, frame_h, stride, frame_pitch, p, nullptr, stages, ticket, d_origins, win_w, win_h);
+}
+
+int rmcv_pipeline_submit_tracked(rmcv_pipeline* pl, rmcv_tracker* trk, const void* d_frames, int n_frames, int frame_w, int frame_h, int stride,
+                                 int64_t frame_pitch, const rmcv_params* p, int stages, int64_t timestamp, uint64_t* ticket)
+{
+    if (!pl) return RMCV_ERR_BAD_ARG;
+    if (!trk) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_tracked: null tracker");
+    const rmcv_tracker_config& tc = tracker_config(trk);
+    // win_w > 0: a windowed submit whose origins are the tracker's; win_w == 0: whole frames (track only)
+    return submit_counted(pl, d_frames, n_frames, frame_w, frame_h, stride, frame_pitch, p, nullptr, stages, ticket,
+                          tc.win_w > 0 ? tracker_bufs(trk).origins : nullptr, tc.win_w, tc.win_h, trk, timestamp);
 }
 
 // slot of a live ticket, or -1

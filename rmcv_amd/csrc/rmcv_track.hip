@@ -1,6 +1,9 @@
 // rmcv_track.hip -- tracker state of rm::armour with everything readable: rm::armour::reset / update(const armour&) /
 // update(int64) (/root/reference/src/core.cpp:51-122) and the association loop of the tracking thread
-// (executable/main.cpp:57-88).  Host-side by nature: sequential per target, a handful of armours per frame, 6x6 fp64.
+// (executable/main.cpp:57-88).  The HOST-SIDE form, over caller memory: one target or one list at a time, for a host that tracks a
+// single camera itself.  The device-resident form for a batch of streams is k_track.hip / device_track.h; both exist.  This one keeps
+// libm's hypot in the Jacobi rotation (it is compared with the unmodified CPU oracle); the device tracker uses the correctly rounded
+// pm_hypot, so the filter fields of the two may differ in the last bits (include/rmcv_abi.h).
 //
 // The filter is cv::KalmanFilter(6, 6, 0, CV_64F) (core.cpp:21); [OCV] init / predict / correct are restated as recalled from
 // OpenCV's video/src/kalman.cpp (gemm = sequential k-sums in double; the gain through cv::solve(..., DECOMP_SVD) = one-sided

@@ -78,15 +78,24 @@ class Pipeline:
         return o
 
     # ------------------------------------------------------------------ the three calls
-    def submit(self, data_ptr, n, h, w, params=None, stages=STAGE_ALL, stride=None, frame_pitch=None, keepalive=None, legacy=None, windows=None):
+    def submit(self, data_ptr, n, h, w, params=None, stages=STAGE_ALL, stride=None, frame_pitch=None, keepalive=None, legacy=None, windows=None, tracker=None, timestamp=0):
         """enqueue one batch of frames resident in HBM (data_ptr: e.g. torch_tensor.data_ptr()); returns the ticket.
         windows = (d_origins_ptr, win_w, win_h): a windowed batch -- d_origins_ptr a device pointer to n (x, y) int32 pairs (e.g. an
-        int32 (n, 2) torch tensor's data_ptr(); keep it alive like the frames), results in window coordinates (Context.set_windows)"""
+        int32 (n, 2) torch tensor's data_ptr(); keep it alive like the frames), results in window coordinates (Context.set_windows).
+        tracker = a rmcv_amd.Tracker (+ timestamp): a tracked batch (rmcv_pipeline_submit_tracked) -- windowed at the tracker's own origins
+        when its win_w > 0, whole frames otherwise; one step of the tracker runs behind the batch, and the next tracked submit on that
+        tracker reads the origins it wrote: the closed loop with the host only submitting"""
         if params is not None:
             self._params = params
         stride = stride or (w * self.sample_bits // 8 if self.input_format else 3 * w)
         frame_pitch = frame_pitch or stride * h
-        if windows is not None:
+        if tracker is not None:
+            assert legacy is None and windows is None, "a tracked batch takes its windows from the tracker"
+            rc = self._lib.rmcv_pipeline_submit_tracked(self._h, tracker._h, data_ptr, n, w, h, stride, frame_pitch, C.addressof(self._params), int(stages),
+                                                        int(timestamp), C.addressof(self._ticket))
+            if tracker.config.win_w > 0:
+                windows = (0, tracker.config.win_w, tracker.config.win_h)   # (the shape of what the getters return)
+        elif windows is not None:
             assert legacy is None, "the legacy matcher has no windowed submit"
             d_origins, win_w, win_h = windows
             rc = self._lib.rmcv_pipeline_submit_windows(self._h, data_ptr, n, w, h, stride, frame_pitch, int(d_origins), int(win_w), int(win_h),
@@ -100,7 +109,7 @@ class Pipeline:
         if rc != 0:
             self._chk(rc)
         t = self._ticket.value
-        self._keep[t % self.depth] = keepalive
+        self._keep[t % self.depth] = (keepalive, tracker)
         self._n[t % self.depth] = n
         self.shape = (n, h, w) if windows is None else (n, int(windows[2]), int(windows[1]))
         self._shape[t % self.depth] = self.shape     # (windowed and whole-frame batches may alternate: context_of hands out the ticket's)

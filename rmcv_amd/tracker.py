@@ -1,0 +1,110 @@
+"""rmcv_tracker_* (include/rmcv_abi.h): the device-resident tracker.
+
+The tracking state of a batch of camera streams lives in HBM; one step runs behind a batch (Context.track, Pipeline.submit(...,
+tracker=)) and writes the next batch's window origins on the device -- detect, track and re-window without the host.  Tracker.step_host
+is the same step for one stream on the CPU (the source the kernel is compiled from), which needs no device.
+"""
+import ctypes as C
+
+import numpy as np
+
+from .abi import ARMOUR, POINT, TRACK, RmcvError, lib, ptr
+
+TRACKER_OVF = 1
+TRACKER_MAX_CAP = 64
+
+
+class TrackerConfig(C.Structure):
+    """rmcv_tracker_config"""
+    _fields_ = [("n_streams", C.c_int32), ("track_cap", C.c_int32), ("process_noise", C.c_double), ("measurement_noise", C.c_double),
+                ("error", C.c_double), ("tick_frequency", C.c_double), ("roi_scale_w", C.c_float), ("roi_scale_h", C.c_float),
+                ("frame_w", C.c_int32), ("frame_h", C.c_int32), ("win_w", C.c_int32), ("win_h", C.c_int32)]
+
+
+def default_tracker_config(**kw):
+    c = TrackerConfig()
+    lib().rmcv_default_tracker_config(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+class Tracker:
+    def __init__(self, device=0, **config):
+        """config: fields of rmcv_tracker_config (n_streams, track_cap, process_noise, measurement_noise, error, tick_frequency,
+        roi_scale_w, roi_scale_h, frame_w, frame_h, win_w, win_h); win_w = 0: track only, no origins"""
+        self.config = default_tracker_config(**config)
+        h = C.c_void_p()
+        rc = lib().rmcv_tracker_create(int(device), C.byref(self.config), C.byref(h))
+        if rc != 0:
+            raise RmcvError(rc, "rmcv_tracker_create failed (a bad config, or no GPU: the device tracker has no CPU path -- Tracker.step_host has)")
+        self._h, self._lib, self.device = h, lib(), device
+        self.n_streams, self.track_cap = self.config.n_streams, self.config.track_cap
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._lib.rmcv_tracker_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _chk(self, rc):
+        if rc != 0:
+            raise RmcvError(rc, self._lib.rmcv_tracker_last_error(self._h).decode())
+
+    def reset(self):
+        """all lists empty, status cleared"""
+        self._chk(self._lib.rmcv_tracker_reset(self._h))
+
+    def set_origins(self, origins):
+        """the initial requested window origins: (n_streams, 2) int32 (x, y)"""
+        o = np.ascontiguousarray(origins, np.int32).reshape(-1, 2)
+        assert len(o) == self.n_streams
+        self._chk(self._lib.rmcv_tracker_set_origins(self._h, ptr(o)))
+
+    def device_origins(self):
+        """device pointer (int) of the requested origins: what Context.set_windows / Pipeline.submit(windows=) borrow"""
+        d = C.c_void_p()
+        self._chk(self._lib.rmcv_tracker_device_origins(self._h, C.byref(d)))
+        return d.value
+
+    def counts(self):
+        """(n_tracking int32[n_streams], status int32[n_streams]); synchronous"""
+        n, st = np.zeros(self.n_streams, np.int32), np.zeros(self.n_streams, np.int32)
+        self._chk(self._lib.rmcv_tracker_counts(self._h, ptr(n), ptr(st), self.n_streams))
+        return n, st
+
+    def get(self, stream):
+        """(TRACK[n], last vertices float32 (n, 4, 2), (x, y) requested origin) of one stream; synchronous"""
+        tr, side = np.zeros(self.track_cap, TRACK), np.zeros((self.track_cap, 4, 2), np.float32)
+        n, o = C.c_int32(0), np.zeros(1, POINT)
+        self._chk(self._lib.rmcv_tracker_get(self._h, int(stream), ptr(tr), self.track_cap, C.byref(n), ptr(side), ptr(o)))
+        return tr[:n.value].copy(), side[:n.value].copy(), (int(o[0]["x"]), int(o[0]["y"]))
+
+    @staticmethod
+    def step_host(config, tracks, last_vertices, status, origin, armours, identities=None, positions=None, eff=(0, 0), timestamp=0):
+        """rmcv_tracker_step_host: one stream's step on the CPU.  tracks TRACK[n], last_vertices (n, 4, 2), armours ARMOUR[k] in window
+        coordinates with effective origin `eff`, identities int32[k] | None, positions (k, 3) | None.
+        Returns (tracks, last_vertices, status, (x, y) origin)."""
+        cap = config.track_cap
+        tr, side = np.zeros(cap, TRACK), np.zeros((cap, 4, 2), np.float32)
+        n = len(tracks)
+        if n:
+            tr[:n] = tracks
+            side[:n] = last_vertices
+        a = np.ascontiguousarray(armours, ARMOUR)
+        ids = None if identities is None else np.ascontiguousarray(identities, np.int32)
+        pos = None if positions is None else np.ascontiguousarray(positions, np.float64).reshape(-1, 3)
+        assert (ids is None or len(ids) == len(a)) and (pos is None or len(pos) == len(a))
+        nt, st, o = C.c_int32(n), C.c_int32(int(status)), np.zeros(1, POINT)
+        o[0] = (int(origin[0]), int(origin[1]))
+        rc = lib().rmcv_tracker_step_host(C.byref(config), ptr(tr), ptr(side), C.byref(nt), C.byref(st), ptr(o), ptr(a) if len(a) else None, len(a),
+                                          ptr(ids) if ids is not None and len(a) else None, ptr(pos) if pos is not None and len(a) else None,
+                                          int(eff[0]), int(eff[1]), C.c_int64(int(timestamp)))
+        if rc != 0:
+            raise RmcvError(rc, "rmcv_tracker_step_host: bad argument")
+        return tr[:nt.value].copy(), side[:nt.value].copy(), st.value, (int(o[0]["x"]), int(o[0]["y"]))
