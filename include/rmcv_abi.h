@@ -293,6 +293,10 @@ int  rmcv_ctx_get_enhance(const rmcv_ctx* ctx, int32_t* on, float* max_gain, flo
 /* launches of k_binary_ws (RMCV_OPT_PIXEL_SHAPE 1) by this process so far: a diagnostic -- an option that is set but whose
  * conditions a batch does not meet falls back to k_binary silently (tests/test_gpu_pixel_shape.py) */
 int64_t rmcv_pixel_ws_launches(void);
+/* ... and those of them that stored the byte image in DELTA mode: only the 64-byte words that are non-zero now or were when the same
+ * context wrote its image last (a context remembers, per row, which words of its image are non-zero; k_binary_ws alone keeps that
+ * record, any other writer of the image drops it, and the next k_binary_ws launch stores every byte again).  A diagnostic, like the above. */
+int64_t rmcv_pixel_image_delta_launches(void);
 /* every device buffer of a context lies between two 4 KiB guard zones holding a fixed pattern: count the damaged ones (0 in a
  * correct build; rmcv_last_error names the first).  Synchronises the context.  A test/diagnosis hook (tests/test_gpu_canary.py). */
 int  rmcv_ctx_check_guards(rmcv_ctx* ctx, int32_t* n_damaged);

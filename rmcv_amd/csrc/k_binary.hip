@@ -39,6 +39,8 @@ namespace rmcv {
 
 static std::atomic<int64_t> g_ws_launches{0};
 int64_t pixel_ws_launches() { return g_ws_launches.load(std::memory_order_relaxed); }
+static std::atomic<int64_t> g_image_delta_launches{0};
+int64_t pixel_image_delta_launches() { return g_image_delta_launches.load(std::memory_order_relaxed); }
 #define K1_LAUNCH_T launch_binary_t
 #define K1_EXTRA
 #include "k_binary_launch.inc"
@@ -58,18 +60,27 @@ bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound, int pixel_ws)
     return g.input_format == RMCV_INPUT_BGR && !g.enhance && !g.win && pixel_ws && linear && lower_bound > 0 && n_blocks * 2 > n_cu && planes_ws <= 60 * 1024 && n_blocks >= n_cu;
 }
 
-hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s)
+hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s,
+                         ImageState* img)
 {
-    // a Bayer mosaic (RMCV_OPT_INPUT_FORMAT): its own kernel, never k_binary_ws (k_binary_bayer.hip)
-    if (g.input_format != RMCV_INPUT_BGR) return launch_binary_bayer(g, b, camp, lower_bound, morph, image, s);
-    // through the frames' gamma tables (RMCV_OPT_ENHANCE): the same kernel with a lookup in its compare (k_binary_enh.hip)
-    if (g.enhance) return launch_binary_enh(g, b, camp, lower_bound, morph, image, plan, s);
-    // a window of every frame (rmcv_batch_set_windows): the same kernel reading from the frames' effective origins (k_binary_win.hip)
-    if (g.win) return launch_binary_win(g, b, camp, lower_bound, morph, image, plan, s);
+    if (g.input_format != RMCV_INPUT_BGR || g.enhance || g.win) {
+        // these kernels store every byte of the image and know nothing of its mask (image_plan.h: IMAGE_KERNEL_OTHER)
+        const ImageLaunch l = {IMAGE_KERNEL_OTHER, image, g.w, g.h, g.ww, g.n_frames};
+        const ImageState before = img ? *img : IMAGE_STATE_UNKNOWN;
+        if (img) *img = image_step(before, l, false).next;
+        // a Bayer mosaic (RMCV_OPT_INPUT_FORMAT): its own kernel, never k_binary_ws (k_binary_bayer.hip)
+        // through the frames' gamma tables (RMCV_OPT_ENHANCE): the same kernel with a lookup in its compare (k_binary_enh.hip)
+        // a window of every frame (rmcv_batch_set_windows): the same kernel reading from the frames' effective origins (k_binary_win.hip)
+        const hipError_t e = g.input_format != RMCV_INPUT_BGR ? launch_binary_bayer(g, b, camp, lower_bound, morph, image, s)
+                             : g.enhance                      ? launch_binary_enh(g, b, camp, lower_bound, morph, image, plan, s)
+                                                              : launch_binary_win(g, b, camp, lower_bound, morph, image, plan, s);
+        if (img && e == hipSuccess) *img = image_step(before, l, true).next;
+        return e;
+    }
     // imgproc.cpp:56-65: GUIDELIGHT G-R; BLUE B-R; everything else (RED, NEUTRAL) R-B.  BGR byte order.
-    if (camp == RMCV_CAMP_GUIDELIGHT) return launch_binary_t<1, 2>(g, b, lower_bound, morph, image, plan, s);
-    if (camp == RMCV_CAMP_BLUE) return launch_binary_t<0, 2>(g, b, lower_bound, morph, image, plan, s);
-    return launch_binary_t<2, 0>(g, b, lower_bound, morph, image, plan, s);
+    if (camp == RMCV_CAMP_GUIDELIGHT) return launch_binary_t<1, 2>(g, b, lower_bound, morph, image, plan, s, img);
+    if (camp == RMCV_CAMP_BLUE) return launch_binary_t<0, 2>(g, b, lower_bound, morph, image, plan, s, img);
+    return launch_binary_t<2, 0>(g, b, lower_bound, morph, image, plan, s, img);
 }
 
 // binary (0 / non-zero bytes) -> padded bit plane; used when a caller hands in its own binary image
@@ -90,6 +101,7 @@ __global__ void k_pack_bits(const uint8_t* __restrict__ binary, int w, int h, in
     if (word && k < 32) atomicOr(&rowmask[(int64_t)f * h + y], 1u << k); // caller zeroes the masks first
 }
 
+// (the image then is the caller's: whoever fills Bufs::binary for this sets the context's ImageState to IMAGE_STATE_UNKNOWN)
 hipError_t launch_pack_bits(const Geom& g, const Bufs& b, hipStream_t s)
 {
     const int items = g.h * g.ww;

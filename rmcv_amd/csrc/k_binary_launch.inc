@@ -2,12 +2,14 @@
 // 4 GiB, the persistent grid.  The includer defines K1_LAUNCH_T and K1_EXTRA (trailing kernel arguments); with K1_ENH 0 it has also
 // included k_binary_ws.inc and defined g_ws_launches.  K1_WIN (k_binary_win.hip): window rows are not contiguous -- never the linear
 // loader, never k_binary_ws; FAST 2 is not even instantiated.
+// img (nullable; the K1_ENH 0, K1_WIN 0 build alone reads it): what the context knows about its byte image (image_plan.h).  It decides how
+// k_binary_ws stores the image and is rewritten once every chunk has been enqueued -- or left UNKNOWN by an error.
 #ifndef K1_WIN
 #define K1_WIN 0
 #endif
 template <int CA, int CB>
 static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int morph, bool image, const RunPlan& plan,
-                                  hipStream_t s)
+                                  hipStream_t s, ImageState* img = nullptr)
 {
     const int strips = (g.h + SR - 1) / SR;
     int lb = lower_bound, all_pass = 0;
@@ -31,6 +33,14 @@ static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int
     // persistent grid: RMCV_OPT_PIXEL_GROUPS workgroups per CU: alone the kernel is equally fast with 2 and 3 and slower with 4 and
     // more; 2 leaves room on every CU for the kernels of the other batches in flight
     const int bpc = plan.pixel_groups;
+#if !K1_ENH && !K1_WIN
+    // the chunks of a batch share one state: the mode from what held before the batch, the next state from what all of them ran as
+    const ImageState img_before = img ? *img : IMAGE_STATE_UNKNOWN;
+    const ImageLaunch img_launch = {IMAGE_KERNEL_WS, image, g.w, g.h, g.ww, g.n_frames};
+    const ImageMode img_mode = image_step(img_before, img_launch, true).mode;
+    bool all_ws = true;
+    if (img) *img = image_step(img_before, img_launch, false).next; // (until every chunk is enqueued: what an error return leaves behind)
+#endif
     for (int f0 = 0; f0 < g.n_frames; f0 += chunk) {
         const int nf = std::min(chunk, g.n_frames - f0);
         const int n_blocks = nf * strips;
@@ -74,17 +84,21 @@ static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int
             ka.frames = frames; ka.frame_pitch = g.frame_pitch; ka.stride = g.stride; ka.n_frames = nf; ka.w = g.w; ka.h = g.h; ka.ww = g.ww;
             ka.lb = lb; ka.morph = morph; ka.binary = binary; ka.bits = bits; ka.prow = g.prow; ka.plane_pitch = g.plane_pitch;
             ka.strips = strips; ka.n_blocks = n_blocks; ka.rowmask = rowmask; ka.strip_ctr = b.strip_ctr;
+            ka.imgmask = b.imgmask + (int64_t)f0 * g.h; ka.delta = img_mode == IMAGE_DELTA;
             int grid_ws = ((g.n_cu > 0 ? g.n_cu : 256) + 7) & ~7;
             if (grid_ws > ((n_blocks + 7) & ~7)) grid_ws = (n_blocks + 7) & ~7;
             g_ws_launches.fetch_add(1, std::memory_order_relaxed);
+            if (ka.delta && binary) g_image_delta_launches.fetch_add(1, std::memory_order_relaxed);
             // (issue priority 3 for loaders and storers, the sparse kernel's own: in-process A/B against 0 / (2,1) / (3,0) / (1,1):
-            // 0.991 / 1.008 / 1.017 / 1.006 of the step)
+            // 0.991 / 1.008 / 1.017 / 1.006 of the step; again with the delta stores of the image, against (2,2) / (1,1) / (0,0): 0.988 /
+            // 0.997 / 0.999 with the pairs disagreeing in sign -- profiles/image_delta_schedule_ab.txt)
             // (in the pipeline, in-process A/B against this shape: ring of 3 items 1.005, of 4 1.005; 12 loaders + 4 storers 1.087, 10 + 4
             // 1.017, 8 + 4 1.024; loads without the nt hint 1.062)
             const hipError_t e = launch(k_binary_ws<CA, CB, WS_NL, WS_NS, WS_RING, WS_AUX, 3, 3>, dim3(grid_ws), dim3((WS_NL + WS_NS) * 64), planes_ws, s, ka);
             if (e != hipSuccess) return e;
             continue;
         }
+        all_ws = false;
 #endif
 #define RMCV_K1_LAUNCH(F)                                                                                                             \
     launch(K1_KERNEL<CA, CB, F>, dim3(grid), dim3(256), planes, s, frames, g.frame_pitch, g.stride, nf, g.w, g.h, g.ww, lb, all_pass, \
@@ -98,5 +112,8 @@ static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int
 #undef RMCV_K1_LAUNCH
         if (e != hipSuccess) return e;
     }
+#if !K1_ENH && !K1_WIN
+    if (img) *img = image_step(img_before, {all_ws ? IMAGE_KERNEL_WS : IMAGE_KERNEL_OTHER, image, g.w, g.h, g.ww, g.n_frames}, true).next;
+#endif
     return hipSuccess;
 }

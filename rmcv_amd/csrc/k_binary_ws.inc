@@ -29,12 +29,29 @@ struct K1Args {
     int strips, n_blocks;
     uint32_t* rowmask;
     int* strip_ctr;
+    uint32_t* imgmask; // [frame][h] bit k: the 64 bytes of word k of the row in `binary` may be non-zero (image_plan.h); ww <= 32
+    int delta;         // 1: `imgmask` is in force -- store only the words that are or were non-zero; 0: store every byte
 };
 
+// Lane r of storer wave sw: the image's mask of row r of the wave's rows of strip L (0: no such row, or no delta launch).  The wave asks for
+// it while it stores the strip BEFORE -- behind that strip's morphology, where the wave's registers are scarce: the answer comes from HBM,
+// beside a kernel that keeps every channel busy, and takes microseconds.  The read ahead cannot race with a write of the mask: within a
+// launch a row's mask is read and written by ONE wave (the strip's storer wave that owns the row), every strip is drawn once, and the
+// launches of one context are ordered on its streams -- the word read here was last written by an earlier launch.
 template <int NS>
-__device__ __forceinline__ void ws_store_strip(const K1Args& a, const int L, const uint64_t* __restrict__ T, uint64_t* __restrict__ Ew,
+__device__ __forceinline__ uint32_t ws_image_mask(const K1Args& a, const int L, const int sw, const int lane)
+{
+    constexpr int RPW = SR / NS;
+    if (!(a.delta && a.binary && a.ww <= 32) || L < 0) return 0u;
+    const int f = L / a.strips, y = (L - f * a.strips) * SR + sw * RPW + lane;
+    return (lane < RPW && y < a.h) ? a.imgmask[(int64_t)f * a.h + y] : 0u;
+}
+
+template <int NS>
+__device__ __forceinline__ uint32_t ws_store_strip(const K1Args& a, const int L, const uint64_t* __restrict__ T, uint64_t* __restrict__ Ew,
                                                const uint64_t* __restrict__ lut, const int sw, const int lane,
-                                               const __amdgpu_buffer_rsrc_t r_bin, const __amdgpu_buffer_rsrc_t r_plane)
+                                               const __amdgpu_buffer_rsrc_t r_bin, const __amdgpu_buffer_rsrc_t r_plane, const uint32_t m_old,
+                                                   const int L_next)
 {
     constexpr int RPW = SR / NS; // output rows per storer wave
     static_assert(RPW >= 2 && RPW % 2 == 0, "a lane produces a pair of rows");
@@ -42,10 +59,17 @@ __device__ __forceinline__ void ws_store_strip(const K1Args& a, const int L, con
     const int f = L / a.strips, strip = L - f * a.strips;
     const int y0 = strip * SR;
     const int s0 = sw * RPW; // this wave's first row of the strip
-    if (y0 + s0 >= h) return; // (wave-uniform) its rows lie below the image
+    if (y0 + s0 >= h) return ws_image_mask<NS>(a, L_next, sw, lane); // (wave-uniform) its rows lie below the image
     const uint32_t plane_base = (uint32_t)((int64_t)f * a.plane_pitch);
     const int n_task = (RPW / 2) * ww; // (row pair, word)
     const uint32_t r_ww = (uint32_t)((0x100000000ull + ww - 1) / ww);
+    // m_new (lane r: the new mask of row r) is set on exactly one of the two row-mask paths below for every ww <= 32: in the pass itself
+    // when the wave's tasks fit one pass (n_task <= 64), behind the passes otherwise.  (With RPW = 4 the second never runs: n_task = 2 ww.)
+    // m_old: what the image holds in this wave's rows (lane r: row r; ws_image_mask, asked for a strip ahead).  Returns the next strip's.
+    const bool masked = a.binary && ww <= 32, delta = masked && a.delta;
+    const bool my_row = lane < RPW && y0 + s0 + lane < h;
+    uint32_t* const im = a.imgmask + ((int64_t)f * h + y0 + s0 + lane);
+    uint32_t m_new = 0;
     for (int t0 = 0; t0 < n_task; t0 += 64) {
         const int t = t0 + lane;
         const bool on = t < n_task;
@@ -133,6 +157,7 @@ __device__ __forceinline__ void ws_store_strip(const K1Args& a, const int L, con
                 const int pr = lane >> 1;
                 const uint64_t b = (lane & 1) ? b1 : b0;
                 const uint32_t m = (uint32_t)(b >> __umul24(pr, ww)) & (ww == 32 ? 0xFFFFFFFFu : ((1u << ww) - 1u));
+                m_new = m;
 #ifndef RMCV_K1_NOROWMASK
                 if (y0 + s0 + lane < h) a.rowmask[(int64_t)f * h + y0 + s0 + lane] = m;
 #endif
@@ -148,17 +173,32 @@ __device__ __forceinline__ void ws_store_strip(const K1Args& a, const int L, con
             uint32_t m = 0;
             for (int k = 0; k < ww; k++) m |= (uint32_t)(Ew[__umul24(lane, ww) + k] != 0) << k;
             a.rowmask[(int64_t)f * h + y0 + s0 + lane] = m;
+            m_new = m;
         }
     }
+    const uint32_t m_ahead = ws_image_mask<NS>(a, L_next, sw, lane);
     if (a.binary) { // RMCV_STAGE_NO_IMAGE: the 0/255 byte image is not wanted
+        // Delta stores: a 64-byte word of the image that is zero and was zero when this context wrote it last is not stored again (LED
+        // bars on a dark field: 1.5 % of the words are not zero).  `keep` (lane r: row r) = the words to store; the mask then says what
+        // the image holds now.  Nothing to keep in the wave's rows: no LUT work, no pass over the items.
+        // (the unit is ONE aligned 64-byte word: aligned 128-byte pairs measured 4 % worse at C3, profiles/image_delta_schedule_ab.txt)
+        const uint32_t keep = delta ? (m_old | m_new) : 0xFFFFFFFFu;
+        if (masked && my_row && (!delta || m_new != m_old)) *im = m_new;
+        if (delta && __builtin_amdgcn_ballot_w64(my_row && keep != 0) == 0) return m_ahead;
         // w % 64 == 0: the wave's rows are ONE run of 16-pixel items both in its LDS words and in the byte image
         const int n_valid = min(RPW, h - (y0 + s0)) * ww * 4;
         const uint16_t* R16 = reinterpret_cast<const uint16_t*>(Ew);
         const uint32_t out0 = (uint32_t)((int64_t)f * w * h) + (uint32_t)(y0 + s0) * (uint32_t)w;
         for (int b = 0; b < n_valid; b += 64) {
             const int it = b + lane;
-            const bool ok = it < n_valid;
-            const uint32_t m = R16[ok ? it : 0];
+            bool ok = it < n_valid;
+            if (delta) { // (wave-uniform)
+                const int wd = ok ? it >> 2 : 0, r = div_r(wd, r_ww), k = wd - r * ww; // the item's row of the wave and word of the row
+                const uint32_t kr = (uint32_t)__shfl((int)keep, r);
+                ok = ok && ((kr >> k) & 1u);
+                if (__builtin_amdgcn_ballot_w64(ok) == 0) continue; // none of these 64 items is kept
+            }
+            const uint32_t m = R16[it < n_valid ? it : 0];
             const uint64_t lo = lut[m & 0xFF], hi = lut[m >> 8];
             const u32x4v o = {(uint32_t)lo, (uint32_t)(lo >> 32), (uint32_t)hi, (uint32_t)(hi >> 32)};
 #ifdef RMCV_K1_NOSTORE
@@ -169,6 +209,7 @@ __device__ __forceinline__ void ws_store_strip(const K1Args& a, const int L, con
             __builtin_amdgcn_raw_buffer_store_b128(o, r_bin, off, 0, RMCV_K1_STAUX);
         }
     }
+    return m_ahead;
 }
 
 // The loaders never drain: every loader wave keeps a RING of R items (4 dwordx3 loads each) in flight, across item, strip and
@@ -312,6 +353,7 @@ __global__ __launch_bounds__((NL + NS) * 64, 6) void k_binary_ws(const K1Args a)
     } else {
         // ------------------------------------------------------------------------------------------------ storer waves
         if (PRIO_S > 0) __builtin_amdgcn_s_setprio(PRIO_S);
+        uint32_t m_ahead = ws_image_mask<NS>(a, strip_of(s_L[0]), wave - NL, lane); // the image's mask of the strip the loaders are filling
         for (int p = 0;; p++) {
             if (p > 0 && strip_of(s_L[(p - 1) & 3]) < 0) break;
             // the index for strip p+2 is drawn HERE, by a storer: waiting for an atomic's answer means waiting for every older load of
@@ -319,7 +361,7 @@ __global__ __launch_bounds__((NL + NS) * 64, 6) void k_binary_ws(const K1Args a)
             if (tid == NL * 64) s_L[(p + 2) & 3] = atomicAdd(head, 1);
             if (p > 0) {
                 const int Lp = strip_of(s_L[(p - 1) & 3]);
-                ws_store_strip<NS>(a, Lp, ((p - 1) & 1) ? T1 : T0, Ew, s_lut, wave - NL, lane, r_bin, r_plane);
+                m_ahead = ws_store_strip<NS>(a, Lp, ((p - 1) & 1) ? T1 : T0, Ew, s_lut, wave - NL, lane, r_bin, r_plane, m_ahead, strip_of(s_L[p & 3]));
             }
             __syncthreads();
         }

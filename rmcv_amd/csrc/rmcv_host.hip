@@ -35,6 +35,7 @@ struct rmcv_ctx {
     int32_t* pack_offs = nullptr;
     hipStream_t last_stream = nullptr;
     int geom_w = -1, geom_h = -1; // geometry the planes were zeroed for
+    ImageState image = IMAGE_STATE_UNKNOWN; // what Bufs::imgmask is known to say about Bufs::binary (image_plan.h); every launch_binary keeps it
     int order_n = -1, order_h = -1; // (n_frames, h) the frame order on the device was computed for
     hipEvent_t ev_order = nullptr; // recorded behind the work enqueued last: a call on ANOTHER stream first waits for it
     bool order_pending = false;
@@ -227,6 +228,7 @@ extern "C" {
 
 int rmcv_abi_version(void) { return RMCV_ABI_VERSION; }
 int64_t rmcv_pixel_ws_launches(void) { return pixel_ws_launches(); }
+int64_t rmcv_pixel_image_delta_launches(void) { return pixel_image_delta_launches(); }
 
 void rmcv_default_params(rmcv_params* p)
 { // the literals of executable/main.cpp:172-176
@@ -375,6 +377,7 @@ int rmcv_ctx_create(int device, const rmcv_limits* limits, rmcv_ctx** out)
     if (e == hipSuccess) e = dalloc(c, &b.enh_m, 256 * F);
     if (e == hipSuccess) e = dalloc(c, &b.win_eff, F);
     if (e == hipSuccess) e = dalloc(c, &c->win_own, F);
+    if (e == hipSuccess) e = dalloc(c, &b.imgmask, F * d.max_height); // (last: every other buffer stays where it was before there was a mask)
     if (e == hipSuccess) {
         hipMemset(b.strip_ctr, 0, 9 * CTR_STRIDE * sizeof(int));
         hipMemset(b.n_contours, 0, F * 4);
@@ -710,6 +713,7 @@ static int set_extent(rmcv_ctx* c, int w, int h, hipStream_t as)
         HIPCHK(c, hipMemsetAsync(c->bufs.neg, 0, (size_t)c->lim.max_frames * plane * 8, s), "memset planes");
         c->geom_w = w;
         c->geom_h = h;
+        c->image = IMAGE_STATE_UNKNOWN; // rows and frames of the byte image and of its mask now start elsewhere
     }
     if (order_change) {
         const int strips = (h + STRIP_ROWS - 1) / STRIP_ROWS;
@@ -772,7 +776,7 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
         if (g.enhance) HIPCHK(c, launch_enhance_tables(g, b, p->lower_bound, s), "k_frame_sums + k_enhance_table");
         // windows: the effective origins first, at RUN time too (the requests may be a tracker's, rewritten on the device since they were set)
         if (g.win) HIPCHK(c, launch_window_origins(g, b, s), "k_window_origins");
-        HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, !(stages & RMCV_STAGE_NO_IMAGE), plan, s),
+        HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, !(stages & RMCV_STAGE_NO_IMAGE), plan, s, &c->image),
                g.input_format ? "k_binary_bayer" : (g.enhance ? "k_binary_enh" : (g.win ? "k_binary_win" : "k_binary")));
     }
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
@@ -1535,7 +1539,7 @@ static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int
         c->test_delay_us = 0;
     }
     if (g.enhance) HIPCHK(c, launch_enhance_tables(g, b, lower_bound, s), "k_frame_sums + k_enhance_table"); // RMCV_OPT_ENHANCE: the frame is read through its table
-    HIPCHK(c, launch_binary(g, b, camp, lower_bound, morph, binary_out != nullptr, plan, s), g.input_format ? "k_binary_bayer" : (g.enhance ? "k_binary_enh" : "k_binary"));
+    HIPCHK(c, launch_binary(g, b, camp, lower_bound, morph, binary_out != nullptr, plan, s, &c->image), g.input_format ? "k_binary_bayer" : (g.enhance ? "k_binary_enh" : "k_binary"));
     if (binary_out) HIPCHK(c, hipEventRecord(c->ev_fork, s), "image download: mark");
     // running ahead with both parameter sets known: the frame's whole sparse part is ONE kernel (the fused per-frame kernel of
     // the batch path: findContours, fits and pairing back to back), not three

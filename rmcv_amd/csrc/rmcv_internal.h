@@ -7,6 +7,7 @@
 #include <utility>
 
 #include "../../include/rmcv_abi.h"
+#include "image_plan.h"
 #include "sparse_plan.h"
 
 namespace rmcv {
@@ -77,6 +78,8 @@ struct Bufs {
     int* strip_ctr;        // [8] per-XCD strip queue heads of k_binary + [8] = workgroups of the launch that have drawn their
                            // last strip; the last one to leave zeroes all nine, so every launch starts from 0 with no host mirror
     uint32_t* rowmask;     // [frame][h]  bit k: word k of row y of F is non-zero (rows are h apart; k_binary writes them)
+    uint32_t* imgmask;     // [frame][h]  bit k: the 64 bytes of word k of row y in `binary` may be non-zero -- the image's CONTENTS, not the
+                           // last run's result; in force while the context's ImageState says so (image_plan.h; k_binary_ws keeps it)
     uint64_t* lab;         // [frame] padded plane: pixel was visited by a border trace
     uint64_t* neg;         // [frame] padded plane: ... and got the negative ("right exit") label
     // contours in DISCOVERY order; cv::findContours returns them reversed (oracle/rmcv_oracle.c)
@@ -174,6 +177,7 @@ inline hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds
 }
 
 int64_t pixel_ws_launches(); // launches of k_binary_ws by this process (rmcv_pixel_ws_launches)
+int64_t pixel_image_delta_launches(); // ... of them, those that stored the byte image in delta mode (rmcv_pixel_image_delta_launches)
 // kernel launchers (each enqueues on `s` and returns the launch error)
 hipError_t launch_match(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, const rmcv_legacy_params& lp,
                         int mode, bool with_frames, bool pairs, hipStream_t s);
@@ -182,7 +186,9 @@ hipError_t launch_match(const Geom& g, const Bufs& b, const Limits& lim, const r
 hipError_t launch_sparse(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, bool pairs, bool identity, const RunPlan& plan,
                          hipStream_t s, bool* lean = nullptr);
 hipError_t launch_pnp(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s);
-hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s);
+// img: the context's knowledge of its byte image, read for the store mode and rewritten for what this launch leaves (image_plan.h)
+hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s,
+                         ImageState* img);
 bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound, int pixel_ws); // the batch will run as one launch of k_binary_ws with a workgroup on every CU
 // the pixel stage of a Bayer batch (Geom::input_format != 0; k_binary_bayer.hip); launch_binary hands such batches to it
 hipError_t launch_binary_bayer(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, hipStream_t s);
