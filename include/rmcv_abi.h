@@ -642,6 +642,99 @@ int  rmcv_tracker_step_host(const rmcv_tracker_config* cfg, rmcv_track* tracks, 
                             rmcv_point* origin, const rmcv_armour* armours, int n_obs, const int32_t* identities, const double* positions,
                             int x_eff, int y_eff, int64_t timestamp);
 
+/* ---- aiming: rm::ProjectileAngle / SolveGEA / DeltaHeight / Distance (src/mobility.cpp:36-82,127-164) ---------------
+ * Host functions that need no device, no context and no tracker: the reference's statements one by one, evaluated left to right as
+ * written, the transcendentals from the library's pinned functions (the same bits on the host and on the device), sqrt IEEE.
+ * A NaN result is THE quiet NaN 0x7FF8000000000000, here and in every rmcv_aim (the sign of a computed NaN is the machine's).
+ * Lengths of a translation vector are cm, v0 m/s, g m/s^2, angles in: rad, angles out (pitch, yaw): DEGREES, times s -- the reference's.
+ * Mirrored as written: COMPENSATE_CLASSIC takes cos() of the launch angle it has just converted to degrees
+ * (mobility.cpp:147,150), and SolveGEA's `h` -- documented in metres -- is divided by 100 like a length in cm (:145,147). */
+#define RMCV_COMPENSATE_NONE 0     /* rm::COMPENSATE_NONE    (include/mobility.h:20) */
+#define RMCV_COMPENSATE_CLASSIC 1  /* rm::COMPENSATE_CLASSIC */
+#define RMCV_COMPENSATE_NI 2       /* rm::COMPENSATE_NI: the reference returns NAN before it writes anything (mobility.cpp:153) */
+/* the launch angle (rad) of the root with the smaller magnitude; NAN without a real root */
+double rmcv_projectile_angle(double v0, double g, double d, double h);
+/* returns the flight time; gea_out = {pitch, yaw}, untouched for RMCV_COMPENSATE_NI (a mode that is none of the three falls through the
+ * reference's switch with pitch = time = 0, and does here) */
+double rmcv_solve_gea(const double tvec[3], double g, double v0, double h, float offset_x, float offset_y, double angle_offset, int mode,
+                      double gea_out[2]);
+double rmcv_delta_height(const double tvec[3], double motor_angle, float offset_y, double angle_offset);
+double rmcv_distance(const double tvec[3]);
+/* a rigid 4x4 (row-major) [R t; 0 1] -> [R^T  -R^T t; 0 1]; each entry of R^T t is summed left to right.  out == m allowed. */
+int    rmcv_rigid_inverse(const double m[16], double out[16]);
+
+/* ---- device-resident aiming: one rmcv_aim per stream behind the tracker's step, without the host ---------------------
+ * With aiming on, every step of the tracker (rmcv_batch_track, rmcv_pipeline_submit_tracked) is followed, on the same stream and in front
+ * of the tracker's event, by an AIM STEP with `now` = the step's timestamp; rmcv_tracker_aim enqueues the aim step alone.  Per stream:
+ *  1. candidates: the tracks j of the current list with lost_count <= max_lost whose identity is allowed -- identity i in 0..30: bit i of
+ *     identity_mask; any other identity (-1 included): bit 31;
+ *  2. source: initialized == 0: p = position, v = 0; else RMCV_AIM_SRC_FILTER: p = state_post[0..2], v = state_post[3..5];
+ *     RMCV_AIM_SRC_MEASUREMENT: p = measurement[0..2], v = measurement[3..5];
+ *  3. lead: dt = (double)(now - timestamp) / tick_frequency + latency_s;  q_i = p_i + v_i * dt;  cam = world2camera . [q; 1], each row
+ *     ((W0 q0 + W1 q1) + W2 q2) + W3 * 1.0;  h = height (RMCV_AIM_HEIGHT_FIXED) or rmcv_delta_height(cam, motor_angle, offset_y,
+ *     angle_offset) (RMCV_AIM_HEIGHT_DELTA);  (pitch, yaw, t) = rmcv_solve_gea(cam, ...);  then lead_iterations times: t not finite: stop;
+ *     else q = p + v * (dt + t), and cam, h and the solution again;  distance = rmcv_distance(cam);  RMCV_AIM_NO_SOLUTION when the final
+ *     pitch or t is not finite.  A NaN state (a matched update with dt = 0 makes one) runs through and comes out NaN;
+ *  4. pick: RMCV_AIM_PICK_WINDOW: the candidate with the greatest timestamp, lowest index on ties (the tracker's own window rule
+ *     restricted to candidates); RMCV_AIM_PICK_NEAREST: the smallest distance, NaN counting as +infinity, lowest index on ties;
+ *  5. record: the stream's rmcv_aim; `point` is cam of the last solution (the led target in the camera's frame, cm).  No candidate:
+ *     track = identity = -1, lost_count = 0, status = RMCV_AIM_NO_TARGET, every double +0.0.
+ * A stream with RMCV_TRACKER_OVF is aimed like any other, on the list as it stands.  The positions are in whatever frame the tracker's
+ * observations came in; world2camera brings them to the camera frame rm::SolveGEA expects (a pipeline's RMCV_STAGE_POSE has
+ * base2gripper = identity, so positions are in the gripper's frame and world2camera = rmcv_rigid_inverse(gripper2camera)).
+ * Aiming reads the tracker's state and never writes it.  Every byte of every record equals tests/aim_ref.c. */
+#define RMCV_AIM_NO_TARGET 1
+#define RMCV_AIM_NO_SOLUTION 2
+#define RMCV_AIM_HEIGHT_FIXED 0
+#define RMCV_AIM_HEIGHT_DELTA 1
+#define RMCV_AIM_SRC_FILTER 0
+#define RMCV_AIM_SRC_MEASUREMENT 1
+#define RMCV_AIM_PICK_WINDOW 0
+#define RMCV_AIM_PICK_NEAREST 1
+typedef struct {
+    double  g, v0, height;       /* m/s^2, m/s, cm   (9.8, 15, 0: the project's defaults -- the reference gives none) */
+    float   offset_x, offset_y;  /* cm  (0, 0: mobility.h:56,97) */
+    double  angle_offset;        /* rad (0) */
+    double  latency_s;           /* (0) */
+    int32_t mode;                /* RMCV_COMPENSATE_NONE (mobility.h:97); RMCV_COMPENSATE_NI is refused */
+    int32_t height_mode;         /* RMCV_AIM_HEIGHT_FIXED */
+    int32_t source;              /* RMCV_AIM_SRC_FILTER */
+    int32_t pick;                /* RMCV_AIM_PICK_WINDOW */
+    int32_t lead_iterations;     /* 0 .. 4 (1) */
+    int32_t max_lost;            /* (25) */
+    int32_t overloads;           /* bit 0 as bit 0 of RMCV_OPT_OVERLOADS: the unqualified abs(double) of mobility.cpp:74,150 is int abs(int),
+                                    the argument truncated toward zero (a NaN argument: 0); 0: fabs (0) */
+    uint32_t identity_mask;      /* (0xFFFFFFFF) */
+} rmcv_aim_config;               /* 80 bytes */
+typedef struct { double world2camera[16]; double motor_angle; } rmcv_aim_input;   /* per stream, 136 bytes; (identity, 0) */
+typedef struct {
+    int32_t track, identity, lost_count, status;   /* index in the stream's current list; RMCV_AIM_* */
+    double  pitch, yaw, flight_time, distance, point[3];
+} rmcv_aim;                                        /* 72 bytes */
+void rmcv_default_aim_config(rmcv_aim_config* c);
+/* aiming on (cfg) or off (NULL: no aim kernel is launched; the records stay as they are).  Waits for the step in flight; allocates on first
+ * use.  RMCV_ERR_BAD_ARG with a message: a number not finite, an enum out of range, mode == RMCV_COMPENSATE_NI, lead_iterations outside
+ * 0..4, max_lost < 0. */
+int  rmcv_tracker_set_aim(rmcv_tracker* trk, const rmcv_aim_config* cfg);
+/* n_streams inputs, copied (NULL: the defaults).  Waits for the step in flight. */
+int  rmcv_tracker_set_aim_inputs(rmcv_tracker* trk, const rmcv_aim_input* inputs);
+/* device view of the inputs (n_streams rmcv_aim_input): the caller may write them on its own stream before a submit.  Owned by the tracker. */
+int  rmcv_tracker_device_aim_inputs(rmcv_tracker* trk, void** d_inputs);
+/* enqueue the aim step alone on `hip_stream` (NULL: the null stream), on the lists as they are; never synchronises.  RMCV_ERR_BAD_ARG when
+ * aiming is off. */
+int  rmcv_tracker_aim(rmcv_tracker* trk, int64_t now, void* hip_stream);
+/* the first min(cap, n_streams) records; synchronous (the tracker's 5 s deadline).  Zeros until the first aim step. */
+int  rmcv_tracker_get_aims(rmcv_tracker* trk, rmcv_aim* out, int cap);
+/* device view of the records (n_streams rmcv_aim).  Owned by the tracker. */
+int  rmcv_tracker_device_aims(rmcv_tracker* trk, void** d_aims);
+/* seed or restore one stream's current list: n <= track_cap tracks (RMCV_ERR_CAPACITY beyond) and their side records ([n][4][2] floats;
+ * NULL: zeros).  Synchronous; status and origin stay as they are. */
+int  rmcv_tracker_put(rmcv_tracker* trk, int stream, const rmcv_track* tracks, int n, const float* last_vertices);
+/* the aim step for ONE stream on the CPU (no device; the same source the kernel is compiled from): n <= RMCV_TRACKER_MAX_CAP tracks,
+ * input NULL: the defaults.  RMCV_ERR_BAD_ARG: what rmcv_tracker_set_aim refuses, or tick_frequency not finite and positive. */
+int  rmcv_aim_step_host(const rmcv_aim_config* cfg, double tick_frequency, const rmcv_track* tracks, int n, const rmcv_aim_input* input,
+                        int64_t now, rmcv_aim* out);
+
 /* ---- pipelined batches: the process loop behind the ABI ------------------------------------------------------------------------
  * The reference's process_function is a `while (1)` that takes the newest camera frame, runs the three detection calls and hands
  * the armours on (executable/main.cpp:163-209).  Its batch form on one MI355X: `depth` batches in flight, each in a context of its

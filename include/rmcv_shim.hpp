@@ -20,12 +20,14 @@
 // rm::CalcGamma and rm::AutoEnhance (include/imgproc.h:23, 35) are here too, and one more addition: rm::extract_color_enhanced, the two
 // of rm::AutoEnhance + rm::extract_color fused (the enhanced frame is never written).
 // rm::utils::GetROI (include/core.h:142-147), the reference's tracked-ROI helper, is here as well (where the cv:: headers know cv::Size).
+// rm::ProjectileAngle / SolveGEA / DeltaHeight / Distance (include/mobility.h) too, behind the reference's mobility.h.
 // The legacy names of the north star are aliased at the bottom (docs/core_8h_source.html:101,114).
 //
 // Every signature mentions cv:: types, so this header only compiles where OpenCV headers exist.
 #pragma once
 #if __has_include(<opencv2/opencv.hpp>)
 
+#include <cmath>
 #include <cstdlib>
 #include <stdexcept>
 #include <string>
@@ -363,6 +365,43 @@ RMCV_SHIM_LINKAGE cv::Rect GetROI(cv::Point2f* imagePoints, int pointsCount, flo
     return GetROI(imagePoints, pointsCount, cv::Size2f(scaleFactor, scaleFactor), frameSize, previous); // src/core.cpp:221
 }
 } // namespace utils
+#endif
+
+// ---- rm::ProjectileAngle / SolveGEA / DeltaHeight / Distance (include/mobility.h:55-62,75,95-97; bodies src/mobility.cpp:36-82,127-164)
+// over the ABI's host functions, which restate the bodies statement by statement (no device, no context).  rm::CompensateMode and the
+// default arguments live on the reference's declarations.  A translation vector that is not a cv::Mat gives NAN, as in the reference.
+// rm::SolveGEA creates the 2x1 CV_64F output (the reference's create({2, 1}, _OutputArray::MAT) passes the kind flag where the TYPE belongs
+// and gets two bytes for its two doubles); COMPENSATE_NI returns NAN before the output exists, as written.
+// (Guarded: only behind the reference's mobility.h, and where the cv:: headers in use know _InputArray::kind() -- real OpenCV, or a
+// stand-in that says so.)
+#if defined(RMCV_MOBILITY_H) && (defined(CV_VERSION) || defined(RMCV_CV_HAS_ARRAY_KINDS))
+RMCV_SHIM_LINKAGE double ProjectileAngle(const double v0, const double g, const double d, const double h) { return rmcv_projectile_angle(v0, g, d, h); }
+RMCV_SHIM_LINKAGE double DeltaHeight(cv::InputArray translationVector, const double motorAngle, const cv::Point2f& offset, const double angleOffset)
+{
+    if (translationVector.kind() != cv::_InputArray::MAT) return NAN;
+    cv::Mat tvecs = translationVector.getMat();
+    return rmcv_delta_height(tvecs.ptr<double>(0), motorAngle, offset.y, angleOffset);
+}
+RMCV_SHIM_LINKAGE double Distance(cv::InputArray translationVector)
+{
+    if (translationVector.kind() != cv::_InputArray::MAT) return NAN;
+    cv::Mat tvecs = translationVector.getMat();
+    return rmcv_distance(tvecs.ptr<double>(0));
+}
+RMCV_SHIM_LINKAGE double SolveGEA(cv::InputArray translationVector, cv::OutputArray gimbalErrorAngle, const double g, const double v0, const double h,
+                                  const cv::Point2f& offset, const double angleOffset, const rm::CompensateMode mode)
+{
+    if (translationVector.kind() != cv::_InputArray::MAT) return NAN;
+    cv::Mat tvecs = translationVector.getMat();
+    double gea[2] = {0, 0};
+    const double t = rmcv_solve_gea(tvecs.ptr<double>(0), g, v0, h, offset.x, offset.y, angleOffset, static_cast<int>(mode), gea);
+    if (mode == rm::COMPENSATE_NI) return t;
+    cv::Mat out(2, 1, CV_64F);
+    out.ptr<double>(0)[0] = gea[0];
+    out.ptr<double>(1)[0] = gea[1];
+    gimbalErrorAngle.assign(out);
+    return t;
+}
 #endif
 
 using LightBlob = lightblob; // pre-2024 API names used by the north star

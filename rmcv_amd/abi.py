@@ -25,6 +25,10 @@ TRACK = np.dtype([("armour", ARMOUR), ("timestamp", "<i8"), ("lost_count", "<i4"
                   ("measurement_noise_cov", "<f8", (6, 6)), ("error_cov_pre", "<f8", (6, 6)), ("error_cov_post", "<f8", (6, 6)),
                   ("gain", "<f8", (6, 6))])  # rmcv_track
 assert POINT.itemsize == 8 and LIGHTBLOB.itemsize == 56 and ARMOUR.itemsize == 88 and TRACK.itemsize == 2552
+AIM = np.dtype([("track", "<i4"), ("identity", "<i4"), ("lost_count", "<i4"), ("status", "<i4"), ("pitch", "<f8"), ("yaw", "<f8"),
+                ("flight_time", "<f8"), ("distance", "<f8"), ("point", "<f8", (3,))])  # rmcv_aim
+AIM_INPUT = np.dtype([("world2camera", "<f8", (4, 4)), ("motor_angle", "<f8")])  # rmcv_aim_input
+assert AIM.itemsize == 72 and AIM_INPUT.itemsize == 136
 
 OK, ERR_BAD_ARG, ERR_CAPACITY, ERR_NOMEM, ERR_HIP, ERR_NO_DEVICE, ERR_RCCL, ERR_TIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7
 COMM_ID_BYTES = 128
@@ -57,6 +61,11 @@ OPT_ENHANCE = 23
 ENHANCE_MAX_GAIN, ENHANCE_MIN_GAIN = 100.0, 50.0
 STAGE_BINARY, STAGE_CONTOURS, STAGE_BLOBS, STAGE_ARMOURS, STAGE_ALL, STAGE_IDENTITY, STAGE_POSE, STAGE_NO_IMAGE = 1, 2, 4, 8, 15, 16, 32, 64
 SVM_FEATURES = 1200
+COMPENSATE_NONE, COMPENSATE_CLASSIC, COMPENSATE_NI = 0, 1, 2   # rm::CompensateMode (include/mobility.h:18-23)
+AIM_NO_TARGET, AIM_NO_SOLUTION = 1, 2
+AIM_HEIGHT_FIXED, AIM_HEIGHT_DELTA = 0, 1
+AIM_SRC_FILTER, AIM_SRC_MEASUREMENT = 0, 1
+AIM_PICK_WINDOW, AIM_PICK_NEAREST = 0, 1
 FRAME_OVF_CONTOURS, FRAME_OVF_POINTS, FRAME_OVF_BLOBS, FRAME_OVF_ARMOURS, FRAME_SLOW_PATH, FRAME_MID_PATH = 1, 2, 4, 8, 16, 64
 
 EXPORTS = [
@@ -77,6 +86,9 @@ EXPORTS = [
     "rmcv_get_roi", "rmcv_window_origin", "rmcv_armours_to_frame",
     "rmcv_default_tracker_config", "rmcv_tracker_create", "rmcv_tracker_destroy", "rmcv_tracker_last_error", "rmcv_tracker_reset", "rmcv_tracker_set_origins",
     "rmcv_tracker_device_origins", "rmcv_batch_track", "rmcv_tracker_counts", "rmcv_tracker_get", "rmcv_tracker_step_host", "rmcv_pipeline_submit_tracked",
+    "rmcv_projectile_angle", "rmcv_solve_gea", "rmcv_delta_height", "rmcv_distance", "rmcv_rigid_inverse", "rmcv_default_aim_config", "rmcv_tracker_set_aim",
+    "rmcv_tracker_set_aim_inputs", "rmcv_tracker_device_aim_inputs", "rmcv_tracker_aim", "rmcv_tracker_get_aims", "rmcv_tracker_device_aims", "rmcv_tracker_put",
+    "rmcv_aim_step_host",
 ]
 
 
@@ -212,6 +224,26 @@ def load(path):
         L.rmcv_tracker_step_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p,
                                              C.c_int, C.c_int, C.c_int64]
         L.rmcv_pipeline_submit_tracked.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+    if hasattr(L, "rmcv_aim_step_host"):  # (builds from before device-resident aiming stay loadable for A/B runs)
+        L.rmcv_projectile_angle.restype = C.c_double
+        L.rmcv_projectile_angle.argtypes = [C.c_double, C.c_double, C.c_double, C.c_double]
+        L.rmcv_solve_gea.restype = C.c_double
+        L.rmcv_solve_gea.argtypes = [C.c_void_p, C.c_double, C.c_double, C.c_double, C.c_float, C.c_float, C.c_double, C.c_int, C.c_void_p]
+        L.rmcv_delta_height.restype = C.c_double
+        L.rmcv_delta_height.argtypes = [C.c_void_p, C.c_double, C.c_float, C.c_double]
+        L.rmcv_distance.restype = C.c_double
+        L.rmcv_distance.argtypes = [C.c_void_p]
+        L.rmcv_rigid_inverse.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_default_aim_config.restype = None
+        L.rmcv_default_aim_config.argtypes = [C.c_void_p]
+        L.rmcv_tracker_set_aim.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_set_aim_inputs.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_device_aim_inputs.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_aim.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+        L.rmcv_tracker_get_aims.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_tracker_device_aims.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_put.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.rmcv_aim_step_host.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L
@@ -291,6 +323,46 @@ def armours_to_frame(armours, x, y):
     if rc:
         raise RmcvError(rc, "rmcv_armours_to_frame")
     return a
+
+
+def _tvec(tvec):
+    t = np.ascontiguousarray(tvec, np.float64).reshape(-1)
+    assert t.shape == (3,)
+    return t
+
+
+def projectile_angle(v0, g, d, h):
+    """rm::ProjectileAngle (rmcv_projectile_angle: host-side): m/s, m/s^2, m, m -> rad, NaN without a real root"""
+    return lib().rmcv_projectile_angle(float(v0), float(g), float(d), float(h))
+
+
+def solve_gea(tvec, g, v0, h, offset=(0.0, 0.0), angle_offset=0.0, mode=COMPENSATE_NONE):
+    """rm::SolveGEA (rmcv_solve_gea: host-side, the reference's statements as written) -> (flight time, [pitch, yaw] in degrees);
+    COMPENSATE_NI: (NaN, None), as the reference returns before it creates the output"""
+    t, gea = _tvec(tvec), np.full(2, np.nan)
+    time = lib().rmcv_solve_gea(ptr(t), float(g), float(v0), float(h), C.c_float(offset[0]), C.c_float(offset[1]), float(angle_offset), int(mode), ptr(gea))
+    return time, (None if mode == COMPENSATE_NI else gea)
+
+
+def delta_height(tvec, motor_angle, offset=(0.0, 0.0), angle_offset=0.0):
+    """rm::DeltaHeight (rmcv_delta_height: host-side) -> cm"""
+    t = _tvec(tvec)
+    return lib().rmcv_delta_height(ptr(t), float(motor_angle), C.c_float(offset[1]), float(angle_offset))
+
+
+def distance(tvec):
+    """rm::Distance (rmcv_distance: host-side)"""
+    t = _tvec(tvec)
+    return lib().rmcv_distance(ptr(t))
+
+
+def rigid_inverse(m):
+    """[R t; 0 1] -> [R^T  -R^T t; 0 1] (rmcv_rigid_inverse): what turns gripper2camera into an aim input's world2camera"""
+    a, out = np.ascontiguousarray(m, np.float64).reshape(4, 4), np.zeros((4, 4))
+    rc = lib().rmcv_rigid_inverse(ptr(a), ptr(out))
+    if rc:
+        raise RmcvError(rc, "rmcv_rigid_inverse")
+    return out
 
 
 def default_pnp_config():

@@ -12,6 +12,7 @@ import ctypes as C
 import numpy as np
 
 from . import abi
+from .abi import delta_height, distance, projectile_angle, rigid_inverse, solve_gea  # noqa: F401  (rm::ProjectileAngle / SolveGEA / DeltaHeight / Distance: host-side)
 from .abi import (ARMOUR, CAMP_BLUE, LIGHTBLOB, MORPH_CLOSE, POINT, RRECT, STAGE_ALL, LegacyParams, Limits, Params, PnpConfig, RmcvError, default_pnp_config,
                   default_params, lib, ptr)
 

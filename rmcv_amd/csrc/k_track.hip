@@ -98,16 +98,7 @@ hipError_t launch_track(const rmcv_tracker_config& cfg, const TrackerBufs& tb, c
 
 using namespace rmcv;
 
-struct rmcv_tracker {
-    int device = 0;
-    rmcv_tracker_config cfg{};
-    TrackerBufs b{};
-    hipEvent_t ev_step = nullptr;  // recorded behind the step enqueued last
-    bool step_pending = false;
-    hipStream_t last_stream = nullptr;
-    char err[256] = {0};
-    std::vector<void*> allocs;
-};
+// (struct rmcv_tracker: rmcv_internal.h)
 
 static int tfail(rmcv_tracker* t, int code, const char* what, hipError_t e = hipSuccess)
 {
@@ -137,6 +128,8 @@ static int tracker_wait(rmcv_tracker* t)
 }
 
 namespace rmcv {
+int tracker_wait_done(rmcv_tracker* t) { return tracker_wait(t); }
+int tracker_fail(rmcv_tracker* t, int code, const char* what, hipError_t e) { return tfail(t, code, what, e); }
 const rmcv_tracker_config& tracker_config(const rmcv_tracker* t) { return t->cfg; }
 const TrackerBufs& tracker_bufs(const rmcv_tracker* t) { return t->b; }
 int tracker_device(const rmcv_tracker* t) { return t->device; }

@@ -23,6 +23,9 @@
  * Float variants evaluate in double and round once (correctly rounded float
  * results except with probability ~2^-29).
  *
+ * pm_tan (rm::DeltaHeight, src/mobility.cpp:48, for device-resident aiming) is the classical kernel
+ * tangent behind the same reduction, |error| < 1 ulp (tests/test_pinned_tan.py).
+ *
  * pm_hypot (the device tracker's Jacobi rotation) is the one function here that
  * is CORRECTLY ROUNDED, and the one that uses sqrt and the explicit fma besides:
  * see its own comment.
@@ -124,6 +127,61 @@ PM_FN double pm_cos(double x)
         case 1: return -pm_ksin(r, t, 1);
         case 2: return -pm_kcos(r, t);
         default: return pm_ksin(r, t, 1);
+    }
+}
+
+/* tan on [-pi/4, pi/4] (+eps); y is the tail of x; odd: the result is -1 / tan(x + y).  The classical kernel: the odd degree-27
+ * polynomial split into two interleaved sums; above 0.6744 the argument is first reflected at pi/4 (tan(pi/4 - u) = 1 - 2 (u - u^2 / (1 + u))),
+ * and -1 / w is computed from a head / tail split of w so that it keeps its last bit. */
+PM_FN double pm_ktan(double x, double y, int odd)
+{
+    const double T0 = 3.33333333333334091986e-01, T1 = 1.33333333333201242699e-01, T2 = 5.39682539762260521377e-02,
+                 T3 = 2.18694882948595424599e-02, T4 = 8.86323982359930005737e-03, T5 = 3.59207910759131235356e-03,
+                 T6 = 1.45620945432529025516e-03, T7 = 5.88041240820264096874e-04, T8 = 2.46463134818469906812e-04,
+                 T9 = 7.81794442939557092300e-05, T10 = 7.14072491382608190305e-05, T11 = -1.85586374855275456654e-05,
+                 T12 = 2.59073051863633712884e-05;
+    const double pio4 = 7.85398163397448278999e-01, pio4lo = 3.06161699786838301793e-17;
+    const int big = pm_fabs(x) >= 0x1.59428p-1, neg = x < 0; /* 0.67434 */
+    double z, r, v, w, s;
+    if (big) {
+        if (neg) { x = -x; y = -y; }
+        x = (pio4 - x) + (pio4lo - y);
+        y = 0.0;
+    }
+    z = x * x;
+    w = z * z;
+    r = T1 + w * (T3 + w * (T5 + w * (T7 + w * (T9 + w * T11))));
+    v = z * (T2 + w * (T4 + w * (T6 + w * (T8 + w * (T10 + w * T12)))));
+    s = z * x;
+    r = y + z * (s * (r + v) + y) + s * T0;
+    w = x + r;
+    if (big) {
+        s = odd ? -1.0 : 1.0;
+        v = s - 2.0 * (x + (r - w * w / (w + s)));
+        return neg ? -v : v;
+    }
+    if (!odd) return w;
+    {
+        const double w0 = pm_hi_word_only(w);
+        const double a = -1.0 / w, a0 = pm_hi_word_only(a);
+        v = r - (w0 - x); /* w0 + v = r + x */
+        return a0 + a * (1.0 + a0 * w0 + a0 * v);
+    }
+}
+
+/* tan for |x| < ~1e5 (pm_rem_pio2's domain), |error| < 1 ulp; NaN and the infinities give NaN, +-0 gives +-0.  (rm::DeltaHeight,
+ * src/mobility.cpp:48.) */
+PM_FN double pm_tan(double x)
+{
+    double r, t;
+    if (x - x != 0.0) return x - x; /* NaN, +-infinity */
+    if (pm_fabs(x) <= 0.7853981633974483) {
+        if (pm_fabs(x) < 7.450580596923828e-09) return x; /* 2^-27: tan(x) = x, and -0 stays -0 */
+        return pm_ktan(x, 0.0, 0);
+    }
+    {
+        const int n = pm_rem_pio2(x, &r, &t);
+        return pm_ktan(r, t, n & 1);
     }
 }
 

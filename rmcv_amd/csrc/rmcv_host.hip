@@ -2269,6 +2269,7 @@ int ctx_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, int stages, hip
     HIPCHK(c, tracker_order_begin(trk, s), "tracker: wait for its previous step");
     HIPCHK(c, launch_track(tc, tracker_bufs(trk), c->bufs, c->lim, (stages & RMCV_STAGE_IDENTITY) != 0, (stages & RMCV_STAGE_POSE) != 0,
                            g.win ? c->bufs.win_eff : nullptr, timestamp, s), "k_track");
+    if (tracker_aim_on(trk)) HIPCHK(c, launch_aim(trk, timestamp, s), "k_aim"); // the aim step reads the lists the step has just left
     HIPCHK(c, tracker_order_end(trk, s), "tracker: record the step");
     return order_end(c, s);
 }

@@ -5,6 +5,7 @@
 
 #include <tuple>
 #include <utility>
+#include <vector>
 
 #include "../../include/rmcv_abi.h"
 #include "image_plan.h"
@@ -309,5 +310,30 @@ hipError_t tracker_order_begin(rmcv_tracker* t, hipStream_t s);
 hipError_t tracker_order_end(rmcv_tracker* t, hipStream_t s);
 // make `s` wait for the tracker's last step (a consumer of its origins on another stream)
 hipError_t tracker_wait_on(rmcv_tracker* t, hipStream_t s);
+// the host's wait for the step in flight (5 s deadline) and the tracker's error record, for the aim entry points (k_aim.hip)
+int tracker_wait_done(rmcv_tracker* t);
+int tracker_fail(rmcv_tracker* t, int code, const char* what, hipError_t e = hipSuccess);
+
+// ---- device-resident aiming (k_aim.hip) ----
+// aiming on: the aim step of every stream right behind a tracker step (ctx_track), `now` = the step's timestamp
+bool tracker_aim_on(const rmcv_tracker* t);
+hipError_t launch_aim(const rmcv_tracker* t, int64_t now, hipStream_t s);
 
 } // namespace rmcv
+
+// the tracker behind the ABI's handle (k_track.hip owns its lifetime; k_aim.hip the aim fields)
+struct rmcv_tracker {
+    int device = 0;
+    rmcv_tracker_config cfg{};
+    rmcv::TrackerBufs b{};
+    hipEvent_t ev_step = nullptr;  // recorded behind the step enqueued last
+    bool step_pending = false;
+    hipStream_t last_stream = nullptr;
+    char err[256] = {0};
+    std::vector<void*> allocs;
+    // aiming: off until rmcv_tracker_set_aim; the buffers are allocated on first use (and freed with `allocs`)
+    bool aim_on = false;
+    rmcv_aim_config aim_cfg{};
+    rmcv_aim_input* aim_inputs = nullptr; // [n_streams]
+    rmcv_aim* aims = nullptr;             // [n_streams]
+};

@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from .abi import ARMOUR, POINT, TRACK, RmcvError, lib, ptr
+from .abi import AIM, AIM_INPUT, ARMOUR, POINT, TRACK, RmcvError, lib, ptr
 
 TRACKER_OVF = 1
 TRACKER_MAX_CAP = 64
@@ -27,6 +27,42 @@ def default_tracker_config(**kw):
     for k, v in kw.items():
         setattr(c, k, v)
     return c
+
+
+class AimConfig(C.Structure):
+    """rmcv_aim_config"""
+    _fields_ = [("g", C.c_double), ("v0", C.c_double), ("height", C.c_double), ("offset_x", C.c_float), ("offset_y", C.c_float),
+                ("angle_offset", C.c_double), ("latency_s", C.c_double), ("mode", C.c_int32), ("height_mode", C.c_int32), ("source", C.c_int32),
+                ("pick", C.c_int32), ("lead_iterations", C.c_int32), ("max_lost", C.c_int32), ("overloads", C.c_int32), ("identity_mask", C.c_uint32)]
+
+
+assert C.sizeof(AimConfig) == 80
+
+
+def default_aim_config(**kw):
+    c = AimConfig()
+    lib().rmcv_default_aim_config(C.byref(c))
+    for k, v in kw.items():
+        setattr(c, k, v)
+    return c
+
+
+_DEFAULTS = object()   # Tracker.set_aim(): the defaults; set_aim(None): off
+
+
+def _aim_inputs(inputs, n):
+    """(world2camera (4, 4), motor_angle) pairs, an AIM_INPUT array, or None -> AIM_INPUT[n] | None"""
+    if inputs is None:
+        return None
+    if isinstance(inputs, np.ndarray) and inputs.dtype == AIM_INPUT:
+        a = np.ascontiguousarray(inputs)
+    else:
+        a = np.zeros(len(inputs), AIM_INPUT)
+        for k, (w2c, motor) in enumerate(inputs):
+            a[k]["world2camera"] = np.asarray(w2c, np.float64).reshape(4, 4)
+            a[k]["motor_angle"] = motor
+    assert len(a) == n
+    return a
 
 
 class Tracker:
@@ -84,6 +120,65 @@ class Tracker:
         n, o = C.c_int32(0), np.zeros(1, POINT)
         self._chk(self._lib.rmcv_tracker_get(self._h, int(stream), ptr(tr), self.track_cap, C.byref(n), ptr(side), ptr(o)))
         return tr[:n.value].copy(), side[:n.value].copy(), (int(o[0]["x"]), int(o[0]["y"]))
+
+    # ---------------------------------------------------------------- aiming
+    def set_aim(self, config=_DEFAULTS, **fields):
+        """aiming on: an AimConfig, or fields of rmcv_aim_config over the defaults (g, v0, height, offset_x, offset_y, angle_offset, latency_s,
+        mode, height_mode, source, pick, lead_iterations, max_lost, overloads, identity_mask).  set_aim(None): off -- no aim kernel is
+        launched and the records stay as they are.  Waits for the step in flight."""
+        if config is None:
+            assert not fields
+            self._chk(self._lib.rmcv_tracker_set_aim(self._h, None))
+            return None
+        c = default_aim_config(**fields) if config is _DEFAULTS else config
+        self._chk(self._lib.rmcv_tracker_set_aim(self._h, C.byref(c)))
+        return c
+
+    def set_aim_inputs(self, inputs=None):
+        """per stream (world2camera (4, 4), motor_angle) -- a list of pairs or an AIM_INPUT array; None: identity, 0"""
+        a = _aim_inputs(inputs, self.n_streams)
+        self._chk(self._lib.rmcv_tracker_set_aim_inputs(self._h, ptr(a)))
+
+    def device_aim_inputs(self):
+        """device pointer (int) of the n_streams rmcv_aim_input: a caller may write them on its own stream before a submit"""
+        d = C.c_void_p()
+        self._chk(self._lib.rmcv_tracker_device_aim_inputs(self._h, C.byref(d)))
+        return d.value
+
+    def device_aims(self):
+        """device pointer (int) of the n_streams rmcv_aim records"""
+        d = C.c_void_p()
+        self._chk(self._lib.rmcv_tracker_device_aims(self._h, C.byref(d)))
+        return d.value
+
+    def aim(self, now, stream=None):
+        """the aim step alone, on the lists as they are; asynchronous"""
+        self._chk(self._lib.rmcv_tracker_aim(self._h, C.c_int64(int(now)), C.c_void_p(stream or 0)))
+
+    def aims(self):
+        """AIM[n_streams]; synchronous.  Zeros until the first aim step."""
+        out = np.zeros(self.n_streams, AIM)
+        self._chk(self._lib.rmcv_tracker_get_aims(self._h, ptr(out), self.n_streams))
+        return out
+
+    def put(self, stream, tracks, last_vertices=None):
+        """seed or restore one stream's current list: TRACK[n] (n <= track_cap), last vertices (n, 4, 2) | None: zeros; synchronous"""
+        tr = np.ascontiguousarray(tracks, TRACK)
+        side = None if last_vertices is None else np.ascontiguousarray(last_vertices, np.float32).reshape(-1, 4, 2)
+        assert side is None or len(side) == len(tr)
+        self._chk(self._lib.rmcv_tracker_put(self._h, int(stream), ptr(tr) if len(tr) else None, len(tr), ptr(side) if side is not None and len(tr) else None))
+
+    @staticmethod
+    def aim_host(config, tick_frequency, tracks, now, aim_input=None):
+        """rmcv_aim_step_host: one stream's aim step on the CPU (the kernel's source).  tracks TRACK[n], aim_input a (world2camera,
+        motor_angle) pair | None.  Returns one AIM record."""
+        tr = np.ascontiguousarray(tracks, TRACK)
+        a = _aim_inputs(None if aim_input is None else [aim_input], 1)
+        out = np.zeros(1, AIM)
+        rc = lib().rmcv_aim_step_host(C.byref(config), float(tick_frequency), ptr(tr) if len(tr) else None, len(tr), ptr(a), C.c_int64(int(now)), ptr(out))
+        if rc != 0:
+            raise RmcvError(rc, "rmcv_aim_step_host: bad argument (a config rmcv_tracker_set_aim would refuse, more than 64 tracks, a bad tick frequency)")
+        return out[0]
 
     @staticmethod
     def step_host(config, tracks, last_vertices, status, origin, armours, identities=None, positions=None, eff=(0, 0), timestamp=0):
