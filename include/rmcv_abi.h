@@ -442,6 +442,37 @@ int rmcv_window_origin(const int32_t rect[4], int win_w, int win_h, int32_t out_
  * see NOT promised above) */
 int rmcv_armours_to_frame(rmcv_armour* armours, int n, int x, int y);
 
+/* ---- per-frame detection keys: the enemy colour arrives with every frame (serial_package::target, executable/main.cpp:142, carried in
+ * frame_package to the process loop) ---------------------------------------------------------------------------------------------------
+ * A batch is frame f = the next frame of stream f; in a match half of the streams hunt red and half blue, and their cameras are not
+ * exposed alike.  With keys set, frame f is detected with camp camps[f] and lower bound lower_bounds[f] (or the run's p->lower_bound);
+ * rmcv_params::camp and ::lower_bound of the run are otherwise not read, every other field of rmcv_params stays per batch (morph too).
+ * Everything frame f produces -- byte image, bit plane, contours, light blobs including `target`, armours, with RMCV_STAGE_IDENTITY /
+ * RMCV_STAGE_POSE identities, icons and poses, behind a tracker every track byte -- equals, bit for bit, what the same batch run gives for
+ * frame f with p->camp = camps[f] and p->lower_bound = lower_bounds[f].
+ * The raw values are any int32 (a device-side producer may write them).  The EFFECTIVE key of a frame is computed on the device, in one
+ * place (k_frame_keys, in front of the pixel pass), written to a per-frame table and read from there by every consumer:
+ *     channel pair (src/imgproc.cpp:56-65):  camp 2 -> G - R;  camp 1 -> B - R;  every other value -> R - B
+ *     bound (inRange(gray, lb, 255) on a saturated u8 difference):  lb <= 0 -> every pixel passes;  lb > 255 -> none;  otherwise a - b >= lb
+ *     enemy label: blobs[].target is camps[f] verbatim (objdetect.cpp:83), and pairing compares against the same value (:124-129)
+ * The pixel pass is k_binary_camp (with windows k_binary_camp_win): k_binary's shape, the key read once per 32-row strip; never
+ * k_binary_ws, which stays the faster path for a batch of ONE colour -- keys are for fleets that are mixed.
+ * RMCV_ERR_BAD_ARG, with a message, before anything is enqueued -- the families windows refuse too: keys with a Bayer
+ * RMCV_OPT_INPUT_FORMAT (the mosaic kernel takes one camp per run); with RMCV_OPT_ENHANCE (its threshold table folds one bound per run);
+ * with the legacy matcher (rmcv_batch_run_legacy, rmcv_pipeline_submit_legacy: it votes a camp per blob); no frames bound. */
+/* the effective key of (camp, lower_bound): out = channel A, channel B (byte inside a BGR pixel), effective bound 1 .. 256, all-pass flag.
+ * Host-side, no context, no device: the function the prologue kernel runs, compiled for the host */
+int rmcv_frame_key(int32_t camp, int32_t lower_bound, int32_t out[4]);
+/* after the frames are bound (a new binding returns to per-run keys, as it returns to whole frames): n_frames host values each, copied.
+ * lower_bounds NULL: every frame uses the run's p->lower_bound.  camps NULL: back to per-run keys.  Synchronises the context. */
+int rmcv_batch_set_frame_camps(rmcv_ctx* ctx, const int32_t* camps, const int32_t* lower_bounds);
+/* the same with the tables in device memory (n_frames int32 each; d_lower_bounds nullable), BORROWED: every run that includes
+ * RMCV_STAGE_BINARY reads them again, on its stream, in front of its pixel pass */
+int rmcv_batch_set_device_frame_camps(rmcv_ctx* ctx, const void* d_camps, const void* d_lower_bounds);
+/* the effective keys of the last run with the pixel pass, keys_out[f] = {channel A, channel B, bound, all-pass} for the first min(cap,
+ * n_frames) frames; without per-frame keys that is the run's key for every frame.  Synchronises the context. */
+int rmcv_batch_get_frame_keys(rmcv_ctx* ctx, int32_t* keys_out /* [cap][4] */, int cap);
+
 /* ---- icon classifier: the "next" row of the path (executable/main.cpp:178-181) ------------------------ */
 #define RMCV_SVM_FEATURES 1200 /* 20 x 20 x BGR, executable/main.cpp:180 ({20, 20}), core.cpp:202-216 */
 /* linear one-vs-one C_SVC as cv::ml::SVM keeps it after training (executable/svm/optimizer.cpp:16-19): one weight
@@ -625,6 +656,13 @@ int  rmcv_tracker_set_origins(rmcv_tracker* trk, const rmcv_point* origins);
 /* device view of the requested origins (n_streams rmcv_point): what a caller hands to rmcv_batch_set_device_windows /
  * rmcv_pipeline_submit_windows.  Owned by the tracker. */
 int  rmcv_tracker_device_origins(rmcv_tracker* trk, void** d_origins);
+/* per-stream detection keys (see "per-frame detection keys"): a stream's colour is a property of the stream.  n_streams host values each,
+ * copied into tables the tracker owns; lower_bounds NULL: the run's p->lower_bound; camps NULL: off.  Waits for the step in flight.
+ * rmcv_pipeline_submit_tracked on such a tracker is an rmcv_pipeline_submit_camps with the tracker's tables; rmcv_batch_track needs nothing
+ * new (the run before it had its keys: rmcv_batch_set_device_frame_camps with the tables below, or host values) */
+int  rmcv_tracker_set_camps(rmcv_tracker* trk, const int32_t* camps, const int32_t* lower_bounds);
+/* the tracker's two tables (n_streams int32 each), for a device-side writer and for rmcv_batch_set_device_frame_camps; either may be NULL */
+int  rmcv_tracker_device_camps(rmcv_tracker* trk, void** d_camps, void** d_lower_bounds);
 /* enqueue one step on `hip_stream` (NULL: the context's stream) behind the context's last run, on the batch bound to it.  Never
  * synchronises.  RMCV_ERR_BAD_ARG with a message: the batch's n_frames != n_streams; its frame size differs from the config's; the last
  * run had no RMCV_STAGE_ARMOURS; windows are set and their size differs from the config's; context and tracker on different devices. */
@@ -859,6 +897,14 @@ int  rmcv_pipeline_submit_legacy(rmcv_pipeline* pl, const void* d_frames, int n_
  * effective origins. */
 int  rmcv_pipeline_submit_windows(rmcv_pipeline* pl, const void* d_frames, int n_frames, int frame_w, int frame_h, int stride, int64_t frame_pitch,
                                   const void* d_origins, int win_w, int win_h, const rmcv_params* p, int stages, uint64_t* ticket);
+/* a batch with PER-FRAME DETECTION KEYS (see rmcv_batch_set_frame_camps): rmcv_pipeline_submit (win_w == 0; d_origins ignored) or
+ * rmcv_pipeline_submit_windows (win_w > 0) with d_camps = n_frames int32 and d_lower_bounds = n_frames int32 or NULL (the batch's
+ * p->lower_bound) in DEVICE memory, borrowed like the frames and read on the batch's stream in front of its pixel pass; nothing blocks
+ * (host_blocking_calls stays 0).  The batch takes the k_binary shape and stays out of the hot-context rotation, as windowed and enhanced
+ * batches do; submits with and without keys may alternate on one pipeline.  Refused as rmcv_batch_set_frame_camps refuses. */
+int  rmcv_pipeline_submit_camps(rmcv_pipeline* pl, const void* d_frames, int n_frames, int frame_w, int frame_h, int stride, int64_t frame_pitch,
+                                const void* d_camps, const void* d_lower_bounds /* nullable */, const void* d_origins /* nullable */, int win_w,
+                                int win_h, const rmcv_params* p, int stages, uint64_t* ticket);
 /* a TRACKED batch: frame f is the next frame of stream f of `trk` (device-resident tracker, above).  With the tracker's win_w > 0 this is
  * rmcv_pipeline_submit_windows whose origins are the tracker's requested origins; with win_w == 0 a whole-frame submit.  In both cases one
  * step of the tracker (`timestamp`: see rmcv_batch_track) is enqueued behind the batch's compaction on its finishing stream, and the NEXT

@@ -89,6 +89,8 @@ EXPORTS = [
     "rmcv_projectile_angle", "rmcv_solve_gea", "rmcv_delta_height", "rmcv_distance", "rmcv_rigid_inverse", "rmcv_default_aim_config", "rmcv_tracker_set_aim",
     "rmcv_tracker_set_aim_inputs", "rmcv_tracker_device_aim_inputs", "rmcv_tracker_aim", "rmcv_tracker_get_aims", "rmcv_tracker_device_aims", "rmcv_tracker_put",
     "rmcv_aim_step_host",
+    "rmcv_frame_key", "rmcv_batch_set_frame_camps", "rmcv_batch_set_device_frame_camps", "rmcv_batch_get_frame_keys", "rmcv_pipeline_submit_camps",
+    "rmcv_tracker_set_camps", "rmcv_tracker_device_camps",
 ]
 
 
@@ -244,6 +246,15 @@ def load(path):
         L.rmcv_tracker_device_aims.argtypes = [C.c_void_p, C.c_void_p]
         L.rmcv_tracker_put.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.rmcv_aim_step_host.argtypes = [C.c_void_p, C.c_double, C.c_void_p, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+    if hasattr(L, "rmcv_frame_key"):  # (builds from before per-frame detection keys stay loadable for A/B runs)
+        L.rmcv_frame_key.argtypes = [C.c_int32, C.c_int32, C.c_void_p]
+        L.rmcv_batch_set_frame_camps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_batch_set_device_frame_camps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_batch_get_frame_keys.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_pipeline_submit_camps.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p,
+                                                 C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.rmcv_tracker_set_camps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_device_camps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L
@@ -323,6 +334,16 @@ def armours_to_frame(armours, x, y):
     if rc:
         raise RmcvError(rc, "rmcv_armours_to_frame")
     return a
+
+
+def frame_key(camp, lower_bound):
+    """the effective detection key of raw (camp, lower_bound), any int32 (rmcv_frame_key: host-side, the function the device's prologue runs)
+    -> (channel A, channel B, effective bound 1 .. 256, all-pass flag); a pixel is set where all-pass or bgr[A] - bgr[B] >= bound"""
+    out = np.zeros(4, np.int32)
+    rc = lib().rmcv_frame_key(C.c_int32(int(camp)), C.c_int32(int(lower_bound)), ptr(out))
+    if rc:
+        raise RmcvError(rc, "rmcv_frame_key")
+    return tuple(int(v) for v in out)
 
 
 def _tvec(tvec):

@@ -430,6 +430,35 @@ class Context:
     window_origin = staticmethod(abi.window_origin)
     armours_to_frame = staticmethod(abi.armours_to_frame)
 
+    # ---------------------------------------------------------------- per-frame detection keys (serial_package::target per frame)
+    def set_frame_camps(self, camps, lower_bounds=None, keepalive=None):
+        """every frame bound gets its own camp and, optionally, its own lower bound: n integers each on the host (numpy arrays or
+        anything that converts to one), or ints = device pointers to n int32 (borrowed; read again by every run).  Any values:
+        frame_keys() shows what the kernels use.  lower_bounds None: the run's params.lower_bound.  camps None: per-run keys again
+        (a new binding returns to them too)."""
+        n = self.shape[0]
+        if camps is None:
+            self._chk(lib().rmcv_batch_set_frame_camps(self._h, None, None))
+            return
+        if isinstance(camps, (int, np.integer)):
+            assert lower_bounds is None or isinstance(lower_bounds, (int, np.integer)), "device camps take device lower bounds"
+            self._keys_ref = keepalive
+            self._chk(lib().rmcv_batch_set_device_frame_camps(self._h, C.c_void_p(int(camps)), None if lower_bounds is None else C.c_void_p(int(lower_bounds))))
+            return
+        c = np.ascontiguousarray(camps, np.int32).reshape(-1)
+        lb = None if lower_bounds is None else np.ascontiguousarray(lower_bounds, np.int32).reshape(-1)
+        assert len(c) == n and (lb is None or len(lb) == n), "one camp (and one lower bound) per frame bound"
+        self._chk(lib().rmcv_batch_set_frame_camps(self._h, ptr(c), ptr(lb)))
+
+    def frame_keys(self):
+        """the effective keys of the last run, int32 (n, 4): channel A, channel B, bound 1 .. 256, all-pass flag per frame"""
+        n = self.shape[0]
+        out = np.zeros((n, 4), np.int32)
+        self._chk(lib().rmcv_batch_get_frame_keys(self._h, ptr(out), n))
+        return out
+
+    frame_key = staticmethod(abi.frame_key)
+
     def run(self, params=None, stages=STAGE_ALL, stream=None):
         self._params = params or default_params()
         self._chk(lib().rmcv_batch_run(self._h, C.byref(self._params), int(stages), C.c_void_p(stream or 0)))

@@ -57,13 +57,13 @@ bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound, int pixel_ws)
     const bool linear = one_launch && !g.pixel_rowquad && g.stride == 3 * g.w;
     const int n_cu = g.n_cu > 0 ? g.n_cu : 256, n_blocks = g.n_frames * strips;
     const size_t planes_ws = ((size_t)2 * (SR + 4) + SR) * g.ww * sizeof(uint64_t);
-    return g.input_format == RMCV_INPUT_BGR && !g.enhance && !g.win && pixel_ws && linear && lower_bound > 0 && n_blocks * 2 > n_cu && planes_ws <= 60 * 1024 && n_blocks >= n_cu;
+    return g.input_format == RMCV_INPUT_BGR && !g.enhance && !g.win && !g.keys && pixel_ws && linear && lower_bound > 0 && n_blocks * 2 > n_cu && planes_ws <= 60 * 1024 && n_blocks >= n_cu;
 }
 
 hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s,
                          ImageState* img)
 {
-    if (g.input_format != RMCV_INPUT_BGR || g.enhance || g.win) {
+    if (g.input_format != RMCV_INPUT_BGR || g.enhance || g.win || g.keys) {
         // these kernels store every byte of the image and know nothing of its mask (image_plan.h: IMAGE_KERNEL_OTHER)
         const ImageLaunch l = {IMAGE_KERNEL_OTHER, image, g.w, g.h, g.ww, g.n_frames};
         const ImageState before = img ? *img : IMAGE_STATE_UNKNOWN;
@@ -71,8 +71,10 @@ hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound
         // a Bayer mosaic (RMCV_OPT_INPUT_FORMAT): its own kernel, never k_binary_ws (k_binary_bayer.hip)
         // through the frames' gamma tables (RMCV_OPT_ENHANCE): the same kernel with a lookup in its compare (k_binary_enh.hip)
         // a window of every frame (rmcv_batch_set_windows): the same kernel reading from the frames' effective origins (k_binary_win.hip)
+        // per-frame detection keys (rmcv_batch_set_frame_camps): the same kernel reading camp and bound per strip, windows or not (k_binary_camp.hip)
         const hipError_t e = g.input_format != RMCV_INPUT_BGR ? launch_binary_bayer(g, b, camp, lower_bound, morph, image, s)
                              : g.enhance                      ? launch_binary_enh(g, b, camp, lower_bound, morph, image, plan, s)
+                             : g.keys                         ? launch_binary_camp(g, b, morph, image, plan, s)
                                                               : launch_binary_win(g, b, camp, lower_bound, morph, image, plan, s);
         if (img && e == hipSuccess) *img = image_step(before, l, true).next;
         return e;

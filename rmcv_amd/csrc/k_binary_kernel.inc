@@ -5,16 +5,30 @@
 #ifndef K1_WIN
 #define K1_WIN 0
 #endif
+// k_binary_camp.hip / k_binary_camp_win.hip: K1_CAMP 1, k_binary_camp / k_binary_camp_win, per-frame detection keys -- every strip reads its
+// frame's channel pair, bound and all-pass flag from a table (Bufs::key_eff) and runs phase 1 in the thresh16<CA, CB> / K1_PASS
+// instantiation of that pair (with K1_CAMP 0 -- the default -- this file preprocesses to what it was before the switch existed).
+#ifndef K1_CAMP
+#define K1_CAMP 0
+#endif
 
 // Register budget: 6 waves per SIMD = at most 80 VGPRs.  Two launches of consecutive batches overlap (2 workgroups per CU each = 4
 // waves per SIMD) next to one wave of the 4-wavefront sparse kernel (168 VGPRs): 4 x 80 + 168 <= 512.  At 88 the sparse kernel
 // would no longer fit beside them and the batches in flight would take turns instead of sharing the CUs.
+#if K1_CAMP
+template <int FAST>
+#else
 template <int CA, int CB, int FAST /* 0: byte-wise loader, 1: row-quad items, 2: linear items (rows contiguous in memory) */>
+#endif
 #ifndef RMCV_K1_MINBLOCKS
 #define RMCV_K1_MINBLOCKS 6
 #endif
 __global__ __launch_bounds__(256, RMCV_K1_MINBLOCKS) void K1_KERNEL(const uint8_t* __restrict__ frames, int64_t frame_pitch, int stride, int n_frames,
+#if K1_CAMP
+                                                 int w, int h, int ww, int, int /* the run's bound and flag: every strip takes its frame's */, int morph,
+#else
                                                  int w, int h, int ww, int lb, int all_pass, int morph,
+#endif
                                                  uint8_t* __restrict__ binary, uint64_t* __restrict__ bits, int prow,
                                                  int64_t plane_pitch, int strips, int n_blocks, uint32_t* __restrict__ rowmask,
                                                  int* __restrict__ strip_ctr, int taper_head, int taper_tail,
@@ -25,6 +39,9 @@ __global__ __launch_bounds__(256, RMCV_K1_MINBLOCKS) void K1_KERNEL(const uint8_
 #if K1_WIN
                                                  , const rmcv_point* __restrict__ win_eff /* [frame] Bufs::win_eff; w, h are the window's */
                                                  , int in_extent /* bytes from `frames` to the end of the launch's last WHOLE frame */
+#endif
+#if K1_CAMP
+                                                 , const FrameKey* __restrict__ keys /* [frame] Bufs::key_eff */
 #endif
                                                  )
 {
@@ -109,6 +126,20 @@ __global__ __launch_bounds__(256, RMCV_K1_MINBLOCKS) void K1_KERNEL(const uint8_
     // (every wave has left the previous strip's phase 1 -- two barriers ago -- so the table may change under nobody)
     if (f != f_m) { s_m[tid] = mtab[(int64_t)f * 256 + tid]; f_m = f; }
     __syncthreads();
+#endif
+#if K1_CAMP
+    // the frame's key, once per strip (a workgroup's consecutive strips belong to different frames): wave-uniform, one scalar load; phase 1
+    // below is then entered in the instantiation of the key's channel pair -- thresh16's selectors and register indices stay compile-time
+    const FrameKey* const key = keys + __builtin_amdgcn_readfirstlane(f);
+    const int key_ca = __builtin_amdgcn_readfirstlane(key->ca);
+    const int lb = __builtin_amdgcn_readfirstlane(key->lb), all_pass = __builtin_amdgcn_readfirstlane(key->all_pass);
+    // (the whole-frame row-quad loader takes w, ww and stride through a copy made opaque per strip: what its phase 1 derives from them is then
+    // computed per strip on the scalar unit; hoisted out of the strip loop once per instantiation, three sets of loop invariants put that
+    // loader alone one VGPR over the 80 -- 8 bytes of scratch.  The linear and the windowed loader fit as they are and are left alone.)
+    int w_k = w, ww_k = ww, stride_k = stride;
+    if (FAST == 1 && !K1_WIN) asm volatile("" : "+s"(w_k), "+s"(ww_k), "+s"(stride_k));
+    auto phase1 = [&](auto ca_, auto cb_, const int w, const int ww, const int stride) __attribute__((always_inline)) {
+    constexpr int CA = decltype(ca_)::value, CB = decltype(cb_)::value;
 #endif
 
     // ---------------- phase 1: load + threshold -> T
@@ -319,6 +350,13 @@ __global__ __launch_bounds__(256, RMCV_K1_MINBLOCKS) void K1_KERNEL(const uint8_
             if (q >= wq) { q -= wq; rr++; }
         }
     }
+#if K1_CAMP
+    };
+    // (frame_key_eff: channel A is 0 for B-R, 1 for G-R, 2 for R-B)
+    if (key_ca == 1) phase1(std::integral_constant<int, 1>{}, std::integral_constant<int, 2>{}, w_k, ww_k, stride_k);
+    else if (key_ca == 0) phase1(std::integral_constant<int, 0>{}, std::integral_constant<int, 2>{}, w_k, ww_k, stride_k);
+    else phase1(std::integral_constant<int, 2>{}, std::integral_constant<int, 0>{}, w_k, ww_k, stride_k);
+#endif
     __syncthreads();
 
     const uint64_t last_valid = (w & 63) ? ((1ull << (w & 63)) - 1) : ~0ull; // valid bits of the last word

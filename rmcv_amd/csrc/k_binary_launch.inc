@@ -7,7 +7,17 @@
 #ifndef K1_WIN
 #define K1_WIN 0
 #endif
+// K1_CAMP (k_binary_camp.hip, k_binary_camp_win.hip): per-frame detection keys -- the launcher is no template (the kernel picks the channel pair
+// per strip), `lower_bound` is ignored, K1_EXTRA carries the launch's slice of Bufs::key_eff; k_binary's shape, never k_binary_ws.
+#ifndef K1_CAMP
+#define K1_CAMP 0
+#endif
+#if K1_CAMP
+#define K1_INST(F) K1_KERNEL<F>
+#else
+#define K1_INST(F) K1_KERNEL<CA, CB, F>
 template <int CA, int CB>
+#endif
 static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int morph, bool image, const RunPlan& plan,
                                   hipStream_t s, ImageState* img = nullptr)
 {
@@ -33,7 +43,7 @@ static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int
     // persistent grid: RMCV_OPT_PIXEL_GROUPS workgroups per CU: alone the kernel is equally fast with 2 and 3 and slower with 4 and
     // more; 2 leaves room on every CU for the kernels of the other batches in flight
     const int bpc = plan.pixel_groups;
-#if !K1_ENH && !K1_WIN
+#if !K1_ENH && !K1_WIN && !K1_CAMP
     // the chunks of a batch share one state: the mode from what held before the batch, the next state from what all of them ran as
     const ImageState img_before = img ? *img : IMAGE_STATE_UNKNOWN;
     const ImageLaunch img_launch = {IMAGE_KERNEL_WS, image, g.w, g.h, g.ww, g.n_frames};
@@ -66,15 +76,15 @@ static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int
         const int inst = mode;
         if (planes > 60 * 1024 && planes > lds_set[g.device][inst]) {
 #if K1_WIN
-            const void* fn = mode == 1 ? reinterpret_cast<const void*>(K1_KERNEL<CA, CB, 1>) : reinterpret_cast<const void*>(K1_KERNEL<CA, CB, 0>);
+            const void* fn = mode == 1 ? reinterpret_cast<const void*>(K1_INST(1)) : reinterpret_cast<const void*>(K1_INST(0));
 #else
-            const void* fn = mode == 2 ? reinterpret_cast<const void*>(K1_KERNEL<CA, CB, 2>) : mode == 1 ? reinterpret_cast<const void*>(K1_KERNEL<CA, CB, 1>) : reinterpret_cast<const void*>(K1_KERNEL<CA, CB, 0>);
+            const void* fn = mode == 2 ? reinterpret_cast<const void*>(K1_INST(2)) : mode == 1 ? reinterpret_cast<const void*>(K1_INST(1)) : reinterpret_cast<const void*>(K1_INST(0));
 #endif
             const hipError_t ea = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)planes);
             if (ea != hipSuccess) return ea;
             lds_set[g.device][inst] = planes;
         }
-#if !K1_ENH && !K1_WIN // (a batch with enhancement or windows takes the k_binary shape whatever the plan says)
+#if !K1_ENH && !K1_WIN && !K1_CAMP // (a batch with enhancement or windows takes the k_binary shape whatever the plan says)
         // whole batches with contiguous rows, when the caller asks for it (RMCV_OPT_PIXEL_SHAPE; a pipeline does for its calm batches):
         // the wave-specialised kernel, ONE 1024-thread workgroup per CU -- 8 loader wavefronts with 2 items (8 loads) in flight each, 8 storers
         constexpr int WS_NL = 8, WS_NS = 8, WS_RING = 2, WS_AUX = 2 /* nt */;
@@ -101,7 +111,7 @@ static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int
         all_ws = false;
 #endif
 #define RMCV_K1_LAUNCH(F)                                                                                                             \
-    launch(K1_KERNEL<CA, CB, F>, dim3(grid), dim3(256), planes, s, frames, g.frame_pitch, g.stride, nf, g.w, g.h, g.ww, lb, all_pass, \
+    launch(K1_INST(F), dim3(grid), dim3(256), planes, s, frames, g.frame_pitch, g.stride, nf, g.w, g.h, g.ww, lb, all_pass, \
            morph, binary, bits, g.prow, g.plane_pitch, strips, n_blocks, rowmask, b.strip_ctr, taper_head, taper_tail,               \
            g.pixel_halo_nt K1_EXTRA)
 #if K1_WIN
@@ -112,8 +122,9 @@ static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int
 #undef RMCV_K1_LAUNCH
         if (e != hipSuccess) return e;
     }
-#if !K1_ENH && !K1_WIN
+#if !K1_ENH && !K1_WIN && !K1_CAMP
     if (img) *img = image_step(img_before, {all_ws ? IMAGE_KERNEL_WS : IMAGE_KERNEL_OTHER, image, g.w, g.h, g.ww, g.n_frames}, true).next;
 #endif
     return hipSuccess;
 }
+#undef K1_INST

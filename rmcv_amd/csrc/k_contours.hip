@@ -102,6 +102,7 @@ hipError_t launch_sparse(const Geom& g, const Bufs& b, const Limits& lim, const 
     T.max_blobs = lim.max_blobs;
     T.max_armours = lim.max_armours;
     T.enemy = p.camp;
+    T.enemy_tab = enemy_table(g, b);
     T.do_pairs = pairs ? 1 : 0;
     T.angle_diff_max = p.angle_diff_max;
     T.shear_max = p.shear_max;

@@ -152,8 +152,10 @@ __global__ __launch_bounds__(64) void k_match(const rmcv_point* __restrict__ poi
 __global__ __launch_bounds__(64) void k_armours(const rmcv_lightblob* __restrict__ blobs, const int32_t* __restrict__ n_blobs,
                                                int max_blobs, float angle_diff_max, float shear_max,
                                                float length_ratio_max, int enemy, rmcv_armour* __restrict__ armours,
-                                               int32_t* __restrict__ n_armours, int32_t* __restrict__ status, int max_armours, int ov)
+                                               int32_t* __restrict__ n_armours, int32_t* __restrict__ status, int max_armours, int ov,
+                                               const int32_t* __restrict__ enemy_tab /* nullable: [frame], in place of `enemy` */)
 {
+    if (enemy_tab) enemy = enemy_tab[blockIdx.x];
     armours_frame(blockIdx.x, threadIdx.x, blobs, n_blobs[blockIdx.x], max_blobs, angle_diff_max, shear_max, length_ratio_max, enemy,
                   armours, n_armours, status, max_armours, ov);
 }
@@ -166,14 +168,15 @@ __global__ __launch_bounds__(64) void k_pairs(const int32_t* __restrict__ slot_k
 {
     const int f = blockIdx.x, lane = threadIdx.x;
     __builtin_amdgcn_s_setprio(3);
-    const int np = blob_compact_frame(f, lane, slot_kind, slot_ell, n_contours[f], max_contours, T.enemy, T.blobs, T.blob_src,
+    const int enemy = tail_enemy(T, f);
+    const int np = blob_compact_frame(f, lane, slot_kind, slot_ell, n_contours[f], max_contours, enemy, T.blobs, T.blob_src,
                                       T.ellipses, T.neg_idx, T.n_blobs, T.n_neg, T.status, T.max_blobs);
     if (T.do_pairs) {
         // the pair loop re-reads, across lanes, the blobs this wave has just written: workgroup scope is enough (one CU, one L1) -- at
             // device scope the fence is an L2 write-back + invalidate (buffer_wbl2 sc1, buffer_inv sc1) per frame, on the XCD whose
             // L2 the pixel kernels of the other batches are streaming through: it cost the step 3 %
             __threadfence_block();
-        armours_frame(f, lane, T.blobs, np, T.max_blobs, T.angle_diff_max, T.shear_max, T.length_ratio_max, T.enemy, T.armours,
+        armours_frame(f, lane, T.blobs, np, T.max_blobs, T.angle_diff_max, T.shear_max, T.length_ratio_max, enemy, T.armours,
                       T.n_armours, T.status, T.max_armours, T.ov);
     }
 }
@@ -294,6 +297,7 @@ static hipError_t launch_pairs_tail(const Geom& g, const Bufs& b, const Limits& 
     T.max_blobs = lim.max_blobs;
     T.max_armours = lim.max_armours;
     T.enemy = p.camp;
+    T.enemy_tab = enemy_table(g, b);
     T.do_pairs = pairs ? 1 : 0;
     T.angle_diff_max = p.angle_diff_max;
     T.shear_max = p.shear_max;
@@ -368,7 +372,7 @@ hipError_t launch_blobs_armours(const Geom& g, const Bufs& b, const Limits& lim,
 hipError_t launch_armours(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, hipStream_t s)
 {
     return launch(k_armours, dim3(g.n_frames), dim3(64), 0, s, b.blobs, b.n_blobs, lim.max_blobs, p.angle_diff_max,
-                       p.shear_max, p.length_ratio_max, p.camp, b.armours, b.n_armours, b.status, lim.max_armours, g.overloads);
+                       p.shear_max, p.length_ratio_max, p.camp, b.armours, b.n_armours, b.status, lim.max_armours, g.overloads, enemy_table(g, b));
 }
 
 } // namespace rmcv

@@ -202,6 +202,7 @@ int rmcv_tracker_create(int device, const rmcv_tracker_config* cfg, rmcv_tracker
         {(void**)&t->b.tracks, slots * sizeof(rmcv_track)},      {(void**)&t->b.side, slots * 8 * sizeof(float)},
         {(void**)&t->b.sel, (size_t)c.n_streams * 4},            {(void**)&t->b.n_tracking, (size_t)c.n_streams * 4},
         {(void**)&t->b.status, (size_t)c.n_streams * 4},         {(void**)&t->b.origins, (size_t)c.n_streams * sizeof(rmcv_point)},
+        {(void**)&t->b.camps, (size_t)c.n_streams * 4},          {(void**)&t->b.lower_bounds, (size_t)c.n_streams * 4},
     };
     hipError_t e = hipEventCreateWithFlags(&t->ev_step, hipEventDisableTiming);
     for (auto& w : want) {
@@ -262,6 +263,31 @@ int rmcv_tracker_device_origins(rmcv_tracker* t, void** d_origins)
 {
     if (!t || !d_origins) return RMCV_ERR_BAD_ARG;
     *d_origins = t->b.origins;
+    return RMCV_OK;
+}
+
+int rmcv_tracker_set_camps(rmcv_tracker* t, const int32_t* camps, const int32_t* lower_bounds)
+{
+    if (!t) return RMCV_ERR_BAD_ARG;
+    hipSetDevice(t->device);
+    const int rc = tracker_wait(t); // (the step in flight belongs to a batch whose pixel pass may still read the tables)
+    if (rc) return rc;
+    if (!camps) { // off: tracked submits take rmcv_params::camp and ::lower_bound again
+        t->camps_on = t->lower_bounds_on = false;
+        return RMCV_OK;
+    }
+    TCHK(t, hipMemcpy(t->b.camps, camps, (size_t)t->cfg.n_streams * 4, hipMemcpyHostToDevice), "H2D camps");
+    if (lower_bounds) TCHK(t, hipMemcpy(t->b.lower_bounds, lower_bounds, (size_t)t->cfg.n_streams * 4, hipMemcpyHostToDevice), "H2D lower bounds");
+    t->camps_on = true;
+    t->lower_bounds_on = lower_bounds != nullptr;
+    return RMCV_OK;
+}
+
+int rmcv_tracker_device_camps(rmcv_tracker* t, void** d_camps, void** d_lower_bounds)
+{
+    if (!t) return RMCV_ERR_BAD_ARG;
+    if (d_camps) *d_camps = t->b.camps;
+    if (d_lower_bounds) *d_lower_bounds = t->b.lower_bounds;
     return RMCV_OK;
 }
 

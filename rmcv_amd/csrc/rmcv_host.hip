@@ -112,6 +112,8 @@ struct rmcv_ctx {
     int32_t* order_scratch = nullptr; // [2 * max_frames] k_frame_order's work lists for batches beyond its LDS tables
     int last_stages = 0;              // the stages the batch bound has been through since its last pixel pass (rmcv_batch_track asks for RMCV_STAGE_ARMOURS)
     rmcv_point* win_own = nullptr;    // [max_frames] the context's copy of host origins (rmcv_batch_set_windows); Bufs::win_req points here or at the caller's
+    int32_t* key_own = nullptr;       // [2][max_frames] the context's copy of host camps | lower bounds (rmcv_batch_set_frame_camps); Bufs::key_camps / key_lbs point here or at the caller's
+    int last_camp = RMCV_CAMP_BLUE, last_lower_bound = 80; // rmcv_params::camp, ::lower_bound of the last run with the pixel pass (rmcv_batch_get_frame_keys without per-frame keys)
     char err[256] = {0};
     std::vector<void*> allocs;
     struct Guarded { uint8_t* base; size_t bytes; const char* name; size_t rear = 0; };
@@ -378,6 +380,9 @@ int rmcv_ctx_create(int device, const rmcv_limits* limits, rmcv_ctx** out)
     if (e == hipSuccess) e = dalloc(c, &b.win_eff, F);
     if (e == hipSuccess) e = dalloc(c, &c->win_own, F);
     if (e == hipSuccess) e = dalloc(c, &b.imgmask, F * d.max_height); // (last: every other buffer stays where it was before there was a mask)
+    if (e == hipSuccess) e = dalloc(c, &b.key_eff, F); // (per-frame detection keys: behind the mask, for the same reason)
+    if (e == hipSuccess) e = dalloc(c, &b.key_enemy, F);
+    if (e == hipSuccess) e = dalloc(c, &c->key_own, 2 * F);
     if (e == hipSuccess) {
         hipMemset(b.strip_ctr, 0, 9 * CTR_STRIDE * sizeof(int));
         hipMemset(b.n_contours, 0, F * 4);
@@ -388,6 +393,8 @@ int rmcv_ctx_create(int device, const rmcv_limits* limits, rmcv_ctx** out)
         e = hipMemset(b.status, 0, F * 4);
         if (e == hipSuccess) e = hipMemset(b.win_eff, 0, F * sizeof(rmcv_point));
         if (e == hipSuccess) e = hipMemset(c->win_own, 0, F * sizeof(rmcv_point));
+        if (e == hipSuccess) e = hipMemset(b.key_eff, 0, F * sizeof(FrameKey));
+        if (e == hipSuccess) e = hipMemset(b.key_enemy, 0, F * 4);
     }
     if (e == hipSuccess) { // rmcv_batch_get_gammas before the first run with the option: every frame reads 1 (the identity table)
         const std::vector<float> ones(F, 1.0f);
@@ -655,6 +662,14 @@ static int check_windows(rmcv_ctx* c, int fw, int fh, int fmt, int enh, int win_
     return RMCV_OK;
 }
 
+// what per-frame detection keys refuse of the frames' format (fmt / enh: what they are read as), checked before anything of the context moves
+static int check_frame_camps(rmcv_ctx* c, int fmt, int enh)
+{
+    if (fmt != RMCV_INPUT_BGR) return fail(c, RMCV_ERR_BAD_ARG, "per-frame camps with a Bayer input format (RMCV_OPT_INPUT_FORMAT): the mosaic kernel takes one camp per run; not supported");
+    if (enh) return fail(c, RMCV_ERR_BAD_ARG, "per-frame camps with RMCV_OPT_ENHANCE: the threshold table folds one lower bound per run; not supported");
+    return RMCV_OK;
+}
+
 // Make w x h the extent everything behind the frame loads sees (the frames' own, or their windows').  When it changes the padded planes
 // are zeroed and the frame order is recomputed, as set_geom's comment says.
 static int set_extent(rmcv_ctx* c, int w, int h, hipStream_t as);
@@ -686,6 +701,8 @@ static int set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t
     g.frame_w = w;
     g.frame_h = h;
     g.win = win_w > 0;
+    g.keys = 0; // a new binding returns to per-run keys, as it returns to whole frames
+    c->bufs.key_camps = c->bufs.key_lbs = nullptr;
     return set_extent(c, g.win ? win_w : w, g.win ? win_h : h, as);
 }
 
@@ -754,6 +771,7 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
     // every argument check comes BEFORE the first enqueue (the callers': check_bound): an error return leaves the streams as they were
     if (lp && g.input_format) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
     if (lp && g.enhance) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not with RMCV_OPT_ENHANCE");
+    if (lp && g.keys) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes a camp per blob from BGR means: not with per-frame camps (rmcv_batch_set_frame_camps)");
     if ((rc = order_begin(c, s))) return rc;
     if (c->test_delay_us) { // RMCV_OPT_TEST_DELAY_US: a stand-in for a kernel that does not finish in time (one shot)
         HIPCHK(c, launch_delay((unsigned long long)c->test_delay_us * 1000ull, s), "k_delay (RMCV_OPT_TEST_DELAY_US)");
@@ -776,8 +794,12 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
         if (g.enhance) HIPCHK(c, launch_enhance_tables(g, b, p->lower_bound, s), "k_frame_sums + k_enhance_table");
         // windows: the effective origins first, at RUN time too (the requests may be a tracker's, rewritten on the device since they were set)
         if (g.win) HIPCHK(c, launch_window_origins(g, b, s), "k_window_origins");
+        // per-frame keys: the effective keys first, at RUN time too (the raw tables may be a device-side producer's; lower_bounds null: this run's bound)
+        if (g.keys) HIPCHK(c, launch_frame_keys(g, b, p->lower_bound, s), "k_frame_keys");
+        c->last_camp = p->camp;
+        c->last_lower_bound = p->lower_bound;
         HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, !(stages & RMCV_STAGE_NO_IMAGE), plan, s, &c->image),
-               g.input_format ? "k_binary_bayer" : (g.enhance ? "k_binary_enh" : (g.win ? "k_binary_win" : "k_binary")));
+               g.input_format ? "k_binary_bayer" : (g.enhance ? "k_binary_enh" : (g.keys ? (g.win ? "k_binary_camp_win" : "k_binary_camp") : (g.win ? "k_binary_win" : "k_binary"))));
     }
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
     // the icon classifier rides in the per-frame kernel when the armours come from it (BASELINE config 5: no launch of its own)
@@ -882,20 +904,25 @@ namespace rmcv {
 // rmcv_batch_set_device_frames for a pipeline: nothing blocks -- a change of geometry is enqueued on `s`, which the caller has made
 // wait for the context's last batch
 int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t s,
-                    const void* d_origins, int win_w, int win_h)
+                    const void* d_origins, int win_w, int win_h, const void* d_camps, const void* d_lower_bounds)
 {
     if (!c || !d_frames || !s) return RMCV_ERR_BAD_ARG;
     resident_none(c);
     int rc = check_sample_ptr(c, d_frames);
     if (rc) return rc;
+    if (d_camps && (rc = check_frame_camps(c, c->input_format, c->enhance))) return rc;
     if (d_origins && win_w <= 0) return fail(c, RMCV_ERR_BAD_ARG, "window size out of range: win_w and win_h must be at least 1");
     rc = set_geom(c, n_frames, w, h, stride, frame_pitch, s, d_origins ? win_w : 0, win_h);
     if (rc) return rc;
     c->bufs.frames = (const uint8_t*)d_frames;
     c->bufs.win_req = (const rmcv_point*)d_origins; // (the run computes the effective origins in front of its pixel pass)
+    c->geom.keys = d_camps != nullptr;              // (... and the effective keys)
+    c->bufs.key_camps = (const int32_t*)d_camps;
+    c->bufs.key_lbs = d_camps ? (const int32_t*)d_lower_bounds : nullptr;
     c->last_stages = 0;
     return RMCV_OK;
 }
+int ctx_check_frame_camps(rmcv_ctx* c) { return check_frame_camps(c, c->input_format, c->enhance); }
 // what binding a batch would allocate, now (a pipeline does this for every context of its ring when it is created)
 int ctx_prepare_ring(rmcv_ctx* c) { return ensure_mid(c, c->lim.max_frames); }
 int ctx_run(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_params* lp, int stages, hipStream_t s, const RunPlan& plan, bool* lean)
@@ -922,6 +949,7 @@ int rmcv_batch_run_legacy(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_p
     if (!lp) return fail(c, RMCV_ERR_BAD_ARG, "null legacy params");
     if (c->input_format || c->geom.input_format) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
     if (c->enhance || c->geom.enhance) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not with RMCV_OPT_ENHANCE");
+    if (c->geom.keys) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes a camp per blob from BGR means: not with per-frame camps (rmcv_batch_set_frame_camps)");
     hipSetDevice(c->device);
     return run_stages(c, p, stages, hip_stream ? (hipStream_t)hip_stream : c->stream, false, ctx_plan(c), lp);
 }
@@ -1373,6 +1401,7 @@ static int enqueue_blobs(rmcv_ctx* c, const rmcv_ctx::LbParams& q, bool compute 
     p.camp = q.enemy;
     Geom g1 = c->geom;
     g1.n_frames = 1;
+    g1.keys = 0; // (the caller's enemy, whatever keys the batch bound to the context has)
     const Bufs& b = c->bufs;
     hipStream_t s = c->stream;
     if (compute) {
@@ -1422,6 +1451,7 @@ static int enqueue_armours(rmcv_ctx* c, const rmcv_ctx::ArParams& q, bool comput
     p.camp = q.enemy;
     Geom g1 = c->geom;
     g1.n_frames = 1;
+    g1.keys = 0; // (the caller's enemy, whatever keys the batch bound to the context has)
     const Bufs& b = c->bufs;
     hipStream_t s = c->stream;
     if (compute) {
@@ -1797,6 +1827,7 @@ int rmcv_fit_ellipse(rmcv_ctx* c, const rmcv_point* pts, int n, rmcv_rrect* out)
     p.area_hi = 1e300;
     Geom g1 = c->geom;
     g1.n_frames = 1;
+    g1.keys = 0;
     HIPCHK(c, launch_blobs(g1, c->bufs, c->lim, p, c->stream), "k_blobs");
     WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
     int32_t nb = 0, nn = 0;
@@ -1989,6 +2020,7 @@ static int match_one(rmcv_ctx* c, const rmcv_point* pts, int n, const rmcv_legac
     rmcv_default_params(&p);
     Geom g1 = c->geom;
     g1.n_frames = 1;
+    g1.keys = 0;
     HIPCHK(c, launch_match(g1, c->bufs, c->lim, p, lp, mode, false, false, c->stream), "k_match");
     WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
     int32_t nb = 0, st = 0;
@@ -2196,6 +2228,79 @@ int rmcv_batch_device_windows(rmcv_ctx* c, void** d_eff, int32_t* win_w, int32_t
     if (d_eff) *d_eff = c->geom.win ? c->bufs.win_eff : nullptr;
     if (win_w) *win_w = c->geom.win ? c->geom.w : 0;
     if (win_h) *win_h = c->geom.win ? c->geom.h : 0;
+    return RMCV_OK;
+}
+
+/* ---- per-frame detection keys: every frame of the batch bound has its own camp and lower bound (serial_package::target per frame) ---- */
+
+// camps / lower bounds: the host's (copied into the context's own tables) or the caller's device memory (borrowed); both camps null: per-run keys
+static int set_frame_camps(rmcv_ctx* c, const int32_t* h_camps, const int32_t* h_lbs, const void* d_camps, const void* d_lbs)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    Geom& g = c->geom;
+    if (g.n_frames <= 0 || !c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, "no frames bound: per-frame camps are set after the frames");
+    hipSetDevice(c->device);
+    resident_none(c);
+    if (!h_camps && !d_camps) { // per-run keys again
+        g.keys = 0;
+        c->bufs.key_camps = c->bufs.key_lbs = nullptr;
+        return RMCV_OK;
+    }
+    int rc = check_frame_camps(c, g.input_format, g.enhance);
+    if (rc) return rc;
+    if (h_camps) {
+        if ((rc = rmcv_batch_sync(c))) return rc; // the tables about to be rewritten may still be read by a batch in flight
+        int32_t* own_lbs = c->key_own + c->lim.max_frames;
+        HIPCHK(c, hipMemcpy(c->key_own, h_camps, (size_t)g.n_frames * 4, hipMemcpyHostToDevice), "H2D frame camps");
+        if (h_lbs) HIPCHK(c, hipMemcpy(own_lbs, h_lbs, (size_t)g.n_frames * 4, hipMemcpyHostToDevice), "H2D frame lower bounds");
+        c->bufs.key_camps = c->key_own;
+        c->bufs.key_lbs = h_lbs ? own_lbs : nullptr;
+    } else {
+        c->bufs.key_camps = (const int32_t*)d_camps;
+        c->bufs.key_lbs = (const int32_t*)d_lbs;
+    }
+    g.keys = 1;
+    return RMCV_OK;
+}
+
+int rmcv_batch_set_frame_camps(rmcv_ctx* c, const int32_t* camps, const int32_t* lower_bounds)
+{
+    return set_frame_camps(c, camps, camps ? lower_bounds : nullptr, nullptr, nullptr);
+}
+
+int rmcv_batch_set_device_frame_camps(rmcv_ctx* c, const void* d_camps, const void* d_lower_bounds)
+{
+    return set_frame_camps(c, nullptr, nullptr, d_camps, d_camps ? d_lower_bounds : nullptr);
+}
+
+int rmcv_batch_get_frame_keys(rmcv_ctx* c, int32_t* keys_out, int cap)
+{
+    if (!c || cap < 0 || (cap > 0 && !keys_out)) return RMCV_ERR_BAD_ARG;
+    hipSetDevice(c->device);
+    int rc = rmcv_batch_sync(c);
+    if (rc) return rc;
+    const Geom& g = c->geom;
+    const int n = std::min(cap, g.n_frames);
+    if (n <= 0) return RMCV_OK;
+    static_assert(sizeof(FrameKey) == 4 * sizeof(int32_t), "rmcv_batch_get_frame_keys hands the table out as [frame][4] int32");
+    if (!g.keys) { // per-run keys: the last run's, for every frame
+        const FrameKey k = frame_key_eff(c->last_camp, c->last_lower_bound);
+        for (int f = 0; f < n; f++) memcpy(keys_out + 4 * f, &k, sizeof(k));
+        return RMCV_OK;
+    }
+    HIPCHK(c, hipMemcpy(keys_out, c->bufs.key_eff, (size_t)n * sizeof(FrameKey), hipMemcpyDeviceToHost), "D2H frame keys");
+    return RMCV_OK;
+}
+
+/* the rule from raw camp and lower bound to what the kernels use (frame_key_eff, the function k_frame_keys runs): host-side, no context, no device */
+int rmcv_frame_key(int32_t camp, int32_t lower_bound, int32_t out[4])
+{
+    if (!out) return RMCV_ERR_BAD_ARG;
+    const FrameKey k = frame_key_eff(camp, lower_bound);
+    out[0] = k.ca;
+    out[1] = k.cb;
+    out[2] = k.lb;
+    out[3] = k.all_pass;
     return RMCV_OK;
 }
 

@@ -42,6 +42,9 @@ struct Geom {
     // sees a batch of win_w x win_h images -- while stride and frame_pitch stay the frames'; the frames' own extent is kept here
     int win;             // 1: every frame is read at its effective origin (Bufs::win_eff)
     int frame_w, frame_h; // the frames as bound (== w, h without windows)
+    // per-frame detection keys (rmcv_batch_set_frame_camps): camp and lower bound of every frame come from Bufs::key_eff / key_enemy, which every
+    // run with the pixel pass rewrites in front of it; rmcv_params::camp and ::lower_bound are then not read
+    int keys;
 };
 
 // What a run's launches depend on beyond geometry, buffers and params.  The public entry points take it from the context's options
@@ -70,6 +73,25 @@ inline size_t mid_bytes(int slot_cap)
 struct Limits {
     int max_frames, max_width, max_height, max_contours, max_points, max_blobs, max_armours;
 };
+
+// The effective detection key of a frame, the one place it is computed -- by k_frame_keys on the device and by
+// rmcv_frame_key on the host: raw camp and lower bound, any int32 (a device-side producer may write them), -> what the pixel kernels use.
+//   channel pair (imgproc.cpp:56-65, BGR byte order): GUIDELIGHT G-R; BLUE B-R; every other value R-B
+//   bound (inRange(gray, lb, 255) on a saturated u8 difference): lb <= 0 every pixel passes; lb > 255 none; otherwise a - b >= lb
+struct FrameKey {
+    int32_t ca, cb;   // byte of channel A / channel B inside a BGR pixel
+    int32_t lb;       // effective bound, 1 .. 256
+    int32_t all_pass; // 1: every pixel passes (lb is 1 then)
+};
+__host__ __device__ inline FrameKey frame_key_eff(int32_t camp, int32_t lower_bound)
+{
+    FrameKey k;
+    k.ca = camp == RMCV_CAMP_GUIDELIGHT ? 1 : (camp == RMCV_CAMP_BLUE ? 0 : 2);
+    k.cb = (camp == RMCV_CAMP_GUIDELIGHT || camp == RMCV_CAMP_BLUE) ? 2 : 0;
+    k.all_pass = lower_bound <= 0 ? 1 : 0;
+    k.lb = lower_bound <= 0 ? 1 : (lower_bound > 256 ? 256 : lower_bound);
+    return k;
+}
 
 // Device buffers of one context (all sized by Limits at creation, reused by every call).
 struct Bufs {
@@ -127,7 +149,14 @@ struct Bufs {
     // windowed detection (Geom::win): rewritten by every run that includes the pixel pass, in front of it
     const rmcv_point* win_req; // [frame] the requested origins, any value (the context's own copy of host origins, or the caller's device memory)
     rmcv_point* win_eff;   // [frame]      the effective origins (window_origin_eff): what every consumer of the frames reads
+    // per-frame detection keys (Geom::keys): rewritten by every run that includes the pixel pass, in front of it
+    const int32_t* key_camps; // [frame] the raw camps, any value (the context's own copy of host values, or the caller's device memory)
+    const int32_t* key_lbs;   // [frame] the raw lower bounds, any value; null: the run's rmcv_params::lower_bound for every frame
+    FrameKey* key_eff;     // [frame]      the effective keys (frame_key_eff): what the pixel kernel reads
+    int32_t* key_enemy;    // [frame]      the raw camp once more: blobs[].target and what pairing compares against (the sparse stage reads it)
 };
+// the per-frame enemy label of a launch's frames: null without keys (the launch then uses rmcv_params::camp)
+inline const int32_t* enemy_table(const Geom& g, const Bufs& b) { return g.keys ? b.key_enemy : nullptr; }
 
 // The effective origin of a window, the one place it is computed: clamped into the frame, x snapped down to a multiple
 // of 16 pixels (48 bytes: window rows keep the 16-byte alignment the raw-buffer loader wants).  Part of the semantics, always applied.
@@ -202,6 +231,13 @@ hipError_t launch_binary_enh(const Geom& g, const Bufs& b, int camp, int lower_b
 hipError_t launch_window_origins(const Geom& g, const Bufs& b, hipStream_t s);
 // the pixel stage of a windowed batch (Geom::win; launch_binary hands such batches to it): k_binary's shape, row-quad or byte-wise loader
 hipError_t launch_binary_win(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s);
+// per-frame detection keys (k_binary_camp.hip).  launch_frame_keys: Bufs::key_camps, ::key_lbs (or run_lower_bound) -> Bufs::key_eff, ::key_enemy for
+// the frames bound, in front of the pixel pass
+hipError_t launch_frame_keys(const Geom& g, const Bufs& b, int run_lower_bound, hipStream_t s);
+// the pixel stage of a batch with keys (Geom::keys; launch_binary hands such batches to it): k_binary's shape with the key read per strip, all
+// three loaders; with windows too (k_binary_camp_win.hip: row-quad or byte-wise loader); never k_binary_ws
+hipError_t launch_binary_camp(const Geom& g, const Bufs& b, int morph, bool image, const RunPlan& plan, hipStream_t s);
+hipError_t launch_binary_camp_win(const Geom& g, const Bufs& b, int morph, bool image, const RunPlan& plan, hipStream_t s);
 // dst[i] = lut[src[i]] over n16 16-byte vectors of a staged image (rm::CalcGamma); dst == src allowed
 hipError_t launch_bytemap(const uint8_t* d_src, uint8_t* d_dst, int64_t n16, const uint8_t* d_lut, int n_cu, hipStream_t s);
 // lut[0..255] of `gamma` on the device (the table builder of enhance_math.h)
@@ -261,8 +297,11 @@ int ctx_run(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_params* lp, int
 // rmcv_batch_set_device_frames without a blocking call: a change of geometry (planes zeroed, frame order recomputed) is ENQUEUED on `s`,
 // which the caller has made wait for the context's last batch
 // d_origins non-null: a windowed batch (rmcv_batch_set_device_windows in the same step: ONE change of geometry, the window's)
+// d_camps non-null: per-frame detection keys (rmcv_batch_set_device_frame_camps in the same step; d_lower_bounds nullable)
 int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t s,
-                    const void* d_origins = nullptr, int win_w = 0, int win_h = 0);
+                    const void* d_origins = nullptr, int win_w = 0, int win_h = 0, const void* d_camps = nullptr, const void* d_lower_bounds = nullptr);
+// what per-frame keys refuse of a context as it is set (a Bayer input format, RMCV_OPT_ENHANCE), checked without enqueuing anything
+int ctx_check_frame_camps(rmcv_ctx* c);
 // everything binding a full batch would allocate (the mid tier's scratch), now
 int ctx_prepare_ring(rmcv_ctx* c);
 // allocations, host-side synchronisations and blocking copies this context has made while binding geometries
@@ -295,6 +334,8 @@ struct TrackerBufs {
     int32_t* n_tracking; // [n_streams]
     int32_t* status;     // [n_streams] RMCV_TRACKER_OVF
     rmcv_point* origins; // [n_streams] the requested window origins (what Bufs::win_req borrows)
+    int32_t* camps;      // [n_streams] every stream's enemy colour and lower bound (rmcv_tracker_set_camps; what Bufs::key_camps / key_lbs borrow)
+    int32_t* lower_bounds;
 };
 // one step for the n_streams frames of the batch in `b`; identity / pose: the run included those stages; win_eff: null without windows
 hipError_t launch_track(const rmcv_tracker_config& cfg, const TrackerBufs& tb, const Bufs& b, const Limits& lim, bool identity, bool pose,
@@ -336,4 +377,6 @@ struct rmcv_tracker {
     rmcv_aim_config aim_cfg{};
     rmcv_aim_input* aim_inputs = nullptr; // [n_streams]
     rmcv_aim* aims = nullptr;             // [n_streams]
+    // per-stream detection keys: off until rmcv_tracker_set_camps
+    bool camps_on = false, lower_bounds_on = false;
 };

@@ -584,9 +584,10 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
 }
 
 // d_origins non-null: a windowed batch (rmcv_pipeline_submit_windows) -- every frame read through a win_w x win_h window
+// d_camps non-null: per-frame detection keys (rmcv_pipeline_submit_camps; d_lower_bounds nullable) -- taken per batch, as windows are
 static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, const rmcv_params* p,
                   const rmcv_legacy_params* lp, int stages, uint64_t* ticket, const void* d_origins = nullptr, int win_w = 0, int win_h = 0,
-                  rmcv_tracker* trk = nullptr, int64_t timestamp = 0)
+                  rmcv_tracker* trk = nullptr, int64_t timestamp = 0, const void* d_camps = nullptr, const void* d_lower_bounds = nullptr)
 {
     if (!pl || !d_frames || !p) return RMCV_ERR_BAD_ARG;
     if (!(stages & RMCV_STAGE_BINARY)) return pfail(pl, RMCV_ERR_BAD_ARG, "a pipelined batch starts at RMCV_STAGE_BINARY");
@@ -625,7 +626,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     // (so do batches read through their gamma tables, RMCV_OPT_ENHANCE on the slot's context: they take the k_binary shape, and the sums pass in
     // front of it has no use for another batch's planes in the cache)
     // (and windowed batches: the k_binary shape too, and a geometry of their own -- in the rotation they would re-zero the hot contexts' planes)
-    const bool fast = pl->hot && pl->calm && !lp && !(stages & RMCV_STAGE_POSE) && !(stages & RMCV_STAGE_IDENTITY) && !ctx_enhance(pl->ring[k]) && !d_origins && !trk; // (nor tracked ones: the step reads the context's lists behind the compaction)
+    const bool fast = pl->hot && pl->calm && !lp && !(stages & RMCV_STAGE_POSE) && !(stages & RMCV_STAGE_IDENTITY) && !ctx_enhance(pl->ring[k]) && !d_origins && !d_camps && !trk; // (nor batches with per-frame keys: the k_binary shape as well; nor tracked ones: the step reads the context's lists behind the compaction)
     const size_t j = fast ? (size_t)(pl->hot_seq % (uint64_t)pl->hot) : k;
     rmcv_ctx* c = pl->ring[j];
     int rc;
@@ -636,6 +637,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
         if (ctx_enhance(pl->ring[i]) != ctx_enhance(pl->ring[0]))
             return pfail(pl, RMCV_ERR_BAD_ARG, "RMCV_OPT_ENHANCE differs between the pipeline's contexts: set it on EVERY slot (rmcv_pipeline_context)");
     if (lp && ctx_enhance(c)) return pfail(pl, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not with RMCV_OPT_ENHANCE");
+    if (d_camps && (rc = ctx_check_frame_camps(c))) return cfail(pl, c, rc); // (a Bayer input format, RMCV_OPT_ENHANCE: refused before anything is enqueued)
     // a batch is several runs on several streams: everything that could refuse it is checked before the first enqueue (the binding below
     // enqueues a new geometry's work on A)
     if ((rc = ctx_check_stages(c, p, stages))) return cfail(pl, c, rc);
@@ -660,7 +662,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
         PCHK(pl, hipStreamWaitEvent(A, early ? pl->ev_free[last] : pl->ev_done[last], 0), "pipeline: wait for the context");
     }
     // ---- bind: a new geometry's work (planes zeroed, frame order) is ENQUEUED on A, nothing blocks
-    rc = ctx_bind_frames(c, d_frames, n_frames, w, h, stride, frame_pitch, A, d_origins, win_w, win_h);
+    rc = ctx_bind_frames(c, d_frames, n_frames, w, h, stride, frame_pitch, A, d_origins, win_w, win_h, d_camps, d_lower_bounds);
     if (rc) return cfail(pl, c, rc);
     const int pixel = stages & (RMCV_STAGE_BINARY | RMCV_STAGE_NO_IMAGE), sparse = stages & ~(RMCV_STAGE_BINARY | RMCV_STAGE_NO_IMAGE);
     ctx_external_order(c, pl->ev_done[k]);
@@ -695,7 +697,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     if (trk && d_origins) PCHK(pl, tracker_wait_on(trk, A), "pipeline: wait for the tracker's last step");
     rc = ctx_run(c, p, nullptr, pixel, A, plan);
     if (rc) return cfail(pl, c, rc);
-    pl->last_what = ctx_input_format(c) ? "the pixel kernel (k_binary_bayer)" : ctx_bound_enhance(c) ? "k_frame_sums, k_enhance_table, the pixel kernel (k_binary_enh)" : ctx_bound_windows(c) ? "k_window_origins, the pixel kernel (k_binary_win)" : "the pixel kernel (k_binary / k_binary_ws)";
+    pl->last_what = ctx_input_format(c) ? "the pixel kernel (k_binary_bayer)" : ctx_bound_enhance(c) ? "k_frame_sums, k_enhance_table, the pixel kernel (k_binary_enh)" : d_camps ? "k_frame_keys, the pixel kernel (k_binary_camp / k_binary_camp_win)" : ctx_bound_windows(c) ? "k_window_origins, the pixel kernel (k_binary_win)" : "the pixel kernel (k_binary / k_binary_ws)";
     // ---- accepted: the pipeline's state moves
     pl->was_cold = cold;
     if (fast) { pl->hot_seq++; pl->hot_batches++; }
@@ -729,13 +731,13 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
 // submit + its own bookkeeping: the host time of the call, and the blocking calls the ring's contexts counted during it
 static int submit_counted(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, const rmcv_params* p,
                           const rmcv_legacy_params* lp, int stages, uint64_t* ticket, const void* d_origins = nullptr, int win_w = 0, int win_h = 0,
-                          rmcv_tracker* trk = nullptr, int64_t timestamp = 0)
+                          rmcv_tracker* trk = nullptr, int64_t timestamp = 0, const void* d_camps = nullptr, const void* d_lower_bounds = nullptr)
 {
     if (!pl) return RMCV_ERR_BAD_ARG;
     timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     const uint64_t b0 = ring_blocking(pl);
-    const int rc = submit(pl, d_frames, n_frames, w, h, stride, frame_pitch, p, lp, stages, ticket, d_origins, win_w, win_h, trk, timestamp);
+    const int rc = submit(pl, d_frames, n_frames, w, h, stride, frame_pitch, p, lp, stages, ticket, d_origins, win_w, win_h, trk, timestamp, d_camps, d_lower_bounds);
     pl->own_blocking += ring_blocking(pl) - b0;
     clock_gettime(CLOCK_MONOTONIC, &t1);
     const double us = (t1.tv_sec - t0.tv_sec) * 1e6 + (t1.tv_nsec - t0.tv_nsec) * 1e-3;
@@ -779,8 +781,23 @@ int rmcv_pipeline_submit_tracked(rmcv_pipeline* pl, rmcv_tracker* trk, const voi
     if (!trk) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_tracked: null tracker");
     const rmcv_tracker_config& tc = tracker_config(trk);
     // win_w > 0: a windowed submit whose origins are the tracker's; win_w == 0: whole frames (track only)
+    // a tracker with per-stream camps (rmcv_tracker_set_camps): a stream's colour is the stream's -- the submit takes the tracker's tables
+    const TrackerBufs& tb = tracker_bufs(trk);
     return submit_counted(pl, d_frames, n_frames, frame_w, frame_h, stride, frame_pitch, p, nullptr, stages, ticket,
-                          tc.win_w > 0 ? tracker_bufs(trk).origins : nullptr, tc.win_w, tc.win_h, trk, timestamp);
+                          tc.win_w > 0 ? tb.origins : nullptr, tc.win_w, tc.win_h, trk, timestamp, trk->camps_on ? tb.camps : nullptr,
+                          trk->camps_on && trk->lower_bounds_on ? tb.lower_bounds : nullptr);
+}
+
+int rmcv_pipeline_submit_camps(rmcv_pipeline* pl, const void* d_frames, int n_frames, int frame_w, int frame_h, int stride, int64_t frame_pitch,
+                               const void* d_camps, const void* d_lower_bounds, const void* d_origins, int win_w, int win_h, const rmcv_params* p,
+                               int stages, uint64_t* ticket)
+{
+    if (!pl) return RMCV_ERR_BAD_ARG;
+    if (!d_camps) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_camps: null camps (device memory: one int32 per frame)");
+    if (win_w != 0 && !d_origins) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_camps: null origins (device memory: one rmcv_point per frame; win_w == 0: whole frames)");
+    if (win_w < 0 || (win_w > 0 && win_h < 1)) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_camps: window size out of range");
+    return submit_counted(pl, d_frames, n_frames, frame_w, frame_h, stride, frame_pitch, p, nullptr, stages, ticket, win_w > 0 ? d_origins : nullptr,
+                          win_w, win_h, nullptr, 0, d_camps, d_lower_bounds);
 }
 
 // slot of a live ticket, or -1

@@ -488,7 +488,13 @@ struct FitTail { // what k_pairs needs to finish filter_lightblobs and run filte
     int max_blobs, max_armours, enemy, do_pairs;
     float angle_diff_max, shear_max, length_ratio_max;
     int ov; // SURVEY A.6 (device_fit.h: abs_ov)
+    const int32_t* enemy_tab; // nullable: [frame] the enemy per frame (per-frame detection keys, Bufs::key_enemy) in place of `enemy`
 };
+// the enemy label of frame f (f is wave-uniform at every caller -- blockIdx.x, or the frame-order table at it -- so this is one scalar load)
+__device__ __forceinline__ int tail_enemy(const FitTail& T, int f)
+{
+    return T.enemy_tab ? T.enemy_tab[f] : T.enemy;
+}
 
 // ordered compaction of the per-contour results of frame f into the reference's `positive` / `negative` lists
 // (one wavefront); returns the number of positives

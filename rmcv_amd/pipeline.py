@@ -78,23 +78,31 @@ class Pipeline:
         return o
 
     # ------------------------------------------------------------------ the three calls
-    def submit(self, data_ptr, n, h, w, params=None, stages=STAGE_ALL, stride=None, frame_pitch=None, keepalive=None, legacy=None, windows=None, tracker=None, timestamp=0):
+    def submit(self, data_ptr, n, h, w, params=None, stages=STAGE_ALL, stride=None, frame_pitch=None, keepalive=None, legacy=None, windows=None, tracker=None, timestamp=0, camps=None):
         """enqueue one batch of frames resident in HBM (data_ptr: e.g. torch_tensor.data_ptr()); returns the ticket.
         windows = (d_origins_ptr, win_w, win_h): a windowed batch -- d_origins_ptr a device pointer to n (x, y) int32 pairs (e.g. an
         int32 (n, 2) torch tensor's data_ptr(); keep it alive like the frames), results in window coordinates (Context.set_windows).
         tracker = a rmcv_amd.Tracker (+ timestamp): a tracked batch (rmcv_pipeline_submit_tracked) -- windowed at the tracker's own origins
         when its win_w > 0, whole frames otherwise; one step of the tracker runs behind the batch, and the next tracked submit on that
-        tracker reads the origins it wrote: the closed loop with the host only submitting"""
+        tracker reads the origins it wrote: the closed loop with the host only submitting
+        camps = (d_camps_ptr, d_lower_bounds_ptr or None): per-frame detection keys (rmcv_pipeline_submit_camps) -- device pointers to n
+        int32 each (keep them alive like the frames); composes with windows=.  A tracker with set_camps brings its own."""
         if params is not None:
             self._params = params
         stride = stride or (w * self.sample_bits // 8 if self.input_format else 3 * w)
         frame_pitch = frame_pitch or stride * h
         if tracker is not None:
-            assert legacy is None and windows is None, "a tracked batch takes its windows from the tracker"
+            assert legacy is None and windows is None and camps is None, "a tracked batch takes its windows and camps from the tracker"
             rc = self._lib.rmcv_pipeline_submit_tracked(self._h, tracker._h, data_ptr, n, w, h, stride, frame_pitch, C.addressof(self._params), int(stages),
                                                         int(timestamp), C.addressof(self._ticket))
             if tracker.config.win_w > 0:
                 windows = (0, tracker.config.win_w, tracker.config.win_h)   # (the shape of what the getters return)
+        elif camps is not None:
+            assert legacy is None, "the legacy matcher votes a camp per blob: no per-frame camps"
+            d_camps, d_lbs = camps
+            d_origins, win_w, win_h = windows if windows is not None else (0, 0, 0)
+            rc = self._lib.rmcv_pipeline_submit_camps(self._h, data_ptr, n, w, h, stride, frame_pitch, int(d_camps), None if d_lbs is None else int(d_lbs),
+                                                      int(d_origins) or None, int(win_w), int(win_h), C.addressof(self._params), int(stages), C.addressof(self._ticket))
         elif windows is not None:
             assert legacy is None, "the legacy matcher has no windowed submit"
             d_origins, win_w, win_h = windows

@@ -108,6 +108,24 @@ class Tracker:
         self._chk(self._lib.rmcv_tracker_device_origins(self._h, C.byref(d)))
         return d.value
 
+    def set_camps(self, camps, lower_bounds=None):
+        """per-stream detection keys: n_streams integers each, copied into tables the tracker owns (lower_bounds None: the run's
+        params.lower_bound; camps None: off).  Pipeline.submit(..., tracker=) on such a tracker detects stream f with camps[f]."""
+        if camps is None:
+            self._chk(self._lib.rmcv_tracker_set_camps(self._h, None, None))
+            return
+        c = np.ascontiguousarray(camps, np.int32).reshape(-1)
+        lb = None if lower_bounds is None else np.ascontiguousarray(lower_bounds, np.int32).reshape(-1)
+        assert len(c) == self.n_streams and (lb is None or len(lb) == self.n_streams)
+        self._chk(self._lib.rmcv_tracker_set_camps(self._h, ptr(c), ptr(lb)))
+
+    def device_camps(self):
+        """device pointers (ints) of the tracker's camps and lower-bounds tables (n_streams int32 each): for a device-side writer, and what
+        Context.set_frame_camps / Pipeline.submit(camps=) borrow"""
+        d, e = C.c_void_p(), C.c_void_p()
+        self._chk(self._lib.rmcv_tracker_device_camps(self._h, C.byref(d), C.byref(e)))
+        return d.value, e.value
+
     def counts(self):
         """(n_tracking int32[n_streams], status int32[n_streams]); synchronous"""
         n, st = np.zeros(self.n_streams, np.int32), np.zeros(self.n_streams, np.int32)
