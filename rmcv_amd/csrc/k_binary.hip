@@ -45,44 +45,32 @@ int64_t pixel_image_delta_launches() { return g_image_delta_launches.load(std::m
 #define K1_EXTRA
 #include "k_binary_launch.inc"
 
-// launch_binary_t's own rule, for the pipeline's hold-back of a burst's second launch: will the batch bound to (g, b) run as ONE launch of
-// k_binary_ws with a workgroup on every CU?
-bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound, int pixel_ws)
-{
-    const int strips = (g.h + SR - 1) / SR;
-    const bool aligned = (g.w % 64 == 0) && (g.stride % 16 == 0) && (g.frame_pitch % 16 == 0) && ((uintptr_t)b.frames % 16 == 0);
-    const int64_t lim = 0xFFFFF000ll;
-    const int64_t per_frame = std::max<int64_t>(std::max<int64_t>(g.frame_pitch, g.plane_pitch * 8), (int64_t)g.w * g.h);
-    const bool one_launch = aligned && (int64_t)g.n_frames * per_frame < lim;
-    const bool linear = one_launch && !g.pixel_rowquad && g.stride == 3 * g.w;
-    const int n_cu = g.n_cu > 0 ? g.n_cu : 256, n_blocks = g.n_frames * strips;
-    const size_t planes_ws = ((size_t)2 * (SR + 4) + SR) * g.ww * sizeof(uint64_t);
-    return g.input_format == RMCV_INPUT_BGR && !g.enhance && !g.win && !g.keys && pixel_ws && linear && lower_bound > 0 && n_blocks * 2 > n_cu && planes_ws <= 60 * 1024 && n_blocks >= n_cu;
-}
-
 hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s,
                          ImageState* img)
 {
-    if (g.input_format != RMCV_INPUT_BGR || g.enhance || g.win || g.keys) {
-        // these kernels store every byte of the image and know nothing of its mask (image_plan.h: IMAGE_KERNEL_OTHER)
-        const ImageLaunch l = {IMAGE_KERNEL_OTHER, image, g.w, g.h, g.ww, g.n_frames};
-        const ImageState before = img ? *img : IMAGE_STATE_UNKNOWN;
-        if (img) *img = image_step(before, l, false).next;
-        // a Bayer mosaic (RMCV_OPT_INPUT_FORMAT): its own kernel, never k_binary_ws (k_binary_bayer.hip)
-        // through the frames' gamma tables (RMCV_OPT_ENHANCE): the same kernel with a lookup in its compare (k_binary_enh.hip)
-        // a window of every frame (rmcv_batch_set_windows): the same kernel reading from the frames' effective origins (k_binary_win.hip)
-        // per-frame detection keys (rmcv_batch_set_frame_camps): the same kernel reading camp and bound per strip, windows or not (k_binary_camp.hip)
-        const hipError_t e = g.input_format != RMCV_INPUT_BGR ? launch_binary_bayer(g, b, camp, lower_bound, morph, image, s)
-                             : g.enhance                      ? launch_binary_enh(g, b, camp, lower_bound, morph, image, plan, s)
-                             : g.keys                         ? launch_binary_camp(g, b, morph, image, plan, s)
-                                                              : launch_binary_win(g, b, camp, lower_bound, morph, image, plan, s);
-        if (img && e == hipSuccess) *img = image_step(before, l, true).next;
-        return e;
-    }
+    const PixelVariant v = pixel_variant(g.input_format, g.enhance, g.win, g.keys);
     // imgproc.cpp:56-65: GUIDELIGHT G-R; BLUE B-R; everything else (RED, NEUTRAL) R-B.  BGR byte order.
-    if (camp == RMCV_CAMP_GUIDELIGHT) return launch_binary_t<1, 2>(g, b, lower_bound, morph, image, plan, s, img);
-    if (camp == RMCV_CAMP_BLUE) return launch_binary_t<0, 2>(g, b, lower_bound, morph, image, plan, s, img);
-    return launch_binary_t<2, 0>(g, b, lower_bound, morph, image, plan, s, img);
+    if (v == PIXEL_BGR)
+        return with_channel_pair(frame_key_eff(camp, lower_bound), [&](auto ca, auto cb) { return launch_binary_t<ca, cb>(g, b, lower_bound, morph, image, plan, s, img); });
+    // the other kernels store every byte of the image and know nothing of its mask (image_plan.h: IMAGE_KERNEL_OTHER)
+    const ImageLaunch l = {IMAGE_KERNEL_OTHER, image, g.w, g.h, g.ww, g.n_frames};
+    const ImageState before = img ? *img : IMAGE_STATE_UNKNOWN;
+    if (img) *img = image_step(before, l, false).next;
+    hipError_t e = hipSuccess;
+    switch (v) {
+    case PIXEL_BGR: break;
+    // a Bayer mosaic (RMCV_OPT_INPUT_FORMAT): its own kernel (k_binary_bayer.hip)
+    case PIXEL_BAYER: e = launch_binary_bayer(g, b, camp, lower_bound, morph, image, s); break;
+    // through the frames' gamma tables (RMCV_OPT_ENHANCE): the same kernel with a lookup in its compare (k_binary_enh.hip)
+    case PIXEL_ENH: e = launch_binary_enh(g, b, camp, lower_bound, morph, image, plan, s); break;
+    // a window of every frame (rmcv_batch_set_windows): the same kernel reading from the frames' effective origins (k_binary_win.hip)
+    case PIXEL_WIN: e = launch_binary_win(g, b, camp, lower_bound, morph, image, plan, s); break;
+    // per-frame detection keys (rmcv_batch_set_frame_camps): the same kernel reading camp and bound per strip (k_binary_camp.hip), windows or not
+    case PIXEL_CAMP: e = launch_binary_camp(g, b, morph, image, plan, s); break;
+    case PIXEL_CAMP_WIN: e = launch_binary_camp_win(g, b, morph, image, plan, s); break;
+    }
+    if (img && e == hipSuccess) *img = image_step(before, l, true).next;
+    return e;
 }
 
 // binary (0 / non-zero bytes) -> padded bit plane; used when a caller hands in its own binary image

@@ -382,11 +382,8 @@ hipError_t launch_demosaic(const uint8_t* d_raw, int stride, int w, int h, int p
 }
 
 template <int CA, int CB>
-static hipError_t launch_bayer_t(const Geom& g, const Bufs& b, int lower_bound, int morph, bool image, hipStream_t s)
+static hipError_t launch_bayer_t(const Geom& g, const Bufs& b, int lb, int all_pass, int morph, bool image, hipStream_t s)
 {
-    int lb = lower_bound, all_pass = 0;
-    if (lb <= 0) { all_pass = 1; lb = 1; }
-    if (lb > 256) lb = 256;
     // one camera frame (fewer strips than half the CUs): 8-row strips, four times the workgroups
     const int n_cu = g.n_cu > 0 ? g.n_cu : 256;
     const int sr = (int64_t)g.n_frames * ((g.h + BSR - 1) / BSR) * 2 <= n_cu ? BSR / 4 : BSR;
@@ -441,10 +438,9 @@ static hipError_t launch_bayer_t(const Geom& g, const Bufs& b, int lower_bound, 
 
 hipError_t launch_binary_bayer(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, hipStream_t s)
 {
-    // the camps' channel pairs as launch_binary (k_binary.hip): GUIDELIGHT G-R, BLUE B-R, everything else R-B
-    if (camp == RMCV_CAMP_GUIDELIGHT) return launch_bayer_t<1, 2>(g, b, lower_bound, morph, image, s);
-    if (camp == RMCV_CAMP_BLUE) return launch_bayer_t<0, 2>(g, b, lower_bound, morph, image, s);
-    return launch_bayer_t<2, 0>(g, b, lower_bound, morph, image, s);
+    // channel pair and effective bound as every pixel kernel's (pixel_plan.h: frame_key_eff)
+    const FrameKey k = frame_key_eff(camp, lower_bound);
+    return with_channel_pair(k, [&](auto ca, auto cb) { return launch_bayer_t<ca, cb>(g, b, k.lb, k.all_pass, morph, image, s); });
 }
 
 } // namespace rmcv

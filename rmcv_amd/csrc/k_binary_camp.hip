@@ -28,7 +28,6 @@ namespace rmcv {
 
 hipError_t launch_binary_camp(const Geom& g, const Bufs& b, int morph, bool image, const RunPlan& plan, hipStream_t s)
 {
-    if (g.win) return launch_binary_camp_win(g, b, morph, image, plan, s);
     return launch_binary_camp_t(g, b, 0, morph, image, plan, s);
 }
 

@@ -27,9 +27,7 @@ namespace rmcv {
 
 hipError_t launch_binary_enh(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s)
 {
-    if (camp == RMCV_CAMP_GUIDELIGHT) return launch_binary_enh_t<1, 2>(g, b, lower_bound, morph, image, plan, s);
-    if (camp == RMCV_CAMP_BLUE) return launch_binary_enh_t<0, 2>(g, b, lower_bound, morph, image, plan, s);
-    return launch_binary_enh_t<2, 0>(g, b, lower_bound, morph, image, plan, s);
+    return with_channel_pair(frame_key_eff(camp, lower_bound), [&](auto ca, auto cb) { return launch_binary_enh_t<ca, cb>(g, b, lower_bound, morph, image, plan, s); });
 }
 
 } // namespace rmcv

@@ -420,12 +420,14 @@ void ctx_external_order(rmcv_ctx* c, hipEvent_t done)
 const Limits& ctx_limits(const rmcv_ctx* c) { return c->lim; }
 uint64_t ctx_blocking_calls(const rmcv_ctx* c) { return c->blocking_calls; }
 int ctx_wait_timeout_ms(const rmcv_ctx* c) { return c->wait_timeout_ms; }
-bool pixel_ws_full(const rmcv_ctx* c, int lower_bound, int pixel_ws) { return binary_ws_full(c->geom, c->bufs, lower_bound, pixel_ws); }
+static PixelVariant geom_variant(const Geom& g) { return pixel_variant(g.input_format, g.enhance, g.win, g.keys); }
+bool pixel_ws_full(const rmcv_ctx* c, int lower_bound, const RunPlan& plan)
+{
+    return pixel_shape(pixel_batch(c->geom, c->bufs, geom_variant(c->geom), lower_bound, plan)).ws_full;
+}
 RunPlan ctx_plan(const rmcv_ctx* c) { return {c->pixel_shape, c->pixel_groups, c->sparse_waves, c->dense_defer ? SPARSE_SPLIT_BOTH : SPARSE_STANDARD}; }
-int ctx_input_format(const rmcv_ctx* c) { return c->input_format; }
 int ctx_enhance(const rmcv_ctx* c) { return c->enhance; }
-int ctx_bound_enhance(const rmcv_ctx* c) { return c->geom.enhance; }
-int ctx_bound_windows(const rmcv_ctx* c) { return c->geom.win; }
+PixelVariant ctx_pixel_variant(const rmcv_ctx* c) { return geom_variant(c->geom); }
 // bytes of one sample of what the context's options describe: 3 per BGR pixel, 1 or 2 per Bayer sample
 static int ctx_pixel_bytes(const rmcv_ctx* c) { return c->input_format ? c->input_sample_bits / 8 : 3; }
 int ctx_compact(rmcv_ctx* c, void* d_armours_out, int cap, void* d_frame_offs, void* d_status_or, hipStream_t s, void* hd_record, int host_head)
@@ -651,11 +653,13 @@ static int check_sample_ptr(rmcv_ctx* c, const void* p)
     return RMCV_OK;
 }
 
+// a combination of modes pixel_refusal (pixel_plan.h) has a message for
+static int refuse(rmcv_ctx* c, const char* why) { return why ? fail(c, RMCV_ERR_BAD_ARG, why) : RMCV_OK; }
+
 // what rmcv_batch_set_windows refuses, checked before anything of the context moves (fw x fh: the frames; fmt / enh: what they are read as)
 static int check_windows(rmcv_ctx* c, int fw, int fh, int fmt, int enh, int win_w, int win_h)
 {
-    if (fmt != RMCV_INPUT_BGR) return fail(c, RMCV_ERR_BAD_ARG, "windows with a Bayer input format (RMCV_OPT_INPUT_FORMAT): crop-then-demosaic has other border semantics; not supported");
-    if (enh) return fail(c, RMCV_ERR_BAD_ARG, "windows with RMCV_OPT_ENHANCE: the mean of a crop is not the frame's; not supported");
+    if (const int rc = refuse(c, pixel_refusal(fmt, enh, true, false, false))) return rc;
     if (win_w < 1 || win_h < 1) return fail(c, RMCV_ERR_BAD_ARG, "window size out of range: win_w and win_h must be at least 1");
     if (win_w > fw || win_h > fh) return fail(c, RMCV_ERR_BAD_ARG, "window size out of range: larger than the frames");
     if (win_w > c->lim.max_width || win_h > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, "window size out of range: larger than the context's limits");
@@ -663,12 +667,7 @@ static int check_windows(rmcv_ctx* c, int fw, int fh, int fmt, int enh, int win_
 }
 
 // what per-frame detection keys refuse of the frames' format (fmt / enh: what they are read as), checked before anything of the context moves
-static int check_frame_camps(rmcv_ctx* c, int fmt, int enh)
-{
-    if (fmt != RMCV_INPUT_BGR) return fail(c, RMCV_ERR_BAD_ARG, "per-frame camps with a Bayer input format (RMCV_OPT_INPUT_FORMAT): the mosaic kernel takes one camp per run; not supported");
-    if (enh) return fail(c, RMCV_ERR_BAD_ARG, "per-frame camps with RMCV_OPT_ENHANCE: the threshold table folds one lower bound per run; not supported");
-    return RMCV_OK;
-}
+static int check_frame_camps(rmcv_ctx* c, int fmt, int enh) { return refuse(c, pixel_refusal(fmt, enh, false, true, false)); }
 
 // Make w x h the extent everything behind the frame loads sees (the frames' own, or their windows').  When it changes the padded planes
 // are zeroed and the frame order is recomputed, as set_geom's comment says.
@@ -684,7 +683,7 @@ static int set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t
     if (c->input_format && (w < 3 || h < 3)) return fail(c, RMCV_ERR_BAD_ARG, "a Bayer frame needs w >= 3 and h >= 3");
     if (stride < bpp * w || frame_pitch < (int64_t)stride * (h - 1) + bpp * w) return fail(c, RMCV_ERR_BAD_ARG, "bad stride/pitch");
     if (bpp == 2 && ((stride & 1) || (frame_pitch & 1))) return fail(c, RMCV_ERR_BAD_ARG, "16-bit samples (RMCV_OPT_INPUT_SAMPLE_BITS): stride and frame_pitch are bytes and must be even");
-    if (c->enhance && c->input_format) return fail(c, RMCV_ERR_BAD_ARG, "RMCV_OPT_ENHANCE with a Bayer input format: the mean of a demosaiced frame is not a function of the mosaic's sums");
+    { const int rcr = refuse(c, pixel_refusal(c->input_format, c->enhance, false, false, false)); if (rcr) return rcr; }
     if (win_w > 0) { const int rcw = check_windows(c, w, h, c->input_format, c->enhance, win_w, win_h); if (rcw) return rcw; }
     { const int rcm = ensure_mid(c, n_frames); if (rcm) return rcm; }
     Geom& g = c->geom;
@@ -769,9 +768,7 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
     resident_none(c);
     int rc;
     // every argument check comes BEFORE the first enqueue (the callers': check_bound): an error return leaves the streams as they were
-    if (lp && g.input_format) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
-    if (lp && g.enhance) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not with RMCV_OPT_ENHANCE");
-    if (lp && g.keys) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes a camp per blob from BGR means: not with per-frame camps (rmcv_batch_set_frame_camps)");
+    if (lp && (rc = refuse(c, pixel_refusal(g.input_format, g.enhance, false, g.keys != 0, true)))) return rc;
     if ((rc = order_begin(c, s))) return rc;
     if (c->test_delay_us) { // RMCV_OPT_TEST_DELAY_US: a stand-in for a kernel that does not finish in time (one shot)
         HIPCHK(c, launch_delay((unsigned long long)c->test_delay_us * 1000ull, s), "k_delay (RMCV_OPT_TEST_DELAY_US)");
@@ -798,8 +795,7 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
         if (g.keys) HIPCHK(c, launch_frame_keys(g, b, p->lower_bound, s), "k_frame_keys");
         c->last_camp = p->camp;
         c->last_lower_bound = p->lower_bound;
-        HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, !(stages & RMCV_STAGE_NO_IMAGE), plan, s, &c->image),
-               g.input_format ? "k_binary_bayer" : (g.enhance ? "k_binary_enh" : (g.keys ? (g.win ? "k_binary_camp_win" : "k_binary_camp") : (g.win ? "k_binary_win" : "k_binary"))));
+        HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, !(stages & RMCV_STAGE_NO_IMAGE), plan, s, &c->image), PIXEL_VARIANTS[geom_variant(g)].kernel);
     }
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
     // the icon classifier rides in the per-frame kernel when the armours come from it (BASELINE config 5: no launch of its own)
@@ -922,7 +918,7 @@ int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int 
     c->last_stages = 0;
     return RMCV_OK;
 }
-int ctx_check_frame_camps(rmcv_ctx* c) { return check_frame_camps(c, c->input_format, c->enhance); }
+int ctx_check_modes(rmcv_ctx* c, bool keys, bool legacy) { return refuse(c, pixel_refusal(c->input_format, c->enhance, false, keys, legacy)); }
 // what binding a batch would allocate, now (a pipeline does this for every context of its ring when it is created)
 int ctx_prepare_ring(rmcv_ctx* c) { return ensure_mid(c, c->lim.max_frames); }
 int ctx_run(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_params* lp, int stages, hipStream_t s, const RunPlan& plan, bool* lean)
@@ -947,9 +943,8 @@ int rmcv_batch_run_legacy(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_p
     int rc = check_bound(c, p, stages);
     if (rc) return rc;
     if (!lp) return fail(c, RMCV_ERR_BAD_ARG, "null legacy params");
-    if (c->input_format || c->geom.input_format) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
-    if (c->enhance || c->geom.enhance) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not with RMCV_OPT_ENHANCE");
-    if (c->geom.keys) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes a camp per blob from BGR means: not with per-frame camps (rmcv_batch_set_frame_camps)");
+    // (the context's options as they are set now count beside what the frames were bound with; per-frame camps: run_stages)
+    if ((rc = refuse(c, pixel_refusal(c->input_format | c->geom.input_format, c->enhance | c->geom.enhance, false, false, true)))) return rc;
     hipSetDevice(c->device);
     return run_stages(c, p, stages, hip_stream ? (hipStream_t)hip_stream : c->stream, false, ctx_plan(c), lp);
 }
@@ -1569,7 +1564,7 @@ static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int
         c->test_delay_us = 0;
     }
     if (g.enhance) HIPCHK(c, launch_enhance_tables(g, b, lower_bound, s), "k_frame_sums + k_enhance_table"); // RMCV_OPT_ENHANCE: the frame is read through its table
-    HIPCHK(c, launch_binary(g, b, camp, lower_bound, morph, binary_out != nullptr, plan, s, &c->image), g.input_format ? "k_binary_bayer" : (g.enhance ? "k_binary_enh" : "k_binary"));
+    HIPCHK(c, launch_binary(g, b, camp, lower_bound, morph, binary_out != nullptr, plan, s, &c->image), PIXEL_VARIANTS[geom_variant(g)].kernel);
     if (binary_out) HIPCHK(c, hipEventRecord(c->ev_fork, s), "image download: mark");
     // running ahead with both parameter sets known: the frame's whole sparse part is ONE kernel (the fused per-frame kernel of
     // the batch path: findContours, fits and pairing back to back), not three
@@ -2449,10 +2444,10 @@ int rmcv_find_lightblobs(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stri
                          int32_t* blob_src, rmcv_rrect* boxes_out)
 {
     if (!c || !bgr || !lp || (n_contours > 0 && (!pts || !offs))) return RMCV_ERR_BAD_ARG;
-    if (c->input_format) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
-    if (c->enhance) return fail(c, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not with RMCV_OPT_ENHANCE");
+    int rc = refuse(c, pixel_refusal(c->input_format, c->enhance, false, false, true));
+    if (rc) return rc;
     hipSetDevice(c->device);
-    int rc = rmcv_batch_upload(c, bgr, 1, w, h, stride, (int64_t)stride * h); // source.channels() == 3 is the ABI's only format
+    rc = rmcv_batch_upload(c, bgr, 1, w, h, stride, (int64_t)stride * h); // source.channels() == 3 is the ABI's only format
     if (rc) return rc;
     rc = load_contours(c, pts, offs, n_contours);
     if (rc) return rc;

@@ -9,6 +9,7 @@
 
 #include "../../include/rmcv_abi.h"
 #include "image_plan.h"
+#include "pixel_plan.h"
 #include "sparse_plan.h"
 
 namespace rmcv {
@@ -57,10 +58,6 @@ struct RunPlan {
 };
 
 static constexpr int CTR_STRIDE = 32;   // ints between the heads of k_binary's strip queues (Bufs::strip_ctr): a 128-byte line each, 9 of them
-#ifndef RMCV_SR
-#define RMCV_SR 32
-#endif
-static constexpr int STRIP_ROWS = RMCV_SR;   // rows of a k_binary strip (k_binary.hip: SR); the sparse kernel's frame queues follow its strip order
 static constexpr int VISIT_CAP = 4096; // border visits of one frame the contour stage holds in LDS (contours_device.h); more -> mid tier
 static constexpr int NN_MID = 1 << 17;   // border visits of one frame the mid tier holds (tables in global memory); more -> literal scanner
 static constexpr int CAND_MID = 1 << 15; // outer borders (before RETR_EXTERNAL drops the nested ones) the mid tier holds
@@ -73,25 +70,6 @@ inline size_t mid_bytes(int slot_cap)
 struct Limits {
     int max_frames, max_width, max_height, max_contours, max_points, max_blobs, max_armours;
 };
-
-// The effective detection key of a frame, the one place it is computed -- by k_frame_keys on the device and by
-// rmcv_frame_key on the host: raw camp and lower bound, any int32 (a device-side producer may write them), -> what the pixel kernels use.
-//   channel pair (imgproc.cpp:56-65, BGR byte order): GUIDELIGHT G-R; BLUE B-R; every other value R-B
-//   bound (inRange(gray, lb, 255) on a saturated u8 difference): lb <= 0 every pixel passes; lb > 255 none; otherwise a - b >= lb
-struct FrameKey {
-    int32_t ca, cb;   // byte of channel A / channel B inside a BGR pixel
-    int32_t lb;       // effective bound, 1 .. 256
-    int32_t all_pass; // 1: every pixel passes (lb is 1 then)
-};
-__host__ __device__ inline FrameKey frame_key_eff(int32_t camp, int32_t lower_bound)
-{
-    FrameKey k;
-    k.ca = camp == RMCV_CAMP_GUIDELIGHT ? 1 : (camp == RMCV_CAMP_BLUE ? 0 : 2);
-    k.cb = (camp == RMCV_CAMP_GUIDELIGHT || camp == RMCV_CAMP_BLUE) ? 2 : 0;
-    k.all_pass = lower_bound <= 0 ? 1 : 0;
-    k.lb = lower_bound <= 0 ? 1 : (lower_bound > 256 ? 256 : lower_bound);
-    return k;
-}
 
 // Device buffers of one context (all sized by Limits at creation, reused by every call).
 struct Bufs {
@@ -175,6 +153,13 @@ __host__ __device__ inline int64_t frame_origin_offset(const rmcv_point* __restr
     return win_eff ? (int64_t)win_eff[f].y * stride + 3 * (int64_t)win_eff[f].x : 0;
 }
 
+// What pixel_shape (pixel_plan.h) takes of a batch bound to (g, b), as variant `v`, under the run's bound and plan
+inline PixelBatch pixel_batch(const Geom& g, const Bufs& b, PixelVariant v, int lower_bound, const RunPlan& plan)
+{
+    return {v, g.n_frames, g.w, g.h, g.ww, g.stride, g.frame_pitch, g.plane_pitch, g.n_cu, g.pixel_rowquad, (uintptr_t)b.frames % 16 == 0,
+            lower_bound, plan.pixel_ws, plan.pixel_groups};
+}
+
 // internal value of a frame's status word BETWEEN the two launches of the sparse stage (never seen by a caller: the second launch
 // rewrites the word of every frame that carries it)
 #define RMCV_FRAME_DEFERRED_ (1 << 30)
@@ -219,7 +204,6 @@ hipError_t launch_pnp(const Geom& g, const Bufs& b, const Limits& lim, hipStream
 // img: the context's knowledge of its byte image, read for the store mode and rewritten for what this launch leaves (image_plan.h)
 hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s,
                          ImageState* img);
-bool binary_ws_full(const Geom& g, const Bufs& b, int lower_bound, int pixel_ws); // the batch will run as one launch of k_binary_ws with a workgroup on every CU
 // the pixel stage of a Bayer batch (Geom::input_format != 0; k_binary_bayer.hip); launch_binary hands such batches to it
 hipError_t launch_binary_bayer(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, hipStream_t s);
 // exposure-adaptive detection (k_enhance.hip, k_binary_enh.hip).  launch_enhance_tables: the channel sums of the frames bound, then every
@@ -300,28 +284,26 @@ int ctx_run(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_params* lp, int
 // d_camps non-null: per-frame detection keys (rmcv_batch_set_device_frame_camps in the same step; d_lower_bounds nullable)
 int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t s,
                     const void* d_origins = nullptr, int win_w = 0, int win_h = 0, const void* d_camps = nullptr, const void* d_lower_bounds = nullptr);
-// what per-frame keys refuse of a context as it is set (a Bayer input format, RMCV_OPT_ENHANCE), checked without enqueuing anything
-int ctx_check_frame_camps(rmcv_ctx* c);
+// what a batch with per-frame keys / for the legacy matcher refuses of a context's options as they are set (pixel_refusal of a Bayer input
+// format, RMCV_OPT_ENHANCE), checked without enqueuing anything
+int ctx_check_modes(rmcv_ctx* c, bool keys, bool legacy);
 // everything binding a full batch would allocate (the mid tier's scratch), now
 int ctx_prepare_ring(rmcv_ctx* c);
 // allocations, host-side synchronisations and blocking copies this context has made while binding geometries
 uint64_t ctx_blocking_calls(const rmcv_ctx* c);
 int ctx_wait_timeout_ms(const rmcv_ctx* c);
-bool pixel_ws_full(const rmcv_ctx* c, int lower_bound, int pixel_ws); // binary_ws_full of what is bound to the context
+// PixelShape::ws_full of what is bound to the context: the batch will run as one launch of k_binary_ws with a workgroup on every CU
+bool pixel_ws_full(const rmcv_ctx* c, int lower_bound, const RunPlan& plan);
 // waits that poll with a deadline instead of parking the thread in the runtime: 0 done, 1 deadline passed, -1 HIP error (*err)
 int wait_stream_deadline(hipStream_t s, int timeout_ms, hipError_t* err);
 int wait_event_deadline(hipEvent_t ev, int timeout_ms, hipError_t* err);
 hipError_t launch_delay(unsigned long long ns, hipStream_t s); // holds `s` back for `ns` nanoseconds
 // what rmcv_batch_run would refuse for (p, stages) apart from frames not bound, checked without enqueuing anything
 int ctx_check_stages(rmcv_ctx* c, const rmcv_params* p, int stages);
-// RMCV_OPT_INPUT_FORMAT as set on the context (what the next binding records)
-int ctx_input_format(const rmcv_ctx* c);
 // RMCV_OPT_ENHANCE as set on the context
 int ctx_enhance(const rmcv_ctx* c);
-// ... and as the frames bound last recorded it (what the runs on them do)
-int ctx_bound_enhance(const rmcv_ctx* c);
-// whether the frames bound last are read through windows
-int ctx_bound_windows(const rmcv_ctx* c);
+// the pixel kernel variant of the frames bound last (what the runs on them launch)
+PixelVariant ctx_pixel_variant(const rmcv_ctx* c);
 
 
 // ---- device-resident tracker (k_track.hip) ----

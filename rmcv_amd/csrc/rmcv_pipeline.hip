@@ -623,21 +623,23 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
                        !(stages & (RMCV_STAGE_IDENTITY | RMCV_STAGE_POSE)) && (stages & RMCV_STAGE_CONTOURS) && (stages & RMCV_STAGE_BLOBS);
     // (batches with a classifier stage stay out of the hot rotation: measured in round 5, three contexts at 256 x 1920x1200, 0.514 against
     // 0.426 ms per step with them in it)
-    // (so do batches read through their gamma tables, RMCV_OPT_ENHANCE on the slot's context: they take the k_binary shape, and the sums pass in
-    // front of it has no use for another batch's planes in the cache)
-    // (and windowed batches: the k_binary shape too, and a geometry of their own -- in the rotation they would re-zero the hot contexts' planes)
-    const bool fast = pl->hot && pl->calm && !lp && !(stages & RMCV_STAGE_POSE) && !(stages & RMCV_STAGE_IDENTITY) && !ctx_enhance(pl->ring[k]) && !d_origins && !d_camps && !trk; // (nor batches with per-frame keys: the k_binary shape as well; nor tracked ones: the step reads the context's lists behind the compaction)
+    // (so do the batches whose variant takes the k_binary shape whatever the plan says (pixel_plan.h): read through their gamma tables,
+    // RMCV_OPT_ENHANCE on the slot's context -- the sums pass in front has no use for another batch's planes in the cache; windowed -- a
+    // geometry of their own, in the rotation they would re-zero the hot contexts' planes; with per-frame keys.  Mosaics take turns as they
+    // always have: the format is left out of the question)
+    const bool ws_variant = PIXEL_VARIANTS[pixel_variant(RMCV_INPUT_BGR, ctx_enhance(pl->ring[k]), d_origins != nullptr, d_camps != nullptr)].ws;
+    const bool fast = pl->hot && pl->calm && !lp && !(stages & RMCV_STAGE_POSE) && !(stages & RMCV_STAGE_IDENTITY) && ws_variant && !trk; // (nor tracked ones: the step reads the context's lists behind the compaction)
     const size_t j = fast ? (size_t)(pl->hot_seq % (uint64_t)pl->hot) : k;
     rmcv_ctx* c = pl->ring[j];
     int rc;
-    if (lp && ctx_input_format(c)) return pfail(pl, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
     // the rotation is decided from the slot's own context and the batch may run in another (ring[j]): a ring whose contexts disagree
     // about the option would mix the two paths batch by batch -- refused, loudly, whichever slot this batch would take
     for (size_t i = 1; i < pl->ring.size(); i++)
         if (ctx_enhance(pl->ring[i]) != ctx_enhance(pl->ring[0]))
             return pfail(pl, RMCV_ERR_BAD_ARG, "RMCV_OPT_ENHANCE differs between the pipeline's contexts: set it on EVERY slot (rmcv_pipeline_context)");
-    if (lp && ctx_enhance(c)) return pfail(pl, RMCV_ERR_BAD_ARG, "the legacy matcher votes camps from BGR means: not with RMCV_OPT_ENHANCE");
-    if (d_camps && (rc = ctx_check_frame_camps(c))) return cfail(pl, c, rc); // (a Bayer input format, RMCV_OPT_ENHANCE: refused before anything is enqueued)
+    // what the legacy matcher and per-frame keys refuse of the context's options (a Bayer input format, RMCV_OPT_ENHANCE): before anything
+    // is enqueued.  (What windows and the options refuse of each other: the binding below, as for every batch.)
+    if ((lp || d_camps) && (rc = ctx_check_modes(c, d_camps != nullptr, lp != nullptr))) return cfail(pl, c, rc);
     // a batch is several runs on several streams: everything that could refuse it is checked before the first enqueue (the binding below
     // enqueues a new geometry's work on A)
     if ((rc = ctx_check_stages(c, p, stages))) return cfail(pl, c, rc);
@@ -673,7 +675,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     // (tools/trace_regions.py, profiles/r04k_burst_start.txt).  Held back, the second launch finds every CU taken and its workgroups
     // move in as the first one's leave -- the steady state -- at no cost: they would have waited anyway.  (Waiting for the first
     // launch's END instead puts the event's latency between the two: +1-3 %.)  Round 5: only where that reason exists -- the launch
-    // WILL be k_binary_ws on every CU (launch_binary's own rule: pixel_ws_full) -- and for a quarter of the launch's expected time
+    // WILL be k_binary_ws on every CU (the launch plan's own answer: PixelShape::ws_full) -- and for a quarter of the launch's expected time
     // (its bytes at 5.5 TB/s), 60 us at most, nothing below 100 us of launch: two 16-frame batches are not held back at all.
     bool cold = false;
     if (fast) {
@@ -683,7 +685,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
             cold = pl->slot_ticket[s_] == t && hipEventQuery(pl->ev_done[s_]) == hipSuccess;
             (void)hipGetLastError();
         }
-        if (!cold && pl->was_cold && pl->slot_ticket[s_] == t && pixel_ws_full(c, p->lower_bound, plan.pixel_ws)) {
+        if (!cold && pl->was_cold && pl->slot_ticket[s_] == t && pixel_ws_full(c, p->lower_bound, plan)) {
             const double launch_us = (double)n_frames * 4.0 * w * h / 5.5e6;
             const int hold_us = launch_us < 100.0 ? 0 : (int)(launch_us / 4.0 < 60.0 ? launch_us / 4.0 : 60.0);
             if (hold_us > 0) { // hold the second launch back until the first one's workgroups have taken every CU
@@ -697,7 +699,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     if (trk && d_origins) PCHK(pl, tracker_wait_on(trk, A), "pipeline: wait for the tracker's last step");
     rc = ctx_run(c, p, nullptr, pixel, A, plan);
     if (rc) return cfail(pl, c, rc);
-    pl->last_what = ctx_input_format(c) ? "the pixel kernel (k_binary_bayer)" : ctx_bound_enhance(c) ? "k_frame_sums, k_enhance_table, the pixel kernel (k_binary_enh)" : d_camps ? "k_frame_keys, the pixel kernel (k_binary_camp / k_binary_camp_win)" : ctx_bound_windows(c) ? "k_window_origins, the pixel kernel (k_binary_win)" : "the pixel kernel (k_binary / k_binary_ws)";
+    pl->last_what = PIXEL_VARIANTS[ctx_pixel_variant(c)].step;
     // ---- accepted: the pipeline's state moves
     pl->was_cold = cold;
     if (fast) { pl->hot_seq++; pl->hot_batches++; }

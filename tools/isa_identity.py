@@ -3,8 +3,8 @@
 (.LBB<n>_) and the per-file __hip_cuid_<hash> symbol are normalised (a kernel added in front shifts the first, the second hashes the
 source path).  Symbols only one side has are listed, not compared.  No GPU needed.
 
-  for u in k_binary k_binary_bayer k_contours k_contours_w4 k_contours_lean; do
-    hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math --save-temps -c rmcv_amd/csrc/$u.hip -o DIR/$u.o; done
+  for u in $(sed -n 's/^SRCS *:= *//p' rmcv_amd/csrc/Makefile | sed 's/\.hip//g'); do        (every unit of the Makefile's SRCS)
+    (cd DIR && hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math --save-temps -c ROOT/rmcv_amd/csrc/$u.hip -o $u.o); done
   python tools/isa_identity.py BEFORE_DIR AFTER_DIR [unit ...]        exit status 1 if a shared symbol differs"""
 import glob
 import os

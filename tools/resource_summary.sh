@@ -2,7 +2,7 @@
 # kernel resource usage of every device unit as the compiler reports it (-Rpass-analysis=kernel-resource-usage): VGPRs, spills, scratch, occupancy
 #   bash tools/resource_summary.sh > profiles/<tag>_kernel_resources.txt        (no GPU needed)
 cd "$(dirname "$0")/../rmcv_amd/csrc"
-for u in k_binary k_binary_enh k_enhance k_binary_bayer k_contours k_contours_w4 k_detect k_classify k_pnp k_binary_camp k_binary_camp_win; do
+for u in $(sed -n 's/^SRCS *:= *//p' Makefile | sed 's/\.hip//g'); do # every unit of the Makefile's SRCS
   /opt/rocm/bin/hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Rpass-analysis=kernel-resource-usage -c $u.hip -o /tmp/rs_$u.o 2>&1 | c++filt | python3 -c "
 import re, sys
 unit = '$u'
