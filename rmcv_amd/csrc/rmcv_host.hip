@@ -15,127 +15,12 @@
 #include <algorithm>
 #include <vector>
 
-#include "rmcv_internal.h"
+#include "rmcv_ctx.h"
 #include "device_bayer.h"
 #include "enhance_math.h"
 #include "device_track.h"
 
 using namespace rmcv;
-
-struct rmcv_ctx {
-    int device = 0;
-    Limits lim{};
-    Geom geom{};
-    Bufs bufs{};
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[6] = {};
-    uint8_t* own_frames = nullptr; // upload buffer (lazy)
-    size_t own_frames_bytes = 0;
-    rmcv_point* pack_pts = nullptr; // CSR download staging
-    int32_t* pack_offs = nullptr;
-    hipStream_t last_stream = nullptr;
-    int geom_w = -1, geom_h = -1; // geometry the planes were zeroed for
-    ImageState image = IMAGE_STATE_UNKNOWN; // what Bufs::imgmask is known to say about Bufs::binary (image_plan.h); every launch_binary keeps it
-    int order_n = -1, order_h = -1; // (n_frames, h) the frame order on the device was computed for
-    hipEvent_t ev_order = nullptr; // recorded behind the work enqueued last: a call on ANOTHER stream first waits for it
-    bool order_pending = false;
-    bool external_order = false;  // a pipeline owns the ordering of this context's launches (rmcv_internal.h: ctx_external_order)
-    hipEvent_t ext_done = nullptr; // ... and records this event behind the last of them
-    // ---- per-frame drop-in path (rmcv_extract_color -> rmcv_filter_lightblobs -> rmcv_filter_armours, executable/main.cpp:172-176)
-    int frame_upload = 3;          // RMCV_OPT_FRAME_UPLOAD (3: the runtime's pageable copy, the pinned staging buffer while that is slow)
-    int run_ahead = 1;             // RMCV_OPT_RUN_AHEAD
-    struct Reg { const void* p; size_t bytes; };
-    std::vector<Reg> registered;   // caller buffers pinned by hipHostRegister (RMCV_OPT_FRAME_UPLOAD = 2)
-    uint8_t* h_frame = nullptr;    // pinned staging (lazy): the BGR frame on its way up (RMCV_OPT_FRAME_UPLOAD = 1); small results on their way down:
-    size_t h_frame_bytes = 0;
-    int32_t* h_hdr = nullptr;      // [16]: contours at 0, blobs at 4, armours at 8
-    // the same pinned buffers as the device addresses them (k_export stores into them); null: not mappable, copies are used
-    int32_t *hd_hdr = nullptr, *hd_offs = nullptr, *hd_blob_src = nullptr, *hd_neg = nullptr;
-    rmcv_point* hd_pts = nullptr;
-    rmcv_lightblob* hd_blobs = nullptr;
-    rmcv_armour* hd_armours = nullptr;
-    rmcv_point* h_pts = nullptr;   // [max_points]      the CSR the last rmcv_extract_color returned
-    int32_t* h_offs = nullptr;     // [max_contours + 1]
-    rmcv_lightblob* h_blobs = nullptr; // [max_blobs]   the positive list the last rmcv_filter_lightblobs returned
-    int32_t* h_blob_src = nullptr; // [max_blobs]
-    int32_t* h_neg = nullptr;      // [max_contours]
-    rmcv_armour* h_armours = nullptr; // [max_armours]
-    int32_t* d_hdr = nullptr;      // device [16]
-    // Device-resident hand-over: what frame slot 0 of the device buffers holds right now.  When the next call of the chain is
-    // handed exactly these bytes back (the usual case: the reference passes the results straight on), nothing is re-uploaded.
-    int res_nc = -1, res_total = 0; // contours (+ the fit stage's work list) = h_pts / h_offs; -1: not resident
-    int res_nb = -1;                // light blobs = h_blobs; -1: not resident
-    // Run-ahead: a caller that filters every frame with the same parameters (executable/main.cpp:172-176 does) gets the blob and
-    // armour stages enqueued by rmcv_extract_color already, with the parameters its previous frame used -- one stream sequence and
-    // one synchronisation for the whole chain; rmcv_filter_lightblobs / rmcv_filter_armours then only hand the results over.
-    struct LbParams { float tilt_max, ratio_lo, ratio_hi; double area_lo, area_hi; int enemy; } last_lb{};
-    struct ArParams { float angle_diff_max, shear_max, length_ratio_max; int enemy; } last_ar{};
-    bool last_lb_valid = false, last_ar_valid = false; // what the previous frame's calls asked for
-    bool ahead_lb = false, ahead_ar = false;           // this frame's extract_color has run them: headers + windows are in pinned memory
-    hipStream_t side = nullptr;   // the library's own second stream: the byte image's download runs on it beside the sparse kernels
-    hipEvent_t ev_fork = nullptr;
-    int mid_frames = 0;           // frame slots Bufs::mid holds (ensure_mid)
-    bool mid_failed = false;      // ... could not be allocated: the mid tier is absent for this context
-    int sparse_waves = 8;         // RMCV_OPT_SPARSE_WAVES
-    int pixel_groups = 3;         // RMCV_OPT_PIXEL_GROUPS
-    int pixel_shape = 1;          // RMCV_OPT_PIXEL_SHAPE
-    int dense_defer = 0;          // RMCV_OPT_DENSE_DEFER
-    int input_format = 0;         // RMCV_OPT_INPUT_FORMAT: 0 BGR, 1..4 a Bayer pattern (a binding records it in Geom::input_format)
-    int input_sample_bits = 8;    // RMCV_OPT_INPUT_SAMPLE_BITS: 8 or 16   } the Bayer frame as the sensor delivers it; recorded by a
-    int input_valid_bit = 0;      // RMCV_OPT_INPUT_VALID_BIT: 0 .. 4      } binding next to the format (Geom::sample_bytes, valid_bit,
-    int input_orient = 0;         // RMCV_OPT_INPUT_ORIENT: RMCV_ORIENT_*  } orient)
-    int enhance = 0;              // RMCV_OPT_ENHANCE: frames are read through their rm::AutoEnhance table (a binding records it in Geom::enhance)
-    float enh_max_gain = 100.0f, enh_min_gain = 50.0f; // rmcv_ctx_set_enhance_gains (include/imgproc.h:35)
-    // Waits with a deadline (round 5): no entry point parks its caller in the runtime without a bound.  `last_what` names the kernel or
-    // copy enqueued last (every HIPCHK of an enqueue leaves its label here): a wait that runs out returns RMCV_ERR_TIMEOUT with it.
-    int wait_timeout_ms = 5000;   // RMCV_OPT_WAIT_TIMEOUT_MS (0: no deadline)
-    const char* last_what = "nothing";
-    bool timed_out = false;       // a wait ran out: work of this context may still be in flight (cleared by the next wait that completes)
-    int test_delay_us = 0;        // RMCV_OPT_TEST_DELAY_US: the next rmcv_extract_color holds its stream back this long first (tests of the deadline)
-    uint8_t *h_image = nullptr, *hd_image = nullptr; // the byte image on its way home: pinned + mapped, written by k_image_export chunk by chunk
-    size_t h_image_bytes = 0;
-    uint32_t *h_iflags = nullptr, *hd_iflags = nullptr; // [IMG_CHUNKS] a chunk's flag = the sequence number of the frame whose bytes it holds
-    uint32_t img_seq = 0;
-    int image_export = 2;         // RMCV_OPT_IMAGE_EXPORT (2: the runtime's pageable copy, the library's export while that is slow)
-    // The runtime's pageable copies pin and unpin the caller's pages on every call; in some conditions (measured: for tens of seconds
-    // after a large GPU process has exited -- the driver's test suite in front of bench.py, every round) each such copy costs 120-250 us
-    // more, and the per-frame chain reads 0.28 ms (one of them slow) or 0.40 (both) instead of 0.18.  The library measures both copies on
-    // every frame and moves to its own paths -- pinned staging up, export kernel down -- after three slow frames in a row, for 512 frames,
-    // then tries the runtime's again.
-    int upload_now = 0, image_now = 0;   // the paths the last frame took (upload: 0 pageable / 1 pinned staging / 2 registered; image: 0 runtime / 1 export)
-    int slow_upload = 0, slow_image = 0; // consecutive slow frames on the runtime's path
-    int hold_upload = 0, hold_image = 0; // frames left on the library's own path
-    int test_slow_us = 0;                // RMCV_OPT_TEST_SLOW_US: added to what the library measures of the runtime's copies (tests of the switch)
-    uint32_t* d_iarrived = nullptr; // [IMG_CHUNKS] device: workgroups of k_image_export that have stored their slice of a chunk
-    double marks[9] = {};         // rmcv_ctx_frame_timing: host clock at the steps of the last rmcv_extract_color (microseconds)
-    uint64_t blocking_calls = 0;  // allocations, host-side synchronisations and blocking copies made while binding a geometry (ctx_blocking_calls)
-    int32_t* order_scratch = nullptr; // [2 * max_frames] k_frame_order's work lists for batches beyond its LDS tables
-    int last_stages = 0;              // the stages the batch bound has been through since its last pixel pass (rmcv_batch_track asks for RMCV_STAGE_ARMOURS)
-    rmcv_point* win_own = nullptr;    // [max_frames] the context's copy of host origins (rmcv_batch_set_windows); Bufs::win_req points here or at the caller's
-    int32_t* key_own = nullptr;       // [2][max_frames] the context's copy of host camps | lower bounds (rmcv_batch_set_frame_camps); Bufs::key_camps / key_lbs point here or at the caller's
-    int last_camp = RMCV_CAMP_BLUE, last_lower_bound = 80; // rmcv_params::camp, ::lower_bound of the last run with the pixel pass (rmcv_batch_get_frame_keys without per-frame keys)
-    char err[256] = {0};
-    std::vector<void*> allocs;
-    struct Guarded { uint8_t* base; size_t bytes; const char* name; size_t rear = 0; };
-    std::vector<Guarded> guarded; // every dalloc'd buffer with its guard zones (rmcv_ctx_check_guards)
-};
-
-static int fail(rmcv_ctx* c, int code, const char* what, hipError_t e = hipSuccess)
-{
-    if (c) {
-        if (e != hipSuccess) snprintf(c->err, sizeof(c->err), "%s: %s", what, hipGetErrorString(e));
-        else snprintf(c->err, sizeof(c->err), "%s", what);
-    }
-    if (e != hipSuccess) (void)hipGetLastError(); // reported through the return code: do not leave it in the thread's sticky slot for others
-    return code;
-}
-
-#define HIPCHK(c, call, what)                                           \
-    do {                                                                \
-        (c)->last_what = what;                                          \
-        hipError_t e__ = (call);                                        \
-        if (e__ != hipSuccess) return fail((c), RMCV_ERR_HIP, what, e__); \
-    } while (0)
 
 // ---- waits with a deadline ------------------------------------------------------------------------------------------------------
 // hipStreamSynchronize / hipEventSynchronize spin for ~0.1 ms and then park the thread on an interrupt; the wake-up costs another
@@ -143,12 +28,6 @@ static int fail(rmcv_ctx* c, int code, const char* what, hipError_t e = hipSucce
 // went to sleep -- VERDICT r4 weak #4), and a kernel that never finishes parks the caller for good (weak #3).  These poll instead:
 // spinning for the first 2 ms, yielding up to 20 ms, sleeping 0.2 ms at a time after that, up to the context's deadline.
 namespace rmcv {
-static inline double now_us()
-{
-    timespec ts;
-    clock_gettime(CLOCK_MONOTONIC, &ts);
-    return ts.tv_sec * 1e6 + ts.tv_nsec * 1e-3;
-}
 template <typename Q>
 static int poll_deadline(Q query, int timeout_ms, hipError_t* err)
 {
@@ -170,61 +49,6 @@ static int poll_deadline(Q query, int timeout_ms, hipError_t* err)
 int wait_stream_deadline(hipStream_t s, int timeout_ms, hipError_t* err) { return poll_deadline([s] { return hipStreamQuery(s); }, timeout_ms, err); }
 int wait_event_deadline(hipEvent_t ev, int timeout_ms, hipError_t* err) { return poll_deadline([ev] { return hipEventQuery(ev); }, timeout_ms, err); }
 } // namespace rmcv
-
-static int wait_failed(rmcv_ctx* c, int rcw, const char* what, hipError_t e)
-{
-    if (rcw < 0) return fail(c, RMCV_ERR_HIP, what, e);
-    c->timed_out = true;
-    snprintf(c->err, sizeof(c->err), "%s: not finished after %d ms (RMCV_OPT_WAIT_TIMEOUT_MS); enqueued last: %s", what, c->wait_timeout_ms, c->last_what);
-    return RMCV_ERR_TIMEOUT;
-}
-static int wait_stream(rmcv_ctx* c, hipStream_t s, const char* what)
-{
-    hipError_t e = hipSuccess;
-    const int rcw = wait_stream_deadline(s, c->wait_timeout_ms, &e);
-    if (rcw) return wait_failed(c, rcw, what, e);
-    return RMCV_OK;
-}
-static int wait_event(rmcv_ctx* c, hipEvent_t ev, const char* what)
-{
-    hipError_t e = hipSuccess;
-    const int rcw = wait_event_deadline(ev, c->wait_timeout_ms, &e);
-    if (rcw) return wait_failed(c, rcw, what, e);
-    return RMCV_OK;
-}
-#define WAITCHK(c, call)            \
-    do {                            \
-        const int rcw__ = (call);   \
-        if (rcw__) return rcw__;    \
-    } while (0)
-
-// Every device buffer of a context lies between two GUARD-byte zones filled with a fixed pattern when the context is created;
-// rmcv_ctx_check_guards reads them back.  A kernel that stores one row, word or record past either end of its buffer -- the
-// partial last strip of a 1200-row frame, the ragged last block of a 1920-pixel row -- shows up there instead of in a neighbour.
-#ifndef RMCV_GUARD
-#define RMCV_GUARD 4096
-#endif
-static constexpr size_t GUARD = RMCV_GUARD;
-static constexpr int GUARD_BYTE = 0xA5;
-template <typename T>
-static hipError_t dalloc_named(rmcv_ctx* c, T** p, size_t count, const char* name)
-{
-    void* q = nullptr;
-    const size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
-    hipError_t e = hipMalloc(&q, bytes + 2 * GUARD);
-    if (e == hipSuccess) {
-        c->allocs.push_back(q);
-        c->guarded.push_back({(uint8_t*)q, bytes, name});
-        *p = (T*)((uint8_t*)q + GUARD);
-        e = hipMemset(q, GUARD_BYTE, GUARD);
-        // the rounding slack behind the payload belongs to the rear zone
-        if (e == hipSuccess) e = hipMemset((uint8_t*)q + GUARD + count * sizeof(T), GUARD_BYTE, bytes - count * sizeof(T) + GUARD);
-        c->guarded.back().bytes = count * sizeof(T);
-        c->guarded.back().rear = bytes - count * sizeof(T) + GUARD;
-    }
-    return e;
-}
-#define dalloc(c, p, count) dalloc_named((c), (p), (count), #p)
 
 extern "C" {
 
@@ -274,23 +98,16 @@ void rmcv_ctx_destroy(rmcv_ctx* c)
         if (c->external_order && c->ext_done && c->timed_out) stuck |= wait_event_deadline(c->ext_done, t, &e) != 0;
         if (c->order_pending) stuck |= wait_event_deadline(c->ev_order, t, &e) == 1;
         if (c->stream) stuck |= wait_stream_deadline(c->stream, t, &e) == 1;
-        if (c->side) stuck |= wait_stream_deadline(c->side, t, &e) == 1;
+        if (c->chain.side) stuck |= wait_stream_deadline(c->chain.side, t, &e) == 1;
         if (stuck) {
             fprintf(stderr, "rmcv_ctx_destroy: work of this context has not finished after %d ms (enqueued last: %s); its buffers are leaked\n", t, c->last_what);
             delete c;
             return;
         }
     }
-    if (c->side) hipStreamDestroy(c->side);
-    if (c->ev_fork) hipEventDestroy(c->ev_fork);
+    c->chain.release();
     for (void* p : c->allocs) hipFree(p);
     if (c->own_frames) hipFree(c->own_frames);
-    for (auto& r : c->registered) hipHostUnregister(const_cast<void*>(r.p));
-    if (c->h_image) hipHostFree(c->h_image);
-    if (c->h_iflags) hipHostFree(c->h_iflags);
-    for (void* h : {(void*)c->h_frame, (void*)c->h_hdr, (void*)c->h_pts, (void*)c->h_offs, (void*)c->h_blobs,
-                    (void*)c->h_blob_src, (void*)c->h_neg, (void*)c->h_armours})
-        if (h) hipHostFree(h);
     for (auto& e : c->ev)
         if (e) hipEventDestroy(e);
     if (c->ev_order) hipEventDestroy(c->ev_order);
@@ -323,15 +140,10 @@ int rmcv_ctx_create(int device, const rmcv_limits* limits, rmcv_ctx** out)
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking);
     for (int i = 0; i < 6 && e == hipSuccess; i++) e = hipEventCreate(&c->ev[i]);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_order, hipEventDisableTiming);
-    if (e == hipSuccess) e = hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming);
-    if (e == hipSuccess) {
-        e = hipStreamCreateWithPriority(&c->side, hipStreamNonBlocking, 0);
-    }
+    if (e == hipSuccess) e = c->chain.init();
     if (e == hipSuccess) {
         hipDeviceProp_t prop;
         c->geom.device = device;
-        if (getenv("RMCV_IMAGE_EXPORT")) c->image_export = atoi(getenv("RMCV_IMAGE_EXPORT")); // (the options' defaults for hosts that cannot call them: tools/frame_chain.c)
-        if (getenv("RMCV_FRAME_UPLOAD")) c->frame_upload = atoi(getenv("RMCV_FRAME_UPLOAD"));
         c->geom.n_cu = (device < MAX_DEVICES && hipGetDeviceProperties(&prop, device) == hipSuccess) ? prop.multiProcessorCount : 0;
         if (device >= MAX_DEVICES) e = hipErrorInvalidDevice;
     }
@@ -420,7 +232,6 @@ void ctx_external_order(rmcv_ctx* c, hipEvent_t done)
 const Limits& ctx_limits(const rmcv_ctx* c) { return c->lim; }
 uint64_t ctx_blocking_calls(const rmcv_ctx* c) { return c->blocking_calls; }
 int ctx_wait_timeout_ms(const rmcv_ctx* c) { return c->wait_timeout_ms; }
-static PixelVariant geom_variant(const Geom& g) { return pixel_variant(g.input_format, g.enhance, g.win, g.keys); }
 bool pixel_ws_full(const rmcv_ctx* c, int lower_bound, const RunPlan& plan)
 {
     return pixel_shape(pixel_batch(c->geom, c->bufs, geom_variant(c->geom), lower_bound, plan)).ws_full;
@@ -428,8 +239,6 @@ bool pixel_ws_full(const rmcv_ctx* c, int lower_bound, const RunPlan& plan)
 RunPlan ctx_plan(const rmcv_ctx* c) { return {c->pixel_shape, c->pixel_groups, c->sparse_waves, c->dense_defer ? SPARSE_SPLIT_BOTH : SPARSE_STANDARD}; }
 int ctx_enhance(const rmcv_ctx* c) { return c->enhance; }
 PixelVariant ctx_pixel_variant(const rmcv_ctx* c) { return geom_variant(c->geom); }
-// bytes of one sample of what the context's options describe: 3 per BGR pixel, 1 or 2 per Bayer sample
-static int ctx_pixel_bytes(const rmcv_ctx* c) { return c->input_format ? c->input_sample_bits / 8 : 3; }
 int ctx_compact(rmcv_ctx* c, void* d_armours_out, int cap, void* d_frame_offs, void* d_status_or, hipStream_t s, void* hd_record, int host_head)
 {
     HIPCHK(c, launch_compact_armours(c->geom, c->bufs, c->lim, (rmcv_armour*)d_armours_out, cap, (int32_t*)d_frame_offs, s, (int32_t*)d_status_or, (uint8_t*)hd_record, host_head), "k_compact_armours");
@@ -437,14 +246,7 @@ int ctx_compact(rmcv_ctx* c, void* d_armours_out, int cap, void* d_frame_offs, v
 }
 } // namespace rmcv
 
-// frame slot 0 of the device buffers no longer holds what the per-frame chain returned last (see rmcv_ctx::res_nc)
-static void resident_none(rmcv_ctx* c)
-{
-    c->res_nc = c->res_nb = -1;
-    c->ahead_lb = c->ahead_ar = false;
-}
-
-static int ensure_own_frames(rmcv_ctx* c, size_t need)
+int rmcv::ensure_own_frames(rmcv_ctx* c, size_t need)
 {
     if (need <= c->own_frames_bytes) return RMCV_OK;
     if (c->own_frames) hipFree(c->own_frames);
@@ -454,31 +256,6 @@ static int ensure_own_frames(rmcv_ctx* c, size_t need)
     if (cap < need) cap = need;
     HIPCHK(c, hipMalloc((void**)&c->own_frames, cap), "hipMalloc frames");
     c->own_frames_bytes = cap;
-    return RMCV_OK;
-}
-
-// pinned host staging + the device header word of the per-frame path (lazy: batch users never pay for it)
-static int ensure_staging(rmcv_ctx* c)
-{
-    if (c->h_hdr) return RMCV_OK;
-    const Limits& L = c->lim;
-    hipError_t e = hipHostMalloc((void**)&c->h_hdr, 16 * sizeof(int32_t), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_pts, (size_t)L.max_points * sizeof(rmcv_point), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_offs, (size_t)(L.max_contours + 1) * 4, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_blobs, (size_t)L.max_blobs * sizeof(rmcv_lightblob), hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_blob_src, (size_t)L.max_blobs * 4, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_neg, (size_t)L.max_contours * 4, hipHostMallocDefault);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&c->h_armours, (size_t)L.max_armours * sizeof(rmcv_armour), hipHostMallocDefault);
-    if (e == hipSuccess) e = dalloc(c, &c->d_hdr, 16);
-    if (e != hipSuccess) return fail(c, RMCV_ERR_NOMEM, "pinned staging", e);
-    memset(c->h_hdr, 0, 16 * sizeof(int32_t));
-    if (hipHostGetDevicePointer((void**)&c->hd_hdr, c->h_hdr, 0) != hipSuccess || hipHostGetDevicePointer((void**)&c->hd_pts, c->h_pts, 0) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&c->hd_offs, c->h_offs, 0) != hipSuccess || hipHostGetDevicePointer((void**)&c->hd_blobs, c->h_blobs, 0) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&c->hd_blob_src, c->h_blob_src, 0) != hipSuccess || hipHostGetDevicePointer((void**)&c->hd_neg, c->h_neg, 0) != hipSuccess ||
-        hipHostGetDevicePointer((void**)&c->hd_armours, c->h_armours, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        c->hd_hdr = nullptr; // k_export is not used
-    }
     return RMCV_OK;
 }
 
@@ -589,56 +366,12 @@ __global__ void k_delay(unsigned long long ns)
 hipError_t launch_delay(unsigned long long ns, hipStream_t s) { return launch(k_delay, dim3(1), dim3(64), 0, s, ns); }
 } // namespace rmcv
 
-namespace rmcv {
-// The byte image of one frame on its way to the caller (rmcv_extract_color's `binary_out`) WITHOUT the HIP runtime's pageable copy
-// (RMCV_OPT_IMAGE_EXPORT = 1; round 5).  hipMemcpyAsync to pageable memory does its work INSIDE the call: 35 us when all is well,
-// 160-280 us in some processes (bench.py's C-host child, every time; a process started right behind the GPU test suite, once: the
-// per-frame chain then takes 0.28-0.40 ms instead of 0.18 -- VERDICT r4 weak #4; not reproduced by an idle process with three
-// full-size pipelines beside the chain, by 12 hardware queues, or by how the caller's buffer is backed: tools/chain_ab.sh,
-// chain_beside.sh, chain_queues.sh).  This path has no runtime-internal wait: a kernel on the side stream copies the image into pinned host
-// memory chunk by chunk and raises a flag word per chunk (system-scope release behind the chunk's stores); the host polls the flags
-// in memory -- no HIP call -- and copies each chunk into the caller's buffer while the next ones cross PCIe.  Measured: 0.190 ms per
-// chain alone (the runtime's copy: 0.186), 0.19-0.20 where the runtime's copy reads 0.28-0.40.
-constexpr int IMG_CHUNKS = 16, IMG_CHUNKS_DEFAULT = 8, IMG_GROUPS = 16; // IMG_CHUNKS: the flags' capacity.  Measured (1280x1024, from C, ms per chain; the runtime's copy: 0.186): 8 chunks x 16 workgroups 0.190, 4 x 8 0.189, 16 x 16 0.193, 8 x 8 0.195, 4 x 16 0.199, 8 x 32 0.200, 2 x 16 0.201, 1 x 16 0.207 (a fence per chunk and workgroup costs microseconds; all chunks at once leave the CPU copy nothing to overlap)
-// All IMG_GROUPS workgroups work on chunk 0 first, then on chunk 1, ...: the chunks reach the host ONE AFTER THE OTHER (the CPU copies
-// chunk g into the caller's buffer while chunk g + 1 crosses PCIe), not all at the end.  A workgroup that has stored its slice of a
-// chunk (system-scope fence behind the stores) counts itself in; the last one raises the chunk's flag in host memory.
-__global__ __launch_bounds__(256) void k_image_export(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, long long bytes,
-                                                      uint32_t* __restrict__ flags, uint32_t seq, uint32_t* __restrict__ arrived, int n_chunks)
-{
-    const int wg = blockIdx.x, tid = threadIdx.x;
-    const long long per = ((bytes + n_chunks - 1) / n_chunks + 15) & ~15ll; // (the host computes the same chunk bounds: image_chunk)
-    for (int g = 0; g < n_chunks; g++) {
-        const long long lo = (long long)g * per < bytes ? (long long)g * per : bytes, hi = lo + per < bytes ? lo + per : bytes;
-        const long long hv = lo + ((hi - lo) & ~15ll);
-        for (long long o = lo + ((long long)wg * 256 + tid) * 16; o < hv; o += (long long)gridDim.x * 256 * 16)
-            *reinterpret_cast<uint4*>(dst + o) = *reinterpret_cast<const uint4*>(src + o);
-        if (wg == 0 && hv + tid < hi) dst[hv + tid] = src[hv + tid]; // (the image's last bytes: fewer than 16)
-        __threadfence_system();
-        __syncthreads();
-        if (tid == 0) {
-            const uint32_t before = __hip_atomic_fetch_add(&arrived[g], 1u, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_AGENT);
-            if (before == gridDim.x - 1) {
-                __hip_atomic_store(&arrived[g], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); // (for the next frame: launches of one context are ordered)
-                __hip_atomic_store(&flags[g], seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
-            }
-        }
-    }
-}
-static inline void image_chunk(long long bytes, int n_chunks, int g, long long* lo, long long* hi)
-{
-    const long long per = ((bytes + n_chunks - 1) / n_chunks + 15) & ~15ll;
-    *lo = (long long)g * per < bytes ? (long long)g * per : bytes;
-    *hi = *lo + per < bytes ? *lo + per : bytes;
-}
-} // namespace rmcv
-
 // Bind a geometry.  When it changes the padded planes are zeroed (their pads must read 0) and the frame order is recomputed -- both
 // ENQUEUED: on `as` when the caller (a pipeline) orders this context's work on its own streams and has already made `as` wait for the
 // context's last batch; otherwise on the context's stream, behind a wait for everything the context has in flight and with a wait for
 // them behind (the launches that follow may go to any stream of the caller's).
 // BGR frames have no sample size and no orientation of their own: a context left at 16 bits or mirrored / flipped would read them wrongly
-static int check_layout(rmcv_ctx* c)
+int rmcv::check_layout(rmcv_ctx* c)
 {
     if (c->input_format != RMCV_INPUT_BGR) return RMCV_OK;
     if (c->input_sample_bits != 8) return fail(c, RMCV_ERR_BAD_ARG, "a BGR frame with RMCV_OPT_INPUT_SAMPLE_BITS = 16: the option is for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
@@ -646,7 +379,7 @@ static int check_layout(rmcv_ctx* c)
     return RMCV_OK;
 }
 // a frame pointer of 2-byte samples
-static int check_sample_ptr(rmcv_ctx* c, const void* p)
+int rmcv::check_sample_ptr(rmcv_ctx* c, const void* p)
 {
     if (c->input_format && c->input_sample_bits == 16 && ((uintptr_t)p & 1))
         return fail(c, RMCV_ERR_BAD_ARG, "16-bit samples (RMCV_OPT_INPUT_SAMPLE_BITS): the frame pointer must be 2-byte aligned");
@@ -674,7 +407,7 @@ static int check_frame_camps(rmcv_ctx* c, int fmt, int enh) { return refuse(c, p
 static int set_extent(rmcv_ctx* c, int w, int h, hipStream_t as);
 
 // win_w > 0: the frames are read through win_w x win_h windows (checked by the caller: check_windows)
-static int set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t as = nullptr, int win_w = 0, int win_h = 0)
+int rmcv::set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t as, int win_w, int win_h)
 {
     if (n_frames < 1 || n_frames > c->lim.max_frames) return fail(c, RMCV_ERR_BAD_ARG, "n_frames out of range");
     if (w < 1 || h < 1 || w > c->lim.max_width || h > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, "frame size out of range");
@@ -957,16 +690,16 @@ int rmcv_ctx_set_option(rmcv_ctx* c, int option, int value)
         return RMCV_OK;
     }
     if (option == RMCV_OPT_RUN_AHEAD && (value == 0 || value == 1)) {
-        c->run_ahead = value;
+        c->chain.run_ahead = value;
         return RMCV_OK;
     }
     if (option == RMCV_OPT_FRAME_UPLOAD && value >= 0 && value <= 3) {
-        c->frame_upload = value;
-        c->slow_upload = c->hold_upload = 0;
+        c->chain.frame_upload = value;
+        c->chain.copy_up = {};
         return RMCV_OK;
     }
     if (option == RMCV_OPT_TEST_SLOW_US && value >= 0) {
-        c->test_slow_us = value;
+        c->chain.test_slow_us = value;
         return RMCV_OK;
     }
     if (option == RMCV_OPT_PIXEL_HALO_NT && (value == 0 || value == 1)) {
@@ -995,8 +728,8 @@ int rmcv_ctx_set_option(rmcv_ctx* c, int option, int value)
         return RMCV_OK;
     }
     if (option == RMCV_OPT_IMAGE_EXPORT && value >= 0 && value <= 2) {
-        c->image_export = value;
-        c->slow_image = c->hold_image = 0;
+        c->chain.image_export = value;
+        c->chain.copy_img = {};
         return RMCV_OK;
     }
     if (option == RMCV_OPT_WAIT_TIMEOUT_MS && value >= 0) {
@@ -1034,14 +767,6 @@ int rmcv_ctx_set_option(rmcv_ctx* c, int option, int value)
     return fail(c, RMCV_ERR_BAD_ARG, "unknown option or value");
 }
 
-int rmcv_ctx_frame_timing(const rmcv_ctx* c, double* us, int cap)
-{
-    if (!c || !us || cap < 7) return RMCV_ERR_BAD_ARG;
-    for (int i = 0; i < 7; i++) us[i] = c->marks[i + 1] - c->marks[i];
-    if (cap >= 9) { us[7] = c->upload_now; us[8] = c->image_now; }
-    return RMCV_OK;
-}
-
 int rmcv_ctx_check_guards(rmcv_ctx* c, int32_t* n_damaged)
 {
     if (!c || !n_damaged) return RMCV_ERR_BAD_ARG;
@@ -1067,20 +792,6 @@ int rmcv_ctx_check_guards(rmcv_ctx* c, int32_t* n_damaged)
         }
     }
     *n_damaged = bad;
-    return RMCV_OK;
-}
-
-int rmcv_ctx_forget_frame_buffer(rmcv_ctx* c, const void* frame)
-{ // RMCV_OPT_FRAME_UPLOAD = 2 keys its pinnings by address: a buffer must be forgotten before it is freed (see the header)
-    if (!c) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
-    for (size_t i = 0; i < c->registered.size();) {
-        if (!frame || c->registered[i].p == frame) {
-            hipHostUnregister(const_cast<void*>(c->registered[i].p));
-            c->registered.erase(c->registered.begin() + i);
-        } else i++;
-    }
     return RMCV_OK;
 }
 
@@ -1320,519 +1031,6 @@ int rmcv_classify_armours(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int str
     return RMCV_OK;
 }
 
-/* ---------------- single-frame, host-buffer entry points ----------------
- * The chain an unchanged executable/main.cpp:172-176 runs on every camera frame.  Each call is ONE stream sequence with ONE
- * synchronisation: upload (pinned staging) -> kernels -> a header word + fixed windows of the results copied back
- * speculatively (a frame has ~1000 contour points, ~10 blobs, ~3 armours; what does not fit a window is fetched by a second
- * copy).  Results stay on the device: when the next call is handed exactly the bytes the previous one returned, it runs on the
- * resident buffers instead of uploading them again. */
-static constexpr int SF_OFFS_WIN = 1024, SF_PTS_WIN = 8192, SF_BLOB_WIN = 64, SF_NEG_WIN = 1024, SF_ARM_WIN = 32;
-
-// bring one frame (BGR, or a mosaic: rowb = 3 w or w bytes per row) into own_frames (frame slot 0) on the context's stream;
-// RMCV_OPT_FRAME_UPLOAD selects how
-static int upload_one(rmcv_ctx* c, const uint8_t* bgr, int rowb, int h, int stride, int dstride)
-{
-    const size_t dpitch = (size_t)dstride * h;
-    hipStream_t s = c->stream;
-    const int mode = c->frame_upload == 3 ? (c->hold_upload > 0 ? 1 : 0) : c->frame_upload;
-    c->upload_now = mode;
-    if (mode == 2) { // pin the caller's buffer once (camera SDKs hand out a small ring of frame buffers) and DMA from it
-        const size_t span = (size_t)stride * (h - 1) + (size_t)rowb;
-        bool known = false;
-        for (auto& r : c->registered) known |= (r.p == bgr && r.bytes >= span);
-        if (!known) {
-            if (c->registered.size() >= 16) { // a ring larger than this is not a ring: forget the oldest
-                hipHostUnregister(const_cast<void*>(c->registered.front().p));
-                c->registered.erase(c->registered.begin());
-            }
-            if (hipHostRegister(const_cast<uint8_t*>(bgr), span, hipHostRegisterDefault) == hipSuccess) {
-                c->registered.push_back({bgr, span});
-                known = true;
-            } else {
-                (void)hipGetLastError(); // e.g. already registered by the application: plain copy below
-            }
-        }
-        HIPCHK(c, hipMemcpy2DAsync(c->own_frames, dstride, bgr, stride, (size_t)rowb, h, hipMemcpyHostToDevice, s), "H2D frame");
-        return RMCV_OK;
-    }
-    if (mode == 0) { // the runtime's own pageable path
-        HIPCHK(c, hipMemcpy2DAsync(c->own_frames, dstride, bgr, stride, (size_t)rowb, h, hipMemcpyHostToDevice, s), "H2D frame");
-        return RMCV_OK;
-    }
-    if (dpitch > c->h_frame_bytes) {
-        if (c->h_frame) hipHostFree(c->h_frame);
-        c->h_frame = nullptr;
-        c->h_frame_bytes = 0;
-        size_t cap = (size_t)((3 * c->lim.max_width + 15) & ~15) * c->lim.max_height;
-        if (cap < dpitch) cap = dpitch;
-        HIPCHK(c, hipHostMalloc((void**)&c->h_frame, cap, hipHostMallocDefault), "pinned frame staging");
-        c->h_frame_bytes = cap;
-    }
-    // two halves: the DMA of the first runs while the CPU copies the second (eight pieces, measured in round 5: 0.254-0.281 ms per chain
-    // against 0.223 -- every further hipMemcpyAsync costs the host 4-5 us, more than the earlier start of the DMA buys)
-    const int parts = 2;
-    for (int part = 0; part < parts; part++) {
-        const int y0 = (int)((long long)h * part / parts), y1 = (int)((long long)h * (part + 1) / parts);
-        if (y1 <= y0) continue;
-        if (stride == dstride) memcpy(c->h_frame + (size_t)y0 * dstride, bgr + (size_t)y0 * stride, (size_t)(y1 - y0) * dstride);
-        else
-            for (int y = y0; y < y1; y++) memcpy(c->h_frame + (size_t)y * dstride, bgr + (size_t)y * stride, (size_t)rowb);
-        HIPCHK(c, hipMemcpyAsync(c->own_frames + (size_t)y0 * dstride, c->h_frame + (size_t)y0 * dstride, (size_t)(y1 - y0) * dstride,
-                                 hipMemcpyHostToDevice, s), "H2D frame");
-    }
-    return RMCV_OK;
-}
-
-// the blob stage on frame slot 0 + its results on their way to pinned memory (header at h_hdr[4..6]); no synchronisation
-static int enqueue_blobs(rmcv_ctx* c, const rmcv_ctx::LbParams& q, bool compute = true, bool download = true)
-{
-    rmcv_params p;
-    rmcv_default_params(&p);
-    p.tilt_max = q.tilt_max;
-    p.ratio_lo = q.ratio_lo;
-    p.ratio_hi = q.ratio_hi;
-    p.area_lo = q.area_lo;
-    p.area_hi = q.area_hi;
-    p.camp = q.enemy;
-    Geom g1 = c->geom;
-    g1.n_frames = 1;
-    g1.keys = 0; // (the caller's enemy, whatever keys the batch bound to the context has)
-    const Bufs& b = c->bufs;
-    hipStream_t s = c->stream;
-    if (compute) {
-        HIPCHK(c, launch_status_clear(g1, b, RMCV_FRAME_OVF_BLOBS | RMCV_FRAME_OVF_ARMOURS | RMCV_FRAME_HULL, s), "k_status_clear");
-        HIPCHK(c, launch_blobs(g1, b, c->lim, p, s), "k_blobs");
-    }
-    if (!download) return RMCV_OK; // (the caller sends everything home with one k_export)
-    HIPCHK(c, launch_gather3(b.n_blobs, b.n_neg, b.status, c->d_hdr + 4, s), "k_gather3");
-    HIPCHK(c, hipMemcpyAsync(c->h_hdr + 4, c->d_hdr + 4, 3 * 4, hipMemcpyDeviceToHost, s), "D2H");
-    const int bw = std::min(SF_BLOB_WIN, c->lim.max_blobs), nw = std::min(SF_NEG_WIN, c->lim.max_contours);
-    HIPCHK(c, hipMemcpyAsync(c->h_blobs, b.blobs, (size_t)bw * sizeof(rmcv_lightblob), hipMemcpyDeviceToHost, s), "D2H blobs");
-    HIPCHK(c, hipMemcpyAsync(c->h_blob_src, b.blob_src, (size_t)bw * 4, hipMemcpyDeviceToHost, s), "D2H blob_src");
-    HIPCHK(c, hipMemcpyAsync(c->h_neg, b.neg_idx, (size_t)nw * 4, hipMemcpyDeviceToHost, s), "D2H neg");
-    return RMCV_OK;
-}
-
-// after the stream has been synchronised: what did not fit the windows, then the hand-over to the caller
-static int finish_blobs(rmcv_ctx* c, rmcv_lightblob* blobs_out, int blobs_cap, int32_t* n_blobs, int32_t* blob_src, int32_t* neg_idx_out,
-                        int32_t* n_neg)
-{
-    const Bufs& b = c->bufs;
-    const int bw = std::min(SF_BLOB_WIN, c->lim.max_blobs), nw = std::min(SF_NEG_WIN, c->lim.max_contours);
-    const int32_t nb = c->h_hdr[4], nn = c->h_hdr[5], st = c->h_hdr[6];
-    if (n_blobs) *n_blobs = nb;
-    if (n_neg) *n_neg = nn;
-    if (st & RMCV_FRAME_OVF_BLOBS) return fail(c, RMCV_ERR_CAPACITY, "context limit exceeded (max_blobs)");
-    if (nb > bw) {
-        HIPCHK(c, hipMemcpy(c->h_blobs + bw, b.blobs + bw, (size_t)(nb - bw) * sizeof(rmcv_lightblob), hipMemcpyDeviceToHost), "D2H blobs");
-        HIPCHK(c, hipMemcpy(c->h_blob_src + bw, b.blob_src + bw, (size_t)(nb - bw) * 4, hipMemcpyDeviceToHost), "D2H blob_src");
-    }
-    if (nn > nw) HIPCHK(c, hipMemcpy(c->h_neg + nw, b.neg_idx + nw, (size_t)(nn - nw) * 4, hipMemcpyDeviceToHost), "D2H neg");
-    c->res_nb = nb; // the device holds this positive list, h_blobs its bytes
-    if (nb > blobs_cap) return fail(c, RMCV_ERR_CAPACITY, "output capacity exceeded");
-    if (blobs_out && nb) memcpy(blobs_out, c->h_blobs, (size_t)nb * sizeof(rmcv_lightblob));
-    if (blob_src && nb) memcpy(blob_src, c->h_blob_src, (size_t)nb * 4);
-    if (neg_idx_out && nn) memcpy(neg_idx_out, c->h_neg, (size_t)nn * 4);
-    return RMCV_OK;
-}
-
-static int enqueue_armours(rmcv_ctx* c, const rmcv_ctx::ArParams& q, bool compute = true, bool download = true)
-{
-    rmcv_params p;
-    rmcv_default_params(&p);
-    p.angle_diff_max = q.angle_diff_max;
-    p.shear_max = q.shear_max;
-    p.length_ratio_max = q.length_ratio_max;
-    p.camp = q.enemy;
-    Geom g1 = c->geom;
-    g1.n_frames = 1;
-    g1.keys = 0; // (the caller's enemy, whatever keys the batch bound to the context has)
-    const Bufs& b = c->bufs;
-    hipStream_t s = c->stream;
-    if (compute) {
-        HIPCHK(c, launch_status_clear(g1, b, RMCV_FRAME_OVF_ARMOURS, s), "k_status_clear");
-        HIPCHK(c, launch_armours(g1, b, c->lim, p, s), "k_armours");
-    }
-    if (!download) return RMCV_OK;
-    HIPCHK(c, launch_gather3(b.n_armours, b.status, b.status, c->d_hdr + 8, s), "k_gather3");
-    HIPCHK(c, hipMemcpyAsync(c->h_hdr + 8, c->d_hdr + 8, 3 * 4, hipMemcpyDeviceToHost, s), "D2H");
-    const int aw = std::min(SF_ARM_WIN, c->lim.max_armours);
-    HIPCHK(c, hipMemcpyAsync(c->h_armours, b.armours, (size_t)aw * sizeof(rmcv_armour), hipMemcpyDeviceToHost, s), "D2H armours");
-    return RMCV_OK;
-}
-
-static int finish_armours(rmcv_ctx* c, rmcv_armour* armours_out, int armours_cap, int32_t* n_armours)
-{
-    const Bufs& b = c->bufs;
-    const int aw = std::min(SF_ARM_WIN, c->lim.max_armours);
-    const int32_t na = c->h_hdr[8], st = c->h_hdr[9];
-    if (n_armours) *n_armours = na;
-    if (st & RMCV_FRAME_OVF_ARMOURS) return fail(c, RMCV_ERR_CAPACITY, "context limit exceeded (max_armours)");
-    if (na > aw) HIPCHK(c, hipMemcpy(c->h_armours + aw, b.armours + aw, (size_t)(na - aw) * sizeof(rmcv_armour), hipMemcpyDeviceToHost), "D2H armours");
-    if (na > armours_cap) return fail(c, RMCV_ERR_CAPACITY, "output capacity exceeded");
-    if (armours_out && na) memcpy(armours_out, c->h_armours, (size_t)na * sizeof(rmcv_armour));
-    return RMCV_OK;
-}
-
-// the pinned, device-mapped landing buffer of the byte image + its chunk flags (lazy; false: not to be had -> the runtime's copy)
-static bool image_ready(rmcv_ctx* c, size_t bytes)
-{
-    if (!(c->image_export == 1 || (c->image_export == 2 && c->hold_image > 0))) return false; // RMCV_OPT_IMAGE_EXPORT
-    if (!c->h_iflags) {
-        if (hipHostMalloc((void**)&c->h_iflags, IMG_CHUNKS * sizeof(uint32_t), hipHostMallocMapped) != hipSuccess ||
-            hipHostGetDevicePointer((void**)&c->hd_iflags, c->h_iflags, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            if (c->h_iflags) hipHostFree(c->h_iflags);
-            c->h_iflags = c->hd_iflags = nullptr;
-            return false;
-        }
-        memset(c->h_iflags, 0, IMG_CHUNKS * sizeof(uint32_t));
-        if (dalloc(c, &c->d_iarrived, IMG_CHUNKS) != hipSuccess || hipMemset(c->d_iarrived, 0, IMG_CHUNKS * sizeof(uint32_t)) != hipSuccess) {
-            (void)hipGetLastError();
-            hipHostFree(c->h_iflags);
-            c->h_iflags = c->hd_iflags = nullptr;
-            return false;
-        }
-    }
-    if (bytes > c->h_image_bytes) {
-        if (c->h_image) hipHostFree(c->h_image);
-        c->h_image = c->hd_image = nullptr;
-        c->h_image_bytes = 0;
-        size_t cap = (size_t)c->lim.max_width * c->lim.max_height;
-        if (cap < bytes) cap = bytes;
-        if (hipHostMalloc((void**)&c->h_image, cap, hipHostMallocMapped) != hipSuccess || hipHostGetDevicePointer((void**)&c->hd_image, c->h_image, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            if (c->h_image) hipHostFree(c->h_image);
-            c->h_image = c->hd_image = nullptr;
-            return false;
-        }
-        c->h_image_bytes = cap;
-    }
-    return true;
-}
-
-static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, int camp, int lower_bound, int morph,
-                              uint8_t* binary_out, rmcv_point* pts_out, int pts_cap, int32_t* offs_out, int contours_cap,
-                              int32_t* n_contours, int32_t* n_points);
-
-int rmcv_extract_color(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, int camp, int lower_bound, int morph,
-                       uint8_t* binary_out, rmcv_point* pts_out, int pts_cap, int32_t* offs_out, int contours_cap,
-                       int32_t* n_contours, int32_t* n_points)
-{
-    const int rc = extract_color_body(c, bgr, w, h, stride, camp, lower_bound, morph, binary_out, pts_out, pts_cap, offs_out,
-                                      contours_cap, n_contours, n_points);
-    // The body enqueues an upload FROM the caller's frame and a download INTO the caller's `binary_out`.  An error return after
-    // the first of them must not leave either in flight: the caller owns those buffers again the moment this function returns.
-    // (RMCV_ERR_TIMEOUT is the exception: the wait has just run out -- see the header.)
-    if (rc != RMCV_OK && rc != RMCV_ERR_TIMEOUT && c) {
-        hipError_t e = hipSuccess;
-        (void)wait_stream_deadline(c->stream, c->wait_timeout_ms, &e);
-        if (c->side) (void)wait_stream_deadline(c->side, c->wait_timeout_ms, &e);
-    }
-    return rc;
-}
-
-static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, int camp, int lower_bound, int morph,
-                              uint8_t* binary_out, rmcv_point* pts_out, int pts_cap, int32_t* offs_out, int contours_cap,
-                              int32_t* n_contours, int32_t* n_points)
-{
-    if (!c || !bgr) return RMCV_ERR_BAD_ARG;
-    if (morph < RMCV_MORPH_NONE || morph > RMCV_MORPH_CLOSE) return fail(c, RMCV_ERR_BAD_ARG, "bad morph");
-    hipSetDevice(c->device);
-    c->marks[0] = now_us();
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
-    resident_none(c);
-    if ((rc = ensure_staging(c))) return rc;
-    if ((rc = check_layout(c)) || (rc = check_sample_ptr(c, bgr))) return rc;
-    const int rowb = ctx_pixel_bytes(c) * w; // a mosaic (RMCV_OPT_INPUT_FORMAT): one sample per pixel, 1 or 2 bytes
-    const int dstride = (rowb + 15) & ~15;
-    if ((rc = set_geom(c, 1, w, h, dstride, (int64_t)dstride * h))) return rc;
-    if (stride < rowb) return fail(c, RMCV_ERR_BAD_ARG, "bad stride");
-    if (c->geom.sample_bytes == 2 && (stride & 1)) return fail(c, RMCV_ERR_BAD_ARG, "16-bit samples (RMCV_OPT_INPUT_SAMPLE_BITS): stride is bytes and must be even");
-    if ((rc = ensure_own_frames(c, (size_t)dstride * h))) return rc;
-    if ((rc = upload_one(c, bgr, rowb, h, stride, dstride))) return rc;
-    c->marks[1] = now_us(); // the upload is enqueued (pageable: the runtime may have copied it by now)
-    c->bufs.frames = c->own_frames;
-    const Geom& g = c->geom;
-    const Bufs& b = c->bufs;
-    hipStream_t s = c->stream;
-    RunPlan plan = ctx_plan(c);
-    plan.sparse_waves = 8; // one frame: the latency setting
-    if (c->test_delay_us) { // RMCV_OPT_TEST_DELAY_US: a stand-in for a kernel that does not finish in time (one shot)
-        HIPCHK(c, launch_delay((unsigned long long)c->test_delay_us * 1000ull, s), "k_delay (RMCV_OPT_TEST_DELAY_US)");
-        c->test_delay_us = 0;
-    }
-    if (g.enhance) HIPCHK(c, launch_enhance_tables(g, b, lower_bound, s), "k_frame_sums + k_enhance_table"); // RMCV_OPT_ENHANCE: the frame is read through its table
-    HIPCHK(c, launch_binary(g, b, camp, lower_bound, morph, binary_out != nullptr, plan, s, &c->image), PIXEL_VARIANTS[geom_variant(g)].kernel);
-    if (binary_out) HIPCHK(c, hipEventRecord(c->ev_fork, s), "image download: mark");
-    // running ahead with both parameter sets known: the frame's whole sparse part is ONE kernel (the fused per-frame kernel of
-    // the batch path: findContours, fits and pairing back to back), not three
-    const bool fused_ahead = c->run_ahead && c->last_lb_valid && c->last_ar_valid && c->last_lb.enemy == c->last_ar.enemy;
-    if (fused_ahead) {
-        rmcv_params p;
-        rmcv_default_params(&p);
-        p.tilt_max = c->last_lb.tilt_max;
-        p.ratio_lo = c->last_lb.ratio_lo;
-        p.ratio_hi = c->last_lb.ratio_hi;
-        p.area_lo = c->last_lb.area_lo;
-        p.area_hi = c->last_lb.area_hi;
-        p.camp = c->last_lb.enemy;
-        p.angle_diff_max = c->last_ar.angle_diff_max;
-        p.shear_max = c->last_ar.shear_max;
-        p.length_ratio_max = c->last_ar.length_ratio_max;
-        HIPCHK(c, launch_sparse(g, b, c->lim, p, true, false, plan, s), "k_contours (fused)");
-    } else {
-        HIPCHK(c, launch_contours(g, b, c->lim, s), "k_contours");
-    }
-    // Results go home by kernel stores into the pinned buffers (ExportArgs) instead of a row of small copies -- each of those is a
-    // hand-over from the compute queue to the copy engine and back, 5-8 us apiece, nine of them when the chain runs ahead
-    // (0.256 -> 0.202 ms per chain, tools/frame_chain.py).  When the frame's whole sparse part has run already (fused_ahead) the
-    // kernel that packs the contours does it on its way out; otherwise one k_export behind the last stage.
-    static const bool use_export = !(getenv("RMCV_EXPORT") && atoi(getenv("RMCV_EXPORT")) == 0); // dev knob for A/B runs
-    const bool exporting = use_export && c->hd_hdr != nullptr;
-    const bool will_lb = c->last_lb_valid && c->run_ahead, will_ar = will_lb && c->last_ar_valid;
-    ExportArgs ex;
-    memset(&ex, 0, sizeof(ex));
-    if (exporting) {
-        ex.hdr_dst = c->hd_hdr;
-        ex.hdr_src[0] = c->d_hdr; ex.hdr_src[1] = c->d_hdr + 1; ex.hdr_src[2] = c->d_hdr + 2;
-        ex.sec[ex.n_sec++] = {c->pack_offs, c->hd_offs, c->d_hdr, 1, 4, std::min(SF_OFFS_WIN, c->lim.max_contours) + 1};
-        ex.sec[ex.n_sec++] = {c->pack_pts, c->hd_pts, c->d_hdr + 1, 0, (int)sizeof(rmcv_point), std::min(SF_PTS_WIN, c->lim.max_points)};
-        if (will_lb) {
-            const int bw = std::min(SF_BLOB_WIN, c->lim.max_blobs), nw = std::min(SF_NEG_WIN, c->lim.max_contours);
-            ex.hdr_src[4] = b.n_blobs; ex.hdr_src[5] = b.n_neg; ex.hdr_src[6] = b.status;
-            ex.sec[ex.n_sec++] = {b.blobs, c->hd_blobs, b.n_blobs, 0, (int)sizeof(rmcv_lightblob), bw};
-            ex.sec[ex.n_sec++] = {b.blob_src, c->hd_blob_src, b.n_blobs, 0, 4, bw};
-            ex.sec[ex.n_sec++] = {b.neg_idx, c->hd_neg, b.n_neg, 0, 4, nw};
-        }
-        if (will_ar) {
-            ex.hdr_src[8] = b.n_armours; ex.hdr_src[9] = b.status; ex.hdr_src[10] = b.status;
-            ex.sec[ex.n_sec++] = {b.armours, c->hd_armours, b.n_armours, 0, (int)sizeof(rmcv_armour), std::min(SF_ARM_WIN, c->lim.max_armours)};
-        }
-    }
-    const bool export_in_pack = exporting && fused_ahead; // (fused_ahead: the blobs and armours exist before the contours are packed)
-    HIPCHK(c, launch_pack_contours(g, b, c->lim, c->pack_pts, c->pack_offs, c->d_hdr, s, export_in_pack ? &ex : nullptr), "k_pack_contours");
-    if (!exporting) {
-        HIPCHK(c, hipMemcpyAsync(c->h_hdr, c->d_hdr, 3 * 4, hipMemcpyDeviceToHost, s), "D2H");
-        HIPCHK(c, hipMemcpyAsync(c->h_offs, c->pack_offs, (size_t)(std::min(SF_OFFS_WIN, c->lim.max_contours) + 1) * 4, hipMemcpyDeviceToHost, s), "D2H offs");
-        HIPCHK(c, hipMemcpyAsync(c->h_pts, c->pack_pts, (size_t)std::min(SF_PTS_WIN, c->lim.max_points) * sizeof(rmcv_point), hipMemcpyDeviceToHost, s), "D2H pts");
-    }
-    // the byte image goes straight to the caller's buffer (the runtime's pageable path: 37 us for 1.3 MB); through the pinned
-    // staging buffer it cost a 65 us CPU copy on top of the DMA
-    bool ahead_lb = false, ahead_ar = false;
-    if (will_lb) { // the filters of this frame, with the previous frame's parameters (see rmcv_ctx::last_lb)
-        if ((rc = enqueue_blobs(c, c->last_lb, !fused_ahead, !exporting))) return rc;
-        ahead_lb = true;
-        if (will_ar) {
-            if ((rc = enqueue_armours(c, c->last_ar, !fused_ahead, !exporting))) return rc;
-            ahead_ar = true;
-        }
-    }
-    if (exporting && !export_in_pack) HIPCHK(c, launch_export(ex, s), "k_export");
-    // The byte image is complete when k_binary is: its download (1.3 MB, 37 us) runs on the side stream BESIDE the sparse kernels
-    // instead of behind them.  Enqueued last: the runtime's pageable copy may keep this thread busy, and by now everything else of
-    // the frame is on the GPU's queues.
-    c->marks[2] = now_us(); // every kernel of the frame is enqueued
-    if (binary_out && image_ready(c, (size_t)w * h)) {
-        // k_image_export on the side stream, behind the pixel kernel and beside the sparse kernels; the host takes the chunks as their flags come up
-        const long long bytes = (long long)w * h;
-        if (++c->img_seq == 0) c->img_seq = 1;
-        HIPCHK(c, hipStreamWaitEvent(c->side, c->ev_fork, 0), "image download: fork");
-        const int n_chunks = IMG_CHUNKS_DEFAULT;
-        HIPCHK(c, launch(k_image_export, dim3(IMG_GROUPS), dim3(256), 0, c->side, b.binary, c->hd_image, bytes, c->hd_iflags, c->img_seq, c->d_iarrived, n_chunks), "k_image_export");
-        c->last_what = "k_binary, k_image_export";
-        const volatile uint32_t* fl = c->h_iflags;
-        const double t0w = now_us();
-        for (int gch = 0; gch < n_chunks; gch++) {
-            for (unsigned spins = 0; fl[gch] != c->img_seq; spins++) {
-                __builtin_ia32_pause();
-                if ((spins & 1023u) == 1023u) {
-                    const double dtw = now_us() - t0w;
-                    if (c->wait_timeout_ms > 0 && dtw > c->wait_timeout_ms * 1000.0) return wait_failed(c, 1, "rmcv_extract_color: waiting for the byte image", hipSuccess);
-                    if (dtw > 20000.0) { timespec nap = {0, 200000}; nanosleep(&nap, nullptr); } // (20 ms in: something is wrong; stop burning the core)
-                }
-            }
-            __atomic_thread_fence(__ATOMIC_ACQUIRE);
-            if (gch == 0) c->marks[3] = now_us(); // upload and pixel kernel are through, the first chunk is home
-            long long lo, hi;
-            image_chunk(bytes, n_chunks, gch, &lo, &hi);
-            if (hi > lo) memcpy(binary_out + lo, c->h_image + lo, (size_t)(hi - lo));
-        }
-        c->marks[4] = now_us(); // the byte image is in the caller's buffer
-        c->image_now = 1;
-    } else if (binary_out) {
-        c->image_now = 0; // (no mapped pinned memory to be had: the runtime's pageable copy)
-        c->last_what = "k_binary";
-        WAITCHK(c, wait_event(c, c->ev_fork, "rmcv_extract_color: waiting for the pixel kernel"));
-        c->marks[3] = now_us();
-        HIPCHK(c, hipMemcpyAsync(binary_out, b.binary, (size_t)w * h, hipMemcpyDeviceToHost, c->side), "D2H binary");
-        c->marks[4] = now_us();
-        WAITCHK(c, wait_stream(c, c->side, "rmcv_extract_color: waiting for the byte image's download"));
-    } else c->marks[3] = c->marks[4] = c->marks[2];
-    c->marks[5] = now_us();
-    c->last_what = fused_ahead ? "k_binary, k_contours (fused), k_pack_contours + export" : "k_binary, k_contours, k_pack_contours, k_export";
-    WAITCHK(c, wait_stream(c, s, "rmcv_extract_color: waiting for the frame's kernels"));
-    c->marks[6] = now_us();
-    const int32_t nc = c->h_hdr[0], total = c->h_hdr[1], st = c->h_hdr[2];
-    if (n_contours) *n_contours = nc;
-    if (n_points) *n_points = total;
-    if (st & (RMCV_FRAME_OVF_CONTOURS | RMCV_FRAME_OVF_POINTS)) return fail(c, RMCV_ERR_CAPACITY, "context limits exceeded (max_contours/max_points)");
-    if (nc > SF_OFFS_WIN) HIPCHK(c, hipMemcpy(c->h_offs + SF_OFFS_WIN + 1, c->pack_offs + SF_OFFS_WIN + 1, (size_t)(nc - SF_OFFS_WIN) * 4, hipMemcpyDeviceToHost), "D2H offs");
-    if (total > SF_PTS_WIN) HIPCHK(c, hipMemcpy(c->h_pts + SF_PTS_WIN, c->pack_pts + SF_PTS_WIN, (size_t)(total - SF_PTS_WIN) * sizeof(rmcv_point), hipMemcpyDeviceToHost), "D2H pts");
-    c->res_nc = nc; // the device holds these contours (discovery order + the fit work list) and h_pts / h_offs their CSR
-    c->res_total = total;
-    c->ahead_lb = ahead_lb;
-    c->ahead_ar = ahead_ar;
-    if (nc > contours_cap || total > pts_cap) return fail(c, RMCV_ERR_CAPACITY, "output capacity exceeded");
-    if (offs_out) memcpy(offs_out, c->h_offs, (size_t)(nc + 1) * 4);
-    if (pts_out && total) memcpy(pts_out, c->h_pts, (size_t)total * sizeof(rmcv_point));
-    c->marks[7] = now_us();
-    if (binary_out) { // what the runtime's copies cost this frame (see rmcv_ctx::image_export)
-        const double up_us = c->marks[3] - c->marks[1] + c->test_slow_us, img_us = c->marks[4] - c->marks[3] + c->test_slow_us;
-        // (the upload moves what the frame holds: 3 B/px of BGR, 1 or 2 B/px of a mosaic -- RMCV_OPT_INPUT_FORMAT, _SAMPLE_BITS)
-        const double frame_bytes = (double)geom_pixel_bytes(c->geom) * w * h, image_bytes = (double)w * h;
-        if (c->upload_now == 0) {
-            c->slow_upload = up_us > frame_bytes / 45e3 + 100.0 ? c->slow_upload + 1 : 0; // (45 GB/s + the pixel kernel + the waits' slack)
-            if (c->frame_upload == 3 && c->slow_upload >= 3) { c->hold_upload = 512; c->slow_upload = 0; }
-        } else if (c->hold_upload > 0) c->hold_upload--;
-        if (c->image_now == 0) {
-            c->slow_image = img_us > image_bytes / 40e3 + 60.0 ? c->slow_image + 1 : 0;
-            if (c->image_export == 2 && c->slow_image >= 3) { c->hold_image = 512; c->slow_image = 0; }
-        } else if (c->hold_image > 0) c->hold_image--;
-    }
-    return RMCV_OK;
-}
-
-// load host CSR contours (findContours order) into frame slot 0 (stored in discovery order = reversed)
-static int load_contours(rmcv_ctx* c, const rmcv_point* pts, const int32_t* offs, int n)
-{
-    int rc = rmcv_batch_sync(c); // frame slot 0 may belong to a batch in flight on a caller stream
-    if (rc) return rc;
-    resident_none(c);
-    if (n < 0 || n > c->lim.max_contours) return fail(c, RMCV_ERR_CAPACITY, "too many contours for this context");
-    const int total = n ? offs[n] : 0;
-    if (total > c->lim.max_points) return fail(c, RMCV_ERR_CAPACITY, "too many points for this context");
-    std::vector<int32_t> cs(n > 0 ? n : 1), cl(n > 0 ? n : 1), el;
-    for (int i = 0; i < n; i++) {
-        if (offs[i + 1] < offs[i]) return fail(c, RMCV_ERR_BAD_ARG, "offs not monotone");
-        cs[n - 1 - i] = offs[i];
-        cl[n - 1 - i] = offs[i + 1] - offs[i];
-    }
-    for (int k = 0; k < n; k++)
-        if (cl[k] >= 6) el.push_back(k); // the fit stage's work list (what k_contours writes in the batch path)
-    const int32_t ne = (int32_t)el.size();
-    if (c->geom.n_frames < 1) c->geom.n_frames = 1;
-    const Bufs& b = c->bufs;
-    int32_t z = 0;
-    if (total) HIPCHK(c, hipMemcpy(b.points, pts, (size_t)total * sizeof(rmcv_point), hipMemcpyHostToDevice), "H2D points");
-    if (n) {
-        HIPCHK(c, hipMemcpy(b.cont_start, cs.data(), (size_t)n * 4, hipMemcpyHostToDevice), "H2D");
-        HIPCHK(c, hipMemcpy(b.cont_len, cl.data(), (size_t)n * 4, hipMemcpyHostToDevice), "H2D");
-    }
-    HIPCHK(c, hipMemcpy(b.n_contours, &n, 4, hipMemcpyHostToDevice), "H2D");
-    HIPCHK(c, hipMemcpy(b.n_points, &total, 4, hipMemcpyHostToDevice), "H2D");
-    if (n) HIPCHK(c, hipMemset(b.slot_kind, 0, (size_t)n * 4), "memset slot_kind");
-    if (ne) HIPCHK(c, hipMemcpy(b.elig, el.data(), (size_t)ne * 4, hipMemcpyHostToDevice), "H2D elig");
-    HIPCHK(c, hipMemcpy(b.n_elig, &ne, 4, hipMemcpyHostToDevice), "H2D");
-    HIPCHK(c, hipMemcpy(b.status, &z, 4, hipMemcpyHostToDevice), "H2D");
-    return RMCV_OK;
-}
-
-int rmcv_filter_lightblobs(rmcv_ctx* c, const rmcv_point* pts, const int32_t* offs, int n_contours, float tilt_max,
-                           float ratio_lo, float ratio_hi, double area_lo, double area_hi, int enemy,
-                           rmcv_lightblob* blobs_out, int blobs_cap, int32_t* n_blobs, int32_t* blob_src,
-                           int32_t* neg_idx_out, int32_t* n_neg)
-{
-    if (!c || n_contours < 0 || (n_contours > 0 && (!pts || !offs))) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = ensure_staging(c);
-    if (rc) return rc;
-    // handed exactly what rmcv_extract_color returned last?  then the contours (and the fit work list) are already on the device
-    const bool resident = c->res_nc >= 0 && n_contours == c->res_nc &&
-                          (n_contours == 0 || (offs[n_contours] == c->res_total && memcmp(offs, c->h_offs, (size_t)(n_contours + 1) * 4) == 0 &&
-                                               memcmp(pts, c->h_pts, (size_t)c->res_total * sizeof(rmcv_point)) == 0));
-    if (!resident) {
-        rc = load_contours(c, pts, offs, n_contours);
-        if (rc) return rc;
-    }
-    c->res_nb = -1;
-    const rmcv_ctx::LbParams q = {tilt_max, ratio_lo, ratio_hi, area_lo, area_hi, enemy};
-    const bool ran_ahead = resident && c->ahead_lb && memcmp(&q, &c->last_lb, sizeof(q)) == 0; // extract_color did it already
-    c->last_lb = q;
-    c->last_lb_valid = true;
-    if (!ran_ahead) {
-        c->ahead_ar = false; // the armours run ahead (if any) belong to other blobs
-        if (c->geom.n_frames < 1) c->geom.n_frames = 1;
-        if ((rc = enqueue_blobs(c, q))) return rc;
-        WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
-    }
-    c->ahead_lb = false;
-    return finish_blobs(c, blobs_out, blobs_cap, n_blobs, blob_src, neg_idx_out, n_neg);
-}
-
-int rmcv_filter_armours(rmcv_ctx* c, const rmcv_lightblob* blobs, int n_blobs, float angle_diff_max, float shear_max,
-                        float length_ratio_max, int enemy, rmcv_armour* armours_out, int armours_cap, int32_t* n_armours)
-{
-    if (!c || (n_blobs > 0 && !blobs) || n_blobs < 0) return RMCV_ERR_BAD_ARG;
-    if (n_blobs > c->lim.max_blobs) return fail(c, RMCV_ERR_CAPACITY, "too many blobs for this context");
-    hipSetDevice(c->device);
-    int rc = ensure_staging(c);
-    if (rc) return rc;
-    const Bufs& b = c->bufs;
-    hipStream_t s = c->stream;
-    // handed exactly the positive list rmcv_filter_lightblobs returned last?  then it is already on the device
-    const bool resident = c->res_nb >= 0 && n_blobs == c->res_nb &&
-                          (n_blobs == 0 || memcmp(blobs, c->h_blobs, (size_t)n_blobs * sizeof(rmcv_lightblob)) == 0);
-    if (!resident) {
-        rc = rmcv_batch_sync(c);
-        if (rc) return rc;
-        resident_none(c);
-        int32_t z = 0;
-        if (n_blobs) HIPCHK(c, hipMemcpy(b.blobs, blobs, (size_t)n_blobs * sizeof(rmcv_lightblob), hipMemcpyHostToDevice), "H2D blobs");
-        HIPCHK(c, hipMemcpy(b.n_blobs, &n_blobs, 4, hipMemcpyHostToDevice), "H2D");
-        HIPCHK(c, hipMemcpy(b.status, &z, 4, hipMemcpyHostToDevice), "H2D");
-    }
-    const rmcv_ctx::ArParams q = {angle_diff_max, shear_max, length_ratio_max, enemy};
-    const bool ran_ahead = resident && c->ahead_ar && memcmp(&q, &c->last_ar, sizeof(q)) == 0;
-    c->last_ar = q;
-    c->last_ar_valid = true;
-    c->ahead_ar = false;
-    if (!ran_ahead) {
-        if ((rc = enqueue_armours(c, q))) return rc;
-        WAITCHK(c, wait_stream(c, s, "waiting for the stream"));
-    }
-    return finish_armours(c, armours_out, armours_cap, n_armours);
-}
-
-int rmcv_fit_ellipse(rmcv_ctx* c, const rmcv_point* pts, int n, rmcv_rrect* out)
-{
-    if (!c || !pts || !out || n < 5) return RMCV_ERR_BAD_ARG;
-    // run the blob stage on one contour with every gate open; the fitted ellipse is kept next to each blob
-    int32_t offs[2] = {0, n};
-    hipSetDevice(c->device);
-    int rc = load_contours(c, pts, offs, 1);
-    if (rc) return rc;
-    rmcv_params p;
-    rmcv_default_params(&p);
-    p.tilt_max = 1e30f;
-    p.ratio_lo = -1e30f;
-    p.ratio_hi = 1e30f;
-    p.area_lo = -1.0;
-    p.area_hi = 1e300;
-    Geom g1 = c->geom;
-    g1.n_frames = 1;
-    g1.keys = 0;
-    HIPCHK(c, launch_blobs(g1, c->bufs, c->lim, p, c->stream), "k_blobs");
-    WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
-    int32_t nb = 0, nn = 0;
-    HIPCHK(c, hipMemcpy(&nb, c->bufs.n_blobs, 4, hipMemcpyDeviceToHost), "D2H");
-    HIPCHK(c, hipMemcpy(&nn, c->bufs.n_neg, 4, hipMemcpyDeviceToHost), "D2H");
-    if (nb != 1) return fail(c, RMCV_ERR_BAD_ARG, n < 6 ? "contour has fewer than 6 points" : "ellipse fit produced NaN");
-    HIPCHK(c, hipMemcpy(out, c->bufs.ellipses, sizeof(rmcv_rrect), hipMemcpyDeviceToHost), "D2H ellipse");
-    return RMCV_OK;
-}
-
 // ---- armour pose ------------------------------------------------------------------------------------------
 void rmcv_default_pnp_config(rmcv_pnp_config* c)
 {
@@ -2013,9 +1211,7 @@ static int match_one(rmcv_ctx* c, const rmcv_point* pts, int n, const rmcv_legac
     if (rc) return rc;
     rmcv_params p;
     rmcv_default_params(&p);
-    Geom g1 = c->geom;
-    g1.n_frames = 1;
-    g1.keys = 0;
+    const Geom g1 = one_frame_geom(c);
     HIPCHK(c, launch_match(g1, c->bufs, c->lim, p, lp, mode, false, false, c->stream), "k_match");
     WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
     int32_t nb = 0, st = 0;

@@ -1,5 +1,5 @@
 """The per-frame chain returns its lists through pinned staging buffers.  By default the last kernel of the chain stores them there
-itself (ExportArgs / k_export, rmcv_host.hip); RMCV_EXPORT=0 brings back the row of small device-to-host copies of round 2.  Both
+itself (ExportArgs / k_export, rmcv_frame.hip); RMCV_EXPORT=0 brings back the row of small device-to-host copies of round 2.  Both
 must hand the caller the same bytes (plain, stress and a dense frame whose lists exceed the copy windows)."""
 import os
 import subprocess

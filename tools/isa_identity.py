@@ -5,7 +5,10 @@ source path).  Symbols only one side has are listed, not compared.  No GPU neede
 
   for u in $(sed -n 's/^SRCS *:= *//p' rmcv_amd/csrc/Makefile | sed 's/\.hip//g'); do        (every unit of the Makefile's SRCS)
     (cd DIR && hipcc -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math --save-temps -c ROOT/rmcv_amd/csrc/$u.hip -o $u.o); done
-  python tools/isa_identity.py BEFORE_DIR AFTER_DIR [unit ...]        exit status 1 if a shared symbol differs"""
+  python tools/isa_identity.py BEFORE_DIR AFTER_DIR [unit ...]        exit status 1 if a shared symbol differs
+
+A kernel that has moved to another unit (k_image_export: rmcv_host -> rmcv_frame) is compared by concatenating the two units' .s files
+of the side that split them under the name of the unit that held it before."""
 import glob
 import os
 import re
