@@ -773,6 +773,66 @@ int  rmcv_tracker_put(rmcv_tracker* trk, int stream, const rmcv_track* tracks, i
 int  rmcv_aim_step_host(const rmcv_aim_config* cfg, double tick_frequency, const rmcv_track* tracks, int n, const rmcv_aim_input* input,
                         int64_t now, rmcv_aim* out);
 
+/* ---- per-stream gimbal attitude: packet in, aim out, host only submits ------------------------------------------------
+ * Every frame of the reference's process loop carries what the MCU link sent for it (serial_package, executable/main.cpp:24-28): the enemy
+ * colour and the gimbal's rotation.  process_function turns the rotation into h_base2gripper (main.cpp:170) and puts every armour's
+ * position into the base frame with it (main.cpp:189); the tracking thread filters those.  With attitude on, an ATTITUDE STEP (k_attitude,
+ * one lane per stream) runs in front of a tracked batch and writes, per stream f, from the stream's rmcv_attitude or its 24-byte packet:
+ *  1. with a packet (main.cpp:120-143): valid iff pkt[0] == 0x38 and pkt[23] == rmcv_crc8(pkt, 23).  A valid one sets attitude[f] -- yaw,
+ *     pitch, roll the little-endian f32 at bytes 3, 11, 15, each ((double)deg * 3.141592653589793) / 180.0 -- and, where the tracker's camp
+ *     table is on (rmcv_tracker_set_camps), camps[f] = (pkt[1] & 1) ? RMCV_CAMP_RED : RMCV_CAMP_BLUE.  A rejected one leaves both as they
+ *     were (the reference's `continue`: the last good package stays in use) and adds one to packet_errors[f];
+ *  2. B = rmcv_homogeneous(rmcv_euler_to_matrix(attitude[f]), 0) -> base2gripper[f] of the batch's context (skipped without pose tables,
+ *     rmcv_pnp_load).  The matrices are the BATCH's: the table rmcv_batch_set_base2gripper writes is not touched and is in force again
+ *     from the context's next binding of frames (or the next rmcv_batch_set_base2gripper) on;
+ *  3. world2camera[f] = rmcv_rigid_inverse(B x gripper2camera), the 4x4 product's entries ((r0 c0 + r1 c1) + r2 c2) + r3 c3; motor_angle[f]
+ *     stays (RMCV_ATT_MOTOR_KEEP) or becomes attitude[f].pitch (RMCV_ATT_MOTOR_PITCH);
+ *  4. a valid packet with a non-finite angle runs through and comes out NaN (every NaN that leaves is the quiet NaN), as in the aim step.
+ * The step is enqueued on the batch's pixel stream: in front of k_frame_keys / k_window_origins (the camps it may write are read there) and
+ * behind an event wait for the tracker's previous step (the aim inputs it writes are read by that step's k_aim) -- with attitude on that
+ * wait is made for whole-frame trackers (win_w == 0) too, which otherwise have none.  Nothing blocks: host_blocking_calls stays 0.
+ * Every byte written equals tests/attitude_ref.c. */
+typedef struct { double roll, pitch, yaw; } rmcv_attitude;          /* radians = rm::euler<double>{x, y, z}; 24 bytes */
+#define RMCV_ATT_MOTOR_KEEP 0
+#define RMCV_ATT_MOTOR_PITCH 1
+typedef struct { double gripper2camera[16]; int32_t motor_angle_mode; int32_t reserved; } rmcv_attitude_config;   /* 136 bytes */
+#define RMCV_SERIAL_PACKET_BYTES 24
+/* host functions (no device; the source the kernel is compiled from).  R = (Rz(yaw) . Ry(pitch)) . Rx(roll), row-major, every entry
+ * ((a0 b0 + a1 b1) + a2 b2) with pinned sin / cos (rm::euler<double>::to_matrix, include/core.h:66-84) */
+int     rmcv_euler_to_matrix(const rmcv_attitude* a, double R[9]);
+/* rm::utils::homogeneous (src/core.cpp:406-416): R and t in an identity 4x4 */
+int     rmcv_homogeneous(const double R[9], const double t[3] /* NULL: zeros */, double H[16]);
+/* rm::lookup_CRC (hardware/src/serialport.cpp:9-18): polynomial 0x31, MSB first, init 0; n <= 0 or data NULL: 0 */
+uint8_t rmcv_crc8(const uint8_t* data, int n);
+int     rmcv_serial_decode(const uint8_t pkt[24], int32_t* camp, rmcv_attitude* att);   /* 1 valid, 0 rejected (nothing written), <0 bad arg */
+/* the inverse, for replay hosts and tests: header, bit 0 of byte 1 (camp RMCV_CAMP_RED: 1, RMCV_CAMP_BLUE: 0; anything else is
+ * RMCV_ERR_BAD_ARG), the three floats, the CRC; every other byte 0 */
+int     rmcv_serial_encode(int32_t camp, float yaw_deg, float pitch_deg, float roll_deg, uint8_t pkt[24]);
+/* the attitude step for ONE stream on the CPU.  pkt, camp nullable (no packet; camp table off); base2gripper nullable (no pose tables).
+ * RMCV_ERR_BAD_ARG: a null pointer elsewhere, or a config rmcv_tracker_set_attitude refuses */
+int     rmcv_attitude_step_host(const rmcv_attitude_config* cfg, const uint8_t* pkt, rmcv_attitude* att, int32_t* camp,
+                                int32_t* packet_errors, double base2gripper[16], rmcv_aim_input* input);
+void rmcv_default_attitude_config(rmcv_attitude_config* c);          /* gripper2camera of rmcv_default_pnp_config, RMCV_ATT_MOTOR_KEEP */
+/* attitude on (cfg) or off (NULL: no kernel is launched; the tables stay as they are).  Waits for the step in flight; allocates the
+ * attitude tables (zero attitudes, zero packet_errors) and the aim tables on first use.  RMCV_ERR_BAD_ARG with a message: an entry of the
+ * matrix not finite, motor_angle_mode out of range. */
+int  rmcv_tracker_set_attitude(rmcv_tracker* trk, const rmcv_attitude_config* cfg);
+/* n_streams attitudes, copied (NULL: zeros); packet_errors are left alone.  Waits for the step in flight. */
+int  rmcv_tracker_set_attitudes(rmcv_tracker* trk, const rmcv_attitude* attitudes);
+/* the first min(cap, n_streams) attitudes and packet_errors (either pointer may be NULL); synchronous.  Zeros before first use. */
+int  rmcv_tracker_get_attitudes(rmcv_tracker* trk, rmcv_attitude* out, int32_t* packet_errors, int cap);
+/* device view of the attitudes (n_streams rmcv_attitude): a device-side producer may write them on its own stream.  Owned by the tracker. */
+int  rmcv_tracker_device_attitudes(rmcv_tracker* trk, void** d_attitudes);
+/* the first min(cap, n_streams) aim inputs as the device holds them; synchronous.  The defaults before first use. */
+int  rmcv_tracker_get_aim_inputs(rmcv_tracker* trk, rmcv_aim_input* out, int cap);
+/* the first n_frames matrices of the table the bound batch's RMCV_STAGE_POSE reads (the attitude step's, or rmcv_batch_set_base2gripper's);
+ * synchronous.  RMCV_ERR_BAD_ARG without rmcv_pnp_load; RMCV_ERR_CAPACITY beyond max_frames. */
+int  rmcv_batch_get_base2gripper(rmcv_ctx* ctx, double* mats, int n_frames);
+/* context path: enqueue the attitude step for the bound batch on `hip_stream` (NULL: the context's stream), in front of rmcv_batch_run.
+ * d_packets: n_streams x 24 bytes in DEVICE memory, borrowed until the step has run, or NULL.  Never synchronises.  RMCV_ERR_BAD_ARG with
+ * a message, before anything is enqueued: attitude off, no frames bound, n_frames != n_streams, a tracker on another device. */
+int  rmcv_batch_attitude(rmcv_ctx* ctx, rmcv_tracker* trk, const void* d_packets, void* hip_stream);
+
 /* ---- pipelined batches: the process loop behind the ABI ------------------------------------------------------------------------
  * The reference's process_function is a `while (1)` that takes the newest camera frame, runs the three detection calls and hands
  * the armours on (executable/main.cpp:163-209).  Its batch form on one MI355X: `depth` batches in flight, each in a context of its
@@ -917,6 +977,15 @@ int  rmcv_pipeline_submit_camps(rmcv_pipeline* pl, const void* d_frames, int n_f
  * config's, stages without RMCV_STAGE_ARMOURS, a tracker on another device. */
 int  rmcv_pipeline_submit_tracked(rmcv_pipeline* pl, rmcv_tracker* trk, const void* d_frames, int n_frames, int frame_w, int frame_h, int stride,
                                   int64_t frame_pitch, const rmcv_params* p, int stages, int64_t timestamp, uint64_t* ticket);
+/* rmcv_pipeline_submit_tracked + this batch's serial packets: d_packets is n_frames x RMCV_SERIAL_PACKET_BYTES in DEVICE memory, borrowed
+ * like the frames, or NULL.  On a tracker with attitude on (rmcv_tracker_set_attitude) the attitude step (above) is enqueued on the batch's
+ * pixel stream, behind the event wait for the tracker's previous step and in front of k_frame_keys / k_window_origins;
+ * rmcv_pipeline_submit_tracked on such a tracker is this call with d_packets == NULL.  Packet in, aim out, the host only submits.
+ * RMCV_ERR_BAD_ARG, with a message and before anything is enqueued: what rmcv_pipeline_submit_tracked refuses; attitude off and d_packets
+ * given. */
+int  rmcv_pipeline_submit_tracked_serial(rmcv_pipeline* pl, rmcv_tracker* trk, const void* d_frames, int n_frames, int frame_w, int frame_h,
+                                         int stride, int64_t frame_pitch, const void* d_packets, const rmcv_params* p, int stages,
+                                         int64_t timestamp, uint64_t* ticket);
 /* block until the batch is through (its record complete in HBM and, with host_results, on the host) */
 int  rmcv_pipeline_wait(rmcv_pipeline* pl, uint64_t ticket);
 /* wait + hand the batch's armours over, frame-major, in submission order of the frames: frame_offs (nullable) has n_frames + 1

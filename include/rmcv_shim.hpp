@@ -404,6 +404,41 @@ RMCV_SHIM_LINKAGE double SolveGEA(cv::InputArray translationVector, cv::OutputAr
 }
 #endif
 
+// ---- rm::utils::homogeneous (include/core.h:188; body src/core.cpp:406-416) over rmcv_homogeneous: R and t in an identity 4x4, an empty
+// cv::Mat for anything but a 3x3 and a 3x1.  What executable/main.cpp:170 builds h_base2gripper with; the rotation's own matrix is
+// rmcv_euler_to_matrix (rm::euler<T>::to_matrix is a member template of the reference's core.h and stays there).  The default translation
+// lives on the reference's declaration.
+// (Guarded: only where the cv:: headers in use have a CV_64F cv::Mat with rows of doubles -- real OpenCV, or a stand-in that says so.)
+#if defined(CV_VERSION) || defined(RMCV_CV_HAS_MAT64)
+namespace utils {
+RMCV_SHIM_LINKAGE cv::Mat homogeneous(const cv::Mat& rotation, const cv::Mat& translation)
+{
+    if (rotation.rows != 3 || rotation.cols != 3 || translation.rows != 3 || translation.cols != 1) return {};
+    double R[9], t[3], H[16];
+    for (int i = 0; i < 3; i++) {
+        for (int j = 0; j < 3; j++) R[3 * i + j] = rotation.ptr<double>(i)[j];
+        t[i] = translation.ptr<double>(i)[0];
+    }
+    if (rmcv_homogeneous(R, t, H) != RMCV_OK) return {};
+    cv::Mat out(4, 4, CV_64F);
+    for (int i = 0; i < 4; i++)
+        for (int j = 0; j < 4; j++) out.ptr<double>(i)[j] = H[4 * i + j];
+    return out;
+}
+} // namespace utils
+#endif
+
+// ---- rm::lookup_CRC (hardware/include/serialport.h:49; body hardware/src/serialport.cpp:9-18) over rmcv_crc8, which works the polynomial
+// of the reference's table rm::CRC8 (0x31, MSB first, init 0) bit by bit.  The table argument -- rm::CRC8 by default, on the reference's
+// declaration -- is accepted and not read.
+// (Guarded: only behind the reference's serialport.h.)
+#if defined(RMCV_SERIALPORT_H)
+RMCV_SHIM_LINKAGE unsigned char lookup_CRC(unsigned char* data, unsigned char dataLength, const unsigned char* /* crcTable */)
+{
+    return rmcv_crc8(data, dataLength);
+}
+#endif
+
 using LightBlob = lightblob; // pre-2024 API names used by the north star
 using Armour = armour;
 

@@ -29,6 +29,11 @@ AIM = np.dtype([("track", "<i4"), ("identity", "<i4"), ("lost_count", "<i4"), ("
                 ("flight_time", "<f8"), ("distance", "<f8"), ("point", "<f8", (3,))])  # rmcv_aim
 AIM_INPUT = np.dtype([("world2camera", "<f8", (4, 4)), ("motor_angle", "<f8")])  # rmcv_aim_input
 assert AIM.itemsize == 72 and AIM_INPUT.itemsize == 136
+ATTITUDE = np.dtype([("roll", "<f8"), ("pitch", "<f8"), ("yaw", "<f8")])  # rmcv_attitude: radians = rm::euler<double>{x, y, z}
+ATTITUDE_CONFIG = np.dtype([("gripper2camera", "<f8", (4, 4)), ("motor_angle_mode", "<i4"), ("reserved", "<i4")])  # rmcv_attitude_config
+assert ATTITUDE.itemsize == 24 and ATTITUDE_CONFIG.itemsize == 136
+SERIAL_PACKET_BYTES = 24
+ATT_MOTOR_KEEP, ATT_MOTOR_PITCH = 0, 1
 
 OK, ERR_BAD_ARG, ERR_CAPACITY, ERR_NOMEM, ERR_HIP, ERR_NO_DEVICE, ERR_RCCL, ERR_TIMEOUT = 0, -1, -2, -3, -4, -5, -6, -7
 COMM_ID_BYTES = 128
@@ -91,6 +96,9 @@ EXPORTS = [
     "rmcv_aim_step_host",
     "rmcv_frame_key", "rmcv_batch_set_frame_camps", "rmcv_batch_set_device_frame_camps", "rmcv_batch_get_frame_keys", "rmcv_pipeline_submit_camps",
     "rmcv_tracker_set_camps", "rmcv_tracker_device_camps",
+    "rmcv_euler_to_matrix", "rmcv_homogeneous", "rmcv_crc8", "rmcv_serial_decode", "rmcv_serial_encode", "rmcv_attitude_step_host", "rmcv_default_attitude_config",
+    "rmcv_tracker_set_attitude", "rmcv_tracker_set_attitudes", "rmcv_tracker_get_attitudes", "rmcv_tracker_device_attitudes", "rmcv_tracker_get_aim_inputs",
+    "rmcv_batch_get_base2gripper", "rmcv_batch_attitude", "rmcv_pipeline_submit_tracked_serial",
 ]
 
 
@@ -255,6 +263,25 @@ def load(path):
                                                  C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.rmcv_tracker_set_camps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.rmcv_tracker_device_camps.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "rmcv_attitude_step_host"):  # (builds from before the per-stream gimbal attitude stay loadable for A/B runs)
+        L.rmcv_euler_to_matrix.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_homogeneous.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_crc8.restype = C.c_uint8
+        L.rmcv_crc8.argtypes = [C.c_void_p, C.c_int]
+        L.rmcv_serial_decode.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_serial_encode.argtypes = [C.c_int32, C.c_float, C.c_float, C.c_float, C.c_void_p]
+        L.rmcv_attitude_step_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_default_attitude_config.restype = None
+        L.rmcv_default_attitude_config.argtypes = [C.c_void_p]
+        L.rmcv_tracker_set_attitude.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_set_attitudes.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_get_attitudes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_tracker_device_attitudes.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_get_aim_inputs.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_batch_get_base2gripper.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_batch_attitude.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_pipeline_submit_tracked_serial.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
+                                                          C.c_int, C.c_int64, C.c_void_p]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L
@@ -384,6 +411,62 @@ def rigid_inverse(m):
     if rc:
         raise RmcvError(rc, "rmcv_rigid_inverse")
     return out
+
+
+def _attitude(attitude):
+    """(roll, pitch, yaw) in radians, or a 1-element ATTITUDE array -> ATTITUDE[1]"""
+    if isinstance(attitude, np.ndarray) and attitude.dtype == ATTITUDE:
+        return np.ascontiguousarray(attitude).reshape(1).copy()
+    a = np.zeros(1, ATTITUDE)
+    a[0] = tuple(float(v) for v in attitude)
+    return a
+
+
+def euler_to_matrix(attitude):
+    """rm::euler<double>::to_matrix (rmcv_euler_to_matrix: host-side): (roll, pitch, yaw) radians -> R = (Rz(yaw) Ry(pitch)) Rx(roll), (3, 3)"""
+    a, out = _attitude(attitude), np.zeros((3, 3))
+    rc = lib().rmcv_euler_to_matrix(ptr(a), ptr(out))
+    if rc:
+        raise RmcvError(rc, "rmcv_euler_to_matrix")
+    return out
+
+
+def homogeneous(rotation, translation=None):
+    """rm::utils::homogeneous (rmcv_homogeneous: host-side): R (3, 3) and t (3,) | None: zeros, in an identity (4, 4)"""
+    r, out = np.ascontiguousarray(rotation, np.float64).reshape(3, 3), np.zeros((4, 4))
+    t = None if translation is None else _tvec(translation)
+    rc = lib().rmcv_homogeneous(ptr(r), ptr(t), ptr(out))
+    if rc:
+        raise RmcvError(rc, "rmcv_homogeneous")
+    return out
+
+
+def crc8(data):
+    """rm::lookup_CRC (rmcv_crc8: host-side): polynomial 0x31, MSB first, init 0"""
+    b = np.frombuffer(bytes(data), np.uint8)
+    return int(lib().rmcv_crc8(ptr(b) if len(b) else None, len(b)))
+
+
+def serial_decode(packet):
+    """the packet check and decode of executable/main.cpp:120-143 (rmcv_serial_decode: host-side): 24 bytes ->
+    (camp, ATTITUDE record in radians), or None for a rejected packet"""
+    b = np.frombuffer(bytes(packet), np.uint8)
+    if len(b) != SERIAL_PACKET_BYTES:
+        raise RmcvError(ERR_BAD_ARG, "a serial packet is %d bytes" % SERIAL_PACKET_BYTES)
+    camp, a = C.c_int32(0), np.zeros(1, ATTITUDE)
+    rc = lib().rmcv_serial_decode(ptr(b), C.byref(camp), ptr(a))
+    if rc < 0:
+        raise RmcvError(rc, "rmcv_serial_decode")
+    return (camp.value, a[0]) if rc == 1 else None
+
+
+def serial_encode(camp, yaw_deg, pitch_deg, roll_deg):
+    """the packet serial_decode accepts (rmcv_serial_encode: for replay hosts and tests): camp CAMP_RED | CAMP_BLUE, degrees as f32 -> bytes"""
+    out = np.zeros(SERIAL_PACKET_BYTES, np.uint8)
+    rc = lib().rmcv_serial_encode(C.c_int32(int(camp)), C.c_float(yaw_deg), C.c_float(pitch_deg), C.c_float(roll_deg), ptr(out))
+    if rc:
+        raise RmcvError(rc, "rmcv_serial_encode: camp must be CAMP_RED or CAMP_BLUE")
+    return out.tobytes()
 
 
 def default_pnp_config():

@@ -238,6 +238,19 @@ class Context:
         m = np.ascontiguousarray(mats, np.float64).reshape(-1, 16)
         self._chk(lib().rmcv_batch_set_base2gripper(self._h, ptr(m), len(m)))
 
+    def base2gripper(self):
+        """(n_frames, 4, 4): the matrices the bound batch's STAGE_POSE reads -- the attitude step's (Context.attitude) or set_base2gripper's;
+        synchronous"""
+        out = np.zeros((self.shape[0], 4, 4))
+        self._chk(lib().rmcv_batch_get_base2gripper(self._h, ptr(out), len(out)))
+        return out
+
+    def attitude(self, tracker, packets=None, stream=None):
+        """the attitude step of a tracker with set_attitude, enqueued in front of run() for the bound batch (rmcv_batch_attitude): frame f is
+        stream f.  packets: device pointer to n_streams x 24 bytes (keep them alive until the step has run) | None: the tracker's attitude
+        table as it stands.  Asynchronous; never synchronises."""
+        self._chk(lib().rmcv_batch_attitude(self._h, tracker._h, C.c_void_p(int(packets)) if packets else None, C.c_void_p(stream or 0)))
+
     def poses(self):
         """(rvecs, tvecs, positions) of all armours of the batch in the order of armours()"""
         cap = self.shape[0] * self.limits.max_armours

@@ -16,6 +16,7 @@
 
 #include "rmcv_internal.h"
 #include "device_aim.h"
+#include "device_attitude.h"
 
 namespace rmcv {
 
@@ -113,12 +114,7 @@ int rmcv_rigid_inverse(const double m[16], double out[16])
 {
     if (!m || !out) return RMCV_ERR_BAD_ARG;
     double r[16];
-    for (int i = 0; i < 3; i++) {
-        for (int j = 0; j < 3; j++) r[i * 4 + j] = m[j * 4 + i];
-        r[i * 4 + 3] = -((m[0 * 4 + i] * m[3] + m[1 * 4 + i] * m[7]) + m[2 * 4 + i] * m[11]);
-    }
-    r[12] = r[13] = r[14] = 0.0;
-    r[15] = 1.0;
+    att_rigid_inverse(m, r); // (the attitude step's: device_attitude.h)
     memcpy(out, r, sizeof(r));
     return RMCV_OK;
 }

@@ -609,6 +609,7 @@ int rmcv_batch_upload(rmcv_ctx* c, const uint8_t* frames, int n_frames, int w, i
     }
     WAITCHK(c, wait_stream(c, c->stream, "H2D frames"));
     c->bufs.frames = c->own_frames;
+    c->bufs.pose_base2gripper = c->bufs.base2gripper; // (an attitude step's matrices were its batch's)
     c->last_stages = 0; // a new batch: nothing of it has run
     return RMCV_OK;
 }
@@ -624,6 +625,7 @@ int rmcv_batch_set_device_frames(rmcv_ctx* c, const void* d_frames, int n_frames
     rc = set_geom(c, n_frames, w, h, stride, frame_pitch);
     if (rc) return rc;
     c->bufs.frames = (const uint8_t*)d_frames;
+    c->bufs.pose_base2gripper = c->bufs.base2gripper;
     c->last_stages = 0;
     return RMCV_OK;
 }
@@ -648,6 +650,7 @@ int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int 
     c->geom.keys = d_camps != nullptr;              // (... and the effective keys)
     c->bufs.key_camps = (const int32_t*)d_camps;
     c->bufs.key_lbs = d_camps ? (const int32_t*)d_lower_bounds : nullptr;
+    c->bufs.pose_base2gripper = c->bufs.base2gripper;
     c->last_stages = 0;
     return RMCV_OK;
 }
@@ -1058,8 +1061,10 @@ int rmcv_pnp_load(rmcv_ctx* c, const rmcv_pnp_config* cfg)
     if (!b.pnp_cfg) {
         hipError_t e = dalloc(c, &b.pnp_cfg, 1);
         if (e == hipSuccess) e = dalloc(c, &b.base2gripper, (size_t)c->lim.max_frames * 16);
+        if (e == hipSuccess) e = dalloc(c, &b.att_base2gripper, (size_t)c->lim.max_frames * 16);
         if (e == hipSuccess) e = dalloc(c, &b.poses, (size_t)c->lim.max_frames * c->lim.max_armours * 9);
         if (e != hipSuccess) { b.pnp_cfg = nullptr; return fail(c, RMCV_ERR_NOMEM, "pnp buffers", e); }
+        b.pose_base2gripper = b.base2gripper;
         std::vector<double> eye((size_t)c->lim.max_frames * 16, 0.0);
         for (int f = 0; f < c->lim.max_frames; f++)
             for (int k = 0; k < 4; k++) eye[(size_t)f * 16 + 5 * k] = 1.0;
@@ -1078,6 +1083,19 @@ int rmcv_batch_set_base2gripper(rmcv_ctx* c, const double* mats, int n_frames)
     int rc = rmcv_batch_sync(c);
     if (rc) return rc;
     HIPCHK(c, hipMemcpy(c->bufs.base2gripper, mats, (size_t)n_frames * 16 * sizeof(double), hipMemcpyHostToDevice), "H2D base2gripper");
+    c->bufs.pose_base2gripper = c->bufs.base2gripper;
+    return RMCV_OK;
+}
+
+int rmcv_batch_get_base2gripper(rmcv_ctx* c, double* mats, int n_frames)
+{
+    if (!c || !mats || n_frames < 1) return RMCV_ERR_BAD_ARG;
+    if (!c->bufs.pnp_cfg) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_pnp_load first");
+    if (n_frames > c->lim.max_frames) return fail(c, RMCV_ERR_CAPACITY, "more frames than the context holds");
+    hipSetDevice(c->device);
+    int rc = rmcv_batch_sync(c);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpy(mats, c->bufs.pose_base2gripper, (size_t)n_frames * 16 * sizeof(double), hipMemcpyDeviceToHost), "D2H base2gripper");
     return RMCV_OK;
 }
 
@@ -1129,7 +1147,9 @@ int rmcv_locate_armours(rmcv_ctx* c, const rmcv_armour* armours, int n, const do
     Geom g1 = c->geom;
     g1.n_frames = 1;
     g1.win = 0; // (the caller's armours, the default ROI: whatever windows the batch bound to the context has)
-    HIPCHK(c, launch_pnp(g1, c->bufs, c->lim, c->stream), "k_pnp");
+    Bufs b1 = c->bufs;
+    b1.pose_base2gripper = b1.base2gripper; // (... and the caller's matrix, whatever attitude step ran in front of that batch)
+    HIPCHK(c, launch_pnp(g1, b1, c->lim, c->stream), "k_pnp");
     WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
     std::vector<double> all((size_t)n * 9);
     HIPCHK(c, hipMemcpy(all.data(), c->bufs.poses, all.size() * sizeof(double), hipMemcpyDeviceToHost), "D2H poses");
@@ -1527,6 +1547,13 @@ int rmcv_armours_to_frame(rmcv_armour* armours, int n, int x, int y)
     return RMCV_OK;
 }
 
+int rmcv_batch_attitude(rmcv_ctx* c, rmcv_tracker* trk, const void* d_packets, void* hip_stream)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    hipSetDevice(c->device);
+    return ctx_attitude(c, trk, d_packets, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
 int rmcv_batch_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, void* hip_stream)
 {
     if (!c) return RMCV_ERR_BAD_ARG;
@@ -1567,6 +1594,32 @@ int ctx_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, int stages, hip
                            g.win ? c->bufs.win_eff : nullptr, timestamp, s), "k_track");
     if (tracker_aim_on(trk)) HIPCHK(c, launch_aim(trk, timestamp, s), "k_aim"); // the aim step reads the lists the step has just left
     HIPCHK(c, tracker_order_end(trk, s), "tracker: record the step");
+    return order_end(c, s);
+}
+
+// the attitude step in front of the bound batch's run (every check before the first enqueue); never synchronises.  It is a step of the
+// tracker's like any other: behind the previous one (whose k_aim reads the inputs this one writes), recorded as the newest (the setters'
+// and getters' wait covers it).
+int ctx_attitude(rmcv_ctx* c, rmcv_tracker* trk, const void* d_packets, hipStream_t s)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!trk) return fail(c, RMCV_ERR_BAD_ARG, "null tracker");
+    const Geom& g = c->geom;
+    const rmcv_tracker_config& tc = tracker_config(trk);
+    char msg[200];
+    if (tracker_device(trk) != c->device) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_attitude: the tracker lives on another device than the context");
+    if (!tracker_attitude_on(trk)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_attitude: attitude is off (rmcv_tracker_set_attitude)");
+    if (g.n_frames <= 0 || !c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_attitude: no frames bound");
+    if (g.n_frames != tc.n_streams) {
+        snprintf(msg, sizeof(msg), "rmcv_batch_attitude: the batch has %d frames, the tracker %d streams (frame f is the next frame of stream f)", g.n_frames, tc.n_streams);
+        return fail(c, RMCV_ERR_BAD_ARG, msg);
+    }
+    int rc;
+    if ((rc = order_begin(c, s))) return rc;
+    HIPCHK(c, tracker_order_begin(trk, s), "attitude: wait for the tracker's previous step");
+    HIPCHK(c, launch_attitude(trk, d_packets, c->bufs.pnp_cfg ? c->bufs.att_base2gripper : nullptr, s), "k_attitude");
+    if (c->bufs.pnp_cfg) c->bufs.pose_base2gripper = c->bufs.att_base2gripper;
+    HIPCHK(c, tracker_order_end(trk, s), "attitude: record the step");
     return order_end(c, s);
 }
 } // namespace rmcv

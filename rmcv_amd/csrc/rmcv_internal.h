@@ -117,8 +117,10 @@ struct Bufs {
     uint8_t* icons;        // [frame][max_armours][1200]  rectified 20x20 BGR icons
     // armour pose; allocated by rmcv_pnp_load
     rmcv_pnp_config* pnp_cfg;
-    double* base2gripper;  // [frame][16]
-    double* poses;         // [frame][max_armours][9]  rvec | tvec | world position
+    double* base2gripper;  // [frame][16]  the host's table (rmcv_batch_set_base2gripper)
+    double* att_base2gripper; // [frame][16]  the attitude step's table (k_attitude.hip): the matrices of the batch it ran in front of
+    const double* pose_base2gripper; // what k_pnp reads: att_base2gripper behind an attitude step, base2gripper from the next binding on
+    double* poses;        // [frame][max_armours][9]  rvec | tvec | world position
     // exposure-adaptive detection (RMCV_OPT_ENHANCE; k_enhance.hip): rewritten by every run with the option on, in front of the pixel pass
     uint64_t* enh_sums;    // [frame][3]   exact sums of the B, G, R bytes
     float* enh_gamma;      // [frame]      rm::AutoEnhance's gamma of the frame
@@ -342,6 +344,14 @@ int tracker_fail(rmcv_tracker* t, int code, const char* what, hipError_t e = hip
 bool tracker_aim_on(const rmcv_tracker* t);
 hipError_t launch_aim(const rmcv_tracker* t, int64_t now, hipStream_t s);
 
+// ---- per-stream gimbal attitude (k_attitude.hip) ----
+// attitude on: the attitude step of every stream in front of a tracked batch, on its pixel stream
+bool tracker_attitude_on(const rmcv_tracker* t);
+// d_packets (nullable): n_streams x 24 bytes; d_base2gripper (nullable): the batch context's [n_streams][16]
+hipError_t launch_attitude(const rmcv_tracker* t, const void* d_packets, double* d_base2gripper, hipStream_t s);
+// rmcv_batch_attitude on `s` (every check before the first enqueue; never synchronises): behind the tracker's previous step, recorded as its newest
+int ctx_attitude(rmcv_ctx* c, rmcv_tracker* trk, const void* d_packets, hipStream_t s);
+
 } // namespace rmcv
 
 // the tracker behind the ABI's handle (k_track.hip owns its lifetime; k_aim.hip the aim fields)
@@ -361,4 +371,9 @@ struct rmcv_tracker {
     rmcv_aim* aims = nullptr;             // [n_streams]
     // per-stream detection keys: off until rmcv_tracker_set_camps
     bool camps_on = false, lower_bounds_on = false;
+    // gimbal attitude: off until rmcv_tracker_set_attitude; the tables are allocated on first use (and freed with `allocs`)
+    bool att_on = false;
+    rmcv_attitude_config att_cfg{};
+    rmcv_attitude* attitudes = nullptr;   // [n_streams]
+    int32_t* packet_errors = nullptr;     // [n_streams]
 };

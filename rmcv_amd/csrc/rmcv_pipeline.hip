@@ -585,9 +585,11 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
 
 // d_origins non-null: a windowed batch (rmcv_pipeline_submit_windows) -- every frame read through a win_w x win_h window
 // d_camps non-null: per-frame detection keys (rmcv_pipeline_submit_camps; d_lower_bounds nullable) -- taken per batch, as windows are
+// d_packets (nullable): a tracked batch's serial packets (rmcv_pipeline_submit_tracked_serial); the attitude step runs whenever the tracker's attitude is on
 static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, const rmcv_params* p,
                   const rmcv_legacy_params* lp, int stages, uint64_t* ticket, const void* d_origins = nullptr, int win_w = 0, int win_h = 0,
-                  rmcv_tracker* trk = nullptr, int64_t timestamp = 0, const void* d_camps = nullptr, const void* d_lower_bounds = nullptr)
+                  rmcv_tracker* trk = nullptr, int64_t timestamp = 0, const void* d_camps = nullptr, const void* d_lower_bounds = nullptr,
+                  const void* d_packets = nullptr)
 {
     if (!pl || !d_frames || !p) return RMCV_ERR_BAD_ARG;
     if (!(stages & RMCV_STAGE_BINARY)) return pfail(pl, RMCV_ERR_BAD_ARG, "a pipelined batch starts at RMCV_STAGE_BINARY");
@@ -597,7 +599,9 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
         if (n_frames != tc.n_streams) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_tracked: n_frames differs from the tracker's n_streams (frame f is the next frame of stream f)");
         if (w != tc.frame_w || h != tc.frame_h) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_tracked: the frame size differs from the tracker's config");
         if (!(stages & RMCV_STAGE_ARMOURS)) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_tracked: the stages have no RMCV_STAGE_ARMOURS: nothing to track");
+        if (d_packets && !tracker_attitude_on(trk)) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_tracked_serial: packets given and the tracker's attitude is off (rmcv_tracker_set_attitude)");
     }
+    const bool attitude = trk && tracker_attitude_on(trk);
     hipSetDevice(pl->device);
     { const int rcb = finish_back(pl, false); if (rcb) return rcb; } // the batch before this one: a pixel launch follows it
     const uint64_t t = pl->next_ticket;
@@ -696,7 +700,13 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     }
     // strict closed loop: the origins k_window_origins is about to read are those the tracker's last step wrote -- an event wait on the GPU
     // (that step was enqueued by the finish_back above, or earlier)
-    if (trk && d_origins) PCHK(pl, tracker_wait_on(trk, A), "pipeline: wait for the tracker's last step");
+    if (trk && d_origins && !attitude) PCHK(pl, tracker_wait_on(trk, A), "pipeline: wait for the tracker's last step");
+    // attitude on: the attitude step first -- it makes that wait itself, for whole-frame trackers too (the step in flight reads the aim inputs
+    // this one writes), and the camps it may write are read by the k_frame_keys of the run below.  Everything it could refuse has been checked.
+    if (attitude) {
+        rc = ctx_attitude(c, trk, d_packets, A);
+        if (rc) return cfail(pl, c, rc);
+    }
     rc = ctx_run(c, p, nullptr, pixel, A, plan);
     if (rc) return cfail(pl, c, rc);
     pl->last_what = PIXEL_VARIANTS[ctx_pixel_variant(c)].step;
@@ -733,13 +743,14 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
 // submit + its own bookkeeping: the host time of the call, and the blocking calls the ring's contexts counted during it
 static int submit_counted(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, int h, int stride, int64_t frame_pitch, const rmcv_params* p,
                           const rmcv_legacy_params* lp, int stages, uint64_t* ticket, const void* d_origins = nullptr, int win_w = 0, int win_h = 0,
-                          rmcv_tracker* trk = nullptr, int64_t timestamp = 0, const void* d_camps = nullptr, const void* d_lower_bounds = nullptr)
+                          rmcv_tracker* trk = nullptr, int64_t timestamp = 0, const void* d_camps = nullptr, const void* d_lower_bounds = nullptr,
+                          const void* d_packets = nullptr)
 {
     if (!pl) return RMCV_ERR_BAD_ARG;
     timespec t0, t1;
     clock_gettime(CLOCK_MONOTONIC, &t0);
     const uint64_t b0 = ring_blocking(pl);
-    const int rc = submit(pl, d_frames, n_frames, w, h, stride, frame_pitch, p, lp, stages, ticket, d_origins, win_w, win_h, trk, timestamp, d_camps, d_lower_bounds);
+    const int rc = submit(pl, d_frames, n_frames, w, h, stride, frame_pitch, p, lp, stages, ticket, d_origins, win_w, win_h, trk, timestamp, d_camps, d_lower_bounds, d_packets);
     pl->own_blocking += ring_blocking(pl) - b0;
     clock_gettime(CLOCK_MONOTONIC, &t1);
     const double us = (t1.tv_sec - t0.tv_sec) * 1e6 + (t1.tv_nsec - t0.tv_nsec) * 1e-3;
@@ -779,6 +790,13 @@ int rmcv_pipeline_submit_windows(rmcv_pipeline* pl, const void* d_frames, int n_
 int rmcv_pipeline_submit_tracked(rmcv_pipeline* pl, rmcv_tracker* trk, const void* d_frames, int n_frames, int frame_w, int frame_h, int stride,
                                  int64_t frame_pitch, const rmcv_params* p, int stages, int64_t timestamp, uint64_t* ticket)
 {
+    return rmcv_pipeline_submit_tracked_serial(pl, trk, d_frames, n_frames, frame_w, frame_h, stride, frame_pitch, nullptr, p, stages, timestamp, ticket);
+}
+
+int rmcv_pipeline_submit_tracked_serial(rmcv_pipeline* pl, rmcv_tracker* trk, const void* d_frames, int n_frames, int frame_w, int frame_h, int stride,
+                                        int64_t frame_pitch, const void* d_packets, const rmcv_params* p, int stages, int64_t timestamp,
+                                        uint64_t* ticket)
+{
     if (!pl) return RMCV_ERR_BAD_ARG;
     if (!trk) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_tracked: null tracker");
     const rmcv_tracker_config& tc = tracker_config(trk);
@@ -787,7 +805,7 @@ int rmcv_pipeline_submit_tracked(rmcv_pipeline* pl, rmcv_tracker* trk, const voi
     const TrackerBufs& tb = tracker_bufs(trk);
     return submit_counted(pl, d_frames, n_frames, frame_w, frame_h, stride, frame_pitch, p, nullptr, stages, ticket,
                           tc.win_w > 0 ? tb.origins : nullptr, tc.win_w, tc.win_h, trk, timestamp, trk->camps_on ? tb.camps : nullptr,
-                          trk->camps_on && trk->lower_bounds_on ? tb.lower_bounds : nullptr);
+                          trk->camps_on && trk->lower_bounds_on ? tb.lower_bounds : nullptr, d_packets);
 }
 
 int rmcv_pipeline_submit_camps(rmcv_pipeline* pl, const void* d_frames, int n_frames, int frame_w, int frame_h, int stride, int64_t frame_pitch,

@@ -78,7 +78,7 @@ class Pipeline:
         return o
 
     # ------------------------------------------------------------------ the three calls
-    def submit(self, data_ptr, n, h, w, params=None, stages=STAGE_ALL, stride=None, frame_pitch=None, keepalive=None, legacy=None, windows=None, tracker=None, timestamp=0, camps=None):
+    def submit(self, data_ptr, n, h, w, params=None, stages=STAGE_ALL, stride=None, frame_pitch=None, keepalive=None, legacy=None, windows=None, tracker=None, timestamp=0, camps=None, packets=None):
         """enqueue one batch of frames resident in HBM (data_ptr: e.g. torch_tensor.data_ptr()); returns the ticket.
         windows = (d_origins_ptr, win_w, win_h): a windowed batch -- d_origins_ptr a device pointer to n (x, y) int32 pairs (e.g. an
         int32 (n, 2) torch tensor's data_ptr(); keep it alive like the frames), results in window coordinates (Context.set_windows).
@@ -86,17 +86,25 @@ class Pipeline:
         when its win_w > 0, whole frames otherwise; one step of the tracker runs behind the batch, and the next tracked submit on that
         tracker reads the origins it wrote: the closed loop with the host only submitting
         camps = (d_camps_ptr, d_lower_bounds_ptr or None): per-frame detection keys (rmcv_pipeline_submit_camps) -- device pointers to n
-        int32 each (keep them alive like the frames); composes with windows=.  A tracker with set_camps brings its own."""
+        int32 each (keep them alive like the frames); composes with windows=.  A tracker with set_camps brings its own.
+        packets = device pointer to n x 24 bytes: the tracked batch's serial packets (rmcv_pipeline_submit_tracked_serial; keep them alive like
+        the frames) for a tracker with set_attitude -- the attitude step runs in front of the batch: packet in, aim out, the host only submits"""
         if params is not None:
             self._params = params
         stride = stride or (w * self.sample_bits // 8 if self.input_format else 3 * w)
         frame_pitch = frame_pitch or stride * h
         if tracker is not None:
             assert legacy is None and windows is None and camps is None, "a tracked batch takes its windows and camps from the tracker"
-            rc = self._lib.rmcv_pipeline_submit_tracked(self._h, tracker._h, data_ptr, n, w, h, stride, frame_pitch, C.addressof(self._params), int(stages),
-                                                        int(timestamp), C.addressof(self._ticket))
+            if packets is not None:
+                rc = self._lib.rmcv_pipeline_submit_tracked_serial(self._h, tracker._h, data_ptr, n, w, h, stride, frame_pitch, int(packets),
+                                                                   C.addressof(self._params), int(stages), int(timestamp), C.addressof(self._ticket))
+            else:
+                rc = self._lib.rmcv_pipeline_submit_tracked(self._h, tracker._h, data_ptr, n, w, h, stride, frame_pitch, C.addressof(self._params), int(stages),
+                                                            int(timestamp), C.addressof(self._ticket))
             if tracker.config.win_w > 0:
                 windows = (0, tracker.config.win_w, tracker.config.win_h)   # (the shape of what the getters return)
+        elif packets is not None:
+            raise ValueError("packets= belongs to a tracked batch (tracker=)")
         elif camps is not None:
             assert legacy is None, "the legacy matcher votes a camp per blob: no per-frame camps"
             d_camps, d_lbs = camps

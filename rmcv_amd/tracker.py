@@ -8,7 +8,7 @@ import ctypes as C
 
 import numpy as np
 
-from .abi import AIM, AIM_INPUT, ARMOUR, POINT, TRACK, RmcvError, lib, ptr
+from .abi import AIM, AIM_INPUT, ARMOUR, ATTITUDE, POINT, SERIAL_PACKET_BYTES, TRACK, RmcvError, lib, ptr
 
 TRACKER_OVF = 1
 TRACKER_MAX_CAP = 64
@@ -45,6 +45,39 @@ def default_aim_config(**kw):
     for k, v in kw.items():
         setattr(c, k, v)
     return c
+
+
+class AttitudeConfig(C.Structure):
+    """rmcv_attitude_config"""
+    _fields_ = [("gripper2camera", C.c_double * 16), ("motor_angle_mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+assert C.sizeof(AttitudeConfig) == 136
+
+
+def default_attitude_config(**kw):
+    """gripper2camera of default_pnp_config, ATT_MOTOR_KEEP; gripper2camera= takes anything that reshapes to 16 doubles"""
+    c = AttitudeConfig()
+    lib().rmcv_default_attitude_config(C.byref(c))
+    for k, v in kw.items():
+        if k == "gripper2camera":
+            v = (C.c_double * 16)(*np.asarray(v, np.float64).reshape(16))
+        setattr(c, k, v)
+    return c
+
+
+def _attitudes(attitudes, n):
+    """(n, 3) (roll, pitch, yaw) radians, an ATTITUDE array, or None -> ATTITUDE[n] | None"""
+    if attitudes is None:
+        return None
+    if isinstance(attitudes, np.ndarray) and attitudes.dtype == ATTITUDE:
+        a = np.ascontiguousarray(attitudes)
+    else:
+        v = np.asarray(attitudes, np.float64).reshape(-1, 3)
+        a = np.zeros(len(v), ATTITUDE)
+        a["roll"], a["pitch"], a["yaw"] = v[:, 0], v[:, 1], v[:, 2]
+    assert len(a) == n
+    return a
 
 
 _DEFAULTS = object()   # Tracker.set_aim(): the defaults; set_aim(None): off
@@ -178,6 +211,63 @@ class Tracker:
         out = np.zeros(self.n_streams, AIM)
         self._chk(self._lib.rmcv_tracker_get_aims(self._h, ptr(out), self.n_streams))
         return out
+
+    # ---------------------------------------------------------------- gimbal attitude
+    def set_attitude(self, config=_DEFAULTS, **fields):
+        """attitude on: an AttitudeConfig, or fields of rmcv_attitude_config over the defaults (gripper2camera, motor_angle_mode).
+        set_attitude(None): off -- no kernel is launched and the tables stay as they are.  Waits for the step in flight."""
+        if config is None:
+            assert not fields
+            self._chk(self._lib.rmcv_tracker_set_attitude(self._h, None))
+            return None
+        c = default_attitude_config(**fields) if config is _DEFAULTS else config
+        self._chk(self._lib.rmcv_tracker_set_attitude(self._h, C.byref(c)))
+        return c
+
+    def set_attitudes(self, attitudes=None):
+        """per stream (roll, pitch, yaw) in radians -- (n_streams, 3) or an ATTITUDE array; None: zeros"""
+        a = _attitudes(attitudes, self.n_streams)
+        self._chk(self._lib.rmcv_tracker_set_attitudes(self._h, ptr(a)))
+
+    def attitudes(self):
+        """(ATTITUDE[n_streams], packet_errors int32[n_streams]); synchronous.  Zeros before first use."""
+        out, err = np.zeros(self.n_streams, ATTITUDE), np.zeros(self.n_streams, np.int32)
+        self._chk(self._lib.rmcv_tracker_get_attitudes(self._h, ptr(out), ptr(err), self.n_streams))
+        return out, err
+
+    def device_attitudes(self):
+        """device pointer (int) of the n_streams rmcv_attitude: a device-side producer may write them on its own stream"""
+        d = C.c_void_p()
+        self._chk(self._lib.rmcv_tracker_device_attitudes(self._h, C.byref(d)))
+        return d.value
+
+    def aim_inputs(self):
+        """AIM_INPUT[n_streams] as the device holds them; synchronous.  The defaults before first use."""
+        out = np.zeros(self.n_streams, AIM_INPUT)
+        self._chk(self._lib.rmcv_tracker_get_aim_inputs(self._h, ptr(out), self.n_streams))
+        return out
+
+    @staticmethod
+    def attitude_host(config, packet, attitude, camp=None, packet_errors=0, aim_input=None, base2gripper=True):
+        """rmcv_attitude_step_host: one stream's attitude step on the CPU (the kernel's source).  packet 24 bytes | None; attitude a
+        1-element ATTITUDE array, one record of one, or (roll, pitch, yaw); camp an int | None (camp table off); aim_input a 1-element AIM_INPUT array | None
+        (the defaults).  Returns (ATTITUDE record, camp | None, packet_errors, base2gripper (4, 4) | None, AIM_INPUT record)."""
+        if isinstance(attitude, np.void):   # (one record of an ATTITUDE array)
+            attitude = np.array([attitude], ATTITUDE)
+        a = _attitudes(attitude if isinstance(attitude, np.ndarray) else [attitude], 1).copy()
+        pk = None if packet is None else np.frombuffer(bytes(packet), np.uint8)
+        assert pk is None or len(pk) == SERIAL_PACKET_BYTES
+        cm, err = C.c_int32(0 if camp is None else int(camp)), C.c_int32(int(packet_errors))
+        b = np.zeros((4, 4)) if base2gripper else None
+        if aim_input is None:
+            inp = np.zeros(1, AIM_INPUT)
+            inp[0]["world2camera"] = np.eye(4)
+        else:
+            inp = np.ascontiguousarray(aim_input, AIM_INPUT).reshape(1).copy()
+        rc = lib().rmcv_attitude_step_host(C.byref(config), ptr(pk), ptr(a), None if camp is None else C.byref(cm), C.byref(err), ptr(b), ptr(inp))
+        if rc != 0:
+            raise RmcvError(rc, "rmcv_attitude_step_host: bad argument (a config rmcv_tracker_set_attitude would refuse)")
+        return a[0], (None if camp is None else cm.value), err.value, b, inp[0]
 
     def put(self, stream, tracks, last_vertices=None):
         """seed or restore one stream's current list: TRACK[n] (n <= track_cap), last vertices (n, 4, 2) | None: zeros; synchronous"""
