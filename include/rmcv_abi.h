@@ -833,6 +833,41 @@ int  rmcv_batch_get_base2gripper(rmcv_ctx* ctx, double* mats, int n_frames);
  * a message, before anything is enqueued: attitude off, no frames bound, n_frames != n_streams, a tracker on another device. */
 int  rmcv_batch_attitude(rmcv_ctx* ctx, rmcv_tracker* trk, const void* d_packets, void* hip_stream);
 
+/* ---- per-stream camera model and ballistics: a mixed fleet's batch ---------------------------------------------------
+ * cammat, discof and h_gripper2camera (executable/main.cpp:8-19), the plate size handed to rm::solve_PnP (main.cpp:184) and the matrix
+ * positions are placed with (main.cpp:189) belong to ONE physical camera on ONE robot, and so do the muzzle velocity and the offsets
+ * rm::SolveGEA is called with.  A batch whose frame f is the next frame of stream f may take its streams from different robots: the camera
+ * becomes a TABLE in the context, selected per frame on the device; the attitude step's hand-eye matrix and the aim step's config become
+ * per-stream tables of the tracker.  With the tables off every entry point produces the bytes it produced before they existed.
+ *
+ * The rule from a raw index to the table entry used, the ONE function k_pnp runs (pixel_plan.h: frame_camera_eff):
+ *     effective = ((uint32_t)idx < (uint32_t)n_cameras) ? idx : 0
+ * so whatever a device-side producer writes, a frame reads an entry of the table.  Frame f's rvec, tvec and position are, byte for byte,
+ * what the same batch gives with rmcv_pnp_load(cams[effective(idx[f])]).  rmcv_locate_armours (one frame) always uses camera 0. */
+int  rmcv_frame_camera(int32_t idx, int32_t n_cameras);   /* the rule: host-side, no context, no device */
+/* n_cameras configs, copied (1 .. limits.max_frames, else RMCV_ERR_BAD_ARG with a message); waits for the context's work first.  Entry 0
+ * is what rmcv_pnp_load would have loaded; rmcv_pnp_load is "a table of one".  Either call switches per-frame selection off. */
+int  rmcv_pnp_load_cameras(rmcv_ctx* ctx, const rmcv_pnp_config* cams, int n_cameras);
+/* after the frames are bound: n_frames indices, host, copied.  A value outside 0 .. n_cameras - 1 is RMCV_ERR_BAD_ARG with a message and
+ * nothing changes.  NULL: selection off, every frame uses camera 0.  A new binding of frames returns to off, as for camps and windows. */
+int  rmcv_batch_set_frame_cameras(rmcv_ctx* ctx, const int32_t* idx);
+/* ... n_frames int32 in DEVICE memory, BORROWED: read again by every run that includes RMCV_STAGE_POSE, on that run's stream.  Any value
+ * (the rule above).  NULL: selection off. */
+int  rmcv_batch_set_device_frame_cameras(rmcv_ctx* ctx, const void* d_idx);
+/* the EFFECTIVE indices of the first min(cap, n_frames) frames in the last run with RMCV_STAGE_POSE since selection was set; 0 for every
+ * frame without selection; synchronous */
+int  rmcv_batch_get_frame_cameras(rmcv_ctx* ctx, int32_t* out, int cap);
+/* the attitude step's hand-eye matrix per stream: n_streams x 16 doubles, host, copied; step 3 above then reads stream f's own matrix in
+ * place of rmcv_attitude_config::gripper2camera (rmcv_batch_attitude and the tracked submits alike).  NULL: back to the config's one.
+ * Waits for the step in flight.  RMCV_ERR_BAD_ARG with a message naming the stream: an entry not finite.  Keeping this table and the
+ * contexts' camera table consistent is the caller's job, as it is for rmcv_pnp_config against rmcv_attitude_config. */
+int  rmcv_tracker_set_stream_cameras(rmcv_tracker* trk, const double* gripper2camera);
+/* the aim step's config per stream: n_streams rmcv_aim_config, host, copied; k_aim then reads stream f's own.  NULL: back to
+ * rmcv_tracker_set_aim's one.  Waits for the step in flight.  RMCV_ERR_BAD_ARG with a message: aiming off; an entry rmcv_tracker_set_aim
+ * would refuse (the message names the stream).  Every byte stream f's steps write equals rmcv_attitude_step_host / rmcv_aim_step_host
+ * called with stream f's matrix or config. */
+int  rmcv_tracker_set_aim_configs(rmcv_tracker* trk, const rmcv_aim_config* cfgs);
+
 /* ---- pipelined batches: the process loop behind the ABI ------------------------------------------------------------------------
  * The reference's process_function is a `while (1)` that takes the newest camera frame, runs the three detection calls and hands
  * the armours on (executable/main.cpp:163-209).  Its batch form on one MI355X: `depth` batches in flight, each in a context of its
@@ -986,6 +1021,13 @@ int  rmcv_pipeline_submit_tracked(rmcv_pipeline* pl, rmcv_tracker* trk, const vo
 int  rmcv_pipeline_submit_tracked_serial(rmcv_pipeline* pl, rmcv_tracker* trk, const void* d_frames, int n_frames, int frame_w, int frame_h,
                                          int stride, int64_t frame_pitch, const void* d_packets, const rmcv_params* p, int stages,
                                          int64_t timestamp, uint64_t* ticket);
+/* the frames' camera indices for every following submit, of any of the six calls, whose stages include RMCV_STAGE_POSE: a
+ * stream's camera does not change from batch to batch.  d_idx: n_frames int32 in DEVICE memory, borrowed until replaced and until the
+ * batches submitted with it are through; read on the batch's stream in front of k_pnp; any value (rmcv_frame_camera).  NULL: off.  The
+ * cameras themselves are loaded into EVERY slot (rmcv_pipeline_context(k), rmcv_pnp_load_cameras).  Such a submit is refused with
+ * RMCV_ERR_BAD_ARG and a message, before anything is enqueued: its n_frames differs from the table's; the ring's contexts do not all hold
+ * the same n_cameras.  Nothing blocks: host_blocking_calls stays 0. */
+int  rmcv_pipeline_set_frame_cameras(rmcv_pipeline* pl, const void* d_idx, int n_frames);
 /* block until the batch is through (its record complete in HBM and, with host_results, on the host) */
 int  rmcv_pipeline_wait(rmcv_pipeline* pl, uint64_t ticket);
 /* wait + hand the batch's armours over, frame-major, in submission order of the frames: frame_offs (nullable) has n_frames + 1

@@ -8,7 +8,7 @@ armour-detection hot path, behind the reference's own function names.
 from .abi import (ARMOUR, BAYER_BG, BAYER_GB, BAYER_GR, BAYER_PATTERNS, BAYER_RG, CAMP_BLUE, INPUT_BGR, OPT_ENHANCE, OPT_INPUT_FORMAT, OPT_INPUT_ORIENT, OPT_INPUT_SAMPLE_BITS, OPT_INPUT_VALID_BIT, ORIENT_FLIP, ORIENT_MIRROR, CAMP_GUIDELIGHT, CAMP_NEUTRAL, CAMP_RED, LIGHTBLOB, MORPH_CLOSE, MORPH_DILATE,
                   MORPH_NONE, FRAME_MID_PATH, FRAME_SLOW_PATH, OPT_CONTOUR_TIER, OPT_FRAME_UPLOAD, OPT_DENSE_DEFER, OPT_PIXEL_HALO_NT, OPT_OVERLOADS, OPT_PIXEL_GROUPS, OPT_PIXEL_SHAPE, OPT_WAIT_TIMEOUT_MS, OPT_TEST_DELAY_US, OPT_IMAGE_EXPORT, OPT_TEST_SLOW_US, OPT_RUN_AHEAD, OPT_SPARSE_WAVES, POINT, RRECT, STAGE_ALL, STAGE_ARMOURS, STAGE_BINARY, STAGE_BLOBS, STAGE_CONTOURS, STAGE_IDENTITY, STAGE_NO_IMAGE, STAGE_POSE,
                   SVM_FEATURES, LegacyParams, Limits,
-                  Params, PnpConfig, RmcvError, armours_to_frame, default_params, default_pnp_config, frame_key, get_roi, window_origin,
+                  Params, PnpConfig, RmcvError, armours_to_frame, default_params, default_pnp_config, frame_camera, frame_key, get_roi, window_origin,
                   AIM, AIM_INPUT, AIM_HEIGHT_DELTA, AIM_HEIGHT_FIXED, AIM_NO_SOLUTION, AIM_NO_TARGET, AIM_PICK_NEAREST, AIM_PICK_WINDOW, AIM_SRC_FILTER,
                   AIM_SRC_MEASUREMENT, COMPENSATE_CLASSIC, COMPENSATE_NI, COMPENSATE_NONE, delta_height, distance, projectile_angle, rigid_inverse, solve_gea,
                   ATTITUDE, ATTITUDE_CONFIG, ATT_MOTOR_KEEP, ATT_MOTOR_PITCH, SERIAL_PACKET_BYTES, crc8, euler_to_matrix, homogeneous, serial_decode, serial_encode)

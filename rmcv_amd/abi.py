@@ -99,6 +99,8 @@ EXPORTS = [
     "rmcv_euler_to_matrix", "rmcv_homogeneous", "rmcv_crc8", "rmcv_serial_decode", "rmcv_serial_encode", "rmcv_attitude_step_host", "rmcv_default_attitude_config",
     "rmcv_tracker_set_attitude", "rmcv_tracker_set_attitudes", "rmcv_tracker_get_attitudes", "rmcv_tracker_device_attitudes", "rmcv_tracker_get_aim_inputs",
     "rmcv_batch_get_base2gripper", "rmcv_batch_attitude", "rmcv_pipeline_submit_tracked_serial",
+    "rmcv_frame_camera", "rmcv_pnp_load_cameras", "rmcv_batch_set_frame_cameras", "rmcv_batch_set_device_frame_cameras", "rmcv_batch_get_frame_cameras",
+    "rmcv_pipeline_set_frame_cameras", "rmcv_tracker_set_stream_cameras", "rmcv_tracker_set_aim_configs",
 ]
 
 
@@ -282,6 +284,15 @@ def load(path):
         L.rmcv_batch_attitude.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rmcv_pipeline_submit_tracked_serial.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_void_p, C.c_void_p,
                                                           C.c_int, C.c_int64, C.c_void_p]
+    if hasattr(L, "rmcv_frame_camera"):  # (builds from before the per-stream camera tables stay loadable for A/B runs)
+        L.rmcv_frame_camera.argtypes = [C.c_int32, C.c_int32]
+        L.rmcv_pnp_load_cameras.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_batch_set_frame_cameras.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_batch_set_device_frame_cameras.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_batch_get_frame_cameras.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_pipeline_set_frame_cameras.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_tracker_set_stream_cameras.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_set_aim_configs.argtypes = [C.c_void_p, C.c_void_p]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L
@@ -467,6 +478,13 @@ def serial_encode(camp, yaw_deg, pitch_deg, roll_deg):
     if rc:
         raise RmcvError(rc, "rmcv_serial_encode: camp must be CAMP_RED or CAMP_BLUE")
     return out.tobytes()
+
+
+def frame_camera(idx, n_cameras):
+    """the camera-table entry a frame with raw index `idx`, any int32, uses (rmcv_frame_camera: host-side, the function k_pnp runs)"""
+    idx, n_cameras = int(idx), int(n_cameras)
+    assert -2**31 <= idx < 2**31 and -2**31 <= n_cameras < 2**31
+    return int(lib().rmcv_frame_camera(C.c_int32(idx), C.c_int32(n_cameras)))
 
 
 def default_pnp_config():

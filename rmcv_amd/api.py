@@ -224,6 +224,37 @@ class Context:
         self._pnp = cfg or default_pnp_config()
         self._chk(lib().rmcv_pnp_load(self._h, C.byref(self._pnp)))
 
+    def pnp_load_cameras(self, cfgs):
+        """the context's camera table: a sequence of PnpConfig, one per physical camera of the fleet (rmcv_pnp_load_cameras).  Entry 0 is
+        also locate_armours' camera; set_frame_cameras picks an entry per frame.  Switches per-frame selection off."""
+        cfgs = list(cfgs)
+        arr = (PnpConfig * max(len(cfgs), 1))(*cfgs)
+        self._chk(lib().rmcv_pnp_load_cameras(self._h, arr, len(cfgs)))
+        self._pnp = arr
+
+    def set_frame_cameras(self, idx, keepalive=None):
+        """every frame bound is located through its own entry of the camera table: n integers on the host (each inside the table, else
+        RmcvError and nothing changes), or an int = device pointer to n int32 (borrowed; read again by every run with STAGE_POSE; any
+        values: frame_cameras() shows what the kernel used).  None: camera 0 for every frame (a new binding returns to that too)."""
+        if idx is None:
+            self._chk(lib().rmcv_batch_set_frame_cameras(self._h, None))
+            return
+        if isinstance(idx, (int, np.integer)):
+            self._cams_ref = keepalive
+            self._chk(lib().rmcv_batch_set_device_frame_cameras(self._h, C.c_void_p(int(idx))))
+            return
+        i = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        assert len(i) == self.shape[0], "one camera index per frame bound"
+        self._chk(lib().rmcv_batch_set_frame_cameras(self._h, ptr(i)))
+
+    def frame_cameras(self):
+        """the effective camera index of every frame in the last run with STAGE_POSE, int32 (n,); zeros without selection"""
+        out = np.zeros(self.shape[0], np.int32)
+        self._chk(lib().rmcv_batch_get_frame_cameras(self._h, ptr(out), len(out)))
+        return out
+
+    frame_camera = staticmethod(abi.frame_camera)
+
     def locate_armours(self, armours, base2gripper=None):
         """per armour: rm::solve_PnP on its vertices + the world transform; returns (rvecs, tvecs, positions), each [n, 3]"""
         arm = np.ascontiguousarray(armours, ARMOUR)

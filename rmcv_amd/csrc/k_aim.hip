@@ -9,6 +9,7 @@
 // on its own, the pick is a butterfly of __shfl_xor over a (key, index) pair and the lane that won stores the 72-byte record with ordinary
 // vector stores.  No LDS, no atomics, no waits between workgroups; nothing is indexed dynamically in registers (no scratch).
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -21,10 +22,12 @@
 namespace rmcv {
 
 __global__ __launch_bounds__(64) void k_aim(rmcv_aim_config cfg, double tick_frequency, TrackerBufs tb, int n_streams, int cap,
-                                            const rmcv_aim_input* __restrict__ inputs, int64_t now, rmcv_aim* __restrict__ aims)
+                                            const rmcv_aim_input* __restrict__ inputs, int64_t now, rmcv_aim* __restrict__ aims,
+                                            const rmcv_aim_config* __restrict__ stream_cfgs /* nullable: [n_streams], the streams' own configs */)
 {
     const int f = blockIdx.x, lane = threadIdx.x;
     if (f >= n_streams) return;
+    if (stream_cfgs) cfg = stream_cfgs[f]; // the stream is the workgroup: a uniform (scalar) load of one entry
     const int sel = tb.sel[f] & 1;
     int nt = tb.n_tracking[f];
     nt = nt < 0 ? 0 : (nt > cap ? cap : nt);
@@ -37,7 +40,7 @@ bool tracker_aim_on(const rmcv_tracker* t) { return t->aim_on; }
 hipError_t launch_aim(const rmcv_tracker* t, int64_t now, hipStream_t s)
 {
     return launch(k_aim, dim3(t->cfg.n_streams), dim3(64), 0, s, t->aim_cfg, t->cfg.tick_frequency, t->b, t->cfg.n_streams, t->cfg.track_cap,
-                  (const rmcv_aim_input*)t->aim_inputs, now, t->aims);
+                  (const rmcv_aim_input*)t->aim_inputs, now, t->aims, t->aim_cfgs_on ? t->aim_cfgs : nullptr);
 }
 
 } // namespace rmcv
@@ -148,6 +151,40 @@ int rmcv_tracker_set_aim(rmcv_tracker* t, const rmcv_aim_config* cfg)
     if ((rc = aim_alloc(t))) return rc;
     t->aim_cfg = *cfg;
     t->aim_on = true;
+    return RMCV_OK;
+}
+
+int rmcv_tracker_set_aim_configs(rmcv_tracker* t, const rmcv_aim_config* cfgs)
+{
+    if (!t) return RMCV_ERR_BAD_ARG;
+    if (!t->aim_on) return tracker_fail(t, RMCV_ERR_BAD_ARG, "rmcv_tracker_set_aim_configs: aiming is off (rmcv_tracker_set_aim)");
+    const size_t n = (size_t)t->cfg.n_streams;
+    if (cfgs) { // (the refusals need no device)
+        for (size_t f = 0; f < n; f++) {
+            const char* bad = aim_check_config(&cfgs[f]);
+            if (bad) {
+                char msg[200];
+                snprintf(msg, sizeof(msg), "rmcv_tracker_set_aim_configs: stream %d: %s", (int)f, bad);
+                return tracker_fail(t, RMCV_ERR_BAD_ARG, msg);
+            }
+        }
+    }
+    hipSetDevice(t->device);
+    const int rc = tracker_wait_done(t);
+    if (rc) return rc;
+    if (!cfgs) {
+        t->aim_cfgs_on = false;
+        return RMCV_OK;
+    }
+    if (!t->aim_cfgs) {
+        rmcv_aim_config* d = nullptr;
+        const hipError_t e = hipMalloc((void**)&d, n * sizeof(rmcv_aim_config));
+        if (e != hipSuccess) return tracker_fail(t, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the streams' aim configs", e);
+        t->allocs.push_back(d);
+        t->aim_cfgs = d;
+    }
+    ACHK(t, hipMemcpy(t->aim_cfgs, cfgs, n * sizeof(rmcv_aim_config), hipMemcpyHostToDevice), "H2D aim configs");
+    t->aim_cfgs_on = true;
     return RMCV_OK;
 }
 

@@ -12,6 +12,7 @@
 // nothing is indexed dynamically in registers (no scratch).  Latency-bound like k_aim: the point is not its speed but that the host does
 // nothing.
 #include <math.h>
+#include <stdio.h>
 #include <string.h>
 
 #include <algorithm>
@@ -22,13 +23,22 @@
 
 namespace rmcv {
 
+// PER_STREAM: the lane's own hand-eye matrix in place of the config's -- 16 doubles that live in 32 VGPRs where the config's
+// live in SGPRs.  A build of its own, so that the kernel a tracker without the table launches is the one it always launched.
+template <bool PER_STREAM>
 __global__ __launch_bounds__(64) void k_attitude(rmcv_attitude_config cfg, int n_streams, const uint8_t* __restrict__ packets,
                                                  rmcv_attitude* __restrict__ attitudes, int32_t* __restrict__ camps,
                                                  int32_t* __restrict__ packet_errors, double* __restrict__ base2gripper,
-                                                 rmcv_aim_input* __restrict__ inputs)
+                                                 rmcv_aim_input* __restrict__ inputs,
+                                                 const double* __restrict__ stream_g2c /* PER_STREAM: [n_streams][16] */)
 {
     const int f = blockIdx.x * 64 + threadIdx.x;
     if (f >= n_streams) return;
+    if (PER_STREAM) { // 16 ordinary vector loads, constant indices
+        const double* m = stream_g2c + (size_t)f * 16;
+#pragma unroll
+        for (int i = 0; i < 16; i++) cfg.gripper2camera[i] = m[i];
+    }
     att_stream(&cfg, packets ? packets + (size_t)f * RMCV_SERIAL_PACKET_BYTES : nullptr, &attitudes[f], camps ? &camps[f] : nullptr,
                &packet_errors[f], base2gripper ? base2gripper + (size_t)f * 16 : nullptr, &inputs[f]);
 }
@@ -38,8 +48,11 @@ bool tracker_attitude_on(const rmcv_tracker* t) { return t->att_on; }
 hipError_t launch_attitude(const rmcv_tracker* t, const void* d_packets, double* d_base2gripper, hipStream_t s)
 {
     const int n = t->cfg.n_streams;
-    return launch(k_attitude, dim3((n + 63) / 64), dim3(64), 0, s, t->att_cfg, n, (const uint8_t*)d_packets, t->attitudes,
-                  t->camps_on ? t->b.camps : nullptr, t->packet_errors, d_base2gripper, t->aim_inputs);
+    auto go = [&](auto kernel, const double* g2c) {
+        return launch(kernel, dim3((n + 63) / 64), dim3(64), 0, s, t->att_cfg, n, (const uint8_t*)d_packets, t->attitudes,
+                      t->camps_on ? t->b.camps : nullptr, t->packet_errors, d_base2gripper, t->aim_inputs, g2c);
+    };
+    return t->stream_g2c_on ? go(k_attitude<true>, t->stream_g2c) : go(k_attitude<false>, nullptr);
 }
 
 } // namespace rmcv
@@ -161,6 +174,38 @@ int rmcv_tracker_set_attitude(rmcv_tracker* t, const rmcv_attitude_config* cfg)
     if ((rc = att_alloc(t))) return rc;
     t->att_cfg = *cfg;
     t->att_on = true;
+    return RMCV_OK;
+}
+
+int rmcv_tracker_set_stream_cameras(rmcv_tracker* t, const double* gripper2camera)
+{
+    if (!t) return RMCV_ERR_BAD_ARG;
+    const size_t n = (size_t)t->cfg.n_streams;
+    if (gripper2camera) { // (the refusals need no device)
+        for (size_t f = 0; f < n; f++)
+            for (int i = 0; i < 16; i++)
+                if (!att_finite(gripper2camera[f * 16 + i])) {
+                    char msg[160];
+                    snprintf(msg, sizeof(msg), "rmcv_tracker_set_stream_cameras: stream %d: every entry of gripper2camera must be finite", (int)f);
+                    return tracker_fail(t, RMCV_ERR_BAD_ARG, msg);
+                }
+    }
+    hipSetDevice(t->device);
+    int rc = tracker_wait_done(t);
+    if (rc) return rc;
+    if (!gripper2camera) {
+        t->stream_g2c_on = false;
+        return RMCV_OK;
+    }
+    if (!t->stream_g2c) {
+        double* d = nullptr;
+        const hipError_t e = hipMalloc((void**)&d, n * 16 * sizeof(double));
+        if (e != hipSuccess) return tracker_fail(t, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the streams' gripper2camera table", e);
+        t->allocs.push_back(d);
+        t->stream_g2c = d;
+    }
+    TCHK(t, hipMemcpy(t->stream_g2c, gripper2camera, n * 16 * sizeof(double), hipMemcpyHostToDevice), "H2D stream cameras");
+    t->stream_g2c_on = true;
     return RMCV_OK;
 }
 

@@ -223,13 +223,22 @@ __device__ inline int solve_pnp(const float vertices[4][2], const rmcv_pnp_confi
 }
 
 // one wavefront per frame, one lane per armour; poses[frame][armour] = rvec[3] | tvec[3] | position[3]
+// cam_idx (nullable: camera 0 for every frame): the frames' raw camera indices.  The frame is the workgroup, so index and
+// config are uniform: scalar loads of ONE table entry into SGPRs as before -- the table is indexed in memory, never a copy in registers.
+// cam_eff[f] = the entry used (what rmcv_batch_get_frame_cameras reads); written only with cam_idx.
 __global__ __launch_bounds__(64) void k_pnp(const rmcv_armour* __restrict__ armours, const int32_t* __restrict__ n_armours,
                                            int max_armours, const rmcv_pnp_config* __restrict__ cfg_p,
                                            const double* __restrict__ base2gripper, double* __restrict__ poses,
-                                           const rmcv_point* __restrict__ win_eff /* nullable: the frames' window origins = the ROI of solve_PnP */)
+                                           const rmcv_point* __restrict__ win_eff /* nullable: the frames' window origins = the ROI of solve_PnP */,
+                                           const int32_t* __restrict__ cam_idx, int n_cameras, int32_t* __restrict__ cam_eff)
 {
     const int f = blockIdx.x;
-    const rmcv_pnp_config cfg = *cfg_p;
+    int cam = 0;
+    if (cam_idx) {
+        cam = __builtin_amdgcn_readfirstlane(frame_camera_eff(cam_idx[f], n_cameras));
+        if (threadIdx.x == 0) cam_eff[f] = cam;
+    }
+    const rmcv_pnp_config cfg = cfg_p[cam];
     int n = n_armours[f];
     n = n > max_armours ? max_armours : n;
     const double* B = base2gripper + (int64_t)f * 16;
@@ -258,8 +267,8 @@ __global__ __launch_bounds__(64) void k_pnp(const rmcv_armour* __restrict__ armo
 
 hipError_t launch_pnp(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s)
 {
-    return launch(k_pnp, dim3(g.n_frames), dim3(64), 0, s, b.armours, b.n_armours, lim.max_armours, b.pnp_cfg, b.pose_base2gripper,
-                       b.poses, g.win ? b.win_eff : nullptr);
+    return launch(k_pnp, dim3(g.n_frames), dim3(64), 0, s, b.armours, b.n_armours, lim.max_armours, b.pnp_cams, b.pose_base2gripper,
+                       b.poses, g.win ? b.win_eff : nullptr, b.cam_req, b.n_cameras, b.cam_eff);
 }
 
 } // namespace rmcv

@@ -86,6 +86,11 @@ RMCV_PLAN_FN FrameKey frame_key_eff(int32_t camp, int32_t lower_bound)
     k.lb = lower_bound <= 0 ? 1 : (lower_bound > 256 ? 256 : lower_bound);
     return k;
 }
+// ---- the effective camera of a frame, the one place it is computed -- by k_pnp on the device, by rmcv_frame_camera and the
+// host setter on the host: a raw index, any int32 (a device-side producer may write it), -> an entry of the context's camera table.
+// Every value outside 0 .. n_cameras - 1 is camera 0.
+RMCV_PLAN_FN int32_t frame_camera_eff(int32_t idx, int32_t n_cameras) { return (uint32_t)idx < (uint32_t)n_cameras ? idx : 0; }
+
 // A key's channel pair as compile-time values: fn(CA, CB) with std::integral_constants, for the launchers whose kernels are templates
 // over the pair.  The three pairs frame_key_eff can give: <1, 2>, <0, 2>, <2, 0>.
 template <typename Fn>

@@ -105,6 +105,7 @@ struct rmcv_ctx {
     int last_stages = 0;              // the stages the batch bound has been through since its last pixel pass (rmcv_batch_track asks for RMCV_STAGE_ARMOURS)
     rmcv_point* win_own = nullptr;    // [max_frames] the context's copy of host origins (rmcv_batch_set_windows); Bufs::win_req points here or at the caller's
     int32_t* key_own = nullptr;       // [2][max_frames] the context's copy of host camps | lower bounds (rmcv_batch_set_frame_camps); Bufs::key_camps / key_lbs point here or at the caller's
+    int32_t* cam_own = nullptr;       // [max_frames] the context's copy of host camera indices (rmcv_batch_set_frame_cameras); Bufs::cam_req points here or at the caller's
     int last_camp = RMCV_CAMP_BLUE, last_lower_bound = 80; // rmcv_params::camp, ::lower_bound of the last run with the pixel pass (rmcv_batch_get_frame_keys without per-frame keys)
     char err[256] = {0};
     std::vector<void*> allocs;

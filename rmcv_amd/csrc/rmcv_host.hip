@@ -238,6 +238,8 @@ bool pixel_ws_full(const rmcv_ctx* c, int lower_bound, const RunPlan& plan)
 }
 RunPlan ctx_plan(const rmcv_ctx* c) { return {c->pixel_shape, c->pixel_groups, c->sparse_waves, c->dense_defer ? SPARSE_SPLIT_BOTH : SPARSE_STANDARD}; }
 int ctx_enhance(const rmcv_ctx* c) { return c->enhance; }
+int ctx_n_cameras(const rmcv_ctx* c) { return c->bufs.pnp_cams ? c->bufs.n_cameras : 0; }
+void ctx_set_frame_cameras(rmcv_ctx* c, const void* d_idx) { c->bufs.cam_req = (const int32_t*)d_idx; }
 PixelVariant ctx_pixel_variant(const rmcv_ctx* c) { return geom_variant(c->geom); }
 int ctx_compact(rmcv_ctx* c, void* d_armours_out, int cap, void* d_frame_offs, void* d_status_or, hipStream_t s, void* hd_record, int host_head)
 {
@@ -435,6 +437,7 @@ int rmcv::set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t 
     g.win = win_w > 0;
     g.keys = 0; // a new binding returns to per-run keys, as it returns to whole frames
     c->bufs.key_camps = c->bufs.key_lbs = nullptr;
+    c->bufs.cam_req = nullptr; // ... and to camera 0 for every frame
     return set_extent(c, g.win ? win_w : w, g.win ? win_h : h, as);
 }
 
@@ -1063,6 +1066,9 @@ int rmcv_pnp_load(rmcv_ctx* c, const rmcv_pnp_config* cfg)
         if (e == hipSuccess) e = dalloc(c, &b.base2gripper, (size_t)c->lim.max_frames * 16);
         if (e == hipSuccess) e = dalloc(c, &b.att_base2gripper, (size_t)c->lim.max_frames * 16);
         if (e == hipSuccess) e = dalloc(c, &b.poses, (size_t)c->lim.max_frames * c->lim.max_armours * 9);
+        if (e == hipSuccess) e = dalloc(c, &b.cam_eff, (size_t)c->lim.max_frames); // (the camera table's indices: behind the others, which stay where they were)
+        if (e == hipSuccess) e = dalloc(c, &c->cam_own, (size_t)c->lim.max_frames);
+        if (e == hipSuccess) e = hipMemset(b.cam_eff, 0, (size_t)c->lim.max_frames * 4);
         if (e != hipSuccess) { b.pnp_cfg = nullptr; return fail(c, RMCV_ERR_NOMEM, "pnp buffers", e); }
         b.pose_base2gripper = b.base2gripper;
         std::vector<double> eye((size_t)c->lim.max_frames * 16, 0.0);
@@ -1071,8 +1077,86 @@ int rmcv_pnp_load(rmcv_ctx* c, const rmcv_pnp_config* cfg)
         HIPCHK(c, hipMemcpy(b.base2gripper, eye.data(), eye.size() * sizeof(double), hipMemcpyHostToDevice), "H2D base2gripper");
     }
     HIPCHK(c, hipMemcpy(b.pnp_cfg, cfg, sizeof(*cfg), hipMemcpyHostToDevice), "H2D pnp config");
+    // a table of one, per-frame selection off
+    b.pnp_cams = b.pnp_cfg;
+    b.n_cameras = 1;
+    b.cam_req = nullptr;
     return RMCV_OK;
 }
+
+int rmcv_pnp_load_cameras(rmcv_ctx* c, const rmcv_pnp_config* cams, int n_cameras)
+{
+    if (!c || !cams) return RMCV_ERR_BAD_ARG;
+    if (n_cameras < 1 || n_cameras > c->lim.max_frames) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_pnp_load_cameras: n_cameras out of range (1 .. limits.max_frames)");
+    hipSetDevice(c->device);
+    int rc = rmcv_batch_sync(c); // the table about to be rewritten may still be read by a batch in flight
+    if (rc) return rc;
+    if ((rc = rmcv_pnp_load(c, &cams[0]))) return rc; // allocates what the pose stage needs on first use; selection off
+    Bufs& b = c->bufs;
+    if (!b.cam_table) {
+        const hipError_t e = dalloc(c, &b.cam_table, (size_t)c->lim.max_frames);
+        if (e != hipSuccess) { b.cam_table = nullptr; return fail(c, RMCV_ERR_NOMEM, "camera table", e); }
+    }
+    HIPCHK(c, hipMemcpy(b.cam_table, cams, (size_t)n_cameras * sizeof(*cams), hipMemcpyHostToDevice), "H2D camera table");
+    b.pnp_cams = b.cam_table;
+    b.n_cameras = n_cameras;
+    return RMCV_OK;
+}
+
+/* ---- per-frame cameras: every frame of the batch bound is located through its own entry of the camera table ---- */
+
+// indices: the host's (validated, copied into the context's own table) or the caller's device memory (borrowed, any value); both null: camera 0
+static int set_frame_cameras(rmcv_ctx* c, const int32_t* h_idx, const void* d_idx)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    const Geom& g = c->geom;
+    Bufs& b = c->bufs;
+    if (g.n_frames <= 0 || !b.frames) return fail(c, RMCV_ERR_BAD_ARG, "no frames bound: per-frame cameras are set after the frames");
+    if (!h_idx && !d_idx) {
+        b.cam_req = nullptr;
+        return RMCV_OK;
+    }
+    if (!b.pnp_cams) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_pnp_load_cameras first");
+    if (h_idx) {
+        for (int f = 0; f < g.n_frames; f++)
+            if (frame_camera_eff(h_idx[f], b.n_cameras) != h_idx[f]) {
+                char msg[160];
+                snprintf(msg, sizeof(msg), "rmcv_batch_set_frame_cameras: frame %d: camera %d is outside the table (0 .. %d)", f, (int)h_idx[f], b.n_cameras - 1);
+                return fail(c, RMCV_ERR_BAD_ARG, msg);
+            }
+        hipSetDevice(c->device);
+        const int rc = rmcv_batch_sync(c); // the table about to be rewritten may still be read by a batch in flight
+        if (rc) return rc;
+        HIPCHK(c, hipMemcpy(c->cam_own, h_idx, (size_t)g.n_frames * 4, hipMemcpyHostToDevice), "H2D frame cameras");
+        b.cam_req = c->cam_own;
+    } else {
+        b.cam_req = (const int32_t*)d_idx;
+    }
+    return RMCV_OK;
+}
+
+int rmcv_batch_set_frame_cameras(rmcv_ctx* c, const int32_t* idx) { return set_frame_cameras(c, idx, nullptr); }
+
+int rmcv_batch_set_device_frame_cameras(rmcv_ctx* c, const void* d_idx) { return set_frame_cameras(c, nullptr, d_idx); }
+
+int rmcv_batch_get_frame_cameras(rmcv_ctx* c, int32_t* out, int cap)
+{
+    if (!c || cap < 0 || (cap > 0 && !out)) return RMCV_ERR_BAD_ARG;
+    hipSetDevice(c->device);
+    const int rc = rmcv_batch_sync(c);
+    if (rc) return rc;
+    const int n = std::min(cap, c->geom.n_frames);
+    if (n <= 0) return RMCV_OK;
+    if (!c->bufs.cam_req) { // selection off: camera 0 for every frame
+        memset(out, 0, (size_t)n * 4);
+        return RMCV_OK;
+    }
+    HIPCHK(c, hipMemcpy(out, c->bufs.cam_eff, (size_t)n * 4, hipMemcpyDeviceToHost), "D2H frame cameras");
+    return RMCV_OK;
+}
+
+/* the rule from a raw index to the table entry k_pnp uses (frame_camera_eff, the function it runs): host-side, no context, no device */
+int rmcv_frame_camera(int32_t idx, int32_t n_cameras) { return frame_camera_eff(idx, n_cameras); }
 
 int rmcv_batch_set_base2gripper(rmcv_ctx* c, const double* mats, int n_frames)
 {
@@ -1149,6 +1233,7 @@ int rmcv_locate_armours(rmcv_ctx* c, const rmcv_armour* armours, int n, const do
     g1.win = 0; // (the caller's armours, the default ROI: whatever windows the batch bound to the context has)
     Bufs b1 = c->bufs;
     b1.pose_base2gripper = b1.base2gripper; // (... and the caller's matrix, whatever attitude step ran in front of that batch)
+    b1.cam_req = nullptr;                   // (... and camera 0, whatever cameras its frames have)
     HIPCHK(c, launch_pnp(g1, b1, c->lim, c->stream), "k_pnp");
     WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
     std::vector<double> all((size_t)n * 9);

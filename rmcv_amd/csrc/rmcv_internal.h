@@ -116,7 +116,14 @@ struct Bufs {
     int32_t* identity;     // [frame][max_armours]
     uint8_t* icons;        // [frame][max_armours][1200]  rectified 20x20 BGR icons
     // armour pose; allocated by rmcv_pnp_load
-    rmcv_pnp_config* pnp_cfg;
+    rmcv_pnp_config* pnp_cfg; //  [1]            rmcv_pnp_load's one camera
+    // the camera table: what k_pnp reads.  pnp_cfg with n_cameras = 1 behind rmcv_pnp_load, cam_table behind
+    // rmcv_pnp_load_cameras; frame f takes entry frame_camera_eff(cam_req[f], n_cameras), entry 0 while cam_req is null
+    rmcv_pnp_config* cam_table;   // [max_frames]  allocated by the first rmcv_pnp_load_cameras
+    const rmcv_pnp_config* pnp_cams;
+    int n_cameras;
+    const int32_t* cam_req;       // [frame] the raw indices, any value (the context's own copy of host values, or the caller's device memory); null: off
+    int32_t* cam_eff;             // [frame] the effective indices the last k_pnp with cam_req used
     double* base2gripper;  // [frame][16]  the host's table (rmcv_batch_set_base2gripper)
     double* att_base2gripper; // [frame][16]  the attitude step's table (k_attitude.hip): the matrices of the batch it ran in front of
     const double* pose_base2gripper; // what k_pnp reads: att_base2gripper behind an attitude step, base2gripper from the next binding on
@@ -304,6 +311,10 @@ hipError_t launch_delay(unsigned long long ns, hipStream_t s); // holds `s` back
 int ctx_check_stages(rmcv_ctx* c, const rmcv_params* p, int stages);
 // RMCV_OPT_ENHANCE as set on the context
 int ctx_enhance(const rmcv_ctx* c);
+// entries of the context's camera table (0: nothing loaded)
+int ctx_n_cameras(const rmcv_ctx* c);
+// rmcv_batch_set_device_frame_cameras on what ctx_bind_frames has just bound: nothing is enqueued, nothing blocks
+void ctx_set_frame_cameras(rmcv_ctx* c, const void* d_idx);
 // the pixel kernel variant of the frames bound last (what the runs on them launch)
 PixelVariant ctx_pixel_variant(const rmcv_ctx* c);
 
@@ -369,6 +380,8 @@ struct rmcv_tracker {
     rmcv_aim_config aim_cfg{};
     rmcv_aim_input* aim_inputs = nullptr; // [n_streams]
     rmcv_aim* aims = nullptr;             // [n_streams]
+    rmcv_aim_config* aim_cfgs = nullptr;  // [n_streams] allocated by the first rmcv_tracker_set_aim_configs
+    bool aim_cfgs_on = false;             // k_aim reads stream f's own entry instead of aim_cfg
     // per-stream detection keys: off until rmcv_tracker_set_camps
     bool camps_on = false, lower_bounds_on = false;
     // gimbal attitude: off until rmcv_tracker_set_attitude; the tables are allocated on first use (and freed with `allocs`)
@@ -376,4 +389,6 @@ struct rmcv_tracker {
     rmcv_attitude_config att_cfg{};
     rmcv_attitude* attitudes = nullptr;   // [n_streams]
     int32_t* packet_errors = nullptr;     // [n_streams]
+    double* stream_g2c = nullptr;         // [n_streams][16] allocated by the first rmcv_tracker_set_stream_cameras
+    bool stream_g2c_on = false;           // k_attitude takes stream f's own gripper2camera instead of att_cfg's
 };

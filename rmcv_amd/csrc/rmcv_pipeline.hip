@@ -107,6 +107,8 @@ struct rmcv_pipeline {
     std::vector<hipEvent_t> ev_chg;    // per slot: the tail of the stream the slot's record was finished on, when that stream changes
     int wait_timeout_ms = 5000;        // rmcv_pipeline_set_wait_timeout
     const char* last_what = "nothing"; // the enqueue made last (PCHK's label): named when a wait runs out
+    const void* cam_idx = nullptr;     // rmcv_pipeline_set_frame_cameras: the frames' camera indices (device, borrowed), for every pose submit
+    int cam_frames = 0;
     int hot_cfg = 0;                   // rmcv_pipeline_config::hot_contexts as given (0: derived from the bound geometry)
     int64_t hot_plane_bytes = 0;       // ... the bit planes' bytes of a batch of the geometry `hot` was derived for
     double max_submit_us = 0;          // the longest single submit call (host time) since rmcv_pipeline_reset_stats
@@ -641,6 +643,19 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     for (size_t i = 1; i < pl->ring.size(); i++)
         if (ctx_enhance(pl->ring[i]) != ctx_enhance(pl->ring[0]))
             return pfail(pl, RMCV_ERR_BAD_ARG, "RMCV_OPT_ENHANCE differs between the pipeline's contexts: set it on EVERY slot (rmcv_pipeline_context)");
+    // the sticky camera table (rmcv_pipeline_set_frame_cameras) is this batch's when it has a pose stage: one index per frame, and every
+    // slot's context must hold a table of the same size -- the batch runs in whichever slot its ticket gives it
+    const bool cameras = pl->cam_idx && (stages & RMCV_STAGE_POSE);
+    if (cameras) {
+        if (n_frames != pl->cam_frames) {
+            char msg[200];
+            snprintf(msg, sizeof(msg), "the batch has %d frames, the pipeline's camera table %d (rmcv_pipeline_set_frame_cameras)", n_frames, pl->cam_frames);
+            return pfail(pl, RMCV_ERR_BAD_ARG, msg);
+        }
+        for (size_t i = 1; i < pl->ring.size(); i++)
+            if (ctx_n_cameras(pl->ring[i]) != ctx_n_cameras(pl->ring[0]))
+                return pfail(pl, RMCV_ERR_BAD_ARG, "n_cameras differs between the pipeline's contexts: load the same cameras into EVERY slot (rmcv_pipeline_context, rmcv_pnp_load_cameras)");
+    }
     // what the legacy matcher and per-frame keys refuse of the context's options (a Bayer input format, RMCV_OPT_ENHANCE): before anything
     // is enqueued.  (What windows and the options refuse of each other: the binding below, as for every batch.)
     if ((lp || d_camps) && (rc = ctx_check_modes(c, d_camps != nullptr, lp != nullptr))) return cfail(pl, c, rc);
@@ -670,6 +685,7 @@ static int submit(rmcv_pipeline* pl, const void* d_frames, int n_frames, int w, 
     // ---- bind: a new geometry's work (planes zeroed, frame order) is ENQUEUED on A, nothing blocks
     rc = ctx_bind_frames(c, d_frames, n_frames, w, h, stride, frame_pitch, A, d_origins, win_w, win_h, d_camps, d_lower_bounds);
     if (rc) return cfail(pl, c, rc);
+    if (cameras) ctx_set_frame_cameras(c, pl->cam_idx); // (read by the batch's k_pnp, on its stream)
     const int pixel = stages & (RMCV_STAGE_BINARY | RMCV_STAGE_NO_IMAGE), sparse = stages & ~(RMCV_STAGE_BINARY | RMCV_STAGE_NO_IMAGE);
     ctx_external_order(c, pl->ev_done[k]);
     // A burst's SECOND pixel launch is held back (k_delay on its stream).  k_binary_ws is one workgroup per CU: when two launches
@@ -756,6 +772,15 @@ static int submit_counted(rmcv_pipeline* pl, const void* d_frames, int n_frames,
     const double us = (t1.tv_sec - t0.tv_sec) * 1e6 + (t1.tv_nsec - t0.tv_nsec) * 1e-3;
     if (us > pl->max_submit_us) pl->max_submit_us = us;
     return rc;
+}
+
+int rmcv_pipeline_set_frame_cameras(rmcv_pipeline* pl, const void* d_idx, int n_frames)
+{
+    if (!pl) return RMCV_ERR_BAD_ARG;
+    if (d_idx && (n_frames < 1 || n_frames > pl->lim.max_frames)) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_frame_cameras: n_frames out of range");
+    pl->cam_idx = d_idx;
+    pl->cam_frames = d_idx ? n_frames : 0;
+    return RMCV_OK;
 }
 
 int rmcv_pipeline_reset_stats(rmcv_pipeline* pl)

@@ -77,6 +77,13 @@ class Pipeline:
         self._chk(self._lib.rmcv_pipeline_get_info(self._h, C.byref(o)))
         return o
 
+    def set_frame_cameras(self, d_idx, n=0, keepalive=None):
+        """the frames' camera indices for every following submit with STAGE_POSE (rmcv_pipeline_set_frame_cameras): d_idx a device pointer
+        to n int32, borrowed until replaced (keepalive= is held for that long); None: off.  Load the cameras into every slot first:
+        `for c in pipeline.contexts: c.pnp_load_cameras(cfgs)`."""
+        self._cams_ref = keepalive if d_idx else None
+        self._chk(self._lib.rmcv_pipeline_set_frame_cameras(self._h, C.c_void_p(int(d_idx)) if d_idx else None, int(n)))
+
     # ------------------------------------------------------------------ the three calls
     def submit(self, data_ptr, n, h, w, params=None, stages=STAGE_ALL, stride=None, frame_pitch=None, keepalive=None, legacy=None, windows=None, tracker=None, timestamp=0, camps=None, packets=None):
         """enqueue one batch of frames resident in HBM (data_ptr: e.g. torch_tensor.data_ptr()); returns the ticket.

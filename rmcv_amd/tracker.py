@@ -185,6 +185,16 @@ class Tracker:
         self._chk(self._lib.rmcv_tracker_set_aim(self._h, C.byref(c)))
         return c
 
+    def set_aim_configs(self, configs):
+        """per-stream ballistics: n_streams AimConfig, copied (rmcv_tracker_set_aim_configs); k_aim then reads stream f's own.  None: back to
+        set_aim's one.  Aiming must be on.  Waits for the step in flight."""
+        if configs is None:
+            self._chk(self._lib.rmcv_tracker_set_aim_configs(self._h, None))
+            return
+        configs = list(configs)
+        assert len(configs) == self.n_streams, "one AimConfig per stream"
+        self._chk(self._lib.rmcv_tracker_set_aim_configs(self._h, (AimConfig * len(configs))(*configs)))
+
     def set_aim_inputs(self, inputs=None):
         """per stream (world2camera (4, 4), motor_angle) -- a list of pairs or an AIM_INPUT array; None: identity, 0"""
         a = _aim_inputs(inputs, self.n_streams)
@@ -223,6 +233,19 @@ class Tracker:
         c = default_attitude_config(**fields) if config is _DEFAULTS else config
         self._chk(self._lib.rmcv_tracker_set_attitude(self._h, C.byref(c)))
         return c
+
+    def set_stream_cameras(self, cameras):
+        """per-stream hand-eye matrices for the attitude step (rmcv_tracker_set_stream_cameras): n_streams PnpConfig (their gripper2camera
+        is taken), or anything that reshapes to (n_streams, 16) doubles; copied.  None: back to the config's one.  Waits for the step in
+        flight.  Keep it consistent with the contexts' camera table (Context.pnp_load_cameras)."""
+        if cameras is None:
+            self._chk(self._lib.rmcv_tracker_set_stream_cameras(self._h, None))
+            return
+        if not isinstance(cameras, np.ndarray):
+            cameras = [list(c.gripper2camera) if hasattr(c, "gripper2camera") else c for c in cameras]
+        m = np.ascontiguousarray(np.asarray(cameras, np.float64).reshape(-1, 16))
+        assert len(m) == self.n_streams, "one gripper2camera per stream"
+        self._chk(self._lib.rmcv_tracker_set_stream_cameras(self._h, ptr(m)))
 
     def set_attitudes(self, attitudes=None):
         """per stream (roll, pitch, yaw) in radians -- (n_streams, 3) or an ATTITUDE array; None: zeros"""
