@@ -48,15 +48,7 @@ struct Geom {
     int keys;
 };
 
-// What a run's launches depend on beyond geometry, buffers and params.  The public entry points take it from the context's options
-// (ctx_plan); a pipeline overrides parts of it per batch (rmcv_pipeline.hip) instead of writing options before a run and undoing them after.
-struct RunPlan {
-    int pixel_ws;     // RMCV_OPT_PIXEL_SHAPE: whole batches with contiguous rows go to k_binary_ws (one 1024-thread workgroup per CU)
-    int pixel_groups; // RMCV_OPT_PIXEL_GROUPS: k_binary's workgroups per CU
-    int sparse_waves; // RMCV_OPT_SPARSE_WAVES: wavefronts per frame of the fused sparse kernel
-    SparseForm form;  // see sparse_plan.h (RMCV_OPT_DENSE_DEFER: SPARSE_SPLIT_BOTH)
-};
-
+// (RunPlan, what a run's launches depend on beyond geometry, buffers and params: sparse_plan.h)
 static constexpr int CTR_STRIDE = 32;   // ints between the heads of k_binary's strip queues (Bufs::strip_ctr): a 128-byte line each, 9 of them
 static constexpr int VISIT_CAP = 4096; // border visits of one frame the contour stage holds in LDS (contours_device.h); more -> mid tier
 static constexpr int NN_MID = 1 << 17;   // border visits of one frame the mid tier holds (tables in global memory); more -> literal scanner

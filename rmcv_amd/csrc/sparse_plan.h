@@ -10,6 +10,14 @@ namespace rmcv {
 // build (k_contours_lean.hip).  SPLIT_*: such frames are marked by the 4-wavefront launch and left to one with 8 wavefronts -- a pipeline's
 // split batch runs the first and the second launch apart; SPLIT_BOTH (RMCV_OPT_DENSE_DEFER) runs both.
 enum SparseForm { SPARSE_STANDARD = 0, SPARSE_LEAN, SPARSE_SPLIT_FIRST, SPARSE_SPLIT_SECOND, SPARSE_SPLIT_BOTH };
+// What a run's launches depend on beyond geometry, buffers and params.  The public entry points take it from the context's options
+// (ctx_plan); a pipeline overrides parts of it per batch (batch_plan.h) instead of writing options before a run and undoing them after.
+struct RunPlan {
+    int pixel_ws;     // RMCV_OPT_PIXEL_SHAPE: whole batches with contiguous rows go to k_binary_ws (one 1024-thread workgroup per CU)
+    int pixel_groups; // RMCV_OPT_PIXEL_GROUPS: k_binary's workgroups per CU
+    int sparse_waves; // RMCV_OPT_SPARSE_WAVES: wavefronts per frame of the fused sparse kernel
+    SparseForm form;  // RMCV_OPT_DENSE_DEFER: SPARSE_SPLIT_BOTH
+};
 enum SparseKernel { SPARSE_W8, SPARSE_W4, SPARSE_W_LEAN };
 // LDS_ONE_PER_CU: at least 84 KB, one workgroup per CU beside k_binary_ws (k_contours_w4.hip)
 enum SparseLds { LDS_FRAME, LDS_ONE_PER_CU };

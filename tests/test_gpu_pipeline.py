@@ -510,3 +510,58 @@ def test_dense_mode_follows_the_stream(oracle):
     st = pl.context_of(len(kinds) - 1).counts()["status"]
     assert not (st & abi.FRAME_MID_PATH).any()                         # the last plain batch ran the standard kernel
     pl.close()
+
+
+def test_a_waited_for_stream_is_scheduled_exactly_as_predicted(oracle):
+    """every submit followed by a wait: the record of batch t - 1 is always back when batch t is planned, so nothing of the schedule depends
+    on a race and every decision is predicted from what came back -- the rules as restated in tests/batch_plan_ref.py, fed with the frames'
+    status words and point counts of the batch's own context -- and the counters must move by exactly that: plain batches, then dense ones,
+    then plain again (whatever a kind turns out to be at this size: the prediction reads the counts, not the kind)"""
+    import torch
+
+    import batch_plan_ref as R
+    dev = torch.device("cuda", 0)
+    n, w, h, depth = 16, 640, 512, 8
+    pl = Pipeline(device=0, depth=depth, max_frames=n, max_width=w, max_height=h, max_contours=4096)
+    cfg = pl.info
+    assert (cfg.host_results, cfg.sparse_waves) == (1, 4)
+    hot = R.hot_for(0, depth, n, w, h)
+    assert pl.get_info().hot_contexts == hot
+    p = default_params()
+    kinds = [0] * 6 + [14] * 7 + [0] * 7
+    ws0 = abi.lib().rmcv_pixel_ws_launches()
+    calm = heavy = split_now = False                                   # a new pipeline's
+    words, leans = {}, {}                                              # per ticket: its record's report word; whether its sparse stage ran the lean build
+    count = (0, 0, 0, 0)                                               # hot_batches, heavy_batches, dense_split, launches of k_binary_ws
+    hot_seq = latency = 0
+    for t, kind in enumerate(kinds):
+        fr = synth.batch(440000 + 53 * t, n, w, h, CAMP_BLUE, kind, threads=16)
+        d = torch.from_numpy(fr).to(dev)
+        if t > 0:                                                      # the newest record that has come back is the last batch's
+            heavy, calm = R.mood(words[t - 1], leans[t - 1], n)
+        fast, hv, j = R.front(hot, calm, heavy, cfg.host_results, cfg.sparse_waves, STAGE_ALL, False, True, False, hot_seq, t % depth)
+        assert pl.submit(d.data_ptr(), n, h, w, p, STAGE_ALL) == t
+        pl.wait(t)                                                     # its back half goes out now, with nothing launched beside it
+        if t >= depth and cfg.dense_streams:                           # the batch that last left the slot
+            split_now = R.split_now(words[t - depth], n)
+        w8, split = R.back(True, cfg.sparse_waves, False, R.LEAN if hv else R.STANDARD, cfg.sparse_waves, split_now, cfg.dense_streams, STAGE_ALL & ~STAGE_BINARY, t % depth)[:2]
+        info = pl.get_info()
+        count = (count[0] + fast, count[1] + hv, count[2] + split, count[3] + fast)
+        got = (info.hot_batches, info.heavy_batches, info.dense_split, abi.lib().rmcv_pixel_ws_launches() - ws0)
+        print("ticket %d kind %d: fast %d heavy %d context %d w8 %d split %d; counters %s" % (t, kind, fast, hv, j, w8, split, got))
+        assert got == count, (t, kind, got, count)
+        hot_seq += fast
+        latency += w8
+        assert w8 == (not hv)                                          # (never legacy here)
+        c = pl.context_of(t).counts()
+        mid = int(np.count_nonzero(c["status"] & abi.FRAME_MID_PATH))
+        words[t] = R.report_word(mid, int(np.maximum(c["n_points"], 0).sum()) // n)
+        leans[t] = hv                                                  # (fused stages, no classifier, the mid tier's scratch there, 512 rows: dense mode takes the lean build)
+        assert not hv or mid == n
+        check_batch(oracle, fr, *pl.collect(t))
+    info = pl.get_info()
+    assert info.latency_batches == latency and info.held_back == 0 and info.host_blocking_calls == 0
+    # (observed on an MI355X: 11 hot batches, 7 in dense mode -- tickets 7 to 13, the last of them a plain batch behind a heavy record --, ticket
+    # 14 neither: the lean record's 16 mid-tier frames are not calm.)  Both branches and the way back must have been taken:
+    assert count[0] > 0 and count[1] > 0 and any(leans[t - 1] and not leans[t] for t in range(1, len(kinds)))
+    pl.close()
