@@ -1051,6 +1051,53 @@ int  rmcv_pipeline_set_hook(rmcv_pipeline* pl, rmcv_pipeline_hook fn, void* user
 int  rmcv_pipeline_set_gather(rmcv_pipeline* pl, rmcv_comm* comm, int root);
 int  rmcv_pipeline_gathered(rmcv_pipeline* pl, uint64_t ticket, void** d_recv, int64_t* bytes);
 
+/* ---- the operator's view: the debug image of the reference's loop, rendered on the device -------------------------
+ * executable/main.cpp:200-207 builds a debug image from `binary` -- cvtColor(GRAY2BGR), rm::debug::draw_lightblobs(positive, negative),
+ * rm::debug::draw_armours(armours) (src/debug.cpp:43-93) -- and its debug thread (:90-100) shows it resized to 1024 x 768.  For a frame f of
+ * a batch whose run included RMCV_STAGE_ARMOURS and a view size (vw, vh):
+ *     V(f) = resize( draw_armours( draw_lightblobs( GRAY2BGR(binary_f) ) ), (vw, vh), INTER_LINEAR ),   8UC3, BGR
+ * every byte equal to the CPU restatement rmcv_debug_view_host of those calls (OpenCV 4.8.0 as recalled: SURVEY.md A.10), with one stated
+ * deviation: cv::putText (debug.cpp:53-57) is not rendered -- the label's data (identity, position, vertices[0]) comes from the getters.
+ * A segment with an endpoint that is not finite or of magnitude >= 2^30 is skipped.  In a windowed batch the view is the window's.  The view
+ * is written from the frame's bit plane and its result tables: it is the same with and without RMCV_STAGE_NO_IMAGE.
+ * Colours (BGR): a positive blob (0, 255, 0) if its target is RMCV_CAMP_RED, (0, 0, 255) otherwise; negatives, armours' vertices and icons
+ * (0, 255, 255); later draws overwrite earlier ones. */
+#define RMCV_VIEW_BLOBS 1     /* the positive light blobs                         */
+#define RMCV_VIEW_NEGATIVES 2 /* the negative contours                            */
+#define RMCV_VIEW_ARMOURS 4   /* every armour's vertices and icon quadrilaterals  */
+#define RMCV_VIEW_ALL 7       /* the reference                                    */
+/* the views of n frames of the batch bound, frames[k] -> d_out + k * out_pitch (DEVICE memory of the caller's, rows out_stride >= 3 vw bytes
+ * apart, views out_pitch >= out_stride (vh - 1) + 3 vw apart).  Asynchronous: enqueued on hip_stream (NULL: the context's) behind the run;
+ * renders what the tables hold and reports no frame status.  RMCV_ERR_BAD_ARG, with a message, before anything is enqueued: n < 1 or beyond
+ * the batch; a frame index out of range or repeated; vw / vh < 1 or beyond the context's max_width / max_height; a stride or pitch too small;
+ * unknown flags; a batch whose last run lacked the stages the flags need (RMCV_STAGE_BINARY; _CONTOURS and _BLOBS for blobs and negatives;
+ * _ARMOURS for armours). */
+int rmcv_batch_debug_views(rmcv_ctx* ctx, const int32_t* frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch,
+                           void* hip_stream);
+/* one frame's view to HOST memory; waits with the context's deadline.  Also RMCV_ERR_BAD_ARG: the frame carries an RMCV_FRAME_OVF_* status
+ * (its tables are not the frame's lists). */
+int rmcv_batch_get_debug_view(rmcv_ctx* ctx, int frame, int vw, int vh, int flags, uint8_t* out, int out_stride);
+/* stage-wise: host lists through the same two kernels, buffers of its own (nothing bound to the context moves).  binary: h rows of
+ * `stride >= w` bytes, 0 / 255 (any other non-zero byte counts as 255); neg_pts / neg_offs: the negative contours as CSR, n_neg + 1
+ * offsets; w, h, vw, vh within the context's max_width / max_height. */
+int rmcv_debug_view(rmcv_ctx* ctx, const uint8_t* binary, int w, int h, int stride, const rmcv_lightblob* blobs, int n_blobs,
+                    const rmcv_point* neg_pts, const int32_t* neg_offs, int n_neg, const rmcv_armour* armours, int n_armours, int flags,
+                    int vw, int vh, uint8_t* out, int out_stride);
+/* the same arguments, host-side (no context, no device, any size): the sequential restatement -- a BGR canvas drawn in the reference's
+ * call order, every blob in its own colour, then resized */
+int rmcv_debug_view_host(const uint8_t* binary, int w, int h, int stride, const rmcv_lightblob* blobs, int n_blobs, const rmcv_point* neg_pts,
+                         const int32_t* neg_offs, int n_neg, const rmcv_armour* armours, int n_armours, int flags, int vw, int vh,
+                         uint8_t* out, int out_stride);
+/* a pipeline's views: from the next submit on, every batch's frames[0 .. n) are rendered behind its sparse stage into the slot's own view
+ * buffer (allocated HERE, one per ring slot: this call blocks, no submit does).  n == 0: off -- a submit then enqueues exactly what it did
+ * before.  RMCV_ERR_BAD_ARG as rmcv_batch_debug_views; a later submit whose n_frames does not reach every index, or whose stages lack what
+ * the flags need, is refused before anything is enqueued. */
+int rmcv_pipeline_set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags);
+/* the views of a ticket's batch: n views of vh rows, *stride bytes between rows, *pitch between views, in device memory; complete once the
+ * ticket has been waited for, valid as long as the ticket's record (until ticket + depth is submitted).  RMCV_ERR_BAD_ARG: the ticket was
+ * never issued, its slot has been reused, or it was submitted without views. */
+int rmcv_pipeline_views(rmcv_pipeline* pl, uint64_t ticket, void** d_views, int32_t* stride, int64_t* pitch, int32_t* n);
+
 /* ---- device memory for hosts without HIP headers (tools/pipeline_bench.c): frames resident in HBM ------------------------------- */
 int  rmcv_device_alloc(int device, int64_t bytes, void** d_ptr);
 void rmcv_device_free(int device, void* d_ptr);

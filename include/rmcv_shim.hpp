@@ -21,6 +21,7 @@
 // of rm::AutoEnhance + rm::extract_color fused (the enhanced frame is never written).
 // rm::utils::GetROI (include/core.h:142-147), the reference's tracked-ROI helper, is here as well (where the cv:: headers know cv::Size).
 // rm::ProjectileAngle / SolveGEA / DeltaHeight / Distance (include/mobility.h) too, behind the reference's mobility.h.
+// One more addition: rm::debug::device_view, the loop's debug image of a batch frame rendered on the device (where the cv:: headers know cv::Size).
 // The legacy names of the north star are aliased at the bottom (docs/core_8h_source.html:101,114).
 //
 // Every signature mentions cv:: types, so this header only compiles where OpenCV headers exist.
@@ -365,6 +366,25 @@ RMCV_SHIM_LINKAGE cv::Rect GetROI(cv::Point2f* imagePoints, int pointsCount, flo
     return GetROI(imagePoints, pointsCount, cv::Size2f(scaleFactor, scaleFactor), frameSize, previous); // src/core.cpp:221
 }
 } // namespace utils
+#endif
+
+// ---- rm::debug::device_view: ONE ADDITION the reference does not have -- the debug image its loop builds (executable/main.cpp:200-207:
+// binary -> BGR, rm::debug::draw_lightblobs, rm::debug::draw_armours) and its debug thread shows resized (:90-100), for frame `frame` of the
+// batch a context has run, rendered on the device (rmcv_batch_get_debug_view; no text: DESIGN.md 4j).  The context is the CALLER's: views
+// are of batches (rmcv_batch_run, a pipeline's slot), not of the per-frame chain's hidden context.  rm::debug::draw_lightblobs / draw_armours
+// on a host cv::Mat stay the reference's own -- the shim does not define them.  The default size lives on the host's declaration.
+// (Guarded like rm::utils::GetROI: only where the cv:: headers in use know cv::Size.)
+#if defined(CV_VERSION) || defined(RMCV_CV_HAS_SIZE)
+namespace debug {
+RMCV_SHIM_LINKAGE cv::Mat device_view(rmcv_ctx* context, int frame, const cv::Size& size)
+{
+    if (!context || size.width < 1 || size.height < 1) throw std::invalid_argument("rm::debug::device_view: null context or an empty size");
+    cv::Mat view(size.height, size.width, CV_8UC3);
+    if (rmcv_batch_get_debug_view(context, frame, size.width, size.height, RMCV_VIEW_ALL, view.data, (int)(size_t)view.step) != RMCV_OK)
+        throw std::runtime_error(std::string("rm::debug::device_view: ") + rmcv_last_error(context));
+    return view;
+}
+} // namespace debug
 #endif
 
 // ---- rm::ProjectileAngle / SolveGEA / DeltaHeight / Distance (include/mobility.h:55-62,75,95-97; bodies src/mobility.cpp:36-82,127-164)

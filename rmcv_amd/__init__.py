@@ -11,8 +11,9 @@ from .abi import (ARMOUR, BAYER_BG, BAYER_GB, BAYER_GR, BAYER_PATTERNS, BAYER_RG
                   Params, PnpConfig, RmcvError, armours_to_frame, default_params, default_pnp_config, frame_camera, frame_key, get_roi, window_origin,
                   AIM, AIM_INPUT, AIM_HEIGHT_DELTA, AIM_HEIGHT_FIXED, AIM_NO_SOLUTION, AIM_NO_TARGET, AIM_PICK_NEAREST, AIM_PICK_WINDOW, AIM_SRC_FILTER,
                   AIM_SRC_MEASUREMENT, COMPENSATE_CLASSIC, COMPENSATE_NI, COMPENSATE_NONE, delta_height, distance, projectile_angle, rigid_inverse, solve_gea,
-                  ATTITUDE, ATTITUDE_CONFIG, ATT_MOTOR_KEEP, ATT_MOTOR_PITCH, SERIAL_PACKET_BYTES, crc8, euler_to_matrix, homogeneous, serial_decode, serial_encode)
-from .api import Context
+                  ATTITUDE, ATTITUDE_CONFIG, ATT_MOTOR_KEEP, ATT_MOTOR_PITCH, SERIAL_PACKET_BYTES, crc8, euler_to_matrix, homogeneous, serial_decode, serial_encode,
+                  VIEW_ALL, VIEW_ARMOURS, VIEW_BLOBS, VIEW_NEGATIVES, debug_view_host)
+from .api import Context, debug_view
 from .pipeline import Pipeline
 from .tracker import TRACKER_OVF, AimConfig, AttitudeConfig, Tracker, TrackerConfig, default_aim_config, default_attitude_config, default_tracker_config
 

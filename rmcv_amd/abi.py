@@ -71,6 +71,7 @@ AIM_NO_TARGET, AIM_NO_SOLUTION = 1, 2
 AIM_HEIGHT_FIXED, AIM_HEIGHT_DELTA = 0, 1
 AIM_SRC_FILTER, AIM_SRC_MEASUREMENT = 0, 1
 AIM_PICK_WINDOW, AIM_PICK_NEAREST = 0, 1
+VIEW_BLOBS, VIEW_NEGATIVES, VIEW_ARMOURS, VIEW_ALL = 1, 2, 4, 7  # RMCV_VIEW_*: what the debug view draws over the binary (all: the reference)
 FRAME_OVF_CONTOURS, FRAME_OVF_POINTS, FRAME_OVF_BLOBS, FRAME_OVF_ARMOURS, FRAME_SLOW_PATH, FRAME_MID_PATH = 1, 2, 4, 8, 16, 64
 
 EXPORTS = [
@@ -101,6 +102,7 @@ EXPORTS = [
     "rmcv_batch_get_base2gripper", "rmcv_batch_attitude", "rmcv_pipeline_submit_tracked_serial",
     "rmcv_frame_camera", "rmcv_pnp_load_cameras", "rmcv_batch_set_frame_cameras", "rmcv_batch_set_device_frame_cameras", "rmcv_batch_get_frame_cameras",
     "rmcv_pipeline_set_frame_cameras", "rmcv_tracker_set_stream_cameras", "rmcv_tracker_set_aim_configs",
+    "rmcv_batch_debug_views", "rmcv_batch_get_debug_view", "rmcv_debug_view", "rmcv_debug_view_host", "rmcv_pipeline_set_views", "rmcv_pipeline_views",
 ]
 
 
@@ -293,6 +295,15 @@ def load(path):
         L.rmcv_pipeline_set_frame_cameras.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
         L.rmcv_tracker_set_stream_cameras.argtypes = [C.c_void_p, C.c_void_p]
         L.rmcv_tracker_set_aim_configs.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(L, "rmcv_debug_view_host"):  # (builds from before the debug view stay loadable for A/B runs)
+        view = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                C.c_void_p, C.c_int]
+        L.rmcv_debug_view_host.argtypes = view
+        L.rmcv_debug_view.argtypes = [C.c_void_p] + view
+        L.rmcv_batch_debug_views.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+        L.rmcv_batch_get_debug_view.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.rmcv_pipeline_set_views.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
+        L.rmcv_pipeline_views.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L
@@ -382,6 +393,42 @@ def frame_key(camp, lower_bound):
     if rc:
         raise RmcvError(rc, "rmcv_frame_key")
     return tuple(int(v) for v in out)
+
+
+def view_args(binary, blobs, negatives, armours, flags, size):
+    """the argument list rmcv_debug_view and rmcv_debug_view_host share, and the arrays it points into (keep them until the call is through):
+    binary (h, w) uint8; blobs LIGHTBLOB[]; negatives a list of (k, 2) int32 contours, or (POINT[], offs int32[n + 1]); armours ARMOUR[];
+    size (vw, vh) -> (args, out (vh, vw, 3) uint8, keepalive)"""
+    binary = np.ascontiguousarray(binary, np.uint8)
+    h, w = binary.shape
+    blobs = np.ascontiguousarray(blobs if blobs is not None else [], LIGHTBLOB).reshape(-1)
+    armours = np.ascontiguousarray(armours if armours is not None else [], ARMOUR).reshape(-1)
+    if isinstance(negatives, tuple):
+        pts, offs = np.ascontiguousarray(negatives[0], POINT).reshape(-1), np.ascontiguousarray(negatives[1], np.int32).reshape(-1)
+        assert len(offs) >= 1
+    else:
+        negatives = [np.ascontiguousarray(c, np.int32).reshape(-1, 2) for c in (negatives if negatives is not None else [])]
+        pts = np.zeros(sum(len(c) for c in negatives), POINT)
+        offs = np.zeros(len(negatives) + 1, np.int32)
+        for i, c in enumerate(negatives):
+            offs[i + 1] = offs[i] + len(c)
+            pts["x"][offs[i]:offs[i + 1]], pts["y"][offs[i]:offs[i + 1]] = c[:, 0], c[:, 1]
+    vw, vh = int(size[0]), int(size[1])
+    out = np.zeros((max(vh, 0), max(vw, 0), 3), np.uint8)
+    keep = (binary, blobs, armours, pts, offs)
+    args = [ptr(binary), w, h, w, ptr(blobs) if len(blobs) else None, len(blobs), ptr(pts) if len(pts) else None, ptr(offs), len(offs) - 1,
+            ptr(armours) if len(armours) else None, len(armours), int(flags), vw, vh, ptr(out), 3 * vw]
+    return args, out, keep
+
+
+def debug_view_host(binary, blobs=None, negatives=None, armours=None, size=(1024, 768), flags=VIEW_ALL):
+    """the debug image of executable/main.cpp:200-207 at `size` = (vw, vh), on the CPU (rmcv_debug_view_host: the sequential restatement, no
+    device): GRAY2BGR(binary), rm::debug::draw_lightblobs, rm::debug::draw_armours (no text), resized INTER_LINEAR -> (vh, vw, 3) uint8 BGR"""
+    args, out, keep = view_args(binary, blobs, negatives, armours, flags, size)
+    rc = lib().rmcv_debug_view_host(*args)
+    if rc:
+        raise RmcvError(rc, "rmcv_debug_view_host: sizes >= 1, known flags, contour offsets that do not decrease")
+    return out
 
 
 def _tvec(tvec):

@@ -561,6 +561,46 @@ class Context:
         self._chk(lib().rmcv_batch_get_armours(self._h, ptr(out), cap, ptr(offs), C.byref(tot)))
         return out[:tot.value].copy(), offs
 
+    # ---------------------------------------------------------------- the operator's debug view
+    def debug_views(self, frames, size=(1024, 768), flags=abi.VIEW_ALL, out=None, stream=None):
+        """the debug images (executable/main.cpp:200-207, no text) of the chosen frames of the batch run last, rendered on the device at
+        `size` = (vw, vh) (rmcv_batch_debug_views; asynchronous, behind the run).  out: a device pointer of the caller's for n contiguous
+        (vh, vw, 3) views, e.g. a torch uint8 tensor's data_ptr() -- then returns None; without it the views come back as a host
+        (n, vh, vw, 3) uint8 array (through a device buffer of the call's own; synchronises)."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        vw, vh = int(size[0]), int(size[1])
+        pitch = 3 * vw * vh
+        if out is not None:
+            self._chk(lib().rmcv_batch_debug_views(self._h, ptr(fr), len(fr), vw, vh, int(flags), C.c_void_p(int(out)), 3 * vw, pitch, C.c_void_p(stream or 0)))
+            return None
+        d = C.c_void_p()
+        nbytes = max(len(fr), 1) * max(pitch, 1)
+        if lib().rmcv_device_alloc(self.device, C.c_int64(nbytes), C.byref(d)):
+            raise RmcvError(abi.ERR_NOMEM, "rmcv_device_alloc")
+        try:
+            self._chk(lib().rmcv_batch_debug_views(self._h, ptr(fr), len(fr), vw, vh, int(flags), d, 3 * vw, pitch, C.c_void_p(stream or 0)))
+            self.sync()
+            host = np.empty((len(fr), vh, vw, 3), np.uint8)
+            rc = lib().rmcv_device_download(self.device, ptr(host), d, C.c_int64(host.nbytes))
+            if rc:
+                raise RmcvError(rc, "rmcv_device_download")
+            return host
+        finally:
+            lib().rmcv_device_free(self.device, d)
+
+    def debug_view(self, frame, size=(1024, 768), flags=abi.VIEW_ALL):
+        """one frame's debug image on the host, (vh, vw, 3) uint8 BGR (rmcv_batch_get_debug_view; refuses a frame with an overflow status)"""
+        vw, vh = int(size[0]), int(size[1])
+        out = np.empty((max(vh, 0), max(vw, 0), 3), np.uint8)
+        self._chk(lib().rmcv_batch_get_debug_view(self._h, int(frame), vw, vh, int(flags), ptr(out), 3 * vw))
+        return out
+
+    def debug_view_of(self, binary, blobs=None, negatives=None, armours=None, size=(1024, 768), flags=abi.VIEW_ALL):
+        """stage-wise: the debug image of host lists through the same kernels (rmcv_debug_view; arguments as abi.debug_view_host)"""
+        args, out, keep = abi.view_args(binary, blobs, negatives, armours, flags, size)
+        self._chk(lib().rmcv_debug_view(self._h, *args))
+        return out
+
     def device_views(self):
         """(armours device pointer, counts device pointer, per-frame capacity, n_frames) for a collective"""
         a, c = C.c_void_p(), C.c_void_p()
@@ -614,3 +654,9 @@ class Context:
         self.run(params)
         self.sync()
         return self.armours()
+
+
+def debug_view(ctx, binary, blobs=None, negatives=None, armours=None, size=(1024, 768), flags=abi.VIEW_ALL):
+    """the debug image of host lists, rendered on ctx's device (rmcv_debug_view: the stage-wise form of Context.debug_views; arguments as
+    rmcv_amd.debug_view_host, which is the same on the CPU)"""
+    return ctx.debug_view_of(binary, blobs, negatives, armours, size, flags)

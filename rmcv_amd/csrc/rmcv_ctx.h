@@ -107,6 +107,11 @@ struct rmcv_ctx {
     int32_t* key_own = nullptr;       // [2][max_frames] the context's copy of host camps | lower bounds (rmcv_batch_set_frame_camps); Bufs::key_camps / key_lbs point here or at the caller's
     int32_t* cam_own = nullptr;       // [max_frames] the context's copy of host camera indices (rmcv_batch_set_frame_cameras); Bufs::cam_req points here or at the caller's
     int last_camp = RMCV_CAMP_BLUE, last_lower_bound = 80; // rmcv_params::camp, ::lower_bound of the last run with the pixel pass (rmcv_batch_get_frame_keys without per-frame keys)
+    // the debug view: allocated on first use (ctx_view_prepare), never by a run
+    uint64_t* view_overlay = nullptr; // [view_cap][2] colour planes, each as large as a plane of the largest frame
+    int view_cap = 0;                 // views the overlay holds
+    int32_t* view_frames = nullptr;   // [max_frames] the frame list of the views enqueued last
+    uint8_t* view_out = nullptr;      // [3 * max_width * max_height] one view on its way to the host (rmcv_batch_get_debug_view)
     char err[256] = {0};
     std::vector<void*> allocs;
     struct Guarded { uint8_t* base; size_t bytes; const char* name; size_t rear = 0; };

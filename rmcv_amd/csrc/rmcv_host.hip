@@ -19,6 +19,7 @@
 #include "device_bayer.h"
 #include "enhance_math.h"
 #include "device_track.h"
+#include "device_view.h"
 
 using namespace rmcv;
 
@@ -1821,6 +1822,173 @@ int rmcv_lightblob_overlap(const rmcv_lightblob* lb, int n, int left, int right,
         }
     }
     return RMCV_OK;
+}
+
+} // extern "C"
+
+/* ---- the operator's debug view (k_view.hip) ---- */
+
+namespace rmcv {
+
+int ctx_view_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int flags, int out_stride, int64_t out_pitch)
+{
+    if (!frames || n < 1) return fail(c, RMCV_ERR_BAD_ARG, "debug views: no frames chosen");
+    if (n > n_frames) return fail(c, RMCV_ERR_BAD_ARG, "debug views: more views than the batch has frames");
+    if (flags < 0 || flags > RMCV_VIEW_ALL) return fail(c, RMCV_ERR_BAD_ARG, "debug views: unknown view flags");
+    if (vw < 1 || vh < 1 || vw > c->lim.max_width || vh > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, "debug views: the view size must be 1 .. max_width x 1 .. max_height");
+    if (out_stride < 3 * (int64_t)vw) return fail(c, RMCV_ERR_BAD_ARG, "debug views: out_stride < 3 vw");
+    if (n > 1 && out_pitch < (int64_t)out_stride * (vh - 1) + 3 * (int64_t)vw) return fail(c, RMCV_ERR_BAD_ARG, "debug views: out_pitch < out_stride (vh - 1) + 3 vw");
+    std::vector<char> seen((size_t)n_frames, 0);
+    for (int k = 0; k < n; k++) {
+        if (frames[k] < 0 || frames[k] >= n_frames) return fail(c, RMCV_ERR_BAD_ARG, "debug views: a frame index is outside the batch");
+        if (seen[frames[k]]) return fail(c, RMCV_ERR_BAD_ARG, "debug views: a frame index is repeated");
+        seen[frames[k]] = 1;
+    }
+    const int need = view_stages_needed(flags);
+    if ((stages & need) != need) return fail(c, RMCV_ERR_BAD_ARG, "debug views: the batch's run lacked a stage the view flags need");
+    return RMCV_OK;
+}
+
+int ctx_view_prepare(rmcv_ctx* c, int n)
+{
+    hipError_t e = hipSuccess;
+    if (!c->view_frames) e = dalloc(c, &c->view_frames, (size_t)c->lim.max_frames);
+    if (e == hipSuccess && n > c->view_cap) { // a handful of views, or every frame: at most two allocations in a context's life
+        const int cap = n <= 8 && c->lim.max_frames > 8 ? 8 : c->lim.max_frames;
+        const size_t plane = (size_t)(c->lim.max_height + 2) * ((c->lim.max_width + 63) / 64 + 2);
+        uint64_t* p = nullptr;
+        e = dalloc_named(c, &p, (size_t)cap * 2 * plane, "view_overlay");
+        if (e == hipSuccess) {
+            c->view_overlay = p;
+            c->view_cap = cap;
+        }
+    }
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the debug views' planes", e);
+    return RMCV_OK;
+}
+
+int ctx_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
+{
+    const Geom& g = c->geom;
+    const Bufs& b = c->bufs;
+    ViewJob j{};
+    j.w = g.w; j.h = g.h; j.prow = g.prow; j.plane_pitch = g.plane_pitch;
+    j.bits = b.bits; j.overlay = c->view_overlay; j.frames = d_frames;
+    j.n = n; j.vw = vw; j.vh = vh; j.flags = flags;
+    j.out = (uint8_t*)d_out; j.out_stride = out_stride; j.out_pitch = out_pitch;
+    j.lists = ViewLists{b.blobs, b.n_blobs, b.armours, b.n_armours, b.points, b.cont_start, b.cont_len, b.n_contours, b.neg_idx, b.n_neg, nullptr,
+                        c->lim.max_blobs, c->lim.max_armours, c->lim.max_points, c->lim.max_contours, 0};
+    HIPCHK(c, launch_view(j, s), "k_view_overlay + k_view_resize");
+    return RMCV_OK;
+}
+
+} // namespace rmcv
+
+// rmcv_batch_debug_views behind its checks
+static int view_batch(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
+{
+    int rc = ctx_view_prepare(c, n);
+    if (rc) return rc;
+    if ((rc = order_begin(c, s))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->view_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D view frames");
+    if ((rc = ctx_view_enqueue(c, c->view_frames, n, vw, vh, flags, d_out, out_stride, out_pitch, s))) return rc;
+    return order_end(c, s);
+}
+
+extern "C" {
+
+int rmcv_batch_debug_views(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch,
+                           void* hip_stream)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!d_out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_debug_views: null output");
+    const int rc = ctx_view_check(c, frames, n, c->geom.n_frames, c->last_stages, vw, vh, flags, out_stride, out_pitch);
+    if (rc) return rc;
+    hipSetDevice(c->device);
+    return view_batch(c, frames, n, vw, vh, flags, d_out, out_stride, out_pitch, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int rmcv_batch_get_debug_view(rmcv_ctx* c, int frame, int vw, int vh, int flags, uint8_t* out, int out_stride)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_get_debug_view: null output");
+    const int32_t one = frame;
+    int rc = ctx_view_check(c, &one, 1, c->geom.n_frames, c->last_stages, vw, vh, flags, out_stride, 0);
+    if (rc) return rc;
+    hipSetDevice(c->device);
+    if ((rc = rmcv_batch_sync(c))) return rc;
+    int32_t st = 0;
+    HIPCHK(c, hipMemcpy(&st, c->bufs.status + frame, 4, hipMemcpyDeviceToHost), "D2H");
+    if (st & (RMCV_FRAME_OVF_CONTOURS | RMCV_FRAME_OVF_POINTS | RMCV_FRAME_OVF_BLOBS | RMCV_FRAME_OVF_ARMOURS))
+        return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_get_debug_view: the frame exceeded a context limit (see its status): its tables are not its lists");
+    if (!c->view_out) {
+        const hipError_t e = dalloc(c, &c->view_out, (size_t)3 * c->lim.max_width * c->lim.max_height);
+        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the debug view's staging", e);
+    }
+    if ((rc = view_batch(c, &one, 1, vw, vh, flags, c->view_out, 3 * vw, (int64_t)3 * vw * vh, c->stream))) return rc;
+    WAITCHK(c, wait_stream(c, c->stream, "k_view_resize"));
+    HIPCHK(c, hipMemcpy2D(out, out_stride, c->view_out, (size_t)3 * vw, (size_t)3 * vw, vh, hipMemcpyDeviceToHost), "D2H view");
+    return RMCV_OK;
+}
+
+int rmcv_debug_view(rmcv_ctx* c, const uint8_t* binary, int w, int h, int stride, const rmcv_lightblob* blobs, int n_blobs, const rmcv_point* neg_pts,
+                    const int32_t* neg_offs, int n_neg, const rmcv_armour* armours, int n_armours, int flags, int vw, int vh, uint8_t* out,
+                    int out_stride)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!binary || !out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_debug_view: null buffer");
+    const char* bad = view_check_lists(w, h, stride, blobs, n_blobs, neg_pts, neg_offs, n_neg, armours, n_armours, flags, vw, vh, out_stride);
+    if (bad) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "rmcv_debug_view: %s", bad);
+        return fail(c, RMCV_ERR_BAD_ARG, msg);
+    }
+    if (w > c->lim.max_width || h > c->lim.max_height || vw > c->lim.max_width || vh > c->lim.max_height)
+        return fail(c, RMCV_ERR_BAD_ARG, "rmcv_debug_view: image or view beyond the context's max_width / max_height");
+    hipSetDevice(c->device);
+    int rc = rmcv_batch_sync(c);
+    if (rc) return rc;
+    // (a stage-wise helper: buffers of its own, so that nothing bound to the context moves) -- one host block, one upload
+    const int prow = (w + 63) / 64 + 2, n_pts = n_neg ? neg_offs[n_neg] : 0;
+    const size_t plane = (size_t)(h + 2) * prow;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_blobs = up16(plane * 8), o_arm = o_blobs + up16((size_t)n_blobs * sizeof(rmcv_lightblob));
+    const size_t o_pts = o_arm + up16((size_t)n_armours * sizeof(rmcv_armour)), o_offs = o_pts + up16((size_t)n_pts * sizeof(rmcv_point));
+    const size_t o_cnt = o_offs + up16((size_t)(n_neg + 1) * 4), in_bytes = o_cnt + 16;
+    const size_t o_ov = in_bytes, o_out = o_ov + up16(2 * plane * 8), total = o_out + (size_t)3 * vw * vh;
+    std::vector<uint8_t> host(in_bytes, 0);
+    uint64_t* hp = reinterpret_cast<uint64_t*>(host.data());
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < w; x++)
+            if (binary[(size_t)y * stride + x]) hp[(size_t)(y + 1) * prow + (x >> 6) + 1] |= 1ull << (x & 63);
+    if (n_blobs) memcpy(&host[o_blobs], blobs, (size_t)n_blobs * sizeof(rmcv_lightblob));
+    if (n_armours) memcpy(&host[o_arm], armours, (size_t)n_armours * sizeof(rmcv_armour));
+    if (n_pts) memcpy(&host[o_pts], neg_pts, (size_t)n_pts * sizeof(rmcv_point));
+    if (n_neg) memcpy(&host[o_offs], neg_offs, (size_t)(n_neg + 1) * 4);
+    const int32_t counts[4] = {n_blobs, n_armours, n_neg, 0};
+    memcpy(&host[o_cnt], counts, sizeof(counts));
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, total);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        const int32_t* cnt = reinterpret_cast<const int32_t*>(d + o_cnt);
+        ViewJob j{};
+        j.w = w; j.h = h; j.prow = prow; j.plane_pitch = (int64_t)plane;
+        j.bits = reinterpret_cast<const uint64_t*>(d); j.overlay = reinterpret_cast<uint64_t*>(d + o_ov); j.frames = nullptr;
+        j.n = 1; j.vw = vw; j.vh = vh; j.flags = flags;
+        j.out = d + o_out; j.out_stride = 3 * vw; j.out_pitch = (int64_t)3 * vw * vh;
+        j.lists = ViewLists{reinterpret_cast<const rmcv_lightblob*>(d + o_blobs), cnt, reinterpret_cast<const rmcv_armour*>(d + o_arm), cnt + 1,
+                            reinterpret_cast<const rmcv_point*>(d + o_pts), nullptr, nullptr, cnt + 3, nullptr, cnt + 2,
+                            reinterpret_cast<const int32_t*>(d + o_offs), n_blobs, n_armours, n_pts, n_neg, 1};
+        e = launch_view(j, c->stream);
+    }
+    c->last_what = "k_view_overlay + k_view_resize";
+    int rcw = 0;
+    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_view_resize");
+    if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(out, out_stride, d + o_out, (size_t)3 * vw, (size_t)3 * vw, vh, hipMemcpyDeviceToHost);
+    if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernels may still be using it)
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_debug_view", e);
+    return rcw;
 }
 
 } // extern "C"

@@ -266,6 +266,52 @@ hipError_t launch_pack_contours(const Geom& g, const Bufs& b, const Limits& lim,
                                 int32_t* d_hdr /* nullable: frame 0's {n_contours, n_points, status} */, hipStream_t s, const ExportArgs* ex = nullptr); // ex: frame 0's workgroup also exports (one-frame chains)
 hipError_t launch_gather3(const int32_t* a, const int32_t* b, const int32_t* c, int32_t* d_out, hipStream_t s); // d_out[0..2] = *a, *b, *c
 
+// ---- the operator's debug view (k_view.hip) ----
+// Where the lists of the frames to draw are: the batch tables (frame f's rows of Bufs), or -- csr -- ONE frame's lists as the stage-wise
+// helper uploads them (the negatives as CSR: neg_offs has n_neg + 1 entries, points holds the contours back to back)
+struct ViewLists {
+    const rmcv_lightblob* blobs; // [frame][max_blobs]
+    const int32_t* n_blobs;      // [frame]
+    const rmcv_armour* armours;  // [frame][max_armours]
+    const int32_t* n_armours;    // [frame]
+    const rmcv_point* points;    // [frame][max_points]
+    const int32_t* cont_start;   // [frame][max_contours]  (discovery order; unused with csr)
+    const int32_t* cont_len;
+    const int32_t* n_contours;   // [frame]
+    const int32_t* neg_idx;      // [frame][max_contours]  findContours indices (unused with csr)
+    const int32_t* n_neg;        // [frame]
+    const int32_t* neg_offs;     // csr only
+    int max_blobs, max_armours, max_points, max_contours, csr;
+};
+// n views of vw x vh: view k is of frame frames[k] (device memory; null: frame k), drawn through overlay planes [n][2][plane_pitch]
+struct ViewJob {
+    int w, h, prow;              // the frames' extent (a windowed batch: the window's) and their planes' padded row
+    int64_t plane_pitch;
+    const uint64_t* bits;        // [frame] Bufs::bits
+    uint64_t* overlay;
+    const int32_t* frames;
+    int n, vw, vh, flags;
+    uint8_t* out;
+    int out_stride;
+    int64_t out_pitch;
+    ViewLists lists;
+};
+// k_view_overlay + k_view_resize on `s`; every argument has been checked by the caller
+hipError_t launch_view(const ViewJob& j, hipStream_t s);
+// the stages a view with `flags` reads the results of
+inline int view_stages_needed(int flags)
+{
+    return RMCV_STAGE_BINARY | ((flags & (RMCV_VIEW_BLOBS | RMCV_VIEW_NEGATIVES)) ? RMCV_STAGE_CONTOURS | RMCV_STAGE_BLOBS : 0) |
+           ((flags & RMCV_VIEW_ARMOURS) ? RMCV_STAGE_CONTOURS | RMCV_STAGE_BLOBS | RMCV_STAGE_ARMOURS : 0);
+}
+// (the view entry points of a context: rmcv_host.hip)
+// what a pipeline needs of them: everything n views need allocated now (blocking); the check of a request against the context's limits;
+// and the enqueue itself on frames the caller has bound and run, the frame list already on the device, nothing blocking
+int ctx_view_prepare(rmcv_ctx* c, int n);
+// (frames: host values; n_frames / stages: the batch the views are of and the stages it has been, or will be, through)
+int ctx_view_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int flags, int out_stride, int64_t out_pitch);
+int ctx_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s);
+
 // ---- what rmcv_pipeline.hip needs of a context beyond the public ABI (rmcv_host.hip) ----
 // external order: the pipeline chains a context's launches with its own events (it knows which stream ran what), so the context
 // does not record / wait for its own ordering event around every launch (two HIP calls per launch); rmcv_batch_sync and the getters

@@ -38,6 +38,9 @@ struct Slot {
     hipStream_t stream = nullptr; // the stream the slot's record was finished on
     int frames = 0, ctx = 0;      // of its batch: frames, and the context it ran in
     bool lean = false;            // its batch's sparse stage ran the lean build (every frame of its record reports the mid tier)
+    // debug views (rmcv_pipeline_set_views): the slot's buffer, and what its batch rendered into it (view_n == 0: nothing)
+    uint8_t* d_views = nullptr;
+    int view_n = 0, view_w = 0, view_h = 0;
 };
 
 // what a submit asks for: each rmcv_pipeline_submit* fills one -- what every submit has by position (down to `stages`), the rest by name
@@ -90,6 +93,7 @@ struct rmcv_pipeline {
         RunPlan plan{};         // the context's options, the pixel shape submit chose, SPARSE_LEAN in dense mode
         int sparse = 0;         // its stages behind the pixel stage
         hipStream_t B = nullptr;
+        bool views = false;     // debug views are rendered behind its sparse stage
     } pend;
     rmcv_pipeline_hook hook = nullptr; // ... or the built-in gather hook
     void* hook_user = nullptr;
@@ -105,6 +109,11 @@ struct rmcv_pipeline {
     const void* cam_idx = nullptr;     // rmcv_pipeline_set_frame_cameras: the frames' camera indices (device, borrowed), for every pose submit
     int cam_frames = 0;
     double max_submit_us = 0;          // the longest single submit call (host time) since rmcv_pipeline_reset_stats
+    // rmcv_pipeline_set_views: every following batch renders these frames behind its sparse stage (n == 0: off)
+    struct Views {
+        int n = 0, vw = 0, vh = 0, flags = 0, max_index = 0, need = 0; // need: the stages the flags read the results of
+        int32_t* d_frames = nullptr;   // [n] the frame list, on the device
+    } views;
     char err[256] = {0};
 };
 
@@ -175,6 +184,7 @@ static void slot_destroy(Slot& s) // (a slot of a pipeline whose creation failed
     if (s.d_rec) hipFree(s.d_rec);
     if (s.d_recv) hipFree(s.d_recv);
     if (s.h_rec) hipHostFree(s.h_rec);
+    if (s.d_views) hipFree(s.d_views);
 }
 // what the slot's record, in its host mirror, says of its batch
 static RecordReport slot_report(const rmcv_pipeline* pl, const Slot& s) { return record_report(reinterpret_cast<const uint32_t*>(s.h_rec)[pl->rec.report_word]); }
@@ -215,6 +225,7 @@ void rmcv_pipeline_destroy(rmcv_pipeline* pl)
     }
     for (auto c : pl->ring) rmcv_ctx_destroy(c);
     for (auto& s : pl->slots) slot_destroy(s);
+    if (pl->views.d_frames) hipFree(pl->views.d_frames);
     if (pl->ev_gather) hipEventDestroy(pl->ev_gather);
     for (auto streams : {&pl->pix, &pl->sp, &pl->dn})
         for (auto s : *streams) if (s) hipStreamDestroy(s);
@@ -416,6 +427,15 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
         }
         if (rc) return cfail(pl, P.c, rc);
     }
+    // the debug views: behind the sparse stage (they read its tables), in front of ev_free (they read the pixel stage's bit planes)
+    S.view_n = 0;
+    if (P.views) {
+        const rmcv_pipeline::Views& V = pl->views; // (as at the submit: rmcv_pipeline_set_views drains first)
+        rc = ctx_view_enqueue(P.c, V.d_frames, V.n, V.vw, V.vh, V.flags, S.d_views, 3 * V.vw, (int64_t)3 * V.vw * V.vh, T);
+        if (rc) return cfail(pl, P.c, rc);
+        pl->last_what = "k_view_resize";
+        S.view_n = V.n, S.view_w = V.vw, S.view_h = V.vh;
+    }
     PCHK(pl, hipEventRecord(S.ev_free, T), "pipeline: mark the pixel outputs' last reader");
     // the record is rewritten: a reader on another stream (the hook's) must be through; readers on B are by stream order
     if (S.ev_hook) {
@@ -469,6 +489,10 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
     if (q.trk)
         if (const char* no = tracked_refusal(tracker_device(q.trk), pl->device, tracker_config(q.trk), q.n_frames, q.w, q.h, stages, q.d_packets != nullptr, attitude))
             return pfail(pl, RMCV_ERR_BAD_ARG, no);
+    if (pl->views.n) { // (with no views set: nothing here, and nothing further down)
+        if (q.n_frames <= pl->views.max_index) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch has fewer frames than the debug views name (rmcv_pipeline_set_views)");
+        if ((stages & pl->views.need) != pl->views.need) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch's stages lack what the debug views' flags need (rmcv_pipeline_set_views)");
+    }
     hipSetDevice(pl->device);
     int rc = finish_back(pl, false); // the batch before this one: a pixel launch follows it
     if (rc) return rc;
@@ -564,7 +588,7 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
     PCHK(pl, hipStreamWaitEvent(B, S.ev_bin, 0), "pipeline: chain the sparse stages");
     pl->next_ticket = t + 1;
     if (ticket) *ticket = t;
-    pl->pend = {true, t, q, *q.p, lp ? *lp : rmcv_legacy_params{}, k, c, used, plan, sparse, B};
+    pl->pend = {true, t, q, *q.p, lp ? *lp : rmcv_legacy_params{}, k, c, used, plan, sparse, B, pl->views.n > 0};
     pl->pend.req.p = &pl->pend.p; // (the caller's params live as long as its call)
     pl->pend.req.lp = lp ? &pl->pend.lp : nullptr;
     // (a hook or the gather hands the record to a consumer the pipeline does not see waiting: its batches are finished here and now)
@@ -732,6 +756,57 @@ int rmcv_pipeline_record(rmcv_pipeline* pl, uint64_t ticket, void** d_record, vo
     if (!s) return RMCV_ERR_BAD_ARG;
     if (d_record) *d_record = s->d_rec;
     if (hip_stream) *hip_stream = s->stream;
+    return RMCV_OK;
+}
+
+int rmcv_pipeline_set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags)
+{
+    if (!pl || n < 0) return RMCV_ERR_BAD_ARG;
+    hipSetDevice(pl->device);
+    // the slots' buffers may be replaced: everything submitted so far is through first (this call may block; no submit does)
+    int rc = rmcv_pipeline_drain(pl);
+    if (rc) return rc;
+    if (n == 0) {
+        pl->views.n = 0;
+        return RMCV_OK;
+    }
+    rmcv_ctx* c0 = pl->ring[0];
+    if ((rc = ctx_view_check(c0, frames, n, pl->lim.max_frames, ~0, vw, vh, flags, 3 * vw, (int64_t)3 * vw * vh))) return cfail(pl, c0, rc);
+    pl->views.n = 0; // (off, should anything below fail)
+    for (auto c : pl->ring)
+        if ((rc = ctx_view_prepare(c, n))) return cfail(pl, c, rc);
+    const size_t bytes = (size_t)n * 3 * vw * vh;
+    hipError_t e = hipSuccess;
+    for (auto& S : pl->slots) {
+        if (S.d_views) (void)hipFree(S.d_views);
+        S.d_views = nullptr;
+        S.view_n = 0;
+        if (e == hipSuccess) e = hipMalloc((void**)&S.d_views, bytes);
+    }
+    if (pl->views.d_frames) (void)hipFree(pl->views.d_frames);
+    pl->views.d_frames = nullptr;
+    if (e == hipSuccess) e = hipMalloc((void**)&pl->views.d_frames, (size_t)n * 4);
+    if (e == hipSuccess) e = hipMemcpy(pl->views.d_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return pfail(pl, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_pipeline_set_views", e);
+    int top = 0;
+    for (int k = 0; k < n; k++) top = frames[k] > top ? frames[k] : top;
+    pl->views.vw = vw, pl->views.vh = vh, pl->views.flags = flags, pl->views.max_index = top;
+    pl->views.need = view_stages_needed(flags);
+    pl->views.n = n;
+    return RMCV_OK;
+}
+
+int rmcv_pipeline_views(rmcv_pipeline* pl, uint64_t ticket, void** d_views, int32_t* stride, int64_t* pitch, int32_t* n)
+{
+    if (!pl) return RMCV_ERR_BAD_ARG;
+    if (const int rcb = finish_newest(pl, ticket)) return rcb;
+    const Slot* s = live_slot(pl, ticket);
+    if (!s) return RMCV_ERR_BAD_ARG;
+    if (!s->view_n) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_views: the ticket's batch was submitted without views");
+    if (d_views) *d_views = s->d_views;
+    if (stride) *stride = 3 * s->view_w;
+    if (pitch) *pitch = (int64_t)3 * s->view_w * s->view_h;
+    if (n) *n = s->view_n;
     return RMCV_OK;
 }
 

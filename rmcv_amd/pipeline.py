@@ -153,6 +153,27 @@ class Pipeline:
         n = self._n[int(ticket) % self.depth]
         return out[:tot.value].copy(), offs[:n + 1].copy()
 
+    # ------------------------------------------------------------------ the operator's debug views
+    def set_views(self, frames, size=(1024, 768), flags=abi.VIEW_ALL):
+        """from the next submit on, every batch renders the debug images of `frames` (indices into the batch) at size = (vw, vh) behind its
+        sparse stage, into its slot's own buffer (rmcv_pipeline_set_views: allocates and drains HERE; no submit blocks).  frames empty or
+        None: off."""
+        fr = np.ascontiguousarray(frames if frames is not None else [], np.int32).reshape(-1)
+        self._chk(self._lib.rmcv_pipeline_set_views(self._h, ptr(fr) if len(fr) else None, len(fr), int(size[0]), int(size[1]), int(flags)))
+
+    def views(self, ticket):
+        """the views of a ticket's batch as a torch uint8 tensor [n, vh, vw, 3] OVER the slot's device buffer (no copy): complete once the
+        ticket has been waited for, valid until ticket + depth is submitted"""
+        import torch
+        d, stride, pitch, n = C.c_void_p(), C.c_int32(0), C.c_int64(0), C.c_int32(0)
+        self._chk(self._lib.rmcv_pipeline_views(self._h, int(ticket), C.addressof(d), C.addressof(stride), C.addressof(pitch), C.addressof(n)))
+        vw = stride.value // 3
+        vh = pitch.value // stride.value
+
+        class _Span:  # what torch needs to see device memory it does not own
+            __cuda_array_interface__ = {"shape": (n.value, vh, vw, 3), "typestr": "|u1", "data": (d.value, False), "version": 2, "strides": None}
+        return torch.as_tensor(_Span(), device="cuda:%d" % self.device)
+
     def set_hot_contexts(self, n):
         """rmcv_pipeline_config::hot_contexts from the next submit on (0: off)"""
         self._chk(self._lib.rmcv_pipeline_set_hot_contexts(self._h, int(n)))
