@@ -1098,6 +1098,106 @@ int rmcv_pipeline_set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int
  * never issued, its slot has been reused, or it was submitted without views. */
 int rmcv_pipeline_views(rmcv_pipeline* pl, uint64_t ticket, void** d_views, int32_t* stride, int64_t* pitch, int32_t* n);
 
+/* ---- the session recorder: rm::debug::logger (include/debug.h:13-29, src/debug.cpp:9-41) for frames resident in HBM ----
+ * The reference records every frame the detector saw, losslessly (FFV1), with a `data` record per frame.  Here chosen frames of every batch
+ * are packed losslessly ON THE DEVICE into a ring of the last `slots` batches, together with what is needed to run the batch again; the
+ * ring is downloaded, saved, loaded and replayed bit for bit.  deviation: the packed format is this library's (below), not FFV1 / AVI.
+ *
+ * The packed form of a plane of h rows of w_bytes bytes with a byte lag of 1 .. 4 (the distance to the previous sample of the same kind:
+ * 3 for BGR, 2 for an 8-bit Bayer mosaic, 4 for Bayer in 2-byte samples, 1 otherwise), S = ceil(w_bytes / 256) segments of 256 bytes a row
+ * (the last one extended with virtual bytes of raw value 0 and residual 0 that are never read):
+ *   per segment: b_raw = the bit length of its greatest byte; b_pred = the bit length of its greatest z, where for byte i of the row
+ *   r = (v[i] - (i >= lag ? v[i - lag] : 0)) mod 256 and z = ((s << 1) ^ (s >> 7)) & 0xFF with s = r as int8; raw mode with b = b_raw if
+ *   b_raw <= b_pred, predicted mode with b = b_pred otherwise; header byte b | mode_predicted << 4; payload 32 b bytes: for j < b
+ *   (outermost), k < 4: one little-endian u64 whose bit L is bit j of the coded value (v or z) of the segment's byte 4 L + k
+ *   a frame: h S header bytes (row-major), zeros to a multiple of 8 | h + 1 u32 offsets of the rows' first segments from the start of the
+ *   payload area (entry h: its size), zeros to a multiple of 8 | the payloads in segment order
+ * rmcv_pack_bound: the size with b = 8 everywhere.  An all-zero plane packs to the header and the table alone. */
+int64_t rmcv_pack_bound(int w_bytes, int h);
+/* host-side (no device).  pack: *size = the packed size; RMCV_ERR_CAPACITY when cap is smaller (*size then says what is needed, or the
+ * bound where that is not known yet).  unpack: RMCV_ERR_BAD_ARG for a buffer whose header, row table or size do not agree with w_bytes, h
+ * and len -- it never reads outside packed[0 .. len) -- and bytes beyond w_bytes of a destination row are left alone. */
+int rmcv_pack_host(const uint8_t* src, int w_bytes, int h, int64_t stride, int lag, uint8_t* out, int64_t cap, int64_t* size);
+int rmcv_unpack_host(const uint8_t* packed, int64_t len, int w_bytes, int h, int lag, uint8_t* dst, int64_t stride);
+/* device-side, asynchronous on hip_stream, nothing allocated: n frames (rows `stride` >= w_bytes apart, frames `pitch` apart) -> n packed
+ * frames out_pitch >= rmcv_pack_bound apart (d_out and out_pitch multiples of 8), their sizes in d_sizes[n] (int64, device).  n <= 65535. */
+int rmcv_pack_frames(int device, const void* d_frames, int n, int w_bytes, int h, int stride, int64_t pitch, int lag, void* d_out,
+                     int64_t out_pitch, int64_t* d_sizes, void* hip_stream);
+/* the inverse: packed frames in_pitch apart -> frames.  A packed frame that points outside its in_pitch bytes is left unfinished. */
+int rmcv_unpack_frames(int device, const void* d_packed, int n, int w_bytes, int h, int64_t in_pitch, int lag, void* d_frames, int stride,
+                       int64_t pitch, void* hip_stream);
+
+#define RMCV_RECORDER_MAX_FRAMES 64
+typedef struct rmcv_recorder rmcv_recorder;
+typedef struct rmcv_session rmcv_session;
+typedef struct rmcv_recorder_config {
+    int32_t slots;       /* batches the ring holds                                (default 8)          */
+    int32_t max_frames;  /* chosen frames of a batch, <= RMCV_RECORDER_MAX_FRAMES (default 8)          */
+    int32_t max_w_bytes; /* bytes of a row                                        (default 3 * 1280)   */
+    int32_t max_h;       /*                                                       (default 1024)       */
+    int32_t user_bytes;  /* capacity of the user blob                             (default 256)        */
+    int32_t _reserved;
+} rmcv_recorder_config;
+/* what the host knows of a recorded batch at its submit, plus what the device reported of it */
+typedef struct rmcv_record_entry {
+    uint64_t ticket;       /* the pipeline's ticket; a stand-alone record: == sequence */
+    uint64_t sequence;     /* batches recorded before this one; the slot is sequence mod slots */
+    int64_t timestamp;     /* a tracked submit's */
+    int32_t n_frames;      /* frames recorded */
+    int32_t batch_frames;  /* frames of the batch they were chosen from */
+    int32_t w, h;          /* pixels of a frame (a stand-alone record: w = w_bytes) */
+    int32_t w_bytes, stride; /* bytes of a row as recorded; bytes between the rows of the frames as submitted */
+    int32_t lag, input_format, sample_bits, valid_bit, orient, stages;
+    int32_t win_w, win_h;  /* a windowed batch's window (0: whole frames) */
+    int32_t has_keys;      /* keys[] holds the batch's effective per-frame detection keys (rmcv_batch_get_frame_keys), camps[] the raw camps */
+    int32_t has_origins;   /* origins[] holds the batch's effective window origins (rmcv_batch_get_windows) */
+    int32_t user_bytes, _pad;
+    rmcv_params params;
+    int32_t frames[RMCV_RECORDER_MAX_FRAMES];   /* indices into the batch */
+    int64_t sizes[RMCV_RECORDER_MAX_FRAMES];    /* packed sizes */
+    int32_t keys[RMCV_RECORDER_MAX_FRAMES][4];
+    int32_t camps[RMCV_RECORDER_MAX_FRAMES];    /* with has_keys: the frames' raw camps (what blobs' targets and the pairing compare against) */
+    rmcv_point origins[RMCV_RECORDER_MAX_FRAMES];
+} rmcv_record_entry;
+void rmcv_default_recorder_config(rmcv_recorder_config* c);
+/* allocates the ring (slots x max_frames areas of rmcv_pack_bound(max_w_bytes, max_h) bytes, and the small tables); 0 in a field = default */
+int rmcv_recorder_create(int device, const rmcv_recorder_config* cfg, rmcv_recorder** out);
+void rmcv_recorder_destroy(rmcv_recorder* rec);
+const char* rmcv_recorder_last_error(const rmcv_recorder* rec);
+/* the user blob of the NEXT batch recorded (and every one after it, until set again): the `data` of logger::write */
+int rmcv_recorder_set_user(rmcv_recorder* rec, const void* data, int bytes);
+/* stand-alone: pack frames[0 .. n) (indices; NULL: 0 .. n - 1) of device frames into the next slot, asynchronously on hip_stream; the
+ * frames must stay as they are until the stream has passed.  Frozen: RMCV_OK, nothing recorded. */
+int rmcv_recorder_record(rmcv_recorder* rec, const void* d_frames, int w_bytes, int h, int stride, int64_t pitch, int lag, const int32_t* frames,
+                         int n, void* hip_stream);
+/* while frozen nothing is recorded and nothing is overwritten */
+int rmcv_recorder_freeze(rmcv_recorder* rec);
+int rmcv_recorder_resume(rmcv_recorder* rec);
+/* readers: each waits for the packing of what it reads, with a 5 s deadline (RMCV_ERR_TIMEOUT).  i = 0 is the oldest batch held.
+ * user_out (nullable): the first min(user_cap, entry->user_bytes) bytes of the blob.  frame: the packed bytes only (*size of them). */
+int rmcv_recorder_count(rmcv_recorder* rec, int32_t* n);
+int rmcv_recorder_entry(rmcv_recorder* rec, int i, rmcv_record_entry* entry, void* user_out, int user_cap);
+int rmcv_recorder_frame(rmcv_recorder* rec, int i, int k, void* out, int64_t cap, int64_t* size);
+int rmcv_recorder_device_frame(rmcv_recorder* rec, int i, int k, void** d_packed, int64_t* size);
+/* the ring as a session file (little-endian, magic, version), oldest batch first; an existing file is replaced */
+int rmcv_recorder_save(rmcv_recorder* rec, const char* path);
+/* one host-packed batch behind what a session file holds (created when missing): what rm::debug::logger::write does.  No device. */
+int rmcv_session_append(const char* path, const rmcv_record_entry* entry, const void* user, const uint8_t* const* packed);
+/* a session file, host-side (no device): every length is checked against the file's size; RMCV_ERR_BAD_ARG for a truncated or
+ * inconsistent file */
+int rmcv_session_open(const char* path, rmcv_session** out);
+int rmcv_session_count(const rmcv_session* s, int32_t* n);
+int rmcv_session_entry(const rmcv_session* s, int i, rmcv_record_entry* entry, void* user_out, int user_cap);
+int rmcv_session_frame(const rmcv_session* s, int i, int k, void* out, int64_t cap, int64_t* size);
+void rmcv_session_close(rmcv_session* s);
+/* a pipeline's recorder: from the next submit of any form on, frames[0 .. n) of every batch are packed into `rec` behind the batch's pixel
+ * kernel, off the pixel streams, so that rmcv_pipeline_wait(ticket) implies the entry is complete.  This call drains; no submit blocks
+ * (rmcv_pipeline_info::host_blocking_calls stays 0).  n == 0 (or rec NULL): off -- a submit then enqueues exactly what it did before.
+ * RMCV_ERR_BAD_ARG: an index repeated, negative or beyond the pipeline's max_frames; n beyond the recorder's max_frames; another device.  A
+ * later submit whose n_frames does not reach every index, or whose rows or height are beyond the recorder's, is refused before anything
+ * is enqueued. */
+int rmcv_pipeline_set_recorder(rmcv_pipeline* pl, rmcv_recorder* rec, const int32_t* frames, int n);
+
 /* ---- device memory for hosts without HIP headers (tools/pipeline_bench.c): frames resident in HBM ------------------------------- */
 int  rmcv_device_alloc(int device, int64_t bytes, void** d_ptr);
 void rmcv_device_free(int device, void* d_ptr);

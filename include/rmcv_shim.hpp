@@ -22,6 +22,7 @@
 // rm::utils::GetROI (include/core.h:142-147), the reference's tracked-ROI helper, is here as well (where the cv:: headers know cv::Size).
 // rm::ProjectileAngle / SolveGEA / DeltaHeight / Distance (include/mobility.h) too, behind the reference's mobility.h.
 // One more addition: rm::debug::device_view, the loop's debug image of a batch frame rendered on the device (where the cv:: headers know cv::Size).
+// rm::debug::logger (include/debug.h:13-29) too, behind the reference's debug.h: the frames go into a session file, not into an AVI.
 // The legacy names of the north star are aliased at the bottom (docs/core_8h_source.html:101,114).
 //
 // Every signature mentions cv:: types, so this header only compiles where OpenCV headers exist.
@@ -30,6 +31,7 @@
 
 #include <cmath>
 #include <cstdlib>
+#include <filesystem>
 #include <stdexcept>
 #include <string>
 #include <tuple>
@@ -383,6 +385,51 @@ RMCV_SHIM_LINKAGE cv::Mat device_view(rmcv_ctx* context, int frame, const cv::Si
     if (rmcv_batch_get_debug_view(context, frame, size.width, size.height, RMCV_VIEW_ALL, view.data, (int)(size_t)view.step) != RMCV_OK)
         throw std::runtime_error(std::string("rm::debug::device_view: ") + rmcv_last_error(context));
     return view;
+}
+} // namespace debug
+#endif
+
+// ---- rm::debug::logger (include/debug.h:13-29; bodies src/debug.cpp:9-41): the member functions of the reference's own class, defined where
+// the host has included its debug.h.  deviation: write() packs the frame losslessly on the host (rmcv_pack_host) into ONE session file,
+// <current directory>/<section_id>/session.rmcv, with `data`'s bytes as the record's user blob -- no FFV1 video, no metadata.xml; FPS and
+// resolution are accepted and not needed (a record carries its frame's own size).  As in the reference the logger is read-only when the
+// section's directory already exists: write() then returns at once.  8-bit frames of one or three channels; anything else throws.
+#if defined(RMCV_DEBUG_H) && (defined(CV_VERSION) || defined(RMCV_CV_HAS_SIZE))
+namespace debug {
+RMCV_SHIM_LINKAGE logger::logger(const int64 section_id, int FPS, const cv::Size& resolution) : section_id(section_id)
+{
+    (void)FPS;
+    (void)resolution;
+    const auto path = std::filesystem::current_path() / std::to_string(section_id);
+    reading = std::filesystem::exists(path);
+    if (!reading) std::filesystem::create_directory(path);
+}
+RMCV_SHIM_LINKAGE logger::~logger() {}
+RMCV_SHIM_LINKAGE void logger::write(const cv::Mat& image, const cv::Mat& data)
+{
+    if (reading) return;
+    const int ch = image.channels();
+    if (!image.data || image.rows < 1 || image.cols < 1 || (image.type() != CV_8UC1 && image.type() != CV_8UC3))
+        throw std::invalid_argument("rm::debug::logger::write: an 8-bit frame of one or three channels");
+    const int w_bytes = image.cols * ch, lag = ch == 3 ? 3 : 1;
+    const int64_t bound = rmcv_pack_bound(w_bytes, image.rows);
+    if (bound < 0) throw std::invalid_argument("rm::debug::logger::write: the frame is too large to pack");
+    std::vector<uint8_t> packed((size_t)bound);
+    int64_t size = 0;
+    if (rmcv_pack_host(image.data, w_bytes, image.rows, (int64_t)(size_t)image.step, lag, packed.data(), bound, &size) != RMCV_OK)
+        throw std::runtime_error("rm::debug::logger::write: rmcv_pack_host failed");
+    rmcv_record_entry e{};
+    e.ticket = e.sequence = (uint64_t)frame_id;
+    e.n_frames = e.batch_frames = 1;
+    e.w = image.cols, e.h = image.rows, e.w_bytes = e.stride = w_bytes, e.lag = lag;
+    e.input_format = ch == 3 ? RMCV_INPUT_BGR : -1, e.sample_bits = 8;
+    e.user_bytes = data.data ? (int32_t)((size_t)data.rows * (size_t)data.step) : 0;
+    e.sizes[0] = size;
+    const uint8_t* frames[1] = {packed.data()};
+    const auto file = std::filesystem::current_path() / std::to_string(section_id) / "session.rmcv";
+    if (rmcv_session_append(file.string().c_str(), &e, data.data, frames) != RMCV_OK)
+        throw std::runtime_error("rm::debug::logger::write: the session file cannot be written");
+    frame_id++;
 }
 } // namespace debug
 #endif

@@ -103,6 +103,11 @@ EXPORTS = [
     "rmcv_frame_camera", "rmcv_pnp_load_cameras", "rmcv_batch_set_frame_cameras", "rmcv_batch_set_device_frame_cameras", "rmcv_batch_get_frame_cameras",
     "rmcv_pipeline_set_frame_cameras", "rmcv_tracker_set_stream_cameras", "rmcv_tracker_set_aim_configs",
     "rmcv_batch_debug_views", "rmcv_batch_get_debug_view", "rmcv_debug_view", "rmcv_debug_view_host", "rmcv_pipeline_set_views", "rmcv_pipeline_views",
+    "rmcv_pack_bound", "rmcv_pack_host", "rmcv_unpack_host", "rmcv_pack_frames", "rmcv_unpack_frames",
+    "rmcv_default_recorder_config", "rmcv_recorder_create", "rmcv_recorder_destroy", "rmcv_recorder_last_error", "rmcv_recorder_set_user", "rmcv_recorder_record",
+    "rmcv_recorder_freeze", "rmcv_recorder_resume", "rmcv_recorder_count", "rmcv_recorder_entry", "rmcv_recorder_frame", "rmcv_recorder_device_frame",
+    "rmcv_recorder_save", "rmcv_session_append", "rmcv_session_open", "rmcv_session_count", "rmcv_session_entry", "rmcv_session_frame", "rmcv_session_close",
+    "rmcv_pipeline_set_recorder",
 ]
 
 
@@ -147,6 +152,29 @@ class PipelineInfo(C.Structure):
                 ("record_bytes", C.c_int64), ("armours_offset", C.c_int64), ("submitted", C.c_uint64), ("collected", C.c_uint64),
                 ("dense_split", C.c_uint64), ("hot_batches", C.c_uint64), ("hot_contexts", C.c_int32), ("_pad2", C.c_int32), ("latency_batches", C.c_uint64),
                 ("host_blocking_calls", C.c_uint64), ("wait_timeout_ms", C.c_int32), ("_pad3", C.c_int32), ("max_submit_us", C.c_double), ("heavy_batches", C.c_uint64), ("held_back", C.c_uint64)]
+
+
+RECORDER_MAX_FRAMES = 64
+
+
+class RecorderConfig(C.Structure):
+    """rmcv_recorder_config (0 in a field = the default)"""
+    _fields_ = [("slots", C.c_int32), ("max_frames", C.c_int32), ("max_w_bytes", C.c_int32), ("max_h", C.c_int32), ("user_bytes", C.c_int32),
+                ("_reserved", C.c_int32)]
+
+
+class RecordEntry(C.Structure):
+    """rmcv_record_entry: what the host knew of a recorded batch at its submit, plus the packed sizes, keys and origins the device reported"""
+    _fields_ = [("ticket", C.c_uint64), ("sequence", C.c_uint64), ("timestamp", C.c_int64), ("n_frames", C.c_int32), ("batch_frames", C.c_int32),
+                ("w", C.c_int32), ("h", C.c_int32), ("w_bytes", C.c_int32), ("stride", C.c_int32), ("lag", C.c_int32), ("input_format", C.c_int32),
+                ("sample_bits", C.c_int32), ("valid_bit", C.c_int32), ("orient", C.c_int32), ("stages", C.c_int32), ("win_w", C.c_int32), ("win_h", C.c_int32),
+                ("has_keys", C.c_int32), ("has_origins", C.c_int32), ("user_bytes", C.c_int32), ("_pad", C.c_int32), ("params", Params),
+                ("frames", C.c_int32 * RECORDER_MAX_FRAMES), ("sizes", C.c_int64 * RECORDER_MAX_FRAMES), ("keys", (C.c_int32 * 4) * RECORDER_MAX_FRAMES),
+                ("camps", C.c_int32 * RECORDER_MAX_FRAMES),
+                ("origins", (C.c_int32 * 2) * RECORDER_MAX_FRAMES)]
+
+
+assert C.sizeof(RecordEntry) == 2712
 
 
 # rmcv_pipeline_hook: int (*)(void* user, uint64_t ticket, void* d_record, int64_t record_bytes, void* hip_stream, void** done_event)
@@ -304,6 +332,37 @@ def load(path):
         L.rmcv_batch_get_debug_view.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.rmcv_pipeline_set_views.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.rmcv_pipeline_views.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    if hasattr(L, "rmcv_pack_bound"):  # (builds from before the session recorder stay loadable for A/B runs)
+        L.rmcv_pack_bound.restype = C.c_int64
+        L.rmcv_pack_bound.argtypes = [C.c_int, C.c_int]
+        L.rmcv_pack_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        L.rmcv_unpack_host.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int64]
+        L.rmcv_pack_frames.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+        L.rmcv_unpack_frames.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+        L.rmcv_default_recorder_config.restype = None
+        L.rmcv_default_recorder_config.argtypes = [C.c_void_p]
+        L.rmcv_recorder_create.argtypes = [C.c_int, C.c_void_p, C.c_void_p]
+        L.rmcv_recorder_destroy.restype = None
+        L.rmcv_recorder_destroy.argtypes = [C.c_void_p]
+        L.rmcv_recorder_last_error.restype = C.c_char_p
+        L.rmcv_recorder_last_error.argtypes = [C.c_void_p]
+        L.rmcv_recorder_set_user.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_recorder_record.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.rmcv_recorder_freeze.argtypes = [C.c_void_p]
+        L.rmcv_recorder_resume.argtypes = [C.c_void_p]
+        L.rmcv_recorder_count.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_recorder_entry.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_recorder_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        L.rmcv_recorder_device_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.rmcv_recorder_save.argtypes = [C.c_void_p, C.c_char_p]
+        L.rmcv_session_append.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_session_open.argtypes = [C.c_char_p, C.c_void_p]
+        L.rmcv_session_count.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_session_entry.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_session_frame.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        L.rmcv_session_close.restype = None
+        L.rmcv_session_close.argtypes = [C.c_void_p]
+        L.rmcv_pipeline_set_recorder.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L

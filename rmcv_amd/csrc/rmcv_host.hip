@@ -20,6 +20,7 @@
 #include "enhance_math.h"
 #include "device_track.h"
 #include "device_view.h"
+#include "device_pack.h"
 
 using namespace rmcv;
 
@@ -242,6 +243,17 @@ int ctx_enhance(const rmcv_ctx* c) { return c->enhance; }
 int ctx_n_cameras(const rmcv_ctx* c) { return c->bufs.pnp_cams ? c->bufs.n_cameras : 0; }
 void ctx_set_frame_cameras(rmcv_ctx* c, const void* d_idx) { c->bufs.cam_req = (const int32_t*)d_idx; }
 PixelVariant ctx_pixel_variant(const rmcv_ctx* c) { return geom_variant(c->geom); }
+int ctx_frame_pixel_bytes(const rmcv_ctx* c) { return ctx_pixel_bytes(c); }
+void ctx_record_batch(const rmcv_ctx* c, RecordBatch* b)
+{
+    const Geom& g = c->geom;
+    b->input_format = g.input_format, b->sample_bits = 8 * g.sample_bytes, b->valid_bit = g.valid_bit, b->orient = g.orient;
+    b->w_bytes = g.frame_w * geom_pixel_bytes(g);
+    b->lag = pack_lag(g.input_format, b->sample_bits);
+    b->key_eff = g.keys ? c->bufs.key_eff : nullptr;
+    b->key_enemy = g.keys ? c->bufs.key_enemy : nullptr;
+    b->win_eff = g.win ? c->bufs.win_eff : nullptr;
+}
 int ctx_compact(rmcv_ctx* c, void* d_armours_out, int cap, void* d_frame_offs, void* d_status_or, hipStream_t s, void* hd_record, int host_head)
 {
     HIPCHK(c, launch_compact_armours(c->geom, c->bufs, c->lim, (rmcv_armour*)d_armours_out, cap, (int32_t*)d_frame_offs, s, (int32_t*)d_status_or, (uint8_t*)hd_record, host_head), "k_compact_armours");

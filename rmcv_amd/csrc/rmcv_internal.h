@@ -401,6 +401,61 @@ hipError_t launch_attitude(const rmcv_tracker* t, const void* d_packets, double*
 // rmcv_batch_attitude on `s` (every check before the first enqueue; never synchronises): behind the tracker's previous step, recorded as its newest
 int ctx_attitude(rmcv_ctx* c, rmcv_tracker* trk, const void* d_packets, hipStream_t s);
 
+// ---- the session recorder's frame packer (k_pack.hip) ----
+static constexpr int PACK_MAX_FRAMES = 64; // frames of one pack job (their indices travel as a kernel argument)
+struct PackIdx { int32_t f[PACK_MAX_FRAMES]; };
+// n planes of h rows of w_bytes bytes -> n packed frames, out_pitch apart (device_pack.h: the format), their sizes in sizes[n].
+// Plane k is frame idx.f[k] of `frames` when use_idx, frame k otherwise.  keys_out / origins_out (nullable): the batch's effective
+// detection keys / window origins of those frames, copied alongside by the same launches.
+struct PackJob {
+    const uint8_t* frames;
+    int64_t pitch;
+    int stride, w_bytes, h, lag, n;
+    uint8_t* out;
+    int64_t out_pitch;
+    int64_t* sizes;
+    int use_idx;
+    PackIdx idx;
+    const FrameKey* key_eff;
+    int32_t* keys_out;        // [n][4]
+    const int32_t* key_enemy; // the raw camps, with key_eff
+    int32_t* camps_out;       // [n]
+    const rmcv_point* win_eff;
+    rmcv_point* origins_out;  // [n]
+};
+// k_pack_widths + k_pack_scan + k_pack_emit on `s`; every argument has been checked by the caller (pack_job_refusal)
+hipError_t launch_pack(const PackJob& j, hipStream_t s);
+// n packed frames, in_pitch apart -> n planes; a frame whose header or row table points outside its in_pitch bytes is left unfinished, never read past
+hipError_t launch_unpack(const uint8_t* packed, int64_t in_pitch, int n, int w_bytes, int h, int lag, uint8_t* frames, int stride, int64_t pitch, hipStream_t s);
+// why the kernels cannot take this geometry and these buffers (null: they can)
+const char* pack_job_refusal(const void* frames, int n, int w_bytes, int h, int stride, int64_t pitch, int lag, const void* packed, int64_t packed_pitch);
+
+// ---- the session recorder (rmcv_record.hip) as the pipeline drives it ----
+// what a pipeline knows of a batch at its submit; everything else is the recorder's
+struct RecordBatch {
+    const void* d_frames;
+    int w, h, stride;          // the frames as bound (pixels; bytes between rows)
+    int w_bytes, lag;          // bytes of a row, and the distance to the previous sample of the same kind (device_pack.h: pack_lag)
+    int64_t pitch;
+    int batch_frames;
+    int input_format, sample_bits, valid_bit, orient;
+    int stages, win_w, win_h;
+    rmcv_params params;
+    int64_t timestamp;
+    uint64_t ticket;
+    const FrameKey* key_eff;   // device; null: per-run keys
+    const int32_t* key_enemy;  // device, with key_eff: the raw camps
+    const rmcv_point* win_eff; // device; null: whole frames
+};
+// why the recorder cannot take `n` chosen frames of this geometry (null: it can); nothing is enqueued
+const char* recorder_refusal(const rmcv_recorder* r, int device, int n, int w_bytes, int h);
+// pack frames[0 .. n) of the batch into the recorder's next slot on `s`: launches and event calls only, nothing blocks.  Frozen: nothing happens.
+int recorder_enqueue(rmcv_recorder* r, const RecordBatch& b, const int32_t* frames, int n, hipStream_t s);
+// the frames bound to a context as the recorder describes them: format, row bytes, lag, the effective key / origin tables (rmcv_host.hip)
+void ctx_record_batch(const rmcv_ctx* c, RecordBatch* b);
+// bytes of one pixel of the frames the context's options describe (what the next binding will record)
+int ctx_frame_pixel_bytes(const rmcv_ctx* c);
+
 } // namespace rmcv
 
 // the tracker behind the ABI's handle (k_track.hip owns its lifetime; k_aim.hip the aim fields)

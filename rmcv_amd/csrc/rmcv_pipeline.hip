@@ -114,6 +114,12 @@ struct rmcv_pipeline {
         int n = 0, vw = 0, vh = 0, flags = 0, max_index = 0, need = 0; // need: the stages the flags read the results of
         int32_t* d_frames = nullptr;   // [n] the frame list, on the device
     } views;
+    // rmcv_pipeline_set_recorder: every following batch packs these frames into the recorder behind its pixel kernel (n == 0: off)
+    struct Recording {
+        rmcv_recorder* rec = nullptr;
+        int n = 0, max_index = 0;
+        int32_t frames[RMCV_RECORDER_MAX_FRAMES] = {};
+    } recd;
     char err[256] = {0};
 };
 
@@ -493,6 +499,10 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
         if (q.n_frames <= pl->views.max_index) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch has fewer frames than the debug views name (rmcv_pipeline_set_views)");
         if ((stages & pl->views.need) != pl->views.need) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch's stages lack what the debug views' flags need (rmcv_pipeline_set_views)");
     }
+    if (pl->recd.n) { // (with no recorder set: nothing here, and nothing further down)
+        if (q.n_frames <= pl->recd.max_index) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch has fewer frames than the recorder's frame list names (rmcv_pipeline_set_recorder)");
+        if (const char* no = recorder_refusal(pl->recd.rec, pl->device, pl->recd.n, q.w * ctx_frame_pixel_bytes(pl->ring[0]), q.h)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
+    }
     hipSetDevice(pl->device);
     int rc = finish_back(pl, false); // the batch before this one: a pixel launch follows it
     if (rc) return rc;
@@ -586,6 +596,17 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
     S.ctx = (int)fp.j;
     PCHK(pl, hipEventRecord(S.ev_bin, A), "pipeline: mark the pixel kernel");
     PCHK(pl, hipStreamWaitEvent(B, S.ev_bin, 0), "pipeline: chain the sparse stages");
+    // the recorder: the chosen frames as delivered, and the effective keys and origins the pixel stage's prologue has just written, packed on
+    // the batch's sparse stream in front of its sparse stage -- off the pixel stream, and in front of ev_done: a wait for the ticket covers it
+    if (pl->recd.n) {
+        RecordBatch rb{};
+        rb.d_frames = q.d_frames, rb.w = q.w, rb.h = q.h, rb.stride = q.stride, rb.pitch = q.frame_pitch, rb.batch_frames = q.n_frames;
+        rb.stages = stages, rb.win_w = q.d_origins ? q.win_w : 0, rb.win_h = q.d_origins ? q.win_h : 0;
+        rb.params = *q.p, rb.timestamp = q.timestamp, rb.ticket = t;
+        ctx_record_batch(c, &rb);
+        if ((rc = recorder_enqueue(pl->recd.rec, rb, pl->recd.frames, pl->recd.n, B))) return pfail(pl, rc, rmcv_recorder_last_error(pl->recd.rec));
+        pl->last_what = "k_pack_emit";
+    }
     pl->next_ticket = t + 1;
     if (ticket) *ticket = t;
     pl->pend = {true, t, q, *q.p, lp ? *lp : rmcv_legacy_params{}, k, c, used, plan, sparse, B, pl->views.n > 0};
@@ -793,6 +814,32 @@ int rmcv_pipeline_set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int
     pl->views.vw = vw, pl->views.vh = vh, pl->views.flags = flags, pl->views.max_index = top;
     pl->views.need = view_stages_needed(flags);
     pl->views.n = n;
+    return RMCV_OK;
+}
+
+int rmcv_pipeline_set_recorder(rmcv_pipeline* pl, rmcv_recorder* rec, const int32_t* frames, int n)
+{
+    if (!pl || n < 0) return RMCV_ERR_BAD_ARG;
+    hipSetDevice(pl->device);
+    // batches in flight keep the recorder they were submitted under: everything submitted so far is through first (this call may block)
+    int rc = rmcv_pipeline_drain(pl);
+    if (rc) return rc;
+    if (n == 0 || !rec) {
+        pl->recd.n = 0, pl->recd.rec = nullptr;
+        return RMCV_OK;
+    }
+    if (!frames) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_recorder: null frame list");
+    // (the rows and the height are the batch's: checked at every submit)
+    if (const char* no = recorder_refusal(rec, pl->device, n, 1, 1)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
+    int top = 0;
+    for (int k = 0; k < n; k++) {
+        if (frames[k] < 0 || frames[k] >= pl->lim.max_frames) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_recorder: a frame index out of range");
+        for (int q = 0; q < k; q++) if (frames[q] == frames[k]) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_recorder: a frame index is repeated");
+        top = frames[k] > top ? frames[k] : top;
+    }
+    pl->recd.rec = rec, pl->recd.max_index = top;
+    for (int k = 0; k < n; k++) pl->recd.frames[k] = frames[k];
+    pl->recd.n = n;
     return RMCV_OK;
 }
 

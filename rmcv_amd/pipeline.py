@@ -174,6 +174,15 @@ class Pipeline:
             __cuda_array_interface__ = {"shape": (n.value, vh, vw, 3), "typestr": "|u1", "data": (d.value, False), "version": 2, "strides": None}
         return torch.as_tensor(_Span(), device="cuda:%d" % self.device)
 
+    # ------------------------------------------------------------------ the session recorder
+    def set_recorder(self, rec, frames):
+        """from the next submit of any form on, every batch packs `frames` (indices into the batch) losslessly into the Recorder `rec`,
+        behind its pixel kernel and off the pixel streams: wait(ticket) implies the entry is complete (rmcv_pipeline_set_recorder: drains
+        HERE; no submit blocks).  rec None or frames empty: off."""
+        fr = np.ascontiguousarray(frames if frames is not None and rec is not None else [], np.int32).reshape(-1)
+        self._chk(self._lib.rmcv_pipeline_set_recorder(self._h, rec._h if rec is not None else None, ptr(fr) if len(fr) else None, len(fr)))
+        self._recorder = rec if len(fr) else None   # (kept alive as long as batches go into it)
+
     def set_hot_contexts(self, n):
         """rmcv_pipeline_config::hot_contexts from the next submit on (0: off)"""
         self._chk(self._lib.rmcv_pipeline_set_hot_contexts(self._h, int(n)))
