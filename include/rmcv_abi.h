@@ -696,6 +696,8 @@ double rmcv_projectile_angle(double v0, double g, double d, double h);
  * reference's switch with pitch = time = 0, and does here) */
 double rmcv_solve_gea(const double tvec[3], double g, double v0, double h, float offset_x, float offset_y, double angle_offset, int mode,
                       double gea_out[2]);
+/* motor_angle (rad) is not checked, here or in rmcv_aim_input: the pinned tangent is NaN for a non-finite argument and for one of 3.37e9 rad
+ * or more (|x * 2 / pi| >= 2^31 - 1, pinned_math.h "the conversion's edge"), the same on the host and on the device, and so is the height */
 double rmcv_delta_height(const double tvec[3], double motor_angle, float offset_y, double angle_offset);
 double rmcv_distance(const double tvec[3]);
 /* a rigid 4x4 (row-major) [R t; 0 1] -> [R^T  -R^T t; 0 1]; each entry of R^T t is summed left to right.  out == m allowed. */
@@ -788,6 +790,8 @@ int  rmcv_aim_step_host(const rmcv_aim_config* cfg, double tick_frequency, const
  *  3. world2camera[f] = rmcv_rigid_inverse(B x gripper2camera), the 4x4 product's entries ((r0 c0 + r1 c1) + r2 c2) + r3 c3; motor_angle[f]
  *     stays (RMCV_ATT_MOTOR_KEEP) or becomes attitude[f].pitch (RMCV_ATT_MOTOR_PITCH);
  *  4. a valid packet with a non-finite angle runs through and comes out NaN (every NaN that leaves is the quiet NaN), as in the aim step.
+ *     So does an angle of 3.37e9 rad (1.93e11 degrees) or more: the pinned sine and cosine reduce by a quadrant number held in an int, and
+ *     where |angle * 2 / pi| >= 2^31 - 1 they return NaN on the host and on the device alike (pinned_math.h, "the conversion's edge");
  * The step is enqueued on the batch's pixel stream: in front of k_frame_keys / k_window_origins (the camps it may write are read there) and
  * behind an event wait for the tracker's previous step (the aim inputs it writes are read by that step's k_aim) -- with attitude on that
  * wait is made for whole-frame trackers (win_w == 0) too, which otherwise have none.  Nothing blocks: host_blocking_calls stays 0.

@@ -29,6 +29,22 @@
  * pm_hypot (the device tracker's Jacobi rotation) is the one function here that
  * is CORRECTLY ROUNDED, and the one that uses sqrt and the explicit fma besides:
  * see its own comment.
+ *
+ * "The same bits" is tested directly: tests/leaf/leaf_main.hip evaluates every function of this file in a trivial kernel and in hipcc's host
+ * pass, tests/leaf/leaf_host_main.c with gcc, and the three must agree bit for bit (NaNs as a class) over tests/leaf_cases.py
+ * (tests/test_leaf_cpu.py, tests/test_gpu_leaf.py).
+ *
+ * Accuracy against the TRUE value (mpmath at 200 bits, tests/test_leaf_cpu.py; the comparisons with glibc above say nothing about it).
+ * Max error measured over that case list, in ulp of the true value, and the bound the test holds it to:
+ *     pm_sin 0.79, pm_cos 0.80, pm_tan 0.75 (|x| <= 1e4), pm_acos 0.83                           below 1
+ *     pm_atan 0.74, pm_atan2 1.26, pm_log 0.78, pm_exp 1.09                                       at most 2
+ *     pm_hypot                                                                                    the correctly rounded value, always
+ *     pm_pow, all 2 011 575 pairs (i, gamma) with |g ln x| <= 700: relative error up to           (2.5 |g ln x| + 2) 2^-53, each pair
+ *       987 x 2^-53 (at |g ln x| = 600); never more than 0.842 of the pair's own bound            against its own
+ *     pm_atan2f, pm_sinf, pm_cosf: no result of 800 000 differs from the correctly rounded float  at most 1 in 2^20; none on integer
+ *                                                                                                 pairs in [-64, 64]^2 (contour points)
+ * Defined everywhere: no input makes a conversion or a shift undefined (tests/test_leaf_cpu.py runs the list under
+ * -fsanitize=undefined,float-cast-overflow); see pm_rem_pio2 for the one edge that needed a rule.
  */
 #ifndef RMCV_PINNED_MATH_H
 #define RMCV_PINNED_MATH_H
@@ -84,7 +100,12 @@ PM_FN double pm_kcos(double x, double y)
 }
 
 /* reduce x to r+t with |r| <= pi/4 (+eps); returns quadrant n mod 4.
- * Accurate for |x| < ~1e5 (n*p1 and n*p2 exact while |n| < 2^20). */
+ * Accurate for |x| < ~1e5 (n*p1 and n*p2 exact while |n| < 2^20).
+ * THE CONVERSION'S EDGE: the quadrant number is an int.  Where |x * invpio2| >= 2^31 - 1 (|x| >= ~3.37e9), and for the infinities and NaN,
+ * the conversion below would be undefined in C -- x86 gives INT_MIN there (a "sine" of 7e121), gfx950 saturates -- so the reduction refuses
+ * such an x: r and t are NaN, and pm_sin, pm_cos and pm_tan return NaN, the same on every build.  The arguments are reachable (att_decode
+ * turns any float of a CRC-valid packet into radians; rmcv_aim_input.motor_angle is unchecked), and att_canon / aim_canon carry the NaN out
+ * through the ABI.  Below the edge nothing changed: the comparison is on the product the reduction computes anyway. */
 PM_FN int pm_rem_pio2(double x, double* r_hi, double* r_lo)
 {
     const double invpio2 = 0.6366197723675814;
@@ -92,6 +113,11 @@ PM_FN int pm_rem_pio2(double x, double* r_hi, double* r_lo)
     const double p2 = 6.077100506303966e-11;    /* next 33 bits          */
     const double p3 = 2.0222662487959506e-21;   /* the rest, as a double */
     double fn = x * invpio2;
+    if (!(pm_fabs(fn) < 2147483647.0)) { /* 2^31 - 1; NaN fails the comparison too */
+        *r_hi = __builtin_nan("");
+        *r_lo = __builtin_nan("");
+        return 0;
+    }
     int n = (int)(fn < 0 ? fn - 0.5 : fn + 0.5);
     double dn = (double)n;
     double r = x - dn * p1;
@@ -169,8 +195,8 @@ PM_FN double pm_ktan(double x, double y, int odd)
     }
 }
 
-/* tan for |x| < ~1e5 (pm_rem_pio2's domain), |error| < 1 ulp; NaN and the infinities give NaN, +-0 gives +-0.  (rm::DeltaHeight,
- * src/mobility.cpp:48.) */
+/* tan for |x| < ~1e5 (pm_rem_pio2's domain), |error| < 1 ulp; NaN, the infinities and |x| >= ~3.37e9 (pm_rem_pio2: the conversion's edge)
+ * give NaN, +-0 gives +-0.  (rm::DeltaHeight, src/mobility.cpp:48.) */
 PM_FN double pm_tan(double x)
 {
     double r, t;
@@ -225,7 +251,8 @@ PM_FN double pm_atan(double x)
 }
 
 /* atan2 for finite arguments (infinities/NaN are not produced on this path;
- * they are still mapped to something sensible). */
+ * they are still mapped to something sensible).  Within 2 ulp of the true value (a correctly rounded quotient, pm_atan below 1 ulp, one
+ * final subtraction; 1.26 measured) -- the "<= 1 ulp" of tests/test_pinned_math.py is the distance to glibc's result, not to the truth. */
 PM_FN double pm_atan2(double y, double x)
 {
     const double pi = 3.1415926535897931160e+00, pi_lo = 1.2246467991473531772e-16;
@@ -299,7 +326,11 @@ PM_FN float pm_atan2f(float y, float x) { return (float)pm_atan2((double)y, (dou
 PM_FN float pm_sinf(float x) { return (float)pm_sin((double)x); }
 PM_FN float pm_cosf(float x) { return (float)pm_cos((double)x); }
 
-/* fmod(x, 180) for 0 <= x < 720 -- each subtraction is exact (Sterbenz) */
+/* fmod(x, 180) for 0 <= x < 720 -- each subtraction is exact (Sterbenz).  NaN comes back at once.  NOTHING ELSE MAY REACH IT: the loop
+ * does not end for +infinity and runs ~1e298 times for 1e300 -- on a GPU that is a hang.  Its two callers (device_fit.h, direct_finish) pass
+ * theta * 180 / pi and 90 + theta * 180 / pi, where theta is 0, pi / 2 or pi / 2 + 0.5 * pm_atan2(..): pm_atan2 returns a value in
+ * [-pi, pi] or NaN for EVERY input (pm_atan is bounded by its hi + lo constants), so theta is in [0, pi] or NaN and the argument is below
+ * 270.000001 or NaN. */
 PM_FN double pm_fmod180(double x)
 {
     while (x >= 180.0) x -= 180.0;
@@ -310,26 +341,34 @@ PM_FN double pm_fmod180(double x)
  * pow(x, g) = exp(g * log(x)) for finite x > 0 (normal) and EVERY finite g, with pow(x, 0) = 1 and pow(0, g > 0) = 0; a result below
  * the normal range is 0 (pm_exp), so the table of a huge gamma is 0 .. 0 255, as the host libm's is.
  * log: x = 2^k m, m in [sqrt(1/2), sqrt(2)), log m = 2 atanh(s), s = (m - 1) / (m + 1), |s| <= 0.1716 (the odd series to s^23);
- * exp: y = n ln2 + r, |r| <= 0.347 (Cody-Waite in two pieces, Taylor to r^13).  Both kernels are good to ~1 ulp; the product
- * g * log(x) (up to 51 for the table's arguments) carries its rounding into the exponent, so the result's relative error is up to
- * ~1e-14 -- the table needs 1e-9 (no pow(..) * 255 of the contract's gammas comes closer than 3e-7 to a rounding tie;
- * tests/test_enhance_cpu.py compares all 256 entries with the host libm's for every such gamma). */
+ * exp: y = n ln2 + r, |r| <= 0.347 (Cody-Waite in two pieces, Taylor to r^13).
+ * log is below 1 ulp of the true value (0.78 measured; its sum starts from the exact m - 1, see the function), exp within 2 (1.09
+ * measured); the product g * log(x) (up to 51 for the table's arguments) carries its rounding into the exponent, so the result's
+ * relative error is up to (2.5 |g ln x| + 2) 2^-53 (tests/test_leaf_cpu.py), ~1.4e-14 for the table -- the table needs 1e-9 (no
+ * pow(..) * 255 of the contract's gammas comes closer than 3e-7 to a rounding tie; tests/test_enhance_cpu.py compares all 256 entries
+ * with the host libm's for every such gamma). */
 PM_FN double pm_log(double x)
 {
     const double ln2_hi = 6.93147180369123816490e-01, ln2_lo = 1.90821492927058770002e-10;
     uint64_t u;
     int k;
-    double m, s, z, p;
+    double m, f, s, z, p, hfsq, dk;
     __builtin_memcpy(&u, &x, 8);
     k = (int)(u >> 52) - 1023;
     u = (u & 0x000FFFFFFFFFFFFFull) | 0x3FF0000000000000ull;
     __builtin_memcpy(&m, &u, 8);
     if (m > 1.4142135623730951) { m = m * 0.5; k = k + 1; }
-    s = (m - 1.0) / (m + 1.0);
+    f = m - 1.0; /* exact */
+    s = f / (2.0 + f);
     z = s * s;
     p = z * (1.0 / 3.0 + z * (1.0 / 5.0 + z * (1.0 / 7.0 + z * (1.0 / 9.0 + z * (1.0 / 11.0 + z * (1.0 / 13.0 + z * (1.0 / 15.0 +
         z * (1.0 / 17.0 + z * (1.0 / 19.0 + z * (1.0 / 21.0 + z * (1.0 / 23.0)))))))))));
-    return (double)k * ln2_hi + ((2.0 * s + 2.0 * s * p) + (double)k * ln2_lo);
+    /* log m = 2 s + 2 s p, and 2 s = f - f^2 / 2 + s f^2 / 2: summed from the exact f, so that the rounding of s reaches only the small
+     * terms (the classical arrangement; 2 s + 2 s p itself lost up to 1.9 ulp where k ln2 cancels half of it) */
+    hfsq = 0.5 * f * f;
+    dk = (double)k;
+    if (k == 0) return f - (hfsq - s * (hfsq + 2.0 * p));
+    return dk * ln2_hi - ((hfsq - (s * (hfsq + 2.0 * p) + dk * ln2_lo)) - f);
 }
 
 /* exp for every y that is not NaN: 0 below -708 (there the result leaves the normal range; its one caller rounds anything below

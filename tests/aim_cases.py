@@ -91,3 +91,14 @@ def aim_inputs(n):
         a[k]["world2camera"] = np.eye(4) if k == 0 else abi.rigid_inverse(rigid(0.05 * k, -0.1 + 0.03 * k, (5.0 * k, -3.0, 12.0 + k)))
         a[k]["motor_angle"] = 0.04 * k
     return a
+
+
+HUGE_MOTOR_ANGLE = 1e12
+
+
+def aim_inputs_huge(n):
+    """aim_inputs(n) with a motor angle beyond the range of pm_rem_pio2's quadrant number (rmcv_aim_input.motor_angle is unchecked): under
+    RMCV_AIM_HEIGHT_DELTA the tangent, and with it the height and the pitch, is NaN on every build"""
+    a = aim_inputs(n)
+    a["motor_angle"] = HUGE_MOTOR_ANGLE
+    return a

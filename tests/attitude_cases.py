@@ -6,8 +6,8 @@ import numpy as np
 
 from rmcv_amd import CAMP_BLUE, CAMP_RED, abi
 
-KINDS = ("valid_red", "valid_blue", "bad_header", "bad_payload", "bad_crc", "valid_upper_bits", "valid_nan", "valid_large")
-VALID = {"valid_red": CAMP_RED, "valid_blue": CAMP_BLUE, "valid_upper_bits": CAMP_BLUE, "valid_nan": CAMP_RED, "valid_large": CAMP_BLUE}
+KINDS = ("valid_red", "valid_blue", "bad_header", "bad_payload", "bad_crc", "valid_upper_bits", "valid_nan", "valid_large", "valid_huge")
+VALID = {"valid_red": CAMP_RED, "valid_blue": CAMP_BLUE, "valid_upper_bits": CAMP_BLUE, "valid_nan": CAMP_RED, "valid_large": CAMP_BLUE, "valid_huge": CAMP_RED}
 
 
 def py_crc8(data):
@@ -44,6 +44,9 @@ def packet(kind, rng):
         return py_packet(0x81, yaw, float("nan"), roll, filler)    # a valid packet with a non-finite angle runs through
     if kind == "valid_large":
         return py_packet(0, 1e4, -1e4, 720.0, filler)
+    if kind == "valid_huge":
+        # radians beyond the range of pm_rem_pio2's quadrant number (an int): the sines and cosines are NaN on every build (pinned_math.h)
+        return py_packet(1, 1e12, -1e12, 3.4028234663852886e38, filler)
     good = bytearray(py_packet(1, yaw, pitch, roll, filler))
     if kind == "bad_header":
         good[0] ^= 0x10

@@ -215,30 +215,33 @@ def scenario_lists():
     return out
 
 
-def step_cases(scenario_lists):
-    """(label, tracks, now, aim input | None)"""
+def step_cases(scenario_lists, huge=False):
+    """(label, tracks, now, aim input | None); huge: the seeded lists once more with the motor angle of K.aim_inputs_huge"""
     inputs = K.aim_inputs(3)
     for name, k, tr, ts in scenario_lists:
         yield "%s[%d]" % (name, k), tr, ts + (k % 3) * 4 * K.MS, (None if k % 2 else inputs[1 + k % 2:2 + k % 2])
     for name, tr in sorted(K.lists().items()):
-        for i in (None, inputs[1:2], inputs[2:3]):
+        for i in (None, inputs[1:2], inputs[2:3]) + ((K.aim_inputs_huge(3)[1:2],) if huge else ()):
             yield name, tr, K.NOW, i
 
 
 def test_step_host_equals_the_reference_byte_for_byte(scenario_lists):
-    seen = {"target": 0, "none": 0, "nosol": 0, "nan": 0, "led": 0}
+    seen = {"target": 0, "none": 0, "nosol": 0, "nan": 0, "led": 0, "huge": 0}
     cfgs = K.configs()
-    for label, tr, now, inp in step_cases(scenario_lists):
+    for label, tr, now, inp in step_cases(scenario_lists, huge=True):
         pair = None if inp is None else (inp[0]["world2camera"], float(inp[0]["motor_angle"]))
         for cname, cfg in cfgs.items():
             got = Tracker.aim_host(cfg, K.TICK, tr, now, pair)
             ref, _ = R.step(cfg, K.TICK, tr, now, inp)
             assert got.tobytes() == ref.tobytes(), (label, cname, got, ref)
+            if pair is not None and pair[1] == K.HUGE_MOTOR_ANGLE and cfg.height_mode == abi.AIM_HEIGHT_DELTA and got["track"] >= 0:
+                assert np.isnan(got["pitch"]), (label, cname, got)          # the tangent of 1e12 is NaN, not a number from an undefined conversion
+                seen["huge"] += 1
             seen["none"] += got["status"] == abi.AIM_NO_TARGET
             seen["target"] += got["track"] >= 0
             seen["nosol"] += got["status"] == abi.AIM_NO_SOLUTION
             seen["nan"] += bool(np.isnan(got["point"]).any())
-    assert all(seen[k] > 0 for k in ("target", "none", "nosol", "nan")), seen
+    assert all(seen[k] > 0 for k in ("target", "none", "nosol", "nan", "huge")), seen
 
 
 def test_step_corners():

@@ -87,6 +87,20 @@ def test_euler_to_matrix_and_homogeneous_equal_the_reference_bytes():
             assert h[3].tolist() == [0, 0, 0, 1] and h[:3, 3].tolist() == ([0, 0, 0] if tr is None else t.tolist())
 
 
+def test_angles_beyond_the_quadrant_number_come_out_nan():
+    """a CRC-valid packet may carry any float: from 1.93e11 degrees on the pinned sine and cosine are NaN (pinned_math.h, the conversion's
+    edge), on every build -- not the 7e121 an undefined conversion to int gave on x86"""
+    for deg in (1e12, -1e12, 3.4028234663852886e38, -3.4028234663852886e38):
+        _, att = rmcv_amd.serial_decode(K.py_packet(1, deg, 0.25, -0.5))
+        assert att["yaw"] == float(np.float32(deg)) * PI / 180.0 and math.isfinite(att["yaw"])
+        got = rmcv_amd.euler_to_matrix(att)
+        assert got.tobytes() == R.to_matrix(att["roll"], att["pitch"], att["yaw"]).tobytes()
+        assert np.isnan(got[:2]).all() and not np.isnan(got[2]).any()             # rows 0 and 1 carry cos / sin of the yaw, row 2 does not
+    below = 3.3e9                                                                   # ... and just below the edge both are numbers in [-1, 1]
+    m = rmcv_amd.euler_to_matrix((0.0, 0.0, below))
+    assert np.isfinite(m).all() and np.abs(m).max() <= 1.0 and m.tobytes() == R.to_matrix(0.0, 0.0, below).tobytes()
+
+
 def test_signed_zeros_are_a_general_product_s():
     m = rmcv_amd.euler_to_matrix((0.0, 0.0, 0.0))
     assert m.tobytes() == R.to_matrix(0.0, 0.0, 0.0).tobytes() == np.eye(3).tobytes()      # every zero +0: (x * 0 + -0 * 1) + ... sums to +0

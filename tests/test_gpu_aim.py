@@ -43,14 +43,14 @@ def test_seeded_lists_every_configuration(cap, names):
         assert e.value.code == abi.ERR_CAPACITY
     inputs = K.aim_inputs(len(lists))
     seen = set()
-    for use_inputs in (False, True):
-        trk.set_aim_inputs(inputs if use_inputs else None)
+    for use_inputs in (None, inputs, K.aim_inputs_huge(len(lists))):         # ... and a motor angle whose tangent is NaN by pinned_math.h's rule
+        trk.set_aim_inputs(use_inputs)
         for name, cfg in K.configs().items():
             trk.set_aim(cfg)
             trk.aim(K.NOW)
             got = trk.aims()
-            want = expect(cfg, lists, inputs if use_inputs else None, K.NOW)
-            assert got.tobytes() == want.tobytes(), (name, use_inputs, got, want)
+            want = expect(cfg, lists, use_inputs, K.NOW)
+            assert got.tobytes() == want.tobytes(), (name, use_inputs is not None, got, want)
             seen |= {(int(a["track"]), int(a["status"])) for a in got}
     if cap == 64:
         tracks = {t for t, _ in seen}

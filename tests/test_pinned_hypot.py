@@ -72,32 +72,30 @@ def check(pm, x, y):
         assert not bad, (name, len(bad), [(a.hex(), b.hex(), r.hex()) for a, b, r in bad[:5]])
 
 
-def test_random_pairs(pm):
-    """10^6 seeded pairs, exponent differences 0 .. 60, signs mixed"""
+# ---- the generators (tests/leaf_cases.py imports them for the device-against-host bit tests, with smaller counts) ----------------------------
+def gen_random_pairs(n=1_000_000):
+    """seeded pairs, exponent differences 0 .. 60, signs mixed"""
     rng = np.random.default_rng(20240517)
-    n = 1_000_000
     ea = rng.integers(-20, 21, n)
     d = rng.integers(0, 61, n)
     x = np.ldexp(rng.uniform(1, 2, n), ea) * rng.choice([-1.0, 1.0], n)
     y = np.ldexp(rng.uniform(1, 2, n), ea - d) * rng.choice([-1.0, 1.0], n)
     swap = rng.random(n) < 0.5
-    x, y = np.where(swap, y, x), np.where(swap, x, y)
-    check(pm, x, y)
+    return np.where(swap, y, x), np.where(swap, x, y)
 
 
-def test_near_midpoints_and_ties(pm):
+def gen_midpoints_and_ties(n_mid=40000, n_ties=3000):
     """the hard cases: b^2 / (2 a) next to an odd number of half ulps of a (sqrt lands ~2^-53 of an ulp from a rounding boundary), and
-    Pythagorean triples whose hypotenuse needs 54 bits (an exact tie: the even neighbour)"""
+    Pythagorean triples whose hypotenuse needs 54 bits (an exact tie: the even neighbour) -> ((x, y) near midpoints, (x, y) ties)"""
     rng = np.random.default_rng(7)
-    a = np.ldexp(rng.uniform(1, 2, 40000), rng.integers(-8, 9, 40000))
-    k = 2 * rng.integers(0, 6, 40000) + 1
+    a = np.ldexp(rng.uniform(1, 2, n_mid), rng.integers(-8, 9, n_mid))
+    k = 2 * rng.integers(0, 6, n_mid) + 1
     ulp = np.ldexp(1.0, np.frexp(a)[1] - 53)
     b = np.sqrt(k * a * ulp)
     x = np.concatenate([a, a, a])
     y = np.concatenate([b, np.nextafter(b, 0), np.nextafter(b, np.inf)])
-    check(pm, x, y)
     xs, ys, n_tie = [], [], 0
-    while n_tie < 3000:
+    while n_tie < n_ties:
         m, n = int(rng.integers(1 << 26, 3 << 25)), int(rng.integers(1, 1 << 26))
         if (m - n) % 2 == 0 or n >= m:
             continue
@@ -108,39 +106,66 @@ def test_near_midpoints_and_ties(pm):
         xs.append(math.ldexp(p, sc))
         ys.append(math.ldexp(q, sc))
         n_tie += 1
-    check(pm, np.array(xs), np.array(ys))
+    return (x, y), (np.array(xs), np.array(ys))
+
+
+TINY, BIG = 5e-324, 1.7976931348623157e308
+ZEROS = (np.array([0.0, -0.0, 3.5, -3.5, 0.0, TINY, BIG]), np.array([2.5, -2.5, 0.0, -0.0, -0.0, 0.0, 0.0]))
+NON_FINITE = (np.array([math.inf, -math.inf, math.nan, math.nan, 1.0, BIG, BIG]), np.array([1.0, math.nan, math.inf, 1.0, math.nan, BIG, 1e300]))
+
+
+def gen_extremes(n=20000):
+    """finite, non-zero pairs at the ends of the range: a list of (x, y)"""
+    rng = np.random.default_rng(3)
+    sub = np.ldexp(rng.integers(1, 1 << 52, n).astype(np.float64), -1074)      # subnormals
+    sub2 = np.ldexp(rng.integers(1, 1 << 52, n).astype(np.float64), -1074 - rng.integers(0, 30, n)).astype(np.float64)
+    near = np.ldexp(rng.uniform(1, 2, n), rng.integers(-1030, -1000, n))  # around the smallest normal
+    huge = np.ldexp(rng.uniform(1, 1.41, n), 1022)                            # near overflow (stays finite: below 2^1023.5 each)
+    huge2 = np.ldexp(rng.uniform(1, 2, n), 1022 - rng.integers(0, 40, n))
+    eq = np.ldexp(rng.uniform(1, 2, n), rng.integers(-1000, 1000, n))
+    ok = sub2 > 0
+    return [(sub[ok], sub2[ok]), (near, sub), (huge * 0.7, huge2 * 0.7), (eq, eq),
+            (np.array([TINY, TINY, 3 * TINY, 2.2250738585072014e-308, 1.0, 1e300]), np.array([TINY, 2 * TINY, 4 * TINY, 2.2250738585072014e-308, 1.0, 1e300]))]
+
+
+def gen_tracker_pairs():
+    """the (p, beta) arguments the Jacobi rotation met in the scenarios of tests/test_tracker_cpu.py (recorded once from the reference,
+    tests/golden/track_hypot_pairs.json, doubles as hex): (n, 2)"""
+    with open(os.path.join(ROOT, "tests", "golden", "track_hypot_pairs.json")) as f:
+        return np.array([[float.fromhex(a), float.fromhex(b)] for a, b in json.load(f)["pairs"]])
+
+
+def test_random_pairs(pm):
+    """10^6 seeded pairs, exponent differences 0 .. 60, signs mixed"""
+    x, y = gen_random_pairs(1_000_000)
+    assert len(x) == 1_000_000
+    check(pm, x, y)
+
+
+def test_near_midpoints_and_ties(pm):
+    (x, y), (xs, ys) = gen_midpoints_and_ties(40000, 3000)
+    assert len(x) == 120000 and len(xs) == 3000
+    check(pm, x, y)
+    check(pm, xs, ys)
 
 
 def test_extremes(pm):
-    tiny, big = 5e-324, 1.7976931348623157e308
-    rng = np.random.default_rng(3)
-    sub = np.ldexp(rng.integers(1, 1 << 52, 20000).astype(np.float64), -1074)      # subnormals
-    sub2 = np.ldexp(rng.integers(1, 1 << 52, 20000).astype(np.float64), -1074 - rng.integers(0, 30, 20000)).astype(np.float64)
-    near = np.ldexp(rng.uniform(1, 2, 20000), rng.integers(-1030, -1000, 20000))  # around the smallest normal
-    huge = np.ldexp(rng.uniform(1, 1.41, 20000), 1022)                            # near overflow (stays finite: below 2^1023.5 each)
-    huge2 = np.ldexp(rng.uniform(1, 2, 20000), 1022 - rng.integers(0, 40, 20000))
-    eq = np.ldexp(rng.uniform(1, 2, 20000), rng.integers(-1000, 1000, 20000))
-    ok = sub2 > 0
-    check(pm, sub[ok], sub2[ok])
-    check(pm, near, sub)
-    check(pm, huge * 0.7, huge2 * 0.7)
-    check(pm, eq, eq)
-    check(pm, np.array([tiny, tiny, 3 * tiny, 2.2250738585072014e-308, 1.0, 1e300]), np.array([tiny, 2 * tiny, 4 * tiny, 2.2250738585072014e-308, 1.0, 1e300]))
-    z = np.array([0.0, -0.0, 3.5, -3.5, 0.0, tiny, big])
-    w = np.array([2.5, -2.5, 0.0, -0.0, -0.0, 0.0, 0.0])
+    tiny, big = TINY, BIG
+    groups = gen_extremes(20000)
+    assert len(groups) == 5 and all(len(x) >= 6 for x, _ in groups)
+    for x, y in groups:
+        check(pm, x, y)
+    z, w = ZEROS
     for name, o in both(pm, z, w):
         assert o.tolist() == [2.5, 2.5, 3.5, 3.5, 0.0, tiny, big] and not np.signbit(o).any(), name
-    inf, nan = math.inf, math.nan
-    for name, o in both(pm, np.array([inf, -inf, nan, nan, 1.0, big, big]), np.array([1.0, nan, inf, 1.0, nan, big, 1e300])):
+    inf = math.inf
+    for name, o in both(pm, *NON_FINITE):
         assert o[0] == inf and o[1] == inf and o[2] == inf and math.isnan(o[3]) and math.isnan(o[4]) and o[5] == inf, name   # C99 F.9.4.3
         assert o[6] == big, name
 
 
 def test_pairs_from_the_tracker_scenarios(pm):
-    """the (p, beta) arguments the Jacobi rotation met in the scenarios of tests/test_tracker_cpu.py (recorded once from the reference,
-    tests/golden/track_hypot_pairs.json, doubles as hex)"""
-    with open(os.path.join(ROOT, "tests", "golden", "track_hypot_pairs.json")) as f:
-        pairs = np.array([[float.fromhex(a), float.fromhex(b)] for a, b in json.load(f)["pairs"]])
+    pairs = gen_tracker_pairs()
     assert len(pairs) >= 1000
     fin = np.isfinite(pairs).all(1) & (pairs != 0).any(1)
     check(pm, pairs[fin, 0], pairs[fin, 1])
