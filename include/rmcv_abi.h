@@ -320,7 +320,11 @@ int rmcv_extract_color(rmcv_ctx* ctx, const uint8_t* bgr, int w, int h, int stri
                        int contours_cap, int32_t* n_contours, int32_t* n_points);
 
 /* rm::filter_lightblobs (include/objdetect.h:47-49, src/objdetect.cpp:55-87).  The negative
- * list is returned as contour indices.  blob_src (nullable) = contour index of each positive. */
+ * list is returned as contour indices.  blob_src (nullable) = contour index of each positive.
+ * Points are what cv::findContours returns: a list with a negative coordinate is refused with
+ * RMCV_ERR_BAD_ARG before anything runs (the context stays usable).  The gates compare as the
+ * reference does: a zero-width ellipse has ratio = inf, which ratio_hi = +inf admits; 0 / 0 is NaN
+ * and goes to the negative list whatever the bounds. */
 int rmcv_filter_lightblobs(rmcv_ctx* ctx, const rmcv_point* pts, const int32_t* offs, int n_contours,
                            float tilt_max, float ratio_lo, float ratio_hi, double area_lo, double area_hi,
                            int enemy, rmcv_lightblob* blobs_out, int blobs_cap, int32_t* n_blobs,
@@ -331,7 +335,11 @@ int rmcv_filter_armours(rmcv_ctx* ctx, const rmcv_lightblob* blobs, int n_blobs,
                         float shear_max, float length_ratio_max, int enemy, rmcv_armour* armours_out,
                         int armours_cap, int32_t* n_armours);
 
-/* cv::fitEllipseDirect on one contour (the step of src/objdetect.cpp:68), for stage-wise parity */
+/* cv::fitEllipseDirect on one contour (the step of src/objdetect.cpp:68), for stage-wise parity.
+ * RMCV_OK and the fitted ellipse for every contour of six or more points whose result is finite -- zero
+ * width or height included (collinear or coinciding points).  RMCV_ERR_BAD_ARG: fewer than six points, a
+ * negative coordinate (see rmcv_filter_lightblobs), or a result with a NaN or infinite field, which is
+ * not handed out. */
 int rmcv_fit_ellipse(rmcv_ctx* ctx, const rmcv_point* pts, int n, rmcv_rrect* out);
 
 /* D(m) of one host mosaic (RMCV_OPT_INPUT_FORMAT) as a host BGR frame, for stage-wise parity and for callers that still want a
@@ -525,7 +533,7 @@ typedef struct {            /* the float arguments of rm::MatchLightBlob / rm::F
  * anything else is RMCV_ERR_BAD_ARG. */
 int rmcv_min_area_rect(rmcv_ctx* ctx, const rmcv_point* pts, int n, rmcv_rrect* out);
 /* rm::MatchLightBlob (include/objdetect.h:22-23, src/objdetect.cpp:9-28): *matched = 1 and *box_out set when the
- * contour passes every gate */
+ * contour passes every gate.  A list with a negative coordinate is RMCV_ERR_BAD_ARG (see rmcv_filter_lightblobs). */
 int rmcv_match_lightblob(rmcv_ctx* ctx, const rmcv_point* pts, int n, const rmcv_legacy_params* lp, rmcv_rrect* box_out,
                          int32_t* matched);
 /* rm::FindLightBlobs (include/objdetect.h:35-37, src/objdetect.cpp:30-53): every matching contour becomes a light blob

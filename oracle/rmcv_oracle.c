@@ -314,15 +314,64 @@ double orc_contour_area(const orc_point* pts, int n)
  * (orthes + hqr2, public-domain NIST algorithm as adopted by modules/core/src/lda.cpp).
  * V columns are the eigenvectors, d/e the real/imaginary eigenvalue parts. */
 #define EN 3
+
+/* Branch census of the ellipse fit (tests/test_fit_units_cpu.py, tests/test_fit_cases_cpu.py): one counter per branch of the
+ * eigen-solver, the direct fit's finish, the Jacobi / normal-equation solver and the general fit; a test reads and clears them
+ * (orc_census_read).  Counting only: no counter is ever read by the arithmetic.  Per thread, so that threaded callers share no
+ * cache line. */
+#define ORC_CENSUS(X)                                                                                                          \
+    X(orthes_reduce) X(orthes_scale_zero) X(orthes_ort_positive) X(orthes_ort_not_positive) X(orthes_accumulate)               \
+    X(orthes_accumulate_skipped) X(scan_s_zero) X(one_root) X(real_pair) X(real_pair_p_negative) X(real_pair_z_zero)           \
+    X(complex_pair) X(qr_step) X(iter10) X(iter30) X(iter30_shift) X(guard) X(qr_m_search_continues) X(qr_k_not_first)         \
+    X(qr_x_zero_break) X(qr_s_negated) X(qr_s_zero) X(norm_zero) X(back_real) X(back_real_e_negative) X(back_real_w_nonzero)   \
+    X(back_real_w_zero) X(back_real_pair_solve) X(back_real_pair_x_larger) X(back_real_pair_z_larger) X(back_real_rescale)     \
+    X(back_complex) X(back_complex_lower_larger) X(back_complex_cdiv) X(back_complex_e_negative) X(back_complex_e_zero)        \
+    X(back_complex_pair_solve) X(back_complex_rescale) X(cdiv_real_larger) X(cdiv_imag_larger) X(sort_swap01)                  \
+    X(sort_move2_front) X(sort_move2_middle)                                                                                   \
+    X(direct_attempt0) X(direct_attempt1) X(direct_none) X(direct_bad_box) X(cond_pick0) X(cond_pick1) X(cond_pick2)           \
+    X(norm_negated) X(norm_kept) X(theta_pv1_zero_0) X(theta_pv1_zero_90) X(theta_atan2) X(direct_swap) X(direct_no_swap)      \
+    X(jacobi_diagonal_on_entry) X(jacobi_converged) X(jacobi_sweeps_exhausted) X(jacobi_apq_zero) X(jacobi_apq_tiny)           \
+    X(jacobi_apq_negligible) X(jacobi_rotate) X(jacobi_theta_negative) X(normal_lam_not_positive) X(normal_column_dropped)     \
+    X(normal_column_used) X(general_fit) X(general_jitter_retry) X(general_no_retry) X(centre_det_zero) X(centre_det_nonzero)  \
+    X(finish_c_above_eps) X(finish_c_below_eps) X(finish_rp2_above) X(finish_rp2_below) X(finish_rp3_above)                    \
+    X(finish_rp3_below) X(general_swap) X(general_no_swap) X(angle_wrap_up) X(angle_wrap_down)
+enum {
+#define X(name) CEN_##name,
+    ORC_CENSUS(X)
+#undef X
+    CEN_COUNT
+};
+static __thread long long g_census[CEN_COUNT];
+#define CEN(name) (g_census[CEN_##name]++)
+int orc_census_size(void) { return CEN_COUNT; }
+const char* orc_census_name(int i)
+{
+    static const char* const names[CEN_COUNT] = {
+#define X(name) #name,
+        ORC_CENSUS(X)
+#undef X
+    };
+    return (i >= 0 && i < CEN_COUNT) ? names[i] : "";
+}
+void orc_census_read(long long* out, int clear)
+{
+    for (int i = 0; i < CEN_COUNT; i++) {
+        if (out) out[i] = g_census[i];
+        if (clear) g_census[i] = 0;
+    }
+}
+
 static void cdiv_(double xr, double xi, double yr, double yi, double* cr, double* ci)
 {
     double r, d;
     if (fabs(yr) > fabs(yi)) {
+        CEN(cdiv_real_larger);
         r = yi / yr;
         d = yr + r * yi;
         *cr = (xr + r * xi) / d;
         *ci = (xi - r * xr) / d;
     } else {
+        CEN(cdiv_imag_larger);
         r = yr / yi;
         d = yi + r * yr;
         *cr = (r * xr + xi) / d;
@@ -337,13 +386,16 @@ static void eig_orthes(double H[EN][EN], double V[EN][EN])
     for (int m = low + 1; m <= high - 1; m++) {
         double scale = 0.0;
         for (int i = m; i <= high; i++) scale = scale + fabs(H[i][m - 1]);
+        if (scale == 0.0) CEN(orthes_scale_zero);
         if (scale != 0.0) {
+            CEN(orthes_reduce);
             double h = 0.0;
             for (int i = high; i >= m; i--) {
                 ort[i] = H[i][m - 1] / scale;
                 h += ort[i] * ort[i];
             }
             double g = sqrt(h);
+            if (ort[m] > 0) CEN(orthes_ort_positive); else CEN(orthes_ort_not_positive);
             if (ort[m] > 0) g = -g;
             h = h - ort[m] * g;
             ort[m] = ort[m] - g;
@@ -366,7 +418,9 @@ static void eig_orthes(double H[EN][EN], double V[EN][EN])
     for (int i = 0; i < EN; i++)
         for (int j = 0; j < EN; j++) V[i][j] = (i == j ? 1.0 : 0.0);
     for (int m = high - 1; m >= low + 1; m--) {
+        if (H[m][m - 1] == 0.0) CEN(orthes_accumulate_skipped);
         if (H[m][m - 1] != 0.0) {
+            CEN(orthes_accumulate);
             for (int i = m + 1; i <= high; i++) ort[i] = H[i][m - 1];
             for (int j = m; j <= high; j++) {
                 double g = 0.0;
@@ -395,11 +449,13 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
         int l = n;
         while (l > low) {
             s = fabs(H[l - 1][l - 1]) + fabs(H[l][l]);
+            if (s == 0.0) CEN(scan_s_zero);
             if (s == 0.0) s = norm;
             if (fabs(H[l][l - 1]) < eps * s) break;
             l--;
         }
         if (l == n) { /* one root */
+            CEN(one_root);
             H[n][n] = H[n][n] + exshift;
             d[n] = H[n][n];
             e[n] = 0.0;
@@ -414,9 +470,12 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
             H[n - 1][n - 1] = H[n - 1][n - 1] + exshift;
             x = H[n][n];
             if (q >= 0) { /* real pair */
+                CEN(real_pair);
+                if (!(p >= 0)) CEN(real_pair_p_negative);
                 if (p >= 0) z = p + z; else z = p - z;
                 d[n - 1] = x + z;
                 d[n] = d[n - 1];
+                if (!(z != 0.0)) CEN(real_pair_z_zero);
                 if (z != 0.0) d[n] = x - w / z;
                 e[n - 1] = 0.0;
                 e[n] = 0.0;
@@ -443,6 +502,7 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
                     V[i][n] = q * V[i][n] - p * z;
                 }
             } else { /* complex pair */
+                CEN(complex_pair);
                 d[n - 1] = x + p;
                 d[n] = x + p;
                 e[n - 1] = z;
@@ -459,6 +519,7 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
                 w = H[n][n - 1] * H[n - 1][n];
             }
             if (iter == 10) { /* Wilkinson's original ad hoc shift */
+                CEN(iter10);
                 exshift += x;
                 for (int i = low; i <= n; i++) H[i][i] -= x;
                 s = fabs(H[n][n - 1]) + fabs(H[n - 1][n - 2]);
@@ -466,9 +527,11 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
                 w = -0.4375 * s * s;
             }
             if (iter == 30) { /* MATLAB's new ad hoc shift */
+                CEN(iter30);
                 s = (y - x) / 2.0;
                 s = s * s + w;
                 if (s > 0) {
+                    CEN(iter30_shift);
                     s = sqrt(s);
                     if (y < x) s = -s;
                     s = x - w / ((y - x) / 2.0 + s);
@@ -479,12 +542,14 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
             }
             iter = iter + 1;
             if (iter > 300) { /* not in JAMA: a guard so the oracle (and the GPU twin) always terminate */
+                CEN(guard);
                 d[n] = H[n][n] + exshift;
                 e[n] = 0.0;
                 n--;
                 iter = 0;
                 continue;
             }
+            CEN(qr_step);
             int m = n - 2;
             while (m >= l) {
                 z = H[m][m];
@@ -501,6 +566,7 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
                 if (fabs(H[m][m - 1]) * (fabs(q) + fabs(r)) <
                     eps * (fabs(p) * (fabs(H[m - 1][m - 1]) + fabs(z) + fabs(H[m + 1][m + 1]))))
                     break;
+                CEN(qr_m_search_continues);
                 m--;
             }
             for (int i = m + 2; i <= n; i++) {
@@ -510,6 +576,7 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
             for (int k = m; k <= n - 1; k++) {
                 int notlast = (k != n - 1);
                 if (k != m) {
+                    CEN(qr_k_not_first);
                     p = H[k][k - 1];
                     q = H[k + 1][k - 1];
                     r = (notlast ? H[k + 2][k - 1] : 0.0);
@@ -520,9 +587,12 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
                         r = r / x;
                     }
                 }
+                if (x == 0.0) CEN(qr_x_zero_break);
                 if (x == 0.0) break;
                 s = sqrt(p * p + q * q + r * r);
+                if (p < 0) CEN(qr_s_negated);
                 if (p < 0) s = -s;
+                if (!(s != 0)) CEN(qr_s_zero);
                 if (s != 0) {
                     if (k != m) H[k][k - 1] = -s * x;
                     else if (l != m) H[k][k - 1] = -H[k][k - 1];
@@ -565,12 +635,14 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
         }
     }
 
+    if (norm == 0.0) CEN(norm_zero);
     if (norm == 0.0) return;
 
     for (n = nn - 1; n >= 0; n--) {
         p = d[n];
         q = e[n];
         if (q == 0) { /* real vector */
+            CEN(back_real);
             int l = n;
             H[n][n] = 1.0;
             for (int i = n - 1; i >= 0; i--) {
@@ -578,14 +650,18 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
                 r = 0.0;
                 for (int j = l; j <= n; j++) r = r + H[i][j] * H[j][n];
                 if (e[i] < 0.0) {
+                    CEN(back_real_e_negative);
                     z = w;
                     s = r;
                 } else {
                     l = i;
                     if (e[i] == 0.0) {
+                        if (w != 0.0) CEN(back_real_w_nonzero); else CEN(back_real_w_zero);
                         if (w != 0.0) H[i][n] = -r / w;
                         else H[i][n] = -r / (eps * norm);
                     } else {
+                        CEN(back_real_pair_solve);
+                        if (fabs(H[i][i + 1]) > fabs(z)) CEN(back_real_pair_x_larger); else CEN(back_real_pair_z_larger);
                         x = H[i][i + 1];
                         y = H[i + 1][i];
                         q = (d[i] - p) * (d[i] - p) + e[i] * e[i];
@@ -595,13 +671,16 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
                         else H[i + 1][n] = (-s - y * t) / z;
                     }
                     t = fabs(H[i][n]);
+                    if ((eps * t) * t > 1) CEN(back_real_rescale);
                     if ((eps * t) * t > 1)
                         for (int j = i; j <= n; j++) H[j][n] = H[j][n] / t;
                 }
             }
         } else if (q < 0) { /* complex vector */
+            CEN(back_complex);
             int l = n - 1;
             double cr, ci;
+            if (fabs(H[n][n - 1]) > fabs(H[n - 1][n])) CEN(back_complex_lower_larger); else CEN(back_complex_cdiv);
             if (fabs(H[n][n - 1]) > fabs(H[n - 1][n])) {
                 H[n - 1][n - 1] = q / H[n][n - 1];
                 H[n - 1][n] = -(H[n][n] - p) / H[n][n - 1];
@@ -620,11 +699,13 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
                 }
                 w = H[i][i] - p;
                 if (e[i] < 0.0) {
+                    CEN(back_complex_e_negative);
                     z = w;
                     r = ra;
                     s = sa;
                 } else {
                     l = i;
+                    if (e[i] == 0) CEN(back_complex_e_zero); else CEN(back_complex_pair_solve);
                     if (e[i] == 0) {
                         cdiv_(-ra, -sa, w, q, &cr, &ci);
                         H[i][n - 1] = cr;
@@ -649,6 +730,7 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
                         }
                     }
                     t = fabs(H[i][n - 1]) > fabs(H[i][n]) ? fabs(H[i][n - 1]) : fabs(H[i][n]);
+                    if ((eps * t) * t > 1) CEN(back_complex_rescale);
                     if ((eps * t) * t > 1)
                         for (int j = i; j <= n; j++) {
                             H[j][n - 1] = H[j][n - 1] / t;
@@ -668,7 +750,7 @@ static void eig_hqr2(double H[EN][EN], double V[EN][EN], double d[EN], double e[
 }
 
 /* [OCV] eigenNonSymmetric: eigenvalues sorted descending, eigenvectors as rows. */
-static void eigen_nonsymmetric3(const double M[3][3], double eval[3], double evec[3][3])
+static void eigen_nonsymmetric3(const double M[3][3], double eval[3], double evec[3][3], double* eimag /* nullable: [3] */)
 {
     double H[3][3], V[3][3], d[3] = {0, 0, 0}, e[3] = {0, 0, 0};
     memcpy(H, M, sizeof(H));
@@ -683,10 +765,24 @@ static void eigen_nonsymmetric3(const double M[3][3], double eval[3], double eve
         }
         idx[j + 1] = k;
     }
+    if (idx[0] == 1 || (idx[0] == 2 && idx[1] == 1)) CEN(sort_swap01); /* d[0] < d[1] */
+    if (idx[0] == 2) CEN(sort_move2_front);
+    if (idx[1] == 2) CEN(sort_move2_middle);
     for (int i = 0; i < 3; i++) {
         eval[i] = d[idx[i]];
+        if (eimag) eimag[i] = e[idx[i]];
         for (int j = 0; j < 3; j++) evec[i][j] = V[j][idx[i]];
     }
+}
+
+/* the eigen-solver alone (tests/fit_unit_cases.py): M row-major; eval, evec as cv::eigenNonSymmetric returns them (eigenvectors as
+ * rows), eimag = the imaginary parts in the same order (a complex pair's vectors are the real and imaginary part of one vector) */
+void orc_eigen_nonsymmetric3(const double* M9, double* eval, double* evec9, double* eimag)
+{
+    double M[3][3], ev[3][3];
+    memcpy(M, M9, sizeof(M));
+    eigen_nonsymmetric3((const double(*)[3])M, eval, ev, eimag);
+    memcpy(evec9, ev, sizeof(ev));
 }
 
 /* Cyclic Jacobi for a symmetric k x k matrix (k <= 5).  BUILD-DEFINED: OpenCV's general fit
@@ -698,22 +794,30 @@ static void jacobi_sym(double* A, int k, double* lam, double* V)
 {
     for (int i = 0; i < k; i++)
         for (int j = 0; j < k; j++) V[i * k + j] = (i == j) ? 1.0 : 0.0;
-    for (int sweep = 0; sweep < 60; sweep++) {
+    int sweep;
+    for (sweep = 0; sweep < 60; sweep++) {
         double off = 0.0;
         for (int p = 0; p < k; p++)
             for (int q = p + 1; q < k; q++) off += fabs(A[p * k + q]);
-        if (off == 0.0) break;
+        if (off == 0.0) {
+            if (sweep == 0) CEN(jacobi_diagonal_on_entry); else CEN(jacobi_converged);
+            break;
+        }
         for (int p = 0; p < k; p++)
             for (int q = p + 1; q < k; q++) {
                 double apq = A[p * k + q];
+                if (apq == 0.0) CEN(jacobi_apq_zero);
                 if (apq == 0.0) continue;
                 double app = A[p * k + p], aqq = A[q * k + q];
                 if (fabs(apq) < 1e-300 || fabs(apq) <= 1.1102230246251565e-16 * 1e-3 * sqrt(fabs(app * aqq))) {
+                    if (fabs(apq) < 1e-300) CEN(jacobi_apq_tiny); else CEN(jacobi_apq_negligible);
                     A[p * k + q] = A[q * k + p] = 0.0;
                     continue;
                 }
+                CEN(jacobi_rotate);
                 double theta = (aqq - app) / (2.0 * apq);
                 double t = 1.0 / (fabs(theta) + sqrt(theta * theta + 1.0));
+                if (theta < 0) CEN(jacobi_theta_negative);
                 if (theta < 0) t = -t;
                 double c = 1.0 / sqrt(t * t + 1.0);
                 double s = t * c;
@@ -734,6 +838,7 @@ static void jacobi_sym(double* A, int k, double* lam, double* V)
                 }
             }
     }
+    if (sweep == 60) CEN(jacobi_sweeps_exhausted);
     for (int i = 0; i < k; i++) lam[i] = A[i * k + i];
 }
 
@@ -759,6 +864,7 @@ static void normal_factor(const double* G, int k, normal_fac* F)
     jacobi_sym(A, k, F->lam, F->V);
     double wsum = 0, mx = 0, mn = 0;
     for (int i = 0; i < k; i++) {
+        if (!(F->lam[i] > 0)) CEN(normal_lam_not_positive);
         F->w[i] = F->lam[i] > 0 ? sqrt(F->lam[i]) : 0.0;
         wsum += F->w[i];
         if (i == 0 || F->w[i] > mx) mx = F->w[i];
@@ -774,6 +880,7 @@ static void normal_apply(const normal_fac* F, const double* g, double* x)
     const int k = F->k;
     for (int i = 0; i < k; i++) x[i] = 0.0;
     for (int c = 0; c < k; c++) {
+        if (!(F->w[c] > F->thr)) CEN(normal_column_dropped); else CEN(normal_column_used);
         if (!(F->w[c] > F->thr)) continue;
         double dot = 0.0;
         for (int r = 0; r < k; r++) dot += F->V[r * k + c] * g[r];
@@ -870,11 +977,72 @@ static void gen_row3(const void* ctx, int i, double* row)
     row[0] = (px - R->r0) * (px - R->r0); row[1] = (py - R->r1) * (py - R->r1); row[2] = (px - R->r0) * (py - R->r1);
 }
 
+/* What the last fit of this thread handed to its scalar tails (tests/fit_unit_cases.py harvests the unit cases of the contour cases
+ * from it): written, never read back by the fit.  dm[a]: the 21 upper-triangle scatter entries of direct attempt a, already / n. */
+typedef struct {
+    double dm[2][21], d_scale, d_cx, d_cy, d_attempts;
+    double G5[25], g5[5], G3[9], g3[3], gfp5[5], gfp3[3], rp0, rp1, g_scale, g_cx, g_cy, g_ran;
+} orc_fit_trace;
+static __thread orc_fit_trace g_trace;
+int orc_debug_last_fit(double* out, int cap)
+{
+    const int n = (int)(sizeof(g_trace) / sizeof(double));
+    if (out && cap >= n) memcpy(out, &g_trace, sizeof(g_trace));
+    return n;
+}
+
+/* general fit, after the 5-parameter solve: centre from the conic gradient */
+static void general_centre(const double gfp[5], double rp[5])
+{
+    double a00 = 2 * gfp[0], a01 = gfp[2], a11 = 2 * gfp[1];
+    double det = a00 * a11 - a01 * a01;
+    rp[0] = rp[1] = 0.0;
+    if (det != 0.0) {
+        CEN(centre_det_nonzero);
+        rp[0] = (gfp[3] * a11 - gfp[4] * a01) / det;
+        rp[1] = (a00 * gfp[4] - a01 * gfp[3]) / det;
+    } else CEN(centre_det_zero);
+}
+
+/* general fit, after the 3-parameter re-fit: angle, radii, RotatedRect */
+static void general_finish(const double gfp[3], double rp[5], double scale, float cx, float cy, orc_rrect* box)
+{
+    const double min_eps = 1e-8;
+    double t;
+    rp[4] = -0.5 * m_atan2(gfp[2], gfp[1] - gfp[0]);
+    if (fabs(gfp[2]) > min_eps) CEN(finish_c_above_eps); else CEN(finish_c_below_eps);
+    if (fabs(gfp[2]) > min_eps) t = gfp[2] / m_sin(-2.0 * rp[4]);
+    else t = gfp[1] - gfp[0];
+    rp[2] = fabs(gfp[0] + gfp[1] - t);
+    if (rp[2] > min_eps) CEN(finish_rp2_above); else CEN(finish_rp2_below);
+    if (rp[2] > min_eps) rp[2] = sqrt(2.0 / rp[2]);
+    rp[3] = fabs(gfp[0] + gfp[1] + t);
+    if (rp[3] > min_eps) CEN(finish_rp3_above); else CEN(finish_rp3_below);
+    if (rp[3] > min_eps) rp[3] = sqrt(2.0 / rp[3]);
+    box->cx = (float)(rp[0] / scale) + cx;
+    box->cy = (float)(rp[1] / scale) + cy;
+    box->w = (float)(rp[2] * 2 / scale);
+    box->h = (float)(rp[3] * 2 / scale);
+    box->angle = 0.0f; /* [OCV] only the swapped branch assigns the angle; the unswapped case arises only
+                          for an axis-aligned ellipse with a vertical major axis, where 0 is the answer */
+    if (box->w > box->h) {
+        CEN(general_swap);
+        float tmp = box->w;
+        box->w = box->h;
+        box->h = tmp;
+        box->angle = (float)(90 + rp[4] * 180 / ORC_PI);
+    } else CEN(general_no_swap);
+    if (box->angle < -180) CEN(angle_wrap_up);
+    if (box->angle > 360) CEN(angle_wrap_down);
+    if (box->angle < -180) box->angle += 360;
+    if (box->angle > 360) box->angle -= 360;
+}
+
 /* [OCV] fitEllipseNoDirect (general "LIN" conic fit, D. Weiss): structure restated, the two
  * least-squares sub-problems solved via normal_factor / normal_apply / normal_refine (BUILD-DEFINED, see above). */
 static void fit_ellipse_general(const orc_point* pts, int n, orc_rrect* box)
 {
-    const double min_eps = 1e-8;
+    CEN(general_fit);
     float cx = 0, cy = 0; /* Point2f accumulator */
     for (int i = 0; i < n; i++) {
         cx += (float)pts[i].x;
@@ -898,22 +1066,20 @@ static void fit_ellipse_general(const orc_point* pts, int n, orc_rrect* box)
         normal_equations(gen_row5, &R, n, 5, 10000.0, G, g);
         normal_factor(G, 5, &F);
         if (iter == 0 && F.wmax * FLT_EPSILON > F.wmin) {
+            CEN(general_jitter_retry);
             eps = (float)(s / (n * 2) * 1e-3);
             continue;
         }
+        if (iter == 0) CEN(general_no_retry);
+        memcpy(g_trace.G5, G, sizeof(G));
+        memcpy(g_trace.g5, g, sizeof(g));
         normal_apply(&F, g, gfp);
         normal_refine(&F, gen_row5, &R, n, 10000.0, gfp);
         break;
     }
     /* centre: differentiate the general form */
-    {
-        double a00 = 2 * gfp[0], a01 = gfp[2], a11 = 2 * gfp[1];
-        double det = a00 * a11 - a01 * a01;
-        if (det != 0.0) {
-            rp[0] = (gfp[3] * a11 - gfp[4] * a01) / det;
-            rp[1] = (a00 * gfp[4] - a01 * gfp[3]) / det;
-        }
-    }
+    memcpy(g_trace.gfp5, gfp, sizeof(gfp));
+    general_centre(gfp, rp);
     /* re-fit A..C with that centre */
     {
         double G[9], g[3];
@@ -922,38 +1088,145 @@ static void fit_ellipse_general(const orc_point* pts, int n, orc_rrect* box)
         R.r0 = rp[0];
         R.r1 = rp[1];
         normal_equations(gen_row3, &R, n, 3, 1.0, G, g);
+        memcpy(g_trace.G3, G, sizeof(G));
+        memcpy(g_trace.g3, g, sizeof(g));
         normal_factor(G, 3, &F);
         normal_apply(&F, g, gfp);
         normal_refine(&F, gen_row3, &R, n, 1.0, gfp);
     }
-    double t;
-    rp[4] = -0.5 * m_atan2(gfp[2], gfp[1] - gfp[0]);
-    if (fabs(gfp[2]) > min_eps) t = gfp[2] / m_sin(-2.0 * rp[4]);
-    else t = gfp[1] - gfp[0];
-    rp[2] = fabs(gfp[0] + gfp[1] - t);
-    if (rp[2] > min_eps) rp[2] = sqrt(2.0 / rp[2]);
-    rp[3] = fabs(gfp[0] + gfp[1] + t);
-    if (rp[3] > min_eps) rp[3] = sqrt(2.0 / rp[3]);
-    box->cx = (float)(rp[0] / scale) + cx;
-    box->cy = (float)(rp[1] / scale) + cy;
-    box->w = (float)(rp[2] * 2 / scale);
-    box->h = (float)(rp[3] * 2 / scale);
-    box->angle = 0.0f; /* [OCV] only the swapped branch assigns the angle; the unswapped case arises only
-                          for an axis-aligned ellipse with a vertical major axis, where 0 is the answer */
-    if (box->w > box->h) {
-        float tmp = box->w;
-        box->w = box->h;
-        box->h = tmp;
-        box->angle = (float)(90 + rp[4] * 180 / ORC_PI);
+    memcpy(g_trace.gfp3, gfp, sizeof(double) * 3);
+    g_trace.rp0 = rp[0];
+    g_trace.rp1 = rp[1];
+    g_trace.g_scale = scale;
+    g_trace.g_cx = cx;
+    g_trace.g_cy = cy;
+    g_trace.g_ran = 1;
+    general_finish(gfp, rp, scale, cx, cy, box);
+}
+
+/* the general fit's scalar tails alone (tests/fit_unit_cases.py).  k = 5 or 3; use: bit c set <=> column c is applied */
+void orc_normal_unit(const double* G, const double* g, int k, double* lam, int* use, double* wmax, double* wmin, double* x)
+{
+    normal_fac F;
+    normal_factor(G, k, &F);
+    *use = 0;
+    for (int c = 0; c < k; c++) {
+        lam[c] = F.lam[c];
+        *use |= (F.w[c] > F.thr ? 1 : 0) << c;
     }
-    if (box->angle < -180) box->angle += 360;
-    if (box->angle > 360) box->angle -= 360;
+    *wmax = F.wmax;
+    *wmin = F.wmin;
+    for (int i = 0; i < 5; i++) x[i] = 0.0;
+    normal_apply(&F, g, x);
+}
+void orc_general_centre(const double* gfp5, double* rp2)
+{
+    double rp[5] = {0, 0, 0, 0, 0};
+    general_centre(gfp5, rp);
+    rp2[0] = rp[0];
+    rp2[1] = rp[1];
+}
+void orc_general_finish(const double* gfp3, double rp0, double rp1, double scale, float cx, float cy, orc_rrect* box)
+{
+    double rp[5] = {rp0, rp1, 0, 0, 0};
+    general_finish(gfp3, rp, scale, cx, cy, box);
 }
 
 /* [OCV] isGoodBox: the direct/AMS fits are replaced by the general fit when the box is wild */
 static double g_dbg_det[2];
 double orc_debug_last_det(int k) { return g_dbg_det[k & 1]; }
 static int is_good_box(const orc_rrect* b) { return (b->h <= b->w * 30) && (b->w <= b->h * 30); }
+
+/* direct fit: scatter matrix DM (6x6, already divided by n) -> TM, Ts, M; returns det(M) */
+static double direct_reduce(double DM[6][6], double TM[3][3], double* Ts_out, double M[3][3])
+{
+    /* TM = -adj(S3) * S2^T, written as the six-term cofactor expressions */
+    for (int c = 0; c < 3; c++) {
+        TM[0][c] = DM[c][5] * DM[3][5] * DM[4][4] - DM[c][5] * DM[3][4] * DM[4][5] - DM[c][4] * DM[3][5] * DM[5][4] +
+                   DM[c][3] * DM[4][5] * DM[5][4] + DM[c][4] * DM[3][4] * DM[5][5] - DM[c][3] * DM[4][4] * DM[5][5];
+        TM[1][c] = DM[c][5] * DM[3][3] * DM[4][5] - DM[c][5] * DM[3][5] * DM[4][3] + DM[c][4] * DM[3][5] * DM[5][3] -
+                   DM[c][3] * DM[4][5] * DM[5][3] - DM[c][4] * DM[3][3] * DM[5][5] + DM[c][3] * DM[4][3] * DM[5][5];
+        TM[2][c] = DM[c][5] * DM[3][4] * DM[4][3] - DM[c][5] * DM[3][3] * DM[4][4] - DM[c][4] * DM[3][4] * DM[5][3] +
+                   DM[c][3] * DM[4][4] * DM[5][3] + DM[c][4] * DM[3][3] * DM[5][4] - DM[c][3] * DM[4][3] * DM[5][4];
+    }
+    double Ts = (-(DM[3][5] * DM[4][4] * DM[5][3]) + DM[3][4] * DM[4][5] * DM[5][3] + DM[3][5] * DM[4][3] * DM[5][4] -
+                 DM[3][3] * DM[4][5] * DM[5][4] - DM[3][4] * DM[4][3] * DM[5][5] + DM[3][3] * DM[4][4] * DM[5][5]);
+    for (int c = 0; c < 3; c++) {
+        M[0][c] = (DM[2][c] + (DM[2][3] * TM[0][c] + DM[2][4] * TM[1][c] + DM[2][5] * TM[2][c]) / Ts) / 2.;
+        M[1][c] = -DM[1][c] - (DM[1][3] * TM[0][c] + DM[1][4] * TM[1][c] + DM[1][5] * TM[2][c]) / Ts;
+        M[2][c] = (DM[0][c] + (DM[0][3] * TM[0][c] + DM[0][4] * TM[1][c] + DM[0][5] * TM[2][c]) / Ts) / 2.;
+    }
+    *Ts_out = Ts;
+    return M[0][0] * (M[1][1] * M[2][2] - M[2][1] * M[1][2]) - M[0][1] * (M[1][0] * M[2][2] - M[2][0] * M[1][2]) +
+           M[0][2] * (M[1][0] * M[2][1] - M[2][0] * M[1][1]);
+}
+
+/* direct fit: eigenvector selection, conic -> RotatedRect (width <= height, angle in [0,180)) */
+static void direct_finish(double M[3][3], double TM[3][3], double Ts, double scale, double cx, double cy, orc_rrect* box)
+{
+    double eval[3], ev[3][3], cond[3];
+    int i;
+    eigen_nonsymmetric3((const double(*)[3])M, eval, ev, NULL);
+    cond[0] = (4.0 * ev[0][0] * ev[0][2] - ev[0][1] * ev[0][1]);
+    cond[1] = (4.0 * ev[1][0] * ev[1][2] - ev[1][1] * ev[1][1]);
+    cond[2] = (4.0 * ev[2][0] * ev[2][2] - ev[2][1] * ev[2][1]);
+    if (cond[0] < cond[1]) i = (cond[1] < cond[2]) ? 2 : 1;
+    else i = (cond[0] < cond[2]) ? 2 : 0;
+    if (i == 0) CEN(cond_pick0); else if (i == 1) CEN(cond_pick1); else CEN(cond_pick2);
+    double norm = sqrt(ev[i][0] * ev[i][0] + ev[i][1] * ev[i][1] + ev[i][2] * ev[i][2]);
+    if (((ev[i][0] < 0.0 ? -1 : 1) * (ev[i][1] < 0.0 ? -1 : 1) * (ev[i][2] < 0.0 ? -1 : 1)) <= 0.0) CEN(norm_negated); else CEN(norm_kept);
+    if (((ev[i][0] < 0.0 ? -1 : 1) * (ev[i][1] < 0.0 ? -1 : 1) * (ev[i][2] < 0.0 ? -1 : 1)) <= 0.0) norm = -1.0 * norm;
+    double pv0 = ev[i][0] / norm, pv1 = ev[i][1] / norm, pv2 = ev[i][2] / norm;
+    /* Q = (TM . pVec) / Ts */
+    double q0 = (TM[0][0] * pv0 + TM[0][1] * pv1 + TM[0][2] * pv2) / Ts;
+    double q1 = (TM[1][0] * pv0 + TM[1][1] * pv1 + TM[1][2] * pv2) / Ts;
+    double q2 = (TM[2][0] * pv0 + TM[2][1] * pv1 + TM[2][2] * pv2) / Ts;
+    double u1 = pv2 * q0 * q0 - pv1 * q0 * q1 + pv0 * q1 * q1 + pv1 * pv1 * q2;
+    double u2 = pv0 * pv2 * q2;
+    double l1 = sqrt(pv1 * pv1 + (pv0 - pv2) * (pv0 - pv2));
+    double l2 = pv0 + pv2;
+    double l3 = pv1 * pv1 - 4 * pv0 * pv2;
+    double p1 = 2 * pv2 * q0 - pv1 * q1;
+    double p2 = 2 * pv0 * q1 - pv1 * q0;
+    double x0 = (p1 / l3 / scale) + cx;
+    double y0 = (p2 / l3 / scale) + cy;
+    double a = sqrt(2.) * sqrt((u1 - 4.0 * u2) / ((l1 - l2) * l3)) / scale;
+    double b = sqrt(2.) * sqrt(-1.0 * ((u1 - 4.0 * u2) / ((l1 + l2) * l3))) / scale;
+    double theta;
+    if (pv1 == 0) {
+        if (pv0 < pv2) CEN(theta_pv1_zero_0); else CEN(theta_pv1_zero_90);
+        theta = (pv0 < pv2) ? 0 : ORC_PI / 2.;
+    } else {
+        CEN(theta_atan2);
+        theta = ORC_PI / 2. + 0.5 * m_atan2(pv1, (pv0 - pv2));
+    }
+    box->cx = (float)x0;
+    box->cy = (float)y0;
+    box->w = (float)(2.0 * a);
+    box->h = (float)(2.0 * b);
+    if (box->w > box->h) {
+        CEN(direct_swap);
+        float tmp = box->w;
+        box->w = box->h;
+        box->h = tmp;
+        box->angle = (float)(m_fmod180(90 + theta * 180 / ORC_PI));
+    } else {
+        CEN(direct_no_swap);
+        box->angle = (float)(m_fmod180(theta * 180 / ORC_PI));
+    }
+}
+
+/* the direct fit's scalar tail alone (tests/fit_unit_cases.py): dm21 = the upper triangle of the scatter matrix, row-major */
+void orc_direct_unit(const double* dm21, double scale, double cx, double cy, double* det, double* M9, double* Ts, orc_rrect* box)
+{
+    double DM[6][6], TM[3][3], M[3][3];
+    int e = 0;
+    for (int a = 0; a < 6; a++)
+        for (int b = a; b < 6; b++, e++) DM[a][b] = DM[b][a] = dm21[e];
+    *det = direct_reduce(DM, TM, Ts, M);
+    memcpy(M9, M, sizeof(M));
+    direct_finish(M, TM, *Ts, scale, cx, cy, box);
+}
 
 /* [OCV] cv::fitEllipseDirect (Fitzgibbon et al. 1999, numerically stable form of Halir &
  * Flusser): centroid -> L1 scale -> n x 6 design rows [x^2 xy y^2 x y 1] -> DM = A^T A / n
@@ -975,6 +1248,10 @@ int orc_fit_ellipse_direct(const orc_point* pts, int n, orc_rrect* box)
     double DM[6][6], TM[3][3], M[3][3], Ts = 0;
     float eps = 0;
     int iter;
+    memset(&g_trace, 0, sizeof(g_trace));
+    g_trace.d_scale = scale;
+    g_trace.d_cx = cx;
+    g_trace.d_cy = cy;
     for (iter = 0; iter < 2; iter++) {
         double acc[6][6];
         memset(acc, 0, sizeof(acc));
@@ -987,74 +1264,19 @@ int orc_fit_ellipse_direct(const orc_point* pts, int n, orc_rrect* box)
                 for (int b = a; b < 6; b++) acc[a][b] += row[a] * row[b]; /* mulTransposed: sequential over rows */
         }
         double inv_n = 1.0 / n;
-        for (int a = 0; a < 6; a++)
-            for (int b = a; b < 6; b++) DM[a][b] = DM[b][a] = acc[a][b] * inv_n; /* DM *= (1.0/n) */
-
-        /* TM = -adj(S3) * S2^T, written as the six-term cofactor expressions */
-        for (int c = 0; c < 3; c++) {
-            TM[0][c] = DM[c][5] * DM[3][5] * DM[4][4] - DM[c][5] * DM[3][4] * DM[4][5] - DM[c][4] * DM[3][5] * DM[5][4] +
-                       DM[c][3] * DM[4][5] * DM[5][4] + DM[c][4] * DM[3][4] * DM[5][5] - DM[c][3] * DM[4][4] * DM[5][5];
-            TM[1][c] = DM[c][5] * DM[3][3] * DM[4][5] - DM[c][5] * DM[3][5] * DM[4][3] + DM[c][4] * DM[3][5] * DM[5][3] -
-                       DM[c][3] * DM[4][5] * DM[5][3] - DM[c][4] * DM[3][3] * DM[5][5] + DM[c][3] * DM[4][3] * DM[5][5];
-            TM[2][c] = DM[c][5] * DM[3][4] * DM[4][3] - DM[c][5] * DM[3][3] * DM[4][4] - DM[c][4] * DM[3][4] * DM[5][3] +
-                       DM[c][3] * DM[4][4] * DM[5][3] + DM[c][4] * DM[3][3] * DM[5][4] - DM[c][3] * DM[4][3] * DM[5][4];
-        }
-        Ts = (-(DM[3][5] * DM[4][4] * DM[5][3]) + DM[3][4] * DM[4][5] * DM[5][3] + DM[3][5] * DM[4][3] * DM[5][4] -
-              DM[3][3] * DM[4][5] * DM[5][4] - DM[3][4] * DM[4][3] * DM[5][5] + DM[3][3] * DM[4][4] * DM[5][5]);
-        for (int c = 0; c < 3; c++) {
-            M[0][c] = (DM[2][c] + (DM[2][3] * TM[0][c] + DM[2][4] * TM[1][c] + DM[2][5] * TM[2][c]) / Ts) / 2.;
-            M[1][c] = -DM[1][c] - (DM[1][3] * TM[0][c] + DM[1][4] * TM[1][c] + DM[1][5] * TM[2][c]) / Ts;
-            M[2][c] = (DM[0][c] + (DM[0][3] * TM[0][c] + DM[0][4] * TM[1][c] + DM[0][5] * TM[2][c]) / Ts) / 2.;
-        }
-        double det = M[0][0] * (M[1][1] * M[2][2] - M[2][1] * M[1][2]) - M[0][1] * (M[1][0] * M[2][2] - M[2][0] * M[1][2]) +
-                     M[0][2] * (M[1][0] * M[2][1] - M[2][0] * M[1][1]);
+        for (int a = 0, e = 0; a < 6; a++)
+            for (int b = a; b < 6; b++, e++) g_trace.dm[iter][e] = DM[a][b] = DM[b][a] = acc[a][b] * inv_n; /* DM *= (1.0/n) */
+        g_trace.d_attempts = iter + 1;
+        double det = direct_reduce(DM, TM, &Ts, M);
         g_dbg_det[iter] = det;
         if (fabs(det) > 1.0e-10) break;
         eps = (float)(s / (n * 2) * 1e-2);
     }
+    if (iter == 0) CEN(direct_attempt0); else if (iter == 1) CEN(direct_attempt1); else CEN(direct_none);
     if (iter < 2) {
-        double eval[3], ev[3][3], cond[3];
-        int i;
-        eigen_nonsymmetric3(M, eval, ev);
-        cond[0] = (4.0 * ev[0][0] * ev[0][2] - ev[0][1] * ev[0][1]);
-        cond[1] = (4.0 * ev[1][0] * ev[1][2] - ev[1][1] * ev[1][1]);
-        cond[2] = (4.0 * ev[2][0] * ev[2][2] - ev[2][1] * ev[2][1]);
-        if (cond[0] < cond[1]) i = (cond[1] < cond[2]) ? 2 : 1;
-        else i = (cond[0] < cond[2]) ? 2 : 0;
-        double norm = sqrt(ev[i][0] * ev[i][0] + ev[i][1] * ev[i][1] + ev[i][2] * ev[i][2]);
-        if (((ev[i][0] < 0.0 ? -1 : 1) * (ev[i][1] < 0.0 ? -1 : 1) * (ev[i][2] < 0.0 ? -1 : 1)) <= 0.0) norm = -1.0 * norm;
-        double pv0 = ev[i][0] / norm, pv1 = ev[i][1] / norm, pv2 = ev[i][2] / norm;
-        /* Q = (TM . pVec) / Ts */
-        double q0 = (TM[0][0] * pv0 + TM[0][1] * pv1 + TM[0][2] * pv2) / Ts;
-        double q1 = (TM[1][0] * pv0 + TM[1][1] * pv1 + TM[1][2] * pv2) / Ts;
-        double q2 = (TM[2][0] * pv0 + TM[2][1] * pv1 + TM[2][2] * pv2) / Ts;
-        double u1 = pv2 * q0 * q0 - pv1 * q0 * q1 + pv0 * q1 * q1 + pv1 * pv1 * q2;
-        double u2 = pv0 * pv2 * q2;
-        double l1 = sqrt(pv1 * pv1 + (pv0 - pv2) * (pv0 - pv2));
-        double l2 = pv0 + pv2;
-        double l3 = pv1 * pv1 - 4 * pv0 * pv2;
-        double p1 = 2 * pv2 * q0 - pv1 * q1;
-        double p2 = 2 * pv0 * q1 - pv1 * q0;
-        double x0 = (p1 / l3 / scale) + cx;
-        double y0 = (p2 / l3 / scale) + cy;
-        double a = sqrt(2.) * sqrt((u1 - 4.0 * u2) / ((l1 - l2) * l3)) / scale;
-        double b = sqrt(2.) * sqrt(-1.0 * ((u1 - 4.0 * u2) / ((l1 + l2) * l3))) / scale;
-        double theta;
-        if (pv1 == 0) theta = (pv0 < pv2) ? 0 : ORC_PI / 2.;
-        else theta = ORC_PI / 2. + 0.5 * m_atan2(pv1, (pv0 - pv2));
-        box->cx = (float)x0;
-        box->cy = (float)y0;
-        box->w = (float)(2.0 * a);
-        box->h = (float)(2.0 * b);
-        if (box->w > box->h) {
-            float tmp = box->w;
-            box->w = box->h;
-            box->h = tmp;
-            box->angle = (float)(m_fmod180(90 + theta * 180 / ORC_PI));
-        } else {
-            box->angle = (float)(m_fmod180(theta * 180 / ORC_PI));
-        }
+        direct_finish(M, TM, Ts, scale, cx, cy, box);
         if (is_good_box(box)) return 0;
+        CEN(direct_bad_box);
     }
     fit_ellipse_general(pts, n, box);
     return 1;

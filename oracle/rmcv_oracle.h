@@ -90,6 +90,18 @@ int orc_find_contours(const uint8_t* binary, int w, int h, orc_point* pts, int c
 double orc_contour_area(const orc_point* pts, int n);                   /* cv::contourArea */
 int    orc_fit_ellipse_direct(const orc_point* pts, int n, orc_rrect* out); /* cv::fitEllipseDirect; returns
                                  0 direct solution, 1 fell back to the general (LIN) fit */
+/* The scalar tails of the fit, alone, for tests/fit_unit_cases.py (the arithmetic is the fit's own: the same static functions),
+ * the branch census of everything the fit runs (read and cleared by a test; per thread) and what the last fit handed to its tails. */
+void   orc_eigen_nonsymmetric3(const double* M9, double* eval, double* evec9, double* eimag);
+void   orc_direct_unit(const double* dm21, double scale, double cx, double cy, double* det, double* M9, double* Ts, orc_rrect* box);
+void   orc_normal_unit(const double* G, const double* g, int k, double* lam, int* use, double* wmax, double* wmin, double* x);
+void   orc_general_centre(const double* gfp5, double* rp2);
+void   orc_general_finish(const double* gfp3, double rp0, double rp1, double scale, float cx, float cy, orc_rrect* box);
+int    orc_census_size(void);
+const char* orc_census_name(int i);
+void   orc_census_read(long long* out, int clear);
+double orc_debug_last_det(int k);
+int    orc_debug_last_fit(double* out, int cap);
 void   orc_rrect_points(const orc_rrect* r, float pt[4][2]);            /* cv::RotatedRect::points */
 void   orc_make_lightblob(const orc_rrect* box, int camp, orc_lightblob* out); /* core.cpp:9-19 */
 void   orc_make_armour(const orc_lightblob* a, const orc_lightblob* b, orc_armour* out); /* core.cpp:21-49 */

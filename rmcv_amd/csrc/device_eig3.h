@@ -7,7 +7,8 @@
 // and that step always starts at m = 0 and sweeps k = 0, 1.  Written out per shape there is no loop or subscript bookkeeping on the
 // wave's single dependent chain and every element access has a constant position (the run-time-subscript form of device_fit.h
 // spent about two thirds of a direct fit, 18-22 us, here).  Operations, their order and every rounding are those of the general
-// routine: the values are bit-identical (tests: every fit of the parity suites).
+// routine: the values are bit-identical (tests: tests/test_gpu_fit_units.py -- this solver alone, every branch of every shape by the census of
+// tests/test_fit_units_cpu.py, against the oracle and against the general routine built with -DRMCV_EIG3_GENERAL; and every fit of the parity suites).
 #pragma once
 
 namespace rmcv {

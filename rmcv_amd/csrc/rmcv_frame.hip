@@ -5,6 +5,7 @@
 #include <string.h>
 
 #include <algorithm>
+#include <cmath>
 #include <vector>
 
 #include "rmcv_ctx.h"
@@ -514,6 +515,11 @@ int rmcv::load_contours(rmcv_ctx* c, const rmcv_point* pts, const int32_t* offs,
         cs[n - 1 - i] = offs[i];
         cl[n - 1 - i] = offs[i + 1] - offs[i];
     }
+    // cv::findContours never returns a negative coordinate, and the fit's rule "a float sum of coordinates is exact below 2^24"
+    // (wave_detect.h: fit_ellipse_wave) holds for non-negative terms only: such a list is refused here, on the host, before anything
+    // is copied (rmcv_abi.h: rmcv_fit_ellipse, rmcv_filter_lightblobs, rmcv_match_lightblob)
+    for (int i = 0; i < total; i++)
+        if (pts[i].x < 0 || pts[i].y < 0) return fail(c, RMCV_ERR_BAD_ARG, "contour point with a negative coordinate");
     for (int k = 0; k < n; k++)
         if (cl[k] >= 6) el.push_back(k); // the fit stage's work list (what k_contours writes in the batch path)
     const int32_t ne = (int32_t)el.size();
@@ -607,7 +613,9 @@ int rmcv_filter_armours(rmcv_ctx* c, const rmcv_lightblob* blobs, int n_blobs, f
 int rmcv_fit_ellipse(rmcv_ctx* c, const rmcv_point* pts, int n, rmcv_rrect* out)
 {
     if (!c || !pts || !out || n < 5) return RMCV_ERR_BAD_ARG;
-    // run the blob stage on one contour with every gate open; the fitted ellipse is kept next to each blob
+    // run the blob stage on one contour with every gate open.  The fitted ellipse is read from the contour's own slot (k_fit writes it
+    // whatever the ratio and tilt tests then say): a zero-width result has ratio = inf, 0 / 0 has ratio = NaN, and neither may keep a
+    // finite ellipse from the caller (the positive list, which the ratio test guards, once did)
     int32_t offs[2] = {0, n};
     hipSetDevice(c->device);
     int rc = load_contours(c, pts, offs, 1);
@@ -622,11 +630,14 @@ int rmcv_fit_ellipse(rmcv_ctx* c, const rmcv_point* pts, int n, rmcv_rrect* out)
     const Geom g1 = one_frame_geom(c);
     HIPCHK(c, launch_blobs(g1, c->bufs, c->lim, p, c->stream), "k_blobs");
     WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
-    int32_t nb = 0, nn = 0;
-    HIPCHK(c, hipMemcpy(&nb, c->bufs.n_blobs, 4, hipMemcpyDeviceToHost), "D2H");
-    HIPCHK(c, hipMemcpy(&nn, c->bufs.n_neg, 4, hipMemcpyDeviceToHost), "D2H");
-    if (nb != 1) return fail(c, RMCV_ERR_BAD_ARG, n < 6 ? "contour has fewer than 6 points" : "ellipse fit produced NaN");
-    HIPCHK(c, hipMemcpy(out, c->bufs.ellipses, sizeof(rmcv_rrect), hipMemcpyDeviceToHost), "D2H ellipse");
+    int32_t kind = 0;
+    rmcv_rrect ell;
+    HIPCHK(c, hipMemcpy(&kind, c->bufs.slot_kind, 4, hipMemcpyDeviceToHost), "D2H");
+    if ((kind & 15) == 0) return fail(c, RMCV_ERR_BAD_ARG, n < 6 ? "contour has fewer than 6 points" : "the contour was not fitted");
+    HIPCHK(c, hipMemcpy(&ell, c->bufs.slot_ell, sizeof(rmcv_rrect), hipMemcpyDeviceToHost), "D2H ellipse");
+    if (!(std::isfinite(ell.cx) && std::isfinite(ell.cy) && std::isfinite(ell.w) && std::isfinite(ell.h) && std::isfinite(ell.angle)))
+        return fail(c, RMCV_ERR_BAD_ARG, "ellipse fit produced NaN");
+    *out = ell;
     return RMCV_OK;
 }
 

@@ -122,6 +122,84 @@ def fit_ellipse_direct(pts):
     return out[0], path
 
 
+# ---- the fit's scalar tails alone, its branch census and what the last fit handed to its tails (tests/fit_unit_cases.py, fit_cases.py)
+def census_names():
+    L = lib()
+    L.orc_census_name.restype = C.c_char_p
+    return [L.orc_census_name(i).decode() for i in range(L.orc_census_size())]
+
+
+def census(clear=True):
+    """{branch name: count since the last clear} of this thread's fits"""
+    names = census_names()
+    out = (C.c_longlong * len(names))()
+    lib().orc_census_read(out, 1 if clear else 0)
+    return dict(zip(names, list(out)))
+
+
+def debug_last_det(k):
+    lib().orc_debug_last_det.restype = C.c_double
+    return lib().orc_debug_last_det(int(k))
+
+
+_TRACE_FIELDS = [("dm", 42), ("d_scale", 1), ("d_cx", 1), ("d_cy", 1), ("d_attempts", 1), ("G5", 25), ("g5", 5), ("G3", 9), ("g3", 3),
+                 ("gfp5", 5), ("gfp3", 3), ("rp0", 1), ("rp1", 1), ("g_scale", 1), ("g_cx", 1), ("g_cy", 1), ("g_ran", 1)]
+
+
+def last_fit():
+    """what the last fit_ellipse_direct of this thread handed to its scalar tails, as a dict of float64 arrays / scalars"""
+    n = lib().orc_debug_last_fit(None, 0)
+    assert n == sum(k for _, k in _TRACE_FIELDS), n
+    buf = np.zeros(n)
+    lib().orc_debug_last_fit(_p(buf), n)
+    out, o = {}, 0
+    for name, k in _TRACE_FIELDS:
+        out[name] = buf[o:o + k].copy() if k > 1 else buf[o]
+        o += k
+    return out
+
+
+def eigen_nonsymmetric3(M):
+    """(eval[3], evec[3, 3] rows, eimag[3]) of cv::eigenNonSymmetric as the fit runs it"""
+    M = np.ascontiguousarray(M, np.float64).reshape(9)
+    ev, vec, im = np.zeros(3), np.zeros(9), np.zeros(3)
+    lib().orc_eigen_nonsymmetric3(_p(M), _p(ev), _p(vec), _p(im))
+    return ev, vec.reshape(3, 3), im
+
+
+def direct_unit(dm21, scale, cx, cy):
+    """direct_reduce + direct_finish -> (det, M[9], Ts, RRECT)"""
+    dm = np.ascontiguousarray(dm21, np.float64)
+    assert dm.shape == (21,)
+    det, Ts, M, box = C.c_double(0), C.c_double(0), np.zeros(9), np.zeros(1, RRECT)
+    lib().orc_direct_unit(_p(dm), C.c_double(scale), C.c_double(cx), C.c_double(cy), C.byref(det), _p(M), C.byref(Ts), _p(box))
+    return det.value, M, Ts.value, box[0]
+
+
+def normal_unit(G, g, k):
+    """normal_factor + normal_apply -> (lam[5] (k used), use bits, wmax, wmin, x[5])"""
+    G = np.ascontiguousarray(G, np.float64).reshape(k * k)
+    g = np.ascontiguousarray(g, np.float64).reshape(k)
+    lam, x = np.zeros(5), np.zeros(5)
+    use, wmax, wmin = C.c_int(0), C.c_double(0), C.c_double(0)
+    lib().orc_normal_unit(_p(G), _p(g), int(k), _p(lam), C.byref(use), C.byref(wmax), C.byref(wmin), _p(x))
+    return lam, use.value, wmax.value, wmin.value, x
+
+
+def general_centre(gfp5):
+    gfp = np.ascontiguousarray(gfp5, np.float64).reshape(5)
+    rp = np.zeros(2)
+    lib().orc_general_centre(_p(gfp), _p(rp))
+    return rp
+
+
+def general_finish(gfp3, rp0, rp1, scale, cx, cy):
+    gfp = np.ascontiguousarray(gfp3, np.float64).reshape(3)
+    box = np.zeros(1, RRECT)
+    lib().orc_general_finish(_p(gfp), C.c_double(rp0), C.c_double(rp1), C.c_double(scale), C.c_float(cx), C.c_float(cy), _p(box))
+    return box[0]
+
+
 def make_lightblob(rrect, camp):
     r = np.zeros(1, RRECT)
     r[0] = rrect
