@@ -1,6 +1,6 @@
-// rmcv_ctx.h -- the context behind the ABI's handle and what the two units that implement its entry points share: rmcv_host.hip
-// (context, batches, stage-wise helpers) and rmcv_frame.hip (the per-frame chain).  Private to those two: every other unit goes
-// through the ctx_* functions of rmcv_internal.h.
+// rmcv_ctx.h -- the context behind the ABI's handle and what the three units that implement its entry points share: rmcv_host.hip
+// (context, binding, run, batch setters and getters), rmcv_stagewise.hip (the helpers that run on the caller's own data) and
+// rmcv_frame.hip (the per-frame chain).  Private to those three: every other unit goes through the ctx_* functions of rmcv_internal.h.
 #pragma once
 #include <stdio.h>
 #include <time.h>
@@ -88,12 +88,7 @@ struct rmcv_ctx {
     int pixel_groups = 3;         // RMCV_OPT_PIXEL_GROUPS
     int pixel_shape = 1;          // RMCV_OPT_PIXEL_SHAPE
     int dense_defer = 0;          // RMCV_OPT_DENSE_DEFER
-    int input_format = 0;         // RMCV_OPT_INPUT_FORMAT: 0 BGR, 1..4 a Bayer pattern (a binding records it in Geom::input_format)
-    int input_sample_bits = 8;    // RMCV_OPT_INPUT_SAMPLE_BITS: 8 or 16   } the Bayer frame as the sensor delivers it; recorded by a
-    int input_valid_bit = 0;      // RMCV_OPT_INPUT_VALID_BIT: 0 .. 4      } binding next to the format (Geom::sample_bytes, valid_bit,
-    int input_orient = 0;         // RMCV_OPT_INPUT_ORIENT: RMCV_ORIENT_*  } orient)
-    int enhance = 0;              // RMCV_OPT_ENHANCE: frames are read through their rm::AutoEnhance table (a binding records it in Geom::enhance)
-    float enh_max_gain = 100.0f, enh_min_gain = 50.0f; // rmcv_ctx_set_enhance_gains (include/imgproc.h:35)
+    rmcv::InputOptions input;     // RMCV_OPT_INPUT_*, RMCV_OPT_ENHANCE and its gains: what the next binding records in Geom (bind_plan.h)
     // Waits with a deadline (round 5): no entry point parks its caller in the runtime without a bound.  `last_what` names the kernel or
     // copy enqueued last (every HIPCHK of an enqueue leaves its label here): a wait that runs out returns RMCV_ERR_TIMEOUT with it.
     int wait_timeout_ms = 5000;   // RMCV_OPT_WAIT_TIMEOUT_MS (0: no deadline)
@@ -128,7 +123,11 @@ static int fail(rmcv_ctx* c, int code, const char* what, hipError_t e = hipSucce
     return code;
 }
 
-#define HIPCHK(c, call, what)                                           \
+// a refusal of the plan headers (a message, or a code with it; none: RMCV_OK) as an entry point returns it
+static int refuse(rmcv_ctx* c, const char* why) { return why ? fail(c, RMCV_ERR_BAD_ARG, why) : RMCV_OK; }
+static int refuse(rmcv_ctx* c, const rmcv::Refusal& r) { return r ? fail(c, r.code, r.why) : RMCV_OK; }
+
+#define HIPCHK(c, call, what)                                        \
     do {                                                                \
         (c)->last_what = what;                                          \
         hipError_t e__ = (call);                                        \
@@ -171,6 +170,8 @@ static int wait_event(rmcv_ctx* c, hipEvent_t ev, const char* what)
         const int rcw__ = (call);   \
         if (rcw__) return rcw__;    \
     } while (0)
+// how an entry point that reads results, or rewrites what a batch in flight may read, begins: on the context's device, with all its work finished
+static int ctx_ready(rmcv_ctx* c) { hipSetDevice(c->device); return rmcv_batch_sync(c); }
 
 // Every device buffer of a context lies between two GUARD-byte zones filled with a fixed pattern when the context is created;
 // rmcv_ctx_check_guards reads them back.  A kernel that stores one row, word or record past either end of its buffer -- the
@@ -204,7 +205,24 @@ static hipError_t dalloc_named(rmcv_ctx* c, T** p, size_t count, const char* nam
 namespace rmcv {
 inline PixelVariant geom_variant(const Geom& g) { return pixel_variant(g.input_format, g.enhance, g.win, g.keys); }
 // bytes of one sample of what the context's options describe: 3 per BGR pixel, 1 or 2 per Bayer sample
-inline int ctx_pixel_bytes(const rmcv_ctx* c) { return c->input_format ? c->input_sample_bits / 8 : 3; }
+inline int ctx_pixel_bytes(const rmcv_ctx* c) { return c->input.pixel_bytes(); }
+// every per-frame mode of a binding off: per-run keys (Geom::keys is bind_geom's), camera 0 for every frame, no window requests
+inline void reset_modes(rmcv_ctx* c)
+{
+    c->bufs.key_camps = c->bufs.key_lbs = nullptr;
+    c->bufs.cam_req = nullptr;
+    c->bufs.win_req = nullptr;
+}
+// one armour's row of Bufs::poses, rvec | tvec | world position, into the callers' three arrays (each may be null)
+struct PoseRow { double v[9]; };
+inline void scatter_pose(const PoseRow& row, double* rvecs, double* tvecs, double* positions, size_t dst)
+{
+    for (int k = 0; k < 3; k++) {
+        if (rvecs) rvecs[3 * dst + k] = row.v[k];
+        if (tvecs) tvecs[3 * dst + k] = row.v[3 + k];
+        if (positions) positions[3 * dst + k] = row.v[6 + k];
+    }
+}
 // frame slot 0 of what is bound, for a stage-wise call on the caller's own data (the caller's enemy, whatever keys the batch bound to
 // the context has)
 inline Geom one_frame_geom(const rmcv_ctx* c)
@@ -214,7 +232,8 @@ inline Geom one_frame_geom(const rmcv_ctx* c)
     g1.keys = 0;
     return g1;
 }
-// win_w > 0: the frames are read through win_w x win_h windows (checked by the caller: check_windows)
+// checks and records a binding (bind_plan.h) and enqueues what a change of extent costs; win_w > 0: the frames are read through
+// win_w x win_h windows.  The per-frame modes of the binding before are the caller's to reset (reset_modes).
 int set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t as = nullptr, int win_w = 0, int win_h = 0);
 int ensure_own_frames(rmcv_ctx* c, size_t need);
 int check_layout(rmcv_ctx* c);

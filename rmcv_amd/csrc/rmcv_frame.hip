@@ -360,6 +360,7 @@ static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int
     const int rowb = ctx_pixel_bytes(c) * w; // a mosaic (RMCV_OPT_INPUT_FORMAT): one sample per pixel, 1 or 2 bytes
     const int dstride = (rowb + 15) & ~15;
     if ((rc = set_geom(c, 1, w, h, dstride, (int64_t)dstride * h))) return rc;
+    reset_modes(c);
     if (stride < rowb) return fail(c, RMCV_ERR_BAD_ARG, "bad stride");
     if (c->geom.sample_bytes == 2 && (stride & 1)) return fail(c, RMCV_ERR_BAD_ARG, "16-bit samples (RMCV_OPT_INPUT_SAMPLE_BITS): stride is bytes and must be even");
     if ((rc = ensure_own_frames(c, (size_t)dstride * h))) return rc;

@@ -1,25 +1,20 @@
-// rmcv_host.hip -- the C-ABI of include/rmcv_abi.h: context, HBM buffers, stage sequencing.
+// rmcv_host.hip -- the C-ABI of include/rmcv_abi.h: the context and its HBM buffers, binding a batch, the run, sync, and the batch
+// setters and getters; the tracker and attitude steps and the debug views of a batch.  What a binding and a run decide is bind_plan.h's
+// (pure, checked by a host compiler); the stage-wise helpers are rmcv_stagewise.hip, the context-free entry points rmcv_rules.hip.
 //
 // Host side of the drop-in boundary.  The reference's boundary is the C++ linkage of `librmcv`
 // (/root/reference/CMakeLists.txt:13-16); the calls a maintainer re-hosts on this ABI are exactly
 // rm::extract_color / rm::filter_lightblobs / rm::filter_armours (executable/main.cpp:172-176).
 // No CPU path exists here: every entry point enqueues hand-written HIP kernels.
-#include <math.h>
-#include <cmath>
 #include <sched.h>
 #include <time.h>
 #include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 
 #include <algorithm>
 #include <vector>
 
 #include "rmcv_ctx.h"
-#include "device_bayer.h"
-#include "enhance_math.h"
-#include "device_track.h"
-#include "device_view.h"
 #include "device_pack.h"
 
 using namespace rmcv;
@@ -57,34 +52,6 @@ extern "C" {
 int rmcv_abi_version(void) { return RMCV_ABI_VERSION; }
 int64_t rmcv_pixel_ws_launches(void) { return pixel_ws_launches(); }
 int64_t rmcv_pixel_image_delta_launches(void) { return pixel_image_delta_launches(); }
-
-void rmcv_default_params(rmcv_params* p)
-{ // the literals of executable/main.cpp:172-176
-    memset(p, 0, sizeof(*p));
-    p->camp = RMCV_CAMP_BLUE;
-    p->lower_bound = 80;
-    p->morph = RMCV_MORPH_CLOSE;
-    p->tilt_max = 70.0f;
-    p->ratio_lo = 1.5f;
-    p->ratio_hi = 80.0f;
-    p->area_lo = 10.0;
-    p->area_hi = 99999.0;
-    p->angle_diff_max = 12.0f;
-    p->shear_max = 22.0f;
-    p->length_ratio_max = 0.4f;
-}
-
-void rmcv_default_limits(rmcv_limits* l)
-{
-    memset(l, 0, sizeof(*l));
-    l->max_frames = 256;
-    l->max_width = 1920;
-    l->max_height = 1200;
-    l->max_contours = 2048;
-    l->max_points = 65536;
-    l->max_blobs = 256;
-    l->max_armours = 256;
-}
 
 const char* rmcv_last_error(const rmcv_ctx* ctx) { return ctx ? ctx->err : "null context"; }
 
@@ -239,7 +206,7 @@ bool pixel_ws_full(const rmcv_ctx* c, int lower_bound, const RunPlan& plan)
     return pixel_shape(pixel_batch(c->geom, c->bufs, geom_variant(c->geom), lower_bound, plan)).ws_full;
 }
 RunPlan ctx_plan(const rmcv_ctx* c) { return {c->pixel_shape, c->pixel_groups, c->sparse_waves, c->dense_defer ? SPARSE_SPLIT_BOTH : SPARSE_STANDARD}; }
-int ctx_enhance(const rmcv_ctx* c) { return c->enhance; }
+int ctx_enhance(const rmcv_ctx* c) { return c->input.enhance; }
 int ctx_n_cameras(const rmcv_ctx* c) { return c->bufs.pnp_cams ? c->bufs.n_cameras : 0; }
 void ctx_set_frame_cameras(rmcv_ctx* c, const void* d_idx) { c->bufs.cam_req = (const int32_t*)d_idx; }
 PixelVariant ctx_pixel_variant(const rmcv_ctx* c) { return geom_variant(c->geom); }
@@ -381,112 +348,120 @@ __global__ void k_delay(unsigned long long ns)
 hipError_t launch_delay(unsigned long long ns, hipStream_t s) { return launch(k_delay, dim3(1), dim3(64), 0, s, ns); }
 } // namespace rmcv
 
-// Bind a geometry.  When it changes the padded planes are zeroed (their pads must read 0) and the frame order is recomputed -- both
-// ENQUEUED: on `as` when the caller (a pipeline) orders this context's work on its own streams and has already made `as` wait for the
-// context's last batch; otherwise on the context's stream, behind a wait for everything the context has in flight and with a wait for
-// them behind (the launches that follow may go to any stream of the caller's).
-// BGR frames have no sample size and no orientation of their own: a context left at 16 bits or mirrored / flipped would read them wrongly
-int rmcv::check_layout(rmcv_ctx* c)
-{
-    if (c->input_format != RMCV_INPUT_BGR) return RMCV_OK;
-    if (c->input_sample_bits != 8) return fail(c, RMCV_ERR_BAD_ARG, "a BGR frame with RMCV_OPT_INPUT_SAMPLE_BITS = 16: the option is for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
-    if (c->input_orient != 0) return fail(c, RMCV_ERR_BAD_ARG, "a BGR frame with RMCV_OPT_INPUT_ORIENT set: the option is for Bayer frames (RMCV_OPT_INPUT_FORMAT)");
-    return RMCV_OK;
-}
+// ---- binding a geometry: what is refused and what is recorded is bind_plan.h's; here are the HIP calls ----
+int rmcv::check_layout(rmcv_ctx* c) { return refuse(c, layout_refusal(c->input)); }
 // a frame pointer of 2-byte samples
 int rmcv::check_sample_ptr(rmcv_ctx* c, const void* p)
 {
-    if (c->input_format && c->input_sample_bits == 16 && ((uintptr_t)p & 1))
+    if (c->input.format && c->input.sample_bits == 16 && ((uintptr_t)p & 1))
         return fail(c, RMCV_ERR_BAD_ARG, "16-bit samples (RMCV_OPT_INPUT_SAMPLE_BITS): the frame pointer must be 2-byte aligned");
-    return RMCV_OK;
-}
-
-// a combination of modes pixel_refusal (pixel_plan.h) has a message for
-static int refuse(rmcv_ctx* c, const char* why) { return why ? fail(c, RMCV_ERR_BAD_ARG, why) : RMCV_OK; }
-
-// what rmcv_batch_set_windows refuses, checked before anything of the context moves (fw x fh: the frames; fmt / enh: what they are read as)
-static int check_windows(rmcv_ctx* c, int fw, int fh, int fmt, int enh, int win_w, int win_h)
-{
-    if (const int rc = refuse(c, pixel_refusal(fmt, enh, true, false, false))) return rc;
-    if (win_w < 1 || win_h < 1) return fail(c, RMCV_ERR_BAD_ARG, "window size out of range: win_w and win_h must be at least 1");
-    if (win_w > fw || win_h > fh) return fail(c, RMCV_ERR_BAD_ARG, "window size out of range: larger than the frames");
-    if (win_w > c->lim.max_width || win_h > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, "window size out of range: larger than the context's limits");
     return RMCV_OK;
 }
 
 // what per-frame detection keys refuse of the frames' format (fmt / enh: what they are read as), checked before anything of the context moves
 static int check_frame_camps(rmcv_ctx* c, int fmt, int enh) { return refuse(c, pixel_refusal(fmt, enh, false, true, false)); }
 
-// Make w x h the extent everything behind the frame loads sees (the frames' own, or their windows').  When it changes the padded planes
-// are zeroed and the frame order is recomputed, as set_geom's comment says.
-static int set_extent(rmcv_ctx* c, int w, int h, hipStream_t as);
-
-// win_w > 0: the frames are read through win_w x win_h windows (checked by the caller: check_windows)
-int rmcv::set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t as, int win_w, int win_h)
+// The extent in Geom (extent_fields) has been set.  When it changes the padded planes are zeroed (their pads must read 0) and the frame
+// order is recomputed -- both ENQUEUED: on `as` when the caller (a pipeline) orders this context's work on its own streams and has
+// already made `as` wait for the context's last batch; otherwise on the context's stream, behind a wait for everything the context has
+// in flight and with a wait for them behind (the launches that follow may go to any stream of the caller's).
+static int extent_apply(rmcv_ctx* c, hipStream_t as)
 {
-    if (n_frames < 1 || n_frames > c->lim.max_frames) return fail(c, RMCV_ERR_BAD_ARG, "n_frames out of range");
-    if (w < 1 || h < 1 || w > c->lim.max_width || h > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, "frame size out of range");
-    { const int rcl = check_layout(c); if (rcl) return rcl; }
-    const int bpp = ctx_pixel_bytes(c); // bytes per pixel of what is bound (RMCV_OPT_INPUT_FORMAT, RMCV_OPT_INPUT_SAMPLE_BITS)
-    if (c->input_format && (w < 3 || h < 3)) return fail(c, RMCV_ERR_BAD_ARG, "a Bayer frame needs w >= 3 and h >= 3");
-    if (stride < bpp * w || frame_pitch < (int64_t)stride * (h - 1) + bpp * w) return fail(c, RMCV_ERR_BAD_ARG, "bad stride/pitch");
-    if (bpp == 2 && ((stride & 1) || (frame_pitch & 1))) return fail(c, RMCV_ERR_BAD_ARG, "16-bit samples (RMCV_OPT_INPUT_SAMPLE_BITS): stride and frame_pitch are bytes and must be even");
-    { const int rcr = refuse(c, pixel_refusal(c->input_format, c->enhance, false, false, false)); if (rcr) return rcr; }
-    if (win_w > 0) { const int rcw = check_windows(c, w, h, c->input_format, c->enhance, win_w, win_h); if (rcw) return rcw; }
-    { const int rcm = ensure_mid(c, n_frames); if (rcm) return rcm; }
-    Geom& g = c->geom;
-    g.enhance = c->enhance;
-    g.enh_max_gain = c->enh_max_gain;
-    g.enh_min_gain = c->enh_min_gain;
-    g.input_format = c->input_format;
-    g.sample_bytes = c->input_format ? c->input_sample_bits / 8 : 1;
-    g.valid_bit = g.sample_bytes == 2 ? c->input_valid_bit : 0;
-    g.orient = c->input_format ? c->input_orient : 0;
-    g.n_frames = n_frames;
-    g.stride = stride;
-    g.frame_pitch = frame_pitch;
-    g.frame_w = w;
-    g.frame_h = h;
-    g.win = win_w > 0;
-    g.keys = 0; // a new binding returns to per-run keys, as it returns to whole frames
-    c->bufs.key_camps = c->bufs.key_lbs = nullptr;
-    c->bufs.cam_req = nullptr; // ... and to camera 0 for every frame
-    return set_extent(c, g.win ? win_w : w, g.win ? win_h : h, as);
-}
-
-static int set_extent(rmcv_ctx* c, int w, int h, hipStream_t as)
-{
-    Geom& g = c->geom;
-    const int n_frames = g.n_frames;
-    g.w = w;
-    g.h = h;
-    g.ww = (w + 63) / 64;
-    g.prow = g.ww + 2;
-    g.plane_pitch = (int64_t)(h + 2) * g.prow;
-    const bool planes_change = c->geom_w != w || c->geom_h != h, order_change = c->order_n != n_frames || c->order_h != h;
-    if (!planes_change && !order_change) return RMCV_OK;
+    const Geom& g = c->geom;
+    const ExtentChange change = extent_change(c->geom_w, c->geom_h, c->order_n, c->order_h, g.w, g.h, g.n_frames);
+    if (!change.planes && !change.order) return RMCV_OK;
     hipStream_t s = as ? as : c->stream;
     if (!as) { // the planes are re-zeroed and the frame order rewritten under the kernels' feet otherwise
         c->blocking_calls++;
         const int rcs = rmcv_batch_sync(c);
         if (rcs) return rcs;
     }
-    if (planes_change) {
+    if (change.planes) {
         const size_t plane = (size_t)(c->lim.max_height + 2) * ((c->lim.max_width + 63) / 64 + 2);
         HIPCHK(c, hipMemsetAsync(c->bufs.bits, 0, (size_t)c->lim.max_frames * plane * 8, s), "memset planes");
         HIPCHK(c, hipMemsetAsync(c->bufs.lab, 0, (size_t)c->lim.max_frames * plane * 8, s), "memset planes");
         HIPCHK(c, hipMemsetAsync(c->bufs.neg, 0, (size_t)c->lim.max_frames * plane * 8, s), "memset planes");
-        c->geom_w = w;
-        c->geom_h = h;
+        c->geom_w = g.w;
+        c->geom_h = g.h;
         c->image = IMAGE_STATE_UNKNOWN; // rows and frames of the byte image and of its mask now start elsewhere
     }
-    if (order_change) {
-        const int strips = (h + STRIP_ROWS - 1) / STRIP_ROWS;
-        HIPCHK(c, launch(k_frame_order, dim3(1), dim3(256), 0, s, c->bufs.frame_order, c->order_scratch, n_frames, strips), "k_frame_order");
-        c->order_n = n_frames;
-        c->order_h = h;
+    if (change.order) {
+        const int strips = (g.h + STRIP_ROWS - 1) / STRIP_ROWS;
+        HIPCHK(c, launch(k_frame_order, dim3(1), dim3(256), 0, s, c->bufs.frame_order, c->order_scratch, g.n_frames, strips), "k_frame_order");
+        c->order_n = g.n_frames;
+        c->order_h = g.h;
     }
     if (!as) WAITCHK(c, wait_stream(c, s, "binding a geometry"));
+    return RMCV_OK;
+}
+
+// win_w > 0: the frames are read through win_w x win_h windows
+int rmcv::set_geom(rmcv_ctx* c, int n_frames, int w, int h, int stride, int64_t frame_pitch, hipStream_t as, int win_w, int win_h)
+{
+    int rc = refuse(c, binding_refusal(c->lim, c->input, n_frames, w, h, stride, frame_pitch, win_w, win_h));
+    if (rc || (rc = ensure_mid(c, n_frames))) return rc;
+    bind_geom(c->geom, c->input, n_frames, w, h, stride, frame_pitch, win_w, win_h);
+    return extent_apply(c, as);
+}
+
+// The tail of every binder: `frames` are what the context reads from now on.  A new batch starts with every per-frame mode off
+// (reset_modes), the host's pose matrices (an attitude step's were its batch's) and nothing of it run.
+static int bound(rmcv_ctx* c, const void* frames)
+{
+    c->bufs.frames = (const uint8_t*)frames;
+    reset_modes(c);
+    c->bufs.pose_base2gripper = c->bufs.base2gripper;
+    c->last_stages = 0;
+    return RMCV_OK;
+}
+
+// ---- the shapes the batch setters and getters share ----
+
+// A per-frame request table (window origins, camps, lower bounds, cameras) is the host's values, copied into the context's `own` table
+// once nothing in flight reads it (`sync`: the caller has not waited already), or the caller's device memory, borrowed; both null: off.
+// *req is what the runs read from then on; it changes only on success.
+template <typename T>
+static int set_request_table(rmcv_ctx* c, const T** req, T* own, const T* h_vals, const void* d_vals, bool sync, const char* what)
+{
+    if (h_vals) {
+        if (sync) {
+            if (const int rc = ctx_ready(c)) return rc; // the table about to be rewritten may still be read by a batch in flight
+        }
+        HIPCHK(c, hipMemcpy(own, h_vals, (size_t)c->geom.n_frames * sizeof(T), hipMemcpyHostToDevice), what);
+    }
+    *req = h_vals ? own : (const T*)d_vals;
+    return RMCV_OK;
+}
+
+// An effective per-frame table as the last run left it, for the first `cap` frames bound (the context is ready: the caller has waited):
+// d_eff's entries while the mode is on, `off` for every frame otherwise
+template <typename T>
+static int get_effective_table(rmcv_ctx* c, T* out, int cap, bool on, const T* d_eff, const T& off, const char* what)
+{
+    const int n = std::min(cap, c->geom.n_frames);
+    if (n <= 0) return RMCV_OK;
+    if (!on) std::fill_n(out, n, off);
+    else HIPCHK(c, hipMemcpy(out, d_eff, (size_t)n * sizeof(T), hipMemcpyDeviceToHost), what);
+    return RMCV_OK;
+}
+
+// the armour counts of the frames bound and their sum: what the gathers go by
+static int armour_counts(rmcv_ctx* c, std::vector<int32_t>& cnt, int64_t* total)
+{
+    cnt.resize(c->geom.n_frames);
+    HIPCHK(c, hipMemcpy(cnt.data(), c->bufs.n_armours, cnt.size() * 4, hipMemcpyDeviceToHost), "D2H");
+    *total = 0;
+    for (const int32_t n : cnt) *total += n;
+    return RMCV_OK;
+}
+// the first cnt[f] rows of every frame's block of a device table [frame][max_armours], frame after frame
+template <typename T>
+static int gather_rows(rmcv_ctx* c, const T* d_table, const std::vector<int32_t>& cnt, T* out, const char* what)
+{
+    const size_t row_cap = (size_t)c->lim.max_armours;
+    std::vector<T> all(cnt.size() * row_cap);
+    HIPCHK(c, hipMemcpy(all.data(), d_table, all.size() * sizeof(T), hipMemcpyDeviceToHost), what);
+    for (size_t f = 0; f < cnt.size(); f++) out = std::copy_n(all.data() + f * row_cap, cnt[f], out);
     return RMCV_OK;
 }
 
@@ -508,126 +483,90 @@ static int order_end(rmcv_ctx* c, hipStream_t s)
     return RMCV_OK;
 }
 
+// One run: the launches run_steps (bind_plan.h) decides on, in its order; `timed`: the events of rmcv_batch_run_timed between the stages
 static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t s, bool timed, const RunPlan& plan,
                       const rmcv_legacy_params* lp = nullptr, bool* lean = nullptr)
 {
     const Geom& g = c->geom;
     const Bufs& b = c->bufs;
+    const Limits& lim = c->lim;
+    const RunSteps st = run_steps(stages, timed, lp != nullptr, g.input_format, g.enhance, g.win, g.keys);
     int k = 0;
     resident_none(c);
     int rc;
     // every argument check comes BEFORE the first enqueue (the callers': check_bound): an error return leaves the streams as they were
-    if (lp && (rc = refuse(c, pixel_refusal(g.input_format, g.enhance, false, g.keys != 0, true)))) return rc;
-    if ((rc = order_begin(c, s))) return rc;
+    if ((rc = refuse(c, st.refusal)) || (rc = order_begin(c, s))) return rc;
     if (c->test_delay_us) { // RMCV_OPT_TEST_DELAY_US: a stand-in for a kernel that does not finish in time (one shot)
         HIPCHK(c, launch_delay((unsigned long long)c->test_delay_us * 1000ull, s), "k_delay (RMCV_OPT_TEST_DELAY_US)");
         c->test_delay_us = 0;
     }
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
-    // Status bits belong to the stage that sets them: k_contours rewrites the whole word; a run that starts at a later stage
-    // clears only the bits of the stages it runs, so OVF_CONTOURS / OVF_POINTS / SLOW_PATH of the contour run it builds on survive.
-    if (!(stages & RMCV_STAGE_CONTOURS)) {
-        const int own = ((stages & RMCV_STAGE_BLOBS) ? (RMCV_FRAME_OVF_BLOBS | RMCV_FRAME_HULL) : 0) |
-                        ((stages & RMCV_STAGE_ARMOURS) ? RMCV_FRAME_OVF_ARMOURS : 0);
-        if (own) HIPCHK(c, launch_status_clear(g, b, own, s), "k_status_clear");
-    }
-    // findContours + filter_lightblobs (+ filter_armours) as ONE per-frame kernel when the stages are asked for together;
-    // the per-stage events of rmcv_batch_run_timed need per-stage launches
+    if (st.status_clear) HIPCHK(c, launch_status_clear(g, b, st.status_clear, s), "k_status_clear");
     if (lean) *lean = false;
-    const bool one_sparse = !timed && !lp && (stages & RMCV_STAGE_CONTOURS) && (stages & RMCV_STAGE_BLOBS);
-    if (stages & RMCV_STAGE_BINARY) {
-        // RMCV_OPT_ENHANCE: every frame's sums, gamma and tables first, at RUN time (borrowed frames may have changed since they were bound)
-        if (g.enhance) HIPCHK(c, launch_enhance_tables(g, b, p->lower_bound, s), "k_frame_sums + k_enhance_table");
-        // windows: the effective origins first, at RUN time too (the requests may be a tracker's, rewritten on the device since they were set)
-        if (g.win) HIPCHK(c, launch_window_origins(g, b, s), "k_window_origins");
-        // per-frame keys: the effective keys first, at RUN time too (the raw tables may be a device-side producer's; lower_bounds null: this run's bound)
-        if (g.keys) HIPCHK(c, launch_frame_keys(g, b, p->lower_bound, s), "k_frame_keys");
+    if (st.enhance_tables) HIPCHK(c, launch_enhance_tables(g, b, p->lower_bound, s), "k_frame_sums + k_enhance_table");
+    if (st.window_origins) HIPCHK(c, launch_window_origins(g, b, s), "k_window_origins");
+    if (st.frame_keys) HIPCHK(c, launch_frame_keys(g, b, p->lower_bound, s), "k_frame_keys");
+    if (st.binary) {
         c->last_camp = p->camp;
         c->last_lower_bound = p->lower_bound;
-        HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, !(stages & RMCV_STAGE_NO_IMAGE), plan, s, &c->image), PIXEL_VARIANTS[geom_variant(g)].kernel);
+        HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, st.image, plan, s, &c->image), PIXEL_VARIANTS[geom_variant(g)].kernel);
     }
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
-    // the icon classifier rides in the per-frame kernel when the armours come from it (BASELINE config 5: no launch of its own)
-    // (not for mosaics: the sparse kernel's classifier reads BGR; k_classify has the Bayer accessor -- and the one through a frame's gamma table)
-    const bool identity_fused = one_sparse && (stages & RMCV_STAGE_ARMOURS) && (stages & RMCV_STAGE_IDENTITY) && g.input_format == RMCV_INPUT_BGR && !g.enhance && !g.win; // (windows: k_classify takes the origins)
-    if (one_sparse) HIPCHK(c, launch_sparse(g, b, c->lim, *p, (stages & RMCV_STAGE_ARMOURS) != 0, identity_fused, plan, s, lean), "k_contours (fused)");
-    else if (stages & RMCV_STAGE_CONTOURS) HIPCHK(c, launch_contours(g, b, c->lim, s), "k_contours");
+    if (st.sparse) HIPCHK(c, launch_sparse(g, b, lim, *p, st.sparse_pairs, st.sparse_identity, plan, s, lean), "k_contours (fused)");
+    if (st.contours) HIPCHK(c, launch_contours(g, b, lim, s), "k_contours");
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
-    const bool fused = (stages & RMCV_STAGE_BLOBS) && (stages & RMCV_STAGE_ARMOURS); // one launch for both
-    if (one_sparse) {
-    } else if (lp && (stages & RMCV_STAGE_BLOBS)) HIPCHK(c, launch_match(g, b, c->lim, *p, *lp, 0, b.frames != nullptr, fused, s), "k_match");
-    else if (fused) HIPCHK(c, launch_blobs_armours(g, b, c->lim, *p, s), "k_fit");
-    else if (stages & RMCV_STAGE_BLOBS) HIPCHK(c, launch_blobs(g, b, c->lim, *p, s), "k_fit");
+    if (st.match) HIPCHK(c, launch_match(g, b, lim, *p, *lp, 0, b.frames != nullptr, st.match_pairs, s), "k_match");
+    if (st.blobs_armours) HIPCHK(c, launch_blobs_armours(g, b, lim, *p, s), "k_fit");
+    if (st.blobs) HIPCHK(c, launch_blobs(g, b, lim, *p, s), "k_fit");
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
-    if (!one_sparse && !fused && (stages & RMCV_STAGE_ARMOURS)) HIPCHK(c, launch_armours(g, b, c->lim, *p, s), "k_armours");
-    if ((stages & RMCV_STAGE_IDENTITY) && !identity_fused) HIPCHK(c, launch_classify(g, b, c->lim, s), "k_classify");
-    if (stages & RMCV_STAGE_POSE) HIPCHK(c, launch_pnp(g, b, c->lim, s), "k_pnp");
+    if (st.armours) HIPCHK(c, launch_armours(g, b, lim, *p, s), "k_armours");
+    if (st.classify) HIPCHK(c, launch_classify(g, b, lim, s), "k_classify");
+    if (st.pnp) HIPCHK(c, launch_pnp(g, b, lim, s), "k_pnp");
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
-    c->last_stages = (stages & RMCV_STAGE_BINARY) ? stages : (c->last_stages | stages);
+    c->last_stages = next_last_stages(c->last_stages, stages);
     return order_end(c, s);
 }
 
-static int check_params(rmcv_ctx* c, const rmcv_params* p, int stages)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!p) return fail(c, RMCV_ERR_BAD_ARG, "null params");
-    if (p->morph < RMCV_MORPH_NONE || p->morph > RMCV_MORPH_CLOSE) return fail(c, RMCV_ERR_BAD_ARG, "bad morph");
-    if (stages <= 0 || stages > (RMCV_STAGE_ALL | RMCV_STAGE_IDENTITY | RMCV_STAGE_POSE | RMCV_STAGE_NO_IMAGE)) return fail(c, RMCV_ERR_BAD_ARG, "bad stage mask");
-    if ((stages & RMCV_STAGE_IDENTITY) && !c->bufs.svm_w) return fail(c, RMCV_ERR_BAD_ARG, "RMCV_STAGE_IDENTITY needs rmcv_svm_load first");
-    if ((stages & RMCV_STAGE_POSE) && !c->bufs.pnp_cfg) return fail(c, RMCV_ERR_BAD_ARG, "RMCV_STAGE_POSE needs rmcv_pnp_load first");
-    return RMCV_OK;
-}
-// check_params of the public entry points, which run on what the caller has bound
-static int check_bound(rmcv_ctx* c, const rmcv_params* p, int stages)
-{
-    const int rc = check_params(c, p, stages);
-    if (rc) return rc;
-    if ((c->geom.n_frames <= 0 || !c->bufs.frames) && (stages & RMCV_STAGE_BINARY)) return fail(c, RMCV_ERR_BAD_ARG, "no frames bound");
-    return RMCV_OK;
-}
-
-namespace rmcv {
 // everything rmcv_batch_run would refuse for this stage mask, WITHOUT enqueuing anything and before any frames are bound: the pipeline
 // splits a batch into several runs on different streams and must not find out at the second one that the batch cannot run (a pixel
 // kernel already enqueued, nothing ordered behind it), nor after its binding has enqueued a change of geometry
-int ctx_check_stages(rmcv_ctx* c, const rmcv_params* p, int stages) { return check_params(c, p, stages); }
-} // namespace rmcv
+int rmcv::ctx_check_stages(rmcv_ctx* c, const rmcv_params* p, int stages)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    return refuse(c, stage_refusal(p, stages, c->bufs.svm_w != nullptr, c->bufs.pnp_cfg != nullptr));
+}
+// ... of the public entry points, which run on what the caller has bound
+static int check_bound(rmcv_ctx* c, const rmcv_params* p, int stages)
+{
+    if (const int rc = ctx_check_stages(c, p, stages)) return rc;
+    if ((c->geom.n_frames <= 0 || !c->bufs.frames) && (stages & RMCV_STAGE_BINARY)) return fail(c, RMCV_ERR_BAD_ARG, "no frames bound");
+    return RMCV_OK;
+}
 
 extern "C" {
 
 int rmcv_batch_upload(rmcv_ctx* c, const uint8_t* frames, int n_frames, int w, int h, int stride, int64_t frame_pitch)
 {
     if (!c || !frames) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c); // the buffer about to be overwritten may still be read by a batch in flight
+    int rc = ctx_ready(c); // the buffer about to be overwritten may still be read by a batch in flight
     if (rc) return rc;
     resident_none(c);
-    // device layout: tightly packed rows (stride 3*w -- w or 2*w for a mosaic -- rounded up to 16 bytes), frames back to back
     if ((rc = check_layout(c)) || (rc = check_sample_ptr(c, frames))) return rc;
-    const int bpp = ctx_pixel_bytes(c);
-    const int rowb = bpp * w;
-    if (c->input_format && (stride < rowb || frame_pitch < (int64_t)stride * (h - 1) + rowb)) return fail(c, RMCV_ERR_BAD_ARG, "bad stride/pitch");
-    if (bpp == 2 && ((stride & 1) || (frame_pitch & 1))) return fail(c, RMCV_ERR_BAD_ARG, "16-bit samples (RMCV_OPT_INPUT_SAMPLE_BITS): stride and frame_pitch are bytes and must be even");
-    const int dstride = (rowb + 15) & ~15;
-    const int64_t dpitch = (int64_t)dstride * h;
-    rc = set_geom(c, n_frames, w, h, dstride, dpitch);
-    if (rc) return rc;
-    const size_t need = (size_t)dpitch * n_frames;
+    const UploadLayout dev = upload_layout(ctx_pixel_bytes(c), w, h);
+    if ((rc = refuse(c, dev.refusal(stride, frame_pitch))) || (rc = set_geom(c, n_frames, w, h, dev.stride, dev.pitch))) return rc;
+    const size_t need = (size_t)dev.pitch * n_frames;
     rc = ensure_own_frames(c, need);
     if (rc) return rc;
-    if (stride == dstride && frame_pitch == dpitch) {
+    if (dev.same(stride, frame_pitch)) {
         HIPCHK(c, hipMemcpyAsync(c->own_frames, frames, need, hipMemcpyHostToDevice, c->stream), "H2D frames");
     } else {
         for (int f = 0; f < n_frames; f++)
-            HIPCHK(c, hipMemcpy2DAsync(c->own_frames + (size_t)f * dpitch, dstride, frames + (size_t)f * frame_pitch, stride,
-                                       (size_t)rowb, h, hipMemcpyHostToDevice, c->stream),
+            HIPCHK(c, hipMemcpy2DAsync(c->own_frames + (size_t)f * dev.pitch, dev.stride, frames + (size_t)f * frame_pitch, stride,
+                                       (size_t)dev.row_bytes, h, hipMemcpyHostToDevice, c->stream),
                    "H2D frames 2D");
     }
     WAITCHK(c, wait_stream(c, c->stream, "H2D frames"));
-    c->bufs.frames = c->own_frames;
-    c->bufs.pose_base2gripper = c->bufs.base2gripper; // (an attitude step's matrices were its batch's)
-    c->last_stages = 0; // a new batch: nothing of it has run
-    return RMCV_OK;
+    return bound(c, c->own_frames);
 }
 
 int rmcv_batch_set_device_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int h, int stride,
@@ -640,10 +579,7 @@ int rmcv_batch_set_device_frames(rmcv_ctx* c, const void* d_frames, int n_frames
     if (rc) return rc;
     rc = set_geom(c, n_frames, w, h, stride, frame_pitch);
     if (rc) return rc;
-    c->bufs.frames = (const uint8_t*)d_frames;
-    c->bufs.pose_base2gripper = c->bufs.base2gripper;
-    c->last_stages = 0;
-    return RMCV_OK;
+    return bound(c, d_frames);
 }
 
 } // extern "C"
@@ -657,20 +593,17 @@ int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int 
     resident_none(c);
     int rc = check_sample_ptr(c, d_frames);
     if (rc) return rc;
-    if (d_camps && (rc = check_frame_camps(c, c->input_format, c->enhance))) return rc;
+    if (d_camps && (rc = check_frame_camps(c, c->input.format, c->input.enhance))) return rc;
     if (d_origins && win_w <= 0) return fail(c, RMCV_ERR_BAD_ARG, "window size out of range: win_w and win_h must be at least 1");
     rc = set_geom(c, n_frames, w, h, stride, frame_pitch, s, d_origins ? win_w : 0, win_h);
-    if (rc) return rc;
-    c->bufs.frames = (const uint8_t*)d_frames;
+    if (rc || (rc = bound(c, d_frames))) return rc;
     c->bufs.win_req = (const rmcv_point*)d_origins; // (the run computes the effective origins in front of its pixel pass)
     c->geom.keys = d_camps != nullptr;              // (... and the effective keys)
     c->bufs.key_camps = (const int32_t*)d_camps;
     c->bufs.key_lbs = d_camps ? (const int32_t*)d_lower_bounds : nullptr;
-    c->bufs.pose_base2gripper = c->bufs.base2gripper;
-    c->last_stages = 0;
     return RMCV_OK;
 }
-int ctx_check_modes(rmcv_ctx* c, bool keys, bool legacy) { return refuse(c, pixel_refusal(c->input_format, c->enhance, false, keys, legacy)); }
+int ctx_check_modes(rmcv_ctx* c, bool keys, bool legacy) { return refuse(c, pixel_refusal(c->input.format, c->input.enhance, false, keys, legacy)); }
 // what binding a batch would allocate, now (a pipeline does this for every context of its ring when it is created)
 int ctx_prepare_ring(rmcv_ctx* c) { return ensure_mid(c, c->lim.max_frames); }
 int ctx_run(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_params* lp, int stages, hipStream_t s, const RunPlan& plan, bool* lean)
@@ -696,7 +629,7 @@ int rmcv_batch_run_legacy(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_p
     if (rc) return rc;
     if (!lp) return fail(c, RMCV_ERR_BAD_ARG, "null legacy params");
     // (the context's options as they are set now count beside what the frames were bound with; per-frame camps: run_stages)
-    if ((rc = refuse(c, pixel_refusal(c->input_format | c->geom.input_format, c->enhance | c->geom.enhance, false, false, true)))) return rc;
+    if ((rc = refuse(c, pixel_refusal(c->input.format | c->geom.input_format, c->input.enhance | c->geom.enhance, false, false, true)))) return rc;
     hipSetDevice(c->device);
     return run_stages(c, p, stages, hip_stream ? (hipStream_t)hip_stream : c->stream, false, ctx_plan(c), lp);
 }
@@ -704,94 +637,37 @@ int rmcv_batch_run_legacy(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_p
 int rmcv_ctx_set_option(rmcv_ctx* c, int option, int value)
 {
     if (!c) return RMCV_ERR_BAD_ARG;
-    if (option == RMCV_OPT_SPARSE_WAVES && (value == 4 || value == 8)) {
-        c->sparse_waves = value;
-        return RMCV_OK;
+    const OptionRule* rule = option_rule(option); // the values each option takes: bind_plan.h
+    if (!rule || !rule->accepts(value)) return fail(c, RMCV_ERR_BAD_ARG, "unknown option or value");
+    switch (option) {
+    case RMCV_OPT_SPARSE_WAVES: c->sparse_waves = value; break;
+    case RMCV_OPT_RUN_AHEAD: c->chain.run_ahead = value; break;
+    case RMCV_OPT_FRAME_UPLOAD: c->chain.frame_upload = value, c->chain.copy_up = {}; break;
+    case RMCV_OPT_TEST_SLOW_US: c->chain.test_slow_us = value; break;
+    case RMCV_OPT_PIXEL_HALO_NT: c->geom.pixel_halo_nt = value; break;
+    case OPT_PIXEL_ROWQUAD: c->geom.pixel_rowquad = value; break; // k_binary's row-quad loader even where rows are contiguous (one pipeline, regions alternating)
+    case RMCV_OPT_PIXEL_SHAPE: c->pixel_shape = value; break;
+    case RMCV_OPT_OVERLOADS: c->geom.overloads = value, resident_none(c); break; // (results run ahead with the other setting are not this setting's)
+    case RMCV_OPT_DENSE_DEFER: c->dense_defer = value; break;
+    case RMCV_OPT_CONTOUR_TIER: c->geom.contour_tier = value; break;
+    case RMCV_OPT_IMAGE_EXPORT: c->chain.image_export = value, c->chain.copy_img = {}; break;
+    case RMCV_OPT_WAIT_TIMEOUT_MS: c->wait_timeout_ms = value; break;
+    case RMCV_OPT_TEST_DELAY_US: c->test_delay_us = value; break;
+    // the input options: frames bound before keep what they were bound with
+    case RMCV_OPT_INPUT_FORMAT: c->input.format = value; break;
+    case RMCV_OPT_INPUT_SAMPLE_BITS: c->input.sample_bits = value; break;
+    case RMCV_OPT_INPUT_VALID_BIT: c->input.valid_bit = value; break;
+    case RMCV_OPT_INPUT_ORIENT: c->input.orient = value; break;
+    case RMCV_OPT_ENHANCE: c->input.enhance = value; break;
+    case RMCV_OPT_PIXEL_GROUPS: c->pixel_groups = value; break;
     }
-    if (option == RMCV_OPT_RUN_AHEAD && (value == 0 || value == 1)) {
-        c->chain.run_ahead = value;
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_FRAME_UPLOAD && value >= 0 && value <= 3) {
-        c->chain.frame_upload = value;
-        c->chain.copy_up = {};
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_TEST_SLOW_US && value >= 0) {
-        c->chain.test_slow_us = value;
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_PIXEL_HALO_NT && (value == 0 || value == 1)) {
-        c->geom.pixel_halo_nt = value;
-        return RMCV_OK;
-    }
-    if (option == 1001 && (value == 0 || value == 1)) { // dev (not in the header): k_binary's row-quad loader even where rows are contiguous,
-        c->geom.pixel_rowquad = value;                  // for bench.py's RMCV_BENCH_AB=1001:0:1 (one pipeline, regions alternating)
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_PIXEL_SHAPE && (value == 0 || value == 1)) {
-        c->pixel_shape = value;
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_OVERLOADS && value >= 0 && value <= 3) {
-        c->geom.overloads = value;
-        resident_none(c); // (results run ahead with the other setting are not this setting's)
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_DENSE_DEFER && (value == 0 || value == 1)) {
-        c->dense_defer = value;
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_CONTOUR_TIER && value >= 0 && value <= 2) {
-        c->geom.contour_tier = value;
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_IMAGE_EXPORT && value >= 0 && value <= 2) {
-        c->chain.image_export = value;
-        c->chain.copy_img = {};
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_WAIT_TIMEOUT_MS && value >= 0) {
-        c->wait_timeout_ms = value;
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_TEST_DELAY_US && value >= 0 && value <= 10000000) {
-        c->test_delay_us = value;
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_INPUT_FORMAT && value >= RMCV_INPUT_BGR && value <= RMCV_BAYER_BG) {
-        c->input_format = value; // (frames bound before keep the format they were bound with)
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_INPUT_SAMPLE_BITS && (value == 8 || value == 16)) {
-        c->input_sample_bits = value; // (like the format: frames bound before keep what they were bound with)
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_INPUT_VALID_BIT && value >= 0 && value <= 4) {
-        c->input_valid_bit = value;
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_INPUT_ORIENT && value >= 0 && value <= (RMCV_ORIENT_MIRROR | RMCV_ORIENT_FLIP)) {
-        c->input_orient = value;
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_ENHANCE && (value == 0 || value == 1)) {
-        c->enhance = value; // (like the format: frames bound before keep what they were bound with)
-        return RMCV_OK;
-    }
-    if (option == RMCV_OPT_PIXEL_GROUPS && value >= 1 && value <= 8) {
-        c->pixel_groups = value;
-        return RMCV_OK;
-    }
-    return fail(c, RMCV_ERR_BAD_ARG, "unknown option or value");
+    return RMCV_OK;
 }
 
 int rmcv_ctx_check_guards(rmcv_ctx* c, int32_t* n_damaged)
 {
     if (!c || !n_damaged) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
+    if (const int rc = ctx_ready(c)) return rc;
     std::vector<uint8_t> h;
     int bad = 0;
     c->err[0] = 0;
@@ -845,9 +721,7 @@ int rmcv_batch_counts(rmcv_ctx* c, int32_t* n_contours, int32_t* n_points, int32
                       int32_t* status)
 {
     if (!c) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
+    if (const int rc = ctx_ready(c)) return rc;
     const size_t n = (size_t)c->geom.n_frames * 4;
     if (n_contours) HIPCHK(c, hipMemcpy(n_contours, c->bufs.n_contours, n, hipMemcpyDeviceToHost), "D2H");
     if (n_points) HIPCHK(c, hipMemcpy(n_points, c->bufs.n_points, n, hipMemcpyDeviceToHost), "D2H");
@@ -860,9 +734,7 @@ int rmcv_batch_counts(rmcv_ctx* c, int32_t* n_contours, int32_t* n_points, int32
 int rmcv_batch_get_binary(rmcv_ctx* c, int frame, uint8_t* out)
 {
     if (!c || !out || frame < 0 || frame >= c->geom.n_frames) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
+    if (const int rc = ctx_ready(c)) return rc;
     const size_t sz = (size_t)c->geom.w * c->geom.h;
     HIPCHK(c, hipMemcpy(out, c->bufs.binary + (size_t)frame * sz, sz, hipMemcpyDeviceToHost), "D2H binary");
     return RMCV_OK;
@@ -872,9 +744,7 @@ int rmcv_batch_get_contours(rmcv_ctx* c, int frame, rmcv_point* pts_out, int pts
                             int32_t* n_contours, int32_t* n_points)
 {
     if (!c || frame < 0 || frame >= c->geom.n_frames) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
+    if (const int rc = ctx_ready(c)) return rc;
     hipStream_t s = c->stream;
     // pack this frame only: a one-frame view of the buffers
     Geom g1 = c->geom;
@@ -903,9 +773,7 @@ int rmcv_batch_get_contours(rmcv_ctx* c, int frame, rmcv_point* pts_out, int pts
 int rmcv_batch_get_blobs(rmcv_ctx* c, int frame, rmcv_lightblob* blobs_out, int cap, int32_t* n_blobs, int32_t* blob_src)
 {
     if (!c || frame < 0 || frame >= c->geom.n_frames) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
+    if (const int rc = ctx_ready(c)) return rc;
     int32_t nb = 0, st = 0;
     HIPCHK(c, hipMemcpy(&nb, c->bufs.n_blobs + frame, 4, hipMemcpyDeviceToHost), "D2H");
     HIPCHK(c, hipMemcpy(&st, c->bufs.status + frame, 4, hipMemcpyDeviceToHost), "D2H");
@@ -922,33 +790,24 @@ int rmcv_batch_get_blobs(rmcv_ctx* c, int frame, rmcv_lightblob* blobs_out, int 
 int rmcv_batch_get_armours(rmcv_ctx* c, rmcv_armour* armours_out, int cap, int32_t* frame_offs, int32_t* n_total)
 {
     if (!c) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
     const int nf = c->geom.n_frames;
-    std::vector<int32_t> cnt(nf), st(nf);
-    HIPCHK(c, hipMemcpy(cnt.data(), c->bufs.n_armours, (size_t)nf * 4, hipMemcpyDeviceToHost), "D2H");
-    HIPCHK(c, hipMemcpy(st.data(), c->bufs.status, (size_t)nf * 4, hipMemcpyDeviceToHost), "D2H");
+    std::vector<int32_t> cnt, st(nf);
     int64_t total = 0;
+    int rc = ctx_ready(c);
+    if (rc || (rc = armour_counts(c, cnt, &total))) return rc;
+    HIPCHK(c, hipMemcpy(st.data(), c->bufs.status, (size_t)nf * 4, hipMemcpyDeviceToHost), "D2H");
     int ovf = 0;
+    int64_t off = 0;
     for (int f = 0; f < nf; f++) {
-        if (frame_offs) frame_offs[f] = (int32_t)total;
-        total += cnt[f];
+        if (frame_offs) frame_offs[f] = (int32_t)off;
+        off += cnt[f];
         ovf |= st[f] & (RMCV_FRAME_OVF_CONTOURS | RMCV_FRAME_OVF_POINTS | RMCV_FRAME_OVF_BLOBS | RMCV_FRAME_OVF_ARMOURS);
     }
     if (frame_offs) frame_offs[nf] = (int32_t)total;
     if (n_total) *n_total = (int32_t)total;
     if (ovf) return fail(c, RMCV_ERR_CAPACITY, "context limits exceeded on at least one frame (see status)");
     if (total > cap) return fail(c, RMCV_ERR_CAPACITY, "output capacity exceeded");
-    if (armours_out && total) {
-        std::vector<rmcv_armour> all((size_t)nf * c->lim.max_armours);
-        HIPCHK(c, hipMemcpy(all.data(), c->bufs.armours, all.size() * sizeof(rmcv_armour), hipMemcpyDeviceToHost), "D2H armours");
-        int64_t o = 0;
-        for (int f = 0; f < nf; f++) {
-            memcpy(armours_out + o, all.data() + (size_t)f * c->lim.max_armours, (size_t)cnt[f] * sizeof(rmcv_armour));
-            o += cnt[f];
-        }
-    }
+    if (armours_out && total) return gather_rows(c, c->bufs.armours, cnt, armours_out, "D2H armours");
     return RMCV_OK;
 }
 
@@ -997,29 +856,19 @@ int rmcv_svm_load(rmcv_ctx* c, const float* weights, const double* rho, const in
 int rmcv_batch_get_identities(rmcv_ctx* c, int32_t* identity_out, int cap, int32_t* n_total)
 {
     if (!c || !c->bufs.identity) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
-    const int nf = c->geom.n_frames;
-    std::vector<int32_t> cnt(nf), all((size_t)nf * c->lim.max_armours);
-    HIPCHK(c, hipMemcpy(cnt.data(), c->bufs.n_armours, (size_t)nf * 4, hipMemcpyDeviceToHost), "D2H");
-    HIPCHK(c, hipMemcpy(all.data(), c->bufs.identity, all.size() * 4, hipMemcpyDeviceToHost), "D2H identity");
+    std::vector<int32_t> cnt;
     int64_t total = 0;
-    for (int f = 0; f < nf; f++) total += cnt[f];
+    int rc = ctx_ready(c);
+    if (rc || (rc = armour_counts(c, cnt, &total))) return rc;
     if (n_total) *n_total = (int32_t)total;
     if (total > cap) return fail(c, RMCV_ERR_CAPACITY, "output capacity exceeded");
-    int64_t o = 0;
-    for (int f = 0; f < nf; f++)
-        for (int a = 0; a < cnt[f]; a++) identity_out[o++] = all[(size_t)f * c->lim.max_armours + a];
-    return RMCV_OK;
+    return gather_rows(c, c->bufs.identity, cnt, identity_out, "D2H identity");
 }
 
 int rmcv_batch_get_icons(rmcv_ctx* c, int frame, uint8_t* icons_out, int cap_armours, int32_t* n_armours)
 {
     if (!c || !c->bufs.icons || !icons_out || frame < 0 || frame >= c->geom.n_frames) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
+    if (const int rc = ctx_ready(c)) return rc;
     int32_t na = 0;
     HIPCHK(c, hipMemcpy(&na, c->bufs.n_armours + frame, 4, hipMemcpyDeviceToHost), "D2H");
     if (n_armours) *n_armours = na;
@@ -1030,45 +879,7 @@ int rmcv_batch_get_icons(rmcv_ctx* c, int frame, uint8_t* icons_out, int cap_arm
     return RMCV_OK;
 }
 
-int rmcv_classify_armours(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, rmcv_armour* armours, int n,
-                          int32_t* identity_out, uint8_t* icons_out)
-{
-    if (!c || !bgr || (n > 0 && (!armours || !identity_out)) || n < 0) return RMCV_ERR_BAD_ARG;
-    if (!c->bufs.svm_w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_svm_load first");
-    if (n > c->lim.max_armours) return fail(c, RMCV_ERR_CAPACITY, "too many armours for this context");
-    int rc = rmcv_batch_upload(c, bgr, 1, w, h, stride, (int64_t)stride * h); // syncs the context first
-    if (rc) return rc;
-    if (n == 0) return RMCV_OK;
-    HIPCHK(c, hipMemcpy(c->bufs.armours, armours, (size_t)n * sizeof(rmcv_armour), hipMemcpyHostToDevice), "H2D armours");
-    HIPCHK(c, hipMemcpy(c->bufs.n_armours, &n, 4, hipMemcpyHostToDevice), "H2D");
-    if (c->geom.enhance) HIPCHK(c, launch_enhance_tables(c->geom, c->bufs, 1, c->stream), "k_frame_sums + k_enhance_table"); // the icon is cut from E(f)
-    HIPCHK(c, launch_classify(c->geom, c->bufs, c->lim, c->stream), "k_classify");
-    WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
-    HIPCHK(c, hipMemcpy(armours, c->bufs.armours, (size_t)n * sizeof(rmcv_armour), hipMemcpyDeviceToHost), "D2H armours");
-    HIPCHK(c, hipMemcpy(identity_out, c->bufs.identity, (size_t)n * 4, hipMemcpyDeviceToHost), "D2H identity");
-    if (icons_out) HIPCHK(c, hipMemcpy(icons_out, c->bufs.icons, (size_t)n * RMCV_SVM_FEATURES, hipMemcpyDeviceToHost), "D2H icons");
-    return RMCV_OK;
-}
-
 // ---- armour pose ------------------------------------------------------------------------------------------
-void rmcv_default_pnp_config(rmcv_pnp_config* c)
-{
-    if (!c) return;
-    // executable/main.cpp:7-19: every literal carries an `f` suffix, i.e. it is a float widened to double
-    const float K[9] = {1782.672144409928f, 0.0f, 598.8983414505224f, 0.0f, 1783.860175007369f, 523.4209809658056f, 0.0f, 0.0f, 1.0f};
-    const float D[5] = {-0.03436366268485048f, 0.1953669264956857f, 0.0001485060439399386f, -0.003814875777013483f,
-                        -0.3181808766352414f};
-    const float G[16] = {0.0007941130268316332f, 0.009683274185178004f, -0.9999528006788897f, -27.25811584661768f,
-                         0.9989588796104363f, 0.04560298009571095f, 0.001234930707386894f, -51.46996511920027f,
-                         0.04561278583864914f, -0.9989127101040636f, -0.009636978810429797f, 77.11760876626687f,
-                         0.0f, 0.0f, 0.0f, 1.0f};
-    for (int i = 0; i < 9; i++) c->camera_matrix[i] = K[i];
-    for (int i = 0; i < 5; i++) c->dist[i] = D[i];
-    for (int i = 0; i < 16; i++) c->gripper2camera[i] = G[i];
-    c->square_w = 27.0f; // executable/main.cpp:184
-    c->square_h = 27.0f;
-}
-
 int rmcv_pnp_load(rmcv_ctx* c, const rmcv_pnp_config* cfg)
 {
     if (!c || !cfg) return RMCV_ERR_BAD_ARG;
@@ -1101,10 +912,8 @@ int rmcv_pnp_load_cameras(rmcv_ctx* c, const rmcv_pnp_config* cams, int n_camera
 {
     if (!c || !cams) return RMCV_ERR_BAD_ARG;
     if (n_cameras < 1 || n_cameras > c->lim.max_frames) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_pnp_load_cameras: n_cameras out of range (1 .. limits.max_frames)");
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c); // the table about to be rewritten may still be read by a batch in flight
-    if (rc) return rc;
-    if ((rc = rmcv_pnp_load(c, &cams[0]))) return rc; // allocates what the pose stage needs on first use; selection off
+    int rc = ctx_ready(c); // the table about to be rewritten may still be read by a batch in flight
+    if (rc || (rc = rmcv_pnp_load(c, &cams[0]))) return rc; // allocates what the pose stage needs on first use; selection off
     Bufs& b = c->bufs;
     if (!b.cam_table) {
         const hipError_t e = dalloc(c, &b.cam_table, (size_t)c->lim.max_frames);
@@ -1125,27 +934,14 @@ static int set_frame_cameras(rmcv_ctx* c, const int32_t* h_idx, const void* d_id
     const Geom& g = c->geom;
     Bufs& b = c->bufs;
     if (g.n_frames <= 0 || !b.frames) return fail(c, RMCV_ERR_BAD_ARG, "no frames bound: per-frame cameras are set after the frames");
-    if (!h_idx && !d_idx) {
-        b.cam_req = nullptr;
-        return RMCV_OK;
-    }
-    if (!b.pnp_cams) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_pnp_load_cameras first");
-    if (h_idx) {
-        for (int f = 0; f < g.n_frames; f++)
-            if (frame_camera_eff(h_idx[f], b.n_cameras) != h_idx[f]) {
-                char msg[160];
-                snprintf(msg, sizeof(msg), "rmcv_batch_set_frame_cameras: frame %d: camera %d is outside the table (0 .. %d)", f, (int)h_idx[f], b.n_cameras - 1);
-                return fail(c, RMCV_ERR_BAD_ARG, msg);
-            }
-        hipSetDevice(c->device);
-        const int rc = rmcv_batch_sync(c); // the table about to be rewritten may still be read by a batch in flight
-        if (rc) return rc;
-        HIPCHK(c, hipMemcpy(c->cam_own, h_idx, (size_t)g.n_frames * 4, hipMemcpyHostToDevice), "H2D frame cameras");
-        b.cam_req = c->cam_own;
-    } else {
-        b.cam_req = (const int32_t*)d_idx;
-    }
-    return RMCV_OK;
+    if ((h_idx || d_idx) && !b.pnp_cams) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_pnp_load_cameras first");
+    for (int f = 0; h_idx && f < g.n_frames; f++)
+        if (frame_camera_eff(h_idx[f], b.n_cameras) != h_idx[f]) {
+            char msg[160];
+            snprintf(msg, sizeof(msg), "rmcv_batch_set_frame_cameras: frame %d: camera %d is outside the table (0 .. %d)", f, (int)h_idx[f], b.n_cameras - 1);
+            return fail(c, RMCV_ERR_BAD_ARG, msg);
+        }
+    return set_request_table(c, &b.cam_req, c->cam_own, h_idx, d_idx, true, "H2D frame cameras");
 }
 
 int rmcv_batch_set_frame_cameras(rmcv_ctx* c, const int32_t* idx) { return set_frame_cameras(c, idx, nullptr); }
@@ -1155,30 +951,17 @@ int rmcv_batch_set_device_frame_cameras(rmcv_ctx* c, const void* d_idx) { return
 int rmcv_batch_get_frame_cameras(rmcv_ctx* c, int32_t* out, int cap)
 {
     if (!c || cap < 0 || (cap > 0 && !out)) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    const int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
-    const int n = std::min(cap, c->geom.n_frames);
-    if (n <= 0) return RMCV_OK;
-    if (!c->bufs.cam_req) { // selection off: camera 0 for every frame
-        memset(out, 0, (size_t)n * 4);
-        return RMCV_OK;
-    }
-    HIPCHK(c, hipMemcpy(out, c->bufs.cam_eff, (size_t)n * 4, hipMemcpyDeviceToHost), "D2H frame cameras");
-    return RMCV_OK;
+    if (const int rc = ctx_ready(c)) return rc;
+    // selection off: camera 0 for every frame
+    return get_effective_table(c, out, cap, c->bufs.cam_req != nullptr, c->bufs.cam_eff, int32_t{0}, "D2H frame cameras");
 }
-
-/* the rule from a raw index to the table entry k_pnp uses (frame_camera_eff, the function it runs): host-side, no context, no device */
-int rmcv_frame_camera(int32_t idx, int32_t n_cameras) { return frame_camera_eff(idx, n_cameras); }
 
 int rmcv_batch_set_base2gripper(rmcv_ctx* c, const double* mats, int n_frames)
 {
     if (!c || !mats || n_frames < 1) return RMCV_ERR_BAD_ARG;
     if (!c->bufs.pnp_cfg) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_pnp_load first");
     if (n_frames > c->lim.max_frames) return fail(c, RMCV_ERR_CAPACITY, "more frames than the context holds");
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
+    if (const int rc = ctx_ready(c)) return rc;
     HIPCHK(c, hipMemcpy(c->bufs.base2gripper, mats, (size_t)n_frames * 16 * sizeof(double), hipMemcpyHostToDevice), "H2D base2gripper");
     c->bufs.pose_base2gripper = c->bufs.base2gripper;
     return RMCV_OK;
@@ -1189,285 +972,56 @@ int rmcv_batch_get_base2gripper(rmcv_ctx* c, double* mats, int n_frames)
     if (!c || !mats || n_frames < 1) return RMCV_ERR_BAD_ARG;
     if (!c->bufs.pnp_cfg) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_pnp_load first");
     if (n_frames > c->lim.max_frames) return fail(c, RMCV_ERR_CAPACITY, "more frames than the context holds");
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
+    if (const int rc = ctx_ready(c)) return rc;
     HIPCHK(c, hipMemcpy(mats, c->bufs.pose_base2gripper, (size_t)n_frames * 16 * sizeof(double), hipMemcpyDeviceToHost), "D2H base2gripper");
     return RMCV_OK;
-}
-
-static void scatter_poses(const std::vector<double>& all, size_t src, double* rvecs, double* tvecs, double* positions, size_t dst)
-{
-    for (int k = 0; k < 3; k++) {
-        if (rvecs) rvecs[3 * dst + k] = all[9 * src + k];
-        if (tvecs) tvecs[3 * dst + k] = all[9 * src + 3 + k];
-        if (positions) positions[3 * dst + k] = all[9 * src + 6 + k];
-    }
 }
 
 int rmcv_batch_get_poses(rmcv_ctx* c, double* rvecs, double* tvecs, double* positions, int cap, int32_t* n_total)
 {
     if (!c || !c->bufs.poses) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
-    const int nf = c->geom.n_frames;
-    std::vector<int32_t> cnt(nf);
-    std::vector<double> all((size_t)nf * c->lim.max_armours * 9);
-    HIPCHK(c, hipMemcpy(cnt.data(), c->bufs.n_armours, (size_t)nf * 4, hipMemcpyDeviceToHost), "D2H");
-    HIPCHK(c, hipMemcpy(all.data(), c->bufs.poses, all.size() * sizeof(double), hipMemcpyDeviceToHost), "D2H poses");
+    std::vector<int32_t> cnt;
     int64_t total = 0;
-    for (int f = 0; f < nf; f++) total += cnt[f];
+    int rc = ctx_ready(c);
+    if (rc || (rc = armour_counts(c, cnt, &total))) return rc;
     if (n_total) *n_total = (int32_t)total;
     if (total > cap) return fail(c, RMCV_ERR_CAPACITY, "output capacity exceeded");
-    size_t o = 0;
-    for (int f = 0; f < nf; f++)
-        for (int a = 0; a < cnt[f]; a++) scatter_poses(all, (size_t)f * c->lim.max_armours + a, rvecs, tvecs, positions, o++);
+    std::vector<PoseRow> rows((size_t)total);
+    if ((rc = gather_rows(c, reinterpret_cast<const PoseRow*>(c->bufs.poses), cnt, rows.data(), "D2H poses"))) return rc;
+    for (size_t i = 0; i < rows.size(); i++) scatter_pose(rows[i], rvecs, tvecs, positions, i);
     return RMCV_OK;
-}
-
-int rmcv_locate_armours(rmcv_ctx* c, const rmcv_armour* armours, int n, const double* base2gripper, double* rvecs, double* tvecs,
-                        double* positions)
-{
-    if (!c || n < 0 || (n > 0 && !armours)) return RMCV_ERR_BAD_ARG;
-    if (!c->bufs.pnp_cfg) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_pnp_load first");
-    if (n > c->lim.max_armours) return fail(c, RMCV_ERR_CAPACITY, "too many armours for this context");
-    if (n == 0) return RMCV_OK;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
-    resident_none(c);
-    static const double eye[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    HIPCHK(c, hipMemcpy(c->bufs.armours, armours, (size_t)n * sizeof(rmcv_armour), hipMemcpyHostToDevice), "H2D armours");
-    HIPCHK(c, hipMemcpy(c->bufs.n_armours, &n, 4, hipMemcpyHostToDevice), "H2D");
-    HIPCHK(c, hipMemcpy(c->bufs.base2gripper, base2gripper ? base2gripper : eye, sizeof(eye), hipMemcpyHostToDevice), "H2D base2gripper");
-    Geom g1 = c->geom;
-    g1.n_frames = 1;
-    g1.win = 0; // (the caller's armours, the default ROI: whatever windows the batch bound to the context has)
-    Bufs b1 = c->bufs;
-    b1.pose_base2gripper = b1.base2gripper; // (... and the caller's matrix, whatever attitude step ran in front of that batch)
-    b1.cam_req = nullptr;                   // (... and camera 0, whatever cameras its frames have)
-    HIPCHK(c, launch_pnp(g1, b1, c->lim, c->stream), "k_pnp");
-    WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
-    std::vector<double> all((size_t)n * 9);
-    HIPCHK(c, hipMemcpy(all.data(), c->bufs.poses, all.size() * sizeof(double), hipMemcpyDeviceToHost), "D2H poses");
-    for (int a = 0; a < n; a++) scatter_poses(all, (size_t)a, rvecs, tvecs, positions, (size_t)a);
-    return RMCV_OK;
-}
-
-// ---- tracker bookkeeping: host-side, see include/rmcv_abi.h --------------------------------------------------
-namespace {
-struct RectF { float x, y, w, h; };
-inline bool rect_empty(const RectF& r) { return r.w <= 0 || r.h <= 0; }
-// cv::Rect_<float>::operator& (the overflow-safe form of OpenCV >= 4.5)
-inline RectF rect_and(const RectF& a, const RectF& b)
-{
-    const RectF zero = {0, 0, 0, 0};
-    if (rect_empty(a) || rect_empty(b)) return zero;
-    const RectF& rx_min = (a.x < b.x) ? a : b;
-    const RectF& rx_max = (a.x < b.x) ? b : a;
-    const RectF& ry_min = (a.y < b.y) ? a : b;
-    const RectF& ry_max = (a.y < b.y) ? b : a;
-    if ((rx_min.x < 0 && rx_min.x + rx_min.w < rx_max.x) || (ry_min.y < 0 && ry_min.y + ry_min.h < ry_max.y)) return zero;
-    RectF o;
-    o.w = std::min(rx_min.w - (rx_max.x - rx_min.x), rx_max.w);
-    o.h = std::min(ry_min.h - (ry_max.y - ry_min.y), ry_max.h);
-    o.x = rx_max.x;
-    o.y = ry_max.y;
-    return rect_empty(o) ? zero : o;
-}
-} // namespace
-
-int rmcv_max_iou(const rmcv_armour* self, const rmcv_armour* list, int n, int32_t* index, float* iou_out)
-{
-    if (!self || !index || !iou_out || n < 0 || (n > 0 && !list)) return RMCV_ERR_BAD_ARG;
-    int idx = -1;
-    float max = 0;
-    const RectF me = {self->bbox[0], self->bbox[1], self->bbox[2], self->bbox[3]};
-    for (int i = 0; i < n; i++) { // src/core.cpp:148-160
-        const RectF other = {list[i].bbox[0], list[i].bbox[1], list[i].bbox[2], list[i].bbox[3]};
-        const RectF in = rect_and(me, other);
-        const float union_area = me.w * me.h + other.w * other.h - in.w * in.h;
-        const float iou = in.w * in.h / union_area;
-        if (iou > max) {
-            max = iou;
-            idx = i;
-        }
-    }
-    *index = idx;
-    *iou_out = max;
-    return RMCV_OK;
-}
-
-int rmcv_identity_max(const int32_t* ids, const int32_t* counts, int n, int32_t* max_id, double* prob_out)
-{
-    if (!max_id || !prob_out || n < 0 || (n > 0 && (!ids || !counts))) return RMCV_ERR_BAD_ARG;
-    for (int i = 1; i < n; i++)
-        if (ids[i] <= ids[i - 1]) return RMCV_ERR_BAD_ARG; // std::map order
-    double sum = 0;
-    for (int i = 0; i < n; i++) sum += exp((double)counts[i]); // src/core.cpp:127
-    double max = 0;
-    int id = -1;
-    for (int i = 0; i < n; i++) {
-        const double prob = exp((double)counts[i]) / sum; // :133
-        if (prob > max) {
-            max = prob;
-            id = ids[i];
-        }
-    }
-    *max_id = id;
-    *prob_out = max;
-    return RMCV_OK;
-}
-
-// ---- legacy per-contour matcher --------------------------------------------------------------------------
-static int match_one(rmcv_ctx* c, const rmcv_point* pts, int n, const rmcv_legacy_params& lp, int mode, rmcv_rrect* box, int32_t* matched)
-{
-    int32_t offs[2] = {0, n};
-    hipSetDevice(c->device);
-    int rc = load_contours(c, pts, offs, 1);
-    if (rc) return rc;
-    rmcv_params p;
-    rmcv_default_params(&p);
-    const Geom g1 = one_frame_geom(c);
-    HIPCHK(c, launch_match(g1, c->bufs, c->lim, p, lp, mode, false, false, c->stream), "k_match");
-    WAITCHK(c, wait_stream(c, c->stream, "waiting for the context's stream"));
-    int32_t nb = 0, st = 0;
-    HIPCHK(c, hipMemcpy(&nb, c->bufs.n_blobs, 4, hipMemcpyDeviceToHost), "D2H");
-    HIPCHK(c, hipMemcpy(&st, c->bufs.status, 4, hipMemcpyDeviceToHost), "D2H");
-    if (st & RMCV_FRAME_HULL)
-        return fail(c, RMCV_ERR_BAD_ARG, "minAreaRect: not a closed border (a column of the bounding box is empty) or wider than the context's max_width");
-    *matched = nb == 1;
-    if (nb == 1) HIPCHK(c, hipMemcpy(box, c->bufs.ellipses, sizeof(rmcv_rrect), hipMemcpyDeviceToHost), "D2H box");
-    return RMCV_OK;
-}
-
-int rmcv_min_area_rect(rmcv_ctx* c, const rmcv_point* pts, int n, rmcv_rrect* out)
-{
-    if (!c || !pts || !out || n < 1) return RMCV_ERR_BAD_ARG;
-    rmcv_legacy_params lp = {0, 0, 0, 0, 0, 0};
-    int32_t m = 0;
-    int rc = match_one(c, pts, n, lp, 1, out, &m);
-    if (rc) return rc;
-    return m ? RMCV_OK : fail(c, RMCV_ERR_HIP, "minAreaRect produced no result");
-}
-
-int rmcv_match_lightblob(rmcv_ctx* c, const rmcv_point* pts, int n, const rmcv_legacy_params* lp, rmcv_rrect* box_out, int32_t* matched)
-{
-    if (!c || !lp || !box_out || !matched || n < 0 || (n > 0 && !pts)) return RMCV_ERR_BAD_ARG;
-    *matched = 0;
-    if (n < 6) return RMCV_OK; // src/objdetect.cpp:12
-    return match_one(c, pts, n, *lp, 0, box_out, matched);
 }
 
 } // extern "C"
 
-// rmcv_demosaic / rmcv_demosaic_raw: the arguments are checked, then D(T(r)) of the buffer in layout `lay` (0: a plain 8-bit mosaic)
-static int demosaic_body(rmcv_ctx* c, const uint8_t* raw, int w, int h, int stride, int pattern, int lay, uint8_t* bgr_out, int out_stride)
-{
-    const int sb = rmcv::lay_bytes(lay);
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
-    // (a stage-wise helper: buffers of its own, so that nothing bound to the context moves)
-    uint8_t *d_raw = nullptr, *d_out = nullptr;
-    const size_t in_bytes = (size_t)sb * w * h, out_bytes = (size_t)3 * w * h;
-    hipError_t e = hipMalloc((void**)&d_raw, in_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, out_bytes);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(d_raw, (size_t)sb * w, raw, stride, (size_t)sb * w, h, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_demosaic(d_raw, sb * w, w, h, pattern, lay, d_out, 3 * w, c->stream);
-    c->last_what = "k_demosaic";
-    int rcw = 0;
-    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_demosaic");
-    if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(bgr_out, out_stride, d_out, 3 * w, 3 * w, h, hipMemcpyDeviceToHost);
-    if (rcw == 0 || e != hipSuccess) { // (after a wait that ran out the kernel may still be using them)
-        if (d_raw) hipFree(d_raw);
-        if (d_out) hipFree(d_out);
-    }
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_demosaic", e);
-    return rcw;
-}
-
 extern "C" {
 
-int rmcv_demosaic(rmcv_ctx* c, const uint8_t* raw, int w, int h, int stride, int pattern, uint8_t* bgr_out, int out_stride)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!raw || !bgr_out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: null buffer");
-    if (w < 3 || h < 3) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: a mosaic needs w >= 3 and h >= 3");
-    if (stride < w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: stride < w");
-    if (out_stride < 3 * w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: out_stride < 3 w");
-    if (pattern < RMCV_BAYER_RG || pattern > RMCV_BAYER_BG) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic: unknown Bayer pattern");
-    return demosaic_body(c, raw, w, h, stride, pattern, 0, bgr_out, out_stride);
-}
-
-int rmcv_demosaic_raw(rmcv_ctx* c, const void* raw, int w, int h, int stride, int pattern, int sample_bits, int valid_bit, int orient,
-                      uint8_t* bgr_out, int out_stride)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!raw || !bgr_out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: null buffer");
-    if (w < 3 || h < 3) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: a mosaic needs w >= 3 and h >= 3");
-    if (sample_bits != 8 && sample_bits != 16) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: sample_bits is 8 or 16");
-    if (valid_bit < 0 || valid_bit > 4) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: valid_bit is 0 .. 4");
-    if (orient < 0 || orient > (RMCV_ORIENT_MIRROR | RMCV_ORIENT_FLIP)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: unknown orientation bits");
-    if (stride < sample_bits / 8 * w) return fail(c, RMCV_ERR_BAD_ARG, sample_bits == 16 ? "rmcv_demosaic_raw: stride < 2 w" : "rmcv_demosaic_raw: stride < w");
-    if (sample_bits == 16 && (stride & 1)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: odd stride with 16-bit samples");
-    if (sample_bits == 16 && ((uintptr_t)raw & 1)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: 16-bit samples need a 2-byte aligned buffer");
-    if (out_stride < 3 * w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: out_stride < 3 w");
-    if (pattern < RMCV_BAYER_RG || pattern > RMCV_BAYER_BG) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_demosaic_raw: unknown Bayer pattern");
-    return demosaic_body(c, (const uint8_t*)raw, w, h, stride, pattern, rmcv::raw_layout(sample_bits, valid_bit, orient), bgr_out, out_stride);
-}
-
 /* ---- exposure-adaptive detection: rm::CalcGamma / rm::AutoEnhance (src/imgproc.cpp:37-48, 77-98) ---- */
-
-int rmcv_gamma_lut(float gamma, uint8_t lut[256])
-{
-    if (!lut || !(gamma >= 0.0f) || !std::isfinite(gamma)) return RMCV_ERR_BAD_ARG;
-    for (int i = 0; i < 256; i++) lut[i] = enh_lut_entry(i, gamma);
-    return RMCV_OK;
-}
-
-static bool gains_ok(float max_gain, float min_gain) { return std::isfinite(max_gain) && std::isfinite(min_gain) && max_gain != min_gain; }
-
-int rmcv_enhance_gamma(const uint64_t sums_bgr[3], int64_t n_pixels, float max_gain, float min_gain, float* gamma)
-{
-    if (!sums_bgr || !gamma || n_pixels <= 0 || !gains_ok(max_gain, min_gain)) return RMCV_ERR_BAD_ARG;
-    *gamma = enh_gamma(sums_bgr, n_pixels, max_gain, min_gain);
-    return RMCV_OK;
-}
 
 int rmcv_ctx_set_enhance_gains(rmcv_ctx* c, float max_gain, float min_gain)
 {
     if (!c) return RMCV_ERR_BAD_ARG;
     if (!gains_ok(max_gain, min_gain)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_ctx_set_enhance_gains: the gains must be finite and differ");
-    c->enh_max_gain = max_gain; // (like the option: frames bound before keep what they were bound with)
-    c->enh_min_gain = min_gain;
+    c->input.max_gain = max_gain; // (like the option: frames bound before keep what they were bound with)
+    c->input.min_gain = min_gain;
     return RMCV_OK;
 }
 
 int rmcv_ctx_get_enhance(const rmcv_ctx* c, int32_t* on, float* max_gain, float* min_gain)
 {
     if (!c) return RMCV_ERR_BAD_ARG;
-    if (on) *on = c->enhance;
-    if (max_gain) *max_gain = c->enh_max_gain;
-    if (min_gain) *min_gain = c->enh_min_gain;
+    if (on) *on = c->input.enhance;
+    if (max_gain) *max_gain = c->input.max_gain;
+    if (min_gain) *min_gain = c->input.min_gain;
     return RMCV_OK;
 }
 
 int rmcv_batch_get_gammas(rmcv_ctx* c, float* gamma_out, int cap)
 {
     if (!c || !gamma_out || cap < 0) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
-    const int n = std::min(cap, c->geom.n_frames);
-    if (n <= 0) return RMCV_OK;
-    if (!c->geom.enhance) { // read as they are: gamma 1 is the identity table
-        for (int i = 0; i < n; i++) gamma_out[i] = 1.0f;
-        return RMCV_OK;
-    }
-    HIPCHK(c, hipMemcpy(gamma_out, c->bufs.enh_gamma, (size_t)n * sizeof(float), hipMemcpyDeviceToHost), "D2H gammas");
-    return RMCV_OK;
+    if (const int rc = ctx_ready(c)) return rc;
+    // without the option the frames are read as they are: gamma 1 is the identity table
+    return get_effective_table(c, gamma_out, cap, c->geom.enhance != 0, c->bufs.enh_gamma, 1.0f, "D2H gammas");
 }
 
 /* ---- windowed detection: the frames bound are read through one window each (rm::utils::GetROI -> extract_color(image(roi))) ---- */
@@ -1484,16 +1038,17 @@ static int set_windows(rmcv_ctx* c, const rmcv_point* h_origins, const void* d_o
         if (!g.win) return RMCV_OK;
         g.win = 0;
         c->bufs.win_req = nullptr;
-        return set_extent(c, g.frame_w, g.frame_h, nullptr);
+        extent_fields(g, g.frame_w, g.frame_h);
+        return extent_apply(c, nullptr);
     }
     if (!h_origins && !d_origins) return fail(c, RMCV_ERR_BAD_ARG, "null origins");
-    int rc = check_windows(c, g.frame_w, g.frame_h, g.input_format, g.enhance, win_w, win_h);
+    int rc = refuse(c, windows_refusal(c->lim, g.frame_w, g.frame_h, g.input_format, g.enhance, win_w, win_h));
     if (rc) return rc;
-    if ((rc = rmcv_batch_sync(c))) return rc; // the tables about to be rewritten may still be read by a batch in flight
-    if (h_origins) HIPCHK(c, hipMemcpy(c->win_own, h_origins, (size_t)g.n_frames * sizeof(rmcv_point), hipMemcpyHostToDevice), "H2D window origins");
-    c->bufs.win_req = h_origins ? c->win_own : (const rmcv_point*)d_origins;
+    // the tables about to be rewritten may still be read by a batch in flight: whichever origins they are, wait here
+    if ((rc = rmcv_batch_sync(c)) || (rc = set_request_table(c, &c->bufs.win_req, c->win_own, h_origins, d_origins, false, "H2D window origins"))) return rc;
     g.win = 1;
-    if ((rc = set_extent(c, win_w, win_h, nullptr))) return rc;
+    extent_fields(g, win_w, win_h);
+    if ((rc = extent_apply(c, nullptr))) return rc;
     // the effective origins now (rmcv_batch_get_windows before the first run reads them); every run with the pixel pass computes them again
     if ((rc = order_begin(c, c->stream))) return rc;
     HIPCHK(c, launch_window_origins(g, c->bufs, c->stream), "k_window_origins");
@@ -1515,20 +1070,12 @@ int rmcv_batch_set_device_windows(rmcv_ctx* c, const void* d_origins, int win_w,
 int rmcv_batch_get_windows(rmcv_ctx* c, rmcv_point* eff_out, int cap, int32_t* win_w, int32_t* win_h)
 {
     if (!c || cap < 0 || (cap > 0 && !eff_out)) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
+    if (const int rc = ctx_ready(c)) return rc;
     const Geom& g = c->geom;
     if (win_w) *win_w = g.win ? g.w : 0;
     if (win_h) *win_h = g.win ? g.h : 0;
-    const int n = std::min(cap, g.n_frames);
-    if (n <= 0) return RMCV_OK;
-    if (!g.win) { // whole frames: every origin is (0, 0)
-        memset(eff_out, 0, (size_t)n * sizeof(rmcv_point));
-        return RMCV_OK;
-    }
-    HIPCHK(c, hipMemcpy(eff_out, c->bufs.win_eff, (size_t)n * sizeof(rmcv_point), hipMemcpyDeviceToHost), "D2H window origins");
-    return RMCV_OK;
+    // whole frames: every origin is (0, 0)
+    return get_effective_table(c, eff_out, cap, g.win != 0, c->bufs.win_eff, rmcv_point{0, 0}, "D2H window origins");
 }
 
 int rmcv_batch_device_windows(rmcv_ctx* c, void** d_eff, int32_t* win_w, int32_t* win_h)
@@ -1547,28 +1094,18 @@ static int set_frame_camps(rmcv_ctx* c, const int32_t* h_camps, const int32_t* h
 {
     if (!c) return RMCV_ERR_BAD_ARG;
     Geom& g = c->geom;
-    if (g.n_frames <= 0 || !c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, "no frames bound: per-frame camps are set after the frames");
+    Bufs& b = c->bufs;
+    if (g.n_frames <= 0 || !b.frames) return fail(c, RMCV_ERR_BAD_ARG, "no frames bound: per-frame camps are set after the frames");
     hipSetDevice(c->device);
     resident_none(c);
-    if (!h_camps && !d_camps) { // per-run keys again
-        g.keys = 0;
-        c->bufs.key_camps = c->bufs.key_lbs = nullptr;
-        return RMCV_OK;
-    }
-    int rc = check_frame_camps(c, g.input_format, g.enhance);
+    const bool on = h_camps || d_camps;
+    int rc = on ? check_frame_camps(c, g.input_format, g.enhance) : RMCV_OK;
     if (rc) return rc;
-    if (h_camps) {
-        if ((rc = rmcv_batch_sync(c))) return rc; // the tables about to be rewritten may still be read by a batch in flight
-        int32_t* own_lbs = c->key_own + c->lim.max_frames;
-        HIPCHK(c, hipMemcpy(c->key_own, h_camps, (size_t)g.n_frames * 4, hipMemcpyHostToDevice), "H2D frame camps");
-        if (h_lbs) HIPCHK(c, hipMemcpy(own_lbs, h_lbs, (size_t)g.n_frames * 4, hipMemcpyHostToDevice), "H2D frame lower bounds");
-        c->bufs.key_camps = c->key_own;
-        c->bufs.key_lbs = h_lbs ? own_lbs : nullptr;
-    } else {
-        c->bufs.key_camps = (const int32_t*)d_camps;
-        c->bufs.key_lbs = (const int32_t*)d_lbs;
-    }
-    g.keys = 1;
+    // (the lower bounds go with the camps: behind the camps' wait, and null with null camps)
+    if ((rc = set_request_table(c, &b.key_camps, c->key_own, h_camps, d_camps, true, "H2D frame camps")) ||
+        (rc = set_request_table(c, &b.key_lbs, c->key_own + c->lim.max_frames, h_lbs, d_lbs, false, "H2D frame lower bounds")))
+        return rc;
+    g.keys = on;
     return RMCV_OK;
 }
 
@@ -1585,64 +1122,11 @@ int rmcv_batch_set_device_frame_camps(rmcv_ctx* c, const void* d_camps, const vo
 int rmcv_batch_get_frame_keys(rmcv_ctx* c, int32_t* keys_out, int cap)
 {
     if (!c || cap < 0 || (cap > 0 && !keys_out)) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
-    const Geom& g = c->geom;
-    const int n = std::min(cap, g.n_frames);
-    if (n <= 0) return RMCV_OK;
+    if (const int rc = ctx_ready(c)) return rc;
     static_assert(sizeof(FrameKey) == 4 * sizeof(int32_t), "rmcv_batch_get_frame_keys hands the table out as [frame][4] int32");
-    if (!g.keys) { // per-run keys: the last run's, for every frame
-        const FrameKey k = frame_key_eff(c->last_camp, c->last_lower_bound);
-        for (int f = 0; f < n; f++) memcpy(keys_out + 4 * f, &k, sizeof(k));
-        return RMCV_OK;
-    }
-    HIPCHK(c, hipMemcpy(keys_out, c->bufs.key_eff, (size_t)n * sizeof(FrameKey), hipMemcpyDeviceToHost), "D2H frame keys");
-    return RMCV_OK;
-}
-
-/* the rule from raw camp and lower bound to what the kernels use (frame_key_eff, the function k_frame_keys runs): host-side, no context, no device */
-int rmcv_frame_key(int32_t camp, int32_t lower_bound, int32_t out[4])
-{
-    if (!out) return RMCV_ERR_BAD_ARG;
-    const FrameKey k = frame_key_eff(camp, lower_bound);
-    out[0] = k.ca;
-    out[1] = k.cb;
-    out[2] = k.lb;
-    out[3] = k.all_pass;
-    return RMCV_OK;
-}
-
-/* rm::utils::GetROI (src/core.cpp:224-263), verbatim: host-side, no context, no device */
-int rmcv_get_roi(const float* points, int n, float scale_w, float scale_h, int frame_w, int frame_h, const int32_t previous[4], int32_t out[4])
-{
-    if (!out || n < 0 || (n > 0 && !points)) return RMCV_ERR_BAD_ARG;
-    trk_get_roi(points, n, scale_w, scale_h, frame_w, frame_h, previous, out); // (device_track.h: the device tracker compiles the same body)
-    return RMCV_OK;
-}
-
-int rmcv_window_origin(const int32_t rect[4], int win_w, int win_h, int32_t out_xy[2])
-{
-    if (!rect || !out_xy || win_w < 1 || win_h < 1) return RMCV_ERR_BAD_ARG;
-    trk_window_origin(rect, win_w, win_h, out_xy); // (device_track.h)
-    return RMCV_OK;
-}
-
-int rmcv_armours_to_frame(rmcv_armour* armours, int n, int x, int y)
-{
-    if (n < 0 || (n > 0 && !armours)) return RMCV_ERR_BAD_ARG;
-    const float fx = (float)x, fy = (float)y;
-    for (int i = 0; i < n; i++) {
-        for (int k = 0; k < 4; k++) {
-            armours[i].icon[k][0] += fx;
-            armours[i].icon[k][1] += fy;
-            armours[i].vertices[k][0] += fx;
-            armours[i].vertices[k][1] += fy;
-        }
-        armours[i].bbox[0] += fx;
-        armours[i].bbox[1] += fy;
-    }
-    return RMCV_OK;
+    // per-run keys: the last run's, for every frame
+    return get_effective_table(c, reinterpret_cast<FrameKey*>(keys_out), cap, c->geom.keys != 0, c->bufs.key_eff,
+                               frame_key_eff(c->last_camp, c->last_lower_bound), "D2H frame keys");
 }
 
 int rmcv_batch_attitude(rmcv_ctx* c, rmcv_tracker* trk, const void* d_packets, void* hip_stream)
@@ -1721,122 +1205,6 @@ int ctx_attitude(rmcv_ctx* c, rmcv_tracker* trk, const void* d_packets, hipStrea
     return order_end(c, s);
 }
 } // namespace rmcv
-
-// rmcv_calc_gamma / rmcv_auto_enhance: a host image of `rows` rows of `row_bytes` bytes through a table, on the device.  A stage-wise
-// helper like rmcv_demosaic: buffers of its own, so that nothing bound to the context moves.  auto_w > 0: the image is a BGR frame of
-// auto_w pixels per row and the table is that of ITS gamma (sums and table on the device); otherwise the table of `gamma`.
-static int bytemap_body(rmcv_ctx* c, const uint8_t* src, int row_bytes, int rows, int src_stride, float gamma, int auto_w, float max_gain, float min_gain,
-                        uint8_t* dst, int dst_stride, float* gamma_out, const char* who)
-{
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
-    const int dstride = (row_bytes + 15) & ~15;
-    const size_t img = (size_t)dstride * rows;
-    // [image | sums 3 x 8 | gamma 4 + pad 4 | table 256 | threshold table 512]
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, img + 32 + 256 + 512);
-    hipStream_t s = c->stream;
-    if (e == hipSuccess && dstride != row_bytes) e = hipMemsetAsync(d, 0, img, s); // (the pad bytes go through the table too: keep them defined)
-    if (e == hipSuccess) e = hipMemcpy2DAsync(d, dstride, src, src_stride, (size_t)row_bytes, rows, hipMemcpyHostToDevice, s);
-    uint8_t* d_lut = d + img + 32;
-    if (e == hipSuccess) {
-        if (auto_w > 0) {
-            Geom g1 = c->geom;
-            g1.n_frames = 1; g1.w = auto_w; g1.h = rows; g1.stride = dstride; g1.frame_pitch = (int64_t)img;
-            g1.enh_max_gain = max_gain; g1.enh_min_gain = min_gain;
-            Bufs b1{};
-            b1.frames = d;
-            b1.enh_sums = reinterpret_cast<uint64_t*>(d + img);
-            b1.enh_gamma = reinterpret_cast<float*>(d + img + 24);
-            b1.enh_lut = d_lut;
-            b1.enh_m = reinterpret_cast<uint16_t*>(d + img + 32 + 256);
-            e = launch_enhance_tables(g1, b1, 1, s);
-        } else e = launch_gamma_lut(gamma, d_lut, s);
-    }
-    if (e == hipSuccess) e = launch_bytemap(d, d, (int64_t)(img / 16), d_lut, c->geom.n_cu, s);
-    c->last_what = auto_w > 0 ? "k_frame_sums, k_enhance_table, k_bytemap" : "k_gamma_lut, k_bytemap";
-    int rcw = 0;
-    if (e == hipSuccess) rcw = wait_stream(c, s, who);
-    if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(dst, dst_stride, d, dstride, (size_t)row_bytes, rows, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rcw == 0 && gamma_out && auto_w > 0) e = hipMemcpy(gamma_out, d + img + 24, sizeof(float), hipMemcpyDeviceToHost);
-    if (d && (rcw == 0 || e != hipSuccess)) hipFree(d); // (after a wait that ran out the kernels may still be using it)
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, who, e);
-    return rcw;
-}
-
-extern "C" {
-
-int rmcv_calc_gamma(rmcv_ctx* c, const uint8_t* src, int row_bytes, int rows, int src_stride, float gamma, uint8_t* dst, int dst_stride)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!src || !dst) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_calc_gamma: null buffer");
-    if (row_bytes < 1 || rows < 1 || src_stride < row_bytes || dst_stride < row_bytes) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_calc_gamma: bad size or stride");
-    if (!(gamma >= 0.0f) || !std::isfinite(gamma)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_calc_gamma: gamma must be finite and not negative");
-    return bytemap_body(c, src, row_bytes, rows, src_stride, gamma, 0, 0.0f, 0.0f, dst, dst_stride, nullptr, "rmcv_calc_gamma");
-}
-
-int rmcv_auto_enhance(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, float max_gain, float min_gain, uint8_t* out, int out_stride,
-                      float* gamma_out)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!bgr || !out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_auto_enhance: null buffer");
-    if (w < 1 || h < 1 || w > 65536 || h > 65536 || stride < 3 * w || out_stride < 3 * w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_auto_enhance: bad size or stride");
-    if (!gains_ok(max_gain, min_gain)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_auto_enhance: the gains must be finite and differ");
-    return bytemap_body(c, bgr, 3 * w, h, stride, 0.0f, w, max_gain, min_gain, out, out_stride, gamma_out, "rmcv_auto_enhance");
-}
-
-int rmcv_find_lightblobs(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, const rmcv_point* pts, const int32_t* offs,
-                         int n_contours, const rmcv_legacy_params* lp, rmcv_lightblob* blobs_out, int blobs_cap, int32_t* n_blobs,
-                         int32_t* blob_src, rmcv_rrect* boxes_out)
-{
-    if (!c || !bgr || !lp || (n_contours > 0 && (!pts || !offs))) return RMCV_ERR_BAD_ARG;
-    int rc = refuse(c, pixel_refusal(c->input_format, c->enhance, false, false, true));
-    if (rc) return rc;
-    hipSetDevice(c->device);
-    rc = rmcv_batch_upload(c, bgr, 1, w, h, stride, (int64_t)stride * h); // source.channels() == 3 is the ABI's only format
-    if (rc) return rc;
-    rc = load_contours(c, pts, offs, n_contours);
-    if (rc) return rc;
-    for (int i = 0; i < (n_contours ? offs[n_contours] : 0); i++)
-        if (pts[i].x < 0 || pts[i].x >= w || pts[i].y < 0 || pts[i].y >= h) return fail(c, RMCV_ERR_BAD_ARG, "contour point outside the frame");
-    rmcv_params p;
-    rmcv_default_params(&p);
-    HIPCHK(c, launch_match(c->geom, c->bufs, c->lim, p, *lp, 0, true, false, c->stream), "k_match");
-    int32_t nb = 0;
-    rc = rmcv_batch_get_blobs(c, 0, blobs_out, blobs_cap, &nb, blob_src);
-    if (rc) return rc;
-    if (n_blobs) *n_blobs = nb;
-    int32_t st = 0;
-    HIPCHK(c, hipMemcpy(&st, c->bufs.status, 4, hipMemcpyDeviceToHost), "D2H");
-    if (st & RMCV_FRAME_HULL) return fail(c, RMCV_ERR_BAD_ARG, "minAreaRect: a contour is not a closed border or exceeds the hull tables");
-    if (boxes_out && nb) HIPCHK(c, hipMemcpy(boxes_out, c->bufs.ellipses, (size_t)nb * sizeof(rmcv_rrect), hipMemcpyDeviceToHost), "D2H boxes");
-    return RMCV_OK;
-}
-
-int rmcv_lightblob_overlap(const rmcv_lightblob* lb, int n, int left, int right, int32_t* overlap)
-{
-    if (!overlap || (n > 0 && !lb)) return RMCV_ERR_BAD_ARG;
-    *overlap = 0;
-    if (left < 0 || right > n || right - left < 2) return RMCV_OK; // src/objdetect.cpp:91
-    if (right == n) return RMCV_ERR_BAD_ARG;                       // the reference reads lightBlobs[size()] here
-    if (lb[left].target != lb[right].target) return RMCV_OK;       // :92
-    const float lower_y = std::min(std::min(lb[left].vertices[1][1], lb[left].vertices[2][1]),
-                                   std::min(lb[right].vertices[1][1], lb[right].vertices[2][1])); // :94-96
-    const float upper_y = std::max(std::max(lb[left].vertices[0][1], lb[left].vertices[3][1]),
-                                   std::max(lb[right].vertices[0][1], lb[right].vertices[3][1])); // :97-99
-    for (int i = left; i < right; i++) {
-        if (lb[i].target != lb[left].target) continue;
-        if (lb[i].center[0] > lb[left].center[0] && lb[i].center[0] < lb[right].center[0] && lb[i].center[1] > lower_y &&
-            lb[i].center[1] < upper_y) {
-            *overlap = 1;
-            return RMCV_OK;
-        }
-    }
-    return RMCV_OK;
-}
-
-} // extern "C"
 
 /* ---- the operator's debug view (k_view.hip) ---- */
 
@@ -1927,8 +1295,7 @@ int rmcv_batch_get_debug_view(rmcv_ctx* c, int frame, int vw, int vh, int flags,
     const int32_t one = frame;
     int rc = ctx_view_check(c, &one, 1, c->geom.n_frames, c->last_stages, vw, vh, flags, out_stride, 0);
     if (rc) return rc;
-    hipSetDevice(c->device);
-    if ((rc = rmcv_batch_sync(c))) return rc;
+    if ((rc = ctx_ready(c))) return rc;
     int32_t st = 0;
     HIPCHK(c, hipMemcpy(&st, c->bufs.status + frame, 4, hipMemcpyDeviceToHost), "D2H");
     if (st & (RMCV_FRAME_OVF_CONTOURS | RMCV_FRAME_OVF_POINTS | RMCV_FRAME_OVF_BLOBS | RMCV_FRAME_OVF_ARMOURS))
@@ -1941,66 +1308,6 @@ int rmcv_batch_get_debug_view(rmcv_ctx* c, int frame, int vw, int vh, int flags,
     WAITCHK(c, wait_stream(c, c->stream, "k_view_resize"));
     HIPCHK(c, hipMemcpy2D(out, out_stride, c->view_out, (size_t)3 * vw, (size_t)3 * vw, vh, hipMemcpyDeviceToHost), "D2H view");
     return RMCV_OK;
-}
-
-int rmcv_debug_view(rmcv_ctx* c, const uint8_t* binary, int w, int h, int stride, const rmcv_lightblob* blobs, int n_blobs, const rmcv_point* neg_pts,
-                    const int32_t* neg_offs, int n_neg, const rmcv_armour* armours, int n_armours, int flags, int vw, int vh, uint8_t* out,
-                    int out_stride)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!binary || !out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_debug_view: null buffer");
-    const char* bad = view_check_lists(w, h, stride, blobs, n_blobs, neg_pts, neg_offs, n_neg, armours, n_armours, flags, vw, vh, out_stride);
-    if (bad) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "rmcv_debug_view: %s", bad);
-        return fail(c, RMCV_ERR_BAD_ARG, msg);
-    }
-    if (w > c->lim.max_width || h > c->lim.max_height || vw > c->lim.max_width || vh > c->lim.max_height)
-        return fail(c, RMCV_ERR_BAD_ARG, "rmcv_debug_view: image or view beyond the context's max_width / max_height");
-    hipSetDevice(c->device);
-    int rc = rmcv_batch_sync(c);
-    if (rc) return rc;
-    // (a stage-wise helper: buffers of its own, so that nothing bound to the context moves) -- one host block, one upload
-    const int prow = (w + 63) / 64 + 2, n_pts = n_neg ? neg_offs[n_neg] : 0;
-    const size_t plane = (size_t)(h + 2) * prow;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_blobs = up16(plane * 8), o_arm = o_blobs + up16((size_t)n_blobs * sizeof(rmcv_lightblob));
-    const size_t o_pts = o_arm + up16((size_t)n_armours * sizeof(rmcv_armour)), o_offs = o_pts + up16((size_t)n_pts * sizeof(rmcv_point));
-    const size_t o_cnt = o_offs + up16((size_t)(n_neg + 1) * 4), in_bytes = o_cnt + 16;
-    const size_t o_ov = in_bytes, o_out = o_ov + up16(2 * plane * 8), total = o_out + (size_t)3 * vw * vh;
-    std::vector<uint8_t> host(in_bytes, 0);
-    uint64_t* hp = reinterpret_cast<uint64_t*>(host.data());
-    for (int y = 0; y < h; y++)
-        for (int x = 0; x < w; x++)
-            if (binary[(size_t)y * stride + x]) hp[(size_t)(y + 1) * prow + (x >> 6) + 1] |= 1ull << (x & 63);
-    if (n_blobs) memcpy(&host[o_blobs], blobs, (size_t)n_blobs * sizeof(rmcv_lightblob));
-    if (n_armours) memcpy(&host[o_arm], armours, (size_t)n_armours * sizeof(rmcv_armour));
-    if (n_pts) memcpy(&host[o_pts], neg_pts, (size_t)n_pts * sizeof(rmcv_point));
-    if (n_neg) memcpy(&host[o_offs], neg_offs, (size_t)(n_neg + 1) * 4);
-    const int32_t counts[4] = {n_blobs, n_armours, n_neg, 0};
-    memcpy(&host[o_cnt], counts, sizeof(counts));
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, total);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        const int32_t* cnt = reinterpret_cast<const int32_t*>(d + o_cnt);
-        ViewJob j{};
-        j.w = w; j.h = h; j.prow = prow; j.plane_pitch = (int64_t)plane;
-        j.bits = reinterpret_cast<const uint64_t*>(d); j.overlay = reinterpret_cast<uint64_t*>(d + o_ov); j.frames = nullptr;
-        j.n = 1; j.vw = vw; j.vh = vh; j.flags = flags;
-        j.out = d + o_out; j.out_stride = 3 * vw; j.out_pitch = (int64_t)3 * vw * vh;
-        j.lists = ViewLists{reinterpret_cast<const rmcv_lightblob*>(d + o_blobs), cnt, reinterpret_cast<const rmcv_armour*>(d + o_arm), cnt + 1,
-                            reinterpret_cast<const rmcv_point*>(d + o_pts), nullptr, nullptr, cnt + 3, nullptr, cnt + 2,
-                            reinterpret_cast<const int32_t*>(d + o_offs), n_blobs, n_armours, n_pts, n_neg, 1};
-        e = launch_view(j, c->stream);
-    }
-    c->last_what = "k_view_overlay + k_view_resize";
-    int rcw = 0;
-    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_view_resize");
-    if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(out, out_stride, d + o_out, (size_t)3 * vw, (size_t)3 * vw, vh, hipMemcpyDeviceToHost);
-    if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernels may still be using it)
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_debug_view", e);
-    return rcw;
 }
 
 } // extern "C"

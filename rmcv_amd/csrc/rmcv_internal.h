@@ -1,4 +1,6 @@
-// rmcv_internal.h -- shared declarations of the HIP translation units (not part of the ABI).
+// rmcv_internal.h -- shared declarations of the HIP translation units (not part of the ABI): the device buffers, the kernel launchers of
+// the k_*.hip units, and what the units behind the ABI (rmcv_host, rmcv_stagewise, rmcv_frame, rmcv_pipeline, rmcv_track, rmcv_record,
+// rmcv_gather) need of each other.  Limits and Geom come from bind_plan.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -8,46 +10,14 @@
 #include <vector>
 
 #include "../../include/rmcv_abi.h"
+#include "bind_plan.h"
 #include "image_plan.h"
 #include "pixel_plan.h"
 #include "sparse_plan.h"
 
 namespace rmcv {
 
-// Geometry of the frames currently bound to a context and of the bit planes derived from them.
-// Bit planes (foreground F, "labelled" LAB, "right-exit" NEG) hold one bit per pixel in u64 words,
-// bit b of word k = pixel x = 64*k + b.  Each plane is padded with one zero word left and right of
-// every row and one zero row above and below the image, so a 3x3 neighbourhood never needs a
-// bounds check:  word(y, k) lives at (y + 1) * prow + (k + 1).
-struct Geom {
-    int device;          // HIP device of the owning context: per-device launch state (function attributes) is indexed by it
-    int n_cu;            // compute units of that device (sizes the persistent grid of k_binary)
-    int pixel_halo_nt;   // RMCV_OPT_PIXEL_HALO_NT: the row quads a strip shares with its neighbours are loaded non-temporal too
-    int pixel_rowquad;   // hidden option 1001 (bench.py's RMCV_BENCH_AB): k_binary's row-quad loader even where rows are contiguous
-    int overloads;       // RMCV_OPT_OVERLOADS: SURVEY A.6, which functions the reference's unqualified abs / atan2 / sin / cos on floats are
-    int contour_tier;    // RMCV_OPT_CONTOUR_TIER: 0 = per frame (LDS tables, else mid tier, else literal scanner), 1 = literal, 2 = mid tier
-    int input_format;    // RMCV_OPT_INPUT_FORMAT of the frames bound: 0 BGR, 1..4 a Bayer pattern (recorded when the frames are bound)
-    int sample_bytes;    // RMCV_OPT_INPUT_SAMPLE_BITS of the frames bound, as bytes: 1, or 2 (16-bit Bayer samples; BGR: always 1)
-    int valid_bit;       // RMCV_OPT_INPUT_VALID_BIT: the pixel is bits valid_bit .. valid_bit + 7 of a 2-byte sample
-    int orient;          // RMCV_OPT_INPUT_ORIENT: RMCV_ORIENT_MIRROR | RMCV_ORIENT_FLIP of the frames bound
-    int n_frames;
-    int w, h;
-    int stride;          // bytes between rows of the input (BGR or mosaic)
-    int64_t frame_pitch; // bytes between frames of the input
-    int ww;              // words per row = ceil(w / 64)
-    int prow;            // padded words per row = ww + 2
-    int64_t plane_pitch; // words per frame = (h + 2) * prow
-    int enhance;         // RMCV_OPT_ENHANCE of the frames bound: the pixel pass and the classifier read every byte through the frame's gamma table
-    float enh_max_gain, enh_min_gain; // rmcv_ctx_set_enhance_gains, recorded with it
-    // windowed detection (rmcv_batch_set_windows): w, h, ww, prow, plane_pitch above are the WINDOW's -- everything behind the pixel pass
-    // sees a batch of win_w x win_h images -- while stride and frame_pitch stay the frames'; the frames' own extent is kept here
-    int win;             // 1: every frame is read at its effective origin (Bufs::win_eff)
-    int frame_w, frame_h; // the frames as bound (== w, h without windows)
-    // per-frame detection keys (rmcv_batch_set_frame_camps): camp and lower bound of every frame come from Bufs::key_eff / key_enemy, which every
-    // run with the pixel pass rewrites in front of it; rmcv_params::camp and ::lower_bound are then not read
-    int keys;
-};
-
+// (Limits and Geom, the geometry of the frames currently bound to a context and of the bit planes derived from them: bind_plan.h)
 // (RunPlan, what a run's launches depend on beyond geometry, buffers and params: sparse_plan.h)
 static constexpr int CTR_STRIDE = 32;   // ints between the heads of k_binary's strip queues (Bufs::strip_ctr): a 128-byte line each, 9 of them
 static constexpr int VISIT_CAP = 4096; // border visits of one frame the contour stage holds in LDS (contours_device.h); more -> mid tier
@@ -58,10 +28,6 @@ inline size_t mid_bytes(int slot_cap)
 {
     return (size_t)slot_cap * (6 * 8 + 2 * 4) + (size_t)NN_MID * (2 * 8 + 2 * 4) + (size_t)CAND_MID * 4 * 4;
 }
-
-struct Limits {
-    int max_frames, max_width, max_height, max_contours, max_points, max_blobs, max_armours;
-};
 
 // Device buffers of one context (all sized by Limits at creation, reused by every call).
 struct Bufs {
@@ -304,7 +270,7 @@ inline int view_stages_needed(int flags)
     return RMCV_STAGE_BINARY | ((flags & (RMCV_VIEW_BLOBS | RMCV_VIEW_NEGATIVES)) ? RMCV_STAGE_CONTOURS | RMCV_STAGE_BLOBS : 0) |
            ((flags & RMCV_VIEW_ARMOURS) ? RMCV_STAGE_CONTOURS | RMCV_STAGE_BLOBS | RMCV_STAGE_ARMOURS : 0);
 }
-// (the view entry points of a context: rmcv_host.hip)
+// (the view entry points of a context: rmcv_host.hip; the stage-wise rmcv_debug_view: rmcv_stagewise.hip)
 // what a pipeline needs of them: everything n views need allocated now (blocking); the check of a request against the context's limits;
 // and the enqueue itself on frames the caller has bound and run, the frame list already on the device, nothing blocking
 int ctx_view_prepare(rmcv_ctx* c, int n);

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/../rmcv_amd/csrc"
 name=$1; flags=$2
 mkdir -p /tmp/varall_$name
 objs=""
-for u in k_binary k_contours k_contours_w4 k_detect k_classify k_pnp rmcv_host rmcv_frame rmcv_track rmcv_gather; do
+for u in k_binary k_contours k_contours_w4 k_detect k_classify k_pnp rmcv_host rmcv_stagewise rmcv_rules rmcv_frame rmcv_track rmcv_gather; do
   /opt/rocm/bin/hipcc $flags -O3 -std=c++17 -fPIC --offload-arch=gfx950 -ffp-contract=off -fno-fast-math -Wno-unused-value -c $u.hip -o /tmp/varall_$name/$u.o &
   objs="$objs /tmp/varall_$name/$u.o"
 done
