@@ -495,6 +495,62 @@ int rmcv_classify_armours(rmcv_ctx* ctx, const uint8_t* bgr, int w, int h, int s
 int rmcv_batch_get_identities(rmcv_ctx* ctx, int32_t* identity_out, int cap, int32_t* n_total);
 int rmcv_batch_get_icons(rmcv_ctx* ctx, int frame, uint8_t* icons_out, int cap_armours, int32_t* n_armours);
 
+/* ---- training the icon classifier (executable/svm/optimizer.cpp: C_SVC, LINEAR, trainAuto) -------------------------
+ * The model rmcv_svm_load takes, trained from rows as rmcv_batch_get_icons / rmcv_classify_armours hand them out (1200 raw bytes each,
+ * features = the bytes as f32, unscaled).  OpenCV's solver is not pinned, so the library defines its own exact rule, modelled on
+ * cv::ml::SVM (first-order SMO on the exact integer Gram matrix; rmcv_amd/csrc/device_svm.h is its one source for host and device):
+ * rmcv_svm_train runs it on the GPU, rmcv_svm_train_host sequentially on the CPU, and the two agree bit for bit in every output.
+ * Folds of the grid search come from the caller's permutation, so a result is a function of its arguments alone. */
+#define RMCV_SVM_MAX_GRID 16   /* C values of one grid search */
+#define RMCV_SVM_MAX_DF 28     /* decision functions of 8 classes */
+#define RMCV_SVM_MAX_FOLDS 64
+#define RMCV_SVM_MAX_SAMPLES 8192      /* rows of one training set (the Gram matrix is rows x rows int32) */
+#define RMCV_SVM_MAX_PAIR_SAMPLES 2048 /* rows of two classes together (one pair problem lives in one workgroup's LDS) */
+typedef struct {
+    double  eps;       /* stop when the maximal violation falls below it; >= 0, finite       (1e-3: optimizer.cpp's TermCriteria) */
+    int32_t max_iter;  /* SMO iterations of one pair problem, >= 1; a model cut off here is a valid result               (1000) */
+    int32_t k_fold;    /* folds of the grid search, <= RMCV_SVM_MAX_FOLDS; <= 1: no search, plain training at c_grid[0]    (10) */
+    int32_t n_c;       /* 1 .. RMCV_SVM_MAX_GRID entries of c_grid; 1: plain training                                       (6) */
+    int32_t reserved;  /* 0 */
+    double  c_grid[RMCV_SVM_MAX_GRID]; /* each > 0 and finite           (0.1 * 5^k, k = 0 .. 5: cv::ml::SVM's default grid for C) */
+} rmcv_svm_train_params;
+typedef struct {
+    double  best_c;                           /* the C of the returned model ...                                                   */
+    int32_t best_index;                       /* ... and its grid entry: the lowest cv_errors, the earlier entry on a tie          */
+    int32_t n_df;                             /* n_class * (n_class - 1) / 2                                                       */
+    int32_t cv_errors[RMCV_SVM_MAX_GRID];     /* misclassified test rows over all folds per grid entry; -1: no search was run      */
+    int32_t iterations[RMCV_SVM_MAX_DF];      /* of the returned model's pair problems (i < j, row-major) ...                      */
+    int32_t converged[RMCV_SVM_MAX_DF];       /* ... 0: cut off at max_iter                                                        */
+    double  objective[RMCV_SVM_MAX_DF];       /* ... their dual objectives, 1/2 a'Qa - e'a                                         */
+    double  phase_ms[6];                      /* Gram; the search's solver, weights and predict; the returned model's solver and
+                                               * weights: GPU time between events (rmcv_svm_train), wall time (rmcv_svm_train_host)  */
+    double* alpha_out;                        /* IN, may be NULL: [n_df][n], the returned model's alphas by dataset row (0 for rows
+                                               * of other classes)                                                                 */
+    char    message[128];                     /* why the call was refused (RMCV_ERR_BAD_ARG); empty otherwise                      */
+} rmcv_svm_train_report;
+void rmcv_svm_train_defaults(rmcv_svm_train_params* out);
+/* samples u8 [n][1200], responses i32 [n] (any values: the distinct ones in ascending order become labels_out, 2 .. 8 of them),
+ * perm i32 [n] or NULL (identity): fold k of K tests rows perm[floor(k n / K) .. floor((k + 1) n / K)) and trains on the rest.
+ * params NULL: the defaults.  weights_out [n_df][1200], rho_out [n_df], labels_out [n_class] are sized by the caller for 8 classes or
+ * for what it knows; report may be NULL.  RMCV_ERR_BAD_ARG with a message (rmcv_last_error, report->message), decided before any GPU
+ * work: fewer than 2 or more than 8 classes; perm not a permutation; a fold whose training part lacks a class; n or two classes' rows
+ * beyond the limits above; a parameter outside its range.  The device workspace is allocated per call and freed on every path; waits
+ * run against the context's deadline (RMCV_ERR_TIMEOUT names the kernel). */
+int rmcv_svm_train(rmcv_ctx* ctx, const uint8_t* samples, const int32_t* responses, int n, const int32_t* perm,
+                   const rmcv_svm_train_params* params, float* weights_out, double* rho_out, int32_t* labels_out, int32_t* n_class_out,
+                   rmcv_svm_train_report* report);
+/* the same without a context and without a GPU: the sequential form of the same header */
+int rmcv_svm_train_host(const uint8_t* samples, const int32_t* responses, int n, const int32_t* perm,
+                        const rmcv_svm_train_params* params, float* weights_out, double* rho_out, int32_t* labels_out, int32_t* n_class_out,
+                        rmcv_svm_train_report* report);
+/* gram_out [n][n] int32: the exact dot products of the rows (each <= 1200 * 255^2 < 2^31); n <= RMCV_SVM_MAX_SAMPLES */
+int rmcv_svm_gram(rmcv_ctx* ctx, const uint8_t* samples, int n, int32_t* gram_out);
+int rmcv_svm_gram_host(const uint8_t* samples, int n, int32_t* gram_out);
+/* identity_out[r] = the loaded model's (rmcv_svm_load) class label of row r of samples u8 [n][1200], in the arithmetic of RMCV_STAGE_IDENTITY */
+int rmcv_svm_predict(rmcv_ctx* ctx, const uint8_t* samples, int n, int32_t* identity_out);
+int rmcv_svm_predict_host(const float* weights, const double* rho, const int32_t* labels, int n_class, const uint8_t* samples, int n,
+                          int32_t* identity_out);
+
 /* device-side, frame-major compaction into caller-provided HBM (e.g. torch tensors): d_armours_out has room
  * for `cap` armours, d_frame_offs for n_frames+1 int32 (last entry = total, which may exceed cap: then only the
  * first `cap` were written).  Asynchronous on hip_stream.  This is the payload of the multi-GPU gather. */

@@ -16,6 +16,7 @@ from .abi import (ARMOUR, BAYER_BG, BAYER_GB, BAYER_GR, BAYER_PATTERNS, BAYER_RG
 from .api import Context, debug_view
 from .pipeline import Pipeline
 from .recorder import Recorder, Session, pack, pack_bound, unpack
+from . import svm
 from .tracker import TRACKER_OVF, AimConfig, AttitudeConfig, Tracker, TrackerConfig, default_aim_config, default_attitude_config, default_tracker_config
 
 __all__ = [n for n in dir() if not n.startswith("_")]

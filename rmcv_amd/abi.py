@@ -108,6 +108,7 @@ EXPORTS = [
     "rmcv_recorder_freeze", "rmcv_recorder_resume", "rmcv_recorder_count", "rmcv_recorder_entry", "rmcv_recorder_frame", "rmcv_recorder_device_frame",
     "rmcv_recorder_save", "rmcv_session_append", "rmcv_session_open", "rmcv_session_count", "rmcv_session_entry", "rmcv_session_frame", "rmcv_session_close",
     "rmcv_pipeline_set_recorder",
+    "rmcv_svm_train_defaults", "rmcv_svm_train", "rmcv_svm_train_host", "rmcv_svm_gram", "rmcv_svm_gram_host", "rmcv_svm_predict", "rmcv_svm_predict_host",
 ]
 
 
@@ -153,6 +154,24 @@ class PipelineInfo(C.Structure):
                 ("dense_split", C.c_uint64), ("hot_batches", C.c_uint64), ("hot_contexts", C.c_int32), ("_pad2", C.c_int32), ("latency_batches", C.c_uint64),
                 ("host_blocking_calls", C.c_uint64), ("wait_timeout_ms", C.c_int32), ("_pad3", C.c_int32), ("max_submit_us", C.c_double), ("heavy_batches", C.c_uint64), ("held_back", C.c_uint64)]
 
+
+SVM_MAX_GRID, SVM_MAX_DF, SVM_MAX_FOLDS, SVM_MAX_SAMPLES, SVM_MAX_PAIR_SAMPLES = 16, 28, 64, 8192, 2048
+
+
+class SvmTrainParams(C.Structure):
+    """rmcv_svm_train_params (defaults: rmcv_svm_train_defaults = optimizer.cpp's criteria and cv::ml::SVM's default C grid)"""
+    _fields_ = [("eps", C.c_double), ("max_iter", C.c_int32), ("k_fold", C.c_int32), ("n_c", C.c_int32), ("reserved", C.c_int32),
+                ("c_grid", C.c_double * SVM_MAX_GRID)]
+
+
+class SvmTrainReport(C.Structure):
+    """rmcv_svm_train_report"""
+    _fields_ = [("best_c", C.c_double), ("best_index", C.c_int32), ("n_df", C.c_int32), ("cv_errors", C.c_int32 * SVM_MAX_GRID),
+                ("iterations", C.c_int32 * SVM_MAX_DF), ("converged", C.c_int32 * SVM_MAX_DF), ("objective", C.c_double * SVM_MAX_DF),
+                ("phase_ms", C.c_double * 6), ("alpha_out", C.c_void_p), ("message", C.c_char * 128)]
+
+
+assert C.sizeof(SvmTrainParams) == 152 and C.sizeof(SvmTrainReport) == 712
 
 RECORDER_MAX_FRAMES = 64
 
@@ -363,6 +382,16 @@ def load(path):
         L.rmcv_session_close.restype = None
         L.rmcv_session_close.argtypes = [C.c_void_p]
         L.rmcv_pipeline_set_recorder.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    if hasattr(L, "rmcv_svm_train_host"):  # (builds from before the classifier's trainer stay loadable for A/B runs)
+        train = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_svm_train_defaults.restype = None
+        L.rmcv_svm_train_defaults.argtypes = [C.c_void_p]
+        L.rmcv_svm_train_host.argtypes = train
+        L.rmcv_svm_train.argtypes = [C.c_void_p] + train
+        L.rmcv_svm_gram_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rmcv_svm_gram.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+        L.rmcv_svm_predict_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.rmcv_svm_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L

@@ -623,6 +623,20 @@ class Context:
         assert weights.shape == (n_class * (n_class - 1) // 2, abi.SVM_FEATURES) and len(rho) == weights.shape[0]
         self._chk(lib().rmcv_svm_load(self._h, ptr(weights), ptr(rho), ptr(labels), n_class))
 
+    def svm_predict(self, samples):
+        """rmcv_svm_predict: the loaded model's labels of uint8 [n, 1200] icon rows, in the arithmetic of RMCV_STAGE_IDENTITY"""
+        s = np.ascontiguousarray(samples, np.uint8)
+        s = s.reshape(len(s), -1) if s.size else s.reshape(0, abi.SVM_FEATURES)
+        assert s.shape[1] == abi.SVM_FEATURES
+        out = np.zeros(len(s), np.int32)
+        self._chk(lib().rmcv_svm_predict(self._h, ptr(s) if len(s) else None, len(s), ptr(out) if len(s) else None))
+        return out
+
+    def svm_train(self, samples, responses, perm=None, **params):
+        """rmcv_svm_train on this context's GPU -> rmcv_amd.svm.Model (rmcv_amd.svm.train_auto with ctx=self)"""
+        from . import svm
+        return svm.train_auto(samples, responses, perm, ctx=self, **params)
+
     def classify_armours(self, image, armours):
         """main.cpp:178-181 for one frame -> (identity int32[n], armours with clamped icon, icons uint8[n,20,20,3])"""
         image, h, w, rowb = self._frame(image)

@@ -14,6 +14,7 @@
 #include "image_plan.h"
 #include "pixel_plan.h"
 #include "sparse_plan.h"
+#include "svm_plan.h"
 
 namespace rmcv {
 
@@ -421,6 +422,15 @@ int recorder_enqueue(rmcv_recorder* r, const RecordBatch& b, const int32_t* fram
 void ctx_record_batch(const rmcv_ctx* c, RecordBatch* b);
 // bytes of one pixel of the frames the context's options describe (what the next binding will record)
 int ctx_frame_pixel_bytes(const rmcv_ctx* c);
+
+// ---- the icon classifier's trainer (k_svm.hip) ----
+// int32 [n][n] of u8 [n][1200]
+hipError_t launch_svm_gram(const uint8_t* d_samples, int n, int32_t* d_gram, hipStream_t s);
+// k_svm_smo + k_svm_weights over d.problems[0 .. n_problems): alphas, rho, outs, weights [n_problems][1200]; between (nullable): recorded between the two
+hipError_t launch_svm_solve(const SvmDevice& d, int n_problems, double eps, int max_iter, hipStream_t s, hipEvent_t between = nullptr);
+// d_out[m * n + r], m < n_models: row r under model m * k_fold + d_fold_of[r] (d_fold_of null: model 0); d_labels null: class indices
+hipError_t launch_svm_predict(const uint8_t* d_samples, int n, const float* d_weights, const double* d_rho, int n_class, const int32_t* d_fold_of, int k_fold,
+                              int n_models, const int32_t* d_labels, int32_t* d_out, hipStream_t s);
 
 } // namespace rmcv
 
