@@ -1204,7 +1204,7 @@ typedef struct rmcv_recorder_config {
     int32_t max_w_bytes; /* bytes of a row                                        (default 3 * 1280)   */
     int32_t max_h;       /*                                                       (default 1024)       */
     int32_t user_bytes;  /* capacity of the user blob                             (default 256)        */
-    int32_t _reserved;
+    int32_t track_cap;   /* tracks a loop record keeps per chosen frame, 1 .. RMCV_TRACKER_MAX_CAP; 0: no loop records (default 0) */
 } rmcv_recorder_config;
 /* what the host knows of a recorded batch at its submit, plus what the device reported of it */
 typedef struct rmcv_record_entry {
@@ -1219,7 +1219,8 @@ typedef struct rmcv_record_entry {
     int32_t win_w, win_h;  /* a windowed batch's window (0: whole frames) */
     int32_t has_keys;      /* keys[] holds the batch's effective per-frame detection keys (rmcv_batch_get_frame_keys), camps[] the raw camps */
     int32_t has_origins;   /* origins[] holds the batch's effective window origins (rmcv_batch_get_windows) */
-    int32_t user_bytes, _pad;
+    int32_t user_bytes;
+    int32_t loop_bytes;    /* bytes of ONE loop record of this entry (rmcv_loop_bound of the recorder's track_cap); 0: the batch has none */
     rmcv_params params;
     int32_t frames[RMCV_RECORDER_MAX_FRAMES];   /* indices into the batch */
     int64_t sizes[RMCV_RECORDER_MAX_FRAMES];    /* packed sizes */
@@ -1265,6 +1266,137 @@ void rmcv_session_close(rmcv_session* s);
  * later submit whose n_frames does not reach every index, or whose rows or height are beyond the recorder's, is refused before anything
  * is enqueued. */
 int rmcv_pipeline_set_recorder(rmcv_pipeline* pl, rmcv_recorder* rec, const int32_t* frames, int n);
+
+/* ---- the recorder for the closed loop: loop records, tracked replay, device-side triggers --------------------------------
+ * A recorder created with track_cap > 0 keeps, for every chosen frame k of every TRACKED submit (rmcv_pipeline_submit_tracked[_serial]), a
+ * LOOP RECORD: the state of stream frames[k] right behind the batch's tracker step and aim step, written on the device by one launch
+ * (k_loop_record, one workgroup per chosen frame) on the stream that ran those steps, in front of the tracker's event and of the batch's
+ * completion -- rmcv_pipeline_wait(ticket) covers it.  A loop record is a rmcv_loop_state followed by n_tracks x { rmcv_track, float[8] }
+ * (the side record: rmcv_tracker_get's last_vertices), in an area of rmcv_loop_bound(track_cap) bytes whose tail is zero.  Untracked
+ * submits, stand-alone records and recorders with track_cap == 0 have none (rmcv_record_entry::loop_bytes == 0), and record exactly what
+ * they did before.
+ * The step of a batch is enqueued by the NEXT call on the pipeline (see rmcv_pipeline_submit): until then the readers of the recorder
+ * (rmcv_recorder_count / _entry / _frame / _loop / _save) answer RMCV_ERR_BAD_ARG for that newest batch, with a message -- wait for its
+ * ticket, or drain, first.  They never return a half-written record: each waits, 5 s deadline, for the packing AND the loop launch. */
+#define RMCV_LOOP_TRUNCATED 1  /* rmcv_loop_state::flags: n_tracking exceeded the recorder's track_cap; the first track_cap tracks are kept */
+typedef struct rmcv_loop_state {
+    int32_t stream;              /* index of the stream = of the frame in its batch */
+    int32_t n_tracking, status;  /* rmcv_tracker_counts' */
+    int32_t n_armours;           /* the frame's armours the step observed */
+    rmcv_point origin_next;      /* the requested origin the step left: the next batch's request (rmcv_tracker_get's origin) */
+    rmcv_point origin_eff;       /* the effective origin this batch was read at (rmcv_batch_get_windows); (0, 0): whole frames */
+    int32_t frame_status;        /* the frame's RMCV_FRAME_* word */
+    int32_t has_camps;           /* bit 0: camp is the tracker's (rmcv_tracker_set_camps); bit 1: lower_bound too */
+    int32_t camp, lower_bound;   /* raw, as the tracker's tables held them behind the step */
+    int32_t has_key;             /* key[] holds the frame's effective detection key (the batch ran with per-frame keys) */
+    int32_t key[4];              /* rmcv_batch_get_frame_keys' */
+    int32_t has_cameras;         /* cam_eff is the effective index of a camera table (rmcv_pipeline_set_frame_cameras); else 0 */
+    int32_t cam_eff;
+    int32_t has_aim;             /* aiming was on: aim is this step's record */
+    int32_t has_attitude;        /* attitude was on: attitude, packet_errors, attitude_config, gripper2camera are this batch's */
+    int32_t has_packet;          /* packet[] holds the 24 bytes the attitude step of this batch read */
+    int32_t packet_errors;
+    int32_t n_tracks;            /* tracks stored behind this struct: min(n_tracking, track_cap of the recorder) */
+    int32_t flags;               /* RMCV_LOOP_* */
+    uint32_t fired;              /* RMCV_TRIG_* this record raised against its predecessor, BEFORE the trigger mask; 0 without one */
+    int32_t has_prev;            /* a predecessor was compared */
+    int32_t trig_frame_status_mask; /* the rule's inputs beside the two records, as the recorder's trigger config had them at the launch: */
+    double  trig_aim_jump_deg;      /* with them fired can be recomputed from a file alone (+inf and 0 while triggers are off) */
+    int64_t timestamp;           /* the step's */
+    uint64_t sequence;           /* the recorder's, of the batch */
+    rmcv_aim aim;
+    rmcv_aim_input aim_input;    /* what the aim step read (behind this batch's attitude step) */
+    rmcv_attitude attitude;
+    uint8_t packet[24];
+    rmcv_tracker_config tracker_config;    /* the setup the step ran under: a record is self-contained */
+    rmcv_aim_config aim_config;            /* the stream's effective one (global or per-stream); zero without has_aim */
+    rmcv_attitude_config attitude_config;  /* zero without has_attitude */
+    double gripper2camera[16];             /* the stream's effective one (the config's or rmcv_tracker_set_stream_cameras'); zero without has_attitude */
+} rmcv_loop_state;
+/* bytes of one loop area: sizeof(rmcv_loop_state) + track_cap x (sizeof(rmcv_track) + 32); track_cap 0 .. RMCV_TRACKER_MAX_CAP, else -1 */
+int64_t rmcv_loop_bound(int track_cap);
+
+/* THE TRIGGER RULE, a pure function of two loop records of one stream in consecutive batches and the config (device_loop.h: loop_trigger,
+ * compiled for host and device from one source).  had_target(r) := !(r.aim.status & RMCV_AIM_NO_TARGET); solved(r) := had_target(r) &&
+ * !(r.aim.status & RMCV_AIM_NO_SOLUTION).
+ *   RMCV_TRIG_NO_ARMOURS     prev.n_armours > 0 && cur.n_armours == 0
+ *   RMCV_TRIG_TRACK_DROPPED  cur.n_tracking < prev.n_tracking
+ *   RMCV_TRIG_TRACKER_OVF    (cur.status & RMCV_TRACKER_OVF) && !(prev.status & RMCV_TRACKER_OVF)
+ *   RMCV_TRIG_FRAME_STATUS   (cur.frame_status & cfg.frame_status_mask & ~prev.frame_status) != 0
+ *   only with prev.has_aim && cur.has_aim:
+ *   RMCV_TRIG_TARGET_LOST    had_target(prev) && (cur.aim.status & RMCV_AIM_NO_TARGET)
+ *   RMCV_TRIG_TARGET_SWITCH  had_target(prev) && had_target(cur) && cur.aim.identity != prev.aim.identity
+ *   RMCV_TRIG_NO_SOLUTION    (cur.aim.status & RMCV_AIM_NO_SOLUTION) && !(prev.aim.status & RMCV_AIM_NO_SOLUTION)
+ *   RMCV_TRIG_AIM_JUMP       solved(prev) && solved(cur) && (fabs(cur.aim.yaw - prev.aim.yaw) > cfg.aim_jump_deg ||
+ *                            fabs(cur.aim.pitch - prev.aim.pitch) > cfg.aim_jump_deg)   -- a NaN difference compares false
+ *   only with prev.has_attitude && cur.has_attitude:
+ *   RMCV_TRIG_PACKET_ERROR   cur.packet_errors > prev.packet_errors
+ * The device evaluates it for a record only against the record of the SAME chosen frame in the recorder's previous slot, and only when
+ * that slot holds the immediately preceding sequence, of the same tracker, with the same chosen frames, recorded with loop records, and
+ * no rmcv_recorder_resume lies between; otherwise nothing is compared, fired == 0 and has_prev == 0. */
+#define RMCV_TRIG_NO_ARMOURS 1
+#define RMCV_TRIG_TRACK_DROPPED 2
+#define RMCV_TRIG_TRACKER_OVF 4
+#define RMCV_TRIG_FRAME_STATUS 8
+#define RMCV_TRIG_TARGET_LOST 16
+#define RMCV_TRIG_TARGET_SWITCH 32
+#define RMCV_TRIG_NO_SOLUTION 64
+#define RMCV_TRIG_AIM_JUMP 128
+#define RMCV_TRIG_PACKET_ERROR 256
+#define RMCV_TRIG_ALL 511
+typedef struct rmcv_trigger_config {
+    uint32_t mask;              /* RMCV_TRIG_* that take the latch; 0: none */
+    int32_t post_batches;       /* batches still recorded once the host has noticed the latch, >= 0 */
+    int32_t frame_status_mask;  /* RMCV_FRAME_* bits RMCV_TRIG_FRAME_STATUS looks at */
+    int32_t reserved;
+    double aim_jump_deg;        /* RMCV_TRIG_AIM_JUMP's bound, in the unit of rmcv_aim::yaw / ::pitch; not NaN, >= 0 (+inf: never) */
+} rmcv_trigger_config;
+typedef struct rmcv_trigger_info {
+    int32_t fired;              /* the latch is taken (as the host sees it now) */
+    uint32_t mask;              /* fired & mask of the record that took it */
+    uint64_t sequence;          /* the recorder sequence of its batch */
+    int32_t k, stream;          /* the chosen frame's index in the entry, and its stream */
+    int32_t noticed;            /* a submit has seen the latch */
+    int32_t batches_since;      /* batches recorded since then */
+} rmcv_trigger_info;
+/* the rule on the host (no device).  prev / cur: loop records (only their fixed parts are read).  RMCV_ERR_BAD_ARG: a null argument. */
+int rmcv_loop_trigger_host(const void* prev, const void* cur, const rmcv_trigger_config* cfg, uint32_t* fired);
+/* THE LATCH.  A record with (fired & mask) != 0 takes the recorder's latch with one atomic compare-and-swap on a device word -- the first
+ * wins -- and the winner writes {mask fired, sequence, k, stream} to device memory and to a mapped pinned host copy.  Every submit that
+ * records reads that host copy on entry (a plain load: no HIP call, no wait); once it sees the latch, post_batches more batches are
+ * recorded, STARTING WITH THE ONE BEING ENQUEUED, and the recorder is then frozen exactly as rmcv_recorder_freeze leaves it.
+ * rmcv_recorder_resume clears the latch and re-arms it (synchronous: it waits for the recorder's launches in flight).
+ * SIZING.  The step of the batch with sequence s, and with it the launch that may take the latch, is enqueued by the next call on the
+ * pipeline, and is complete once its ticket t has been waited for or collected.  A caller keeps the pipeline's contract -- ticket t is
+ * collected (or waited for) before ticket t + depth is submitted -- so the submit of sequence s + depth at the latest sees the latch, and
+ * the last batch recorded is at most s + depth + post_batches - 1: a ring of
+ *     slots >= depth + post_batches
+ * still holds the triggering batch when the recorder freezes.  rmcv_pipeline_set_recorder, and every submit, refuse a recorder whose
+ * triggers are armed on a smaller ring.  (A host that waits for every ticket before the next submit notices at s + 1 and holds exactly
+ * post_batches batches behind s.)
+ * cfg NULL: triggers off.  RMCV_ERR_BAD_ARG with a message: post_batches < 0, aim_jump_deg NaN or negative, mask beyond RMCV_TRIG_ALL, a
+ * non-zero mask on a recorder with track_cap == 0. */
+int rmcv_recorder_set_trigger(rmcv_recorder* rec, const rmcv_trigger_config* cfg);
+int rmcv_recorder_trigger(rmcv_recorder* rec, rmcv_trigger_info* info);
+/* frame k's loop record of held batch i: *size = rmcv_loop_bound(track_cap) bytes (the tail behind n_tracks tracks is zero).
+ * RMCV_ERR_BAD_ARG: the batch has none; RMCV_ERR_CAPACITY: cap is smaller (*size says what is needed). */
+int rmcv_recorder_loop(rmcv_recorder* rec, int i, int k, void* out, int64_t cap, int64_t* size);
+int rmcv_session_loop(const rmcv_session* s, int i, int k, void* out, int64_t cap, int64_t* size);
+/* rmcv_session_append for an entry with loop records: loops[k] = entry->loop_bytes bytes, written behind the packed frames.  The reader
+ * checks loop_bytes against rmcv_loop_bound, and every record's n_tracks against loop_bytes, before it reads anything else of them. */
+int rmcv_session_append_loop(const char* path, const rmcv_record_entry* entry, const void* user, const uint8_t* const* packed,
+                             const uint8_t* const* loops);
+/* RESTORING A TRACKER for a replay.  rmcv_tracker_restore sets stream `stream` of `trk` to what a loop record holds: list, side records,
+ * count, status, requested origin (origin_next), camp and lower bound (with has_camps; the tracker's per-stream camps are switched on as
+ * the record says), aim record and aim input (with has_aim), attitude and packet_errors (with has_attitude).  Synchronous.  The setup is
+ * the caller's: the *_from_loop extractors hand it out (n_streams is the recorded tracker's).  RMCV_ERR_BAD_ARG with a message: a
+ * truncated record (RMCV_LOOP_TRUNCATED), n_tracks outside 0 .. the tracker's track_cap or != n_tracking, has_aim / has_attitude on a
+ * tracker whose aiming / attitude is off.  The extractors refuse a truncated record or an n_tracks outside 0 .. RMCV_TRACKER_MAX_CAP;
+ * *has == 0: the part was off (the output is zero). */
+int rmcv_tracker_restore(rmcv_tracker* trk, int stream, const void* loop_record);
+int rmcv_tracker_config_from_loop(const void* loop_record, rmcv_tracker_config* out);
+int rmcv_tracker_aim_config_from_loop(const void* loop_record, rmcv_aim_config* out, int32_t* has);
+int rmcv_tracker_attitude_config_from_loop(const void* loop_record, rmcv_attitude_config* out, double gripper2camera[16], int32_t* has);
 
 /* ---- device memory for hosts without HIP headers (tools/pipeline_bench.c): frames resident in HBM ------------------------------- */
 int  rmcv_device_alloc(int device, int64_t bytes, void** d_ptr);

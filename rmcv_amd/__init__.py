@@ -15,8 +15,10 @@ from .abi import (ARMOUR, BAYER_BG, BAYER_GB, BAYER_GR, BAYER_PATTERNS, BAYER_RG
                   VIEW_ALL, VIEW_ARMOURS, VIEW_BLOBS, VIEW_NEGATIVES, debug_view_host)
 from .api import Context, debug_view
 from .pipeline import Pipeline
-from .recorder import Recorder, Session, pack, pack_bound, unpack
+from .recorder import LoopRecord, Recorder, Session, loop_bound, loop_field_at, loop_trigger, pack, pack_bound, unpack
 from . import svm
+from .abi import (LOOP_TRUNCATED, TRIG_AIM_JUMP, TRIG_ALL, TRIG_FRAME_STATUS, TRIG_NO_ARMOURS, TRIG_NO_SOLUTION, TRIG_PACKET_ERROR, TRIG_TARGET_LOST, TRIG_TARGET_SWITCH,
+                  TRIG_TRACK_DROPPED, TRIG_TRACKER_OVF, LoopState, TriggerConfig, TriggerInfo)
 from .tracker import TRACKER_OVF, AimConfig, AttitudeConfig, Tracker, TrackerConfig, default_aim_config, default_attitude_config, default_tracker_config
 
 __all__ = [n for n in dir() if not n.startswith("_")]

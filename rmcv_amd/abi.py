@@ -108,6 +108,8 @@ EXPORTS = [
     "rmcv_recorder_freeze", "rmcv_recorder_resume", "rmcv_recorder_count", "rmcv_recorder_entry", "rmcv_recorder_frame", "rmcv_recorder_device_frame",
     "rmcv_recorder_save", "rmcv_session_append", "rmcv_session_open", "rmcv_session_count", "rmcv_session_entry", "rmcv_session_frame", "rmcv_session_close",
     "rmcv_pipeline_set_recorder",
+    "rmcv_loop_bound", "rmcv_loop_trigger_host", "rmcv_recorder_set_trigger", "rmcv_recorder_trigger", "rmcv_recorder_loop", "rmcv_session_loop", "rmcv_session_append_loop",
+    "rmcv_tracker_restore", "rmcv_tracker_config_from_loop", "rmcv_tracker_aim_config_from_loop", "rmcv_tracker_attitude_config_from_loop",
     "rmcv_svm_train_defaults", "rmcv_svm_train", "rmcv_svm_train_host", "rmcv_svm_gram", "rmcv_svm_gram_host", "rmcv_svm_predict", "rmcv_svm_predict_host",
 ]
 
@@ -179,7 +181,7 @@ RECORDER_MAX_FRAMES = 64
 class RecorderConfig(C.Structure):
     """rmcv_recorder_config (0 in a field = the default)"""
     _fields_ = [("slots", C.c_int32), ("max_frames", C.c_int32), ("max_w_bytes", C.c_int32), ("max_h", C.c_int32), ("user_bytes", C.c_int32),
-                ("_reserved", C.c_int32)]
+                ("track_cap", C.c_int32)]
 
 
 class RecordEntry(C.Structure):
@@ -187,13 +189,81 @@ class RecordEntry(C.Structure):
     _fields_ = [("ticket", C.c_uint64), ("sequence", C.c_uint64), ("timestamp", C.c_int64), ("n_frames", C.c_int32), ("batch_frames", C.c_int32),
                 ("w", C.c_int32), ("h", C.c_int32), ("w_bytes", C.c_int32), ("stride", C.c_int32), ("lag", C.c_int32), ("input_format", C.c_int32),
                 ("sample_bits", C.c_int32), ("valid_bit", C.c_int32), ("orient", C.c_int32), ("stages", C.c_int32), ("win_w", C.c_int32), ("win_h", C.c_int32),
-                ("has_keys", C.c_int32), ("has_origins", C.c_int32), ("user_bytes", C.c_int32), ("_pad", C.c_int32), ("params", Params),
+                ("has_keys", C.c_int32), ("has_origins", C.c_int32), ("user_bytes", C.c_int32), ("loop_bytes", C.c_int32), ("params", Params),
                 ("frames", C.c_int32 * RECORDER_MAX_FRAMES), ("sizes", C.c_int64 * RECORDER_MAX_FRAMES), ("keys", (C.c_int32 * 4) * RECORDER_MAX_FRAMES),
                 ("camps", C.c_int32 * RECORDER_MAX_FRAMES),
                 ("origins", (C.c_int32 * 2) * RECORDER_MAX_FRAMES)]
 
 
 assert C.sizeof(RecordEntry) == 2712
+
+# ---- the recorder's loop records (include/rmcv_abi.h: rmcv_loop_state, rmcv_trigger_config)
+LOOP_TRUNCATED = 1
+(TRIG_NO_ARMOURS, TRIG_TRACK_DROPPED, TRIG_TRACKER_OVF, TRIG_FRAME_STATUS, TRIG_TARGET_LOST, TRIG_TARGET_SWITCH, TRIG_NO_SOLUTION, TRIG_AIM_JUMP,
+ TRIG_PACKET_ERROR) = (1 << b for b in range(9))
+TRIG_ALL = 511
+
+
+class _Aim(C.Structure):
+    """rmcv_aim"""
+    _fields_ = [("track", C.c_int32), ("identity", C.c_int32), ("lost_count", C.c_int32), ("status", C.c_int32), ("pitch", C.c_double), ("yaw", C.c_double),
+                ("flight_time", C.c_double), ("distance", C.c_double), ("point", C.c_double * 3)]
+
+
+class _AimInput(C.Structure):
+    """rmcv_aim_input"""
+    _fields_ = [("world2camera", C.c_double * 16), ("motor_angle", C.c_double)]
+
+
+class _Attitude(C.Structure):
+    """rmcv_attitude"""
+    _fields_ = [("roll", C.c_double), ("pitch", C.c_double), ("yaw", C.c_double)]
+
+
+class _TrackerConfig(C.Structure):
+    """rmcv_tracker_config (tracker.TrackerConfig is the same layout)"""
+    _fields_ = [("n_streams", C.c_int32), ("track_cap", C.c_int32), ("process_noise", C.c_double), ("measurement_noise", C.c_double),
+                ("error", C.c_double), ("tick_frequency", C.c_double), ("roi_scale_w", C.c_float), ("roi_scale_h", C.c_float),
+                ("frame_w", C.c_int32), ("frame_h", C.c_int32), ("win_w", C.c_int32), ("win_h", C.c_int32)]
+
+
+class _AimConfig(C.Structure):
+    """rmcv_aim_config (tracker.AimConfig is the same layout)"""
+    _fields_ = [("g", C.c_double), ("v0", C.c_double), ("height", C.c_double), ("offset_x", C.c_float), ("offset_y", C.c_float),
+                ("angle_offset", C.c_double), ("latency_s", C.c_double), ("mode", C.c_int32), ("height_mode", C.c_int32), ("source", C.c_int32),
+                ("pick", C.c_int32), ("lead_iterations", C.c_int32), ("max_lost", C.c_int32), ("overloads", C.c_int32), ("identity_mask", C.c_uint32)]
+
+
+class _AttitudeConfig(C.Structure):
+    """rmcv_attitude_config (tracker.AttitudeConfig is the same layout)"""
+    _fields_ = [("gripper2camera", C.c_double * 16), ("motor_angle_mode", C.c_int32), ("reserved", C.c_int32)]
+
+
+class LoopState(C.Structure):
+    """rmcv_loop_state: the fixed part of a loop record"""
+    _fields_ = [("stream", C.c_int32), ("n_tracking", C.c_int32), ("status", C.c_int32), ("n_armours", C.c_int32),
+                ("origin_next", C.c_int32 * 2), ("origin_eff", C.c_int32 * 2), ("frame_status", C.c_int32), ("has_camps", C.c_int32),
+                ("camp", C.c_int32), ("lower_bound", C.c_int32), ("has_key", C.c_int32), ("key", C.c_int32 * 4), ("has_cameras", C.c_int32),
+                ("cam_eff", C.c_int32), ("has_aim", C.c_int32), ("has_attitude", C.c_int32), ("has_packet", C.c_int32), ("packet_errors", C.c_int32),
+                ("n_tracks", C.c_int32), ("flags", C.c_int32), ("fired", C.c_uint32), ("has_prev", C.c_int32), ("trig_frame_status_mask", C.c_int32),
+                ("trig_aim_jump_deg", C.c_double), ("timestamp", C.c_int64), ("sequence", C.c_uint64), ("aim", _Aim), ("aim_input", _AimInput), ("attitude", _Attitude),
+                ("packet", C.c_uint8 * 24), ("tracker_config", _TrackerConfig), ("aim_config", _AimConfig), ("attitude_config", _AttitudeConfig),
+                ("gripper2camera", C.c_double * 16)]
+
+
+class TriggerConfig(C.Structure):
+    """rmcv_trigger_config"""
+    _fields_ = [("mask", C.c_uint32), ("post_batches", C.c_int32), ("frame_status_mask", C.c_int32), ("reserved", C.c_int32), ("aim_jump_deg", C.c_double)]
+
+
+class TriggerInfo(C.Structure):
+    """rmcv_trigger_info"""
+    _fields_ = [("fired", C.c_int32), ("mask", C.c_uint32), ("sequence", C.c_uint64), ("k", C.c_int32), ("stream", C.c_int32), ("noticed", C.c_int32),
+                ("batches_since", C.c_int32)]
+
+
+LOOP_SIDE_BYTES = 32
+assert C.sizeof(TriggerConfig) == 24 and C.sizeof(TriggerInfo) == 32 and C.sizeof(LoopState) % 8 == 0
 
 
 # rmcv_pipeline_hook: int (*)(void* user, uint64_t ticket, void* d_record, int64_t record_bytes, void* hip_stream, void** done_event)
@@ -382,6 +452,19 @@ def load(path):
         L.rmcv_session_close.restype = None
         L.rmcv_session_close.argtypes = [C.c_void_p]
         L.rmcv_pipeline_set_recorder.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]
+    if hasattr(L, "rmcv_loop_bound"):  # (builds from before the recorder's loop records stay loadable for A/B runs)
+        L.rmcv_loop_bound.restype = C.c_int64
+        L.rmcv_loop_bound.argtypes = [C.c_int]
+        L.rmcv_loop_trigger_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_recorder_set_trigger.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_recorder_trigger.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_recorder_loop.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        L.rmcv_session_loop.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int64, C.c_void_p]
+        L.rmcv_session_append_loop.argtypes = [C.c_char_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_restore.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rmcv_tracker_config_from_loop.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_aim_config_from_loop.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_tracker_attitude_config_from_loop.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     if hasattr(L, "rmcv_svm_train_host"):  # (builds from before the classifier's trainer stay loadable for A/B runs)
         train = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rmcv_svm_train_defaults.restype = None

@@ -1147,7 +1147,7 @@ int rmcv_batch_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, void* hi
 
 namespace rmcv {
 // one step of the device tracker behind the context's last run (every check before the first enqueue); never synchronises
-int ctx_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, int stages, hipStream_t s)
+int ctx_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, int stages, hipStream_t s, const LoopTicket* loop)
 {
     if (!c) return RMCV_ERR_BAD_ARG;
     if (!trk) return fail(c, RMCV_ERR_BAD_ARG, "null tracker");
@@ -1175,6 +1175,25 @@ int ctx_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, int stages, hip
     HIPCHK(c, launch_track(tc, tracker_bufs(trk), c->bufs, c->lim, (stages & RMCV_STAGE_IDENTITY) != 0, (stages & RMCV_STAGE_POSE) != 0,
                            g.win ? c->bufs.win_eff : nullptr, timestamp, s), "k_track");
     if (tracker_aim_on(trk)) HIPCHK(c, launch_aim(trk, timestamp, s), "k_aim"); // the aim step reads the lists the step has just left
+    // the recorder's loop records: the state the two steps have just left, in front of the tracker's event -- the next batch's
+    // attitude step, which rewrites attitudes and aim inputs, waits for that event
+    if (loop && loop->rec) {
+        LoopArgs a{};
+        if ((rc = recorder_loop_begin(*loop, trk, &a, s))) return fail(c, rc, rmcv_recorder_last_error(loop->rec));
+        const Bufs& b = c->bufs;
+        a.n_streams = tc.n_streams, a.trk_cap = tc.track_cap, a.tb = tracker_bufs(trk);
+        a.aims = trk->aims, a.aim_inputs = trk->aim_inputs, a.aim_cfgs = trk->aim_cfgs_on ? trk->aim_cfgs : nullptr;
+        a.attitudes = trk->attitudes, a.packet_errors = trk->packet_errors, a.stream_g2c = trk->stream_g2c_on ? trk->stream_g2c : nullptr;
+        a.has_aim = trk->aim_on, a.has_att = trk->att_on, a.has_camps = (trk->camps_on ? 1 : 0) | (trk->camps_on && trk->lower_bounds_on ? 2 : 0);
+        a.packets = trk->att_on ? static_cast<const uint8_t*>(loop->d_packets) : nullptr;
+        a.n_armours = b.n_armours, a.frame_status = b.status;
+        a.win_eff = g.win ? b.win_eff : nullptr;
+        a.key_eff = g.keys ? b.key_eff : nullptr;
+        a.cam_eff = b.cam_req && (stages & RMCV_STAGE_POSE) ? b.cam_eff : nullptr;
+        a.tcfg = tc, a.aim_cfg = trk->aim_cfg, a.att_cfg = trk->att_cfg, a.timestamp = timestamp;
+        HIPCHK(c, launch_loop_record(a, s), "k_loop_record");
+        if ((rc = recorder_loop_end(*loop, s))) return fail(c, rc, rmcv_recorder_last_error(loop->rec));
+    }
     HIPCHK(c, tracker_order_end(trk, s), "tracker: record the step");
     return order_end(c, s);
 }

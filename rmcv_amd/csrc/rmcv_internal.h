@@ -341,7 +341,9 @@ struct TrackerBufs {
 hipError_t launch_track(const rmcv_tracker_config& cfg, const TrackerBufs& tb, const Bufs& b, const Limits& lim, bool identity, bool pose,
                         const rmcv_point* win_eff, int64_t timestamp, hipStream_t s);
 // rmcv_batch_track with the stages given (a pipeline runs a batch's halves separately: the context's record of its last run is not the batch's)
-int ctx_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, int stages, hipStream_t s);
+// loop (nullable): the recorder's loop records of this batch (k_loop.hip) go behind the aim step, in front of the tracker's event
+struct LoopTicket;
+int ctx_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, int stages, hipStream_t s, const LoopTicket* loop = nullptr);
 // what the step reads of the tracker; the event is recorded behind every step enqueued
 const rmcv_tracker_config& tracker_config(const rmcv_tracker* t);
 const TrackerBufs& tracker_bufs(const rmcv_tracker* t);
@@ -413,15 +415,70 @@ struct RecordBatch {
     const FrameKey* key_eff;   // device; null: per-run keys
     const int32_t* key_enemy;  // device, with key_eff: the raw camps
     const rmcv_point* win_eff; // device; null: whole frames
+    const rmcv_tracker* trk;   // a tracked submit's tracker: with the recorder's track_cap > 0 the batch gets loop records; null: none
 };
 // why the recorder cannot take `n` chosen frames of this geometry (null: it can); nothing is enqueued
 const char* recorder_refusal(const rmcv_recorder* r, int device, int n, int w_bytes, int h);
 // pack frames[0 .. n) of the batch into the recorder's next slot on `s`: launches and event calls only, nothing blocks.  Frozen: nothing happens.
-int recorder_enqueue(rmcv_recorder* r, const RecordBatch& b, const int32_t* frames, int n, hipStream_t s);
+// loop (nullable): set to where the batch's loop records go (LoopTicket::rec null: the batch gets none)
+int recorder_enqueue(rmcv_recorder* r, const RecordBatch& b, const int32_t* frames, int n, hipStream_t s, LoopTicket* loop = nullptr);
 // the frames bound to a context as the recorder describes them: format, row bytes, lag, the effective key / origin tables (rmcv_host.hip)
 void ctx_record_batch(const rmcv_ctx* c, RecordBatch* b);
 // bytes of one pixel of the frames the context's options describe (what the next binding will record)
 int ctx_frame_pixel_bytes(const rmcv_ctx* c);
+
+// ---- the recorder's loop records (k_loop.hip, rmcv_record.hip) ----
+// the latch record as the device writes it, in device memory and in the mapped host copy; `set` last
+struct LoopLatch {
+    uint32_t fired;    // fired & mask of the record that took the latch
+    int32_t k, stream;
+    int32_t set;       // 1 once the fields above are written
+    uint64_t sequence;
+};
+// what a pipeline keeps of a recorded tracked batch between its submit (the slot is chosen there) and the call that enqueues its step
+struct LoopTicket {
+    rmcv_recorder* rec = nullptr; // null: the batch gets no loop records
+    int slot = 0;
+    uint64_t sequence = 0;
+    const void* d_packets = nullptr; // the batch's serial packets (device; nullable)
+};
+// one launch of k_loop_record: everything by value
+struct LoopArgs {
+    int n, rec_cap, n_streams, trk_cap; // chosen frames; the recorder's and the tracker's track_cap
+    PackIdx idx;                        // [n] the chosen frames = streams
+    uint8_t* out;                       // [n] areas, `pitch` apart
+    const uint8_t* prev;                // the previous slot's areas, or null: nothing is compared
+    int64_t pitch;
+    TrackerBufs tb;
+    const rmcv_aim* aims;               // null: aiming was never on
+    const rmcv_aim_input* aim_inputs;   // null: the defaults
+    const rmcv_aim_config* aim_cfgs;    // null: aim_cfg for every stream
+    const rmcv_attitude* attitudes;
+    const int32_t* packet_errors;
+    const double* stream_g2c;           // null: att_cfg's for every stream
+    const uint8_t* packets;             // null: none
+    const int32_t *n_armours, *frame_status; // the batch context's
+    const rmcv_point* win_eff;          // null: whole frames
+    const FrameKey* key_eff;            // null: per-run keys
+    const int32_t* cam_eff;             // null: no camera table in use
+    int has_aim, has_att, has_camps;
+    rmcv_tracker_config tcfg;
+    rmcv_aim_config aim_cfg;
+    rmcv_attitude_config att_cfg;
+    int64_t timestamp;
+    uint64_t sequence;
+    rmcv_trigger_config trig;           // (mask 0: nothing takes the latch)
+    uint32_t* latch_word;               // device; 0: free
+    LoopLatch *d_latch, *hd_latch;      // device memory; the mapped host copy's device address
+};
+hipError_t launch_loop_record(const LoopArgs& a, hipStream_t s);
+// fill in the recorder's part of `a` for the ticket's batch (areas, predecessor, trigger, latch), make `s` wait for what still uses the
+// slot's areas: event calls only.  trk: the tracker whose step this is.  RMCV_OK, or the recorder's error
+int recorder_loop_begin(const LoopTicket& t, const rmcv_tracker* trk, LoopArgs* a, hipStream_t s);
+// behind the launch: the slot's second event
+int recorder_loop_end(const LoopTicket& t, hipStream_t s);
+// why a pipeline of `depth` slots cannot take this recorder's armed triggers (null: it can)
+const char* recorder_trigger_refusal(const rmcv_recorder* r, int depth);
 
 // ---- the icon classifier's trainer (k_svm.hip) ----
 // int32 [n][n] of u8 [n][1200]

@@ -94,6 +94,7 @@ struct rmcv_pipeline {
         int sparse = 0;         // its stages behind the pixel stage
         hipStream_t B = nullptr;
         bool views = false;     // debug views are rendered behind its sparse stage
+        LoopTicket loop{};      // a recorded tracked batch: the recorder slot its loop records go into (chosen at the submit; the step runs a call later)
     } pend;
     rmcv_pipeline_hook hook = nullptr; // ... or the built-in gather hook
     void* hook_user = nullptr;
@@ -457,9 +458,9 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
     // armours, identities, poses and effective origins, so it comes BEFORE ev_done frees them; ctx_track records the tracker's event
     // behind it (the next tracked submit's k_window_origins waits for that), and wait / collect / drain of the ticket cover the step
     if (q.trk) {
-        rc = ctx_track(P.c, q.trk, q.timestamp, q.stages, T);
+        rc = ctx_track(P.c, q.trk, q.timestamp, q.stages, T, &P.loop);
         if (rc) return cfail(pl, P.c, rc);
-        pl->last_what = "k_track";
+        pl->last_what = P.loop.rec ? "k_loop_record" : "k_track";
     }
     // the context's buffers are free from here on: the next pixel kernel of this slot does not wait for the hook
     PCHK(pl, hipEventRecord(S.ev_done, T), "pipeline: mark the slot");
@@ -502,6 +503,7 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
     if (pl->recd.n) { // (with no recorder set: nothing here, and nothing further down)
         if (q.n_frames <= pl->recd.max_index) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch has fewer frames than the recorder's frame list names (rmcv_pipeline_set_recorder)");
         if (const char* no = recorder_refusal(pl->recd.rec, pl->device, pl->recd.n, q.w * ctx_frame_pixel_bytes(pl->ring[0]), q.h)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
+        if (const char* no = recorder_trigger_refusal(pl->recd.rec, pl->cfg.depth)) return pfail(pl, RMCV_ERR_BAD_ARG, no); // (armed since rmcv_pipeline_set_recorder)
     }
     hipSetDevice(pl->device);
     int rc = finish_back(pl, false); // the batch before this one: a pixel launch follows it
@@ -598,18 +600,21 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
     PCHK(pl, hipStreamWaitEvent(B, S.ev_bin, 0), "pipeline: chain the sparse stages");
     // the recorder: the chosen frames as delivered, and the effective keys and origins the pixel stage's prologue has just written, packed on
     // the batch's sparse stream in front of its sparse stage -- off the pixel stream, and in front of ev_done: a wait for the ticket covers it
+    LoopTicket loop{};
     if (pl->recd.n) {
         RecordBatch rb{};
         rb.d_frames = q.d_frames, rb.w = q.w, rb.h = q.h, rb.stride = q.stride, rb.pitch = q.frame_pitch, rb.batch_frames = q.n_frames;
         rb.stages = stages, rb.win_w = q.d_origins ? q.win_w : 0, rb.win_h = q.d_origins ? q.win_h : 0;
         rb.params = *q.p, rb.timestamp = q.timestamp, rb.ticket = t;
         ctx_record_batch(c, &rb);
-        if ((rc = recorder_enqueue(pl->recd.rec, rb, pl->recd.frames, pl->recd.n, B))) return pfail(pl, rc, rmcv_recorder_last_error(pl->recd.rec));
+        rb.trk = q.trk;
+        if ((rc = recorder_enqueue(pl->recd.rec, rb, pl->recd.frames, pl->recd.n, B, &loop))) return pfail(pl, rc, rmcv_recorder_last_error(pl->recd.rec));
+        loop.d_packets = q.d_packets;
         pl->last_what = "k_pack_emit";
     }
     pl->next_ticket = t + 1;
     if (ticket) *ticket = t;
-    pl->pend = {true, t, q, *q.p, lp ? *lp : rmcv_legacy_params{}, k, c, used, plan, sparse, B, pl->views.n > 0};
+    pl->pend = {true, t, q, *q.p, lp ? *lp : rmcv_legacy_params{}, k, c, used, plan, sparse, B, pl->views.n > 0, loop};
     pl->pend.req.p = &pl->pend.p; // (the caller's params live as long as its call)
     pl->pend.req.lp = lp ? &pl->pend.lp : nullptr;
     // (a hook or the gather hands the record to a consumer the pipeline does not see waiting: its batches are finished here and now)
@@ -831,6 +836,7 @@ int rmcv_pipeline_set_recorder(rmcv_pipeline* pl, rmcv_recorder* rec, const int3
     if (!frames) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_recorder: null frame list");
     // (the rows and the height are the batch's: checked at every submit)
     if (const char* no = recorder_refusal(rec, pl->device, n, 1, 1)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
+    if (const char* no = recorder_trigger_refusal(rec, pl->cfg.depth)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
     int top = 0;
     for (int k = 0; k < n; k++) {
         if (frames[k] < 0 || frames[k] >= pl->lim.max_frames) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_recorder: a frame index out of range");

@@ -5,6 +5,9 @@
 // slot = sequence mod slots, every chosen frame a fixed area of rmcv_pack_bound bytes (no allocator on the device), a small device table
 // of the packed sizes (and the batch's effective keys and window origins), and on the host the entry with everything known at the submit.
 // Recording is three launches and two event calls on the caller's stream; the readers wait for the slot's event with the 5 s deadline.
+// With track_cap > 0 a tracked batch of a pipeline also gets loop records (k_loop.hip): a second fixed area per chosen frame, written by
+// one launch behind the batch's tracker step -- on another stream and a pipeline call later than the packing, so the slot has a second
+// event and the readers wait for both -- and the trigger latch, whose mapped host copy recorder_enqueue reads with a plain load.
 #include <stdio.h>
 #include <string.h>
 
@@ -23,7 +26,14 @@ struct RecSlot {
     int32_t* d_camps = nullptr;      // [max_frames]
     rmcv_point* d_origins = nullptr; // [max_frames]
     hipEvent_t ev = nullptr;         // behind the slot's last packing
+    uint8_t* d_loop = nullptr;       // [max_frames] loop areas of `loop_bytes` bytes (track_cap > 0)
+    hipEvent_t ev_loop = nullptr;    // behind the slot's last k_loop_record
     bool used = false;
+    bool loop_on = false;            // the slot's batch has loop records ...
+    bool loop_pending = false;       // ... whose launch has not been enqueued yet (the pipeline's next call does)
+    bool loop_ever = false;          // ev_loop has been recorded
+    bool chained = false;            // the batch may be compared with the previous slot's (no resume in between)
+    const rmcv_tracker* trk = nullptr; // the tracker of the slot's batch (compared, never dereferenced)
     rmcv_record_entry e{};           // (sizes, keys, origins: filled by the readers)
     std::vector<uint8_t> user;
 };
@@ -35,6 +45,15 @@ struct rmcv_recorder {
     std::vector<RecSlot> slots;
     uint64_t seq = 0;                // batches recorded
     bool frozen = false;
+    int64_t loop_bytes = 0;          // loop_bound(track_cap); 0: no loop records
+    // the trigger latch (track_cap > 0): a device word taken by compare-and-swap, the latch record in device memory and in mapped host memory
+    uint32_t* d_latch_word = nullptr;
+    LoopLatch *d_latch = nullptr, *h_latch = nullptr, *hd_latch = nullptr;
+    rmcv_trigger_config trig{};      // mask 0: off
+    bool noticed = false;            // a recorder_enqueue has seen the latch ...
+    int remaining = 0;               // ... and this many batches are still recorded
+    int since = 0;                   // batches recorded since it was noticed
+    bool rechain = true;             // the next batch has no predecessor (the first one; the first after a resume)
     std::vector<uint8_t> user;       // the blob of the next batch
     int wait_timeout_ms = 5000;
     char err[256] = {0};
@@ -67,6 +86,12 @@ static RecSlot* held_slot(rmcv_recorder* r, int i, int* rc)
     const int rcw = wait_event_deadline(S.ev, r->wait_timeout_ms, &e);
     if (rcw < 0) { *rc = rfail(r, RMCV_ERR_HIP, "recorder: wait for the packing", e); return nullptr; }
     if (rcw > 0) { *rc = rfail(r, RMCV_ERR_TIMEOUT, "recorder: the packing has not finished after 5000 ms"); return nullptr; }
+    if (S.loop_on) { // the loop records: a launch of the pipeline call AFTER the batch's submit, on the stream of its tracker step
+        if (S.loop_pending) { *rc = rfail(r, RMCV_ERR_BAD_ARG, "recorder: the newest batch's tracker step has not been enqueued yet (rmcv_pipeline_wait its ticket, or drain, first)"); return nullptr; }
+        const int rcl = wait_event_deadline(S.ev_loop, r->wait_timeout_ms, &e);
+        if (rcl < 0) { *rc = rfail(r, RMCV_ERR_HIP, "recorder: wait for the loop records", e); return nullptr; }
+        if (rcl > 0) { *rc = rfail(r, RMCV_ERR_TIMEOUT, "recorder: the loop records have not finished after 5000 ms"); return nullptr; }
+    }
     return &S;
 }
 // the device's part of a slot's entry
@@ -95,8 +120,26 @@ const char* recorder_refusal(const rmcv_recorder* r, int device, int n, int w_by
     return nullptr;
 }
 
-int recorder_enqueue(rmcv_recorder* r, const RecordBatch& b, const int32_t* frames, int n, hipStream_t s)
+const char* recorder_trigger_refusal(const rmcv_recorder* r, int depth)
 {
+    if (!r || !r->trig.mask) return nullptr;
+    return r->cfg.slots < loop_ring_bound(depth, r->trig.post_batches)
+               ? "the recorder's triggers are armed and its ring is smaller than the pipeline's depth + post_batches: the triggering batch could be overwritten before the recorder freezes (rmcv_recorder_set_trigger)"
+               : nullptr;
+}
+
+int recorder_enqueue(rmcv_recorder* r, const RecordBatch& b, const int32_t* frames, int n, hipStream_t s, LoopTicket* loop)
+{
+    if (loop) *loop = LoopTicket{};
+    // the trigger latch: a plain load of the mapped host copy.  Once seen, post_batches more batches are recorded, this one the first
+    if (r->trig.mask && !r->frozen && !r->noticed && r->h_latch && *(volatile int32_t*)&r->h_latch->set) {
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        r->noticed = true, r->remaining = r->trig.post_batches, r->since = 0;
+    }
+    if (r->noticed && !r->frozen) {
+        if (r->remaining == 0) r->frozen = true;
+        else r->remaining--, r->since++;
+    }
     if (r->frozen) return RMCV_OK;
     const int w_bytes = b.w_bytes, lag = b.lag;
     RecSlot& S = r->slots[(size_t)(r->seq % (uint64_t)r->cfg.slots)];
@@ -126,7 +169,53 @@ int recorder_enqueue(rmcv_recorder* r, const RecordBatch& b, const int32_t* fram
     for (int k = 0; k < n; k++) E.frames[k] = frames[k];
     S.user = r->user;
     S.used = true;
+    S.loop_on = S.loop_pending = b.trk && r->loop_bytes;
+    S.trk = b.trk;
+    S.chained = !r->rechain;
+    r->rechain = false;
+    if (S.loop_on) {
+        E.loop_bytes = (int32_t)r->loop_bytes;
+        if (loop) loop->rec = r, loop->slot = (int)(r->seq % (uint64_t)r->cfg.slots), loop->sequence = r->seq;
+    }
     r->seq++;
+    return RMCV_OK;
+}
+
+int recorder_loop_begin(const LoopTicket& t, const rmcv_tracker* trk, LoopArgs* a, hipStream_t s)
+{
+    rmcv_recorder* r = t.rec;
+    const int slots = r->cfg.slots;
+    RecSlot& S = r->slots[(size_t)t.slot];
+    if (!S.used || S.e.sequence != t.sequence || !S.loop_on) return rfail(r, RMCV_ERR_BAD_ARG, "recorder: the batch's slot has been reused before its tracker step was enqueued");
+    const rmcv_record_entry& E = S.e;
+    a->n = E.n_frames, a->rec_cap = r->cfg.track_cap;
+    for (int k = 0; k < E.n_frames; k++) a->idx.f[k] = E.frames[k];
+    a->out = S.d_loop, a->pitch = r->loop_bytes, a->prev = nullptr, a->sequence = t.sequence;
+    // the predecessor: the previous slot, when it holds the immediately preceding sequence of the same tracker with the same chosen frames,
+    // recorded with loop records, and no resume lies between
+    const RecSlot& P = r->slots[(size_t)((t.slot + slots - 1) % slots)];
+    if (slots >= 2 && S.chained && t.sequence > 0 && P.used && P.e.sequence + 1 == t.sequence && P.loop_on && !P.loop_pending && P.trk == trk &&
+        P.e.n_frames == E.n_frames && memcmp(P.e.frames, E.frames, (size_t)E.n_frames * 4) == 0)
+        a->prev = P.d_loop;
+    a->trig = r->trig;
+    a->latch_word = r->d_latch_word, a->d_latch = r->d_latch, a->hd_latch = r->hd_latch;
+    // the areas are rewritten: the launch that wrote them last, and the one that read them as ITS predecessor (the next slot's), may have run
+    // on other streams
+    const RecSlot& N = r->slots[(size_t)((t.slot + 1) % slots)];
+    hipError_t e = S.loop_ever ? hipStreamWaitEvent(s, S.ev_loop, 0) : hipSuccess;
+    if (e == hipSuccess && &N != &S && N.loop_ever) e = hipStreamWaitEvent(s, N.ev_loop, 0);
+    if (e != hipSuccess) return rfail(r, RMCV_ERR_HIP, "recorder: wait for the slot's loop records", e);
+    return RMCV_OK;
+}
+
+int recorder_loop_end(const LoopTicket& t, hipStream_t s)
+{
+    rmcv_recorder* r = t.rec;
+    RecSlot& S = r->slots[(size_t)t.slot];
+    const hipError_t e = hipEventRecord(S.ev_loop, s);
+    if (e != hipSuccess) return rfail(r, RMCV_ERR_HIP, "recorder: k_loop_record", e);
+    S.loop_ever = true;
+    S.loop_pending = false;
     return RMCV_OK;
 }
 
@@ -147,15 +236,18 @@ void rmcv_recorder_destroy(rmcv_recorder* r)
     hipSetDevice(r->device);
     for (auto& S : r->slots) { // with the deadline: a packing that does not finish is not waited for without one
         hipError_t e = hipSuccess;
-        if (S.used && wait_event_deadline(S.ev, r->wait_timeout_ms, &e) > 0) {
+        if ((S.used && wait_event_deadline(S.ev, r->wait_timeout_ms, &e) > 0) || (S.loop_ever && wait_event_deadline(S.ev_loop, r->wait_timeout_ms, &e) > 0)) {
             fprintf(stderr, "rmcv_recorder_destroy: a packing has not finished; the recorder's buffers are leaked\n");
             return;
         }
     }
     for (auto& S : r->slots) {
-        for (void* p : {(void*)S.d_area, (void*)S.d_sizes, (void*)S.d_keys, (void*)S.d_camps, (void*)S.d_origins}) if (p) (void)hipFree(p);
+        for (void* p : {(void*)S.d_area, (void*)S.d_sizes, (void*)S.d_keys, (void*)S.d_camps, (void*)S.d_origins, (void*)S.d_loop}) if (p) (void)hipFree(p);
         if (S.ev) (void)hipEventDestroy(S.ev);
+        if (S.ev_loop) (void)hipEventDestroy(S.ev_loop);
     }
+    for (void* p : {(void*)r->d_latch_word, (void*)r->d_latch}) if (p) (void)hipFree(p);
+    if (r->h_latch) (void)hipHostFree(r->h_latch);
     (void)hipGetLastError();
     delete r;
 }
@@ -172,14 +264,17 @@ int rmcv_recorder_create(int device, const rmcv_recorder_config* cfg, rmcv_recor
         if (cfg->max_w_bytes) c.max_w_bytes = cfg->max_w_bytes;
         if (cfg->max_h) c.max_h = cfg->max_h;
         if (cfg->user_bytes) c.user_bytes = cfg->user_bytes;
+        c.track_cap = cfg->track_cap; // (0: no loop records -- nothing below is allocated, nothing further is ever launched)
     }
     if (c.slots < 1 || c.slots > 4096 || c.max_frames < 1 || c.max_frames > RMCV_RECORDER_MAX_FRAMES || c.user_bytes < 0 || c.user_bytes > (1 << 20) ||
-        !pack_geometry_ok(c.max_w_bytes, c.max_h, 1))
+        !pack_geometry_ok(c.max_w_bytes, c.max_h, 1) || c.track_cap < 0 || c.track_cap > RMCV_TRACKER_MAX_CAP)
         return RMCV_ERR_BAD_ARG;
     if (hipSetDevice(device) != hipSuccess) { (void)hipGetLastError(); return RMCV_ERR_NO_DEVICE; }
     rmcv_recorder* r = new (std::nothrow) rmcv_recorder();
     if (!r) return RMCV_ERR_NOMEM;
     r->device = device, r->cfg = c, r->area = pack_bound(c.max_w_bytes, c.max_h);
+    r->loop_bytes = c.track_cap ? loop_bound(c.track_cap) : 0;
+    r->trig.aim_jump_deg = __builtin_inf(); // (triggers off: the records' fired is the rule with no jump bound and no status bits)
     r->slots.resize((size_t)c.slots);
     hipError_t e = hipSuccess;
     const size_t n = (size_t)c.max_frames;
@@ -190,6 +285,17 @@ int rmcv_recorder_create(int device, const rmcv_recorder_config* cfg, rmcv_recor
         if (e == hipSuccess) e = hipMalloc((void**)&S.d_camps, n * 4);
         if (e == hipSuccess) e = hipMalloc((void**)&S.d_origins, n * sizeof(rmcv_point));
         if (e == hipSuccess) e = hipEventCreateWithFlags(&S.ev, hipEventDisableTiming);
+        if (e == hipSuccess && r->loop_bytes) e = hipMalloc((void**)&S.d_loop, n * (size_t)r->loop_bytes);
+        if (e == hipSuccess && r->loop_bytes) e = hipEventCreateWithFlags(&S.ev_loop, hipEventDisableTiming);
+    }
+    if (r->loop_bytes) { // the latch: free
+        if (e == hipSuccess) e = hipMalloc((void**)&r->d_latch_word, sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMalloc((void**)&r->d_latch, sizeof(LoopLatch));
+        if (e == hipSuccess) e = hipHostMalloc((void**)&r->h_latch, sizeof(LoopLatch), hipHostMallocMapped);
+        if (e == hipSuccess) memset(r->h_latch, 0, sizeof(LoopLatch));
+        if (e == hipSuccess) e = hipHostGetDevicePointer((void**)&r->hd_latch, r->h_latch, 0);
+        if (e == hipSuccess) e = hipMemset(r->d_latch_word, 0, sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(r->d_latch, 0, sizeof(LoopLatch));
     }
     if (e != hipSuccess) {
         (void)hipGetLastError();
@@ -234,7 +340,77 @@ int rmcv_recorder_record(rmcv_recorder* r, const void* d_frames, int w_bytes, in
 }
 
 int rmcv_recorder_freeze(rmcv_recorder* r) { if (!r) return RMCV_ERR_BAD_ARG; r->frozen = true; return RMCV_OK; }
-int rmcv_recorder_resume(rmcv_recorder* r) { if (!r) return RMCV_ERR_BAD_ARG; r->frozen = false; return RMCV_OK; }
+int rmcv_recorder_resume(rmcv_recorder* r)
+{
+    if (!r) return RMCV_ERR_BAD_ARG;
+    if (r->loop_bytes) { // clear the latch and re-arm it: behind every launch of the recorder's that is in flight (this call may block; no submit does)
+        hipSetDevice(r->device);
+        for (auto& S : r->slots) {
+            hipError_t e = hipSuccess;
+            const int rcw = S.loop_ever ? wait_event_deadline(S.ev_loop, r->wait_timeout_ms, &e) : 0;
+            if (rcw < 0) return rfail(r, RMCV_ERR_HIP, "rmcv_recorder_resume: wait for the loop records", e);
+            if (rcw > 0) return rfail(r, RMCV_ERR_TIMEOUT, "rmcv_recorder_resume: the loop records have not finished after 5000 ms");
+        }
+        hipError_t e = hipMemset(r->d_latch_word, 0, sizeof(uint32_t));
+        if (e == hipSuccess) e = hipMemset(r->d_latch, 0, sizeof(LoopLatch));
+        if (e == hipSuccess) e = hipStreamSynchronize(nullptr);
+        if (e != hipSuccess) return rfail(r, RMCV_ERR_HIP, "rmcv_recorder_resume: clearing the latch", e);
+        memset(r->h_latch, 0, sizeof(LoopLatch));
+        r->noticed = false, r->remaining = 0, r->since = 0;
+    }
+    r->rechain = true; // (the first batch behind a resume has no predecessor)
+    r->frozen = false;
+    return RMCV_OK;
+}
+
+int rmcv_recorder_set_trigger(rmcv_recorder* r, const rmcv_trigger_config* cfg)
+{
+    if (!r) return RMCV_ERR_BAD_ARG;
+    if (!cfg) { r->trig = rmcv_trigger_config{}; r->trig.aim_jump_deg = __builtin_inf(); return RMCV_OK; }
+    if (const char* no = loop_trigger_refusal(cfg)) return rfail(r, RMCV_ERR_BAD_ARG, no);
+    if (cfg->mask && !r->loop_bytes) return rfail(r, RMCV_ERR_BAD_ARG, "rmcv_recorder_set_trigger: a mask on a recorder without loop records (track_cap == 0)");
+    r->trig = *cfg;
+    r->trig.reserved = 0;
+    return RMCV_OK;
+}
+
+int rmcv_recorder_trigger(rmcv_recorder* r, rmcv_trigger_info* info)
+{
+    if (!r || !info) return RMCV_ERR_BAD_ARG;
+    memset(info, 0, sizeof(*info));
+    if (r->h_latch && *(volatile int32_t*)&r->h_latch->set) {
+        __atomic_thread_fence(__ATOMIC_ACQUIRE);
+        info->fired = 1, info->mask = r->h_latch->fired, info->sequence = r->h_latch->sequence, info->k = r->h_latch->k, info->stream = r->h_latch->stream;
+    }
+    info->noticed = r->noticed, info->batches_since = r->since;
+    return RMCV_OK;
+}
+
+int rmcv_recorder_loop(rmcv_recorder* r, int i, int k, void* out, int64_t cap, int64_t* size)
+{
+    if (!r || cap < 0 || (cap > 0 && !out)) return RMCV_ERR_BAD_ARG;
+    int rc = RMCV_OK;
+    RecSlot* S = held_slot(r, i, &rc);
+    if (!S) return rc;
+    if (k < 0 || k >= S->e.n_frames) return rfail(r, RMCV_ERR_BAD_ARG, "no such frame in the recorded batch");
+    if (!S->loop_on) return rfail(r, RMCV_ERR_BAD_ARG, "the recorded batch has no loop records (an untracked submit, or track_cap == 0)");
+    if (size) *size = r->loop_bytes;
+    if (r->loop_bytes > cap) return rfail(r, RMCV_ERR_CAPACITY, "output capacity exceeded");
+    // the fixed part first: it says how many tracks the area holds; the tail behind them is zero for every reader
+    uint8_t* o = static_cast<uint8_t*>(out);
+    const uint8_t* d = S->d_loop + (int64_t)k * r->loop_bytes;
+    hipError_t e = hipMemcpy(o, d, sizeof(rmcv_loop_state), hipMemcpyDeviceToHost);
+    rmcv_loop_state st;
+    if (e == hipSuccess) {
+        memcpy(&st, o, sizeof(st));
+        if (!loop_counts_ok(&st, r->loop_bytes)) return rfail(r, RMCV_ERR_HIP, "recorder: a loop record's counts beyond its area");
+        const int64_t live = loop_bound(st.n_tracks);
+        if (live > (int64_t)sizeof(st)) e = hipMemcpy(o + sizeof(st), d + sizeof(st), (size_t)(live - (int64_t)sizeof(st)), hipMemcpyDeviceToHost);
+        memset(o + live, 0, (size_t)(r->loop_bytes - live));
+    }
+    if (e != hipSuccess) return rfail(r, RMCV_ERR_HIP, "recorder: D2H loop record", e);
+    return RMCV_OK;
+}
 
 int rmcv_recorder_count(rmcv_recorder* r, int32_t* n)
 {
@@ -306,7 +482,13 @@ int rmcv_recorder_save(rmcv_recorder* r, const char* path)
             rc = rmcv_recorder_frame(r, i, k, bufs[(size_t)k].data(), e.sizes[k], nullptr);
             ptrs[k] = bufs[(size_t)k].data();
         }
-        if (rc == RMCV_OK && (rc = session_write_record(f, e, S.user.data(), ptrs))) rfail(r, rc, "rmcv_recorder_save: write failed");
+        std::vector<uint8_t> loops((size_t)e.n_frames * (size_t)e.loop_bytes);
+        const uint8_t* lptrs[RMCV_RECORDER_MAX_FRAMES] = {nullptr};
+        for (int k = 0; k < e.n_frames && e.loop_bytes && rc == RMCV_OK; k++) {
+            lptrs[k] = loops.data() + (size_t)k * (size_t)e.loop_bytes;
+            rc = rmcv_recorder_loop(r, i, k, loops.data() + (size_t)k * (size_t)e.loop_bytes, e.loop_bytes, nullptr);
+        }
+        if (rc == RMCV_OK && (rc = session_write_record(f, e, S.user.data(), ptrs, e.loop_bytes ? lptrs : nullptr))) rfail(r, rc, "rmcv_recorder_save: write failed");
     }
     if (fclose(f) != 0 && rc == RMCV_OK) rc = rfail(r, RMCV_ERR_BAD_ARG, "rmcv_recorder_save: write failed");
     return rc;
@@ -314,7 +496,14 @@ int rmcv_recorder_save(rmcv_recorder* r, const char* path)
 
 int rmcv_session_append(const char* path, const rmcv_record_entry* entry, const void* user, const uint8_t* const* packed)
 {
+    return rmcv_session_append_loop(path, entry, user, packed, nullptr);
+}
+
+int rmcv_session_append_loop(const char* path, const rmcv_record_entry* entry, const void* user, const uint8_t* const* packed,
+                             const uint8_t* const* loops)
+{
     if (!path || !entry) return RMCV_ERR_BAD_ARG;
+    if ((entry->loop_bytes != 0) != (loops != nullptr)) return RMCV_ERR_BAD_ARG; // (before a file is created)
     FILE* f = fopen(path, "r+b");
     int rc = RMCV_OK;
     if (f) { // an existing file must be a session of this version
@@ -327,7 +516,7 @@ int rmcv_session_append(const char* path, const rmcv_record_entry* entry, const 
         if (!f) return RMCV_ERR_BAD_ARG;
         rc = session_write_header(f);
     }
-    if (rc == RMCV_OK) rc = session_write_record(f, *entry, user, packed);
+    if (rc == RMCV_OK) rc = session_write_record(f, *entry, user, packed, loops);
     if (fclose(f) != 0 && rc == RMCV_OK) rc = RMCV_ERR_BAD_ARG;
     return rc;
 }
@@ -378,6 +567,18 @@ int rmcv_session_frame(const rmcv_session* s, int i, int k, void* out, int64_t c
     if (size) *size = e.sizes[k];
     if (e.sizes[k] > cap) return RMCV_ERR_CAPACITY;
     memcpy(out, s->data.data() + s->recs[(size_t)i].frame[k], (size_t)e.sizes[k]);
+    return RMCV_OK;
+}
+
+int rmcv_session_loop(const rmcv_session* s, int i, int k, void* out, int64_t cap, int64_t* size)
+{
+    if (!s || i < 0 || (size_t)i >= s->recs.size() || cap < 0 || (cap > 0 && !out)) return RMCV_ERR_BAD_ARG;
+    rmcv_record_entry e;
+    memcpy(&e, s->data.data() + s->recs[(size_t)i].entry, sizeof(e));
+    if (k < 0 || k >= e.n_frames || !e.loop_bytes) return RMCV_ERR_BAD_ARG;
+    if (size) *size = e.loop_bytes;
+    if (e.loop_bytes > cap) return RMCV_ERR_CAPACITY;
+    memcpy(out, s->data.data() + s->recs[(size_t)i].loop + (int64_t)k * e.loop_bytes, (size_t)e.loop_bytes);
     return RMCV_OK;
 }
 

@@ -299,6 +299,13 @@ class Tracker:
         assert side is None or len(side) == len(tr)
         self._chk(self._lib.rmcv_tracker_put(self._h, int(stream), ptr(tr) if len(tr) else None, len(tr), ptr(side) if side is not None and len(tr) else None))
 
+    def restore(self, stream, loop_record):
+        """one stream back to what a recorder's loop record holds (rmcv_tracker_restore): list, side records, count, status, requested
+        origin, camp and lower bound, aim record and input, attitude.  loop_record: a LoopRecord or its bytes.  Refused: a truncated record,
+        an aim or attitude part on a tracker whose aiming / attitude is off.  Synchronous."""
+        raw = np.ascontiguousarray(loop_record.raw if hasattr(loop_record, "raw") else np.frombuffer(bytes(loop_record), np.uint8))
+        self._chk(self._lib.rmcv_tracker_restore(self._h, int(stream), ptr(raw)))
+
     @staticmethod
     def aim_host(config, tick_frequency, tracks, now, aim_input=None):
         """rmcv_aim_step_host: one stream's aim step on the CPU (the kernel's source).  tracks TRACK[n], aim_input a (world2camera,
