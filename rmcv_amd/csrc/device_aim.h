@@ -260,4 +260,11 @@ PM_FN const char* aim_check_config(const rmcv_aim_config* c)
     return (const char*)0;
 }
 
+/* the default input of a stream: world2camera the identity, motor_angle 0 (17 doubles: the struct has no padding) */
+PM_FN void aim_default_input(rmcv_aim_input* in)
+{
+    for (int i = 0; i < 16; i++) in->world2camera[i] = (i % 5 == 0) ? 1.0 : 0.0;
+    in->motor_angle = 0.0;
+}
+
 #endif /* RMCV_DEVICE_AIM_H */

@@ -6,8 +6,10 @@
  *   rm::utils::GetROI + the window's origin    /root/reference/src/core.cpp:218-263
  * The arithmetic is that of oracle/rmcv_oracle_track.c, operation for operation (sequential k-sums, one-sided Jacobi SVD with at
  * most 30 sweeps, SVBkSb, the general sums: nothing is made of H = I or of the diagonal noise matrices) with ONE difference: the
- * Jacobi rotation's hypot is pm_hypot (pinned_math.h, correctly rounded) -- a libm's is neither portable to the GPU nor the same
- * from one machine to the next.  Compile with -ffp-contract=off, no fast-math.
+ * Jacobi rotation's hypot is TRK_HYPOT, by default pm_hypot (pinned_math.h, correctly rounded) -- a libm's is neither portable to the
+ * GPU nor the same from one machine to the next.  That default is the device tracker's (k_track.hip, rmcv_tracker_step_host).  The
+ * host-side rmcv_track_* functions (rmcv_track.hip) run this same filter with TRK_HYPOT defined as libm's hypot, as the oracle they are
+ * compared with does: the macro is the only thing that differs between the two forms.  Compile with -ffp-contract=off, no fast-math.
  *
  * Execution model.  A step of a stream is  trk_plan  (one lane: the association, on indices only -- the matching depends on bounding
  * boxes that update() never touches and on the lost counts, so the pass can be walked before anything is changed: that walk IS the
@@ -46,6 +48,10 @@
 #endif
 #define TRK_ONE
 #define TRK_SYNC() do { } while (0)
+#endif
+
+#ifndef TRK_HYPOT
+#define TRK_HYPOT pm_hypot /* the Jacobi rotation's hypot (see the head of this file) */
 #endif
 
 #define TRK_MAX_CAP 64                   /* rmcv_tracker_config::track_cap at most */
@@ -253,7 +259,7 @@ PM_FN void trk_jacobi_svd(trk_ws* ws, int lane)
                 for (int k = 0; k < 6; k++) p += At[i * 6 + k] * At[j * 6 + k];
                 if (__builtin_fabs(p) <= eps * __builtin_sqrt(a * b)) continue;
                 p *= 2;
-                const double beta = a - b, gamma = pm_hypot(p, beta);
+                const double beta = a - b, gamma = TRK_HYPOT(p, beta);
                 double c, s;
                 if (beta < 0) {
                     const double delta = (gamma - beta) * 0.5;

@@ -2,18 +2,15 @@
 // target chosen, led with the filter's velocity over latency and flight time, and the reference's gimbal-error-angle solution on it.
 //   rm::DeltaHeight / Distance / ProjectileAngle   src/mobility.cpp:36-82
 //   rm::SolveGEA                                   src/mobility.cpp:127-164
-// The step itself is device_aim.h, the same source rmcv_aim_step_host and the four host functions run on the CPU.
+// The step itself is device_aim.h, the same source rmcv_aim_step_host and the four host functions run on the CPU.  The tracker's aim
+// tables, their setters and getters and rmcv_tracker_aim: rmcv_tracker.hip; the launcher takes the view of them (tracker_plan.h).
 //
 // Mapping (gfx950, wave64).  A few hundred wavefronts of latency-bound scalar fp64: ONE 64-LANE WORKGROUP PER STREAM, lane = track
 // (track_cap <= 64).  A lane loads the dozen fields it needs from its rmcv_track (the 2.5 KB record is not staged), runs its dependent chain
 // on its own, the pick is a butterfly of __shfl_xor over a (key, index) pair and the lane that won stores the 72-byte record with ordinary
 // vector stores.  No LDS, no atomics, no waits between workgroups; nothing is indexed dynamically in registers (no scratch).
 #include <math.h>
-#include <stdio.h>
 #include <string.h>
-
-#include <algorithm>
-#include <vector>
 
 #include "rmcv_internal.h"
 #include "device_aim.h"
@@ -35,56 +32,16 @@ __global__ __launch_bounds__(64) void k_aim(rmcv_aim_config cfg, double tick_fre
     aim_stream(&cfg, tick_frequency, cur, nt, &inputs[f], now, &aims[f], lane);
 }
 
-bool tracker_aim_on(const rmcv_tracker* t) { return t->aim_on; }
-
-hipError_t launch_aim(const rmcv_tracker* t, int64_t now, hipStream_t s)
+// v: the tracker's (tracker_plan.h); its aim tables are there while aiming is on
+hipError_t launch_aim(const TrackerView& v, int64_t now, hipStream_t s)
 {
-    return launch(k_aim, dim3(t->cfg.n_streams), dim3(64), 0, s, t->aim_cfg, t->cfg.tick_frequency, t->b, t->cfg.n_streams, t->cfg.track_cap,
-                  (const rmcv_aim_input*)t->aim_inputs, now, t->aims, t->aim_cfgs_on ? t->aim_cfgs : nullptr);
+    return launch(k_aim, dim3(v.cfg.n_streams), dim3(64), 0, s, v.aim_cfg, v.cfg.tick_frequency, v.b, v.cfg.n_streams, v.cfg.track_cap,
+                  (const rmcv_aim_input*)v.aim_inputs, now, v.aims, v.aim_cfgs);
 }
 
 } // namespace rmcv
 
 using namespace rmcv;
-
-#define ACHK(t, call, what)                                                        \
-    do {                                                                           \
-        hipError_t e__ = (call);                                                   \
-        if (e__ != hipSuccess) return tracker_fail((t), RMCV_ERR_HIP, what, e__);  \
-    } while (0)
-
-static void default_input(rmcv_aim_input* in)
-{
-    memset(in, 0, sizeof(*in));
-    for (int i = 0; i < 4; i++) in->world2camera[i * 5] = 1.0;
-}
-
-// the records (zero until the first aim step) and the inputs (the defaults), on first use
-static int aim_alloc(rmcv_tracker* t)
-{
-    if (t->aims) return RMCV_OK;
-    const size_t n = (size_t)t->cfg.n_streams;
-    rmcv_aim* d_aims = nullptr;
-    rmcv_aim_input* d_in = nullptr;
-    hipError_t e = hipMalloc((void**)&d_aims, n * sizeof(rmcv_aim));
-    if (e == hipSuccess) {
-        t->allocs.push_back(d_aims);
-        e = hipMalloc((void**)&d_in, n * sizeof(rmcv_aim_input));
-    }
-    if (e == hipSuccess) {
-        t->allocs.push_back(d_in);
-        e = hipMemset(d_aims, 0, n * sizeof(rmcv_aim));
-    }
-    if (e == hipSuccess) {
-        std::vector<rmcv_aim_input> def(n);
-        for (auto& in : def) default_input(&in);
-        e = hipMemcpy(d_in, def.data(), n * sizeof(rmcv_aim_input), hipMemcpyHostToDevice);
-    }
-    if (e != hipSuccess) return tracker_fail(t, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the aim records", e);
-    t->aim_inputs = d_in;
-    t->aims = d_aims;
-    return RMCV_OK;
-}
 
 extern "C" {
 
@@ -134,144 +91,6 @@ void rmcv_default_aim_config(rmcv_aim_config* c)
     c->identity_mask = 0xFFFFFFFFu;
 }
 
-int rmcv_tracker_set_aim(rmcv_tracker* t, const rmcv_aim_config* cfg)
-{
-    if (!t) return RMCV_ERR_BAD_ARG;
-    if (cfg) { // (the refusals need no device)
-        const char* bad = aim_check_config(cfg);
-        if (bad) return tracker_fail(t, RMCV_ERR_BAD_ARG, bad);
-    }
-    hipSetDevice(t->device);
-    int rc = tracker_wait_done(t);
-    if (rc) return rc;
-    if (!cfg) {
-        t->aim_on = false;
-        return RMCV_OK;
-    }
-    if ((rc = aim_alloc(t))) return rc;
-    t->aim_cfg = *cfg;
-    t->aim_on = true;
-    return RMCV_OK;
-}
-
-int rmcv_tracker_set_aim_configs(rmcv_tracker* t, const rmcv_aim_config* cfgs)
-{
-    if (!t) return RMCV_ERR_BAD_ARG;
-    if (!t->aim_on) return tracker_fail(t, RMCV_ERR_BAD_ARG, "rmcv_tracker_set_aim_configs: aiming is off (rmcv_tracker_set_aim)");
-    const size_t n = (size_t)t->cfg.n_streams;
-    if (cfgs) { // (the refusals need no device)
-        for (size_t f = 0; f < n; f++) {
-            const char* bad = aim_check_config(&cfgs[f]);
-            if (bad) {
-                char msg[200];
-                snprintf(msg, sizeof(msg), "rmcv_tracker_set_aim_configs: stream %d: %s", (int)f, bad);
-                return tracker_fail(t, RMCV_ERR_BAD_ARG, msg);
-            }
-        }
-    }
-    hipSetDevice(t->device);
-    const int rc = tracker_wait_done(t);
-    if (rc) return rc;
-    if (!cfgs) {
-        t->aim_cfgs_on = false;
-        return RMCV_OK;
-    }
-    if (!t->aim_cfgs) {
-        rmcv_aim_config* d = nullptr;
-        const hipError_t e = hipMalloc((void**)&d, n * sizeof(rmcv_aim_config));
-        if (e != hipSuccess) return tracker_fail(t, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the streams' aim configs", e);
-        t->allocs.push_back(d);
-        t->aim_cfgs = d;
-    }
-    ACHK(t, hipMemcpy(t->aim_cfgs, cfgs, n * sizeof(rmcv_aim_config), hipMemcpyHostToDevice), "H2D aim configs");
-    t->aim_cfgs_on = true;
-    return RMCV_OK;
-}
-
-int rmcv_tracker_set_aim_inputs(rmcv_tracker* t, const rmcv_aim_input* inputs)
-{
-    if (!t) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(t->device);
-    int rc = tracker_wait_done(t);
-    if (rc) return rc;
-    if ((rc = aim_alloc(t))) return rc;
-    const size_t n = (size_t)t->cfg.n_streams;
-    std::vector<rmcv_aim_input> def;
-    if (!inputs) {
-        def.resize(n);
-        for (auto& in : def) default_input(&in);
-        inputs = def.data();
-    }
-    ACHK(t, hipMemcpy(t->aim_inputs, inputs, n * sizeof(rmcv_aim_input), hipMemcpyHostToDevice), "H2D aim inputs");
-    return RMCV_OK;
-}
-
-int rmcv_tracker_device_aim_inputs(rmcv_tracker* t, void** d_inputs)
-{
-    if (!t || !d_inputs) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(t->device);
-    const int rc = aim_alloc(t);
-    if (rc) return rc;
-    *d_inputs = t->aim_inputs;
-    return RMCV_OK;
-}
-
-int rmcv_tracker_device_aims(rmcv_tracker* t, void** d_aims)
-{
-    if (!t || !d_aims) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(t->device);
-    const int rc = aim_alloc(t);
-    if (rc) return rc;
-    *d_aims = t->aims;
-    return RMCV_OK;
-}
-
-int rmcv_tracker_aim(rmcv_tracker* t, int64_t now, void* hip_stream)
-{
-    if (!t) return RMCV_ERR_BAD_ARG;
-    if (!t->aim_on) return tracker_fail(t, RMCV_ERR_BAD_ARG, "rmcv_tracker_aim: aiming is off (rmcv_tracker_set_aim)");
-    hipSetDevice(t->device);
-    hipStream_t s = (hipStream_t)hip_stream;
-    ACHK(t, tracker_order_begin(t, s), "aim: wait for the tracker's previous step");
-    ACHK(t, launch_aim(t, now, s), "k_aim");
-    ACHK(t, tracker_order_end(t, s), "aim: record the step");
-    return RMCV_OK;
-}
-
-int rmcv_tracker_get_aims(rmcv_tracker* t, rmcv_aim* out, int cap)
-{
-    if (!t || cap < 0 || (cap > 0 && !out)) return RMCV_ERR_BAD_ARG;
-    hipSetDevice(t->device);
-    const int rc = tracker_wait_done(t);
-    if (rc) return rc;
-    const size_t n = (size_t)std::min(cap, t->cfg.n_streams);
-    if (!n) return RMCV_OK;
-    if (!t->aims) memset(out, 0, n * sizeof(rmcv_aim)); // (never aimed: what the records would hold)
-    else ACHK(t, hipMemcpy(out, t->aims, n * sizeof(rmcv_aim), hipMemcpyDeviceToHost), "D2H aims");
-    return RMCV_OK;
-}
-
-int rmcv_tracker_put(rmcv_tracker* t, int stream, const rmcv_track* tracks, int n, const float* last_vertices)
-{
-    if (!t) return RMCV_ERR_BAD_ARG;
-    if (stream < 0 || stream >= t->cfg.n_streams) return tracker_fail(t, RMCV_ERR_BAD_ARG, "no such stream");
-    if (n < 0 || (n > 0 && !tracks)) return tracker_fail(t, RMCV_ERR_BAD_ARG, "rmcv_tracker_put: bad list");
-    if (n > t->cfg.track_cap) return tracker_fail(t, RMCV_ERR_CAPACITY, "rmcv_tracker_put: more tracks than track_cap");
-    hipSetDevice(t->device);
-    const int rc = tracker_wait_done(t);
-    if (rc) return rc;
-    int32_t sel = 0, count = n;
-    ACHK(t, hipMemcpy(&sel, t->b.sel + stream, 4, hipMemcpyDeviceToHost), "D2H current list");
-    const size_t at = ((size_t)(sel & 1) * t->cfg.n_streams + stream) * t->cfg.track_cap;
-    if (n) {
-        ACHK(t, hipMemcpy(t->b.tracks + at, tracks, (size_t)n * sizeof(rmcv_track), hipMemcpyHostToDevice), "H2D tracks");
-        if (last_vertices) ACHK(t, hipMemcpy(t->b.side + at * 8, last_vertices, (size_t)n * 8 * sizeof(float), hipMemcpyHostToDevice), "H2D side records");
-        else ACHK(t, hipMemset(t->b.side + at * 8, 0, (size_t)n * 8 * sizeof(float)), "side records");
-    }
-    ACHK(t, hipMemcpy(t->b.n_tracking + stream, &count, 4, hipMemcpyHostToDevice), "H2D count");
-    return RMCV_OK;
-}
-
 int rmcv_aim_step_host(const rmcv_aim_config* cfg, double tick_frequency, const rmcv_track* tracks, int n, const rmcv_aim_input* input, int64_t now,
                        rmcv_aim* out)
 {
@@ -279,7 +98,7 @@ int rmcv_aim_step_host(const rmcv_aim_config* cfg, double tick_frequency, const 
     if (aim_check_config(cfg) || !std::isfinite(tick_frequency) || !(tick_frequency > 0)) return RMCV_ERR_BAD_ARG;
     rmcv_aim_input def;
     if (!input) {
-        default_input(&def);
+        aim_default_input(&def);
         input = &def;
     }
     aim_stream(cfg, tick_frequency, tracks, n, input, now, out, 0);

@@ -1,7 +1,7 @@
 // k_loop.hip -- the session recorder's loop records: the tracker, aim and attitude state of the recorded streams, captured
 // on the device behind a tracked batch's step, the trigger rule evaluated against the previous batch's record, and the latch that makes the
 // recorder freeze by itself.  The record's layout and the rule are device_loop.h, the same source the host readers and
-// rmcv_loop_trigger_host use.  Here too: rmcv_tracker_restore and the *_from_loop extractors, a replay's way back from a record.
+// rmcv_loop_trigger_host use.  Here too: the *_from_loop extractors, a replay's way back from a record (rmcv_tracker_restore: rmcv_tracker.hip).
 //
 // Mapping (gfx950, wave64).  ONE LAUNCH, one workgroup of 4 wavefronts per chosen frame; nothing here is heavy -- a record is under 1 KB
 // of scalars plus 2584 bytes a track -- so the shape is chosen for latency: every copy is 8-byte words, one word per lane and trip (a track
@@ -10,7 +10,6 @@
 // only its own stores.  No workgroup waits for another; every loop is bounded by the recorder's track_cap or a struct's size; nothing is
 // indexed dynamically in registers (no scratch).  The latch is ONE vector atomic compare-and-swap on a device word; the winner writes the
 // latch record with ordinary vector stores to device memory and to the mapped host copy, __threadfence_system(), then the `set` words.
-#include <stdio.h>
 #include <string.h>
 
 #include "rmcv_internal.h"
@@ -156,52 +155,6 @@ int rmcv_tracker_aim_config_from_loop(const void* rec, rmcv_aim_config* out, int
 int rmcv_tracker_attitude_config_from_loop(const void* rec, rmcv_attitude_config* out, double g2c[16], int32_t* has)
 {
     return loop_attitude_config(rec, out, g2c, has);
-}
-
-int rmcv_tracker_restore(rmcv_tracker* t, int stream, const void* rec)
-{
-    if (!t) return RMCV_ERR_BAD_ARG;
-    if (!rec) return tracker_fail(t, RMCV_ERR_BAD_ARG, "rmcv_tracker_restore: null record");
-    if (stream < 0 || stream >= t->cfg.n_streams) return tracker_fail(t, RMCV_ERR_BAD_ARG, "no such stream");
-    rmcv_loop_state s;
-    memcpy(&s, rec, sizeof(s));
-    if (s.flags & RMCV_LOOP_TRUNCATED) return tracker_fail(t, RMCV_ERR_BAD_ARG, "rmcv_tracker_restore: the record is truncated (RMCV_LOOP_TRUNCATED): it does not hold the stream's whole list");
-    if (!loop_tracks_ok(&s) || s.n_tracks != s.n_tracking) return tracker_fail(t, RMCV_ERR_BAD_ARG, "rmcv_tracker_restore: the record's counts are not a recorder's");
-    if (s.n_tracks > t->cfg.track_cap) return tracker_fail(t, RMCV_ERR_BAD_ARG, "rmcv_tracker_restore: more tracks than the tracker's track_cap");
-    if (s.has_aim && !t->aim_on) return tracker_fail(t, RMCV_ERR_BAD_ARG, "rmcv_tracker_restore: the record has an aim step and the tracker's aiming is off (rmcv_tracker_set_aim)");
-    if (s.has_attitude && !t->att_on) return tracker_fail(t, RMCV_ERR_BAD_ARG, "rmcv_tracker_restore: the record has an attitude and the tracker's attitude is off (rmcv_tracker_set_attitude)");
-    hipSetDevice(t->device);
-    const int rc = tracker_wait_done(t);
-    if (rc) return rc;
-    const uint8_t* base = static_cast<const uint8_t*>(rec);
-    int32_t sel = 0;
-    hipError_t e = hipMemcpy(&sel, t->b.sel + stream, 4, hipMemcpyDeviceToHost);
-    const size_t at = ((size_t)(sel & 1) * t->cfg.n_streams + stream) * t->cfg.track_cap;
-    for (int j = 0; j < s.n_tracks && e == hipSuccess; j++) {
-        e = hipMemcpy(t->b.tracks + at + j, base + loop_track_at(j), sizeof(rmcv_track), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = hipMemcpy(t->b.side + (at + j) * 8, base + loop_side_at(j), LOOP_SIDE_BYTES, hipMemcpyHostToDevice);
-    }
-    const auto put = [&e](void* dst, const void* src, size_t n) { if (e == hipSuccess) e = hipMemcpy(dst, src, n, hipMemcpyHostToDevice); };
-    put(t->b.n_tracking + stream, &s.n_tracking, 4);
-    put(t->b.status + stream, &s.status, 4);
-    put(t->b.origins + stream, &s.origin_next, sizeof(rmcv_point));
-    if (s.has_camps & 1) {
-        put(t->b.camps + stream, &s.camp, 4);
-        put(t->b.lower_bounds + stream, &s.lower_bound, 4);
-        t->camps_on = true;
-        t->lower_bounds_on = (s.has_camps & 2) != 0;
-    }
-    if (s.has_aim) { // (aiming on: the tables are there)
-        put(t->aims + stream, &s.aim, sizeof(rmcv_aim));
-        put(t->aim_inputs + stream, &s.aim_input, sizeof(rmcv_aim_input));
-    }
-    if (s.has_attitude) {
-        put(t->attitudes + stream, &s.attitude, sizeof(rmcv_attitude));
-        put(t->packet_errors + stream, &s.packet_errors, 4);
-        if (!s.has_aim) put(t->aim_inputs + stream, &s.aim_input, sizeof(rmcv_aim_input)); // (the attitude step's output; allocated with its tables)
-    }
-    if (e != hipSuccess) return tracker_fail(t, RMCV_ERR_HIP, "rmcv_tracker_restore: H2D", e);
-    return RMCV_OK;
 }
 
 } // extern "C"

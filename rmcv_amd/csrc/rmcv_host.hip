@@ -1146,51 +1146,49 @@ int rmcv_batch_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, void* hi
 } // extern "C"
 
 namespace rmcv {
+// the batch bound to `c` as step_refusal (tracker_plan.h) reads it
+static StepBatch step_batch(const rmcv_ctx* c)
+{
+    const Geom& g = c->geom;
+    return {c->device, g.n_frames, c->bufs.frames != nullptr, g.frame_w, g.frame_h, g.win, g.w, g.h};
+}
+
+// the tracker's and the batch context's part of a loop record's launch (the recorder's: recorder_loop_begin)
+static void loop_args_fill(LoopArgs& a, const TrackerView& v, const Geom& g, const Bufs& b, int stages, const void* d_packets, int64_t timestamp)
+{
+    a.n_streams = v.cfg.n_streams, a.trk_cap = v.cfg.track_cap, a.tb = v.b;
+    a.aims = v.aims, a.aim_inputs = v.aim_inputs, a.aim_cfgs = v.aim_cfgs;
+    a.attitudes = v.attitudes, a.packet_errors = v.packet_errors, a.stream_g2c = v.stream_g2c;
+    a.has_aim = v.has_aim, a.has_att = v.has_att, a.has_camps = v.has_camps;
+    a.packets = v.att_on ? static_cast<const uint8_t*>(d_packets) : nullptr; // (the batch's own, not a table of the tracker's: recorded where an attitude step read them)
+    a.n_armours = b.n_armours, a.frame_status = b.status;
+    a.win_eff = g.win ? b.win_eff : nullptr;
+    a.key_eff = g.keys ? b.key_eff : nullptr;
+    a.cam_eff = b.cam_req && (stages & RMCV_STAGE_POSE) ? b.cam_eff : nullptr;
+    a.tcfg = v.cfg, a.aim_cfg = v.aim_cfg, a.att_cfg = v.att_cfg, a.timestamp = timestamp;
+}
+
 // one step of the device tracker behind the context's last run (every check before the first enqueue); never synchronises
 int ctx_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, int stages, hipStream_t s, const LoopTicket* loop)
 {
     if (!c) return RMCV_ERR_BAD_ARG;
     if (!trk) return fail(c, RMCV_ERR_BAD_ARG, "null tracker");
     const Geom& g = c->geom;
-    const rmcv_tracker_config& tc = tracker_config(trk);
+    const TrackerView& v = tracker_view(trk);
     char msg[200];
-    if (tracker_device(trk) != c->device) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_track: the tracker lives on another device than the context");
-    if (g.n_frames <= 0 || !c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_track: no frames bound");
-    if (g.n_frames != tc.n_streams) {
-        snprintf(msg, sizeof(msg), "rmcv_batch_track: the batch has %d frames, the tracker %d streams (frame f is the next frame of stream f)", g.n_frames, tc.n_streams);
-        return fail(c, RMCV_ERR_BAD_ARG, msg);
-    }
-    if (g.frame_w != tc.frame_w || g.frame_h != tc.frame_h) {
-        snprintf(msg, sizeof(msg), "rmcv_batch_track: the frames are %d x %d, the tracker's config says %d x %d", g.frame_w, g.frame_h, tc.frame_w, tc.frame_h);
-        return fail(c, RMCV_ERR_BAD_ARG, msg);
-    }
-    if (!(stages & RMCV_STAGE_ARMOURS)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_track: the last run had no RMCV_STAGE_ARMOURS: nothing to track");
-    if (g.win && (g.w != tc.win_w || g.h != tc.win_h)) {
-        snprintf(msg, sizeof(msg), "rmcv_batch_track: the batch's windows are %d x %d, the tracker's config says %d x %d", g.w, g.h, tc.win_w, tc.win_h);
-        return fail(c, RMCV_ERR_BAD_ARG, msg);
-    }
+    if (const char* no = step_refusal("rmcv_batch_track", true, v, step_batch(c), stages, msg)) return fail(c, RMCV_ERR_BAD_ARG, no);
     int rc;
     if ((rc = order_begin(c, s))) return rc;
     HIPCHK(c, tracker_order_begin(trk, s), "tracker: wait for its previous step");
-    HIPCHK(c, launch_track(tc, tracker_bufs(trk), c->bufs, c->lim, (stages & RMCV_STAGE_IDENTITY) != 0, (stages & RMCV_STAGE_POSE) != 0,
+    HIPCHK(c, launch_track(v.cfg, v.b, c->bufs, c->lim, (stages & RMCV_STAGE_IDENTITY) != 0, (stages & RMCV_STAGE_POSE) != 0,
                            g.win ? c->bufs.win_eff : nullptr, timestamp, s), "k_track");
-    if (tracker_aim_on(trk)) HIPCHK(c, launch_aim(trk, timestamp, s), "k_aim"); // the aim step reads the lists the step has just left
+    if (v.aim_on) HIPCHK(c, launch_aim(v, timestamp, s), "k_aim"); // the aim step reads the lists the step has just left
     // the recorder's loop records: the state the two steps have just left, in front of the tracker's event -- the next batch's
     // attitude step, which rewrites attitudes and aim inputs, waits for that event
     if (loop && loop->rec) {
         LoopArgs a{};
         if ((rc = recorder_loop_begin(*loop, trk, &a, s))) return fail(c, rc, rmcv_recorder_last_error(loop->rec));
-        const Bufs& b = c->bufs;
-        a.n_streams = tc.n_streams, a.trk_cap = tc.track_cap, a.tb = tracker_bufs(trk);
-        a.aims = trk->aims, a.aim_inputs = trk->aim_inputs, a.aim_cfgs = trk->aim_cfgs_on ? trk->aim_cfgs : nullptr;
-        a.attitudes = trk->attitudes, a.packet_errors = trk->packet_errors, a.stream_g2c = trk->stream_g2c_on ? trk->stream_g2c : nullptr;
-        a.has_aim = trk->aim_on, a.has_att = trk->att_on, a.has_camps = (trk->camps_on ? 1 : 0) | (trk->camps_on && trk->lower_bounds_on ? 2 : 0);
-        a.packets = trk->att_on ? static_cast<const uint8_t*>(loop->d_packets) : nullptr;
-        a.n_armours = b.n_armours, a.frame_status = b.status;
-        a.win_eff = g.win ? b.win_eff : nullptr;
-        a.key_eff = g.keys ? b.key_eff : nullptr;
-        a.cam_eff = b.cam_req && (stages & RMCV_STAGE_POSE) ? b.cam_eff : nullptr;
-        a.tcfg = tc, a.aim_cfg = trk->aim_cfg, a.att_cfg = trk->att_cfg, a.timestamp = timestamp;
+        loop_args_fill(a, v, g, c->bufs, stages, loop->d_packets, timestamp);
         HIPCHK(c, launch_loop_record(a, s), "k_loop_record");
         if ((rc = recorder_loop_end(*loop, s))) return fail(c, rc, rmcv_recorder_last_error(loop->rec));
     }
@@ -1205,20 +1203,13 @@ int ctx_attitude(rmcv_ctx* c, rmcv_tracker* trk, const void* d_packets, hipStrea
 {
     if (!c) return RMCV_ERR_BAD_ARG;
     if (!trk) return fail(c, RMCV_ERR_BAD_ARG, "null tracker");
-    const Geom& g = c->geom;
-    const rmcv_tracker_config& tc = tracker_config(trk);
+    const TrackerView& v = tracker_view(trk);
     char msg[200];
-    if (tracker_device(trk) != c->device) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_attitude: the tracker lives on another device than the context");
-    if (!tracker_attitude_on(trk)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_attitude: attitude is off (rmcv_tracker_set_attitude)");
-    if (g.n_frames <= 0 || !c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_attitude: no frames bound");
-    if (g.n_frames != tc.n_streams) {
-        snprintf(msg, sizeof(msg), "rmcv_batch_attitude: the batch has %d frames, the tracker %d streams (frame f is the next frame of stream f)", g.n_frames, tc.n_streams);
-        return fail(c, RMCV_ERR_BAD_ARG, msg);
-    }
+    if (const char* no = step_refusal("rmcv_batch_attitude", false, v, step_batch(c), 0, msg)) return fail(c, RMCV_ERR_BAD_ARG, no);
     int rc;
     if ((rc = order_begin(c, s))) return rc;
     HIPCHK(c, tracker_order_begin(trk, s), "attitude: wait for the tracker's previous step");
-    HIPCHK(c, launch_attitude(trk, d_packets, c->bufs.pnp_cfg ? c->bufs.att_base2gripper : nullptr, s), "k_attitude");
+    HIPCHK(c, launch_attitude(v, d_packets, c->bufs.pnp_cfg ? c->bufs.att_base2gripper : nullptr, s), "k_attitude");
     if (c->bufs.pnp_cfg) c->bufs.pose_base2gripper = c->bufs.att_base2gripper;
     HIPCHK(c, tracker_order_end(trk, s), "attitude: record the step");
     return order_end(c, s);

@@ -1,6 +1,6 @@
 // rmcv_internal.h -- shared declarations of the HIP translation units (not part of the ABI): the device buffers, the kernel launchers of
-// the k_*.hip units, and what the units behind the ABI (rmcv_host, rmcv_stagewise, rmcv_frame, rmcv_pipeline, rmcv_track, rmcv_record,
-// rmcv_gather) need of each other.  Limits and Geom come from bind_plan.h.
+// the k_*.hip units, and what the units behind the ABI (rmcv_host, rmcv_stagewise, rmcv_frame, rmcv_pipeline, rmcv_track, rmcv_tracker,
+// rmcv_record, rmcv_gather) need of each other.  Limits and Geom come from bind_plan.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -15,6 +15,7 @@
 #include "pixel_plan.h"
 #include "sparse_plan.h"
 #include "svm_plan.h"
+#include "tracker_plan.h"
 
 namespace rmcv {
 
@@ -324,19 +325,8 @@ void ctx_set_frame_cameras(rmcv_ctx* c, const void* d_idx);
 PixelVariant ctx_pixel_variant(const rmcv_ctx* c);
 
 
-// ---- device-resident tracker (k_track.hip) ----
-// Device state of a tracker: two copies of every stream's list (a step reads the current one and writes the other; `sel` says which is
-// current, per stream -- a stream whose step is refused or sees no observation simply does not flip)
-struct TrackerBufs {
-    rmcv_track* tracks;  // [2][n_streams][track_cap]
-    float* side;         // [2][n_streams][track_cap][8]   frame-coordinate vertices of the observation that created / last matched the track
-    int32_t* sel;        // [n_streams] 0 / 1
-    int32_t* n_tracking; // [n_streams]
-    int32_t* status;     // [n_streams] RMCV_TRACKER_OVF
-    rmcv_point* origins; // [n_streams] the requested window origins (what Bufs::win_req borrows)
-    int32_t* camps;      // [n_streams] every stream's enemy colour and lower bound (rmcv_tracker_set_camps; what Bufs::key_camps / key_lbs borrow)
-    int32_t* lower_bounds;
-};
+// ---- device-resident tracker (k_track.hip, rmcv_tracker.hip) ----
+// (TrackerBufs, the device state of a tracker, and TrackerView, what is read of one outside rmcv_tracker.hip: tracker_plan.h)
 // one step for the n_streams frames of the batch in `b`; identity / pose: the run included those stages; win_eff: null without windows
 hipError_t launch_track(const rmcv_tracker_config& cfg, const TrackerBufs& tb, const Bufs& b, const Limits& lim, bool identity, bool pose,
                         const rmcv_point* win_eff, int64_t timestamp, hipStream_t s);
@@ -344,29 +334,22 @@ hipError_t launch_track(const rmcv_tracker_config& cfg, const TrackerBufs& tb, c
 // loop (nullable): the recorder's loop records of this batch (k_loop.hip) go behind the aim step, in front of the tracker's event
 struct LoopTicket;
 int ctx_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, int stages, hipStream_t s, const LoopTicket* loop = nullptr);
-// what the step reads of the tracker; the event is recorded behind every step enqueued
-const rmcv_tracker_config& tracker_config(const rmcv_tracker* t);
-const TrackerBufs& tracker_bufs(const rmcv_tracker* t);
-int tracker_device(const rmcv_tracker* t);
-// order a step on `s`: wait (on the GPU) for the tracker's last step if that ran on another stream; afterwards record it
+// what a caller outside rmcv_tracker.hip has of the object: the view of its state as it stands (tracker_plan.h: tracker_view_of; kept in the
+// tracker and refreshed by its setters: valid until the next rmcv_tracker_* call on it) ...
+const TrackerView& tracker_view(const rmcv_tracker* t);
+// ... and the order of a step on `s`: wait (on the GPU) for the tracker's last step if that ran on another stream -- a consumer of its
+// origins on another stream does the same --; afterwards record it
 hipError_t tracker_order_begin(rmcv_tracker* t, hipStream_t s);
 hipError_t tracker_order_end(rmcv_tracker* t, hipStream_t s);
-// make `s` wait for the tracker's last step (a consumer of its origins on another stream)
-hipError_t tracker_wait_on(rmcv_tracker* t, hipStream_t s);
-// the host's wait for the step in flight (5 s deadline) and the tracker's error record, for the aim entry points (k_aim.hip)
-int tracker_wait_done(rmcv_tracker* t);
-int tracker_fail(rmcv_tracker* t, int code, const char* what, hipError_t e = hipSuccess);
 
 // ---- device-resident aiming (k_aim.hip) ----
-// aiming on: the aim step of every stream right behind a tracker step (ctx_track), `now` = the step's timestamp
-bool tracker_aim_on(const rmcv_tracker* t);
-hipError_t launch_aim(const rmcv_tracker* t, int64_t now, hipStream_t s);
+// aiming on (TrackerView::aim_on): the aim step of every stream right behind a tracker step (ctx_track), `now` = the step's timestamp
+hipError_t launch_aim(const TrackerView& v, int64_t now, hipStream_t s);
 
 // ---- per-stream gimbal attitude (k_attitude.hip) ----
-// attitude on: the attitude step of every stream in front of a tracked batch, on its pixel stream
-bool tracker_attitude_on(const rmcv_tracker* t);
+// attitude on (TrackerView::att_on): the attitude step of every stream in front of a tracked batch, on its pixel stream
 // d_packets (nullable): n_streams x 24 bytes; d_base2gripper (nullable): the batch context's [n_streams][16]
-hipError_t launch_attitude(const rmcv_tracker* t, const void* d_packets, double* d_base2gripper, hipStream_t s);
+hipError_t launch_attitude(const TrackerView& v, const void* d_packets, double* d_base2gripper, hipStream_t s);
 // rmcv_batch_attitude on `s` (every check before the first enqueue; never synchronises): behind the tracker's previous step, recorded as its newest
 int ctx_attitude(rmcv_ctx* c, rmcv_tracker* trk, const void* d_packets, hipStream_t s);
 
@@ -490,31 +473,3 @@ hipError_t launch_svm_predict(const uint8_t* d_samples, int n, const float* d_we
                               int n_models, const int32_t* d_labels, int32_t* d_out, hipStream_t s);
 
 } // namespace rmcv
-
-// the tracker behind the ABI's handle (k_track.hip owns its lifetime; k_aim.hip the aim fields)
-struct rmcv_tracker {
-    int device = 0;
-    rmcv_tracker_config cfg{};
-    rmcv::TrackerBufs b{};
-    hipEvent_t ev_step = nullptr;  // recorded behind the step enqueued last
-    bool step_pending = false;
-    hipStream_t last_stream = nullptr;
-    char err[256] = {0};
-    std::vector<void*> allocs;
-    // aiming: off until rmcv_tracker_set_aim; the buffers are allocated on first use (and freed with `allocs`)
-    bool aim_on = false;
-    rmcv_aim_config aim_cfg{};
-    rmcv_aim_input* aim_inputs = nullptr; // [n_streams]
-    rmcv_aim* aims = nullptr;             // [n_streams]
-    rmcv_aim_config* aim_cfgs = nullptr;  // [n_streams] allocated by the first rmcv_tracker_set_aim_configs
-    bool aim_cfgs_on = false;             // k_aim reads stream f's own entry instead of aim_cfg
-    // per-stream detection keys: off until rmcv_tracker_set_camps
-    bool camps_on = false, lower_bounds_on = false;
-    // gimbal attitude: off until rmcv_tracker_set_attitude; the tables are allocated on first use (and freed with `allocs`)
-    bool att_on = false;
-    rmcv_attitude_config att_cfg{};
-    rmcv_attitude* attitudes = nullptr;   // [n_streams]
-    int32_t* packet_errors = nullptr;     // [n_streams]
-    double* stream_g2c = nullptr;         // [n_streams][16] allocated by the first rmcv_tracker_set_stream_cameras
-    bool stream_g2c_on = false;           // k_attitude takes stream f's own gripper2camera instead of att_cfg's
-};

@@ -492,10 +492,13 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
     const rmcv_legacy_params* lp = q.lp;
     const int stages = q.stages;
     if (!(stages & RMCV_STAGE_BINARY)) return pfail(pl, RMCV_ERR_BAD_ARG, "a pipelined batch starts at RMCV_STAGE_BINARY");
-    const bool attitude = q.trk && tracker_attitude_on(q.trk);
-    if (q.trk)
-        if (const char* no = tracked_refusal(tracker_device(q.trk), pl->device, tracker_config(q.trk), q.n_frames, q.w, q.h, stages, q.d_packets != nullptr, attitude))
+    bool attitude = false;
+    if (q.trk) {
+        const TrackerView& v = tracker_view(q.trk);
+        attitude = v.att_on;
+        if (const char* no = tracked_refusal(v.device, pl->device, v.cfg, q.n_frames, q.w, q.h, stages, q.d_packets != nullptr, attitude))
             return pfail(pl, RMCV_ERR_BAD_ARG, no);
+    }
     if (pl->views.n) { // (with no views set: nothing here, and nothing further down)
         if (q.n_frames <= pl->views.max_index) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch has fewer frames than the debug views name (rmcv_pipeline_set_views)");
         if ((stages & pl->views.need) != pl->views.need) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch's stages lack what the debug views' flags need (rmcv_pipeline_set_views)");
@@ -580,7 +583,7 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
     }
     // strict closed loop: the origins k_window_origins is about to read are those the tracker's last step wrote -- an event wait on the GPU
     // (that step was enqueued by the finish_back above, or earlier)
-    if (q.trk && q.d_origins && !attitude) PCHK(pl, tracker_wait_on(q.trk, A), "pipeline: wait for the tracker's last step");
+    if (q.trk && q.d_origins && !attitude) PCHK(pl, tracker_order_begin(q.trk, A), "pipeline: wait for the tracker's last step");
     // attitude on: the attitude step first -- it makes that wait itself, for whole-frame trackers too (the step in flight reads the aim inputs
     // this one writes), and the camps it may write are read by the k_frame_keys of the run below.  Everything it could refuse has been checked.
     if (attitude) {
@@ -691,14 +694,13 @@ int rmcv_pipeline_submit_tracked_serial(rmcv_pipeline* pl, rmcv_tracker* trk, co
 {
     if (!pl) return RMCV_ERR_BAD_ARG;
     if (!trk) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_submit_tracked: null tracker");
-    const rmcv_tracker_config& tc = tracker_config(trk);
-    const TrackerBufs& tb = tracker_bufs(trk);
+    const TrackerView& v = tracker_view(trk);
     BatchRequest q{d_frames, n_frames, frame_w, frame_h, stride, frame_pitch, p, stages};
     q.trk = trk, q.timestamp = timestamp, q.d_packets = d_packets;
     // win_w > 0: a windowed submit whose origins are the tracker's; win_w == 0: whole frames (track only)
-    q.d_origins = tc.win_w > 0 ? tb.origins : nullptr, q.win_w = tc.win_w, q.win_h = tc.win_h;
+    q.d_origins = v.origins, q.win_w = v.cfg.win_w, q.win_h = v.cfg.win_h;
     // a tracker with per-stream camps (rmcv_tracker_set_camps): a stream's colour is the stream's -- the submit takes the tracker's tables
-    q.d_camps = trk->camps_on ? tb.camps : nullptr, q.d_lower_bounds = trk->camps_on && trk->lower_bounds_on ? tb.lower_bounds : nullptr;
+    q.d_camps = v.camps, q.d_lower_bounds = v.lower_bounds;
     return submit_counted(pl, q, ticket);
 }
 

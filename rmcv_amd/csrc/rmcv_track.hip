@@ -1,13 +1,14 @@
 // rmcv_track.hip -- tracker state of rm::armour with everything readable: rm::armour::reset / update(const armour&) /
 // update(int64) (/root/reference/src/core.cpp:51-122) and the association loop of the tracking thread
 // (executable/main.cpp:57-88).  The HOST-SIDE form, over caller memory: one target or one list at a time, for a host that tracks a
-// single camera itself.  The device-resident form for a batch of streams is k_track.hip / device_track.h; both exist.  This one keeps
-// libm's hypot in the Jacobi rotation (it is compared with the unmodified CPU oracle); the device tracker uses the correctly rounded
-// pm_hypot, so the filter fields of the two may differ in the last bits (include/rmcv_abi.h).
+// single camera itself.  The device-resident form for a batch of streams is k_track.hip / device_track.h; both exist.
 //
-// The filter is cv::KalmanFilter(6, 6, 0, CV_64F) (core.cpp:21); [OCV] init / predict / correct are restated as recalled from
-// OpenCV's video/src/kalman.cpp (gemm = sequential k-sums in double; the gain through cv::solve(..., DECOMP_SVD) = one-sided
-// Jacobi SVD + back substitution), parity unpinned like every [OCV] piece (oracle/rmcv_oracle.h).
+// The filter -- cv::KalmanFilter(6, 6, 0, CV_64F) (core.cpp:21): predict and correct as sequential k-sums, the gain through a one-sided
+// Jacobi SVD and back substitution -- is device_track.h's trk_kf_predict / trk_kf_correct, the source the device tracker compiles, run
+// here as plain loops on a workspace whose record is the caller's, copied in and out.  ONE thing differs between the two forms: this one
+// is compared with the unmodified CPU oracle and keeps libm's hypot in the Jacobi rotation (TRK_HYPOT below); the device tracker uses the
+// correctly rounded pm_hypot, so the filter fields of the two may differ in the last bits (include/rmcv_abi.h).  What is
+// this file's own: init and reset, the identity history, and rmcv_track_step with its dry run and capacity rule.
 #include <math.h>
 #include <string.h>
 
@@ -16,136 +17,10 @@
 #include <algorithm>
 
 #include "../../include/rmcv_abi.h"
+#define TRK_HYPOT hypot
+#include "device_track.h"
 
 namespace {
-
-typedef double M6[36];
-
-// C = A * B (6x6, row-major); every entry a sequential sum over k ([OCV] GEMMSingleMul)
-void mul(const double* A, const double* B, double* C, int n, int m, int p) // (n x m) * (m x p)
-{
-    for (int i = 0; i < n; i++)
-        for (int j = 0; j < p; j++) {
-            double s = 0;
-            for (int k = 0; k < m; k++) s += A[i * m + k] * B[k * p + j];
-            C[i * p + j] = s;
-        }
-}
-// C = A * B^T + D  ([OCV] gemm(A, B, 1, D, 1, C, GEMM_2_T))
-void mul_bt_add(const double* A, const double* B, const double* D, double* C)
-{
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j < 6; j++) {
-            double s = 0;
-            for (int k = 0; k < 6; k++) s += A[i * 6 + k] * B[j * 6 + k];
-            C[i * 6 + j] = s + D[i * 6 + j];
-        }
-}
-
-// [OCV] JacobiSVDImpl_<double> on At (n rows of length m: the TRANSPOSE of the m x n matrix), as recalled: one-sided Jacobi
-// (Hestenes), eps = DBL_EPSILON * 10, at most max(m, 30) sweeps, singular values sorted descending; At's rows become the
-// left singular vectors (scaled to unit length), Vt the right ones.
-void jacobi_svd(double* At, double* W, double* Vt, int m, int n)
-{
-    const double eps = 2.220446049250313e-16 * 10, minval = 2.2250738585072014e-308;
-    double Wd[6];
-    for (int i = 0; i < n; i++) {
-        double sd = 0;
-        for (int k = 0; k < m; k++) sd += At[i * m + k] * At[i * m + k];
-        Wd[i] = sd;
-        for (int k = 0; k < n; k++) Vt[i * n + k] = 0;
-        Vt[i * n + i] = 1;
-    }
-    const int max_iter = std::max(m, 30);
-    for (int iter = 0; iter < max_iter; iter++) {
-        bool changed = false;
-        for (int i = 0; i < n - 1; i++)
-            for (int j = i + 1; j < n; j++) {
-                double *Ai = At + i * m, *Aj = At + j * m;
-                double a = Wd[i], p = 0, b = Wd[j];
-                for (int k = 0; k < m; k++) p += Ai[k] * Aj[k];
-                if (fabs(p) <= eps * sqrt(a * b)) continue;
-                p *= 2;
-                const double beta = a - b, gamma = hypot(p, beta);
-                double c, s;
-                if (beta < 0) {
-                    const double delta = (gamma - beta) * 0.5;
-                    s = sqrt(delta / gamma);
-                    c = p / (gamma * s * 2);
-                } else {
-                    c = sqrt((gamma + beta) / (gamma * 2));
-                    s = p / (gamma * c * 2);
-                }
-                a = b = 0;
-                for (int k = 0; k < m; k++) {
-                    const double t0 = c * Ai[k] + s * Aj[k], t1 = -s * Ai[k] + c * Aj[k];
-                    Ai[k] = t0;
-                    Aj[k] = t1;
-                    a += t0 * t0;
-                    b += t1 * t1;
-                }
-                Wd[i] = a;
-                Wd[j] = b;
-                changed = true;
-                double *Vi = Vt + i * n, *Vj = Vt + j * n;
-                for (int k = 0; k < n; k++) {
-                    const double t0 = c * Vi[k] + s * Vj[k], t1 = -s * Vi[k] + c * Vj[k];
-                    Vi[k] = t0;
-                    Vj[k] = t1;
-                }
-            }
-        if (!changed) break;
-    }
-    for (int i = 0; i < n; i++) {
-        double sd = 0;
-        for (int k = 0; k < m; k++) sd += At[i * m + k] * At[i * m + k];
-        Wd[i] = sqrt(sd);
-    }
-    for (int i = 0; i < n - 1; i++) {
-        int j = i;
-        for (int k = i + 1; k < n; k++)
-            if (Wd[j] < Wd[k]) j = k;
-        if (i != j) {
-            std::swap(Wd[i], Wd[j]);
-            for (int k = 0; k < m; k++) std::swap(At[i * m + k], At[j * m + k]);
-            for (int k = 0; k < n; k++) std::swap(Vt[i * n + k], Vt[j * n + k]);
-        }
-    }
-    for (int i = 0; i < n; i++) {
-        W[i] = Wd[i];
-        // [OCV] a null singular value gets a random unit vector here; a 6x6 innovation covariance H P H^T + R with R > 0 has none
-        const double s = Wd[i] > minval ? 1 / Wd[i] : 0.;
-        for (int k = 0; k < m; k++) At[i * m + k] *= s;
-    }
-}
-
-// X = A^-1 * B for 6x6 A, B: [OCV] cv::solve(A, B, X, DECOMP_SVD) = JacobiSVD of A^T's rows + SVBkSb (threshold 2 eps * sum w)
-void solve_svd(const double* A, const double* B, double* X)
-{
-    double At[36], W[6], Vt[36], buffer[6];
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j < 6; j++) At[i * 6 + j] = A[j * 6 + i];
-    jacobi_svd(At, W, Vt, 6, 6); // rows of At: u_i; rows of Vt: v_i
-    double threshold = 0;
-    for (int i = 0; i < 6; i++) threshold += W[i];
-    threshold *= 2.220446049250313e-16 * 2;
-    for (int i = 0; i < 36; i++) X[i] = 0;
-    for (int i = 0; i < 6; i++) {
-        double wi = W[i];
-        if (fabs(wi) <= threshold) continue;
-        wi = 1 / wi;
-        for (int j = 0; j < 6; j++) buffer[j] = 0;
-        for (int k = 0; k < 6; k++) { // MatrAXPY: buffer += u_i[k] * B[k][:]
-            const double s = At[i * 6 + k];
-            for (int j = 0; j < 6; j++) buffer[j] += s * B[k * 6 + j];
-        }
-        for (int j = 0; j < 6; j++) buffer[j] *= wi;
-        for (int k = 0; k < 6; k++) { // MatrAXPY: X[k][:] += v_i[k] * buffer
-            const double s = Vt[i * 6 + k];
-            for (int j = 0; j < 6; j++) X[k * 6 + j] += s * buffer[j];
-        }
-    }
-}
 
 void set_identity(double* M, double v)
 {
@@ -153,33 +28,17 @@ void set_identity(double* M, double v)
     for (int i = 0; i < 6; i++) M[i * 7] = v;
 }
 
-// [OCV] KalmanFilter::predict() without control
-void kf_predict(rmcv_track* t)
+// a filter step of device_track.h on the caller's record: the workspace (5 KB, on the stack) lives for the call
+template <typename Step>
+void on_workspace(rmcv_track* t, Step step)
 {
-    double temp1[36];
-    mul(t->transition, t->state_post, t->state_pre, 6, 6, 1);
-    mul(t->transition, t->error_cov_post, temp1, 6, 6, 6);
-    mul_bt_add(temp1, t->transition, t->process_noise_cov, t->error_cov_pre);
-    memcpy(t->state_post, t->state_pre, sizeof(t->state_pre));
-    memcpy(t->error_cov_post, t->error_cov_pre, sizeof(t->error_cov_pre));
+    trk_ws ws;
+    ws.rec = *t;
+    step(&ws, 0);
+    *t = ws.rec;
 }
-
-// [OCV] KalmanFilter::correct(measurement)
-void kf_correct(rmcv_track* t)
-{
-    double temp2[36], temp3[36], temp4[36], temp5[6], hx[6], kt2[36];
-    mul(t->measurement_matrix, t->error_cov_pre, temp2, 6, 6, 6);
-    mul_bt_add(temp2, t->measurement_matrix, t->measurement_noise_cov, temp3);
-    solve_svd(temp3, temp2, temp4);
-    for (int i = 0; i < 6; i++)
-        for (int j = 0; j < 6; j++) t->gain[i * 6 + j] = temp4[j * 6 + i];
-    mul(t->measurement_matrix, t->state_pre, hx, 6, 6, 1);
-    for (int i = 0; i < 6; i++) temp5[i] = t->measurement[i] - hx[i];
-    mul(t->gain, temp5, hx, 6, 6, 1);
-    for (int i = 0; i < 6; i++) t->state_post[i] = t->state_pre[i] + hx[i];
-    mul(t->gain, temp2, kt2, 6, 6, 6);
-    for (int i = 0; i < 36; i++) t->error_cov_post[i] = t->error_cov_pre[i] - kt2[i];
-}
+void kf_predict(rmcv_track* t) { on_workspace(t, trk_kf_predict); } // [OCV] KalmanFilter::predict() without control
+void kf_correct(rmcv_track* t) { on_workspace(t, trk_kf_correct); } // [OCV] KalmanFilter::correct(measurement)
 
 } // namespace
 

@@ -227,3 +227,42 @@ def test_pipeline_two_trackers_interleaved_with_untracked_submits(oracle):
     pl.close()
     trk_a.close()
     trk_b.close()
+
+
+# ---------------------------------------------------------------- 4. the object's tables, without a kernel
+def test_tables_before_first_use_switched_tables_and_put_get():
+    """what the getters hand out of tables that have never been allocated, a refused setter, every switched table on, off and on again, and
+    a list put and read back: host calls and copies only, no launch"""
+    from rmcv_amd import CAMP_RED, default_aim_config
+    n = 3
+    trk = Tracker(device=0, n_streams=n, track_cap=2, frame_w=FW, frame_h=FH)
+    # never used: what the tables would hold
+    att, err = trk.attitudes()
+    assert trk.aims().tobytes() == bytes(72 * n) and att.tobytes() == bytes(24 * n) and err.tolist() == [0] * n
+    want = np.zeros(n, abi.AIM_INPUT)
+    want["world2camera"] = np.eye(4)
+    assert trk.aim_inputs().tobytes() == want.tobytes() and want.nbytes == 136 * n
+    camps_before = trk.device_camps()
+    cfgs = [default_aim_config(v0=10.0 + f) for f in range(n)]
+    with pytest.raises(RmcvError) as e:
+        trk.set_aim_configs(cfgs)
+    assert e.value.code == abi.ERR_BAD_ARG and "aiming is off" in str(e.value)
+    assert [c.tolist() for c in trk.counts()] == [[0] * n, [0] * n]          # (still usable)
+    # every switched table on, off, on: a tracked submit takes the tracker's own two tables whatever was switched meanwhile
+    trk.set_aim()
+    trk.set_aim_configs(cfgs)
+    trk.set_aim_configs(None)
+    trk.set_aim_configs(cfgs)
+    trk.set_stream_cameras(np.tile(np.eye(4).reshape(16), (n, 1)))
+    trk.set_stream_cameras(None)
+    trk.set_camps([CAMP_BLUE, CAMP_RED, CAMP_BLUE], [100, 110, 120])
+    trk.set_camps(None)
+    assert trk.device_camps() == camps_before and all(camps_before)
+    assert trk.aims().tobytes() == bytes(72 * n) and trk.aim_inputs().tobytes() == want.tobytes()   # (allocated now: zero records, the defaults)
+    # a list goes in and comes back byte for byte; no side records given: zeros
+    two = np.frombuffer(np.random.default_rng(5).integers(0, 256, 2 * abi.TRACK.itemsize, dtype=np.uint8).tobytes(), abi.TRACK).copy()
+    trk.put(1, two)
+    tr, side, _ = trk.get(1)
+    assert tr.tobytes() == two.tobytes() and side.tobytes() == bytes(2 * 8 * 4)
+    assert trk.counts()[0].tolist() == [0, 2, 0] and len(trk.get(0)[0]) == len(trk.get(2)[0]) == 0
+    trk.close()
