@@ -1398,6 +1398,68 @@ int rmcv_tracker_config_from_loop(const void* loop_record, rmcv_tracker_config* 
 int rmcv_tracker_aim_config_from_loop(const void* loop_record, rmcv_aim_config* out, int32_t* has);
 int rmcv_tracker_attitude_config_from_loop(const void* loop_record, rmcv_attitude_config* out, double gripper2camera[16], int32_t* has);
 
+/* ---- dataset harvest: the labeler's job (executable/svm/labeler.cpp) on the device ---------------------------------
+ * A dataset is `capacity_rows` icon rows (u8 [1200], as rmcv_batch_get_icons hands them out) and their metadata in device memory.  Any
+ * batch whose last run included RMCV_STAGE_ARMOURS appends its armours' rows to it, with one label per frame (= per stream of a
+ * labelling session) and no host round trip; no model is needed, and RMCV_STAGE_IDENTITY only for RMCV_HARVEST_MISSES.  The rule:
+ *   - frame f contributes nothing when labels[f] == RMCV_HARVEST_SKIP or its status word carries an RMCV_FRAME_OVF_* bit;
+ *   - otherwise its candidates are armours 0 .. min(n[f], max_armours) - 1 in the order of rmcv_batch_get_armours;
+ *   - RMCV_HARVEST_MISSES keeps a candidate only when its identity != labels[f]; without the flag every candidate is kept;
+ *   - kept rows are numbered frame-major, then armour-major; kept row k of the call goes to slot count + k;
+ *   - a row whose slot is >= capacity is dropped: count = min(count + kept, capacity), dropped += max(0, count + kept - capacity).
+ * Appends to one dataset land in the order of the calls, whatever streams they are enqueued on: each waits, on the device, for the
+ * event of the one before.  The armour table is never written. */
+#define RMCV_HARVEST_SKIP INT32_MIN /* a label: the frame contributes nothing */
+#define RMCV_HARVEST_MISSES 1       /* a flag: keep only the armours the loaded model does not give the frame's label */
+typedef struct rmcv_harvest_meta { /* 64 bytes per row */
+    uint64_t tag;          /* the pipeline's ticket, or the caller's tag on a bare context */
+    int32_t  frame, armour, label;
+    int32_t  identity;     /* INT32_MIN when the run had no identity stage */
+    int32_t  win_x, win_y; /* the frame's effective window origin; 0, 0 without windows */
+    float    icon[4][2];   /* the icon quadrilateral as clamped by imgproc.cpp:11-15 (window coordinates in a windowed batch) */
+} rmcv_harvest_meta;
+typedef struct rmcv_harvest_item { int32_t frame, armour, slot; } rmcv_harvest_item;
+typedef struct rmcv_dataset rmcv_dataset;
+/* on the context's device; the context outlives the dataset (its deadline is the dataset's).  RMCV_ERR_BAD_ARG: capacity_rows < 1 */
+int  rmcv_dataset_create(rmcv_ctx* ctx, int capacity_rows, rmcv_dataset** out);
+void rmcv_dataset_destroy(rmcv_dataset* ds); /* waits for its last append */
+int  rmcv_dataset_clear(rmcv_dataset* ds);   /* waits for its last append; count = dropped = 0 */
+const char* rmcv_dataset_last_error(const rmcv_dataset* ds);
+/* waits for the last append with the context's deadline (RMCV_ERR_TIMEOUT); either pointer may be NULL */
+int  rmcv_dataset_count(rmcv_dataset* ds, int32_t* rows, int64_t* dropped);
+/* rows first .. first + n - 1 to host memory: rows_out u8 [n][1200], meta_out [n] (either may be NULL).  RMCV_ERR_BAD_ARG beyond count. */
+int  rmcv_dataset_get(rmcv_dataset* ds, int first, int n, uint8_t* rows_out, rmcv_harvest_meta* meta_out);
+/* zero-copy views: u8 [capacity][1200], rmcv_harvest_meta [capacity], and the int32 count (device memory).  Never synchronises: order a
+ * reader behind the appending stream. */
+int  rmcv_dataset_device(rmcv_dataset* ds, void** d_rows, void** d_meta, void** d_count);
+/* append the bound batch's armours, behind its last run on `hip_stream` (NULL: the context's).  labels: n_frames int32, host, copied.
+ * Asynchronous.  RMCV_ERR_BAD_ARG, with a message, before anything is enqueued: no frames bound; the last run lacked RMCV_STAGE_ARMOURS;
+ * RMCV_HARVEST_MISSES without RMCV_STAGE_IDENTITY in the last run; unknown flags; a dataset of another device. */
+int  rmcv_batch_harvest(rmcv_ctx* ctx, rmcv_dataset* ds, const int32_t* labels, int flags, uint64_t tag, void* hip_stream);
+/* the same with the labels in DEVICE memory (n_frames int32), borrowed until the append has run */
+int  rmcv_batch_harvest_device(rmcv_ctx* ctx, rmcv_dataset* ds, const void* d_labels, int flags, uint64_t tag, void* hip_stream);
+/* the rule on the host (no context, no device).  identity [n_frames][max_armours]: may be NULL without RMCV_HARVEST_MISSES.  items_out:
+ * the (frame, armour, slot) of every row that gets a slot, `cap` entries (RMCV_ERR_CAPACITY beyond; *n_items says what is needed);
+ * *count_out, *dropped_out: the counters behind the call (dropped_in + what this call drops). */
+int  rmcv_harvest_plan_host(const int32_t* n_armours, const int32_t* status, const int32_t* labels, const int32_t* identity, int n_frames,
+                            int max_armours, int flags, int32_t count, int32_t capacity, int64_t dropped_in, rmcv_harvest_item* items_out, int cap,
+                            int32_t* n_items, int32_t* count_out, int64_t* dropped_out);
+/* every following submit appends its batch behind its sparse stage (with RMCV_STAGE_IDENTITY: behind the classifier); tag = the ticket.
+ * labels: n_labels int32, host, copied.  ds NULL: off -- a submit then enqueues exactly what it did before.  The call itself may drain
+ * the pipeline; no submit blocks (rmcv_pipeline_info::host_blocking_calls stays 0).  RMCV_ERR_BAD_ARG, with a message: what
+ * rmcv_batch_harvest refuses; n_labels outside 1 .. max_frames; and, before anything is enqueued, a later submit whose batch has more
+ * frames than the label table, lacks RMCV_STAGE_ARMOURS, or lacks RMCV_STAGE_IDENTITY under RMCV_HARVEST_MISSES.  Detach (ds NULL) before
+ * destroying the dataset. */
+int  rmcv_pipeline_set_harvest(rmcv_pipeline* pl, rmcv_dataset* ds, const int32_t* labels, int n_labels, int flags);
+/* rmcv_svm_train on rows of the dataset, in place: rows = n int32 slot indices (host), or NULL = slots 0 .. n - 1; the responses are the
+ * rows' labels.  The rows are gathered on the device and only the responses (4 bytes per row) come to the host; every output is bit-identical
+ * to rmcv_svm_train on the same rows obtained through rmcv_dataset_get.  RMCV_ERR_BAD_ARG with a message: an index outside 0 .. count - 1,
+ * n < 1 or beyond RMCV_SVM_MAX_SAMPLES, a dataset of another device, and everything rmcv_svm_train refuses. */
+int  rmcv_svm_train_dataset(rmcv_ctx* ctx, rmcv_dataset* ds, const int32_t* rows, int n, const int32_t* perm, const rmcv_svm_train_params* params,
+                            float* weights_out, double* rho_out, int32_t* labels_out, int32_t* n_class_out, rmcv_svm_train_report* report);
+/* rmcv_svm_predict on rows of the dataset, in place (the validation pass of optimizer.cpp:27-40 without moving rows) */
+int  rmcv_svm_predict_dataset(rmcv_ctx* ctx, rmcv_dataset* ds, const int32_t* rows, int n, int32_t* identity_out);
+
 /* ---- device memory for hosts without HIP headers (tools/pipeline_bench.c): frames resident in HBM ------------------------------- */
 int  rmcv_device_alloc(int device, int64_t bytes, void** d_ptr);
 void rmcv_device_free(int device, void* d_ptr);

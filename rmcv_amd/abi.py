@@ -73,6 +73,10 @@ AIM_SRC_FILTER, AIM_SRC_MEASUREMENT = 0, 1
 AIM_PICK_WINDOW, AIM_PICK_NEAREST = 0, 1
 VIEW_BLOBS, VIEW_NEGATIVES, VIEW_ARMOURS, VIEW_ALL = 1, 2, 4, 7  # RMCV_VIEW_*: what the debug view draws over the binary (all: the reference)
 FRAME_OVF_CONTOURS, FRAME_OVF_POINTS, FRAME_OVF_BLOBS, FRAME_OVF_ARMOURS, FRAME_SLOW_PATH, FRAME_MID_PATH = 1, 2, 4, 8, 16, 64
+# dataset harvest: a label that keeps a frame out, the flag that keeps only the model's misses, a row's 64-byte metadata
+HARVEST_SKIP, HARVEST_MISSES = -2**31, 1
+HARVEST_META = np.dtype([("tag", "<u8"), ("frame", "<i4"), ("armour", "<i4"), ("label", "<i4"), ("identity", "<i4"), ("win_x", "<i4"), ("win_y", "<i4"),
+                         ("icon", "<f4", (4, 2))])
 
 EXPORTS = [
     "rmcv_abi_version", "rmcv_default_params", "rmcv_default_limits", "rmcv_ctx_create", "rmcv_ctx_destroy",
@@ -111,6 +115,8 @@ EXPORTS = [
     "rmcv_loop_bound", "rmcv_loop_trigger_host", "rmcv_recorder_set_trigger", "rmcv_recorder_trigger", "rmcv_recorder_loop", "rmcv_session_loop", "rmcv_session_append_loop",
     "rmcv_tracker_restore", "rmcv_tracker_config_from_loop", "rmcv_tracker_aim_config_from_loop", "rmcv_tracker_attitude_config_from_loop",
     "rmcv_svm_train_defaults", "rmcv_svm_train", "rmcv_svm_train_host", "rmcv_svm_gram", "rmcv_svm_gram_host", "rmcv_svm_predict", "rmcv_svm_predict_host",
+    "rmcv_dataset_create", "rmcv_dataset_destroy", "rmcv_dataset_clear", "rmcv_dataset_last_error", "rmcv_dataset_count", "rmcv_dataset_get", "rmcv_dataset_device",
+    "rmcv_batch_harvest", "rmcv_batch_harvest_device", "rmcv_harvest_plan_host", "rmcv_pipeline_set_harvest", "rmcv_svm_train_dataset", "rmcv_svm_predict_dataset",
 ]
 
 
@@ -475,6 +481,23 @@ def load(path):
         L.rmcv_svm_gram.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
         L.rmcv_svm_predict_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
         L.rmcv_svm_predict.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "rmcv_dataset_create"):  # (builds from before the dataset harvest stay loadable for A/B runs)
+        L.rmcv_dataset_create.argtypes = [C.c_void_p, C.c_int, C.c_void_p]
+        L.rmcv_dataset_destroy.restype = None
+        L.rmcv_dataset_destroy.argtypes = [C.c_void_p]
+        L.rmcv_dataset_clear.argtypes = [C.c_void_p]
+        L.rmcv_dataset_last_error.restype = C.c_char_p
+        L.rmcv_dataset_last_error.argtypes = [C.c_void_p]
+        L.rmcv_dataset_count.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_dataset_get.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.rmcv_dataset_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_batch_harvest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]
+        L.rmcv_batch_harvest_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64, C.c_void_p]
+        L.rmcv_harvest_plan_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int32, C.c_int32, C.c_int64, C.c_void_p,
+                                             C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_pipeline_set_harvest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
+        L.rmcv_svm_train_dataset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_svm_predict_dataset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L

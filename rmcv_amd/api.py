@@ -632,6 +632,20 @@ class Context:
         self._chk(lib().rmcv_svm_predict(self._h, ptr(s) if len(s) else None, len(s), ptr(out) if len(s) else None))
         return out
 
+    def harvest(self, ds, labels, flags=0, tag=0, stream=None):
+        """rmcv_batch_harvest: append the bound batch's armours' icon rows to the DeviceDataset `ds`, behind its last run (which included
+        STAGE_ARMOURS; no model needed).  labels: one int per frame (HARVEST_SKIP: the frame contributes nothing), or a device pointer (int)
+        to them, borrowed (rmcv_batch_harvest_device).  flags: HARVEST_MISSES keeps only the armours the loaded model gives another label.
+        Asynchronous: ds.count waits."""
+        if isinstance(labels, int):
+            self._chk(lib().rmcv_batch_harvest_device(self._h, ds._h, C.c_void_p(labels), int(flags), int(tag), stream))
+            return
+        lb = np.ascontiguousarray(labels, np.int32).reshape(-1)
+        shape = getattr(self, "shape", None)
+        if shape is not None and len(lb) != shape[0]:
+            raise RmcvError(abi.ERR_BAD_ARG, "harvest: one label per frame bound")
+        self._chk(lib().rmcv_batch_harvest(self._h, ds._h, ptr(lb), int(flags), int(tag), stream))
+
     def svm_train(self, samples, responses, perm=None, **params):
         """rmcv_svm_train on this context's GPU -> rmcv_amd.svm.Model (rmcv_amd.svm.train_auto with ctx=self)"""
         from . import svm

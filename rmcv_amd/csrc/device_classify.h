@@ -92,24 +92,16 @@ struct ClassifyArgs { // what the classification of a frame's armours needs (Buf
 
 ClassifyArgs classify_args(const Geom& g, const Bufs& b); // k_classify.hip
 
-// armours wave, wave + nwaves, ... of frame f by this wavefront.  feat: NFEAT floats, sums: 32 doubles of wave-private LDS.
-// BAYER: the frames are mosaics of pattern `pattern` in the layout `lay` (the stand-alone k_classify only: the sparse kernel classifies BGR frames)
-template <int BAYER = 0>
-__device__ inline void classify_frame(int f, int lane, int wave, int nwaves, int n, const ClassifyArgs& C, rmcv_armour* __restrict__ armours,
-                                      int max_armours, float* feat, double* sums, int pattern = 0, int lay = 0, const uint8_t* __restrict__ luts = nullptr,
-                                      int64_t origin = 0 /* frame_origin_offset of the frame's window (C.w, C.h are then the window's); 0: the whole frame */)
+// One armour's 20x20xBGR row by one wavefront (imgproc.cpp:11-32): clamp, integer box, getAffineTransform, warp on demand, resize, in OpenCV's
+// fixed point.  ic: the clamped quadrilateral (every lane has it); put(o, res): called by the lane that owns output pixel o with its three
+// bytes as ints.  Shared by classify_frame below and the dataset harvest (k_harvest.hip: k_harvest_rows); A is only read.
+// w, h: the extent the icon is clamped to (the frame's, or its window's); frame: the frame's first byte (its window's origin applied)
+template <int BAYER, class Put>
+__device__ __forceinline__ void icon_row(const uint8_t* frame, int f, int lane, const rmcv_armour* A, int w, int h, int stride, int pattern, int lay,
+                                         const uint8_t* luts, float ic[4][2], Put put)
 {
-    const uint8_t* frame = C.frames + (int64_t)f * C.frame_pitch + origin;
-    const int w = C.w, h = C.h, stride = C.stride, n_class = C.n_class;
-    const float* __restrict__ weights = C.weights;
-    const double* __restrict__ rho = C.rho;
-    const int32_t* __restrict__ labels = C.labels;
-    int32_t* __restrict__ identity = C.identity;
-    uint8_t* __restrict__ icons = C.icons;
-    for (int a = wave; a < n; a += nwaves) {
-        rmcv_armour* A = armours + (int64_t)f * max_armours + a;
+    {
         // ---- imgproc.cpp:11-15 clamp (in place, like the reference), :17 integer bounding box
-        float ic[4][2];
         int minx = 0, maxx = 0, miny = 0, maxy = 0;
 #pragma unroll
         for (int i = 0; i < 4; i++) {
@@ -249,12 +241,35 @@ __device__ inline void classify_frame(int f, int lane, int wave, int nwaves, int
                     }
                 }
             }
+            put(o, res);
+        }
+    }
+}
+
+// armours wave, wave + nwaves, ... of frame f by this wavefront.  feat: NFEAT floats, sums: 32 doubles of wave-private LDS.
+// BAYER: the frames are mosaics of pattern `pattern` in the layout `lay` (the stand-alone k_classify only: the sparse kernel classifies BGR frames)
+template <int BAYER = 0>
+__device__ inline void classify_frame(int f, int lane, int wave, int nwaves, int n, const ClassifyArgs& C, rmcv_armour* __restrict__ armours,
+                                      int max_armours, float* feat, double* sums, int pattern = 0, int lay = 0, const uint8_t* __restrict__ luts = nullptr,
+                                      int64_t origin = 0 /* frame_origin_offset of the frame's window (C.w, C.h are then the window's); 0: the whole frame */)
+{
+    const uint8_t* frame = C.frames + (int64_t)f * C.frame_pitch + origin;
+    const int w = C.w, h = C.h, stride = C.stride, n_class = C.n_class;
+    const float* __restrict__ weights = C.weights;
+    const double* __restrict__ rho = C.rho;
+    const int32_t* __restrict__ labels = C.labels;
+    int32_t* __restrict__ identity = C.identity;
+    uint8_t* __restrict__ icons = C.icons;
+    for (int a = wave; a < n; a += nwaves) {
+        rmcv_armour* A = armours + (int64_t)f * max_armours + a;
+        float ic[4][2];
+        icon_row<BAYER>(frame, f, lane, A, w, h, stride, pattern, lay, luts, ic, [&](int o, const int (&res)[3]) __attribute__((always_inline)) {
 #pragma unroll
             for (int c = 0; c < 3; c++) {
                 feat[o * 3 + c] = (float)res[c]; // flatten_image: reshape(1,1), CV_32FC1
                 if (icons) icons[((int64_t)f * max_armours + a) * NFEAT + o * 3 + c] = (uint8_t)res[c];
             }
-        }
+        });
         __builtin_amdgcn_wave_barrier();
         // ---- main.cpp:181 svm->predict: one lane per decision function
         const int n_df = n_class * (n_class - 1) / 2;

@@ -1,6 +1,7 @@
 // rmcv_ctx.h -- the context behind the ABI's handle and what the three units that implement its entry points share: rmcv_host.hip
 // (context, binding, run, batch setters and getters), rmcv_stagewise.hip (the helpers that run on the caller's own data) and
-// rmcv_frame.hip (the per-frame chain); rmcv_svm.hip (the classifier's trainer) takes the error and wait helpers.  Private to those:
+// rmcv_frame.hip (the per-frame chain); rmcv_svm.hip (the classifier's trainer) and rmcv_harvest.hip (the dataset's entry points) take
+// the error and wait helpers.  Private to those:
 // every other unit goes through the ctx_* functions of rmcv_internal.h.
 #pragma once
 #include <stdio.h>

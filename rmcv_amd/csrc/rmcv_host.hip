@@ -1214,6 +1214,35 @@ int ctx_attitude(rmcv_ctx* c, rmcv_tracker* trk, const void* d_packets, hipStrea
     HIPCHK(c, tracker_order_end(trk, s), "attitude: record the step");
     return order_end(c, s);
 }
+
+// the dataset harvest behind the bound batch's last run: every check before the first enqueue; never synchronises.  An append
+// is a step of the dataset's: behind its previous one, whatever stream that ran on, and recorded as its newest.
+const char* ctx_harvest_refusal(int device, int n_frames, bool frames_bound, const rmcv_dataset* ds, int n_labels, int flags, int stages)
+{
+    if (!ds) return "harvest: null dataset";
+    if (const char* no = harvest_refusal(frames_bound, stages, flags, device, dataset_view(ds).device)) return no;
+    if (n_frames > n_labels) return "harvest: the batch has more frames than the label table";
+    return nullptr;
+}
+int ctx_harvest(rmcv_ctx* c, rmcv_dataset* ds, const int32_t* h_labels, const void* d_labels, int n_labels, int flags, uint64_t tag, int stages, hipStream_t s)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!h_labels && !d_labels) return fail(c, RMCV_ERR_BAD_ARG, "harvest: null labels");
+    const Geom& g = c->geom;
+    if (h_labels && ds) { // host labels travel through the dataset's own table, rewritten behind its previous append
+        n_labels = dataset_view(ds).label_cap;
+        d_labels = dataset_view(ds).labels;
+    }
+    if (const char* no = ctx_harvest_refusal(c->device, g.n_frames, g.n_frames > 0 && c->bufs.frames, ds, n_labels, flags, stages)) return fail(c, RMCV_ERR_BAD_ARG, no);
+    int rc;
+    if ((rc = order_begin(c, s))) return rc;
+    HIPCHK(c, dataset_order_begin(ds, s), "harvest: wait for the dataset's previous append");
+    if (h_labels) HIPCHK(c, hipMemcpyAsync(const_cast<void*>(d_labels), h_labels, (size_t)g.n_frames * 4, hipMemcpyHostToDevice, s), "H2D harvest labels");
+    HIPCHK(c, launch_harvest(g, c->bufs, c->lim, dataset_view(ds), static_cast<const int32_t*>(d_labels), flags, (stages & RMCV_STAGE_IDENTITY) != 0, tag, s),
+           "k_harvest_plan + k_harvest_rows");
+    HIPCHK(c, dataset_order_end(ds, s), "harvest: record the append");
+    return order_end(c, s);
+}
 } // namespace rmcv
 
 /* ---- the operator's debug view (k_view.hip) ---- */

@@ -1,6 +1,6 @@
 // rmcv_internal.h -- shared declarations of the HIP translation units (not part of the ABI): the device buffers, the kernel launchers of
 // the k_*.hip units, and what the units behind the ABI (rmcv_host, rmcv_stagewise, rmcv_frame, rmcv_pipeline, rmcv_track, rmcv_tracker,
-// rmcv_record, rmcv_gather) need of each other.  Limits and Geom come from bind_plan.h.
+// rmcv_record, rmcv_gather, rmcv_harvest) need of each other.  Limits and Geom come from bind_plan.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -11,6 +11,7 @@
 
 #include "../../include/rmcv_abi.h"
 #include "bind_plan.h"
+#include "device_harvest.h"
 #include "image_plan.h"
 #include "pixel_plan.h"
 #include "sparse_plan.h"
@@ -471,5 +472,39 @@ hipError_t launch_svm_solve(const SvmDevice& d, int n_problems, double eps, int 
 // d_out[m * n + r], m < n_models: row r under model m * k_fold + d_fold_of[r] (d_fold_of null: model 0); d_labels null: class indices
 hipError_t launch_svm_predict(const uint8_t* d_samples, int n, const float* d_weights, const double* d_rho, int n_class, const int32_t* d_fold_of, int k_fold,
                               int n_models, const int32_t* d_labels, int32_t* d_out, hipStream_t s);
+// rmcv_svm_train / rmcv_svm_predict behind their pointer checks (rmcv_svm.hip).  d_samples non-null: the rows are on the device already
+// (rmcv_svm_train_dataset: the upload is skipped, `samples` is not read); null: `samples` (host) is uploaded
+int svm_train_rows(rmcv_ctx* c, const uint8_t* d_samples, const uint8_t* samples, const int32_t* responses, int n, const int32_t* perm,
+                   const rmcv_svm_train_params* params, float* weights_out, double* rho_out, int32_t* labels_out, int32_t* n_class_out,
+                   rmcv_svm_train_report* report);
+int svm_predict_rows(rmcv_ctx* c, const uint8_t* d_samples, const uint8_t* samples, int n, int32_t* identity_out);
+
+// ---- the dataset harvest (k_harvest.hip, rmcv_harvest.hip) ----
+// what is read of a dataset outside rmcv_harvest.hip, the one unit that knows struct rmcv_dataset
+struct DatasetView {
+    int device;
+    int32_t capacity;
+    uint8_t* rows;           // [capacity][1200]
+    rmcv_harvest_meta* meta; // [capacity]
+    HarvestCounters* ctr;    // count, the last append's list length, dropped
+    HarvestItem* list;       // [capacity] the work list of the append in flight (appends are ordered: one at a time)
+    int32_t* labels;         // [label_cap] the host labels of the append in flight (rmcv_batch_harvest copies them here)
+    int label_cap;
+};
+const DatasetView& dataset_view(const rmcv_dataset* ds);
+// the order of an append on `s`: wait (on the GPU) for the dataset's last append if that ran on another stream; afterwards record it
+hipError_t dataset_order_begin(rmcv_dataset* ds, hipStream_t s);
+hipError_t dataset_order_end(rmcv_dataset* ds, hipStream_t s);
+// k_harvest_plan + k_harvest_rows on `s`; identity: the batch's run included RMCV_STAGE_IDENTITY.  Every argument has been checked by the caller.
+hipError_t launch_harvest(const Geom& g, const Bufs& b, const Limits& lim, const DatasetView& d, const int32_t* d_labels, int flags, bool identity,
+                          uint64_t tag, hipStream_t s);
+// d_out [n][1200] (nullable), d_responses [n] (nullable) of slots d_idx[0 .. n) (null: 0 .. n - 1)
+hipError_t launch_harvest_gather(const DatasetView& d, const int32_t* d_idx, int n, uint8_t* d_out, int32_t* d_responses, hipStream_t s);
+// rmcv_batch_harvest_device with the stages given (a pipeline runs a batch's halves separately), on `s` (rmcv_host.hip): every check before the
+// first enqueue.  d_labels: n_labels entries (a batch with more frames is refused), launches and event calls only; or h_labels (host, one per
+// frame bound): copied into the dataset's own table on `s`, behind its previous append
+int ctx_harvest(rmcv_ctx* c, rmcv_dataset* ds, const int32_t* h_labels, const void* d_labels, int n_labels, int flags, uint64_t tag, int stages, hipStream_t s);
+// ... and what it would refuse, checked without enqueuing anything (a pipeline's submit asks before its first enqueue)
+const char* ctx_harvest_refusal(int device, int n_frames, bool frames_bound, const rmcv_dataset* ds, int n_labels, int flags, int stages);
 
 } // namespace rmcv

@@ -95,6 +95,7 @@ struct rmcv_pipeline {
         hipStream_t B = nullptr;
         bool views = false;     // debug views are rendered behind its sparse stage
         LoopTicket loop{};      // a recorded tracked batch: the recorder slot its loop records go into (chosen at the submit; the step runs a call later)
+        bool harvest = false;   // its armours' icon rows are appended to the dataset behind its sparse stage
     } pend;
     rmcv_pipeline_hook hook = nullptr; // ... or the built-in gather hook
     void* hook_user = nullptr;
@@ -121,6 +122,12 @@ struct rmcv_pipeline {
         int n = 0, max_index = 0;
         int32_t frames[RMCV_RECORDER_MAX_FRAMES] = {};
     } recd;
+    // rmcv_pipeline_set_harvest: every following batch appends its armours' icon rows to the dataset behind its sparse stage (ds null: off)
+    struct Harvest {
+        rmcv_dataset* ds = nullptr;
+        int32_t* d_labels = nullptr; // [n_labels] the label table, on the device (the pipeline's own copy)
+        int n_labels = 0, flags = 0;
+    } harv;
     char err[256] = {0};
 };
 
@@ -233,6 +240,7 @@ void rmcv_pipeline_destroy(rmcv_pipeline* pl)
     for (auto c : pl->ring) rmcv_ctx_destroy(c);
     for (auto& s : pl->slots) slot_destroy(s);
     if (pl->views.d_frames) hipFree(pl->views.d_frames);
+    if (pl->harv.d_labels) hipFree(pl->harv.d_labels);
     if (pl->ev_gather) hipEventDestroy(pl->ev_gather);
     for (auto streams : {&pl->pix, &pl->sp, &pl->dn})
         for (auto s : *streams) if (s) hipStreamDestroy(s);
@@ -443,6 +451,15 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
         pl->last_what = "k_view_resize";
         S.view_n = V.n, S.view_w = V.vw, S.view_h = V.vh;
     }
+    // the dataset harvest: behind the sparse stage (it reads the armours, and the identities behind the classifier), in front of ev_free (it reads
+    // the frames through the effective origins / gamma tables the next pixel pass of this context rewrites); an append waits, on the GPU, for
+    // the dataset's previous one, so the rows land in ticket order whichever streams the slots finish on
+    if (P.harvest) {
+        const rmcv_pipeline::Harvest& Hv = pl->harv; // (as at the submit: rmcv_pipeline_set_harvest drains first)
+        rc = ctx_harvest(P.c, Hv.ds, nullptr, Hv.d_labels, Hv.n_labels, Hv.flags, P.t, q.stages, T);
+        if (rc) return cfail(pl, P.c, rc);
+        pl->last_what = "k_harvest_rows";
+    }
     PCHK(pl, hipEventRecord(S.ev_free, T), "pipeline: mark the pixel outputs' last reader");
     // the record is rewritten: a reader on another stream (the hook's) must be through; readers on B are by stream order
     if (S.ev_hook) {
@@ -508,6 +525,8 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
         if (const char* no = recorder_refusal(pl->recd.rec, pl->device, pl->recd.n, q.w * ctx_frame_pixel_bytes(pl->ring[0]), q.h)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
         if (const char* no = recorder_trigger_refusal(pl->recd.rec, pl->cfg.depth)) return pfail(pl, RMCV_ERR_BAD_ARG, no); // (armed since rmcv_pipeline_set_recorder)
     }
+    if (pl->harv.ds) // (with no dataset set: nothing here, and nothing further down)
+        if (const char* no = ctx_harvest_refusal(pl->device, q.n_frames, true, pl->harv.ds, pl->harv.n_labels, pl->harv.flags, stages)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
     hipSetDevice(pl->device);
     int rc = finish_back(pl, false); // the batch before this one: a pixel launch follows it
     if (rc) return rc;
@@ -617,7 +636,7 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
     }
     pl->next_ticket = t + 1;
     if (ticket) *ticket = t;
-    pl->pend = {true, t, q, *q.p, lp ? *lp : rmcv_legacy_params{}, k, c, used, plan, sparse, B, pl->views.n > 0, loop};
+    pl->pend = {true, t, q, *q.p, lp ? *lp : rmcv_legacy_params{}, k, c, used, plan, sparse, B, pl->views.n > 0, loop, pl->harv.ds != nullptr};
     pl->pend.req.p = &pl->pend.p; // (the caller's params live as long as its call)
     pl->pend.req.lp = lp ? &pl->pend.lp : nullptr;
     // (a hook or the gather hands the record to a consumer the pipeline does not see waiting: its batches are finished here and now)
@@ -848,6 +867,28 @@ int rmcv_pipeline_set_recorder(rmcv_pipeline* pl, rmcv_recorder* rec, const int3
     pl->recd.rec = rec, pl->recd.max_index = top;
     for (int k = 0; k < n; k++) pl->recd.frames[k] = frames[k];
     pl->recd.n = n;
+    return RMCV_OK;
+}
+
+int rmcv_pipeline_set_harvest(rmcv_pipeline* pl, rmcv_dataset* ds, const int32_t* labels, int n_labels, int flags)
+{
+    if (!pl) return RMCV_ERR_BAD_ARG;
+    hipSetDevice(pl->device);
+    // batches in flight keep the dataset and the labels they were submitted under: everything submitted so far is through first (this call may block)
+    int rc = rmcv_pipeline_drain(pl);
+    if (rc) return rc;
+    pl->harv.ds = nullptr; // (off, should anything below fail)
+    if (pl->harv.d_labels) (void)hipFree(pl->harv.d_labels);
+    pl->harv.d_labels = nullptr;
+    if (!ds) return RMCV_OK;
+    if (!labels) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_harvest: null labels");
+    if (n_labels < 1 || n_labels > pl->lim.max_frames) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_harvest: n_labels outside 1 .. max_frames");
+    // (the frames and the stages are the batch's: checked at every submit)
+    if (const char* no = ctx_harvest_refusal(pl->device, 1, true, ds, n_labels, flags, ~0)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
+    hipError_t e = hipMalloc((void**)&pl->harv.d_labels, (size_t)n_labels * 4);
+    if (e == hipSuccess) e = hipMemcpy(pl->harv.d_labels, labels, (size_t)n_labels * 4, hipMemcpyHostToDevice);
+    if (e != hipSuccess) return pfail(pl, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_pipeline_set_harvest", e);
+    pl->harv.ds = ds, pl->harv.n_labels = n_labels, pl->harv.flags = flags;
     return RMCV_OK;
 }
 

@@ -105,21 +105,7 @@ int rmcv_svm_gram(rmcv_ctx* c, const uint8_t* samples, int n, int32_t* gram_out)
 int rmcv_svm_predict(rmcv_ctx* c, const uint8_t* samples, int n, int32_t* identity_out)
 {
     if (!c || n < 0 || (n && (!samples || !identity_out))) return RMCV_ERR_BAD_ARG;
-    if (!c->bufs.svm_w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_svm_predict needs a model: rmcv_svm_load first");
-    if (n > (1 << 20)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_svm_predict: more than 1048576 rows in one call");
-    if (n == 0) return RMCV_OK;
-    if (const int rc = ctx_ready(c)) return rc;
-    SvmScratch ws;
-    uint8_t* d_samples = nullptr;
-    int32_t* d_out = nullptr;
-    hipError_t e = ws.get(&d_samples, (size_t)n * SVM_NFEAT);
-    if (e == hipSuccess) e = ws.get(&d_out, (size_t)n * sizeof(int32_t));
-    if (e != hipSuccess) return fail(c, RMCV_ERR_NOMEM, "svm predict workspace", e);
-    HIPCHK(c, hipMemcpy(d_samples, samples, (size_t)n * SVM_NFEAT, hipMemcpyHostToDevice), "H2D svm samples");
-    HIPCHK(c, launch_svm_predict(d_samples, n, c->bufs.svm_w, c->bufs.svm_rho, c->bufs.svm_classes, nullptr, 0, 1, c->bufs.svm_labels, d_out, c->stream), "k_svm_predict");
-    WAITCHK(c, wait_stream(c, c->stream, "rmcv_svm_predict"));
-    HIPCHK(c, hipMemcpy(identity_out, d_out, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost), "D2H svm identities");
-    return RMCV_OK;
+    return svm_predict_rows(c, nullptr, samples, n, identity_out);
 }
 
 int rmcv_svm_train(rmcv_ctx* c, const uint8_t* samples, const int32_t* responses, int n, const int32_t* perm, const rmcv_svm_train_params* params,
@@ -128,6 +114,36 @@ int rmcv_svm_train(rmcv_ctx* c, const uint8_t* samples, const int32_t* responses
     svm_report_reset(report, nullptr);
     if (!c) return RMCV_ERR_BAD_ARG;
     if (!samples || !responses || !weights_out || !rho_out || !labels_out || !n_class_out) return refuse_train(c, report, "svm train: a null pointer");
+    return svm_train_rows(c, nullptr, samples, responses, n, perm, params, weights_out, rho_out, labels_out, n_class_out, report);
+}
+
+} // extern "C"
+
+namespace rmcv {
+
+int svm_predict_rows(rmcv_ctx* c, const uint8_t* d_rows, const uint8_t* samples, int n, int32_t* identity_out)
+{
+    if (!c->bufs.svm_w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_svm_predict needs a model: rmcv_svm_load first");
+    if (n > (1 << 20)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_svm_predict: more than 1048576 rows in one call");
+    if (n == 0) return RMCV_OK;
+    if (const int rc = ctx_ready(c)) return rc;
+    SvmScratch ws;
+    uint8_t* d_samples = const_cast<uint8_t*>(d_rows); // (only read)
+    int32_t* d_out = nullptr;
+    hipError_t e = d_rows ? hipSuccess : ws.get(&d_samples, (size_t)n * SVM_NFEAT);
+    if (e == hipSuccess) e = ws.get(&d_out, (size_t)n * sizeof(int32_t));
+    if (e != hipSuccess) return fail(c, RMCV_ERR_NOMEM, "svm predict workspace", e);
+    if (!d_rows) HIPCHK(c, hipMemcpy(d_samples, samples, (size_t)n * SVM_NFEAT, hipMemcpyHostToDevice), "H2D svm samples");
+    HIPCHK(c, launch_svm_predict(d_samples, n, c->bufs.svm_w, c->bufs.svm_rho, c->bufs.svm_classes, nullptr, 0, 1, c->bufs.svm_labels, d_out, c->stream), "k_svm_predict");
+    WAITCHK(c, wait_stream(c, c->stream, "rmcv_svm_predict"));
+    HIPCHK(c, hipMemcpy(identity_out, d_out, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost), "D2H svm identities");
+    return RMCV_OK;
+}
+
+int svm_train_rows(rmcv_ctx* c, const uint8_t* d_rows, const uint8_t* samples, const int32_t* responses, int n, const int32_t* perm,
+                   const rmcv_svm_train_params* params, float* weights_out, double* rho_out, int32_t* labels_out, int32_t* n_class_out,
+                   rmcv_svm_train_report* report)
+{
     rmcv_svm_train_params p;
     if (params) p = *params;
     else svm_default_params(&p);
@@ -139,13 +155,13 @@ int rmcv_svm_train(rmcv_ctx* c, const uint8_t* samples, const int32_t* responses
     hipStream_t s = c->stream;
     // ---- the workspace
     SvmScratch ws;
-    uint8_t* d_samples = nullptr;
+    uint8_t* d_samples = const_cast<uint8_t*>(d_rows); // (only read)
     int32_t *d_gram = nullptr, *d_cls = nullptr, *d_lists = nullptr, *d_fold_of = nullptr, *d_pred = nullptr;
     SvmProblem* d_problems = nullptr;
     double *d_alphas = nullptr, *d_rho = nullptr;
     float* d_weights = nullptr;
     SvmPairOut* d_outs = nullptr;
-    hipError_t e = ws.get(&d_samples, sz.samples);
+    hipError_t e = d_rows ? hipSuccess : ws.get(&d_samples, sz.samples);
     if (e == hipSuccess) e = ws.get(&d_gram, sz.gram);
     if (e == hipSuccess) e = ws.get(&d_cls, sz.cls);
     if (e == hipSuccess) e = ws.get(&d_lists, sz.lists);
@@ -158,7 +174,7 @@ int rmcv_svm_train(rmcv_ctx* c, const uint8_t* samples, const int32_t* responses
     if (e == hipSuccess) e = ws.get(&d_pred, sz.pred);
     if (e == hipSuccess) e = ws.events();
     if (e != hipSuccess) return fail(c, RMCV_ERR_NOMEM, "svm train workspace", e);
-    HIPCHK(c, hipMemcpy(d_samples, samples, sz.samples, hipMemcpyHostToDevice), "H2D svm samples");
+    if (!d_rows) HIPCHK(c, hipMemcpy(d_samples, samples, sz.samples, hipMemcpyHostToDevice), "H2D svm samples");
     HIPCHK(c, hipMemcpy(d_cls, pl.cls.data(), sz.cls, hipMemcpyHostToDevice), "H2D svm classes");
     HIPCHK(c, hipMemcpy(d_lists, pl.lists.data(), sz.lists, hipMemcpyHostToDevice), "H2D svm lists");
     const SvmDevice dev{d_samples, d_gram, n, d_cls, d_lists, d_problems, d_alphas, d_weights, d_rho, d_outs};
@@ -212,4 +228,4 @@ int rmcv_svm_train(rmcv_ctx* c, const uint8_t* samples, const int32_t* responses
     return RMCV_OK;
 }
 
-} // extern "C"
+} // namespace rmcv

@@ -183,6 +183,15 @@ class Pipeline:
         self._chk(self._lib.rmcv_pipeline_set_recorder(self._h, rec._h if rec is not None else None, ptr(fr) if len(fr) else None, len(fr)))
         self._recorder = rec if len(fr) else None   # (kept alive as long as batches go into it)
 
+    def set_harvest(self, ds, labels=None, flags=0):
+        """from the next submit of any form on, every batch appends its armours' icon rows to the DeviceDataset `ds` behind its sparse stage
+        (behind the classifier with STAGE_IDENTITY), tagged with its ticket, in ticket order (rmcv_pipeline_set_harvest: drains HERE; no
+        submit blocks).  labels: one int per frame of the batches to come (HARVEST_SKIP: none of that frame).  ds None: off -- detach
+        before closing the dataset."""
+        lb = np.ascontiguousarray(labels if labels is not None and ds is not None else [], np.int32).reshape(-1)
+        self._chk(self._lib.rmcv_pipeline_set_harvest(self._h, ds._h if ds is not None else None, ptr(lb) if len(lb) else None, len(lb), int(flags)))
+        self._harvest = ds   # (kept alive as long as batches go into it)
+
     def set_hot_contexts(self, n):
         """rmcv_pipeline_config::hot_contexts from the next submit on (0: off)"""
         self._chk(self._lib.rmcv_pipeline_set_hot_contexts(self._h, int(n)))
