@@ -297,6 +297,10 @@ int64_t rmcv_pixel_ws_launches(void);
  * context wrote its image last (a context remembers, per row, which words of its image are non-zero; k_binary_ws alone keeps that
  * record, any other writer of the image drops it, and the next k_binary_ws launch stores every byte again).  A diagnostic, like the above. */
 int64_t rmcv_pixel_image_delta_launches(void);
+/* ... and of those, the launches that stored the bit plane the same way: only the words that are or were non-zero, no pad words, only the row
+ * masks that changed.  Possible while plane and image of the context come from the same launches; a pixel launch without the image
+ * (RMCV_STAGE_NO_IMAGE) ends that until the next launch with it, which stores the whole plane.  A diagnostic, like the above. */
+int64_t rmcv_pixel_plane_delta_launches(void);
 /* every device buffer of a context lies between two 4 KiB guard zones holding a fixed pattern: count the damaged ones (0 in a
  * correct build; rmcv_last_error names the first).  Synchronises the context.  A test/diagnosis hook (tests/test_gpu_canary.py). */
 int  rmcv_ctx_check_guards(rmcv_ctx* ctx, int32_t* n_damaged);

@@ -48,4 +48,21 @@ inline ImageStep image_step(const ImageState& st, const ImageLaunch& l, bool ok)
     return r;
 }
 
+// ---- the bit plane beside the image: plane word k of row y is zero exactly when image word k is, so in a delta launch the
+// image's mask says which plane words to store as well -- as long as plane, row masks, image and image mask of the context all come from
+// the SAME launches.  A pixel launch without the image (RMCV_STAGE_NO_IMAGE) writes plane and row masks alone and breaks that.
+// sync: the leading frames whose plane and row masks were last written by a launch that wrote their image and its mask too (0: none).
+struct PlaneStep { bool delta; int next; };
+// mode: image_step's for this launch.  delta: k_binary_ws stores only the plane words that are or were non-zero, no pad words, and only the
+// row masks that changed; next: `sync` once the launch has been enqueued (ok) or has failed to be.
+inline PlaneStep plane_step(int sync, ImageMode mode, const ImageLaunch& l, bool ok)
+{
+    PlaneStep r = {false, 0};
+    if (!l.image || l.kernel != IMAGE_KERNEL_WS) return r; // the plane is rewritten without the image, or the image's state is lost anyway
+    r.delta = mode == IMAGE_DELTA && l.frames <= sync;
+    // (a delta launch with fewer frames leaves the rest in sync: neither their planes nor their images are touched)
+    if (ok) r.next = r.delta ? sync : l.frames;
+    return r;
+}
+
 } // namespace rmcv

@@ -41,21 +41,24 @@ static std::atomic<int64_t> g_ws_launches{0};
 int64_t pixel_ws_launches() { return g_ws_launches.load(std::memory_order_relaxed); }
 static std::atomic<int64_t> g_image_delta_launches{0};
 int64_t pixel_image_delta_launches() { return g_image_delta_launches.load(std::memory_order_relaxed); }
+static std::atomic<int64_t> g_plane_delta_launches{0};
+int64_t pixel_plane_delta_launches() { return g_plane_delta_launches.load(std::memory_order_relaxed); }
 #define K1_LAUNCH_T launch_binary_t
 #define K1_EXTRA
 #include "k_binary_launch.inc"
 
 hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s,
-                         ImageState* img)
+                         ImageState* img, int* plane)
 {
     const PixelVariant v = pixel_variant(g.input_format, g.enhance, g.win, g.keys);
     // imgproc.cpp:56-65: GUIDELIGHT G-R; BLUE B-R; everything else (RED, NEUTRAL) R-B.  BGR byte order.
     if (v == PIXEL_BGR)
-        return with_channel_pair(frame_key_eff(camp, lower_bound), [&](auto ca, auto cb) { return launch_binary_t<ca, cb>(g, b, lower_bound, morph, image, plan, s, img); });
+        return with_channel_pair(frame_key_eff(camp, lower_bound), [&](auto ca, auto cb) { return launch_binary_t<ca, cb>(g, b, lower_bound, morph, image, plan, s, img, plane); });
     // the other kernels store every byte of the image and know nothing of its mask (image_plan.h: IMAGE_KERNEL_OTHER)
     const ImageLaunch l = {IMAGE_KERNEL_OTHER, image, g.w, g.h, g.ww, g.n_frames};
     const ImageState before = img ? *img : IMAGE_STATE_UNKNOWN;
     if (img) *img = image_step(before, l, false).next;
+    if (plane) *plane = 0; // (plane_step: no other kernel keeps the plane in step with the image)
     hipError_t e = hipSuccess;
     switch (v) {
     case PIXEL_BGR: break;

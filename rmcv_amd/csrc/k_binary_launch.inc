@@ -5,6 +5,7 @@
 // contiguous -- never the linear loader, never k_binary_ws; FAST 2 is not even instantiated.
 // img (nullable; the K1_ENH 0, K1_WIN 0 build alone reads it): what the context knows about its byte image (image_plan.h).  It decides how
 // k_binary_ws stores the image and is rewritten once every chunk has been enqueued -- or left UNKNOWN by an error.
+// plane (nullable, beside img): the frames whose bit plane and row masks are in step with the image (image_plan.h: plane_step), kept the same way.
 #ifndef K1_WIN
 #define K1_WIN 0
 #endif
@@ -20,7 +21,7 @@
 template <int CA, int CB>
 #endif
 static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int morph, bool image, const RunPlan& plan,
-                                  hipStream_t s, ImageState* img = nullptr)
+                                  hipStream_t s, ImageState* img = nullptr, int* plane = nullptr)
 {
     // everything about the launches but the HIP calls: pixel_plan.h
     constexpr PixelVariant variant = K1_CAMP ? (K1_WIN ? PIXEL_CAMP_WIN : PIXEL_CAMP) : K1_WIN ? PIXEL_WIN : K1_ENH ? PIXEL_ENH : PIXEL_BGR;
@@ -32,8 +33,11 @@ static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int
     const ImageState img_before = img ? *img : IMAGE_STATE_UNKNOWN;
     const ImageLaunch img_launch = {IMAGE_KERNEL_WS, image, g.w, g.h, g.ww, g.n_frames};
     const ImageMode img_mode = image_step(img_before, img_launch, true).mode;
+    const int plane_before = plane ? *plane : 0;
+    const bool plane_delta = plane_step(plane_before, img_mode, img_launch, true).delta;
     bool all_ws = true;
     if (img) *img = image_step(img_before, img_launch, false).next; // (until every chunk is enqueued: what an error return leaves behind)
+    if (plane) *plane = plane_step(plane_before, img_mode, img_launch, false).next;
 #endif
     for (int f0 = 0; f0 < g.n_frames; f0 += ps.chunk) {
         const int nf = std::min(ps.chunk, g.n_frames - f0);
@@ -64,8 +68,10 @@ static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int
             ka.lb = lb; ka.morph = morph; ka.binary = binary; ka.bits = bits; ka.prow = g.prow; ka.plane_pitch = g.plane_pitch;
             ka.strips = strips; ka.n_blocks = n_blocks; ka.rowmask = rowmask; ka.strip_ctr = b.strip_ctr;
             ka.imgmask = b.imgmask + (int64_t)f0 * g.h; ka.delta = img_mode == IMAGE_DELTA;
+            ka.plane_delta = plane_delta;
             g_ws_launches.fetch_add(1, std::memory_order_relaxed);
             if (ka.delta && binary) g_image_delta_launches.fetch_add(1, std::memory_order_relaxed);
+            if (ka.delta && binary && plane_delta) g_plane_delta_launches.fetch_add(1, std::memory_order_relaxed);
             // (issue priority 3 for loaders and storers, the sparse kernel's own: in-process A/B against 0 / (2,1) / (3,0) / (1,1):
             // 0.991 / 1.008 / 1.017 / 1.006 of the step; again with the delta stores of the image, against (2,2) / (1,1) / (0,0): 0.988 /
             // 0.997 / 0.999 with the pairs disagreeing in sign -- profiles/image_delta_schedule_ab.txt)
@@ -90,7 +96,9 @@ static hipError_t K1_LAUNCH_T(const Geom& g, const Bufs& b, int lower_bound, int
         if (e != hipSuccess) return e;
     }
 #if !K1_ENH && !K1_WIN && !K1_CAMP
-    if (img) *img = image_step(img_before, {all_ws ? IMAGE_KERNEL_WS : IMAGE_KERNEL_OTHER, image, g.w, g.h, g.ww, g.n_frames}, true).next;
+    const ImageLaunch img_ran = {all_ws ? IMAGE_KERNEL_WS : IMAGE_KERNEL_OTHER, image, g.w, g.h, g.ww, g.n_frames};
+    if (img) *img = image_step(img_before, img_ran, true).next;
+    if (plane) *plane = plane_step(plane_before, img_mode, img_ran, true).next;
 #endif
     return hipSuccess;
 }

@@ -31,6 +31,8 @@ struct K1Args {
     int* strip_ctr;
     uint32_t* imgmask; // [frame][h] bit k: the 64 bytes of word k of the row in `binary` may be non-zero (image_plan.h); ww <= 32
     int delta;         // 1: `imgmask` is in force -- store only the words that are or were non-zero; 0: store every byte
+    int plane_delta;   // 1 (with delta): plane and row masks come from the same launches as the image (image_plan.h: plane_step) -- the plane's
+                       // words go by the image's mask as well, pad words are not stored, a row mask only where it changed
 };
 
 // Lane r of storer wave sw: the image's mask of row r of the wave's rows of strip L (0: no such row, or no delta launch).  The wave asks for
@@ -66,7 +68,7 @@ __device__ __forceinline__ uint32_t ws_store_strip(const K1Args& a, const int L,
     // m_new (lane r: the new mask of row r) is set on exactly one of the two row-mask paths below for every ww <= 32: in the pass itself
     // when the wave's tasks fit one pass (n_task <= 64), behind the passes otherwise.  (With RPW = 4 the second never runs: n_task = 2 ww.)
     // m_old: what the image holds in this wave's rows (lane r: row r; ws_image_mask, asked for a strip ahead).  Returns the next strip's.
-    const bool masked = a.binary && ww <= 32, delta = masked && a.delta;
+    const bool masked = a.binary && ww <= 32, delta = masked && a.delta, pdelta = delta && a.plane_delta;
     const bool my_row = lane < RPW && y0 + s0 + lane < h;
     uint32_t* const im = a.imgmask + ((int64_t)f * h + y0 + s0 + lane);
     uint32_t m_new = 0;
@@ -127,6 +129,25 @@ __device__ __forceinline__ uint32_t ws_store_strip(const K1Args& a, const int L,
             }
         }
         const int y = y0 + s;
+        // Delta stores of the plane: plane word k of a row is zero exactly when image word k is, so a word that is zero and was zero when the
+        // context wrote it last (the image's mask says so) is not stored again; nor are the pads, which the last full launch left zero.
+        bool k0 = true, k1 = true;
+        if (pdelta) { // (wave-uniform)
+            // the old masks of the wave's rows laid out as the tasks are -- bit t of mo0 / mo1: word k of the first / second row of task t's
+            // pair was non-zero -- so that they meet the ballots of the new words bit for bit (ww <= 32: one pass of at most 64 tasks)
+            static_assert(RPW / 2 * 32 <= 64, "a delta launch's tasks fit one pass");
+            uint64_t mo0 = 0, mo1 = 0;
+#pragma unroll
+            for (int i = 0; i < RPW / 2; i++) {
+                mo0 |= (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)m_old, 2 * i) << (i * ww);
+                mo1 |= (uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)m_old, 2 * i + 1) << (i * ww);
+            }
+            const uint64_t kb0 = mo0 | __builtin_amdgcn_ballot_w64(on && e0 != 0), kb1 = mo1 | __builtin_amdgcn_ballot_w64(on && e1 != 0);
+            // (the unit is ONE word: whole rows with their pads, kept wherever the row is or was non-empty, measured no faster --
+            // profiles/plane_delta_ab.txt)
+            k0 = (kb0 >> lane) & 1ull;
+            k1 = (kb1 >> lane) & 1ull;
+        }
         if (on) {
             Ew[__umul24(2 * p, ww) + k] = e0;
             Ew[__umul24(2 * p + 1, ww) + k] = e1;
@@ -135,8 +156,8 @@ __device__ __forceinline__ uint32_t ws_store_strip(const K1Args& a, const int L,
 #ifdef RMCV_K1_NOBITS
         const uint32_t po0 = OOB, po1 = OOB; // ablation build: the bit plane is not written
 #else
-        const uint32_t po0 = (on && y < h) ? (plane_base + __umul24(y + 1, a.prow) + 1u + (uint32_t)k) * 8u : OOB;
-        const uint32_t po1 = (on && y + 1 < h) ? (plane_base + __umul24(y + 2, a.prow) + 1u + (uint32_t)k) * 8u : OOB;
+        const uint32_t po0 = (on && y < h && k0) ? (plane_base + __umul24(y + 1, a.prow) + 1u + (uint32_t)k) * 8u : OOB;
+        const uint32_t po1 = (on && y + 1 < h && k1) ? (plane_base + __umul24(y + 2, a.prow) + 1u + (uint32_t)k) * 8u : OOB;
 #endif
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, e0), r_plane, po0, 0, RMCV_K1_PLAIN_PLAUX);
         __builtin_amdgcn_raw_buffer_store_b64(__builtin_bit_cast(u32x2v, e1), r_plane, po1, 0, RMCV_K1_PLAIN_PLAUX);
@@ -145,7 +166,7 @@ __device__ __forceinline__ uint32_t ws_store_strip(const K1Args& a, const int L,
         // masked write that the memory side has to merge: free while the planes of all batches in flight sit in the Infinity Cache
         // (4 x 46 MB), 15 % of the kernel's time when they do not (8 x 46 MB) -- profiles/r04f_k_binary_ws.txt
         {
-            const bool last = on && k == ww - 1;
+            const bool last = on && k == ww - 1 && !pdelta;
             const u32x4v z = {0u, 0u, 0u, 0u};
             __builtin_amdgcn_raw_buffer_store_b128(z, r_plane, last && po0 != OOB ? po0 + 8u : OOB, 0, RMCV_K1_PLAIN_PLAUX);
             __builtin_amdgcn_raw_buffer_store_b128(z, r_plane, last && po1 != OOB ? po1 + 8u : OOB, 0, RMCV_K1_PLAIN_PLAUX);
@@ -159,7 +180,7 @@ __device__ __forceinline__ uint32_t ws_store_strip(const K1Args& a, const int L,
                 const uint32_t m = (uint32_t)(b >> __umul24(pr, ww)) & (ww == 32 ? 0xFFFFFFFFu : ((1u << ww) - 1u));
                 m_new = m;
 #ifndef RMCV_K1_NOROWMASK
-                if (y0 + s0 + lane < h) a.rowmask[(int64_t)f * h + y0 + s0 + lane] = m;
+                if (y0 + s0 + lane < h && (!pdelta || m != m_old)) a.rowmask[(int64_t)f * h + y0 + s0 + lane] = m;
 #endif
             }
         }
@@ -172,7 +193,7 @@ __device__ __forceinline__ uint32_t ws_store_strip(const K1Args& a, const int L,
         if (lane < RPW && y0 + s0 + lane < h) {
             uint32_t m = 0;
             for (int k = 0; k < ww; k++) m |= (uint32_t)(Ew[__umul24(lane, ww) + k] != 0) << k;
-            a.rowmask[(int64_t)f * h + y0 + s0 + lane] = m;
+            if (!pdelta || m != m_old) a.rowmask[(int64_t)f * h + y0 + s0 + lane] = m;
             m_new = m;
         }
     }
@@ -237,7 +258,8 @@ __global__ __launch_bounds__((NL + NS) * 64, 6) void k_binary_ws(const K1Args a)
     __shared__ int s_L[4];
     // ONE of these workgroups per CU, whatever the allocator finds: two (of consecutive batches, on the two pixel streams) would take
     // every wave slot of the CU and lock the sparse kernels of the batches in flight out until a whole launch has ended.  72 VGPRs
-    // do that: 8 x 72 > 512, while 4 x 72 + the sparse kernel's 184 still fit.
+    // do that: 8 x 72 > 512, while 4 x 72 + the sparse kernel's 184 still fit.  (With the plane's delta stores the compiler takes 73,
+    // allocated as 80: 8 x 80 > 512 and 4 x 80 + 184 = 504 <= 512 hold as well.)
     asm volatile("v_mov_b32 v71, 0" ::: "v71");
     if (tid < 256) s_lut[tid] = (uint64_t)expand4(tid) | ((uint64_t)expand4(tid >> 4) << 32);
     const int xcd = blockIdx.x & 7;

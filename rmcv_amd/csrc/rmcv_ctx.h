@@ -78,6 +78,18 @@ struct rmcv_ctx {
     hipStream_t last_stream = nullptr;
     int geom_w = -1, geom_h = -1; // geometry the planes were zeroed for
     rmcv::ImageState image = rmcv::IMAGE_STATE_UNKNOWN; // what Bufs::imgmask is known to say about Bufs::binary (image_plan.h); every launch_binary keeps it
+    int plane_sync = 0;           // frames whose bit plane and row masks are in step with the image and its mask (image_plan.h: plane_step); kept beside `image`
+    // A second set of what the pixel kernel writes ("two pixel-output sets"): a pipeline's hot context takes its batches in the
+    // two sets in turn, so that a pixel launch need not wait for the sparse stage of the context's batch before.  Bufs, `image` and
+    // `plane_sync` are the CURRENT set's; `parked` holds the other one's (ctx_use_pixel_set swaps them).  n_sets 1: there is no second set.
+    struct PixelSet {
+        uint8_t* binary = nullptr;
+        uint64_t* bits = nullptr;
+        uint32_t *rowmask = nullptr, *imgmask = nullptr;
+        rmcv::ImageState image = rmcv::IMAGE_STATE_UNKNOWN;
+        int plane_sync = 0;
+    } parked;
+    int n_sets = 1, cur_set = 0;
     int order_n = -1, order_h = -1; // (n_frames, h) the frame order on the device was computed for
     hipEvent_t ev_order = nullptr; // recorded behind the work enqueued last: a call on ANOTHER stream first waits for it
     bool order_pending = false;

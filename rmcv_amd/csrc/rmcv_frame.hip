@@ -377,7 +377,7 @@ static int extract_color_body(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int
         c->test_delay_us = 0;
     }
     if (g.enhance) HIPCHK(c, launch_enhance_tables(g, b, lower_bound, s), "k_frame_sums + k_enhance_table"); // RMCV_OPT_ENHANCE: the frame is read through its table
-    HIPCHK(c, launch_binary(g, b, camp, lower_bound, morph, binary_out != nullptr, plan, s, &c->image), PIXEL_VARIANTS[geom_variant(g)].kernel);
+    HIPCHK(c, launch_binary(g, b, camp, lower_bound, morph, binary_out != nullptr, plan, s, &c->image, &c->plane_sync), PIXEL_VARIANTS[geom_variant(g)].kernel);
     if (binary_out) HIPCHK(c, hipEventRecord(ch.ev_fork, s), "image download: mark");
     // running ahead with both parameter sets known: the frame's whole sparse part is ONE kernel (the fused per-frame kernel of
     // the batch path: findContours, fits and pairing back to back), not three

@@ -52,6 +52,7 @@ extern "C" {
 int rmcv_abi_version(void) { return RMCV_ABI_VERSION; }
 int64_t rmcv_pixel_ws_launches(void) { return pixel_ws_launches(); }
 int64_t rmcv_pixel_image_delta_launches(void) { return pixel_image_delta_launches(); }
+int64_t rmcv_pixel_plane_delta_launches(void) { return pixel_plane_delta_launches(); }
 
 const char* rmcv_last_error(const rmcv_ctx* ctx) { return ctx ? ctx->err : "null context"; }
 
@@ -204,6 +205,23 @@ int ctx_wait_timeout_ms(const rmcv_ctx* c) { return c->wait_timeout_ms; }
 bool pixel_ws_full(const rmcv_ctx* c, int lower_bound, const RunPlan& plan)
 {
     return pixel_shape(pixel_batch(c->geom, c->bufs, geom_variant(c->geom), lower_bound, plan)).ws_full;
+}
+int ctx_pixel_sets(const rmcv_ctx* c) { return c->n_sets; }
+int ctx_pixel_set(const rmcv_ctx* c) { return c->cur_set; }
+void ctx_use_pixel_set(rmcv_ctx* c, int s)
+{
+    if (s == c->cur_set || s < 0 || s >= c->n_sets) return;
+    Bufs& b = c->bufs;
+    const rmcv_ctx::PixelSet mine = {b.binary, b.bits, b.rowmask, b.imgmask, c->image, c->plane_sync};
+    b.binary = c->parked.binary, b.bits = c->parked.bits, b.rowmask = c->parked.rowmask, b.imgmask = c->parked.imgmask;
+    c->image = c->parked.image, c->plane_sync = c->parked.plane_sync;
+    c->parked = mine;
+    c->cur_set = s;
+}
+bool ctx_bind_enqueues(const rmcv_ctx* c, int n_frames, int w, int h)
+{
+    const ExtentChange change = extent_change(c->geom_w, c->geom_h, c->order_n, c->order_h, w, h, n_frames);
+    return change.planes || change.order;
 }
 RunPlan ctx_plan(const rmcv_ctx* c) { return {c->pixel_shape, c->pixel_groups, c->sparse_waves, c->dense_defer ? SPARSE_SPLIT_BOTH : SPARSE_STANDARD}; }
 int ctx_enhance(const rmcv_ctx* c) { return c->input.enhance; }
@@ -379,11 +397,13 @@ static int extent_apply(rmcv_ctx* c, hipStream_t as)
     if (change.planes) {
         const size_t plane = (size_t)(c->lim.max_height + 2) * ((c->lim.max_width + 63) / 64 + 2);
         HIPCHK(c, hipMemsetAsync(c->bufs.bits, 0, (size_t)c->lim.max_frames * plane * 8, s), "memset planes");
+        if (c->n_sets > 1) HIPCHK(c, hipMemsetAsync(c->parked.bits, 0, (size_t)c->lim.max_frames * plane * 8, s), "memset planes");
         HIPCHK(c, hipMemsetAsync(c->bufs.lab, 0, (size_t)c->lim.max_frames * plane * 8, s), "memset planes");
         HIPCHK(c, hipMemsetAsync(c->bufs.neg, 0, (size_t)c->lim.max_frames * plane * 8, s), "memset planes");
         c->geom_w = g.w;
         c->geom_h = g.h;
-        c->image = IMAGE_STATE_UNKNOWN; // rows and frames of the byte image and of its mask now start elsewhere
+        c->image = c->parked.image = IMAGE_STATE_UNKNOWN; // rows and frames of the byte image and of its mask now start elsewhere
+        c->plane_sync = c->parked.plane_sync = 0;
     }
     if (change.order) {
         const int strips = (g.h + STRIP_ROWS - 1) / STRIP_ROWS;
@@ -509,7 +529,7 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
     if (st.binary) {
         c->last_camp = p->camp;
         c->last_lower_bound = p->lower_bound;
-        HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, st.image, plan, s, &c->image), PIXEL_VARIANTS[geom_variant(g)].kernel);
+        HIPCHK(c, launch_binary(g, b, p->camp, p->lower_bound, p->morph, st.image, plan, s, &c->image, &c->plane_sync), PIXEL_VARIANTS[geom_variant(g)].kernel);
     }
     if (timed) HIPCHK(c, hipEventRecord(c->ev[k++], s), "event");
     if (st.sparse) HIPCHK(c, launch_sparse(g, b, lim, *p, st.sparse_pairs, st.sparse_identity, plan, s, lean), "k_contours (fused)");
@@ -606,6 +626,25 @@ int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int 
 int ctx_check_modes(rmcv_ctx* c, bool keys, bool legacy) { return refuse(c, pixel_refusal(c->input.format, c->input.enhance, false, keys, legacy)); }
 // what binding a batch would allocate, now (a pipeline does this for every context of its ring when it is created)
 int ctx_prepare_ring(rmcv_ctx* c) { return ensure_mid(c, c->lim.max_frames); }
+int ctx_prepare_pixel_sets(rmcv_ctx* c)
+{
+    if (c->n_sets > 1) return RMCV_OK;
+    hipSetDevice(c->device);
+    c->blocking_calls++;
+    const size_t F = (size_t)c->lim.max_frames;
+    const size_t plane = (size_t)(c->lim.max_height + 2) * ((c->lim.max_width + 63) / 64 + 2);
+    rmcv_ctx::PixelSet& p = c->parked;
+    HIPCHK(c, dalloc(c, &p.binary, F * c->lim.max_width * c->lim.max_height), "hipMalloc (second pixel set)");
+    HIPCHK(c, dalloc(c, &p.bits, F * plane), "hipMalloc (second pixel set)");
+    HIPCHK(c, dalloc(c, &p.rowmask, F * c->lim.max_height), "hipMalloc (second pixel set)");
+    HIPCHK(c, dalloc(c, &p.imgmask, F * c->lim.max_height), "hipMalloc (second pixel set)");
+    // (the planes' pads must read 0 for the geometry bound, if one is: the first set's were zeroed when it was bound)
+    HIPCHK(c, hipMemset(p.bits, 0, F * plane * 8), "memset planes");
+    p.image = IMAGE_STATE_UNKNOWN;
+    p.plane_sync = 0;
+    c->n_sets = 2;
+    return RMCV_OK;
+}
 int ctx_run(rmcv_ctx* c, const rmcv_params* p, const rmcv_legacy_params* lp, int stages, hipStream_t s, const RunPlan& plan, bool* lean)
 {
     const int rc = check_bound(c, p, stages);

@@ -163,6 +163,7 @@ inline hipError_t launch(void (*kernel)(P...), dim3 grid, dim3 block, size_t lds
 
 int64_t pixel_ws_launches(); // launches of k_binary_ws by this process (rmcv_pixel_ws_launches)
 int64_t pixel_image_delta_launches(); // ... of them, those that stored the byte image in delta mode (rmcv_pixel_image_delta_launches)
+int64_t pixel_plane_delta_launches(); // ... and of those, the ones that stored the bit plane in delta mode too (rmcv_pixel_plane_delta_launches)
 // kernel launchers (each enqueues on `s` and returns the launch error)
 hipError_t launch_match(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, const rmcv_legacy_params& lp,
                         int mode, bool with_frames, bool pairs, hipStream_t s);
@@ -171,9 +172,10 @@ hipError_t launch_match(const Geom& g, const Bufs& b, const Limits& lim, const r
 hipError_t launch_sparse(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, bool pairs, bool identity, const RunPlan& plan,
                          hipStream_t s, bool* lean = nullptr);
 hipError_t launch_pnp(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s);
-// img: the context's knowledge of its byte image, read for the store mode and rewritten for what this launch leaves (image_plan.h)
+// img: the context's knowledge of its byte image, read for the store mode and rewritten for what this launch leaves (image_plan.h);
+// plane: the frames whose bit plane is in step with it (plane_step), likewise
 hipError_t launch_binary(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, const RunPlan& plan, hipStream_t s,
-                         ImageState* img);
+                         ImageState* img, int* plane);
 // the pixel stage of a Bayer batch (Geom::input_format != 0; k_binary_bayer.hip); launch_binary hands such batches to it
 hipError_t launch_binary_bayer(const Geom& g, const Bufs& b, int camp, int lower_bound, int morph, bool image, hipStream_t s);
 // exposure-adaptive detection (k_enhance.hip, k_binary_enh.hip).  launch_enhance_tables: the channel sums of the frames bound, then every
@@ -305,6 +307,14 @@ int ctx_bind_frames(rmcv_ctx* c, const void* d_frames, int n_frames, int w, int 
 int ctx_check_modes(rmcv_ctx* c, bool keys, bool legacy);
 // everything binding a full batch would allocate (the mid tier's scratch), now
 int ctx_prepare_ring(rmcv_ctx* c);
+// the second set of the pixel kernel's outputs (plane, row masks, image, image mask), allocated and zeroed now (blocking; once); then
+// ctx_pixel_sets is 2 and ctx_use_pixel_set(c, s) makes set s the one Bufs name -- between batches, by the one thread that owns the context
+int ctx_prepare_pixel_sets(rmcv_ctx* c);
+int ctx_pixel_sets(const rmcv_ctx* c);
+int ctx_pixel_set(const rmcv_ctx* c); // the current one
+void ctx_use_pixel_set(rmcv_ctx* c, int s);
+// whether binding this extent would enqueue anything (planes zeroed, frame order recomputed: extent_change)
+bool ctx_bind_enqueues(const rmcv_ctx* c, int n_frames, int w, int h);
 // allocations, host-side synchronisations and blocking copies this context has made while binding geometries
 uint64_t ctx_blocking_calls(const rmcv_ctx* c);
 int ctx_wait_timeout_ms(const rmcv_ctx* c);

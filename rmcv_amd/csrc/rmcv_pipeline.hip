@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "batch_plan.h"
+#include "pixel_sets_plan.h"
 #include "rmcv_internal.h"
 
 using namespace rmcv;
@@ -37,6 +38,7 @@ struct Slot {
     uint64_t ticket = 0;          // ticket + 1 of the batch that lives in the slot (0: none yet)
     hipStream_t stream = nullptr; // the stream the slot's record was finished on
     int frames = 0, ctx = 0;      // of its batch: frames, and the context it ran in
+    int set = 0;                  // ... and the pixel-output set of that context it used (pixel_sets_plan.h)
     bool lean = false;            // its batch's sparse stage ran the lean build (every frame of its record reports the mid tier)
     // debug views (rmcv_pipeline_set_views): the slot's buffer, and what its batch rendered into it (view_n == 0: nothing)
     uint8_t* d_views = nullptr;
@@ -66,6 +68,9 @@ struct rmcv_pipeline {
     RecordLayout rec{};
     std::vector<rmcv_ctx*> ring;
     std::vector<int> ctx_last;          // per CONTEXT: the slot of its last batch (-1: none)
+    // per context and pixel-output set (2 j + s): recorded beside ev_done of every batch that used the set.  An event of the set's own: the
+    // slot of the set's last batch may have a later batch in it by the time the set comes round again (2 hot > depth)
+    std::vector<hipEvent_t> ev_set;
     std::vector<Slot> slots;
     std::vector<hipStream_t> pix, sp, dn; // pixel streams, sparse streams, streams of the dense frames' second launch
     uint64_t next_ticket = 0, collected = 0;
@@ -155,6 +160,16 @@ static int cfail(rmcv_pipeline* pl, rmcv_ctx* c, int rc)
     return rc;
 }
 
+// the second pixel-output set (pixel_sets_plan.h) for the first n contexts of the ring, where the rotation can run at all: allocated and
+// zeroed NOW -- rmcv_pipeline_submit never allocates; a context without one takes every batch in set 0 and keeps the old wait
+static int prepare_pixel_sets(rmcv_pipeline* pl, int n)
+{
+    if (pl->cfg.host_results != 1 || pl->cfg.sparse_waves != 4) return RMCV_OK;
+    for (int j = 0; j < n && j < (int)pl->ring.size(); j++)
+        if (const int rc = ctx_prepare_pixel_sets(pl->ring[(size_t)j])) return cfail(pl, pl->ring[(size_t)j], rc);
+    return RMCV_OK;
+}
+
 // a wait with the pipeline's deadline (wait: wait_event_deadline / wait_stream_deadline): RMCV_ERR_TIMEOUT names the enqueue made last
 template <class Wait, class What> static int pwait(rmcv_pipeline* pl, Wait wait, What on, const char* what)
 {
@@ -242,6 +257,7 @@ void rmcv_pipeline_destroy(rmcv_pipeline* pl)
     if (pl->views.d_frames) hipFree(pl->views.d_frames);
     if (pl->harv.d_labels) hipFree(pl->harv.d_labels);
     if (pl->ev_gather) hipEventDestroy(pl->ev_gather);
+    for (hipEvent_t ev : pl->ev_set) if (ev) hipEventDestroy(ev);
     for (auto streams : {&pl->pix, &pl->sp, &pl->dn})
         for (auto s : *streams) if (s) hipStreamDestroy(s);
     delete pl;
@@ -299,7 +315,11 @@ int rmcv_pipeline_create(int device, const rmcv_limits* limits, const rmcv_pipel
     }
     if (e == hipSuccess) e = hipEventCreateWithFlags(&pl->ev_gather, hipEventDisableTiming);
     pl->ctx_last.assign((size_t)d.depth, -1);
+    pl->ev_set.assign(2 * (size_t)d.depth, nullptr);
+    for (hipEvent_t& ev : pl->ev_set) if (e == hipSuccess) e = hipEventCreateWithFlags(&ev, hipEventDisableTiming);
     pl->hot = hot_for(pl->hot_cfg, d.depth, pl->lim.max_frames, pl->lim.max_width, pl->lim.max_height); // (derived again for the geometry of every submit)
+    // (the contexts the rotation reaches at the limits' geometry; a smaller one may reach further: those contexts keep one set)
+    if (e == hipSuccess && prepare_pixel_sets(pl, pl->hot) != RMCV_OK) e = hipErrorOutOfMemory;
     pl->wait_timeout_ms = ctx_wait_timeout_ms(pl->ring[0]);
     if (e != hipSuccess) {
         fprintf(stderr, "rmcv_pipeline_create: %s\n", hipGetErrorString(e));
@@ -350,6 +370,8 @@ int rmcv_pipeline_set_hot_contexts(rmcv_pipeline* pl, int n)
     if (!pl) return RMCV_ERR_BAD_ARG;
     if (n <= 0) { pl->hot = 0; pl->hot_cfg = -1; return RMCV_OK; }
     if (const char* no = hot_contexts_refusal(n, pl->cfg)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
+    hipSetDevice(pl->device);
+    if (const int rc = prepare_pixel_sets(pl, n)) return rc;
     pl->hot = pl->hot_cfg = n;
     return RMCV_OK;
 }
@@ -481,6 +503,7 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
     }
     // the context's buffers are free from here on: the next pixel kernel of this slot does not wait for the hook
     PCHK(pl, hipEventRecord(S.ev_done, T), "pipeline: mark the slot");
+    PCHK(pl, hipEventRecord(pl->ev_set[2 * (size_t)S.ctx + (size_t)S.set], T), "pipeline: mark the pixel-output set");
     S.ticket = P.t + 1;
     S.frames = q.n_frames;
     S.lean = lean;
@@ -570,16 +593,27 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
     if ((rc = ctx_check_stages(c, q.p, stages))) return cfail(pl, c, rc);
     const RunPlan plan = fp.plan(ctx_plan(c));
     hipStream_t A = pl->pix[at.pixel], B = pl->sp[at.sparse];
+    // the context's pixel-output set the batch takes, and what its streams wait for (pixel_sets_plan.h)
+    const int set = pixel_set_for(fp.fast, pl->hot_seq, pl->hot, ctx_pixel_sets(c));
+    const SetWaits sw = pixel_set_waits(fp.fast, ctx_pixel_sets(c), ctx_bind_enqueues(c, q.n_frames, q.d_origins ? q.win_w : q.w, q.d_origins ? q.win_h : q.h));
     // ---- waits first: stream A is behind everything that still uses the slot and the context when the binding below enqueues on it.
     // (Nothing of the pipeline's own state moves before the batch has been accepted: an error return leaves tickets, rotation and
     // context ownership as they were; the waits already enqueued on A are harmless.)
     // the slot's context buffers are free once its previous list is compacted
     if (used) PCHK(pl, hipStreamWaitEvent(A, S.ev_done, 0), "pipeline: wait for the slot");
     // the context's last batch (another slot's, when the hot contexts take turns): its sparse stage or its compaction (batch_plan.h: waits_for_free)
+    // -- or, with two pixel-output sets, the last batch in the SAME set, and the pixel kernel alone of the context's last batch
     if (pl->ctx_last[fp.j] >= 0 && pl->ctx_last[fp.j] != (int)k) {
         const Slot& last = pl->slots[(size_t)pl->ctx_last[fp.j]];
-        PCHK(pl, hipStreamWaitEvent(A, waits_for_free(last.stream, B) ? last.ev_free : last.ev_done, 0), "pipeline: wait for the context");
+        if (sw.pixel_ctx_last) PCHK(pl, hipStreamWaitEvent(A, waits_for_free(last.stream, B) ? last.ev_free : last.ev_done, 0), "pipeline: wait for the context");
+        if (sw.pixel_ctx_bin) PCHK(pl, hipStreamWaitEvent(A, last.ev_bin, 0), "pipeline: wait for the context's pixel kernel");
     }
+    // (an event that has never been recorded is not waited for)
+    if (sw.pixel_set_last) PCHK(pl, hipStreamWaitEvent(A, pl->ev_set[2 * fp.j + (size_t)set], 0), "pipeline: wait for the context's pixel-output set");
+    // the sparse stage shares the context's one set of tables with the context's last batch: its stream waits, the pixel stream does not
+    // (enqueued here, in front of the chain to the pixel kernel: the batch's sparse stage is enqueued by the next call)
+    if (sw.sparse_ctx_last && pl->ctx_last[fp.j] >= 0 && pl->ctx_last[fp.j] != (int)k)
+        PCHK(pl, hipStreamWaitEvent(B, pl->slots[(size_t)pl->ctx_last[fp.j]].ev_done, 0), "pipeline: the sparse stream waits for the context");
     // ---- bind: a new geometry's work (planes zeroed, frame order) is ENQUEUED on A, nothing blocks
     rc = ctx_bind_frames(c, q.d_frames, q.n_frames, q.w, q.h, q.stride, q.frame_pitch, A, q.d_origins, q.win_w, q.win_h, q.d_camps, q.d_lower_bounds);
     if (rc) return cfail(pl, c, rc);
@@ -609,15 +643,21 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
         rc = ctx_attitude(c, q.trk, q.d_packets, A);
         if (rc) return cfail(pl, c, rc);
     }
+    // (the binding is the same for both sets; a refused run leaves the context with the set of its last batch, which the getters read)
+    const int set_before = ctx_pixel_set(c);
+    ctx_use_pixel_set(c, set);
     rc = ctx_run(c, q.p, nullptr, pixel, A, plan);
-    if (rc) return cfail(pl, c, rc);
+    if (rc) {
+        ctx_use_pixel_set(c, set_before);
+        return cfail(pl, c, rc);
+    }
     pl->last_what = PIXEL_VARIANTS[ctx_pixel_variant(c)].step;
     // ---- accepted: the pipeline's state moves
     pl->was_cold = hb.cold;
     if (fp.fast) { pl->hot_seq++; pl->hot_batches++; }
     if (fp.heavy) pl->heavy_batches++;
     pl->ctx_last[fp.j] = (int)k;
-    S.ctx = (int)fp.j;
+    S.ctx = (int)fp.j, S.set = set;
     PCHK(pl, hipEventRecord(S.ev_bin, A), "pipeline: mark the pixel kernel");
     PCHK(pl, hipStreamWaitEvent(B, S.ev_bin, 0), "pipeline: chain the sparse stages");
     // the recorder: the chosen frames as delivered, and the effective keys and origins the pixel stage's prologue has just written, packed on
