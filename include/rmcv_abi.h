@@ -1427,7 +1427,7 @@ typedef struct rmcv_dataset rmcv_dataset;
 /* on the context's device; the context outlives the dataset (its deadline is the dataset's).  RMCV_ERR_BAD_ARG: capacity_rows < 1 */
 int  rmcv_dataset_create(rmcv_ctx* ctx, int capacity_rows, rmcv_dataset** out);
 void rmcv_dataset_destroy(rmcv_dataset* ds); /* waits for its last append */
-int  rmcv_dataset_clear(rmcv_dataset* ds);   /* waits for its last append; count = dropped = 0 */
+int  rmcv_dataset_clear(rmcv_dataset* ds);   /* waits for its last append; count = dropped = 0 (and the novelty state: near, pushed, rings) */
 const char* rmcv_dataset_last_error(const rmcv_dataset* ds);
 /* waits for the last append with the context's deadline (RMCV_ERR_TIMEOUT); either pointer may be NULL */
 int  rmcv_dataset_count(rmcv_dataset* ds, int32_t* rows, int64_t* dropped);
@@ -1463,6 +1463,46 @@ int  rmcv_svm_train_dataset(rmcv_ctx* ctx, rmcv_dataset* ds, const int32_t* rows
                             float* weights_out, double* rho_out, int32_t* labels_out, int32_t* n_class_out, rmcv_svm_train_report* report);
 /* rmcv_svm_predict on rows of the dataset, in place (the validation pass of optimizer.cpp:27-40 without moving rows) */
 int  rmcv_svm_predict_dataset(rmcv_ctx* ctx, rmcv_dataset* ds, const int32_t* rows, int n, int32_t* identity_out);
+
+/* ---- novelty: a dataset that skips near-duplicates of the icons it kept last from the same stream -------------------
+ * Consecutive frames of a stream show the same plate from almost the same pose; a dataset with novelty on remembers, per stream (= frame
+ * index of every append), the last `ring_rows` rows it kept and does not keep a candidate whose sum of absolute byte differences to one
+ * of them is <= max_sad.  The rule, in full (rmcv_amd/csrc/device_novelty.h is its one source for host and device):
+ *   - the candidates of an append are exactly the rows it would keep with novelty off, taken frame by frame in armour order;
+ *   - d = min of rmcv_icon_sad(row, r) over the rows r the frame's ring holds at that moment, rows pushed by earlier candidates of the same
+ *     frame in the same append included; an empty ring gives no d and the candidate is kept;
+ *   - d <= max_sad: the candidate is near -- not kept, near += 1; otherwise it is kept and pushed to the ring (the row pushed as number k
+ *     lies at position k % ring_rows), whether or not the dataset has a slot left for it;
+ *   - kept rows are numbered, placed, dropped and described exactly as with novelty off.
+ * Novelty is a property of the dataset, not a flag: every append to it (rmcv_batch_harvest*, a pipeline's, rmcv_dataset_append_rows) is
+ * filtered.  With ring_rows == 0 (the default) an append enqueues exactly what it did before. */
+#define RMCV_ICON_SAD_MAX 306000  /* 1200 * 255 */
+#define RMCV_HARVEST_RING_MAX 8
+int32_t rmcv_icon_sad(const uint8_t* a, const uint8_t* b); /* host; two rows of 1200 bytes */
+/* waits for the last append; allocates the rings on first use; sets ring_rows and max_sad and empties every ring (pushed = 0, every
+ * position zero; `near` is kept).  ring_rows 0: off.  RMCV_ERR_BAD_ARG with a message: ring_rows outside 0 .. RMCV_HARVEST_RING_MAX,
+ * max_sad outside 0 .. RMCV_ICON_SAD_MAX.  With a pipeline appending to the dataset, call it when every submitted ticket has been waited
+ * for (the newest batch's append is enqueued by the call that waits for it), as rmcv_dataset_clear. */
+int  rmcv_dataset_set_novelty(rmcv_dataset* ds, int ring_rows, int32_t max_sad);
+/* waits like rmcv_dataset_count; any pointer may be NULL.  rmcv_dataset_clear additionally zeroes near, every pushed and every ring. */
+int  rmcv_dataset_novelty(rmcv_dataset* ds, int* ring_rows, int32_t* max_sad, int64_t* near);
+/* the state as it lies: rows_out u8 [n_streams][ring_rows][1200] (positions not yet written read as zero), pushed_out int64 [n_streams];
+ * either may be NULL.  RMCV_ERR_BAD_ARG: streams outside 0 .. the creating context's max_frames - 1. */
+int  rmcv_dataset_get_rings(rmcv_dataset* ds, int first_stream, int n_streams, uint8_t* rows_out, int64_t* pushed_out);
+/* append rows the caller already has (icons of an earlier session, seeded rows): the same rule, in the same order as any other append, on
+ * the creating context's stream.  rows u8 [sum n_rows][1200], stream-major; stream s gives n_rows[s] candidates in order, none when
+ * labels[s] == RMCV_HARVEST_SKIP (its rows are stepped over).  Metadata: frame = s, armour = the index within the stream, label = labels[s],
+ * identity = INT32_MIN, window origin 0, icon quadrilateral zeros.  Waits for the dataset's last append, then copies the host tables before it
+ * returns; the append itself is asynchronous.  RMCV_ERR_BAD_ARG with a message, before anything is enqueued: a null pointer, n_streams
+ * outside 1 .. the creating context's max_frames, an n_rows[s] outside 0 .. its max_armours. */
+int  rmcv_dataset_append_rows(rmcv_dataset* ds, const uint8_t* rows, const int32_t* n_rows, const int32_t* labels, int n_streams, uint64_t tag);
+/* the rule on the host (no context, no device) over rows the caller has, laid out as for rmcv_dataset_append_rows.  rings u8
+ * [n_streams][ring_rows][1200] and pushed int64 [n_streams]: in and out (NULL is allowed with ring_rows == 0); keep_out u8 [sum n_rows]: 1
+ * kept, 0 near or skipped; min_sad_out (nullable) int32 [sum n_rows]: each candidate's d, INT32_MAX where the ring was empty, the stream
+ * skipped or ring_rows == 0; *near_out (nullable): the near candidates of this call.  RMCV_ERR_BAD_ARG: null tables, n_streams < 0, a negative
+ * n_rows[s], arguments rmcv_dataset_set_novelty refuses. */
+int  rmcv_harvest_novel_host(const uint8_t* rows, const int32_t* n_rows, const int32_t* labels, int n_streams, int ring_rows, int32_t max_sad,
+                             uint8_t* rings, int64_t* pushed, uint8_t* keep_out, int32_t* min_sad_out, int64_t* near_out);
 
 /* ---- device memory for hosts without HIP headers (tools/pipeline_bench.c): frames resident in HBM ------------------------------- */
 int  rmcv_device_alloc(int device, int64_t bytes, void** d_ptr);

@@ -17,8 +17,8 @@ from .api import Context, debug_view
 from .pipeline import Pipeline
 from .recorder import LoopRecord, Recorder, Session, loop_bound, loop_field_at, loop_trigger, pack, pack_bound, unpack
 from . import svm
-from .abi import HARVEST_META, HARVEST_MISSES, HARVEST_SKIP
-from .harvest import DeviceDataset, harvest_plan
+from .abi import HARVEST_META, HARVEST_MISSES, HARVEST_RING_MAX, HARVEST_SKIP, ICON_SAD_MAX
+from .harvest import DeviceDataset, harvest_novel, harvest_plan, icon_sad
 from .abi import (LOOP_TRUNCATED, TRIG_AIM_JUMP, TRIG_ALL, TRIG_FRAME_STATUS, TRIG_NO_ARMOURS, TRIG_NO_SOLUTION, TRIG_PACKET_ERROR, TRIG_TARGET_LOST, TRIG_TARGET_SWITCH,
                   TRIG_TRACK_DROPPED, TRIG_TRACKER_OVF, LoopState, TriggerConfig, TriggerInfo)
 from .tracker import TRACKER_OVF, AimConfig, AttitudeConfig, Tracker, TrackerConfig, default_aim_config, default_attitude_config, default_tracker_config

@@ -75,6 +75,7 @@ VIEW_BLOBS, VIEW_NEGATIVES, VIEW_ARMOURS, VIEW_ALL = 1, 2, 4, 7  # RMCV_VIEW_*: 
 FRAME_OVF_CONTOURS, FRAME_OVF_POINTS, FRAME_OVF_BLOBS, FRAME_OVF_ARMOURS, FRAME_SLOW_PATH, FRAME_MID_PATH = 1, 2, 4, 8, 16, 64
 # dataset harvest: a label that keeps a frame out, the flag that keeps only the model's misses, a row's 64-byte metadata
 HARVEST_SKIP, HARVEST_MISSES = -2**31, 1
+ICON_SAD_MAX, HARVEST_RING_MAX = 306000, 8   # novelty: the largest distance of two icon rows, the deepest ring per stream
 HARVEST_META = np.dtype([("tag", "<u8"), ("frame", "<i4"), ("armour", "<i4"), ("label", "<i4"), ("identity", "<i4"), ("win_x", "<i4"), ("win_y", "<i4"),
                          ("icon", "<f4", (4, 2))])
 
@@ -117,6 +118,7 @@ EXPORTS = [
     "rmcv_svm_train_defaults", "rmcv_svm_train", "rmcv_svm_train_host", "rmcv_svm_gram", "rmcv_svm_gram_host", "rmcv_svm_predict", "rmcv_svm_predict_host",
     "rmcv_dataset_create", "rmcv_dataset_destroy", "rmcv_dataset_clear", "rmcv_dataset_last_error", "rmcv_dataset_count", "rmcv_dataset_get", "rmcv_dataset_device",
     "rmcv_batch_harvest", "rmcv_batch_harvest_device", "rmcv_harvest_plan_host", "rmcv_pipeline_set_harvest", "rmcv_svm_train_dataset", "rmcv_svm_predict_dataset",
+    "rmcv_icon_sad", "rmcv_dataset_set_novelty", "rmcv_dataset_novelty", "rmcv_dataset_get_rings", "rmcv_dataset_append_rows", "rmcv_harvest_novel_host",
 ]
 
 
@@ -501,6 +503,15 @@ def load(path):
         L.rmcv_pipeline_set_harvest.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int]
         L.rmcv_svm_train_dataset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rmcv_svm_predict_dataset.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    if hasattr(L, "rmcv_dataset_set_novelty"):  # (builds from before the harvest's novelty rings stay loadable for A/B runs)
+        L.rmcv_icon_sad.restype = C.c_int32
+        L.rmcv_icon_sad.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_dataset_set_novelty.argtypes = [C.c_void_p, C.c_int, C.c_int32]
+        L.rmcv_dataset_novelty.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_dataset_get_rings.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.rmcv_dataset_append_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64]
+        L.rmcv_harvest_novel_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L

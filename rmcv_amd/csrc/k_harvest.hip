@@ -11,6 +11,8 @@
 //                    function classify_frame computes it with) into rows[slot] and fills meta[slot].  The loop is bounded by the list's
 //                    length: no inter-workgroup wait, no spin.  The armour table is only read.
 //   k_harvest_gather rows[idx[k]] -> out[k], meta[idx[k]].label -> responses[k]: a training or validation subset, contiguous.
+// A dataset with novelty on (k_novelty.hip) gets k_harvest_novel in front and k_harvest_plan_novel in k_harvest_plan's place;
+// k_harvest_rows then runs over the shorter list as ever.
 #include "device_classify.h"
 #include "device_harvest.h"
 
@@ -20,47 +22,11 @@ static_assert(sizeof(rmcv_harvest_meta) == 64, "rmcv_harvest_meta is 64 bytes");
 static_assert(sizeof(HarvestItem) == sizeof(rmcv_harvest_item), "the work list's entry is the ABI's item");
 static_assert(NFEAT == RMCV_SVM_FEATURES && NFEAT % 16 == 0, "a row is 75 uint4");
 
-__global__ __launch_bounds__(256) void k_harvest_plan(const int32_t* __restrict__ n_armours, const int32_t* __restrict__ status,
-                                                     const int32_t* __restrict__ labels, const int32_t* __restrict__ identity, int n_frames,
-                                                     int max_armours, int flags, int32_t capacity, HarvestCounters* __restrict__ ctr,
-                                                     HarvestItem* __restrict__ list)
-{
-    __shared__ int s_carry[4];
-    const int t = threadIdx.x, lane = t & 63, wave = t >> 6;
-    const int per = (n_frames + 255) / 256;
-    const int f0 = t * per, f1 = f0 + per < n_frames ? f0 + per : n_frames;
-    const int32_t count = ctr->count; // (read by every thread before thread 0 rewrites it: the barriers below lie between)
-    int mine = 0;
-    for (int f = f0; f < f1; f++)
-        mine += harvest_frame_kept(n_armours[f], max_armours, status[f], labels[f], flags, identity ? identity + (int64_t)f * max_armours : nullptr);
-    // inclusive scan of the wave's 64 totals, then the waves' carries through LDS
-    int incl = mine;
-#pragma unroll
-    for (int d = 1; d < 64; d <<= 1) {
-        const int v = __shfl_up(incl, d);
-        if (lane >= d) incl += v;
-    }
-    if (lane == 63) s_carry[wave] = incl;
-    __syncthreads();
-    int base = 0, total = 0;
-#pragma unroll
-    for (int q = 0; q < 4; q++) {
-        if (q < wave) base += s_carry[q];
-        total += s_carry[q];
-    }
-    int64_t k0 = (int64_t)base + incl - mine;
-    for (int f = f0; f < f1; f++)
-        k0 += harvest_frame_emit(f, n_armours[f], max_armours, status[f], labels[f], flags, identity ? identity + (int64_t)f * max_armours : nullptr, k0,
-                                 count, capacity, list);
-    __syncthreads();
-    if (t == 0) {
-        int32_t now;
-        int64_t drop;
-        ctr->n_list = harvest_finish(count, capacity, total, &now, &drop);
-        ctr->count = now;
-        ctr->dropped += drop;
-    }
-}
+// k_harvest_plan: the body lives in k_harvest_plan.inc and is compiled twice -- here as it always was, and in k_novelty.hip with the keep bytes
+// of k_harvest_novel as a further input
+#define HP_KERNEL k_harvest_plan
+#include "k_harvest_plan.inc"
+#undef HP_KERNEL
 
 // what k_harvest_rows needs of the batch and the dataset
 struct HarvestRowsArgs {
@@ -133,12 +99,21 @@ __global__ __launch_bounds__(128) void k_harvest_gather(const uint8_t* __restric
     if (responses && threadIdx.x == 0) responses[k] = ok ? meta[slot].label : 0;
 }
 
+hipError_t launch_harvest_plan(const int32_t* n_armours, const int32_t* status, const int32_t* d_labels, const int32_t* ident, int n_frames, int max_armours,
+                               int flags, const DatasetView& d, hipStream_t s)
+{
+    if (d.ring_rows > 0) return launch_harvest_plan_novel(n_armours, status, d_labels, ident, n_frames, max_armours, flags, d, s);
+    return launch(k_harvest_plan, dim3(1), dim3(256), 0, s, n_armours, status, d_labels, ident, n_frames, max_armours, flags, d.capacity, d.ctr, d.list);
+}
+
 hipError_t launch_harvest(const Geom& g, const Bufs& b, const Limits& lim, const DatasetView& d, const int32_t* d_labels, int flags, bool identity,
                           uint64_t tag, hipStream_t s)
 {
     const int32_t* ident = identity ? b.identity : nullptr;
-    hipError_t e = launch(k_harvest_plan, dim3(1), dim3(256), 0, s, b.n_armours, b.status, d_labels, ident, g.n_frames, lim.max_armours, flags, d.capacity,
-                          d.ctr, d.list);
+    hipError_t e = hipSuccess;
+    // novelty on: the keep bytes first; the plan then takes them in, and the rows kernels run over its list as ever (a kept row is computed twice)
+    if (d.ring_rows > 0) e = launch_harvest_novel(g, b, lim, nullptr, d, d_labels, flags, ident, s);
+    if (e == hipSuccess) e = launch_harvest_plan(b.n_armours, b.status, d_labels, ident, g.n_frames, lim.max_armours, flags, d, s);
     if (e != hipSuccess) return e;
     HarvestRowsArgs H;
     H.frames = b.frames, H.frame_pitch = g.frame_pitch, H.stride = g.stride, H.w = g.w, H.h = g.h, H.max_armours = lim.max_armours;

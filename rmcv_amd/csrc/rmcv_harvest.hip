@@ -18,6 +18,10 @@ struct rmcv_dataset {
     hipStream_t last_stream = nullptr;
     char err[256] = {0};
     std::vector<void*> allocs;
+    // what rmcv_dataset_append_rows stages its host tables in (free once the last append has finished: it waits for that first)
+    int32_t* src_tables = nullptr; // [4][label_cap]: n_rows, row_off, zeros, (spare)
+    uint8_t* src_rows = nullptr;
+    size_t src_rows_bytes = 0;
 };
 
 static int dfail(rmcv_dataset* d, int code, const char* what, hipError_t e = hipSuccess)
@@ -155,11 +159,137 @@ void rmcv_dataset_destroy(rmcv_dataset* d)
 
 const char* rmcv_dataset_last_error(const rmcv_dataset* d) { return d ? d->err : "null dataset"; }
 
+// the novelty state emptied: every pushed, every ring position (and near, on a clear)
+static int novelty_reset(rmcv_dataset* d, bool near_too)
+{
+    if (!d->v.rings) return RMCV_OK;
+    DCHK(d, hipMemset(d->v.rings, 0, (size_t)d->v.label_cap * RMCV_HARVEST_RING_MAX * RMCV_SVM_FEATURES), "emptying the dataset's rings");
+    DCHK(d, hipMemset(d->v.pushed, 0, (size_t)d->v.label_cap * 8), "emptying the dataset's rings");
+    if (near_too) DCHK(d, hipMemset(d->v.near, 0, 8), "clearing the dataset's near counter");
+    return RMCV_OK;
+}
+
 int rmcv_dataset_clear(rmcv_dataset* d)
 {
     if (!d) return RMCV_ERR_BAD_ARG;
     if (const int rc = ready(d)) return rc;
     DCHK(d, hipMemset(d->v.ctr, 0, sizeof(HarvestCounters)), "clearing the dataset's counters");
+    return novelty_reset(d, true);
+}
+
+int32_t rmcv_icon_sad(const uint8_t* a, const uint8_t* b) { return a && b ? icon_sad(a, b) : -1; }
+
+int rmcv_dataset_set_novelty(rmcv_dataset* d, int ring_rows, int32_t max_sad)
+{
+    if (!d) return RMCV_ERR_BAD_ARG;
+    if (const char* no = novelty_refusal(ring_rows, max_sad)) return dfail(d, RMCV_ERR_BAD_ARG, no);
+    if (const int rc = ready(d)) return rc;
+    if (ring_rows > 0 && !d->v.rings) { // first use: rings of the largest depth, so that a later depth needs no memory
+        const size_t n = (size_t)d->v.label_cap;
+        d->v.keep_armours = d->owner->lim.max_armours;
+        uint8_t *rings = nullptr, *keep = nullptr;
+        int64_t* state = nullptr; // near, then pushed[label_cap]
+        hipError_t e = hipMalloc((void**)&rings, n * RMCV_HARVEST_RING_MAX * RMCV_SVM_FEATURES);
+        if (e == hipSuccess) e = hipMalloc((void**)&keep, n * (size_t)d->v.keep_armours);
+        if (e == hipSuccess) e = hipMalloc((void**)&state, (n + 1) * 8);
+        if (e == hipSuccess) e = hipMemset(state, 0, (n + 1) * 8);
+        if (e != hipSuccess) {
+            hipFree(rings), hipFree(keep), hipFree(state);
+            return dfail(d, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_dataset_set_novelty", e);
+        }
+        d->allocs.push_back(rings), d->allocs.push_back(keep), d->allocs.push_back(state);
+        d->v.rings = rings, d->v.keep = keep, d->v.near = reinterpret_cast<unsigned long long*>(state), d->v.pushed = state + 1;
+    }
+    if (const int rc = novelty_reset(d, false)) return rc;
+    d->v.ring_rows = ring_rows, d->v.max_sad = max_sad;
+    return RMCV_OK;
+}
+
+int rmcv_dataset_novelty(rmcv_dataset* d, int* ring_rows, int32_t* max_sad, int64_t* near)
+{
+    if (!d) return RMCV_ERR_BAD_ARG;
+    if (const int rc = ready(d)) return rc;
+    if (ring_rows) *ring_rows = d->v.ring_rows;
+    if (max_sad) *max_sad = d->v.max_sad;
+    if (near) {
+        *near = 0;
+        if (d->v.near) DCHK(d, hipMemcpy(near, d->v.near, 8, hipMemcpyDeviceToHost), "D2H dataset near counter");
+    }
+    return RMCV_OK;
+}
+
+int rmcv_dataset_get_rings(rmcv_dataset* d, int first_stream, int n_streams, uint8_t* rows_out, int64_t* pushed_out)
+{
+    if (!d) return RMCV_ERR_BAD_ARG;
+    if (const int rc = ready(d)) return rc;
+    if (first_stream < 0 || n_streams < 0 || (int64_t)first_stream + n_streams > d->v.label_cap)
+        return dfail(d, RMCV_ERR_BAD_ARG, "rmcv_dataset_get_rings: streams outside 0 .. max_frames - 1");
+    if (n_streams == 0) return RMCV_OK;
+    const size_t per = (size_t)d->v.ring_rows * RMCV_SVM_FEATURES;
+    if (pushed_out) {
+        if (d->v.pushed) DCHK(d, hipMemcpy(pushed_out, d->v.pushed + first_stream, (size_t)n_streams * 8, hipMemcpyDeviceToHost), "D2H dataset pushed");
+        else memset(pushed_out, 0, (size_t)n_streams * 8);
+    }
+    if (rows_out && per) DCHK(d, hipMemcpy(rows_out, d->v.rings + first_stream * per, n_streams * per, hipMemcpyDeviceToHost), "D2H dataset rings");
+    return RMCV_OK;
+}
+
+int rmcv_dataset_append_rows(rmcv_dataset* d, const uint8_t* rows, const int32_t* n_rows, const int32_t* labels, int n_streams, uint64_t tag)
+{
+    if (!d) return RMCV_ERR_BAD_ARG;
+    rmcv_ctx* c = d->owner;
+    const int cap = d->v.label_cap;
+    if (const char* no = novelty_rows_refusal(rows, n_rows, labels, n_streams, cap, c->lim.max_armours)) return dfail(d, RMCV_ERR_BAD_ARG, no);
+    if (const int rc = ready(d)) return rc; // the staged tables of the previous call are free from here on
+    std::vector<int32_t> tables((size_t)3 * cap, 0); // n_rows, row_off, zeros
+    int64_t total = 0;
+    for (int s = 0; s < n_streams; s++) {
+        tables[s] = n_rows[s];
+        tables[(size_t)cap + s] = (int32_t)total;
+        total += n_rows[s];
+    }
+    const size_t bytes = (size_t)total * RMCV_SVM_FEATURES;
+    if (!d->src_tables) {
+        hipError_t e = hipMalloc((void**)&d->src_tables, (size_t)3 * cap * 4);
+        if (e != hipSuccess) return dfail(d, RMCV_ERR_NOMEM, "rmcv_dataset_append_rows: tables", e);
+        d->allocs.push_back(d->src_tables);
+    }
+    if (bytes > d->src_rows_bytes) {
+        uint8_t* p = nullptr;
+        hipError_t e = hipMalloc((void**)&p, bytes);
+        if (e != hipSuccess) return dfail(d, RMCV_ERR_NOMEM, "rmcv_dataset_append_rows: rows", e);
+        for (void*& q : d->allocs)
+            if (q == d->src_rows && q) { hipFree(q); q = nullptr; } // (hipFree(nullptr) at the end is harmless)
+        d->allocs.push_back(p);
+        d->src_rows = p, d->src_rows_bytes = bytes;
+    }
+    DCHK(d, hipMemcpy(d->src_tables, tables.data(), tables.size() * 4, hipMemcpyHostToDevice), "H2D append_rows tables");
+    DCHK(d, hipMemcpy(d->v.labels, labels, (size_t)n_streams * 4, hipMemcpyHostToDevice), "H2D append_rows labels");
+    if (bytes) DCHK(d, hipMemcpy(d->src_rows, rows, bytes, hipMemcpyHostToDevice), "H2D append_rows rows");
+    DatasetRowsSource src;
+    src.rows = d->src_rows, src.n_rows = d->src_tables, src.row_off = d->src_tables + cap, src.zeros = d->src_tables + 2 * (size_t)cap, src.labels = d->v.labels;
+    src.n_streams = n_streams, src.max_armours = c->lim.max_armours;
+    hipStream_t s = c->stream;
+    DCHK(d, dataset_order_begin(d, s), "append_rows: wait for the dataset's previous append");
+    DCHK(d, launch_harvest_rows_source(src, d->v, c->geom.n_cu, tag, s), "k_harvest_novel + k_harvest_plan + k_harvest_copy_rows");
+    DCHK(d, dataset_order_end(d, s), "append_rows: record the append");
+    return RMCV_OK;
+}
+
+int rmcv_harvest_novel_host(const uint8_t* rows, const int32_t* n_rows, const int32_t* labels, int n_streams, int ring_rows, int32_t max_sad, uint8_t* rings,
+                            int64_t* pushed, uint8_t* keep_out, int32_t* min_sad_out, int64_t* near_out)
+{
+    if (n_streams < 0 || novelty_refusal(ring_rows, max_sad)) return RMCV_ERR_BAD_ARG;
+    if (n_streams && (!n_rows || !labels)) return RMCV_ERR_BAD_ARG;
+    if (n_streams && ring_rows && (!rings || !pushed)) return RMCV_ERR_BAD_ARG;
+    int64_t total = 0;
+    for (int s = 0; s < n_streams; s++) {
+        if (n_rows[s] < 0) return RMCV_ERR_BAD_ARG;
+        total += n_rows[s];
+    }
+    if (total && (!rows || !keep_out)) return RMCV_ERR_BAD_ARG;
+    const int64_t near = novelty_seq(rows, n_rows, labels, n_streams, ring_rows, max_sad, rings, pushed, keep_out, min_sad_out);
+    if (near_out) *near_out = near;
     return RMCV_OK;
 }
 

@@ -1256,11 +1256,14 @@ int ctx_attitude(rmcv_ctx* c, rmcv_tracker* trk, const void* d_packets, hipStrea
 
 // the dataset harvest behind the bound batch's last run: every check before the first enqueue; never synchronises.  An append
 // is a step of the dataset's: behind its previous one, whatever stream that ran on, and recorded as its newest.
-const char* ctx_harvest_refusal(int device, int n_frames, bool frames_bound, const rmcv_dataset* ds, int n_labels, int flags, int stages)
+const char* ctx_harvest_refusal(int device, int n_frames, bool frames_bound, const rmcv_dataset* ds, int n_labels, int flags, int stages, int max_armours)
 {
     if (!ds) return "harvest: null dataset";
-    if (const char* no = harvest_refusal(frames_bound, stages, flags, device, dataset_view(ds).device)) return no;
+    const DatasetView& v = dataset_view(ds);
+    if (const char* no = harvest_refusal(frames_bound, stages, flags, device, v.device)) return no;
     if (n_frames > n_labels) return "harvest: the batch has more frames than the label table";
+    if (v.ring_rows > 0 && n_frames > v.label_cap) return "harvest: the batch has more frames than the dataset has rings (its creating context's max_frames)";
+    if (v.ring_rows > 0 && max_armours > v.keep_armours) return "harvest: max_armours is beyond that of the context the dataset with novelty was created on";
     return nullptr;
 }
 int ctx_harvest(rmcv_ctx* c, rmcv_dataset* ds, const int32_t* h_labels, const void* d_labels, int n_labels, int flags, uint64_t tag, int stages, hipStream_t s)
@@ -1272,13 +1275,13 @@ int ctx_harvest(rmcv_ctx* c, rmcv_dataset* ds, const int32_t* h_labels, const vo
         n_labels = dataset_view(ds).label_cap;
         d_labels = dataset_view(ds).labels;
     }
-    if (const char* no = ctx_harvest_refusal(c->device, g.n_frames, g.n_frames > 0 && c->bufs.frames, ds, n_labels, flags, stages)) return fail(c, RMCV_ERR_BAD_ARG, no);
+    if (const char* no = ctx_harvest_refusal(c->device, g.n_frames, g.n_frames > 0 && c->bufs.frames, ds, n_labels, flags, stages, c->lim.max_armours)) return fail(c, RMCV_ERR_BAD_ARG, no);
     int rc;
     if ((rc = order_begin(c, s))) return rc;
     HIPCHK(c, dataset_order_begin(ds, s), "harvest: wait for the dataset's previous append");
     if (h_labels) HIPCHK(c, hipMemcpyAsync(const_cast<void*>(d_labels), h_labels, (size_t)g.n_frames * 4, hipMemcpyHostToDevice, s), "H2D harvest labels");
     HIPCHK(c, launch_harvest(g, c->bufs, c->lim, dataset_view(ds), static_cast<const int32_t*>(d_labels), flags, (stages & RMCV_STAGE_IDENTITY) != 0, tag, s),
-           "k_harvest_plan + k_harvest_rows");
+           "k_harvest_plan + k_harvest_rows"); // (a dataset with novelty on: k_harvest_novel in front)
     HIPCHK(c, dataset_order_end(ds, s), "harvest: record the append");
     return order_end(c, s);
 }

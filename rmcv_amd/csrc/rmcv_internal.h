@@ -12,6 +12,7 @@
 #include "../../include/rmcv_abi.h"
 #include "bind_plan.h"
 #include "device_harvest.h"
+#include "device_novelty.h"
 #include "image_plan.h"
 #include "pixel_plan.h"
 #include "sparse_plan.h"
@@ -500,6 +501,23 @@ struct DatasetView {
     HarvestItem* list;       // [capacity] the work list of the append in flight (appends are ordered: one at a time)
     int32_t* labels;         // [label_cap] the host labels of the append in flight (rmcv_batch_harvest copies them here)
     int label_cap;
+    // novelty (device_novelty.h); the pointers are null until rmcv_dataset_set_novelty has turned it on once
+    int ring_rows;           // 0: off
+    int32_t max_sad;
+    uint8_t* rings;          // [label_cap][ring_rows][1200]
+    int64_t* pushed;         // [label_cap]
+    unsigned long long* near;
+    uint8_t* keep;           // [label_cap][keep_armours] the keep bytes of the append in flight
+    int keep_armours;        // the creating context's max_armours
+};
+// the rows rmcv_dataset_append_rows has staged on the device
+struct DatasetRowsSource {
+    const uint8_t* rows;     // [sum n_rows][1200]
+    const int32_t* n_rows;   // [n_streams]
+    const int32_t* row_off;  // [n_streams] exclusive sums of n_rows
+    const int32_t* zeros;    // [n_streams] (the status words of k_harvest_plan)
+    const int32_t* labels;   // [n_streams]
+    int n_streams, max_armours;
 };
 const DatasetView& dataset_view(const rmcv_dataset* ds);
 // the order of an append on `s`: wait (on the GPU) for the dataset's last append if that ran on another stream; afterwards record it
@@ -509,12 +527,23 @@ hipError_t dataset_order_end(rmcv_dataset* ds, hipStream_t s);
 hipError_t launch_harvest(const Geom& g, const Bufs& b, const Limits& lim, const DatasetView& d, const int32_t* d_labels, int flags, bool identity,
                           uint64_t tag, hipStream_t s);
 // d_out [n][1200] (nullable), d_responses [n] (nullable) of slots d_idx[0 .. n) (null: 0 .. n - 1)
+// k_harvest_plan alone over any per-frame tables (device); with d.ring_rows > 0 its second instantiation, which takes d.keep in
+hipError_t launch_harvest_plan(const int32_t* n_armours, const int32_t* status, const int32_t* d_labels, const int32_t* ident, int n_frames, int max_armours,
+                               int flags, const DatasetView& d, hipStream_t s);
+hipError_t launch_harvest_plan_novel(const int32_t* n_armours, const int32_t* status, const int32_t* d_labels, const int32_t* ident, int n_frames, int max_armours,
+                                     int flags, const DatasetView& d, hipStream_t s); // (k_novelty.hip)
+// the same for rows from memory (rmcv_dataset_append_rows): the plan, then a copy of 75 uint4 per kept row
+hipError_t launch_harvest_rows_source(const DatasetRowsSource& src, const DatasetView& d, int n_cu, uint64_t tag, hipStream_t s);
+// k_harvest_novel (k_novelty.hip) in front of the plan, novelty on: the keep bytes, rings, pushed and near of one append.  src null: the bound batch
+hipError_t launch_harvest_novel(const Geom& g, const Bufs& b, const Limits& lim, const DatasetRowsSource* src, const DatasetView& d, const int32_t* d_labels,
+                                int flags, const int32_t* ident, hipStream_t s);
 hipError_t launch_harvest_gather(const DatasetView& d, const int32_t* d_idx, int n, uint8_t* d_out, int32_t* d_responses, hipStream_t s);
 // rmcv_batch_harvest_device with the stages given (a pipeline runs a batch's halves separately), on `s` (rmcv_host.hip): every check before the
 // first enqueue.  d_labels: n_labels entries (a batch with more frames is refused), launches and event calls only; or h_labels (host, one per
 // frame bound): copied into the dataset's own table on `s`, behind its previous append
 int ctx_harvest(rmcv_ctx* c, rmcv_dataset* ds, const int32_t* h_labels, const void* d_labels, int n_labels, int flags, uint64_t tag, int stages, hipStream_t s);
 // ... and what it would refuse, checked without enqueuing anything (a pipeline's submit asks before its first enqueue)
-const char* ctx_harvest_refusal(int device, int n_frames, bool frames_bound, const rmcv_dataset* ds, int n_labels, int flags, int stages);
+// max_armours: the appending context's limit (a dataset with novelty on has one ring per stream and keep bytes for its creator's limits)
+const char* ctx_harvest_refusal(int device, int n_frames, bool frames_bound, const rmcv_dataset* ds, int n_labels, int flags, int stages, int max_armours);
 
 } // namespace rmcv

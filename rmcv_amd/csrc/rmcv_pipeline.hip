@@ -549,7 +549,7 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
         if (const char* no = recorder_trigger_refusal(pl->recd.rec, pl->cfg.depth)) return pfail(pl, RMCV_ERR_BAD_ARG, no); // (armed since rmcv_pipeline_set_recorder)
     }
     if (pl->harv.ds) // (with no dataset set: nothing here, and nothing further down)
-        if (const char* no = ctx_harvest_refusal(pl->device, q.n_frames, true, pl->harv.ds, pl->harv.n_labels, pl->harv.flags, stages)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
+        if (const char* no = ctx_harvest_refusal(pl->device, q.n_frames, true, pl->harv.ds, pl->harv.n_labels, pl->harv.flags, stages, pl->lim.max_armours)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
     hipSetDevice(pl->device);
     int rc = finish_back(pl, false); // the batch before this one: a pixel launch follows it
     if (rc) return rc;
@@ -924,7 +924,7 @@ int rmcv_pipeline_set_harvest(rmcv_pipeline* pl, rmcv_dataset* ds, const int32_t
     if (!labels) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_harvest: null labels");
     if (n_labels < 1 || n_labels > pl->lim.max_frames) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_harvest: n_labels outside 1 .. max_frames");
     // (the frames and the stages are the batch's: checked at every submit)
-    if (const char* no = ctx_harvest_refusal(pl->device, 1, true, ds, n_labels, flags, ~0)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
+    if (const char* no = ctx_harvest_refusal(pl->device, 1, true, ds, n_labels, flags, ~0, pl->lim.max_armours)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
     hipError_t e = hipMalloc((void**)&pl->harv.d_labels, (size_t)n_labels * 4);
     if (e == hipSuccess) e = hipMemcpy(pl->harv.d_labels, labels, (size_t)n_labels * 4, hipMemcpyHostToDevice);
     if (e != hipSuccess) return pfail(pl, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_pipeline_set_harvest", e);

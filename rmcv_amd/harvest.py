@@ -7,6 +7,10 @@
     train, held_out = ds.sample(0.6, seed=1)             # per-label index lists, rm::svm::dataset::sample's rule, seeded
     model = ds.train_auto(np.concatenate(list(train.values())))   # rmcv_svm_train_dataset: the rows never leave the device
     model.load_into(ctx); ds.predict(rows)               # rmcv_svm_predict_dataset
+Novelty: a dataset that skips near-duplicates of the icons it kept last from the same stream.
+    ds.set_novelty(8, 2000)                              # per stream, remember the last 8 kept rows; a candidate within SAD 2000 of one is not kept
+    ds.novelty                                           # {"ring_rows": 8, "max_sad": 2000, "near": candidates skipped so far}
+    ds.append_rows(rows, n_rows, labels)                 # rows the caller already has go through the same rule
 """
 import ctypes as C
 
@@ -40,6 +44,40 @@ def harvest_plan(n_armours, status, labels, identity=None, max_armours=None, fla
     if rc:
         raise RmcvError(rc, "rmcv_harvest_plan_host")
     return items[:n_items.value].copy(), now.value, drop.value
+
+
+def icon_sad(a, b):
+    """rmcv_icon_sad: the sum of absolute byte differences of two icon rows (uint8 [1200]), 0 .. ICON_SAD_MAX"""
+    a, b = np.ascontiguousarray(a, np.uint8).reshape(-1), np.ascontiguousarray(b, np.uint8).reshape(-1)
+    if len(a) != abi.SVM_FEATURES or len(b) != abi.SVM_FEATURES:
+        raise RmcvError(abi.ERR_BAD_ARG, "icon_sad: a row is 1200 bytes")
+    return int(lib().rmcv_icon_sad(ptr(a), ptr(b)))
+
+
+def _row_tables(rows, n_rows, labels):
+    n = np.ascontiguousarray(n_rows, np.int32).reshape(-1)
+    lb = np.ascontiguousarray(labels, np.int32).reshape(-1)
+    r = np.ascontiguousarray(rows, np.uint8).reshape(-1, abi.SVM_FEATURES)
+    if len(n) != len(lb) or (n < 0).any() or int(n.sum()) != len(r):
+        raise RmcvError(abi.ERR_BAD_ARG, "rows is [sum(n_rows), 1200], stream-major, with one count (>= 0) and one label per stream")
+    return r, n, lb
+
+
+def harvest_novel(rows, n_rows, labels, ring_rows, max_sad, rings=None, pushed=None):
+    """the novelty rule on the host (rmcv_harvest_novel_host: device_novelty.h compiled for the host) over rows laid out as for
+    DeviceDataset.append_rows -> (keep uint8 [sum n_rows], min_sad int32 [sum n_rows] (INT32_MAX: no distance), near, rings, pushed).
+    rings uint8 [n_streams, ring_rows, 1200] and pushed int64 [n_streams] are the state before the call (None: empty); the returned ones
+    are copies behind it."""
+    r, n, lb = _row_tables(rows, n_rows, labels)
+    R = int(ring_rows)
+    rg = np.zeros((len(n), max(R, 0), abi.SVM_FEATURES), np.uint8) if rings is None else np.array(rings, np.uint8).reshape(len(n), max(R, 0), abi.SVM_FEATURES)
+    pu = np.zeros(len(n), np.int64) if pushed is None else np.array(pushed, np.int64).reshape(len(n))
+    keep, sad, near = np.zeros(max(len(r), 1), np.uint8), np.zeros(max(len(r), 1), np.int32), C.c_int64(0)
+    rc = lib().rmcv_harvest_novel_host(ptr(r) if len(r) else None, ptr(n) if len(n) else None, ptr(lb) if len(n) else None, len(n), R, int(max_sad),
+                                       ptr(rg) if rg.size else None, ptr(pu) if len(n) else None, ptr(keep), ptr(sad), C.byref(near))
+    if rc:
+        raise RmcvError(rc, "rmcv_harvest_novel_host")
+    return keep[:len(r)], sad[:len(r)], near.value, rg, pu
 
 
 class DeviceDataset:
@@ -83,6 +121,38 @@ class DeviceDataset:
 
     def clear(self):
         self._chk(lib().rmcv_dataset_clear(self._h))
+
+    def set_novelty(self, ring_rows, max_sad):
+        """rmcv_dataset_set_novelty: from the next append on, per stream (= frame index of an append) the last `ring_rows` kept rows are
+        remembered (0 .. HARVEST_RING_MAX; 0: off) and a candidate whose icon_sad to one of them is <= max_sad is not kept.  Waits for the
+        last append; empties every ring."""
+        self._chk(lib().rmcv_dataset_set_novelty(self._h, int(ring_rows), int(max_sad)))
+
+    @property
+    def novelty(self):
+        """{"ring_rows", "max_sad", "near"}: the setting and the candidates skipped as near since the last clear() (waits for the last append)"""
+        r, t, near = C.c_int(0), C.c_int32(0), C.c_int64(0)
+        self._chk(lib().rmcv_dataset_novelty(self._h, C.byref(r), C.byref(t), C.byref(near)))
+        return {"ring_rows": r.value, "max_sad": t.value, "near": near.value}
+
+    def rings(self, first=0, n=None):
+        """(rows uint8 [n, ring_rows, 1200], pushed int64 [n]) of streams first .. first + n - 1 (n None: to the last) as they lie: the row
+        pushed as number k of a stream at position k % ring_rows, positions not yet written zero"""
+        first = int(first)
+        n = self._ctx.limits.max_frames - first if n is None else int(n)
+        R = self.novelty["ring_rows"]
+        rows, pushed = np.zeros((max(n, 0), R, abi.SVM_FEATURES), np.uint8), np.zeros(max(n, 0), np.int64)
+        self._chk(lib().rmcv_dataset_get_rings(self._h, first, n, ptr(rows) if rows.size else None, ptr(pushed) if n > 0 else None))
+        return rows, pushed
+
+    def append_rows(self, rows, n_rows, labels, tag=0):
+        """rmcv_dataset_append_rows: rows the caller already has (uint8 [sum(n_rows), 1200], stream-major: stream s gives n_rows[s]
+        candidates in order, none under HARVEST_SKIP) through the rule of any other append, novelty included.  frame = the stream, armour =
+        the index within it.  Asynchronous: count waits."""
+        r, n, lb = _row_tables(rows, n_rows, labels)
+        if len(r) == 0:
+            r = np.zeros((1, abi.SVM_FEATURES), np.uint8)   # (a table to point at: no row of it is read)
+        self._chk(lib().rmcv_dataset_append_rows(self._h, ptr(r), ptr(n) if len(n) else None, ptr(lb) if len(n) else None, len(n), int(tag)))
 
     def _range(self, first, n):
         first = int(first)

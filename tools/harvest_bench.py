@@ -1,10 +1,15 @@
 """What the dataset harvest costs a pipelined step: ONE pipeline at the benchmark's geometry (256 resident 1280x1024 frames,
 RMCV_STAGE_ALL, the host only submits) in one process, regions alternating between harvest off and on (rmcv_pipeline_set_harvest toggles it
-between regions; the call drains, no submit blocks); REGIONS x STEPS per arm (median, spread), written to profiles/harvest_bench.json:
+between regions; the call drains, no submit blocks); REGIONS x STEPS per arm (median, spread), written to profiles/novelty_bench.json
+(profiles/harvest_bench.json is the record of the three-arm tool of DESIGN.md 4m):
   off        no dataset attached: the step as it was (the yardstick)
   off2       the same arm once more: what "no difference" means is the spread between these two
   on         every batch appends its armours' rows (a label per frame, none skipped); the dataset is cleared between regions
-and, on a context of its own, the two kernels alone (k_harvest_plan + k_harvest_rows between HIP events, REPS appends of one batch).
+  novel      the same into a dataset with novelty on (ring_rows 8, max_sad 0), never cleared: the frame sets repeat, so from their
+             second round on every candidate is an exact duplicate of a row its stream's ring holds -- the steady state of a calm stream
+and, on a context of its own, the kernels alone between HIP events, REPS appends of one batch: k_harvest_plan + k_harvest_rows, and with
+novelty on k_harvest_novel + k_harvest_plan_novel + k_harvest_rows (the first append after a clear, which keeps every row, and the ones
+behind it, which keep none).
 python tools/harvest_bench.py [regions steps]"""
 import json
 import os
@@ -23,7 +28,8 @@ argv = sys.argv[1:]
 REGIONS = int(argv[0]) if len(argv) > 0 else 7
 STEPS = int(argv[1]) if len(argv) > 1 else 20
 N, W, H = 256, 1280, 1024
-ARMS = ["off", "off2", "on"]
+ARMS = ["off", "off2", "on", "novel"]
+RING_ROWS, MAX_SAD = 8, 0
 dev = torch.device("cuda", 0)
 torch.cuda.set_device(0)
 p = default_params()
@@ -44,12 +50,14 @@ ctx.run(p, STAGE_ALL)
 ctx.sync()
 per_batch = int(ctx.counts()["n_armours"].sum())
 ds = DeviceDataset(ctx, max(1, per_batch) * (STEPS + 40))   # room for a region's appends: nothing is dropped
+novel = DeviceDataset(ctx, max(1, per_batch) * (len(ARMS) * REGIONS * STEPS // 4 + 80))   # never cleared: room for what every region keeps
+novel.set_novelty(RING_ROWS, MAX_SAD)
 count = 0
 
 
 def region(arm, k):
     global count
-    pl.set_harvest(ds if arm == "on" else None, labels)
+    pl.set_harvest({"on": ds, "novel": novel}.get(arm), labels)
     ds.clear()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
@@ -63,14 +71,19 @@ def region(arm, k):
 
 for arm in ARMS:  # warm-up: every context of the ring has bound the geometry
     region(arm, 40)
-ms, rows = {arm: [] for arm in ARMS}, []
+ms, rows, kept, near = {arm: [] for arm in ARMS}, [], [], []
 for r in range(REGIONS):
-    for arm in ARMS[r % 3:] + ARMS[:r % 3]:
+    for arm in ARMS[r % len(ARMS):] + ARMS[:r % len(ARMS)]:
+        before = (novel.count, novel.novelty["near"])
         ms[arm].append(region(arm, STEPS))
         if arm == "on":
             rows.append(ds.count)
+        if arm == "novel":
+            kept.append(novel.count - before[0]), near.append(novel.novelty["near"] - before[1])
 out = {"tool": "harvest_bench", "frames": N, "w": W, "h": H, "regions": REGIONS, "steps": STEPS, "stages": "ALL", "rows_per_batch": per_batch,
-       "rows_per_on_region": rows, "dropped": ds.dropped, "host_blocking_calls": int(pl.get_info().host_blocking_calls)}
+       "rows_per_on_region": rows, "novelty": {"ring_rows": RING_ROWS, "max_sad": MAX_SAD, "rows_kept_per_novel_region": kept, "near_per_novel_region": near,
+                                               "rows_kept_in_warm_up": novel.count - sum(kept), "dropped": novel.dropped},
+       "dropped": ds.dropped, "host_blocking_calls": int(pl.get_info().host_blocking_calls)}
 base = float(np.median(ms["off"]))
 for arm in ARMS:
     s = stats(ms[arm])
@@ -95,9 +108,24 @@ for _ in range(REPS):
 b.record(side)
 side.synchronize()
 out["harvest_kernels_alone"] = {"ms_per_append": round(a.elapsed_time(b) / REPS, 4), "rows_per_append": per_batch, "appends": REPS, "rows": ds.count}
+# ... and with novelty on: the append that meets empty rings (every row kept, pushed and computed twice), then REPS that keep nothing
+novel.clear()
+a.record(side)
+ctx.harvest(novel, d_labels.data_ptr(), stream=side.cuda_stream)
+b.record(side)
+side.synchronize()
+first_ms, first_rows = a.elapsed_time(b), novel.count
+a.record(side)
+for _ in range(REPS):
+    ctx.harvest(novel, d_labels.data_ptr(), stream=side.cuda_stream)
+b.record(side)
+side.synchronize()
+out["novelty_kernels_alone"] = {"first_append_ms": round(first_ms, 4), "first_append_rows_kept": first_rows, "ms_per_append_all_near": round(a.elapsed_time(b) / REPS, 4),
+                                "appends": REPS, "rows_kept_by_them": novel.count - first_rows, "near": novel.novelty["near"]}
+novel.close()
 ds.close()
 ctx.close()
 os.makedirs(os.path.join(ROOT, "profiles"), exist_ok=True)
-with open(os.path.join(ROOT, "profiles", "harvest_bench.json"), "w") as f:
+with open(os.path.join(ROOT, "profiles", "novelty_bench.json"), "w") as f:
     f.write(json.dumps(out, indent=1) + "\n")
 print(json.dumps(out), flush=True)
