@@ -499,6 +499,43 @@ int rmcv_classify_armours(rmcv_ctx* ctx, const uint8_t* bgr, int w, int h, int s
 int rmcv_batch_get_identities(rmcv_ctx* ctx, int32_t* identity_out, int cap, int32_t* n_total);
 int rmcv_batch_get_icons(rmcv_ctx* ctx, int frame, uint8_t* icons_out, int cap_armours, int32_t* n_armours);
 
+/* ---- one model per colour, or per robot: a table of models, one chosen per frame on the device -------------------
+ * The reference's loop owns one classifier per enemy colour, svm_red and svm_blue (executable/main.cpp:21-22).  A context holds a table
+ * of up to RMCV_SVM_MAX_MODELS models; a batch classifies frame f with entry rmcv_frame_model(idx[f], n_models) of it.
+ *
+ * rmcv_svm_load_models copies the table, waiting for the context's work first.  Entry 0 is also what every single-model consumer reads
+ * (rmcv_classify_armours, rmcv_svm_predict, rmcv_svm_predict_dataset, and every batch with selection off): exactly what
+ * rmcv_svm_load(models[0]) gives.  rmcv_svm_load is a table of one.  Either call switches per-frame selection off; so does a new binding
+ * of frames.  Refused with RMCV_ERR_BAD_ARG and a message, before any GPU work: n_models outside 1 .. RMCV_SVM_MAX_MODELS; an entry with
+ * a null pointer, with n_class outside 2 .. 8, or with a weight or rho that is not finite (the message names the entry).
+ *
+ * Selection on: frame f's identities, icons and clamped icon vertices are, byte for byte, what the same batch gives after
+ * rmcv_svm_load(models[eff(idx[f])]).  Models may differ in n_class and labels.  The indices are read on the run's stream, in front of
+ * the classifier, by every run with RMCV_STAGE_IDENTITY: host indices are validated and copied (one outside the table: RMCV_ERR_BAD_ARG,
+ * nothing changes); device indices are BORROWED and may hold any int32 -- every value outside 0 .. n_models - 1 reads model 0.
+ *
+ * Camps as indices: the raw camp values are RMCV_CAMP_RED 0, RMCV_CAMP_BLUE 1, guide light 2 and neutral -1.  With the table
+ * {svm_red, svm_blue} the device camps table of rmcv_pipeline_submit_camps, or rmcv_tracker_device_camps, can be handed over as the model
+ * index table as it is: red streams read svm_red, blue streams svm_blue, every other value model 0. */
+#define RMCV_SVM_MAX_MODELS 64
+typedef struct {
+    const float*   weights; /* [n_class*(n_class-1)/2][1200] */
+    const double*  rho;     /* [n_class*(n_class-1)/2] */
+    const int32_t* labels;  /* [n_class] */
+    int32_t n_class;        /* 2 .. 8 */
+    int32_t reserved;
+} rmcv_svm_model;
+int rmcv_frame_model(int32_t idx, int32_t n_models);   /* the rule: host-side, no context, no device */
+int rmcv_svm_load_models(rmcv_ctx* ctx, const rmcv_svm_model* models, int n_models);
+/* idx: n_frames int32 of the host, copied; an index outside the table: RMCV_ERR_BAD_ARG, nothing changes; NULL: off */
+int rmcv_batch_set_frame_models(rmcv_ctx* ctx, const int32_t* idx);
+/* d_idx: n_frames int32 in DEVICE memory, BORROWED, read again by every run with RMCV_STAGE_IDENTITY; NULL: off */
+int rmcv_batch_set_device_frame_models(rmcv_ctx* ctx, const void* d_idx);
+/* the EFFECTIVE indices of the last such run for the first min(cap, n_frames) frames; 0 everywhere when off.  Synchronises the context. */
+int rmcv_batch_get_frame_models(rmcv_ctx* ctx, int32_t* out, int cap);
+/* rmcv_svm_predict with entry `model` of the table (0 .. n_models - 1; anything else: RMCV_ERR_BAD_ARG) */
+int rmcv_svm_predict_model(rmcv_ctx* ctx, int model, const uint8_t* samples, int n, int32_t* identity_out);
+
 /* ---- training the icon classifier (executable/svm/optimizer.cpp: C_SVC, LINEAR, trainAuto) -------------------------
  * The model rmcv_svm_load takes, trained from rows as rmcv_batch_get_icons / rmcv_classify_armours hand them out (1200 raw bytes each,
  * features = the bytes as f32, unscaled).  OpenCV's solver is not pinned, so the library defines its own exact rule, modelled on
@@ -1100,6 +1137,13 @@ int  rmcv_pipeline_submit_tracked_serial(rmcv_pipeline* pl, rmcv_tracker* trk, c
  * RMCV_ERR_BAD_ARG and a message, before anything is enqueued: its n_frames differs from the table's; the ring's contexts do not all hold
  * the same n_cameras.  Nothing blocks: host_blocking_calls stays 0. */
 int  rmcv_pipeline_set_frame_cameras(rmcv_pipeline* pl, const void* d_idx, int n_frames);
+/* the frames' model indices for every following submit, of any of the six calls, whose stages include RMCV_STAGE_IDENTITY.
+ * d_idx: n_frames int32 in DEVICE memory, borrowed until replaced and until the batches submitted with it are through; read on the batch's
+ * stream in front of the classifier; any value (rmcv_frame_model).  NULL: off.  The models themselves are loaded into EVERY slot
+ * (rmcv_pipeline_context(k), rmcv_svm_load_models).  Such a submit is refused with RMCV_ERR_BAD_ARG and a message, before anything is
+ * enqueued: its n_frames differs from the table's; the ring's contexts do not all hold the same n_models.  Nothing blocks:
+ * host_blocking_calls stays 0.  The device camps table of rmcv_pipeline_submit_camps may be the same buffer (see rmcv_svm_load_models). */
+int  rmcv_pipeline_set_frame_models(rmcv_pipeline* pl, const void* d_idx, int n_frames);
 /* block until the batch is through (its record complete in HBM and, with host_results, on the host) */
 int  rmcv_pipeline_wait(rmcv_pipeline* pl, uint64_t ticket);
 /* wait + hand the batch's armours over, frame-major, in submission order of the frames: frame_offs (nullable) has n_frames + 1

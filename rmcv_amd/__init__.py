@@ -17,6 +17,7 @@ from .api import Context, debug_view
 from .pipeline import Pipeline
 from .recorder import LoopRecord, Recorder, Session, loop_bound, loop_field_at, loop_trigger, pack, pack_bound, unpack
 from . import svm
+from .abi import SVM_MAX_MODELS, SvmModel, frame_model
 from .abi import HARVEST_META, HARVEST_MISSES, HARVEST_RING_MAX, HARVEST_SKIP, ICON_SAD_MAX
 from .harvest import DeviceDataset, harvest_novel, harvest_plan, icon_sad
 from .abi import (LOOP_TRUNCATED, TRIG_AIM_JUMP, TRIG_ALL, TRIG_FRAME_STATUS, TRIG_NO_ARMOURS, TRIG_NO_SOLUTION, TRIG_PACKET_ERROR, TRIG_TARGET_LOST, TRIG_TARGET_SWITCH,

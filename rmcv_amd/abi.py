@@ -119,6 +119,8 @@ EXPORTS = [
     "rmcv_dataset_create", "rmcv_dataset_destroy", "rmcv_dataset_clear", "rmcv_dataset_last_error", "rmcv_dataset_count", "rmcv_dataset_get", "rmcv_dataset_device",
     "rmcv_batch_harvest", "rmcv_batch_harvest_device", "rmcv_harvest_plan_host", "rmcv_pipeline_set_harvest", "rmcv_svm_train_dataset", "rmcv_svm_predict_dataset",
     "rmcv_icon_sad", "rmcv_dataset_set_novelty", "rmcv_dataset_novelty", "rmcv_dataset_get_rings", "rmcv_dataset_append_rows", "rmcv_harvest_novel_host",
+    "rmcv_frame_model", "rmcv_svm_load_models", "rmcv_batch_set_frame_models", "rmcv_batch_set_device_frame_models", "rmcv_batch_get_frame_models",
+    "rmcv_pipeline_set_frame_models", "rmcv_svm_predict_model",
 ]
 
 
@@ -512,6 +514,14 @@ def load(path):
         L.rmcv_dataset_append_rows.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_uint64]
         L.rmcv_harvest_novel_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                               C.c_void_p]
+    if hasattr(L, "rmcv_frame_model"):  # (builds from before the per-stream model tables stay loadable for A/B runs)
+        L.rmcv_frame_model.argtypes = [C.c_int32, C.c_int32]
+        L.rmcv_svm_load_models.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_batch_set_frame_models.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_batch_set_device_frame_models.argtypes = [C.c_void_p, C.c_void_p]
+        L.rmcv_batch_get_frame_models.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_pipeline_set_frame_models.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_svm_predict_model.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
     L.rmcv_device_free.restype = None
     L.rmcv_device_free.argtypes = [C.c_int, C.c_void_p]
     return L
@@ -740,6 +750,21 @@ def frame_camera(idx, n_cameras):
     idx, n_cameras = int(idx), int(n_cameras)
     assert -2**31 <= idx < 2**31 and -2**31 <= n_cameras < 2**31
     return int(lib().rmcv_frame_camera(C.c_int32(idx), C.c_int32(n_cameras)))
+
+
+SVM_MAX_MODELS = 64  # RMCV_SVM_MAX_MODELS
+
+
+class SvmModel(C.Structure):
+    """rmcv_svm_model: one entry of rmcv_svm_load_models' table, pointers into arrays the caller keeps alive for the call"""
+    _fields_ = [("weights", C.c_void_p), ("rho", C.c_void_p), ("labels", C.c_void_p), ("n_class", C.c_int32), ("reserved", C.c_int32)]
+
+
+def frame_model(idx, n_models):
+    """the model-table entry a frame with raw index `idx`, any int32, uses (rmcv_frame_model: host-side, the function k_classify_models runs)"""
+    idx, n_models = int(idx), int(n_models)
+    assert -2**31 <= idx < 2**31 and -2**31 <= n_models < 2**31
+    return int(lib().rmcv_frame_model(C.c_int32(idx), C.c_int32(n_models)))
 
 
 def default_pnp_config():

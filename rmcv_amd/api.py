@@ -623,14 +623,56 @@ class Context:
         assert weights.shape == (n_class * (n_class - 1) // 2, abi.SVM_FEATURES) and len(rho) == weights.shape[0]
         self._chk(lib().rmcv_svm_load(self._h, ptr(weights), ptr(rho), ptr(labels), n_class))
 
-    def svm_predict(self, samples):
-        """rmcv_svm_predict: the loaded model's labels of uint8 [n, 1200] icon rows, in the arithmetic of RMCV_STAGE_IDENTITY"""
+    def svm_predict(self, samples, model=0):
+        """rmcv_svm_predict: the loaded model's labels of uint8 [n, 1200] icon rows, in the arithmetic of RMCV_STAGE_IDENTITY.
+        model=k: entry k of the table of svm_load_models (rmcv_svm_predict_model); entry 0 is the loaded model."""
         s = np.ascontiguousarray(samples, np.uint8)
         s = s.reshape(len(s), -1) if s.size else s.reshape(0, abi.SVM_FEATURES)
         assert s.shape[1] == abi.SVM_FEATURES
         out = np.zeros(len(s), np.int32)
-        self._chk(lib().rmcv_svm_predict(self._h, ptr(s) if len(s) else None, len(s), ptr(out) if len(s) else None))
+        if model:
+            self._chk(lib().rmcv_svm_predict_model(self._h, int(model), ptr(s) if len(s) else None, len(s), ptr(out) if len(s) else None))
+        else:
+            self._chk(lib().rmcv_svm_predict(self._h, ptr(s) if len(s) else None, len(s), ptr(out) if len(s) else None))
         return out
+
+    def svm_load_models(self, models):
+        """the context's model table (rmcv_svm_load_models): a sequence of (weights [n_df, 1200] f32, rho [n_df] f64, labels [n_class] i32),
+        or of objects with those attributes (rmcv_amd.svm.Model), one per colour or per robot.  Entry 0 is also what classify_armours
+        and svm_predict use; set_frame_models picks an entry per frame.  Switches per-frame selection off."""
+        keep, arr = [], (abi.SvmModel * max(len(models), 1))()
+        for k, m in enumerate(models):
+            w, r, l = (m.weights, m.rho, m.labels) if hasattr(m, "weights") else m
+            w, r, l = np.ascontiguousarray(w, np.float32), np.ascontiguousarray(r, np.float64), np.ascontiguousarray(l, np.int32)
+            n_class = len(l)
+            assert w.size == n_class * (n_class - 1) // 2 * abi.SVM_FEATURES and r.size * abi.SVM_FEATURES == w.size
+            keep.append((w, r, l))
+            arr[k] = abi.SvmModel(w.ctypes.data, r.ctypes.data, l.ctypes.data, n_class, 0)
+        self._chk(lib().rmcv_svm_load_models(self._h, arr, len(models)))
+
+    def set_frame_models(self, idx, keepalive=None):
+        """every frame bound is classified with its own entry of the model table: n integers on the host (each inside the table, else
+        RmcvError and nothing changes), or an int = device pointer to n int32 (borrowed; read again by every run with STAGE_IDENTITY; any
+        values: frame_models() shows what the kernel used -- a device camps table works as it is with the table [svm_red, svm_blue]).
+        None: model 0 for every frame (a new binding returns to that too)."""
+        if idx is None:
+            self._chk(lib().rmcv_batch_set_frame_models(self._h, None))
+            return
+        if isinstance(idx, (int, np.integer)):
+            self._models_ref = keepalive
+            self._chk(lib().rmcv_batch_set_device_frame_models(self._h, C.c_void_p(int(idx))))
+            return
+        i = np.ascontiguousarray(idx, np.int32).reshape(-1)
+        assert len(i) == self.shape[0], "one model index per frame bound"
+        self._chk(lib().rmcv_batch_set_frame_models(self._h, ptr(i)))
+
+    def frame_models(self):
+        """the effective model index of every frame in the last run with STAGE_IDENTITY and selection on, int32 (n,); zeros without selection"""
+        out = np.zeros(self.shape[0], np.int32)
+        self._chk(lib().rmcv_batch_get_frame_models(self._h, ptr(out), len(out)))
+        return out
+
+    frame_model = staticmethod(abi.frame_model)
 
     def harvest(self, ds, labels, flags=0, tag=0, stream=None):
         """rmcv_batch_harvest: append the bound batch's armours' icon rows to the DeviceDataset `ds`, behind its last run (which included

@@ -50,6 +50,9 @@ struct Geom {
     // per-frame detection keys (rmcv_batch_set_frame_camps): camp and lower bound of every frame come from Bufs::key_eff / key_enemy, which every
     // run with the pixel pass rewrites in front of it; rmcv_params::camp and ::lower_bound are then not read
     int keys;
+    // per-frame icon models (rmcv_batch_set_frame_models): every frame is classified with its own entry of the context's model
+    // table (Bufs::model_idx), by k_classify_models; 0: entry 0 for every frame, the single-model kernels
+    int models;
 };
 
 // What a binding records of the context's options (frames bound before keep what they were bound with)
@@ -136,6 +139,7 @@ inline void bind_geom(Geom& g, const InputOptions& in, int n_frames, int w, int 
     g.frame_h = h;
     g.win = win_w > 0;
     g.keys = 0;
+    g.models = 0;
     extent_fields(g, g.win ? win_w : w, g.win ? win_h : h);
 }
 
@@ -192,12 +196,13 @@ struct RunSteps {
     bool binary, image;   // the pixel pass; with the 0/255 byte image
     // findContours + filter_lightblobs (+ filter_armours) as ONE per-frame kernel when the stages are asked for together; the per-stage
     // events of rmcv_batch_run_timed need per-stage launches.  The icon classifier rides in it when the armours come from it (not for
-    // mosaics: its classifier reads BGR; nor through a gamma table or windows: k_classify takes those)
+    // mosaics: its classifier reads BGR; nor through a gamma table or windows: k_classify takes those; nor with per-frame models: the
+    // fused classifier is never given a table, k_classify_models takes every such batch)
     bool sparse, sparse_pairs, sparse_identity, contours;
     bool match, match_pairs, blobs_armours, blobs; // the legacy matcher (+ pairing in the same launch); fit and pairing in one launch; the fit alone
     bool armours, classify, pnp;
 };
-inline RunSteps run_steps(int stages, bool timed, bool legacy, int input_format, int enhance, int win, int keys)
+inline RunSteps run_steps(int stages, bool timed, bool legacy, int input_format, int enhance, int win, int keys, int models = 0)
 {
     const auto has = [stages](int s) { return (stages & s) != 0; };
     RunSteps r{};
@@ -211,7 +216,7 @@ inline RunSteps run_steps(int stages, bool timed, bool legacy, int input_format,
     r.frame_keys = r.binary && keys;
     r.sparse = !timed && !legacy && has(RMCV_STAGE_CONTOURS) && has(RMCV_STAGE_BLOBS);
     r.sparse_pairs = r.sparse && has(RMCV_STAGE_ARMOURS);
-    r.sparse_identity = r.sparse_pairs && has(RMCV_STAGE_IDENTITY) && input_format == RMCV_INPUT_BGR && !enhance && !win;
+    r.sparse_identity = r.sparse_pairs && has(RMCV_STAGE_IDENTITY) && input_format == RMCV_INPUT_BGR && !enhance && !win && !models;
     r.contours = !r.sparse && has(RMCV_STAGE_CONTOURS);
     const bool both = has(RMCV_STAGE_BLOBS) && has(RMCV_STAGE_ARMOURS), rest = !r.sparse && has(RMCV_STAGE_BLOBS);
     r.match = rest && legacy;

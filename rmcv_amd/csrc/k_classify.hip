@@ -65,6 +65,7 @@ ClassifyArgs classify_args(const Geom& g, const Bufs& b)
 
 hipError_t launch_classify(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s)
 {
+    if (g.models) return launch_classify_models(g, b, lim, s); // per-frame models: a kernel of its own, k_classify_models.hip
     if (g.input_format != RMCV_INPUT_BGR)
         return launch(k_classify_bayer, dim3(g.n_frames), dim3(256), 0, s, classify_args(g, b), b.armours, b.n_armours, lim.max_armours, g.input_format,
                       raw_layout(8 * g.sample_bytes, g.valid_bit, g.orient));

@@ -115,6 +115,8 @@ struct rmcv_ctx {
     rmcv_point* win_own = nullptr;    // [max_frames] the context's copy of host origins (rmcv_batch_set_windows); Bufs::win_req points here or at the caller's
     int32_t* key_own = nullptr;       // [2][max_frames] the context's copy of host camps | lower bounds (rmcv_batch_set_frame_camps); Bufs::key_camps / key_lbs point here or at the caller's
     int32_t* cam_own = nullptr;       // [max_frames] the context's copy of host camera indices (rmcv_batch_set_frame_cameras); Bufs::cam_req points here or at the caller's
+    int32_t* model_own = nullptr;     // [max_frames] the context's copy of host model indices (rmcv_batch_set_frame_models); Bufs::model_idx points here or at the caller's
+    int model_classes[RMCV_SVM_MAX_MODELS] = {0}; // n_class of every entry of Bufs::svm_table (rmcv_svm_predict_model launches with it)
     int last_camp = RMCV_CAMP_BLUE, last_lower_bound = 80; // rmcv_params::camp, ::lower_bound of the last run with the pixel pass (rmcv_batch_get_frame_keys without per-frame keys)
     // the debug view: allocated on first use (ctx_view_prepare), never by a run
     uint64_t* view_overlay = nullptr; // [view_cap][2] colour planes, each as large as a plane of the largest frame
@@ -220,11 +222,13 @@ namespace rmcv {
 inline PixelVariant geom_variant(const Geom& g) { return pixel_variant(g.input_format, g.enhance, g.win, g.keys); }
 // bytes of one sample of what the context's options describe: 3 per BGR pixel, 1 or 2 per Bayer sample
 inline int ctx_pixel_bytes(const rmcv_ctx* c) { return c->input.pixel_bytes(); }
-// every per-frame mode of a binding off: per-run keys (Geom::keys is bind_geom's), camera 0 for every frame, no window requests
+// every per-frame mode of a binding off: per-run keys (Geom::keys is bind_geom's), camera 0 and model 0 for every frame, no window requests
 inline void reset_modes(rmcv_ctx* c)
 {
     c->bufs.key_camps = c->bufs.key_lbs = nullptr;
     c->bufs.cam_req = nullptr;
+    c->bufs.model_idx = nullptr;
+    c->geom.models = 0;
     c->bufs.win_req = nullptr;
 }
 // one armour's row of Bufs::poses, rvec | tvec | world position, into the callers' three arrays (each may be null)

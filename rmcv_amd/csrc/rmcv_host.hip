@@ -227,6 +227,12 @@ RunPlan ctx_plan(const rmcv_ctx* c) { return {c->pixel_shape, c->pixel_groups, c
 int ctx_enhance(const rmcv_ctx* c) { return c->input.enhance; }
 int ctx_n_cameras(const rmcv_ctx* c) { return c->bufs.pnp_cams ? c->bufs.n_cameras : 0; }
 void ctx_set_frame_cameras(rmcv_ctx* c, const void* d_idx) { c->bufs.cam_req = (const int32_t*)d_idx; }
+int ctx_n_models(const rmcv_ctx* c) { return c->bufs.svm_table ? c->bufs.svm_models : 0; }
+void ctx_set_frame_models(rmcv_ctx* c, const void* d_idx)
+{
+    c->bufs.model_idx = (const int32_t*)d_idx;
+    c->geom.models = d_idx != nullptr;
+}
 PixelVariant ctx_pixel_variant(const rmcv_ctx* c) { return geom_variant(c->geom); }
 int ctx_frame_pixel_bytes(const rmcv_ctx* c) { return ctx_pixel_bytes(c); }
 void ctx_record_batch(const rmcv_ctx* c, RecordBatch* b)
@@ -510,7 +516,7 @@ static int run_stages(rmcv_ctx* c, const rmcv_params* p, int stages, hipStream_t
     const Geom& g = c->geom;
     const Bufs& b = c->bufs;
     const Limits& lim = c->lim;
-    const RunSteps st = run_steps(stages, timed, lp != nullptr, g.input_format, g.enhance, g.win, g.keys);
+    const RunSteps st = run_steps(stages, timed, lp != nullptr, g.input_format, g.enhance, g.win, g.keys, g.models);
     int k = 0;
     resident_none(c);
     int rc;
@@ -871,11 +877,11 @@ int rmcv_batch_compact_armours(rmcv_ctx* c, void* d_armours_out, int cap, void* 
     return order_end(c, s);
 }
 
-int rmcv_svm_load(rmcv_ctx* c, const float* weights, const double* rho, const int32_t* labels, int n_class)
+// The context's model table := models[0 .. n) (checked by the callers), per-frame selection off.  Entry 0 also goes into
+// svm_w / svm_rho / svm_labels, which every single-model consumer reads.
+static int load_model_table(rmcv_ctx* c, const rmcv_svm_model* models, int n)
 {
-    if (!c || !weights || !rho || !labels || n_class < 2 || n_class > 8) return RMCV_ERR_BAD_ARG;
     hipSetDevice(c->device);
-    const int n_df = n_class * (n_class - 1) / 2;
     Bufs& b = c->bufs;
     if (!b.svm_w) {
         hipError_t e = dalloc(c, &b.svm_w, (size_t)28 * RMCV_SVM_FEATURES);
@@ -883,13 +889,75 @@ int rmcv_svm_load(rmcv_ctx* c, const float* weights, const double* rho, const in
         if (e == hipSuccess) e = dalloc(c, &b.svm_labels, 8);
         if (e == hipSuccess) e = dalloc(c, &b.identity, (size_t)c->lim.max_frames * c->lim.max_armours);
         if (e == hipSuccess) e = dalloc(c, &b.icons, (size_t)c->lim.max_frames * c->lim.max_armours * RMCV_SVM_FEATURES);
+        if (e == hipSuccess) e = dalloc(c, &b.svm_table, (size_t)RMCV_SVM_MAX_MODELS); // (the model table: behind the others, which stay where they were)
+        if (e == hipSuccess) e = dalloc(c, &b.model_eff, (size_t)c->lim.max_frames);
+        if (e == hipSuccess) e = dalloc(c, &c->model_own, (size_t)c->lim.max_frames);
+        if (e == hipSuccess) e = hipMemset(b.model_eff, 0, (size_t)c->lim.max_frames * 4);
         if (e != hipSuccess) { b.svm_w = nullptr; return fail(c, RMCV_ERR_NOMEM, "svm buffers", e); }
     }
-    HIPCHK(c, hipMemcpy(b.svm_w, weights, (size_t)n_df * RMCV_SVM_FEATURES * sizeof(float), hipMemcpyHostToDevice), "H2D svm");
-    HIPCHK(c, hipMemcpy(b.svm_rho, rho, (size_t)n_df * sizeof(double), hipMemcpyHostToDevice), "H2D svm");
-    HIPCHK(c, hipMemcpy(b.svm_labels, labels, (size_t)n_class * sizeof(int32_t), hipMemcpyHostToDevice), "H2D svm");
-    b.svm_classes = n_class;
+    const rmcv_svm_model& m0 = models[0];
+    const int n_df = model_n_df(m0.n_class);
+    HIPCHK(c, hipMemcpy(b.svm_w, m0.weights, (size_t)n_df * RMCV_SVM_FEATURES * sizeof(float), hipMemcpyHostToDevice), "H2D svm");
+    HIPCHK(c, hipMemcpy(b.svm_rho, m0.rho, (size_t)n_df * sizeof(double), hipMemcpyHostToDevice), "H2D svm");
+    HIPCHK(c, hipMemcpy(b.svm_labels, m0.labels, (size_t)m0.n_class * sizeof(int32_t), hipMemcpyHostToDevice), "H2D svm");
+    b.svm_classes = m0.n_class;
+    std::vector<SvmModelEntry> table((size_t)n);
+    for (int m = 0; m < n; m++) {
+        model_pack(models[m], &table[(size_t)m]);
+        c->model_classes[m] = models[m].n_class;
+    }
+    HIPCHK(c, hipMemcpy(b.svm_table, table.data(), table.size() * sizeof(SvmModelEntry), hipMemcpyHostToDevice), "H2D model table");
+    b.svm_models = n;
+    b.model_idx = nullptr;
+    c->geom.models = 0;
     return RMCV_OK;
+}
+
+// a table of one
+int rmcv_svm_load(rmcv_ctx* c, const float* weights, const double* rho, const int32_t* labels, int n_class)
+{
+    if (!c || !weights || !rho || !labels || n_class < 2 || n_class > 8) return RMCV_ERR_BAD_ARG;
+    const rmcv_svm_model one = {weights, rho, labels, n_class, 0};
+    return load_model_table(c, &one, 1);
+}
+
+int rmcv_svm_load_models(rmcv_ctx* c, const rmcv_svm_model* models, int n_models)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    char msg[200];
+    if (const int rc = refuse(c, models_refusal(models, n_models, msg))) return rc; // before any GPU work
+    if (const int rc = ctx_ready(c)) return rc; // the table about to be rewritten may still be read by a batch in flight
+    return load_model_table(c, models, n_models);
+}
+
+/* ---- per-frame models: every frame of the batch bound is classified with its own entry of the model table ---- */
+
+// indices: the host's (validated, copied into the context's own table) or the caller's device memory (borrowed, any value); both null: model 0
+static int set_frame_models(rmcv_ctx* c, const int32_t* h_idx, const void* d_idx)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    Geom& g = c->geom;
+    Bufs& b = c->bufs;
+    if (g.n_frames <= 0 || !b.frames) return fail(c, RMCV_ERR_BAD_ARG, "no frames bound: per-frame models are set after the frames");
+    if ((h_idx || d_idx) && !b.svm_table) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_svm_load_models first");
+    char msg[200];
+    if (h_idx)
+        if (const int rc = refuse(c, frame_models_refusal(h_idx, g.n_frames, b.svm_models, msg))) return rc;
+    const int rc = set_request_table(c, &b.model_idx, c->model_own, h_idx, d_idx, true, "H2D frame models");
+    if (rc == RMCV_OK) g.models = b.model_idx != nullptr;
+    return rc;
+}
+
+int rmcv_batch_set_frame_models(rmcv_ctx* c, const int32_t* idx) { return set_frame_models(c, idx, nullptr); }
+
+int rmcv_batch_set_device_frame_models(rmcv_ctx* c, const void* d_idx) { return set_frame_models(c, nullptr, d_idx); }
+
+int rmcv_batch_get_frame_models(rmcv_ctx* c, int32_t* out, int cap)
+{
+    if (!c || cap < 0 || (cap > 0 && !out)) return RMCV_ERR_BAD_ARG;
+    if (const int rc = ctx_ready(c)) return rc;
+    // selection off: model 0 for every frame
+    return get_effective_table(c, out, cap, c->geom.models != 0, c->bufs.model_eff, int32_t{0}, "D2H frame models");
 }
 
 int rmcv_batch_get_identities(rmcv_ctx* c, int32_t* identity_out, int cap, int32_t* n_total)

@@ -14,6 +14,7 @@
 #include "device_harvest.h"
 #include "device_novelty.h"
 #include "image_plan.h"
+#include "model_plan.h"
 #include "pixel_plan.h"
 #include "sparse_plan.h"
 #include "svm_plan.h"
@@ -77,6 +78,12 @@ struct Bufs {
     int svm_classes;
     int32_t* identity;     // [frame][max_armours]
     uint8_t* icons;        // [frame][max_armours][1200]  rectified 20x20 BGR icons
+    // the model table: what k_classify_models reads.  Entry 0 is the model of svm_w / svm_rho / svm_labels above once more;
+    // frame f takes entry frame_model_eff(model_idx[f], svm_models), and while model_idx is null every frame is classified from svm_*
+    SvmModelEntry* svm_table;     // [RMCV_SVM_MAX_MODELS]  allocated with svm_w
+    int svm_models;               // entries loaded: 1 behind rmcv_svm_load
+    const int32_t* model_idx;     // [frame] the raw indices, any value (the context's own copy of host values, or the caller's device memory); null: off
+    int32_t* model_eff;           // [frame] the effective indices the last k_classify_models used
     // armour pose; allocated by rmcv_pnp_load
     rmcv_pnp_config* pnp_cfg; //  [1]            rmcv_pnp_load's one camera
     // the camera table: what k_pnp reads.  pnp_cfg with n_cameras = 1 behind rmcv_pnp_load, cam_table behind
@@ -214,6 +221,8 @@ hipError_t launch_compact_armours(const Geom& g, const Bufs& b, const Limits& li
                                   int32_t* d_frame_offs, hipStream_t s, int32_t* d_status_or = nullptr, uint8_t* hd_record = nullptr, int host_head = 0);
 hipError_t launch_status_clear(const Geom& g, const Bufs& b, int mask, hipStream_t s); // status[f] &= ~mask
 hipError_t launch_classify(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s);
+// the classifier of a batch with per-frame models (Geom::models; k_classify_models.hip); launch_classify hands such batches to it
+hipError_t launch_classify_models(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s);
 // stage-wise helpers: binary (host-supplied 0/255 image) -> bit plane
 hipError_t launch_pack_bits(const Geom& g, const Bufs& b, hipStream_t s);
 // contours in findContours order as CSR (for download); d_offs has max_contours+1 entries per frame
@@ -333,6 +342,10 @@ int ctx_enhance(const rmcv_ctx* c);
 int ctx_n_cameras(const rmcv_ctx* c);
 // rmcv_batch_set_device_frame_cameras on what ctx_bind_frames has just bound: nothing is enqueued, nothing blocks
 void ctx_set_frame_cameras(rmcv_ctx* c, const void* d_idx);
+// entries of the context's model table (0: nothing loaded)
+int ctx_n_models(const rmcv_ctx* c);
+// rmcv_batch_set_device_frame_models on what ctx_bind_frames has just bound: nothing is enqueued, nothing blocks
+void ctx_set_frame_models(rmcv_ctx* c, const void* d_idx);
 // the pixel kernel variant of the frames bound last (what the runs on them launch)
 PixelVariant ctx_pixel_variant(const rmcv_ctx* c);
 
@@ -488,7 +501,8 @@ hipError_t launch_svm_predict(const uint8_t* d_samples, int n, const float* d_we
 int svm_train_rows(rmcv_ctx* c, const uint8_t* d_samples, const uint8_t* samples, const int32_t* responses, int n, const int32_t* perm,
                    const rmcv_svm_train_params* params, float* weights_out, double* rho_out, int32_t* labels_out, int32_t* n_class_out,
                    rmcv_svm_train_report* report);
-int svm_predict_rows(rmcv_ctx* c, const uint8_t* d_samples, const uint8_t* samples, int n, int32_t* identity_out);
+// model: an entry of the context's model table (its caller has checked it); -1: the single model's buffers, which hold entry 0
+int svm_predict_rows(rmcv_ctx* c, const uint8_t* d_samples, const uint8_t* samples, int n, int32_t* identity_out, int model = -1);
 
 // ---- the dataset harvest (k_harvest.hip, rmcv_harvest.hip) ----
 // what is read of a dataset outside rmcv_harvest.hip, the one unit that knows struct rmcv_dataset

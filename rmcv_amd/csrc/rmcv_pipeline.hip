@@ -115,6 +115,8 @@ struct rmcv_pipeline {
     const char* last_what = "nothing"; // the enqueue made last (PCHK's label): named when a wait runs out
     const void* cam_idx = nullptr;     // rmcv_pipeline_set_frame_cameras: the frames' camera indices (device, borrowed), for every pose submit
     int cam_frames = 0;
+    const void* model_idx = nullptr;   // rmcv_pipeline_set_frame_models: the frames' model indices (device, borrowed), for every submit with the classifier
+    int model_frames = 0;
     double max_submit_us = 0;          // the longest single submit call (host time) since rmcv_pipeline_reset_stats
     // rmcv_pipeline_set_views: every following batch renders these frames behind its sparse stage (n == 0: off)
     struct Views {
@@ -586,6 +588,14 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
         for (size_t i = 1; i < pl->ring.size(); i++) agree &= ctx_n_cameras(pl->ring[i]) == ctx_n_cameras(pl->ring[0]);
         if (const char* no = cameras_refusal(q.n_frames, pl->cam_frames, agree, msg)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
     }
+    // ... and the sticky model index table (rmcv_pipeline_set_frame_models) when it has the classifier
+    const bool models = pl->model_idx && (stages & RMCV_STAGE_IDENTITY);
+    if (models) {
+        bool agree = true;
+        char msg[200];
+        for (size_t i = 1; i < pl->ring.size(); i++) agree &= ctx_n_models(pl->ring[i]) == ctx_n_models(pl->ring[0]);
+        if (const char* no = pipeline_models_refusal(q.n_frames, pl->model_frames, agree, msg)) return pfail(pl, RMCV_ERR_BAD_ARG, no);
+    }
     // what the legacy matcher and per-frame keys refuse of the context's options (a Bayer input format, RMCV_OPT_ENHANCE); what windows and
     // the options refuse of each other: the binding below, as for every batch
     if ((lp || q.d_camps) && (rc = ctx_check_modes(c, q.d_camps != nullptr, lp != nullptr))) return cfail(pl, c, rc);
@@ -618,6 +628,7 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
     rc = ctx_bind_frames(c, q.d_frames, q.n_frames, q.w, q.h, q.stride, q.frame_pitch, A, q.d_origins, q.win_w, q.win_h, q.d_camps, q.d_lower_bounds);
     if (rc) return cfail(pl, c, rc);
     if (cameras) ctx_set_frame_cameras(c, pl->cam_idx); // (read by the batch's k_pnp, on its stream)
+    if (models) ctx_set_frame_models(c, pl->model_idx); // (read by the batch's k_classify_models, on its stream)
     const int pixel = stages & (RMCV_STAGE_BINARY | RMCV_STAGE_NO_IMAGE), sparse = stages & ~(RMCV_STAGE_BINARY | RMCV_STAGE_NO_IMAGE);
     ctx_external_order(c, S.ev_done);
     // a burst's second pixel launch is held back (batch_plan.h: hold_back, which says when each of these is asked)
@@ -705,6 +716,15 @@ int rmcv_pipeline_set_frame_cameras(rmcv_pipeline* pl, const void* d_idx, int n_
     if (d_idx && (n_frames < 1 || n_frames > pl->lim.max_frames)) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_frame_cameras: n_frames out of range");
     pl->cam_idx = d_idx;
     pl->cam_frames = d_idx ? n_frames : 0;
+    return RMCV_OK;
+}
+
+int rmcv_pipeline_set_frame_models(rmcv_pipeline* pl, const void* d_idx, int n_frames)
+{
+    if (!pl) return RMCV_ERR_BAD_ARG;
+    if (d_idx && (n_frames < 1 || n_frames > pl->lim.max_frames)) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_frame_models: n_frames out of range");
+    pl->model_idx = d_idx;
+    pl->model_frames = d_idx ? n_frames : 0;
     return RMCV_OK;
 }
 

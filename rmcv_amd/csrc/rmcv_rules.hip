@@ -9,6 +9,7 @@
 #include "../../include/rmcv_abi.h"
 #include "bind_plan.h"
 #include "enhance_math.h"
+#include "model_plan.h"
 #include "device_track.h"
 
 using namespace rmcv;
@@ -63,6 +64,9 @@ void rmcv_default_pnp_config(rmcv_pnp_config* c)
 
 /* the rule from a raw index to the table entry k_pnp uses (frame_camera_eff, the function it runs): host-side, no context, no device */
 int rmcv_frame_camera(int32_t idx, int32_t n_cameras) { return frame_camera_eff(idx, n_cameras); }
+
+/* ... and to the model-table entry k_classify_models uses (frame_model_eff, model_plan.h) */
+int rmcv_frame_model(int32_t idx, int32_t n_models) { return frame_model_eff(idx, n_models); }
 
 // ---- tracker bookkeeping: host-side, see include/rmcv_abi.h --------------------------------------------------
 namespace {

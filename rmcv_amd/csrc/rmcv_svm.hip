@@ -108,6 +108,18 @@ int rmcv_svm_predict(rmcv_ctx* c, const uint8_t* samples, int n, int32_t* identi
     return svm_predict_rows(c, nullptr, samples, n, identity_out);
 }
 
+int rmcv_svm_predict_model(rmcv_ctx* c, int model, const uint8_t* samples, int n, int32_t* identity_out)
+{
+    if (!c || n < 0 || (n && (!samples || !identity_out))) return RMCV_ERR_BAD_ARG;
+    if (!c->bufs.svm_w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_svm_predict needs a model: rmcv_svm_load first");
+    if (model < 0 || model >= c->bufs.svm_models) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "rmcv_svm_predict_model: model %d is outside the table (0 .. %d)", model, c->bufs.svm_models - 1);
+        return fail(c, RMCV_ERR_BAD_ARG, msg);
+    }
+    return svm_predict_rows(c, nullptr, samples, n, identity_out, model);
+}
+
 int rmcv_svm_train(rmcv_ctx* c, const uint8_t* samples, const int32_t* responses, int n, const int32_t* perm, const rmcv_svm_train_params* params,
                    float* weights_out, double* rho_out, int32_t* labels_out, int32_t* n_class_out, rmcv_svm_train_report* report)
 {
@@ -121,7 +133,7 @@ int rmcv_svm_train(rmcv_ctx* c, const uint8_t* samples, const int32_t* responses
 
 namespace rmcv {
 
-int svm_predict_rows(rmcv_ctx* c, const uint8_t* d_rows, const uint8_t* samples, int n, int32_t* identity_out)
+int svm_predict_rows(rmcv_ctx* c, const uint8_t* d_rows, const uint8_t* samples, int n, int32_t* identity_out, int model)
 {
     if (!c->bufs.svm_w) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_svm_predict needs a model: rmcv_svm_load first");
     if (n > (1 << 20)) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_svm_predict: more than 1048576 rows in one call");
@@ -134,7 +146,11 @@ int svm_predict_rows(rmcv_ctx* c, const uint8_t* d_rows, const uint8_t* samples,
     if (e == hipSuccess) e = ws.get(&d_out, (size_t)n * sizeof(int32_t));
     if (e != hipSuccess) return fail(c, RMCV_ERR_NOMEM, "svm predict workspace", e);
     if (!d_rows) HIPCHK(c, hipMemcpy(d_samples, samples, (size_t)n * SVM_NFEAT, hipMemcpyHostToDevice), "H2D svm samples");
-    HIPCHK(c, launch_svm_predict(d_samples, n, c->bufs.svm_w, c->bufs.svm_rho, c->bufs.svm_classes, nullptr, 0, 1, c->bufs.svm_labels, d_out, c->stream), "k_svm_predict");
+    if (model >= 0) { // the entry's own rows of the table: the same kernel, the same arithmetic
+        const SvmModelEntry* E = c->bufs.svm_table + model;
+        HIPCHK(c, launch_svm_predict(d_samples, n, &E->weights[0][0], E->rho, c->model_classes[model], nullptr, 0, 1, E->labels, d_out, c->stream), "k_svm_predict");
+    } else
+        HIPCHK(c, launch_svm_predict(d_samples, n, c->bufs.svm_w, c->bufs.svm_rho, c->bufs.svm_classes, nullptr, 0, 1, c->bufs.svm_labels, d_out, c->stream), "k_svm_predict");
     WAITCHK(c, wait_stream(c, c->stream, "rmcv_svm_predict"));
     HIPCHK(c, hipMemcpy(identity_out, d_out, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost), "D2H svm identities");
     return RMCV_OK;

@@ -77,6 +77,13 @@ class Pipeline:
         self._chk(self._lib.rmcv_pipeline_get_info(self._h, C.byref(o)))
         return o
 
+    def set_frame_models(self, d_idx, n=0, keepalive=None):
+        """the frames' model indices for every following submit with STAGE_IDENTITY (rmcv_pipeline_set_frame_models): d_idx a device pointer
+        to n int32, borrowed until replaced (keepalive= is held for that long); None: off.  Load the models into every slot first:
+        `for c in pipeline.contexts: c.svm_load_models(models)`.  The device camps table of submit_camps may be the same buffer."""
+        self._models_ref = keepalive if d_idx else None
+        self._chk(self._lib.rmcv_pipeline_set_frame_models(self._h, C.c_void_p(int(d_idx)) if d_idx else None, int(n)))
+
     def set_frame_cameras(self, d_idx, n=0, keepalive=None):
         """the frames' camera indices for every following submit with STAGE_POSE (rmcv_pipeline_set_frame_cameras): d_idx a device pointer
         to n int32, borrowed until replaced (keepalive= is held for that long); None: off.  Load the cameras into every slot first:

@@ -91,6 +91,10 @@ class Model:
         ctx.svm_load(self.weights, self.rho, self.labels)
         return ctx
 
+    def as_entry(self):
+        """(weights, rho, labels): one entry of Context.svm_load_models' table"""
+        return self.weights, self.rho, self.labels
+
     def predict(self, samples):
         """rmcv_svm_predict_host: the labels of uint8 [n, 1200] rows, on the CPU"""
         s = _rows(samples)
@@ -120,6 +124,12 @@ class Model:
         rho = np.frombuffer(b, "<f8", n_df, at + 4 * n_class)
         weights = np.frombuffer(b, "<f4", n_df * abi.SVM_FEATURES, at + 4 * n_class + 8 * n_df)
         return cls(weights, rho, labels)
+
+
+def load_models(ctx, models):
+    """rmcv_svm_load_models: the Models `models` as ctx's model table, one per colour or per robot (Context.set_frame_models picks per frame)"""
+    ctx.svm_load_models([m.as_entry() for m in models])
+    return ctx
 
 
 def gram(samples, ctx=None):
