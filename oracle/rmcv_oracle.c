@@ -319,6 +319,25 @@ double orc_contour_area(const orc_point* pts, int n)
  * eigen-solver, the direct fit's finish, the Jacobi / normal-equation solver and the general fit; a test reads and clears them
  * (orc_census_read).  Counting only: no counter is ever read by the arithmetic.  Per thread, so that threaded callers share no
  * cache line. */
+/* ... and of the icon path (tests/test_icon_cases_cpu.py): the clamp, the box, the 6x6 LU per column, the inversion, the warp (only at
+ * the pixels the resize reads: the device computes no others), the resize and the one-vs-one vote.  Every name starts icon_ or vote_. */
+#define ORC_CENSUS_LU(X, i) X(icon_lu_col##i##_swap) X(icon_lu_col##i##_no_swap) X(icon_lu_col##i##_singular)
+#define ORC_CENSUS_ICON(X)                                                                                                     \
+    X(icon_clamp_x_below) X(icon_clamp_x_above) X(icon_clamp_x_nan) X(icon_clamp_x_negative_zero) X(icon_clamp_x_inside)       \
+    X(icon_clamp_y_below) X(icon_clamp_y_above) X(icon_clamp_y_nan) X(icon_clamp_y_negative_zero) X(icon_clamp_y_inside)       \
+    X(icon_box_degenerate) X(icon_box_ok)                                                                                      \
+    ORC_CENSUS_LU(X, 0) ORC_CENSUS_LU(X, 1) ORC_CENSUS_LU(X, 2) ORC_CENSUS_LU(X, 3) ORC_CENSUS_LU(X, 4) ORC_CENSUS_LU(X, 5)    \
+    X(icon_invert_det_zero) X(icon_invert_det_nonzero)                                                                         \
+    X(icon_warp_w00_saturated) X(icon_warp_w00_fits) X(icon_warp_tap00_in) X(icon_warp_tap00_out) X(icon_warp_tap01_in)        \
+    X(icon_warp_tap01_out) X(icon_warp_tap10_in) X(icon_warp_tap10_out) X(icon_warp_tap11_in) X(icon_warp_tap11_out)           \
+    X(icon_warp_sx_saturated_high) X(icon_warp_sx_saturated_low) X(icon_warp_sy_saturated_high) X(icon_warp_sy_saturated_low)  \
+    X(icon_warp_v_below) X(icon_warp_v_above) X(icon_warp_v_inside)                                                            \
+    X(icon_resize_area) X(icon_resize_linear) X(icon_resize_sx_negative) X(icon_resize_edge_column)                            \
+    X(icon_resize_edge_clamped) X(icon_resize_edge_not_clamped) X(icon_resize_interior_column) X(icon_resize_sy0_low)          \
+    X(icon_resize_sy0_high) X(icon_resize_sy1_low) X(icon_resize_sy1_high) X(icon_resize_v_below) X(icon_resize_v_above)       \
+    X(icon_resize_v_inside)                                                                                                    \
+    X(vote_sum_positive) X(vote_sum_zero) X(vote_sum_negative) X(vote_sum_nan) X(vote_tie) X(vote_no_tie) X(vote_winner_0)     \
+    X(vote_winner_1) X(vote_winner_2) X(vote_winner_3) X(vote_winner_4) X(vote_winner_5) X(vote_winner_6) X(vote_winner_7)
 #define ORC_CENSUS(X)                                                                                                          \
     X(orthes_reduce) X(orthes_scale_zero) X(orthes_ort_positive) X(orthes_ort_not_positive) X(orthes_accumulate)               \
     X(orthes_accumulate_skipped) X(scan_s_zero) X(one_root) X(real_pair) X(real_pair_p_negative) X(real_pair_z_zero)           \
@@ -334,7 +353,8 @@ double orc_contour_area(const orc_point* pts, int n)
     X(jacobi_apq_negligible) X(jacobi_rotate) X(jacobi_theta_negative) X(normal_lam_not_positive) X(normal_column_dropped)     \
     X(normal_column_used) X(general_fit) X(general_jitter_retry) X(general_no_retry) X(centre_det_zero) X(centre_det_nonzero)  \
     X(finish_c_above_eps) X(finish_c_below_eps) X(finish_rp2_above) X(finish_rp2_below) X(finish_rp3_above)                    \
-    X(finish_rp3_below) X(general_swap) X(general_no_swap) X(angle_wrap_up) X(angle_wrap_down)
+    X(finish_rp3_below) X(general_swap) X(general_no_swap) X(angle_wrap_up) X(angle_wrap_down)                                 \
+    ORC_CENSUS_ICON(X)
 enum {
 #define X(name) CEN_##name,
     ORC_CENSUS(X)
@@ -343,8 +363,9 @@ enum {
 };
 static __thread long long g_census[CEN_COUNT];
 #define CEN(name) (g_census[CEN_##name]++)
-int orc_census_size(void) { return CEN_COUNT; }
-const char* orc_census_name(int i)
+/* the fit's counters come first (orc_census_*), the icon path's behind them (orc_icon_census_*): each test reads and clears its own */
+#define CEN_FIT_COUNT CEN_icon_clamp_x_below
+static const char* census_name_at(int i)
 {
     static const char* const names[CEN_COUNT] = {
 #define X(name) #name,
@@ -353,13 +374,19 @@ const char* orc_census_name(int i)
     };
     return (i >= 0 && i < CEN_COUNT) ? names[i] : "";
 }
-void orc_census_read(long long* out, int clear)
+static void census_read_range(int first, int end, long long* out, int clear)
 {
-    for (int i = 0; i < CEN_COUNT; i++) {
-        if (out) out[i] = g_census[i];
+    for (int i = first; i < end; i++) {
+        if (out) out[i - first] = g_census[i];
         if (clear) g_census[i] = 0;
     }
 }
+int orc_census_size(void) { return CEN_FIT_COUNT; }
+const char* orc_census_name(int i) { return (i >= 0 && i < CEN_FIT_COUNT) ? census_name_at(i) : ""; }
+void orc_census_read(long long* out, int clear) { census_read_range(0, CEN_FIT_COUNT, out, clear); }
+int orc_icon_census_size(void) { return CEN_COUNT - CEN_FIT_COUNT; }
+const char* orc_icon_census_name(int i) { return (i >= 0 && i < CEN_COUNT - CEN_FIT_COUNT) ? census_name_at(CEN_FIT_COUNT + i) : ""; }
+void orc_icon_census_read(long long* out, int clear) { census_read_range(CEN_FIT_COUNT, CEN_COUNT, out, clear); }
 
 static void cdiv_(double xr, double xi, double yr, double yi, double* cr, double* ci)
 {
@@ -1567,7 +1594,8 @@ static int lu_solve6(double A[6][6], double b[6])
         int k = i;
         for (int j = i + 1; j < m; j++)
             if (fabs(A[j][i]) > fabs(A[k][i])) k = j;
-        if (fabs(A[k][i]) < DBL_EPSILON * 100) return 0;
+        if (fabs(A[k][i]) < DBL_EPSILON * 100) { g_census[CEN_icon_lu_col0_singular + 3 * i]++; return 0; }
+        g_census[(k != i ? CEN_icon_lu_col0_swap : CEN_icon_lu_col0_no_swap) + 3 * i]++; /* the columns' counters are consecutive triples */
         if (k != i) {
             for (int j = i; j < m; j++) { double t = A[i][j]; A[i][j] = A[k][j]; A[k][j] = t; }
             double t = b[i]; b[i] = b[k]; b[k] = t;
@@ -1607,12 +1635,14 @@ static int get_affine_transform(const float src[3][2], const float dst[3][2], do
 /* [OCV] cv::warpAffine(src ROI, dst, M, dsize = src size, INTER_LINEAR, BORDER_CONSTANT 0) for CV_8UC3:
  * the matrix is inverted, source coordinates are computed in 1/1024 px fixed point and quantised to 1/32 px
  * (INTER_BITS = 5), the four taps are blended with 15-bit weights (32 - fx)(32 - fy)*32 ... and rounded. */
-static void warp_affine_roi(const uint8_t* src, int sw, int sh, int sstride, const double Min[6], uint8_t* dst /* sw*sh*3 */)
+static void warp_affine_roi(const uint8_t* src, int sw, int sh, int sstride, const double Min[6], uint8_t* dst /* sw*sh*3 */,
+                            const uint8_t* read /* sw*sh: the pixels the resize will read (the census counts only those), or NULL */)
 {
     double M[6];
     memcpy(M, Min, sizeof(M));
     {
         double D = M[0] * M[4] - M[1] * M[3];
+        if (D != 0) CEN(icon_invert_det_nonzero); else CEN(icon_invert_det_zero);
         D = D != 0 ? 1. / D : 0;
         double A11 = M[4] * D, A22 = M[0] * D;
         M[0] = A11; M[1] *= -D;
@@ -1630,10 +1660,25 @@ static void warp_affine_roi(const uint8_t* src, int sw, int sh, int sstride, con
             const int adelta = cv_round(M[0] * x * AB_SCALE), bdelta = cv_round(M[3] * x * AB_SCALE);
             const int X = (X0 + adelta) >> (AB_BITS - INTER_BITS), Y = (Y0 + bdelta) >> (AB_BITS - INTER_BITS);
             int sx = X >> INTER_BITS, sy = Y >> INTER_BITS;
+            const int counted = read && read[(size_t)y * sw + x];
+            if (counted) {
+                if (sx > 32767) CEN(icon_warp_sx_saturated_high);
+                if (sx < -32768) CEN(icon_warp_sx_saturated_low);
+                if (sy > 32767) CEN(icon_warp_sy_saturated_high);
+                if (sy < -32768) CEN(icon_warp_sy_saturated_low);
+            }
             if (sx > 32767) sx = 32767; if (sx < -32768) sx = -32768; /* saturate_cast<short> */
             if (sy > 32767) sy = 32767; if (sy < -32768) sy = -32768;
             const int fx = X & (TAB - 1), fy = Y & (TAB - 1);
             int w00 = (TAB - fx) * (TAB - fy) * 32, w01 = fx * (TAB - fy) * 32, w10 = (TAB - fx) * fy * 32, w11 = fx * fy * 32;
+            if (counted) {
+                if (w00 > 32767) CEN(icon_warp_w00_saturated); else CEN(icon_warp_w00_fits);
+                const int y0 = sy >= 0 && sy < sh, y1 = sy + 1 >= 0 && sy + 1 < sh, x0 = sx >= 0 && sx < sw, x1 = sx + 1 >= 0 && sx + 1 < sw;
+                if (y0 && x0) CEN(icon_warp_tap00_in); else CEN(icon_warp_tap00_out);
+                if (y0 && x1) CEN(icon_warp_tap01_in); else CEN(icon_warp_tap01_out);
+                if (y1 && x0) CEN(icon_warp_tap10_in); else CEN(icon_warp_tap10_out);
+                if (y1 && x1) CEN(icon_warp_tap11_in); else CEN(icon_warp_tap11_out);
+            }
             if (w00 > 32767) { w00 = 32767; w11 += 1; } /* saturate_cast<short>(32768) and the table's sum correction */
             uint8_t* d = dst + ((size_t)y * sw + x) * 3;
             for (int c = 0; c < 3; c++) {
@@ -1647,6 +1692,7 @@ static void warp_affine_roi(const uint8_t* src, int sw, int sh, int sstride, con
                     if (sx + 1 >= 0 && sx + 1 < sw) v11 = src[(size_t)(sy + 1) * sstride + 3 * (sx + 1) + c];
                 }
                 int v = (v00 * w00 + v01 * w01 + v10 * w10 + v11 * w11 + (1 << 14)) >> 15;
+                if (counted) { if (v < 0) CEN(icon_warp_v_below); else if (v > 255) CEN(icon_warp_v_above); else CEN(icon_warp_v_inside); }
                 d[c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
             }
         }
@@ -1655,10 +1701,13 @@ static void warp_affine_roi(const uint8_t* src, int sw, int sh, int sstride, con
 
 /* [OCV] cv::resize(src, dst, 20x20, INTER_LINEAR) for CV_8UC3: 11-bit fixed-point coefficients; an exact 2:1
  * decimation is done as INTER_AREA (2x2 box, rounded) */
-static void resize_linear_20(const uint8_t* src, int sw, int sh, uint8_t* dst /* 20*20*3 */)
+/* read != NULL: no pixel is computed and nothing is counted; read[sw*sh] gets a 1 at every source pixel the resize would read */
+static void resize_linear_20(const uint8_t* src, int sw, int sh, uint8_t* dst /* 20*20*3 */, uint8_t* read)
 {
     const int dw = ORC_ICON_SIDE, dh = ORC_ICON_SIDE;
     if (sw == 2 * dw && sh == 2 * dh) {
+        if (read) { memset(read, 1, (size_t)sw * sh); return; }
+        CEN(icon_resize_area);
         for (int y = 0; y < dh; y++)
             for (int x = 0; x < dw; x++)
                 for (int c = 0; c < 3; c++) {
@@ -1672,15 +1721,17 @@ static void resize_linear_20(const uint8_t* src, int sw, int sh, uint8_t* dst /*
     int xofs[ORC_ICON_SIDE], yofs[ORC_ICON_SIDE];
     short ia[ORC_ICON_SIDE][2], ib[ORC_ICON_SIDE][2];
     int xmax = dw;
+    if (!read) CEN(icon_resize_linear);
     for (int dx = 0; dx < dw; dx++) {
         float fx = (float)((dx + 0.5) * scale_x - 0.5);
         int sx = cv_floor_f(fx);
         fx -= sx;
-        if (sx < 0) { fx = 0; sx = 0; }
+        if (sx < 0) { fx = 0; sx = 0; if (!read) CEN(icon_resize_sx_negative); }
         if (sx + 1 >= sw) {
+            if (!read) { CEN(icon_resize_edge_column); if (sx >= sw - 1) CEN(icon_resize_edge_clamped); else CEN(icon_resize_edge_not_clamped); }
             if (dx < xmax) xmax = dx;
             if (sx >= sw - 1) { fx = 0; sx = sw - 1; }
-        }
+        } else if (!read) CEN(icon_resize_interior_column);
         xofs[dx] = sx;
         ia[dx][0] = (short)cv_round((1.f - fx) * 2048);
         ia[dx][1] = (short)cv_round(fx * 2048);
@@ -1695,8 +1746,21 @@ static void resize_linear_20(const uint8_t* src, int sw, int sh, uint8_t* dst /*
     }
     for (int dy = 0; dy < dh; dy++) {
         int sy0 = yofs[dy], sy1 = yofs[dy] + 1;
+        if (!read) {
+            if (sy0 < 0) CEN(icon_resize_sy0_low);
+            if (sy0 > sh - 1) CEN(icon_resize_sy0_high);
+            if (sy1 < 0) CEN(icon_resize_sy1_low);
+            if (sy1 > sh - 1) CEN(icon_resize_sy1_high);
+        }
         if (sy0 < 0) sy0 = 0; if (sy0 > sh - 1) sy0 = sh - 1; /* clip(sy + k, 0, ssize.height) */
         if (sy1 < 0) sy1 = 0; if (sy1 > sh - 1) sy1 = sh - 1;
+        if (read) {
+            for (int dx = 0; dx < dw; dx++) {
+                read[(size_t)sy0 * sw + xofs[dx]] = read[(size_t)sy1 * sw + xofs[dx]] = 1;
+                if (dx < xmax) read[(size_t)sy0 * sw + xofs[dx] + 1] = read[(size_t)sy1 * sw + xofs[dx] + 1] = 1;
+            }
+            continue;
+        }
         for (int dx = 0; dx < dw; dx++)
             for (int c = 0; c < 3; c++) {
                 int r0, r1;
@@ -1709,19 +1773,32 @@ static void resize_linear_20(const uint8_t* src, int sw, int sh, uint8_t* dst /*
                     r1 = src[((size_t)sy1 * sw + sx) * 3 + c] * 2048;
                 }
                 const int v = (((ib[dy][0] * (r0 >> 4)) >> 16) + ((ib[dy][1] * (r1 >> 4)) >> 16) + 2) >> 2;
+                if (v < 0) CEN(icon_resize_v_below); else if (v > 255) CEN(icon_resize_v_above); else CEN(icon_resize_v_inside);
                 dst[(dy * dw + dx) * 3 + c] = (uint8_t)(v < 0 ? 0 : (v > 255 ? 255 : v));
             }
     }
 }
 
+/* std::max(0.0f, std::min(v, lim)) as the standard library defines the two: min(a, b) is b when b < a and a otherwise, max(a, b) is b
+ * when a < b and a otherwise.  A NaN fails every comparison, so min hands it on and max then returns its FIRST argument, +0; -0 is not
+ * below +0, so max returns +0 for it too; +Inf gives lim and -Inf +0. */
+static float clamp_coordinate(float v, float lim)
+{
+    const float t = lim < v ? lim : v;
+    return 0.0f < t ? t : 0.0f;
+}
+
 int orc_affine_correction(const uint8_t* bgr, int w, int h, int stride, float icon[4][2], uint8_t* out)
 {
-    /* imgproc.cpp:11-15 */
+    /* imgproc.cpp:11-15: std::max(0.0f, std::min(v, cols - 1)) */
     for (int i = 0; i < 4; i++) {
-        float vx = icon[i][0] < (float)w - 1 ? icon[i][0] : (float)w - 1; /* std::min(v, cols - 1) */
-        icon[i][0] = 0.0f > vx ? 0.0f : vx;                               /* std::max(0, .) */
-        float vy = icon[i][1] < (float)h - 1 ? icon[i][1] : (float)h - 1;
-        icon[i][1] = 0.0f > vy ? 0.0f : vy;
+        const float vx = icon[i][0], vy = icon[i][1];
+        if (vx != vx) CEN(icon_clamp_x_nan); else if (vx < 0) CEN(icon_clamp_x_below); else if (vx > (float)w - 1) CEN(icon_clamp_x_above);
+        else if (vx == 0 && signbit(vx)) CEN(icon_clamp_x_negative_zero); else CEN(icon_clamp_x_inside);
+        if (vy != vy) CEN(icon_clamp_y_nan); else if (vy < 0) CEN(icon_clamp_y_below); else if (vy > (float)h - 1) CEN(icon_clamp_y_above);
+        else if (vy == 0 && signbit(vy)) CEN(icon_clamp_y_negative_zero); else CEN(icon_clamp_y_inside);
+        icon[i][0] = clamp_coordinate(vx, (float)w - 1);
+        icon[i][1] = clamp_coordinate(vy, (float)h - 1);
     }
     /* :17 boundingRect(vector<Point>(vertices)): Point2f -> Point rounds (cvRound); int points: inclusive box */
     int minx = 0, maxx = 0, miny = 0, maxy = 0;
@@ -1734,7 +1811,8 @@ int orc_affine_correction(const uint8_t* bgr, int w, int h, int stride, float ic
     }
     const int bx = minx, by = miny, bw = maxx - minx + 1, bh = maxy - miny + 1;
     memset(out, 0, ORC_SVM_FEATURES);
-    if (bw <= 0 || bh <= 0 || bx < 0 || by < 0 || bx + bw > w || by + bh > h) return 1;
+    if (bw <= 0 || bh <= 0 || bx < 0 || by < 0 || bx + bw > w || by + bh > h) { CEN(icon_box_degenerate); return 1; }
+    CEN(icon_box_ok);
     /* :18-27 */
     const float srcPts[3][2] = {{icon[1][0] - (float)bx, icon[1][1] - (float)by},
                                 {icon[2][0] - (float)bx, icon[2][1] - (float)by},
@@ -1743,10 +1821,13 @@ int orc_affine_correction(const uint8_t* bgr, int w, int h, int stride, float ic
     double M[6];
     get_affine_transform(srcPts, dstPts, M); /* :28 */
     /* :30-32 warpAffine(source(box), calibration, warp, Size()) -> same size as the ROI; resize to 20x20 */
-    uint8_t* tmp = (uint8_t*)malloc((size_t)bw * bh * 3);
+    uint8_t* tmp = (uint8_t*)malloc((size_t)bw * bh * 4); /* the warped ROI, then the mask of its pixels that the resize reads */
     if (!tmp) return 1;
-    warp_affine_roi(bgr + (size_t)by * stride + 3 * (size_t)bx, bw, bh, stride, M, tmp);
-    resize_linear_20(tmp, bw, bh, out);
+    uint8_t* read = tmp + (size_t)bw * bh * 3;
+    memset(read, 0, (size_t)bw * bh);
+    resize_linear_20(NULL, bw, bh, NULL, read);
+    warp_affine_roi(bgr + (size_t)by * stride + 3 * (size_t)bx, bw, bh, stride, M, tmp, read);
+    resize_linear_20(tmp, bw, bh, out, NULL);
     free(tmp);
     return 0;
 }
@@ -1766,11 +1847,18 @@ int orc_svm_predict(const float* x, int n_feat, const float* weights, const doub
             for (; k < n_feat; k++) s += wv[k] * x[k];
             const float kval = (float)(s * 1.0 + 0.0);
             const double sum = -rho[dfi] + 1.0 * kval;
+            if (sum > 0) CEN(vote_sum_positive); else if (sum == 0) CEN(vote_sum_zero); else if (sum < 0) CEN(vote_sum_negative); else CEN(vote_sum_nan);
             vote[sum > 0 ? i : j]++;
         }
     int best = 0;
     for (int i = 1; i < n_class; i++)
         if (vote[i] > vote[best]) best = i;
+    {
+        int tied = 0;
+        for (int i = 0; i < n_class; i++) tied += i != best && vote[i] == vote[best];
+        if (tied) CEN(vote_tie); else CEN(vote_no_tie);
+        if (best < 8) g_census[CEN_vote_winner_0 + best]++;
+    }
     return labels[best];
 }
 

@@ -100,6 +100,10 @@ void   orc_general_finish(const double* gfp3, double rp0, double rp1, double sca
 int    orc_census_size(void);
 const char* orc_census_name(int i);
 void   orc_census_read(long long* out, int clear);
+/* ... and the icon path's counters (names icon_*, vote_*), kept apart: tests/test_icon_cases_cpu.py */
+int    orc_icon_census_size(void);
+const char* orc_icon_census_name(int i);
+void   orc_icon_census_read(long long* out, int clear);
 double orc_debug_last_det(int k);
 int    orc_debug_last_fit(double* out, int cap);
 void   orc_rrect_points(const orc_rrect* r, float pt[4][2]);            /* cv::RotatedRect::points */

@@ -106,9 +106,10 @@ __device__ __forceinline__ void icon_row(const uint8_t* frame, int f, int lane, 
 #pragma unroll
         for (int i = 0; i < 4; i++) {
             const float vx0 = A->icon[i][0], vy0 = A->icon[i][1];
-            const float vx = vx0 < (float)w - 1 ? vx0 : (float)w - 1, vy = vy0 < (float)h - 1 ? vy0 : (float)h - 1;
-            ic[i][0] = 0.0f > vx ? 0.0f : vx;
-            ic[i][1] = 0.0f > vy ? 0.0f : vy;
+            // std::max(0.0f, std::min(v, lim)): min(a, b) is b when b < a, max(a, b) is b when a < b -- so NaN and -0 both end as +0
+            const float vx = (float)w - 1 < vx0 ? (float)w - 1 : vx0, vy = (float)h - 1 < vy0 ? (float)h - 1 : vy0;
+            ic[i][0] = 0.0f < vx ? vx : 0.0f;
+            ic[i][1] = 0.0f < vy ? vy : 0.0f;
             const int px = cv_round_f(ic[i][0]), py = cv_round_f(ic[i][1]);
             if (i == 0 || px < minx) minx = px;
             if (i == 0 || px > maxx) maxx = px;

@@ -47,8 +47,12 @@ def expected_meta(items, labels, identity, tag, origins=None):
 def clamp_icon(icon, w, h):
     """imgproc.cpp:11-15 on one armour's icon [4, 2] float32: x into [0, w - 1], y into [0, h - 1], in float32 as the reference compares"""
     ic = np.asarray(icon, np.float32).reshape(4, 2).copy()
-    ic[:, 0] = np.maximum(np.float32(0), np.minimum(ic[:, 0], np.float32(w) - np.float32(1)))
-    ic[:, 1] = np.maximum(np.float32(0), np.minimum(ic[:, 1], np.float32(h) - np.float32(1)))
+    lim = np.array([np.float32(w) - np.float32(1), np.float32(h) - np.float32(1)], np.float32)
+    for i in range(4):
+        for k in range(2):                                                    # std::max(0.0f, std::min(v, lim)), scalar by scalar:
+            v = ic[i, k]
+            t = lim[k] if lim[k] < v else v                                   # min(a, b): b when b < a, else a (a NaN stays)
+            ic[i, k] = t if np.float32(0) < t else np.float32(0)              # max(a, b): b when a < b, else a (NaN and -0 give +0)
     return ic
 
 

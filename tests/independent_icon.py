@@ -44,13 +44,18 @@ def bilinear_table():
 _ITAB = bilinear_table()
 
 
-def lu_solve(a, b):
-    """cv::solve(DECOMP_LU) on a small dense system in double: partial pivoting, elimination with alpha = a[j][i] * (-1 / pivot)"""
+def lu_solve(a, b, last_maximum=False):
+    """cv::solve(DECOMP_LU) on a small dense system in double: partial pivoting, elimination with alpha = a[j][i] * (-1 / pivot).
+    last_maximum: what it is NOT -- the pivot search taking the last of equal magnitudes (tests/test_icon_cases_cpu.py shows the case list
+    tells the two apart)"""
     a = np.array(a, np.float64)
     b = np.array(b, np.float64)
     m = len(b)
     for i in range(m):
-        k = i + int(np.argmax(np.abs(a[i:, i])))             # first maximum, as a linear search finds it
+        col = np.abs(a[i:, i])
+        k = i + int(np.argmax(col))                          # first maximum, as a linear search finds it
+        if last_maximum:
+            k = i + len(col) - 1 - int(np.argmax(col[::-1]))
         if abs(a[k, i]) < np.finfo(np.float64).eps * 100:
             return None
         if k != i:
@@ -144,12 +149,24 @@ def resize_to(src, dw, dh):
     return np.clip(v, 0, 255).astype(np.uint8)
 
 
+def clamp_coordinates(v, lim):
+    """std::max(0.0f, std::min(v, lim)) on a float32 array.  The two library functions are defined by ONE comparison each and return
+    their first argument whenever it is false: min(a, b) = b if b < a else a; max(a, b) = b if a < b else a.  So a NaN passes min
+    unchanged and max then answers its first argument, +0; -0 (not less than +0, nor greater) becomes +0 as well.  numpy's
+    minimum / maximum propagate NaN and may keep -0, hence the selects."""
+    v = np.asarray(v, np.float32)
+    lim = np.float32(lim)
+    with np.errstate(invalid="ignore"):
+        t = np.where(lim < v, lim, v).astype(np.float32)
+        return np.where(np.float32(0) < t, t, np.float32(0)).astype(np.float32)
+
+
 def affine_correction(img, icon, side=20):
     """rm::affine_correction(img, icon, {side, side}) -> (out uint8 [side, side, 3] or zeros, icon clamped in place (float32 [4, 2]), rc)"""
     h, w, _ = img.shape
     icon = np.array(icon, np.float32)
-    icon[:, 0] = np.maximum(np.float32(0), np.minimum(icon[:, 0], np.float32(w) - np.float32(1)))
-    icon[:, 1] = np.maximum(np.float32(0), np.minimum(icon[:, 1], np.float32(h) - np.float32(1)))
+    icon[:, 0] = clamp_coordinates(icon[:, 0], np.float32(w) - np.float32(1))
+    icon[:, 1] = clamp_coordinates(icon[:, 1], np.float32(h) - np.float32(1))
     pi = np.rint(icon.astype(np.float64)).astype(np.int64)                  # Point2f -> Point: cvRound
     bx, by = int(pi[:, 0].min()), int(pi[:, 1].min())
     bw, bh = int(pi[:, 0].max()) - bx + 1, int(pi[:, 1].max()) - by + 1

@@ -137,6 +137,20 @@ def census(clear=True):
     return dict(zip(names, list(out)))
 
 
+def icon_census_names():
+    L = lib()
+    L.orc_icon_census_name.restype = C.c_char_p
+    return [L.orc_icon_census_name(i).decode() for i in range(L.orc_icon_census_size())]
+
+
+def icon_census(clear=True):
+    """{branch name: count since the last clear} of this thread's icon rectifications and votes (names icon_*, vote_*)"""
+    names = icon_census_names()
+    out = (C.c_longlong * len(names))()
+    lib().orc_icon_census_read(out, 1 if clear else 0)
+    return dict(zip(names, list(out)))
+
+
 def debug_last_det(k):
     lib().orc_debug_last_det.restype = C.c_double
     return lib().orc_debug_last_det(int(k))

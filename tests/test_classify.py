@@ -87,7 +87,8 @@ def test_classify_parity_single_frame(ctx, oracle):
         assert ga.tobytes() == ra.tobytes(), idx      # icon vertices clamped in place, like the reference
         total += len(arm)
     assert total > 5
-    # icons that leave the frame are clamped; a degenerate (zero-area) icon gives a zero image, not a crash
+    # icons that leave the frame are clamped; a zero-area icon has a 1 x 1 box and a singular system: M = 0, so every output pixel is the
+    # ROI's pixel (0, 0) -- a constant image, not a zero one and not a crash (tests/test_icon_cases_cpu.py asserts it)
     f = synth.frame(3, 640, 480)
     weird = np.zeros(3, oracle.ARMOUR)
     weird[0]["icon"] = [[-50, 600], [-50, -30], [700, -30], [700, 600]]

@@ -7,36 +7,7 @@ import numpy as np
 
 import independent_icon as ind
 import oracle_lib as O
-
-
-def scene(rng, h, w):
-    img = rng.integers(0, 256, (h, w, 3), dtype=np.uint8)
-    img[..., 1] = (np.arange(w)[None, :] * 255 // max(1, w - 1)).astype(np.uint8)      # a ramp: interpolation errors cannot hide in noise
-    yy, xx = np.mgrid[0:h, 0:w]
-    img[..., 2] = ((xx // 7 + yy // 5) % 2 * 200 + 20).astype(np.uint8)                # and a checkerboard: every tap matters
-    return img
-
-
-def random_icon(rng, h, w):
-    kind = rng.integers(0, 6)
-    cx, cy = rng.uniform(0, w), rng.uniform(0, h)
-    if kind == 0:                                             # exact 40 x 40 box: the 2:1 area branch of resize
-        x0, y0 = int(rng.integers(0, w - 41)), int(rng.integers(0, h - 41))
-        return np.array([[x0, y0 + 39], [x0, y0], [x0 + 39, y0], [x0 + 39, y0 + 39]], np.float32)
-    if kind == 1:                                             # tiny: 1..4 px boxes (every column clamped in resize)
-        s = rng.uniform(0.3, 3.5)
-        q = np.array([[-s, s], [-s, -s], [s, -s], [s, s]]) * 0.5 + (cx, cy)
-        return q.astype(np.float32)
-    sx, sy = rng.uniform(4, 160), rng.uniform(4, 160)
-    ang = rng.uniform(-0.6, 0.6)
-    base = np.array([[-sx, sy], [-sx, -sy], [sx, -sy], [sx, sy]]) * 0.5        # [0] bottom-left, [1] top-left, [2] top-right, [3] bottom-right
-    if kind >= 4:
-        base += rng.normal(0, 0.08 * min(sx, sy), base.shape)                  # a sheared / perspective-looking quad
-    r = np.array([[np.cos(ang), -np.sin(ang)], [np.sin(ang), np.cos(ang)]])
-    q = base @ r.T + (cx, cy)
-    if kind == 3:
-        q += rng.uniform(-0.4, 0.4) * np.array([w, h])                          # partly (or wholly) outside: the clamp of imgproc.cpp:11-15
-    return q.astype(np.float32)
+from icon_cases import random_icon, scene
 
 
 def test_warp_resize_second_opinion_on_1200_regions():
