@@ -176,6 +176,14 @@ typedef struct {
 } orc_pnp_config;
 void orc_default_pnp_config(orc_pnp_config* c);
 int  orc_solve_pnp(const float vertices[4][2], const orc_pnp_config* cfg, double rvec[3], double tvec[3]);
+/* the undistortion of one pixel alone; the solve with its intermediates; the pose's branch census (names pose_*), kept apart from the
+ * fit's and the icon path's: tests/test_pose_cases_cpu.py */
+#define ORC_POSE_TRACE_LEN 45
+void orc_undistort_point(float u, float v, const orc_pnp_config* cfg, float* ox, float* oy);
+int  orc_solve_pnp_trace(const float vertices[4][2], const orc_pnp_config* cfg, double rvec[3], double tvec[3], double* out /* ORC_POSE_TRACE_LEN */);
+int    orc_pose_census_size(void);
+const char* orc_pose_census_name(int i);
+void   orc_pose_census_read(long long* out, int clear);
 void orc_armour_position(const double tvec[3], const double base2gripper[16], const double gripper2camera[16], double pos[3]);
 void orc_locate_armours(const orc_armour* armours, int n, const orc_pnp_config* cfg, const double base2gripper[16] /* NULL = I */,
                         double* rvecs, double* tvecs, double* positions);

@@ -9,8 +9,18 @@
  * Estimation", IJCV 2014): homography of the square, its Jacobian at the origin, the two rotations, each one's
  * least-squares translation, the pose with the smaller reprojection error first.  OpenCV is an un-vendored dependency:
  * the structure follows its implementation as recalled, the homography's closed form and the order of the floating-point
- * operations are this file's own.  PARITY UNPINNED against real OpenCV (see rmcv_oracle.h); tests/test_oracle_pnp.py
- * checks the solver against poses it was not told (forward projection with numpy).
+ * operations are this file's own.
+ *
+ * WHAT IS PINNED, AND BY WHICH FILE.  Bit parity with a real OpenCV build is not pinned (none is available to the tests).  Pinned are:
+ *   - the mathematics, against an independent restatement in mpmath at 200 bits written from the paper and the distortion model, not from
+ *     this file (tests/pose_ref.py): the undistortion within one float32 ulp of the correctly rounded value, both IPPE candidates, the
+ *     pose taken and the rc, on the seeded case list tests/pose_cases.py -- tests/test_pose_cases_cpu.py, bounds in DESIGN.md (pose section);
+ *   - every decision of this file, branch by branch: the pose census below (pose_*, orc_pose_census_*) over that list reaches both sides of
+ *     each, or the counter is listed unreachable with its argument -- tests/test_pose_cases_cpu.py;
+ *   - what wild inputs give (degenerate configurations, NaN / Inf vertices, rotations by pi, collinear pixels under distortion), in raw
+ *     bits -- tests/test_pose_cases_cpu.py::test_named_findings;
+ *   - k_pnp.hip against this file, byte for byte, on every case through every route -- tests/test_gpu_pose_cases.py, tests/test_gpu_pnp.py;
+ *   - recovery of poses it was not told (forward projection with numpy) -- tests/test_oracle_pnp.py.
  */
 #include <float.h>
 #include <math.h>
@@ -24,6 +34,46 @@
 
 static double p_acos(double x) { return orc_get_math_mode() ? acos(x) : pm_acos(x); }
 static double p_sin(double x) { return orc_get_math_mode() ? sin(x) : pm_sin(x); }
+
+/* Branch census of the pose (tests/test_pose_cases_cpu.py): both sides of every decision below, kept apart from the fit's and the icon
+ * path's counters (rmcv_oracle.c).  Counting only: no counter is ever read by the arithmetic.  Per thread. */
+#define ORC_CENSUS_POSE(X)                                                                                                     \
+    X(pose_icdist_negative) X(pose_icdist_not_negative) X(pose_undistort_completed) X(pose_undistort_abandoned)                \
+    X(pose_den_not_positive) X(pose_den_positive) X(pose_antipode) X(pose_antipode_not) X(pose_gamma2_exit) X(pose_gamma2_ok)  \
+    X(pose_gamma_exit) X(pose_gamma_ok) X(pose_b0sq_clamped) X(pose_b0sq_positive) X(pose_b1sq_clamped) X(pose_b1sq_positive)  \
+    X(pose_sp_negative) X(pose_sp_not_negative) X(pose_z_zero) X(pose_z_nonzero) X(pose_ea_greater) X(pose_ea_equal)           \
+    X(pose_ea_less) X(pose_ea_nan) X(pose_w_norm_below_eps) X(pose_w_norm_not_below) X(pose_w_norm_nan)
+enum {
+#define X(name) PCEN_##name,
+    ORC_CENSUS_POSE(X)
+#undef X
+    PCEN_COUNT
+};
+static __thread long long g_pose_census[PCEN_COUNT];
+#define PCEN(name) (g_pose_census[PCEN_##name]++)
+int orc_pose_census_size(void) { return PCEN_COUNT; }
+const char* orc_pose_census_name(int i)
+{
+    static const char* const names[PCEN_COUNT] = {
+#define X(name) #name,
+        ORC_CENSUS_POSE(X)
+#undef X
+    };
+    return (i >= 0 && i < PCEN_COUNT) ? names[i] : "";
+}
+void orc_pose_census_read(long long* out, int clear)
+{
+    for (int i = 0; i < PCEN_COUNT; i++) {
+        if (out) out[i] = g_pose_census[i];
+        if (clear) g_pose_census[i] = 0;
+    }
+}
+
+/* what one solve hands on between its steps (orc_solve_pnp_trace); filled only when asked for, never read by the arithmetic */
+typedef struct {
+    double img[8], H[9], Ra[9], Rb[9], ta[3], tb[3], ea, eb, taken, rc;
+} pose_trace;
+_Static_assert(sizeof(pose_trace) == ORC_POSE_TRACE_LEN * sizeof(double), "orc_solve_pnp_trace's layout");
 
 /* executable/main.cpp:7-19: every literal carries an `f` suffix, i.e. it is a float widened to double */
 void orc_default_pnp_config(orc_pnp_config* c)
@@ -51,24 +101,36 @@ static void undistort_point(float u, float v, const double* K, const double* k, 
     const double ifx = 1. / fx, ify = 1. / fy;
     double x = ((double)u - cx) * ifx, y = ((double)v - cy) * ify;
     const double x0 = x, y0 = y;
+    int abandoned = 0;
     for (int j = 0; j < 5; j++) {
         const double r2 = x * x + y * y;
         const double icdist = (1 + ((0 * r2 + 0) * r2 + 0) * r2) / (1 + ((k[4] * r2 + k[1]) * r2 + k[0]) * r2);
         if (icdist < 0) { /* OpenCV gives up on the point and returns the undistorted guess */
+            PCEN(pose_icdist_negative);
+            PCEN(pose_undistort_abandoned);
             x = ((double)u - cx) * ifx;
             y = ((double)v - cy) * ify;
+            abandoned = 1;
             break;
         }
+        PCEN(pose_icdist_not_negative);
         const double deltaX = 2 * k[2] * x * y + k[3] * (r2 + 2 * x * x);
         const double deltaY = k[2] * (r2 + 2 * y * y) + 2 * k[3] * x * y;
         x = (x0 - deltaX) * icdist;
         y = (y0 - deltaY) * icdist;
     }
+    if (!abandoned) PCEN(pose_undistort_completed);
     { /* the narrowing IS the semantics (dst is CV_32FC2): keep it out of the optimiser's reach */
         volatile float fx32 = (float)x, fy32 = (float)y;
         *ox = fx32;
         *oy = fy32;
     }
+}
+
+/* one point through the undistortion alone (tests/test_pose_cases_cpu.py compares it with tests/pose_ref.py) */
+void orc_undistort_point(float u, float v, const orc_pnp_config* cfg, float* ox, float* oy)
+{
+    undistort_point(u, v, cfg->camera_matrix, cfg->dist, ox, oy);
 }
 
 /* homography from the canonical square (-h, h), (h, h), (h, -h), (-h, -h) to the four (normalised) image points q0..q3,
@@ -106,10 +168,12 @@ static void rotate_vec_to_z(const double a[3], double R[9])
     az = az / nrm;
     const double c = az;
     if (fabs(1.0 + c) < DBL_EPSILON) {
+        PCEN(pose_antipode);
         memset(R, 0, 9 * sizeof(double));
         R[0] = 1.0; R[4] = 1.0; R[8] = -1.0;
         return;
     }
+    PCEN(pose_antipode_not);
     const double d = 1.0 / (1.0 + c);
     const double ax2 = ax * ax, ay2 = ay * ay, axay = ax * ay;
     R[0] = -ax2 * d + 1.0; R[1] = -axay * d;       R[2] = -ax;
@@ -133,14 +197,25 @@ static int compute_rotations(double j00, double j01, double j10, double j11, dou
     /* largest singular value of A */
     const double ata00 = a00 * a00 + a01 * a01, ata01 = a00 * a10 + a01 * a11, ata11 = a10 * a10 + a11 * a11;
     const double gamma2 = 0.5 * (ata00 + ata11 + sqrt((ata00 - ata11) * (ata00 - ata11) + 4.0 * ata01 * ata01));
-    if (!(gamma2 >= 0)) return 1;
+    if (!(gamma2 >= 0)) {
+        PCEN(pose_gamma2_exit);
+        return 1;
+    }
+    PCEN(pose_gamma2_ok);
     const double gamma = sqrt(gamma2);
-    if (fabs(gamma) < DBL_EPSILON) return 1;
+    if (fabs(gamma) < DBL_EPSILON) {
+        PCEN(pose_gamma_exit);
+        return 1;
+    }
+    PCEN(pose_gamma_ok);
     const double rt00 = a00 / gamma, rt01 = a01 / gamma, rt10 = a10 / gamma, rt11 = a11 / gamma;
     double b0sq = -rt00 * rt00 - rt10 * rt10 + 1.0, b1sq = -rt01 * rt01 - rt11 * rt11 + 1.0;
     double b0 = sqrt(b0sq > 0 ? b0sq : 0.0), b1 = sqrt(b1sq > 0 ? b1sq : 0.0);
+    if (b0sq > 0) PCEN(pose_b0sq_positive); else PCEN(pose_b0sq_clamped);
+    if (b1sq > 0) PCEN(pose_b1sq_positive); else PCEN(pose_b1sq_clamped);
     const double sp = -rt00 * rt01 - rt10 * rt11;
     if (sp < 0) b1 = -b1;
+    if (sp < 0) PCEN(pose_sp_negative); else PCEN(pose_sp_not_negative);
     const double c0 = b1 * rt10 - b0 * rt11, c1 = b0 * rt01 - b1 * rt00, c2 = rt00 * rt11 - rt01 * rt10;
     const double rv[3][3] = {{rv00, rv01, rv02}, {rv10, rv11, rv12}, {rv20, rv21, rv22}};
     for (int i = 0; i < 3; i++) {
@@ -191,9 +266,11 @@ static void rot2vec(const double R[9], double r[3])
     const double w_norm = p_acos((trace - 1.0) / 2.0);
     const double eps = (double)FLT_EPSILON;
     if (w_norm < eps) {
+        PCEN(pose_w_norm_below_eps);
         r[0] = r[1] = r[2] = 0;
         return;
     }
+    if (w_norm != w_norm) PCEN(pose_w_norm_nan); else PCEN(pose_w_norm_not_below);
     const double d = 1 / (2 * p_sin(w_norm)) * w_norm;
     r[0] = d * (R[7] - R[5]);
     r[1] = d * (R[2] - R[6]);
@@ -209,6 +286,7 @@ static float reproj_error(const double obj[4][2], const double img[4][2], const 
         const double Y = R[3] * obj[i][0] + R[4] * obj[i][1] + t[1];
         const double Z = R[6] * obj[i][0] + R[7] * obj[i][1] + t[2];
         const double z = Z != 0 ? 1. / Z : 1.;
+        if (Z != 0) PCEN(pose_z_nonzero); else PCEN(pose_z_zero);
         const float dx = (float)(X * z) - (float)img[i][0], dy = (float)(Y * z) - (float)img[i][1];
         err += dx * dx + dy * dy;
     }
@@ -217,7 +295,7 @@ static float reproj_error(const double obj[4][2], const double img[4][2], const 
 
 /* rm::solve_PnP(armour.vertices, cammat, discof, {27, 27}) -- mobility.cpp:166-190 with the default ROI (0,0,0,0).
  * Returns 0, or 1 when the four points are degenerate (then rvec/tvec are zero). */
-int orc_solve_pnp(const float vertices[4][2], const orc_pnp_config* cfg, double rvec[3], double tvec[3])
+static int solve_pnp(const float vertices[4][2], const orc_pnp_config* cfg, double rvec[3], double tvec[3], pose_trace* tr)
 {
     /* mobility.cpp:175-185: object corners (-w/2, h/2), (w/2, h/2), (w/2, -h/2), (-w/2, -h/2); image points 1, 2, 3, 0 */
     const float hw = cfg->square_w / 2.0f, hhgt = cfg->square_h / 2.0f;
@@ -230,6 +308,7 @@ int orc_solve_pnp(const float vertices[4][2], const orc_pnp_config* cfg, double 
         img[i][0] = nx;
         img[i][1] = ny;
     }
+    if (tr) memcpy(tr->img, img, sizeof(tr->img));
     rvec[0] = rvec[1] = rvec[2] = tvec[0] = tvec[1] = tvec[2] = 0;
     /* solveSquare: side length from the first two object points (float arithmetic) */
     const float ddx = (float)obj[1][0] - (float)obj[0][0], ddy = (float)obj[1][1] - (float)obj[0][1];
@@ -237,9 +316,14 @@ int orc_solve_pnp(const float vertices[4][2], const orc_pnp_config* cfg, double 
     double H[9];
     {
         const double den = (img[1][0] - img[2][0]) * (img[3][1] - img[2][1]) - (img[3][0] - img[2][0]) * (img[1][1] - img[2][1]);
-        if (!(fabs(den) > 0)) return 1;
+        if (!(fabs(den) > 0)) {
+            PCEN(pose_den_not_positive);
+            return 1;
+        }
+        PCEN(pose_den_positive);
     }
     homography_from_square(img, square_length / 2.0, H);
+    if (tr) memcpy(tr->H, H, sizeof(tr->H));
 #ifdef ORC_PNP_DEBUG
     printf("img %a %a %a %a %a %a %a %a\n", img[0][0], img[0][1], img[1][0], img[1][1], img[2][0], img[2][1], img[3][0], img[3][1]);
     printf("sq %a H %a %a %a %a %a %a %a %a\n", square_length, H[0], H[1], H[2], H[3], H[4], H[5], H[6], H[7]);
@@ -251,9 +335,38 @@ int orc_solve_pnp(const float vertices[4][2], const orc_pnp_config* cfg, double 
     compute_translation(obj, img, Rb, tb);
     const float ea = reproj_error(obj, img, Ra, ta), eb = reproj_error(obj, img, Rb, tb);
     const int first_a = !(ea > eb); /* the poses are swapped only when the first one is strictly worse */
+    if (ea > eb) PCEN(pose_ea_greater); else if (ea == eb) PCEN(pose_ea_equal); else if (ea < eb) PCEN(pose_ea_less); else PCEN(pose_ea_nan);
+    if (tr) {
+        memcpy(tr->Ra, Ra, sizeof(Ra));
+        memcpy(tr->Rb, Rb, sizeof(Rb));
+        memcpy(tr->ta, ta, sizeof(ta));
+        memcpy(tr->tb, tb, sizeof(tb));
+        tr->ea = ea;
+        tr->eb = eb;
+        tr->taken = first_a ? 0 : 1;
+    }
     rot2vec(first_a ? Ra : Rb, rvec);
     memcpy(tvec, first_a ? ta : tb, 3 * sizeof(double));
     return 0;
+}
+
+int orc_solve_pnp(const float vertices[4][2], const orc_pnp_config* cfg, double rvec[3], double tvec[3])
+{
+    return solve_pnp(vertices, cfg, rvec, tvec, NULL);
+}
+
+/* orc_solve_pnp with what it computed on the way, as ORC_POSE_TRACE_LEN doubles: the four narrowed image points (8), H (9), both rotations
+ * (9 + 9), both translations (3 + 3), both errors, which pose was taken (0 = the first, 1 = the second), the rc.  What an early exit never
+ * reached is NaN (taken: -1). */
+int orc_solve_pnp_trace(const float vertices[4][2], const orc_pnp_config* cfg, double rvec[3], double tvec[3], double* out)
+{
+    pose_trace tr;
+    double* d = (double*)&tr;
+    for (int i = 0; i < ORC_POSE_TRACE_LEN; i++) d[i] = NAN;
+    tr.taken = -1;
+    tr.rc = solve_pnp(vertices, cfg, rvec, tvec, &tr);
+    memcpy(out, &tr, sizeof(tr));
+    return (int)tr.rc;
 }
 
 /* main.cpp:186-192: world = h_base2gripper * (h_gripper2camera * [tvec; 1]); row-major 4x4, dot products left to right */

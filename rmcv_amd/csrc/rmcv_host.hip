@@ -471,13 +471,18 @@ static int get_effective_table(rmcv_ctx* c, T* out, int cap, bool on, const T* d
     return RMCV_OK;
 }
 
-// the armour counts of the frames bound and their sum: what the gathers go by
+// the armour counts of the frames bound and their sum: what the gathers go by.  The detection kernels never leave a count beyond max_armours
+// (they clamp and set RMCV_FRAME_OVF_ARMOURS), but a caller who writes the table through rmcv_batch_device_views may: the kernels behind it
+// (k_pnp, the classifier, the harvest) then take rows 0 .. min(n, max_armours) - 1, and so do the gathers -- a frame's block has no more rows.
 static int armour_counts(rmcv_ctx* c, std::vector<int32_t>& cnt, int64_t* total)
 {
     cnt.resize(c->geom.n_frames);
     HIPCHK(c, hipMemcpy(cnt.data(), c->bufs.n_armours, cnt.size() * 4, hipMemcpyDeviceToHost), "D2H");
     *total = 0;
-    for (const int32_t n : cnt) *total += n;
+    for (int32_t& n : cnt) {
+        n = n < 0 ? 0 : (n > c->lim.max_armours ? c->lim.max_armours : n);
+        *total += n;
+    }
     return RMCV_OK;
 }
 // the first cnt[f] rows of every frame's block of a device table [frame][max_armours], frame after frame

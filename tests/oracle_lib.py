@@ -373,6 +373,48 @@ def solve_pnp(vertices, cfg=None):
     return rc, r, t
 
 
+# ---- the pose's branch census, the undistortion alone and the solve with its intermediates (tests/pose_cases.py, test_pose_cases_cpu.py)
+POSE_TRACE_FIELDS = [("img", 8), ("H", 9), ("Ra", 9), ("Rb", 9), ("ta", 3), ("tb", 3), ("ea", 1), ("eb", 1), ("taken", 1), ("rc", 1)]
+
+
+def pose_census_names():
+    L = lib()
+    L.orc_pose_census_name.restype = C.c_char_p
+    return [L.orc_pose_census_name(i).decode() for i in range(L.orc_pose_census_size())]
+
+
+def pose_census(clear=True):
+    """{branch name: count since the last clear} of this thread's pose solves (names pose_*)"""
+    names = pose_census_names()
+    out = (C.c_longlong * len(names))()
+    lib().orc_pose_census_read(out, 1 if clear else 0)
+    return dict(zip(names, list(out)))
+
+
+def undistort_point(u, v, cfg=None):
+    """cv::undistortPoints of one pixel (float32) -> normalised (x, y) as float32"""
+    cfg = cfg or default_pnp_config()
+    x, y = C.c_float(0), C.c_float(0)
+    lib().orc_undistort_point(C.c_float(u), C.c_float(v), C.byref(cfg), C.byref(x), C.byref(y))
+    return np.float32(x.value), np.float32(y.value)
+
+
+def solve_pnp_trace(vertices, cfg=None):
+    """solve_pnp with its intermediates: (rc, rvec, tvec, dict of POSE_TRACE_FIELDS); what an early exit never reached is NaN, taken -1"""
+    cfg = cfg or default_pnp_config()
+    v = np.ascontiguousarray(vertices, np.float32).reshape(4, 2)
+    r, t = np.zeros(3), np.zeros(3)
+    n = sum(k for _, k in POSE_TRACE_FIELDS)
+    buf = np.zeros(n)
+    rc = lib().orc_solve_pnp_trace(_p(v), C.byref(cfg), _p(r), _p(t), _p(buf))
+    out, o = {}, 0
+    for name, k in POSE_TRACE_FIELDS:
+        out[name] = buf[o:o + k].copy() if k > 1 else buf[o]
+        o += k
+    assert out["rc"] == rc
+    return rc, r, t, out
+
+
 def locate_armours(armours, cfg=None, base2gripper=None):
     """returns (rvecs[n,3], tvecs[n,3], positions[n,3])"""
     cfg = cfg or default_pnp_config()
