@@ -1214,6 +1214,43 @@ int rmcv_pipeline_set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int
  * never issued, its slot has been reused, or it was submitted without views. */
 int rmcv_pipeline_views(rmcv_pipeline* pl, uint64_t ticket, void** d_views, int32_t* stride, int64_t* pitch, int32_t* n);
 
+/* ---- the source view: the camera frame with the loop's overlays, rendered on the device ------------------------------
+ * The operator's view shows what the detector kept; executable/svm/labeler.cpp:108-111 copies the CAMERA FRAME and draws the armours and
+ * light blobs on it -- the picture a person labelling icons, checking an exposure or judging a threshold looks at.  For a frame f of a
+ * batch, flags in 0 .. RMCV_VIEW_ALL and a view size (vw, vh):
+ *     S(f) = resize( draw_armours( draw_lightblobs( SRC(f) ) ), (vw, vh), INTER_LINEAR ),   8UC3, BGR
+ * everything as for V(f) above -- the order of the draws, colours, clipping, the skipped segments, the three resize modes, no text -- but
+ * the canvas: SRC(f), the BGR image the frame's results are defined on:
+ *     BGR frames                                          the frame
+ *     a Bayer RMCV_OPT_INPUT_FORMAT, in any layout        D(T(r)): rmcv_demosaic / rmcv_demosaic_raw of the frame, D's border clamp included
+ *     RMCV_OPT_ENHANCE                                    E(f): every frame byte through the frame's own table, the one the run built
+ *                                                         (overlay colours are drawn afterwards and do not go through it)
+ *     windows                                             the crop at the frame's effective origin, win_w x win_h, in window coordinates
+ * A set overlay pixel replaces the source pixel.  Flags 0 is the plain resized frame, a thumbnail.  Every byte equals the CPU restatement
+ * rmcv_source_view_host of SRC(f) and the frame's lists.  The view is the same with and without RMCV_STAGE_NO_IMAGE.  There is no flag bit
+ * for it: the entry points above keep refusing flags > RMCV_VIEW_ALL. */
+/* rmcv_batch_debug_views' arguments, RMCV_ERR_BAD_ARG list and stage rule.  Asynchronous: enqueued on hip_stream (NULL: the context's)
+ * behind the run.  The kernels read the frames: BORROWED device frames (rmcv_batch_set_device_frames) must stay valid, and unchanged, until
+ * the views have finished on that stream. */
+int rmcv_batch_source_views(rmcv_ctx* ctx, const int32_t* frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch,
+                            void* hip_stream);
+/* one frame's source view to HOST memory; waits with the context's deadline.  Also RMCV_ERR_BAD_ARG: the frame carries an RMCV_FRAME_OVF_*
+ * status (its tables are not the frame's lists). */
+int rmcv_batch_get_source_view(rmcv_ctx* ctx, int frame, int vw, int vh, int flags, uint8_t* out, int out_stride);
+/* stage-wise: a host BGR image (h rows of `stride >= 3 w` bytes) and host lists (as rmcv_debug_view's) through the same kernels, buffers of
+ * its own (nothing bound to the context moves); w, h, vw, vh within the context's max_width / max_height. */
+int rmcv_source_view(rmcv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, const rmcv_lightblob* blobs, int n_blobs,
+                     const rmcv_point* neg_pts, const int32_t* neg_offs, int n_neg, const rmcv_armour* armours, int n_armours, int flags,
+                     int vw, int vh, uint8_t* out, int out_stride);
+/* the same arguments, host-side (no context, no device, any size): the sequential restatement -- the image copied to a BGR canvas, drawn in
+ * the reference's call order, then resized */
+int rmcv_source_view_host(const uint8_t* bgr, int w, int h, int stride, const rmcv_lightblob* blobs, int n_blobs, const rmcv_point* neg_pts,
+                          const int32_t* neg_offs, int n_neg, const rmcv_armour* armours, int n_armours, int flags, int vw, int vh,
+                          uint8_t* out, int out_stride);
+/* a pipeline's source views: rmcv_pipeline_set_views' semantics (allocates HERE, no submit blocks, n == 0: off).  A pipeline renders ONE kind
+ * of view at a time: the later of the two setters wins, and rmcv_pipeline_views returns whichever kind was rendered for the ticket. */
+int rmcv_pipeline_set_source_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags);
+
 /* ---- the session recorder: rm::debug::logger (include/debug.h:13-29, src/debug.cpp:9-41) for frames resident in HBM ----
  * The reference records every frame the detector saw, losslessly (FFV1), with a `data` record per frame.  Here chosen frames of every batch
  * are packed losslessly ON THE DEVICE into a ring of the last `slots` batches, together with what is needed to run the batch again; the

@@ -12,7 +12,7 @@ from .abi import (ARMOUR, BAYER_BG, BAYER_GB, BAYER_GR, BAYER_PATTERNS, BAYER_RG
                   AIM, AIM_INPUT, AIM_HEIGHT_DELTA, AIM_HEIGHT_FIXED, AIM_NO_SOLUTION, AIM_NO_TARGET, AIM_PICK_NEAREST, AIM_PICK_WINDOW, AIM_SRC_FILTER,
                   AIM_SRC_MEASUREMENT, COMPENSATE_CLASSIC, COMPENSATE_NI, COMPENSATE_NONE, delta_height, distance, projectile_angle, rigid_inverse, solve_gea,
                   ATTITUDE, ATTITUDE_CONFIG, ATT_MOTOR_KEEP, ATT_MOTOR_PITCH, SERIAL_PACKET_BYTES, crc8, euler_to_matrix, homogeneous, serial_decode, serial_encode,
-                  VIEW_ALL, VIEW_ARMOURS, VIEW_BLOBS, VIEW_NEGATIVES, debug_view_host)
+                  VIEW_ALL, VIEW_ARMOURS, VIEW_BLOBS, VIEW_NEGATIVES, debug_view_host, source_view_host)
 from .api import Context, debug_view
 from .pipeline import Pipeline
 from .recorder import LoopRecord, Recorder, Session, loop_bound, loop_field_at, loop_trigger, pack, pack_bound, unpack

@@ -121,6 +121,7 @@ EXPORTS = [
     "rmcv_icon_sad", "rmcv_dataset_set_novelty", "rmcv_dataset_novelty", "rmcv_dataset_get_rings", "rmcv_dataset_append_rows", "rmcv_harvest_novel_host",
     "rmcv_frame_model", "rmcv_svm_load_models", "rmcv_batch_set_frame_models", "rmcv_batch_set_device_frame_models", "rmcv_batch_get_frame_models",
     "rmcv_pipeline_set_frame_models", "rmcv_svm_predict_model",
+    "rmcv_batch_source_views", "rmcv_batch_get_source_view", "rmcv_source_view", "rmcv_source_view_host", "rmcv_pipeline_set_source_views",
 ]
 
 
@@ -434,6 +435,12 @@ def load(path):
         L.rmcv_batch_get_debug_view.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.rmcv_pipeline_set_views.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]
         L.rmcv_pipeline_views.argtypes = [C.c_void_p, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        if hasattr(L, "rmcv_source_view_host"):  # (the source view, DESIGN.md 4p: the same argument shapes)
+            L.rmcv_source_view_host.argtypes = view
+            L.rmcv_source_view.argtypes = [C.c_void_p] + view
+            L.rmcv_batch_source_views.argtypes = L.rmcv_batch_debug_views.argtypes
+            L.rmcv_batch_get_source_view.argtypes = L.rmcv_batch_get_debug_view.argtypes
+            L.rmcv_pipeline_set_source_views.argtypes = L.rmcv_pipeline_set_views.argtypes
     if hasattr(L, "rmcv_pack_bound"):  # (builds from before the session recorder stay loadable for A/B runs)
         L.rmcv_pack_bound.restype = C.c_int64
         L.rmcv_pack_bound.argtypes = [C.c_int, C.c_int]
@@ -646,6 +653,26 @@ def debug_view_host(binary, blobs=None, negatives=None, armours=None, size=(1024
     rc = lib().rmcv_debug_view_host(*args)
     if rc:
         raise RmcvError(rc, "rmcv_debug_view_host: sizes >= 1, known flags, contour offsets that do not decrease")
+    return out
+
+
+def source_view_args(bgr, blobs, negatives, armours, flags, size):
+    """view_args for rmcv_source_view and rmcv_source_view_host: bgr (h, w, 3) uint8 in place of the binary, everything else the same"""
+    bgr = np.ascontiguousarray(bgr, np.uint8)
+    assert bgr.ndim == 3 and bgr.shape[2] == 3, "the source view takes an (h, w, 3) BGR image"
+    args, out, keep = view_args(np.zeros(bgr.shape[:2], np.uint8), blobs, negatives, armours, flags, size)
+    args[0], args[3] = ptr(bgr), 3 * bgr.shape[1]
+    return args, out, keep + (bgr,)
+
+
+def source_view_host(bgr, blobs=None, negatives=None, armours=None, size=(1024, 768), flags=VIEW_ALL):
+    """the labeler's picture (executable/svm/labeler.cpp:108-111) at `size` = (vw, vh), on the CPU (rmcv_source_view_host: the sequential
+    restatement, no device): the BGR image with rm::debug::draw_lightblobs and rm::debug::draw_armours (no text) over it, resized
+    INTER_LINEAR -> (vh, vw, 3) uint8 BGR"""
+    args, out, keep = source_view_args(bgr, blobs, negatives, armours, flags, size)
+    rc = lib().rmcv_source_view_host(*args)
+    if rc:
+        raise RmcvError(rc, "rmcv_source_view_host: sizes >= 1, known flags, contour offsets that do not decrease")
     return out
 
 

@@ -601,6 +601,48 @@ class Context:
         self._chk(lib().rmcv_debug_view(self._h, *args))
         return out
 
+    # ---------------------------------------------------------------- the source view
+    def source_views(self, frames, dst=None, size=(1024, 768), flags=abi.VIEW_ALL, stream=None):
+        """the labeler's pictures (executable/svm/labeler.cpp:108-111, no text) of the chosen frames of the batch run last: the frame the
+        results are defined on -- demosaiced, through its gamma table, cropped to its window, as the batch was read -- with the overlays
+        of `flags` over it, rendered on the device at `size` = (vw, vh) (rmcv_batch_source_views; asynchronous, behind the run).  dst: a
+        device pointer of the caller's for n contiguous (vh, vw, 3) views -- then returns None, and borrowed frames must stay valid until
+        the views have finished; without it the views come back as a host (n, vh, vw, 3) uint8 array (synchronises)."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        vw, vh = int(size[0]), int(size[1])
+        pitch = 3 * vw * vh
+        if dst is not None:
+            self._chk(lib().rmcv_batch_source_views(self._h, ptr(fr), len(fr), vw, vh, int(flags), C.c_void_p(int(dst)), 3 * vw, pitch, C.c_void_p(stream or 0)))
+            return None
+        d = C.c_void_p()
+        nbytes = max(len(fr), 1) * max(pitch, 1)
+        if lib().rmcv_device_alloc(self.device, C.c_int64(nbytes), C.byref(d)):
+            raise RmcvError(abi.ERR_NOMEM, "rmcv_device_alloc")
+        try:
+            self._chk(lib().rmcv_batch_source_views(self._h, ptr(fr), len(fr), vw, vh, int(flags), d, 3 * vw, pitch, C.c_void_p(stream or 0)))
+            self.sync()
+            host = np.empty((len(fr), vh, vw, 3), np.uint8)
+            rc = lib().rmcv_device_download(self.device, ptr(host), d, C.c_int64(host.nbytes))
+            if rc:
+                raise RmcvError(rc, "rmcv_device_download")
+            return host
+        finally:
+            lib().rmcv_device_free(self.device, d)
+
+    def source_view(self, frame, size=(1024, 768), flags=abi.VIEW_ALL):
+        """one frame's source view on the host, (vh, vw, 3) uint8 BGR (rmcv_batch_get_source_view; refuses a frame with an overflow status)"""
+        vw, vh = int(size[0]), int(size[1])
+        out = np.empty((max(vh, 0), max(vw, 0), 3), np.uint8)
+        self._chk(lib().rmcv_batch_get_source_view(self._h, int(frame), vw, vh, int(flags), ptr(out), 3 * vw))
+        return out
+
+    def source_view_of(self, bgr, blobs=None, negatives=None, armours=None, size=(1024, 768), flags=abi.VIEW_ALL):
+        """stage-wise: the source view of a host BGR image and host lists through the same kernels (rmcv_source_view; arguments as
+        abi.source_view_host)"""
+        args, out, keep = abi.source_view_args(bgr, blobs, negatives, armours, flags, size)
+        self._chk(lib().rmcv_source_view(self._h, *args))
+        return out
+
     def device_views(self):
         """(armours device pointer, counts device pointer, per-frame capacity, n_frames) for a collective"""
         a, c = C.c_void_p(), C.c_void_p()

@@ -229,17 +229,11 @@ static inline const char* view_check_lists(int w, int h, int stride, const rmcv_
     return nullptr;
 }
 
-// the sequential restatement: a full-resolution BGR canvas drawn in the reference's call order, then resized pixel by pixel
-static inline void view_host(const uint8_t* binary, int w, int h, int stride, const rmcv_lightblob* blobs, int n_blobs, const rmcv_point* neg_pts,
+// what both sequential restatements share behind their canvas's initialisation: the draws on the full-resolution BGR canvas (3 w bytes a
+// row) in the reference's call order, then the resize pixel by pixel
+static inline void view_canvas_finish(std::vector<uint8_t>& canvas, int w, int h, const rmcv_lightblob* blobs, int n_blobs, const rmcv_point* neg_pts,
                const int32_t* neg_offs, int n_neg, const rmcv_armour* armours, int n_armours, int flags, int vw, int vh, uint8_t* out, int out_stride)
 {
-    std::vector<uint8_t> canvas((size_t)3 * w * h);
-    for (int y = 0; y < h; y++) // cvtColor(GRAY2BGR) of a 0 / 255 image (any other non-zero byte counts as 255)
-        for (int x = 0; x < w; x++) {
-            const uint8_t g = binary[(size_t)y * stride + x] ? 255 : 0;
-            uint8_t* p = &canvas[((size_t)y * w + x) * 3];
-            p[0] = p[1] = p[2] = g;
-        }
     int colour = VIEW_YELLOW;
     auto put = [&](int x, int y) {
         uint8_t* p = &canvas[((size_t)y * w + x) * 3];
@@ -276,6 +270,30 @@ static inline void view_host(const uint8_t* binary, int w, int h, int stride, co
             }
         }
     }
+}
+
+// the sequential restatement: a full-resolution BGR canvas drawn in the reference's call order, then resized pixel by pixel
+static inline void view_host(const uint8_t* binary, int w, int h, int stride, const rmcv_lightblob* blobs, int n_blobs, const rmcv_point* neg_pts,
+               const int32_t* neg_offs, int n_neg, const rmcv_armour* armours, int n_armours, int flags, int vw, int vh, uint8_t* out, int out_stride)
+{
+    std::vector<uint8_t> canvas((size_t)3 * w * h);
+    for (int y = 0; y < h; y++) // cvtColor(GRAY2BGR) of a 0 / 255 image (any other non-zero byte counts as 255)
+        for (int x = 0; x < w; x++) {
+            const uint8_t g = binary[(size_t)y * stride + x] ? 255 : 0;
+            uint8_t* p = &canvas[((size_t)y * w + x) * 3];
+            p[0] = p[1] = p[2] = g;
+        }
+    view_canvas_finish(canvas, w, h, blobs, n_blobs, neg_pts, neg_offs, n_neg, armours, n_armours, flags, vw, vh, out, out_stride);
+}
+
+// the source view's: the canvas starts as the BGR image itself (labeler.cpp:108 copies the camera frame), stride >= 3 w
+static inline void source_view_host(const uint8_t* bgr, int w, int h, int stride, const rmcv_lightblob* blobs, int n_blobs, const rmcv_point* neg_pts,
+               const int32_t* neg_offs, int n_neg, const rmcv_armour* armours, int n_armours, int flags, int vw, int vh, uint8_t* out, int out_stride)
+{
+    std::vector<uint8_t> canvas((size_t)3 * w * h);
+    for (int y = 0; y < h; y++)
+        for (int x = 0; x < 3 * w; x++) canvas[(size_t)y * 3 * w + x] = bgr[(size_t)y * stride + x];
+    view_canvas_finish(canvas, w, h, blobs, n_blobs, neg_pts, neg_offs, n_neg, armours, n_armours, flags, vw, vh, out, out_stride);
 }
 
 #endif /* RMCV_DEVICE_VIEW_H */

@@ -1401,7 +1401,8 @@ int ctx_view_prepare(rmcv_ctx* c, int n)
     return RMCV_OK;
 }
 
-int ctx_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
+// the job of n views of the batch bound, the frame list already on the device
+static ViewJob view_job(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch)
 {
     const Geom& g = c->geom;
     const Bufs& b = c->bufs;
@@ -1412,7 +1413,26 @@ int ctx_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh
     j.out = (uint8_t*)d_out; j.out_stride = out_stride; j.out_pitch = out_pitch;
     j.lists = ViewLists{b.blobs, b.n_blobs, b.armours, b.n_armours, b.points, b.cont_start, b.cont_len, b.n_contours, b.neg_idx, b.n_neg, nullptr,
                         c->lim.max_blobs, c->lim.max_armours, c->lim.max_points, c->lim.max_contours, 0};
-    HIPCHK(c, launch_view(j, s), "k_view_overlay + k_view_resize");
+    return j;
+}
+
+int ctx_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
+{
+    HIPCHK(c, launch_view(view_job(c, d_frames, n, vw, vh, flags, d_out, out_stride, out_pitch), s), "k_view_overlay + k_view_resize");
+    return RMCV_OK;
+}
+
+// ---- the source view (k_view_source.hip): the operator's view's entry points over SRC(f); the planes are the same ----
+int ctx_source_view_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int flags, int out_stride, int64_t out_pitch)
+{
+    return refuse(c, source_views_refusal(frames, n, n_frames, stages, view_stages_needed(flags & RMCV_VIEW_ALL), vw, vh, c->lim.max_width, c->lim.max_height, flags,
+                                          out_stride, out_pitch));
+}
+
+int ctx_source_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
+{
+    if (!c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, SOURCE_VIEW_NOTHING_BOUND);
+    HIPCHK(c, launch_source_view(c->geom, c->bufs, view_job(c, d_frames, n, vw, vh, flags, d_out, out_stride, out_pitch), s), "k_view_overlay + k_view_source");
     return RMCV_OK;
 }
 
@@ -1460,6 +1480,54 @@ int rmcv_batch_get_debug_view(rmcv_ctx* c, int frame, int vw, int vh, int flags,
     }
     if ((rc = view_batch(c, &one, 1, vw, vh, flags, c->view_out, 3 * vw, (int64_t)3 * vw * vh, c->stream))) return rc;
     WAITCHK(c, wait_stream(c, c->stream, "k_view_resize"));
+    HIPCHK(c, hipMemcpy2D(out, out_stride, c->view_out, (size_t)3 * vw, (size_t)3 * vw, vh, hipMemcpyDeviceToHost), "D2H view");
+    return RMCV_OK;
+}
+
+} // extern "C"
+
+// rmcv_batch_source_views behind its checks
+static int source_view_batch(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
+{
+    if (!c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, SOURCE_VIEW_NOTHING_BOUND); // (before anything is enqueued)
+    int rc = ctx_view_prepare(c, n);
+    if (rc) return rc;
+    if ((rc = order_begin(c, s))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->view_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D view frames");
+    if ((rc = ctx_source_view_enqueue(c, c->view_frames, n, vw, vh, flags, d_out, out_stride, out_pitch, s))) return rc;
+    return order_end(c, s);
+}
+
+extern "C" {
+
+int rmcv_batch_source_views(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch,
+                            void* hip_stream)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!d_out) return fail(c, RMCV_ERR_BAD_ARG, SOURCE_VIEW_NULL_OUTPUT);
+    const int rc = ctx_source_view_check(c, frames, n, c->geom.n_frames, c->last_stages, vw, vh, flags, out_stride, out_pitch);
+    if (rc) return rc;
+    hipSetDevice(c->device);
+    return source_view_batch(c, frames, n, vw, vh, flags, d_out, out_stride, out_pitch, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int rmcv_batch_get_source_view(rmcv_ctx* c, int frame, int vw, int vh, int flags, uint8_t* out, int out_stride)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!out) return fail(c, RMCV_ERR_BAD_ARG, SOURCE_VIEW_NULL_OUTPUT);
+    const int32_t one = frame;
+    int rc = ctx_source_view_check(c, &one, 1, c->geom.n_frames, c->last_stages, vw, vh, flags, out_stride, 0);
+    if (rc) return rc;
+    if ((rc = ctx_ready(c))) return rc;
+    int32_t st = 0;
+    HIPCHK(c, hipMemcpy(&st, c->bufs.status + frame, 4, hipMemcpyDeviceToHost), "D2H");
+    if (st & (RMCV_FRAME_OVF_CONTOURS | RMCV_FRAME_OVF_POINTS | RMCV_FRAME_OVF_BLOBS | RMCV_FRAME_OVF_ARMOURS)) return fail(c, RMCV_ERR_BAD_ARG, SOURCE_VIEW_OVERFLOW);
+    if (!c->view_out) {
+        const hipError_t e = dalloc(c, &c->view_out, (size_t)3 * c->lim.max_width * c->lim.max_height);
+        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the source view's staging", e);
+    }
+    if ((rc = source_view_batch(c, &one, 1, vw, vh, flags, c->view_out, 3 * vw, (int64_t)3 * vw * vh, c->stream))) return rc;
+    WAITCHK(c, wait_stream(c, c->stream, "k_view_source"));
     HIPCHK(c, hipMemcpy2D(out, out_stride, c->view_out, (size_t)3 * vw, (size_t)3 * vw, vh, hipMemcpyDeviceToHost), "D2H view");
     return RMCV_OK;
 }

@@ -16,6 +16,7 @@
 #include "image_plan.h"
 #include "model_plan.h"
 #include "pixel_plan.h"
+#include "source_view_plan.h"
 #include "sparse_plan.h"
 #include "svm_plan.h"
 #include "tracker_plan.h"
@@ -292,6 +293,28 @@ int ctx_view_prepare(rmcv_ctx* c, int n);
 // (frames: host values; n_frames / stages: the batch the views are of and the stages it has been, or will be, through)
 int ctx_view_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int flags, int out_stride, int64_t out_pitch);
 int ctx_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s);
+
+// ---- the source view (k_view_source.hip): the same views over SRC(f), the BGR image the frame's results are defined on ----
+// view: the job k_view_overlay is launched with as it is (w, h: the extent of SRC, a windowed batch's the window's; bits is never read)
+struct SourceViewJob {
+    ViewJob view;
+    int kind;                    // SourceKind (source_view_plan.h)
+    const uint8_t* src;          // [frame] the frames as bound: BGR or mosaic, rows `stride` bytes apart, frames `frame_pitch`
+    const uint8_t* src_end;      // one past the last byte bound: no load of the kernel's reaches outside src .. src_end
+    int stride;
+    int64_t frame_pitch;
+    int rx, ry, lay;             // a mosaic's R site and layout word (device_bayer.h: raw_rx, raw_ry, raw_layout of T(r))
+    const uint8_t* lut;          // [frame][256] SOURCE_BGR_LUT: Bufs::enh_lut
+    const rmcv_point* win_eff;   // [frame]      SOURCE_BGR_WIN: Bufs::win_eff
+};
+// k_view_overlay + k_view_source<kind> on `s`; every argument has been checked by the caller
+hipError_t launch_source_view(const SourceViewJob& j, hipStream_t s);
+// the same for views of the batch bound to (g, b): the kind and the source fields come from them
+hipError_t launch_source_view(const Geom& g, const Bufs& b, const ViewJob& view, hipStream_t s);
+// (the entry points of a context: rmcv_host.hip; the stage-wise rmcv_source_view: rmcv_stagewise.hip).  What a pipeline needs of them, as
+// of the operator's view: the planes come from ctx_view_prepare, the check takes the frames as host values, the enqueue blocks nothing
+int ctx_source_view_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int flags, int out_stride, int64_t out_pitch);
+int ctx_source_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s);
 
 // ---- what rmcv_pipeline.hip needs of a context beyond the public ABI (rmcv_host.hip) ----
 // external order: the pipeline chains a context's launches with its own events (it knows which stream ran what), so the context

@@ -121,6 +121,7 @@ struct rmcv_pipeline {
     // rmcv_pipeline_set_views: every following batch renders these frames behind its sparse stage (n == 0: off)
     struct Views {
         int n = 0, vw = 0, vh = 0, flags = 0, max_index = 0, need = 0; // need: the stages the flags read the results of
+        bool source = false;           // rmcv_pipeline_set_source_views set them: the source view, not the binary's
         int32_t* d_frames = nullptr;   // [n] the frame list, on the device
     } views;
     // rmcv_pipeline_set_recorder: every following batch packs these frames into the recorder behind its pixel kernel (n == 0: off)
@@ -470,9 +471,10 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
     S.view_n = 0;
     if (P.views) {
         const rmcv_pipeline::Views& V = pl->views; // (as at the submit: rmcv_pipeline_set_views drains first)
-        rc = ctx_view_enqueue(P.c, V.d_frames, V.n, V.vw, V.vh, V.flags, S.d_views, 3 * V.vw, (int64_t)3 * V.vw * V.vh, T);
+        // (the source view also reads the frames, through the effective origins / gamma tables: in front of ev_free for that too, as the harvest is)
+        rc = (V.source ? ctx_source_view_enqueue : ctx_view_enqueue)(P.c, V.d_frames, V.n, V.vw, V.vh, V.flags, S.d_views, 3 * V.vw, (int64_t)3 * V.vw * V.vh, T);
         if (rc) return cfail(pl, P.c, rc);
-        pl->last_what = "k_view_resize";
+        pl->last_what = V.source ? "k_view_source" : "k_view_resize";
         S.view_n = V.n, S.view_w = V.vw, S.view_h = V.vh;
     }
     // the dataset harvest: behind the sparse stage (it reads the armours, and the identities behind the classifier), in front of ev_free (it reads
@@ -542,8 +544,10 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
             return pfail(pl, RMCV_ERR_BAD_ARG, no);
     }
     if (pl->views.n) { // (with no views set: nothing here, and nothing further down)
-        if (q.n_frames <= pl->views.max_index) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch has fewer frames than the debug views name (rmcv_pipeline_set_views)");
-        if ((stages & pl->views.need) != pl->views.need) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch's stages lack what the debug views' flags need (rmcv_pipeline_set_views)");
+        if (q.n_frames <= pl->views.max_index)
+            return pfail(pl, RMCV_ERR_BAD_ARG, pl->views.source ? SOURCE_VIEW_FEWER_FRAMES : "the batch has fewer frames than the debug views name (rmcv_pipeline_set_views)");
+        if ((stages & pl->views.need) != pl->views.need)
+            return pfail(pl, RMCV_ERR_BAD_ARG, pl->views.source ? SOURCE_VIEW_FEWER_STAGES : "the batch's stages lack what the debug views' flags need (rmcv_pipeline_set_views)");
     }
     if (pl->recd.n) { // (with no recorder set: nothing here, and nothing further down)
         if (q.n_frames <= pl->recd.max_index) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch has fewer frames than the recorder's frame list names (rmcv_pipeline_set_recorder)");
@@ -866,7 +870,8 @@ int rmcv_pipeline_record(rmcv_pipeline* pl, uint64_t ticket, void** d_record, vo
     return RMCV_OK;
 }
 
-int rmcv_pipeline_set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags)
+// rmcv_pipeline_set_views and rmcv_pipeline_set_source_views: one set of views per pipeline, of the kind set last
+static int set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags, bool source)
 {
     if (!pl || n < 0) return RMCV_ERR_BAD_ARG;
     hipSetDevice(pl->device);
@@ -878,7 +883,7 @@ int rmcv_pipeline_set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int
         return RMCV_OK;
     }
     rmcv_ctx* c0 = pl->ring[0];
-    if ((rc = ctx_view_check(c0, frames, n, pl->lim.max_frames, ~0, vw, vh, flags, 3 * vw, (int64_t)3 * vw * vh))) return cfail(pl, c0, rc);
+    if ((rc = (source ? ctx_source_view_check : ctx_view_check)(c0, frames, n, pl->lim.max_frames, ~0, vw, vh, flags, 3 * vw, (int64_t)3 * vw * vh))) return cfail(pl, c0, rc);
     pl->views.n = 0; // (off, should anything below fail)
     for (auto c : pl->ring)
         if ((rc = ctx_view_prepare(c, n))) return cfail(pl, c, rc);
@@ -894,14 +899,19 @@ int rmcv_pipeline_set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int
     pl->views.d_frames = nullptr;
     if (e == hipSuccess) e = hipMalloc((void**)&pl->views.d_frames, (size_t)n * 4);
     if (e == hipSuccess) e = hipMemcpy(pl->views.d_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return pfail(pl, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_pipeline_set_views", e);
+    if (e != hipSuccess) return pfail(pl, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, source ? "rmcv_pipeline_set_source_views" : "rmcv_pipeline_set_views", e);
     int top = 0;
     for (int k = 0; k < n; k++) top = frames[k] > top ? frames[k] : top;
     pl->views.vw = vw, pl->views.vh = vh, pl->views.flags = flags, pl->views.max_index = top;
     pl->views.need = view_stages_needed(flags);
+    pl->views.source = source;
     pl->views.n = n;
     return RMCV_OK;
 }
+
+int rmcv_pipeline_set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags) { return set_views(pl, frames, n, vw, vh, flags, false); }
+
+int rmcv_pipeline_set_source_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags) { return set_views(pl, frames, n, vw, vh, flags, true); }
 
 int rmcv_pipeline_set_recorder(rmcv_pipeline* pl, rmcv_recorder* rec, const int32_t* frames, int n)
 {

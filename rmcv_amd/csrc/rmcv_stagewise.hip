@@ -298,4 +298,63 @@ int rmcv_debug_view(rmcv_ctx* c, const uint8_t* binary, int w, int h, int stride
     return rcw;
 }
 
+int rmcv_source_view(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, const rmcv_lightblob* blobs, int n_blobs, const rmcv_point* neg_pts,
+                     const int32_t* neg_offs, int n_neg, const rmcv_armour* armours, int n_armours, int flags, int vw, int vh, uint8_t* out,
+                     int out_stride)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    const char* bad = rmcv::source_image_refusal(bgr, out, w, h, stride);
+    if (!bad) bad = view_check_lists(w, h, w, blobs, n_blobs, neg_pts, neg_offs, n_neg, armours, n_armours, flags, vw, vh, out_stride);
+    if (bad) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "rmcv_source_view: %s", bad);
+        return fail(c, RMCV_ERR_BAD_ARG, msg);
+    }
+    if (w > c->lim.max_width || h > c->lim.max_height || vw > c->lim.max_width || vh > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, rmcv::SOURCE_VIEW_BEYOND_LIMITS);
+    if (const int rc = ctx_ready(c)) return rc;
+    // (a stage-wise helper: buffers of its own, so that nothing bound to the context moves) -- one host block, one upload; the image
+    // packed to rows of 3 w bytes rounded up to 16
+    const int prow = (w + 63) / 64 + 2, n_pts = n_neg ? neg_offs[n_neg] : 0, dstride = (3 * w + 15) & ~15;
+    const size_t plane = (size_t)(h + 2) * prow;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_blobs = (size_t)dstride * h, o_arm = o_blobs + up16((size_t)n_blobs * sizeof(rmcv_lightblob));
+    const size_t o_pts = o_arm + up16((size_t)n_armours * sizeof(rmcv_armour)), o_offs = o_pts + up16((size_t)n_pts * sizeof(rmcv_point));
+    const size_t o_cnt = o_offs + up16((size_t)(n_neg + 1) * 4), in_bytes = o_cnt + 16;
+    const size_t o_ov = in_bytes, o_out = o_ov + up16(2 * plane * 8), total = o_out + (size_t)3 * vw * vh;
+    std::vector<uint8_t> host(in_bytes, 0);
+    for (int y = 0; y < h; y++) memcpy(&host[(size_t)y * dstride], bgr + (size_t)y * stride, (size_t)3 * w);
+    if (n_blobs) memcpy(&host[o_blobs], blobs, (size_t)n_blobs * sizeof(rmcv_lightblob));
+    if (n_armours) memcpy(&host[o_arm], armours, (size_t)n_armours * sizeof(rmcv_armour));
+    if (n_pts) memcpy(&host[o_pts], neg_pts, (size_t)n_pts * sizeof(rmcv_point));
+    if (n_neg) memcpy(&host[o_offs], neg_offs, (size_t)(n_neg + 1) * 4);
+    const int32_t counts[4] = {n_blobs, n_armours, n_neg, 0};
+    memcpy(&host[o_cnt], counts, sizeof(counts));
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, total);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        const int32_t* cnt = reinterpret_cast<const int32_t*>(d + o_cnt);
+        SourceViewJob sj{};
+        ViewJob& j = sj.view;
+        j.w = w; j.h = h; j.prow = prow; j.plane_pitch = (int64_t)plane;
+        j.bits = nullptr; j.overlay = reinterpret_cast<uint64_t*>(d + o_ov); j.frames = nullptr;
+        j.n = 1; j.vw = vw; j.vh = vh; j.flags = flags;
+        j.out = d + o_out; j.out_stride = 3 * vw; j.out_pitch = (int64_t)3 * vw * vh;
+        j.lists = ViewLists{reinterpret_cast<const rmcv_lightblob*>(d + o_blobs), cnt, reinterpret_cast<const rmcv_armour*>(d + o_arm), cnt + 1,
+                            reinterpret_cast<const rmcv_point*>(d + o_pts), nullptr, nullptr, cnt + 3, nullptr, cnt + 2,
+                            reinterpret_cast<const int32_t*>(d + o_offs), n_blobs, n_armours, n_pts, n_neg, 1};
+        sj.kind = SOURCE_BGR;
+        sj.src = d; sj.src_end = d + (size_t)dstride * (h - 1) + (size_t)3 * w;
+        sj.stride = dstride; sj.frame_pitch = (int64_t)dstride * h;
+        e = launch_source_view(sj, c->stream);
+    }
+    c->last_what = "k_view_overlay + k_view_source";
+    int rcw = 0;
+    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_view_source");
+    if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(out, out_stride, d + o_out, (size_t)3 * vw, (size_t)3 * vw, vh, hipMemcpyDeviceToHost);
+    if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernels may still be using it)
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_source_view", e);
+    return rcw;
+}
+
 } // extern "C"

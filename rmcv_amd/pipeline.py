@@ -161,12 +161,14 @@ class Pipeline:
         return out[:tot.value].copy(), offs[:n + 1].copy()
 
     # ------------------------------------------------------------------ the operator's debug views
-    def set_views(self, frames, size=(1024, 768), flags=abi.VIEW_ALL):
+    def set_views(self, frames, size=(1024, 768), flags=abi.VIEW_ALL, source=False):
         """from the next submit on, every batch renders the debug images of `frames` (indices into the batch) at size = (vw, vh) behind its
         sparse stage, into its slot's own buffer (rmcv_pipeline_set_views: allocates and drains HERE; no submit blocks).  frames empty or
-        None: off."""
+        None: off.  source: the source views instead (rmcv_pipeline_set_source_views: the frame under the overlays, not the
+        binary); a pipeline renders one kind at a time, the one set last."""
         fr = np.ascontiguousarray(frames if frames is not None else [], np.int32).reshape(-1)
-        self._chk(self._lib.rmcv_pipeline_set_views(self._h, ptr(fr) if len(fr) else None, len(fr), int(size[0]), int(size[1]), int(flags)))
+        setter = self._lib.rmcv_pipeline_set_source_views if source else self._lib.rmcv_pipeline_set_views
+        self._chk(setter(self._h, ptr(fr) if len(fr) else None, len(fr), int(size[0]), int(size[1]), int(flags)))
 
     def views(self, ticket):
         """the views of a ticket's batch as a torch uint8 tensor [n, vh, vw, 3] OVER the slot's device buffer (no copy): complete once the
