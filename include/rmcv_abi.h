@@ -1173,7 +1173,8 @@ int  rmcv_pipeline_gathered(rmcv_pipeline* pl, uint64_t ticket, void** d_recv, i
  * a batch whose run included RMCV_STAGE_ARMOURS and a view size (vw, vh):
  *     V(f) = resize( draw_armours( draw_lightblobs( GRAY2BGR(binary_f) ) ), (vw, vh), INTER_LINEAR ),   8UC3, BGR
  * every byte equal to the CPU restatement rmcv_debug_view_host of those calls (OpenCV 4.8.0 as recalled: SURVEY.md A.10), with one stated
- * deviation: cv::putText (debug.cpp:53-57) is not rendered -- the label's data (identity, position, vertices[0]) comes from the getters.
+ * deviation: cv::putText (debug.cpp:53-57) is not rendered BY THESE ENTRY POINTS -- the label pass over the finished view draws it (see "view
+ * labels" below: rmcv_batch_view_labels, rmcv_pipeline_set_view_labels); its data (identity, position, vertices[0]) also comes from the getters.
  * A segment with an endpoint that is not finite or of magnitude >= 2^30 is skipped.  In a windowed batch the view is the window's.  The view
  * is written from the frame's bit plane and its result tables: it is the same with and without RMCV_STAGE_NO_IMAGE.
  * Colours (BGR): a positive blob (0, 255, 0) if its target is RMCV_CAMP_RED, (0, 0, 255) otherwise; negatives, armours' vertices and icons
@@ -1250,6 +1251,78 @@ int rmcv_source_view_host(const uint8_t* bgr, int w, int h, int stride, const rm
 /* a pipeline's source views: rmcv_pipeline_set_views' semantics (allocates HERE, no submit blocks, n == 0: off).  A pipeline renders ONE kind
  * of view at a time: the later of the two setters wins, and rmcv_pipeline_views returns whichever kind was rendered for the ticket. */
 int rmcv_pipeline_set_source_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags);
+
+/* ---- view labels: armour labels and tracker targets over finished views, rendered on the device ------------------------
+ * rm::debug::draw_armours writes a text line at every armour's vertices[0] (src/debug.cpp:53-57):
+ *     to_string(identity) + ": " + to_string(x) + ", " + to_string(y) + ", " + to_string(z)
+ * The label pass draws it over views either kind above has FINISHED (BGR, vw x vh, device memory), and for a tracked run every target the
+ * tracker holds: its quadrilateral and the same line followed by ", " + to_string(lost_count).  Every byte equals the CPU restatement
+ * rmcv_view_labels_host.  Stated deviations from the reference:
+ *   - the text is drawn IN VIEW SPACE, behind the resize, with an integer scale 1 .. 8 -- the reference writes it on the full frame, then the
+ *     contours, then resizes; a label must stay legible in a thumbnail;
+ *   - the font is this library's own 5 x 7 bitmap glyphs (rmcv_view_glyph), not FONT_HERSHEY_SIMPLEX;
+ *   - to_string(double) is "%f" for finite |v| < 1e15 -- six decimals, round-half-even on the exact binary value, the sign bit printed also
+ *     for -0.0 and for negatives that round to zero --; a NaN prints "nan" whatever its sign (glibc: "-nan"); a finite |v| >= 1e15 prints
+ *     "big" / "-big" (the reference: up to 309 digits); +-inf print "inf" / "-inf";
+ *   - the tracker's targets are not drawn by the reference at all.
+ * The line.  An armour's: identity from the run's RMCV_STAGE_IDENTITY, else -1; position from its RMCV_STAGE_POSE, else (0, 0, 0) -- the
+ * tracker's observations' defaults.  A track's: rmcv_track::identity; state_post[0 .. 2] if `initialized`, else `position` (the aim step's
+ * source rule); rmcv_track::lost_count.
+ * Placement.  (w, h) is the geometry the frame's tables are in (a windowed batch: the window's).  An anchor vertex is rounded as
+ * cv::Point(Point2f) does (cvRound, half to even) to (px, py); view anchor ax = floor(px vw / w), ay = floor(py vh / h) (a true floor).  With
+ * scale s, a set bit of character k at glyph column c (0 .. 4, left to right) and row r (0 .. 6, top to bottom) fills the s x s block at
+ * x = ax + (6 k + c) s, y = ay - (7 - r) s: the text's bottom-left sits at the anchor, as putText's origin does.  Every pixel is clipped to the
+ * view; only set bits write (no background box).  A vertex that is not finite or of magnitude >= 2^30 is not drawable: a line whose anchor
+ * is not is skipped, and so is a quadrilateral with such a vertex.
+ * A track's quadrilateral: the side record's four vertices (frame coordinates), each rounded, moved by the frame's effective window origin
+ * ((0, 0) without windows) and mapped by the two floors, joined j -> j + 1 (closed) through the views' line iterator and clip with the view
+ * as the canvas; its line's anchor is the mapped vertex 0.
+ * Colours (BGR): armours' lines (0, 255, 255), the reference's; tracks' quadrilaterals and lines (255, 0, 255).  Everything of the tracks is
+ * drawn first, then the armours' lines. */
+#define RMCV_LABEL_MAX_CHARS 112 /* >= the longest line: 11 + 2 + 3 x 23 + 2 x 2 + 2 + 11 = 99 characters */
+#define RMCV_LABEL_ARMOURS 1
+#define RMCV_LABEL_TRACKS 2
+/* host-side (no context, no device).  The three text functions write a terminated string into out[0 .. cap) and return its length;
+ * RMCV_ERR_CAPACITY when cap cannot hold it and the terminator (out is terminated within cap, its contents otherwise unspecified);
+ * RMCV_ERR_BAD_ARG for a null pointer or cap < 1.  rmcv_format_f6 is to_string(double) as stated above. */
+int rmcv_format_f6(double v, char* out, int cap);
+int rmcv_label_text(int32_t identity, const double position[3], char* out, int cap); /* position NULL: (0, 0, 0) */
+int rmcv_track_label_text(const rmcv_track* t, char* out, int cap);
+/* a glyph: 7 row bytes, top to bottom, 5 bits each, the LEFT column in bit 4.  The set is 0-9 - . : , space n a i f b g (21 glyphs; space
+ * is empty); RMCV_ERR_BAD_ARG for any other character. */
+int rmcv_view_glyph(int ch, uint8_t rows[7]);
+/* the sequential restatement, drawing in place: view is vh rows of `stride >= 3 vw` bytes; armours in the geometry's coordinates with
+ * identities (NULL: -1) and positions (n_armours x 3 doubles; NULL: zeros); tracks (NULL: none) with last_vertices [n_tracks][4][2] in
+ * frame coordinates (rmcv_tracker_get's) and the effective window origin (x_eff, y_eff) they are moved by.  RMCV_ERR_BAD_ARG: a null
+ * view or list, sizes < 1, a stride too small, scale outside 1 .. 8. */
+int rmcv_view_labels_host(uint8_t* view, int vw, int vh, int stride, int w, int h, int scale, const rmcv_armour* armours, const int32_t* identities,
+                          const double* positions, int n_armours, const rmcv_track* tracks, const float* last_vertices, int n_tracks, int x_eff, int y_eff);
+/* stage-wise: the same arguments through the kernel, on a HOST view returned in place, buffers of its own (nothing bound to the context
+ * moves); vw, vh within the context's max_width / max_height. */
+int rmcv_view_labels(rmcv_ctx* ctx, uint8_t* view, int vw, int vh, int stride, int w, int h, int scale, const rmcv_armour* armours,
+                     const int32_t* identities, const double* positions, int n_armours, const rmcv_track* tracks, const float* last_vertices,
+                     int n_tracks, int x_eff, int y_eff);
+/* the armours' lines of frames[k] of the batch bound over view k at d_views + k * pitch (DEVICE memory, rows `stride` bytes apart): the views
+ * rmcv_batch_debug_views / rmcv_batch_source_views wrote for the same frames and size.  Asynchronous: enqueued on hip_stream (NULL: the
+ * context's) behind the run; nothing is allocated (but, once in a context's life, the views' frame list where no view call has run yet).
+ * RMCV_ERR_BAD_ARG, with a message, before anything is enqueued: everything rmcv_batch_debug_views refuses about frames, n, sizes, stride and
+ * pitch; scale outside 1 .. 8; a last run without RMCV_STAGE_ARMOURS. */
+int rmcv_batch_view_labels(rmcv_ctx* ctx, const int32_t* frames, int n, int vw, int vh, int scale, void* d_views, int stride, int64_t pitch,
+                           void* hip_stream);
+/* the tracks of stream frames[k] (frame f of the batch is stream f) over view k: behind the run and behind the tracker's step in flight,
+ * whichever stream that ran on; the tracker's next step waits for it.  Also RMCV_ERR_BAD_ARG: everything rmcv_batch_track refuses about
+ * the tracker and the batch. */
+int rmcv_batch_view_tracks(rmcv_ctx* ctx, rmcv_tracker* trk, const int32_t* frames, int n, int vw, int vh, int scale, void* d_views, int stride,
+                           int64_t pitch, void* hip_stream);
+/* a pipeline's labels: from the next submit on, `what` (RMCV_LABEL_* bits) is drawn at `scale` over the views of every batch, whichever kind
+ * the pipeline renders (rmcv_pipeline_set_views / _set_source_views), in front of the batch's completion; RMCV_LABEL_TRACKS behind the
+ * tracker step of the same submit.  what == 0: off -- a submit then enqueues exactly what it did before.  No submit blocks
+ * (host_blocking_calls stays 0).  RMCV_ERR_BAD_ARG: unknown bits, scale outside 1 .. 8, no views set (turning the views off turns the labels
+ * off).  A later submit without a tracker while RMCV_LABEL_TRACKS is set, or whose stages lack RMCV_STAGE_ARMOURS, is refused before
+ * anything is enqueued. */
+int rmcv_pipeline_set_view_labels(rmcv_pipeline* pl, int what, int scale);
+/* launches of the label kernel (k_view_text) by this process so far: a submit with the labels off adds none */
+int64_t rmcv_view_text_launches(void);
 
 /* ---- the session recorder: rm::debug::logger (include/debug.h:13-29, src/debug.cpp:9-41) for frames resident in HBM ----
  * The reference records every frame the detector saw, losslessly (FFV1), with a `data` record per frame.  Here chosen frames of every batch

@@ -14,6 +14,7 @@ from .abi import (ARMOUR, BAYER_BG, BAYER_GB, BAYER_GR, BAYER_PATTERNS, BAYER_RG
                   ATTITUDE, ATTITUDE_CONFIG, ATT_MOTOR_KEEP, ATT_MOTOR_PITCH, SERIAL_PACKET_BYTES, crc8, euler_to_matrix, homogeneous, serial_decode, serial_encode,
                   VIEW_ALL, VIEW_ARMOURS, VIEW_BLOBS, VIEW_NEGATIVES, debug_view_host, source_view_host)
 from .api import Context, debug_view
+from .abi import LABEL_ARMOURS, LABEL_CHARSET, LABEL_MAX_CHARS, LABEL_TRACKS, format_f6, label_text, track_label_text, view_glyph, view_labels_host
 from .pipeline import Pipeline
 from .recorder import LoopRecord, Recorder, Session, loop_bound, loop_field_at, loop_trigger, pack, pack_bound, unpack
 from . import svm

@@ -72,6 +72,8 @@ AIM_HEIGHT_FIXED, AIM_HEIGHT_DELTA = 0, 1
 AIM_SRC_FILTER, AIM_SRC_MEASUREMENT = 0, 1
 AIM_PICK_WINDOW, AIM_PICK_NEAREST = 0, 1
 VIEW_BLOBS, VIEW_NEGATIVES, VIEW_ARMOURS, VIEW_ALL = 1, 2, 4, 7  # RMCV_VIEW_*: what the debug view draws over the binary (all: the reference)
+LABEL_ARMOURS, LABEL_TRACKS, LABEL_MAX_CHARS = 1, 2, 112  # RMCV_LABEL_*: what the label pass draws over finished views
+LABEL_CHARSET = "0123456789-.:, naifbg"  # the characters a line can contain = the glyphs rmcv_view_glyph hands out
 FRAME_OVF_CONTOURS, FRAME_OVF_POINTS, FRAME_OVF_BLOBS, FRAME_OVF_ARMOURS, FRAME_SLOW_PATH, FRAME_MID_PATH = 1, 2, 4, 8, 16, 64
 # dataset harvest: a label that keeps a frame out, the flag that keeps only the model's misses, a row's 64-byte metadata
 HARVEST_SKIP, HARVEST_MISSES = -2**31, 1
@@ -122,6 +124,8 @@ EXPORTS = [
     "rmcv_frame_model", "rmcv_svm_load_models", "rmcv_batch_set_frame_models", "rmcv_batch_set_device_frame_models", "rmcv_batch_get_frame_models",
     "rmcv_pipeline_set_frame_models", "rmcv_svm_predict_model",
     "rmcv_batch_source_views", "rmcv_batch_get_source_view", "rmcv_source_view", "rmcv_source_view_host", "rmcv_pipeline_set_source_views",
+    "rmcv_format_f6", "rmcv_label_text", "rmcv_track_label_text", "rmcv_view_glyph", "rmcv_view_labels_host", "rmcv_view_labels", "rmcv_batch_view_labels",
+    "rmcv_batch_view_tracks", "rmcv_pipeline_set_view_labels", "rmcv_view_text_launches",
 ]
 
 
@@ -441,6 +445,20 @@ def load(path):
             L.rmcv_batch_source_views.argtypes = L.rmcv_batch_debug_views.argtypes
             L.rmcv_batch_get_source_view.argtypes = L.rmcv_batch_get_debug_view.argtypes
             L.rmcv_pipeline_set_source_views.argtypes = L.rmcv_pipeline_set_views.argtypes
+    if hasattr(L, "rmcv_view_labels_host"):  # (builds from before the view labels stay loadable for A/B runs)
+        labels = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                  C.c_int, C.c_int]
+        L.rmcv_format_f6.argtypes = [C.c_double, C.c_void_p, C.c_int]
+        L.rmcv_label_text.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_track_label_text.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_view_glyph.argtypes = [C.c_int, C.c_void_p]
+        L.rmcv_view_labels_host.argtypes = labels
+        L.rmcv_view_labels.argtypes = [C.c_void_p] + labels
+        L.rmcv_batch_view_labels.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+        L.rmcv_batch_view_tracks.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+        L.rmcv_pipeline_set_view_labels.argtypes = [C.c_void_p, C.c_int, C.c_int]
+        L.rmcv_view_text_launches.restype = C.c_int64
+        L.rmcv_view_text_launches.argtypes = []
     if hasattr(L, "rmcv_pack_bound"):  # (builds from before the session recorder stay loadable for A/B runs)
         L.rmcv_pack_bound.restype = C.c_int64
         L.rmcv_pack_bound.argtypes = [C.c_int, C.c_int]
@@ -674,6 +692,85 @@ def source_view_host(bgr, blobs=None, negatives=None, armours=None, size=(1024, 
     if rc:
         raise RmcvError(rc, "rmcv_source_view_host: sizes >= 1, known flags, contour offsets that do not decrease")
     return out
+
+
+def _text(call, what):
+    buf = C.create_string_buffer(LABEL_MAX_CHARS + 1)
+    rc = call(buf, len(buf))
+    if rc < 0:
+        raise RmcvError(rc, what)
+    return buf.value.decode("ascii")
+
+
+def format_f6(v):
+    """std::to_string(double) as the label pass writes it (rmcv_format_f6: host-side, the function the device runs): "%f" for finite
+    |v| < 1e15, correctly rounded half to even in integer arithmetic; "nan", "inf" / "-inf", and "big" / "-big" from 1e15 on"""
+    return _text(lambda b, n: lib().rmcv_format_f6(C.c_double(float(v)), b, n), "rmcv_format_f6")
+
+
+def label_text(identity, position=None):
+    """an armour's line, 'identity: x, y, z' (rmcv_label_text; position None: zeros)"""
+    pos = None if position is None else _tvec(position)
+    return _text(lambda b, n: lib().rmcv_label_text(C.c_int32(int(identity)), ptr(pos), b, n), "rmcv_label_text")
+
+
+def track_label_text(track):
+    """a track's line, 'identity: x, y, z, lost_count' of one TRACK record (rmcv_track_label_text): the filter's posterior once the track
+    is initialised, else the observation's position"""
+    t = np.ascontiguousarray(track, TRACK).reshape(-1)
+    assert len(t) == 1
+    return _text(lambda b, n: lib().rmcv_track_label_text(ptr(t), b, n), "rmcv_track_label_text")
+
+
+def view_glyph(ch):
+    """the library's 5 x 7 glyph of one character of LABEL_CHARSET: 7 row bytes, top to bottom, the left column in bit 4 (rmcv_view_glyph;
+    raises for any other character)"""
+    rows = np.zeros(7, np.uint8)
+    rc = lib().rmcv_view_glyph(ord(ch) if isinstance(ch, str) else int(ch), ptr(rows))
+    if rc:
+        raise RmcvError(rc, "rmcv_view_glyph: a character outside the label set")
+    return rows
+
+
+def view_labels_args(view, geometry, scale, armours, identities, positions, tracks, last_vertices, origin, stride=None):
+    """the argument list rmcv_view_labels_host and rmcv_view_labels share, and the arrays it points into (keep them until the call is
+    through).  view: (vh, vw, 3) uint8, drawn IN PLACE -- or, with `stride`, a flat uint8 buffer of rows `stride` bytes apart and
+    geometry = (w, h, vw, vh); geometry otherwise (w, h), what the lists' coordinates are in"""
+    if stride is None:
+        assert view.dtype == np.uint8 and view.ndim == 3 and view.shape[2] == 3 and view.flags.c_contiguous
+        vh, vw = view.shape[:2]
+        w, h = int(geometry[0]), int(geometry[1])
+        stride = 3 * vw
+    else:
+        assert view.dtype == np.uint8 and view.ndim == 1 and view.flags.c_contiguous
+        w, h, vw, vh = (int(v) for v in geometry)
+        assert len(view) >= stride * (vh - 1) + 3 * vw
+    armours = np.ascontiguousarray(armours if armours is not None else [], ARMOUR).reshape(-1)
+    n = len(armours)
+    ids = None if identities is None else np.ascontiguousarray(identities, np.int32).reshape(-1)
+    pos = None if positions is None else np.ascontiguousarray(positions, np.float64).reshape(-1, 3)
+    assert ids is None or len(ids) == n
+    assert pos is None or len(pos) == n
+    tracks = np.ascontiguousarray(tracks if tracks is not None else [], TRACK).reshape(-1)
+    nt = len(tracks)
+    side = np.ascontiguousarray(last_vertices if last_vertices is not None else [], np.float32).reshape(-1, 4, 2)
+    assert len(side) == nt
+    keep = (view, armours, ids, pos, tracks, side)
+    args = [ptr(view), vw, vh, int(stride), w, h, int(scale), ptr(armours) if n else None, ptr(ids) if n else None, ptr(pos) if n else None, n,
+            ptr(tracks) if nt else None, ptr(side) if nt else None, nt, int(origin[0]), int(origin[1])]
+    return args, keep
+
+
+def view_labels_host(view, geometry, scale=1, armours=None, identities=None, positions=None, tracks=None, last_vertices=None, origin=(0, 0), stride=None):
+    """the label pass on the CPU, in place (rmcv_view_labels_host: the sequential restatement, no device): every track's quadrilateral and
+    line in (255, 0, 255), then every armour's line in (0, 255, 255), over a finished view of a frame whose lists are in `geometry` =
+    (w, h).  identities None: -1; positions None: zeros; origin: the effective window origin the tracks' frame coordinates are moved by.
+    Returns view."""
+    args, keep = view_labels_args(view, geometry, scale, armours, identities, positions, tracks, last_vertices, origin, stride)
+    rc = lib().rmcv_view_labels_host(*args)
+    if rc:
+        raise RmcvError(rc, "rmcv_view_labels_host: sizes >= 1, stride >= 3 vw, scale 1 .. 8")
+    return view
 
 
 def _tvec(tvec):

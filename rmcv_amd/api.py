@@ -643,6 +643,34 @@ class Context:
         self._chk(lib().rmcv_source_view(self._h, *args))
         return out
 
+    # ---------------------------------------------------------------- view labels
+    def view_labels(self, view, geometry, scale=1, armours=None, identities=None, positions=None, tracks=None, last_vertices=None, origin=(0, 0), stride=None):
+        """stage-wise: the label pass over a HOST view through the kernel, in place (rmcv_view_labels; arguments as abi.view_labels_host,
+        which is the same on the CPU)"""
+        args, keep = abi.view_labels_args(view, geometry, scale, armours, identities, positions, tracks, last_vertices, origin, stride)
+        self._chk(lib().rmcv_view_labels(self._h, *args))
+        return view
+
+    def batch_view_labels(self, frames, views, size=(1024, 768), scale=1, stride=None, pitch=None, stream=None):
+        """the armours' lines -- 'identity: x, y, z' at vertices[0] -- of the chosen frames of the batch run last over their FINISHED views
+        (rmcv_batch_view_labels; asynchronous, behind the run).  views: a device pointer to n views of `size` = (vw, vh), as debug_views /
+        source_views wrote them for the same frames (rows `stride` bytes apart, views `pitch`; default: contiguous)"""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        vw, vh = int(size[0]), int(size[1])
+        stride = 3 * vw if stride is None else int(stride)
+        pitch = stride * vh if pitch is None else int(pitch)
+        self._chk(lib().rmcv_batch_view_labels(self._h, ptr(fr), len(fr), vw, vh, int(scale), C.c_void_p(int(views)), stride, pitch, C.c_void_p(stream or 0)))
+
+    def batch_view_tracks(self, tracker, frames, views, size=(1024, 768), scale=1, stride=None, pitch=None, stream=None):
+        """the targets `tracker` holds for the streams `frames` (frame f of the batch is stream f) over their finished views: quadrilateral
+        and 'identity: x, y, z, lost_count' (rmcv_batch_view_tracks; asynchronous, behind the run and the tracker's step in flight)"""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        vw, vh = int(size[0]), int(size[1])
+        stride = 3 * vw if stride is None else int(stride)
+        pitch = stride * vh if pitch is None else int(pitch)
+        self._chk(lib().rmcv_batch_view_tracks(self._h, tracker._h if tracker is not None else None, ptr(fr), len(fr), vw, vh, int(scale), C.c_void_p(int(views)),
+                                               stride, pitch, C.c_void_p(stream or 0)))
+
     def device_views(self):
         """(armours device pointer, counts device pointer, per-frame capacity, n_frames) for a collective"""
         a, c = C.c_void_p(), C.c_void_p()

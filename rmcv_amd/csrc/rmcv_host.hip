@@ -1533,3 +1533,96 @@ int rmcv_batch_get_source_view(rmcv_ctx* c, int frame, int vw, int vh, int flags
 }
 
 } // extern "C"
+
+/* ---- view labels (k_view_text.hip): the batch entry points; the host-side ones and the stage-wise one: rmcv_labels.hip ---- */
+
+namespace rmcv {
+
+int ctx_label_check(rmcv_ctx* c, const char* who, rmcv_tracker* trk, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int scale,
+                    int out_stride, int64_t out_pitch)
+{
+    char msg[200];
+    // (the views are finished ones: what their renderer refused of the list and the layout is refused here, whatever stages it needed)
+    if (const int rc = ctx_view_check(c, frames, n, n_frames, ~0, vw, vh, 0, out_stride, out_pitch)) return rc;
+    if (scale < 1 || scale > 8) {
+        snprintf(msg, sizeof(msg), "%s: scale %d is outside 1 .. 8", who, scale);
+        return fail(c, RMCV_ERR_BAD_ARG, msg);
+    }
+    if (trk) {
+        if (const char* no = step_refusal(who, true, tracker_view(trk), step_batch(c), stages, msg)) return fail(c, RMCV_ERR_BAD_ARG, no);
+    } else if (!(stages & RMCV_STAGE_ARMOURS)) {
+        snprintf(msg, sizeof(msg), "%s: the last run had no RMCV_STAGE_ARMOURS: nothing to label", who);
+        return fail(c, RMCV_ERR_BAD_ARG, msg);
+    }
+    return RMCV_OK;
+}
+
+int ctx_label_enqueue(rmcv_ctx* c, rmcv_tracker* trk, int what, int stages, const int32_t* d_frames, int n, int vw, int vh, int scale, void* d_views,
+                      int out_stride, int64_t out_pitch, hipStream_t s)
+{
+    const Geom& g = c->geom;
+    const Bufs& b = c->bufs;
+    LabelJob j{};
+    j.n = n, j.vw = vw, j.vh = vh, j.w = g.w, j.h = g.h, j.scale = scale, j.n_frames = g.n_frames;
+    j.out = static_cast<uint8_t*>(d_views), j.out_stride = out_stride, j.out_pitch = out_pitch, j.frames = d_frames;
+    if (what & RMCV_LABEL_ARMOURS) { // identity and position as the tracker's observations take them: from the run's stages, else -1 and zeros
+        j.armours = b.armours, j.n_armours = b.n_armours, j.max_armours = c->lim.max_armours;
+        j.identity = (stages & RMCV_STAGE_IDENTITY) ? b.identity : nullptr;
+        j.positions = (stages & RMCV_STAGE_POSE) && b.poses ? b.poses + 6 : nullptr;
+        j.pos_stride = 9;
+    }
+    const bool tracks = (what & RMCV_LABEL_TRACKS) && trk;
+    if (tracks) {
+        const TrackerView& v = tracker_view(trk);
+        j.tracks = v.b.tracks, j.side = v.b.side, j.sel = v.b.sel, j.n_tracking = v.b.n_tracking;
+        j.n_streams = v.cfg.n_streams, j.track_cap = v.cfg.track_cap;
+        j.win_eff = g.win ? b.win_eff : nullptr;
+        HIPCHK(c, tracker_order_begin(trk, s), "view labels: wait for the tracker's step");
+    }
+    HIPCHK(c, launch_view_text(j, s), "k_view_text");
+    if (tracks) HIPCHK(c, tracker_order_end(trk, s), "view labels: record the read of the tracker's lists");
+    return RMCV_OK;
+}
+
+} // namespace rmcv
+
+// rmcv_batch_view_labels / rmcv_batch_view_tracks behind their checks.  The frame list travels through the views' own table
+// (rmcv_ctx::view_frames: allocated once in a context's life, by whichever view or label call comes first)
+static int label_batch(rmcv_ctx* c, rmcv_tracker* trk, const int32_t* frames, int n, int vw, int vh, int scale, void* d_views, int stride, int64_t pitch, hipStream_t s)
+{
+    int rc = RMCV_OK;
+    if (!c->view_frames) {
+        const hipError_t e = dalloc(c, &c->view_frames, (size_t)c->lim.max_frames);
+        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the views' frame list", e);
+    }
+    if ((rc = order_begin(c, s))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->view_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D view frames");
+    if ((rc = ctx_label_enqueue(c, trk, trk ? RMCV_LABEL_TRACKS : RMCV_LABEL_ARMOURS, c->last_stages, c->view_frames, n, vw, vh, scale, d_views, stride, pitch, s))) return rc;
+    return order_end(c, s);
+}
+
+extern "C" {
+
+int rmcv_batch_view_labels(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int scale, void* d_views, int stride, int64_t pitch, void* hip_stream)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!d_views) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_view_labels: null views");
+    const int rc = ctx_label_check(c, "rmcv_batch_view_labels", nullptr, frames, n, c->geom.n_frames, c->last_stages, vw, vh, scale, stride, pitch);
+    if (rc) return rc;
+    hipSetDevice(c->device);
+    return label_batch(c, nullptr, frames, n, vw, vh, scale, d_views, stride, pitch, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int rmcv_batch_view_tracks(rmcv_ctx* c, rmcv_tracker* trk, const int32_t* frames, int n, int vw, int vh, int scale, void* d_views, int stride, int64_t pitch,
+                           void* hip_stream)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!trk) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_view_tracks: null tracker");
+    if (!d_views) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_view_tracks: null views");
+    const int rc = ctx_label_check(c, "rmcv_batch_view_tracks", trk, frames, n, c->geom.n_frames, c->last_stages, vw, vh, scale, stride, pitch);
+    if (rc) return rc;
+    hipSetDevice(c->device);
+    return label_batch(c, trk, frames, n, vw, vh, scale, d_views, stride, pitch, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+} // extern "C"

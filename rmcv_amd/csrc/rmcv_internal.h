@@ -316,6 +316,43 @@ hipError_t launch_source_view(const Geom& g, const Bufs& b, const ViewJob& view,
 int ctx_source_view_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int flags, int out_stride, int64_t out_pitch);
 int ctx_source_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s);
 
+// ---- view labels (k_view_text.hip): text lines and tracker targets over finished views ----
+// n views of vw x vh in `out`; view k is of frame frames[k] (device memory; null: frame k) of tables in the geometry (w, h).  Either half
+// may be off (armours / tracks null); the tracks are drawn first.
+struct LabelJob {
+    int n, vw, vh, w, h, scale, n_frames;
+    uint8_t* out;
+    int out_stride;
+    int64_t out_pitch;
+    const int32_t* frames;
+    // the armours' lines
+    const rmcv_armour* armours;  // [frame][max_armours]
+    const int32_t* n_armours;    // [frame]
+    int max_armours;
+    const int32_t* identity;     // [frame][max_armours]; null: -1
+    const double* positions;     // armour i of frame f: positions[(f max_armours + i) pos_stride + 0 .. 2]; null: (0, 0, 0)
+    int pos_stride;
+    // the tracks' quadrilaterals and lines: TrackerBufs' tables (sel null: list 0 is current)
+    const rmcv_track* tracks;
+    const float* side;
+    const int32_t *sel, *n_tracking;
+    int n_streams, track_cap;
+    const rmcv_point* win_eff;   // [frame] the effective window origins the side records are moved by; null: (x_eff, y_eff) for every frame
+    int x_eff, y_eff;
+};
+// k_view_text on `s`; every argument has been checked by the caller
+hipError_t launch_view_text(const LabelJob& j, hipStream_t s);
+int64_t view_text_launches(); // launches of k_view_text by this process (rmcv_view_text_launches)
+// what the label entry points of a context refuse before anything is enqueued (rmcv_host.hip): the views' list and layout as
+// ctx_view_check, the scale, the stages (RMCV_STAGE_ARMOURS), and for tracks (trk non-null) what a tracker step refuses of the batch
+// (n_frames / stages: the batch the views are of).  who: the entry point, for the message
+int ctx_label_check(rmcv_ctx* c, const char* who, rmcv_tracker* trk, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int scale,
+                    int out_stride, int64_t out_pitch);
+// the enqueue on frames the caller has bound and run, the frame list already on the device, nothing blocking.  what: RMCV_LABEL_*; with
+// RMCV_LABEL_TRACKS the launch is ordered as a step of the tracker's (behind its last one; the next one waits for it)
+int ctx_label_enqueue(rmcv_ctx* c, rmcv_tracker* trk, int what, int stages, const int32_t* d_frames, int n, int vw, int vh, int scale, void* d_views,
+                      int out_stride, int64_t out_pitch, hipStream_t s);
+
 // ---- what rmcv_pipeline.hip needs of a context beyond the public ABI (rmcv_host.hip) ----
 // external order: the pipeline chains a context's launches with its own events (it knows which stream ran what), so the context
 // does not record / wait for its own ordering event around every launch (two HIP calls per launch); rmcv_batch_sync and the getters

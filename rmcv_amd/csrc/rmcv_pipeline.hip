@@ -101,6 +101,7 @@ struct rmcv_pipeline {
         bool views = false;     // debug views are rendered behind its sparse stage
         LoopTicket loop{};      // a recorded tracked batch: the recorder slot its loop records go into (chosen at the submit; the step runs a call later)
         bool harvest = false;   // its armours' icon rows are appended to the dataset behind its sparse stage
+        int labels = 0;         // RMCV_LABEL_* drawn over its views (0: none)
     } pend;
     rmcv_pipeline_hook hook = nullptr; // ... or the built-in gather hook
     void* hook_user = nullptr;
@@ -123,6 +124,7 @@ struct rmcv_pipeline {
         int n = 0, vw = 0, vh = 0, flags = 0, max_index = 0, need = 0; // need: the stages the flags read the results of
         bool source = false;           // rmcv_pipeline_set_source_views set them: the source view, not the binary's
         int32_t* d_frames = nullptr;   // [n] the frame list, on the device
+        int label_what = 0, label_scale = 0; // rmcv_pipeline_set_view_labels: RMCV_LABEL_* drawn over them (0: nothing)
     } views;
     // rmcv_pipeline_set_recorder: every following batch packs these frames into the recorder behind its pixel kernel (n == 0: off)
     struct Recording {
@@ -505,6 +507,14 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
         if (rc) return cfail(pl, P.c, rc);
         pl->last_what = P.loop.rec ? "k_loop_record" : "k_track";
     }
+    // the view labels: over the views rendered above, behind the tracker's step (they read its lists; ctx_label_enqueue makes the tracker's
+    // next step wait for them) and in front of ev_done (they read the context's armours, identities, poses and effective origins)
+    if (P.labels) {
+        const rmcv_pipeline::Views& V = pl->views; // (as at the submit: rmcv_pipeline_set_view_labels drains first)
+        rc = ctx_label_enqueue(P.c, q.trk, P.labels, q.stages, V.d_frames, V.n, V.vw, V.vh, V.label_scale, S.d_views, 3 * V.vw, (int64_t)3 * V.vw * V.vh, T);
+        if (rc) return cfail(pl, P.c, rc);
+        pl->last_what = "k_view_text";
+    }
     // the context's buffers are free from here on: the next pixel kernel of this slot does not wait for the hook
     PCHK(pl, hipEventRecord(S.ev_done, T), "pipeline: mark the slot");
     PCHK(pl, hipEventRecord(pl->ev_set[2 * (size_t)S.ctx + (size_t)S.set], T), "pipeline: mark the pixel-output set");
@@ -548,6 +558,11 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
             return pfail(pl, RMCV_ERR_BAD_ARG, pl->views.source ? SOURCE_VIEW_FEWER_FRAMES : "the batch has fewer frames than the debug views name (rmcv_pipeline_set_views)");
         if ((stages & pl->views.need) != pl->views.need)
             return pfail(pl, RMCV_ERR_BAD_ARG, pl->views.source ? SOURCE_VIEW_FEWER_STAGES : "the batch's stages lack what the debug views' flags need (rmcv_pipeline_set_views)");
+        if (pl->views.label_what) { // (with no labels set: nothing here, and nothing further down)
+            if (!(stages & RMCV_STAGE_ARMOURS)) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch's stages lack RMCV_STAGE_ARMOURS, which the view labels need (rmcv_pipeline_set_view_labels)");
+            if ((pl->views.label_what & RMCV_LABEL_TRACKS) && !q.trk)
+                return pfail(pl, RMCV_ERR_BAD_ARG, "RMCV_LABEL_TRACKS is set (rmcv_pipeline_set_view_labels): the submit needs a tracker (rmcv_pipeline_submit_tracked)");
+        }
     }
     if (pl->recd.n) { // (with no recorder set: nothing here, and nothing further down)
         if (q.n_frames <= pl->recd.max_index) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch has fewer frames than the recorder's frame list names (rmcv_pipeline_set_recorder)");
@@ -692,6 +707,7 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
     pl->next_ticket = t + 1;
     if (ticket) *ticket = t;
     pl->pend = {true, t, q, *q.p, lp ? *lp : rmcv_legacy_params{}, k, c, used, plan, sparse, B, pl->views.n > 0, loop, pl->harv.ds != nullptr};
+    pl->pend.labels = pl->views.n > 0 ? pl->views.label_what : 0;
     pl->pend.req.p = &pl->pend.p; // (the caller's params live as long as its call)
     pl->pend.req.lp = lp ? &pl->pend.lp : nullptr;
     // (a hook or the gather hands the record to a consumer the pipeline does not see waiting: its batches are finished here and now)
@@ -880,6 +896,7 @@ static int set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, in
     if (rc) return rc;
     if (n == 0) {
         pl->views.n = 0;
+        pl->views.label_what = 0; // (labels are drawn over views: off with them)
         return RMCV_OK;
     }
     rmcv_ctx* c0 = pl->ring[0];
@@ -912,6 +929,24 @@ static int set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, in
 int rmcv_pipeline_set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags) { return set_views(pl, frames, n, vw, vh, flags, false); }
 
 int rmcv_pipeline_set_source_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags) { return set_views(pl, frames, n, vw, vh, flags, true); }
+
+int rmcv_pipeline_set_view_labels(rmcv_pipeline* pl, int what, int scale)
+{
+    if (!pl) return RMCV_ERR_BAD_ARG;
+    hipSetDevice(pl->device);
+    // the batch in hand keeps the labels it was submitted under: everything submitted so far is through first (this call may block; no submit does)
+    const int rc = rmcv_pipeline_drain(pl);
+    if (rc) return rc;
+    if (what == 0) {
+        pl->views.label_what = 0;
+        return RMCV_OK;
+    }
+    if (what < 0 || what > (RMCV_LABEL_ARMOURS | RMCV_LABEL_TRACKS)) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_view_labels: unknown RMCV_LABEL_* bits");
+    if (scale < 1 || scale > 8) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_view_labels: scale outside 1 .. 8");
+    if (!pl->views.n) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_set_view_labels: no views are set (rmcv_pipeline_set_views, rmcv_pipeline_set_source_views)");
+    pl->views.label_what = what, pl->views.label_scale = scale;
+    return RMCV_OK;
+}
 
 int rmcv_pipeline_set_recorder(rmcv_pipeline* pl, rmcv_recorder* rec, const int32_t* frames, int n)
 {

@@ -170,6 +170,12 @@ class Pipeline:
         setter = self._lib.rmcv_pipeline_set_source_views if source else self._lib.rmcv_pipeline_set_views
         self._chk(setter(self._h, ptr(fr) if len(fr) else None, len(fr), int(size[0]), int(size[1]), int(flags)))
 
+    def set_view_labels(self, what, scale=1):
+        """from the next submit on, the label pass over every batch's views, whichever kind is set: what = abi.LABEL_ARMOURS
+        (the armours' lines) | abi.LABEL_TRACKS (the tracker's targets, behind the tracker step of the same tracked submit) at an integer
+        `scale` 1 .. 8 (rmcv_pipeline_set_view_labels: drains HERE; no submit blocks).  what 0: off.  Refused while no views are set."""
+        self._chk(self._lib.rmcv_pipeline_set_view_labels(self._h, int(what), int(scale)))
+
     def views(self, ticket):
         """the views of a ticket's batch as a torch uint8 tensor [n, vh, vw, 3] OVER the slot's device buffer (no copy): complete once the
         ticket has been waited for, valid until ticket + depth is submitted"""
