@@ -1324,6 +1324,68 @@ int rmcv_pipeline_set_view_labels(rmcv_pipeline* pl, int what, int scale);
 /* launches of the label kernel (k_view_text) by this process so far: a submit with the labels off adds none */
 int64_t rmcv_view_text_launches(void);
 
+/* ---- the labeler's screen: icons at any size and the combined sheet, rendered on the device ------------------------------
+ * executable/svm/labeler.cpp:93-106 rectifies every armour's icon with rm::affine_correction(frame, tmp, armour.icon, {80, 80}) and lays the
+ * icons side by side; :113-119 puts the frame with its overlays, the binary image and that strip into one canvas.
+ * The icon.  rm::affine_correction (src/imgproc.cpp:9-35) at an output size (ow, oh), 1 .. RMCV_ICON_SIDE_MAX each: the vertices clamped in
+ * place to the image, their integer bounding box, getAffineTransform of ([1], [2], [0]) onto the box's corners, warpAffine INTER_LINEAR /
+ * BORDER_CONSTANT 0 of the box, resize INTER_LINEAR to (ow, oh) -- the exact 2:1 case as the 2 x 2 box average -- all in OpenCV's fixed
+ * point.  At 20 x 20 it is the row rmcv_batch_get_icons hands out.  A degenerate box gives zeros.
+ * The strip.  For a frame f, a side and a cap: `side` rows of cap * side pixels (8UC3, BGR); the icon of armour j < min(n_armours, cap) at
+ * side x side in columns [j side, (j + 1) side); every other byte zero (the labeler's Mat::zeros; the uninitialised tail of its strip is not
+ * mirrored).  The icon is computed on SRC(f), the image the frame's results are defined on (the source view's: the frame, its demosaic, the
+ * frame through its gamma table, its window).  The armour table is only read: the strip is the same with and without RMCV_STAGE_IDENTITY
+ * (the clamp that stage writes back is idempotent).  Every byte equals rmcv_icon_strip_host of SRC(f) and the frame's armours.
+ * The sheet.  labeler.cpp:113-119 at view size, one canvas of 2 vw x (vh + side) pixels: S(f) with `flags` in [0, vw) x [0, vh); the plain
+ * binary as BGR -- V(f) with flags 0 -- in [vw, 2 vw) x [0, vh); the strip with cap = min(floor(2 vw / side), max_armours) in rows
+ * [vh, vh + side), the rest of those rows zero.  Stated deviations: the strip is square; the views keep their draw order (blobs, then armours;
+ * the labeler draws the armours first); no text under the icons; no window, no keyboard. */
+#define RMCV_ICON_SIDE_MAX 256
+#define RMCV_ICON_STRIP_CAP_MAX 1024 /* slots of a host strip (a context's: its max_armours) */
+/* host-side (no context, no device): rm::affine_correction(bgr, out, icon, {ow, oh}) on an image of h rows of `stride >= 3 w` bytes.  icon is
+ * clamped in place (imgproc.cpp:11-15); *degenerate (nullable) is set to 1 when the box is, and `out` (oh rows of out_stride >= 3 ow bytes)
+ * is then zero-filled.  RMCV_ERR_BAD_ARG: a null buffer; w or h < 1; stride < 3 w; ow or oh outside 1 .. 256; out_stride < 3 ow. */
+int rmcv_affine_correction_host(const uint8_t* bgr, int w, int h, int stride, float icon[4][2], int ow, int oh, uint8_t* out, int out_stride,
+                                int32_t* degenerate);
+/* stage-wise: a host image and host armours through the kernel, buffers of its own (nothing bound to the context moves); w, h within the
+ * context's max_width / max_height, n and cap within its max_armours.  out: `side` rows of out_stride >= 3 cap side bytes, of which
+ * 3 cap side are written. */
+int rmcv_icon_strip(rmcv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, const rmcv_armour* armours, int n, int side, int cap, uint8_t* out,
+                    int out_stride);
+/* the same on the CPU (icon_host.h); no context; cap 1 .. RMCV_ICON_STRIP_CAP_MAX */
+int rmcv_icon_strip_host(const uint8_t* bgr, int w, int h, int stride, const rmcv_armour* armours, int n, int side, int cap, uint8_t* out,
+                         int out_stride);
+/* chosen frames of the batch run last: strip k (of frame frames[k]) at d_out + k * out_pitch (DEVICE memory), `side` rows of out_stride >=
+ * 3 cap side bytes; d_counts (device, may be NULL): int32 per strip, the icons rendered, min(n_armours, cap).  Asynchronous: enqueued on
+ * hip_stream (NULL: the context's) behind the run; the kernel reads the frames, as the source view's do.  RMCV_ERR_BAD_ARG, with a message,
+ * before anything is enqueued: everything rmcv_batch_source_views refuses about frames and n; side outside 1 .. 256; cap outside
+ * 1 .. max_armours; out_stride < 3 cap side; out_pitch < out_stride (side - 1) + 3 cap side for n > 1; a null output; nothing bound; a last
+ * run without RMCV_STAGE_ARMOURS.  The call renders what the tables hold. */
+int rmcv_batch_icon_strips(rmcv_ctx* ctx, const int32_t* frames, int n, int side, int cap, void* d_out, int out_stride, int64_t out_pitch,
+                           int32_t* d_counts, void* hip_stream);
+/* one frame's strip to HOST memory, *n_icons (nullable) the icons rendered; waits with the context's deadline.  Also RMCV_ERR_BAD_ARG: the
+ * frame carries an RMCV_FRAME_OVF_* status. */
+int rmcv_batch_get_icon_strip(rmcv_ctx* ctx, int frame, int side, int cap, uint8_t* out, int out_stride, int32_t* n_icons);
+/* host-side: the sheet's extent, 2 vw x (vh + side).  RMCV_ERR_BAD_ARG: vw or vh < 1, side outside 1 .. 256 or > 2 vw, null outputs. */
+int rmcv_sheet_size(int vw, int vh, int side, int32_t* sheet_w, int32_t* sheet_h);
+/* sheet k (of frame frames[k]) at d_out + k * out_pitch (DEVICE memory), vh + side rows of out_stride >= 6 vw bytes.  The two panes are the
+ * view launches aimed at sub-rectangles of the sheet: no copy pass.  Asynchronous, behind the run.  RMCV_ERR_BAD_ARG, before anything is
+ * enqueued: what rmcv_batch_source_views and rmcv_batch_debug_views refuse; a last run without RMCV_STAGE_BINARY, what the flags need, or
+ * RMCV_STAGE_ARMOURS; side outside 1 .. 256 or > 2 vw; out_stride < 6 vw; out_pitch < out_stride (vh + side - 1) + 6 vw for n > 1. */
+int rmcv_batch_labeler_sheets(rmcv_ctx* ctx, const int32_t* frames, int n, int vw, int vh, int side, int flags, void* d_out, int out_stride,
+                              int64_t out_pitch, void* hip_stream);
+/* one frame's sheet to HOST memory; also RMCV_ERR_BAD_ARG: the frame carries an RMCV_FRAME_OVF_* status */
+int rmcv_batch_get_labeler_sheet(rmcv_ctx* ctx, int frame, int vw, int vh, int side, int flags, uint8_t* out, int out_stride);
+/* the same on the CPU: rmcv_source_view_host's image and lists plus the binary image (h rows of binary_stride >= w bytes); the strip holds
+ * min(floor(2 vw / side), RMCV_ICON_STRIP_CAP_MAX) slots */
+int rmcv_labeler_sheet_host(const uint8_t* bgr, int w, int h, int stride, const uint8_t* binary, int binary_stride, const rmcv_lightblob* blobs,
+                            int n_blobs, const rmcv_point* neg_pts, const int32_t* neg_offs, int n_neg, const rmcv_armour* armours, int n_armours,
+                            int vw, int vh, int side, int flags, uint8_t* out, int out_stride);
+/* a pipeline's sheets: rmcv_pipeline_set_source_views' semantics (allocates HERE, no submit blocks, n == 0: off).  A third kind of view: the
+ * latest of the three setters wins, rmcv_pipeline_views then returns sheets (n of vh + side rows, stride 6 vw), and with
+ * rmcv_pipeline_set_view_labels on the label pass draws over the left pane.  With sheets off a submit enqueues exactly what it did before. */
+int rmcv_pipeline_set_sheets(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int side, int flags);
+
 /* ---- the session recorder: rm::debug::logger (include/debug.h:13-29, src/debug.cpp:9-41) for frames resident in HBM ----
  * The reference records every frame the detector saw, losslessly (FFV1), with a `data` record per frame.  Here chosen frames of every batch
  * are packed losslessly ON THE DEVICE into a ring of the last `slots` batches, together with what is needed to run the batch again; the

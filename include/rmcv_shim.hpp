@@ -19,6 +19,7 @@
 // rm::extract_color_raw, the same on the sensor's buffer as delivered (8- or 16-bit samples, to be mirrored and / or flipped).
 // rm::CalcGamma and rm::AutoEnhance (include/imgproc.h:23, 35) are here too, and one more addition: rm::extract_color_enhanced, the two
 // of rm::AutoEnhance + rm::extract_color fused (the enhanced frame is never written).
+// rm::affine_correction (include/imgproc.h:17), the icon executable/main.cpp:180 rectifies per armour, at any output size up to 256 x 256.
 // rm::utils::GetROI (include/core.h:142-147), the reference's tracked-ROI helper, is here as well (where the cv:: headers know cv::Size).
 // rm::ProjectileAngle / SolveGEA / DeltaHeight / Distance (include/mobility.h) too, behind the reference's mobility.h.
 // One more addition: rm::debug::device_view, the loop's debug image of a batch frame rendered on the device (where the cv:: headers know cv::Size).
@@ -192,6 +193,25 @@ RMCV_SHIM_LINKAGE void AutoEnhance(cv::Mat& frame, float maxGainFactor, float mi
     hip_detail::check(rmcv_auto_enhance(hip_detail::ctx(), frame.data, frame.cols, frame.rows, (int)frame.step, maxGainFactor, minGainFactor,
                                         frame.data, (int)frame.step, nullptr));
 }
+
+// ---- rm::affine_correction (include/imgproc.h:17; body src/imgproc.cpp:9-35), what executable/main.cpp:180 calls per armour with {20, 20}
+// and the labeler with {80, 80}: the vertices are clamped in place, the icon comes back as a new CV_8UC3 matrix of outSize (any size up to
+// 256 x 256), zeros when the clamped quadrilateral's box is degenerate.  On the CPU (rmcv_affine_correction_host): no context, no device.
+// (Guarded like rm::utils::GetROI below: only where the cv:: headers in use know cv::Size.)
+#if defined(CV_VERSION) || defined(RMCV_CV_HAS_SIZE)
+RMCV_SHIM_LINKAGE cv::Mat affine_correction(const cv::Mat& source, cv::Point2f vertices[4], const cv::Size outSize)
+{
+    CV_Assert(source.type() == CV_8UC3);
+    float icon[4][2];
+    for (int i = 0; i < 4; i++) icon[i][0] = vertices[i].x, icon[i][1] = vertices[i].y;
+    cv::Mat out(outSize.height, outSize.width, CV_8UC3);
+    if (rmcv_affine_correction_host(source.data, source.cols, source.rows, (int)source.step, icon, outSize.width, outSize.height, out.data, (int)out.step, nullptr) !=
+        RMCV_OK)
+        throw std::runtime_error("rmcv: rm::affine_correction needs an image of at least 1 x 1 and an outSize of 1 .. 256 x 1 .. 256");
+    for (int i = 0; i < 4; i++) vertices[i].x = icon[i][0], vertices[i].y = icon[i][1];
+    return out;
+}
+#endif
 
 // Not a reference function: rm::AutoEnhance + rm::extract_color as ONE call -- the results are rm::extract_color's on the enhanced
 // frame, which is never written (include/rmcv_abi.h: RMCV_OPT_ENHANCE): the host drops two full-frame CPU passes and `image` stays as

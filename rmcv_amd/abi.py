@@ -126,6 +126,8 @@ EXPORTS = [
     "rmcv_batch_source_views", "rmcv_batch_get_source_view", "rmcv_source_view", "rmcv_source_view_host", "rmcv_pipeline_set_source_views",
     "rmcv_format_f6", "rmcv_label_text", "rmcv_track_label_text", "rmcv_view_glyph", "rmcv_view_labels_host", "rmcv_view_labels", "rmcv_batch_view_labels",
     "rmcv_batch_view_tracks", "rmcv_pipeline_set_view_labels", "rmcv_view_text_launches",
+    "rmcv_affine_correction_host", "rmcv_icon_strip", "rmcv_icon_strip_host", "rmcv_batch_icon_strips", "rmcv_batch_get_icon_strip", "rmcv_sheet_size",
+    "rmcv_batch_labeler_sheets", "rmcv_batch_get_labeler_sheet", "rmcv_labeler_sheet_host", "rmcv_pipeline_set_sheets",
 ]
 
 
@@ -459,6 +461,19 @@ def load(path):
         L.rmcv_pipeline_set_view_labels.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.rmcv_view_text_launches.restype = C.c_int64
         L.rmcv_view_text_launches.argtypes = []
+    if hasattr(L, "rmcv_icon_strip_host"):  # (builds from before the icon strip stay loadable for A/B runs)
+        strip = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.rmcv_affine_correction_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.rmcv_icon_strip_host.argtypes = strip
+        L.rmcv_icon_strip.argtypes = [C.c_void_p] + strip
+        L.rmcv_batch_icon_strips.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p]
+        L.rmcv_batch_get_icon_strip.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
+        L.rmcv_sheet_size.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.rmcv_batch_labeler_sheets.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int64, C.c_void_p]
+        L.rmcv_batch_get_labeler_sheet.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.rmcv_labeler_sheet_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_int,
+                                              C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.rmcv_pipeline_set_sheets.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     if hasattr(L, "rmcv_pack_bound"):  # (builds from before the session recorder stay loadable for A/B runs)
         L.rmcv_pack_bound.restype = C.c_int64
         L.rmcv_pack_bound.argtypes = [C.c_int, C.c_int]
@@ -691,6 +706,71 @@ def source_view_host(bgr, blobs=None, negatives=None, armours=None, size=(1024, 
     rc = lib().rmcv_source_view_host(*args)
     if rc:
         raise RmcvError(rc, "rmcv_source_view_host: sizes >= 1, known flags, contour offsets that do not decrease")
+    return out
+
+
+ICON_SIDE_MAX, ICON_STRIP_CAP_MAX = 256, 1024   # the icon strip
+
+
+def affine_correction_host(bgr, icon, size=(20, 20)):
+    """rm::affine_correction(bgr, out, icon, size) on the CPU (rmcv_affine_correction_host: the sequential restatement, no device), size =
+    (ow, oh) up to 256 x 256 -> (out (oh, ow, 3) uint8 BGR, zeros for a degenerate box; the icon clamped to the image, float32 [4, 2];
+    whether the box was degenerate)"""
+    bgr = np.ascontiguousarray(bgr, np.uint8)
+    assert bgr.ndim == 3 and bgr.shape[2] == 3, "an (h, w, 3) BGR image"
+    ic = np.array(icon, np.float32).reshape(4, 2).copy()
+    ow, oh = int(size[0]), int(size[1])
+    out = np.empty((max(oh, 0), max(ow, 0), 3), np.uint8)
+    deg = C.c_int32(0)
+    rc = lib().rmcv_affine_correction_host(ptr(bgr), bgr.shape[1], bgr.shape[0], 3 * bgr.shape[1], ptr(ic), ow, oh, ptr(out), 3 * ow, C.byref(deg))
+    if rc:
+        raise RmcvError(rc, "rmcv_affine_correction_host: an image of at least 1 x 1, an output size of 1 .. 256 x 1 .. 256")
+    return out, ic, bool(deg.value)
+
+
+def icon_strip_args(bgr, armours, side, cap):
+    """the argument list rmcv_icon_strip and rmcv_icon_strip_host share, and the arrays it points into: bgr (h, w, 3) uint8; armours ARMOUR[];
+    cap None: as many slots as armours (at least one) -> (args, out (side, cap side, 3) uint8, keepalive)"""
+    bgr = np.ascontiguousarray(bgr, np.uint8)
+    assert bgr.ndim == 3 and bgr.shape[2] == 3, "an (h, w, 3) BGR image"
+    armours = np.ascontiguousarray(armours if armours is not None else [], ARMOUR).reshape(-1)
+    side, cap = int(side), int(max(len(armours), 1) if cap is None else cap)
+    out = np.empty((max(side, 0), max(cap * side, 0), 3), np.uint8)
+    args = [ptr(bgr), bgr.shape[1], bgr.shape[0], 3 * bgr.shape[1], ptr(armours) if len(armours) else None, len(armours), side, cap, ptr(out), 3 * cap * side]
+    return args, out, (bgr, armours)
+
+
+def icon_strip_host(bgr, armours, side=80, cap=None):
+    """the labeler's icon strip (executable/svm/labeler.cpp:93-106) on the CPU (rmcv_icon_strip_host): the icon of armour j < min(n, cap) at
+    side x side in columns [j side, (j + 1) side), zeros elsewhere -> (side, cap side, 3) uint8 BGR"""
+    args, out, keep = icon_strip_args(bgr, armours, side, cap)
+    rc = lib().rmcv_icon_strip_host(*args)
+    if rc:
+        raise RmcvError(rc, "rmcv_icon_strip_host: an image of at least 1 x 1, side 1 .. 256, cap 1 .. 1024")
+    return out
+
+
+def sheet_size(size, side):
+    """(sheet_w, sheet_h) = (2 vw, vh + side) of the labeler's sheet at view size `size` = (vw, vh) (rmcv_sheet_size)"""
+    sw, sh = C.c_int32(0), C.c_int32(0)
+    rc = lib().rmcv_sheet_size(int(size[0]), int(size[1]), int(side), C.byref(sw), C.byref(sh))
+    if rc:
+        raise RmcvError(rc, "rmcv_sheet_size: a view of at least 1 x 1, side 1 .. 256 and at most 2 vw")
+    return sw.value, sh.value
+
+
+def labeler_sheet_host(bgr, binary, blobs=None, negatives=None, armours=None, size=(640, 512), side=80, flags=VIEW_ALL):
+    """the labeler's sheet (executable/svm/labeler.cpp:113-119) at view size `size` = (vw, vh) on the CPU (rmcv_labeler_sheet_host):
+    source_view_host(bgr, ..., flags) | debug_view_host(binary, flags=0) over icon_strip_host -> (vh + side, 2 vw, 3) uint8 BGR"""
+    args, _, keep = source_view_args(bgr, blobs, negatives, armours, flags, size)
+    binary = np.ascontiguousarray(binary, np.uint8)
+    assert binary.shape == keep[-1].shape[:2], "the binary image has the frame's extent"
+    vw, vh, side = int(size[0]), int(size[1]), int(side)
+    out = np.empty((max(vh + side, 0), max(2 * vw, 0), 3), np.uint8)
+    # (view_args' tail is flags, vw, vh, out, out_stride: the sheet's is vw, vh, side, flags, out, out_stride)
+    rc = lib().rmcv_labeler_sheet_host(*args[:4], ptr(binary), binary.shape[1], *args[4:11], vw, vh, side, int(flags), ptr(out), 6 * vw)
+    if rc:
+        raise RmcvError(rc, "rmcv_labeler_sheet_host: sizes >= 1, side 1 .. 256 and at most 2 vw, known flags")
     return out
 
 

@@ -643,6 +643,80 @@ class Context:
         self._chk(lib().rmcv_source_view(self._h, *args))
         return out
 
+    # ---------------------------------------------------------------- the icon strip and the labeler's sheet
+    def _to_host(self, call, n, rows, row_bytes):
+        """run call(device pointer) into a device buffer of this call's own for n images of rows x row_bytes bytes; synchronise; download"""
+        d = C.c_void_p()
+        if lib().rmcv_device_alloc(self.device, C.c_int64(max(n * rows * row_bytes, 1)), C.byref(d)):
+            raise RmcvError(abi.ERR_NOMEM, "rmcv_device_alloc")
+        try:
+            call(d)
+            self.sync()
+            host = np.empty((n, rows, row_bytes // 3, 3), np.uint8)
+            rc = lib().rmcv_device_download(self.device, ptr(host), d, C.c_int64(host.nbytes))
+            if rc:
+                raise RmcvError(rc, "rmcv_device_download")
+            return host
+        finally:
+            lib().rmcv_device_free(self.device, d)
+
+    def icon_strips(self, frames, side=80, cap=None, dst=None, stream=None, counts=None):
+        """the labeler's icon strips (executable/svm/labeler.cpp:93-106) of the chosen frames of the batch run last: every armour's icon
+        rectified to side x side on the frame the results are defined on, slot j at columns [j side, (j + 1) side), zeros from the frame's
+        count on (rmcv_batch_icon_strips; asynchronous, behind the run).  cap: slots per strip (default: the context's max_armours).
+        dst: a device pointer of the caller's for n contiguous (side, cap side, 3) strips -- then returns None; counts: a device pointer for n
+        int32, the icons rendered.  Without dst the strips come back as a host (n, side, cap side, 3) uint8 array (synchronises)."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        side, cap = int(side), int(self.limits.max_armours if cap is None else cap)
+        stride = 3 * cap * side
+        cnt = C.c_void_p(int(counts)) if counts is not None else None
+
+        def call(d):
+            self._chk(lib().rmcv_batch_icon_strips(self._h, ptr(fr), len(fr), side, cap, d, stride, stride * side, cnt, C.c_void_p(stream or 0)))
+        if dst is not None:
+            call(C.c_void_p(int(dst)))
+            return None
+        return self._to_host(call, len(fr), max(side, 0), max(stride, 0))
+
+    def icon_strip(self, frame, side=80, cap=None):
+        """one frame's icon strip on the host -> ((side, cap side, 3) uint8 BGR, icons rendered) (rmcv_batch_get_icon_strip; refuses a frame
+        with an overflow status)"""
+        side, cap = int(side), int(self.limits.max_armours if cap is None else cap)
+        out = np.empty((max(side, 0), max(cap * side, 0), 3), np.uint8)
+        na = C.c_int32(0)
+        self._chk(lib().rmcv_batch_get_icon_strip(self._h, int(frame), side, cap, ptr(out), 3 * cap * side, C.byref(na)))
+        return out, na.value
+
+    def icon_strip_of(self, bgr, armours, side=80, cap=None):
+        """stage-wise: the icon strip of a host BGR image and host armours through the same kernel (rmcv_icon_strip; arguments as
+        abi.icon_strip_host)"""
+        args, out, keep = abi.icon_strip_args(bgr, armours, side, cap)
+        self._chk(lib().rmcv_icon_strip(self._h, *args))
+        return out
+
+    def labeler_sheets(self, frames, size=(640, 512), side=80, flags=abi.VIEW_ALL, dst=None, stream=None):
+        """the labeler's sheets (executable/svm/labeler.cpp:113-119) of the chosen frames of the batch run last at view size `size` =
+        (vw, vh): the source view with `flags` | the plain binary as BGR, over the icon strip -- (vh + side, 2 vw, 3) each
+        (rmcv_batch_labeler_sheets; asynchronous, behind the run).  dst: a device pointer of the caller's for n contiguous sheets -- then
+        returns None; without it the sheets come back as a host (n, vh + side, 2 vw, 3) uint8 array (synchronises)."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        vw, vh, side = int(size[0]), int(size[1]), int(side)
+        stride, rows = 6 * vw, vh + side
+
+        def call(d):
+            self._chk(lib().rmcv_batch_labeler_sheets(self._h, ptr(fr), len(fr), vw, vh, side, int(flags), d, stride, stride * rows, C.c_void_p(stream or 0)))
+        if dst is not None:
+            call(C.c_void_p(int(dst)))
+            return None
+        return self._to_host(call, len(fr), max(rows, 0), max(stride, 0))
+
+    def labeler_sheet(self, frame, size=(640, 512), side=80, flags=abi.VIEW_ALL):
+        """one frame's sheet on the host, (vh + side, 2 vw, 3) uint8 BGR (rmcv_batch_get_labeler_sheet; refuses a frame with an overflow status)"""
+        vw, vh, side = int(size[0]), int(size[1]), int(side)
+        out = np.empty((max(vh + side, 0), max(2 * vw, 0), 3), np.uint8)
+        self._chk(lib().rmcv_batch_get_labeler_sheet(self._h, int(frame), vw, vh, side, int(flags), ptr(out), 6 * vw))
+        return out
+
     # ---------------------------------------------------------------- view labels (DESIGN.md 4q)
     def view_labels(self, view, geometry, scale=1, armours=None, identities=None, positions=None, tracks=None, last_vertices=None, origin=(0, 0), stride=None):
         """stage-wise: the label pass over a HOST view through the kernel, in place (rmcv_view_labels; arguments as abi.view_labels_host,

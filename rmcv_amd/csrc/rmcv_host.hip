@@ -1534,6 +1534,142 @@ int rmcv_batch_get_source_view(rmcv_ctx* c, int frame, int vw, int vh, int flags
 
 } // extern "C"
 
+/* ---- the icon strip and the labeler's sheet (k_icon_strip.hip): the batch entry points; the host-side ones: k_icon_strip.hip,
+ * the stage-wise one: rmcv_stagewise.hip ---- */
+
+// rmcv_batch_icon_strips behind its checks
+static int icon_strip_batch(rmcv_ctx* c, const int32_t* frames, int n, int side, int cap, void* d_out, int out_stride, int64_t out_pitch, int32_t* d_counts,
+                            hipStream_t s)
+{
+    hipError_t e = hipSuccess;
+    if (!c->view_frames) e = dalloc(c, &c->view_frames, (size_t)c->lim.max_frames);
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the icon strips' frame list", e);
+    int rc = order_begin(c, s);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->view_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D view frames");
+    HIPCHK(c, launch_icon_strip(c->geom, c->bufs, c->lim, c->view_frames, n, side, cap, cap * side, (uint8_t*)d_out, out_stride, out_pitch, d_counts, s), "k_icon_strip");
+    return order_end(c, s);
+}
+
+static int icon_strip_check(rmcv_ctx* c, const int32_t* frames, int n, int side, int cap, int out_stride, int64_t out_pitch)
+{
+    if (!c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, ICON_STRIP_NOTHING_BOUND);
+    return refuse(c, icon_strips_refusal(frames, n, c->geom.n_frames, c->last_stages, side, cap, c->lim.max_armours, out_stride, out_pitch));
+}
+
+namespace rmcv {
+
+int ctx_sheet_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int side, int flags, int out_stride, int64_t out_pitch)
+{
+    const int need = view_stages_needed(flags & RMCV_VIEW_ALL) | view_stages_needed(0) | RMCV_STAGE_ARMOURS;
+    return refuse(c, sheets_refusal(frames, n, n_frames, stages, need, vw, vh, side, c->lim.max_width, c->lim.max_height, flags, out_stride, out_pitch));
+}
+
+// left pane, right pane, strip: the two view launches aimed at their sub-rectangles of the sheet, then k_icon_strip over its last rows
+int ctx_sheet_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int side, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
+{
+    uint8_t* sheet = (uint8_t*)d_out;
+    int rc = ctx_source_view_enqueue(c, d_frames, n, vw, vh, flags, sheet, out_stride, out_pitch, s);
+    if (rc) return rc;
+    if ((rc = ctx_view_enqueue(c, d_frames, n, vw, vh, 0, sheet + 3 * (size_t)vw, out_stride, out_pitch, s))) return rc;
+    HIPCHK(c, launch_icon_strip(c->geom, c->bufs, c->lim, d_frames, n, side, sheet_cap(vw, side, c->lim.max_armours), 2 * vw, sheet + (size_t)vh * out_stride,
+                                out_stride, out_pitch, nullptr, s),
+           "k_icon_strip");
+    return RMCV_OK;
+}
+
+} // namespace rmcv
+
+// rmcv_batch_labeler_sheets behind its checks
+static int sheet_batch(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int side, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
+{
+    if (!c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, SOURCE_VIEW_NOTHING_BOUND); // (before anything is enqueued)
+    int rc = ctx_view_prepare(c, n);
+    if (rc) return rc;
+    if ((rc = order_begin(c, s))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->view_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D view frames");
+    if ((rc = ctx_sheet_enqueue(c, c->view_frames, n, vw, vh, side, flags, d_out, out_stride, out_pitch, s))) return rc;
+    return order_end(c, s);
+}
+
+extern "C" {
+
+int rmcv_batch_icon_strips(rmcv_ctx* c, const int32_t* frames, int n, int side, int cap, void* d_out, int out_stride, int64_t out_pitch, int32_t* d_counts,
+                           void* hip_stream)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!d_out) return fail(c, RMCV_ERR_BAD_ARG, ICON_STRIP_NULL_OUTPUT);
+    const int rc = icon_strip_check(c, frames, n, side, cap, out_stride, out_pitch);
+    if (rc) return rc;
+    hipSetDevice(c->device);
+    return icon_strip_batch(c, frames, n, side, cap, d_out, out_stride, out_pitch, d_counts, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int rmcv_batch_get_icon_strip(rmcv_ctx* c, int frame, int side, int cap, uint8_t* out, int out_stride, int32_t* n_icons)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!out) return fail(c, RMCV_ERR_BAD_ARG, ICON_STRIP_NULL_OUTPUT);
+    const int32_t one = frame;
+    int rc = icon_strip_check(c, &one, 1, side, cap, out_stride, 0);
+    if (rc) return rc;
+    if ((rc = ctx_ready(c))) return rc;
+    int32_t st = 0;
+    HIPCHK(c, hipMemcpy(&st, c->bufs.status + frame, 4, hipMemcpyDeviceToHost), "D2H");
+    if (st & (RMCV_FRAME_OVF_CONTOURS | RMCV_FRAME_OVF_POINTS | RMCV_FRAME_OVF_BLOBS | RMCV_FRAME_OVF_ARMOURS)) return fail(c, RMCV_ERR_BAD_ARG, ICON_STRIP_OVERFLOW);
+    // (a getter: staging of its own for this one call, 16 bytes in front for the count)
+    const size_t row = (size_t)3 * cap * side;
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, 16 + row * side);
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the icon strip's staging", e);
+    rc = icon_strip_batch(c, &one, 1, side, cap, d + 16, (int)row, (int64_t)row * side, reinterpret_cast<int32_t*>(d), c->stream);
+    if (!rc) rc = wait_stream(c, c->stream, "k_icon_strip");
+    int32_t na = 0;
+    if (!rc) e = hipMemcpy2D(out, out_stride, d + 16, row, row, side, hipMemcpyDeviceToHost);
+    if (!rc && e == hipSuccess) e = hipMemcpy(&na, d, 4, hipMemcpyDeviceToHost);
+    if (rc != RMCV_ERR_TIMEOUT) hipFree(d); // (after a wait that ran out the kernel may still be using it)
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(c, RMCV_ERR_HIP, "D2H icon strip", e);
+    if (n_icons) *n_icons = na;
+    return RMCV_OK;
+}
+
+int rmcv_batch_labeler_sheets(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int side, int flags, void* d_out, int out_stride, int64_t out_pitch,
+                              void* hip_stream)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!d_out) return fail(c, RMCV_ERR_BAD_ARG, SHEET_NULL_OUTPUT);
+    const int rc = ctx_sheet_check(c, frames, n, c->geom.n_frames, c->last_stages, vw, vh, side, flags, out_stride, out_pitch);
+    if (rc) return rc;
+    hipSetDevice(c->device);
+    return sheet_batch(c, frames, n, vw, vh, side, flags, d_out, out_stride, out_pitch, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int rmcv_batch_get_labeler_sheet(rmcv_ctx* c, int frame, int vw, int vh, int side, int flags, uint8_t* out, int out_stride)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!out) return fail(c, RMCV_ERR_BAD_ARG, SHEET_NULL_OUTPUT);
+    const int32_t one = frame;
+    int rc = ctx_sheet_check(c, &one, 1, c->geom.n_frames, c->last_stages, vw, vh, side, flags, out_stride, 0);
+    if (rc) return rc;
+    if ((rc = ctx_ready(c))) return rc;
+    int32_t st = 0;
+    HIPCHK(c, hipMemcpy(&st, c->bufs.status + frame, 4, hipMemcpyDeviceToHost), "D2H");
+    if (st & (RMCV_FRAME_OVF_CONTOURS | RMCV_FRAME_OVF_POINTS | RMCV_FRAME_OVF_BLOBS | RMCV_FRAME_OVF_ARMOURS)) return fail(c, RMCV_ERR_BAD_ARG, SHEET_OVERFLOW);
+    const size_t row = (size_t)6 * vw, rows = (size_t)vh + side;
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, row * rows);
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the sheet's staging", e);
+    rc = sheet_batch(c, &one, 1, vw, vh, side, flags, d, (int)row, (int64_t)(row * rows), c->stream);
+    if (!rc) rc = wait_stream(c, c->stream, "k_icon_strip");
+    if (!rc) e = hipMemcpy2D(out, out_stride, d, row, row, rows, hipMemcpyDeviceToHost);
+    if (rc != RMCV_ERR_TIMEOUT) hipFree(d);
+    if (rc) return rc;
+    if (e != hipSuccess) return fail(c, RMCV_ERR_HIP, "D2H sheet", e);
+    return RMCV_OK;
+}
+
+} // extern "C"
+
 /* ---- view labels (k_view_text.hip): the batch entry points; the host-side ones and the stage-wise one: rmcv_labels.hip ---- */
 
 namespace rmcv {

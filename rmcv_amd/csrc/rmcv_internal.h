@@ -13,6 +13,7 @@
 #include "bind_plan.h"
 #include "device_harvest.h"
 #include "device_novelty.h"
+#include "icon_strip_plan.h"
 #include "image_plan.h"
 #include "model_plan.h"
 #include "pixel_plan.h"
@@ -352,6 +353,33 @@ int ctx_label_check(rmcv_ctx* c, const char* who, rmcv_tracker* trk, const int32
 // RMCV_LABEL_TRACKS the launch is ordered as a step of the tracker's (behind its last one; the next one waits for it)
 int ctx_label_enqueue(rmcv_ctx* c, rmcv_tracker* trk, int what, int stages, const int32_t* d_frames, int n, int vw, int vh, int scale, void* d_views,
                       int out_stride, int64_t out_pitch, hipStream_t s);
+
+// ---- the icon strip and the labeler's sheet (k_icon_strip.hip) ----
+// n strips of `side` rows of strip_w >= cap * side pixels: strip k holds the icons of frame view_frames[k] (device memory; null: frame k) at
+// side x side, slot j at columns [j side, (j + 1) side); slots from the frame's count on and the remainder behind slot cap - 1 are zeros
+struct IconStripJob {
+    const uint8_t* frames;
+    int64_t frame_pitch;
+    int stride, w, h, max_armours;
+    const rmcv_armour* armours;   // [frame][max_armours], only read
+    const int32_t* n_armours;     // [frame]
+    const rmcv_point* win_eff;    // null: whole frames
+    const int32_t* view_frames;
+    int n, side, cap, strip_w;
+    uint8_t* out;
+    int out_stride;
+    int64_t out_pitch;
+    int32_t* counts;              // [n] the icons rendered (nullable)
+};
+// k_icon_strip (BGR frames) on `s`; every argument has been checked by the caller
+hipError_t launch_icon_strip(const IconStripJob& j, hipStream_t s);
+// the strips of the batch bound to (g, b), by the kernel of the batch's kind
+hipError_t launch_icon_strip(const Geom& g, const Bufs& b, const Limits& lim, const int32_t* d_frames, int n, int side, int cap, int strip_w, uint8_t* d_out,
+                             int out_stride, int64_t out_pitch, int32_t* d_counts, hipStream_t s);
+// the sheet's entry points of a context (rmcv_host.hip) as a pipeline needs them, as of the views: the planes come from ctx_view_prepare, the
+// check takes the frames as host values, the enqueue (left pane, right pane, strip) blocks nothing
+int ctx_sheet_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int side, int flags, int out_stride, int64_t out_pitch);
+int ctx_sheet_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int side, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s);
 
 // ---- what rmcv_pipeline.hip needs of a context beyond the public ABI (rmcv_host.hip) ----
 // external order: the pipeline chains a context's launches with its own events (it knows which stream ran what), so the context

@@ -123,6 +123,9 @@ struct rmcv_pipeline {
     struct Views {
         int n = 0, vw = 0, vh = 0, flags = 0, max_index = 0, need = 0; // need: the stages the flags read the results of
         bool source = false;           // rmcv_pipeline_set_source_views set them: the source view, not the binary's
+        int side = 0;                  // > 0: rmcv_pipeline_set_sheets set them: the labeler's sheet, 2 vw x (vh + side) pixels each
+        int stride() const { return side ? 6 * vw : 3 * vw; }
+        int64_t pitch() const { return (int64_t)stride() * (vh + side); }
         int32_t* d_frames = nullptr;   // [n] the frame list, on the device
         int label_what = 0, label_scale = 0; // rmcv_pipeline_set_view_labels: RMCV_LABEL_* drawn over them (0: nothing)
     } views;
@@ -474,10 +477,11 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
     if (P.views) {
         const rmcv_pipeline::Views& V = pl->views; // (as at the submit: rmcv_pipeline_set_views drains first)
         // (the source view also reads the frames, through the effective origins / gamma tables: in front of ev_free for that too, as the harvest is)
-        rc = (V.source ? ctx_source_view_enqueue : ctx_view_enqueue)(P.c, V.d_frames, V.n, V.vw, V.vh, V.flags, S.d_views, 3 * V.vw, (int64_t)3 * V.vw * V.vh, T);
+        if (V.side) rc = ctx_sheet_enqueue(P.c, V.d_frames, V.n, V.vw, V.vh, V.side, V.flags, S.d_views, V.stride(), V.pitch(), T);
+        else rc = (V.source ? ctx_source_view_enqueue : ctx_view_enqueue)(P.c, V.d_frames, V.n, V.vw, V.vh, V.flags, S.d_views, V.stride(), V.pitch(), T);
         if (rc) return cfail(pl, P.c, rc);
-        pl->last_what = V.source ? "k_view_source" : "k_view_resize";
-        S.view_n = V.n, S.view_w = V.vw, S.view_h = V.vh;
+        pl->last_what = V.side ? "k_icon_strip" : (V.source ? "k_view_source" : "k_view_resize");
+        S.view_n = V.n, S.view_w = V.side ? 2 * V.vw : V.vw, S.view_h = V.vh + V.side;
     }
     // the dataset harvest: behind the sparse stage (it reads the armours, and the identities behind the classifier), in front of ev_free (it reads
     // the frames through the effective origins / gamma tables the next pixel pass of this context rewrites); an append waits, on the GPU, for
@@ -511,7 +515,8 @@ static int finish_back(rmcv_pipeline* pl, bool latency)
     // next step wait for them) and in front of ev_done (they read the context's armours, identities, poses and effective origins)
     if (P.labels) {
         const rmcv_pipeline::Views& V = pl->views; // (as at the submit: rmcv_pipeline_set_view_labels drains first)
-        rc = ctx_label_enqueue(P.c, q.trk, P.labels, q.stages, V.d_frames, V.n, V.vw, V.vh, V.label_scale, S.d_views, 3 * V.vw, (int64_t)3 * V.vw * V.vh, T);
+        // (a sheet's left pane starts at the sheet's first byte: the labels get its pointer, the sheet's stride and pitch)
+        rc = ctx_label_enqueue(P.c, q.trk, P.labels, q.stages, V.d_frames, V.n, V.vw, V.vh, V.label_scale, S.d_views, V.stride(), V.pitch(), T);
         if (rc) return cfail(pl, P.c, rc);
         pl->last_what = "k_view_text";
     }
@@ -555,9 +560,9 @@ static int submit(rmcv_pipeline* pl, const BatchRequest& q, uint64_t* ticket)
     }
     if (pl->views.n) { // (with no views set: nothing here, and nothing further down)
         if (q.n_frames <= pl->views.max_index)
-            return pfail(pl, RMCV_ERR_BAD_ARG, pl->views.source ? SOURCE_VIEW_FEWER_FRAMES : "the batch has fewer frames than the debug views name (rmcv_pipeline_set_views)");
+            return pfail(pl, RMCV_ERR_BAD_ARG, pl->views.side ? SHEET_FEWER_FRAMES : pl->views.source ? SOURCE_VIEW_FEWER_FRAMES : "the batch has fewer frames than the debug views name (rmcv_pipeline_set_views)");
         if ((stages & pl->views.need) != pl->views.need)
-            return pfail(pl, RMCV_ERR_BAD_ARG, pl->views.source ? SOURCE_VIEW_FEWER_STAGES : "the batch's stages lack what the debug views' flags need (rmcv_pipeline_set_views)");
+            return pfail(pl, RMCV_ERR_BAD_ARG, pl->views.side ? SHEET_FEWER_STAGES : pl->views.source ? SOURCE_VIEW_FEWER_STAGES : "the batch's stages lack what the debug views' flags need (rmcv_pipeline_set_views)");
         if (pl->views.label_what) { // (with no labels set: nothing here, and nothing further down)
             if (!(stages & RMCV_STAGE_ARMOURS)) return pfail(pl, RMCV_ERR_BAD_ARG, "the batch's stages lack RMCV_STAGE_ARMOURS, which the view labels need (rmcv_pipeline_set_view_labels)");
             if ((pl->views.label_what & RMCV_LABEL_TRACKS) && !q.trk)
@@ -886,8 +891,8 @@ int rmcv_pipeline_record(rmcv_pipeline* pl, uint64_t ticket, void** d_record, vo
     return RMCV_OK;
 }
 
-// rmcv_pipeline_set_views and rmcv_pipeline_set_source_views: one set of views per pipeline, of the kind set last
-static int set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags, bool source)
+// rmcv_pipeline_set_views, rmcv_pipeline_set_source_views and rmcv_pipeline_set_sheets (side > 0): one set of views per pipeline, of the kind set last
+static int set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags, bool source, int side = 0, bool sheets = false)
 {
     if (!pl || n < 0) return RMCV_ERR_BAD_ARG;
     hipSetDevice(pl->device);
@@ -900,11 +905,13 @@ static int set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, in
         return RMCV_OK;
     }
     rmcv_ctx* c0 = pl->ring[0];
-    if ((rc = (source ? ctx_source_view_check : ctx_view_check)(c0, frames, n, pl->lim.max_frames, ~0, vw, vh, flags, 3 * vw, (int64_t)3 * vw * vh))) return cfail(pl, c0, rc);
+    if (sheets) rc = ctx_sheet_check(c0, frames, n, pl->lim.max_frames, ~0, vw, vh, side, flags, 6 * vw, (int64_t)6 * vw * ((int64_t)vh + side));
+    else rc = (source ? ctx_source_view_check : ctx_view_check)(c0, frames, n, pl->lim.max_frames, ~0, vw, vh, flags, 3 * vw, (int64_t)3 * vw * vh);
+    if (rc) return cfail(pl, c0, rc);
     pl->views.n = 0; // (off, should anything below fail)
     for (auto c : pl->ring)
         if ((rc = ctx_view_prepare(c, n))) return cfail(pl, c, rc);
-    const size_t bytes = (size_t)n * 3 * vw * vh;
+    const size_t bytes = sheets ? (size_t)n * 6 * vw * ((size_t)vh + side) : (size_t)n * 3 * vw * vh;
     hipError_t e = hipSuccess;
     for (auto& S : pl->slots) {
         if (S.d_views) (void)hipFree(S.d_views);
@@ -916,12 +923,13 @@ static int set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, in
     pl->views.d_frames = nullptr;
     if (e == hipSuccess) e = hipMalloc((void**)&pl->views.d_frames, (size_t)n * 4);
     if (e == hipSuccess) e = hipMemcpy(pl->views.d_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice);
-    if (e != hipSuccess) return pfail(pl, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, source ? "rmcv_pipeline_set_source_views" : "rmcv_pipeline_set_views", e);
+    if (e != hipSuccess) return pfail(pl, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, sheets ? "rmcv_pipeline_set_sheets" : source ? "rmcv_pipeline_set_source_views" : "rmcv_pipeline_set_views", e);
     int top = 0;
     for (int k = 0; k < n; k++) top = frames[k] > top ? frames[k] : top;
     pl->views.vw = vw, pl->views.vh = vh, pl->views.flags = flags, pl->views.max_index = top;
-    pl->views.need = view_stages_needed(flags);
+    pl->views.need = view_stages_needed(flags) | (sheets ? RMCV_STAGE_ARMOURS : 0);
     pl->views.source = source;
+    pl->views.side = sheets ? side : 0;
     pl->views.n = n;
     return RMCV_OK;
 }
@@ -929,6 +937,8 @@ static int set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, in
 int rmcv_pipeline_set_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags) { return set_views(pl, frames, n, vw, vh, flags, false); }
 
 int rmcv_pipeline_set_source_views(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int flags) { return set_views(pl, frames, n, vw, vh, flags, true); }
+
+int rmcv_pipeline_set_sheets(rmcv_pipeline* pl, const int32_t* frames, int n, int vw, int vh, int side, int flags) { return set_views(pl, frames, n, vw, vh, flags, true, side, true); }
 
 int rmcv_pipeline_set_view_labels(rmcv_pipeline* pl, int what, int scale)
 {
@@ -1005,7 +1015,7 @@ int rmcv_pipeline_views(rmcv_pipeline* pl, uint64_t ticket, void** d_views, int3
     if (!s) return RMCV_ERR_BAD_ARG;
     if (!s->view_n) return pfail(pl, RMCV_ERR_BAD_ARG, "rmcv_pipeline_views: the ticket's batch was submitted without views");
     if (d_views) *d_views = s->d_views;
-    if (stride) *stride = 3 * s->view_w;
+    if (stride) *stride = 3 * s->view_w; // (a sheet's view_w is its own: 2 vw, and view_h its vh + side)
     if (pitch) *pitch = (int64_t)3 * s->view_w * s->view_h;
     if (n) *n = s->view_n;
     return RMCV_OK;

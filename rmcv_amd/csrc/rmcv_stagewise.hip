@@ -357,4 +357,45 @@ int rmcv_source_view(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, 
     return rcw;
 }
 
+int rmcv_icon_strip(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, const rmcv_armour* armours, int n, int side, int cap, uint8_t* out,
+                    int out_stride)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (const char* bad = rmcv::icon_strip_image_refusal(bgr, out, w, h, stride, armours, n, side, cap, out_stride)) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "rmcv_icon_strip: %s", bad);
+        return fail(c, RMCV_ERR_BAD_ARG, msg);
+    }
+    if (w > c->lim.max_width || h > c->lim.max_height || cap > c->lim.max_armours || n > c->lim.max_armours) return fail(c, RMCV_ERR_BAD_ARG, rmcv::ICON_STRIP_BEYOND_LIMITS);
+    if (const int rc = ctx_ready(c)) return rc;
+    // (a stage-wise helper: buffers of its own, so that nothing bound to the context moves) -- one host block, one upload; the image
+    // packed to rows of 3 w bytes rounded up to 16
+    const int dstride = (3 * w + 15) & ~15;
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_arm = (size_t)dstride * h, o_cnt = o_arm + up16((size_t)n * sizeof(rmcv_armour)), in_bytes = o_cnt + 16;
+    const size_t row = (size_t)3 * cap * side, o_out = in_bytes, total = o_out + row * side;
+    std::vector<uint8_t> host(in_bytes, 0);
+    for (int y = 0; y < h; y++) memcpy(&host[(size_t)y * dstride], bgr + (size_t)y * stride, (size_t)3 * w);
+    if (n) memcpy(&host[o_arm], armours, (size_t)n * sizeof(rmcv_armour));
+    const int32_t count = n;
+    memcpy(&host[o_cnt], &count, 4);
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, total);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        IconStripJob S{};
+        S.frames = d, S.frame_pitch = (int64_t)dstride * h, S.stride = dstride, S.w = w, S.h = h, S.max_armours = n > 0 ? n : 1;
+        S.armours = reinterpret_cast<const rmcv_armour*>(d + o_arm), S.n_armours = reinterpret_cast<const int32_t*>(d + o_cnt);
+        S.n = 1, S.side = side, S.cap = cap, S.strip_w = cap * side, S.out = d + o_out, S.out_stride = (int)row, S.out_pitch = (int64_t)row * side;
+        e = launch_icon_strip(S, c->stream);
+    }
+    c->last_what = "k_icon_strip";
+    int rcw = 0;
+    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_icon_strip");
+    if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(out, out_stride, d + o_out, row, row, side, hipMemcpyDeviceToHost);
+    if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernel may still be using it)
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_icon_strip", e);
+    return rcw;
+}
+
 } // extern "C"

@@ -170,6 +170,13 @@ class Pipeline:
         setter = self._lib.rmcv_pipeline_set_source_views if source else self._lib.rmcv_pipeline_set_views
         self._chk(setter(self._h, ptr(fr) if len(fr) else None, len(fr), int(size[0]), int(size[1]), int(flags)))
 
+    def set_sheets(self, frames, size=(640, 512), side=80, flags=abi.VIEW_ALL):
+        """from the next submit on, every batch renders the labeler's sheets of `frames` at view size = (vw, vh) with icons of
+        side x side: views() then returns [n, vh + side, 2 vw, 3] (rmcv_pipeline_set_sheets: allocates and drains HERE; no submit blocks).
+        A third kind of view: the one set last wins.  frames empty or None: off."""
+        fr = np.ascontiguousarray(frames if frames is not None else [], np.int32).reshape(-1)
+        self._chk(self._lib.rmcv_pipeline_set_sheets(self._h, ptr(fr) if len(fr) else None, len(fr), int(size[0]), int(size[1]), int(side), int(flags)))
+
     def set_view_labels(self, what, scale=1):
         """from the next submit on, the label pass over every batch's views, whichever kind is set: what = abi.LABEL_ARMOURS
         (the armours' lines) | abi.LABEL_TRACKS (the tracker's targets, behind the tracker step of the same tracked submit) at an integer
