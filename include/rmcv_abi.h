@@ -1720,6 +1720,50 @@ int  rmcv_dataset_append_rows(rmcv_dataset* ds, const uint8_t* rows, const int32
 int  rmcv_harvest_novel_host(const uint8_t* rows, const int32_t* n_rows, const int32_t* labels, int n_streams, int ring_rows, int32_t max_sad,
                              uint8_t* rings, int64_t* pushed, uint8_t* keep_out, int32_t* min_sad_out, int64_t* near_out);
 
+/* ---- calibration capture: sub-pixel corner refinement ------------------------------------------------------------------
+ * The pixel step of executable/calibration/hand_eye.cpp (:121, cornerSubPix(gray, corners, {8, 8}, {-1, -1}, {EPS + COUNT, 40, 0.001})) on
+ * frames resident on the device.  The rule is the library's own pinned statement of cv::cornerSubPix, rmcv_amd/csrc/device_corner.h: one
+ * source for the host form below and the kernel, which agree bit for bit.  Gray of a BGR pixel is (1868 B + 9617 G + 4899 R + 8192) >> 14.
+ * A corner is two floats (x, y), pixel centres at integers, in the coordinates of SRC(f), the BGR image a frame's results are defined on
+ * (a windowed batch: window coordinates).  The coarse guess is the caller's.  One status word per corner: */
+#define RMCV_CORNER_ITERS_MASK 0xFF        /* bits 0-7: iterations run */
+#define RMCV_CORNER_DET_ZERO   (1 << 8)    /* the window's gradient matrix was singular: the iteration stopped where it was */
+#define RMCV_CORNER_LEFT_IMAGE (1 << 9)    /* the iterate left [0, w) x [0, h): the iteration stopped there */
+#define RMCV_CORNER_REVERTED   (1 << 10)   /* the result lay more than (win_x, win_y) from the input: the input is returned */
+#define RMCV_CORNER_CONVERGED  (1 << 11)   /* the last step's squared length was <= eps * eps */
+#define RMCV_CORNER_BAD_INPUT  (1 << 12)   /* a non-finite input corner: left untouched, 0 iterations */
+#define RMCV_CORNER_WIN_MAX 15             /* win_x, win_y: 1 .. 15 (the window is (2 win_x + 1) x (2 win_y + 1)) */
+#define RMCV_CORNER_ITERS_MAX 100          /* max_iters: 1 .. 100 */
+#define RMCV_CORNER_PER_FRAME_MAX 1024     /* corners per frame: 1 .. 1024 */
+/* host, no context.  mask_out: (2 win_y + 1) rows of (2 win_x + 1) floats, the window's weights; zero zone (zero_x, zero_y): (-1, -1) none,
+ * 0 <= zero_x < win_x && 0 <= zero_y < win_y zeroes the middle (2 zero_x + 1) x (2 zero_y + 1); anything else is RMCV_ERR_BAD_ARG (OpenCV
+ * ignores it). */
+int  rmcv_corner_mask(int win_x, int win_y, int zero_x, int zero_y, float* mask_out);
+/* host, no context: gray_out[y * gray_stride + x] of a BGR image (stride >= 3 w, gray_stride >= w) */
+int  rmcv_gray_host(const uint8_t* bgr, int w, int h, int stride, uint8_t* gray_out, int gray_stride);
+/* host, no context: the sequential statement of the rule.  corners: n x 2 floats, refined in place; status_out (nullable): n words.
+ * RMCV_ERR_BAD_ARG: a null buffer, w or h < 1, stride < 3 w, n < 0, win / zero zone / max_iters / eps (finite, >= 0) outside their limits. */
+int  rmcv_corner_subpix_host(const uint8_t* bgr, int w, int h, int stride, float* corners, int n, int win_x, int win_y, int zero_x, int zero_y,
+                             int max_iters, double eps, int32_t* status_out);
+/* stage-wise: the same through the kernel, on a host image and host corners, with device buffers of its own (nothing bound to the context
+ * moves).  n: 1 .. RMCV_CORNER_PER_FRAME_MAX; w, h within the context's max_width / max_height.  Waits with the context's deadline. */
+int  rmcv_corner_subpix(rmcv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, float* corners, int n, int win_x, int win_y, int zero_x,
+                        int zero_y, int max_iters, double eps, int32_t* status_out);
+/* the corners of n chosen frames of the batch bound, refined in place in the caller's device table: d_corners float [n][per_frame][2], chosen
+ * frame k's corners in row k; d_counts (nullable) int32 [n]: row k holds d_counts[k] corners (clamped to 0 .. per_frame), entries beyond are not
+ * touched; d_status (nullable) int32 [n][per_frame].  SRC(f) is read as rmcv_batch_source_views reads it: all five kinds of source, a windowed
+ * batch at its effective origin, RMCV_OPT_ENHANCE through the frame's table -- for those two the call goes behind the run that made them (a
+ * last run with RMCV_STAGE_BINARY).  Asynchronous: enqueued on hip_stream (NULL: the context's), ordered behind the context's earlier work;
+ * borrowed frames must stay valid until it has finished.  RMCV_ERR_BAD_ARG with a message, before anything is enqueued: what
+ * rmcv_batch_source_views refuses about frames and n; no frames bound; a null d_corners; per_frame outside 1 .. RMCV_CORNER_PER_FRAME_MAX;
+ * win, zero zone, max_iters or eps outside their limits. */
+int  rmcv_batch_refine_corners(rmcv_ctx* ctx, const int32_t* frames, int n, void* d_corners, int per_frame, const void* d_counts, int win_x,
+                               int win_y, int zero_x, int zero_y, int max_iters, double eps, void* d_status, void* hip_stream);
+/* one frame of the batch bound, host corners (n x 2 floats) in and out, status_out nullable: the batch call on a table of the context's own,
+ * then a wait with the context's deadline */
+int  rmcv_batch_get_refined_corners(rmcv_ctx* ctx, int frame, float* corners, int n, int win_x, int win_y, int zero_x, int zero_y, int max_iters,
+                                    double eps, int32_t* status_out);
+
 /* ---- device memory for hosts without HIP headers (tools/pipeline_bench.c): frames resident in HBM ------------------------------- */
 int  rmcv_device_alloc(int device, int64_t bytes, void** d_ptr);
 void rmcv_device_free(int device, void* d_ptr);

@@ -128,6 +128,7 @@ EXPORTS = [
     "rmcv_batch_view_tracks", "rmcv_pipeline_set_view_labels", "rmcv_view_text_launches",
     "rmcv_affine_correction_host", "rmcv_icon_strip", "rmcv_icon_strip_host", "rmcv_batch_icon_strips", "rmcv_batch_get_icon_strip", "rmcv_sheet_size",
     "rmcv_batch_labeler_sheets", "rmcv_batch_get_labeler_sheet", "rmcv_labeler_sheet_host", "rmcv_pipeline_set_sheets",
+    "rmcv_corner_mask", "rmcv_gray_host", "rmcv_corner_subpix_host", "rmcv_corner_subpix", "rmcv_batch_refine_corners", "rmcv_batch_get_refined_corners",
 ]
 
 
@@ -461,6 +462,14 @@ def load(path):
         L.rmcv_pipeline_set_view_labels.argtypes = [C.c_void_p, C.c_int, C.c_int]
         L.rmcv_view_text_launches.restype = C.c_int64
         L.rmcv_view_text_launches.argtypes = []
+    if hasattr(L, "rmcv_corner_subpix_host"):  # (builds from before the corner refinement stay loadable for A/B runs)
+        rule = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_void_p]  # win_x, win_y, zero_x, zero_y, max_iters, eps, status
+        L.rmcv_corner_mask.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.rmcv_gray_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
+        L.rmcv_corner_subpix_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int] + rule
+        L.rmcv_corner_subpix.argtypes = [C.c_void_p] + L.rmcv_corner_subpix_host.argtypes
+        L.rmcv_batch_refine_corners.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + rule + [C.c_void_p]
+        L.rmcv_batch_get_refined_corners.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + rule
     if hasattr(L, "rmcv_icon_strip_host"):  # (builds from before the icon strip stay loadable for A/B runs)
         strip = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.rmcv_affine_correction_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -707,6 +716,51 @@ def source_view_host(bgr, blobs=None, negatives=None, armours=None, size=(1024, 
     if rc:
         raise RmcvError(rc, "rmcv_source_view_host: sizes >= 1, known flags, contour offsets that do not decrease")
     return out
+
+
+# corner refinement: the status word of a corner, the limits
+CORNER_ITERS_MASK, CORNER_DET_ZERO, CORNER_LEFT_IMAGE, CORNER_REVERTED, CORNER_CONVERGED, CORNER_BAD_INPUT = 0xFF, 1 << 8, 1 << 9, 1 << 10, 1 << 11, 1 << 12
+CORNER_WIN_MAX, CORNER_ITERS_MAX, CORNER_PER_FRAME_MAX = 15, 100, 1024
+
+
+def corner_mask(win=(8, 8), zero_zone=(-1, -1)):
+    """the window's weights, (2 win_y + 1, 2 win_x + 1) float32 (rmcv_corner_mask; host)"""
+    wx, wy = int(win[0]), int(win[1])
+    out = np.empty((max(2 * wy + 1, 1), max(2 * wx + 1, 1)), np.float32)
+    rc = lib().rmcv_corner_mask(wx, wy, int(zero_zone[0]), int(zero_zone[1]), ptr(out))
+    if rc:
+        raise RmcvError(rc, "rmcv_corner_mask: win 1 .. 15, a zero zone of (-1, -1) or inside the window")
+    return out
+
+
+def gray_host(bgr):
+    """(h, w) uint8 gray of an (h, w, 3) BGR image: (1868 B + 9617 G + 4899 R + 8192) >> 14 (rmcv_gray_host)"""
+    bgr = np.ascontiguousarray(bgr, np.uint8)
+    assert bgr.ndim == 3 and bgr.shape[2] == 3, "gray_host takes an (h, w, 3) BGR image"
+    out = np.empty(bgr.shape[:2], np.uint8)
+    rc = lib().rmcv_gray_host(ptr(bgr), bgr.shape[1], bgr.shape[0], 3 * bgr.shape[1], ptr(out), bgr.shape[1])
+    if rc:
+        raise RmcvError(rc, "rmcv_gray_host: an image of at least 1 x 1")
+    return out
+
+
+def corner_args(bgr, corners):
+    """(bgr, corners copy (n, 2) float32, status (n,) int32) as the corner entry points take them"""
+    bgr = np.ascontiguousarray(bgr, np.uint8)
+    assert bgr.ndim == 3 and bgr.shape[2] == 3, "corner refinement takes an (h, w, 3) BGR image"
+    c = np.array(corners, np.float32).reshape(-1, 2)
+    return bgr, c, np.zeros(len(c), np.int32)
+
+
+def corner_subpix_host(bgr, corners, win=(8, 8), zero_zone=(-1, -1), max_iters=40, eps=0.001):
+    """cornerSubPix(gray(bgr), corners, win, zero_zone, {EPS + COUNT, max_iters, eps}) on the CPU (rmcv_corner_subpix_host: the sequential
+    statement of the pinned rule) -> (corners (n, 2) float32, status (n,) int32)"""
+    bgr, c, st = corner_args(bgr, corners)
+    rc = lib().rmcv_corner_subpix_host(ptr(bgr), bgr.shape[1], bgr.shape[0], 3 * bgr.shape[1], ptr(c), len(c), int(win[0]), int(win[1]), int(zero_zone[0]),
+                                       int(zero_zone[1]), int(max_iters), float(eps), ptr(st))
+    if rc:
+        raise RmcvError(rc, "rmcv_corner_subpix_host: win 1 .. 15, a zero zone of (-1, -1) or inside the window, max_iters 1 .. 100, eps finite and >= 0")
+    return c, st
 
 
 ICON_SIDE_MAX, ICON_STRIP_CAP_MAX = 256, 1024   # the icon strip (DESIGN.md 4r)

@@ -643,6 +643,59 @@ class Context:
         self._chk(lib().rmcv_source_view(self._h, *args))
         return out
 
+    # ---------------------------------------------------------------- corner refinement
+    def refine_corners(self, frames, corners, counts=None, win=(8, 8), zero_zone=(-1, -1), max_iters=40, eps=0.001, status=None, per_frame=None, stream=None):
+        """cornerSubPix (executable/calibration/hand_eye.cpp:121) for the corners of the chosen frames of the batch bound, on the device
+        (rmcv_batch_refine_corners; asynchronous).  corners: a host (n, per_frame, 2) array -- then returns (corners float32, status int32
+        (n, per_frame)) (synchronises; counts: host (n,) or None) -- or a device pointer of the caller's to such a float32 table, with per_frame
+        given, refined in place: counts and status are then device pointers or None, and the call returns None.  Corners are in the coordinates
+        of the image the frame's results are defined on (a windowed batch: the window's)."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        rule = (int(win[0]), int(win[1]), int(zero_zone[0]), int(zero_zone[1]), int(max_iters), float(eps))
+        if isinstance(corners, (int, C.c_void_p)):
+            d = lambda p: C.c_void_p(p.value if isinstance(p, C.c_void_p) else (int(p) if p else 0))
+            self._chk(lib().rmcv_batch_refine_corners(self._h, ptr(fr), len(fr), d(corners), int(per_frame or 0), d(counts), *rule, d(status), C.c_void_p(stream or 0)))
+            return None
+        c = np.array(corners, np.float32)
+        assert c.ndim == 3 and c.shape[2] == 2 and c.shape[0] == len(fr), "corners: (n, per_frame, 2)"
+        n, per = c.shape[0], c.shape[1]
+        cnt = None if counts is None else np.ascontiguousarray(counts, np.int32).reshape(-1)
+        assert cnt is None or len(cnt) == n, "counts: one per chosen frame"
+        st = np.zeros((n, per), np.int32)
+        o_st, o_cnt = c.nbytes, c.nbytes + st.nbytes
+        d = C.c_void_p()
+        if lib().rmcv_device_alloc(self.device, C.c_int64(max(o_cnt + 4 * n, 1)), C.byref(d)):
+            raise RmcvError(abi.ERR_NOMEM, "rmcv_device_alloc")
+        try:
+            at = lambda o: C.c_void_p((d.value or 0) + o)
+            for o, a in ((0, c), (o_st, st)) + (((o_cnt, cnt),) if cnt is not None else ()):
+                if a.nbytes and lib().rmcv_device_upload(self.device, at(o), ptr(a), C.c_int64(a.nbytes)):
+                    raise RmcvError(abi.ERR_HIP, "rmcv_device_upload")
+            self._chk(lib().rmcv_batch_refine_corners(self._h, ptr(fr), n, at(0), per, at(o_cnt) if cnt is not None else None, *rule, at(o_st), C.c_void_p(stream or 0)))
+            self.sync()
+            for o, a in ((0, c), (o_st, st)):
+                if a.nbytes and lib().rmcv_device_download(self.device, ptr(a), at(o), C.c_int64(a.nbytes)):
+                    raise RmcvError(abi.ERR_HIP, "rmcv_device_download")
+            return c, st
+        finally:
+            lib().rmcv_device_free(self.device, d)
+
+    def refined_corners(self, frame, corners, win=(8, 8), zero_zone=(-1, -1), max_iters=40, eps=0.001):
+        """one frame of the batch bound, host corners in and out (rmcv_batch_get_refined_corners) -> (corners (n, 2) float32, status (n,) int32)"""
+        c = np.array(corners, np.float32).reshape(-1, 2)
+        st = np.zeros(len(c), np.int32)
+        self._chk(lib().rmcv_batch_get_refined_corners(self._h, int(frame), ptr(c), len(c), int(win[0]), int(win[1]), int(zero_zone[0]), int(zero_zone[1]),
+                                                       int(max_iters), float(eps), ptr(st)))
+        return c, st
+
+    def refine_corners_of(self, bgr, corners, win=(8, 8), zero_zone=(-1, -1), max_iters=40, eps=0.001):
+        """stage-wise: a host BGR image and host corners through the same kernel (rmcv_corner_subpix; arguments and result as
+        abi.corner_subpix_host)"""
+        bgr, c, st = abi.corner_args(bgr, corners)
+        self._chk(lib().rmcv_corner_subpix(self._h, ptr(bgr), bgr.shape[1], bgr.shape[0], 3 * bgr.shape[1], ptr(c), len(c), int(win[0]), int(win[1]),
+                                           int(zero_zone[0]), int(zero_zone[1]), int(max_iters), float(eps), ptr(st)))
+        return c, st
+
     # ---------------------------------------------------------------- the icon strip and the labeler's sheet (DESIGN.md 4r)
     def _to_host(self, call, n, rows, row_bytes):
         """run call(device pointer) into a device buffer of this call's own for n images of rows x row_bytes bytes; synchronise; download"""

@@ -123,6 +123,11 @@ struct rmcv_ctx {
     int view_cap = 0;                 // views the overlay holds
     int32_t* view_frames = nullptr;   // [max_frames] the frame list of the views enqueued last
     uint8_t* view_out = nullptr;      // [3 * max_width * max_height] one view on its way to the host (rmcv_batch_get_debug_view)
+    // corner refinement: allocated on first use, never by a run
+    float* corner_mask = nullptr;     // [CORNER_MASK_MAX] the mask of the call enqueued last, behind its host copy
+    float corner_mask_host[rmcv::CORNER_MASK_MAX] = {0};
+    int32_t* corner_frames = nullptr; // [max_frames] the frame list of the call enqueued last
+    int32_t* corner_tab = nullptr;    // [3 * RMCV_CORNER_PER_FRAME_MAX] one frame's corners and status words on their way (rmcv_batch_get_refined_corners)
     char err[256] = {0};
     std::vector<void*> allocs;
     struct Guarded { uint8_t* base; size_t bytes; const char* name; size_t rear = 0; };

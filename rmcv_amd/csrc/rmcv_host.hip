@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "rmcv_ctx.h"
+#include "device_corner.h"
 #include "device_pack.h"
 
 using namespace rmcv;
@@ -1529,6 +1530,78 @@ int rmcv_batch_get_source_view(rmcv_ctx* c, int frame, int vw, int vh, int flags
     if ((rc = source_view_batch(c, &one, 1, vw, vh, flags, c->view_out, 3 * vw, (int64_t)3 * vw * vh, c->stream))) return rc;
     WAITCHK(c, wait_stream(c, c->stream, "k_view_source"));
     HIPCHK(c, hipMemcpy2D(out, out_stride, c->view_out, (size_t)3 * vw, (size_t)3 * vw, vh, hipMemcpyDeviceToHost), "D2H view");
+    return RMCV_OK;
+}
+
+} // extern "C"
+
+/* ---- corner refinement (k_corner.hip): the batch entry points; the host-side ones: k_corner.hip, the stage-wise one:
+ * rmcv_stagewise.hip ---- */
+
+// rmcv_batch_refine_corners behind its checks
+static int corner_batch(rmcv_ctx* c, const int32_t* frames, int n, void* d_corners, int per_frame, const void* d_counts, int win_x, int win_y, int zero_x,
+                        int zero_y, int max_iters, double eps, void* d_status, hipStream_t s)
+{
+    hipError_t e = hipSuccess;
+    if (!c->corner_frames) e = dalloc(c, &c->corner_frames, (size_t)c->lim.max_frames);
+    if (e == hipSuccess && !c->corner_mask) e = dalloc(c, &c->corner_mask, (size_t)CORNER_MASK_MAX);
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the corner refinement's tables", e);
+    int rc = order_begin(c, s);
+    if (rc) return rc;
+    const int nel = (2 * win_x + 1) * (2 * win_y + 1);
+    corner_mask(win_x, win_y, zero_x, zero_y, c->corner_mask_host);
+    HIPCHK(c, hipMemcpyAsync(c->corner_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D corner frames");
+    HIPCHK(c, hipMemcpyAsync(c->corner_mask, c->corner_mask_host, (size_t)nel * 4, hipMemcpyHostToDevice, s), "H2D corner mask");
+    CornerJob j{};
+    corner_job_source(c->geom, c->bufs, &j);
+    j.frames = c->corner_frames; j.n = n; j.per_frame = per_frame;
+    j.corners = (float*)d_corners; j.counts = (const int32_t*)d_counts; j.status = (int32_t*)d_status;
+    j.mask = c->corner_mask;
+    j.win_x = win_x; j.win_y = win_y; j.max_iters = max_iters; j.eps = eps;
+    HIPCHK(c, launch_corner(j, s), "k_corner_subpix");
+    return order_end(c, s);
+}
+
+static int corner_check(rmcv_ctx* c, const int32_t* frames, int n, const void* d_corners, int per_frame, int win_x, int win_y, int zero_x, int zero_y,
+                        int max_iters, double eps)
+{
+    if (!c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, CORNER_NOTHING_BOUND);
+    return refuse(c, corners_refusal(frames, n, c->geom.n_frames, source_kind(c->geom), c->last_stages, d_corners, per_frame, win_x, win_y, zero_x, zero_y,
+                                     max_iters, eps));
+}
+
+extern "C" {
+
+int rmcv_batch_refine_corners(rmcv_ctx* c, const int32_t* frames, int n, void* d_corners, int per_frame, const void* d_counts, int win_x, int win_y,
+                              int zero_x, int zero_y, int max_iters, double eps, void* d_status, void* hip_stream)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    const int rc = corner_check(c, frames, n, d_corners, per_frame, win_x, win_y, zero_x, zero_y, max_iters, eps);
+    if (rc) return rc;
+    hipSetDevice(c->device);
+    return corner_batch(c, frames, n, d_corners, per_frame, d_counts, win_x, win_y, zero_x, zero_y, max_iters, eps, d_status,
+                        hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int rmcv_batch_get_refined_corners(rmcv_ctx* c, int frame, float* corners, int n, int win_x, int win_y, int zero_x, int zero_y, int max_iters, double eps,
+                                   int32_t* status_out)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    if (!corners) return fail(c, RMCV_ERR_BAD_ARG, CORNER_NULL_TABLE);
+    const int32_t one = frame;
+    int rc = corner_check(c, &one, 1, corners, n, win_x, win_y, zero_x, zero_y, max_iters, eps);
+    if (rc) return rc;
+    if ((rc = ctx_ready(c))) return rc;
+    if (!c->corner_tab) {
+        const hipError_t e = dalloc(c, &c->corner_tab, (size_t)3 * RMCV_CORNER_PER_FRAME_MAX);
+        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the corner refinement's staging", e);
+    }
+    int32_t* d_status = c->corner_tab + 2 * RMCV_CORNER_PER_FRAME_MAX;
+    HIPCHK(c, hipMemcpy(c->corner_tab, corners, (size_t)n * 8, hipMemcpyHostToDevice), "H2D corners");
+    if ((rc = corner_batch(c, &one, 1, c->corner_tab, n, nullptr, win_x, win_y, zero_x, zero_y, max_iters, eps, d_status, c->stream))) return rc;
+    WAITCHK(c, wait_stream(c, c->stream, "k_corner_subpix"));
+    HIPCHK(c, hipMemcpy(corners, c->corner_tab, (size_t)n * 8, hipMemcpyDeviceToHost), "D2H corners");
+    if (status_out) HIPCHK(c, hipMemcpy(status_out, d_status, (size_t)n * 4, hipMemcpyDeviceToHost), "D2H corner status");
     return RMCV_OK;
 }
 

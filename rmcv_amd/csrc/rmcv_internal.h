@@ -11,6 +11,7 @@
 
 #include "../../include/rmcv_abi.h"
 #include "bind_plan.h"
+#include "corner_plan.h"
 #include "device_harvest.h"
 #include "device_novelty.h"
 #include "icon_strip_plan.h"
@@ -380,6 +381,31 @@ hipError_t launch_icon_strip(const Geom& g, const Bufs& b, const Limits& lim, co
 // check takes the frames as host values, the enqueue (left pane, right pane, strip) blocks nothing
 int ctx_sheet_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int side, int flags, int out_stride, int64_t out_pitch);
 int ctx_sheet_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int side, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s);
+
+// ---- sub-pixel corner refinement (k_corner.hip, device_corner.h) ----
+// per_frame corners of each of n chosen frames, refined in place; SRC(f) is read by `kind` as the source view reads it
+struct CornerJob {
+    int kind;                    // SourceKind (source_view_plan.h)
+    const uint8_t* src;          // [frame] the frames as bound: BGR or mosaic, rows `stride` bytes apart, frames `frame_pitch`
+    int stride;
+    int64_t frame_pitch;
+    int w, h;                    // the extent of SRC (a windowed batch's: the window's)
+    int rx, ry, lay;             // a mosaic's R site and layout word (device_bayer.h)
+    const uint8_t* lut;          // [frame][256] SOURCE_BGR_LUT: Bufs::enh_lut
+    const rmcv_point* win_eff;   // [frame]      SOURCE_BGR_WIN: Bufs::win_eff
+    const int32_t* frames;       // [n] device memory; null: row k is of frame k
+    int n, per_frame;
+    float* corners;              // [n][per_frame][2]
+    const int32_t* counts;       // [n] nullable: corners in row k, clamped to 0 .. per_frame
+    int32_t* status;             // [n][per_frame] nullable
+    const float* mask;           // [win_h][win_w] device memory (device_corner.h: corner_mask)
+    int win_x, win_y, max_iters;
+    double eps;
+};
+// k_corner_subpix<kind> on `s`; every argument has been checked by the caller (corner_plan.h)
+hipError_t launch_corner(const CornerJob& j, hipStream_t s);
+// the source fields of a job on the batch bound to (g, b)
+void corner_job_source(const Geom& g, const Bufs& b, CornerJob* j);
 
 // ---- what rmcv_pipeline.hip needs of a context beyond the public ABI (rmcv_host.hip) ----
 // external order: the pipeline chains a context's launches with its own events (it knows which stream ran what), so the context

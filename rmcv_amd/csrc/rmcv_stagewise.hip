@@ -7,6 +7,7 @@
 
 #include "rmcv_ctx.h"
 #include "device_bayer.h"
+#include "device_corner.h"
 #include "device_view.h"
 
 using namespace rmcv;
@@ -354,6 +355,53 @@ int rmcv_source_view(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, 
     if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(out, out_stride, d + o_out, (size_t)3 * vw, (size_t)3 * vw, vh, hipMemcpyDeviceToHost);
     if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernels may still be using it)
     if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_source_view", e);
+    return rcw;
+}
+
+int rmcv_corner_subpix(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, float* corners, int n, int win_x, int win_y, int zero_x, int zero_y,
+                       int max_iters, double eps, int32_t* status_out)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    const char* bad = rmcv::corner_image_refusal(bgr, corners, w, h, stride, n);
+    if (!bad && (n < 1 || n > RMCV_CORNER_PER_FRAME_MAX)) bad = rmcv::CORNER_PER_FRAME;
+    if (!bad) bad = rmcv::corner_params_refusal(win_x, win_y, zero_x, zero_y, max_iters, eps);
+    if (bad) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "rmcv_corner_subpix: %s", bad);
+        return fail(c, RMCV_ERR_BAD_ARG, msg);
+    }
+    if (w > c->lim.max_width || h > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, rmcv::CORNER_BEYOND_LIMITS);
+    if (const int rc = ctx_ready(c)) return rc;
+    // (a stage-wise helper: buffers of its own) -- one host block, one upload: the image packed to rows of 3 w bytes rounded up to 16, the
+    // corners, the mask; the status words behind them
+    const int dstride = (3 * w + 15) & ~15, nel = (2 * win_x + 1) * (2 * win_y + 1);
+    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
+    const size_t o_cor = (size_t)dstride * h, o_mask = o_cor + up16((size_t)n * 8), in_bytes = o_mask + up16((size_t)nel * 4);
+    const size_t o_st = in_bytes, total = o_st + (size_t)n * 4;
+    std::vector<uint8_t> host(in_bytes, 0);
+    for (int y = 0; y < h; y++) memcpy(&host[(size_t)y * dstride], bgr + (size_t)y * stride, (size_t)3 * w);
+    memcpy(&host[o_cor], corners, (size_t)n * 8);
+    corner_mask(win_x, win_y, zero_x, zero_y, reinterpret_cast<float*>(&host[o_mask]));
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, total);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        CornerJob j{};
+        j.kind = SOURCE_BGR;
+        j.src = d; j.stride = dstride; j.frame_pitch = (int64_t)dstride * h; j.w = w; j.h = h;
+        j.frames = nullptr; j.n = 1; j.per_frame = n;
+        j.corners = reinterpret_cast<float*>(d + o_cor); j.counts = nullptr; j.status = reinterpret_cast<int32_t*>(d + o_st);
+        j.mask = reinterpret_cast<const float*>(d + o_mask);
+        j.win_x = win_x; j.win_y = win_y; j.max_iters = max_iters; j.eps = eps;
+        e = launch_corner(j, c->stream);
+    }
+    c->last_what = "k_corner_subpix";
+    int rcw = 0;
+    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_corner_subpix");
+    if (e == hipSuccess && rcw == 0) e = hipMemcpy(corners, d + o_cor, (size_t)n * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rcw == 0 && status_out) e = hipMemcpy(status_out, d + o_st, (size_t)n * 4, hipMemcpyDeviceToHost);
+    if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernel may still be using it)
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_corner_subpix", e);
     return rcw;
 }
 

@@ -76,3 +76,27 @@ def svm_weights(seed=20241008, n_class=7):
     w = (rng.standard_normal((n_df, 1200)) * 1e-3).astype(np.float32)
     rho = (rng.standard_normal(n_df) * 0.05).astype(np.float64)
     return w, rho, np.arange(n_class, dtype=np.int32)
+
+
+def chessboard(w, h, H, nx, ny, ss=4, lo=40, hi=215):
+    """a chessboard of nx x ny unit squares under the homography H (3 x 3: board coordinates -> pixels, pixel centres at integers), every
+    pixel the mean of ss x ss samples; dark squares `lo`, light squares and everything off the board `hi` -> (bgr (h, w, 3) uint8 with equal
+    channels, the (nx - 1)(ny - 1) analytic inner corners (row-major, (x, y)) float64).  Plain numpy: what the corner refinement's tests
+    and tools/corner_bench.py draw"""
+    H = np.asarray(H, np.float64).reshape(3, 3)
+    Hi = np.linalg.inv(H)
+    off = (np.arange(ss) + 0.5) / ss - 0.5
+    xs = (np.arange(w)[:, None] + off[None, :]).reshape(-1)          # sample centres, w ss of them
+    ys = (np.arange(h)[:, None] + off[None, :]).reshape(-1)
+    X, Y = np.meshgrid(xs, ys)
+    den = Hi[2, 0] * X + Hi[2, 1] * Y + Hi[2, 2]
+    u = (Hi[0, 0] * X + Hi[0, 1] * Y + Hi[0, 2]) / den
+    v = (Hi[1, 0] * X + Hi[1, 1] * Y + Hi[1, 2]) / den
+    inside = (u >= 0) & (u < nx) & (v >= 0) & (v < ny)
+    dark = inside & (((np.floor(u) + np.floor(v)).astype(np.int64) & 1) == 0)
+    val = np.where(dark, float(lo), float(hi)).reshape(h, ss, w, ss).mean(axis=(1, 3))
+    gray = np.clip(np.floor(val + 0.5), 0, 255).astype(np.uint8)
+    bgr = np.repeat(gray[:, :, None], 3, axis=2)
+    ij = np.array([(i, j, 1.0) for j in range(1, ny) for i in range(1, nx)], np.float64)
+    p = ij @ H.T
+    return np.ascontiguousarray(bgr), p[:, :2] / p[:, 2:3]
