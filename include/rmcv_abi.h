@@ -1764,6 +1764,51 @@ int  rmcv_batch_refine_corners(rmcv_ctx* ctx, const int32_t* frames, int n, void
 int  rmcv_batch_get_refined_corners(rmcv_ctx* ctx, int frame, float* corners, int n, int win_x, int win_y, int zero_x, int zero_y, int max_iters,
                                     double eps, int32_t* status_out);
 
+/* ---- calibration capture: the chessboard detector -------------------------------------------------------------------------
+ * The step in front of the refinement in executable/calibration/hand_eye.cpp (:119, findChessboardCorners): the inner corners of a
+ * cols x rows pattern, coarse (whole pixels), in the order and the coordinates rmcv_batch_refine_corners takes.  OpenCV's detector is not
+ * restated: the rule is the library's own, in integer arithmetic throughout, written at the head of rmcv_amd/csrc/device_chess.h -- a ChESS
+ * response, non-maximum suppression, a graph of mutually accepted neighbours whose edges run along square borders, a breadth-first labelling
+ * -- one source for the host form below and the kernels, which agree byte for byte.  One status word per frame: */
+#define RMCV_CHESS_COUNT_MASK 0x7FF        /* bits 0-10: candidates found, saturating */
+#define RMCV_CHESS_FOUND      (1 << 11)    /* a board: cols * rows corners were written */
+#define RMCV_CHESS_OVERFLOW   (1 << 12)    /* more than RMCV_CHESS_CAND_MAX candidates: no board, no candidate list */
+#define RMCV_CHESS_NO_GRID    (1 << 13)    /* no component of the neighbour graph labels as a cols x rows grid */
+#define RMCV_CHESS_CAND_MAX 1024
+typedef struct rmcv_chess_params {
+    int32_t threshold;  /* >= 0: a candidate's response exceeds it */
+    int32_t contrast;   /* 0 .. 255: gray levels the two sides of an edge differ by, at least */
+    int32_t nms;        /* 1 .. 7: a candidate is the maximum of its (2 nms + 1)^2 neighbourhood */
+    int32_t dist_min;   /* 1 <= dist_min <= dist_max <= 1023: the distance of neighbouring corners, pixels */
+    int32_t dist_max;
+} rmcv_chess_params;
+/* threshold 1000, contrast 10, nms 3, dist 6 .. 255: the values the rule was prototyped with on drawn boards, not tuned on footage */
+void rmcv_chess_defaults(rmcv_chess_params* p);
+/* host, no context: the sequential statement of the rule.  cols, rows: 2 .. 32 with cols * rows <= RMCV_CORNER_PER_FRAME_MAX; params: null =
+ * the defaults.  corners_out: cols * rows x 2 floats, row-major (j * cols + i), written when a board is found (untouched otherwise);
+ * status_out (nullable): the status word; cand_out (nullable): RMCV_CHESS_CAND_MAX x 3 int32, the candidates (x, y, R) in row-major order of
+ * the image, *cand_n_out (nullable) rows written.  RMCV_ERR_BAD_ARG: a null image or corner table, w or h outside 1 .. 32767, stride < 3 w,
+ * the pattern or a parameter outside its limits. */
+int  rmcv_find_chessboard_host(const uint8_t* bgr, int w, int h, int stride, int cols, int rows, const rmcv_chess_params* params, float* corners_out,
+                               int32_t* status_out, int32_t* cand_out, int32_t* cand_n_out);
+/* stage-wise: the same through the kernels, on a host image, with device buffers of its own (nothing bound to the context moves).  w, h
+ * within the context's max_width / max_height.  Waits with the context's deadline. */
+int  rmcv_find_chessboard(rmcv_ctx* ctx, const uint8_t* bgr, int w, int h, int stride, int cols, int rows, const rmcv_chess_params* params,
+                          float* corners_out, int32_t* status_out, int32_t* cand_out, int32_t* cand_n_out);
+/* the boards of n chosen frames of the batch bound, into the caller's device tables: d_corners float [n][per_frame][2], chosen frame k's
+ * corners at the head of row k; d_counts int32 [n]: cols * rows for a frame with a board, 0 for one without (whose corner row is not touched);
+ * d_status (nullable) int32 [n].  The tables have the layout rmcv_batch_refine_corners reads: the two calls chain on the device.  SRC(f) is
+ * read as rmcv_batch_refine_corners reads it, under the same condition for windowed and enhanced batches.  Asynchronous: enqueued on
+ * hip_stream (NULL: the context's), ordered behind the context's earlier work.  RMCV_ERR_BAD_ARG with a message, before anything is
+ * enqueued: what rmcv_batch_source_views refuses about frames and n; no frames bound; a null d_corners or d_counts; the pattern or a
+ * parameter outside its limits; per_frame outside cols * rows .. RMCV_CORNER_PER_FRAME_MAX. */
+int  rmcv_batch_find_chessboards(rmcv_ctx* ctx, const int32_t* frames, int n, int cols, int rows, const rmcv_chess_params* params, void* d_corners,
+                                 int per_frame, void* d_counts, void* d_status, void* hip_stream);
+/* one frame of the batch bound, host outputs as rmcv_find_chessboard_host's: the batch call on tables of the context's own, then a wait with
+ * the context's deadline */
+int  rmcv_batch_get_chessboard(rmcv_ctx* ctx, int frame, int cols, int rows, const rmcv_chess_params* params, float* corners_out, int32_t* status_out,
+                               int32_t* cand_out, int32_t* cand_n_out);
+
 /* ---- device memory for hosts without HIP headers (tools/pipeline_bench.c): frames resident in HBM ------------------------------- */
 int  rmcv_device_alloc(int device, int64_t bytes, void** d_ptr);
 void rmcv_device_free(int device, void* d_ptr);

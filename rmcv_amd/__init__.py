@@ -18,6 +18,7 @@ from .abi import LABEL_ARMOURS, LABEL_CHARSET, LABEL_MAX_CHARS, LABEL_TRACKS, fo
 from .abi import ICON_SIDE_MAX, ICON_STRIP_CAP_MAX, affine_correction_host, icon_strip_host, labeler_sheet_host, sheet_size
 from .abi import (CORNER_BAD_INPUT, CORNER_CONVERGED, CORNER_DET_ZERO, CORNER_ITERS_MASK, CORNER_ITERS_MAX, CORNER_LEFT_IMAGE, CORNER_PER_FRAME_MAX, CORNER_REVERTED,
                   CORNER_WIN_MAX, corner_mask, corner_subpix_host, gray_host)
+from .abi import CHESS_CAND_MAX, CHESS_COUNT_MASK, CHESS_FOUND, CHESS_NO_GRID, CHESS_OVERFLOW, chess_defaults, chess_params, find_chessboard_host
 from .pipeline import Pipeline
 from .recorder import LoopRecord, Recorder, Session, loop_bound, loop_field_at, loop_trigger, pack, pack_bound, unpack
 from . import svm

@@ -129,6 +129,7 @@ EXPORTS = [
     "rmcv_affine_correction_host", "rmcv_icon_strip", "rmcv_icon_strip_host", "rmcv_batch_icon_strips", "rmcv_batch_get_icon_strip", "rmcv_sheet_size",
     "rmcv_batch_labeler_sheets", "rmcv_batch_get_labeler_sheet", "rmcv_labeler_sheet_host", "rmcv_pipeline_set_sheets",
     "rmcv_corner_mask", "rmcv_gray_host", "rmcv_corner_subpix_host", "rmcv_corner_subpix", "rmcv_batch_refine_corners", "rmcv_batch_get_refined_corners",
+    "rmcv_chess_defaults", "rmcv_find_chessboard_host", "rmcv_find_chessboard", "rmcv_batch_find_chessboards", "rmcv_batch_get_chessboard",
 ]
 
 
@@ -470,6 +471,14 @@ def load(path):
         L.rmcv_corner_subpix.argtypes = [C.c_void_p] + L.rmcv_corner_subpix_host.argtypes
         L.rmcv_batch_refine_corners.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p] + rule + [C.c_void_p]
         L.rmcv_batch_get_refined_corners.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + rule
+    if hasattr(L, "rmcv_find_chessboard_host"):  # (builds from before the chessboard detector stay loadable for A/B runs)
+        out = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # corners, status, candidates, candidate count
+        L.rmcv_chess_defaults.restype = None
+        L.rmcv_chess_defaults.argtypes = [C.c_void_p]
+        L.rmcv_find_chessboard_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p] + out
+        L.rmcv_find_chessboard.argtypes = [C.c_void_p] + L.rmcv_find_chessboard_host.argtypes
+        L.rmcv_batch_find_chessboards.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_batch_get_chessboard.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + out
     if hasattr(L, "rmcv_icon_strip_host"):  # (builds from before the icon strip stay loadable for A/B runs)
         strip = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.rmcv_affine_correction_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -761,6 +770,55 @@ def corner_subpix_host(bgr, corners, win=(8, 8), zero_zone=(-1, -1), max_iters=4
     if rc:
         raise RmcvError(rc, "rmcv_corner_subpix_host: win 1 .. 15, a zero zone of (-1, -1) or inside the window, max_iters 1 .. 100, eps finite and >= 0")
     return c, st
+
+
+# the chessboard detector: the status word of a frame, the limits
+CHESS_COUNT_MASK, CHESS_FOUND, CHESS_OVERFLOW, CHESS_NO_GRID, CHESS_CAND_MAX = 0x7FF, 1 << 11, 1 << 12, 1 << 13, 1024
+CHESS_PARAMS = ("threshold", "contrast", "nms", "dist_min", "dist_max")
+
+
+def chess_defaults():
+    """rmcv_chess_defaults as a dict: threshold, contrast, nms, dist_min, dist_max"""
+    p = np.zeros(5, np.int32)
+    lib().rmcv_chess_defaults(ptr(p))
+    return dict(zip(CHESS_PARAMS, (int(v) for v in p)))
+
+
+def chess_params(params=None, **changes):
+    """struct rmcv_chess_params as 5 int32: the defaults, then `params` (a dict), then the keyword changes"""
+    p = chess_defaults()
+    for k, v in list((params or {}).items()) + list(changes.items()):
+        assert k in p, "no chessboard parameter %r" % k
+        p[k] = int(v)
+    return np.array([p[k] for k in CHESS_PARAMS], np.int32)
+
+
+def chess_outputs(cols, rows):
+    """(corners (cols rows, 2) float32 of NaN, status (1,), candidates (1024, 3), candidate count (1,)) int32, as the entry points fill them"""
+    return (np.full((max(int(cols) * int(rows), 1), 2), np.nan, np.float32), np.zeros(1, np.int32), np.zeros((CHESS_CAND_MAX, 3), np.int32),
+            np.zeros(1, np.int32))
+
+
+def chess_result(out):
+    """(corners (cols rows, 2) float32 or None without a board, status, candidates (n, 3) int32: x, y, R)"""
+    cor, st, cand, n = out
+    return (cor if int(st[0]) & CHESS_FOUND else None), int(st[0]), cand[:int(n[0])].copy()
+
+
+CHESS_REFUSED = "a cols x rows pattern of 2 .. 32 a side and at most 1024 corners, threshold >= 0, contrast 0 .. 255, nms 1 .. 7, 1 <= dist_min <= dist_max <= 1023"
+
+
+def find_chessboard_host(bgr, cols, rows, params=None, **changes):
+    """the inner corners of a cols x rows chessboard in an (h, w, 3) BGR image on the CPU (rmcv_find_chessboard_host: the sequential statement
+    of the rule) -> (corners (cols rows, 2) float32 in row-major order, or None; the status word; the candidates (n, 3) int32)"""
+    bgr = np.ascontiguousarray(bgr, np.uint8)
+    assert bgr.ndim == 3 and bgr.shape[2] == 3, "find_chessboard_host takes an (h, w, 3) BGR image"
+    out = chess_outputs(cols, rows)
+    rc = lib().rmcv_find_chessboard_host(ptr(bgr), bgr.shape[1], bgr.shape[0], 3 * bgr.shape[1], int(cols), int(rows), ptr(chess_params(params, **changes)),
+                                         *[ptr(a) for a in out])
+    if rc:
+        raise RmcvError(rc, "rmcv_find_chessboard_host: " + CHESS_REFUSED)
+    return chess_result(out)
 
 
 ICON_SIDE_MAX, ICON_STRIP_CAP_MAX = 256, 1024   # the icon strip (DESIGN.md 4r)

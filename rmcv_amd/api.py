@@ -696,6 +696,79 @@ class Context:
                                            int(zero_zone[0]), int(zero_zone[1]), int(max_iters), float(eps), ptr(st)))
         return c, st
 
+    # ---------------------------------------------------------------- the chessboard detector
+    def find_chessboards(self, frames, cols, rows, params=None, corners=None, per_frame=None, counts=None, status=None, stream=None, **changes):
+        """the inner corners of a cols x rows chessboard (findChessboardCorners, executable/calibration/hand_eye.cpp:119) in the chosen frames
+        of the batch bound, on the device (rmcv_batch_find_chessboards; asynchronous).  Without `corners`: tables of this call's own ->
+        (corners (n, cols rows, 2) float32, NaN where no board was found, counts (n,) int32, status (n,) int32) (synchronises).  With `corners`,
+        a device pointer of the caller's to a float32 [n][per_frame][2] table: counts (int32 [n]) and status (int32 [n] or None) are device
+        pointers too, and the call returns None -- the tables are what refine_corners takes.  params: a dict of abi.chess_defaults' keys."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        prm = abi.chess_params(params, **changes)
+        d = lambda p: C.c_void_p(p.value if isinstance(p, C.c_void_p) else (int(p) if p else 0))
+        if corners is not None:
+            self._chk(lib().rmcv_batch_find_chessboards(self._h, ptr(fr), len(fr), int(cols), int(rows), ptr(prm), d(corners), int(per_frame or 0), d(counts), d(status),
+                                                        C.c_void_p(stream or 0)))
+            return None
+        n, per = len(fr), max(int(cols) * int(rows), 1)
+        c, cnt, st = np.full((n, per, 2), np.nan, np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32)
+        o_cnt, o_st = c.nbytes, c.nbytes + 4 * n
+        dev = C.c_void_p()
+        if lib().rmcv_device_alloc(self.device, C.c_int64(max(o_st + 4 * n, 1)), C.byref(dev)):
+            raise RmcvError(abi.ERR_NOMEM, "rmcv_device_alloc")
+        try:
+            at = lambda o: C.c_void_p((dev.value or 0) + o)
+            if c.nbytes and lib().rmcv_device_upload(self.device, at(0), ptr(c), C.c_int64(c.nbytes)):
+                raise RmcvError(abi.ERR_HIP, "rmcv_device_upload")
+            self._chk(lib().rmcv_batch_find_chessboards(self._h, ptr(fr), n, int(cols), int(rows), ptr(prm), at(0), per, at(o_cnt), at(o_st), C.c_void_p(stream or 0)))
+            self.sync()
+            for o, a in ((0, c), (o_cnt, cnt), (o_st, st)):
+                if a.nbytes and lib().rmcv_device_download(self.device, ptr(a), at(o), C.c_int64(a.nbytes)):
+                    raise RmcvError(abi.ERR_HIP, "rmcv_device_download")
+            return c, cnt, st
+        finally:
+            lib().rmcv_device_free(self.device, dev)
+
+    def chessboard_of(self, frame, cols, rows, params=None, **changes):
+        """one frame of the batch bound (rmcv_batch_get_chessboard) -> (corners (cols rows, 2) float32 or None, status, candidates (n, 3) int32)"""
+        out = abi.chess_outputs(cols, rows)
+        self._chk(lib().rmcv_batch_get_chessboard(self._h, int(frame), int(cols), int(rows), ptr(abi.chess_params(params, **changes)), *[ptr(a) for a in out]))
+        return abi.chess_result(out)
+
+    def find_chessboard(self, bgr, cols, rows, params=None, **changes):
+        """stage-wise: a host BGR image through the same kernels (rmcv_find_chessboard; arguments and result as abi.find_chessboard_host)"""
+        bgr = np.ascontiguousarray(bgr, np.uint8)
+        assert bgr.ndim == 3 and bgr.shape[2] == 3, "find_chessboard takes an (h, w, 3) BGR image"
+        out = abi.chess_outputs(cols, rows)
+        self._chk(lib().rmcv_find_chessboard(self._h, ptr(bgr), bgr.shape[1], bgr.shape[0], 3 * bgr.shape[1], int(cols), int(rows),
+                                             ptr(abi.chess_params(params, **changes)), *[ptr(a) for a in out]))
+        return abi.chess_result(out)
+
+    def capture_corners(self, frames, cols, rows, win=(8, 8), params=None, zero_zone=(-1, -1), max_iters=40, eps=0.001):
+        """a calibration capture: find then refine on one device table, two asynchronous calls with no host step in between ->
+        (corners (n, cols rows, 2) float32, NaN where no board was found, counts (n,), board status (n,), corner status (n, cols rows)) int32"""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        n, per = len(fr), max(int(cols) * int(rows), 1)
+        c, cnt, st, cst = np.full((n, per, 2), np.nan, np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, per), np.int32)
+        o_cnt, o_st, o_cst = c.nbytes, c.nbytes + 4 * n, c.nbytes + 8 * n
+        dev = C.c_void_p()
+        if lib().rmcv_device_alloc(self.device, C.c_int64(max(o_cst + cst.nbytes, 1)), C.byref(dev)):
+            raise RmcvError(abi.ERR_NOMEM, "rmcv_device_alloc")
+        try:
+            at = lambda o: (dev.value or 0) + o
+            for o, a in ((0, c), (o_cst, cst)):
+                if a.nbytes and lib().rmcv_device_upload(self.device, C.c_void_p(at(o)), ptr(a), C.c_int64(a.nbytes)):
+                    raise RmcvError(abi.ERR_HIP, "rmcv_device_upload")
+            self.find_chessboards(fr, cols, rows, params, corners=at(0), per_frame=per, counts=at(o_cnt), status=at(o_st))
+            self.refine_corners(fr, at(0), at(o_cnt), win, zero_zone, max_iters, eps, status=at(o_cst), per_frame=per)
+            self.sync()
+            for o, a in ((0, c), (o_cnt, cnt), (o_st, st), (o_cst, cst)):
+                if a.nbytes and lib().rmcv_device_download(self.device, ptr(a), C.c_void_p(at(o)), C.c_int64(a.nbytes)):
+                    raise RmcvError(abi.ERR_HIP, "rmcv_device_download")
+            return c, cnt, st, cst
+        finally:
+            lib().rmcv_device_free(self.device, dev)
+
     # ---------------------------------------------------------------- the icon strip and the labeler's sheet (DESIGN.md 4r)
     def _to_host(self, call, n, rows, row_bytes):
         """run call(device pointer) into a device buffer of this call's own for n images of rows x row_bytes bytes; synchronise; download"""

@@ -128,6 +128,10 @@ struct rmcv_ctx {
     float corner_mask_host[rmcv::CORNER_MASK_MAX] = {0};
     int32_t* corner_frames = nullptr; // [max_frames] the frame list of the call enqueued last
     int32_t* corner_tab = nullptr;    // [3 * RMCV_CORNER_PER_FRAME_MAX] one frame's corners and status words on their way (rmcv_batch_get_refined_corners)
+    // the chessboard detector: allocated on first use, never by a run
+    int32_t* chess_frames = nullptr;  // [max_frames] the frame list of the call enqueued last
+    uint32_t* chess_lists = nullptr;  // [max_frames][1 + CHESS_LIST_WORDS] the candidates between its two kernels
+    int32_t* chess_tab = nullptr;     // one frame's corners, count, status and candidates on their way (rmcv_batch_get_chessboard)
     char err[256] = {0};
     std::vector<void*> allocs;
     struct Guarded { uint8_t* base; size_t bytes; const char* name; size_t rear = 0; };

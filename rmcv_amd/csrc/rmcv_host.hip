@@ -1607,6 +1607,79 @@ int rmcv_batch_get_refined_corners(rmcv_ctx* c, int frame, float* corners, int n
 
 } // extern "C"
 
+/* ---- the chessboard detector (k_chess.hip): the batch entry points; the host-side ones: k_chess.hip, the stage-wise one:
+ * rmcv_stagewise.hip ---- */
+
+// rmcv_batch_find_chessboards behind its checks
+static int chess_batch(rmcv_ctx* c, const int32_t* frames, int n, int cols, int rows, const rmcv_chess_params& prm, void* d_corners, int per_frame, void* d_counts,
+                       void* d_status, void* d_cand, void* d_cand_n, hipStream_t s)
+{
+    hipError_t e = hipSuccess;
+    if (!c->chess_frames) e = dalloc(c, &c->chess_frames, (size_t)c->lim.max_frames);
+    if (e == hipSuccess && !c->chess_lists) e = dalloc(c, &c->chess_lists, (size_t)c->lim.max_frames * (1 + CHESS_LIST_WORDS));
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the chessboard detector's tables", e);
+    int rc = order_begin(c, s);
+    if (rc) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->chess_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D chessboard frames");
+    ChessJob j{};
+    corner_job_source(c->geom, c->bufs, &j.src);
+    j.src.frames = c->chess_frames; j.src.n = n;
+    j.cols = cols; j.rows = rows; j.prm = prm;
+    j.lists = c->chess_lists;
+    j.corners = (float*)d_corners; j.per_frame = per_frame; j.counts = (int32_t*)d_counts; j.status = (int32_t*)d_status;
+    j.cand = (int32_t*)d_cand; j.cand_n = (int32_t*)d_cand_n;
+    HIPCHK(c, launch_chess(j, s), "k_chess");
+    return order_end(c, s);
+}
+
+static int chess_check(rmcv_ctx* c, const int32_t* frames, int n, const void* d_corners, const void* d_counts, int per_frame, int cols, int rows,
+                       const rmcv_chess_params& prm)
+{
+    if (!c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, CHESS_NOTHING_BOUND);
+    return refuse(c, chessboards_refusal(frames, n, c->geom.n_frames, source_kind(c->geom), c->last_stages, d_corners, d_counts, per_frame, cols, rows, prm));
+}
+
+extern "C" {
+
+int rmcv_batch_find_chessboards(rmcv_ctx* c, const int32_t* frames, int n, int cols, int rows, const rmcv_chess_params* params, void* d_corners, int per_frame,
+                                void* d_counts, void* d_status, void* hip_stream)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    const rmcv_chess_params prm = params ? *params : chess_default_params();
+    const int rc = chess_check(c, frames, n, d_corners, d_counts, per_frame, cols, rows, prm);
+    if (rc) return rc;
+    hipSetDevice(c->device);
+    return chess_batch(c, frames, n, cols, rows, prm, d_corners, per_frame, d_counts, d_status, nullptr, nullptr, hip_stream ? (hipStream_t)hip_stream : c->stream);
+}
+
+int rmcv_batch_get_chessboard(rmcv_ctx* c, int frame, int cols, int rows, const rmcv_chess_params* params, float* corners_out, int32_t* status_out,
+                              int32_t* cand_out, int32_t* cand_n_out)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    const rmcv_chess_params prm = params ? *params : chess_default_params();
+    const int32_t one = frame;
+    int rc = chess_check(c, &one, 1, corners_out, corners_out, RMCV_CORNER_PER_FRAME_MAX, cols, rows, prm);
+    if (rc) return rc;
+    if ((rc = ctx_ready(c))) return rc;
+    constexpr int CAP = RMCV_CHESS_CAND_MAX, O_WORDS = 2 * RMCV_CORNER_PER_FRAME_MAX, O_CAND = O_WORDS + 4;   // corners | count, status, candidates, - | (x, y, R)
+    if (!c->chess_tab) {
+        const hipError_t e = dalloc(c, &c->chess_tab, (size_t)O_CAND + 3 * CAP);
+        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the chessboard detector's staging", e);
+    }
+    int32_t* t = c->chess_tab;
+    if ((rc = chess_batch(c, &one, 1, cols, rows, prm, t, RMCV_CORNER_PER_FRAME_MAX, t + O_WORDS, t + O_WORDS + 1, t + O_CAND, t + O_WORDS + 2, c->stream))) return rc;
+    WAITCHK(c, wait_stream(c, c->stream, "k_chess"));
+    int32_t words[3];
+    HIPCHK(c, hipMemcpy(words, t + O_WORDS, sizeof(words), hipMemcpyDeviceToHost), "D2H chessboard words");
+    if (words[0] > 0) HIPCHK(c, hipMemcpy(corners_out, t, (size_t)words[0] * 8, hipMemcpyDeviceToHost), "D2H chessboard corners");
+    if (cand_out && words[2] > 0) HIPCHK(c, hipMemcpy(cand_out, t + O_CAND, (size_t)words[2] * 12, hipMemcpyDeviceToHost), "D2H chessboard candidates");
+    if (status_out) *status_out = words[1];
+    if (cand_n_out) *cand_n_out = words[2];
+    return RMCV_OK;
+}
+
+} // extern "C"
+
 /* ---- the icon strip and the labeler's sheet (k_icon_strip.hip): the batch entry points; the host-side ones: k_icon_strip.hip,
  * the stage-wise one: rmcv_stagewise.hip ---- */
 

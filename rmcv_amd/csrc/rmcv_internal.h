@@ -11,6 +11,7 @@
 
 #include "../../include/rmcv_abi.h"
 #include "bind_plan.h"
+#include "chess_plan.h"
 #include "corner_plan.h"
 #include "device_harvest.h"
 #include "device_novelty.h"
@@ -406,6 +407,23 @@ struct CornerJob {
 hipError_t launch_corner(const CornerJob& j, hipStream_t s);
 // the source fields of a job on the batch bound to (g, b)
 void corner_job_source(const Geom& g, const Bufs& b, CornerJob* j);
+
+// ---- the chessboard detector (k_chess.hip, device_chess.h) ----
+// the board of each of n chosen frames; SRC(f) is read by the source fields of a CornerJob (corner_job_source)
+struct ChessJob {
+    CornerJob src;               // kind .. win_eff; frames (null: row k is of frame k) and n
+    int cols, rows;
+    rmcv_chess_params prm;
+    uint32_t* lists;             // [n][1 + CHESS_LIST_WORDS] the candidates between the two kernels: count, keys, responses
+    float* corners;              // [n][per_frame][2]
+    int per_frame;
+    int32_t* counts;             // [n]
+    int32_t* status;             // [n] nullable
+    int32_t* cand;               // [n][RMCV_CHESS_CAND_MAX][3] nullable: the sorted candidates (x, y, R)
+    int32_t* cand_n;             // [n] nullable
+};
+// the count words zeroed, k_chess_response<kind>, k_chess_grid<kind> on `s`; every argument has been checked by the caller (chess_plan.h)
+hipError_t launch_chess(const ChessJob& j, hipStream_t s);
 
 // ---- what rmcv_pipeline.hip needs of a context beyond the public ABI (rmcv_host.hip) ----
 // external order: the pipeline chains a context's launches with its own events (it knows which stream ran what), so the context

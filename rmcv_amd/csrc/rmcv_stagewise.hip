@@ -405,6 +405,59 @@ int rmcv_corner_subpix(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride
     return rcw;
 }
 
+int rmcv_find_chessboard(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, int cols, int rows, const rmcv_chess_params* params, float* corners_out,
+                         int32_t* status_out, int32_t* cand_out, int32_t* cand_n_out)
+{
+    if (!c) return RMCV_ERR_BAD_ARG;
+    const rmcv_chess_params prm = params ? *params : rmcv::chess_default_params();
+    const char* bad = rmcv::chess_image_refusal(bgr, corners_out, w, h, stride);
+    if (!bad) bad = rmcv::chess_params_refusal(cols, rows, prm);
+    if (bad) {
+        char msg[160];
+        snprintf(msg, sizeof(msg), "rmcv_find_chessboard: %s", bad);
+        return fail(c, RMCV_ERR_BAD_ARG, msg);
+    }
+    if (w > c->lim.max_width || h > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, rmcv::CHESS_BEYOND_LIMITS);
+    if (const int rc = ctx_ready(c)) return rc;
+    // (a stage-wise helper: buffers of its own) -- the image packed to rows of 3 w bytes rounded up to 16; behind it the words (count, status,
+    // candidates, -), the corners, the sorted candidates and the list between the two kernels
+    constexpr size_t CAP = RMCV_CHESS_CAND_MAX;
+    const int dstride = (3 * w + 15) & ~15, want = cols * rows;
+    const size_t o_words = (size_t)dstride * h, o_cor = o_words + 16, o_cand = o_cor + (size_t)want * 8, o_list = o_cand + 12 * CAP;
+    const size_t total = o_list + 4 * (1 + (size_t)rmcv::CHESS_LIST_WORDS);
+    std::vector<uint8_t> host(o_words, 0);
+    for (int y = 0; y < h; y++) memcpy(&host[(size_t)y * dstride], bgr + (size_t)y * stride, (size_t)3 * w);
+    uint8_t* d = nullptr;
+    hipError_t e = hipMalloc((void**)&d, total);
+    if (e == hipSuccess) e = hipMemcpyAsync(d, host.data(), o_words, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) {
+        ChessJob j{};
+        j.src.kind = SOURCE_BGR;
+        j.src.src = d; j.src.stride = dstride; j.src.frame_pitch = (int64_t)dstride * h; j.src.w = w; j.src.h = h;
+        j.src.frames = nullptr; j.src.n = 1;
+        j.cols = cols; j.rows = rows; j.prm = prm;
+        j.lists = reinterpret_cast<uint32_t*>(d + o_list);
+        j.corners = reinterpret_cast<float*>(d + o_cor); j.per_frame = want;
+        int32_t* words = reinterpret_cast<int32_t*>(d + o_words);
+        j.counts = words; j.status = words + 1; j.cand_n = words + 2;
+        j.cand = reinterpret_cast<int32_t*>(d + o_cand);
+        e = launch_chess(j, c->stream);
+    }
+    c->last_what = "k_chess";
+    int rcw = 0;
+    int32_t words[3] = {0, 0, 0};
+    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_chess");
+    if (e == hipSuccess && rcw == 0) e = hipMemcpy(words, d + o_words, sizeof(words), hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rcw == 0 && words[0] == want) e = hipMemcpy(corners_out, d + o_cor, (size_t)want * 8, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && rcw == 0 && cand_out && words[2] > 0 && words[2] <= (int)CAP) e = hipMemcpy(cand_out, d + o_cand, (size_t)words[2] * 12, hipMemcpyDeviceToHost);
+    if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernels may still be using it)
+    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_find_chessboard", e);
+    if (rcw) return rcw;
+    if (status_out) *status_out = words[1];
+    if (cand_n_out) *cand_n_out = words[2];
+    return RMCV_OK;
+}
+
 int rmcv_icon_strip(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, const rmcv_armour* armours, int n, int side, int cap, uint8_t* out,
                     int out_stride)
 {
