@@ -1809,6 +1809,77 @@ int  rmcv_batch_find_chessboards(rmcv_ctx* ctx, const int32_t* frames, int n, in
 int  rmcv_batch_get_chessboard(rmcv_ctx* ctx, int frame, int cols, int rows, const rmcv_chess_params* params, float* corners_out, int32_t* status_out,
                                int32_t* cand_out, int32_t* cand_n_out);
 
+/* ---- calibration solve: camera matrix and distortion from boards ------------------------------------------------------------
+ * The first solver of executable/calibration/hand_eye.cpp (:128-131, calibrateCamera) on the tables rmcv_batch_find_chessboards and
+ * rmcv_batch_refine_corners leave on the device: a capture is three asynchronous calls (find, refine, solve) and its result goes into
+ * rmcv_pnp_load_cameras.  OpenCV's solver is not restated: the rule is the library's own, written at the head of
+ * rmcv_amd/csrc/device_calib.h -- a homography per view (Hartley, DLT, a pinned cyclic Jacobi), intrinsics from the vanishing points, poses
+ * as unit quaternions, Levenberg-Marquardt with per-view elimination, every sum in a pinned order -- one source for the host form below and
+ * the kernels, which agree bit for bit.  calibrateHandEye is not here.  One status word per camera: */
+#define RMCV_CALIB_CONVERGED      (1 << 0)   /* an accepted step had |step|^2 <= eps^2 |parameters|^2 */
+#define RMCV_CALIB_MAX_ITERS      (1 << 1)   /* max_iters trials were made */
+#define RMCV_CALIB_STALLED        (1 << 2)   /* the damping passed 1e12 without an accepted step */
+#define RMCV_CALIB_TOO_FEW_VIEWS  (1 << 3)   /* fewer than 3 used views: nothing but status, views_used and iters (0) is written */
+#define RMCV_CALIB_BAD_INIT       (1 << 4)   /* the initial focal lengths or the initial cost are not finite and positive: likewise */
+#define RMCV_CALIB_TOO_MANY_VIEWS (1 << 5)   /* more than RMCV_CALIB_VIEWS_PER_CAMERA_MAX used views: likewise */
+#define RMCV_CALIB_VIEWS_MAX 4096
+#define RMCV_CALIB_VIEWS_PER_CAMERA_MAX 256
+#define RMCV_CALIB_CAMERAS_MAX 64
+/* bits of fix_mask: the parameter keeps its initial value */
+#define RMCV_CALIB_FIX_FX (1 << 0)
+#define RMCV_CALIB_FIX_FY (1 << 1)
+#define RMCV_CALIB_FIX_CX (1 << 2)
+#define RMCV_CALIB_FIX_CY (1 << 3)
+#define RMCV_CALIB_FIX_K1 (1 << 4)
+#define RMCV_CALIB_FIX_K2 (1 << 5)
+#define RMCV_CALIB_FIX_P1 (1 << 6)
+#define RMCV_CALIB_FIX_P2 (1 << 7)
+#define RMCV_CALIB_FIX_K3 (1 << 8)
+typedef struct rmcv_calib_params {
+    int32_t max_iters;  /* 1 .. 100: trials, accepted or not */
+    int32_t fix_mask;   /* 0 .. 511 */
+    double  eps;        /* finite, >= 0 */
+} rmcv_calib_params;
+/* max_iters 30, eps DBL_EPSILON (calibrateCamera's default criteria), fix_mask 0 */
+void rmcv_calib_defaults(rmcv_calib_params* p);
+typedef struct rmcv_calib_guess {  /* a camera's starting point, laid out as rmcv_pnp_config's head; camera_matrix[0] == 0: none for this camera */
+    double camera_matrix[9];
+    double dist[5];
+} rmcv_calib_guess;
+typedef struct rmcv_calib_result {
+    double  camera_matrix[9];  /* as rmcv_pnp_config's */
+    double  dist[5];           /* k1 k2 p1 p2 k3 */
+    double  rms, rms_init;     /* sqrt(cost / points): what calibrateCamera returns, and the same at the starting point */
+    int32_t views_used, iters, status, reserved;
+} rmcv_calib_result;
+typedef struct rmcv_calib_view {
+    double  rvec[3], tvec[3];  /* board to camera, as calibrateCamera's rvecs / tvecs */
+    double  q[4];              /* the same rotation as the unit quaternion (w, x, y, z) the solver carries */
+    double  rms;
+    int32_t used, reserved;    /* used = 1 is written for a used view of a solved camera; no other row is touched */
+} rmcv_calib_view;
+/* host, no context, one camera: the sequential statement of the rule.  corners float [n_views][per_frame][2], counts int32 [n_views]; a view
+ * is used iff its count is cols * rows and its corners are finite.  params: null = the defaults; guess: nullable.  result: one;
+ * views_out: n_views rows.  RMCV_ERR_BAD_ARG: a null table; n_views outside 1 .. RMCV_CALIB_VIEWS_MAX; cols * rows outside
+ * 4 .. RMCV_CORNER_PER_FRAME_MAX or a side < 1; per_frame outside cols * rows .. RMCV_CORNER_PER_FRAME_MAX; square not finite and > 0; w or h < 1;
+ * a parameter outside its limits; a guess that is not finite or has a focal length <= 0. */
+int  rmcv_calibrate_camera_host(const float* corners, int per_frame, const int32_t* counts, int n_views, int cols, int rows, double square, int w, int h,
+                                const rmcv_calib_params* params, const rmcv_calib_guess* guess, rmcv_calib_result* result, rmcv_calib_view* views_out);
+/* a fleet in one call, on device tables: d_corners / d_counts as rmcv_batch_find_chessboards and rmcv_batch_refine_corners leave them;
+ * d_view_camera (nullable: camera 0) int32 [n_views], any value (rmcv_batch_set_device_frame_cameras' rule); guesses: a HOST table of
+ * n_cameras, nullable, copied; d_results rmcv_calib_result [n_cameras], d_views rmcv_calib_view [n_views].  Asynchronous: enqueued on
+ * hip_stream (NULL: the context's), ordered behind the context's earlier work.  RMCV_ERR_BAD_ARG with a message, before anything is
+ * enqueued: what the host form refuses; n_cameras outside 1 .. RMCV_CALIB_CAMERAS_MAX. */
+int  rmcv_calibrate_cameras(rmcv_ctx* ctx, const void* d_corners, int per_frame, const void* d_counts, int n_views, const void* d_view_camera, int n_cameras,
+                            int cols, int rows, double square, int w, int h, const rmcv_calib_params* params, const rmcv_calib_guess* guesses, void* d_results,
+                            void* d_views, void* hip_stream);
+/* stage-wise: one camera, host tables through the same kernels, with device buffers of its own.  Waits with the context's deadline. */
+int  rmcv_calibrate_camera(rmcv_ctx* ctx, const float* corners, int per_frame, const int32_t* counts, int n_views, int cols, int rows, double square, int w,
+                           int h, const rmcv_calib_params* params, const rmcv_calib_guess* guess, rmcv_calib_result* result, rmcv_calib_view* views_out);
+/* camera_matrix and dist of a result into cfg; gripper2camera and the square are left alone.  RMCV_ERR_BAD_ARG: null, or a result without a
+ * solution (none of CONVERGED, MAX_ITERS, STALLED) */
+int  rmcv_calib_to_pnp_config(const rmcv_calib_result* result, rmcv_pnp_config* cfg);
+
 /* ---- device memory for hosts without HIP headers (tools/pipeline_bench.c): frames resident in HBM ------------------------------- */
 int  rmcv_device_alloc(int device, int64_t bytes, void** d_ptr);
 void rmcv_device_free(int device, void* d_ptr);

@@ -19,6 +19,9 @@ from .abi import ICON_SIDE_MAX, ICON_STRIP_CAP_MAX, affine_correction_host, icon
 from .abi import (CORNER_BAD_INPUT, CORNER_CONVERGED, CORNER_DET_ZERO, CORNER_ITERS_MASK, CORNER_ITERS_MAX, CORNER_LEFT_IMAGE, CORNER_PER_FRAME_MAX, CORNER_REVERTED,
                   CORNER_WIN_MAX, corner_mask, corner_subpix_host, gray_host)
 from .abi import CHESS_CAND_MAX, CHESS_COUNT_MASK, CHESS_FOUND, CHESS_NO_GRID, CHESS_OVERFLOW, chess_defaults, chess_params, find_chessboard_host
+from .abi import (CALIB_BAD_INIT, CALIB_CAMERAS_MAX, CALIB_CONVERGED, CALIB_FIX, CALIB_GUESS, CALIB_MAX_ITERS, CALIB_PARAMS, CALIB_RESULT, CALIB_SOLVED, CALIB_STALLED,
+                  CALIB_TOO_FEW_VIEWS, CALIB_TOO_MANY_VIEWS, CALIB_VIEW, CALIB_VIEWS_MAX, CALIB_VIEWS_PER_CAMERA_MAX, CalibResult, calib_defaults, calib_params,
+                  calibrate_camera_host)
 from .pipeline import Pipeline
 from .recorder import LoopRecord, Recorder, Session, loop_bound, loop_field_at, loop_trigger, pack, pack_bound, unpack
 from . import svm

@@ -130,6 +130,7 @@ EXPORTS = [
     "rmcv_batch_labeler_sheets", "rmcv_batch_get_labeler_sheet", "rmcv_labeler_sheet_host", "rmcv_pipeline_set_sheets",
     "rmcv_corner_mask", "rmcv_gray_host", "rmcv_corner_subpix_host", "rmcv_corner_subpix", "rmcv_batch_refine_corners", "rmcv_batch_get_refined_corners",
     "rmcv_chess_defaults", "rmcv_find_chessboard_host", "rmcv_find_chessboard", "rmcv_batch_find_chessboards", "rmcv_batch_get_chessboard",
+    "rmcv_calib_defaults", "rmcv_calibrate_camera_host", "rmcv_calibrate_cameras", "rmcv_calibrate_camera", "rmcv_calib_to_pnp_config",
 ]
 
 
@@ -479,6 +480,14 @@ def load(path):
         L.rmcv_find_chessboard.argtypes = [C.c_void_p] + L.rmcv_find_chessboard_host.argtypes
         L.rmcv_batch_find_chessboards.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
         L.rmcv_batch_get_chessboard.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p] + out
+    if hasattr(L, "rmcv_calibrate_camera_host"):  # (builds from before the calibration solve stay loadable for A/B runs)
+        tail = [C.c_int, C.c_int, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]  # cols, rows, square, w, h, params, guess(es), result(s), views
+        L.rmcv_calib_defaults.restype = None
+        L.rmcv_calib_defaults.argtypes = [C.c_void_p]
+        L.rmcv_calibrate_camera_host.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_int] + tail
+        L.rmcv_calibrate_camera.argtypes = [C.c_void_p] + L.rmcv_calibrate_camera_host.argtypes
+        L.rmcv_calibrate_cameras.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + tail + [C.c_void_p]
+        L.rmcv_calib_to_pnp_config.argtypes = [C.c_void_p, C.c_void_p]
     if hasattr(L, "rmcv_icon_strip_host"):  # (builds from before the icon strip stay loadable for A/B runs)
         strip = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.rmcv_affine_correction_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -819,6 +828,112 @@ def find_chessboard_host(bgr, cols, rows, params=None, **changes):
     if rc:
         raise RmcvError(rc, "rmcv_find_chessboard_host: " + CHESS_REFUSED)
     return chess_result(out)
+
+
+# the calibration solve: the status word of a camera, the limits, the fix mask, the records
+CALIB_CONVERGED, CALIB_MAX_ITERS, CALIB_STALLED, CALIB_TOO_FEW_VIEWS, CALIB_BAD_INIT, CALIB_TOO_MANY_VIEWS = 1, 2, 4, 8, 16, 32
+CALIB_SOLVED = CALIB_CONVERGED | CALIB_MAX_ITERS | CALIB_STALLED
+CALIB_VIEWS_MAX, CALIB_VIEWS_PER_CAMERA_MAX, CALIB_CAMERAS_MAX = 4096, 256, 64
+CALIB_FIX = dict(fx=1, fy=2, cx=4, cy=8, k1=16, k2=32, p1=64, p2=128, k3=256)
+CALIB_PARAMS = np.dtype([("max_iters", "<i4"), ("fix_mask", "<i4"), ("eps", "<f8")])
+CALIB_GUESS = np.dtype([("camera_matrix", "<f8", 9), ("dist", "<f8", 5)])
+CALIB_RESULT = np.dtype([("camera_matrix", "<f8", 9), ("dist", "<f8", 5), ("rms", "<f8"), ("rms_init", "<f8"), ("views_used", "<i4"), ("iters", "<i4"), ("status", "<i4"),
+                         ("reserved", "<i4")])
+CALIB_VIEW = np.dtype([("rvec", "<f8", 3), ("tvec", "<f8", 3), ("q", "<f8", 4), ("rms", "<f8"), ("used", "<i4"), ("reserved", "<i4")])
+CALIB_REFUSED = ("tables that are not null, n_views 1 .. 4096, n_cameras 1 .. 64, a cols x rows pattern of 4 .. 1024 corners, per_frame cols * rows .. 1024, a finite "
+                 "square > 0, w, h >= 1, max_iters 1 .. 100, fix_mask 0 .. 511, a finite eps >= 0, finite guesses with focal lengths > 0")
+
+
+def calib_defaults():
+    """rmcv_calib_defaults as a dict: max_iters, fix_mask, eps"""
+    p = np.zeros(1, CALIB_PARAMS)
+    lib().rmcv_calib_defaults(ptr(p))
+    return dict(max_iters=int(p["max_iters"][0]), fix_mask=int(p["fix_mask"][0]), eps=float(p["eps"][0]))
+
+
+def calib_params(params=None, **changes):
+    """struct rmcv_calib_params: the defaults, then `params` (a dict), then the keyword changes; fix_mask may be an iterable of CALIB_FIX's names"""
+    p = calib_defaults()
+    for k, v in list((params or {}).items()) + list(changes.items()):
+        assert k in p, "no calibration parameter %r" % k
+        p[k] = v
+    if not isinstance(p["fix_mask"], (int, np.integer)):
+        p["fix_mask"] = sum(CALIB_FIX[n] for n in p["fix_mask"])
+    out = np.zeros(1, CALIB_PARAMS)
+    out["max_iters"], out["fix_mask"], out["eps"] = int(p["max_iters"]), int(p["fix_mask"]), float(p["eps"])
+    return out
+
+
+def calib_guesses(guesses, n_cameras):
+    """a table of n_cameras struct rmcv_calib_guess, or None: `guesses` is None, one (camera_matrix, dist) pair for every camera, or a list of
+    pairs / None per camera (None: no guess for that camera)"""
+    if guesses is None:
+        return None
+    if len(guesses) == 2 and np.size(guesses[0]) == 9:
+        guesses = [guesses] * n_cameras
+    assert len(guesses) == n_cameras, "one guess per camera"
+    out = np.zeros(n_cameras, CALIB_GUESS)
+    for k, g in enumerate(guesses):
+        if g is not None:
+            out["camera_matrix"][k] = np.asarray(g[0], np.float64).reshape(9)
+            out["dist"][k] = np.asarray(g[1], np.float64).reshape(5)
+    return out
+
+
+class CalibResult:
+    """one camera's struct rmcv_calib_result (`.rec`, a numpy record) with its fields as attributes"""
+
+    def __init__(self, rec):
+        self.rec = rec
+        self.camera_matrix = np.array(rec["camera_matrix"], np.float64).reshape(3, 3)
+        self.dist = np.array(rec["dist"], np.float64)
+        self.rms, self.rms_init = float(rec["rms"]), float(rec["rms_init"])
+        self.views_used, self.iters, self.status = int(rec["views_used"]), int(rec["iters"]), int(rec["status"])
+
+    @property
+    def solved(self):
+        return bool(self.status & CALIB_SOLVED)
+
+    def as_pnp_config(self, base=None):
+        """a PnpConfig with this camera and distortion (rmcv_calib_to_pnp_config); everything else is `base`'s, or
+        the defaults'"""
+        cfg = default_pnp_config() if base is None else PnpConfig.from_buffer_copy(base)
+        rec = np.array(self.rec, CALIB_RESULT).reshape(1)
+        rc = lib().rmcv_calib_to_pnp_config(ptr(rec), C.byref(cfg))
+        if rc:
+            raise RmcvError(rc, "rmcv_calib_to_pnp_config: the result holds no solution (status %d)" % self.status)
+        return cfg
+
+    def __repr__(self):
+        return "CalibResult(status=%d, views_used=%d, iters=%d, rms=%.6g)" % (self.status, self.views_used, self.iters, self.rms)
+
+
+def calib_tables(corners, counts):
+    """(corners (n_views, per_frame, 2) float32 contiguous, counts (n_views,) int32; counts None: every view has per_frame corners)"""
+    corners = np.ascontiguousarray(corners, np.float32)
+    assert corners.ndim == 3 and corners.shape[2] == 2, "the corner table is (n_views, per_frame, 2)"
+    counts = np.full(len(corners), corners.shape[1], np.int32) if counts is None else np.ascontiguousarray(counts, np.int32).reshape(-1)
+    assert len(counts) == len(corners), "one count per view"
+    return corners, counts
+
+
+def calib_outputs(n_cameras, n_views):
+    """(results, views) as the entry points take them: zeroed, so that rows they do not touch read used = 0, status = 0"""
+    return np.zeros(n_cameras, CALIB_RESULT), np.zeros(n_views, CALIB_VIEW)
+
+
+def calibrate_camera_host(corners, counts, cols, rows, square, size, params=None, guess=None, **changes):
+    """camera matrix and distortion from chessboard views on the CPU (rmcv_calibrate_camera_host: the sequential statement of the rule, DESIGN.md
+    4u).  corners (n_views, per_frame, 2) float32 and counts (n_views,) as find / refine leave them; size = (w, h) ->
+    (CalibResult, views: a CALIB_VIEW record array of n_views rows, used = 0 for a view that was skipped)"""
+    corners, counts = calib_tables(corners, counts)
+    res, views = calib_outputs(1, len(corners))
+    g = calib_guesses(None if guess is None else [guess], 1)
+    rc = lib().rmcv_calibrate_camera_host(ptr(corners), corners.shape[1], ptr(counts), len(corners), int(cols), int(rows), float(square), int(size[0]), int(size[1]),
+                                          ptr(calib_params(params, **changes)), ptr(g) if g is not None else None, ptr(res), ptr(views))
+    if rc:
+        raise RmcvError(rc, "rmcv_calibrate_camera_host: " + CALIB_REFUSED)
+    return CalibResult(res[0]), views
 
 
 ICON_SIDE_MAX, ICON_STRIP_CAP_MAX = 256, 1024   # the icon strip (DESIGN.md 4r)

@@ -769,6 +769,100 @@ class Context:
         finally:
             lib().rmcv_device_free(self.device, dev)
 
+    # ---------------------------------------------------------------- the calibration solve
+    def _dev_tables(self, arrays):
+        """one device allocation holding the host arrays one behind the other, each at a multiple of 8 -> (base c_void_p, offsets)"""
+        offs, total = [], 0
+        for a in arrays:
+            offs.append(total)
+            total += (a.nbytes + 7) & ~7
+        dev = C.c_void_p()
+        if lib().rmcv_device_alloc(self.device, C.c_int64(max(total, 8)), C.byref(dev)):
+            raise RmcvError(abi.ERR_NOMEM, "rmcv_device_alloc")
+        return dev, offs
+
+    def _dev_copy(self, dev, off, a, up):
+        call = lib().rmcv_device_upload if up else lib().rmcv_device_download
+        args = (C.c_void_p((dev.value or 0) + off), ptr(a)) if up else (ptr(a), C.c_void_p((dev.value or 0) + off))
+        if a.nbytes and call(self.device, *args, C.c_int64(a.nbytes)):
+            raise RmcvError(abi.ERR_HIP, "rmcv_device_upload" if up else "rmcv_device_download")
+
+    def calibrate_cameras(self, corners, counts, cols, rows, square, size, view_camera=None, n_cameras=1, params=None, guesses=None, results=None, views=None,
+                          per_frame=None, n_views=None, stream=None, **changes):
+        """camera matrix and distortion of every camera of a fleet from its chessboard views, on the device (calibrateCamera,
+        executable/calibration/hand_eye.cpp:128-131; rmcv_calibrate_cameras; asynchronous).  With host arrays -- corners (n_views, per_frame, 2)
+        float32, counts (n_views,) or None, view_camera (n_views,) int32 or None -- returns ([CalibResult per camera], views: a CALIB_VIEW record
+        array) (synchronises; `results` / `views`: record arrays the device tables start from, zeroed by default).  With `results`, a device
+        pointer of the caller's to n_cameras struct rmcv_calib_result: corners, counts, view_camera (or None) and views are device pointers too --
+        the tables find_chessboards and refine_corners wrote -- per_frame and n_views say their shape, and the call returns None.
+        size = (w, h); guesses: abi.calib_guesses' forms (a host table either way)."""
+        prm = abi.calib_params(params, **changes)
+        g = abi.calib_guesses(guesses, int(n_cameras))
+        d = lambda p: C.c_void_p(p.value if isinstance(p, C.c_void_p) else (int(p) if p else 0))
+        call = lambda cor, cnt, vc, res, vw, per, n: self._chk(lib().rmcv_calibrate_cameras(
+            self._h, cor, int(per), cnt, int(n), vc, int(n_cameras), int(cols), int(rows), float(square), int(size[0]), int(size[1]), ptr(prm), ptr(g), res, vw,
+            C.c_void_p(stream or 0)))
+        if results is not None and not isinstance(results, np.ndarray):
+            call(d(corners), d(counts), d(view_camera), d(results), d(views), per_frame or 0, n_views or 0)
+            return None
+        corners, counts = abi.calib_tables(corners, counts)
+        n = len(corners)
+        vc = np.zeros(0, np.int32) if view_camera is None else np.ascontiguousarray(view_camera, np.int32).reshape(-1)
+        assert view_camera is None or len(vc) == n, "one camera index per view"
+        res0, views0 = abi.calib_outputs(max(int(n_cameras), 0), n)
+        res = res0 if results is None else np.array(results, abi.CALIB_RESULT).reshape(-1)
+        vw = views0 if views is None else np.array(views, abi.CALIB_VIEW).reshape(-1)
+        tabs = [corners, counts, vc, res, vw]
+        dev, offs = self._dev_tables(tabs)
+        try:
+            for o, a in zip(offs, tabs):
+                self._dev_copy(dev, o, a, True)
+            at = lambda k: C.c_void_p((dev.value or 0) + offs[k])
+            call(at(0), at(1), at(2) if view_camera is not None else C.c_void_p(0), at(3), at(4), corners.shape[1], n)
+            self.sync()
+            self._dev_copy(dev, offs[3], res, False)
+            self._dev_copy(dev, offs[4], vw, False)
+            return [abi.CalibResult(r) for r in res], vw
+        finally:
+            lib().rmcv_device_free(self.device, dev)
+
+    def calibrate_camera(self, corners, counts, cols, rows, square, size, params=None, guess=None, **changes):
+        """stage-wise: one camera, host tables through the same kernels (rmcv_calibrate_camera; arguments and result as
+        abi.calibrate_camera_host)"""
+        corners, counts = abi.calib_tables(corners, counts)
+        res, views = abi.calib_outputs(1, len(corners))
+        g = abi.calib_guesses(None if guess is None else [guess], 1)
+        self._chk(lib().rmcv_calibrate_camera(self._h, ptr(corners), corners.shape[1], ptr(counts), len(corners), int(cols), int(rows), float(square), int(size[0]),
+                                              int(size[1]), ptr(abi.calib_params(params, **changes)), ptr(g), ptr(res), ptr(views)))
+        return abi.CalibResult(res[0]), views
+
+    def calibrate(self, frames, cols, rows, square, size=None, win=(8, 8), chess_params=None, zero_zone=(-1, -1), corner_iters=40, corner_eps=0.001, params=None,
+                  guess=None, **changes):
+        """a calibration from the frames bound: find, refine and solve on one device allocation, three asynchronous calls with no host step in
+        between (beside capture_corners) -> (CalibResult, views (n,) CALIB_VIEW records, corners (n, cols rows, 2) float32 -- NaN where no board
+        was found --, counts (n,), board status (n,), corner status (n, cols rows)) int32.  size: (w, h) of the frames, the bound batch's by default."""
+        fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
+        n, per = len(fr), max(int(cols) * int(rows), 1)
+        size = size or (self.shape[2], self.shape[1])
+        c, cnt, st, cst = np.full((n, per, 2), np.nan, np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, per), np.int32)
+        res, vw = abi.calib_outputs(1, n)
+        tabs = [c, cnt, st, cst, res, vw]
+        dev, offs = self._dev_tables(tabs)
+        try:
+            for o, a in zip(offs, tabs):
+                self._dev_copy(dev, o, a, True)
+            at = lambda k: (dev.value or 0) + offs[k]
+            self.find_chessboards(fr, cols, rows, chess_params, corners=at(0), per_frame=per, counts=at(1), status=at(2))
+            self.refine_corners(fr, at(0), at(1), win, zero_zone, corner_iters, corner_eps, status=at(3), per_frame=per)
+            self.calibrate_cameras(at(0), at(1), cols, rows, square, size, params=params, guesses=None if guess is None else [guess], results=at(4), views=at(5),
+                                   per_frame=per, n_views=n, **changes)
+            self.sync()
+            for o, a in zip(offs, tabs):
+                self._dev_copy(dev, o, a, False)
+            return abi.CalibResult(res[0]), vw, c, cnt, st, cst
+        finally:
+            lib().rmcv_device_free(self.device, dev)
+
     # ---------------------------------------------------------------- the icon strip and the labeler's sheet (DESIGN.md 4r)
     def _to_host(self, call, n, rows, row_bytes):
         """run call(device pointer) into a device buffer of this call's own for n images of rows x row_bytes bytes; synchronise; download"""

@@ -132,6 +132,10 @@ struct rmcv_ctx {
     int32_t* chess_frames = nullptr;  // [max_frames] the frame list of the call enqueued last
     uint32_t* chess_lists = nullptr;  // [max_frames][1 + CHESS_LIST_WORDS] the candidates between its two kernels
     int32_t* chess_tab = nullptr;     // one frame's corners, count, status and candidates on their way (rmcv_batch_get_chessboard)
+    // the calibration solve: allocated on first use, never by a run
+    double* calib_ws = nullptr;       // [RMCV_CALIB_VIEWS_MAX][CALIB_VIEW_WS] a view's homography, poses and eliminated blocks
+    int32_t* calib_vcam = nullptr;    // [RMCV_CALIB_VIEWS_MAX] a view's effective camera, -1 for one not used
+    rmcv_calib_guess* calib_guesses = nullptr; // [RMCV_CALIB_CAMERAS_MAX] the guesses of the call enqueued last
     char err[256] = {0};
     std::vector<void*> allocs;
     struct Guarded { uint8_t* base; size_t bytes; const char* name; size_t rear = 0; };

@@ -11,6 +11,7 @@
 
 #include "../../include/rmcv_abi.h"
 #include "bind_plan.h"
+#include "calib_plan.h"
 #include "chess_plan.h"
 #include "corner_plan.h"
 #include "device_harvest.h"
@@ -424,6 +425,11 @@ struct ChessJob {
 };
 // the count words zeroed, k_chess_response<kind>, k_chess_grid<kind> on `s`; every argument has been checked by the caller (chess_plan.h)
 hipError_t launch_chess(const ChessJob& j, hipStream_t s);
+
+// ---- the calibration solve (k_calib.hip, device_calib.h) ----
+struct CalibJob;
+// k_calib_homography, k_calib_solve on `s`; every argument has been checked by the caller (calib_plan.h)
+hipError_t launch_calib(const CalibJob& j, hipStream_t s);
 
 // ---- what rmcv_pipeline.hip needs of a context beyond the public ABI (rmcv_host.hip) ----
 // external order: the pipeline chains a context's launches with its own events (it knows which stream ran what), so the context
