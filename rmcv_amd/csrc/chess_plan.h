@@ -42,12 +42,12 @@ static constexpr const char* CHESS_BEYOND_LIMITS = "rmcv_find_chessboard: image 
 static constexpr const char* CHESS_NULL_TABLE = "chessboard: null corner or count table";
 static constexpr const char* CHESS_NOTHING_BOUND = "chessboard: no frames are bound";
 static constexpr const char* CHESS_NEEDS_RUN = "chessboard: a windowed or enhanced batch is read behind a run with RMCV_STAGE_BINARY (its origins / tables)";
-// the batch entry points (rmcv_batch_find_chessboards, rmcv_batch_get_chessboard): source_views_refusal's rules for frames / n, then the
+// the batch entry points (rmcv_batch_find_chessboards, rmcv_batch_get_chessboard): the frame-list rule in the source views' words, then the
 // tables and the parameters.  kind: source_kind of the batch; stages: those of its last run
 inline const char* chessboards_refusal(const int32_t* frames, int n, int n_frames, int kind, int stages, const void* d_corners, const void* d_counts, int per_frame,
                                        int cols, int rows, const rmcv_chess_params& p)
 {
-    if (const char* why = source_views_refusal(frames, n, n_frames, ~0, 0, 1, 1, 1, 1, 0, 3, 3)) return why;
+    if (const FrameListFault bad = frame_list_fault(frames, n, n_frames)) return SOURCE_VIEW_FRAME_LIST[bad];
     if (!d_corners || !d_counts) return CHESS_NULL_TABLE;
     if (const char* why = chess_params_refusal(cols, rows, p)) return why;
     if (per_frame < cols * rows || per_frame > RMCV_CORNER_PER_FRAME_MAX) return CHESS_PER_FRAME;

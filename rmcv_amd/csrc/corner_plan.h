@@ -35,12 +35,12 @@ static constexpr const char* CORNER_BEYOND_LIMITS = "rmcv_corner_subpix: image b
 static constexpr const char* CORNER_NULL_TABLE = "corners: null corner table";
 static constexpr const char* CORNER_NOTHING_BOUND = "corners: no frames are bound";
 static constexpr const char* CORNER_NEEDS_RUN = "corners: a windowed or enhanced batch is read behind a run with RMCV_STAGE_BINARY (its origins / tables)";
-// the batch entry points (rmcv_batch_refine_corners, rmcv_batch_get_refined_corners): source_views_refusal's rules for frames / n, then the
+// the batch entry points (rmcv_batch_refine_corners, rmcv_batch_get_refined_corners): the frame-list rule in the source views' words, then the
 // table and the parameters.  kind: source_kind of the batch; stages: those of its last run
 inline const char* corners_refusal(const int32_t* frames, int n, int n_frames, int kind, int stages, const void* d_corners, int per_frame, int win_x, int win_y,
                                    int zero_x, int zero_y, int max_iters, double eps)
 {
-    if (const char* why = source_views_refusal(frames, n, n_frames, ~0, 0, 1, 1, 1, 1, 0, 3, 3)) return why;
+    if (const FrameListFault bad = frame_list_fault(frames, n, n_frames)) return SOURCE_VIEW_FRAME_LIST[bad];
     if (!d_corners) return CORNER_NULL_TABLE;
     if (per_frame < 1 || per_frame > RMCV_CORNER_PER_FRAME_MAX) return CORNER_PER_FRAME;
     if (const char* why = corner_params_refusal(win_x, win_y, zero_x, zero_y, max_iters, eps)) return why;

@@ -38,19 +38,16 @@ static constexpr const char* ICON_STRIP_BEYOND_LIMITS = "rmcv_icon_strip: image 
 
 // ---- the batch entry points (rmcv_batch_icon_strips, rmcv_batch_get_icon_strip) ----
 // frames: host values; n_frames / stages: the batch the strips are of and the stages it has been, or will be, through
+static constexpr FrameListWords ICON_STRIP_FRAME_LIST = {nullptr, "icon strips: no frames chosen", "icon strips: more strips than the batch has frames",
+                                                         "icon strips: a frame index is outside the batch", "icon strips: a frame index is repeated"};
 inline const char* icon_strips_refusal(const int32_t* frames, int n, int n_frames, int stages, int side, int cap, int max_armours, int out_stride, int64_t out_pitch)
 {
-    if (!frames || n < 1) return "icon strips: no frames chosen";
-    if (n > n_frames) return "icon strips: more strips than the batch has frames";
+    if (const FrameListFault bad = frame_count_fault(frames, n, n_frames)) return ICON_STRIP_FRAME_LIST[bad];
     if (side < 1 || side > ICON_SIDE_MAX) return "icon strips: side must be 1 .. 256";
     if (cap < 1 || cap > max_armours) return "icon strips: cap must be 1 .. max_armours";
     if (out_stride < 3 * (int64_t)cap * side) return "icon strips: out_stride < 3 cap side";
     if (n > 1 && out_pitch < (int64_t)out_stride * (side - 1) + 3 * (int64_t)cap * side) return "icon strips: out_pitch < out_stride (side - 1) + 3 cap side";
-    for (int k = 0; k < n; k++) {
-        if (frames[k] < 0 || frames[k] >= n_frames) return "icon strips: a frame index is outside the batch";
-        for (int q = 0; q < k; q++)
-            if (frames[q] == frames[k]) return "icon strips: a frame index is repeated";
-    }
+    if (const FrameListFault bad = frame_index_fault(frames, n, n_frames)) return ICON_STRIP_FRAME_LIST[bad];
     if (!(stages & RMCV_STAGE_ARMOURS)) return "icon strips: the batch's run lacked RMCV_STAGE_ARMOURS";
     return nullptr;
 }

@@ -1,7 +1,8 @@
 // rmcv_calib.hip -- the calibration solve behind the ABI: the host-side functions, which need no context and no device
 // (rmcv_calib_defaults, rmcv_calibrate_camera_host, rmcv_calib_to_pnp_config), the fleet call on device tables (rmcv_calibrate_cameras) and
-// the stage-wise rmcv_calibrate_camera, the same kernels on host tables with buffers of its own.  The rule is device_calib.h, every refusal
-// calib_plan.h, the kernels k_calib.hip.  No kernel lives here.
+// the stage-wise rmcv_calibrate_camera, the same kernels on host tables in a Scratch block of its own.  The rule is device_calib.h, every
+// refusal calib_plan.h, the kernels k_calib.hip; the fleet call takes its place in the context's order as every batch call does (rmcv_ctx.h:
+// order_begin / order_end).  No kernel lives here.
 #include <string.h>
 
 #include <vector>
@@ -20,21 +21,6 @@ static CalibJob calib_job(const void* corners, int per_frame, const void* counts
     j.cols = cols; j.rows = rows; j.square = square; j.w = w; j.h = h;
     j.max_iters = p.max_iters; j.fix_mask = p.fix_mask; j.eps = p.eps;
     return j;
-}
-
-// the context's ordering rule (rmcv_host.hip: order_begin / order_end), for the one call enqueued here
-static int calib_order_begin(rmcv_ctx* c, hipStream_t s)
-{
-    if (!c->external_order && c->order_pending && c->last_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_order, 0), "order: wait for the previous stream");
-    return RMCV_OK;
-}
-static int calib_order_end(rmcv_ctx* c, hipStream_t s)
-{
-    c->last_stream = s;
-    if (c->external_order) return RMCV_OK;
-    HIPCHK(c, hipEventRecord(c->ev_order, s), "order: record");
-    c->order_pending = true;
-    return RMCV_OK;
 }
 
 extern "C" {
@@ -80,7 +66,7 @@ int rmcv_calibrate_cameras(rmcv_ctx* c, const void* d_corners, int per_frame, co
     if (e == hipSuccess && !c->calib_vcam) e = dalloc(c, &c->calib_vcam, (size_t)RMCV_CALIB_VIEWS_MAX);
     if (e == hipSuccess && !c->calib_guesses) e = dalloc(c, &c->calib_guesses, (size_t)RMCV_CALIB_CAMERAS_MAX);
     if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the calibration solve's workspace", e);
-    if ((rc = calib_order_begin(c, s))) return rc;
+    if ((rc = order_begin(c, s))) return rc;
     CalibJob j = calib_job(d_corners, per_frame, d_counts, n_views, d_view_camera, n_cameras, cols, rows, square, w, h, prm);
     if (guesses) {
         HIPCHK(c, hipMemcpyAsync(c->calib_guesses, guesses, (size_t)n_cameras * sizeof(rmcv_calib_guess), hipMemcpyHostToDevice, s), "H2D calibration guesses");
@@ -88,7 +74,7 @@ int rmcv_calibrate_cameras(rmcv_ctx* c, const void* d_corners, int per_frame, co
     }
     j.ws = c->calib_ws; j.vcam = c->calib_vcam; j.results = (rmcv_calib_result*)d_results; j.views = (rmcv_calib_view*)d_views;
     HIPCHK(c, launch_calib(j, s), "k_calib");
-    return calib_order_end(c, s);
+    return order_end(c, s);
 }
 
 int rmcv_calibrate_camera(rmcv_ctx* c, const float* corners, int per_frame, const int32_t* counts, int n_views, int cols, int rows, double square, int w, int h,
@@ -96,18 +82,15 @@ int rmcv_calibrate_camera(rmcv_ctx* c, const float* corners, int per_frame, cons
 {
     if (!c) return RMCV_ERR_BAD_ARG;
     const rmcv_calib_params prm = params ? *params : calib_default_params();
-    if (const char* bad = calib_refusal(corners, counts, result, views_out, per_frame, n_views, 1, cols, rows, square, w, h, prm, guess)) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "rmcv_calibrate_camera: %s", bad);
-        return fail(c, RMCV_ERR_BAD_ARG, msg);
-    }
-    if (const int rc = ctx_ready(c)) return rc;
+    int rc = refuse_as(c, "rmcv_calibrate_camera", calib_refusal(corners, counts, result, views_out, per_frame, n_views, 1, cols, rows, square, w, h, prm, guess));
+    if (rc || (rc = ctx_ready(c))) return rc;
     // (a stage-wise helper: buffers of its own) -- the workspace | the result | the views | the guess | the corners | the counts | the flags
     const size_t b_ws = (size_t)calib_ws_doubles(n_views) * 8, b_views = (size_t)n_views * sizeof(rmcv_calib_view), b_cor = (size_t)n_views * per_frame * 8;
     const size_t o_res = b_ws, o_views = o_res + sizeof(rmcv_calib_result), o_guess = o_views + b_views, o_cor = o_guess + sizeof(rmcv_calib_guess);
     const size_t o_cnt = o_cor + b_cor, o_vcam = o_cnt + (size_t)n_views * 4, total = o_vcam + (size_t)n_views * 4;
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, total);
+    Scratch blk;
+    hipError_t e = blk.alloc(total);
+    uint8_t* const d = blk.d;
     if (e == hipSuccess) e = hipMemcpyAsync(d + o_res, result, sizeof(rmcv_calib_result), hipMemcpyHostToDevice, c->stream);   // (rows not written keep the caller's bytes)
     if (e == hipSuccess) e = hipMemcpyAsync(d + o_views, views_out, b_views, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess && guess) e = hipMemcpyAsync(d + o_guess, guess, sizeof(rmcv_calib_guess), hipMemcpyHostToDevice, c->stream);
@@ -124,10 +107,9 @@ int rmcv_calibrate_camera(rmcv_ctx* c, const float* corners, int per_frame, cons
     }
     c->last_what = "k_calib";
     int rcw = 0;
-    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_calib");
+    if (e == hipSuccess) rcw = blk.waited(wait_stream(c, c->stream, "k_calib"));
     if (e == hipSuccess && rcw == 0) e = hipMemcpy(result, d + o_res, sizeof(rmcv_calib_result), hipMemcpyDeviceToHost);
     if (e == hipSuccess && rcw == 0) e = hipMemcpy(views_out, d + o_views, b_views, hipMemcpyDeviceToHost);
-    if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernels may still be using it)
     if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_calibrate_camera", e);
     return rcw;
 }

@@ -1,10 +1,11 @@
-// rmcv_ctx.h -- the context behind the ABI's handle and what the three units that implement its entry points share: rmcv_host.hip
-// (context, binding, run, batch setters and getters), rmcv_stagewise.hip (the helpers that run on the caller's own data) and
-// rmcv_frame.hip (the per-frame chain); rmcv_svm.hip (the classifier's trainer) and rmcv_harvest.hip (the dataset's entry points) take
-// the error and wait helpers.  Private to those:
-// every other unit goes through the ctx_* functions of rmcv_internal.h.
+// rmcv_ctx.h -- the context behind the ABI's handle and what the units that implement its entry points share: rmcv_host.hip (context,
+// binding, run, batch setters and getters), rmcv_views.hip and rmcv_capture.hip (the views and the calibration capture: chosen frames of the
+// batch bound, and their stage-wise twins), rmcv_stagewise.hip (the other helpers that run on the caller's own data), rmcv_calib.hip (the solve)
+// and rmcv_frame.hip (the per-frame chain); rmcv_svm.hip (the classifier's trainer) and rmcv_harvest.hip (the dataset's entry points) take
+// the error and wait helpers.  Private to those: every other unit goes through the ctx_* functions of rmcv_internal.h.
 #pragma once
 #include <stdio.h>
+#include <string.h>
 #include <time.h>
 
 #include <vector>
@@ -121,15 +122,17 @@ struct rmcv_ctx {
     // the debug view: allocated on first use (ctx_view_prepare), never by a run
     uint64_t* view_overlay = nullptr; // [view_cap][2] colour planes, each as large as a plane of the largest frame
     int view_cap = 0;                 // views the overlay holds
-    int32_t* view_frames = nullptr;   // [max_frames] the frame list of the views enqueued last
     uint8_t* view_out = nullptr;      // [3 * max_width * max_height] one view on its way to the host (rmcv_batch_get_debug_view)
+    // [max_frames] the chosen frames of the view, label, strip, sheet, corner or chessboard call enqueued last (below:
+    // frame_list_begin; allocated on first use).  One table serves them all: it is written behind order_begin, and order_begin /
+    // order_end put all work of a context in one order whatever stream it comes on, so no call's copy lands before the kernels of the
+    // call before have read theirs.  Under external_order nothing orders these calls, which a table per family did not mend either.
+    int32_t* frame_list = nullptr;
     // corner refinement: allocated on first use, never by a run
     float* corner_mask = nullptr;     // [CORNER_MASK_MAX] the mask of the call enqueued last, behind its host copy
     float corner_mask_host[rmcv::CORNER_MASK_MAX] = {0};
-    int32_t* corner_frames = nullptr; // [max_frames] the frame list of the call enqueued last
     int32_t* corner_tab = nullptr;    // [3 * RMCV_CORNER_PER_FRAME_MAX] one frame's corners and status words on their way (rmcv_batch_get_refined_corners)
     // the chessboard detector: allocated on first use, never by a run
-    int32_t* chess_frames = nullptr;  // [max_frames] the frame list of the call enqueued last
     uint32_t* chess_lists = nullptr;  // [max_frames][1 + CHESS_LIST_WORDS] the candidates between its two kernels
     int32_t* chess_tab = nullptr;     // one frame's corners, count, status and candidates on their way (rmcv_batch_get_chessboard)
     // the calibration solve: allocated on first use, never by a run
@@ -155,6 +158,14 @@ static int fail(rmcv_ctx* c, int code, const char* what, hipError_t e = hipSucce
 // a refusal of the plan headers (a message, or a code with it; none: RMCV_OK) as an entry point returns it
 static int refuse(rmcv_ctx* c, const char* why) { return why ? fail(c, RMCV_ERR_BAD_ARG, why) : RMCV_OK; }
 static int refuse(rmcv_ctx* c, const rmcv::Refusal& r) { return r ? fail(c, r.code, r.why) : RMCV_OK; }
+// ... behind the name of an entry point whose plan header words its refusals without one
+static int refuse_as(rmcv_ctx* c, const char* entry, const char* why)
+{
+    if (!why) return RMCV_OK;
+    char msg[160];
+    snprintf(msg, sizeof(msg), "%s: %s", entry, why);
+    return fail(c, RMCV_ERR_BAD_ARG, msg);
+}
 
 #define HIPCHK(c, call, what)                                        \
     do {                                                                \
@@ -202,6 +213,48 @@ static int wait_event(rmcv_ctx* c, hipEvent_t ev, const char* what)
 // how an entry point that reads results, or rewrites what a batch in flight may read, begins: on the context's device, with all its work finished
 static int ctx_ready(rmcv_ctx* c) { hipSetDevice(c->device); return rmcv_batch_sync(c); }
 
+// Work of one context is ordered, whatever streams the caller hands in: every launch shares the context's buffers (and
+// k_binary's strip queue).  An event is recorded behind the work enqueued last; a call on ANOTHER stream first waits for it,
+// so two streams on one context interleave correctly instead of racing (a context still has ONE owner thread).
+static int order_begin(rmcv_ctx* c, hipStream_t s)
+{
+    if (c->external_order) return RMCV_OK;
+    if (c->order_pending && c->last_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_order, 0), "order: wait for the previous stream");
+    return RMCV_OK;
+}
+static int order_end(rmcv_ctx* c, hipStream_t s)
+{
+    c->last_stream = s;
+    if (c->external_order) return RMCV_OK;
+    HIPCHK(c, hipEventRecord(c->ev_order, s), "order: record");
+    c->order_pending = true;
+    return RMCV_OK;
+}
+
+// The device block of ONE call that keeps nothing of its own in the context (a stage-wise helper's image, lists and result; a getter's
+// staging).  It is freed when the call returns -- unless a wait of the call ran out: the kernels enqueued may still be using it, and it is
+// leaked, as rmcv_ctx_destroy leaks a context whose work does not finish.  Every wait behind a launch on the block goes through waited().
+// (In an unnamed namespace, as the functions here are static: the library exports nothing of it.)
+namespace {
+struct Scratch {
+    uint8_t* d = nullptr;
+    bool in_flight = false;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch()
+    {
+        if (d && !in_flight) hipFree(d);
+    }
+    hipError_t alloc(size_t bytes) { return hipMalloc((void**)&d, bytes); }
+    int waited(int rc)
+    {
+        in_flight = rc == RMCV_ERR_TIMEOUT;
+        return rc;
+    }
+};
+} // namespace
+
 // Every device buffer of a context lies between two GUARD-byte zones filled with a fixed pattern when the context is created;
 // rmcv_ctx_check_guards reads them back.  A kernel that stores one row, word or record past either end of its buffer -- the
 // partial last strip of a 1200-row frame, the ragged last block of a 1920-pixel row -- shows up there instead of in a neighbour.
@@ -229,6 +282,51 @@ static hipError_t dalloc_named(rmcv_ctx* c, T** p, size_t count, const char* nam
     return e;
 }
 #define dalloc(c, p, count) dalloc_named((c), (p), (count), #p)
+
+// ---- what the entry points on chosen frames of a batch and their stage-wise twins share (rmcv_views.hip, rmcv_capture.hip) ----
+static int hip_failed(rmcv_ctx* c, const char* what, hipError_t e) { return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, what, e); }
+static hipStream_t stream_of(rmcv_ctx* c, void* hip_stream) { return hip_stream ? (hipStream_t)hip_stream : c->stream; }
+// a table of the context's, allocated when the first call needs it; `what` words the failure
+template <typename T>
+static int lazy_table(rmcv_ctx* c, T** p, size_t count, const char* name, const char* what)
+{
+    if (*p) return RMCV_OK;
+    const hipError_t e = dalloc_named(c, p, count, name);
+    return e == hipSuccess ? RMCV_OK : hip_failed(c, what, e);
+}
+#define LAZY_TABLE(c, p, count, what) lazy_table((c), (p), (count), #p, (what))
+// How every batch form begins to enqueue: the call takes its place in the context's order and its chosen frames (host values, checked) go
+// to rmcv_ctx::frame_list behind the work enqueued before.  The caller launches on `s` and ends with order_end.
+static int frame_list_begin(rmcv_ctx* c, const int32_t* frames, int n, hipStream_t s, const char* what)
+{
+    int rc = LAZY_TABLE(c, &c->frame_list, (size_t)c->lim.max_frames, "allocating the chosen frames' list");
+    if (rc || (rc = order_begin(c, s))) return rc;
+    HIPCHK(c, hipMemcpyAsync(c->frame_list, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), what);
+    return RMCV_OK;
+}
+// The host block of a stage-wise helper: the caller's BGR image first, as rows of 3 w bytes rounded up to 16, the parts behind it 16-byte aligned
+static size_t up16(size_t v) { return (v + 15) & ~(size_t)15; }
+static int bgr_row_bytes(int w) { return (3 * w + 15) & ~15; }
+static void pack_bgr(uint8_t* dst, const uint8_t* bgr, int w, int h, int stride)
+{
+    for (int y = 0; y < h; y++) memcpy(dst + (size_t)y * bgr_row_bytes(w), bgr + (size_t)y * stride, (size_t)3 * w);
+}
+// How such a helper runs, behind its checks and ctx_ready: a Scratch block of `total` bytes, its first `in_bytes` uploaded from `host`,
+// launch(d) on the context's stream (`what` names it for a later timeout), the wait under `kernel`, then download(d); `who` words a failure
+template <typename Launch, typename Download>
+static int scratch_call(rmcv_ctx* c, size_t total, const void* host, size_t in_bytes, Launch launch, const char* what, const char* kernel, const char* who,
+                        Download download)
+{
+    Scratch d;
+    hipError_t e = d.alloc(total);
+    if (e == hipSuccess) e = hipMemcpyAsync(d.d, host, in_bytes, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch(d.d);
+    c->last_what = what;
+    int rcw = 0;
+    if (e == hipSuccess) rcw = d.waited(wait_stream(c, c->stream, kernel));
+    if (e == hipSuccess && rcw == 0) e = download(d.d);
+    return e != hipSuccess ? hip_failed(c, who, e) : rcw;
+}
 
 // ---- what the chain needs of the batch side (rmcv_host.hip) and the batch side of the chain (rmcv_frame.hip) ----
 namespace rmcv {
@@ -262,6 +360,12 @@ inline Geom one_frame_geom(const rmcv_ctx* c)
     g1.n_frames = 1;
     g1.keys = 0;
     return g1;
+}
+// the batch bound to `c` as step_refusal (tracker_plan.h) reads it
+inline StepBatch step_batch(const rmcv_ctx* c)
+{
+    const Geom& g = c->geom;
+    return {c->device, g.n_frames, c->bufs.frames != nullptr, g.frame_w, g.frame_h, g.win, g.w, g.h};
 }
 // checks and records a binding (bind_plan.h) and enqueues what a change of extent costs; win_w > 0: the frames are read through
 // win_w x win_h windows.  The per-frame modes of the binding before are the caller's to reset (reset_modes).

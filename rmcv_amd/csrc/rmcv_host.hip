@@ -1,6 +1,7 @@
 // rmcv_host.hip -- the C-ABI of include/rmcv_abi.h: the context and its HBM buffers, binding a batch, the run, sync, and the batch
-// setters and getters; the tracker and attitude steps and the debug views of a batch.  What a binding and a run decide is bind_plan.h's
-// (pure, checked by a host compiler); the stage-wise helpers are rmcv_stagewise.hip, the context-free entry points rmcv_rules.hip.
+// setters and getters; the tracker, attitude and harvest steps of a batch.  What a binding and a run decide is bind_plan.h's (pure, checked
+// by a host compiler); the views and the calibration capture of a batch are rmcv_views.hip and rmcv_capture.hip, the stage-wise helpers
+// rmcv_stagewise.hip, the context-free entry points rmcv_rules.hip.
 //
 // Host side of the drop-in boundary.  The reference's boundary is the C++ linkage of `librmcv`
 // (/root/reference/CMakeLists.txt:13-16); the calls a maintainer re-hosts on this ABI are exactly
@@ -15,7 +16,6 @@
 #include <vector>
 
 #include "rmcv_ctx.h"
-#include "device_corner.h"
 #include "device_pack.h"
 
 using namespace rmcv;
@@ -494,24 +494,6 @@ static int gather_rows(rmcv_ctx* c, const T* d_table, const std::vector<int32_t>
     std::vector<T> all(cnt.size() * row_cap);
     HIPCHK(c, hipMemcpy(all.data(), d_table, all.size() * sizeof(T), hipMemcpyDeviceToHost), what);
     for (size_t f = 0; f < cnt.size(); f++) out = std::copy_n(all.data() + f * row_cap, cnt[f], out);
-    return RMCV_OK;
-}
-
-// Work of one context is ordered, whatever streams the caller hands in: every launch shares the context's buffers (and
-// k_binary's strip queue).  An event is recorded behind the work enqueued last; a call on ANOTHER stream first waits for it,
-// so two streams on one context interleave correctly instead of racing (a context still has ONE owner thread).
-static int order_begin(rmcv_ctx* c, hipStream_t s)
-{
-    if (c->external_order) return RMCV_OK;
-    if (c->order_pending && c->last_stream != s) HIPCHK(c, hipStreamWaitEvent(s, c->ev_order, 0), "order: wait for the previous stream");
-    return RMCV_OK;
-}
-static int order_end(rmcv_ctx* c, hipStream_t s)
-{
-    c->last_stream = s;
-    if (c->external_order) return RMCV_OK;
-    HIPCHK(c, hipEventRecord(c->ev_order, s), "order: record");
-    c->order_pending = true;
     return RMCV_OK;
 }
 
@@ -1259,13 +1241,6 @@ int rmcv_batch_track(rmcv_ctx* c, rmcv_tracker* trk, int64_t timestamp, void* hi
 } // extern "C"
 
 namespace rmcv {
-// the batch bound to `c` as step_refusal (tracker_plan.h) reads it
-static StepBatch step_batch(const rmcv_ctx* c)
-{
-    const Geom& g = c->geom;
-    return {c->device, g.n_frames, c->bufs.frames != nullptr, g.frame_w, g.frame_h, g.win, g.w, g.h};
-}
-
 // the tracker's and the batch context's part of a loop record's launch (the recorder's: recorder_loop_begin)
 static void loop_args_fill(LoopArgs& a, const TrackerView& v, const Geom& g, const Bufs& b, int stages, const void* d_packets, int64_t timestamp)
 {
@@ -1360,551 +1335,3 @@ int ctx_harvest(rmcv_ctx* c, rmcv_dataset* ds, const int32_t* h_labels, const vo
     return order_end(c, s);
 }
 } // namespace rmcv
-
-/* ---- the operator's debug view (k_view.hip) ---- */
-
-namespace rmcv {
-
-int ctx_view_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int flags, int out_stride, int64_t out_pitch)
-{
-    if (!frames || n < 1) return fail(c, RMCV_ERR_BAD_ARG, "debug views: no frames chosen");
-    if (n > n_frames) return fail(c, RMCV_ERR_BAD_ARG, "debug views: more views than the batch has frames");
-    if (flags < 0 || flags > RMCV_VIEW_ALL) return fail(c, RMCV_ERR_BAD_ARG, "debug views: unknown view flags");
-    if (vw < 1 || vh < 1 || vw > c->lim.max_width || vh > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, "debug views: the view size must be 1 .. max_width x 1 .. max_height");
-    if (out_stride < 3 * (int64_t)vw) return fail(c, RMCV_ERR_BAD_ARG, "debug views: out_stride < 3 vw");
-    if (n > 1 && out_pitch < (int64_t)out_stride * (vh - 1) + 3 * (int64_t)vw) return fail(c, RMCV_ERR_BAD_ARG, "debug views: out_pitch < out_stride (vh - 1) + 3 vw");
-    std::vector<char> seen((size_t)n_frames, 0);
-    for (int k = 0; k < n; k++) {
-        if (frames[k] < 0 || frames[k] >= n_frames) return fail(c, RMCV_ERR_BAD_ARG, "debug views: a frame index is outside the batch");
-        if (seen[frames[k]]) return fail(c, RMCV_ERR_BAD_ARG, "debug views: a frame index is repeated");
-        seen[frames[k]] = 1;
-    }
-    const int need = view_stages_needed(flags);
-    if ((stages & need) != need) return fail(c, RMCV_ERR_BAD_ARG, "debug views: the batch's run lacked a stage the view flags need");
-    return RMCV_OK;
-}
-
-int ctx_view_prepare(rmcv_ctx* c, int n)
-{
-    hipError_t e = hipSuccess;
-    if (!c->view_frames) e = dalloc(c, &c->view_frames, (size_t)c->lim.max_frames);
-    if (e == hipSuccess && n > c->view_cap) { // a handful of views, or every frame: at most two allocations in a context's life
-        const int cap = n <= 8 && c->lim.max_frames > 8 ? 8 : c->lim.max_frames;
-        const size_t plane = (size_t)(c->lim.max_height + 2) * ((c->lim.max_width + 63) / 64 + 2);
-        uint64_t* p = nullptr;
-        e = dalloc_named(c, &p, (size_t)cap * 2 * plane, "view_overlay");
-        if (e == hipSuccess) {
-            c->view_overlay = p;
-            c->view_cap = cap;
-        }
-    }
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the debug views' planes", e);
-    return RMCV_OK;
-}
-
-// the job of n views of the batch bound, the frame list already on the device
-static ViewJob view_job(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch)
-{
-    const Geom& g = c->geom;
-    const Bufs& b = c->bufs;
-    ViewJob j{};
-    j.w = g.w; j.h = g.h; j.prow = g.prow; j.plane_pitch = g.plane_pitch;
-    j.bits = b.bits; j.overlay = c->view_overlay; j.frames = d_frames;
-    j.n = n; j.vw = vw; j.vh = vh; j.flags = flags;
-    j.out = (uint8_t*)d_out; j.out_stride = out_stride; j.out_pitch = out_pitch;
-    j.lists = ViewLists{b.blobs, b.n_blobs, b.armours, b.n_armours, b.points, b.cont_start, b.cont_len, b.n_contours, b.neg_idx, b.n_neg, nullptr,
-                        c->lim.max_blobs, c->lim.max_armours, c->lim.max_points, c->lim.max_contours, 0};
-    return j;
-}
-
-int ctx_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
-{
-    HIPCHK(c, launch_view(view_job(c, d_frames, n, vw, vh, flags, d_out, out_stride, out_pitch), s), "k_view_overlay + k_view_resize");
-    return RMCV_OK;
-}
-
-// ---- the source view (k_view_source.hip): the operator's view's entry points over SRC(f); the planes are the same ----
-int ctx_source_view_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int flags, int out_stride, int64_t out_pitch)
-{
-    return refuse(c, source_views_refusal(frames, n, n_frames, stages, view_stages_needed(flags & RMCV_VIEW_ALL), vw, vh, c->lim.max_width, c->lim.max_height, flags,
-                                          out_stride, out_pitch));
-}
-
-int ctx_source_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
-{
-    if (!c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, SOURCE_VIEW_NOTHING_BOUND);
-    HIPCHK(c, launch_source_view(c->geom, c->bufs, view_job(c, d_frames, n, vw, vh, flags, d_out, out_stride, out_pitch), s), "k_view_overlay + k_view_source");
-    return RMCV_OK;
-}
-
-} // namespace rmcv
-
-// rmcv_batch_debug_views behind its checks
-static int view_batch(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
-{
-    int rc = ctx_view_prepare(c, n);
-    if (rc) return rc;
-    if ((rc = order_begin(c, s))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->view_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D view frames");
-    if ((rc = ctx_view_enqueue(c, c->view_frames, n, vw, vh, flags, d_out, out_stride, out_pitch, s))) return rc;
-    return order_end(c, s);
-}
-
-extern "C" {
-
-int rmcv_batch_debug_views(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch,
-                           void* hip_stream)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!d_out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_debug_views: null output");
-    const int rc = ctx_view_check(c, frames, n, c->geom.n_frames, c->last_stages, vw, vh, flags, out_stride, out_pitch);
-    if (rc) return rc;
-    hipSetDevice(c->device);
-    return view_batch(c, frames, n, vw, vh, flags, d_out, out_stride, out_pitch, hip_stream ? (hipStream_t)hip_stream : c->stream);
-}
-
-int rmcv_batch_get_debug_view(rmcv_ctx* c, int frame, int vw, int vh, int flags, uint8_t* out, int out_stride)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_get_debug_view: null output");
-    const int32_t one = frame;
-    int rc = ctx_view_check(c, &one, 1, c->geom.n_frames, c->last_stages, vw, vh, flags, out_stride, 0);
-    if (rc) return rc;
-    if ((rc = ctx_ready(c))) return rc;
-    int32_t st = 0;
-    HIPCHK(c, hipMemcpy(&st, c->bufs.status + frame, 4, hipMemcpyDeviceToHost), "D2H");
-    if (st & (RMCV_FRAME_OVF_CONTOURS | RMCV_FRAME_OVF_POINTS | RMCV_FRAME_OVF_BLOBS | RMCV_FRAME_OVF_ARMOURS))
-        return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_get_debug_view: the frame exceeded a context limit (see its status): its tables are not its lists");
-    if (!c->view_out) {
-        const hipError_t e = dalloc(c, &c->view_out, (size_t)3 * c->lim.max_width * c->lim.max_height);
-        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the debug view's staging", e);
-    }
-    if ((rc = view_batch(c, &one, 1, vw, vh, flags, c->view_out, 3 * vw, (int64_t)3 * vw * vh, c->stream))) return rc;
-    WAITCHK(c, wait_stream(c, c->stream, "k_view_resize"));
-    HIPCHK(c, hipMemcpy2D(out, out_stride, c->view_out, (size_t)3 * vw, (size_t)3 * vw, vh, hipMemcpyDeviceToHost), "D2H view");
-    return RMCV_OK;
-}
-
-} // extern "C"
-
-// rmcv_batch_source_views behind its checks
-static int source_view_batch(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
-{
-    if (!c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, SOURCE_VIEW_NOTHING_BOUND); // (before anything is enqueued)
-    int rc = ctx_view_prepare(c, n);
-    if (rc) return rc;
-    if ((rc = order_begin(c, s))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->view_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D view frames");
-    if ((rc = ctx_source_view_enqueue(c, c->view_frames, n, vw, vh, flags, d_out, out_stride, out_pitch, s))) return rc;
-    return order_end(c, s);
-}
-
-extern "C" {
-
-int rmcv_batch_source_views(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch,
-                            void* hip_stream)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!d_out) return fail(c, RMCV_ERR_BAD_ARG, SOURCE_VIEW_NULL_OUTPUT);
-    const int rc = ctx_source_view_check(c, frames, n, c->geom.n_frames, c->last_stages, vw, vh, flags, out_stride, out_pitch);
-    if (rc) return rc;
-    hipSetDevice(c->device);
-    return source_view_batch(c, frames, n, vw, vh, flags, d_out, out_stride, out_pitch, hip_stream ? (hipStream_t)hip_stream : c->stream);
-}
-
-int rmcv_batch_get_source_view(rmcv_ctx* c, int frame, int vw, int vh, int flags, uint8_t* out, int out_stride)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!out) return fail(c, RMCV_ERR_BAD_ARG, SOURCE_VIEW_NULL_OUTPUT);
-    const int32_t one = frame;
-    int rc = ctx_source_view_check(c, &one, 1, c->geom.n_frames, c->last_stages, vw, vh, flags, out_stride, 0);
-    if (rc) return rc;
-    if ((rc = ctx_ready(c))) return rc;
-    int32_t st = 0;
-    HIPCHK(c, hipMemcpy(&st, c->bufs.status + frame, 4, hipMemcpyDeviceToHost), "D2H");
-    if (st & (RMCV_FRAME_OVF_CONTOURS | RMCV_FRAME_OVF_POINTS | RMCV_FRAME_OVF_BLOBS | RMCV_FRAME_OVF_ARMOURS)) return fail(c, RMCV_ERR_BAD_ARG, SOURCE_VIEW_OVERFLOW);
-    if (!c->view_out) {
-        const hipError_t e = dalloc(c, &c->view_out, (size_t)3 * c->lim.max_width * c->lim.max_height);
-        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the source view's staging", e);
-    }
-    if ((rc = source_view_batch(c, &one, 1, vw, vh, flags, c->view_out, 3 * vw, (int64_t)3 * vw * vh, c->stream))) return rc;
-    WAITCHK(c, wait_stream(c, c->stream, "k_view_source"));
-    HIPCHK(c, hipMemcpy2D(out, out_stride, c->view_out, (size_t)3 * vw, (size_t)3 * vw, vh, hipMemcpyDeviceToHost), "D2H view");
-    return RMCV_OK;
-}
-
-} // extern "C"
-
-/* ---- corner refinement (k_corner.hip): the batch entry points; the host-side ones: k_corner.hip, the stage-wise one:
- * rmcv_stagewise.hip ---- */
-
-// rmcv_batch_refine_corners behind its checks
-static int corner_batch(rmcv_ctx* c, const int32_t* frames, int n, void* d_corners, int per_frame, const void* d_counts, int win_x, int win_y, int zero_x,
-                        int zero_y, int max_iters, double eps, void* d_status, hipStream_t s)
-{
-    hipError_t e = hipSuccess;
-    if (!c->corner_frames) e = dalloc(c, &c->corner_frames, (size_t)c->lim.max_frames);
-    if (e == hipSuccess && !c->corner_mask) e = dalloc(c, &c->corner_mask, (size_t)CORNER_MASK_MAX);
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the corner refinement's tables", e);
-    int rc = order_begin(c, s);
-    if (rc) return rc;
-    const int nel = (2 * win_x + 1) * (2 * win_y + 1);
-    corner_mask(win_x, win_y, zero_x, zero_y, c->corner_mask_host);
-    HIPCHK(c, hipMemcpyAsync(c->corner_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D corner frames");
-    HIPCHK(c, hipMemcpyAsync(c->corner_mask, c->corner_mask_host, (size_t)nel * 4, hipMemcpyHostToDevice, s), "H2D corner mask");
-    CornerJob j{};
-    corner_job_source(c->geom, c->bufs, &j);
-    j.frames = c->corner_frames; j.n = n; j.per_frame = per_frame;
-    j.corners = (float*)d_corners; j.counts = (const int32_t*)d_counts; j.status = (int32_t*)d_status;
-    j.mask = c->corner_mask;
-    j.win_x = win_x; j.win_y = win_y; j.max_iters = max_iters; j.eps = eps;
-    HIPCHK(c, launch_corner(j, s), "k_corner_subpix");
-    return order_end(c, s);
-}
-
-static int corner_check(rmcv_ctx* c, const int32_t* frames, int n, const void* d_corners, int per_frame, int win_x, int win_y, int zero_x, int zero_y,
-                        int max_iters, double eps)
-{
-    if (!c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, CORNER_NOTHING_BOUND);
-    return refuse(c, corners_refusal(frames, n, c->geom.n_frames, source_kind(c->geom), c->last_stages, d_corners, per_frame, win_x, win_y, zero_x, zero_y,
-                                     max_iters, eps));
-}
-
-extern "C" {
-
-int rmcv_batch_refine_corners(rmcv_ctx* c, const int32_t* frames, int n, void* d_corners, int per_frame, const void* d_counts, int win_x, int win_y,
-                              int zero_x, int zero_y, int max_iters, double eps, void* d_status, void* hip_stream)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    const int rc = corner_check(c, frames, n, d_corners, per_frame, win_x, win_y, zero_x, zero_y, max_iters, eps);
-    if (rc) return rc;
-    hipSetDevice(c->device);
-    return corner_batch(c, frames, n, d_corners, per_frame, d_counts, win_x, win_y, zero_x, zero_y, max_iters, eps, d_status,
-                        hip_stream ? (hipStream_t)hip_stream : c->stream);
-}
-
-int rmcv_batch_get_refined_corners(rmcv_ctx* c, int frame, float* corners, int n, int win_x, int win_y, int zero_x, int zero_y, int max_iters, double eps,
-                                   int32_t* status_out)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!corners) return fail(c, RMCV_ERR_BAD_ARG, CORNER_NULL_TABLE);
-    const int32_t one = frame;
-    int rc = corner_check(c, &one, 1, corners, n, win_x, win_y, zero_x, zero_y, max_iters, eps);
-    if (rc) return rc;
-    if ((rc = ctx_ready(c))) return rc;
-    if (!c->corner_tab) {
-        const hipError_t e = dalloc(c, &c->corner_tab, (size_t)3 * RMCV_CORNER_PER_FRAME_MAX);
-        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the corner refinement's staging", e);
-    }
-    int32_t* d_status = c->corner_tab + 2 * RMCV_CORNER_PER_FRAME_MAX;
-    HIPCHK(c, hipMemcpy(c->corner_tab, corners, (size_t)n * 8, hipMemcpyHostToDevice), "H2D corners");
-    if ((rc = corner_batch(c, &one, 1, c->corner_tab, n, nullptr, win_x, win_y, zero_x, zero_y, max_iters, eps, d_status, c->stream))) return rc;
-    WAITCHK(c, wait_stream(c, c->stream, "k_corner_subpix"));
-    HIPCHK(c, hipMemcpy(corners, c->corner_tab, (size_t)n * 8, hipMemcpyDeviceToHost), "D2H corners");
-    if (status_out) HIPCHK(c, hipMemcpy(status_out, d_status, (size_t)n * 4, hipMemcpyDeviceToHost), "D2H corner status");
-    return RMCV_OK;
-}
-
-} // extern "C"
-
-/* ---- the chessboard detector (k_chess.hip): the batch entry points; the host-side ones: k_chess.hip, the stage-wise one:
- * rmcv_stagewise.hip ---- */
-
-// rmcv_batch_find_chessboards behind its checks
-static int chess_batch(rmcv_ctx* c, const int32_t* frames, int n, int cols, int rows, const rmcv_chess_params& prm, void* d_corners, int per_frame, void* d_counts,
-                       void* d_status, void* d_cand, void* d_cand_n, hipStream_t s)
-{
-    hipError_t e = hipSuccess;
-    if (!c->chess_frames) e = dalloc(c, &c->chess_frames, (size_t)c->lim.max_frames);
-    if (e == hipSuccess && !c->chess_lists) e = dalloc(c, &c->chess_lists, (size_t)c->lim.max_frames * (1 + CHESS_LIST_WORDS));
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the chessboard detector's tables", e);
-    int rc = order_begin(c, s);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->chess_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D chessboard frames");
-    ChessJob j{};
-    corner_job_source(c->geom, c->bufs, &j.src);
-    j.src.frames = c->chess_frames; j.src.n = n;
-    j.cols = cols; j.rows = rows; j.prm = prm;
-    j.lists = c->chess_lists;
-    j.corners = (float*)d_corners; j.per_frame = per_frame; j.counts = (int32_t*)d_counts; j.status = (int32_t*)d_status;
-    j.cand = (int32_t*)d_cand; j.cand_n = (int32_t*)d_cand_n;
-    HIPCHK(c, launch_chess(j, s), "k_chess");
-    return order_end(c, s);
-}
-
-static int chess_check(rmcv_ctx* c, const int32_t* frames, int n, const void* d_corners, const void* d_counts, int per_frame, int cols, int rows,
-                       const rmcv_chess_params& prm)
-{
-    if (!c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, CHESS_NOTHING_BOUND);
-    return refuse(c, chessboards_refusal(frames, n, c->geom.n_frames, source_kind(c->geom), c->last_stages, d_corners, d_counts, per_frame, cols, rows, prm));
-}
-
-extern "C" {
-
-int rmcv_batch_find_chessboards(rmcv_ctx* c, const int32_t* frames, int n, int cols, int rows, const rmcv_chess_params* params, void* d_corners, int per_frame,
-                                void* d_counts, void* d_status, void* hip_stream)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    const rmcv_chess_params prm = params ? *params : chess_default_params();
-    const int rc = chess_check(c, frames, n, d_corners, d_counts, per_frame, cols, rows, prm);
-    if (rc) return rc;
-    hipSetDevice(c->device);
-    return chess_batch(c, frames, n, cols, rows, prm, d_corners, per_frame, d_counts, d_status, nullptr, nullptr, hip_stream ? (hipStream_t)hip_stream : c->stream);
-}
-
-int rmcv_batch_get_chessboard(rmcv_ctx* c, int frame, int cols, int rows, const rmcv_chess_params* params, float* corners_out, int32_t* status_out,
-                              int32_t* cand_out, int32_t* cand_n_out)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    const rmcv_chess_params prm = params ? *params : chess_default_params();
-    const int32_t one = frame;
-    int rc = chess_check(c, &one, 1, corners_out, corners_out, RMCV_CORNER_PER_FRAME_MAX, cols, rows, prm);
-    if (rc) return rc;
-    if ((rc = ctx_ready(c))) return rc;
-    constexpr int CAP = RMCV_CHESS_CAND_MAX, O_WORDS = 2 * RMCV_CORNER_PER_FRAME_MAX, O_CAND = O_WORDS + 4;   // corners | count, status, candidates, - | (x, y, R)
-    if (!c->chess_tab) {
-        const hipError_t e = dalloc(c, &c->chess_tab, (size_t)O_CAND + 3 * CAP);
-        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the chessboard detector's staging", e);
-    }
-    int32_t* t = c->chess_tab;
-    if ((rc = chess_batch(c, &one, 1, cols, rows, prm, t, RMCV_CORNER_PER_FRAME_MAX, t + O_WORDS, t + O_WORDS + 1, t + O_CAND, t + O_WORDS + 2, c->stream))) return rc;
-    WAITCHK(c, wait_stream(c, c->stream, "k_chess"));
-    int32_t words[3];
-    HIPCHK(c, hipMemcpy(words, t + O_WORDS, sizeof(words), hipMemcpyDeviceToHost), "D2H chessboard words");
-    if (words[0] > 0) HIPCHK(c, hipMemcpy(corners_out, t, (size_t)words[0] * 8, hipMemcpyDeviceToHost), "D2H chessboard corners");
-    if (cand_out && words[2] > 0) HIPCHK(c, hipMemcpy(cand_out, t + O_CAND, (size_t)words[2] * 12, hipMemcpyDeviceToHost), "D2H chessboard candidates");
-    if (status_out) *status_out = words[1];
-    if (cand_n_out) *cand_n_out = words[2];
-    return RMCV_OK;
-}
-
-} // extern "C"
-
-/* ---- the icon strip and the labeler's sheet (k_icon_strip.hip): the batch entry points; the host-side ones: k_icon_strip.hip,
- * the stage-wise one: rmcv_stagewise.hip ---- */
-
-// rmcv_batch_icon_strips behind its checks
-static int icon_strip_batch(rmcv_ctx* c, const int32_t* frames, int n, int side, int cap, void* d_out, int out_stride, int64_t out_pitch, int32_t* d_counts,
-                            hipStream_t s)
-{
-    hipError_t e = hipSuccess;
-    if (!c->view_frames) e = dalloc(c, &c->view_frames, (size_t)c->lim.max_frames);
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the icon strips' frame list", e);
-    int rc = order_begin(c, s);
-    if (rc) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->view_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D view frames");
-    HIPCHK(c, launch_icon_strip(c->geom, c->bufs, c->lim, c->view_frames, n, side, cap, cap * side, (uint8_t*)d_out, out_stride, out_pitch, d_counts, s), "k_icon_strip");
-    return order_end(c, s);
-}
-
-static int icon_strip_check(rmcv_ctx* c, const int32_t* frames, int n, int side, int cap, int out_stride, int64_t out_pitch)
-{
-    if (!c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, ICON_STRIP_NOTHING_BOUND);
-    return refuse(c, icon_strips_refusal(frames, n, c->geom.n_frames, c->last_stages, side, cap, c->lim.max_armours, out_stride, out_pitch));
-}
-
-namespace rmcv {
-
-int ctx_sheet_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int side, int flags, int out_stride, int64_t out_pitch)
-{
-    const int need = view_stages_needed(flags & RMCV_VIEW_ALL) | view_stages_needed(0) | RMCV_STAGE_ARMOURS;
-    return refuse(c, sheets_refusal(frames, n, n_frames, stages, need, vw, vh, side, c->lim.max_width, c->lim.max_height, flags, out_stride, out_pitch));
-}
-
-// left pane, right pane, strip: the two view launches aimed at their sub-rectangles of the sheet, then k_icon_strip over its last rows
-int ctx_sheet_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int side, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
-{
-    uint8_t* sheet = (uint8_t*)d_out;
-    int rc = ctx_source_view_enqueue(c, d_frames, n, vw, vh, flags, sheet, out_stride, out_pitch, s);
-    if (rc) return rc;
-    if ((rc = ctx_view_enqueue(c, d_frames, n, vw, vh, 0, sheet + 3 * (size_t)vw, out_stride, out_pitch, s))) return rc;
-    HIPCHK(c, launch_icon_strip(c->geom, c->bufs, c->lim, d_frames, n, side, sheet_cap(vw, side, c->lim.max_armours), 2 * vw, sheet + (size_t)vh * out_stride,
-                                out_stride, out_pitch, nullptr, s),
-           "k_icon_strip");
-    return RMCV_OK;
-}
-
-} // namespace rmcv
-
-// rmcv_batch_labeler_sheets behind its checks
-static int sheet_batch(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int side, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
-{
-    if (!c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, SOURCE_VIEW_NOTHING_BOUND); // (before anything is enqueued)
-    int rc = ctx_view_prepare(c, n);
-    if (rc) return rc;
-    if ((rc = order_begin(c, s))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->view_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D view frames");
-    if ((rc = ctx_sheet_enqueue(c, c->view_frames, n, vw, vh, side, flags, d_out, out_stride, out_pitch, s))) return rc;
-    return order_end(c, s);
-}
-
-extern "C" {
-
-int rmcv_batch_icon_strips(rmcv_ctx* c, const int32_t* frames, int n, int side, int cap, void* d_out, int out_stride, int64_t out_pitch, int32_t* d_counts,
-                           void* hip_stream)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!d_out) return fail(c, RMCV_ERR_BAD_ARG, ICON_STRIP_NULL_OUTPUT);
-    const int rc = icon_strip_check(c, frames, n, side, cap, out_stride, out_pitch);
-    if (rc) return rc;
-    hipSetDevice(c->device);
-    return icon_strip_batch(c, frames, n, side, cap, d_out, out_stride, out_pitch, d_counts, hip_stream ? (hipStream_t)hip_stream : c->stream);
-}
-
-int rmcv_batch_get_icon_strip(rmcv_ctx* c, int frame, int side, int cap, uint8_t* out, int out_stride, int32_t* n_icons)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!out) return fail(c, RMCV_ERR_BAD_ARG, ICON_STRIP_NULL_OUTPUT);
-    const int32_t one = frame;
-    int rc = icon_strip_check(c, &one, 1, side, cap, out_stride, 0);
-    if (rc) return rc;
-    if ((rc = ctx_ready(c))) return rc;
-    int32_t st = 0;
-    HIPCHK(c, hipMemcpy(&st, c->bufs.status + frame, 4, hipMemcpyDeviceToHost), "D2H");
-    if (st & (RMCV_FRAME_OVF_CONTOURS | RMCV_FRAME_OVF_POINTS | RMCV_FRAME_OVF_BLOBS | RMCV_FRAME_OVF_ARMOURS)) return fail(c, RMCV_ERR_BAD_ARG, ICON_STRIP_OVERFLOW);
-    // (a getter: staging of its own for this one call, 16 bytes in front for the count)
-    const size_t row = (size_t)3 * cap * side;
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, 16 + row * side);
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the icon strip's staging", e);
-    rc = icon_strip_batch(c, &one, 1, side, cap, d + 16, (int)row, (int64_t)row * side, reinterpret_cast<int32_t*>(d), c->stream);
-    if (!rc) rc = wait_stream(c, c->stream, "k_icon_strip");
-    int32_t na = 0;
-    if (!rc) e = hipMemcpy2D(out, out_stride, d + 16, row, row, side, hipMemcpyDeviceToHost);
-    if (!rc && e == hipSuccess) e = hipMemcpy(&na, d, 4, hipMemcpyDeviceToHost);
-    if (rc != RMCV_ERR_TIMEOUT) hipFree(d); // (after a wait that ran out the kernel may still be using it)
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(c, RMCV_ERR_HIP, "D2H icon strip", e);
-    if (n_icons) *n_icons = na;
-    return RMCV_OK;
-}
-
-int rmcv_batch_labeler_sheets(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int side, int flags, void* d_out, int out_stride, int64_t out_pitch,
-                              void* hip_stream)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!d_out) return fail(c, RMCV_ERR_BAD_ARG, SHEET_NULL_OUTPUT);
-    const int rc = ctx_sheet_check(c, frames, n, c->geom.n_frames, c->last_stages, vw, vh, side, flags, out_stride, out_pitch);
-    if (rc) return rc;
-    hipSetDevice(c->device);
-    return sheet_batch(c, frames, n, vw, vh, side, flags, d_out, out_stride, out_pitch, hip_stream ? (hipStream_t)hip_stream : c->stream);
-}
-
-int rmcv_batch_get_labeler_sheet(rmcv_ctx* c, int frame, int vw, int vh, int side, int flags, uint8_t* out, int out_stride)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!out) return fail(c, RMCV_ERR_BAD_ARG, SHEET_NULL_OUTPUT);
-    const int32_t one = frame;
-    int rc = ctx_sheet_check(c, &one, 1, c->geom.n_frames, c->last_stages, vw, vh, side, flags, out_stride, 0);
-    if (rc) return rc;
-    if ((rc = ctx_ready(c))) return rc;
-    int32_t st = 0;
-    HIPCHK(c, hipMemcpy(&st, c->bufs.status + frame, 4, hipMemcpyDeviceToHost), "D2H");
-    if (st & (RMCV_FRAME_OVF_CONTOURS | RMCV_FRAME_OVF_POINTS | RMCV_FRAME_OVF_BLOBS | RMCV_FRAME_OVF_ARMOURS)) return fail(c, RMCV_ERR_BAD_ARG, SHEET_OVERFLOW);
-    const size_t row = (size_t)6 * vw, rows = (size_t)vh + side;
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, row * rows);
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the sheet's staging", e);
-    rc = sheet_batch(c, &one, 1, vw, vh, side, flags, d, (int)row, (int64_t)(row * rows), c->stream);
-    if (!rc) rc = wait_stream(c, c->stream, "k_icon_strip");
-    if (!rc) e = hipMemcpy2D(out, out_stride, d, row, row, rows, hipMemcpyDeviceToHost);
-    if (rc != RMCV_ERR_TIMEOUT) hipFree(d);
-    if (rc) return rc;
-    if (e != hipSuccess) return fail(c, RMCV_ERR_HIP, "D2H sheet", e);
-    return RMCV_OK;
-}
-
-} // extern "C"
-
-/* ---- view labels (k_view_text.hip): the batch entry points; the host-side ones and the stage-wise one: rmcv_labels.hip ---- */
-
-namespace rmcv {
-
-int ctx_label_check(rmcv_ctx* c, const char* who, rmcv_tracker* trk, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int scale,
-                    int out_stride, int64_t out_pitch)
-{
-    char msg[200];
-    // (the views are finished ones: what their renderer refused of the list and the layout is refused here, whatever stages it needed)
-    if (const int rc = ctx_view_check(c, frames, n, n_frames, ~0, vw, vh, 0, out_stride, out_pitch)) return rc;
-    if (scale < 1 || scale > 8) {
-        snprintf(msg, sizeof(msg), "%s: scale %d is outside 1 .. 8", who, scale);
-        return fail(c, RMCV_ERR_BAD_ARG, msg);
-    }
-    if (trk) {
-        if (const char* no = step_refusal(who, true, tracker_view(trk), step_batch(c), stages, msg)) return fail(c, RMCV_ERR_BAD_ARG, no);
-    } else if (!(stages & RMCV_STAGE_ARMOURS)) {
-        snprintf(msg, sizeof(msg), "%s: the last run had no RMCV_STAGE_ARMOURS: nothing to label", who);
-        return fail(c, RMCV_ERR_BAD_ARG, msg);
-    }
-    return RMCV_OK;
-}
-
-int ctx_label_enqueue(rmcv_ctx* c, rmcv_tracker* trk, int what, int stages, const int32_t* d_frames, int n, int vw, int vh, int scale, void* d_views,
-                      int out_stride, int64_t out_pitch, hipStream_t s)
-{
-    const Geom& g = c->geom;
-    const Bufs& b = c->bufs;
-    LabelJob j{};
-    j.n = n, j.vw = vw, j.vh = vh, j.w = g.w, j.h = g.h, j.scale = scale, j.n_frames = g.n_frames;
-    j.out = static_cast<uint8_t*>(d_views), j.out_stride = out_stride, j.out_pitch = out_pitch, j.frames = d_frames;
-    if (what & RMCV_LABEL_ARMOURS) { // identity and position as the tracker's observations take them: from the run's stages, else -1 and zeros
-        j.armours = b.armours, j.n_armours = b.n_armours, j.max_armours = c->lim.max_armours;
-        j.identity = (stages & RMCV_STAGE_IDENTITY) ? b.identity : nullptr;
-        j.positions = (stages & RMCV_STAGE_POSE) && b.poses ? b.poses + 6 : nullptr;
-        j.pos_stride = 9;
-    }
-    const bool tracks = (what & RMCV_LABEL_TRACKS) && trk;
-    if (tracks) {
-        const TrackerView& v = tracker_view(trk);
-        j.tracks = v.b.tracks, j.side = v.b.side, j.sel = v.b.sel, j.n_tracking = v.b.n_tracking;
-        j.n_streams = v.cfg.n_streams, j.track_cap = v.cfg.track_cap;
-        j.win_eff = g.win ? b.win_eff : nullptr;
-        HIPCHK(c, tracker_order_begin(trk, s), "view labels: wait for the tracker's step");
-    }
-    HIPCHK(c, launch_view_text(j, s), "k_view_text");
-    if (tracks) HIPCHK(c, tracker_order_end(trk, s), "view labels: record the read of the tracker's lists");
-    return RMCV_OK;
-}
-
-} // namespace rmcv
-
-// rmcv_batch_view_labels / rmcv_batch_view_tracks behind their checks.  The frame list travels through the views' own table
-// (rmcv_ctx::view_frames: allocated once in a context's life, by whichever view or label call comes first)
-static int label_batch(rmcv_ctx* c, rmcv_tracker* trk, const int32_t* frames, int n, int vw, int vh, int scale, void* d_views, int stride, int64_t pitch, hipStream_t s)
-{
-    int rc = RMCV_OK;
-    if (!c->view_frames) {
-        const hipError_t e = dalloc(c, &c->view_frames, (size_t)c->lim.max_frames);
-        if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "allocating the views' frame list", e);
-    }
-    if ((rc = order_begin(c, s))) return rc;
-    HIPCHK(c, hipMemcpyAsync(c->view_frames, frames, (size_t)n * 4, hipMemcpyHostToDevice, s), "H2D view frames");
-    if ((rc = ctx_label_enqueue(c, trk, trk ? RMCV_LABEL_TRACKS : RMCV_LABEL_ARMOURS, c->last_stages, c->view_frames, n, vw, vh, scale, d_views, stride, pitch, s))) return rc;
-    return order_end(c, s);
-}
-
-extern "C" {
-
-int rmcv_batch_view_labels(rmcv_ctx* c, const int32_t* frames, int n, int vw, int vh, int scale, void* d_views, int stride, int64_t pitch, void* hip_stream)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!d_views) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_view_labels: null views");
-    const int rc = ctx_label_check(c, "rmcv_batch_view_labels", nullptr, frames, n, c->geom.n_frames, c->last_stages, vw, vh, scale, stride, pitch);
-    if (rc) return rc;
-    hipSetDevice(c->device);
-    return label_batch(c, nullptr, frames, n, vw, vh, scale, d_views, stride, pitch, hip_stream ? (hipStream_t)hip_stream : c->stream);
-}
-
-int rmcv_batch_view_tracks(rmcv_ctx* c, rmcv_tracker* trk, const int32_t* frames, int n, int vw, int vh, int scale, void* d_views, int stride, int64_t pitch,
-                           void* hip_stream)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!trk) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_view_tracks: null tracker");
-    if (!d_views) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_batch_view_tracks: null views");
-    const int rc = ctx_label_check(c, "rmcv_batch_view_tracks", trk, frames, n, c->geom.n_frames, c->last_stages, vw, vh, scale, stride, pitch);
-    if (rc) return rc;
-    hipSetDevice(c->device);
-    return label_batch(c, trk, frames, n, vw, vh, scale, d_views, stride, pitch, hip_stream ? (hipStream_t)hip_stream : c->stream);
-}
-
-} // extern "C"

@@ -290,7 +290,7 @@ inline int view_stages_needed(int flags)
     return RMCV_STAGE_BINARY | ((flags & (RMCV_VIEW_BLOBS | RMCV_VIEW_NEGATIVES)) ? RMCV_STAGE_CONTOURS | RMCV_STAGE_BLOBS : 0) |
            ((flags & RMCV_VIEW_ARMOURS) ? RMCV_STAGE_CONTOURS | RMCV_STAGE_BLOBS | RMCV_STAGE_ARMOURS : 0);
 }
-// (the view entry points of a context: rmcv_host.hip; the stage-wise rmcv_debug_view: rmcv_stagewise.hip)
+// (the view entry points of a context and the stage-wise rmcv_debug_view: rmcv_views.hip)
 // what a pipeline needs of them: everything n views need allocated now (blocking); the check of a request against the context's limits;
 // and the enqueue itself on frames the caller has bound and run, the frame list already on the device, nothing blocking
 int ctx_view_prepare(rmcv_ctx* c, int n);
@@ -315,7 +315,7 @@ struct SourceViewJob {
 hipError_t launch_source_view(const SourceViewJob& j, hipStream_t s);
 // the same for views of the batch bound to (g, b): the kind and the source fields come from them
 hipError_t launch_source_view(const Geom& g, const Bufs& b, const ViewJob& view, hipStream_t s);
-// (the entry points of a context: rmcv_host.hip; the stage-wise rmcv_source_view: rmcv_stagewise.hip).  What a pipeline needs of them, as
+// (the entry points of a context: rmcv_views.hip; the stage-wise rmcv_source_view: rmcv_stagewise.hip).  What a pipeline needs of them, as
 // of the operator's view: the planes come from ctx_view_prepare, the check takes the frames as host values, the enqueue blocks nothing
 int ctx_source_view_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int flags, int out_stride, int64_t out_pitch);
 int ctx_source_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s);
@@ -347,7 +347,7 @@ struct LabelJob {
 // k_view_text on `s`; every argument has been checked by the caller
 hipError_t launch_view_text(const LabelJob& j, hipStream_t s);
 int64_t view_text_launches(); // launches of k_view_text by this process (rmcv_view_text_launches)
-// what the label entry points of a context refuse before anything is enqueued (rmcv_host.hip): the views' list and layout as
+// what the label entry points of a context refuse before anything is enqueued (rmcv_views.hip): the views' list and layout as
 // ctx_view_check, the scale, the stages (RMCV_STAGE_ARMOURS), and for tracks (trk non-null) what a tracker step refuses of the batch
 // (n_frames / stages: the batch the views are of).  who: the entry point, for the message
 int ctx_label_check(rmcv_ctx* c, const char* who, rmcv_tracker* trk, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int scale,
@@ -379,7 +379,7 @@ hipError_t launch_icon_strip(const IconStripJob& j, hipStream_t s);
 // the strips of the batch bound to (g, b), by the kernel of the batch's kind
 hipError_t launch_icon_strip(const Geom& g, const Bufs& b, const Limits& lim, const int32_t* d_frames, int n, int side, int cap, int strip_w, uint8_t* d_out,
                              int out_stride, int64_t out_pitch, int32_t* d_counts, hipStream_t s);
-// the sheet's entry points of a context (rmcv_host.hip) as a pipeline needs them, as of the views: the planes come from ctx_view_prepare, the
+// the sheet's entry points of a context (rmcv_views.hip) as a pipeline needs them, as of the views: the planes come from ctx_view_prepare, the
 // check takes the frames as host values, the enqueue (left pane, right pane, strip) blocks nothing
 int ctx_sheet_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int side, int flags, int out_stride, int64_t out_pitch);
 int ctx_sheet_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int side, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s);

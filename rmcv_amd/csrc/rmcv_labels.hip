@@ -1,7 +1,7 @@
 // rmcv_labels.hip -- view labels behind the ABI: the host-side functions, which need no context and no device -- the two
 // number formats' public face, the lines, the glyphs, and the sequential restatement rmcv_view_labels_host -- and the stage-wise
 // rmcv_view_labels, the kernel on host lists with buffers of its own.  The rule is device_text.h; the batch entry points, which live
-// on a context's bound tables, are rmcv_host.hip's; the pipeline's setter is rmcv_pipeline.hip's.  No kernel lives here.
+// on a context's bound tables, are rmcv_views.hip's; the pipeline's setter is rmcv_pipeline.hip's.  No kernel lives here.
 // With RMCV_LABELS_HOST_ONLY defined only the host-side functions are compiled, by any C++ compiler, with no HIP header in sight: the
 // form tests/labels_san_main.cpp builds under the sanitizers.
 #include <string.h>
@@ -84,7 +84,6 @@ int rmcv_view_labels(rmcv_ctx* c, uint8_t* view, int vw, int vh, int stride, int
     if (const int rc = ctx_ready(c)) return rc;
     // (a stage-wise helper: buffers of its own, so that nothing bound to the context moves) -- one host block, one upload.  The view keeps
     // the caller's stride on the device: the kernel writes into the layout it was given
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
     const size_t view_bytes = (size_t)stride * (vh - 1) + (size_t)3 * vw;
     const size_t o_arm = up16(view_bytes), o_id = o_arm + up16((size_t)n_armours * sizeof(rmcv_armour)), o_pos = o_id + up16((size_t)n_armours * 4);
     const size_t o_trk = o_pos + up16((size_t)n_armours * 24), o_side = o_trk + up16((size_t)n_tracks * sizeof(rmcv_track));
@@ -98,8 +97,9 @@ int rmcv_view_labels(rmcv_ctx* c, uint8_t* view, int vw, int vh, int stride, int
     if (n_tracks) memcpy(&host[o_side], last_vertices, (size_t)n_tracks * 32);
     const int32_t counts[4] = {n_armours, n_tracks, 0, 0};
     memcpy(&host[o_cnt], counts, sizeof(counts));
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, total);
+    Scratch blk;
+    hipError_t e = blk.alloc(total);
+    uint8_t* const d = blk.d;
     if (e == hipSuccess) e = hipMemcpyAsync(d, host.data(), total, hipMemcpyHostToDevice, c->stream);
     if (e == hipSuccess) {
         const int32_t* cnt = reinterpret_cast<const int32_t*>(d + o_cnt);
@@ -121,9 +121,8 @@ int rmcv_view_labels(rmcv_ctx* c, uint8_t* view, int vw, int vh, int stride, int
     }
     c->last_what = "k_view_text";
     int rcw = 0;
-    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_view_text");
+    if (e == hipSuccess) rcw = blk.waited(wait_stream(c, c->stream, "k_view_text"));
     if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(view, stride, d, stride, (size_t)3 * vw, vh, hipMemcpyDeviceToHost);
-    if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernel may still be using it)
     if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_view_labels", e);
     return rcw;
 }

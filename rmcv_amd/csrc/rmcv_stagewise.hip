@@ -1,13 +1,17 @@
 // rmcv_stagewise.hip -- the stage-wise helpers of include/rmcv_abi.h: one stage of the path on the CALLER's own data (an image, a
 // contour, a list of armours), through the same kernels the batch path launches.  They use a context for its device, stream, limits and
-// loaded models; what they bind or allocate is their own, so that nothing the caller has bound to the context moves unless said.
+// loaded models; what they bind or allocate is their own, so that nothing the caller has bound to the context moves unless said.  The
+// stage-wise debug view and icon strip stand with their batch forms in rmcv_views.hip, the corner refinement and the chessboard detector in
+// rmcv_capture.hip, the stage-wise calibration solve in rmcv_calib.hip.  rmcv_source_view stays here, in the text it had before those units
+// existed: its move onto their shared pieces (ViewBlock, pack_bgr, scratch_call) met a GPU fault in
+// tests/test_gpu_source_view.py::test_stagewise_view_equals_the_reference[640x400-40x25] whose cause has not been found, and it goes there
+// only once that cause is known.
 #include <string.h>
 
 #include <cmath>
 
 #include "rmcv_ctx.h"
 #include "device_bayer.h"
-#include "device_corner.h"
 #include "device_view.h"
 
 using namespace rmcv;
@@ -107,20 +111,16 @@ static int demosaic_body(rmcv_ctx* c, const uint8_t* raw, int w, int h, int stri
     const int sb = rmcv::lay_bytes(lay);
     if (const int rc = ctx_ready(c)) return rc;
     // (a stage-wise helper: buffers of its own, so that nothing bound to the context moves)
-    uint8_t *d_raw = nullptr, *d_out = nullptr;
+    Scratch d_raw, d_out;
     const size_t in_bytes = (size_t)sb * w * h, out_bytes = (size_t)3 * w * h;
-    hipError_t e = hipMalloc((void**)&d_raw, in_bytes);
-    if (e == hipSuccess) e = hipMalloc((void**)&d_out, out_bytes);
-    if (e == hipSuccess) e = hipMemcpy2DAsync(d_raw, (size_t)sb * w, raw, stride, (size_t)sb * w, h, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) e = launch_demosaic(d_raw, sb * w, w, h, pattern, lay, d_out, 3 * w, c->stream);
+    hipError_t e = d_raw.alloc(in_bytes);
+    if (e == hipSuccess) e = d_out.alloc(out_bytes);
+    if (e == hipSuccess) e = hipMemcpy2DAsync(d_raw.d, (size_t)sb * w, raw, stride, (size_t)sb * w, h, hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = launch_demosaic(d_raw.d, sb * w, w, h, pattern, lay, d_out.d, 3 * w, c->stream);
     c->last_what = "k_demosaic";
     int rcw = 0;
-    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_demosaic");
-    if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(bgr_out, out_stride, d_out, 3 * w, 3 * w, h, hipMemcpyDeviceToHost);
-    if (rcw == 0 || e != hipSuccess) { // (after a wait that ran out the kernel may still be using them)
-        if (d_raw) hipFree(d_raw);
-        if (d_out) hipFree(d_out);
-    }
+    if (e == hipSuccess) rcw = d_raw.waited(d_out.waited(wait_stream(c, c->stream, "k_demosaic")));
+    if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(bgr_out, out_stride, d_out.d, 3 * w, 3 * w, h, hipMemcpyDeviceToHost);
     if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_demosaic", e);
     return rcw;
 }
@@ -163,8 +163,9 @@ static int bytemap_body(rmcv_ctx* c, const uint8_t* src, int row_bytes, int rows
     const int dstride = (row_bytes + 15) & ~15;
     const size_t img = (size_t)dstride * rows;
     // [image | sums 3 x 8 | gamma 4 + pad 4 | table 256 | threshold table 512]
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, img + 32 + 256 + 512);
+    Scratch blk;
+    hipError_t e = blk.alloc(img + 32 + 256 + 512);
+    uint8_t* const d = blk.d;
     hipStream_t s = c->stream;
     if (e == hipSuccess && dstride != row_bytes) e = hipMemsetAsync(d, 0, img, s); // (the pad bytes go through the table too: keep them defined)
     if (e == hipSuccess) e = hipMemcpy2DAsync(d, dstride, src, src_stride, (size_t)row_bytes, rows, hipMemcpyHostToDevice, s);
@@ -186,10 +187,9 @@ static int bytemap_body(rmcv_ctx* c, const uint8_t* src, int row_bytes, int rows
     if (e == hipSuccess) e = launch_bytemap(d, d, (int64_t)(img / 16), d_lut, c->geom.n_cu, s);
     c->last_what = auto_w > 0 ? "k_frame_sums, k_enhance_table, k_bytemap" : "k_gamma_lut, k_bytemap";
     int rcw = 0;
-    if (e == hipSuccess) rcw = wait_stream(c, s, who);
+    if (e == hipSuccess) rcw = blk.waited(wait_stream(c, s, who));
     if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(dst, dst_stride, d, dstride, (size_t)row_bytes, rows, hipMemcpyDeviceToHost);
     if (e == hipSuccess && rcw == 0 && gamma_out && auto_w > 0) e = hipMemcpy(gamma_out, d + img + 24, sizeof(float), hipMemcpyDeviceToHost);
-    if (d && (rcw == 0 || e != hipSuccess)) hipFree(d); // (after a wait that ran out the kernels may still be using it)
     if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, who, e);
     return rcw;
 }
@@ -239,64 +239,6 @@ int rmcv_find_lightblobs(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stri
     if (st & RMCV_FRAME_HULL) return fail(c, RMCV_ERR_BAD_ARG, "minAreaRect: a contour is not a closed border or exceeds the hull tables");
     if (boxes_out && nb) HIPCHK(c, hipMemcpy(boxes_out, c->bufs.ellipses, (size_t)nb * sizeof(rmcv_rrect), hipMemcpyDeviceToHost), "D2H boxes");
     return RMCV_OK;
-}
-
-int rmcv_debug_view(rmcv_ctx* c, const uint8_t* binary, int w, int h, int stride, const rmcv_lightblob* blobs, int n_blobs, const rmcv_point* neg_pts,
-                    const int32_t* neg_offs, int n_neg, const rmcv_armour* armours, int n_armours, int flags, int vw, int vh, uint8_t* out,
-                    int out_stride)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (!binary || !out) return fail(c, RMCV_ERR_BAD_ARG, "rmcv_debug_view: null buffer");
-    const char* bad = view_check_lists(w, h, stride, blobs, n_blobs, neg_pts, neg_offs, n_neg, armours, n_armours, flags, vw, vh, out_stride);
-    if (bad) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "rmcv_debug_view: %s", bad);
-        return fail(c, RMCV_ERR_BAD_ARG, msg);
-    }
-    if (w > c->lim.max_width || h > c->lim.max_height || vw > c->lim.max_width || vh > c->lim.max_height)
-        return fail(c, RMCV_ERR_BAD_ARG, "rmcv_debug_view: image or view beyond the context's max_width / max_height");
-    if (const int rc = ctx_ready(c)) return rc;
-    // (a stage-wise helper: buffers of its own, so that nothing bound to the context moves) -- one host block, one upload
-    const int prow = (w + 63) / 64 + 2, n_pts = n_neg ? neg_offs[n_neg] : 0;
-    const size_t plane = (size_t)(h + 2) * prow;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_blobs = up16(plane * 8), o_arm = o_blobs + up16((size_t)n_blobs * sizeof(rmcv_lightblob));
-    const size_t o_pts = o_arm + up16((size_t)n_armours * sizeof(rmcv_armour)), o_offs = o_pts + up16((size_t)n_pts * sizeof(rmcv_point));
-    const size_t o_cnt = o_offs + up16((size_t)(n_neg + 1) * 4), in_bytes = o_cnt + 16;
-    const size_t o_ov = in_bytes, o_out = o_ov + up16(2 * plane * 8), total = o_out + (size_t)3 * vw * vh;
-    std::vector<uint8_t> host(in_bytes, 0);
-    uint64_t* hp = reinterpret_cast<uint64_t*>(host.data());
-    for (int y = 0; y < h; y++)
-        for (int x = 0; x < w; x++)
-            if (binary[(size_t)y * stride + x]) hp[(size_t)(y + 1) * prow + (x >> 6) + 1] |= 1ull << (x & 63);
-    if (n_blobs) memcpy(&host[o_blobs], blobs, (size_t)n_blobs * sizeof(rmcv_lightblob));
-    if (n_armours) memcpy(&host[o_arm], armours, (size_t)n_armours * sizeof(rmcv_armour));
-    if (n_pts) memcpy(&host[o_pts], neg_pts, (size_t)n_pts * sizeof(rmcv_point));
-    if (n_neg) memcpy(&host[o_offs], neg_offs, (size_t)(n_neg + 1) * 4);
-    const int32_t counts[4] = {n_blobs, n_armours, n_neg, 0};
-    memcpy(&host[o_cnt], counts, sizeof(counts));
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, total);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        const int32_t* cnt = reinterpret_cast<const int32_t*>(d + o_cnt);
-        ViewJob j{};
-        j.w = w; j.h = h; j.prow = prow; j.plane_pitch = (int64_t)plane;
-        j.bits = reinterpret_cast<const uint64_t*>(d); j.overlay = reinterpret_cast<uint64_t*>(d + o_ov); j.frames = nullptr;
-        j.n = 1; j.vw = vw; j.vh = vh; j.flags = flags;
-        j.out = d + o_out; j.out_stride = 3 * vw; j.out_pitch = (int64_t)3 * vw * vh;
-        j.lists = ViewLists{reinterpret_cast<const rmcv_lightblob*>(d + o_blobs), cnt, reinterpret_cast<const rmcv_armour*>(d + o_arm), cnt + 1,
-                            reinterpret_cast<const rmcv_point*>(d + o_pts), nullptr, nullptr, cnt + 3, nullptr, cnt + 2,
-                            reinterpret_cast<const int32_t*>(d + o_offs), n_blobs, n_armours, n_pts, n_neg, 1};
-        e = launch_view(j, c->stream);
-    }
-    c->last_what = "k_view_overlay + k_view_resize";
-    int rcw = 0;
-    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_view_resize");
-    if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(out, out_stride, d + o_out, (size_t)3 * vw, (size_t)3 * vw, vh, hipMemcpyDeviceToHost);
-    if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernels may still be using it)
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_debug_view", e);
-    return rcw;
 }
 
 int rmcv_source_view(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, const rmcv_lightblob* blobs, int n_blobs, const rmcv_point* neg_pts,
@@ -355,147 +297,6 @@ int rmcv_source_view(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, 
     if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(out, out_stride, d + o_out, (size_t)3 * vw, (size_t)3 * vw, vh, hipMemcpyDeviceToHost);
     if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernels may still be using it)
     if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_source_view", e);
-    return rcw;
-}
-
-int rmcv_corner_subpix(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, float* corners, int n, int win_x, int win_y, int zero_x, int zero_y,
-                       int max_iters, double eps, int32_t* status_out)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    const char* bad = rmcv::corner_image_refusal(bgr, corners, w, h, stride, n);
-    if (!bad && (n < 1 || n > RMCV_CORNER_PER_FRAME_MAX)) bad = rmcv::CORNER_PER_FRAME;
-    if (!bad) bad = rmcv::corner_params_refusal(win_x, win_y, zero_x, zero_y, max_iters, eps);
-    if (bad) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "rmcv_corner_subpix: %s", bad);
-        return fail(c, RMCV_ERR_BAD_ARG, msg);
-    }
-    if (w > c->lim.max_width || h > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, rmcv::CORNER_BEYOND_LIMITS);
-    if (const int rc = ctx_ready(c)) return rc;
-    // (a stage-wise helper: buffers of its own) -- one host block, one upload: the image packed to rows of 3 w bytes rounded up to 16, the
-    // corners, the mask; the status words behind them
-    const int dstride = (3 * w + 15) & ~15, nel = (2 * win_x + 1) * (2 * win_y + 1);
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_cor = (size_t)dstride * h, o_mask = o_cor + up16((size_t)n * 8), in_bytes = o_mask + up16((size_t)nel * 4);
-    const size_t o_st = in_bytes, total = o_st + (size_t)n * 4;
-    std::vector<uint8_t> host(in_bytes, 0);
-    for (int y = 0; y < h; y++) memcpy(&host[(size_t)y * dstride], bgr + (size_t)y * stride, (size_t)3 * w);
-    memcpy(&host[o_cor], corners, (size_t)n * 8);
-    corner_mask(win_x, win_y, zero_x, zero_y, reinterpret_cast<float*>(&host[o_mask]));
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, total);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        CornerJob j{};
-        j.kind = SOURCE_BGR;
-        j.src = d; j.stride = dstride; j.frame_pitch = (int64_t)dstride * h; j.w = w; j.h = h;
-        j.frames = nullptr; j.n = 1; j.per_frame = n;
-        j.corners = reinterpret_cast<float*>(d + o_cor); j.counts = nullptr; j.status = reinterpret_cast<int32_t*>(d + o_st);
-        j.mask = reinterpret_cast<const float*>(d + o_mask);
-        j.win_x = win_x; j.win_y = win_y; j.max_iters = max_iters; j.eps = eps;
-        e = launch_corner(j, c->stream);
-    }
-    c->last_what = "k_corner_subpix";
-    int rcw = 0;
-    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_corner_subpix");
-    if (e == hipSuccess && rcw == 0) e = hipMemcpy(corners, d + o_cor, (size_t)n * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rcw == 0 && status_out) e = hipMemcpy(status_out, d + o_st, (size_t)n * 4, hipMemcpyDeviceToHost);
-    if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernel may still be using it)
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_corner_subpix", e);
-    return rcw;
-}
-
-int rmcv_find_chessboard(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, int cols, int rows, const rmcv_chess_params* params, float* corners_out,
-                         int32_t* status_out, int32_t* cand_out, int32_t* cand_n_out)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    const rmcv_chess_params prm = params ? *params : rmcv::chess_default_params();
-    const char* bad = rmcv::chess_image_refusal(bgr, corners_out, w, h, stride);
-    if (!bad) bad = rmcv::chess_params_refusal(cols, rows, prm);
-    if (bad) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "rmcv_find_chessboard: %s", bad);
-        return fail(c, RMCV_ERR_BAD_ARG, msg);
-    }
-    if (w > c->lim.max_width || h > c->lim.max_height) return fail(c, RMCV_ERR_BAD_ARG, rmcv::CHESS_BEYOND_LIMITS);
-    if (const int rc = ctx_ready(c)) return rc;
-    // (a stage-wise helper: buffers of its own) -- the image packed to rows of 3 w bytes rounded up to 16; behind it the words (count, status,
-    // candidates, -), the corners, the sorted candidates and the list between the two kernels
-    constexpr size_t CAP = RMCV_CHESS_CAND_MAX;
-    const int dstride = (3 * w + 15) & ~15, want = cols * rows;
-    const size_t o_words = (size_t)dstride * h, o_cor = o_words + 16, o_cand = o_cor + (size_t)want * 8, o_list = o_cand + 12 * CAP;
-    const size_t total = o_list + 4 * (1 + (size_t)rmcv::CHESS_LIST_WORDS);
-    std::vector<uint8_t> host(o_words, 0);
-    for (int y = 0; y < h; y++) memcpy(&host[(size_t)y * dstride], bgr + (size_t)y * stride, (size_t)3 * w);
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, total);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, host.data(), o_words, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        ChessJob j{};
-        j.src.kind = SOURCE_BGR;
-        j.src.src = d; j.src.stride = dstride; j.src.frame_pitch = (int64_t)dstride * h; j.src.w = w; j.src.h = h;
-        j.src.frames = nullptr; j.src.n = 1;
-        j.cols = cols; j.rows = rows; j.prm = prm;
-        j.lists = reinterpret_cast<uint32_t*>(d + o_list);
-        j.corners = reinterpret_cast<float*>(d + o_cor); j.per_frame = want;
-        int32_t* words = reinterpret_cast<int32_t*>(d + o_words);
-        j.counts = words; j.status = words + 1; j.cand_n = words + 2;
-        j.cand = reinterpret_cast<int32_t*>(d + o_cand);
-        e = launch_chess(j, c->stream);
-    }
-    c->last_what = "k_chess";
-    int rcw = 0;
-    int32_t words[3] = {0, 0, 0};
-    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_chess");
-    if (e == hipSuccess && rcw == 0) e = hipMemcpy(words, d + o_words, sizeof(words), hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rcw == 0 && words[0] == want) e = hipMemcpy(corners_out, d + o_cor, (size_t)want * 8, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && rcw == 0 && cand_out && words[2] > 0 && words[2] <= (int)CAP) e = hipMemcpy(cand_out, d + o_cand, (size_t)words[2] * 12, hipMemcpyDeviceToHost);
-    if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernels may still be using it)
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_find_chessboard", e);
-    if (rcw) return rcw;
-    if (status_out) *status_out = words[1];
-    if (cand_n_out) *cand_n_out = words[2];
-    return RMCV_OK;
-}
-
-int rmcv_icon_strip(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, const rmcv_armour* armours, int n, int side, int cap, uint8_t* out,
-                    int out_stride)
-{
-    if (!c) return RMCV_ERR_BAD_ARG;
-    if (const char* bad = rmcv::icon_strip_image_refusal(bgr, out, w, h, stride, armours, n, side, cap, out_stride)) {
-        char msg[160];
-        snprintf(msg, sizeof(msg), "rmcv_icon_strip: %s", bad);
-        return fail(c, RMCV_ERR_BAD_ARG, msg);
-    }
-    if (w > c->lim.max_width || h > c->lim.max_height || cap > c->lim.max_armours || n > c->lim.max_armours) return fail(c, RMCV_ERR_BAD_ARG, rmcv::ICON_STRIP_BEYOND_LIMITS);
-    if (const int rc = ctx_ready(c)) return rc;
-    // (a stage-wise helper: buffers of its own, so that nothing bound to the context moves) -- one host block, one upload; the image
-    // packed to rows of 3 w bytes rounded up to 16
-    const int dstride = (3 * w + 15) & ~15;
-    auto up16 = [](size_t v) { return (v + 15) & ~(size_t)15; };
-    const size_t o_arm = (size_t)dstride * h, o_cnt = o_arm + up16((size_t)n * sizeof(rmcv_armour)), in_bytes = o_cnt + 16;
-    const size_t row = (size_t)3 * cap * side, o_out = in_bytes, total = o_out + row * side;
-    std::vector<uint8_t> host(in_bytes, 0);
-    for (int y = 0; y < h; y++) memcpy(&host[(size_t)y * dstride], bgr + (size_t)y * stride, (size_t)3 * w);
-    if (n) memcpy(&host[o_arm], armours, (size_t)n * sizeof(rmcv_armour));
-    const int32_t count = n;
-    memcpy(&host[o_cnt], &count, 4);
-    uint8_t* d = nullptr;
-    hipError_t e = hipMalloc((void**)&d, total);
-    if (e == hipSuccess) e = hipMemcpyAsync(d, host.data(), in_bytes, hipMemcpyHostToDevice, c->stream);
-    if (e == hipSuccess) {
-        IconStripJob S{};
-        S.frames = d, S.frame_pitch = (int64_t)dstride * h, S.stride = dstride, S.w = w, S.h = h, S.max_armours = n > 0 ? n : 1;
-        S.armours = reinterpret_cast<const rmcv_armour*>(d + o_arm), S.n_armours = reinterpret_cast<const int32_t*>(d + o_cnt);
-        S.n = 1, S.side = side, S.cap = cap, S.strip_w = cap * side, S.out = d + o_out, S.out_stride = (int)row, S.out_pitch = (int64_t)row * side;
-        e = launch_icon_strip(S, c->stream);
-    }
-    c->last_what = "k_icon_strip";
-    int rcw = 0;
-    if (e == hipSuccess) rcw = wait_stream(c, c->stream, "k_icon_strip");
-    if (e == hipSuccess && rcw == 0) e = hipMemcpy2D(out, out_stride, d + o_out, row, row, side, hipMemcpyDeviceToHost);
-    if ((rcw == 0 || e != hipSuccess) && d) hipFree(d); // (after a wait that ran out the kernel may still be using it)
-    if (e != hipSuccess) return fail(c, e == hipErrorOutOfMemory ? RMCV_ERR_NOMEM : RMCV_ERR_HIP, "rmcv_icon_strip", e);
     return rcw;
 }
 

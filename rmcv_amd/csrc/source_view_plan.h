@@ -8,6 +8,7 @@
 
 #include "../../include/rmcv_abi.h"
 #include "bind_plan.h"
+#include "view_plan.h"
 
 namespace rmcv {
 
@@ -35,20 +36,17 @@ inline SourceKind source_kind(const Geom& g) { return source_kind(g.input_format
 // ---- the refusals: the message an entry point fails with (RMCV_ERR_BAD_ARG), or null ----
 // the batch entry points (rmcv_batch_source_views, rmcv_batch_get_source_view, rmcv_pipeline_set_source_views): rmcv_batch_debug_views' list.
 // frames: host values; n_frames / stages: the batch the views are of and the stages it has been, or will be, through; need: view_stages_needed(flags)
+static constexpr FrameListWords SOURCE_VIEW_FRAME_LIST = {nullptr, "source views: no frames chosen", "source views: more views than the batch has frames",
+                                                          "source views: a frame index is outside the batch", "source views: a frame index is repeated"};
 inline const char* source_views_refusal(const int32_t* frames, int n, int n_frames, int stages, int need, int vw, int vh, int max_width, int max_height, int flags,
                                         int out_stride, int64_t out_pitch)
 {
-    if (!frames || n < 1) return "source views: no frames chosen";
-    if (n > n_frames) return "source views: more views than the batch has frames";
+    if (const FrameListFault bad = frame_count_fault(frames, n, n_frames)) return SOURCE_VIEW_FRAME_LIST[bad];
     if (flags < 0 || flags > RMCV_VIEW_ALL) return "source views: unknown view flags";
     if (vw < 1 || vh < 1 || vw > max_width || vh > max_height) return "source views: the view size must be 1 .. max_width x 1 .. max_height";
     if (out_stride < 3 * (int64_t)vw) return "source views: out_stride < 3 vw";
     if (n > 1 && out_pitch < (int64_t)out_stride * (vh - 1) + 3 * (int64_t)vw) return "source views: out_pitch < out_stride (vh - 1) + 3 vw";
-    for (int k = 0; k < n; k++) {
-        if (frames[k] < 0 || frames[k] >= n_frames) return "source views: a frame index is outside the batch";
-        for (int q = 0; q < k; q++)
-            if (frames[q] == frames[k]) return "source views: a frame index is repeated";
-    }
+    if (const FrameListFault bad = frame_index_fault(frames, n, n_frames)) return SOURCE_VIEW_FRAME_LIST[bad];
     if ((stages & need) != need) return "source views: the batch's run lacked a stage the view flags need";
     return nullptr;
 }

@@ -448,3 +448,53 @@ def test_refusals_on_the_device_paths(small):
         c.icon_strip_of(np.zeros((8, 700, 3), np.uint8), arm, 20, 2)
     # the context still works
     assert c.icon_strips([1], 20, 4).shape == (1, 20, 80, 3)
+
+
+def test_one_frame_table_serves_calls_on_two_streams():
+    """The chosen frames of every view, label, strip, sheet, corner and chessboard call travel through ONE table of the context
+    (rmcv_ctx::frame_list), written behind the context's ordering event.  Corners of frames [3, 1] on a caller stream A, at once debug views
+    of [0, 2] on a second stream B, then a strip of [2] on A again: each result equals, bit for bit, what the same call returns alone on a
+    fresh context from the same frames -- no call's list lands before the kernels of the call before have read theirs -- and the same holds
+    for a second round in the same context."""
+    import torch
+    frames = frames_of(W, H, SPECIAL)[:4]
+    p = default_params(tilt_max=TILT)
+    view, side, cap = (100, 68), 20, 4
+    guess = np.tile(np.array([(30, 30), (60, 40), (100, 70), (150, 100), (170, 20), (20, 120)], np.float32), (2, 1, 1))
+
+    def fresh():
+        c = Context(device=0, max_frames=4, max_width=W, max_height=H)
+        c.upload(frames)
+        c.run(p, STAGE_ALL)
+        return c
+
+    alone = []
+    for call in (lambda c: c.refine_corners([3, 1], guess), lambda c: c.debug_views([0, 2], view), lambda c: c.icon_strips([2], side, cap)):
+        c = fresh()
+        try:
+            alone.append(call(c))
+        finally:
+            c.close()
+    (want_corners, want_status), want_views, want_strips = alone
+    assert want_corners[0].tobytes() != want_corners[1].tobytes() and not np.array_equal(want_views[0], want_views[1])   # (a list that went astray would show)
+    c = fresh()
+    try:
+        c.sync()
+        a, b = torch.cuda.Stream(), torch.cuda.Stream()
+        corners, status = torch.empty((2, 6, 2), dtype=torch.float32, device="cuda"), torch.empty((2, 6), dtype=torch.int32, device="cuda")
+        views = torch.empty((2, view[1], view[0], 3), dtype=torch.uint8, device="cuda")
+        strips = torch.empty((1, side, cap * side, 3), dtype=torch.uint8, device="cuda")
+        for _ in range(2):
+            corners.copy_(torch.from_numpy(guess))
+            status.fill_(-1), views.fill_(0xEE), strips.fill_(0xEE)
+            torch.cuda.synchronize()
+            c.refine_corners([3, 1], corners.data_ptr(), status=status.data_ptr(), per_frame=6, stream=a.cuda_stream)
+            c.debug_views([0, 2], view, out=views.data_ptr(), stream=b.cuda_stream)
+            c.icon_strips([2], side, cap, dst=strips.data_ptr(), stream=a.cuda_stream)
+            a.synchronize(), b.synchronize()
+            assert corners.cpu().numpy().tobytes() == want_corners.tobytes() and status.cpu().numpy().tolist() == want_status.tolist()
+            assert np.array_equal(views.cpu().numpy(), want_views)
+            assert np.array_equal(strips.cpu().numpy(), want_strips)
+            assert c.check_guards()[0] == 0
+    finally:
+        c.close()

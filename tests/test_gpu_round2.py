@@ -462,6 +462,7 @@ def test_armour_list_compaction_many_frames_and_overflow(oracle):
     for cap in (total + 10, total, total // 2 + 3, 1):
         out = torch.full((cap * dt.itemsize,), 0xEE, dtype=torch.uint8, device="cuda")
         fo = torch.full((n + 1,), -1, dtype=torch.int32, device="cuda")
+        torch.cuda.synchronize()                                    # (the fills run on torch's stream, the kernel on the context's own: not ordered otherwise)
         c.compact_armours_into(out.data_ptr(), cap, fo.data_ptr())
         torch.cuda.synchronize()
         assert fo.cpu().numpy().tolist() == offs.tolist(), cap      # the offsets always describe the complete list
