@@ -54,6 +54,8 @@ struct Geom {
     // table (Bufs::model_idx), by k_classify_models; 0: entry 0 for every frame, the single-model kernels
     int models;
 };
+// bytes of one pixel of the frames a geometry describes: 3 (BGR), or the Bayer sample's 1 or 2
+inline int geom_pixel_bytes(const Geom& g) { return g.input_format ? g.sample_bytes : 3; }
 
 // What a binding records of the context's options (frames bound before keep what they were bound with)
 struct InputOptions {

@@ -31,7 +31,7 @@
 #include "source_view_plan.h"
 
 #if defined(__HIPCC__)
-#include "device_bayer.h"
+#include "frame_source.h"
 #define CORNER_FN __host__ __device__ static inline
 #else
 #define CORNER_FN static inline
@@ -210,15 +210,9 @@ static inline void corner_subpix_host(const uint8_t* bgr, int w, int h, int stri
 
 #if defined(__HIPCC__)
 // ---- the device's gray accessor: gray of SRC(f) at (x, y), both clamped into w x h, by the kind of source (source_view_plan.h) -- what
-// k_view_source and the icon paths read.  frame: the frame's first byte, a windowed batch's at its effective origin (frame_origin_offset);
-// lut: the frame's table (SOURCE_BGR_LUT); rx, ry, lay: a mosaic's R site and layout word (device_bayer.h).
-struct CornerSource {
-    const uint8_t* frame;
-    const uint8_t* lut;
-    int stride, w, h, rx, ry, lay;
-};
+// k_view_source and the icon paths read -- of the frame frame_pixels (frame_source.h) has resolved
 template <int SRC>
-__device__ inline int corner_gray_at(const CornerSource& s, int x, int y)
+__device__ inline int corner_gray_at(const FramePixels& s, int x, int y)
 {
     x = corner_clamp(x, s.w);
     y = corner_clamp(y, s.h);

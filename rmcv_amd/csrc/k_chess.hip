@@ -20,24 +20,13 @@
 namespace rmcv {
 
 template <int SRC>
-__device__ inline CornerSource chess_source(const CornerJob& j, int k)
-{
-    const int f = j.frames ? j.frames[k] : k;
-    CornerSource S;
-    S.frame = j.src + (int64_t)f * j.frame_pitch + (SRC == SOURCE_BGR_WIN ? frame_origin_offset(j.win_eff, f, j.stride) : 0);
-    S.lut = SRC == SOURCE_BGR_LUT ? j.lut + (int64_t)f * 256 : nullptr;
-    S.stride = j.stride; S.w = j.w; S.h = j.h; S.rx = j.rx; S.ry = j.ry; S.lay = j.lay;
-    return S;
-}
-
-template <int SRC>
 __global__ __launch_bounds__(256) void k_chess_response(ChessJob j)
 {
     __shared__ uint32_t s_gray[CHESS_GRAY_MAX / 4];
     __shared__ int16_t s_resp[CHESS_RESP_MAX];
     constexpr int GP = CHESS_GRAY_PITCH, RP = CHESS_RESP_PITCH;   // (constants: every tap's LDS offset is an immediate)
     const int tid = threadIdx.x, lane = tid & 63, k = blockIdx.z;
-    const CornerSource S = chess_source<SRC>(j.src, k);
+    const FramePixels S = frame_pixels<SRC>(j.src, j.frames ? j.frames[k] : k);
     const int nms = j.prm.nms, halo = CHESS_RING_R + nms, w = j.src.w, h = j.src.h;
     const int x0 = blockIdx.x * CHESS_TILE_X, y0 = blockIdx.y * CHESS_TILE_Y;
     const int gc = chess_gray_cols(nms), gr = chess_gray_rows(nms), rc = chess_resp_cols(nms), rr = chess_resp_rows(nms);
@@ -58,7 +47,7 @@ __global__ __launch_bounds__(256) void k_chess_response(ChessJob j)
     }
     __syncthreads();
     uint32_t* count = j.lists + k;
-    uint32_t* keys = j.lists + j.src.n + (int64_t)k * CHESS_LIST_WORDS;
+    uint32_t* keys = j.lists + j.n + (int64_t)k * CHESS_LIST_WORDS;
     for (int it = 0; it < CHESS_TILE_Y / 4; it++) {
         const int r = it * 4 + (tid >> 6), c = lane;   // (a wavefront: one row of the tile)
         const int16_t* centre = s_resp + (r + nms) * RP + c + nms;
@@ -95,7 +84,7 @@ __global__ __launch_bounds__(CHESS_GRID_THREADS) void k_chess_grid(ChessJob j)
     __shared__ int s_found;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, k = blockIdx.x;
     const uint32_t total = j.lists[k];
-    const uint32_t* keys = j.lists + j.src.n + (int64_t)k * CHESS_LIST_WORDS;
+    const uint32_t* keys = j.lists + j.n + (int64_t)k * CHESS_LIST_WORDS;
     if (total > RMCV_CHESS_CAND_MAX) {   // (the whole workgroup)
         if (tid == 0) {
             j.counts[k] = 0;
@@ -118,7 +107,7 @@ __global__ __launch_bounds__(CHESS_GRID_THREADS) void k_chess_grid(ChessJob j)
         s_val[rank] = s_val0[i];
     }
     __syncthreads();
-    const CornerSource S = chess_source<SRC>(j.src, k);
+    const FramePixels S = frame_pixels<SRC>(j.src, j.frames ? j.frames[k] : k);
     const int dmin2 = j.prm.dist_min * j.prm.dist_min, dmax2 = j.prm.dist_max * j.prm.dist_max, bar = 9 * j.prm.contrast;
     for (int a = wv; a < n; a += CHESS_GRID_THREADS / 64) {
         const uint32_t pa = s_key[a];
@@ -208,23 +197,16 @@ __global__ __launch_bounds__(CHESS_GRID_THREADS) void k_chess_grid(ChessJob j)
 template <int SRC>
 static hipError_t launch_chess_kind(const ChessJob& j, hipStream_t s)
 {
-    const dim3 tiles((unsigned)chess_tiles_x(j.src.w), (unsigned)chess_tiles_y(j.src.h), (unsigned)j.src.n);
-    hipError_t e = hipMemsetAsync(j.lists, 0, (size_t)j.src.n * 4, s);
+    const dim3 tiles((unsigned)chess_tiles_x(j.src.w), (unsigned)chess_tiles_y(j.src.h), (unsigned)j.n);
+    hipError_t e = hipMemsetAsync(j.lists, 0, (size_t)j.n * 4, s);
     if (e == hipSuccess) e = launch(k_chess_response<SRC>, tiles, dim3(256), 0, s, j);
-    if (e == hipSuccess) e = launch(k_chess_grid<SRC>, dim3((unsigned)j.src.n), dim3(CHESS_GRID_THREADS), 0, s, j);
+    if (e == hipSuccess) e = launch(k_chess_grid<SRC>, dim3((unsigned)j.n), dim3(CHESS_GRID_THREADS), 0, s, j);
     return e;
 }
 
 hipError_t launch_chess(const ChessJob& j, hipStream_t s)
 {
-    switch (j.src.kind) {
-    case SOURCE_BGR: return launch_chess_kind<SOURCE_BGR>(j, s);
-    case SOURCE_BGR_WIN: return launch_chess_kind<SOURCE_BGR_WIN>(j, s);
-    case SOURCE_MOSAIC: return launch_chess_kind<SOURCE_MOSAIC>(j, s);
-    case SOURCE_MOSAIC_RAW: return launch_chess_kind<SOURCE_MOSAIC_RAW>(j, s);
-    case SOURCE_BGR_LUT: return launch_chess_kind<SOURCE_BGR_LUT>(j, s);
-    }
-    return hipErrorInvalidValue; // (no kernel for the kind: an error, never another path)
+    return with_source_kind(j.src.kind, [&](auto K) { return launch_chess_kind<decltype(K)::value>(j, s); });
 }
 
 } // namespace rmcv

@@ -42,15 +42,11 @@ __global__ __launch_bounds__(256) void k_corner_subpix(CornerJob j)
         cnt = cnt < 0 ? 0 : (cnt > j.per_frame ? j.per_frame : cnt);
     }
     if (q >= cnt) return;
-    const int f = j.frames ? j.frames[k] : k;
-    CornerSource S;
-    S.frame = j.src + (int64_t)f * j.frame_pitch + (SRC == SOURCE_BGR_WIN ? frame_origin_offset(j.win_eff, f, j.stride) : 0);
-    S.lut = SRC == SOURCE_BGR_LUT ? j.lut + (int64_t)f * 256 : nullptr;
-    S.stride = j.stride; S.w = j.w; S.h = j.h; S.rx = j.rx; S.ry = j.ry; S.lay = j.lay;
+    const FramePixels S = frame_pixels<SRC>(j.src, j.frames ? j.frames[k] : k);
     uint8_t* g8 = reinterpret_cast<uint8_t*>(s_gray[wv]);
     float* pt = s_patch[wv];
     auto sums = [&](float cx, float cy) {
-        const CornerPatch P = corner_patch(cx, cy, win_w, win_h, j.w, j.h);
+        const CornerPatch P = corner_patch(cx, cy, win_w, win_h, j.src.w, j.src.h);
         corner_wave_sync(); // (the pass before has read its patch)
         for (int i = lane; i < gw * gh; i += 64) {
             const int r = i / gw, c = i - r * gw;
@@ -83,7 +79,7 @@ __global__ __launch_bounds__(256) void k_corner_subpix(CornerJob j)
     float* cp = j.corners + 2 * item;
     float x = cp[0], y = cp[1];
     int32_t st = 0;
-    corner_refine(x, y, st, j.w, j.h, j.win_x, j.win_y, j.max_iters, j.eps, sums);
+    corner_refine(x, y, st, j.src.w, j.src.h, j.win_x, j.win_y, j.max_iters, j.eps, sums);
     if (lane == 0) {
         cp[0] = x;
         cp[1] = y;
@@ -94,32 +90,7 @@ __global__ __launch_bounds__(256) void k_corner_subpix(CornerJob j)
 hipError_t launch_corner(const CornerJob& j, hipStream_t s)
 {
     const dim3 grid((unsigned)corner_workgroups(j.n, j.per_frame)), block(64 * CORNER_WAVES);
-    switch (j.kind) {
-    case SOURCE_BGR: return launch(k_corner_subpix<SOURCE_BGR>, grid, block, 0, s, j);
-    case SOURCE_BGR_WIN: return launch(k_corner_subpix<SOURCE_BGR_WIN>, grid, block, 0, s, j);
-    case SOURCE_MOSAIC: return launch(k_corner_subpix<SOURCE_MOSAIC>, grid, block, 0, s, j);
-    case SOURCE_MOSAIC_RAW: return launch(k_corner_subpix<SOURCE_MOSAIC_RAW>, grid, block, 0, s, j);
-    case SOURCE_BGR_LUT: return launch(k_corner_subpix<SOURCE_BGR_LUT>, grid, block, 0, s, j);
-    }
-    return hipErrorInvalidValue; // (no kernel for the kind: an error, never another path)
-}
-
-void corner_job_source(const Geom& g, const Bufs& b, CornerJob* j)
-{
-    j->kind = source_kind(g);
-    j->src = b.frames;
-    j->stride = g.stride;
-    j->frame_pitch = g.frame_pitch;
-    j->w = g.w;
-    j->h = g.h;
-    j->rx = j->ry = j->lay = 0;
-    if (g.input_format) {
-        j->lay = raw_layout(8 * g.sample_bytes, g.valid_bit, g.orient);
-        j->rx = raw_rx(g.input_format, j->lay, g.w);
-        j->ry = raw_ry(g.input_format, j->lay, g.h);
-    }
-    j->lut = j->kind == SOURCE_BGR_LUT ? b.enh_lut : nullptr;
-    j->win_eff = j->kind == SOURCE_BGR_WIN ? b.win_eff : nullptr;
+    return with_source_kind(j.src.kind, [&](auto K) { return launch(k_corner_subpix<decltype(K)::value>, grid, block, 0, s, j); });
 }
 
 } // namespace rmcv

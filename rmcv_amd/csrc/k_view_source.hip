@@ -16,10 +16,10 @@
 //                        tap reads its overlay bits and, where they are clear, its source pixel through the caches.  The pixels go to an
 //                        LDS tile that is stored as whole dwords where the caller's layout is 4-byte aligned.
 // Ordinary vector loads and stores; no scratch (nothing is indexed dynamically in registers); static LDS: 39 168 B at most.
+#include <assert.h>
+
 #include "rmcv_internal.h"
-#include "device_bayer.h"
 #include "device_view.h"
-#include "source_view_plan.h"
 
 namespace rmcv {
 
@@ -52,11 +52,12 @@ __global__ __launch_bounds__(256) void k_view_source(SourceViewJob sj)
     __shared__ uint32_t s_out[VT_Y * VT_X * 3 / 4];
     __shared__ view_tap s_tx[VT_X], s_ty[VT_Y];
     const ViewJob& j = sj.view;
+    const FrameSource& fs = sj.src;
     const int v = blockIdx.z, tid = threadIdx.x;
-    const int f = j.frames ? j.frames[v] : v;
+    const FramePixels P = frame_pixels<SRC>(fs, j.frames ? j.frames[v] : v);
     const uint64_t* pa = j.overlay + (int64_t)v * 2 * j.plane_pitch;
     const uint64_t* pb = pa + j.plane_pitch;
-    const uint8_t* frame = sj.src + (int64_t)f * sj.frame_pitch + (SRC == SOURCE_BGR_WIN ? frame_origin_offset(sj.win_eff, f, sj.stride) : 0);
+    const uint8_t* frame = P.frame;
     const int mode = view_resize_mode(j.w, j.h, j.vw, j.vh);
     const int x0 = blockIdx.x * VT_X, y0 = blockIdx.y * VT_Y;
     const int nx = j.vw - x0 < VT_X ? j.vw - x0 : VT_X, ny = j.vh - y0 < VT_Y ? j.vh - y0 : VT_Y;
@@ -66,7 +67,7 @@ __global__ __launch_bounds__(256) void k_view_source(SourceViewJob sj)
     } else if (tid < VT_X + VT_Y) {
         if (tid - VT_X < ny) s_ty[tid - VT_X] = view_tap_y(mode, y0 + tid - VT_X, j.h, j.vh);
     } else if (SRC == SOURCE_BGR_LUT && tid >= 128 && tid < 192) {
-        s_lut[tid - 128] = reinterpret_cast<const uint32_t*>(sj.lut + (int64_t)f * 256)[tid - 128];
+        s_lut[tid - 128] = reinterpret_cast<const uint32_t*>(P.lut)[tid - 128];
     }
     __syncthreads();
     const uint8_t* lut8 = reinterpret_cast<const uint8_t*>(s_lut);
@@ -75,19 +76,19 @@ __global__ __launch_bounds__(256) void k_view_source(SourceViewJob sj)
     const int pitch = source_span_pitch(sp.cols);
     uint8_t* px8 = reinterpret_cast<uint8_t*>(s_px);
     // where pixel (row r of the span, its first column) lies in LDS: a BGR row keeps the byte phase it has in memory
-    const uint8_t* span0 = frame + (int64_t)sp.r0 * sj.stride + 3 * (int64_t)sp.c0;
-    auto row_at = [&](int r) { return r * pitch + (BGRISH ? (int)((uintptr_t)(span0 + (int64_t)r * sj.stride) & 3) : 0); };
+    const uint8_t* span0 = frame + (int64_t)sp.r0 * fs.stride + 3 * (int64_t)sp.c0;
+    auto row_at = [&](int r) { return r * pitch + (BGRISH ? (int)((uintptr_t)(span0 + (int64_t)r * fs.stride) & 3) : 0); };
     if (staged) {
         if constexpr (BGRISH) { // a wavefront per row: the aligned dwords that hold its 3 cols bytes
             const int nb = 3 * sp.cols;
             for (int r = tid >> 6; r < sp.rows; r += 4) {
-                const uint8_t* a = span0 + (int64_t)r * sj.stride;
+                const uint8_t* a = span0 + (int64_t)r * fs.stride;
                 const int lead = (int)((uintptr_t)a & 3);
                 const int ndw = (lead + nb + 3) >> 2;
                 for (int i = tid & 63; i < ndw; i += 64) {
                     const uint8_t* q = a - lead + 4 * i;
                     uint32_t d = 0;
-                    if (q >= sj.src && q + 4 <= sj.src_end) d = *reinterpret_cast<const uint32_t*>(q);
+                    if (q >= fs.src && q + 4 <= fs.src_end) d = *reinterpret_cast<const uint32_t*>(q);
                     else { // the dword reaches outside what is bound (the first or the last of a buffer): the span's own bytes alone
 #pragma unroll
                         for (int k = 0; k < 4; k++)
@@ -106,7 +107,7 @@ __global__ __launch_bounds__(256) void k_view_source(SourceViewJob sj)
             uint8_t* ring = reinterpret_cast<uint8_t*>(s_ring);
             for (int i = tid; i < mrows * mcols; i += 256) {
                 const int r = i / mcols, c = i - r * mcols;
-                ring[i] = frame[(int64_t)(my0 + r) * sj.stride + mx0 + c];
+                ring[i] = frame[(int64_t)(my0 + r) * fs.stride + mx0 + c];
             }
             __syncthreads();
             for (int i = tid; i < sp.rows * sp.cols; i += 256) {
@@ -114,7 +115,7 @@ __global__ __launch_bounds__(256) void k_view_source(SourceViewJob sj)
                 const int x = clampsv(sp.c0 + c, 1, w - 2), y = clampsv(sp.r0 + r, 1, h - 2);
                 const uint8_t* m = ring + (y - my0) * mcols + (x - mx0);
                 int o[3];
-                bayer_site(m[0], m[-1] + m[1], m[-mcols] + m[mcols], m[-mcols - 1] + m[-mcols + 1] + m[mcols - 1] + m[mcols + 1], (x ^ sj.rx) & 1, (y ^ sj.ry) & 1, o);
+                bayer_site(m[0], m[-1] + m[1], m[-mcols] + m[mcols], m[-mcols - 1] + m[-mcols + 1] + m[mcols - 1] + m[mcols + 1], (x ^ fs.rx) & 1, (y ^ fs.ry) & 1, o);
                 uint8_t* p = px8 + r * pitch + 3 * c;
                 p[0] = (uint8_t)o[0];
                 p[1] = (uint8_t)o[1];
@@ -124,7 +125,7 @@ __global__ __launch_bounds__(256) void k_view_source(SourceViewJob sj)
             for (int i = tid; i < sp.rows * sp.cols; i += 256) {
                 const int r = i / sp.cols, c = i - r * sp.cols;
                 int o[3];
-                bayer_bgr_raw(frame, sj.stride, j.w, j.h, sj.rx, sj.ry, sj.lay, sp.c0 + c, sp.r0 + r, o);
+                bayer_bgr_raw(frame, fs.stride, j.w, j.h, fs.rx, fs.ry, fs.lay, sp.c0 + c, sp.r0 + r, o);
                 uint8_t* p = px8 + r * pitch + 3 * c;
                 p[0] = (uint8_t)o[0];
                 p[1] = (uint8_t)o[1];
@@ -162,13 +163,13 @@ __global__ __launch_bounds__(256) void k_view_source(SourceViewJob sj)
             o[1] = 255 * a;
             o[2] = 255 * b;
         } else if constexpr (BGRISH) {
-            const uint8_t* q = frame + (int64_t)y * sj.stride + 3 * (int64_t)x;
+            const uint8_t* q = frame + (int64_t)y * fs.stride + 3 * (int64_t)x;
 #pragma unroll
             for (int c = 0; c < 3; c++) o[c] = SRC == SOURCE_BGR_LUT ? lut8[q[c]] : q[c];
         } else if constexpr (SRC == SOURCE_MOSAIC) {
-            bayer_bgr(frame, sj.stride, j.w, j.h, sj.rx, sj.ry, x, y, o);
+            bayer_bgr(frame, fs.stride, j.w, j.h, fs.rx, fs.ry, x, y, o);
         } else {
-            bayer_bgr_raw(frame, sj.stride, j.w, j.h, sj.rx, sj.ry, sj.lay, x, y, o);
+            bayer_bgr_raw(frame, fs.stride, j.w, j.h, fs.rx, fs.ry, fs.lay, x, y, o);
         }
     };
     const int col = tid & 63;
@@ -220,37 +221,11 @@ __global__ __launch_bounds__(256) void k_view_source(SourceViewJob sj)
 hipError_t launch_source_view(const SourceViewJob& sj, hipStream_t s)
 {
     const ViewJob& j = sj.view;
+    assert(j.w == sj.src.w && j.h == sj.src.h); // (one extent: the overlay's planes and SRC)
     hipError_t e = launch(k_view_overlay, dim3(j.n), dim3(256), 0, s, j);
     if (e != hipSuccess) return e;
     const dim3 grid((j.vw + VT_X - 1) / VT_X, (j.vh + VT_Y - 1) / VT_Y, j.n), block(256);
-    switch (sj.kind) {
-    case SOURCE_BGR: return launch(k_view_source<SOURCE_BGR>, grid, block, 0, s, sj);
-    case SOURCE_BGR_WIN: return launch(k_view_source<SOURCE_BGR_WIN>, grid, block, 0, s, sj);
-    case SOURCE_MOSAIC: return launch(k_view_source<SOURCE_MOSAIC>, grid, block, 0, s, sj);
-    case SOURCE_MOSAIC_RAW: return launch(k_view_source<SOURCE_MOSAIC_RAW>, grid, block, 0, s, sj);
-    case SOURCE_BGR_LUT: return launch(k_view_source<SOURCE_BGR_LUT>, grid, block, 0, s, sj);
-    }
-    return hipErrorInvalidValue; // (no kernel for the kind: an error, never another path)
-}
-
-// the views of the batch bound to (g, b): SRC(f) by the batch's kind, read as the run read it (Bufs::enh_lut, Bufs::win_eff)
-hipError_t launch_source_view(const Geom& g, const Bufs& b, const ViewJob& view, hipStream_t s)
-{
-    SourceViewJob sj{};
-    sj.view = view;
-    sj.kind = source_kind(g);
-    sj.src = b.frames;
-    sj.src_end = b.frames + (int64_t)(g.n_frames - 1) * g.frame_pitch + (int64_t)(g.frame_h - 1) * g.stride + (int64_t)geom_pixel_bytes(g) * g.frame_w;
-    sj.stride = g.stride;
-    sj.frame_pitch = g.frame_pitch;
-    if (g.input_format) {
-        sj.lay = raw_layout(8 * g.sample_bytes, g.valid_bit, g.orient);
-        sj.rx = raw_rx(g.input_format, sj.lay, g.w);
-        sj.ry = raw_ry(g.input_format, sj.lay, g.h);
-    }
-    sj.lut = sj.kind == SOURCE_BGR_LUT ? b.enh_lut : nullptr;
-    sj.win_eff = sj.kind == SOURCE_BGR_WIN ? b.win_eff : nullptr;
-    return launch_source_view(sj, s);
+    return with_source_kind(sj.src.kind, [&](auto K) { return launch(k_view_source<decltype(K)::value>, grid, block, 0, s, sj); });
 }
 
 } // namespace rmcv

@@ -24,7 +24,7 @@ static int corner_batch(rmcv_ctx* c, const int32_t* frames, int n, void* d_corne
     corner_mask(win_x, win_y, zero_x, zero_y, c->corner_mask_host);
     HIPCHK(c, hipMemcpyAsync(c->corner_mask, c->corner_mask_host, (size_t)nel * 4, hipMemcpyHostToDevice, s), "H2D corner mask");
     CornerJob j{};
-    corner_job_source(c->geom, c->bufs, &j);
+    j.src = frame_source_of(c->geom, c->bufs);
     j.frames = c->frame_list; j.n = n; j.per_frame = per_frame;
     j.corners = (float*)d_corners; j.counts = (const int32_t*)d_counts; j.status = (int32_t*)d_status;
     j.mask = c->corner_mask;
@@ -90,8 +90,7 @@ int rmcv_corner_subpix(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride
     corner_mask(win_x, win_y, zero_x, zero_y, reinterpret_cast<float*>(&host[o_mask]));
     auto launch = [&](uint8_t* d) {
         CornerJob j{};
-        j.kind = SOURCE_BGR;
-        j.src = d; j.stride = dstride; j.frame_pitch = (int64_t)dstride * h; j.w = w; j.h = h;
+        j.src = frame_source_packed(d, w, h, dstride);
         j.frames = nullptr; j.n = 1; j.per_frame = n;
         j.corners = reinterpret_cast<float*>(d + o_cor); j.counts = nullptr; j.status = reinterpret_cast<int32_t*>(d + o_st);
         j.mask = reinterpret_cast<const float*>(d + o_mask);
@@ -115,8 +114,8 @@ static int chess_batch(rmcv_ctx* c, const int32_t* frames, int n, int cols, int 
     int rc = LAZY_TABLE(c, &c->chess_lists, (size_t)c->lim.max_frames * (1 + CHESS_LIST_WORDS), "allocating the chessboard detector's tables");
     if (rc || (rc = frame_list_begin(c, frames, n, s, "H2D chessboard frames"))) return rc;
     ChessJob j{};
-    corner_job_source(c->geom, c->bufs, &j.src);
-    j.src.frames = c->frame_list; j.src.n = n;
+    j.src = frame_source_of(c->geom, c->bufs);
+    j.frames = c->frame_list; j.n = n;
     j.cols = cols; j.rows = rows; j.prm = prm;
     j.lists = c->chess_lists;
     j.corners = (float*)d_corners; j.per_frame = per_frame; j.counts = (int32_t*)d_counts; j.status = (int32_t*)d_status;
@@ -186,9 +185,8 @@ int rmcv_find_chessboard(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stri
     pack_bgr(host.data(), bgr, w, h, stride);
     auto launch = [&](uint8_t* d) {
         ChessJob j{};
-        j.src.kind = SOURCE_BGR;
-        j.src.src = d; j.src.stride = dstride; j.src.frame_pitch = (int64_t)dstride * h; j.src.w = w; j.src.h = h;
-        j.src.frames = nullptr; j.src.n = 1;
+        j.src = frame_source_packed(d, w, h, dstride);
+        j.frames = nullptr; j.n = 1;
         j.cols = cols; j.rows = rows; j.prm = prm;
         j.lists = reinterpret_cast<uint32_t*>(d + o_list);
         j.corners = reinterpret_cast<float*>(d + o_cor); j.per_frame = want;

@@ -1,6 +1,7 @@
 // rmcv_internal.h -- shared declarations of the HIP translation units (not part of the ABI): the device buffers, the kernel launchers of
 // the k_*.hip units, and what the units behind the ABI (rmcv_host, rmcv_stagewise, rmcv_frame, rmcv_pipeline, rmcv_track, rmcv_tracker,
-// rmcv_record, rmcv_gather, rmcv_harvest) need of each other.  Limits and Geom come from bind_plan.h.
+// rmcv_record, rmcv_gather, rmcv_harvest) need of each other.  Limits and Geom come from bind_plan.h; FrameSource, what the jobs of the
+// source view, the corner refinement and the chessboard detector say of SRC(f), and its fillers from frame_source.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -16,6 +17,7 @@
 #include "corner_plan.h"
 #include "device_harvest.h"
 #include "device_novelty.h"
+#include "frame_source.h"
 #include "icon_strip_plan.h"
 #include "image_plan.h"
 #include "model_plan.h"
@@ -129,12 +131,9 @@ __host__ __device__ inline rmcv_point window_origin_eff(rmcv_point req, int fram
     e.y = req.y < 0 ? 0 : (req.y > ym ? ym : req.y);
     return e;
 }
-// Byte offset of what frame f's consumers read inside the frame: its window's effective origin; a null table is whole frames (0).
-// Shared by the pixel kernel (k_binary_win), the classifier and the legacy matcher's camp vote; k_pnp adds the same origin as floats.
-__host__ __device__ inline int64_t frame_origin_offset(const rmcv_point* __restrict__ win_eff, int f, int stride)
-{
-    return win_eff ? (int64_t)win_eff[f].y * stride + 3 * (int64_t)win_eff[f].x : 0;
-}
+// (frame_origin_offset, the byte offset of that origin inside frame f: frame_source.h)
+// SRC(f) of the batch bound to (g, b), read as the run read it
+inline FrameSource frame_source_of(const Geom& g, const Bufs& b) { return frame_source_of(g, b.frames, b.enh_lut, b.win_eff); }
 
 // What pixel_shape (pixel_plan.h) takes of a batch bound to (g, b), as variant `v`, under the run's bound and plan
 inline PixelBatch pixel_batch(const Geom& g, const Bufs& b, PixelVariant v, int lower_bound, const RunPlan& plan)
@@ -214,8 +213,6 @@ hipError_t launch_gamma_lut(float gamma, uint8_t* d_lut, hipStream_t s);
 // D(m) of one device mosaic into a device BGR frame (rmcv_demosaic)
 // lay: the buffer's layout word (device_bayer.h: raw_layout; 0 = a plain 8-bit mosaic) -> D(T(r)) (rmcv_demosaic_raw)
 hipError_t launch_demosaic(const uint8_t* d_raw, int stride, int w, int h, int pattern, int lay, uint8_t* d_out, int out_stride, hipStream_t s);
-// bytes of one pixel of the frames a geometry / a context's options describe: 3 (BGR), or the Bayer sample's 1 or 2
-inline int geom_pixel_bytes(const Geom& g) { return g.input_format ? g.sample_bytes : 3; }
 hipError_t launch_contours(const Geom& g, const Bufs& b, const Limits& lim, hipStream_t s);
 hipError_t launch_blobs(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, hipStream_t s);
 hipError_t launch_armours(const Geom& g, const Bufs& b, const Limits& lim, const rmcv_params& p, hipStream_t s);
@@ -302,19 +299,10 @@ int ctx_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh
 // view: the job k_view_overlay is launched with as it is (w, h: the extent of SRC, a windowed batch's the window's; bits is never read)
 struct SourceViewJob {
     ViewJob view;
-    int kind;                    // SourceKind (source_view_plan.h)
-    const uint8_t* src;          // [frame] the frames as bound: BGR or mosaic, rows `stride` bytes apart, frames `frame_pitch`
-    const uint8_t* src_end;      // one past the last byte bound: no load of the kernel's reaches outside src .. src_end
-    int stride;
-    int64_t frame_pitch;
-    int rx, ry, lay;             // a mosaic's R site and layout word (device_bayer.h: raw_rx, raw_ry, raw_layout of T(r))
-    const uint8_t* lut;          // [frame][256] SOURCE_BGR_LUT: Bufs::enh_lut
-    const rmcv_point* win_eff;   // [frame]      SOURCE_BGR_WIN: Bufs::win_eff
+    FrameSource src;             // (src.w, src.h == view.w, view.h)
 };
-// k_view_overlay + k_view_source<kind> on `s`; every argument has been checked by the caller
+// k_view_overlay + k_view_source<src.kind> on `s`; every argument has been checked by the caller
 hipError_t launch_source_view(const SourceViewJob& j, hipStream_t s);
-// the same for views of the batch bound to (g, b): the kind and the source fields come from them
-hipError_t launch_source_view(const Geom& g, const Bufs& b, const ViewJob& view, hipStream_t s);
 // (the entry points of a context: rmcv_views.hip; the stage-wise rmcv_source_view: rmcv_stagewise.hip).  What a pipeline needs of them, as
 // of the operator's view: the planes come from ctx_view_prepare, the check takes the frames as host values, the enqueue blocks nothing
 int ctx_source_view_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int stages, int vw, int vh, int flags, int out_stride, int64_t out_pitch);
@@ -385,16 +373,9 @@ int ctx_sheet_check(rmcv_ctx* c, const int32_t* frames, int n, int n_frames, int
 int ctx_sheet_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int side, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s);
 
 // ---- sub-pixel corner refinement (k_corner.hip, device_corner.h) ----
-// per_frame corners of each of n chosen frames, refined in place; SRC(f) is read by `kind` as the source view reads it
+// per_frame corners of each of n chosen frames, refined in place; SRC(f) is read as the source view reads it
 struct CornerJob {
-    int kind;                    // SourceKind (source_view_plan.h)
-    const uint8_t* src;          // [frame] the frames as bound: BGR or mosaic, rows `stride` bytes apart, frames `frame_pitch`
-    int stride;
-    int64_t frame_pitch;
-    int w, h;                    // the extent of SRC (a windowed batch's: the window's)
-    int rx, ry, lay;             // a mosaic's R site and layout word (device_bayer.h)
-    const uint8_t* lut;          // [frame][256] SOURCE_BGR_LUT: Bufs::enh_lut
-    const rmcv_point* win_eff;   // [frame]      SOURCE_BGR_WIN: Bufs::win_eff
+    FrameSource src;
     const int32_t* frames;       // [n] device memory; null: row k is of frame k
     int n, per_frame;
     float* corners;              // [n][per_frame][2]
@@ -404,15 +385,15 @@ struct CornerJob {
     int win_x, win_y, max_iters;
     double eps;
 };
-// k_corner_subpix<kind> on `s`; every argument has been checked by the caller (corner_plan.h)
+// k_corner_subpix<src.kind> on `s`; every argument has been checked by the caller (corner_plan.h)
 hipError_t launch_corner(const CornerJob& j, hipStream_t s);
-// the source fields of a job on the batch bound to (g, b)
-void corner_job_source(const Geom& g, const Bufs& b, CornerJob* j);
 
 // ---- the chessboard detector (k_chess.hip, device_chess.h) ----
-// the board of each of n chosen frames; SRC(f) is read by the source fields of a CornerJob (corner_job_source)
+// the board of each of n chosen frames
 struct ChessJob {
-    CornerJob src;               // kind .. win_eff; frames (null: row k is of frame k) and n
+    FrameSource src;
+    const int32_t* frames;       // [n] device memory; null: row k is of frame k
+    int n;
     int cols, rows;
     rmcv_chess_params prm;
     uint32_t* lists;             // [n][1 + CHESS_LIST_WORDS] the candidates between the two kernels: count, keys, responses
@@ -423,7 +404,7 @@ struct ChessJob {
     int32_t* cand;               // [n][RMCV_CHESS_CAND_MAX][3] nullable: the sorted candidates (x, y, R)
     int32_t* cand_n;             // [n] nullable
 };
-// the count words zeroed, k_chess_response<kind>, k_chess_grid<kind> on `s`; every argument has been checked by the caller (chess_plan.h)
+// the count words zeroed, k_chess_response<src.kind>, k_chess_grid<src.kind> on `s`; every argument has been checked by the caller (chess_plan.h)
 hipError_t launch_chess(const ChessJob& j, hipStream_t s);
 
 // ---- the calibration solve (k_calib.hip, device_calib.h) ----

@@ -286,9 +286,7 @@ int rmcv_source_view(rmcv_ctx* c, const uint8_t* bgr, int w, int h, int stride, 
         j.lists = ViewLists{reinterpret_cast<const rmcv_lightblob*>(d + o_blobs), cnt, reinterpret_cast<const rmcv_armour*>(d + o_arm), cnt + 1,
                             reinterpret_cast<const rmcv_point*>(d + o_pts), nullptr, nullptr, cnt + 3, nullptr, cnt + 2,
                             reinterpret_cast<const int32_t*>(d + o_offs), n_blobs, n_armours, n_pts, n_neg, 1};
-        sj.kind = SOURCE_BGR;
-        sj.src = d; sj.src_end = d + (size_t)dstride * (h - 1) + (size_t)3 * w;
-        sj.stride = dstride; sj.frame_pitch = (int64_t)dstride * h;
+        sj.src = frame_source_packed(d, w, h, dstride);
         e = launch_source_view(sj, c->stream);
     }
     c->last_what = "k_view_overlay + k_view_source";

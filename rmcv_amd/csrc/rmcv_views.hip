@@ -118,7 +118,8 @@ int ctx_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh
 int ctx_source_view_enqueue(rmcv_ctx* c, const int32_t* d_frames, int n, int vw, int vh, int flags, void* d_out, int out_stride, int64_t out_pitch, hipStream_t s)
 {
     if (!c->bufs.frames) return fail(c, RMCV_ERR_BAD_ARG, SOURCE_VIEW_NOTHING_BOUND);
-    HIPCHK(c, launch_source_view(c->geom, c->bufs, view_job(c, d_frames, n, vw, vh, flags, d_out, out_stride, out_pitch), s), "k_view_overlay + k_view_source");
+    const SourceViewJob sj{view_job(c, d_frames, n, vw, vh, flags, d_out, out_stride, out_pitch), frame_source_of(c->geom, c->bufs)};
+    HIPCHK(c, launch_source_view(sj, s), "k_view_overlay + k_view_source");
     return RMCV_OK;
 }
 
