@@ -1815,7 +1815,7 @@ int  rmcv_batch_get_chessboard(rmcv_ctx* ctx, int frame, int cols, int rows, con
  * rmcv_pnp_load_cameras.  OpenCV's solver is not restated: the rule is the library's own, written at the head of
  * rmcv_amd/csrc/device_calib.h -- a homography per view (Hartley, DLT, a pinned cyclic Jacobi), intrinsics from the vanishing points, poses
  * as unit quaternions, Levenberg-Marquardt with per-view elimination, every sum in a pinned order -- one source for the host form below and
- * the kernels, which agree bit for bit.  calibrateHandEye is not here.  One status word per camera: */
+ * the kernels, which agree bit for bit.  calibrateHandEye is the next section.  One status word per camera: */
 #define RMCV_CALIB_CONVERGED      (1 << 0)   /* an accepted step had |step|^2 <= eps^2 |parameters|^2 */
 #define RMCV_CALIB_MAX_ITERS      (1 << 1)   /* max_iters trials were made */
 #define RMCV_CALIB_STALLED        (1 << 2)   /* the damping passed 1e12 without an accepted step */
@@ -1879,6 +1879,60 @@ int  rmcv_calibrate_camera(rmcv_ctx* ctx, const float* corners, int per_frame, c
 /* camera_matrix and dist of a result into cfg; gripper2camera and the square are left alone.  RMCV_ERR_BAD_ARG: null, or a result without a
  * solution (none of CONVERGED, MAX_ITERS, STALLED) */
 int  rmcv_calib_to_pnp_config(const rmcv_calib_result* result, rmcv_pnp_config* cfg);
+
+/* ---- calibration solve: the gimbal-to-camera transform ----------------------------------------------------------------------
+ * The second solver of executable/calibration/hand_eye.cpp (:140-155, calibrateHandEye) and the check loop behind it (:157-180), on the view
+ * table rmcv_calibrate_cameras leaves on the device and a table of gimbal attitudes (rmcv_tracker_device_attitudes' layout): the fourth
+ * asynchronous call of a camera's setup.  Its result is the h_gripper2camera of executable/main.cpp:14-19 and goes into
+ * rmcv_pnp_config::gripper2camera, rmcv_attitude_config::gripper2camera and rmcv_tracker_set_stream_cameras.  OpenCV's solver is not
+ * restated: the rule is the library's own, written at the head of rmcv_amd/csrc/device_handeye.h -- the closed form of Horaud and Dornaika
+ * over all pairs of used views, every sum in a pinned order -- one source for the host form below and the kernel, which agree bit for bit.
+ * One status word per camera: */
+#define RMCV_HANDEYE_OK              (1 << 0)   /* rotation and translation solved */
+#define RMCV_HANDEYE_T_UNOBSERVABLE  (1 << 1)   /* a pivot of the translation's 3 x 3 was not finite and > 0: t = 0, the rotation is reported */
+#define RMCV_HANDEYE_TOO_FEW_VIEWS   (1 << 2)   /* fewer than 3 used views, or no pair left: nothing but status and the four counts is written */
+#define RMCV_HANDEYE_TOO_MANY_VIEWS  (1 << 3)   /* more than RMCV_CALIB_VIEWS_PER_CAMERA_MAX used views: likewise */
+typedef struct rmcv_handeye_params {
+    double  min_w;        /* finite, in [0, 1): a pair whose relative rotation has a scalar part below it is skipped */
+    int32_t reserved[2];
+} rmcv_handeye_params;
+/* min_w 0.5: relative turns over 120 degrees are skipped */
+void rmcv_handeye_defaults(rmcv_handeye_params* p);
+typedef struct rmcv_handeye_result {
+    double  cam2gripper[16];   /* row-major 4x4 [R t; 0 1]: the h_gripper2camera hand_eye.cpp:165-167 assembles, rmcv_pnp_config::gripper2camera */
+    double  q[4], t[3];        /* its rotation as the unit quaternion (w, x, y, z), w >= 0, and its translation (the views' tvec units) */
+    double  eig[4];            /* the eigenvalues of the rotation's 4 x 4, ascending: eig[1] near eig[0] says the rotation is not determined */
+    double  pivots[3];         /* the Cholesky pivots of the translation's 3 x 3; behind a failed one: 0 */
+    double  rot_rms, trans_rms;   /* rms residuals of the rotation (quaternion units) and the translation equations over the pairs used */
+    double  world_mean[3];     /* the mean of the board's origin in the base frame over the used views (the check loop, hand_eye.cpp:157-180) */
+    double  world_rms;         /* the rms distance of those origins from their mean */
+    int32_t views_used, pairs_used, pairs_skipped, sweeps;
+    int32_t status, reserved[3];
+} rmcv_handeye_result;         /* 320 bytes */
+typedef struct rmcv_handeye_view {
+    double  world[3];          /* the board's origin in the base frame as this view has it */
+    int32_t used, reserved;    /* used = 1 is written for a used view of a solved camera; no other row is touched */
+} rmcv_handeye_view;
+/* host, no context, one camera: the sequential statement of the rule.  views rmcv_calib_view [n_views] as rmcv_calibrate_camera* leaves them
+ * (q and tvec are read, and used); attitudes rmcv_attitude [n_views], radians; gripper_t double [n_views][3], null: zeros (hand_eye.cpp:150).
+ * A view is used iff its used == 1 and every double read for it is finite.  params: null = the defaults.  result: one; views_out: n_views
+ * rows.  RMCV_ERR_BAD_ARG: a null table; n_views outside 1 .. RMCV_CALIB_VIEWS_MAX; min_w not finite or outside [0, 1). */
+int  rmcv_calibrate_hand_eye_host(const rmcv_calib_view* views, const rmcv_attitude* attitudes, const double* gripper_t, int n_views,
+                                  const rmcv_handeye_params* params, rmcv_handeye_result* result, rmcv_handeye_view* views_out);
+/* a fleet in one call, on device tables: d_views as rmcv_calibrate_cameras leaves them, d_attitudes as rmcv_tracker_device_attitudes,
+ * d_gripper_t nullable, d_view_camera (nullable: camera 0) int32 [n_views], any value (rmcv_calibrate_cameras' rule); d_results
+ * rmcv_handeye_result [n_cameras], d_views_out rmcv_handeye_view [n_views].  Asynchronous: enqueued on hip_stream (NULL: the context's),
+ * ordered behind the context's earlier work; nothing is allocated.  RMCV_ERR_BAD_ARG with a message, before anything is enqueued: what the
+ * host form refuses; n_cameras outside 1 .. RMCV_CALIB_CAMERAS_MAX. */
+int  rmcv_calibrate_hand_eyes(rmcv_ctx* ctx, const void* d_views, const void* d_attitudes, const void* d_gripper_t, int n_views, const void* d_view_camera,
+                              int n_cameras, const rmcv_handeye_params* params, void* d_results, void* d_views_out, void* hip_stream);
+/* stage-wise: one camera, host tables through the same kernel, with device buffers of its own.  Waits with the context's deadline. */
+int  rmcv_calibrate_hand_eye(rmcv_ctx* ctx, const rmcv_calib_view* views, const rmcv_attitude* attitudes, const double* gripper_t, int n_views,
+                             const rmcv_handeye_params* params, rmcv_handeye_result* result, rmcv_handeye_view* views_out);
+/* cam2gripper of a result into cfg->gripper2camera; nothing else of cfg is written.  RMCV_ERR_BAD_ARG: null; a result without a rotation
+ * (neither OK nor T_UNOBSERVABLE); one with T_UNOBSERVABLE unless allow_rotation_only != 0 */
+int  rmcv_handeye_to_pnp_config(const rmcv_handeye_result* result, rmcv_pnp_config* cfg, int allow_rotation_only);
+int  rmcv_handeye_to_attitude_config(const rmcv_handeye_result* result, rmcv_attitude_config* cfg, int allow_rotation_only);
 
 /* ---- device memory for hosts without HIP headers (tools/pipeline_bench.c): frames resident in HBM ------------------------------- */
 int  rmcv_device_alloc(int device, int64_t bytes, void** d_ptr);

@@ -22,6 +22,8 @@ from .abi import CHESS_CAND_MAX, CHESS_COUNT_MASK, CHESS_FOUND, CHESS_NO_GRID, C
 from .abi import (CALIB_BAD_INIT, CALIB_CAMERAS_MAX, CALIB_CONVERGED, CALIB_FIX, CALIB_GUESS, CALIB_MAX_ITERS, CALIB_PARAMS, CALIB_RESULT, CALIB_SOLVED, CALIB_STALLED,
                   CALIB_TOO_FEW_VIEWS, CALIB_TOO_MANY_VIEWS, CALIB_VIEW, CALIB_VIEWS_MAX, CALIB_VIEWS_PER_CAMERA_MAX, CalibResult, calib_defaults, calib_params,
                   calibrate_camera_host)
+from .abi import (HANDEYE_OK, HANDEYE_PARAMS, HANDEYE_RESULT, HANDEYE_T_UNOBSERVABLE, HANDEYE_TOO_FEW_VIEWS, HANDEYE_TOO_MANY_VIEWS, HANDEYE_VIEW, HandEyeResult,
+                  calibrate_hand_eye_host, handeye_defaults, handeye_params)
 from .pipeline import Pipeline
 from .recorder import LoopRecord, Recorder, Session, loop_bound, loop_field_at, loop_trigger, pack, pack_bound, unpack
 from . import svm

@@ -131,6 +131,8 @@ EXPORTS = [
     "rmcv_corner_mask", "rmcv_gray_host", "rmcv_corner_subpix_host", "rmcv_corner_subpix", "rmcv_batch_refine_corners", "rmcv_batch_get_refined_corners",
     "rmcv_chess_defaults", "rmcv_find_chessboard_host", "rmcv_find_chessboard", "rmcv_batch_find_chessboards", "rmcv_batch_get_chessboard",
     "rmcv_calib_defaults", "rmcv_calibrate_camera_host", "rmcv_calibrate_cameras", "rmcv_calibrate_camera", "rmcv_calib_to_pnp_config",
+    "rmcv_handeye_defaults", "rmcv_calibrate_hand_eye_host", "rmcv_calibrate_hand_eyes", "rmcv_calibrate_hand_eye", "rmcv_handeye_to_pnp_config",
+    "rmcv_handeye_to_attitude_config",
 ]
 
 
@@ -488,6 +490,14 @@ def load(path):
         L.rmcv_calibrate_camera.argtypes = [C.c_void_p] + L.rmcv_calibrate_camera_host.argtypes
         L.rmcv_calibrate_cameras.argtypes = [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int] + tail + [C.c_void_p]
         L.rmcv_calib_to_pnp_config.argtypes = [C.c_void_p, C.c_void_p]
+    if hasattr(L, "rmcv_calibrate_hand_eye_host"):  # (builds from before the hand-eye solve stay loadable for A/B runs)
+        L.rmcv_handeye_defaults.restype = None
+        L.rmcv_handeye_defaults.argtypes = [C.c_void_p]
+        L.rmcv_calibrate_hand_eye_host.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_calibrate_hand_eye.argtypes = [C.c_void_p] + L.rmcv_calibrate_hand_eye_host.argtypes
+        L.rmcv_calibrate_hand_eyes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.rmcv_handeye_to_pnp_config.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
+        L.rmcv_handeye_to_attitude_config.argtypes = [C.c_void_p, C.c_void_p, C.c_int]
     if hasattr(L, "rmcv_icon_strip_host"):  # (builds from before the icon strip stay loadable for A/B runs)
         strip = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int]
         L.rmcv_affine_correction_host.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_void_p]
@@ -934,6 +944,107 @@ def calibrate_camera_host(corners, counts, cols, rows, square, size, params=None
     if rc:
         raise RmcvError(rc, "rmcv_calibrate_camera_host: " + CALIB_REFUSED)
     return CalibResult(res[0]), views
+
+
+# the hand-eye solve: the status word of a camera and the records
+HANDEYE_OK, HANDEYE_T_UNOBSERVABLE, HANDEYE_TOO_FEW_VIEWS, HANDEYE_TOO_MANY_VIEWS = 1, 2, 4, 8
+HANDEYE_PARAMS = np.dtype([("min_w", "<f8"), ("reserved", "<i4", 2)])
+HANDEYE_RESULT = np.dtype([("cam2gripper", "<f8", 16), ("q", "<f8", 4), ("t", "<f8", 3), ("eig", "<f8", 4), ("pivots", "<f8", 3), ("rot_rms", "<f8"), ("trans_rms", "<f8"),
+                           ("world_mean", "<f8", 3), ("world_rms", "<f8"), ("views_used", "<i4"), ("pairs_used", "<i4"), ("pairs_skipped", "<i4"), ("sweeps", "<i4"),
+                           ("status", "<i4"), ("reserved", "<i4", 3)])
+HANDEYE_VIEW = np.dtype([("world", "<f8", 3), ("used", "<i4"), ("reserved", "<i4")])
+assert HANDEYE_PARAMS.itemsize == 16 and HANDEYE_RESULT.itemsize == 320 and HANDEYE_VIEW.itemsize == 32
+HANDEYE_REFUSED = "tables that are not null, n_views 1 .. 4096, n_cameras 1 .. 64, a finite min_w in [0, 1)"
+
+
+def handeye_defaults():
+    """rmcv_handeye_defaults as a dict: min_w"""
+    p = np.zeros(1, HANDEYE_PARAMS)
+    lib().rmcv_handeye_defaults(ptr(p))
+    return dict(min_w=float(p["min_w"][0]))
+
+
+def handeye_params(params=None, **changes):
+    """struct rmcv_handeye_params: the defaults, then `params` (a dict), then the keyword changes"""
+    p = handeye_defaults()
+    for k, v in list((params or {}).items()) + list(changes.items()):
+        assert k in p, "no hand-eye parameter %r" % k
+        p[k] = v
+    out = np.zeros(1, HANDEYE_PARAMS)
+    out["min_w"] = float(p["min_w"])
+    return out
+
+
+class HandEyeResult:
+    """one camera's struct rmcv_handeye_result (`.rec`, a numpy record) with its fields as attributes"""
+
+    def __init__(self, rec):
+        self.rec = rec
+        self.cam2gripper = np.array(rec["cam2gripper"], np.float64).reshape(4, 4)
+        self.q, self.t, self.eig, self.pivots = (np.array(rec[k], np.float64) for k in ("q", "t", "eig", "pivots"))
+        self.rot_rms, self.trans_rms, self.world_rms = float(rec["rot_rms"]), float(rec["trans_rms"]), float(rec["world_rms"])
+        self.world_mean = np.array(rec["world_mean"], np.float64)
+        self.views_used, self.pairs_used, self.pairs_skipped = int(rec["views_used"]), int(rec["pairs_used"]), int(rec["pairs_skipped"])
+        self.sweeps, self.status = int(rec["sweeps"]), int(rec["status"])
+
+    @property
+    def solved(self):
+        """a rotation is there (the translation too unless the status is HANDEYE_T_UNOBSERVABLE)"""
+        return bool(self.status & (HANDEYE_OK | HANDEYE_T_UNOBSERVABLE))
+
+    def _into(self, call, name, cfg, allow_rotation_only):
+        rec = np.array(self.rec, HANDEYE_RESULT).reshape(1)
+        rc = call(ptr(rec), C.byref(cfg), int(bool(allow_rotation_only)))
+        if rc:
+            raise RmcvError(rc, "%s: the result holds no mounting (status %d)" % (name, self.status))
+        return cfg
+
+    def as_pnp_config(self, base=None, allow_rotation_only=False):
+        """a PnpConfig with this gripper2camera (rmcv_handeye_to_pnp_config); everything else is `base`'s, or the defaults'"""
+        cfg = default_pnp_config() if base is None else PnpConfig.from_buffer_copy(base)
+        return self._into(lib().rmcv_handeye_to_pnp_config, "rmcv_handeye_to_pnp_config", cfg, allow_rotation_only)
+
+    def as_attitude_config(self, base=None, allow_rotation_only=False):
+        """an AttitudeConfig with this gripper2camera (rmcv_handeye_to_attitude_config); everything else is `base`'s, or the defaults'"""
+        from .tracker import AttitudeConfig, default_attitude_config
+        cfg = default_attitude_config() if base is None else AttitudeConfig.from_buffer_copy(base)
+        return self._into(lib().rmcv_handeye_to_attitude_config, "rmcv_handeye_to_attitude_config", cfg, allow_rotation_only)
+
+    def __repr__(self):
+        return "HandEyeResult(status=%d, views_used=%d, pairs_used=%d, rot_rms=%.3g, trans_rms=%.3g, world_rms=%.3g)" % (
+            self.status, self.views_used, self.pairs_used, self.rot_rms, self.trans_rms, self.world_rms)
+
+
+def handeye_tables(views, attitudes, gripper_t=None):
+    """(views CALIB_VIEW (n,), attitudes ATTITUDE (n,) -- an ATTITUDE array or (n, 3) (roll, pitch, yaw) radians --, gripper_t (n, 3) float64 or None)"""
+    views = np.ascontiguousarray(views, CALIB_VIEW).reshape(-1)
+    if not (isinstance(attitudes, np.ndarray) and attitudes.dtype == ATTITUDE):
+        a = np.asarray(attitudes, np.float64).reshape(-1, 3)
+        attitudes = np.zeros(len(a), ATTITUDE)
+        attitudes["roll"], attitudes["pitch"], attitudes["yaw"] = a[:, 0], a[:, 1], a[:, 2]
+    attitudes = np.ascontiguousarray(attitudes).reshape(-1)
+    assert len(attitudes) == len(views), "one attitude per view"
+    if gripper_t is not None:
+        gripper_t = np.ascontiguousarray(gripper_t, np.float64).reshape(-1, 3)
+        assert len(gripper_t) == len(views), "one gripper translation per view"
+    return views, attitudes, gripper_t
+
+
+def handeye_outputs(n_cameras, n_views):
+    """(results, view rows) as the entry points take them: zeroed, so that rows they do not touch read used = 0, status = 0"""
+    return np.zeros(n_cameras, HANDEYE_RESULT), np.zeros(n_views, HANDEYE_VIEW)
+
+
+def calibrate_hand_eye_host(views, attitudes, gripper_t=None, params=None, **changes):
+    """the camera's mounting on the gimbal from the calibration solve's view rows and the gimbal's attitudes, on the CPU
+    (rmcv_calibrate_hand_eye_host: the sequential statement of the rule) -> (HandEyeResult, rows: a HANDEYE_VIEW record array
+    of n_views rows, used = 0 for a view that was skipped)"""
+    views, attitudes, gripper_t = handeye_tables(views, attitudes, gripper_t)
+    res, rows = handeye_outputs(1, len(views))
+    rc = lib().rmcv_calibrate_hand_eye_host(ptr(views), ptr(attitudes), ptr(gripper_t), len(views), ptr(handeye_params(params, **changes)), ptr(res), ptr(rows))
+    if rc:
+        raise RmcvError(rc, "rmcv_calibrate_hand_eye_host: " + HANDEYE_REFUSED)
+    return HandEyeResult(res[0]), rows
 
 
 ICON_SIDE_MAX, ICON_STRIP_CAP_MAX = 256, 1024   # the icon strip (DESIGN.md 4r)

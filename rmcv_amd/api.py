@@ -836,17 +836,74 @@ class Context:
                                               int(size[1]), ptr(abi.calib_params(params, **changes)), ptr(g), ptr(res), ptr(views)))
         return abi.CalibResult(res[0]), views
 
+    # ---------------------------------------------------------------- the hand-eye solve
+    def calibrate_hand_eyes(self, views, attitudes, gripper_t=None, view_camera=None, n_cameras=1, params=None, results=None, rows=None, n_views=None, stream=None,
+                            **changes):
+        """the mounting of every camera of a fleet on its gimbal from the calibration solve's view rows and the gimbals' attitudes, on the device
+        (calibrateHandEye and the check loop, executable/calibration/hand_eye.cpp:140-180; rmcv_calibrate_hand_eyes; asynchronous).  With host
+        arrays -- views CALIB_VIEW (n_views,), attitudes ATTITUDE (n_views,) or (n_views, 3) (roll, pitch, yaw), gripper_t (n_views, 3) or None,
+        view_camera (n_views,) int32 or None -- returns ([HandEyeResult per camera], rows: a HANDEYE_VIEW record array) (synchronises;
+        `results` / `rows`: record arrays the device tables start from, zeroed by default).  With `results`, a device pointer of the caller's to
+        n_cameras struct rmcv_handeye_result: views, attitudes, gripper_t (or None), view_camera (or None) and rows are device pointers too --
+        views as calibrate_cameras wrote them, attitudes for instance a Tracker's device_attitudes() -- n_views says their length, and the call
+        returns None."""
+        prm = abi.handeye_params(params, **changes)
+        d = lambda p: C.c_void_p(p.value if isinstance(p, C.c_void_p) else (int(p) if p else 0))
+        call = lambda vw, att, gt, vc, res, out, n: self._chk(lib().rmcv_calibrate_hand_eyes(self._h, vw, att, gt, int(n), vc, int(n_cameras), ptr(prm), res, out,
+                                                                                            C.c_void_p(stream or 0)))
+        if results is not None and not isinstance(results, np.ndarray):
+            call(d(views), d(attitudes), d(gripper_t), d(view_camera), d(results), d(rows), n_views or 0)
+            return None
+        views, attitudes, gripper_t = abi.handeye_tables(views, attitudes, gripper_t)
+        n = len(views)
+        gt = np.zeros(0, np.float64) if gripper_t is None else gripper_t
+        vc = np.zeros(0, np.int32) if view_camera is None else np.ascontiguousarray(view_camera, np.int32).reshape(-1)
+        assert view_camera is None or len(vc) == n, "one camera index per view"
+        res0, rows0 = abi.handeye_outputs(max(int(n_cameras), 0), n)
+        res = res0 if results is None else np.array(results, abi.HANDEYE_RESULT).reshape(-1)
+        out = rows0 if rows is None else np.array(rows, abi.HANDEYE_VIEW).reshape(-1)
+        tabs = [views, attitudes, gt, vc, res, out]
+        dev, offs = self._dev_tables(tabs)
+        try:
+            for o, a in zip(offs, tabs):
+                self._dev_copy(dev, o, a, True)
+            at = lambda k: C.c_void_p((dev.value or 0) + offs[k])
+            none = C.c_void_p(0)
+            call(at(0), at(1), at(2) if gripper_t is not None else none, at(3) if view_camera is not None else none, at(4), at(5), n)
+            self.sync()
+            self._dev_copy(dev, offs[4], res, False)
+            self._dev_copy(dev, offs[5], out, False)
+            return [abi.HandEyeResult(r) for r in res], out
+        finally:
+            lib().rmcv_device_free(self.device, dev)
+
+    def calibrate_hand_eye(self, views, attitudes, gripper_t=None, params=None, **changes):
+        """stage-wise: one camera, host tables through the same kernel (rmcv_calibrate_hand_eye; arguments and result as
+        abi.calibrate_hand_eye_host)"""
+        views, attitudes, gripper_t = abi.handeye_tables(views, attitudes, gripper_t)
+        res, rows = abi.handeye_outputs(1, len(views))
+        self._chk(lib().rmcv_calibrate_hand_eye(self._h, ptr(views), ptr(attitudes), ptr(gripper_t), len(views), ptr(abi.handeye_params(params, **changes)), ptr(res),
+                                                ptr(rows)))
+        return abi.HandEyeResult(res[0]), rows
+
     def calibrate(self, frames, cols, rows, square, size=None, win=(8, 8), chess_params=None, zero_zone=(-1, -1), corner_iters=40, corner_eps=0.001, params=None,
-                  guess=None, **changes):
+                  guess=None, attitudes=None, gripper_t=None, handeye_params=None, **changes):
         """a calibration from the frames bound: find, refine and solve on one device allocation, three asynchronous calls with no host step in
         between (beside capture_corners) -> (CalibResult, views (n,) CALIB_VIEW records, corners (n, cols rows, 2) float32 -- NaN where no board
-        was found --, counts (n,), board status (n,), corner status (n, cols rows)) int32.  size: (w, h) of the frames, the bound batch's by default."""
+        was found --, counts (n,), board status (n,), corner status (n, cols rows)) int32.  size: (w, h) of the frames, the bound batch's by default.
+        With attitudes (one per frame: an ATTITUDE array or (n, 3) (roll, pitch, yaw) radians; gripper_t (n, 3) optional) the hand-eye solve is
+        enqueued as a fourth call behind the third on the same allocation, and (HandEyeResult, rows (n,) HANDEYE_VIEW records) is appended to the
+        tuple returned."""
         fr = np.ascontiguousarray(frames, np.int32).reshape(-1)
         n, per = len(fr), max(int(cols) * int(rows), 1)
         size = size or (self.shape[2], self.shape[1])
         c, cnt, st, cst = np.full((n, per, 2), np.nan, np.float32), np.zeros(n, np.int32), np.zeros(n, np.int32), np.zeros((n, per), np.int32)
         res, vw = abi.calib_outputs(1, n)
         tabs = [c, cnt, st, cst, res, vw]
+        if attitudes is not None:
+            _, att, gt = abi.handeye_tables(vw, attitudes, gripper_t)
+            hres, hrows = abi.handeye_outputs(1, n)
+            tabs += [att, hres, hrows] + ([gt] if gt is not None else [])
         dev, offs = self._dev_tables(tabs)
         try:
             for o, a in zip(offs, tabs):
@@ -856,9 +913,13 @@ class Context:
             self.refine_corners(fr, at(0), at(1), win, zero_zone, corner_iters, corner_eps, status=at(3), per_frame=per)
             self.calibrate_cameras(at(0), at(1), cols, rows, square, size, params=params, guesses=None if guess is None else [guess], results=at(4), views=at(5),
                                    per_frame=per, n_views=n, **changes)
+            if attitudes is not None:
+                self.calibrate_hand_eyes(at(5), at(6), at(9) if gt is not None else None, params=handeye_params, results=at(7), rows=at(8), n_views=n)
             self.sync()
             for o, a in zip(offs, tabs):
                 self._dev_copy(dev, o, a, False)
+            if attitudes is not None:
+                return abi.CalibResult(res[0]), vw, c, cnt, st, cst, abi.HandEyeResult(hres[0]), hrows
             return abi.CalibResult(res[0]), vw, c, cnt, st, cst
         finally:
             lib().rmcv_device_free(self.device, dev)

@@ -260,6 +260,58 @@ struct CalibHostExec {
     template <class F> void each(int n, F f) { for (int i = 0; i < n; i++) f(i); }           // thread i < n runs f(i); then a barrier
 };
 
+// ---- the cyclic Jacobi of 1 on the symmetric N x N matrix at A, V = I on entry (both row pitch N, memory the whole wavefront sees): A's diagonal
+// becomes the eigenvalues, V's columns the eigenvectors.  Every lane walks the sweeps; lane r takes row r of a rotation.  -> the sweeps begun
+template <int N, class X>
+CALIB_FN int calib_jacobi(X& x, double* A, double* V)
+{
+    int sweep = 0;
+    for (; sweep < CALIB_JACOBI_SWEEPS; sweep++) {
+        double off = 0.0;
+        for (int p = 0; p < N; p++)
+            for (int q = p + 1; q < N; q++) off += calib_abs(A[p * N + q]);
+        if (off == 0.0) break;
+        for (int p = 0; p < N; p++)
+            for (int q = p + 1; q < N; q++) {
+                const double apq = A[p * N + q], app = A[p * N + p], aqq = A[q * N + q];   // (every lane reads them before lane 0 writes)
+                if (apq == 0.0) continue;
+                const bool tiny = calib_abs(apq) < 1e-300 || calib_abs(apq) <= 1.1102230246251565e-16 * 1e-3 * sqrt(calib_abs(app * aqq));
+                double cs = 1.0, sn = 0.0, t = 0.0;
+                if (!tiny) {
+                    const double theta = (aqq - app) / (2.0 * apq);
+                    t = 1.0 / (calib_abs(theta) + sqrt(theta * theta + 1.0));
+                    if (theta < 0) t = -t;
+                    cs = 1.0 / sqrt(t * t + 1.0);
+                    sn = t * cs;
+                }
+                x.lanes(N, [&](int r) {
+                    if (tiny) {
+                        if (r == 0) A[p * N + q] = A[q * N + p] = 0.0;
+                        return;
+                    }
+                    if (r != p && r != q) {
+                        const double arp = A[r * N + p], arq = A[r * N + q];
+                        const double nrp = cs * arp - sn * arq, nrq = sn * arp + cs * arq;
+                        A[r * N + p] = nrp;
+                        A[p * N + r] = nrp;
+                        A[r * N + q] = nrq;
+                        A[q * N + r] = nrq;
+                    }
+                    const double vrp = V[r * N + p], vrq = V[r * N + q];
+                    V[r * N + p] = cs * vrp - sn * vrq;
+                    V[r * N + q] = sn * vrp + cs * vrq;
+                    if (r == p) {   // (lane p owns the pair's own three entries: no row update reads them)
+                        A[p * N + p] = app - t * apq;
+                        A[q * N + q] = aqq + t * apq;
+                        A[p * N + q] = 0.0;
+                        A[q * N + p] = 0.0;
+                    }
+                });
+            }
+    }
+    return sweep;
+}
+
 // ---- 1: the homography of view v, by one wavefront; lds: 162 doubles (A, V) ----
 template <class X, class G>
 CALIB_FN void calib_hartley(X& x, int P, G pt, double* m)
@@ -337,49 +389,7 @@ CALIB_FN void calib_view_homography(X& x, const CalibJob& j, int v)
             for (int i = 0; i < 81; i++) V[i] = (i / 9 == i % 9) ? 1.0 : 0.0;
         });
     }
-    for (int sweep = 0; sweep < CALIB_JACOBI_SWEEPS; sweep++) {
-        double off = 0.0;
-        for (int p = 0; p < 9; p++)
-            for (int q = p + 1; q < 9; q++) off += calib_abs(A[p * 9 + q]);
-        if (off == 0.0) break;
-        for (int p = 0; p < 9; p++)
-            for (int q = p + 1; q < 9; q++) {
-                const double apq = A[p * 9 + q], app = A[p * 9 + p], aqq = A[q * 9 + q];   // (every lane reads them before lane 0 writes)
-                if (apq == 0.0) continue;
-                const bool tiny = calib_abs(apq) < 1e-300 || calib_abs(apq) <= 1.1102230246251565e-16 * 1e-3 * sqrt(calib_abs(app * aqq));
-                double cs = 1.0, sn = 0.0, t = 0.0;
-                if (!tiny) {
-                    const double theta = (aqq - app) / (2.0 * apq);
-                    t = 1.0 / (calib_abs(theta) + sqrt(theta * theta + 1.0));
-                    if (theta < 0) t = -t;
-                    cs = 1.0 / sqrt(t * t + 1.0);
-                    sn = t * cs;
-                }
-                x.lanes(9, [&](int r) {
-                    if (tiny) {
-                        if (r == 0) A[p * 9 + q] = A[q * 9 + p] = 0.0;
-                        return;
-                    }
-                    if (r != p && r != q) {
-                        const double arp = A[r * 9 + p], arq = A[r * 9 + q];
-                        const double nrp = cs * arp - sn * arq, nrq = sn * arp + cs * arq;
-                        A[r * 9 + p] = nrp;
-                        A[p * 9 + r] = nrp;
-                        A[r * 9 + q] = nrq;
-                        A[q * 9 + r] = nrq;
-                    }
-                    const double vrp = V[r * 9 + p], vrq = V[r * 9 + q];
-                    V[r * 9 + p] = cs * vrp - sn * vrq;
-                    V[r * 9 + q] = sn * vrp + cs * vrq;
-                    if (r == p) {   // (lane p owns the pair's own three entries: no row update reads them)
-                        A[p * 9 + p] = app - t * apq;
-                        A[q * 9 + q] = aqq + t * apq;
-                        A[p * 9 + q] = 0.0;
-                        A[q * 9 + p] = 0.0;
-                    }
-                });
-            }
-    }
+    calib_jacobi<9>(x, A, V);
     x.lanes(1, [&](int) {
         int m = 0;
         for (int i = 1; i < 9; i++)
@@ -448,6 +458,33 @@ CALIB_FN void calib_init_intrinsics(const CalibJob& j, const int32_t* list, int 
     for (int k = 4; k < 9; k++) a[k] = 0.0;
 }
 
+// ---- the unit quaternion (w, x, y, z) of a rotation matrix, as 3 states it: the first largest of (trace, R00, R11, R22), then divided by its norm ----
+CALIB_FN void calib_mat_to_quat(double R00, double R01, double R02, double R10, double R11, double R12, double R20, double R21, double R22, double* q)
+{
+    const double tr = R00 + R11 + R22;
+    int br = 0;
+    double best = tr;
+    if (R00 > best) { best = R00; br = 1; }
+    if (R11 > best) { best = R11; br = 2; }
+    if (R22 > best) { best = R22; br = 3; }
+    double w, x, y, z;
+    if (br == 0) {
+        const double s = 2.0 * sqrt(1.0 + tr);
+        w = s / 4.0; x = (R21 - R12) / s; y = (R02 - R20) / s; z = (R10 - R01) / s;
+    } else if (br == 1) {
+        const double s = 2.0 * sqrt(1.0 + R00 - R11 - R22);
+        w = (R21 - R12) / s; x = s / 4.0; y = (R01 + R10) / s; z = (R02 + R20) / s;
+    } else if (br == 2) {
+        const double s = 2.0 * sqrt(1.0 + R11 - R00 - R22);
+        w = (R02 - R20) / s; x = (R01 + R10) / s; y = s / 4.0; z = (R12 + R21) / s;
+    } else {
+        const double s = 2.0 * sqrt(1.0 + R22 - R00 - R11);
+        w = (R10 - R01) / s; x = (R02 + R20) / s; y = (R12 + R21) / s; z = s / 4.0;
+    }
+    const double n = sqrt(w * w + x * x + y * y + z * z);
+    q[0] = w / n; q[1] = x / n; q[2] = y / n; q[3] = z / n;
+}
+
 // ---- 3: the initial pose of a view from its homography and the intrinsics (one lane) ----
 CALIB_FN void calib_init_pose(const double* H, const double* a, double* q, double* t)
 {
@@ -471,28 +508,7 @@ CALIB_FN void calib_init_pose(const double* H, const double* a, double* q, doubl
     const double r2[3] = {r0[1] * r1[2] - r0[2] * r1[1], r0[2] * r1[0] - r0[0] * r1[2], r0[0] * r1[1] - r0[1] * r1[0]};
     // R[i][c]: c = 0 -> r0[i], 1 -> r1[i], 2 -> r2[i]
     const double R00 = r0[0], R01 = r1[0], R02 = r2[0], R10 = r0[1], R11 = r1[1], R12 = r2[1], R20 = r0[2], R21 = r1[2], R22 = r2[2];
-    const double tr = R00 + R11 + R22;
-    int br = 0;
-    double best = tr;
-    if (R00 > best) { best = R00; br = 1; }
-    if (R11 > best) { best = R11; br = 2; }
-    if (R22 > best) { best = R22; br = 3; }
-    double w, x, y, z;
-    if (br == 0) {
-        const double s = 2.0 * sqrt(1.0 + tr);
-        w = s / 4.0; x = (R21 - R12) / s; y = (R02 - R20) / s; z = (R10 - R01) / s;
-    } else if (br == 1) {
-        const double s = 2.0 * sqrt(1.0 + R00 - R11 - R22);
-        w = (R21 - R12) / s; x = s / 4.0; y = (R01 + R10) / s; z = (R02 + R20) / s;
-    } else if (br == 2) {
-        const double s = 2.0 * sqrt(1.0 + R11 - R00 - R22);
-        w = (R02 - R20) / s; x = (R01 + R10) / s; y = s / 4.0; z = (R12 + R21) / s;
-    } else {
-        const double s = 2.0 * sqrt(1.0 + R22 - R00 - R11);
-        w = (R10 - R01) / s; x = (R02 + R20) / s; y = (R12 + R21) / s; z = s / 4.0;
-    }
-    const double n = sqrt(w * w + x * x + y * y + z * z);
-    q[0] = w / n; q[1] = x / n; q[2] = y / n; q[3] = z / n;
+    calib_mat_to_quat(R00, R01, R02, R10, R11, R12, R20, R21, R22, q);
 }
 
 // ---- 4: what a wavefront does for view v ----

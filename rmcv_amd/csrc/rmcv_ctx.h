@@ -1,7 +1,7 @@
 // rmcv_ctx.h -- the context behind the ABI's handle and what the units that implement its entry points share: rmcv_host.hip (context,
 // binding, run, batch setters and getters), rmcv_views.hip and rmcv_capture.hip (the views and the calibration capture: chosen frames of the
-// batch bound, and their stage-wise twins), rmcv_stagewise.hip (the other helpers that run on the caller's own data), rmcv_calib.hip (the solve)
-// and rmcv_frame.hip (the per-frame chain); rmcv_svm.hip (the classifier's trainer) and rmcv_harvest.hip (the dataset's entry points) take
+// batch bound, and their stage-wise twins), rmcv_stagewise.hip (the other helpers that run on the caller's own data), rmcv_calib.hip and
+// rmcv_handeye.hip (the two solves) and rmcv_frame.hip (the per-frame chain); rmcv_svm.hip (the classifier's trainer) and rmcv_harvest.hip (the dataset's entry points) take
 // the error and wait helpers.  Private to those: every other unit goes through the ctx_* functions of rmcv_internal.h.
 #pragma once
 #include <stdio.h>

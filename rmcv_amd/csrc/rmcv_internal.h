@@ -412,6 +412,11 @@ struct CalibJob;
 // k_calib_homography, k_calib_solve on `s`; every argument has been checked by the caller (calib_plan.h)
 hipError_t launch_calib(const CalibJob& j, hipStream_t s);
 
+// ---- the hand-eye solve (k_handeye.hip, device_handeye.h) ----
+struct HandEyeJob;
+// k_handeye on `s`, one workgroup per camera; every argument has been checked by the caller (handeye_plan.h)
+hipError_t launch_handeye(const HandEyeJob& j, hipStream_t s);
+
 // ---- what rmcv_pipeline.hip needs of a context beyond the public ABI (rmcv_host.hip) ----
 // external order: the pipeline chains a context's launches with its own events (it knows which stream ran what), so the context
 // does not record / wait for its own ordering event around every launch (two HIP calls per launch); rmcv_batch_sync and the getters
